@@ -98,6 +98,10 @@ def parse():
     ap.add_argument("--dry-launch", action="store_true", help="testing: with --gpus N > 1 start the N ranks as usual, but every rank only reports its rendezvous environment and exits (no GPU, no torch)")
     ap.add_argument("--no-cpu-pool", action="store_true", help="feti at N=1: do not start the worker processes of the configs[3] CPU leg (the reference's op sequence with a direct K^+, timed live)")
     ap.add_argument("--no-dual-spmv", action="store_true", help="feti at N=1: skip the HBM-streaming measurement of MatMult_BlockDiag (8 DISTINCT K_i, one device copy each) at the headline size")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline, as the --no-* options above select it: the CPU baselines, the inner-Krylov and strict-fp64 passes, the K^+ CG product, "
+                    "the FETI dual SpMV, the whole solve and the reuse extension, the secondary blocks and the measured copy ceiling.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64; feti: the multipliers "
+                    "lambda, c2 / svm: the iterate x, all ranks' shares; an output above its share of 64 MB is a fixed, seeded sample, its indices in DIR/<name>_index.npy)")
     return ap.parse_args()
 
 
@@ -129,6 +133,20 @@ def host_threads():
     for k in ("OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
         os.environ[k] = str(cores)
     return cores
+
+
+def dump_outputs(path, arrays, limit=64 << 20):
+    """--dump-outputs: every array as float64 <name>.npy under `path`, at most `limit` bytes in all; an array above its share is replaced by the values at a fixed, seeded
+    sample of its indices (the same in every run with the same arguments), the indices beside it as <name>_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+        if v.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share // 16, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            v = v[idx]
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def cpu_model():
@@ -264,6 +282,7 @@ def run_c2(ctx, a, steps, warmup, cpu=True, whole_solves=False):
         ctx.sync()
         dt = time.perf_counter() - t1
         assert st.iteration == steps, (st.iteration, steps)
+    outputs = {"x": x.to_numpy()} if getattr(a, "dump_outputs", None) and not whole_solves else None
     n_p1, ms_p1 = A.timing_get(3)  # fused MPGP phase-P1 SpMV launches (the dominant kernel)
     has_ub = p["ub"] is not None
     b_spmv = 12.0 * nnz + 20.0 * n
@@ -290,6 +309,8 @@ def run_c2(ctx, a, steps, warmup, cpu=True, whole_solves=False):
         },
     }
     A.timing_enable(0)
+    if outputs is not None:
+        res["_outputs"] = outputs
     if cpu:
         try:
             res["cpu_baseline"] = cpu_baseline_c2(p, a.cpu_its)
@@ -392,12 +413,21 @@ def run_svm(ctx, a, steps, warmup, rank, world, dist):
     barrier()
     dt = time.perf_counter() - t1
     passes = H.passes() - passes0  # how many times X was streamed in the timed region (pmh_op_svm_dual_passes)
+    outputs = None
+    if getattr(a, "dump_outputs", None):
+        xs = x.to_numpy()
+        if dist is not None:  # the ranks hold contiguous slices of the samples in rank order: the whole iterate
+            parts = [None] * world
+            dist.all_gather_object(parts, xs)
+            xs = np.concatenate(parts)
+        outputs = {"x": xs}
     if dist is not None:
         import torch
 
         dt = dist_max(dist, dt)
     comm_rank, comm_size = ctx.comm_rank()
     return {
+        "_outputs": outputs,
         "rccl_ranks": comm_size if (world > 1 or os.environ.get("PMH_BENCH_FORCE_DIST")) else None, "checksum": {"norm_x_after_last_step": repr(global_norm(dist if world > 1 else None, float(x.norm())))},
         "value": steps / dt, "ms_per_step": dt / steps * 1e3,
         "workload": "configs[4]: PermonSVM-style hinge-loss dual, N=%d samples x d=%d dense fp64 (%.2f GB), H = diag(y) X X' diag(y) matrix-free, MPGP box 0<=a<=1" % (N, d, N * d * 8 / 1e9),
@@ -1001,6 +1031,8 @@ def run_feti(ctx, a, steps, warmup, rank, world, dist):
                 "roofline": roof}
 
     extra = {}
+    full = getattr(a, "full", True)  # --full: the measurements besides the headline's timed steps
+    want_outputs = bool(getattr(a, "dump_outputs", None)) and not getattr(a, "_secondary", False)
     if a.kplus == "explicit":
         E = q.E
         if want_timing:
@@ -1010,6 +1042,7 @@ def run_feti(ctx, a, steps, warmup, rank, world, dist):
         n_w, ms_w, _ = E.timing_get() if want_timing else (0, 0.0, 0.0)
         fk_w = getattr(E, "first_kernel_ms", 0.0) if want_timing else 0.0
         dt, cnt = timed_pass(steps, 0)
+        outputs = {"lambda": q.lam.to_numpy()} if want_outputs else None
         n_k, ms_k, b_k = E.timing_get() if want_timing else (0, 0.0, E.gemv_bytes)
         ms_first = (getattr(E, "first_kernel_ms", 0.0) - fk_w) if want_timing else 0.0  # the first kernel of the dense apply alone (orbit storage: the GEMM; sym: k_fx_symv)
         n_k, ms_k = n_k - n_w, ms_k - ms_w  # the timed region only
@@ -1097,6 +1130,7 @@ def run_feti(ctx, a, steps, warmup, rank, world, dist):
             q.Kplus.attach_explicit(E)
     else:
         r = iterative_pass(steps, warmup, a.mg_precision)
+        outputs = {"lambda": q.lam.to_numpy()} if want_outputs else None
         dt, cnt = r["ms_per_step"] * steps / 1e3, r["steps_by_type"]
         roofline = r["roofline"]
         roofline["timed_over"] = "the timed region"
@@ -1111,7 +1145,7 @@ def run_feti(ctx, a, steps, warmup, rank, world, dist):
     # copy serves all of them: `achieved` / `frac` are on the bytes that copy + the vectors take from HBM (<= the peak); the figure of the block-diagonal product (every K_i
     # counted) is `blockdiag_figure_GBs`, an L2-served speed-up, not an HBM rate
     kx = None
-    if world == 1 and not a.sim_world and not a.no_bsr3 and want_timing:
+    if full and world == 1 and not a.sim_world and not a.no_bsr3 and want_timing:
         os.environ["PMH_TIMING_STRIDE"] = "1"
         rhsv, uv = ctx.vec_from(np.random.default_rng(5).standard_normal(local["n_x"])), ctx.vec(local["n_x"])
         q.Kplus.timing_enable(512)
@@ -1150,46 +1184,48 @@ def run_feti(ctx, a, steps, warmup, rank, world, dist):
             dual = dual_spmv_hbm(ctx, f)
         except Exception as ex:  # noqa: BLE001 - never at the cost of the headline
             dual = {"failed": repr(ex)}
-    # one whole solve from lambda = 0 to the outer tolerance (the REAL stopping rule): what a user waits for after the set-up
-    q.lam.set(0.0)
-    qps_full = q.make_smalxe()  # a fresh solver object (QPS_SMALXE.state = 1 as after QPSCreate; the throughput passes above leave it at 3)
-    ctx.sync()
-    t1 = time.perf_counter()
-    st_full = qps_full.Solve()
-    ctx.sync()
-    t_solve = time.perf_counter() - t1
-    # the same solve and the same throughput window with the EXTENSION pmh_smalxe_set_reuse_products (off in everything above: the headline keeps the reference's
-    # operation sequence): A_rho u carried from the inner solve's last gradient, two operator applications less per outer iteration
-    reuse = None
-    if a.kplus == "explicit" and world == 1 and not a.sim_world:
-        lam_ref = q.lam.to_numpy().copy()
+    full_solve = reuse = None
+    if full:
+        # one whole solve from lambda = 0 to the outer tolerance (the REAL stopping rule): what a user waits for after the set-up
         q.lam.set(0.0)
-        qps_r = q.make_smalxe()
-        qps_r.SMALXESetReuseProducts(True)
+        qps_full = q.make_smalxe()  # a fresh solver object (QPS_SMALXE.state = 1 as after QPSCreate; the throughput passes above leave it at 3)
         ctx.sync()
         t1 = time.perf_counter()
-        st_r = qps_r.Solve()
+        st_full = qps_full.Solve()
         ctx.sync()
-        t_r = time.perf_counter() - t1
-        lam_r = q.lam.to_numpy().copy()
-        if warmup:
-            qps_r.RunFixedSolve(warmup)
-        ctx.sync()
-        t1 = time.perf_counter()
-        cnt_r = qps_r.RunFixedSolve(steps)
-        ctx.sync()
-        dt_r = time.perf_counter() - t1
-        reuse = {"what": "EXTENSION, not the reference's operation sequence (off in the headline): pmh_smalxe_set_reuse_products carries A_rho u from the last gradient of an inner solve into the Lagrangian "
-                         "(QPComputeObjective's own product, smalxe.c:982) and into the next inner solve's first gradient (mpgp.c:500): g' = g + rho B'B u",
-                 "value": steps / dt_r, "unit": "QPS iterations/s", "ms_per_step": dt_r / steps * 1e3, "steps": steps, "warmup": warmup, "steps_by_type": cnt_r,
-                 "full_solve": {"solve_seconds": t_r, "outer_iterations": int(st_r.iteration), "inner_iterations": int(st_r.inner_iter_accu), "hessian_mults": int(st_r.inner.nmv), "reason": int(st_r.reason)},
-                 "reference_sequence": {"solve_seconds": t_solve, "outer_iterations": int(st_full.iteration), "inner_iterations": int(st_full.inner_iter_accu), "hessian_mults": int(st_full.inner.nmv)},
-                 "rel_diff_lambda": float(np.linalg.norm(lam_r - lam_ref) / max(np.linalg.norm(lam_ref), 1e-300))}
-        q.lam.set_numpy(lam_ref)  # (the checksum below is of the reference-sequence solve)
-    full_solve = {"solve_seconds": t_solve, "outer_iterations": int(st_full.iteration), "inner_iterations": int(st_full.inner_iter_accu), "reason": int(st_full.reason),
-                  "setup_seconds": round(t_setup, 2), "time_to_solution_seconds": round(t_setup + t_solve, 3),
-                  "note": "set-up = everything between the generated problem and the first solver iteration as bench.py orchestrates it (uploads, 3x3-block copies, multigrid hierarchy, explicit operators by K^+ solves, "
-                          "coarse problem, dual chain, SMALXE set-up with its power method); solve = pmh_smalxe_solve to rtol 1e-5"}
+        t_solve = time.perf_counter() - t1
+        # the same solve and the same throughput window with the EXTENSION pmh_smalxe_set_reuse_products (off in everything above: the headline keeps the reference's
+        # operation sequence): A_rho u carried from the inner solve's last gradient, two operator applications less per outer iteration
+        reuse = None
+        if a.kplus == "explicit" and world == 1 and not a.sim_world:
+            lam_ref = q.lam.to_numpy().copy()
+            q.lam.set(0.0)
+            qps_r = q.make_smalxe()
+            qps_r.SMALXESetReuseProducts(True)
+            ctx.sync()
+            t1 = time.perf_counter()
+            st_r = qps_r.Solve()
+            ctx.sync()
+            t_r = time.perf_counter() - t1
+            lam_r = q.lam.to_numpy().copy()
+            if warmup:
+                qps_r.RunFixedSolve(warmup)
+            ctx.sync()
+            t1 = time.perf_counter()
+            cnt_r = qps_r.RunFixedSolve(steps)
+            ctx.sync()
+            dt_r = time.perf_counter() - t1
+            reuse = {"what": "EXTENSION, not the reference's operation sequence (off in the headline): pmh_smalxe_set_reuse_products carries A_rho u from the last gradient of an inner solve into the Lagrangian "
+                             "(QPComputeObjective's own product, smalxe.c:982) and into the next inner solve's first gradient (mpgp.c:500): g' = g + rho B'B u",
+                     "value": steps / dt_r, "unit": "QPS iterations/s", "ms_per_step": dt_r / steps * 1e3, "steps": steps, "warmup": warmup, "steps_by_type": cnt_r,
+                     "full_solve": {"solve_seconds": t_r, "outer_iterations": int(st_r.iteration), "inner_iterations": int(st_r.inner_iter_accu), "hessian_mults": int(st_r.inner.nmv), "reason": int(st_r.reason)},
+                     "reference_sequence": {"solve_seconds": t_solve, "outer_iterations": int(st_full.iteration), "inner_iterations": int(st_full.inner_iter_accu), "hessian_mults": int(st_full.inner.nmv)},
+                     "rel_diff_lambda": float(np.linalg.norm(lam_r - lam_ref) / max(np.linalg.norm(lam_ref), 1e-300))}
+            q.lam.set_numpy(lam_ref)  # (the checksum below is of the reference-sequence solve)
+        full_solve = {"solve_seconds": t_solve, "outer_iterations": int(st_full.iteration), "inner_iterations": int(st_full.inner_iter_accu), "reason": int(st_full.reason),
+                      "setup_seconds": round(t_setup, 2), "time_to_solution_seconds": round(t_setup + t_solve, 3),
+                      "note": "set-up = everything between the generated problem and the first solver iteration as bench.py orchestrates it (uploads, 3x3-block copies, multigrid hierarchy, explicit operators by K^+ solves, "
+                              "coarse problem, dual chain, SMALXE set-up with its power method); solve = pmh_smalxe_solve to rtol 1e-5"}
     comm_rank, comm_size = ctx.comm_rank()
     res = {
         "value": steps / dt, "ms_per_step": dt / steps * 1e3, "full_solve": full_solve,
@@ -1210,7 +1246,8 @@ def run_feti(ctx, a, steps, warmup, rank, world, dist):
             per, world, " [REHEARSAL --sim-world %d]" % a.sim_world if (a.sim_world and world == 1) else ""),
         "rccl_ranks": comm_size if (world > 1 or os.environ.get("PMH_BENCH_FORCE_DIST")) else None,
         "steps_by_type": cnt, "precision_note": precision_note, "kplus": kplus_cfg,
-        "checksum": {"norm_lambda_child_after_last_step": repr(float(q.lam.norm()))},  # bitwise comparable between runs (deterministic reductions)
+        # bitwise comparable between runs of the same mode (deterministic reductions): a plain run takes it after the last timed step, --full after its whole solve
+        "checksum": {"norm_lambda_child_after_last_step": repr(float(q.lam.norm())), "taken_after": "the whole solve (--full)" if full else "the last timed step"},
         "generate_seconds": round(t_gen, 1), "setup_seconds": round(t_setup, 1),
         "setup_seconds_max_over_ranks": round(dist_max(dist, t_setup), 1) if dist is not None else None, "generate_seconds_max_over_ranks": round(dist_max(dist, t_gen), 1) if dist is not None else None,
         "host_threads_per_rank": host_threads(), "collective": collective or None,
@@ -1219,6 +1256,8 @@ def run_feti(ctx, a, steps, warmup, rank, world, dist):
         "roofline": roofline, "feti_dual_spmv": dual, "kplus_cg_product": kx, "reuse_products": reuse,
     }
     res.update(extra)
+    if want_outputs:
+        res["_outputs"] = outputs
     return res, f, G, hier, q.b.to_numpy(), q.lb_new.to_numpy()  # (the CPU baseline leg re-uses the generated problem)
 
 
@@ -1428,6 +1467,8 @@ def launch_ranks(a):
 
 def main():
     a = parse()
+    if not a.full:  # a plain run: set-up, warm-up, the timed steps and the line; nothing else is measured
+        a.no_cpu_baseline = a.no_c2 = a.no_iterative = a.no_cpu_pool = a.no_dual_spmv = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # before anything initialises the GPU (or imports torch)
         return launch_ranks(a)
     if a.dry_launch:
@@ -1556,8 +1597,9 @@ def main():
         sbt = r["steps_by_type"]
         out["applies_per_step"] = (sbt["operator_applies"] / steps) if sbt.get("operator_applies") else None
         out["ms_per_operator_apply"] = sbt.get("ms_per_operator_apply")
-        out["time_to_solution_s"] = r["full_solve"]["time_to_solution_seconds"]
-        out["full_solve"] = r["full_solve"]
+        if r["full_solve"] is not None:
+            out["time_to_solution_s"] = r["full_solve"]["time_to_solution_seconds"]
+            out["full_solve"] = r["full_solve"]
         out["feti_dual_spmv"] = r["feti_dual_spmv"]
         out["kplus_cg_product"] = r["kplus_cg_product"]
         if r.get("reuse_products"):
@@ -1673,7 +1715,10 @@ def main():
                         out["contact_solve"]["setup_seconds"], out["contact_solve"]["solve_seconds"], out["full_solve"]["time_to_solution_seconds"])
             if not a.no_c2:
                 secondary("configs1", lambda: run_c2(ctx, a, a.c2_steps, 30, cpu=not a.no_cpu_baseline, whole_solves=True))
-    if rank == 0:
+    outputs = r.pop("_outputs", None)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, outputs)
+    if rank == 0 and a.full:
         try:
             out["roofline"]["measured_ceiling"] = measured_ceiling(ctx)
             if out["roofline"].get("bound") == "mfma":  # compute-bound headline kernel: the comparable measured ceiling is the instruction's issue rate, not the copy rate
@@ -1683,6 +1728,7 @@ def main():
                 out["roofline"]["frac_of_measured_copy"] = out["roofline"]["achieved"] / out["roofline"]["measured_ceiling"]["copy_GBs"]
         except Exception as ex:  # noqa: BLE001
             out["roofline"]["measured_ceiling"] = "failed: %r" % (ex,)
+    if rank == 0:
         if HOST_TRANSPORT and dist is not None:
             out["config"]["transport"] = "host (gloo) -- TEST MODE: the %d ranks share one GPU (PMH_BENCH_TRANSPORT=host); not a multi-GPU measurement" % world
         try:

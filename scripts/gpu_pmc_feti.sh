@@ -1,16 +1,18 @@
 # HBM traffic of the FETI dual SpMV (K_i blocks) from PMC counters, separate passes
 set -x
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/out}  # where the runs below write
+mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $R/gpurun_out/pmcf_$C -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-c2 > $R/gpurun_out/pmcf_$C.log 2>&1
-  tail -1 $R/gpurun_out/pmcf_$C.log | cut -c1-200
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmcf_$C -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-c2 > $OUT/pmcf_$C.log 2>&1
+  tail -1 $OUT/pmcf_$C.log | cut -c1-200
 done
-mkdir -p $R/gpurun_out/pmcf && rm -rf $R/gpurun_out/pmcf/pmc_FETCH_SIZE $R/gpurun_out/pmcf/pmc_WRITE_SIZE
-mv $R/gpurun_out/pmcf_FETCH_SIZE $R/gpurun_out/pmcf/pmc_FETCH_SIZE; mv $R/gpurun_out/pmcf_WRITE_SIZE $R/gpurun_out/pmcf/pmc_WRITE_SIZE
-python3 $R/scripts/pmc_parse.py $R/gpurun_out/pmcf && cp $R/gpurun_out/pmcf/pmc_traffic.json $R/gpurun_out/pmc_traffic_feti.json
+mkdir -p $OUT/pmcf && rm -rf $OUT/pmcf/pmc_FETCH_SIZE $OUT/pmcf/pmc_WRITE_SIZE
+mv $OUT/pmcf_FETCH_SIZE $OUT/pmcf/pmc_FETCH_SIZE; mv $OUT/pmcf_WRITE_SIZE $OUT/pmcf/pmc_WRITE_SIZE
+python3 $R/scripts/pmc_parse.py $OUT/pmcf && cp $OUT/pmcf/pmc_traffic.json $OUT/pmc_traffic_feti.json
 # keep only the summary (the per-dispatch CSVs are tens of MB)
-rm -rf $R/gpurun_out/pmcf/pmc_FETCH_SIZE $R/gpurun_out/pmcf/pmc_WRITE_SIZE
+rm -rf $OUT/pmcf/pmc_FETCH_SIZE $OUT/pmcf/pmc_WRITE_SIZE
 # torch-first import check: libpermonhip must work on torch's bundled HIP runtime + RCCL (the N>1 launch path)
 cd $R
 PMH_COMM_FORCE=1 python3 - <<'PY'

@@ -1,14 +1,17 @@
 # debugging aid: bench.py on one rank and on N ranks sharing the GPU (PMH_BENCH_TRANSPORT=host), same arguments; prints checksums and step mixes.  usage: two_rank_dbg.sh [N]
-cd $GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/out}  # where the runs below write
+mkdir -p "$OUT"
+cd $R
 N=${1:-2}
 run() {
   tag=$1; shift
-  python bench.py "$@" --details gpurun_out/one_$tag.json > /dev/null 2> gpurun_out/one_$tag.err
-  PMH_BENCH_TRANSPORT=host python bench.py --gpus $N "$@" --details gpurun_out/two_$tag.json > /dev/null 2> gpurun_out/two_$tag.err || tail -5 gpurun_out/two_$tag.err
+  python bench.py --full "$@" --details $OUT/one_$tag.json > /dev/null 2> $OUT/one_$tag.err
+  PMH_BENCH_TRANSPORT=host python bench.py --full --gpus $N "$@" --details $OUT/two_$tag.json > /dev/null 2> $OUT/two_$tag.err || tail -5 $OUT/two_$tag.err
   python3 - $tag <<'P'
 import json,sys
 t=sys.argv[1]
-a=json.load(open("gpurun_out/one_%s.json"%t)); b=json.load(open("gpurun_out/two_%s.json"%t))
+a=json.load(open("$OUT/one_%s.json"%t)); b=json.load(open("$OUT/two_%s.json"%t))
 print(t, b["n_gpus"], a["config"]["checksum"], b["config"]["checksum"])
 print("  ", a["config"]["steps_by_type"]); print("  ", b["config"]["steps_by_type"])
 P

@@ -3,7 +3,7 @@ Round 5: `gcc -fsyntax-only` of that TU against PERMON's OWN headers (/root/refe
 qppfimpl.h ...) with a PETSc stand-in that declares types, macros and prototypes only (tests/stubs/petsc/petsc_stub.h, written from PETSc's manual pages; nothing is built,
 linked or shipped; no reference source is compiled).  It catches typos, undeclared identifiers, wrong arity and argument types against PERMON's prototypes -- the first run
 found one: MatMult_Timer is defined in libpermon (src/mat/impls/timer/mattimer.c:5) but declared in none of its headers.  It cannot check PETSc's real struct layouts, macro
-expansions, linking or running.  Skipped where /root/reference does not exist (the GPU box)."""
+expansions, linking or running.  The header checks skip where the reference's headers are not present (the GPU box)."""
 import os
 import subprocess
 import tempfile
@@ -16,15 +16,17 @@ GLUE = os.path.join(ROOT, "permon_amd", "csrc", "petsc_glue", "permonhip_petsc.c
 FLAGS = ["gcc", "-fsyntax-only", "-fmax-errors=0", "-std=gnu11", "-Wall", "-Werror=implicit-function-declaration", "-Werror=incompatible-pointer-types", "-Werror=int-conversion",
          "-Werror=return-type", "-Werror=implicit-int", "-Wno-unused", "-Wno-comment", "-I", os.path.join(ROOT, "tests", "stubs", "petsc"), "-I", REF, "-I", os.path.join(ROOT, "include")]
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's headers are not on this machine")
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's headers are not on this machine")
 
 
+@needs_ref
 def test_glue_passes_syntax_and_arity_check_against_permon_headers():
     out = subprocess.run(FLAGS + [GLUE], capture_output=True, text=True, timeout=300)
     errors = [ln for ln in out.stderr.splitlines() if " error: " in ln]
     assert out.returncode == 0 and not errors, "\n".join(errors[:40])
 
 
+@needs_ref
 @pytest.mark.parametrize("snippet,needle", [
     ("PetscErrorCode f(QP qp) { Vec lb; PetscCall(QPGetBox(qp, &lb)); return 0; }", "too few arguments"),                     # QPGetBox(QP, IS *, Vec *, Vec *): arity against PERMON's prototype
     ("PetscErrorCode f(QPS qps) { qps->ops->solve = (PetscErrorCode(*)(QP))0; return 0; }", "incompatible pointer"),           # _QPSOps.solve takes a QPS (qpsimpl.h:12-24)

@@ -1,5 +1,5 @@
 """bench.py keeps the driver's contract: one JSON line with the agreed keys (small problem sizes here; the real sizes are the
-defaults).  Also the CPU-baseline leg and the secondary configs[1] block on a reduced grid."""
+defaults).  Also the CPU-baseline leg and the secondary configs[1] block on a reduced grid (--full), and the plain run with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -14,14 +14,14 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 ROOF = {"bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source"}
 
 
-def _run(*args, env=None):
-    """Runs bench.py; returns (the compact line the driver parses, the full object of the details file)."""
+def _run(*args, env=None, full=True):
+    """Runs bench.py (with --full unless full=False); returns (the compact line the driver parses, the full object of the details file)."""
     import tempfile
     import time
 
     det = os.path.join(tempfile.mkdtemp(prefix="pmh_bench_test_"), "details.json")
     t0 = time.time()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--details", det] + list(args), capture_output=True, text=True, timeout=900, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--details", det] + (["--full"] if full else []) + list(args), capture_output=True, text=True, timeout=900, env=env)
     wall = time.time() - t0
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -174,8 +174,21 @@ def test_two_ranks_on_one_gpu_host_transport():
                       (("--partition", "staircase", "--nel", "6", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-c2", "--kplus", "iterative", "--no-iterative"), "norm_lambda_child_after_last_step"),
                       # ... and the explicit headline WITH its inner-Krylov pass: every N > 1 line carries `iterative` next to the headline
                       (("--nel", "7", "--steps", "12", "--warmup", "2", "--no-cpu-baseline", "--no-c2"), "norm_lambda_child_after_last_step")):
-        one = _run(*args)[1]
-        two = _run("--gpus", "2", *args, env=env)[1]
+        dump = None
+        if "--workload" in args:  # the SVM iterate is sharded over the ranks: the dump gathers every rank's share
+            import tempfile
+
+            dump = (tempfile.mkdtemp(prefix="pmh_bench_dump1_"), tempfile.mkdtemp(prefix="pmh_bench_dump2_"))
+            one = _run(*args, "--dump-outputs", dump[0])[1]
+            two = _run("--gpus", "2", *args, "--dump-outputs", dump[1], env=env)[1]
+        else:
+            one = _run(*args)[1]
+            two = _run("--gpus", "2", *args, env=env)[1]
+        if dump is not None:
+            import numpy as np
+
+            x1, x2 = np.load(os.path.join(dump[0], "x.npy")), np.load(os.path.join(dump[1], "x.npy"))
+            assert x1.shape == x2.shape == (200000,) and np.linalg.norm(x1 - x2) <= 1e-9 * np.linalg.norm(x1)
         if "--no-iterative" not in args and "--workload" not in args:
             assert two["iterative"]["value"] > 0 and "k_bsr3<double>" in two["iterative"]["roofline"]["kernel"], two.get("iterative")  # (4 blocks per rank: the one-column kernel)
         assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["config"]["rccl_ranks"] == 2 and "host" in two["config"]["transport"]
@@ -201,3 +214,29 @@ def test_four_ranks_on_one_gpu_host_transport():
         assert abs(a - b) <= 1e-12 * abs(a), (args, a, b)
         for k in ("cg", "expansion", "proportioning", "hessian_mults", "outer"):
             assert one["config"]["steps_by_type"][k] == four["config"]["steps_by_type"][k]
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs():
+    """Without --full the run sets up, warms up, times exactly --steps steps and prints the line: none of the secondary measurements.  --dump-outputs writes the
+    multipliers the timed path left after its last step, float64, and two runs with the same arguments write the same values (deterministic reductions)."""
+    import tempfile
+
+    import numpy as np
+
+    dumps = []
+    for _ in range(2):
+        dd = tempfile.mkdtemp(prefix="pmh_bench_dump_")
+        c, d = _run("--nel", "7", "--steps", "30", "--warmup", "3", "--dump-outputs", dd, full=False)
+        assert d["steps"] == 30 and d["warmup"] == 3 and d["config"]["kplus"]["path"] == "explicit" and d["roofline"]["launches_timed"] > 0
+        st = d["config"]["steps_by_type"]
+        assert st["cg"] + st["expansion"] + st["proportioning"] == 30
+        for k in ("cpu_baseline", "cpu_baseline_iterative", "iterative", "strict_fp64", "full_solve", "general", "general_nosym", "configs1", "configs3", "configs4", "contact_solve"):
+            assert k not in d and k not in c, k
+        assert d["feti_dual_spmv"] is None and d["kplus_cg_product"] is None and "measured_ceiling" not in d["roofline"]
+        assert sorted(os.listdir(dd)) == ["lambda.npy"]
+        lam = np.load(os.path.join(dd, "lambda.npy"))
+        assert lam.dtype == np.float64 and lam.shape == (int(d["config"]["workload"].split("n_lambda=")[1].split()[0]),) and np.all(np.isfinite(lam))
+        norm = float(d["config"]["checksum"]["norm_lambda_child_after_last_step"])  # (plain run: taken after the last timed step, nothing else moves lambda)
+        assert norm > 0 and abs(np.linalg.norm(lam) - norm) <= 1e-12 * norm
+        dumps.append(lam)
+    assert np.array_equal(dumps[0], dumps[1])
