@@ -404,6 +404,20 @@ int pmh_fexplicit_compressed_size(pmh_fexplicit E, int *ntot, int *gstart /* [nb
 int pmh_fexplicit_dense_mult(pmh_fexplicit E, const double *xhat, double *yhat);        /* the dense kernel alone, compressed vectors */
 int pmh_fexplicit_timing_enable(pmh_fexplicit E, int max_launches, int stride);         /* HIP-event pairs around the GEMV launches */
 int pmh_fexplicit_timing_get(pmh_fexplicit E, int *launches, double *total_ms, double *first_kernel_ms /* SYM: k_fx_symv alone; CLASS_ORBIT: the GEMM kernel alone (total - first = the finishing kernel); or NULL */);
+/* PCDUAL dirichlet: y = B S B' x, S = blockdiag(S_b), S_b = K_GG - K_GI K_II^{-1} K_IG the Schur complement of block b on Gamma_b (the dofs of the block
+ * that B touches, as pmh_fexplicit_create takes them) against the rest of the block.  The reference's PCApply_Dual (src/pc/impls/dual/pcdual.c:63-78) is
+ * y = At' C_bb At x; PCSetUp_Dual (:105-116) fills C_bb = K for `lumped` only -- this is the same apply with C_bb = S, the preconditioner whose condition
+ * number stays polylogarithmic in H/h.  Set-up: one Jacobi-PCG solve with K_II per column of every S_b that has an interior (all blocks' columns of one batch in one
+ * application of a block CG over blockdiag(K_II,b), tolerance rtol, at most max_it iterations; PMH_ERR_STATE if one does not converge), S_b = K_b[Gamma_b, Gamma_b] for a
+ * block without an interior; S_b is stored exactly symmetric ((S_b + S_b') / 2) in a pmh_fexplicit of `storage` PMH_FX_FULL (8 n_Gamma_b^2 bytes) or PMH_FX_SYM (4 n_Gamma_b^2)
+ * and every apply is pmh_fexplicit_mult.  Class-shared storage and several GPUs: PMH_ERR_SUP.  K_b symmetric; destroy with pmh_op_destroy.
+ * _stats: set-up solves (sum of n_Gamma_b over the blocks with an interior), set-up wall seconds, bytes of the dense storage.  _get_block (tests): S_b as stored,
+ * n_Gamma_b^2 row-major, and Gamma_b (rank-local primal dofs), either may be NULL.  _get_explicit: the pmh_fexplicit inside, borrowed (pmh_fexplicit_sizes /
+ * pmh_fexplicit_timing_*). */
+int pmh_op_create_pc_dual_dirichlet(pmh_gluing B, pmh_blockdiag K, int storage, double rtol, int max_it, pmh_op *op);
+int pmh_pc_dual_dirichlet_stats(pmh_op op, long long *n_solves, double *setup_seconds, double *dense_bytes);
+int pmh_pc_dual_dirichlet_get_block(pmh_op op, int b, double *S_host, int *gamma_host);
+int pmh_pc_dual_dirichlet_get_explicit(pmh_op op, pmh_fexplicit *E);
 /* F = B K^+ B' built on this MATINV (pmh_op_create_feti_dual, the FETI chain) applies through E from now on (E built from the
    same B; NULL detaches).  K^+ f for a general f (d = B K^+ f - c, primal recovery) stays on the inner KSP. */
 int pmh_matinv_attach_explicit(pmh_matinv Kplus, pmh_fexplicit E);
@@ -579,7 +593,7 @@ int pmh_ksp_cg_solve(pmh_ctx ctx, pmh_op A, const double *b, double *x, pmh_op p
  * enforced by B (local indices, KSPFETISetDirichlet(..., FETI_LOCAL, PETSC_TRUE); none if they are eliminated in K), and the
  * kernel vectors R (kdim rows of length N, zero over non-floating blocks; orthonormalised internally).
  * Builds B = [B_d; B_g] (QPFetiAssembleDirichlet, QPFetiGetBgtSF), K^+ (MatRegularize + MATINV, or the Moore-Penrose wrapping),
- * G = R'B', the dual QP chain, solves it with the QPS the reference's QPSSetDefaultType picks (CG on P F, optional lumped PC) and
+ * G = R'B', the dual QP chain, solves it with the QPS the reference's QPSSetDefaultType picks (CG on P F, optional lumped / Dirichlet PC) and
  * recovers u.  One call per solve; everything it creates is released before it returns. */
 typedef struct {
   int    gluing_type;        /* -feti_gluing_type: 0 nonred, 1 full (default, qpfeti.c:322), 2 orth */
@@ -592,7 +606,7 @@ typedef struct {
   int    project;            /* -project (default 1, set by -feti: QPTEnforceEqByProjector).  0: the equality constraint G lambda = e stays in the dual QP, which is homogenised and
                                 handed to QPS SMALXE (QPSSetDefaultType qps.c:437-441; QPTEnforceEqByPenalty inside SMALXE) -- `smalxe` below configures it */
   int    E_orth_type;        /* -dual_qp_E_orth_type (QPTOrthonormalizeEqFromOptions qptransform.c:643-660; MatOrthTypes): 0 none, 1 gs / 2 gslingen (explicit T G, T e), 3 cholesky / 4 implicit (G stays sparse, the projector carries T = L^{-1}) */
-  int    lumped_pc;          /* -dual_pc_dual_type lumped (default none) */
+  int    lumped_pc;          /* -dual_pc_dual_type (PCDualTypes, default none): 0 none, 1 lumped (B K B'), 2 dirichlet (B S B', pmh_op_create_pc_dual_dirichlet) */
   double regularize_rho;     /* > 0: the rho of MatRegularize for every block; 0 (default): the reference's power-method estimate */
   double kplus_rtol; int kplus_max_it; /* inner KSP of MATINV */
   double rtol, atol, divtol; int max_it; /* -qps_rtol ... of the dual solve (qps.c:73-76) */

@@ -223,6 +223,10 @@ _PROTOS = {
     "pmh_feti_gluing_from_l2g": [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, c_int_p, c_int_p, vp, vp, vp],
     "pmh_op_create_feti_dual": [vp, vp, C.POINTER(vp)],
     "pmh_pc_dual_lumped_apply": [vp, vp, vp, vp],
+    "pmh_op_create_pc_dual_dirichlet": [vp, vp, C.c_int, C.c_double, C.c_int, C.POINTER(vp)],
+    "pmh_pc_dual_dirichlet_stats": [vp, C.POINTER(C.c_longlong), c_double_p, c_double_p],
+    "pmh_pc_dual_dirichlet_get_block": [vp, C.c_int, vp, vp],
+    "pmh_pc_dual_dirichlet_get_explicit": [vp, C.POINTER(vp)],
     "pmh_qpt_feti_chain_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
     "pmh_qpt_feti_chain_get": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
     "pmh_qpt_feti_chain_post_solve": [vp, vp, vp, vp, vp],

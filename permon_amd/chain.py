@@ -8,7 +8,7 @@ import numpy as np
 
 from ._lib import check
 from .core import Op, Vec
-from .mat import QPPF, MatBlockDiag, MatCreateFetiDual, MatCreateProjected, MatExplicitDual, MatGluing, MatInv, MatRegularize, PCDualLumpedOp, csr_block_classes
+from .mat import QPPF, MatBlockDiag, MatCreateFetiDual, MatCreateProjected, MatExplicitDual, MatGluing, MatInv, MatRegularize, PCDualDirichletOp, PCDualLumpedOp, csr_block_classes
 from .qps import QP, QPS
 
 
@@ -265,14 +265,27 @@ class FetiDualQP:
         """QPSSetDefaultType: BE present -> SMALXE with inner MPGP (qps.c:443-444)."""
         return self.make_smalxe(rtol=rtol, max_it=max_it, inner=inner, **smalxe).Solve()
 
-    def solve_pcpg(self, rtol=1e-5, max_it=1000, lumped=False):
-        """Equality-only dual QP (no box): projected preconditioned CG (QPSPCPG)."""
+    def _pc_dual(self, lumped, pc_type):
+        """PCDUAL of the dual QP: pc_type "none" | "lumped" (B K B') | "dirichlet" (B S B', built once and kept); None: `lumped` decides."""
+        kind = pc_type if pc_type is not None else ("lumped" if lumped else "none")
+        if kind == "none":
+            return None
+        if kind == "lumped":
+            return PCDualLumpedOp(self.B, self.K)
+        if kind == "dirichlet":
+            if getattr(self, "_dirichlet", None) is None:
+                self._dirichlet = PCDualDirichletOp(self.B, self.K)
+            return self._dirichlet
+        raise ValueError("pc_type %r: none, lumped or dirichlet" % (pc_type,))
+
+    def solve_pcpg(self, rtol=1e-5, max_it=1000, lumped=False, pc_type=None):
+        """Equality-only dual QP (no box): projected preconditioned CG (QPSPCPG).  pc_type "none" | "lumped" | "dirichlet" (None: lumped=True is "lumped")."""
         qp = QP(self.ctx)
         qp.SetOperator(self.F)
         qp.SetRhs(self.b_bar)
         qp.SetInitialVector(self.lam)
         qp.SetEq(self.pf)
-        qp.pc = PCDualLumpedOp(self.B, self.K) if lumped else None
+        qp.pc = self._pc_dual(lumped, pc_type)
         qps = QPS(self.ctx)
         qps.SetQP(qp)
         qps.SetType("pcpg")
@@ -281,17 +294,19 @@ class FetiDualQP:
         self.qps = qps
         return st
 
-    def solve_ksp(self, rtol=1e-5, max_it=10000, lumped=False):
+    def solve_ksp(self, rtol=1e-5, max_it=10000, lumped=False, pc_type=None):
         """The reference's default for a dual QP without box: after QPTEnforceEqByProjector the child QP has operator
         P F, rhs P b_bar, preconditioner P M^{-1} (qptransform.c:272-308) and no constraint left, so QPSSetDefaultType
-        picks QPSKSP = CG (qps.c:448); without floating subdomains it is CG on F lambda = d."""
+        picks QPSKSP = CG (qps.c:448); without floating subdomains it is CG on F lambda = d.
+        pc_type: "none" | "lumped" (M = B K B') | "dirichlet" (M = B S B'); None: lumped=True is "lumped"."""
         qp = QP(self.ctx)
         qp.SetOperator(self.A)
         qp.SetRhs(self.b)
         qp.SetInitialVector(self.lam)
-        if lumped:
-            self._lumped = PCDualLumpedOp(self.B, self.K)
-            qp.pc = MatCreateProjected(self._lumped, self.pf, symmetric=False) if self.pf is not None else self._lumped
+        M = self._pc_dual(lumped, pc_type)
+        if M is not None:
+            self._lumped = M
+            qp.pc = MatCreateProjected(M, self.pf, symmetric=False) if self.pf is not None else M
         qps = QPS(self.ctx)
         qps.SetQP(qp)
         qps.SetType("ksp")
@@ -322,12 +337,14 @@ class FetiDualQP:
 
 
 def KSPFETISolve(ctx, block_rowstart, K, f, l2g, dirichlet_local=None, R=None, gluing="full", scale=True, exclude_dirichlet=False, regularize=None, lumped=False,
-                 rtol=1e-5, atol=1e-50, divtol=1e4, max_it=10000, kplus_rtol=1e-12, kplus_max_it=20000, options=None, regularize_rho=0.0, explicit=False, kplus_pc="jacobi"):
+                 rtol=1e-5, atol=1e-50, divtol=1e4, max_it=10000, kplus_rtol=1e-12, kplus_max_it=20000, options=None, regularize_rho=0.0, explicit=False, kplus_pc="jacobi",
+                 pc_dual_type=None):
     """KSPFETI (src/ksp/impls/feti/feti.c:71-156) for a decomposed linear problem, one call into pmh_kspfeti_solve (C++):
     K block-diagonal scipy CSR, f split among copies, l2g global dof of every local dof, dirichlet_local = local dofs enforced
     by B (TFETI) or None, R = (kdim, N) kernel vectors (zero over non-floating blocks) or None.
     regularize: None = the library's default K^+, which is KSPFETI's (the left generalised inverse K^- P_R; K_reg^{-1} with explicit=True); True = K_reg^{-1} (MatRegularize);
     False = the Moore-Penrose form P_R K^- P_R.
+    pc_dual_type: -dual_pc_dual_type "none" | "lumped" | "dirichlet" (the Dirichlet preconditioner assembled at kplus_rtol / kplus_max_it); None: `lumped` decides.
     Returns (u, lambda, stats) with stats = (iteration, reason, rnorm, n_lambda, n_dirichlet_rows, coarse_dim)."""
     from . import _lib
 
@@ -347,6 +364,8 @@ def KSPFETISolve(ctx, block_rowstart, K, f, l2g, dirichlet_local=None, R=None, g
     if regularize is not None:
         o.kplus_left, o.regularize = 0, int(bool(regularize))
     o.lumped_pc, o.regularize_rho = int(bool(lumped)), float(regularize_rho)
+    if pc_dual_type is not None:
+        o.lumped_pc = {"none": 0, "lumped": 1, "dirichlet": 2}[pc_dual_type]
     o.kplus_rtol, o.kplus_max_it, o.rtol, o.atol, o.divtol, o.max_it = kplus_rtol, kplus_max_it, rtol, atol, divtol, max_it
     o.explicit_dual = int(bool(explicit))  # F through the explicit local dual operators (pmh_fexplicit_*)
     o.kplus_pc = {"jacobi": 0, "gamg": 1, "mg": 1}[kplus_pc]  # -dual_mat_inv_pc_type: the algebraic V-cycle (pmh_mg_create_sa) as the PC of MATINV's inner KSP

@@ -65,6 +65,10 @@ bool pmh_fexplicit_matches(pmh_fexplicit_s *E, pmh_gluing B);
 int  pmh_fexplicit_apply(pmh_fexplicit_s *E, const double *lambda, double *y);
 int  pmh_fexplicit_stages(pmh_fexplicit_s *E, pmh_csr *gather, double **mid_in, pmh_csr *scatter, const double **mid_out); // the sparse stages around the dense one (FetiDualOp::stages)
 int  pmh_fexplicit_mid(pmh_fexplicit_s *E);                                                                                // the dense stage alone: mid_in -> mid_out
+// blocks computed elsewhere (pcdual.hip): W_b = (S + S') / 2 from the dense row-major device matrix S (n_Gamma_b x n_Gamma_b, leading dimension lds) into the
+// FULL / SYM storage (PMH_ERR_SUP otherwise); _mark_assembled once every block is written (n_solves, seconds: what the set-up took)
+int  pmh_fexplicit_store_symmetrized(pmh_fexplicit_s *E, int b, const double *S, int lds);
+int  pmh_fexplicit_mark_assembled(pmh_fexplicit_s *E, long long n_solves, double seconds);
 
 // ---- what the set-up loops of the explicit operators (fexplicit.hip, fshared.hip) need from a K^+ solver: one COLUMN per slot ----------------------------------
 // nslots == solver->nblocks: slot s = block s of the one-column solver (pmh_matinv_mult).  nslots == PMH_MV_R * solver->nblocks: the multi-right-hand-side solver

@@ -958,6 +958,44 @@ extern "C" int pmh_fexplicit_get_block(pmh_fexplicit E, int b, double *out_host,
   return PMH_SUCCESS;
 }
 
+// ---- blocks computed elsewhere (pcdual.hip: the Schur complements of the Dirichlet preconditioner) -----------------------------
+// W_b = (S + S') / 2 from a dense row-major n x n matrix S (leading dimension lds) into the block's storage: FULL row p at W + p ld, SYM the part of row p inside its
+// band (columns 0 .. min(n, 32(k+1)) - 1, the layout of k_fx_extract_tiled).  a + b == b + a in IEEE arithmetic, so the stored matrix is exactly symmetric.
+__global__ __launch_bounds__(PMH_BLOCK) void k_fx_store_sym(int n, int lds, int ld, int sym, const double *__restrict__ S, double *__restrict__ W)
+{
+  const long long tot = (long long)n * n;
+  for (long long t = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; t < tot; t += (long long)gridDim.x * PMH_BLOCK) {
+    const int    p = (int)(t / n), q = (int)(t % n);
+    const double v = 0.5 * (S[(long long)p * lds + q] + S[(long long)q * lds + p]);
+    if (!sym) W[(long long)p * ld + q] = v;
+    else {
+      const int kb = p / FX_RB;
+      if (q < FX_RB * (kb + 1)) W[fx_band_off(kb) + (long long)(q / FX_TC) * FX_TILE + (long long)(p - FX_RB * kb) * FX_TC + q % FX_TC] = v;
+    }
+  }
+}
+
+int pmh_fexplicit_store_symmetrized(pmh_fexplicit_s *E, int b, const double *S, int lds)
+{
+  PMH_ARG(E && b >= 0 && b < E->nb && S && lds >= E->ngam[b]);
+  if (E->sh || (E->storage != PMH_FX_FULL && E->storage != PMH_FX_SYM)) return pmh_set_error(PMH_ERR_SUP, "pmh_fexplicit_store_symmetrized: FULL / SYM storage only");
+  if (E->stripe_size > 1) return pmh_set_error(PMH_ERR_SUP, "pmh_fexplicit_store_symmetrized: not on a striped operator");
+  const int n = E->ngam[b];
+  if (!n) return PMH_SUCCESS;
+  const long long tot = (long long)n * n;
+  const dim3      grid((unsigned)std::max(1LL, std::min(2048LL, (tot + PMH_BLOCK - 1) / PMH_BLOCK)));
+  hipLaunchKernelGGL(k_fx_store_sym, grid, dim3(PMH_BLOCK), 0, E->ctx->stream, n, lds, E->ld[b], E->storage == PMH_FX_SYM ? 1 : 0, S, E->W[b]);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+int pmh_fexplicit_mark_assembled(pmh_fexplicit_s *E, long long n_solves, double seconds)
+{
+  PMH_ARG(E);
+  E->assembled = 1, E->n_solves += n_solves, E->assemble_seconds += seconds;
+  return PMH_SUCCESS;
+}
+
 // ---- apply ----------------------------------------------------------------------------------------------------------------
 
 static int fx_gemv(pmh_fexplicit E)

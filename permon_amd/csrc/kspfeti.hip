@@ -8,7 +8,8 @@
 //   K^+: MATINV on K_reg = MatRegularize(K, R) (-regularize 1, the default) or P_R K^- P_R (-regularize 0 -qpt_dualize_Kplus_mp);
 //   G  = R'B' (explicit, qptransform.c:838), e = R'f;  chain: pmh_qpt_feti_chain_create (dualize, homogenize, project);
 //        or, with -qpt_dualize_Kplus_left (what the reference switches to when it computed the kernel itself, qptransform.c:997-1008), K^- P_R;
-//   QPS: the dual QP has no box, so QPSSetDefaultType picks QPSKSP = CG on P F (qps.c:448) with PC none or P (B K B') (PCDUAL lumped);
+//   QPS: the dual QP has no box, so QPSSetDefaultType picks QPSKSP = CG on P F (qps.c:448) with PC none, P (B K B') (PCDUAL lumped) or P (B S B')
+//        (dirichlet, pcdual.hip);
 //        with -project 0 the equality constraint stays, the QP is homogenised and QPSSetDefaultType picks SMALXE (qps.c:437-441), optionally on orthonormalised
 //          G
 //        (-dual_qp_E_orth_type gs | implicit);
@@ -375,6 +376,7 @@ extern "C" int pmh_kspfeti_solve(pmh_ctx ctx, int nsub, const int *block_rowstar
   pmh_feti_chain ch = nullptr;
   pmh_fexplicit  E  = nullptr;
   LumpedOp      *lump = nullptr;
+  pmh_op         dir  = nullptr; // -dual_pc_dual_type dirichlet
   pmh_op         pc = nullptr;
   double        *d_f = nullptr, *d_c = nullptr, *d_e = nullptr, *d_x = nullptr, *d_lam = nullptr, *d_u0 = nullptr, *d_r = nullptr, *d_alpha = nullptr;
   int            rc = PMH_SUCCESS;
@@ -576,10 +578,19 @@ extern "C" int pmh_kspfeti_solve(pmh_ctx ctx, int nsub, const int *block_rowstar
     pmh_op  A;
     double *b;
     GO(pmh_qpt_feti_chain_get(ch, nullptr, &A, nullptr, nullptr, &b, nullptr, nullptr));
-    if (o->lumped_pc) { // PCDUAL lumped, projected as qptransform.c:301-309 does for an equality-only QP
+    switch (o->lumped_pc) { // PCDUAL, projected as qptransform.c:301-309 does for an equality-only QP
+    case 0: break;
+    case 1: // lumped: B K B'
       lump      = new LumpedOp();
       lump->ctx = ctx, lump->n = nl, lump->B = B, lump->K = Kb;
       if (pfs) GO(pmh_op_create_projected(lump, pfs, 0, &pc));
+      break;
+    case 2: // dirichlet: B S B', the Schur complements on Gamma_b assembled with the inner KSP's tolerances (pcdual.hip); skipped where -project 0 refuses it below
+      if (m && !o->project) break;
+      GO(pmh_op_create_pc_dual_dirichlet(B, Kb, PMH_FX_SYM, o->kplus_rtol, o->kplus_max_it, &dir));
+      if (pfs) GO(pmh_op_create_projected(dir, pfs, 0, &pc));
+      break;
+    default: rc = pmh_set_error(PMH_ERR_ARG, "pmh_kspfeti_solve: lumped_pc = %d (0 none, 1 lumped, 2 dirichlet)", o->lumped_pc); goto done;
     }
     pmh_pcpg_stats ks;
     memset(&ks, 0, sizeof(ks));
@@ -589,7 +600,7 @@ extern "C" int pmh_kspfeti_solve(pmh_ctx ctx, int nsub, const int *block_rowstar
       // default inner solver is then QPSKSP = CG (qps.c:448) under SMALXE's stopping rule; this library's inner solver is MPGP with no bounds, whose steps are
       // all CG steps -- the same iteration.
       if (o->lumped_pc) {
-        rc = pmh_set_error(PMH_ERR_SUP, "pmh_kspfeti_solve: -dual_pc_dual_type lumped with -project 0 is not built");
+        rc = pmh_set_error(PMH_ERR_SUP, "pmh_kspfeti_solve: -dual_pc_dual_type %s with -project 0 is not built", o->lumped_pc == 2 ? "dirichlet" : "lumped");
         goto done;
       }
       pmh_op  F    = nullptr;
@@ -605,7 +616,7 @@ extern "C" int pmh_kspfeti_solve(pmh_ctx ctx, int nsub, const int *block_rowstar
       GO(pmh_smalxe_get_stats(S, &st->smalxe));
       ks.iteration = st->smalxe.iteration, ks.reason = st->smalxe.reason, ks.rnorm = st->smalxe.rnorm;
     } else {
-      GO(pmh_ksp_cg_solve(ctx, A, b, d_x, o->lumped_pc ? (pc ? pc : (pmh_op)lump) : nullptr, o->rtol, o->atol, o->divtol, o->max_it, &ks));
+      GO(pmh_ksp_cg_solve(ctx, A, b, d_x, pc ? pc : (lump ? (pmh_op)lump : dir), o->rtol, o->atol, o->divtol, o->max_it, &ks));
     }
     st->iteration = ks.iteration, st->reason = ks.reason, st->rnorm = ks.rnorm;
     GO(pmh_qpt_feti_chain_post_solve(ch, d_x, d_lam, d_u0, d_r));
@@ -637,6 +648,7 @@ done:
   pmh_free(ctx, d_f), pmh_free(ctx, d_c), pmh_free(ctx, d_e), pmh_free(ctx, d_x), pmh_free(ctx, d_lam), pmh_free(ctx, d_u0), pmh_free(ctx, d_r), pmh_free(ctx, d_alpha);
   if (pc) pmh_op_destroy(pc);
   if (lump) delete lump;
+  if (dir) pmh_op_destroy(dir);
   pmh_smalxe_destroy(S);
   pmh_qpt_feti_chain_destroy(ch);
   if (Kp && E) pmh_matinv_attach_explicit(Kp, nullptr);

@@ -350,7 +350,7 @@ extern "C" int pmh_kspfeti_set_from_options(const char *options, pmh_kspfeti_opt
   std::vector<Token> toks;
   PMH_CHK(tokenize(options, toks));
   static const char *const gtypes[] = {"nonred", "full", "orth"};    // FetiGluingTypes
-  static const char *const pctypes[] = {"none", "lumped"};           // PCDualTypes (pcdual.c)
+  static const char *const pctypes[] = {"none", "lumped", "dirichlet"}; // PCDualTypes (pcdual.c) + dirichlet (pcdual.hip)
   static const char *const orthtypes[] = {"none", "gs", "gslingen", "cholesky", "implicit", "inexact"}; // MatOrthTypes (permonmatorth.c:6)
   std::string left;
   int         inner_alpha_bits = 0;
@@ -368,7 +368,7 @@ extern "C" int pmh_kspfeti_set_from_options(const char *options, pmh_kspfeti_opt
     else if (k == "qpt_dualize_Kplus_mp") {
       rc = get_bool(t, &b) ? -1 : 1;
       if (rc == 1) mp_given = b; // the Moore-Penrose wrapping is this library's -regularize 0 path
-    } else if (k == "dual_pc_dual_type") rc = get_enum(t, pctypes, 2, &o->lumped_pc) ? -1 : 1;
+    } else if (k == "dual_pc_dual_type") rc = get_enum(t, pctypes, 3, &o->lumped_pc) ? -1 : 1;
     else if (k == "dual_mat_inv_ksp_rtol") rc = get_real(t, &o->kplus_rtol) ? -1 : 1;
     else if (k == "dual_mat_inv_ksp_max_it") rc = get_int(t, &o->kplus_max_it) ? -1 : 1;
     else if (k == "dual_mat_inv_pc_type") { // the PC of MATINV's inner KSP (MatInvGetKSP; PETSc's PCType names): jacobi | gamg (mg: the same algebraic hierarchy)

@@ -598,6 +598,48 @@ def PCDualLumpedOp(B, K):
     return Op.shell(ctx, B.n_lambda, fn)
 
 
+class PCDualDirichletOp(Op):
+    """PCDUAL dirichlet: y = B S B' x, S = blockdiag(S_b), S_b = K_GG - K_GI K_II^-1 K_IG the Schur complement of block b on the dofs B touches
+    (pmh_op_create_pc_dual_dirichlet, csrc/pcdual.hip; the reference's PCApply_Dual src/pc/impls/dual/pcdual.c:63-78 with C_bb = S).  The set-up solves
+    with K_II by Jacobi PCG at rtol / max_it; S_b is kept dense and exactly symmetric in "sym" (4 n_Gamma^2 bytes) or "full" (8 n_Gamma^2) storage."""
+
+    def __init__(self, B, K, storage="sym", rtol=1e-12, max_it=20000):
+        h = C.c_void_p()
+        check(B.ctx.L.pmh_op_create_pc_dual_dirichlet(B.h, K.h, {"full": 0, "sym": 1}[storage], float(rtol), int(max_it), C.byref(h)))
+        super().__init__(B.ctx, h, B.n_lambda, keep=[B, K])
+        self.nblocks, self.storage = K.nblocks, storage
+
+    def stats(self):
+        """(set-up solves with K_II, set-up seconds, bytes of the dense storage)"""
+        n, t, db = C.c_longlong(), C.c_double(), C.c_double()
+        check(self.ctx.L.pmh_pc_dual_dirichlet_stats(self.h, C.byref(n), C.byref(t), C.byref(db)))
+        return n.value, t.value, db.value
+
+    def explicit(self):
+        """The pmh_fexplicit that holds S (borrowed handle: pmh_fexplicit_sizes / pmh_fexplicit_timing_*)."""
+        e = C.c_void_p()
+        check(self.ctx.L.pmh_pc_dual_dirichlet_get_explicit(self.h, C.byref(e)))
+        return e
+
+    def block(self, b):
+        """(S_b as stored, Gamma_b as rank-local primal indices)."""
+        ng = np.zeros(self.nblocks, dtype=np.int32)
+        check(self.ctx.L.pmh_fexplicit_sizes(self.explicit(), None, ng.ctypes.data_as(C.c_void_p), None, None))
+        n = int(ng[b])
+        S, g = np.zeros((n, n)), np.zeros(max(n, 1), dtype=np.int32)
+        check(self.ctx.L.pmh_pc_dual_dirichlet_get_block(self.h, int(b), S.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p)))
+        return S, g[:n]
+
+    def timing_enable(self, max_launches, stride=1):
+        check(self.ctx.L.pmh_fexplicit_timing_enable(self.explicit(), int(max_launches), int(stride)))
+
+    def timing_get(self):
+        """(timed dense launches, their total milliseconds)"""
+        n, ms = C.c_int(), C.c_double()
+        check(self.ctx.L.pmh_fexplicit_timing_get(self.explicit(), C.byref(n), C.byref(ms), None))
+        return n.value, ms.value
+
+
 def MatCreateSVMDual(ctx, X, y):
     """Matrix-free H = diag(y) X X' diag(y) of the hinge-loss SVM dual (BASELINE configs[4]); X: (n_local, d) row-major."""
     X = np.ascontiguousarray(X, dtype=np.float64)
