@@ -661,15 +661,34 @@ typedef struct {
   int    mg, mg_min_nodes, mg_degree, mg_precision; /* multigrid PC of the inner KSP: the box hierarchy when dims != NULL (pmh_mg_create_box), else the algebraic one
                                                        (pmh_mg_create_sa on the kernel vectors; max_coarse = 3 mg_min_nodes): blocks of any shape */
   int    bsr3;                      /* K x of the inner CG on the 3x3-block kernel when ndof == 3 */
-  int    explicit_dual; double explicit_rtol; int explicit_storage; /* pmh_fexplicit_* (PMH_FX_SYM / PMH_FX_FULL / PMH_FX_CLASS / PMH_FX_CLASS_SYM / PMH_FX_CLASS_ORBIT) */
+  int    explicit_dual; double explicit_rtol; int explicit_storage; /* explicit_dual: 0 / positive / PMH_KPLUS_AUTO, see below; storage: pmh_fexplicit_* (PMH_FX_SYM / PMH_FX_FULL / PMH_FX_CLASS /
+                                                                 PMH_FX_CLASS_SYM / PMH_FX_CLASS_ORBIT) */
   int    orthonormalize;            /* QPTOrthonormalizeEq: 1 G <- L^{-1} G formed explicitly, 2 implicitly (G stays sparse, -qp_E_orth_form implicit), 0 none */
   int    explicit_symmetry;         /* PMH_FX_CLASS_SYM / _ORBIT with dims != NULL: the symmetries of the box (pmh_fexplicit_set_box_symmetry) serve the set-up / the storage */
+  double expected_applies;          /* explicit_dual == PMH_KPLUS_AUTO: the F applications the caller expects the solve to take; 0: PMH_KPLUS_AUTO_DEFAULT_APPLIES */
 } pmh_feti_contact_opts;
+/* explicit_dual: 0 the inner Krylov K^+ in every F application; any positive value (default 1) the explicit local dual operators; PMH_KPLUS_AUTO the choice between the two
+ * by the estimated time to solution.  The probe (after the hierarchy, the gluing and the projector exist): one timed F application through the inner Krylov K^+ on a fixed
+ * pseudo-random lambda (after one untimed one), t_it; the explicit storage planned exactly as explicit_dual = 1 plans it and the first batch of its set-up solves run and
+ * timed, t_batch (the batch is kept if the explicit path is chosen); the dense apply estimated from the planned storage, t_ex = bytes / 5.87 TB/s (k_fx_symv, whole F
+ * application, storage PMH_FX_SYM on the 43^3-scale staircase cut) or, PMH_FX_CLASS_ORBIT, useful flops / 36.5 TFLOP/s (k_fxo_gemm16 on configs[2]).  Explicit iff
+ *   n_batches t_batch + A t_ex < A t_it,   n_batches = the set-up batches still to run, A = expected_applies (0: PMH_KPLUS_AUTO_DEFAULT_APPLIES);
+ * then exactly the path of explicit_dual = 1 or 0 runs.  F applications of one default solve (rtol 1e-5), measured: configs[2] (2 x 2 x 2 boxes of 43^3 elements, orbit
+ * storage) 196, the staircase cut of feti.irregular_partition at 21^3 scale 165 and at 43^3 scale 207 (profiles/r07_kplus_auto_staircase43.txt); the default A = 250 is the
+ * largest of them with some room.  With it the rule picks explicit on configs[2] and the inner Krylov K^+ on both staircase cuts. */
+#define PMH_KPLUS_AUTO (-1)
+#define PMH_KPLUS_AUTO_DEFAULT_APPLIES 250
 typedef struct {
   pmh_smalxe_stats smalxe;
   int    n_lambda, n_eq, coarse_dim, n_active, explicit_solves;
   double setup_seconds, solve_seconds, explicit_seconds, norm_Glambda_minus_e;
   int    explicit_symmetries;       /* operations used by the set-up by symmetry (0 / 1: none) */
+  int    kplus_path;                /* the K^+ of F this solve ran: 0 inner Krylov, 1 explicit local dual operators (every call) */
+  int    kplus_auto;                /* 1: explicit_dual == PMH_KPLUS_AUTO chose it */
+  long long setup_solves_planned;   /* K^+ solves of the explicit set-up as planned (the explicit path and the probe; the self-check of the set-up by symmetry included) */
+  double expected_applies_used, est_explicit_seconds, est_iterative_seconds; /* PMH_KPLUS_AUTO: A and the two sides of the rule */
+  double probe_seconds;             /* PMH_KPLUS_AUTO: wall time of the probe (inside setup_seconds; its set-up batch is reused when the explicit path is chosen) */
+  int    f_applies;                 /* F applications of the SMALXE solve (set-up and post-solve not counted) */
 } pmh_feti_contact_stats;
 int pmh_feti_contact_default_opts(pmh_feti_contact_opts *o);
 int pmh_feti_contact_solve(pmh_ctx ctx, int nsub, const int *block_rowstart, const int *rowptr, const int *col, const double *val, const double *f, int n_lambda, int n_eq, int n_leaves,

@@ -86,12 +86,15 @@ class KspFetiStats(C.Structure):
 
 class FetiContactOpts(C.Structure):
     _fields_ = [("smalxe", SmalxeOpts), ("kplus_rtol", C.c_double), ("kplus_max_it", C.c_int), ("mg", C.c_int), ("mg_min_nodes", C.c_int), ("mg_degree", C.c_int), ("mg_precision", C.c_int),
-                ("bsr3", C.c_int), ("explicit_dual", C.c_int), ("explicit_rtol", C.c_double), ("explicit_storage", C.c_int), ("orthonormalize", C.c_int), ("explicit_symmetry", C.c_int)]
+                ("bsr3", C.c_int), ("explicit_dual", C.c_int), ("explicit_rtol", C.c_double), ("explicit_storage", C.c_int), ("orthonormalize", C.c_int), ("explicit_symmetry", C.c_int),
+                ("expected_applies", C.c_double)]
 
 
 class FetiContactStats(C.Structure):
     _fields_ = [("smalxe", SmalxeStats), ("n_lambda", C.c_int), ("n_eq", C.c_int), ("coarse_dim", C.c_int), ("n_active", C.c_int), ("explicit_solves", C.c_int),
-                ("setup_seconds", C.c_double), ("solve_seconds", C.c_double), ("explicit_seconds", C.c_double), ("norm_Glambda_minus_e", C.c_double), ("explicit_symmetries", C.c_int)]
+                ("setup_seconds", C.c_double), ("solve_seconds", C.c_double), ("explicit_seconds", C.c_double), ("norm_Glambda_minus_e", C.c_double), ("explicit_symmetries", C.c_int),
+                ("kplus_path", C.c_int), ("kplus_auto", C.c_int), ("setup_solves_planned", C.c_longlong), ("expected_applies_used", C.c_double), ("est_explicit_seconds", C.c_double),
+                ("est_iterative_seconds", C.c_double), ("probe_seconds", C.c_double), ("f_applies", C.c_int)]
 
 
 class PcpgStats(C.Structure):

@@ -11,6 +11,8 @@ from .core import Op, Vec
 from .mat import QPPF, MatBlockDiag, MatCreateFetiDual, MatCreateProjected, MatExplicitDual, MatGluing, MatInv, MatRegularize, PCDualDirichletOp, PCDualLumpedOp, csr_block_classes
 from .qps import QP, QPS
 
+PMH_KPLUS_AUTO = -1  # pmh_feti_contact_opts.explicit_dual: choose the K^+ of F by the estimated time to solution (include/permon_hip.h)
+
 
 def regularize_blocks(ctx, local, rho=None):
     """MatRegularize on a MATBLOCKDIAG (permonmatregularize.c:241-266 works on the rank's diagonal block; with several
@@ -384,9 +386,12 @@ def KSPFETISolve(ctx, block_rowstart, K, f, l2g, dirichlet_local=None, R=None, g
     return u, lam[:st.n_lambda].copy(), st
 
 
-def FETIContactSolve(ctx, f, explicit=True, mg_precision="fp16", rtol=1e-5, kplus_rtol=1e-9, explicit_rtol=1e-12, mg_min_nodes=400, dims=None, explicit_storage=None, explicit_symmetry=True):
+def FETIContactSolve(ctx, f, explicit=True, mg_precision="fp16", rtol=1e-5, kplus_rtol=1e-9, explicit_rtol=1e-12, mg_min_nodes=400, dims=None, explicit_storage=None, explicit_symmetry=True,
+                     expected_applies=0.0):
     """pmh_feti_contact_solve (contact.hip): the whole contact TFETI solve in ONE library call -- QPTFromOptions / QPTAllInOne
     (qptransform.c:2152-2237) + QPSSolve + the post-solve chain; f: a CubeFeti-like problem (K, f, leaves, c, R, n_eq).
+    explicit: True = the explicit local dual operators carry F, False = the inner Krylov K^+, "auto" = the library chooses by the estimated time to solution
+    (PMH_KPLUS_AUTO) for expected_applies F applications (0: the library's default); stats.kplus_path says which ran.
     Returns (u, lambda, stats: _lib.FetiContactStats)."""
     from . import _lib
 
@@ -394,7 +399,14 @@ def FETIContactSolve(ctx, f, explicit=True, mg_precision="fp16", rtol=1e-5, kplu
     K.sort_indices()
     o, st = _lib.FetiContactOpts(), _lib.FetiContactStats()
     check(ctx.L.pmh_feti_contact_default_opts(C.byref(o)))
-    o.smalxe.rtol, o.kplus_rtol, o.explicit_dual, o.explicit_rtol = rtol, kplus_rtol, int(bool(explicit)), explicit_rtol
+    if isinstance(explicit, str):
+        if explicit != "auto":
+            raise ValueError("explicit must be True, False or 'auto', not %r" % explicit)
+        explicit_dual = PMH_KPLUS_AUTO
+    else:
+        explicit_dual = int(bool(explicit))
+    o.smalxe.rtol, o.kplus_rtol, o.explicit_dual, o.explicit_rtol = rtol, kplus_rtol, explicit_dual, explicit_rtol
+    o.expected_applies = float(expected_applies)
     o.mg_precision, o.mg_min_nodes = {"fp64": 0, "fp32": 1, "fp16": 2}[mg_precision], int(mg_min_nodes)
     if explicit_storage is not None:
         o.explicit_storage = {"full": 0, "sym": 1, "class": 2, "class_sym": 3, "class_orbit": 4}[explicit_storage]

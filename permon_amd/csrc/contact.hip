@@ -14,7 +14,7 @@
 #include <map>
 #include <thread>
 
-#include "pmh_internal.h"
+#include "feti_internal.h"
 
 extern "C" int pmh_feti_contact_default_opts(pmh_feti_contact_opts *o)
 {
@@ -182,6 +182,7 @@ extern "C" int pmh_feti_contact_solve(pmh_ctx ctx, int nsub, const int *block_ro
   pmh_fexplicit  E  = nullptr;
   pmh_feti_chain ch = nullptr;
   pmh_smalxe     sx = nullptr;
+  pmh_op         Fd = nullptr; // F = B K^+ B' of the chain (borrowed): its applications during the solve
   double        *d_f = nullptr, *d_c = nullptr, *d_e = nullptr, *d_x = nullptr, *d_lb = nullptr, *d_lam = nullptr, *d_u0 = nullptr, *d_r = nullptr;
   int            rc = PMH_SUCCESS;
 #define GO(call) \
@@ -213,12 +214,15 @@ extern "C" int pmh_feti_contact_solve(pmh_ctx ctx, int nsub, const int *block_ro
     stage("gluing, G, projector");
     std::vector<double> e_raw = e; // pairs with Gd = G0 in the diagnostic below
     if (o->orthonormalize == 2) GO(pmh_qppf_orth_rhs(pf, e_raw.data(), e.data())); // the constraint becomes (T G0) lambda = T e0
-    if (o->explicit_dual) { // MatInvExplicitly restricted to the dofs B touches; congruent blocks share their columns
-      std::vector<int> cls(nsub);
-      GO(pmh_csr_block_classes(nsub, block_rowstart, rowptr, col, val, cls.data(), nullptr));
+    // ---- the explicit local dual operators, in two steps that the forced path and the probe of PMH_KPLUS_AUTO share: plan_explicit (the classes, the symmetry or orbit
+    // decision with its union fallback, the storage: E created, nothing assembled) and assemble_explicit (the K^+ solves of the set-up, all of them or a window of the batches)
+    std::vector<int> cls(nsub);
+    int              ncls = 0;
+    auto plan_explicit = [&]() -> int { // MatInvExplicitly restricted to the dofs B touches; congruent blocks share their columns
+      PMH_CHK(pmh_csr_block_classes(nsub, block_rowstart, rowptr, col, val, cls.data(), nullptr));
       stage("  explicit operators: block classes");
       // blocks of one class share K, hence K^+ (the Moore-Penrose inverse does not depend on the basis chosen for the kernel)
-      int ncls = 0;
+      ncls = 0;
       for (int b = 0; b < nsub; b++) ncls = std::max(ncls, cls[b] + 1);
       // box-shaped blocks: the symmetries of the box that leave the class matrix invariant -> one K^+ solve per orbit of rows (PMH_FX_CLASS_SYM), or only the
       // representatives' rows kept and F's dense part applied as a GEMM (PMH_FX_CLASS_ORBIT; falls back to the symmetric tiles when a class has < 16 operations)
@@ -247,8 +251,8 @@ extern "C" int pmh_feti_contact_solve(pmh_ctx ctx, int nsub, const int *block_ro
       if (storage == PMH_FX_CLASS_ORBIT && !(dims && o->explicit_symmetry)) storage = PMH_FX_CLASS_SYM;
       if (storage == PMH_FX_CLASS_ORBIT) {
         int least = 0;
-        GO(pmh_fexplicit_create_shared_orbit(B, Kb, cls.data(), &E));
-        GO(set_symmetries(&least));
+        PMH_CHK(pmh_fexplicit_create_shared_orbit(B, Kb, cls.data(), &E));
+        PMH_CHK(set_symmetries(&least));
         if (least < 16) {
           // a class whose own touched set (a block's interface faces + a Dirichlet or contact face) is not invariant under the box's group keeps few operations -- the case of
           // non-congruent decompositions, one class per block.  On the CLOSURE of the touched set under the group (the whole boundary of a cube) every operation survives
@@ -270,13 +274,13 @@ extern "C" int pmh_feti_contact_solve(pmh_ctx ctx, int nsub, const int *block_ro
             for (int i = r0; i <= r1; i++) rp[i - r0] = rowptr[i] - k0;
             for (int k = 0; k < nz; k++) cj[k] = col[k0 + k] - r0;
             int n_out = 0;
-            GO(pmh_box_symmetry_closure(dims + 3 * b0, ndof, rp.data(), cj.data(), val + k0, (int)touched[c].size(), touched[c].data(), &n_out, out.data(), nullptr));
+            PMH_CHK(pmh_box_symmetry_closure(dims + 3 * b0, ndof, rp.data(), cj.data(), val + k0, (int)touched[c].size(), touched[c].data(), &n_out, out.data(), nullptr));
             erel.insert(erel.end(), out.begin(), out.begin() + n_out);
             eptr[c + 1] = (int)erel.size();
           }
           if (erel.empty()) erel.push_back(0);
-          GO(pmh_fexplicit_create_shared_orbit_union(B, Kb, cls.data(), eptr.data(), erel.data(), &E));
-          GO(set_symmetries(&least));
+          PMH_CHK(pmh_fexplicit_create_shared_orbit_union(B, Kb, cls.data(), eptr.data(), erel.data(), &E));
+          PMH_CHK(set_symmetries(&least));
           if (least < 16) { // still too few operations for the GEMM form (boxes with three different sides): the symmetric tiles
             pmh_fexplicit_destroy(E);
             E = nullptr, storage = PMH_FX_CLASS_SYM, st->explicit_symmetries = 0;
@@ -284,16 +288,93 @@ extern "C" int pmh_feti_contact_solve(pmh_ctx ctx, int nsub, const int *block_ro
         }
       }
       if (!E) {
-        if (storage == PMH_FX_CLASS) GO(pmh_fexplicit_create_shared(B, Kb, cls.data(), &E)); // congruent blocks share one matrix per class
-        else if (storage == PMH_FX_CLASS_SYM) GO(pmh_fexplicit_create_shared_sym(B, Kb, cls.data(), &E));
-        else GO(pmh_fexplicit_create(B, Kb, storage, &E));
+        if (storage == PMH_FX_CLASS) PMH_CHK(pmh_fexplicit_create_shared(B, Kb, cls.data(), &E)); // congruent blocks share one matrix per class
+        else if (storage == PMH_FX_CLASS_SYM) PMH_CHK(pmh_fexplicit_create_shared_sym(B, Kb, cls.data(), &E));
+        else PMH_CHK(pmh_fexplicit_create(B, Kb, storage, &E));
         if (storage == PMH_FX_CLASS_SYM && dims && o->explicit_symmetry) {
           int least = 0;
-          GO(set_symmetries(&least));
+          PMH_CHK(set_symmetries(&least));
         }
       }
       stage("  explicit operators: class union, gluing of the classes, symmetries");
-      GO(pmh_fexplicit_assemble_auto(E, Kp, cls.data(), cls.data(), o->explicit_rtol, 0, nullptr)); // 8 columns per block and application where the multi-right-hand-side K^+ applies
+      return PMH_SUCCESS;
+    };
+    fx_batch_window win; // the batches of the set-up this call runs (the probe: the first one; the explicit path: the rest)
+    auto assemble_explicit = [&](int begin, int end) -> int {
+      win.begin = begin, win.end = end;
+      PMH_CHK(pmh_fexplicit_set_window(E, &win));
+      const int rc1 = pmh_fexplicit_assemble_auto(E, Kp, cls.data(), cls.data(), o->explicit_rtol, 0, nullptr); // 8 columns per block and application where the multi-right-hand-side K^+ applies
+      pmh_fexplicit_set_window(E, nullptr);
+      st->setup_solves_planned = win.nsolves;
+      return rc1;
+    };
+    bool use_explicit = o->explicit_dual != 0;
+    int  probed       = 0; // set-up batches the probe ran (kept by the explicit path)
+    if (o->explicit_dual == PMH_KPLUS_AUTO) {
+      // ---- the probe: both sides of the rule measured on this problem (the rule and its constants: include/permon_hip.h, explicit_dual)
+      constexpr double fx_apply_bytes_per_s = 5.87e12; // k_fx_symv's F application at 43^3-scale, storage PMH_FX_SYM: 17.64 GB in 3.00 ms (profiles/r06_bench_nosym_staircase43_line_end_of_round.json)
+      constexpr double fxo_useful_flops_per_s = 36.5e12; // k_fxo_gemm16 on configs[2]: 0.464 of the 78.6 TFLOP/s fp64 matrix peak in useful flops (profiles/r06_bench_default_1gpu_line.json)
+      st->kplus_auto = 1;
+      const auto t_probe = std::chrono::steady_clock::now();
+      double     t_it    = 0.0;
+      int        it_cg   = 0; // CG iterations of the timed K^+ (the slowest block)
+      {
+        pmh_op  F0 = nullptr;
+        double *d_l = nullptr, *d_y = nullptr;
+        auto    probe_it = [&]() -> int { // one F application through the inner Krylov K^+: gluing transpose, pmh_matinv_mult, gluing (pmh_op_create_feti_dual)
+          PMH_CHK(pmh_op_create_feti_dual(B, Kp, &F0));
+          PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)nl, (void **)&d_l));
+          PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)nl, (void **)&d_y));
+          std::vector<double> l((size_t)nl);
+          unsigned long long  x = 0x9E3779B97F4A7C15ull; // fixed pseudo-random lambda in [-1, 1) (xorshift64)
+          for (int q = 0; q < nl; q++) {
+            x ^= x << 13, x ^= x >> 7, x ^= x << 17;
+            l[q] = (double)(x >> 11) * 0x1.0p-52 - 1.0;
+          }
+          PMH_CHK(pmh_memcpy_h2d(ctx, d_l, l.data(), sizeof(double) * (size_t)nl));
+          PMH_CHK(pmh_op_mult(F0, d_l, d_y)); // untimed: first launches, the solver's iteration count
+          PMH_CHK(pmh_sync(ctx));
+          const auto t0 = std::chrono::steady_clock::now();
+          PMH_CHK(pmh_op_mult(F0, d_l, d_y));
+          PMH_CHK(pmh_sync(ctx));
+          t_it = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+          return pmh_matinv_last_iterations(Kp, &it_cg, nullptr);
+        };
+        rc = probe_it();
+        pmh_op_destroy(F0);
+        pmh_free(ctx, d_l), pmh_free(ctx, d_y);
+        if (rc) goto done;
+      }
+      stage("  K^+ probe: one inner-Krylov F application");
+      GO(plan_explicit());
+      GO(assemble_explicit(0, 1)); // the first batch of the set-up, kept if the explicit path is chosen
+      probed = 1;
+      stage("  K^+ probe: explicit plan, first set-up batch");
+      {
+        double flops = 0.0, bytes = 0.0;
+        GO(pmh_fexplicit_apply_flops(E, &flops));
+        GO(pmh_fexplicit_sizes(E, nullptr, nullptr, nullptr, &bytes));
+        const double t_ex    = flops > 0.0 ? flops / fxo_useful_flops_per_s : bytes / fx_apply_bytes_per_s;
+        const double t_batch = win.loop_seconds / std::max(1, std::min(win.end, win.nbatch) - win.begin);
+        const double A       = o->expected_applies > 0.0 ? o->expected_applies : (double)PMH_KPLUS_AUTO_DEFAULT_APPLIES;
+        st->expected_applies_used = A;
+        st->est_explicit_seconds  = (double)std::max(0, win.nbatch - probed) * t_batch + A * t_ex;
+        st->est_iterative_seconds = A * t_it;
+        use_explicit              = st->est_explicit_seconds < st->est_iterative_seconds;
+      }
+      if (!use_explicit) { // the inner Krylov path, as explicit_dual = 0 runs it
+        pmh_fexplicit_destroy(E);
+        E = nullptr, st->explicit_symmetries = 0;
+      }
+      st->probe_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_probe).count();
+      if (verbose)
+        fprintf(stderr, "pmh_feti_contact_solve: K^+ probe: F apply %.4f s inner Krylov (%d CG iterations), %d set-up batches of %.4f s (%lld solves); A = %.0f: explicit %.3f s, iterative %.3f s -> %s\n", t_it,
+                it_cg, win.nbatch, win.loop_seconds, (long long)win.nsolves, st->expected_applies_used, st->est_explicit_seconds, st->est_iterative_seconds, use_explicit ? "explicit" : "iterative");
+    }
+    st->kplus_path = use_explicit ? 1 : 0;
+    if (use_explicit) {
+      if (!E) GO(plan_explicit());
+      if (!(probed && win.complete)) GO(assemble_explicit(probed, 1 << 30)); // (a set-up of one batch is complete after the probe)
       GO(pmh_matinv_attach_explicit(Kp, E));
       stage("  explicit operators: assembly (K^+ solves, self-check)");
       long long ns;
@@ -328,7 +409,12 @@ extern "C" int pmh_feti_contact_solve(pmh_ctx ctx, int nsub, const int *block_ro
     pmh_csr_set_host_hint(Kc, nullptr, nullptr, nullptr);
     auto t_solve     = std::chrono::steady_clock::now();
     st->setup_seconds = std::chrono::duration<double>(t_solve - t_start).count();
+    long long fa0, fa1;
+    GO(pmh_qpt_feti_chain_get(ch, &Fd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    GO(pmh_feti_dual_applies(Fd, &fa0));
     GO(pmh_smalxe_solve(sx));
+    GO(pmh_feti_dual_applies(Fd, &fa1));
+    st->f_applies = (int)(fa1 - fa0);
     GO(pmh_smalxe_get_stats(sx, &st->smalxe));
     GO(pmh_sync(ctx));
     st->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_solve).count();

@@ -893,6 +893,7 @@ struct FetiDualOp : pmh_op_s {
   pmh_gluing B;
   pmh_matinv Kplus;
   double    *t1, *t2;
+  long long  applies = 0; // mult + mid_apply (pmh_feti_dual_applies)
   ~FetiDualOp() override
   {
     pmh_free(ctx, t1);
@@ -901,6 +902,7 @@ struct FetiDualOp : pmh_op_s {
   // MatCreateProd(Bt, Kplus, B) applied right to left: qptransform.c:1103-1128, matprod.c:42-48
   int mult(const double *x, double *y) override
   {
+    applies++;
     if (Kplus->E && pmh_fexplicit_matches(Kplus->E, B)) return pmh_fexplicit_apply(Kplus->E, x, y); // explicit local dual operators
     PMH_CHK(pmh_gluing_mult(B, x, t1));
     PMH_CHK(pmh_matinv_mult(Kplus, t1, t2));
@@ -917,10 +919,19 @@ struct FetiDualOp : pmh_op_s {
   }
   int mid_apply() override
   {
+    applies++;
     if (Kplus->E && pmh_fexplicit_matches(Kplus->E, B)) return pmh_fexplicit_mid(Kplus->E);
     return pmh_matinv_mult(Kplus, t1, t2);
   }
 };
+
+int pmh_feti_dual_applies(pmh_op F, long long *n)
+{
+  const FetiDualOp *o = dynamic_cast<const FetiDualOp *>(F);
+  PMH_ARG(o && n);
+  *n = o->applies;
+  return PMH_SUCCESS;
+}
 
 extern "C" int pmh_op_create_feti_dual(pmh_gluing B, pmh_matinv Kplus, pmh_op *F)
 {

@@ -69,6 +69,19 @@ int  pmh_fexplicit_mid(pmh_fexplicit_s *E);                                     
 // FULL / SYM storage (PMH_ERR_SUP otherwise); _mark_assembled once every block is written (n_solves, seconds: what the set-up took)
 int  pmh_fexplicit_store_symmetrized(pmh_fexplicit_s *E, int b, const double *S, int lds);
 int  pmh_fexplicit_mark_assembled(pmh_fexplicit_s *E, long long n_solves, double seconds);
+// A window of the set-up's batches (the probe of pmh_feti_contact_solve's PMH_KPLUS_AUTO, contact.hip): the next pmh_fexplicit_assemble(_auto) runs batches [begin, end) of
+// its plan only, in the order and with the columns the whole set-up would give them; batch nbatch - 1 is the self-check of the set-up by symmetry where there is one.  The
+// operator counts as assembled once a window has reached the last batch.  Out: the plan (batches, K^+ solves) and the device-synchronised seconds of the batches run.
+struct fx_batch_window {
+  int       begin = 0, end = 1 << 30;
+  int       nbatch = 0;
+  long long nsolves = 0;
+  double    loop_seconds = 0.0;
+  bool      complete = false;
+};
+int  pmh_fexplicit_set_window(pmh_fexplicit_s *E, fx_batch_window *w); // NULL: the whole set-up (w is borrowed until then)
+// F = B K^+ B' (pmh_op_create_feti_dual): the applications since its creation, either K^+; PMH_ERR_ARG for another operator
+int  pmh_feti_dual_applies(pmh_op F, long long *n);
 
 // ---- what the set-up loops of the explicit operators (fexplicit.hip, fshared.hip) need from a K^+ solver: one COLUMN per slot ----------------------------------
 // nslots == solver->nblocks: slot s = block s of the one-column solver (pmh_matinv_mult).  nslots == PMH_MV_R * solver->nblocks: the multi-right-hand-side solver

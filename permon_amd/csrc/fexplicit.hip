@@ -67,6 +67,7 @@ struct pmh_fexplicit_s {
   std::vector<std::vector<char>> owned; // [block][super band]
   long long n_solves;
   double   assemble_seconds;
+  fx_batch_window *win; // the next assembly runs this window of its batches only (pmh_fexplicit_set_window); NULL: all of them
   std::vector<hipEvent_t> ev, ev_mid; // pairs around the dense launch(es); SYM: a third event between k_fx_symv and k_fx_symv_fin
   int      ev_used, ev_on, ev_seen, ev_stride;
 };
@@ -392,7 +393,7 @@ static int fx_create(pmh_gluing B, pmh_blockdiag K, int storage, const int *bloc
   pmh_fexplicit E   = new pmh_fexplicit_s();
   E->ctx = ctx, E->B = B, E->K = K, E->Bhat = nullptr, E->nb = K->nblocks;
   E->d_gamma_rel = nullptr, E->Wbase = nullptr, E->d_woff = nullptr, E->d_ld = E->d_gstart = E->d_ngam = E->d_wg_block = E->d_wg_row0 = nullptr;
-  E->xh = E->yh = nullptr, E->assembled = 0, E->n_solves = 0, E->assemble_seconds = 0.0;
+  E->xh = E->yh = nullptr, E->assembled = 0, E->n_solves = 0, E->assemble_seconds = 0.0, E->win = nullptr;
   E->stripe_rank = 0, E->stripe_size = 0, E->sh = nullptr;
   E->ev_used = E->ev_on = E->ev_seen = 0, E->ev_stride = 1;
   E->storage = storage, E->partial = E->ydir = nullptr, E->d_poff = E->d_doff = nullptr, E->d_sw_block = E->d_sw_band = E->d_sw_seg = E->d_fw_block = E->d_fw_col0 = E->d_own_ptr = E->d_own_list = nullptr, E->nsw = E->nfw = 0, E->sym_bytes = 0.0;
@@ -755,8 +756,8 @@ extern "C" int pmh_fexplicit_assemble(pmh_fexplicit E, pmh_matinv solver, int ns
   if (E->sh) { // class-shared storage: one full row of W_c per solve (the classes are those given at creation)
     PMH_ARG(slot_class);
     auto t0s = std::chrono::steady_clock::now();
-    PMH_CHK(fxs_assemble(E->sh, solver, nslots, slot_class, rtol, max_it, &E->n_solves));
-    E->assembled = 1;
+    PMH_CHK(fxs_assemble(E->sh, solver, nslots, slot_class, rtol, max_it, &E->n_solves, E->win));
+    if (!E->win || E->win->complete) E->assembled = 1;
     E->assemble_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0s).count();
     return PMH_SUCCESS;
   }
@@ -806,6 +807,12 @@ extern "C" int pmh_fexplicit_assemble(pmh_fexplicit E, pmh_matinv solver, int ns
   int nbatch = 0;
   for (int c = 0; c < ncls; c++)
     if (!cblocks[c].empty()) nbatch = std::max(nbatch, (int)((cunion[c].size() + cslots[c].size() - 1) / cslots[c].size()));
+  fx_batch_window *w    = E->win; // the batches of this call: all of them, or the caller's window
+  const int        kbeg = w ? std::max(0, w->begin) : 0, kend = w ? std::min(nbatch, w->end) : nbatch;
+  if (w) {
+    w->nbatch = nbatch, w->nsolves = 0, w->complete = w->end >= nbatch;
+    for (int c = 0; c < ncls; c++) w->nsolves += (long long)cunion[c].size();
+  }
   double *rhs, *sol;
   int    *d_idx, *h_idx;
   const size_t nsol = A.len();
@@ -821,8 +828,10 @@ extern "C" int pmh_fexplicit_assemble(pmh_fexplicit E, pmh_matinv solver, int ns
   int        rc = PMH_SUCCESS;
   std::vector<int> col(nslots);
   const bool progress = getenv("PMH_PROGRESS") != nullptr || getenv("PMH_CONTACT_TIMING") != nullptr; // (set-up only: a long assembly says where it is every ~ 20 s)
+  if (w) rc = pmh_sync(ctx); // (the window's seconds are the batches' alone)
   auto       t_prog   = std::chrono::steady_clock::now();
-  for (int k = 0; k < nbatch && !rc; k++) {
+  const auto t_loop   = t_prog;
+  for (int k = kbeg; k < kend && !rc; k++) {
     if (progress && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_prog).count() > 20.0) {
       t_prog = std::chrono::steady_clock::now();
       fprintf(stderr, "  pmh_fexplicit_assemble: batch %d of %d (%d columns per batch), %.0f s\n", k, nbatch, nslots, std::chrono::duration<double>(t_prog - t0).count());
@@ -871,11 +880,12 @@ extern "C" int pmh_fexplicit_assemble(pmh_fexplicit E, pmh_matinv solver, int ns
     if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: launch failed in batch %d", k);
   }
   if (!rc) rc = pmh_sync(ctx);
+  if (w) w->loop_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
   pmh_matinv_set_tolerances(solver, old_rtol, old_atol, old_maxit);
   pmh_free(ctx, rhs), pmh_free(ctx, sol), pmh_free(ctx, d_idx);
   (void)hipHostFree(h_idx);
   if (rc) return rc;
-  E->assembled = 1;
+  if (!w || w->complete) E->assembled = 1;
   E->assemble_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return PMH_SUCCESS;
 }
@@ -916,6 +926,14 @@ extern "C" int pmh_fexplicit_fill_pattern(pmh_fexplicit E, int byte)
   PMH_HIP(hipMemsetAsync(E->Wbase, byte, sizeof(double) * (size_t)tot, E->ctx->stream));
   E->assembled = 1;
   return pmh_sync(E->ctx);
+}
+
+int pmh_fexplicit_set_window(pmh_fexplicit_s *E, fx_batch_window *w)
+{
+  PMH_ARG(E);
+  if (E->assembled && w) return pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_set_window: the operator is assembled already");
+  E->win = w;
+  return PMH_SUCCESS;
 }
 
 extern "C" int pmh_fexplicit_assemble_stats(pmh_fexplicit E, long long *n_solves, double *seconds)

@@ -12,7 +12,7 @@ long long fxs_dense_bytes(fx_shared *S);
 double    fxs_apply_bytes(fx_shared *S);
 double    fxs_apply_flops(fx_shared *S);
 void      fxs_apply_flops_detail(fx_shared *S, double *issued, double *dense);
-int       fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_class, double rtol, int max_it, long long *n_solves);
+int       fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_class, double rtol, int max_it, long long *n_solves, fx_batch_window *w = nullptr); // w: a window of the batches (feti_internal.h)
 int       fxs_apply(fx_shared *S, const double *lambda, double *y);
 int       fxs_dense(fx_shared *S);
 int       fxs_stages(fx_shared *S, pmh_csr *gather, double **mid_in, pmh_csr *scatter, const double **mid_out);

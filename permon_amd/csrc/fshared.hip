@@ -535,7 +535,7 @@ static int fxo_gemm(fx_shared *S)
   return PMH_SUCCESS;
 }
 
-int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_class, double rtol, int max_it, long long *n_solves)
+int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_class, double rtol, int max_it, long long *n_solves, fx_batch_window *w)
 {
   PMH_ARG(S && solver && nslots >= 1 && (solver->nblocks == nslots || solver->nblocks * PMH_MV_R == nslots) && slot_class);
   pmh_ctx                       ctx = S->ctx;
@@ -597,6 +597,15 @@ int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_cl
       for (int p = C.r0; p < std::min(C.r1, C.nc); p++) todo[c].push_back(p); // the rows of this rank's stripe
     nbatch = std::max(nbatch, (int)((todo[c].size() + cslots[c].size() - 1) / cslots[c].size()));
   }
+  bool any_check = false;
+  for (int c = 0; c < S->ncls; c++) any_check = any_check || !check[c].empty();
+  // the batches of this call: all of them, or the caller's window (the self-check is batch nbatch)
+  const int  kbeg = w ? std::max(0, w->begin) : 0, kend = w ? std::min(nbatch, w->end) : nbatch;
+  const bool last = !w || w->end >= nbatch + (any_check ? 1 : 0);
+  if (w) {
+    w->nbatch = nbatch + (any_check ? 1 : 0), w->nsolves = 0, w->complete = last;
+    for (int c = 0; c < S->ncls; c++) w->nsolves += (long long)todo[c].size() + (long long)check[c].size();
+  }
   double      *rhs, *sol;
   int         *d_idx, *h_idx;
   const size_t nsol = A.len();
@@ -611,7 +620,9 @@ int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_cl
   PMH_CHK(pmh_matinv_set_tolerances(solver, rtol, 1e-300, max_it > 0 ? max_it : old_maxit));
   int              rc = PMH_SUCCESS;
   std::vector<int> prow(nslots);
-  for (int k = 0; k < nbatch && !rc; k++) {
+  if (w) rc = pmh_sync(ctx); // (the window's seconds are the batches' alone)
+  const auto t_loop = std::chrono::steady_clock::now();
+  for (int k = kbeg; k < kend && !rc; k++) {
     int *hh = h_idx + (k & 1) * nslots;
     for (int s = 0; s < nslots; s++) hh[s] = -1, prow[s] = -1;
     for (int c = 0; c < S->ncls; c++)
@@ -661,8 +672,7 @@ int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_cl
     if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: launch failed in batch %d", k);
   }
   // self-check of the set-up by symmetry: a few symmetry-filled rows against their direct solves
-  bool any_check = false;
-  for (int c = 0; c < S->ncls; c++) any_check = any_check || !check[c].empty();
+  if (!last) any_check = false;
   if (!rc && any_check) rc = pmh_sync(ctx); // the pinned index buffer is reused below
   if (!rc && any_check) {
     int *hh = h_idx;
@@ -702,6 +712,7 @@ int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_cl
     if (d_out) pmh_free(ctx, d_out);
   }
   if (!rc) rc = pmh_sync(ctx);
+  if (w) w->loop_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
   pmh_matinv_set_tolerances(solver, old_rtol, old_atol, old_maxit);
   pmh_free(ctx, rhs), pmh_free(ctx, sol), pmh_free(ctx, d_idx);
   (void)hipHostFree(h_idx);
