@@ -708,6 +708,18 @@ int pmh_smalxe_run_fixed(pmh_smalxe s, int inner_iters, int *solves, int *outer_
  * pmh_mv_test_spmv: the operator product alone (measurement / test entry): Y = A X for a resident CSR of 3 x 3 blocks and 8 columns, entries kept in `storage`
  * (0 fp64, 1 fp32, 2 fp16 with fp32 vectors); x, y: device, 8 n doubles; the average launch time of `repeats` products through HIP events. */
 int pmh_mv_test_spmv(pmh_csr A, int storage, const double *x, double *y, int repeats, float *ms_per_launch);
+/* ---- CSR product test entries (csrc/spmv.hip: read the plan, or wrap one launch; nothing inside the solvers changes) ----------------------------------------
+ * pmh_csr_kernel_info: the kernel plan pmh_csr_create chose for A.  info[0]: path of a plain product -- 0 ELL (slot-major copy), 1 stream with one lane per row,
+ * 2 medium stream with 8 lanes per row, 3 vector, 4 long-row chunks; info[1]: ELL width or lanes per row (1, 8, 32, 64), 0 for long-row chunks; info[2]: 1 when the
+ * plain product reads 16-bit column offsets; info[3]: entries per row block (paths 1, 2) or the number of chunks (path 4), else 0; info[4]: row blocks (ELL:
+ * blocks of 256 rows); info[5]: partial slots the MPGP epilogue finalises (0 without rows).  With the MPGP epilogue, long-row matrices run the stream kernel of
+ * path 1 (info[4] row blocks).  *uid (or NULL): the matrix's unique, non-zero identity.
+ * pmh_csr_test_mult_epi: one product y = A x with the epilogue `kind` -- 0 none, 1 ADD (y = y1 + A x, y1 may be y), 2 SUB (y = A x - y1), 3 MPGP (y = A x, A square;
+ * scal_host = p'Ap, g'p and the feasible step QPCFeas(xx, p) of p = x, lb / ub may be NULL).  halt != 0: the launch sees a device flag set to 1 and changes
+ * nothing.  Device vectors; synchronises. */
+int pmh_csr_kernel_info(pmh_csr A, int info[6], unsigned long long *uid);
+int pmh_csr_test_mult_epi(pmh_csr A, int kind, const double *x, const double *y1, const double *g, const double *xx, const double *lb, const double *ub, int halt, double *y,
+                          double scal_host[3]);
 /* U = K^+ F for 8 columns per block at once: F, U device arrays of 8 n doubles, entry (dof i, column r) at i * 8 + r; K, the V-cycle (pmh_matinv_set_pc_mg), the kernel
  * basis (pmh_matinv_set_nullspace: K^+ = P_R K^- P_R) and the tolerances are the solver's own; every (block, column) pair converges by its own test.  PMH_ERR_SUP where
  * the multi-right-hand-side kernels do not apply (K without regular 3 x 3 blocks, a V-cycle other than the fused fp32 one, the left generalised inverse). */

@@ -209,6 +209,13 @@ class CsrMat:
     def mult_transpose(self, x, y):  # MatMultTranspose
         check(self.ctx.L.pmh_csr_mult_transpose(self.h, x.p, y.p))
 
+    def kernel_info(self):
+        """(info, uid): the plan pmh_csr_create chose (pmh_csr_kernel_info; info[0] is the path of a plain product: 0 ELL, 1 stream, 2 medium
+        stream, 3 vector, 4 long-row chunks) and the matrix's unique identity."""
+        info, uid = (C.c_int * 6)(), C.c_ulonglong()
+        check(self.ctx.L.pmh_csr_kernel_info(self.h, info, C.byref(uid)))
+        return list(info), uid.value
+
     def algorithmic_bytes(self):
         b = C.c_double()
         check(self.ctx.L.pmh_csr_algorithmic_bytes(self.h, C.byref(b)))

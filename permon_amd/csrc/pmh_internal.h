@@ -263,6 +263,7 @@ int pmh_op_penalized_normG_ready(pmh_op op, const double *u);           // 1: sl
 // launches of the chain's last application (-1: no chain) // 1 if the armed request was served by the last product (and clears it), 0 otherwise (and disarms)
 int pmh_op_penalized_chain_launches(pmh_op op);
 #define PMH_SLOT_NORMBU2 48 // ||B u||^2 prefetched for SMALXE's inner convergence test
+#define PMH_SLOT_TEST_SPMV 56 // [56, 59): p'Ap, g'p, feasible step of pmh_csr_test_mult_epi (spmv.hip; a test entry, no solver writes them)
 int pmh_host_scalar(pmh_ctx ctx, int slot, double *v);                                  // sync + read h_scal[slot]
 
 // ---- 3x3-block SpMV (bsr.hip) -------------------------------------------------------------------------------------

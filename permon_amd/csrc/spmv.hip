@@ -496,11 +496,11 @@ extern "C" int pmh_csr_create(pmh_ctx ctx, int nrows, int ncols, const int *rowp
     if (col[k] < 0 || col[k] >= ncols) return pmh_set_error(PMH_ERR_ARG, "pmh_csr_create: column index %d out of range [0,%d) at nnz %lld", col[k], ncols, k);
   PMH_HIP(hipSetDevice(ctx->device));
   pmh_csr A = new pmh_csr_s();
+  memset(A, 0, sizeof(*A));
   {
     static std::atomic<unsigned long long> next_uid{1};
-    A->uid = next_uid++;
+    A->uid = next_uid++; // after the memset, which would clear it
   }
-  memset(A, 0, sizeof(*A));
   A->ctx   = ctx;
   A->nrows = nrows;
   A->ncols = ncols;
@@ -765,6 +765,14 @@ static int launch(pmh_csr A, const double *x, double *y, const EpiArgs &a)
 
 static int spmv_dispatch(pmh_csr A, const double *x, double *y, const pmh_spmv_epi &e);
 
+// block partials the MPGP epilogue leaves in d_blockpart.  No rows: no kernel runs and nothing is written, so none are read -- the finaliser then
+// stores the identities (0, 0, +inf)
+static int mpgp_nblocks(pmh_csr A)
+{
+  if (A->nrows == 0) return 0;
+  return (A->kind == PMH_SPMV_STREAM && A->st_mode != 0) ? A->n_launch_blocks : A->n_rowblocks;
+}
+
 int pmh_csr_spmv_launch(pmh_csr A, const double *x, double *y, const pmh_spmv_epi &e)
 {
   const bool timed = A->ev && (size_t)(2 * A->ev_used + 1) < A->ev->size();
@@ -850,7 +858,7 @@ static int spmv_dispatch(pmh_csr A, const double *x, double *y, const pmh_spmv_e
       A->ev_pending = 0;
     }
     const int ops[3] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
-    return pmh_finalize_partials(A->ctx, A->d_blockpart, A->n_launch_blocks, (A->kind == PMH_SPMV_STREAM && A->st_mode != 0) ? A->n_launch_blocks : A->n_rowblocks, 3, ops, e.scal_base, e.halt);
+    return pmh_finalize_partials(A->ctx, A->d_blockpart, A->n_launch_blocks, mpgp_nblocks(A), 3, ops, e.scal_base, e.halt);
   }
   }
   return pmh_set_error(PMH_ERR_ARG, "unknown SpMV epilogue %d", e.kind);
@@ -975,4 +983,49 @@ extern "C" int pmh_csr_mult_transpose_add(pmh_csr A, const double *x, const doub
   PMH_ARG(A);
   if (!A->transpose) PMH_CHK(build_transpose(A));
   return pmh_csr_mult_add(A->transpose, x, y1, y);
+}
+
+// ---- test entries (tests/test_gpu_spmv_paths.py): the plan pmh_csr_create chose, and one product with a given epilogue; nothing inside the solvers calls them ----
+extern "C" int pmh_csr_kernel_info(pmh_csr A, int info[6], unsigned long long *uid)
+{
+  PMH_ARG(A && info);
+  int path, width = 0, c16 = 0, per_block = 0, nblocks = A->n_rowblocks;
+  if (A->l_nchunks) { // the order of launch<>: long rows first (the MPGP epilogue skips them), then ELL, stream, vector
+    path = 4, per_block = A->l_nchunks;
+  } else if (A->kind == PMH_SPMV_STREAM && A->d_ell_val) {
+    path = 0, width = A->ell_w, c16 = A->d_ell_c16 != nullptr, nblocks = A->ell_nrb;
+  } else if (A->kind == PMH_SPMV_STREAM) {
+    path = A->st_rl == 1 ? 1 : 2, width = A->st_rl, c16 = A->d_col16 != nullptr, per_block = A->st_nnzb;
+  } else {
+    path = 3, width = A->lanes_per_row;
+  }
+  info[0] = path, info[1] = width, info[2] = c16, info[3] = per_block, info[4] = nblocks, info[5] = mpgp_nblocks(A);
+  if (uid) *uid = A->uid;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_csr_test_mult_epi(pmh_csr A, int kind, const double *x, const double *y1, const double *g, const double *xx, const double *lb, const double *ub, int halt, double *y,
+                                     double scal_host[3])
+{
+  PMH_ARG(A && kind >= PMH_EPI_NONE && kind <= PMH_EPI_MPGP && (x || !A->ncols) && (y || !A->nrows));
+  PMH_ARG((const void *)x != (const void *)y || !A->nrows);
+  PMH_ARG((kind != PMH_EPI_ADD && kind != PMH_EPI_SUB) || y1 || !A->nrows);
+  PMH_ARG(kind != PMH_EPI_MPGP || (A->nrows == A->ncols && scal_host && ((g && xx) || !A->nrows))); // MPGP: p = x is also the row-indexed operand
+  pmh_ctx      ctx = A->ctx;
+  pmh_spmv_epi e;
+  memset(&e, 0, sizeof(e));
+  e.kind = kind, e.y1 = y1, e.g = g, e.xx = xx, e.lb = lb, e.ub = ub, e.scal_base = PMH_SLOT_TEST_SPMV;
+  int *d_halt = nullptr;
+  if (halt) {
+    const int one = 1;
+    PMH_CHK(pmh_malloc(ctx, sizeof(int), (void **)&d_halt));
+    PMH_CHK(pmh_memcpy_h2d(ctx, d_halt, &one, sizeof(int)));
+    e.halt = d_halt;
+  }
+  int rc = pmh_csr_spmv_launch(A, x, y, e);
+  if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_csr_test_mult_epi: stream synchronisation failed");
+  if (!rc && kind == PMH_EPI_MPGP)
+    for (int k = 0; k < 3; k++) scal_host[k] = ctx->h_scal[PMH_SLOT_TEST_SPMV + k];
+  if (d_halt) pmh_free(ctx, d_halt);
+  return rc;
 }
