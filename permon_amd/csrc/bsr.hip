@@ -3,12 +3,12 @@
 // per 3x3 block it is 8.44 (fp64 values), 4.44 (fp32) or 2.44 (fp16 values, fp32 arithmetic) -- the reduced precisions are
 // used only inside the multigrid preconditioner.  The kernel is HBM bound, so the byte count is the run time.
 //
-// Layout: block rows are grouped into tiles of at most BSR_TB blocks (whole block rows per tile, block count padded to a
-// multiple of the load width W with zero blocks); inside a tile the nine entries of the blocks are stored as nine planes of
-// length nbp (structure of arrays), so that a thread reads entry k of its W adjacent blocks with one W-wide load at plane k:
-// every load of the value stream is lane-contiguous.  One workgroup per tile: each thread multiplies its blocks with the
-// three x entries of the block column, writes the three partial products to LDS, then four lanes per scalar row add the
-// row's partials in a fixed order (deterministic, no atomics).
+// Layout: block rows are grouped into tiles of at most 1024 blocks (512 on the coarse multigrid levels; whole block rows per
+// tile, block count padded to a multiple of the load width W = bsr_w<entry type> with zero blocks); inside a tile the nine
+// entries of the blocks are stored as nine planes of length nbp (structure of arrays), so that a thread reads entry k of its
+// W adjacent blocks with one W-wide load at plane k: every load of the value stream is lane-contiguous.  One workgroup per
+// tile: each thread multiplies its blocks with the three x entries of the block column, writes the three partial products to
+// LDS, then four lanes per scalar row add the row's partials in a fixed order (deterministic, no atomics).
 #include "pmh_internal.h"
 
 #include <algorithm>
@@ -17,18 +17,8 @@
 #include <memory>
 #include <thread>
 
-#define BSR_TB_MAX 2048 // largest tile (blocks)
-
-template <typename TM, int W> struct vecw { typedef TM type __attribute__((ext_vector_type(W))); };
-template <typename TM> struct vecw<TM, 1> { typedef TM type; };
-template <int W> struct ivecw { typedef int type __attribute__((ext_vector_type(W))); };
-template <> struct ivecw<1> { typedef int type; };
-template <typename V, int W> struct lane_of {
-  template <typename S> static __device__ __forceinline__ S get(const V &v, int w) { return (S)v[w]; }
-};
-template <typename V> struct lane_of<V, 1> {
-  template <typename S> static __device__ __forceinline__ S get(const V &v, int) { return (S)v; }
-};
+// adjacent blocks per load: 16-byte loads of fp64 / fp32 entries, 8-byte loads of fp16 entries (profiles/r01_bsr3_tune.txt)
+template <typename TM> constexpr int bsr_w = sizeof(TM) == 8 ? 2 : 4;
 
 // Epilogues.  Besides y = A x (+/- y1) the kernel can finish a Chebyshev/Jacobi smoothing step of the V-cycle on the row it
 // has just summed, which removes the separate vector kernels (and their launches) from the cycle.  All fused variants write
@@ -36,16 +26,17 @@ template <typename V> struct lane_of<V, 1> {
 //   PRE   (x = d0 gathered):  y = c0 d0 + c2 dinv (b - A d0)                      second step of the zero-guess pre-smoother
 //   POST1 (x gathered):       r = dinv (b - A x); d = c0 r; y = x + d             first step of the post-smoother
 //   POST2 (x = d gathered):   y += c1 d + c2 (r - dinv A d); optional fp64 copy   second step of the post-smoother
-// TM: storage type of the matrix entries, T: arithmetic / vector type, W: adjacent blocks per thread-load.
+// TM: storage type of the matrix entries, T: arithmetic / vector type, BSR_TB: blocks per tile.
 // nrep > 1 (congruent diagonal blocks, e.g. the 8 cubes of a structured decomposition): the tiles describe ONE diagonal block and are applied to nrep vector segments of
 // rep_stride entries each.  The replicas of a tile are consecutive workgroups of ONE XCD (every 8th workgroup index), so the tile's matrix bytes leave HBM once and the other
 // nrep - 1 readers find them in that XCD's L2: an eighth of the device copy, an eighth of the host conversion, and a product that no longer streams 8 copies of K.
-template <typename TM, typename T, int EPI, int W, int BSR_TB>
+template <typename TM, typename T, int EPI, int BSR_TB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_bsr3(const int4 *__restrict__ tile_meta, const long long *__restrict__ tile_off, int ntiles, const int *__restrict__ browptr, const int *__restrict__ bcol, const TM *__restrict__ val, T scale,
                                                      const T *__restrict__ x, T *__restrict__ y, pmh_bsr3_epi<T> e, const int *__restrict__ halt, int nrep, long long rep_stride)
 {
-  typedef typename vecw<TM, W>::type VM;
-  typedef typename ivecw<W>::type    VI;
+  constexpr int W = bsr_w<TM>;
+  typedef TM    VM __attribute__((ext_vector_type(W)));
+  typedef int   VI __attribute__((ext_vector_type(W)));
   __shared__ T prod[3][BSR_TB];
   const int    tid   = threadIdx.x;
   const int    chunk = (gridDim.x >> 3) / nrep; // XCD-aware: XCD x works on a contiguous slab of tiles (x stays in its L2), every tile for its nrep replicas in a row
@@ -80,9 +71,9 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_bsr3(const int4 *__restrict__ til
       for (int k = 0; k < 9; k++) a[k] = __builtin_nontemporal_load((const VM *)(v + (size_t)k * nbp + j0));
 #pragma unroll
       for (int w = 0; w < W; w++) {
-        const int cw = lane_of<VI, W>::template get<int>(c, w);
+        const int cw = c[w];
         const T   x0 = x[3 * cw], x1 = x[3 * cw + 1], x2 = x[3 * cw + 2];
-#define A_(k) lane_of<VM, W>::template get<T>(a[k], w)
+#define A_(k) ((T)a[k][w])
         prod[0][j0 + w] = A_(0) * x0 + A_(1) * x1 + A_(2) * x2;
         prod[1][j0 + w] = A_(3) * x0 + A_(4) * x1 + A_(5) * x2;
         prod[2][j0 + w] = A_(6) * x0 + A_(7) * x1 + A_(8) * x2;
@@ -124,17 +115,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_bsr3(const int4 *__restrict__ til
   }
 }
 
-static int bsr_tile(int storage)
-{
-  (void)storage;
-  return 1024; // measured on MI355X for every entry type (profiles/r01_bsr3_tune.txt; the tuning knobs PMH_BSR_TB / PMH_BSR_W went at the end of round 6)
-}
-
-static int bsr_width(int storage)
-{
-  return (storage == PMH_BSR_F64) ? 2 : 4; // 16-byte loads for fp64 / fp32, 8-byte for fp16
-}
-
 // Build from a resident CSR (downloaded once); *out = NULL without error when the matrix has no 3x3 block structure that
 // fits the tile (n not a multiple of 3, or a block row with more blocks than a tile holds).
 int pmh_bsr3_from_csr(pmh_csr A, int storage, pmh_bsr3 *out, int tile, int nrep_hint)
@@ -147,7 +127,8 @@ int pmh_bsr3_from_csr(pmh_csr A, int storage, pmh_bsr3 *out, int tile, int nrep_
   int nrep = (nrep_hint > 1 && !no_share && A->nrows % nrep_hint == 0 && (A->nrows / nrep_hint) % 3 == 0 && A->nnz % nrep_hint == 0) ? nrep_hint : 1;
   const int        n_all = A->nrows;
   int              n = n_all / nrep, nbr = n / 3;
-  const int        tb = (tile == 512 || tile == 1024 || tile == 2048) ? tile : bsr_tile(storage), W = bsr_width(storage);
+  const int        tb = tile == 512 ? 512 : 1024; // 1024 measured best on MI355X for every entry type (profiles/r01_bsr3_tune.txt)
+  const int        W  = storage == PMH_BSR_F64 ? bsr_w<double> : storage == PMH_BSR_F32 ? bsr_w<float> : bsr_w<_Float16>;
   const bool       verbose = getenv("PMH_CONTACT_TIMING") != nullptr && A->nnz > 10000000;
   auto             tnow    = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double           tlast   = tnow();
@@ -306,7 +287,7 @@ int pmh_bsr3_from_csr(pmh_csr A, int storage, pmh_bsr3 *out, int tile, int nrep_
   }
   stage("values into the tile planes");
   pmh_bsr3 B = new pmh_bsr3_s();
-  B->ctx = ctx, B->n = n_all, B->nbr = nbr, B->ntiles = ntiles, B->nblocks = nblocks, B->npad = npad, B->storage = storage, B->W = W, B->tb = tb;
+  B->ctx = ctx, B->n = n_all, B->nbr = nbr, B->ntiles = ntiles, B->nblocks = nblocks, B->npad = npad, B->storage = storage, B->tb = tb;
   B->nrep = nrep, B->rep_rows = n; // nbr, ntiles, nblocks, npad describe ONE replica
   B->scale   = 1.0;
   B->ev_used = 0, B->ev_on = 0, B->ev_seen = 0, B->ev_stride = 1;
@@ -387,8 +368,8 @@ double pmh_bsr3_bytes_blockdiag(pmh_bsr3 B)
 
 int pmh_bsr3_replicas(pmh_bsr3 B) { return B->nrep; }
 
-template <typename TM, typename T, int W, int TB>
-static int bsr3_launch_w(pmh_bsr3 B, const T *x, T *y, int epi, const pmh_bsr3_epi<T> &e, const int *halt)
+template <typename TM, typename T, int TB>
+static int bsr3_launch_tb(pmh_bsr3 B, const T *x, T *y, int epi, const pmh_bsr3_epi<T> &e, const int *halt)
 {
   const dim3       grid((unsigned)(((B->ntiles + 7) / 8) * 8 * B->nrep)), blk(PMH_BLOCK);
   hipStream_t      st = B->ctx->stream;
@@ -397,7 +378,7 @@ static int bsr3_launch_w(pmh_bsr3 B, const T *x, T *y, int epi, const pmh_bsr3_e
   const long long *to = B->d_tile_off;
   const TM        *v  = (const TM *)B->d_val;
   const T          sc = (T)B->scale;
-#define BSR_LAUNCH(EPI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bsr3<TM, T, EPI, W, TB>), grid, blk, 0, st, tb, to, B->ntiles, bp, bc, v, sc, x, y, e, halt, B->nrep, (long long)B->rep_rows)
+#define BSR_LAUNCH(EPI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bsr3<TM, T, EPI, TB>), grid, blk, 0, st, tb, to, B->ntiles, bp, bc, v, sc, x, y, e, halt, B->nrep, (long long)B->rep_rows)
   switch (epi) {
   case PMH_EPI_NONE: BSR_LAUNCH(PMH_EPI_NONE); break;
   case PMH_EPI_ADD: BSR_LAUNCH(PMH_EPI_ADD); break;
@@ -419,16 +400,8 @@ static int bsr3_launch(pmh_bsr3 B, const T *x, T *y, int epi, const pmh_bsr3_epi
   // benchmark's timed region should not pay on all of its ~130 launches per step
   const bool  timed = B->ev_on && (B->ev_seen++ % B->ev_stride == 0) && (size_t)(B->ev_used + 2) <= B->ev.size();
   if (timed) PMH_HIP(hipEventRecord(B->ev[B->ev_used], st));
-#define BSR_W(TBV) \
-  do { \
-    if (B->W == 8 && sizeof(TM) == 2) PMH_CHK((bsr3_launch_w<TM, T, (sizeof(TM) == 2 ? 8 : 4), TBV>(B, x, y, epi, e, halt))); \
-    else if (B->W == 4) PMH_CHK((bsr3_launch_w<TM, T, 4, TBV>(B, x, y, epi, e, halt))); \
-    else if (B->W == 2) PMH_CHK((bsr3_launch_w<TM, T, 2, TBV>(B, x, y, epi, e, halt))); \
-    else PMH_CHK((bsr3_launch_w<TM, T, 1, TBV>(B, x, y, epi, e, halt))); \
-  } while (0)
-  if (B->tb == 2048) BSR_W(2048);
-  else if (B->tb == 1024) BSR_W(1024);
-  else BSR_W(512);
+  if (B->tb == 512) PMH_CHK((bsr3_launch_tb<TM, T, 512>(B, x, y, epi, e, halt)));
+  else PMH_CHK((bsr3_launch_tb<TM, T, 1024>(B, x, y, epi, e, halt)));
   if (timed) {
     PMH_HIP(hipEventRecord(B->ev[B->ev_used + 1], st));
     // operands of the fused epilogue beyond y = A x (one vector = n entries of the arithmetic type):

@@ -89,25 +89,25 @@ static inline bool pmh_comm_on(pmh_ctx c) { return (c->comm || c->hook) && (c->s
 int pmh_comm_allreduce_scalars(pmh_ctx c, double *dscal, int K, const int *ops /* PMH_RED_SUM / PMH_RED_MIN per scalar */); // K device scalars, one grouped exchange
 
 // ---- CSR -----------------------------------------------------------------------------------------------
-enum { PMH_SPMV_STREAM = 0, PMH_SPMV_VECTOR = 1 };
+// the product plan pmh_csr_create picks per matrix, numbered as pmh_csr_kernel_info reports it (spmv.hip)
+enum { PMH_SPMV_ELL = 0, PMH_SPMV_STREAM = 1, PMH_SPMV_MEDIUM = 2, PMH_SPMV_VECTOR = 3, PMH_SPMV_LONG = 4 };
 struct pmh_csr_s {
   pmh_ctx   ctx;
   int       nrows, ncols;
   long long nnz;
   int      *d_rowptr, *d_col;
   double   *d_val;
-  int       kind;          // PMH_SPMV_STREAM (row-blocked, LDS staged) or PMH_SPMV_VECTOR (sub-wave per row)
-  int       lanes_per_row; // VECTOR kind
-  int      *d_rowblocks;   // STREAM kind: row block boundaries [n_rowblocks+1]
-  unsigned short *d_col16; // STREAM kind, short rows: 16-bit column offsets from d_cbase[row block] (nullptr: a row block spans >= 65 536 columns)
+  int       plan;          // PMH_SPMV_*
+  int       width;         // ELL: slots per row; STREAM, MEDIUM, VECTOR: lanes per row; LONG: 0
+  int      *d_rowblocks;   // all plans but VECTOR: row block boundaries [n_rowblocks+1] (ELL: they size its grid; LONG: its MPGP epilogue runs on them)
+  unsigned short *d_col16; // STREAM and LONG (built for ELL too): 16-bit column offsets from d_cbase[row block] (nullptr: a row block spans >= 65 536 columns)
   int      *d_cbase;
-  // STREAM kind, uniformly short rows (<= 8 non-zeros, little padding): slot-major copy per block of 256 rows (k_spmv_ell, no LDS staging)
+  // ELL, uniformly short rows (<= 8 non-zeros, little padding): slot-major copy per block of 256 rows (k_spmv_ell, no LDS staging)
   double         *d_ell_val;
   unsigned short *d_ell_c16; // offsets from d_ell_cbase[row block] (blocks span < 65 536 columns) ...
   int            *d_ell_col; // ... or absolute columns
   int            *d_ell_cbase;
-  int             ell_w, ell_nrb;
-  int       st_nnzb, st_mode, st_nt, st_rl; // STREAM kind: tile size, persistence mode, non-temporal streams
+  int             ell_nrb;
   int       n_rowblocks;
   double   *d_blockpart;   // [4][n_launch_blocks] partials of the fused MPGP epilogue
   int       n_launch_blocks;
@@ -127,6 +127,9 @@ struct pmh_csr_s {
   std::vector<int>        *ev_kind;
   int                      ev_used, ev_pending;
 };
+// lanes per row with which the plan sums a row of A x from the LDS tile or the ELL copy: 1 (ELL, STREAM) or 8 (MEDIUM); 0 for VECTOR and LONG.  A kernel
+// that repeats the product in the same order (the fused G' kernels of qppf.hip) applies only where this is non-zero.
+int pmh_csr_row_lanes(pmh_csr A);
 
 // epilogues of the SpMV kernels
 enum { PMH_EPI_NONE = 0, PMH_EPI_ADD = 1, PMH_EPI_SUB = 2, PMH_EPI_MPGP = 3 };
@@ -269,7 +272,7 @@ int pmh_host_scalar(pmh_ctx ctx, int slot, double *v);                          
 // ---- 3x3-block SpMV (bsr.hip) -------------------------------------------------------------------------------------
 struct pmh_bsr3_s {
   pmh_ctx   ctx;
-  int       n, nbr, ntiles, storage, W, tb; // storage: PMH_BSR_F64 / F32 / F16 (matrix entries); W: blocks per load
+  int       n, nbr, ntiles, storage, tb; // storage: PMH_BSR_F64 / F32 / F16 (matrix entries); tb: blocks per tile (512 or 1024)
   int       nrep, rep_rows;                 // nrep > 1: the tiles hold ONE of nrep congruent diagonal blocks of rep_rows rows each (n = nrep * rep_rows)
   long long nblocks, npad;
   double    scale; // F16: the stored entries are A / scale
@@ -291,7 +294,7 @@ template <typename T> struct pmh_bsr3_epi {
   double  *z64;  // POST2: optional fp64 copy of the result
   T        c0, c1, c2;
 };
-// *out = NULL (no error) if A has no usable 3x3 block structure; tile 0 = default; nrep_hint > 1: A is said to be block diagonal with that many congruent
+// *out = NULL (no error) if A has no usable 3x3 block structure; tile: 512 blocks (coarse multigrid levels), any other value 1024; nrep_hint > 1: A is said to be block diagonal with that many congruent
 // blocks (checked entry by entry: one device copy then serves all)
 int    pmh_bsr3_from_csr(pmh_csr A, int storage, pmh_bsr3 *out, int tile = 0, int nrep_hint = 1);
 int    pmh_bsr3_destroy(pmh_bsr3 B);

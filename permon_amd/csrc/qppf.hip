@@ -610,14 +610,13 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused1d(int n, const int *__re
   }
 }
 
-// the fused path applies when G' is the 8-lanes-per-row stream case (a few dozen entries per row: the rigid-body modes of the
-// subdomains a dual row touches), otherwise the callers keep the unfused sequence
+// the fused path applies when G' is summed in the order of a row-block plan (8 lanes per row for a few dozen entries per row: the rigid-body
+// modes of the subdomains a dual row touches; 1 for shorter rows), otherwise the callers keep the unfused sequence
 static bool gt_fusable(pmh_qppf pf)
 {
   if (!pf->orthonormal || pf->d_inv || pf->m == 0 || !pmh_knobs().gt_fusion) return false;
   if (!pf->G->transpose && pmh_csr_ensure_transpose(pf->G)) return false;
-  const pmh_csr Gt = pf->G->transpose;
-  return Gt->kind == PMH_SPMV_STREAM && (Gt->st_rl == 8 || Gt->st_rl == 1) && Gt->l_nchunks == 0;
+  return pmh_csr_row_lanes(pf->G->transpose) != 0;
 }
 
 // the same for G with its dense (G G')^{-1}: one-lane-per-row G' only (k_gt_dual1 / k_gt_fused1)
@@ -625,8 +624,7 @@ static bool gt_fusable_dense_inverse(pmh_qppf pf)
 {
   if (pf->orthonormal || !pf->d_inv || pf->m == 0 || !pmh_knobs().gt_fusion) return false;
   if (!pf->G->transpose && pmh_csr_ensure_transpose(pf->G)) return false;
-  const pmh_csr Gt = pf->G->transpose;
-  return Gt->kind == PMH_SPMV_STREAM && Gt->st_rl == 1 && Gt->l_nchunks == 0;
+  return pmh_csr_row_lanes(pf->G->transpose) == 1;
 }
 
 // Q v's G' product with its vector epilogue, starting from v: G0 v (chunk sums), then everything else in ONE launch where the folded kernel
@@ -636,7 +634,7 @@ static int qppf_left(pmh_qppf pf, const double *v);
 // the one-launch form (k_gt_fused1d) applies: implicit orthonormalisation, long-row G0, one-lane-per-row G0', m <= 64
 static bool q_fused_dense(pmh_qppf pf)
 {
-  return pf->implicit_orth && pf->G->l_nchunks > 0 && pf->m <= 64 && pf->G->transpose && pf->G->transpose->st_rl == 1;
+  return pf->implicit_orth && pf->G->l_nchunks > 0 && pf->m <= 64 && pf->G->transpose && pmh_csr_row_lanes(pf->G->transpose) == 1;
 }
 // aux_u != nullptr (one-launch form only): G0 aux_u shares the pass over G0, T G0 aux_u -> aux_Gu and its squared norm -> scalar slot aux_slot by workgroup 0.
 // epi (mode 1, one-launch form only): the vector phase folded into the kernel, pin = the operator's input vector.
@@ -674,7 +672,7 @@ static int q_fused(pmh_qppf pf, const double *v, int mode, const double *x, doub
 static int gt_fused(pmh_qppf pf, const double *w, int mode, const double *x, double *y, double *z, double rho)
 {
   const pmh_csr Gt = pf->G->transpose;
-  if (Gt->st_rl == 1)
+  if (pmh_csr_row_lanes(Gt) == 1)
     hipLaunchKernelGGL(k_gt_fused1, dim3((Gt->nrows + PMH_BLOCK - 1) / PMH_BLOCK), dim3(PMH_BLOCK), 0, pf->ctx->stream, Gt->nrows, (const int *)Gt->d_rowptr, (const int *)Gt->d_col, (const double *)Gt->d_val, w,
                        mode, x, y, z, rho);
   else

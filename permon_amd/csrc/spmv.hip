@@ -1,16 +1,17 @@
 // CSR SpMV for gfx950 (fp64 values, int32 indices) -- the MatMult_SeqAIJ role of the PERMON QPS path.
 //
-// Two kernels, chosen per matrix at pmh_csr_create:
-//  * STREAM (short rows, e.g. the 5-point Laplacian of BASELINE configs[1]): row-blocked.  A workgroup
-//    owns a contiguous block of rows whose non-zeros fit PMH_NNZ_PER_BLOCK; it streams val/col with
-//    fully coalesced loads, stages the products val*x[col] in LDS, then one lane per row sums that row's
-//    products from LDS LEFT TO RIGHT -- the same order as PETSc's MatMult_SeqAIJ row loop, so y is
-//    bit-identical to the CPU path.  Rows longer than a block are reduced by the whole workgroup.
-//  * VECTOR (long rows, e.g. 81 nnz/row Q1 elasticity blocks K_i): LPR lanes of a 64-wide wavefront
-//    per row, shuffle-tree reduction.
-// Both map workgroups to rows XCD-aware: the dispatcher deals workgroups round-robin over the 8 XCDs, so
-// workgroup b is given the row block (b%8)*chunk + b/8; each XCD then walks a contiguous slab of rows and
-// the gathered x entries of neighbouring row blocks hit that XCD's own L2 (placement only affects speed).
+// pmh_csr_create picks one plan per matrix from its average row length (the PMH_SPMV_* numbering of pmh_internal.h):
+//  * ELL (uniformly short rows, <= 8 non-zeros): k_spmv_ell, a slot-major device copy, one thread per row.
+//  * STREAM (short rows, e.g. the 5-point Laplacian of BASELINE configs[1]) and MEDIUM (24 < avg <= 256, e.g. the 81 nnz/row Q1
+//    elasticity blocks K_i): k_spmv_stream, row-blocked.  A workgroup owns a contiguous block of rows whose non-zeros fit the tile;
+//    it streams val/col with fully coalesced loads and stages the products val*x[col] in LDS.  STREAM: one lane per row sums that
+//    row's products from LDS LEFT TO RIGHT -- the same order as PETSc's MatMult_SeqAIJ row loop, so y is bit-identical to the CPU
+//    path.  MEDIUM: 8 lanes per row and a shuffle tree.  Rows longer than a tile are reduced by the whole workgroup.
+//  * VECTOR (256 < avg <= 1024): k_spmv_vector, 32 or 64 lanes of a wavefront per row, shuffle-tree reduction.
+//  * LONG (avg > 1024, G of the coarse problem): k_spmv_long_part + k_spmv_long_fin, chunk sums added in chunk order.
+// All map workgroups to rows XCD-aware: the dispatcher deals workgroups round-robin over the 8 XCDs, so workgroup b is
+// given the row block (b%8)*chunk + b/8; each XCD then walks a contiguous slab of rows and the gathered x entries of
+// neighbouring row blocks hit that XCD's own L2 (placement only affects speed).
 // Epilogues fuse the row-local follow-up work of the MPGP iteration into the SpMV (SURVEY 8d phase P1).
 //
 // Algorithmic bytes per SpMV: 12*nnz + 20*nrows (8 B value + 4 B column per non-zero; 4 B row pointer,
@@ -24,6 +25,8 @@
 #include "reduce.h"
 
 #define PMH_MAX_ROWS_PER_BLOCK 1024 // bounds the per-row phase when rows are (nearly) empty, e.g. B' of MATGLUING
+#define PMH_STREAM_NNZB 1024        // entries per row block (LDS tile) of the STREAM plan ...
+#define PMH_MEDIUM_NNZB 2048        // ... and of the MEDIUM plan
 
 struct EpiArgs {
   const double *y1;
@@ -90,27 +93,28 @@ __device__ __forceinline__ int xcd_remap(int bid, int nlaunch)
   return (bid & 7) * chunk + (bid >> 3);
 }
 
-// Row-block stream kernel.  MODE 0: one row block per workgroup (grid = #row blocks, XCD-remapped).
-// MODE 1/2: persistent grid of 8*W workgroups (W <= 256 per XCD, all resident); XCD x owns the contiguous
-// slab of row blocks [x*chunk,(x+1)*chunk) and its W workgroups walk it with stride W, so one XCD works on a
-// window of W consecutive row blocks at a time (x stays in its L2) and only 8*W partials reach the finalise
-// kernel.  MODE 1 double-buffers the LDS tile (one barrier per row block, 2 tiles of LDS), MODE 2 keeps one
-// tile (two barriers).  The next row block's val/col stream is issued before the current per-row phase.
-// NT: val/col are read exactly once per SpMV -> non-temporal loads keep them from evicting x out of L2.
-// C16: the column indices of the stream come as 16-bit offsets from the row block's smallest column (col16 / cbase, built when every row block
+// Row-block stream kernel of the STREAM (RL == 1) and MEDIUM (RL == 8) plans.
+// RL == 1: persistent grid of 8*W workgroups (W <= 256 per XCD, all resident); XCD x owns the contiguous slab of row blocks [x*chunk,(x+1)*chunk)
+// and its W workgroups walk it with stride W, so one XCD works on a window of W consecutive row blocks at a time (x stays in its L2) and only 8*W
+// partials reach the finalise kernel.  The next row block's val/col stream is issued before the current per-row phase, so the one LDS tile takes
+// two barriers per row block.  One lane per row.
+// RL == 8: one row block per workgroup (grid = #row blocks, XCD-remapped), 16-byte val / 8-byte col loads, RL lanes per row.
+// val/col are read exactly once per SpMV -> non-temporal loads keep them from evicting x out of L2.
+// C16 (RL == 1): the column indices of the stream come as 16-bit offsets from the row block's smallest column (col16 / cbase, built when every row block
 // spans < 65 536 columns: banded matrices such as the 5-point Laplacian of configs[1]): 10 instead of 12 bytes per non-zero.
-template <int EPI, int NNZB, int MODE, bool NT, bool VL2, int RL, bool C16 = false>
+template <int EPI, int NNZB, int RL, bool C16 = false>
 __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict__ rowblocks, int nrb, int chunk, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ x, double *__restrict__ y, EpiArgs a, double *__restrict__ part, int ld,
                                                           const unsigned short *__restrict__ col16 = nullptr, const int *__restrict__ cbase = nullptr)
 {
+  static_assert(RL == 1 || (RL == 8 && !C16), "the STREAM and MEDIUM plans");
+  constexpr bool PERSIST = RL == 1, VL2 = RL == 8;
   if (a.halt && *a.halt) return; // uniform: every workgroup reads the same flag
   constexpr int     ITEMS = NNZB / PMH_BLOCK;
-  constexpr int     NBUF  = (MODE == 1) ? 2 : 1;
-  __shared__ double prod[NBUF][NNZB];
+  __shared__ double prod[NNZB];
   __shared__ double red[PMH_BLOCK / 64];
   const int         tid = threadIdx.x;
   int               b, end, W;
-  if (MODE == 0) {
+  if (!PERSIST) {
     b   = xcd_remap(blockIdx.x, gridDim.x);
     end = (b < nrb) ? b + 1 : b;
     W   = 1;
@@ -140,8 +144,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
           dbl2      vv = {0.0, 0.0};
           int2v     cc = {-1, -1};
           if (k < s1) {
-            vv = NT ? __builtin_nontemporal_load((const dbl2 *)(val + k)) : *(const dbl2 *)(val + k);
-            cc = NT ? __builtin_nontemporal_load((const int2v *)(col + k)) : *(const int2v *)(col + k);
+            vv = __builtin_nontemporal_load((const dbl2 *)(val + k));
+            cc = __builtin_nontemporal_load((const int2v *)(col + k));
           }
           c[2 * j]     = (k >= s0 && k < s1) ? cc.x : -1;
           c[2 * j + 1] = (k + 1 < s1) ? cc.y : -1;
@@ -154,14 +158,11 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
         for (int j = 0; j < ITEMS; j++) {
           const int k = s0 + tid + j * PMH_BLOCK;
           if (C16) {
-            c[j] = (k < s1) ? cb + (int)(NT ? __builtin_nontemporal_load(&col16[k]) : col16[k]) : -1;
-            v[j] = (k < s1) ? (NT ? __builtin_nontemporal_load(&val[k]) : val[k]) : 0.0;
-          } else if (NT) {
-            c[j] = (k < s1) ? __builtin_nontemporal_load(&col[k]) : -1;
+            c[j] = (k < s1) ? cb + (int)__builtin_nontemporal_load(&col16[k]) : -1;
             v[j] = (k < s1) ? __builtin_nontemporal_load(&val[k]) : 0.0;
           } else {
-            c[j] = (k < s1) ? col[k] : -1;
-            v[j] = (k < s1) ? val[k] : 0.0;
+            c[j] = (k < s1) ? __builtin_nontemporal_load(&col[k]) : -1;
+            v[j] = (k < s1) ? __builtin_nontemporal_load(&val[k]) : 0.0;
           }
         }
       }
@@ -169,25 +170,23 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
   };
 
   if (b < end) prefetch(b);
-  int buf = 0;
   while (b < end) {
     const int cr0 = r0, cr1 = r1, cs0 = s0, cs1 = s1;
     const int nb  = b + W;
     if (cs1 - cs0 <= NNZB - (VL2 ? 1 : 0)) {
-      double *pr = prod[buf];
-      if (MODE == 2) __syncthreads(); // previous row phase done before the tile is overwritten
+      if (PERSIST) __syncthreads(); // previous row phase done before the tile is overwritten
       if (VL2) {
         const int sh = (cs0 & ~1) - cs0; // 0 or -1
 #pragma unroll
         for (int j = 0; j < ITEMS / 2; j++) {
           const int k = sh + 2 * (tid + j * PMH_BLOCK);
-          if (c[2 * j] >= 0) pr[k] = v[2 * j] * x[c[2 * j]];
-          if (c[2 * j + 1] >= 0) pr[k + 1] = v[2 * j + 1] * x[c[2 * j + 1]];
+          if (c[2 * j] >= 0) prod[k] = v[2 * j] * x[c[2 * j]];
+          if (c[2 * j + 1] >= 0) prod[k + 1] = v[2 * j + 1] * x[c[2 * j + 1]];
         }
       } else {
 #pragma unroll
         for (int j = 0; j < ITEMS; j++)
-          if (c[j] >= 0) pr[tid + j * PMH_BLOCK] = v[j] * x[c[j]];
+          if (c[j] >= 0) prod[tid + j * PMH_BLOCK] = v[j] * x[c[j]];
       }
       // short rows: the lane's first row of this block and the operands of its epilogue (row pointers, p, g, x, lb / ub, y1) are
       // requested BEFORE the barrier, so that their latency runs under the barrier and the LDS phase instead of after it
@@ -203,13 +202,13 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
           fy1 = a.y1[fr];
         }
       }
-      if (MODE != 0 && nb < end) prefetch(nb); // next block's stream in flight during this block's row phase
+      if (PERSIST && nb < end) prefetch(nb); // next block's stream in flight during this block's row phase
       __syncthreads();
       if (RL == 1) {
         // one lane per row, left-to-right sum (bit-identical to MatMult_SeqAIJ)
         if (fr < cr1) {
           double sum = 0.0;
-          for (int k = fk0; k < fk1; k++) sum += pr[k];
+          for (int k = fk0; k < fk1; k++) sum += prod[k];
           if (EPI == PMH_EPI_NONE) {
             y[fr] = sum;
           } else if (EPI == PMH_EPI_ADD) {
@@ -227,7 +226,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
         for (int r = fr + PMH_BLOCK; r < cr1; r += PMH_BLOCK) { // (nearly) empty rows: more rows than lanes in a block
           const int k0 = rowptr[r] - cs0, k1 = rowptr[r + 1] - cs0;
           double    sum = 0.0;
-          for (int k = k0; k < k1; k++) sum += pr[k];
+          for (int k = k0; k < k1; k++) sum += prod[k];
           epi_row<EPI, false>(r, sum, x, y, a, acc0, acc1, amin);
         }
       } else {
@@ -238,25 +237,24 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
           double    sum = 0.0;
           if (r < cr1) {
             const int k0 = rowptr[r] - cs0, k1 = rowptr[r + 1] - cs0;
-            for (int k = k0 + lane; k < k1; k += RL) sum += pr[k];
+            for (int k = k0 + lane; k < k1; k += RL) sum += prod[k];
           }
 #pragma unroll
           for (int o = RL / 2; o > 0; o >>= 1) sum += __shfl_down(sum, o, RL);
           if (r < cr1 && lane == 0) epi_row<EPI, false>(r, sum, x, y, a, acc0, acc1, amin);
         }
       }
-      if (MODE == 1) buf ^= 1;
     } else {
       // a single row longer than the LDS tile: the whole workgroup strides over it
       double sum = 0.0;
       for (int k = cs0 + tid; k < cs1; k += PMH_BLOCK) sum += val[k] * x[col[k]];
       sum = pmh_block_reduce<PMH_RED_SUM>(sum, red);
       if (tid == 0) epi_row<EPI>(cr0, sum, x, y, a, acc0, acc1, amin);
-      if (MODE != 0 && nb < end) prefetch(nb);
+      if (PERSIST && nb < end) prefetch(nb);
     }
     b = nb;
   }
-  if (MODE == 0) {
+  if (!PERSIST) {
     const int lb_ = xcd_remap(blockIdx.x, gridDim.x);
     if (lb_ < nrb) epi_finish<EPI>(acc0, acc1, amin, red, part, ld, lb_);
   } else {
@@ -267,7 +265,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
 // Uniformly short rows (the 3-5 non-zeros per row of configs[1]'s 5-point Laplacian): a device-private slot-major copy -- per block of 256 rows, slot k of
 // row r at [block][k][r], columns as 16-bit offsets from the block's smallest column where that fits -- lets one thread own one row with fully coalesced
 // loads and NO LDS staging or barrier; the row is summed left to right over its own entries only (bit-identical to MatMult_SeqAIJ and to the stream
-// kernel), padded slots are loaded but not added.  Same persistent grid and XCD slabs as the stream kernel (mode 2), same epilogues.
+// kernel), padded slots are loaded but not added.  Same persistent grid and XCD slabs as the stream kernel (RL == 1), same epilogues.
 template <int EPI, bool C16, int W>
 __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_ell(int nrows, int nrb, int chunk, const int *__restrict__ rowptr, const double *__restrict__ ev, const unsigned short *__restrict__ ec16,
                                                         const int *__restrict__ ecol, const int *__restrict__ ecbase, const double *__restrict__ x, double *__restrict__ y, EpiArgs a,
@@ -302,7 +300,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_ell(int nrows, int nrb, int 
   epi_finish<EPI>(acc0, acc1, amin, red, part, ld, blockIdx.x);
 }
 
-template <int EPI, int LPR, bool NT>
+template <int EPI, int LPR>
 __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_vector(int nrows, int nblk, int nlaunch, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ x, double *__restrict__ y, EpiArgs a, double *__restrict__ part, int ld)
 {
   __shared__ double red[PMH_BLOCK / 64];
@@ -316,7 +314,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_vector(int nrows, int nblk, 
   double        sum = 0.0;
   if (r < nrows) {
     const int k0 = rowptr[r], k1 = rowptr[r + 1];
-    for (int k = k0 + lane; k < k1; k += LPR) sum += (NT ? __builtin_nontemporal_load(&val[k]) : val[k]) * x[NT ? __builtin_nontemporal_load(&col[k]) : col[k]];
+    for (int k = k0 + lane; k < k1; k += LPR) sum += __builtin_nontemporal_load(&val[k]) * x[__builtin_nontemporal_load(&col[k])];
   }
 #pragma unroll
   for (int o = LPR / 2; o > 0; o >>= 1) sum += __shfl_down(sum, o, LPR);
@@ -330,7 +328,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_vector(int nrows, int nblk, 
 // workgroup per chunk (fixed-tree block reduction), and a second small kernel adds the chunk sums of a row in chunk order
 // and applies the epilogue -- deterministic, ~2 x 5 us.
 #define PMH_LONG_CHUNK 4096
-template <bool NT>
 __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_long_part(const int *__restrict__ chunks, const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ x, const int *__restrict__ halt, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
@@ -343,8 +340,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_long_part(const int *__restr
     int    c[16];
 #pragma unroll
     for (int e = 0; e < 16; e++) {
-      v[e] = NT ? __builtin_nontemporal_load(&val[k + e * PMH_BLOCK]) : val[k + e * PMH_BLOCK];
-      c[e] = NT ? __builtin_nontemporal_load(&col[k + e * PMH_BLOCK]) : col[k + e * PMH_BLOCK];
+      v[e] = __builtin_nontemporal_load(&val[k + e * PMH_BLOCK]);
+      c[e] = __builtin_nontemporal_load(&col[k + e * PMH_BLOCK]);
     }
     double xv[16];
 #pragma unroll
@@ -355,7 +352,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_long_part(const int *__restr
   }
   for (; k + 3 * PMH_BLOCK < k1; k += 4 * PMH_BLOCK) {
 #pragma unroll
-    for (int j = 0; j < 4; j++) s[j] += (NT ? __builtin_nontemporal_load(&val[k + j * PMH_BLOCK]) : val[k + j * PMH_BLOCK]) * x[NT ? __builtin_nontemporal_load(&col[k + j * PMH_BLOCK]) : col[k + j * PMH_BLOCK]];
+    for (int j = 0; j < 4; j++) s[j] += __builtin_nontemporal_load(&val[k + j * PMH_BLOCK]) * x[__builtin_nontemporal_load(&col[k + j * PMH_BLOCK])];
   }
 #pragma unroll
   for (int j = 0; j < 3; j++) { // at most three strides are left
@@ -367,7 +364,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_long_part(const int *__restr
 }
 
 // The chunk sums of A x and A x2 in ONE pass over A (SMALXE's G0 u next to the projector's G0 p): every sum exactly as k_spmv_long_part takes it
-template <bool NT>
 __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_long_part2(const int *__restrict__ chunks, const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ x, const double *__restrict__ x2,
                                                                double *__restrict__ part, double *__restrict__ part2)
 {
@@ -380,8 +376,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_long_part2(const int *__rest
     int    c[16];
 #pragma unroll
     for (int e = 0; e < 16; e++) {
-      v[e] = NT ? __builtin_nontemporal_load(&val[k + e * PMH_BLOCK]) : val[k + e * PMH_BLOCK];
-      c[e] = NT ? __builtin_nontemporal_load(&col[k + e * PMH_BLOCK]) : col[k + e * PMH_BLOCK];
+      v[e] = __builtin_nontemporal_load(&val[k + e * PMH_BLOCK]);
+      c[e] = __builtin_nontemporal_load(&col[k + e * PMH_BLOCK]);
     }
     double xv[16], xw[16];
 #pragma unroll
@@ -393,8 +389,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_long_part2(const int *__rest
   for (; k + 3 * PMH_BLOCK < k1; k += 4 * PMH_BLOCK) {
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const double vv = NT ? __builtin_nontemporal_load(&val[k + j * PMH_BLOCK]) : val[k + j * PMH_BLOCK];
-      const int    cc = NT ? __builtin_nontemporal_load(&col[k + j * PMH_BLOCK]) : col[k + j * PMH_BLOCK];
+      const double vv = __builtin_nontemporal_load(&val[k + j * PMH_BLOCK]);
+      const int    cc = __builtin_nontemporal_load(&col[k + j * PMH_BLOCK]);
       s[j] += vv * x[cc], s2[j] += vv * x2[cc];
     }
   }
@@ -515,19 +511,24 @@ extern "C" int pmh_csr_create(pmh_ctx ctx, int nrows, int ncols, const int *rowp
   PMH_CHK(pmh_memcpy_h2d(ctx, A->d_val, val, sizeof(double) * (size_t)nnz));
 
   const double avg = nrows ? (double)nnz / nrows : 0.0;
-  int medium_stream = 1, m_nnzb = 2048, m_mode = 0, m_nt = 3; // measured best on 81 nnz/row K_i (round 4 sweep at 43^3 x 8 distinct blocks: nt 3 = non-temporal 16-byte value / 8-byte column loads 0.391 ms, nt 1 0.406; 1024 / 4096 entries per row block 0.41 / 0.43)
-  const bool medium = avg > 24.0 && avg <= 256.0 && medium_stream;
-  if (avg <= 24.0 || avg > 1024.0 || medium) { // short rows: LDS-staged row blocks; very long rows (G of the coarse problem): one workgroup per row
-    A->kind = PMH_SPMV_STREAM;
-    // tile (entries per row block), mode (0 one row block per workgroup / 2 persistent grid), non-temporal mask: chosen from the sweeps of rounds 1-4 (profiles/r01_spmv_tune_*.txt;
-    // the tuning knobs PMH_SPMV_TUNE / _MTUNE / _VTUNE went at the end of round 6)
-    A->st_nnzb = 1024, A->st_mode = 2, A->st_nt = 1, A->st_rl = 1;
-    if (medium) A->st_nnzb = m_nnzb, A->st_mode = m_mode, A->st_nt = m_nt, A->st_rl = 8;
+  // the plan, from the sweeps of rounds 1-4 (profiles/r01_spmv_tune_*.txt).  MEDIUM was measured best on 81 nnz/row K_i (round 4 sweep at 43^3 x 8 distinct
+  // blocks: non-temporal 16-byte value / 8-byte column loads 0.391 ms, scalar ones 0.406; 1024 / 4096 entries per row block 0.41 / 0.43).  Very long rows
+  // (G of the coarse problem) take the LONG plan below, and the STREAM row blocks for the MPGP epilogue.
+  if (avg > 256.0 && avg <= 1024.0) {
+    A->plan            = PMH_SPMV_VECTOR;
+    A->width           = avg <= 512.0 ? 32 : 64; // lanes per row
+    const int rpb      = PMH_BLOCK / A->width;
+    A->n_rowblocks     = (nrows + rpb - 1) / rpb;
+    A->n_launch_blocks = ((A->n_rowblocks + 7) / 8) * 8;
+  } else {
+    const bool medium = avg > 24.0 && avg <= 256.0;
+    A->plan           = medium ? PMH_SPMV_MEDIUM : PMH_SPMV_STREAM;
+    A->width          = medium ? 8 : 1; // lanes per row
     std::vector<int> rb;
-    A->n_rowblocks = build_rowblocks(nrows, rowptr, A->st_nnzb - 1, rb); // -1: room for the aligned-down start of the 16-byte load variant
+    A->n_rowblocks = build_rowblocks(nrows, rowptr, (medium ? PMH_MEDIUM_NNZB : PMH_STREAM_NNZB) - 1, rb); // -1: room for the aligned-down start of the 16-byte load variant
     PMH_HIP(hipMalloc((void **)&A->d_rowblocks, sizeof(int) * rb.size()));
     PMH_CHK(pmh_memcpy_h2d(ctx, A->d_rowblocks, rb.data(), sizeof(int) * rb.size()));
-    if (A->st_rl == 1 && !(A->st_nt & 2) && A->st_nnzb <= 2048) {
+    if (!medium) {
       // 16-bit column offsets per row block where every block spans < 65 536 columns (device-private copy next to the int32 indices)
       std::vector<int>            cb((size_t)A->n_rowblocks, 0);
       std::vector<unsigned short> c16((size_t)nnz + 8, 0);
@@ -547,7 +548,7 @@ extern "C" int pmh_csr_create(pmh_ctx ctx, int nrows, int ncols, const int *rowp
         PMH_CHK(pmh_memcpy_h2d(ctx, A->d_cbase, cb.data(), sizeof(int) * cb.size()));
       }
     }
-    if (A->st_rl == 1 && A->st_mode == 2 && nrows > 0) {
+    if (!medium && nrows > 0) {
       // slot-major copy for uniformly short rows (k_spmv_ell): <= 8 non-zeros per row and at most 25 % padding
       int wmax = 0;
       for (int r = 0; r < nrows; r++) wmax = std::max(wmax, rowptr[r + 1] - rowptr[r]);
@@ -586,24 +587,13 @@ extern "C" int pmh_csr_create(pmh_ctx ctx, int nrows, int ncols, const int *rowp
           PMH_HIP(hipMalloc((void **)&A->d_ell_col, sizeof(int) * ec.size()));
           PMH_CHK(pmh_memcpy_h2d(ctx, A->d_ell_col, ec.data(), sizeof(int) * ec.size()));
         }
-        A->ell_w = wmax, A->ell_nrb = nrb_e;
+        A->plan = PMH_SPMV_ELL, A->width = wmax, A->ell_nrb = nrb_e;
       }
     }
-    const int chunk = (A->n_rowblocks + 7) / 8; // row blocks per XCD
-    if (A->st_mode == 0) {
-      A->n_launch_blocks = 8 * (chunk > 0 ? chunk : 1);
-    } else {
-      const int wcap     = (A->st_mode == 1 || A->st_nnzb == 4096) ? 128 : 256; // resident workgroups per XCD (LDS bound)
-      const int W        = chunk < wcap ? (chunk > 0 ? chunk : 1) : wcap;
-      A->n_launch_blocks = 8 * W;
-    }
-  } else {
-    A->kind          = PMH_SPMV_VECTOR;
-    A->lanes_per_row = (avg <= 48.0) ? 8 : (avg <= 160.0 ? 16 : (avg <= 512.0 ? 32 : 64));
-    A->st_nt         = 1;
-    const int rpb    = PMH_BLOCK / A->lanes_per_row;
-    A->n_rowblocks   = (nrows + rpb - 1) / rpb;
-    A->n_launch_blocks = ((A->n_rowblocks + 7) / 8) * 8;
+    // MEDIUM: one workgroup per row block; otherwise (ELL too) a persistent grid of at most 256 resident workgroups per XCD (LDS bound)
+    const int chunk    = (A->n_rowblocks + 7) / 8; // row blocks per XCD
+    const int W        = chunk > 0 ? chunk : 1;
+    A->n_launch_blocks = 8 * (medium ? W : std::min(W, 256));
   }
   PMH_HIP(hipMalloc((void **)&A->d_blockpart, sizeof(double) * 3 * (size_t)(A->n_launch_blocks ? A->n_launch_blocks : 8)));
   if (avg > 1024.0 && !getenv("PMH_SPMV_NO_LONG")) { // chunk table of the long-row kernels (plain / ADD / SUB epilogues)
@@ -622,11 +612,14 @@ extern "C" int pmh_csr_create(pmh_ctx ctx, int nrows, int ncols, const int *rowp
       PMH_HIP(hipMalloc((void **)&A->d_lpart, sizeof(double) * (size_t)A->l_nchunks));
       PMH_CHK(pmh_memcpy_h2d(ctx, A->d_lchunks, ch.data(), sizeof(int) * ch.size()));
       PMH_CHK(pmh_memcpy_h2d(ctx, A->d_lrow, lrow.data(), sizeof(int) * lrow.size()));
+      A->plan = PMH_SPMV_LONG, A->width = 0;
     }
   }
   *out = A;
   return PMH_SUCCESS;
 }
+
+int pmh_csr_row_lanes(pmh_csr A) { return (A->plan == PMH_SPMV_ELL || A->plan == PMH_SPMV_STREAM) ? 1 : A->plan == PMH_SPMV_MEDIUM ? 8 : 0; }
 
 extern "C" int pmh_csr_destroy(pmh_csr A)
 {
@@ -673,26 +666,28 @@ static int launch(pmh_csr A, const double *x, double *y, const EpiArgs &a)
   pmh_ctx   ctx = A->ctx;
   const int nl  = A->n_launch_blocks;
   if (A->nrows == 0) return PMH_SUCCESS;
-  if (A->l_nchunks && EPI != PMH_EPI_MPGP) {
-    const bool long_nt = true; // (non-temporal matrix stream of the long-row kernels)
-    if (long_nt) hipLaunchKernelGGL(k_spmv_long_part<true>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, a.halt, A->d_lpart);
-    else hipLaunchKernelGGL(k_spmv_long_part<false>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, a.halt, A->d_lpart);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_long_fin<EPI>), dim3((A->nrows + PMH_BLOCK - 1) / PMH_BLOCK), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, (const int *)A->d_lrow, (const double *)A->d_lpart, x, y, a);
-    PMH_HIP(hipGetLastError());
-    return PMH_SUCCESS;
+  if constexpr (EPI != PMH_EPI_MPGP) { // (a long-row matrix runs the fused MPGP epilogue on its STREAM row blocks)
+    if (A->plan == PMH_SPMV_LONG) {
+      hipLaunchKernelGGL(k_spmv_long_part, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, a.halt, A->d_lpart);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_long_fin<EPI>), dim3((A->nrows + PMH_BLOCK - 1) / PMH_BLOCK), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, (const int *)A->d_lrow, (const double *)A->d_lpart, x, y, a);
+      PMH_HIP(hipGetLastError());
+      return PMH_SUCCESS;
+    }
   }
-  if (A->kind == PMH_SPMV_STREAM && A->d_ell_val) {
-    const int chunk = (A->ell_nrb + 7) / 8;
+  const int chunk = (A->n_rowblocks + 7) / 8;
+  switch (A->plan) {
+  case PMH_SPMV_ELL: {
+    const int echunk = (A->ell_nrb + 7) / 8;
 #define ELL_LAUNCH(WW) \
   do { \
     if (A->d_ell_c16) \
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_ell<EPI, true, WW>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->ell_nrb, chunk, (const int *)A->d_rowptr, (const double *)A->d_ell_val, \
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_ell<EPI, true, WW>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->ell_nrb, echunk, (const int *)A->d_rowptr, (const double *)A->d_ell_val, \
                          (const unsigned short *)A->d_ell_c16, (const int *)nullptr, (const int *)A->d_ell_cbase, x, y, a, A->d_blockpart, nl); \
     else \
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_ell<EPI, false, WW>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->ell_nrb, chunk, (const int *)A->d_rowptr, (const double *)A->d_ell_val, \
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_ell<EPI, false, WW>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->ell_nrb, echunk, (const int *)A->d_rowptr, (const double *)A->d_ell_val, \
                          (const unsigned short *)nullptr, (const int *)A->d_ell_col, (const int *)A->d_ell_cbase, x, y, a, A->d_blockpart, nl); \
   } while (0)
-    switch (A->ell_w) {
+    switch (A->width) {
     case 1: ELL_LAUNCH(1); break;
     case 2: ELL_LAUNCH(2); break;
     case 3: ELL_LAUNCH(3); break;
@@ -702,62 +697,27 @@ static int launch(pmh_csr A, const double *x, double *y, const EpiArgs &a)
     case 7: ELL_LAUNCH(7); break;
     default: ELL_LAUNCH(8); break;
     }
-    PMH_HIP(hipGetLastError());
-    return PMH_SUCCESS;
-  }
-  if (A->kind == PMH_SPMV_STREAM) {
-#define ST_LAUNCH(NNZB, MODE, NT) \
-  do { \
-    if constexpr (RLV == 1 && (((NT)&2) == 0) && NNZB <= 2048) { \
-      if (A->d_col16) { \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_stream<EPI, NNZB, MODE, ((NT)&1) != 0, false, 1, true>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->d_rowblocks, A->n_rowblocks, (A->n_rowblocks + 7) / 8, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl, \
-                           (const unsigned short *)A->d_col16, (const int *)A->d_cbase); \
-        break; \
-      } \
-    } \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_stream<EPI, NNZB, MODE, ((NT)&1) != 0, ((NT)&2) != 0, RLV>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->d_rowblocks, A->n_rowblocks, (A->n_rowblocks + 7) / 8, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl, \
-                       (const unsigned short *)nullptr, (const int *)nullptr); \
-  } while (0)
-#define ST_MODE(NNZB) \
-  if (A->st_rl == 8) { \
-    constexpr int RLV = 8; \
-    ST_MODE_(NNZB) \
-  } else { \
-    constexpr int RLV = 1; \
-    ST_MODE_(NNZB) \
-  }
-#define ST_MODE_(NNZB) \
-  switch (A->st_mode * 4 + (A->st_nt & 3)) { \
-  case 0: ST_LAUNCH(NNZB, 0, 0); break; \
-  case 1: ST_LAUNCH(NNZB, 0, 1); break; \
-  case 3: ST_LAUNCH(NNZB, 0, 3); break; \
-  case 8: ST_LAUNCH(NNZB, 2, 0); break; \
-  case 9: ST_LAUNCH(NNZB, 2, 1); break; \
-  case 11: ST_LAUNCH(NNZB, 2, 3); break; \
-  default: return pmh_set_error(PMH_ERR_ARG, "PMH_SPMV_TUNE: unsupported mode/nt combination"); \
-  }
-    if (A->st_nnzb == 512) {
-      ST_MODE(512)
-    } else if (A->st_nnzb == 1024) {
-      ST_MODE(1024)
-    } else if (A->st_nnzb == 2048) {
-      ST_MODE(2048)
-    } else {
-      ST_MODE(4096)
-    }
-  } else {
-#define VEC_CASE(L) \
-  case L: \
-    if (A->st_nt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_vector<EPI, L, true>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->n_rowblocks, nl, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl); \
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_vector<EPI, L, false>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->n_rowblocks, nl, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl); \
+#undef ELL_LAUNCH
     break;
-    switch (A->lanes_per_row) {
-      VEC_CASE(8)
-      VEC_CASE(16)
-      VEC_CASE(32)
-      VEC_CASE(64)
-    default: return pmh_set_error(PMH_ERR_STATE, "bad lanes_per_row %d", A->lanes_per_row);
-    }
+  }
+  case PMH_SPMV_STREAM:
+  case PMH_SPMV_LONG:
+    if (A->d_col16)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_stream<EPI, PMH_STREAM_NNZB, 1, true>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->d_rowblocks, A->n_rowblocks, chunk, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl,
+                         (const unsigned short *)A->d_col16, (const int *)A->d_cbase);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_stream<EPI, PMH_STREAM_NNZB, 1>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->d_rowblocks, A->n_rowblocks, chunk, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl,
+                         (const unsigned short *)nullptr, (const int *)nullptr);
+    break;
+  case PMH_SPMV_MEDIUM:
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_stream<EPI, PMH_MEDIUM_NNZB, 8>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->d_rowblocks, A->n_rowblocks, chunk, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl,
+                       (const unsigned short *)nullptr, (const int *)nullptr);
+    break;
+  case PMH_SPMV_VECTOR:
+    if (A->width == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_vector<EPI, 32>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->n_rowblocks, nl, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_vector<EPI, 64>), dim3(nl), dim3(PMH_BLOCK), 0, ctx->stream, A->nrows, A->n_rowblocks, nl, A->d_rowptr, A->d_col, A->d_val, x, y, a, A->d_blockpart, nl);
+    break;
+  default: return pmh_set_error(PMH_ERR_STATE, "bad SpMV plan %d", A->plan);
   }
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
@@ -770,7 +730,7 @@ static int spmv_dispatch(pmh_csr A, const double *x, double *y, const pmh_spmv_e
 static int mpgp_nblocks(pmh_csr A)
 {
   if (A->nrows == 0) return 0;
-  return (A->kind == PMH_SPMV_STREAM && A->st_mode != 0) ? A->n_launch_blocks : A->n_rowblocks;
+  return (A->plan == PMH_SPMV_MEDIUM || A->plan == PMH_SPMV_VECTOR) ? A->n_rowblocks : A->n_launch_blocks; // one workgroup per row block, or a persistent grid
 }
 
 int pmh_csr_spmv_launch(pmh_csr A, const double *x, double *y, const pmh_spmv_epi &e)
@@ -879,9 +839,7 @@ extern "C" int pmh_csr_mult(pmh_csr A, const double *x, double *y)
 int pmh_csr_mult_partials(pmh_csr A, const double *x, const int **lrow, const double **part)
 {
   PMH_ARG(A && x && lrow && part && A->l_nchunks > 0);
-  const bool long_nt = true; // (non-temporal matrix stream of the long-row kernels)
-  if (long_nt) hipLaunchKernelGGL(k_spmv_long_part<true>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, A->ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, (const int *)nullptr, A->d_lpart);
-  else hipLaunchKernelGGL(k_spmv_long_part<false>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, A->ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, (const int *)nullptr, A->d_lpart);
+  hipLaunchKernelGGL(k_spmv_long_part, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, A->ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, (const int *)nullptr, A->d_lpart);
   PMH_HIP(hipGetLastError());
   *lrow = A->d_lrow, *part = A->d_lpart;
   return PMH_SUCCESS;
@@ -891,9 +849,7 @@ int pmh_csr_mult_partials2(pmh_csr A, const double *x, const double *x2, const i
 {
   PMH_ARG(A && x && x2 && lrow && part && part2 && A->l_nchunks > 0);
   if (!A->d_lpart2) PMH_CHK(pmh_malloc(A->ctx, sizeof(double) * (size_t)A->l_nchunks, (void **)&A->d_lpart2));
-  const bool long_nt = true; // (non-temporal matrix stream of the long-row kernels)
-  if (long_nt) hipLaunchKernelGGL(k_spmv_long_part2<true>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, A->ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, x2, A->d_lpart, A->d_lpart2);
-  else hipLaunchKernelGGL(k_spmv_long_part2<false>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, A->ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, x2, A->d_lpart, A->d_lpart2);
+  hipLaunchKernelGGL(k_spmv_long_part2, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, A->ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, x2, A->d_lpart, A->d_lpart2);
   PMH_HIP(hipGetLastError());
   *lrow = A->d_lrow, *part = A->d_lpart, *part2 = A->d_lpart2;
   return PMH_SUCCESS;
@@ -907,9 +863,7 @@ int pmh_csr_mult_then_dense(pmh_csr A, const double *x, const double *Mt, double
   pmh_ctx      ctx = A->ctx;
   const size_t lds = sizeof(double) * (size_t)A->nrows;
   if (A->l_nchunks) {
-    const bool long_nt = true; // (non-temporal matrix stream of the long-row kernels)
-    if (long_nt) hipLaunchKernelGGL(k_spmv_long_part<true>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, (const int *)nullptr, A->d_lpart);
-    else hipLaunchKernelGGL(k_spmv_long_part<false>, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, (const int *)nullptr, A->d_lpart);
+    hipLaunchKernelGGL(k_spmv_long_part, dim3(A->l_nchunks), dim3(PMH_BLOCK), 0, ctx->stream, (const int *)A->d_lchunks, (const int *)A->d_col, (const double *)A->d_val, x, (const int *)nullptr, A->d_lpart);
     hipLaunchKernelGGL(k_rows_then_dense, dim3(1), dim3(PMH_BLOCK), lds, ctx->stream, A->nrows, (const int *)A->d_lrow, (const double *)A->d_lpart, Mt, y, nd, nh);
   } else {
     PMH_CHK(pmh_csr_mult(A, x, tmp));
@@ -989,17 +943,12 @@ extern "C" int pmh_csr_mult_transpose_add(pmh_csr A, const double *x, const doub
 extern "C" int pmh_csr_kernel_info(pmh_csr A, int info[6], unsigned long long *uid)
 {
   PMH_ARG(A && info);
-  int path, width = 0, c16 = 0, per_block = 0, nblocks = A->n_rowblocks;
-  if (A->l_nchunks) { // the order of launch<>: long rows first (the MPGP epilogue skips them), then ELL, stream, vector
-    path = 4, per_block = A->l_nchunks;
-  } else if (A->kind == PMH_SPMV_STREAM && A->d_ell_val) {
-    path = 0, width = A->ell_w, c16 = A->d_ell_c16 != nullptr, nblocks = A->ell_nrb;
-  } else if (A->kind == PMH_SPMV_STREAM) {
-    path = A->st_rl == 1 ? 1 : 2, width = A->st_rl, c16 = A->d_col16 != nullptr, per_block = A->st_nnzb;
-  } else {
-    path = 3, width = A->lanes_per_row;
-  }
-  info[0] = path, info[1] = width, info[2] = c16, info[3] = per_block, info[4] = nblocks, info[5] = mpgp_nblocks(A);
+  int c16 = 0, per_block = 0, nblocks = A->n_rowblocks;
+  if (A->plan == PMH_SPMV_LONG) per_block = A->l_nchunks; // (the MPGP epilogue runs on the STREAM row blocks)
+  else if (A->plan == PMH_SPMV_ELL) c16 = A->d_ell_c16 != nullptr, nblocks = A->ell_nrb;
+  else if (A->plan == PMH_SPMV_STREAM) c16 = A->d_col16 != nullptr, per_block = PMH_STREAM_NNZB;
+  else if (A->plan == PMH_SPMV_MEDIUM) per_block = PMH_MEDIUM_NNZB;
+  info[0] = A->plan, info[1] = A->width, info[2] = c16, info[3] = per_block, info[4] = nblocks, info[5] = mpgp_nblocks(A);
   if (uid) *uid = A->uid;
   return PMH_SUCCESS;
 }
