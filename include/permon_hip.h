@@ -220,6 +220,12 @@ typedef struct pmh_qppf_s *pmh_qppf;
    of G v.  The right-hand side of the constraint transforms with pmh_qppf_orth_rhs (e = T e0, host vectors of length m). */
 int pmh_qppf_create(pmh_ctx ctx, pmh_csr G, int orthonormal, pmh_qppf *pf);
 int pmh_qppf_orth_rhs(pmh_qppf pf, const double *e0_host, double *e_host);
+/* One-row projector (the role of the reference's MATONEROW, src/mat/impls/onerow/onerow.c): G = a' for a dense device vector a of n doubles (borrowed), m = 1.
+   No CSR and no host factorisation: G G' = a'a is one reduction at creation.  Every pmh_qppf_apply_* works on it (G v: one dot product; G's: one scaled copy;
+   Q v = a (a'v) / (a'a)); the rows count as orthonormal where |a'a - 1| <= n eps.  Under a communicator a is sharded as the vectors are and the dot product is
+   joined by pmh_comm_allreduce_sum.  pmh_op_create_penalized over the SVM dual operator and such a projector whose row is a multiple of the labels folds
+   rho G'G into the operator (pmh_op_svm_dual_set_terms' rank-one term) instead of applying the projector */
+int pmh_qppf_create_onerow(pmh_ctx ctx, const double *a_dev, int n, pmh_qppf *pf);
 int pmh_qppf_destroy(pmh_qppf pf);
 /* set-up cost of the coarse problem: GG' assembly on the matrix cores (ms, flops = 2 Mp^2 n) and the host Cholesky + inverse (ms) */
 int pmh_qppf_setup_stats(pmh_qppf pf, double *ggt_mfma_ms, double *ggt_flops, double *host_inverse_ms);
@@ -458,6 +464,10 @@ int pmh_op_create_svm_dual(pmh_ctx ctx, int n_local, int d, const double *X_dev,
    application also does the first pass of the next one wherever the MPGP step allows it -- svm.hip, "paired passes" -- so a run of expansion steps costs 2 passes
    per step instead of 4): what a bandwidth figure for this operator has to be computed from */
 int pmh_op_svm_dual_passes(pmh_op op, long long *passes);
+/* the augmented Hessian H + shift I + sigma y y' (shift, sigma >= 0; both 0: the plain operator, its kernels and its bits).  shift = 1/C is the L2-loss dual's
+   Hessian; sigma y y' is what penalising the bias equality y'a = 0 adds.  One more column sum, s = sum_i y_i a_i, travels with the d of w: no extra pass over X,
+   and every fused epilogue of the plain operator carries both terms */
+int pmh_op_svm_dual_set_terms(pmh_op op, double shift, double sigma);
 
 /* ---- QPS SMALXE (src/qps/impls/smalxe/smalxe.c) -------------------------------------------------------- */
 typedef struct {
@@ -519,6 +529,55 @@ typedef struct {
 } pmh_qps_opts;
 int pmh_qps_default_opts(pmh_qps_opts *q);
 int pmh_qps_set_from_options(const char *options, const char *prefix, pmh_qps_opts *q, pmh_mpgp_opts *m, pmh_smalxe_opts *s /* or NULL */, char *unknown, int unknown_cap);
+
+/* ---- SVM front end: train, model, predict (the role of PermonSVM, a separate repository the reference's README names; its sources were not available when
+ * this was written, so the option names below are this library's own and no compatibility with PermonSVM's is claimed) ----------------------------------------
+ * Dual problems, H = diag(y) X X' diag(y), X n x d row-major on the device (one sample per row), y in {-1, +1}:
+ *   L1: min 1/2 a'Ha - 1'a,          0 <= a <= C      (primal 1/2 |w|^2 + C sum xi)
+ *   L2: min 1/2 a'(H + I/C)a - 1'a,  0 <= a           (primal 1/2 |w|^2 + C/2 sum xi^2)
+ *   bias: additionally y'a = 0, posed as (y / sqrt(n))'a = 0 (a row of unit length).
+ * Without bias the QP goes to MPGP; with bias to SMALXE over a one-row projector (pmh_qppf_create_onerow), whose penalty rho B'B the SVM operator absorbs as its
+ * rank-one term: the same passes over X per inner iteration as without bias.
+ * Model: w = X'(y o a); b = mean over the free support vectors of (y_i - x_i . w), free meaning astol < a_i and, for L1, a_i < C - astol (astol: the inner
+ * MPGP's, 10 eps).  If no sample is free, b is taken from the equality's Lagrange multiplier: with the Lagrangian 1/2 a'Ha - 1'a + mu (y / sqrt(n))'a that SMALXE
+ * works on (it keeps B'mu = mu y / sqrt(n)), stationarity in a free sample reads y_i - x_i . w = mu / sqrt(n), so b = mu / sqrt(n).  Both are reported
+ * (pmh_svm_stats::b_free, ::b_multiplier); they agree to the tolerance of the solve.  Decision function: x . w + b, label +1 where it is >= 0, else -1. */
+enum { PMH_SVM_LOSS_L1 = 0, PMH_SVM_LOSS_L2 = 1 };
+typedef struct {
+  int             loss_type;  /* -svm_loss_type L1 | L2 */
+  double          C;          /* -svm_C, > 0 */
+  int             bias;       /* -svm_bias 0 | 1 */
+  pmh_qps_opts    qps;        /* -qps_rtol / _atol / _divtol / _max_it: the tolerances of the solver that trains (MPGP, or the outer SMALXE) */
+  pmh_mpgp_opts   mpgp;       /* -qps_mpgp_*: the solver without bias */
+  pmh_smalxe_opts smalxe;     /* -qps_smalxe_* and -smalxe_qps_*: the solver with bias and its inner MPGP */
+} pmh_svm_opts;
+typedef struct {
+  int       reason;                            /* converged reason of the training solve */
+  int       outer_iterations, inner_iterations; /* SMALXE's outer and accumulated inner iterations (no bias: 0 and MPGP's iterations) */
+  int       nmv, ncg, nexp, nprop;             /* Hessian multiplications and step types of the (inner) MPGP */
+  long long passes_X;                          /* passes over X of the solve (pmh_op_svm_dual_passes before and after) */
+  long long n_sv, n_free_sv;                   /* support vectors (a_i > astol), free ones */
+  double    yTalpha;                           /* y'a of the returned dual solution */
+  double    b, b_free, b_multiplier;           /* the bias returned, the mean over the free support vectors (NaN: none), the multiplier's value */
+  double    rho, normBu, rnorm;                /* SMALXE's final penalty, |B a| and residual norm (no bias: 0, 0, MPGP's) */
+} pmh_svm_stats;
+typedef struct pmh_svm_s *pmh_svm;
+int pmh_svm_default_opts(pmh_svm_opts *o);
+/* -svm_loss_type, -svm_C, -svm_bias here; everything else through pmh_qps_set_from_options with the empty prefix.  An unknown loss type is PMH_ERR_ARG with a message */
+int pmh_svm_set_from_options(const char *options, pmh_svm_opts *o, char *unknown, int unknown_cap);
+/* X_dev (n_local x d, d <= 256) and y_dev are borrowed: the caller keeps them alive and unchanged.  Under a communicator the samples are sharded by rows */
+int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *svm);
+int pmh_svm_train(pmh_svm svm);                                     /* from a = 0: MPGP (no bias) or SMALXE + MPGP (bias), then the model */
+int pmh_svm_get_model(pmh_svm svm, double *w_host /* d doubles, or NULL */, double *b /* or NULL */);
+int pmh_svm_get_dual(pmh_svm svm, double *alpha_dev);               /* n_local doubles */
+int pmh_svm_get_stats(pmh_svm svm, pmh_svm_stats *st);
+int pmh_svm_get_solver(pmh_svm svm, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh_smalxe *smalxe); /* borrowed; any pointer may be NULL, a solver not in use comes back NULL */
+/* one pass over the n samples of X_dev: scores_dev[i] = x_i . w + b, labels_dev[i] = +-1 (either may be NULL) */
+int pmh_svm_predict(pmh_svm svm, int n, const double *X_dev, double *scores_dev, double *labels_dev);
+/* one pass: counts = (TP, FP, TN, FN) of the predicted labels against y_dev (summed over the ranks under a communicator) */
+int pmh_svm_test(pmh_svm svm, int n, const double *X_dev, const double *y_dev, long long counts[4]);
+int pmh_svm_destroy(pmh_svm svm);
+
 
 /* ---- PC for the inner KSP of MATINV: multigrid V-cycle (PCMG semantics) ----------------------------------------
  * The reference's iterative MATINV applies K^+ with a PETSc KSP whose PC is chosen by -mat_inv_pc_type

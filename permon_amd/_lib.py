@@ -71,6 +71,18 @@ class QpsOpts(C.Structure):
     ]
 
 
+class SvmOpts(C.Structure):  # pmh_svm_opts
+    _fields_ = [("loss_type", C.c_int), ("C", C.c_double), ("bias", C.c_int), ("qps", QpsOpts), ("mpgp", MpgpOpts), ("smalxe", SmalxeOpts)]
+
+
+class SvmStats(C.Structure):  # pmh_svm_stats
+    _fields_ = [("reason", C.c_int), ("outer_iterations", C.c_int), ("inner_iterations", C.c_int),
+                ("nmv", C.c_int), ("ncg", C.c_int), ("nexp", C.c_int), ("nprop", C.c_int),
+                ("passes_X", C.c_longlong), ("n_sv", C.c_longlong), ("n_free_sv", C.c_longlong),
+                ("yTalpha", C.c_double), ("b", C.c_double), ("b_free", C.c_double), ("b_multiplier", C.c_double),
+                ("rho", C.c_double), ("normBu", C.c_double), ("rnorm", C.c_double)]
+
+
 class KspFetiOpts(C.Structure):
     _fields_ = [("gluing_type", C.c_int), ("scale", C.c_int), ("exclude_dirichlet", C.c_int), ("regularize", C.c_int), ("kplus_left", C.c_int), ("project", C.c_int),
                 ("E_orth_type", C.c_int), ("lumped_pc", C.c_int), ("regularize_rho", C.c_double),
@@ -237,6 +249,19 @@ _PROTOS = {
     "pmh_qpt_feti_chain_kkt": [vp, vp, vp, vp, vp, vp],
     "pmh_op_create_svm_dual": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)],
     "pmh_op_svm_dual_passes": [vp, C.POINTER(C.c_longlong)],
+    "pmh_op_svm_dual_set_terms": [vp, C.c_double, C.c_double],
+    "pmh_qppf_create_onerow": [vp, vp, C.c_int, C.POINTER(vp)],
+    "pmh_svm_default_opts": [C.POINTER(SvmOpts)],
+    "pmh_svm_set_from_options": [C.c_char_p, C.POINTER(SvmOpts), C.c_char_p, C.c_int],
+    "pmh_svm_create": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvmOpts), C.POINTER(vp)],
+    "pmh_svm_train": [vp],
+    "pmh_svm_get_model": [vp, vp, c_double_p],
+    "pmh_svm_get_dual": [vp, vp],
+    "pmh_svm_get_stats": [vp, C.POINTER(SvmStats)],
+    "pmh_svm_get_solver": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+    "pmh_svm_predict": [vp, C.c_int, vp, vp, vp],
+    "pmh_svm_test": [vp, C.c_int, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_destroy": [vp],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],
     "pmh_smalxe_destroy": [vp],

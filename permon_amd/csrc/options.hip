@@ -328,6 +328,36 @@ extern "C" int pmh_qps_set_from_options(const char *options, const char *prefix,
   return PMH_SUCCESS;
 }
 
+// Options of the SVM front end (svm_train.hip): -svm_loss_type L1|L2, -svm_C, -svm_bias here; every other key goes through pmh_qps_set_from_options with the
+// empty prefix, unchanged (-qps_rtol ..., -qps_mpgp_*, -qps_smalxe_*, -smalxe_qps_*).  The -svm_* names are this library's own.
+extern "C" int pmh_svm_set_from_options(const char *options, pmh_svm_opts *o, char *unknown, int unknown_cap)
+{
+  PMH_ARG(options && o);
+  std::vector<Token> toks;
+  PMH_CHK(tokenize(options, toks));
+  std::string rest;
+  for (const Token &t : toks) {
+    if (t.key == "svm_loss_type") {
+      if (!t.has_val) return pmh_set_error(PMH_ERR_ARG, "options: -%s needs a value", t.key.c_str());
+      const std::string v = lower(t.val);
+      if (v == "l1") o->loss_type = PMH_SVM_LOSS_L1;
+      else if (v == "l2") o->loss_type = PMH_SVM_LOSS_L2;
+      else return pmh_set_error(PMH_ERR_ARG, "options: unknown SVM loss type \"%s\" for -svm_loss_type (L1 | L2)", t.val.c_str());
+    } else if (t.key == "svm_C") {
+      double c;
+      if (get_real(t, &c)) return PMH_ERR_ARG;
+      if (!(c > 0.0)) return pmh_set_error(PMH_ERR_ARG, "options: -svm_C %s, must be positive", t.val.c_str());
+      o->C = c;
+    } else if (t.key == "svm_bias") {
+      if (get_bool(t, &o->bias)) return PMH_ERR_ARG;
+    } else {
+      rest += (rest.empty() ? "-" : " -") + t.key;
+      if (t.has_val) rest += " " + t.val;
+    }
+  }
+  return pmh_qps_set_from_options(rest.c_str(), "", &o->qps, &o->mpgp, &o->smalxe, unknown, unknown_cap);
+}
+
 // QPSCreate defaults (qps.c:73-76); type "" = QPSSetDefaultType decides at set-up (qps.c:422-455)
 extern "C" int pmh_qps_default_opts(pmh_qps_opts *q)
 {

@@ -234,9 +234,19 @@ struct pmh_qppf_s {
   std::vector<double> h_T;
   double *G_left, *Gt_right;
   double  ggt_mfma_ms, host_inverse_ms; // set-up timings (pmh_qppf_setup_stats)
+  // one-row projector (pmh_qppf_create_onerow, onerow.hip: the MATONEROW role): G = row' is a dense device vector, no CSR (G == nullptr), m = 1;
+  // row_aat = row'row (all-reduced under a communicator); or_part [PMH_MAX_VEC_BLOCKS] / or_s [1]: partial sums and the finished dot product
+  int           onerow = 0;
+  const double *row = nullptr;
+  double        row_aat = 0.0;
+  double       *or_part = nullptr, *or_s = nullptr;
   // QPPFApplyQ's (v,state) -> Qv cache (qppf.c:464-467,495-498) is realised structurally: the penalised
   // operator over a projected operator computes Q x once and reuses it (see PenalizedOp::mult).
 };
+
+// one-row projector (onerow.hip): out[0] = coef * row'v (device scalar; joined across the ranks), and y = x_or_null -/+ (coef s[0]) row
+int pmh_onerow_dot(pmh_qppf pf, const double *v, double coef, double *out);
+int pmh_onerow_scaled_row(pmh_qppf pf, const double *s, double coef, const double *v /* nullptr: y = (coef s) row; else y = v - (coef s) row */, double *y);
 
 // ---- reductions ---------------------------------------------------------------------------------------------
 enum { PMH_RED_SUM = 0, PMH_RED_MIN = 1 };

@@ -13,6 +13,7 @@
 #include "reduce.h"
 #include "box_inline.h"
 #include "dualchain.h"
+#include "svm_internal.h"
 
 
 // y = M x, M dense m x m row-major; one 64-lane wavefront per row
@@ -270,14 +271,20 @@ extern "C" int pmh_qppf_destroy(pmh_qppf pf)
   pmh_free(pf->ctx, pf->Gt_right);
   if (pf->d_inv) pmh_free(pf->ctx, pf->d_inv);
   if (pf->d_Tt) pmh_free(pf->ctx, pf->d_Tt), pmh_free(pf->ctx, pf->d_S), pmh_free(pf->ctx, pf->tmp_m);
+  if (pf->or_part) pmh_free(pf->ctx, pf->or_part);
+  if (pf->or_s) pmh_free(pf->ctx, pf->or_s);
   delete pf;
   return PMH_SUCCESS;
 }
+
+// one-row projector: (G G')^{-1} as the generic code applies it (orthonormal rows: the identity)
+static inline double onerow_inv(pmh_qppf pf) { return pf->orthonormal ? 1.0 : 1.0 / pf->row_aat; }
 
 extern "C" int pmh_qppf_apply_G(pmh_qppf pf, const double *v, double *Gv)
 {
   PMH_ARG(pf);
   if (pf->m == 0) return PMH_SUCCESS;
+  if (pf->onerow) return pmh_onerow_dot(pf, v, 1.0, Gv);
   if (pf->implicit_orth) return pmh_csr_mult_then_dense(pf->G, v, pf->d_Tt, pf->tmp_m, Gv); // (T G0) v
   return pmh_csr_mult(pf->G, v, Gv);
 }
@@ -303,6 +310,10 @@ extern "C" int pmh_qppf_apply_CP(pmh_qppf pf, const double *x, double *y)
 {
   PMH_ARG(pf);
   if (pf->m == 0) return PMH_SUCCESS;
+  if (pf->onerow && !pf->orthonormal) {
+    PMH_CHK(pmh_vec_copy(pf->ctx, 1, x, y));
+    return pmh_vec_scale(pf->ctx, 1, y, onerow_inv(pf));
+  }
   if (!pf->d_inv) return pmh_vec_copy(pf->ctx, pf->m, x, y);
   hipLaunchKernelGGL(k_dense_gemv, dim3((pf->m + 3) / 4), dim3(PMH_BLOCK), 0, pf->ctx->stream, pf->m, pf->d_inv, x, y);
   PMH_HIP(hipGetLastError());
@@ -314,6 +325,10 @@ extern "C" int pmh_qppf_apply_Q(pmh_qppf pf, const double *v, double *Qv)
 {
   PMH_ARG(pf && (const void *)v != (const void *)Qv);
   if (pf->m == 0) return pmh_vec_set(pf->ctx, pf->n, Qv, 0.0);
+  if (pf->onerow) {
+    PMH_CHK(pmh_onerow_dot(pf, v, 1.0, pf->or_s));
+    return pmh_onerow_scaled_row(pf, pf->or_s, onerow_inv(pf), nullptr, Qv);
+  }
   PMH_CHK(qppf_left(pf, v));
   if (pf->d_inv) {
     PMH_CHK(pmh_qppf_apply_CP(pf, pf->G_left, pf->Gt_right));
@@ -325,6 +340,11 @@ extern "C" int pmh_qppf_apply_Q(pmh_qppf pf, const double *v, double *Qv)
 // QPPFApplyP qppf.c:563-575: Pv = v - Qv  (VecAYPX(Pv,-1,v))
 extern "C" int pmh_qppf_apply_P(pmh_qppf pf, const double *v, double *Pv)
 {
+  if (pf && pf->onerow && pf->m) {
+    PMH_ARG((const void *)v != (const void *)Pv);
+    PMH_CHK(pmh_onerow_dot(pf, v, 1.0, pf->or_s));
+    return pmh_onerow_scaled_row(pf, pf->or_s, onerow_inv(pf), v, Pv);
+  }
   PMH_CHK(pmh_qppf_apply_Q(pf, v, Pv));
   return pmh_vec_aypx(pf->ctx, pf->n, Pv, -1.0, v);
 }
@@ -335,6 +355,10 @@ extern "C" int pmh_qppf_apply_GtG(pmh_qppf pf, const double *v, double *y)
   PMH_ARG(pf);
   if (pf->orthonormal) return pmh_qppf_apply_Q(pf, v, y);
   if (pf->m == 0) return pmh_vec_set(pf->ctx, pf->n, y, 0.0);
+  if (pf->onerow) {
+    PMH_CHK(pmh_onerow_dot(pf, v, 1.0, pf->or_s));
+    return pmh_onerow_scaled_row(pf, pf->or_s, 1.0, nullptr, y);
+  }
   PMH_CHK(pmh_csr_mult(pf->G, v, pf->G_left));
   return pmh_csr_mult_transpose(pf->G, pf->G_left, y);
 }
@@ -344,6 +368,7 @@ extern "C" int pmh_qppf_apply_halfQ(pmh_qppf pf, const double *x, double *y)
 {
   PMH_ARG(pf);
   if (pf->m == 0) return PMH_SUCCESS;
+  if (pf->onerow) return pmh_onerow_dot(pf, x, onerow_inv(pf), y);
   if (pf->implicit_orth) return pmh_csr_mult_then_dense(pf->G, x, pf->d_Tt, pf->tmp_m, y); // (GG')^{-1} = I for G = T G0: y = T G0 x
   PMH_CHK(pmh_csr_mult(pf->G, x, pf->G_left));
   return pmh_qppf_apply_CP(pf, pf->G_left, y);
@@ -354,6 +379,7 @@ extern "C" int pmh_qppf_apply_halfQ_transpose(pmh_qppf pf, const double *x, doub
 {
   PMH_ARG(pf);
   if (pf->m == 0) return pmh_vec_set(pf->ctx, pf->n, y, 0.0);
+  if (pf->onerow) return pmh_onerow_scaled_row(pf, x, onerow_inv(pf), nullptr, y);
   if (pf->implicit_orth) { // (T G0)' x = G0' (T' x); k_dense_gemv takes a row-major matrix: T' row-major = d_Tt
     hipLaunchKernelGGL(k_dense_gemv, dim3((pf->m + 3) / 4), dim3(PMH_BLOCK), 0, pf->ctx->stream, pf->m, (const double *)pf->d_Tt, x, pf->Gt_right);
     PMH_HIP(hipGetLastError());
@@ -614,7 +640,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused1d(int n, const int *__re
 // modes of the subdomains a dual row touches; 1 for shorter rows), otherwise the callers keep the unfused sequence
 static bool gt_fusable(pmh_qppf pf)
 {
-  if (!pf->orthonormal || pf->d_inv || pf->m == 0 || !pmh_knobs().gt_fusion) return false;
+  if (pf->onerow || !pf->orthonormal || pf->d_inv || pf->m == 0 || !pmh_knobs().gt_fusion) return false;
   if (!pf->G->transpose && pmh_csr_ensure_transpose(pf->G)) return false;
   return pmh_csr_row_lanes(pf->G->transpose) != 0;
 }
@@ -622,7 +648,7 @@ static bool gt_fusable(pmh_qppf pf)
 // the same for G with its dense (G G')^{-1}: one-lane-per-row G' only (k_gt_dual1 / k_gt_fused1)
 static bool gt_fusable_dense_inverse(pmh_qppf pf)
 {
-  if (pf->orthonormal || !pf->d_inv || pf->m == 0 || !pmh_knobs().gt_fusion) return false;
+  if (pf->onerow || pf->orthonormal || !pf->d_inv || pf->m == 0 || !pmh_knobs().gt_fusion) return false;
   if (!pf->G->transpose && pmh_csr_ensure_transpose(pf->G)) return false;
   return pmh_csr_row_lanes(pf->G->transpose) == 1;
 }
@@ -745,7 +771,7 @@ struct PenalizedOp : pmh_op_s {
     if (dc_state < 0) {
       dc_state        = 0;
       ProjectedOp *pa = dynamic_cast<ProjectedOp *>(A);
-      if (chain_allowed && pa && pa->pf == pf && pa->symmetric && pmh_dc_create(pf, pa->A, &dc) == PMH_SUCCESS && dc) {
+      if (chain_allowed && !pf->onerow && pa && pa->pf == pf && pa->symmetric && pmh_dc_create(pf, pa->A, &dc) == PMH_SUCCESS && dc) {
         dc_state = 1;
         if (norm_Gu) (void)pmh_dc_set_norm_target(dc, norm_Gu, norm_slot);
       }
@@ -754,6 +780,35 @@ struct PenalizedOp : pmh_op_s {
   }
   double *norm_Gu = nullptr;
   int     norm_slot = -1;
+  // The dense-row SVM operator under a one-row projector whose row is c y (the bias equality y'a = 0): rho G'G = rho c^2 y y' is the operator's own rank-one
+  // term -- the product is the operator's, with sigma_fold set around it (the operator on its own, e.g. in SMALXE's power iterations, stays unpenalised), every
+  // fused epilogue it has stays on, and ||G u|| = |c sum_i y_i u_i| comes out of the pass that holds the iterate's rows (svm.hip aux_*).  rho is read at every
+  // product, so pmh_op_penalized_set_penalty needs nothing more.  Probed once, at the first product (one pass over the row and the labels)
+  SvmDualOp *sv = nullptr;
+  double     sv_c = 0.0;
+  int        sv_state = -1;
+  SvmDualOp *fold()
+  {
+    if (sv_state < 0) {
+      sv_state     = 0;
+      SvmDualOp *o = pf->onerow ? dynamic_cast<SvmDualOp *>(A) : nullptr;
+      if (o && pmh_svm_op_row_is_labels(o, pf, &sv_c) == 1) sv = o, sv_state = 1;
+    }
+    return sv_state == 1 ? sv : nullptr;
+  }
+  int spec_expansion_ready() override { return sv_state == 1 ? sv->spec_expansion_ready() : 0; }
+  int fold_apply(const double *x, double *y, const pmh_vec_epi *e)
+  {
+    const double *au = aux_u;
+    sv->sigma_fold   = rho * sv_c * sv_c;
+    sv->aux_done     = 0;
+    if (au) sv->aux_u = au, sv->aux_Gu = aux_Gu, sv->aux_slot = aux_slot, sv->aux_c = sv_c;
+    const int rc   = e ? sv->mult_epi(x, y, *e) : sv->mult(x, y);
+    sv->sigma_fold = 0.0, sv->aux_u = nullptr;
+    if (rc != PMH_EPI_UNSUPPORTED) aux_u = nullptr; // (a declined epilogue is followed by the plain product of the same vector: the request waits for it)
+    if (sv->aux_done) aux_done = 1, sv->aux_done = 0;
+    return rc;
+  }
   int  emit_begin(const double *x, const double *p, pmh_emit_args *ea) override { return chain() ? pmh_dc_emit_begin(dc, x, p, ea) : PMH_EPI_UNSUPPORTED; }
   void emit_invalidate() override
   {
@@ -779,6 +834,7 @@ struct PenalizedOp : pmh_op_s {
   {
     // (the chain leaves its block partials per 1024-entry tile for the HOST to sum: a caller that finalises on the device -- row-distributed scalars, e.hosted == NULL --
     // counts on one partial per workgroup of the streaming Vec kernels' grid, so it gets the separate vector kernels behind the chain's plain product instead)
+    if (fold()) return pmh_knobs().vec_epi ? fold_apply(x, y, &e) : PMH_EPI_UNSUPPORTED;
     if (chain()) return e.hosted ? pmh_dc_apply(dc, x, y, rho, &e) : PMH_EPI_UNSUPPORTED;
     if (!pmh_knobs().vec_epi) return PMH_EPI_UNSUPPORTED; // A/B: the separate vector kernels
     if (!fused_dense() || n > PMH_MAX_VEC_BLOCKS * PMH_BLOCK || pmh_vec_grid(n) != (n + PMH_BLOCK - 1) / PMH_BLOCK) return PMH_EPI_UNSUPPORTED;
@@ -793,6 +849,7 @@ struct PenalizedOp : pmh_op_s {
   // MatMult_Penalized matpenalized.c:12-22: y = BtB x; y *= rho; y = y + A x
   int mult(const double *x, double *y) override
   {
+    if (fold()) return fold_apply(x, y, nullptr);
     ProjectedOp *pa = dynamic_cast<ProjectedOp *>(A);
     if (chain()) return pmh_dc_apply(dc, x, y, rho, nullptr);
     if (fused_dense()) return mult_fused_dense(x, y, nullptr);
@@ -891,6 +948,10 @@ int pmh_op_penalized_arm_aux_normG(pmh_op op, const double *u, double *Gu, int s
   PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
   PMH_ARG(o && u && Gu && slot >= 0 && slot < PMH_NSCAL);
   o->aux_done = 0;
+  if (o->fold()) { // the SVM operator's own pass serves it (one GPU; otherwise the request is dropped there and the caller's own launches follow)
+    o->aux_u = u, o->aux_Gu = Gu, o->aux_slot = slot;
+    return PMH_SUCCESS;
+  }
   if (o->dc || !o->fused_dense()) return PMH_SUCCESS; // not armed: the caller's own launches follow
   o->aux_u = u, o->aux_Gu = Gu, o->aux_slot = slot;
   return PMH_SUCCESS;

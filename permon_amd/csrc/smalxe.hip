@@ -121,11 +121,11 @@ static int prefetch_normBu(void *user)
 
 // pre-P1 hook (pmh_mpgp_set_pre_p1_hook): the iterate u is final when the inner MPGP enqueues the next A_rho p; G0 u then shares the pass over G0 with the
 // projector's G0 p and T G0 u / its squared norm are finished inside the projector's kernel (the one-launch projector form with m <= 64 only -- the condition
-// under which pmh_qppf_apply_G_norm2 takes the same two kernels on its own)
+// under which pmh_qppf_apply_G_norm2 takes the same two kernels on its own; or the one-row equality over the SVM operator, whose own pass then sums it, qppf.hip)
 static int arm_normBu(void *user)
 {
   pmh_smalxe s = (pmh_smalxe)user;
-  if (s->o.be_implicit || s->pf->m == 0 || !(s->pf->implicit_orth && s->pf->m <= 64) || !pmh_knobs().smalxe_prefetch) return PMH_SUCCESS;
+  if (s->o.be_implicit || s->pf->m == 0 || !((s->pf->implicit_orth && s->pf->m <= 64) || s->pf->onerow) || !pmh_knobs().smalxe_prefetch) return PMH_SUCCESS;
   return pmh_op_penalized_arm_aux_normG(s->A_inner, s->u, s->Bu, PMH_SLOT_NORMBU2);
 }
 

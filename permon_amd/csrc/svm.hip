@@ -9,42 +9,17 @@
 #include "reduce.h"
 #include "box_inline.h"
 
-#define SVM_KMAX 4 // d <= 64 * SVM_KMAX
-// a launch that streams X once (counted: pmh_op_svm_dual_passes)
-#define SVM_PASS(...)                 \
-  do {                                \
-    npass++;                          \
-    hipLaunchKernelGGL(__VA_ARGS__);  \
-  } while (0)
-
-struct SvmDualOp : pmh_op_s {
-  int           d;
-  const double *X, *y;
-  double       *w, *part; // w: d; part: [nblocks][d]
-  int           nblocks;
-  int           mult(const double *a, double *Ha) override;
-  // paired passes (d == 64, one GPU): see the block before k_svm_x64_grad
-  int           mult_epi(const double *in, double *out, const pmh_vec_epi &e) override;
-  int           spec_expansion_ready() override { return next_is == NEXT_XSPEC; }
-  enum { NEXT_NONE = 0, NEXT_P, NEXT_XSPEC };
-  // what part_next holds the partial sums of X'(y o v) for: the p of the last gradient split / the prepared expansion iterate
-  int           next_is = NEXT_NONE;
-  const double *next_p = nullptr;
-  double       *part_next = nullptr, *feas_part = nullptr, *d_afeas = nullptr, *x_spec = nullptr;
-  int           grid_epi = 0;
-  long long     npass = 0; // passes over X so far
-  ~SvmDualOp() override
-  {
-    pmh_free(ctx, w);
-    pmh_free(ctx, part);
-    if (part_next) pmh_free(ctx, part_next), pmh_free(ctx, feas_part), pmh_free(ctx, d_afeas), pmh_free(ctx, x_spec);
-  }
-};
+#include "svm_internal.h"
 
 // pass 1: per-workgroup partial of w = sum_i (y_i a_i) x_i ; one wavefront per row, lane j owns columns j, j+64, ...
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part)
+// AUG: also s = sum_i y_i a_i (-> spart[workgroup]) and, where u is given, sum_i y_i u_i (-> upart[workgroup]); every lane of a wave holds the same two sums
+template <int AUG>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
+                                                      double *__restrict__ spart, const double *__restrict__ u, double *__restrict__ upart)
 {
   __shared__ double lds[PMH_BLOCK / 64][64 * SVM_KMAX];
+  __shared__ double sred[AUG ? 2 : 1][AUG ? PMH_BLOCK / 64 : 1]; // (used by the augmented form only)
+  double            as = 0.0, au = 0.0;
   const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   double            acc[SVM_KMAX];
@@ -53,12 +28,17 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double
   for (long long i = gw; i < n; i += nw) {
     const double  s  = y[i] * a[i];
     const double *xr = X + (size_t)i * d;
+    if (AUG) {
+      as += s;
+      if (u) au += y[i] * u[i];
+    }
 #pragma unroll
     for (int k = 0; k < SVM_KMAX; k++) {
       const int c = lane + 64 * k;
       if (c < d) acc[k] += s * __builtin_nontemporal_load(&xr[c]);
     }
   }
+  if (AUG && lane == 0) sred[0][wave] = as, sred[AUG][wave] = au;
 #pragma unroll
   for (int k = 0; k < SVM_KMAX; k++) lds[wave][lane + 64 * k] = acc[k];
   __syncthreads();
@@ -68,22 +48,38 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double
     for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v += lds[wv][c];
     part[(size_t)blockIdx.x * d + c] = v;
   }
+  if (AUG && threadIdx.x == 0) {
+    double v0 = sred[0][0], v1 = sred[AUG][0];
+#pragma unroll
+    for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v0 += sred[0][wv], v1 += sred[AUG][wv];
+    spart[blockIdx.x] = v0;
+    if (upart) upart[blockIdx.x] = v1;
+  }
 }
 
-// w[c] = sum over workgroups of part[b][c], one wavefront per column, fixed order
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w)
+// w[c] = sum over workgroups of part[b][c], one wavefront per column, fixed order; spart != nullptr: one column more, w[d] = sum over workgroups of spart[b]
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart)
 {
   const int lane = threadIdx.x & 63, c = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
-  if (c >= d) return;
+  if (c >= d + (spart ? 1 : 0)) return;
   double v = 0.0;
+  if (c == d) {
+    for (int b = lane; b < nblocks; b += 64) v += spart[b];
+  } else
   for (int b = lane; b < nblocks; b += 64) v += part[(size_t)b * d + c];
   v = pmh_wave_sum(v);
   if (lane == 0) w[c] = v;
 }
 
-// pass 2: (H a)_i = y_i (x_i . w)
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha)
+// the augmented row result: (y_i (x_i . w) + (sigma s) y_i) + shift a_i, in this order (s = w[d])
+static __device__ __forceinline__ double svm_aug_row(double yi, double dot, double sS, double shift, double ai) { return (yi * dot + sS * yi) + shift * ai; }
+
+// pass 2: (H a)_i = y_i (x_i . w); AUG: + sigma s y_i + shift a_i
+template <int AUG>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
+                                                     const double *__restrict__ a, double sigma, double shift)
 {
+  const double sS = AUG ? sigma * w[d] : 0.0;
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   double          wr[SVM_KMAX];
@@ -98,16 +94,19 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double 
       if (c < d) s += __builtin_nontemporal_load(&xr[c]) * wr[k];
     }
     s = pmh_wave_sum(s);
-    if (lane == 0) Ha[i] = y[i] * s;
+    if (lane == 0) Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s;
   }
 }
 
 // ---- d == 64 fast path: 16-byte loads, two rows per wave-instruction (lanes 0-31 row r, lanes 32-63 row r+1), 4-fold unroll ----
 typedef double dbl2 __attribute__((ext_vector_type(2))); // native 16-byte vector: accepted by the non-temporal builtins
-template <int SVM_UNR>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part)
+template <int SVM_UNR, int AUG>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
+                                                        double *__restrict__ spart, const double *__restrict__ uu, double *__restrict__ upart)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
+  __shared__ double red[PMH_BLOCK / 64];
+  double            as = 0.0, au = 0.0; // AUG: sum_i y_i a_i, sum_i y_i u_i, taken by the first lane of each half-wave for its rows
   const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
   const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   double            a0 = 0.0, a1 = 0.0;
@@ -120,6 +119,10 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__r
       const bool      ok = i < n;
       v[u] = ok ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
       s[u] = ok ? y[i] * a[i] : 0.0;
+      if (AUG && l2 == 0) {
+        as += s[u];
+        if (uu && ok) au += y[i] * uu[i];
+      }
     }
 #pragma unroll
     for (int u = 0; u < SVM_UNR; u++) {
@@ -141,11 +144,20 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__r
     for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v += lds[wv][threadIdx.x];
     part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
   }
+  if (AUG) {
+    const double r0 = pmh_block_reduce<PMH_RED_SUM>(as, red), r1 = pmh_block_reduce<PMH_RED_SUM>(au, red);
+    if (threadIdx.x == 0) {
+      spart[blockIdx.x] = r0;
+      if (upart) upart[blockIdx.x] = r1;
+    }
+  }
 }
 
-template <int SVM_UNR>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha)
+template <int SVM_UNR, int AUG>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
+                                                       const double *__restrict__ a, double sigma, double shift)
 {
+  const double sS = AUG ? sigma * w[64] : 0.0;
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   const dbl2      wr = ((const dbl2 *)w)[l2];
@@ -162,7 +174,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__re
       double          s = v[u].x * wr.x + v[u].y * wr.y;
 #pragma unroll
       for (int o = 16; o > 0; o >>= 1) s += __shfl_down(s, o, 32);
-      if (l2 == 0 && i < n) Ha[i] = y[i] * s;
+      if (l2 == 0 && i < n) Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s;
     }
   }
 }
@@ -211,9 +223,13 @@ struct svm_grad_args {
   double       *x_out, *g, *gf, *p, *partials, *feas_part, *part_next;
   double        astol;
   int           ld, prow;
+  // AUG
+  double       *spart_next;
+  double        sigma, shift;
 };
 // pass 2 of g = H x - b with the gradient split, p = gf, the partial sums of (0, |gP|^2, |gc|^2, |gf|^2), QPCFeas(x, p) and X'(y o p)
 #define SVM_EU 4
+template <int AUG>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_grad_args a)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
@@ -221,7 +237,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
   const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
   const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   const dbl2        wr = ((const dbl2 *)w)[l2];
-  double            a0 = 0.0, a1 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, m = INFINITY;
+  const double      sS = AUG ? a.sigma * w[64] : 0.0;
+  double            a0 = 0.0, a1 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, m = INFINITY, ts = 0.0;
   for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
     dbl2 v[SVM_EU];
 #pragma unroll
@@ -250,7 +267,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
     }
     double t = 0.0; // y_i p_i: the row's weight in X'(y o p)
     if (act) {
-      const double gi = yi * sm - bi;
+      const double gi = (AUG ? svm_aug_row(yi, sm, sS, a.shift, xi) : yi * sm) - bi;
       double       f, c;
       pmh_box_split_v(xi, gi, li, ui, a.astol, f, c);
       a.g[i] = gi, a.gf[i] = f, a.p[i] = f;
@@ -259,6 +276,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
       acc1 += gPi * gPi, acc2 += c * c, acc3 += f * f;
       m = pmh_box_feas_v(m, xi, f, li, ui);
       t = yi * f;
+      if (AUG) ts += t;
     }
 #pragma unroll
     for (int u = 0; u < SVM_EU; u++) {
@@ -267,6 +285,10 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
     }
   }
   svm_fold_cols(a0, a1, lds, a.part_next);
+  if (AUG) {
+    const double rs = pmh_block_reduce<PMH_RED_SUM>(ts, red);
+    if (threadIdx.x == 0) a.spart_next[blockIdx.x] = rs;
+  }
   const double z  = pmh_block_reduce<PMH_RED_SUM>(0.0, red);
   const double r1 = pmh_block_reduce<PMH_RED_SUM>(acc1, red), r2 = pmh_block_reduce<PMH_RED_SUM>(acc2, red), r3 = pmh_block_reduce<PMH_RED_SUM>(acc3, red);
   const double rm = pmh_block_reduce<PMH_RED_MIN>(m, red);
@@ -282,9 +304,12 @@ struct svm_p1_args {
   double       *Ap, *partials, *x_spec, *part_next;
   double        alpha, astol;
   int           ld, prow;
+  // AUG
+  double       *spart_next, *aux_part; // aux_part != nullptr: sum_i y_i x_i of the iterate (the one-row equality's B u up to the row's scale)
+  double        sigma, shift;
 };
 // pass 2 of Ap = H p with the partial sums of p'Ap, g'p, QPCFeas(x, p); SPEC: + the iterate of the expansion step and X'(y o x+)
-template <int SPEC>
+template <int SPEC, int AUG>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_p1_args a)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
@@ -293,7 +318,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
   const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   const dbl2        wr = ((const dbl2 *)w)[l2];
   const double      maf = SPEC ? -(*a.afeas) : 0.0, mal = -a.alpha;
-  double            a0 = 0.0, a1 = 0.0, s0 = 0.0, s1 = 0.0, m = INFINITY;
+  const double      sS = AUG ? a.sigma * w[64] : 0.0;
+  double            a0 = 0.0, a1 = 0.0, s0 = 0.0, s1 = 0.0, m = INFINITY, ts = 0.0, sux = 0.0;
   for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
     dbl2 v[SVM_EU];
 #pragma unroll
@@ -320,8 +346,9 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
     }
     double t = 0.0; // y_i x+_i: the row's weight in X'(y o x+)
     if (act) {
-      const double api = yi * sm;
+      const double api = AUG ? svm_aug_row(yi, sm, sS, a.shift, pi) : yi * sm;
       a.Ap[i] = api;
+      if (AUG) sux += yi * xi;
       s0 += pi * api, s1 += gi * pi;
       m = pmh_box_feas_v(m, xi, pi, li, ui);
       if (SPEC) { // k_expansion_std (mpgp.hip) on this entry
@@ -331,6 +358,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
         const double r = pmh_box_reduced_v(xs, f, li, ui, a.lb != nullptr, a.ub != nullptr, a.alpha), xn = xs + mal * r;
         a.x_spec[i] = xn;
         t = yi * xn;
+        if (AUG) ts += t;
       }
     }
     if (SPEC) {
@@ -342,6 +370,13 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
     }
   }
   if (SPEC) svm_fold_cols(a0, a1, lds, a.part_next);
+  if (AUG) {
+    const double rs = pmh_block_reduce<PMH_RED_SUM>(ts, red), ru = pmh_block_reduce<PMH_RED_SUM>(sux, red);
+    if (threadIdx.x == 0) {
+      if (SPEC) a.spart_next[blockIdx.x] = rs;
+      if (a.aux_part) a.aux_part[blockIdx.x] = ru;
+    }
+  }
   const double r0s = pmh_block_reduce<PMH_RED_SUM>(s0, red), r1s = pmh_block_reduce<PMH_RED_SUM>(s1, red), rm = pmh_block_reduce<PMH_RED_MIN>(m, red);
   if (threadIdx.x == 0) {
     double *pp = a.partials + (size_t)a.prow * a.ld + blockIdx.x;
@@ -350,7 +385,9 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
 }
 
 // w[c] = sum over workgroups of part[b][c] (as k_svm_colsum) and, in the last workgroup, afeas = min over workgroups of feas_part (exact: a min has no order)
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum_feas(int nblocks, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ feas_part, double *__restrict__ afeas)
+// spart != nullptr: a 65th column, w[64] = sum over workgroups of spart[b] (the grid then has one workgroup more)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum_feas(int nblocks, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ feas_part, double *__restrict__ afeas,
+                                                               const double *__restrict__ spart)
 {
   __shared__ double red[PMH_BLOCK / 64];
   if (blockIdx.x == gridDim.x - 1) {
@@ -361,11 +398,51 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum_feas(int nblocks, cons
     return;
   }
   const int lane = threadIdx.x & 63, c = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
-  if (c >= 64) return;
+  if (c >= 64 + (spart ? 1 : 0)) return;
   double v = 0.0;
+  if (c == 64) {
+    for (int b = lane; b < nblocks; b += 64) v += spart[b];
+  } else
   for (int b = lane; b < nblocks; b += 64) v += part[(size_t)b * 64 + c];
   v = pmh_wave_sum(v);
   if (lane == 0) w[c] = v;
+}
+
+// (template instances with two arguments, named: a comma inside a macro argument would split it)
+static const auto kp_k_svm_x64_4_0 = k_svm_x64<4, 0>;
+static const auto kp_k_svm_x64_4_1 = k_svm_x64<4, 1>;
+static const auto kp_k_svm_x64_p1_0_0 = k_svm_x64_p1<0, 0>;
+static const auto kp_k_svm_x64_p1_0_1 = k_svm_x64_p1<0, 1>;
+static const auto kp_k_svm_x64_p1_1_0 = k_svm_x64_p1<1, 0>;
+static const auto kp_k_svm_x64_p1_1_1 = k_svm_x64_p1<1, 1>;
+static const auto kp_k_svm_xt64_4_0 = k_svm_xt64<4, 0>;
+static const auto kp_k_svm_xt64_4_1 = k_svm_xt64<4, 1>;
+
+// Gu[0] = c sum_b part[b], its square -> the scalar slot (device + pinned host): ||B u||^2 of the one-row equality with row c y.  One workgroup, fixed order
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_aux_finish(int nb, const double *__restrict__ part, double c, double *__restrict__ Gu, double *__restrict__ dslot, double *__restrict__ hslot)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  double            v = 0.0;
+  for (int b = threadIdx.x; b < nb; b += PMH_BLOCK) v += part[b];
+  v = pmh_block_reduce<PMH_RED_SUM>(v, red);
+  if (threadIdx.x == 0) {
+    const double bu = c * v;
+    Gu[0] = bu, *dslot = bu * bu, *hslot = bu * bu;
+  }
+}
+int SvmDualOp::aux_finish(int nb)
+{
+  hipLaunchKernelGGL(k_svm_aux_finish, dim3(1), dim3(PMH_BLOCK), 0, ctx->stream, nb, (const double *)aux_part, aux_c, aux_Gu, ctx->d_scal + aux_slot, ctx->h_scal + aux_slot);
+  PMH_HIP(hipGetLastError());
+  aux_done = 1;
+  return PMH_SUCCESS;
+}
+// the armed ||B u|| request can ride on this product: the augmented kernels, one GPU, the buffer at hand
+static int svm_aux_ready(SvmDualOp *o, bool aug, bool *ok)
+{
+  *ok = o->aux_u && aug && !pmh_comm_on(o->ctx) && o->aux_Gu && o->aux_slot >= 0;
+  if (*ok && !o->aux_part) PMH_CHK(pmh_malloc(o->ctx, sizeof(double) * PMH_MAX_VEC_BLOCKS, (void **)&o->aux_part));
+  return PMH_SUCCESS;
 }
 
 int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
@@ -382,46 +459,63 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)grid_epi, (void **)&feas_part));
     PMH_CHK(pmh_malloc(ctx, sizeof(double), (void **)&d_afeas));
     PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&x_spec));
+    PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)grid_epi, (void **)&spart_next));
   }
-  const int have = next_is;
-  next_is        = NEXT_NONE;
+  // the augmented forms (shift / rank-one term): the same launches with the 65th column sum s = sum_i y_i v_i beside the 64 of w
+  const bool    AG  = aug();
+  const double  sg  = sigma + sigma_fold;
+  const double *sp  = AG ? spart : nullptr, *spn = AG ? spart_next : nullptr;
+  const size_t  nw  = AG ? 65 : 64;
+  int           have = next_is;
+  if (next_aug != AG) have = NEXT_NONE; // (sums prepared by the other form lack / carry the 65th column)
+  next_is  = NEXT_NONE;
+  next_aug = AG;
+  // w (+ s) of `v`: from the sums the previous pass 2 left (prepared) or by pass 1
+  auto form_w = [&](bool prepared, const double *v) -> int {
+    if (prepared) hipLaunchKernelGGL(k_svm_colsum_feas, dim3(AG ? 18 : 17), dim3(PMH_BLOCK), 0, ctx->stream, grid_epi, (const double *)part_next, w, (const double *)feas_part, d_afeas, spn);
+    else {
+      if (AG) SVM_PASS(kp_k_svm_xt64_4_1, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, spart, (const double *)nullptr, (double *)nullptr);
+      else SVM_PASS(kp_k_svm_xt64_4_0, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
+      hipLaunchKernelGGL(k_svm_colsum, dim3(AG ? 17 : 16), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, sp);
+    }
+    PMH_HIP(hipGetLastError());
+    return pmh_comm_allreduce_sum(ctx, w, nw);
+  };
   if (e.kind == PMH_VEPI_GRAD_SPLIT) {
     const bool spec = e.x_from_spec && have == NEXT_XSPEC;
     if (e.x_from_spec && !spec) return pmh_set_error(PMH_ERR_STATE, "SVM dual operator: the driver asks for the prepared expansion step, none is prepared");
-    // (the min it also takes is not used here)
-    if (spec) hipLaunchKernelGGL(k_svm_colsum_feas, dim3(17), dim3(PMH_BLOCK), 0, ctx->stream, grid_epi, (const double *)part_next, w, (const double *)feas_part, d_afeas);
-    else {
-      SVM_PASS(k_svm_xt64<4>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, in, part);
-      hipLaunchKernelGGL(k_svm_colsum, dim3(16), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w);
-    }
-    PMH_HIP(hipGetLastError());
-    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, 64));
+    // (the min the prepared form also takes is not used here)
+    PMH_CHK(form_w(spec, in));
     svm_grad_args a;
     a.b = e.b, a.x_in = spec ? (const double *)x_spec : in, a.lb = e.lb, a.ub = e.ub, a.x_out = spec ? e.x_out : nullptr, a.g = out, a.gf = e.gf, a.p = e.p;
     a.partials = e.partials, a.feas_part = feas_part, a.part_next = part_next, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
+    a.spart_next = spart_next, a.sigma = sg, a.shift = shift;
     if (spec && !e.x_out) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: x_from_spec needs x_out");
-    SVM_PASS(k_svm_x64_grad, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    if (AG) SVM_PASS(k_svm_x64_grad<1>, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    else SVM_PASS(k_svm_x64_grad<0>, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
     PMH_HIP(hipGetLastError());
     next_is = NEXT_P, next_p = e.p;
     return PMH_SUCCESS;
   }
   if (e.kind == PMH_VEPI_P1) {
     const bool paired = e.p_fresh && have == NEXT_P && next_p == in;
-    if (paired) hipLaunchKernelGGL(k_svm_colsum_feas, dim3(17), dim3(PMH_BLOCK), 0, ctx->stream, grid_epi, (const double *)part_next, w, (const double *)feas_part, d_afeas);
-    else {
-      SVM_PASS(k_svm_xt64<4>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, in, part);
-      hipLaunchKernelGGL(k_svm_colsum, dim3(16), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w);
-    }
-    PMH_HIP(hipGetLastError());
-    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, 64));
+    PMH_CHK(form_w(paired, in));
     if (paired) PMH_CHK(pmh_comm_allreduce_min(ctx, d_afeas, 1)); // the P1 pass forms the expansion iterate with it (k_svm_x64_p1<1>)
+    // the one-row equality's ||B u|| for the iterate this pass holds in registers
+    bool aux = false;
+    PMH_CHK(svm_aux_ready(this, AG, &aux));
+    aux = aux && aux_u == e.xx;
     svm_p1_args a;
     a.p = in, a.g = e.g, a.x = e.xx, a.lb = e.lb, a.ub = e.ub, a.afeas = d_afeas, a.Ap = out, a.partials = e.partials, a.x_spec = x_spec, a.part_next = part_next;
     a.alpha = e.spec_alpha, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
+    a.spart_next = spart_next, a.aux_part = aux ? aux_part : nullptr, a.sigma = sg, a.shift = shift;
     const bool spec = paired && e.spec_alpha > 0.0; // afeas is known before this pass only when the gradient pass computed it
-    if (spec) SVM_PASS(k_svm_x64_p1<1>, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
-    else SVM_PASS(k_svm_x64_p1<0>, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    if (spec && AG) SVM_PASS(kp_k_svm_x64_p1_1_1, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    else if (spec) SVM_PASS(kp_k_svm_x64_p1_1_0, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    else if (AG) SVM_PASS(kp_k_svm_x64_p1_0_1, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    else SVM_PASS(kp_k_svm_x64_p1_0_0, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
     PMH_HIP(hipGetLastError());
+    if (aux) PMH_CHK(aux_finish(grid_epi));
     if (spec) next_is = NEXT_XSPEC;
     return PMH_SUCCESS;
   }
@@ -432,37 +526,121 @@ int SvmDualOp::mult(const double *a, double *Ha)
 {
   next_is = NEXT_NONE; // (whatever was prepared belonged to the MPGP driver's vectors)
   if (n == 0 && pmh_comm_on(ctx)) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: this rank holds no samples; with a communicator every rank needs at least one row");
-  if (d == 64 && n > 0) {
+  if (n == 0) return PMH_SUCCESS;
+  const bool   AG = aug();
+  const double sg = sigma + sigma_fold;
+  bool         aux = false;
+  PMH_CHK(svm_aux_ready(this, AG, &aux));
+  const double *au = aux ? aux_u : nullptr;
+  double       *ap = aux ? aux_part : nullptr;
+  if (d == 64) {
     // rows in flight per wave-instruction group: 2 x UNR rows of 512 B (16-byte loads, UNR of them outstanding per lane).  UNR decides which wave visits which
     // rows, i.e. the summation order of pass 1 (last-digit differences between UNR values; fixed for a given UNR).  Measured 4 / 8 / 12 / 16 on configs[4]: 464
-    // / 452-488 / 433 / 487 iterations per second -- inside the run-to-run spread of the box (the two passes already stream X at the box's copy rate): 4 stays
-    const int unr = 4; // rows in flight per wave of the two passes (4 / 8 / 12 / 16 measured: inside the run-to-run spread)
-#define SVM_GO(U)                                                                                                                          \
-  do {                                                                                                                                     \
-    SVM_PASS(k_svm_xt64<U>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, a, part);                                   \
-    hipLaunchKernelGGL(k_svm_colsum, dim3((d + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w);            \
-    PMH_HIP(hipGetLastError());                                                                                                            \
-    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d));                                                                                    \
-    SVM_PASS(k_svm_x64<U>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, Ha);                      \
-  } while (0)
-    if (unr >= 16) SVM_GO(16);
-    else if (unr >= 12) SVM_GO(12);
-    else if (unr >= 8) SVM_GO(8);
-    else SVM_GO(4);
-#undef SVM_GO
+    // / 452-488 / 433 / 487 iterations per second -- inside the run-to-run spread of the box (the two passes already stream X at the box's copy rate): 4 stays,
+    // and only that instance is compiled
+    if (AG) {
+      SVM_PASS(kp_k_svm_xt64_4_1, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, a, part, spart, au, ap);
+      hipLaunchKernelGGL(k_svm_colsum, dim3((d + 1 + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)spart);
+      PMH_HIP(hipGetLastError());
+      if (aux) PMH_CHK(aux_finish(nblocks));
+      PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d + 1));
+      SVM_PASS(kp_k_svm_x64_4_1, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, Ha, a, sg, shift);
+    } else {
+      SVM_PASS(kp_k_svm_xt64_4_0, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, a, part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
+      hipLaunchKernelGGL(k_svm_colsum, dim3((d + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)nullptr);
+      PMH_HIP(hipGetLastError());
+      PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d));
+      SVM_PASS(kp_k_svm_x64_4_0, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, Ha, (const double *)nullptr, 0.0, 0.0);
+    }
     PMH_HIP(hipGetLastError());
     return PMH_SUCCESS;
   }
-  if (n == 0) {
-    if (pmh_comm_on(ctx)) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: this rank holds no samples; with a communicator every rank needs at least one row");
-    return PMH_SUCCESS;
+  if (AG) {
+    SVM_PASS(k_svm_xt<1>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, a, part, spart, au, ap);
+    hipLaunchKernelGGL(k_svm_colsum, dim3((d + 1 + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)spart);
+    PMH_HIP(hipGetLastError());
+    if (aux) PMH_CHK(aux_finish(nblocks));
+    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d + 1));
+    SVM_PASS(k_svm_x<1>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, Ha, a, sg, shift);
+  } else {
+    SVM_PASS(k_svm_xt<0>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, a, part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
+    hipLaunchKernelGGL(k_svm_colsum, dim3((d + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)nullptr);
+    PMH_HIP(hipGetLastError());
+    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d)); // samples sharded over GPUs: the one exchange step
+    SVM_PASS(k_svm_x<0>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, Ha, (const double *)nullptr, 0.0, 0.0);
   }
-  SVM_PASS(k_svm_xt, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, a, part);
-  hipLaunchKernelGGL(k_svm_colsum, dim3((d + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w);
   PMH_HIP(hipGetLastError());
-  PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d)); // samples sharded over GPUs: the one exchange step
-  SVM_PASS(k_svm_x, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, Ha);
-  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+// w = X'(y o a) by pass 1 alone (the model of a trained SVM)
+int pmh_svm_op_form_w(SvmDualOp *o, const double *a, const double **w_dev)
+{
+  o->next_is = SvmDualOp::NEXT_NONE;
+  if (o->n > 0) {
+    o->npass++;
+    if (o->d == 64) hipLaunchKernelGGL(kp_k_svm_xt64_4_0, dim3(o->nblocks), dim3(PMH_BLOCK), 0, o->ctx->stream, o->n, o->X, o->y, a, o->part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
+    else hipLaunchKernelGGL(k_svm_xt<0>, dim3(o->nblocks), dim3(PMH_BLOCK), 0, o->ctx->stream, o->n, o->d, o->X, o->y, a, o->part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
+    hipLaunchKernelGGL(k_svm_colsum, dim3((o->d + 3) / 4), dim3(PMH_BLOCK), 0, o->ctx->stream, o->nblocks, o->d, (const double *)o->part, o->w, (const double *)nullptr);
+    PMH_HIP(hipGetLastError());
+  } else PMH_CHK(pmh_memset(o->ctx, o->w, 0, sizeof(double) * (size_t)o->d));
+  PMH_CHK(pmh_comm_allreduce_sum(o->ctx, o->w, (size_t)o->d));
+  *w_dev = o->w;
+  return PMH_SUCCESS;
+}
+
+// how many entries of row differ from c y (c = row_0 / y_0): 0 <=> the row is c y, entry by entry, to the rounding of one multiplication
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_row_vs_labels(int n, const double *__restrict__ row, const double *__restrict__ y, int *__restrict__ bad)
+{
+  const double c = row[0] / y[0];
+  int          b = 0;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) b += fabs(row[i] - c * y[i]) > 4.0 * 2.220446049250313e-16 * fabs(row[i]) ? 1 : 0;
+  if (b) atomicAdd(bad, b); // (a count of mismatches: any order gives the same integer)
+}
+// Under a communicator the answer is joined: every rank takes part in ONE all-reduce of (mismatches, ranks that hold rows, sum of c, sum of c^2), so all ranks
+// decide alike (ranks that disagreed would issue different collectives afterwards) and c must be the same on every rank that holds rows
+int pmh_svm_op_row_is_labels(SvmDualOp *o, pmh_qppf pf, double *c)
+{
+  if (!pf->onerow) return 0;
+  pmh_ctx ctx = o->ctx;
+  double  h[4] = {0.0, 0.0, 0.0, 0.0}; // mismatches (or: this rank cannot tell), holds rows, c, c^2
+  if (pf->n != o->n) h[0] = 1.0;
+  else if (o->n > 0) {
+    int *d_bad = nullptr, bad = 1;
+    double r0 = 0.0, y0 = 0.0;
+    int rc = pmh_malloc(ctx, sizeof(int), (void **)&d_bad);
+    if (!rc) rc = pmh_memset(ctx, d_bad, 0, sizeof(int));
+    if (!rc) {
+      hipLaunchKernelGGL(k_svm_row_vs_labels, dim3(pmh_vec_grid(o->n)), dim3(PMH_BLOCK), 0, ctx->stream, o->n, pf->row, o->y, d_bad);
+      rc = (hipGetLastError() != hipSuccess) || pmh_memcpy_d2h(ctx, &bad, d_bad, sizeof(int)) || pmh_memcpy_d2h(ctx, &r0, pf->row, sizeof(double)) || pmh_memcpy_d2h(ctx, &y0, o->y, sizeof(double));
+    }
+    if (d_bad) pmh_free(ctx, d_bad);
+    if (rc || bad || y0 == 0.0 || r0 == 0.0) h[0] = 1.0;
+    else h[1] = 1.0, h[2] = r0 / y0, h[3] = h[2] * h[2];
+  }
+  if (pmh_comm_on(ctx)) {
+    double *d = nullptr;
+    if (pmh_malloc(ctx, sizeof(h), (void **)&d)) return 0;
+    const int rc = pmh_memcpy_h2d(ctx, d, h, sizeof(h)) || pmh_comm_allreduce_sum(ctx, d, 4) || pmh_memcpy_d2h(ctx, h, d, sizeof(h));
+    pmh_free(ctx, d);
+    if (rc) return 0;
+    if (h[0] == 0.0 && h[1] > 0.0) {
+      const double mean = h[2] / h[1];
+      if (fabs(h[3] - h[1] * mean * mean) > 8.0 * 2.220446049250313e-16 * h[3]) return 0; // the ranks' c differ
+      h[2] = mean;
+    }
+  }
+  if (h[0] != 0.0 || h[1] == 0.0) return 0;
+  *c = h[2];
+  return 1;
+}
+
+extern "C" int pmh_op_svm_dual_set_terms(pmh_op op, double shift, double sigma)
+{
+  SvmDualOp *o = dynamic_cast<SvmDualOp *>(op);
+  PMH_ARG(o && shift >= 0.0 && sigma >= 0.0);
+  o->shift = shift, o->sigma = sigma;
+  o->next_is = SvmDualOp::NEXT_NONE;
   return PMH_SUCCESS;
 }
 
@@ -485,8 +663,9 @@ extern "C" int pmh_op_create_svm_dual(pmh_ctx ctx, int n_local, int d, const dou
   o->y         = y_dev;
   long long nb = ((long long)n_local + 4 * 16 - 1) / (4 * 16); // >= 16 rows per wavefront
   o->nblocks   = (int)(nb < 1 ? 1 : (nb > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : nb));
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)d, (void **)&o->w));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * ((size_t)d + 1), (void **)&o->w)); // (w[d]: s = sum_i y_i v_i of the augmented forms)
   PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)o->nblocks * d, (void **)&o->part));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)o->nblocks, (void **)&o->spart));
   *op = o;
   return PMH_SUCCESS;
 }

@@ -1,0 +1,378 @@
+// SVM front end (PermonSVM's role: train, model, predict) over the dense-row dual operator of svm.hip:
+//   L1: min 1/2 a'Ha - 1'a,          0 <= a <= C   (primal 1/2 |w|^2 + C sum xi)
+//   L2: min 1/2 a'(H + I/C)a - 1'a,  0 <= a        (primal 1/2 |w|^2 + C/2 sum xi^2)
+//   bias: additionally y'a = 0, posed as (y / sqrt(n))'a = 0 -- a one-row projector (onerow.hip) under SMALXE, whose penalty term the operator absorbs (qppf.hip)
+// H = diag(y) X X' diag(y).  No bias: MPGP on the box alone.  Model: w = X'(y o a) by the operator's pass-1 kernels; b by one pass over X (k_svm_bias);
+// prediction by one pass over the test samples (k_svm_predict: one wavefront per row, lane j owns columns j, j + 64, ...: any d the operator accepts;
+// k_svm_predict64 for d = 64: the two-rows-per-wave layout of the operator's own pass 2).
+#include <cmath>
+
+#include "svm_internal.h"
+#include "reduce.h"
+
+struct pmh_svm_s {
+  pmh_ctx       ctx;
+  int           n, d;
+  long long     n_global;
+  const double *X, *y;
+  pmh_svm_opts  o;
+  pmh_op        H     = nullptr;
+  pmh_qppf      pf    = nullptr;
+  pmh_mpgp      mpgp  = nullptr;
+  pmh_smalxe    sx    = nullptr;
+  double       *alpha = nullptr, *rhs = nullptr, *lb = nullptr, *ub = nullptr, *row = nullptr, *w = nullptr, *part = nullptr, *scal = nullptr;
+  std::vector<double> h_w;
+  double        b = 0.0;
+  int           trained = 0;
+  pmh_svm_stats st;
+};
+
+#define SVM_NB(n) ((int)((((long long)(n) + 63) / 64) < 1 ? 1 : ((((long long)(n) + 63) / 64) > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : (((long long)(n) + 63) / 64))))
+
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_fill_row(int n, const double *__restrict__ y, double c, double *__restrict__ row)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) row[i] = c * y[i];
+}
+
+// the row's dot product x_i . w in every lane of the wave
+static __device__ __forceinline__ double svm_row_dot_any(const double *__restrict__ xr, int d, const double *wr, int lane)
+{
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < SVM_KMAX; k++) {
+    const int c = lane + 64 * k;
+    if (c < d) s += __builtin_nontemporal_load(&xr[c]) * wr[k];
+  }
+  s = pmh_wave_sum(s);
+  return __shfl(s, 0, 64);
+}
+
+// One pass over X for the bias: per workgroup the partial sums of (sum over free support vectors of y_i - x_i . w, y'a, number of free support vectors, number of
+// support vectors) -> part[4][gridDim.x]; free: astol < a_i and (ubound > 0: a_i < ubound - astol)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, const double *__restrict__ alpha, double astol,
+                                                        double ubound, double *__restrict__ part)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
+  double            wr[SVM_KMAX];
+#pragma unroll
+  for (int k = 0; k < SVM_KMAX; k++) wr[k] = (lane + 64 * k < d) ? w[lane + 64 * k] : 0.0;
+  double sb = 0.0, sya = 0.0, nf = 0.0, ns = 0.0;
+  for (long long i = gw; i < n; i += nw) {
+    const double s = svm_row_dot_any(X + (size_t)i * d, d, wr, lane);
+    if (lane == 0) {
+      const double ai = alpha[i], yi = y[i];
+      sya += yi * ai;
+      if (ai > astol) {
+        ns += 1.0;
+        if (!(ubound > 0.0) || ai < ubound - astol) nf += 1.0, sb += yi - s;
+      }
+    }
+  }
+  const double r0 = pmh_block_reduce<PMH_RED_SUM>(sb, red), r1 = pmh_block_reduce<PMH_RED_SUM>(sya, red), r2 = pmh_block_reduce<PMH_RED_SUM>(nf, red), r3 = pmh_block_reduce<PMH_RED_SUM>(ns, red);
+  if (threadIdx.x == 0) {
+    const size_t g = gridDim.x;
+    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
+  }
+}
+// out[k] = sum_b part[k][b], k < K: one workgroup, fixed order (the counts are sums of ones: exact below 2^53)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_sum_rows(int nb, int K, const double *__restrict__ part, double *__restrict__ out)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  for (int k = 0; k < K; k++) {
+    double v = 0.0;
+    for (int b = threadIdx.x; b < nb; b += PMH_BLOCK) v += part[(size_t)k * nb + b];
+    v = pmh_block_reduce<PMH_RED_SUM>(v, red);
+    if (threadIdx.x == 0) out[k] = v;
+  }
+}
+
+// One pass over the test samples: score_i = x_i . w + b, label_i = +-1 (score >= 0: +1), and with the true labels the confusion counts (TP, FP, TN, FN) per
+// workgroup -> part[4][gridDim.x].  scores / labels / ytrue may each be nullptr
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict(int n, int d, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
+                                                           const double *__restrict__ ytrue, double *__restrict__ part)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
+  double            wr[SVM_KMAX];
+#pragma unroll
+  for (int k = 0; k < SVM_KMAX; k++) wr[k] = (lane + 64 * k < d) ? w[lane + 64 * k] : 0.0;
+  double tp = 0.0, fp = 0.0, tn = 0.0, fn = 0.0;
+  for (long long i = gw; i < n; i += nw) {
+    const double s = svm_row_dot_any(X + (size_t)i * d, d, wr, lane) + b;
+    if (lane == 0) {
+      const double l = s >= 0.0 ? 1.0 : -1.0;
+      if (scores) scores[i] = s;
+      if (labels) labels[i] = l;
+      if (ytrue) {
+        const bool pos = ytrue[i] > 0.0;
+        if (l > 0.0) (pos ? tp : fp) += 1.0;
+        else (pos ? fn : tn) += 1.0;
+      }
+    }
+  }
+  if (!ytrue) return; // (uniform: a kernel argument)
+  const double r0 = pmh_block_reduce<PMH_RED_SUM>(tp, red), r1 = pmh_block_reduce<PMH_RED_SUM>(fp, red), r2 = pmh_block_reduce<PMH_RED_SUM>(tn, red), r3 = pmh_block_reduce<PMH_RED_SUM>(fn, red);
+  if (threadIdx.x == 0) {
+    const size_t g = gridDim.x;
+    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
+  }
+}
+
+// d == 64: the row layout of k_svm_x64 (svm.hip) -- 16-byte loads, two rows per wave-instruction (lanes 0-31 row r, lanes 32-63 row r + 1), four in flight
+typedef double svm_dbl2 __attribute__((ext_vector_type(2)));
+#define SVM_PU 4
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
+                                                             const double *__restrict__ ytrue, double *__restrict__ part)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
+  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
+  const svm_dbl2    wr = ((const svm_dbl2 *)w)[l2];
+  double            tp = 0.0, fp = 0.0, tn = 0.0, fn = 0.0;
+  for (long long r0 = gw * 2 * SVM_PU; r0 < n; r0 += nw * 2 * SVM_PU) {
+    svm_dbl2 v[SVM_PU];
+#pragma unroll
+    for (int u = 0; u < SVM_PU; u++) {
+      const long long i = r0 + 2 * u + half;
+      v[u] = (i < n) ? __builtin_nontemporal_load((const svm_dbl2 *)(X + (size_t)i * 64) + l2) : svm_dbl2{0.0, 0.0};
+    }
+#pragma unroll
+    for (int u = 0; u < SVM_PU; u++) {
+      const long long i = r0 + 2 * u + half;
+      double          s = v[u].x * wr.x + v[u].y * wr.y;
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) s += __shfl_down(s, o, 32);
+      if (l2 == 0 && i < n) {
+        s += b;
+        const double l = s >= 0.0 ? 1.0 : -1.0;
+        if (scores) scores[i] = s;
+        if (labels) labels[i] = l;
+        if (ytrue) {
+          const bool pos = ytrue[i] > 0.0;
+          if (l > 0.0) (pos ? tp : fp) += 1.0;
+          else (pos ? fn : tn) += 1.0;
+        }
+      }
+    }
+  }
+  if (!ytrue) return; // (uniform: a kernel argument)
+  const double q0 = pmh_block_reduce<PMH_RED_SUM>(tp, red), q1 = pmh_block_reduce<PMH_RED_SUM>(fp, red), q2 = pmh_block_reduce<PMH_RED_SUM>(tn, red), q3 = pmh_block_reduce<PMH_RED_SUM>(fn, red);
+  if (threadIdx.x == 0) {
+    const size_t g = gridDim.x;
+    part[blockIdx.x] = q0, part[g + blockIdx.x] = q1, part[2 * g + blockIdx.x] = q2, part[3 * g + blockIdx.x] = q3;
+  }
+}
+
+extern "C" int pmh_svm_default_opts(pmh_svm_opts *o)
+{
+  PMH_ARG(o);
+  memset(o, 0, sizeof(*o));
+  o->loss_type = PMH_SVM_LOSS_L1;
+  o->C         = 1.0;
+  o->bias      = 1;
+  PMH_CHK(pmh_qps_default_opts(&o->qps));
+  PMH_CHK(pmh_mpgp_default_opts(&o->mpgp));
+  return pmh_smalxe_default_opts(&o->smalxe);
+}
+
+extern "C" int pmh_svm_destroy(pmh_svm s)
+{
+  if (!s) return PMH_SUCCESS;
+  if (s->mpgp) pmh_mpgp_destroy(s->mpgp);
+  if (s->sx) pmh_smalxe_destroy(s->sx);
+  if (s->pf) pmh_qppf_destroy(s->pf);
+  if (s->H) pmh_op_destroy(s->H);
+  double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal};
+  for (double *p : v)
+    if (p) pmh_free(s->ctx, p);
+  delete s;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
+{
+  PMH_ARG(ctx && out && opts && n_local >= 0 && d >= 1 && d <= 64 * SVM_KMAX && X_dev && y_dev);
+  if (opts->loss_type != PMH_SVM_LOSS_L1 && opts->loss_type != PMH_SVM_LOSS_L2) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: unknown loss type %d (PMH_SVM_LOSS_L1 | PMH_SVM_LOSS_L2)", opts->loss_type);
+  if (!(opts->C > 0.0)) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: C = %g, must be positive", opts->C);
+  pmh_svm s = new pmh_svm_s();
+  s->ctx = ctx, s->n = n_local, s->d = d, s->X = X_dev, s->y = y_dev, s->o = *opts;
+  memset(&s->st, 0, sizeof(s->st));
+  const int    n  = n_local;
+  const size_t nb = sizeof(double) * (size_t)(n ? n : 1);
+  int          rc = PMH_SUCCESS;
+  do {
+    if ((rc = pmh_op_create_svm_dual(ctx, n, d, X_dev, y_dev, &s->H))) break;
+    if (opts->loss_type == PMH_SVM_LOSS_L2 && (rc = pmh_op_svm_dual_set_terms(s->H, 1.0 / opts->C, 0.0))) break;
+    if ((rc = pmh_malloc(ctx, nb, (void **)&s->alpha)) || (rc = pmh_malloc(ctx, nb, (void **)&s->rhs)) || (rc = pmh_malloc(ctx, nb, (void **)&s->lb))) break;
+    if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)d, (void **)&s->w)) || (rc = pmh_malloc(ctx, sizeof(double) * 4 * PMH_MAX_VEC_BLOCKS, (void **)&s->part)) || (rc = pmh_malloc(ctx, sizeof(double) * 8, (void **)&s->scal))) break;
+    if ((rc = pmh_memset(ctx, s->alpha, 0, nb)) || (rc = pmh_memset(ctx, s->lb, 0, nb)) || (rc = pmh_vec_set(ctx, n, s->rhs, 1.0))) break;
+    if (opts->loss_type == PMH_SVM_LOSS_L1) {
+      if ((rc = pmh_malloc(ctx, nb, (void **)&s->ub)) || (rc = pmh_vec_set(ctx, n, s->ub, opts->C))) break;
+    }
+    // the number of samples over all ranks (the row of the equality is y / sqrt(n))
+    double ng = (double)n;
+    if (pmh_comm_on(ctx)) {
+      if ((rc = pmh_vec_set(ctx, 1, s->scal, ng)) || (rc = pmh_comm_allreduce_sum(ctx, s->scal, 1)) || (rc = pmh_memcpy_d2h(ctx, &ng, s->scal, sizeof(double)))) break;
+    }
+    s->n_global = (long long)ng;
+    if (opts->bias) {
+      if (s->n_global < 1) {
+        rc = pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: no samples");
+        break;
+      }
+      if ((rc = pmh_malloc(ctx, nb, (void **)&s->row))) break;
+      if (n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, y_dev, 1.0 / sqrt(ng), s->row);
+      if (hipGetLastError() != hipSuccess) {
+        rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_create: the launch that fills the equality's row failed");
+        break;
+      }
+      if ((rc = pmh_qppf_create_onerow(ctx, s->row, n, &s->pf))) break;
+      pmh_smalxe_opts so = s->o.smalxe;
+      so.rtol = s->o.qps.rtol, so.atol = s->o.qps.atol, so.divtol = s->o.qps.divtol;
+      if (s->o.qps.max_it_set) so.max_it = s->o.qps.max_it;
+      if ((rc = pmh_smalxe_create(ctx, s->H, s->rhs, s->alpha, s->lb, s->ub, s->pf, &so, &s->sx))) break;
+    } else {
+      pmh_mpgp_opts mo = s->o.mpgp;
+      mo.rtol = s->o.qps.rtol, mo.atol = s->o.qps.atol, mo.divtol = s->o.qps.divtol, mo.max_it = s->o.qps.max_it;
+      if ((rc = pmh_mpgp_create(ctx, s->H, s->rhs, s->alpha, s->lb, s->ub, &mo, &s->mpgp))) break;
+    }
+  } while (0);
+  if (rc) {
+    pmh_svm_destroy(s);
+    return rc;
+  }
+  *out = s;
+  return PMH_SUCCESS;
+}
+
+// w, b and the counts from the current alpha
+static int svm_model(pmh_svm s)
+{
+  pmh_ctx       ctx = s->ctx;
+  SvmDualOp    *H   = static_cast<SvmDualOp *>(s->H);
+  const double *w   = nullptr;
+  PMH_CHK(pmh_svm_op_form_w(H, s->alpha, &w));
+  PMH_CHK(pmh_vec_copy(ctx, s->d, w, s->w));
+  s->h_w.resize((size_t)s->d);
+  const int    nb    = SVM_NB(s->n);
+  const double astol = s->sx ? s->o.smalxe.inner.astol : s->o.mpgp.astol;
+  if (s->n > 0) {
+    H->npass++;
+    hipLaunchKernelGGL(k_svm_bias, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, s->o.loss_type == PMH_SVM_LOSS_L1 ? s->o.C : 0.0, s->part);
+    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, ctx->stream, nb, 4, (const double *)s->part, s->scal);
+    PMH_HIP(hipGetLastError());
+  } else PMH_CHK(pmh_memset(ctx, s->scal, 0, sizeof(double) * 4));
+  PMH_CHK(pmh_comm_allreduce_sum(ctx, s->scal, 4));
+  // the equality's multiplier: SMALXE keeps B'mu = mu row (the Lagrangian is 1/2 a'Ha - 1'a + mu (row'a)), so mu = row'(B'mu) / (row'row) and, with
+  // row = y / sqrt(n), stationarity in a free sample reads y_i - x_i . w = mu / sqrt(n): b = mu / sqrt(n)
+  if (s->sx) {
+    double *Btmu = nullptr;
+    PMH_CHK(pmh_smalxe_get_penalized(s->sx, nullptr, nullptr, &Btmu));
+    PMH_CHK(pmh_onerow_dot(s->pf, Btmu, 1.0 / s->pf->row_aat, s->scal + 4));
+  } else PMH_CHK(pmh_memset(ctx, s->scal + 4, 0, sizeof(double)));
+  double h[5];
+  PMH_CHK(pmh_memcpy_d2h(ctx, h, s->scal, sizeof(h)));
+  PMH_CHK(pmh_memcpy_d2h(ctx, s->h_w.data(), s->w, sizeof(double) * (size_t)s->d));
+  s->st.yTalpha = h[1], s->st.n_free_sv = (long long)h[2], s->st.n_sv = (long long)h[3];
+  s->st.b_multiplier = h[4] / sqrt((double)(s->n_global > 0 ? s->n_global : 1));
+  s->st.b_free       = h[2] > 0.0 ? h[0] / h[2] : NAN;
+  if (!s->o.bias) s->b = 0.0;
+  else s->b = h[2] > 0.0 ? s->st.b_free : s->st.b_multiplier;
+  s->st.b = s->b;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_train(pmh_svm s)
+{
+  PMH_ARG(s);
+  const size_t nb = sizeof(double) * (size_t)(s->n ? s->n : 1);
+  PMH_CHK(pmh_memset(s->ctx, s->alpha, 0, nb));
+  long long p0 = 0, p1 = 0;
+  PMH_CHK(pmh_op_svm_dual_passes(s->H, &p0));
+  if (s->sx) {
+    PMH_CHK(pmh_smalxe_reset(s->sx));
+    PMH_CHK(pmh_smalxe_solve(s->sx));
+    pmh_smalxe_stats st;
+    PMH_CHK(pmh_smalxe_get_stats(s->sx, &st));
+    s->st.reason = st.reason, s->st.outer_iterations = st.iteration, s->st.inner_iterations = st.inner_iter_accu;
+    s->st.nmv = st.inner.nmv, s->st.ncg = st.inner.ncg, s->st.nexp = st.inner.nexp, s->st.nprop = st.inner.nprop;
+    s->st.rho = st.rho, s->st.normBu = st.normBu, s->st.rnorm = st.rnorm;
+  } else {
+    PMH_CHK(pmh_mpgp_solve(s->mpgp));
+    pmh_mpgp_stats st;
+    PMH_CHK(pmh_mpgp_get_stats(s->mpgp, &st));
+    s->st.reason = st.reason, s->st.outer_iterations = 0, s->st.inner_iterations = st.iteration;
+    s->st.nmv = st.nmv, s->st.ncg = st.ncg, s->st.nexp = st.nexp, s->st.nprop = st.nprop;
+    s->st.rho = 0.0, s->st.normBu = 0.0, s->st.rnorm = st.rnorm;
+  }
+  PMH_CHK(pmh_op_svm_dual_passes(s->H, &p1));
+  s->st.passes_X = p1 - p0; // the solve's passes over X (the model's two are not counted)
+  PMH_CHK(svm_model(s));
+  s->trained = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_get_model(pmh_svm s, double *w_host, double *b)
+{
+  PMH_ARG(s);
+  if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_get_model: call pmh_svm_train first");
+  if (w_host) memcpy(w_host, s->h_w.data(), sizeof(double) * (size_t)s->d);
+  if (b) *b = s->b;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_get_dual(pmh_svm s, double *alpha_dev)
+{
+  PMH_ARG(s && alpha_dev);
+  return pmh_vec_copy(s->ctx, s->n, s->alpha, alpha_dev);
+}
+
+extern "C" int pmh_svm_get_stats(pmh_svm s, pmh_svm_stats *st)
+{
+  PMH_ARG(s && st);
+  *st = s->st;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_get_solver(pmh_svm s, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh_smalxe *smalxe)
+{
+  PMH_ARG(s);
+  if (H) *H = s->H;
+  if (pf) *pf = s->pf;
+  if (mpgp) *mpgp = s->mpgp;
+  if (smalxe) *smalxe = s->sx;
+  return PMH_SUCCESS;
+}
+
+static int svm_predict(pmh_svm s, int n, const double *X, double *scores, double *labels, const double *ytrue, long long *counts)
+{
+  PMH_ARG(s && n >= 0 && (X || n == 0));
+  if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict: call pmh_svm_train first");
+  const int nb = SVM_NB(n);
+  if (n > 0) {
+    if (s->d == 64) hipLaunchKernelGGL(k_svm_predict64, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part);
+    else hipLaunchKernelGGL(k_svm_predict, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, s->d, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part);
+    PMH_HIP(hipGetLastError());
+  }
+  if (!counts) return PMH_SUCCESS;
+  if (n > 0) {
+    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, s->ctx->stream, nb, 4, (const double *)s->part, s->scal);
+    PMH_HIP(hipGetLastError());
+  } else PMH_CHK(pmh_memset(s->ctx, s->scal, 0, sizeof(double) * 4));
+  PMH_CHK(pmh_comm_allreduce_sum(s->ctx, s->scal, 4));
+  double h[4];
+  PMH_CHK(pmh_memcpy_d2h(s->ctx, h, s->scal, sizeof(h)));
+  for (int k = 0; k < 4; k++) counts[k] = (long long)h[k];
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_predict(pmh_svm s, int n, const double *X_dev, double *scores_dev, double *labels_dev) { return svm_predict(s, n, X_dev, scores_dev, labels_dev, nullptr, nullptr); }
+
+extern "C" int pmh_svm_test(pmh_svm s, int n, const double *X_dev, const double *y_dev, long long counts[4])
+{
+  PMH_ARG(y_dev && counts);
+  return svm_predict(s, n, X_dev, nullptr, nullptr, y_dev, counts);
+}

@@ -532,6 +532,20 @@ class QPPF:
         return e
 
     @classmethod
+    def onerow(cls, ctx, a):
+        """One-row projector G = a' (pmh_qppf_create_onerow, the reference's MATONEROW role): a dense vector instead of a 1 x n CSR, no host factorisation.
+        a: numpy array or Vec.  The rows count as orthonormal where |a'a - 1| <= n eps."""
+        self = cls.__new__(cls)
+        av = a if isinstance(a, Vec) else Vec.from_numpy(ctx, np.ascontiguousarray(a, dtype=np.float64))
+        self.ctx, self.G, self.row, self.implicit = ctx, None, av, False
+        self.m, self.n = 1, av.n
+        h = C.c_void_p()
+        check(ctx.L.pmh_qppf_create_onerow(ctx.h, av.p, av.n, C.byref(h)))
+        self.h = h
+        self.orthonormal = None  # decided by the library from a'a
+        return self
+
+    @classmethod
     def from_scipy(cls, ctx, G, orthonormal=False):
         G = G.tocsr()
         G.sort_indices()
@@ -656,5 +670,10 @@ def MatCreateSVMDual(ctx, X, y):
         check(ctx.L.pmh_op_svm_dual_passes(op.h, C.byref(k)))
         return int(k.value)
 
+    def set_terms(shift=0.0, sigma=0.0):
+        """H + shift I + sigma y y' (pmh_op_svm_dual_set_terms); both 0: the plain operator."""
+        check(ctx.L.pmh_op_svm_dual_set_terms(op.h, float(shift), float(sigma)))
+
     op.passes = passes
+    op.set_terms = set_terms
     return op

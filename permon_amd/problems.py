@@ -212,6 +212,25 @@ def svm_dual(N, d=64, C=1.0, seed_x=7, seed_w=8):
     return dict(n=N, d=d, X=X, y=y, b=np.ones(N), lb=np.zeros(N), ub=np.full(N, float(C)), x0=np.zeros(N))
 
 
+def svm_offset(N, d=64, offset=3.0, C=1.0, seed_x=7, seed_w=8, seed_test=None, N_test=0):
+    """The data of svm_dual with an offset planted in the labels, y = sign(X w* + offset + 0.1 N(0,1)): a separating plane that does not pass through the
+    origin, so a classifier needs the bias term.  Same draws as svm_dual (X, then the noise, from default_rng(seed_x); w* from default_rng(seed_w)).
+    N_test > 0: a held-out draw (X_test, y_test) of the same model from default_rng(seed_test or seed_x + 1000)."""
+    rng = np.random.default_rng(seed_x)
+    X = rng.standard_normal((N, d))
+    w = np.random.default_rng(seed_w).standard_normal(d)
+    y = np.sign(X @ w + offset + 0.1 * rng.standard_normal(N))
+    y[y == 0] = 1.0
+    out = dict(n=N, d=d, X=X, y=y, C=float(C), offset=float(offset), w_star=w, b=np.ones(N), lb=np.zeros(N), ub=np.full(N, float(C)), x0=np.zeros(N))
+    if N_test > 0:
+        rt = np.random.default_rng(seed_x + 1000 if seed_test is None else seed_test)
+        Xt = rt.standard_normal((N_test, d))
+        yt = np.sign(Xt @ w + offset + 0.1 * rt.standard_normal(N_test))
+        yt[yt == 0] = 1.0
+        out.update(X_test=Xt, y_test=yt)
+    return out
+
+
 def write_contact_problem(path, f):
     """A CubeFeti contact problem (permon_amd.feti.CubeFeti) in the binary layout examples/contact_tfeti.c reads:
     everything pmh_feti_contact_solve takes -- block-diagonal K, f, B as leaves (equality rows first), c, R, the node boxes."""
