@@ -468,6 +468,11 @@ int pmh_op_svm_dual_passes(pmh_op op, long long *passes);
    Hessian; sigma y y' is what penalising the bias equality y'a = 0 adds.  One more column sum, s = sum_i y_i a_i, travels with the d of w: no extra pass over X,
    and every fused epilogue of the plain operator carries both terms */
 int pmh_op_svm_dual_set_terms(pmh_op op, double shift, double sigma);
+/* The same operator for samples in CSR (X: n_local x d, any d >= 1, column indices ascending inside a row; y in {-1, +1}); X and y_dev are borrowed and must
+   stay unchanged.  Two sweeps over the stored entries per application, the work divided by entries, no float atomics: the same input gives the same bits
+   (svm_csr.hip).  Creation builds a column-ordered device copy of X: 12 (nnz + n_local) bytes beside X.  Unsorted column indices and nnz + n_local >= 2^31 are
+   PMH_ERR_ARG.  pmh_op_svm_dual_set_terms and pmh_op_svm_dual_passes apply (a pass = one sweep over all stored entries); no fused MPGP epilogues */
+int pmh_op_create_svm_dual_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, pmh_op *op);
 
 /* ---- QPS SMALXE (src/qps/impls/smalxe/smalxe.c) -------------------------------------------------------- */
 typedef struct {
@@ -576,6 +581,12 @@ int pmh_svm_get_solver(pmh_svm svm, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh
 int pmh_svm_predict(pmh_svm svm, int n, const double *X_dev, double *scores_dev, double *labels_dev);
 /* one pass: counts = (TP, FP, TN, FN) of the predicted labels against y_dev (summed over the ranks under a communicator) */
 int pmh_svm_test(pmh_svm svm, int n, const double *X_dev, const double *y_dev, long long counts[4]);
+/* Samples in CSR (any d; see pmh_op_create_svm_dual_csr): X and y_dev borrowed.  Every other entry works unchanged on the handle.  Test samples may come in
+   either form whatever the training samples were: pmh_svm_predict / pmh_svm_test need d <= 256, the _csr entries a matrix of the model's d columns; a
+   mismatch is PMH_ERR_ARG */
+int pmh_svm_create_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *svm);
+int pmh_svm_predict_csr(pmh_svm svm, pmh_csr Xt, double *scores_dev, double *labels_dev);
+int pmh_svm_test_csr(pmh_svm svm, pmh_csr Xt, const double *y_dev, long long counts[4]);
 int pmh_svm_destroy(pmh_svm svm);
 
 

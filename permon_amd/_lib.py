@@ -248,6 +248,7 @@ _PROTOS = {
     "pmh_qpt_feti_chain_destroy": [vp],
     "pmh_qpt_feti_chain_kkt": [vp, vp, vp, vp, vp, vp],
     "pmh_op_create_svm_dual": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)],
+    "pmh_op_create_svm_dual_csr": [vp, vp, vp, C.POINTER(vp)],
     "pmh_op_svm_dual_passes": [vp, C.POINTER(C.c_longlong)],
     "pmh_op_svm_dual_set_terms": [vp, C.c_double, C.c_double],
     "pmh_qppf_create_onerow": [vp, vp, C.c_int, C.POINTER(vp)],
@@ -261,6 +262,9 @@ _PROTOS = {
     "pmh_svm_get_solver": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
     "pmh_svm_predict": [vp, C.c_int, vp, vp, vp],
     "pmh_svm_test": [vp, C.c_int, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_create_csr": [vp, vp, vp, C.POINTER(SvmOpts), C.POINTER(vp)],
+    "pmh_svm_predict_csr": [vp, vp, vp, vp],
+    "pmh_svm_test_csr": [vp, vp, vp, C.POINTER(C.c_longlong)],
     "pmh_svm_destroy": [vp],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],

@@ -784,14 +784,15 @@ struct PenalizedOp : pmh_op_s {
   // term -- the product is the operator's, with sigma_fold set around it (the operator on its own, e.g. in SMALXE's power iterations, stays unpenalised), every
   // fused epilogue it has stays on, and ||G u|| = |c sum_i y_i u_i| comes out of the pass that holds the iterate's rows (svm.hip aux_*).  rho is read at every
   // product, so pmh_op_penalized_set_penalty needs nothing more.  Probed once, at the first product (one pass over the row and the labels)
-  SvmDualOp *sv = nullptr;
-  double     sv_c = 0.0;
-  int        sv_state = -1;
-  SvmDualOp *fold()
+  // The CSR operator (svm_csr.hip) folds the same way; it has no fused epilogue and does not serve the ||G u|| request (the projector's own dot runs).
+  SvmDualBase *sv = nullptr;
+  double       sv_c = 0.0;
+  int          sv_state = -1;
+  SvmDualBase *fold()
   {
     if (sv_state < 0) {
-      sv_state     = 0;
-      SvmDualOp *o = pf->onerow ? dynamic_cast<SvmDualOp *>(A) : nullptr;
+      sv_state       = 0;
+      SvmDualBase *o = pf->onerow ? dynamic_cast<SvmDualBase *>(A) : nullptr;
       if (o && pmh_svm_op_row_is_labels(o, pf, &sv_c) == 1) sv = o, sv_state = 1;
     }
     return sv_state == 1 ? sv : nullptr;

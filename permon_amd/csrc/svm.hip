@@ -71,9 +71,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, co
   if (lane == 0) w[c] = v;
 }
 
-// the augmented row result: (y_i (x_i . w) + (sigma s) y_i) + shift a_i, in this order (s = w[d])
-static __device__ __forceinline__ double svm_aug_row(double yi, double dot, double sS, double shift, double ai) { return (yi * dot + sS * yi) + shift * ai; }
-
 // pass 2: (H a)_i = y_i (x_i . w); AUG: + sigma s y_i + shift a_i
 template <int AUG>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
@@ -574,8 +571,9 @@ int SvmDualOp::mult(const double *a, double *Ha)
 }
 
 // w = X'(y o a) by pass 1 alone (the model of a trained SVM)
-int pmh_svm_op_form_w(SvmDualOp *o, const double *a, const double **w_dev)
+int SvmDualOp::form_w(const double *a, const double **w_dev)
 {
+  SvmDualOp *o = this;
   o->next_is = SvmDualOp::NEXT_NONE;
   if (o->n > 0) {
     o->npass++;
@@ -599,7 +597,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_row_vs_labels(int n, const do
 }
 // Under a communicator the answer is joined: every rank takes part in ONE all-reduce of (mismatches, ranks that hold rows, sum of c, sum of c^2), so all ranks
 // decide alike (ranks that disagreed would issue different collectives afterwards) and c must be the same on every rank that holds rows
-int pmh_svm_op_row_is_labels(SvmDualOp *o, pmh_qppf pf, double *c)
+int pmh_svm_op_row_is_labels(SvmDualBase *o, pmh_qppf pf, double *c)
 {
   if (!pf->onerow) return 0;
   pmh_ctx ctx = o->ctx;
@@ -637,16 +635,16 @@ int pmh_svm_op_row_is_labels(SvmDualOp *o, pmh_qppf pf, double *c)
 
 extern "C" int pmh_op_svm_dual_set_terms(pmh_op op, double shift, double sigma)
 {
-  SvmDualOp *o = dynamic_cast<SvmDualOp *>(op);
+  SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
   PMH_ARG(o && shift >= 0.0 && sigma >= 0.0);
   o->shift = shift, o->sigma = sigma;
-  o->next_is = SvmDualOp::NEXT_NONE;
+  o->terms_changed();
   return PMH_SUCCESS;
 }
 
 extern "C" int pmh_op_svm_dual_passes(pmh_op op, long long *passes)
 {
-  SvmDualOp *o = dynamic_cast<SvmDualOp *>(op);
+  SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
   PMH_ARG(o && passes);
   *passes = o->npass;
   return PMH_SUCCESS;

@@ -1,0 +1,294 @@
+// The SVM dual Hessian for samples held in CSR (fp64 values, int32 indices, n rows, any number d of columns):
+//   H = diag(y) X X' diag(y) + shift I + (sigma + sigma_fold) y y',
+// applied matrix-free in two sweeps over the stored entries, as the dense operator of svm.hip:
+//   pass 1  w = X'(y o a)  (d doubles) and, in the augmented form, s = sum_i y_i a_i in the same sweep;
+//   all-reduce of w (d or d + 1 doubles) under a communicator;
+//   pass 2  (H a)_i = y_i (x_i . w) + sigma s y_i + shift a_i  (svm_aug_row).
+// Both passes, the bias pass of the model and prediction are ONE kernel pair, a segmented sum over a compressed array (ptr / idx / val): segments are the
+// samples (the caller's CSR) in pass 2 and in prediction, and the features in pass 1, which runs over a column-ordered device copy built once at creation.
+//
+// Work is divided by stored entries, not by segments: workgroup b owns the SVC_SPAN entries [b SVC_SPAN, (b + 1) SVC_SPAN) (k_svc_seg).  It forms their
+// products with the gathered vector in LDS, sums every segment's piece inside the span with G lanes per segment (G = 1 .. 64, from the span's mean piece
+// length: a span that is one piece of a popular feature is summed by a whole wavefront, a span of three hundred rare features by one lane each) and stores
+// the sums of whole segments.  The at most two pieces it shares with its neighbours (its first segment where that began earlier or goes on, its last where
+// that goes on) go to head[b] / tail[b]; k_svc_fin completes every shared segment in the span where it ends: the pieces of spans b0 .. b1 in this order over the
+// lanes of one wavefront (lane l takes b0 + l, b0 + l + 64, ..), then the fixed shuffle tree.  No float atomics, no order that depends on scheduling: the same
+// input gives the same bits.  Segments without entries lie in exactly one span's range and get the sum 0 (an empty feature: w_c = 0; a sample without
+// entries: (H a)_i = sigma s y_i + shift a_i).
+//
+// The column-ordered copy holds y_i x_ic (the labels are +-1: an exact sign flip), rows ascending inside a column, so pass 1 gathers a alone; one more
+// column, d, holds y_i for every sample, so s = sum_i y_i a_i = w[d] is a segment like the others and a long one like the others.  The plain operator
+// (shift = sigma = sigma_fold = 0) stops the sweep before that column and runs the pass-2 kernel without the extra terms (MODE 1 instead of 2).  The copy
+// costs 12 (nnz + n) bytes of device memory beside the caller's matrix (8 value + 4 row index per entry); the labels are read at creation, not later.
+// The first segment of every span is found once, at creation, by binary search (k_svc_first): 4 bytes per span.
+//
+// Algorithmic bytes of one application: 24 nnz + 4 (n + d) + 8 (3 n + 2 d) (both copies' values and indices, the two pointer arrays, a, y, H a, w written
+// and read); HBM-bound, the gathers of a (pass 1) and w (pass 2) are served by the caches where the vectors fit.
+//
+// Out of scope here: the fused MPGP epilogues of the dense d = 64 path (mult_epi, "paired passes" in svm.hip).  mult_epi returns PMH_EPI_UNSUPPORTED and MPGP
+// runs its separate vector kernels; the ||B u|| rider of the penalised operator is declined too (the one-row projector's own dot runs).
+#include <algorithm>
+
+#include "svm_internal.h"
+#include "reduce.h"
+
+#define SVC_SPAN 2048 // stored entries per workgroup: 8 per thread, 16 KiB of products in LDS (up to 8 workgroups per CU)
+typedef double svc_dbl2 __attribute__((ext_vector_type(2)));
+typedef int    svc_int2 __attribute__((ext_vector_type(2)));
+
+// first[b] = the segment that holds entry b SVC_SPAN (the smallest c with ptr[c + 1] > b SVC_SPAN); first[0] = 0, so that leading empty segments belong to span 0
+__global__ __launch_bounds__(PMH_BLOCK) void k_svc_first(int nb, int nseg, const int *__restrict__ ptr, int *__restrict__ first)
+{
+  const int b = blockIdx.x * PMH_BLOCK + threadIdx.x;
+  if (b >= nb) return;
+  const long long start = (long long)b * SVC_SPAN;
+  int             lo = 0, hi = nseg - 1; // the answer lies in [lo, hi]: ptr[nseg] > start for every span of a non-empty array
+  while (b > 0 && lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (ptr[mid + 1] > start) hi = mid;
+    else lo = mid + 1;
+  }
+  first[b] = b > 0 ? lo : 0;
+}
+
+// what a finished segment sum becomes.  MODE 0: out[c] = sum; 1: out[c] = y_c sum; 2: out[c] = svm_aug_row(y_c, sum, sigma s, shift, a_c)
+struct svc_out {
+  double       *out;
+  const double *y, *a, *s; // s: device scalar (w[d])
+  double        sigma, shift;
+};
+template <int MODE> static __device__ __forceinline__ void svc_store(const svc_out &o, int c, double v, double sS)
+{
+  if (MODE == 0) o.out[c] = v;
+  else if (MODE == 1) o.out[c] = o.y[c] * v;
+  else o.out[c] = svm_aug_row(o.y[c], v, sS, o.shift, o.a[c]);
+}
+
+// the segments of span b: c0 .. c1.  A segment that ends exactly at the span's end is the span's; empty segments at that boundary too
+static __device__ __forceinline__ void svc_range(int b, int nb, int nseg, int end, const int *__restrict__ ptr, const int *__restrict__ first, int &c0, int &c1)
+{
+  c0 = first[b];
+  c1 = nseg - 1;
+  if (b + 1 < nb) {
+    const int cf = first[b + 1];
+    c1           = ptr[cf] == end ? cf - 1 : cf;
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svc_seg(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ x,
+                                                       const int *__restrict__ first, double *__restrict__ head, double *__restrict__ tail, svc_out o)
+{
+  __shared__ double prod[SVC_SPAN];
+  const int         b = blockIdx.x, start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent);
+  // the span's products: 16-byte value and 8-byte index loads (start is even and the arrays are 16-byte aligned), all asked for before the gathers
+  svc_dbl2 v[SVC_SPAN / PMH_BLOCK / 2];
+  svc_int2 ix[SVC_SPAN / PMH_BLOCK / 2];
+#pragma unroll
+  for (int j = 0; j < SVC_SPAN / PMH_BLOCK / 2; j++) {
+    const int k = start + 2 * (j * PMH_BLOCK + (int)threadIdx.x);
+    v[j] = svc_dbl2{0.0, 0.0}, ix[j] = svc_int2{0, 0};
+    if (k + 1 < end) {
+      v[j]  = __builtin_nontemporal_load((const svc_dbl2 *)(val + k));
+      ix[j] = __builtin_nontemporal_load((const svc_int2 *)(idx + k));
+    } else if (k < end) v[j].x = val[k], ix[j].x = idx[k];
+  }
+#pragma unroll
+  for (int j = 0; j < SVC_SPAN / PMH_BLOCK / 2; j++) {
+    const int k = 2 * (j * PMH_BLOCK + (int)threadIdx.x);
+    prod[k]     = v[j].x * x[ix[j].x]; // (entries past the end: 0 * x[0], never read below)
+    prod[k + 1] = v[j].y * x[ix[j].y];
+  }
+  __syncthreads();
+  int c0, c1;
+  svc_range(b, nb, nseg, end, ptr, first, c0, c1);
+  // lanes per segment: the largest power of two <= mean piece length / 4, at most a wavefront
+  const int avg = (end - start) / (c1 - c0 + 1);
+  int       G   = 1;
+  while (G < 64 && G * 8 <= avg) G <<= 1;
+  const int    g = threadIdx.x / G, l = threadIdx.x % G;
+  const double sS = MODE == 2 ? o.sigma * *o.s : 0.0;
+  for (int c = c0 + g; c <= c1; c += PMH_BLOCK / G) { // (the trip count is uniform over a segment's G lanes)
+    const int p0 = ptr[c], p1 = ptr[c + 1], lo = max(p0, start) - start, hi = min(p1, end) - start;
+    double    s = 0.0;
+    for (int k = lo + l; k < hi; k += G) s += prod[k];
+    for (int w = G >> 1; w > 0; w >>= 1) s += __shfl_down(s, w, G);
+    if (l == 0) {
+      if (p0 >= start && p1 <= end) svc_store<MODE>(o, c, s, sS); // the whole segment lies in this span
+      else if (c == c0) head[b] = s;
+      else tail[b] = s;
+    }
+  }
+}
+
+// one wavefront per span: where the span's first segment began in an earlier span and ends in this one, add its pieces in span order and store the segment
+template <int MODE>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svc_fin(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ first, const double *__restrict__ head,
+                                                       const double *__restrict__ tail, svc_out o)
+{
+  const int lane = threadIdx.x & 63, b = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
+  if (b >= nb) return;
+  const int start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent), c = first[b], p0 = ptr[c], p1 = ptr[c + 1];
+  if (!(p0 < start && p1 <= end)) return; // (wave-uniform)
+  const int  b0    = p0 / SVC_SPAN;
+  const bool tail0 = first[b0] != c; // in the span where it begins the segment is the last of several: its piece is that span's tail
+  double     s     = 0.0;
+  for (int bb = b0 + lane; bb <= b; bb += 64) s += (bb == b0 && tail0) ? tail[b0] : head[bb];
+  s = pmh_wave_sum(s);
+  if (lane == 0) svc_store<MODE>(o, c, s, MODE == 2 ? o.sigma * *o.s : 0.0);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------------------
+struct svc_tab { // per compressed array: the spans' first segments and their shared pieces
+  int    *first = nullptr;
+  double *head = nullptr, *tail = nullptr;
+  int     nb = 0;
+};
+static inline int svc_nb(long long nent) { return (int)std::max<long long>(1, (nent + SVC_SPAN - 1) / SVC_SPAN); } // (no entries: one span, every segment sums to 0)
+
+static int svc_tab_free(pmh_ctx ctx, svc_tab *t)
+{
+  if (t->first) pmh_free(ctx, t->first), pmh_free(ctx, t->head), pmh_free(ctx, t->tail);
+  t->first = nullptr, t->head = t->tail = nullptr;
+  return PMH_SUCCESS;
+}
+static int svc_tab_build(pmh_ctx ctx, int nseg, const int *ptr, long long nent, svc_tab *t)
+{
+  t->nb = svc_nb(nent);
+  PMH_CHK(pmh_malloc(ctx, sizeof(int) * (size_t)t->nb, (void **)&t->first));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)t->nb, (void **)&t->head));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)t->nb, (void **)&t->tail));
+  hipLaunchKernelGGL(k_svc_first, dim3((t->nb + PMH_BLOCK - 1) / PMH_BLOCK), dim3(PMH_BLOCK), 0, ctx->stream, t->nb, nseg, ptr, t->first);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+// out[c] = MODE(sum of segment c) for the first nseg segments / nent entries of the array the table was built for
+template <int MODE> static int svc_sweep(pmh_ctx ctx, const svc_tab &t, int nseg, long long nent, const int *ptr, const int *idx, const double *val, const double *x, const svc_out &o)
+{
+  const int nb = std::min(t.nb, svc_nb(nent));
+  hipLaunchKernelGGL(k_svc_seg<MODE>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, (int)nent, nseg, nb, ptr, idx, val, x, (const int *)t.first, t.head, t.tail, o);
+  hipLaunchKernelGGL(k_svc_fin<MODE>, dim3((nb + PMH_BLOCK / 64 - 1) / (PMH_BLOCK / 64)), dim3(PMH_BLOCK), 0, ctx->stream, (int)nent, nseg, nb, ptr, (const int *)t.first, (const double *)t.head,
+                     (const double *)t.tail, o);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+struct SvmCsrOp : SvmDualBase {
+  pmh_csr   X = nullptr; // borrowed: the samples by rows
+  long long nnz = 0;
+  int      *cptr = nullptr, *crow = nullptr; // the column-ordered copy: [d + 2], [nnz + n]
+  double   *cval = nullptr, *w = nullptr;    // [nnz + n] (y_i x_ic; column d: y_i), [d + 1]
+  svc_tab   rows, cols;
+  ~SvmCsrOp() override
+  {
+    pmh_free(ctx, cptr), pmh_free(ctx, crow), pmh_free(ctx, cval), pmh_free(ctx, w);
+    svc_tab_free(ctx, &rows), svc_tab_free(ctx, &cols);
+  }
+  // w[0 .. d) = X'(y o a); with_s: also w[d] = sum_i y_i a_i (the sweep goes on through column d)
+  int pass1(const double *a, bool with_s)
+  {
+    npass++;
+    svc_out o{w, nullptr, nullptr, nullptr, 0.0, 0.0};
+    return svc_sweep<0>(ctx, cols, with_s ? d + 1 : d, with_s ? nnz + n : nnz, cptr, crow, cval, a, o);
+  }
+  int mult(const double *a, double *Ha) override
+  {
+    if (n == 0 && pmh_comm_on(ctx)) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: this rank holds no samples; with a communicator every rank needs at least one row");
+    if (n == 0) return PMH_SUCCESS;
+    const bool AG = aug();
+    PMH_CHK(pass1(a, AG));
+    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d + (AG ? 1 : 0))); // samples sharded over GPUs: the one exchange step, as in the dense operator
+    npass++;
+    svc_out o{Ha, y, a, w + d, sigma + sigma_fold, shift};
+    if (AG) return svc_sweep<2>(ctx, rows, n, nnz, X->d_rowptr, X->d_col, X->d_val, w, o);
+    return svc_sweep<1>(ctx, rows, n, nnz, X->d_rowptr, X->d_col, X->d_val, w, o);
+  }
+  int mult_epi(const double *, double *, const pmh_vec_epi &) override
+  {
+    if (n <= 0 && pmh_comm_on(ctx)) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: this rank holds no samples; with a communicator every rank needs at least one row (an empty shard would skip the collectives the other ranks issue)");
+    return PMH_EPI_UNSUPPORTED;
+  }
+  int form_w(const double *a, const double **w_dev) override
+  {
+    if (n > 0) PMH_CHK(pass1(a, false));
+    else PMH_CHK(pmh_memset(ctx, w, 0, sizeof(double) * (size_t)d));
+    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d));
+    *w_dev = w;
+    return PMH_SUCCESS;
+  }
+};
+
+int pmh_svm_csr_op_row_dots(SvmDualBase *op, const double *wv, double *dots)
+{
+  SvmCsrOp *o = dynamic_cast<SvmCsrOp *>(op);
+  PMH_ARG(o && wv && dots);
+  if (o->n == 0) return PMH_SUCCESS;
+  o->npass++;
+  svc_out so{dots, nullptr, nullptr, nullptr, 0.0, 0.0};
+  return svc_sweep<0>(o->ctx, o->rows, o->n, o->nnz, o->X->d_rowptr, o->X->d_col, o->X->d_val, wv, so);
+}
+
+int pmh_svm_csr_row_dots(pmh_csr X, const double *wv, double *dots)
+{
+  PMH_ARG(X && wv && dots);
+  if (X->nrows == 0) return PMH_SUCCESS;
+  if (X->nnz >= (1LL << 31) - SVC_SPAN) return pmh_set_error(PMH_ERR_ARG, "SVM on CSR samples: %lld stored entries, the count must stay below 2^31 (32-bit offsets)", X->nnz);
+  svc_tab t;
+  int     rc = svc_tab_build(X->ctx, X->nrows, X->d_rowptr, X->nnz, &t);
+  svc_out so{dots, nullptr, nullptr, nullptr, 0.0, 0.0};
+  if (!rc) rc = svc_sweep<0>(X->ctx, t, X->nrows, X->nnz, X->d_rowptr, X->d_col, X->d_val, wv, so);
+  svc_tab_free(X->ctx, &t); // (waits for the stream)
+  return rc;
+}
+
+extern "C" int pmh_op_create_svm_dual_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, pmh_op *op)
+{
+  PMH_ARG(ctx && X && op && y_dev && X->ctx == ctx);
+  const int       n = X->nrows, d = X->ncols;
+  const long long nnz = X->nnz;
+  if (d < 1) return pmh_set_error(PMH_ERR_ARG, "pmh_op_create_svm_dual_csr: the sample matrix has no columns");
+  if (nnz + n >= (1LL << 31) - SVC_SPAN) return pmh_set_error(PMH_ERR_ARG, "pmh_op_create_svm_dual_csr: %lld stored entries and %d samples: the entry count must stay below 2^31 (32-bit offsets)", nnz, n);
+  // the caller's matrix on the host: checked (columns ascending inside a row; their range was checked by pmh_csr_create) and turned by columns
+  std::vector<int>    rp((size_t)n + 1, 0), col((size_t)nnz);
+  std::vector<double> val((size_t)nnz), yh((size_t)n);
+  PMH_CHK(pmh_memcpy_d2h(ctx, rp.data(), X->d_rowptr, sizeof(int) * rp.size()));
+  if (nnz) PMH_CHK(pmh_memcpy_d2h(ctx, col.data(), X->d_col, sizeof(int) * col.size()));
+  if (nnz) PMH_CHK(pmh_memcpy_d2h(ctx, val.data(), X->d_val, sizeof(double) * val.size()));
+  if (n) PMH_CHK(pmh_memcpy_d2h(ctx, yh.data(), y_dev, sizeof(double) * yh.size()));
+  std::vector<int> cp((size_t)d + 2, 0);
+  for (int i = 0; i < n; i++)
+    for (int k = rp[i]; k < rp[i + 1]; k++) {
+      if (col[k] < 0 || col[k] >= d) return pmh_set_error(PMH_ERR_ARG, "pmh_op_create_svm_dual_csr: column index %d of sample %d is outside [0, %d)", col[k], i, d);
+      if (k > rp[i] && col[k] < col[k - 1]) return pmh_set_error(PMH_ERR_ARG, "pmh_op_create_svm_dual_csr: the column indices of sample %d are not sorted (%d after %d)", i, col[k], col[k - 1]);
+      cp[(size_t)col[k] + 1]++;
+    }
+  for (int c = 0; c < d; c++) cp[(size_t)c + 1] += cp[c];
+  cp[(size_t)d + 1] = (int)(nnz + n);
+  std::vector<int>    cr((size_t)(nnz + n)), next(cp.begin(), cp.begin() + d);
+  std::vector<double> cv((size_t)(nnz + n));
+  for (int i = 0; i < n; i++) { // samples in ascending order: rows ascending inside every column
+    for (int k = rp[i]; k < rp[i + 1]; k++) {
+      const int q = next[col[k]]++;
+      cr[q] = i, cv[q] = yh[i] * val[k];
+    }
+    cr[(size_t)nnz + i] = i, cv[(size_t)nnz + i] = yh[i];
+  }
+  SvmCsrOp *o = new SvmCsrOp();
+  o->ctx = ctx, o->n = n, o->d = d, o->y = y_dev, o->X = X, o->nnz = nnz;
+  int rc = PMH_SUCCESS;
+  do {
+    if ((rc = pmh_malloc(ctx, sizeof(int) * cp.size(), (void **)&o->cptr)) || (rc = pmh_malloc(ctx, sizeof(int) * (cr.size() + 2), (void **)&o->crow)) ||
+        (rc = pmh_malloc(ctx, sizeof(double) * (cv.size() + 2), (void **)&o->cval)) || (rc = pmh_malloc(ctx, sizeof(double) * ((size_t)d + 1), (void **)&o->w)))
+      break;
+    if ((rc = pmh_memcpy_h2d(ctx, o->cptr, cp.data(), sizeof(int) * cp.size()))) break;
+    if (!cr.empty() && ((rc = pmh_memcpy_h2d(ctx, o->crow, cr.data(), sizeof(int) * cr.size())) || (rc = pmh_memcpy_h2d(ctx, o->cval, cv.data(), sizeof(double) * cv.size())))) break;
+    if ((rc = pmh_memset(ctx, o->w, 0, sizeof(double) * ((size_t)d + 1)))) break;
+    if (n > 0 && ((rc = svc_tab_build(ctx, n, X->d_rowptr, nnz, &o->rows)) || (rc = svc_tab_build(ctx, d + 1, o->cptr, nnz + n, &o->cols)))) break;
+  } while (0);
+  if (rc) {
+    delete o;
+    return rc;
+  }
+  *op = o;
+  return PMH_SUCCESS;
+}

@@ -1,4 +1,4 @@
-// The dense-row SVM dual operator (svm.hip) as the penalised operator (qppf.hip) and the SVM front end (svm_train.hip) see it.
+// The SVM dual operators (svm.hip: dense rows; svm_csr.hip: CSR) as the penalised operator (qppf.hip) and the SVM front end (svm_train.hip) see them.
 #pragma once
 #include "pmh_internal.h"
 
@@ -10,9 +10,30 @@
     hipLaunchKernelGGL(__VA_ARGS__);  \
   } while (0)
 
-struct SvmDualOp : pmh_op_s {
-  int           d;
-  const double *X, *y;
+// What the penalised operator (qppf.hip) and the front end (svm_train.hip) need of an SVM dual operator, whichever way it holds the samples: dense rows
+// (SvmDualOp, svm.hip) or CSR (SvmCsrOp, svm_csr.hip)
+struct SvmDualBase : pmh_op_s {
+  int           d = 0;
+  const double *y = nullptr;
+  long long     npass = 0; // passes over X so far
+  // augmented Hessian H + shift I + (sigma + sigma_fold) y y' (L2 loss: shift = 1/C; the one-row equality y'a = 0 penalised: sigma_fold = rho c^2 for the
+  // row c y, set by the penalised operator around each of its products, see qppf.hip).  s = sum_i y_i v_i travels with the column sums: w[d].  All three zero:
+  // the kernels of the plain operator, the bits of the plain operator.
+  double        shift = 0.0, sigma = 0.0, sigma_fold = 0.0;
+  bool          aug() const { return shift != 0.0 || sigma != 0.0 || sigma_fold != 0.0; }
+  // ||B u|| of the one-row equality riding on the next product (the penalised operator arms it); an operator that does not serve it leaves aux_done 0 and the
+  // caller's own dot product runs
+  const double *aux_u = nullptr;
+  double       *aux_Gu = nullptr;
+  double        aux_c = 0.0;
+  int           aux_slot = -1, aux_done = 0;
+  // w = X'(y o a) into the operator's own w (d doubles, device; all-reduced under a communicator) by the pass-1 kernels (the model of a trained SVM)
+  virtual int   form_w(const double *a, const double **w_dev) = 0;
+  virtual void  terms_changed() {} // pmh_op_svm_dual_set_terms was called
+};
+
+struct SvmDualOp : SvmDualBase {
+  const double *X;
   double       *w, *part; // w: d; part: [nblocks][d]
   int           nblocks;
   int           mult(const double *a, double *Ha) override;
@@ -26,20 +47,14 @@ struct SvmDualOp : pmh_op_s {
   const double *next_p = nullptr;
   double       *part_next = nullptr, *feas_part = nullptr, *d_afeas = nullptr, *x_spec = nullptr;
   int           grid_epi = 0;
-  long long     npass = 0; // passes over X so far
-  // augmented Hessian H + shift I + (sigma + sigma_fold) y y' (L2 loss: shift = 1/C; the one-row equality y'a = 0 penalised: sigma_fold = rho c^2 for the
-  // row c y, set by the penalised operator around each of its products, see qppf.hip).  s = sum_i y_i v_i travels with the column sums: w[d] (and one entry per
-  // workgroup beside part / part_next).  All three zero: the kernels of the plain operator (template argument AUG = 0), the bits of the plain operator.
-  double        shift = 0.0, sigma = 0.0, sigma_fold = 0.0;
+  // the augmented forms (SvmDualBase): s = sum_i y_i v_i is w[d] and one entry per workgroup beside part / part_next; template argument AUG = 0: the plain kernels
   double       *spart = nullptr, *spart_next = nullptr; // [nblocks] / [grid_epi] partial sums of s
-  bool          aug() const { return shift != 0.0 || sigma != 0.0 || sigma_fold != 0.0; }
-  // ||B u|| of the one-row equality riding on the next product (the penalised operator arms it): sum_i y_i u_i taken where the rows' y_i are in registers
-  // anyway, finished by k_svm_aux_finish: Gu[0] = c sum, (c sum)^2 -> scalar slot.  One GPU only (the caller falls back to the projector's own dot otherwise)
-  const double *aux_u = nullptr;
-  double       *aux_Gu = nullptr, *aux_part = nullptr;
-  double        aux_c = 0.0;
-  int           aux_slot = -1, aux_done = 0;
+  // the ||B u|| rider: sum_i y_i u_i taken where the rows' y_i are in registers anyway, finished by k_svm_aux_finish: Gu[0] = c sum, (c sum)^2 -> scalar slot.
+  // One GPU only (the caller falls back to the projector's own dot otherwise)
+  double       *aux_part = nullptr;
   int           aux_finish(int nb);
+  int           form_w(const double *a, const double **w_dev) override;
+  void          terms_changed() override { next_is = NEXT_NONE; }
   ~SvmDualOp() override
   {
     pmh_free(ctx, w);
@@ -51,7 +66,14 @@ struct SvmDualOp : pmh_op_s {
 };
 
 
-// svm.hip, for the front end: w = X'(y o a) into the operator's own w (d doubles, device; all-reduced under a communicator) by the pass-1 kernels
-int pmh_svm_op_form_w(SvmDualOp *o, const double *a, const double **w_dev);
+// the augmented row result: (y_i (x_i . w) + (sigma s) y_i) + shift a_i, in this order (s = w[d])
+static __device__ __forceinline__ double svm_aug_row(double yi, double dot, double sS, double shift, double ai) { return (yi * dot + sS * yi) + shift * ai; }
+
 // 1 (and c, with row = c y) if pf is a one-row projector whose row is a multiple of this operator's labels, entry by entry
-int pmh_svm_op_row_is_labels(SvmDualOp *o, pmh_qppf pf, double *c);
+int pmh_svm_op_row_is_labels(SvmDualBase *o, pmh_qppf pf, double *c);
+
+// ---- svm_csr.hip: samples in CSR --------------------------------------------------------------------------------------------------------------------
+// dots[i] = x_i . w for the rows of X (one sweep over its stored entries, work divided by entries; w: X->ncols doubles, dots: X->nrows doubles, device)
+int pmh_svm_csr_row_dots(pmh_csr X, const double *w, double *dots);
+// the same for the operator's own samples, with the tables it already holds; counted as a pass
+int pmh_svm_csr_op_row_dots(SvmDualBase *op, const double *w, double *dots);

@@ -1,10 +1,11 @@
-// SVM front end (PermonSVM's role: train, model, predict) over the dense-row dual operator of svm.hip:
+// SVM front end (PermonSVM's role: train, model, predict) over the dual operators of svm.hip (dense rows) and svm_csr.hip (samples in CSR):
 //   L1: min 1/2 a'Ha - 1'a,          0 <= a <= C   (primal 1/2 |w|^2 + C sum xi)
 //   L2: min 1/2 a'(H + I/C)a - 1'a,  0 <= a        (primal 1/2 |w|^2 + C/2 sum xi^2)
 //   bias: additionally y'a = 0, posed as (y / sqrt(n))'a = 0 -- a one-row projector (onerow.hip) under SMALXE, whose penalty term the operator absorbs (qppf.hip)
 // H = diag(y) X X' diag(y).  No bias: MPGP on the box alone.  Model: w = X'(y o a) by the operator's pass-1 kernels; b by one pass over X (k_svm_bias);
 // prediction by one pass over the test samples (k_svm_predict: one wavefront per row, lane j owns columns j, j + 64, ...: any d the operator accepts;
-// k_svm_predict64 for d = 64: the two-rows-per-wave layout of the operator's own pass 2).
+// k_svm_predict64 for d = 64: the two-rows-per-wave layout of the operator's own pass 2).  Samples in CSR: x_i . w by the entry-balanced sweep of svm_csr.hip
+// (one pass over the stored entries), then one kernel over the n dot products (k_svm_bias_dots, k_svm_predict_dots).
 #include <cmath>
 
 #include "svm_internal.h"
@@ -15,6 +16,8 @@ struct pmh_svm_s {
   int           n, d;
   long long     n_global;
   const double *X, *y;
+  pmh_csr       Xcsr = nullptr; // the samples in CSR (then X == nullptr), borrowed
+  double       *dots = nullptr; // CSR: x_i . w of the training samples (n doubles, allocated by the first model)
   pmh_svm_opts  o;
   pmh_op        H     = nullptr;
   pmh_qppf      pf    = nullptr;
@@ -166,6 +169,49 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double
   }
 }
 
+// ---- samples in CSR: the same sums as k_svm_bias / k_svm_predict from the rows' dot products x_i . w (svm_csr.hip), one entry per thread ----
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias_dots(int n, const double *__restrict__ dots, const double *__restrict__ y, const double *__restrict__ alpha, double astol, double ubound,
+                                                             double *__restrict__ part)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  double            sb = 0.0, sya = 0.0, nf = 0.0, ns = 0.0;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const double ai = alpha[i], yi = y[i];
+    sya += yi * ai;
+    if (ai > astol) {
+      ns += 1.0;
+      if (!(ubound > 0.0) || ai < ubound - astol) nf += 1.0, sb += yi - dots[i];
+    }
+  }
+  const double r0 = pmh_block_reduce<PMH_RED_SUM>(sb, red), r1 = pmh_block_reduce<PMH_RED_SUM>(sya, red), r2 = pmh_block_reduce<PMH_RED_SUM>(nf, red), r3 = pmh_block_reduce<PMH_RED_SUM>(ns, red);
+  if (threadIdx.x == 0) {
+    const size_t g = gridDim.x;
+    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
+  }
+}
+// (dots and scores may be the same array)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict_dots(int n, const double *dots, double b, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, double *__restrict__ part)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  double            tp = 0.0, fp = 0.0, tn = 0.0, fn = 0.0;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const double s = dots[i] + b, l = s >= 0.0 ? 1.0 : -1.0;
+    if (scores) scores[i] = s;
+    if (labels) labels[i] = l;
+    if (ytrue) {
+      const bool pos = ytrue[i] > 0.0;
+      if (l > 0.0) (pos ? tp : fp) += 1.0;
+      else (pos ? fn : tn) += 1.0;
+    }
+  }
+  if (!ytrue) return; // (uniform: a kernel argument)
+  const double r0 = pmh_block_reduce<PMH_RED_SUM>(tp, red), r1 = pmh_block_reduce<PMH_RED_SUM>(fp, red), r2 = pmh_block_reduce<PMH_RED_SUM>(tn, red), r3 = pmh_block_reduce<PMH_RED_SUM>(fn, red);
+  if (threadIdx.x == 0) {
+    const size_t g = gridDim.x;
+    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
+  }
+}
+
 extern "C" int pmh_svm_default_opts(pmh_svm_opts *o)
 {
   PMH_ARG(o);
@@ -185,26 +231,26 @@ extern "C" int pmh_svm_destroy(pmh_svm s)
   if (s->sx) pmh_smalxe_destroy(s->sx);
   if (s->pf) pmh_qppf_destroy(s->pf);
   if (s->H) pmh_op_destroy(s->H);
-  double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal};
+  double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal, s->dots};
   for (double *p : v)
     if (p) pmh_free(s->ctx, p);
   delete s;
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
+// X_dev (dense rows) or Xcsr
+static int svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_csr Xcsr, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
 {
-  PMH_ARG(ctx && out && opts && n_local >= 0 && d >= 1 && d <= 64 * SVM_KMAX && X_dev && y_dev);
   if (opts->loss_type != PMH_SVM_LOSS_L1 && opts->loss_type != PMH_SVM_LOSS_L2) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: unknown loss type %d (PMH_SVM_LOSS_L1 | PMH_SVM_LOSS_L2)", opts->loss_type);
   if (!(opts->C > 0.0)) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: C = %g, must be positive", opts->C);
   pmh_svm s = new pmh_svm_s();
-  s->ctx = ctx, s->n = n_local, s->d = d, s->X = X_dev, s->y = y_dev, s->o = *opts;
+  s->ctx = ctx, s->n = n_local, s->d = d, s->X = X_dev, s->Xcsr = Xcsr, s->y = y_dev, s->o = *opts;
   memset(&s->st, 0, sizeof(s->st));
   const int    n  = n_local;
   const size_t nb = sizeof(double) * (size_t)(n ? n : 1);
   int          rc = PMH_SUCCESS;
   do {
-    if ((rc = pmh_op_create_svm_dual(ctx, n, d, X_dev, y_dev, &s->H))) break;
+    if ((rc = Xcsr ? pmh_op_create_svm_dual_csr(ctx, Xcsr, y_dev, &s->H) : pmh_op_create_svm_dual(ctx, n, d, X_dev, y_dev, &s->H))) break;
     if (opts->loss_type == PMH_SVM_LOSS_L2 && (rc = pmh_op_svm_dual_set_terms(s->H, 1.0 / opts->C, 0.0))) break;
     if ((rc = pmh_malloc(ctx, nb, (void **)&s->alpha)) || (rc = pmh_malloc(ctx, nb, (void **)&s->rhs)) || (rc = pmh_malloc(ctx, nb, (void **)&s->lb))) break;
     if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)d, (void **)&s->w)) || (rc = pmh_malloc(ctx, sizeof(double) * 4 * PMH_MAX_VEC_BLOCKS, (void **)&s->part)) || (rc = pmh_malloc(ctx, sizeof(double) * 8, (void **)&s->scal))) break;
@@ -248,18 +294,37 @@ extern "C" int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_d
   return PMH_SUCCESS;
 }
 
+extern "C" int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
+{
+  PMH_ARG(ctx && out && opts && n_local >= 0 && d >= 1 && d <= 64 * SVM_KMAX && X_dev && y_dev);
+  return svm_create(ctx, n_local, d, X_dev, nullptr, y_dev, opts, out);
+}
+
+extern "C" int pmh_svm_create_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
+{
+  PMH_ARG(ctx && out && opts && X && y_dev && X->ctx == ctx);
+  if (X->ncols < 1) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create_csr: the sample matrix has no columns");
+  return svm_create(ctx, X->nrows, X->ncols, nullptr, X, y_dev, opts, out);
+}
+
 // w, b and the counts from the current alpha
 static int svm_model(pmh_svm s)
 {
   pmh_ctx       ctx = s->ctx;
-  SvmDualOp    *H   = static_cast<SvmDualOp *>(s->H);
+  SvmDualBase  *H   = static_cast<SvmDualBase *>(s->H);
   const double *w   = nullptr;
-  PMH_CHK(pmh_svm_op_form_w(H, s->alpha, &w));
+  PMH_CHK(H->form_w(s->alpha, &w));
   PMH_CHK(pmh_vec_copy(ctx, s->d, w, s->w));
   s->h_w.resize((size_t)s->d);
   const int    nb    = SVM_NB(s->n);
   const double astol = s->sx ? s->o.smalxe.inner.astol : s->o.mpgp.astol;
-  if (s->n > 0) {
+  if (s->n > 0 && s->Xcsr) {
+    if (!s->dots) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)s->n, (void **)&s->dots));
+    PMH_CHK(pmh_svm_csr_op_row_dots(H, s->w, s->dots));
+    hipLaunchKernelGGL(k_svm_bias_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, (const double *)s->dots, s->y, (const double *)s->alpha, astol, s->o.loss_type == PMH_SVM_LOSS_L1 ? s->o.C : 0.0, s->part);
+    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, ctx->stream, nb, 4, (const double *)s->part, s->scal);
+    PMH_HIP(hipGetLastError());
+  } else if (s->n > 0) {
     H->npass++;
     hipLaunchKernelGGL(k_svm_bias, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, s->o.loss_type == PMH_SVM_LOSS_L1 ? s->o.C : 0.0, s->part);
     hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, ctx->stream, nb, 4, (const double *)s->part, s->scal);
@@ -347,12 +412,25 @@ extern "C" int pmh_svm_get_solver(pmh_svm s, pmh_op *H, pmh_qppf *pf, pmh_mpgp *
   return PMH_SUCCESS;
 }
 
-static int svm_predict(pmh_svm s, int n, const double *X, double *scores, double *labels, const double *ytrue, long long *counts)
+// X (dense rows, n x d) or Xt (CSR)
+static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts)
 {
-  PMH_ARG(s && n >= 0 && (X || n == 0));
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict: call pmh_svm_train first");
+  if (Xt && Xt->ncols != s->d) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict_csr: the test samples have %d features, the model has %d", Xt->ncols, s->d);
+  if (!Xt && s->d > 64 * SVM_KMAX) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict: dense test samples need d <= %d, the model has d = %d: hand them over in CSR (pmh_svm_predict_csr)", 64 * SVM_KMAX, s->d);
   const int nb = SVM_NB(n);
-  if (n > 0) {
+  if (n > 0 && Xt) {
+    double *dots = scores; // the dot products land where the scores go; without scores in a buffer of this call
+    if (!dots) PMH_CHK(pmh_malloc(s->ctx, sizeof(double) * (size_t)n, (void **)&dots));
+    int rc = pmh_svm_csr_row_dots(Xt, s->w, dots);
+    if (!rc) {
+      hipLaunchKernelGGL(k_svm_predict_dots, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, (const double *)dots, s->b, scores, labels, ytrue, s->part);
+      if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_predict_csr: the launch failed");
+    }
+    if (!scores) pmh_free(s->ctx, dots);
+    PMH_CHK(rc);
+  } else if (n > 0) {
     if (s->d == 64) hipLaunchKernelGGL(k_svm_predict64, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part);
     else hipLaunchKernelGGL(k_svm_predict, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, s->d, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part);
     PMH_HIP(hipGetLastError());
@@ -369,10 +447,22 @@ static int svm_predict(pmh_svm s, int n, const double *X, double *scores, double
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_svm_predict(pmh_svm s, int n, const double *X_dev, double *scores_dev, double *labels_dev) { return svm_predict(s, n, X_dev, scores_dev, labels_dev, nullptr, nullptr); }
+extern "C" int pmh_svm_predict(pmh_svm s, int n, const double *X_dev, double *scores_dev, double *labels_dev) { return svm_predict(s, n, X_dev, nullptr, scores_dev, labels_dev, nullptr, nullptr); }
+
+extern "C" int pmh_svm_predict_csr(pmh_svm s, pmh_csr Xt, double *scores_dev, double *labels_dev)
+{
+  PMH_ARG(s && Xt);
+  return svm_predict(s, Xt->nrows, nullptr, Xt, scores_dev, labels_dev, nullptr, nullptr);
+}
+
+extern "C" int pmh_svm_test_csr(pmh_svm s, pmh_csr Xt, const double *y_dev, long long counts[4])
+{
+  PMH_ARG(s && Xt && y_dev && counts);
+  return svm_predict(s, Xt->nrows, nullptr, Xt, nullptr, nullptr, y_dev, counts);
+}
 
 extern "C" int pmh_svm_test(pmh_svm s, int n, const double *X_dev, const double *y_dev, long long counts[4])
 {
   PMH_ARG(y_dev && counts);
-  return svm_predict(s, n, X_dev, nullptr, nullptr, y_dev, counts);
+  return svm_predict(s, n, X_dev, nullptr, nullptr, nullptr, y_dev, counts);
 }

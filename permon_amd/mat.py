@@ -654,15 +654,39 @@ class PCDualDirichletOp(Op):
         return n.value, ms.value
 
 
+def csr_from_scipy(ctx, X):
+    """A scipy.sparse matrix as a CsrMat: CSR with sorted indices, fp64 values, int32 indices (the caller's matrix is not modified)."""
+    X = X.tocsr().astype(np.float64)
+    if not X.has_sorted_indices:
+        X = X.sorted_indices()
+    if X.nnz >= 2 ** 31:
+        raise ValueError("%d stored entries: the library's CSR matrices hold fewer than 2^31" % X.nnz)
+    return CsrMat(ctx, X.shape[0], X.shape[1], X.indptr, X.indices, X.data)
+
+
+def is_sparse(X):
+    """True for a scipy.sparse matrix or array (anything with tocsr), without importing scipy for an ndarray."""
+    return hasattr(X, "tocsr")
+
+
 def MatCreateSVMDual(ctx, X, y):
-    """Matrix-free H = diag(y) X X' diag(y) of the hinge-loss SVM dual (BASELINE configs[4]); X: (n_local, d) row-major."""
-    X = np.ascontiguousarray(X, dtype=np.float64)
-    n, d = X.shape
-    Xd = Vec.from_numpy(ctx, X.ravel())
-    yd = Vec.from_numpy(ctx, y)
-    h = C.c_void_p()
-    check(ctx.L.pmh_op_create_svm_dual(ctx.h, n, d, Xd.p, yd.p, C.byref(h)))
-    op = Op(ctx, h, n, keep=[Xd, yd])
+    """Matrix-free H = diag(y) X X' diag(y) of the hinge-loss SVM dual (BASELINE configs[4]); X: (n_local, d) row-major ndarray (d <= 256), or a scipy.sparse
+    matrix of any width (pmh_op_create_svm_dual_csr: two sweeps over the stored entries per product)."""
+    if is_sparse(X):
+        Xc = csr_from_scipy(ctx, X)
+        n = Xc.nrows
+        yd = Vec.from_numpy(ctx, y)
+        h = C.c_void_p()
+        check(ctx.L.pmh_op_create_svm_dual_csr(ctx.h, Xc.h, yd.p, C.byref(h)))
+        op = Op(ctx, h, n, keep=[Xc, yd])
+    else:
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n, d = X.shape
+        Xd = Vec.from_numpy(ctx, X.ravel())
+        yd = Vec.from_numpy(ctx, y)
+        h = C.c_void_p()
+        check(ctx.L.pmh_op_create_svm_dual(ctx.h, n, d, Xd.p, yd.p, C.byref(h)))
+        op = Op(ctx, h, n, keep=[Xd, yd])
 
     def passes():
         """How many times the operator has streamed X so far (pmh_op_svm_dual_passes)."""

@@ -6,7 +6,7 @@ CSR arrays (int32 indices, fp64 values) + vectors.  No solver code lives here.
 """
 import numpy as np
 
-__all__ = ["ex1", "ex2", "ex3_primal", "jbearing2", "laplace2d_box", "laplace2d_csr", "svm_dual"]
+__all__ = ["ex1", "ex2", "ex3_primal", "jbearing2", "laplace2d_box", "laplace2d_csr", "svm_dual", "svm_sparse"]
 
 
 def _fobst(i, n):
@@ -225,6 +225,42 @@ def svm_offset(N, d=64, offset=3.0, C=1.0, seed_x=7, seed_w=8, seed_test=None, N
     if N_test > 0:
         rt = np.random.default_rng(seed_x + 1000 if seed_test is None else seed_test)
         Xt = rt.standard_normal((N_test, d))
+        yt = np.sign(Xt @ w + offset + 0.1 * rt.standard_normal(N_test))
+        yt[yt == 0] = 1.0
+        out.update(X_test=Xt, y_test=yt)
+    return out
+
+
+def svm_sparse(N, d, nnz_row, skew, offset, C=1.0, seed=7, N_test=0):
+    """Sparse, wide samples with skewed feature popularity (text / click data): per sample nnz_row feature draws with probability proportional to
+    1 / rank^skew, values N(0,1), duplicates summed, rows scaled to unit length (default_rng(seed)); w* ~ N(0,1) from default_rng(seed + 1);
+    y = sign(X w* + offset + 0.1 N(0,1)).  N_test > 0: a held-out draw from default_rng(seed + 1000).  The keys of svm_offset, X (and X_test) scipy CSR."""
+    import scipy.sparse as sp
+
+    p = 1.0 / np.arange(1, d + 1) ** skew
+    p /= p.sum()
+
+    def draw(r, n):
+        cols = r.choice(d, size=(n, nnz_row), p=p)
+        vals = r.standard_normal((n, nnz_row))
+        X = sp.csr_matrix((vals.ravel(), (np.repeat(np.arange(n), nnz_row), cols.ravel())), shape=(n, d))
+        X.sum_duplicates()
+        X.sort_indices()
+        nr = np.sqrt(np.asarray(X.multiply(X).sum(axis=1)).ravel())
+        nr[nr == 0] = 1.0
+        X = (sp.diags(1.0 / nr) @ X).tocsr()
+        X.sort_indices()  # (the product does not promise them sorted; the values are the same either way)
+        return X
+
+    rng = np.random.default_rng(seed)
+    X = draw(rng, N)
+    w = np.random.default_rng(seed + 1).standard_normal(d)
+    y = np.sign(X @ w + offset + 0.1 * rng.standard_normal(N))
+    y[y == 0] = 1.0
+    out = dict(n=N, d=d, X=X, y=y, C=float(C), offset=float(offset), w_star=w, b=np.ones(N), lb=np.zeros(N), ub=np.full(N, float(C)), x0=np.zeros(N))
+    if N_test > 0:
+        rt = np.random.default_rng(seed + 1000)
+        Xt = draw(rt, N_test)
         yt = np.sign(Xt @ w + offset + 0.1 * rt.standard_normal(N_test))
         yt[yt == 0] = 1.0
         out.update(X_test=Xt, y_test=yt)

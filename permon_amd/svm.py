@@ -4,7 +4,8 @@
     L2: min 1/2 a'(H + I/C)a - 1'a,  0 <= a
     bias: additionally y'a = 0 (SMALXE over a one-row projector; without bias MPGP alone)
 
-H = diag(y) X X' diag(y).  Everything is computed by libpermonhip.so; there is no CPU fallback."""
+H = diag(y) X X' diag(y).  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width (kept in CSR on the device: 24 bytes per stored entry for
+the two orderings the operator sweeps).  Everything is computed by libpermonhip.so; there is no CPU fallback."""
 import ctypes as ct
 
 import numpy as np
@@ -12,6 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .core import Vec
+from .mat import csr_from_scipy, is_sparse
 
 
 class SVM:
@@ -36,8 +38,19 @@ class SVM:
         return a if isinstance(a, Vec) else Vec.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.float64).ravel())
 
     def create(self, X, y):
-        """Set the training samples (X: (n, d) row-major, y: +-1) and build the solver without training."""
+        """Set the training samples (X: (n, d) row-major ndarray or scipy.sparse matrix, y: +-1) and build the solver without training."""
         self.destroy()
+        if is_sparse(X):
+            self.n, self.d = X.shape
+            Xd, yd = csr_from_scipy(self.ctx, X), self._dev(y)
+            h = ct.c_void_p()
+            try:
+                check(self.L.pmh_svm_create_csr(self.ctx.h, Xd.h, yd.p, self.opts, ct.byref(h)))
+            except Exception:
+                Xd.destroy(), yd.free()
+                raise
+            self.h, self._keep = h, (Xd, yd)
+            return self
         X = np.ascontiguousarray(X, dtype=np.float64)
         self.n, self.d = X.shape
         Xd, yd = self._dev(X), self._dev(y)
@@ -98,6 +111,22 @@ class SVM:
 
     def _predict(self, X, want_scores, want_labels):
         self._need()
+        if is_sparse(X):
+            if X.shape[1] != self.d:
+                raise ValueError("SVM: X must be (n, %d)" % self.d)
+            n = X.shape[0]
+            Xd = csr_from_scipy(self.ctx, X)
+            s = Vec(self.ctx, n, zero=False) if want_scores else None
+            l = Vec(self.ctx, n, zero=False) if want_labels else None
+            try:
+                check(self.L.pmh_svm_predict_csr(self.h, Xd.h, s.p if s else None, l.p if l else None))
+                out = (s.to_numpy() if s else None, l.to_numpy() if l else None)
+            finally:
+                Xd.destroy()
+                for v in (s, l):
+                    if v is not None:
+                        v.free()
+            return out
         X = np.ascontiguousarray(X, dtype=np.float64)
         if X.ndim != 2 or X.shape[1] != self.d:
             raise ValueError("SVM: X must be (n, %d)" % self.d)
@@ -121,12 +150,20 @@ class SVM:
     def test(self, X, y):
         """Confusion counts of the predicted labels against y: dict(TP, FP, TN, FN, accuracy)."""
         self._need()
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        n = X.shape[0]
-        Xd, yd = self._dev(X), self._dev(y)
         cnt = (ct.c_longlong * 4)()
-        check(self.L.pmh_svm_test(self.h, n, Xd.p, yd.p, cnt))
-        Xd.free(), yd.free()
+        if is_sparse(X):
+            n = X.shape[0]
+            Xd, yd = csr_from_scipy(self.ctx, X), self._dev(y)
+            try:
+                check(self.L.pmh_svm_test_csr(self.h, Xd.h, yd.p, cnt))
+            finally:
+                Xd.destroy(), yd.free()
+        else:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+            n = X.shape[0]
+            Xd, yd = self._dev(X), self._dev(y)
+            check(self.L.pmh_svm_test(self.h, n, Xd.p, yd.p, cnt))
+            Xd.free(), yd.free()
         tp, fp, tn, fn = (int(c) for c in cnt)
         return dict(TP=tp, FP=fp, TN=tn, FN=fn, accuracy=(tp + tn) / n if n else float("nan"))
 
@@ -135,5 +172,54 @@ class SVM:
             self.L.pmh_svm_destroy(self.h)
             self.h = None
             for v in self._keep or ():
-                v.free()
+                v.destroy() if hasattr(v, "destroy") else v.free()
             self._keep = None
+
+
+def load_svmlight(path, n_features=None, zero_based="auto"):
+    """Read a file in the svmlight / libsvm text format, `label idx:val idx:val ...` per sample, into (X, y): X a scipy.sparse CSR matrix (fp64, int32, sorted
+    indices, duplicates summed), y in {-1, +1}.  Text after `#` is a comment; `qid:` tokens are ignored; a sample may have no feature.  The labels must take
+    exactly two distinct values: the smaller becomes -1, the larger +1.  zero_based: True / False, or "auto" (one-based unless an index 0 occurs).
+    n_features: the width of X (default: the largest index + 1 after the shift); an index beyond it is an error."""
+    import scipy.sparse as sp
+
+    labels, indptr, idx, val = [], [0], [], []
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            t = line.split("#", 1)[0].split()
+            if not t:
+                continue
+            try:
+                labels.append(float(t[0]))
+                for tok in t[1:]:
+                    k, v = tok.split(":", 1)
+                    if k == "qid":
+                        continue
+                    idx.append(int(k))
+                    val.append(float(v))
+            except ValueError:
+                raise ValueError("%s:%d: not in the svmlight format: %r" % (path, ln, line.strip())) from None
+            indptr.append(len(idx))
+    idx = np.asarray(idx, dtype=np.int64)
+    if idx.size and idx.min() < 0:
+        raise ValueError("%s: negative feature index" % path)
+    if zero_based == "auto":
+        zero_based = bool(idx.size and idx.min() == 0)
+    if not zero_based:
+        if idx.size and idx.min() < 1:
+            raise ValueError("%s: feature index 0 in a one-based file" % path)
+        idx = idx - 1
+    d = int(idx.max()) + 1 if idx.size else 0
+    if n_features is not None:
+        if d > n_features:
+            raise ValueError("%s: feature index %d with n_features = %d" % (path, d - 1, n_features))
+        d = int(n_features)
+    lab = np.asarray(labels, dtype=np.float64)
+    u = np.unique(lab)
+    if u.size != 2:
+        raise ValueError("%s: %d distinct labels, a binary classifier needs exactly two" % (path, u.size))
+    y = np.where(lab == u[1], 1.0, -1.0)
+    X = sp.csr_matrix((np.asarray(val, dtype=np.float64), idx.astype(np.int32), np.asarray(indptr, dtype=np.int32)), shape=(lab.size, d))
+    X.sum_duplicates()
+    X.sort_indices()
+    return X, y
