@@ -10,6 +10,7 @@
 #include "box_inline.h"
 
 #include "svm_internal.h"
+#include "svm_rows.h"
 
 // pass 1: per-workgroup partial of w = sum_i (y_i a_i) x_i ; one wavefront per row, lane j owns columns j, j+64, ...
 // AUG: also s = sum_i y_i a_i (-> spart[workgroup]) and, where u is given, sum_i y_i u_i (-> upart[workgroup]); every lane of a wave holds the same two sums
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double
 }
 
 // w[c] = sum over workgroups of part[b][c], one wavefront per column, fixed order; spart != nullptr: one column more, w[d] = sum over workgroups of spart[b]
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart)
+static __device__ __forceinline__ void svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart)
 {
   const int lane = threadIdx.x & 63, c = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
   if (c >= d + (spart ? 1 : 0)) return;
@@ -70,6 +71,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, co
   v = pmh_wave_sum(v);
   if (lane == 0) w[c] = v;
 }
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart) { svm_colsum(nblocks, d, part, w, spart); }
 
 // pass 2: (H a)_i = y_i (x_i . w); AUG: + sigma s y_i + shift a_i
 template <int AUG>
@@ -77,26 +79,29 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double 
                                                      const double *__restrict__ a, double sigma, double shift)
 {
   const double sS = AUG ? sigma * w[d] : 0.0;
-  const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  double          wr[SVM_KMAX];
-#pragma unroll
-  for (int k = 0; k < SVM_KMAX; k++) wr[k] = (lane + 64 * k < d) ? w[lane + 64 * k] : 0.0;
-  for (long long i = gw; i < n; i += nw) {
-    const double *xr = X + (size_t)i * d;
-    double        s  = 0.0;
-#pragma unroll
-    for (int k = 0; k < SVM_KMAX; k++) {
-      const int c = lane + 64 * k;
-      if (c < d) s += __builtin_nontemporal_load(&xr[c]) * wr[k];
-    }
-    s = pmh_wave_sum(s);
-    if (lane == 0) Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s;
-  }
+  svm_sweep_rows(n, d, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s; });
 }
 
-// ---- d == 64 fast path: 16-byte loads, two rows per wave-instruction (lanes 0-31 row r, lanes 32-63 row r+1), 4-fold unroll ----
-typedef double dbl2 __attribute__((ext_vector_type(2))); // native 16-byte vector: accepted by the non-temporal builtins
+// ---- d == 64 fast path: the two-rows-per-wave-instruction layout of svm_rows.h, 4-fold unroll ----
+// the two column sums a lane holds (columns 2 l2, 2 l2 + 1 of the rows its half of the wave visited) -> part[workgroup][64]: lanes l and l + 32 hold the same
+// two columns of different rows: fold, then across the 4 waves in order
+static __device__ __forceinline__ void svm_fold_cols(double a0, double a1, double (*lds)[64], double *__restrict__ part)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
+  a0 += __shfl_down(a0, 32, 64);
+  a1 += __shfl_down(a1, 32, 64);
+  if (half == 0) {
+    lds[wave][2 * l2]     = a0;
+    lds[wave][2 * l2 + 1] = a1;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    double v = lds[0][threadIdx.x];
+#pragma unroll
+    for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v += lds[wv][threadIdx.x];
+    part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
+  }
+}
 template <int SVM_UNR, int AUG>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
                                                         double *__restrict__ spart, const double *__restrict__ uu, double *__restrict__ upart)
@@ -127,20 +132,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__r
       a1 += s[u] * v[u].y;
     }
   }
-  // lanes l and l+32 hold the same two columns (2*l2, 2*l2+1) of different rows: fold, then across the 4 waves in order
-  a0 += __shfl_down(a0, 32, 64);
-  a1 += __shfl_down(a1, 32, 64);
-  if (half == 0) {
-    lds[wave][2 * l2]     = a0;
-    lds[wave][2 * l2 + 1] = a1;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    double v = lds[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v += lds[wv][threadIdx.x];
-    part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
-  }
+  svm_fold_cols(a0, a1, lds, part);
   if (AUG) {
     const double r0 = pmh_block_reduce<PMH_RED_SUM>(as, red), r1 = pmh_block_reduce<PMH_RED_SUM>(au, red);
     if (threadIdx.x == 0) {
@@ -155,25 +147,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__re
                                                        const double *__restrict__ a, double sigma, double shift)
 {
   const double sS = AUG ? sigma * w[64] : 0.0;
-  const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
-  const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  const dbl2      wr = ((const dbl2 *)w)[l2];
-  for (long long r0 = gw * 2 * SVM_UNR; r0 < n; r0 += nw * 2 * SVM_UNR) {
-    dbl2 v[SVM_UNR];
-#pragma unroll
-    for (int u = 0; u < SVM_UNR; u++) {
-      const long long i = r0 + 2 * u + half;
-      v[u] = (i < n) ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
-    }
-#pragma unroll
-    for (int u = 0; u < SVM_UNR; u++) {
-      const long long i = r0 + 2 * u + half;
-      double          s = v[u].x * wr.x + v[u].y * wr.y;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) s += __shfl_down(s, o, 32);
-      if (l2 == 0 && i < n) Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s;
-    }
-  }
+  svm_sweep_rows64<SVM_UNR>(n, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s; });
 }
 
 // ---- paired passes -------------------------------------------------------------------------------------------------------------------------
@@ -188,32 +162,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__re
 // A run of expansion steps costs two passes over X per step instead of four; a CG or proportioning step discards the prepared sums and pays the usual passes.
 // The driver says what is fresh (pmh_vec_epi::p_fresh / spec_alpha / x_from_spec); the partial sums of the MPGP reductions go to the same rows of the context's
 // partials as the separate Vec kernels write, one entry per workgroup of pmh_vec_grid(n) (the elements a workgroup sums are other ones: same values to
-// rounding). the two column sums a lane holds (columns 2 l2, 2 l2 + 1 of the rows its half of the wave visited) -> part[workgroup][64], as k_svm_xt64
-static __device__ __forceinline__ void svm_fold_cols(double a0, double a1, double (*lds)[64], double *__restrict__ part)
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
-  a0 += __shfl_down(a0, 32, 64);
-  a1 += __shfl_down(a1, 32, 64);
-  if (half == 0) {
-    lds[wave][2 * l2]     = a0;
-    lds[wave][2 * l2 + 1] = a1;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    double v = lds[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v += lds[wv][threadIdx.x];
-    part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
-  }
-}
-// the row's dot product in the first lane of its half-wave (the tree of k_svm_x64)
-static __device__ __forceinline__ double svm_row_dot(dbl2 v, dbl2 wr)
-{
-  double s = v.x * wr.x + v.y * wr.y;
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) s += __shfl_down(s, o, 32);
-  return s;
-}
+// rounding).
 
 struct svm_grad_args {
   const double *b, *x_in, *lb, *ub;
@@ -238,11 +187,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
   double            a0 = 0.0, a1 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, m = INFINITY, ts = 0.0;
   for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
     dbl2 v[SVM_EU];
-#pragma unroll
-    for (int u = 0; u < SVM_EU; u++) {
-      const long long i = r0 + 2 * u + half;
-      v[u] = (i < n) ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
-    }
+    svm_load_rows64<SVM_EU>(n, X, r0, v);
     // the rows' dot products land in the first lane of each half-wave; lane j < 2 SVM_EU takes row r0 + j (u = j >> 1, half = j & 1): ONE coalesced load per
     // vector for the 2 SVM_EU rows (a load per row costs the address unit a whole instruction each: measured 2 x the time of the plain pass), asked for before
     // the dot products so that they travel with the rows of X, the elementwise work once
@@ -254,14 +199,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
       if (a.lb) li = a.lb[i];
       if (a.ub) ui = a.ub[i];
     }
-    double su[SVM_EU], sm = 0.0;
-#pragma unroll
-    for (int u = 0; u < SVM_EU; u++) su[u] = svm_row_dot(v[u], wr);
-#pragma unroll
-    for (int u = 0; u < SVM_EU; u++) {
-      const double q = __shfl(su[u], (lane & 1) << 5, 64);
-      if ((lane >> 1) == u) sm = q;
-    }
+    const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
     double t = 0.0; // y_i p_i: the row's weight in X'(y o p)
     if (act) {
       const double gi = (AUG ? svm_aug_row(yi, sm, sS, a.shift, xi) : yi * sm) - bi;
@@ -319,11 +257,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
   double            a0 = 0.0, a1 = 0.0, s0 = 0.0, s1 = 0.0, m = INFINITY, ts = 0.0, sux = 0.0;
   for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
     dbl2 v[SVM_EU];
-#pragma unroll
-    for (int u = 0; u < SVM_EU; u++) {
-      const long long i = r0 + 2 * u + half;
-      v[u] = (i < n) ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
-    }
+    svm_load_rows64<SVM_EU>(n, X, r0, v);
     // (as in k_svm_x64_grad: lane j < 2 SVM_EU takes row r0 + j, its scalars asked for up front)
     const long long i   = r0 + lane;
     const bool      act = lane < 2 * SVM_EU && i < n;
@@ -333,14 +267,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
       if (a.lb) li = a.lb[i];
       if (a.ub) ui = a.ub[i];
     }
-    double su[SVM_EU], sm = 0.0;
-#pragma unroll
-    for (int u = 0; u < SVM_EU; u++) su[u] = svm_row_dot(v[u], wr);
-#pragma unroll
-    for (int u = 0; u < SVM_EU; u++) {
-      const double q = __shfl(su[u], (lane & 1) << 5, 64);
-      if ((lane >> 1) == u) sm = q;
-    }
+    const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
     double t = 0.0; // y_i x+_i: the row's weight in X'(y o x+)
     if (act) {
       const double api = AUG ? svm_aug_row(yi, sm, sS, a.shift, pi) : yi * sm;
@@ -394,26 +321,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum_feas(int nblocks, cons
     if (threadIdx.x == 0) *afeas = m;
     return;
   }
-  const int lane = threadIdx.x & 63, c = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
-  if (c >= 64 + (spart ? 1 : 0)) return;
-  double v = 0.0;
-  if (c == 64) {
-    for (int b = lane; b < nblocks; b += 64) v += spart[b];
-  } else
-  for (int b = lane; b < nblocks; b += 64) v += part[(size_t)b * 64 + c];
-  v = pmh_wave_sum(v);
-  if (lane == 0) w[c] = v;
+  svm_colsum(nblocks, 64, part, w, spart);
 }
-
-// (template instances with two arguments, named: a comma inside a macro argument would split it)
-static const auto kp_k_svm_x64_4_0 = k_svm_x64<4, 0>;
-static const auto kp_k_svm_x64_4_1 = k_svm_x64<4, 1>;
-static const auto kp_k_svm_x64_p1_0_0 = k_svm_x64_p1<0, 0>;
-static const auto kp_k_svm_x64_p1_0_1 = k_svm_x64_p1<0, 1>;
-static const auto kp_k_svm_x64_p1_1_0 = k_svm_x64_p1<1, 0>;
-static const auto kp_k_svm_x64_p1_1_1 = k_svm_x64_p1<1, 1>;
-static const auto kp_k_svm_xt64_4_0 = k_svm_xt64<4, 0>;
-static const auto kp_k_svm_xt64_4_1 = k_svm_xt64<4, 1>;
 
 // Gu[0] = c sum_b part[b], its square -> the scalar slot (device + pinned host): ||B u||^2 of the one-row equality with row c y.  One workgroup, fixed order
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_aux_finish(int nb, const double *__restrict__ part, double c, double *__restrict__ Gu, double *__restrict__ dslot, double *__restrict__ hslot)
@@ -442,6 +351,32 @@ static int svm_aux_ready(SvmDualOp *o, bool aug, bool *ok)
   return PMH_SUCCESS;
 }
 
+// pass 1 and the column sums: w = X'(y o v) and, augmented, w[d] = s = sum_i y_i v_i (+ sum_i y_i u_i -> upart[workgroup] where u is given).  The plain form
+// hands the AUG = 0 kernels null pointers: the kernels of the plain operator, the bits of the plain operator
+int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
+{
+  double *sp = aug ? spart : nullptr;
+  // d == 64: rows in flight per wave-instruction group: 2 x UNR rows of 512 B (16-byte loads, UNR of them outstanding per lane).  UNR decides which wave visits
+  // which rows, i.e. the summation order of pass 1 (last-digit differences between UNR values; fixed for a given UNR).  Measured 4 / 8 / 12 / 16 on configs[4]:
+  // 464 / 452-488 / 433 / 487 iterations per second -- inside the run-to-run spread of the box (the two passes already stream X at the box's copy rate): 4 stays,
+  // and only that instance is compiled
+  if (d == 64) SVM_PASS((aug ? k_svm_xt64<4, 1> : k_svm_xt64<4, 0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, sp, u, upart);
+  else SVM_PASS((aug ? k_svm_xt<1> : k_svm_xt<0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, v, part, sp, u, upart);
+  hipLaunchKernelGGL(k_svm_colsum, dim3((d + (aug ? 1 : 0) + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)sp);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+// pass 2: out_i = y_i (x_i . w), augmented + (sigma + sigma_fold) w[d] y_i + shift a_i
+int SvmDualOp::pass2(const double *a, double *out, bool aug)
+{
+  const double *ap = aug ? a : nullptr;
+  const double  sg = aug ? sigma + sigma_fold : 0.0, sh = aug ? shift : 0.0;
+  if (d == 64) SVM_PASS((aug ? k_svm_x64<4, 1> : k_svm_x64<4, 0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, out, ap, sg, sh);
+  else SVM_PASS((aug ? k_svm_x<1> : k_svm_x<0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, out, ap, sg, sh);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
 int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
 {
   // (the switch may change between two solves of one process: pmh_set_knob("svm_pairing"), initial value from PMH_SVM_NO_PAIRING -- no getenv on the
@@ -461,7 +396,7 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
   // the augmented forms (shift / rank-one term): the same launches with the 65th column sum s = sum_i y_i v_i beside the 64 of w
   const bool    AG  = aug();
   const double  sg  = sigma + sigma_fold;
-  const double *sp  = AG ? spart : nullptr, *spn = AG ? spart_next : nullptr;
+  const double *spn = AG ? spart_next : nullptr;
   const size_t  nw  = AG ? 65 : 64;
   int           have = next_is;
   if (next_aug != AG) have = NEXT_NONE; // (sums prepared by the other form lack / carry the 65th column)
@@ -469,13 +404,10 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
   next_aug = AG;
   // w (+ s) of `v`: from the sums the previous pass 2 left (prepared) or by pass 1
   auto form_w = [&](bool prepared, const double *v) -> int {
-    if (prepared) hipLaunchKernelGGL(k_svm_colsum_feas, dim3(AG ? 18 : 17), dim3(PMH_BLOCK), 0, ctx->stream, grid_epi, (const double *)part_next, w, (const double *)feas_part, d_afeas, spn);
-    else {
-      if (AG) SVM_PASS(kp_k_svm_xt64_4_1, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, spart, (const double *)nullptr, (double *)nullptr);
-      else SVM_PASS(kp_k_svm_xt64_4_0, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
-      hipLaunchKernelGGL(k_svm_colsum, dim3(AG ? 17 : 16), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, sp);
-    }
-    PMH_HIP(hipGetLastError());
+    if (prepared) {
+      hipLaunchKernelGGL(k_svm_colsum_feas, dim3(AG ? 18 : 17), dim3(PMH_BLOCK), 0, ctx->stream, grid_epi, (const double *)part_next, w, (const double *)feas_part, d_afeas, spn);
+      PMH_HIP(hipGetLastError());
+    } else PMH_CHK(pass1(v, AG, nullptr, nullptr));
     return pmh_comm_allreduce_sum(ctx, w, nw);
   };
   if (e.kind == PMH_VEPI_GRAD_SPLIT) {
@@ -488,8 +420,7 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     a.partials = e.partials, a.feas_part = feas_part, a.part_next = part_next, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
     a.spart_next = spart_next, a.sigma = sg, a.shift = shift;
     if (spec && !e.x_out) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: x_from_spec needs x_out");
-    if (AG) SVM_PASS(k_svm_x64_grad<1>, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
-    else SVM_PASS(k_svm_x64_grad<0>, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    SVM_PASS((AG ? k_svm_x64_grad<1> : k_svm_x64_grad<0>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
     PMH_HIP(hipGetLastError());
     next_is = NEXT_P, next_p = e.p;
     return PMH_SUCCESS;
@@ -507,10 +438,7 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     a.alpha = e.spec_alpha, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
     a.spart_next = spart_next, a.aux_part = aux ? aux_part : nullptr, a.sigma = sg, a.shift = shift;
     const bool spec = paired && e.spec_alpha > 0.0; // afeas is known before this pass only when the gradient pass computed it
-    if (spec && AG) SVM_PASS(kp_k_svm_x64_p1_1_1, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
-    else if (spec) SVM_PASS(kp_k_svm_x64_p1_1_0, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
-    else if (AG) SVM_PASS(kp_k_svm_x64_p1_0_1, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
-    else SVM_PASS(kp_k_svm_x64_p1_0_0, dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    SVM_PASS((spec ? (AG ? k_svm_x64_p1<1, 1> : k_svm_x64_p1<1, 0>) : (AG ? k_svm_x64_p1<0, 1> : k_svm_x64_p1<0, 0>)), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
     PMH_HIP(hipGetLastError());
     if (aux) PMH_CHK(aux_finish(grid_epi));
     if (spec) next_is = NEXT_XSPEC;
@@ -524,66 +452,23 @@ int SvmDualOp::mult(const double *a, double *Ha)
   next_is = NEXT_NONE; // (whatever was prepared belonged to the MPGP driver's vectors)
   if (n == 0 && pmh_comm_on(ctx)) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: this rank holds no samples; with a communicator every rank needs at least one row");
   if (n == 0) return PMH_SUCCESS;
-  const bool   AG = aug();
-  const double sg = sigma + sigma_fold;
-  bool         aux = false;
+  const bool AG  = aug();
+  bool       aux = false;
   PMH_CHK(svm_aux_ready(this, AG, &aux));
-  const double *au = aux ? aux_u : nullptr;
-  double       *ap = aux ? aux_part : nullptr;
-  if (d == 64) {
-    // rows in flight per wave-instruction group: 2 x UNR rows of 512 B (16-byte loads, UNR of them outstanding per lane).  UNR decides which wave visits which
-    // rows, i.e. the summation order of pass 1 (last-digit differences between UNR values; fixed for a given UNR).  Measured 4 / 8 / 12 / 16 on configs[4]: 464
-    // / 452-488 / 433 / 487 iterations per second -- inside the run-to-run spread of the box (the two passes already stream X at the box's copy rate): 4 stays,
-    // and only that instance is compiled
-    if (AG) {
-      SVM_PASS(kp_k_svm_xt64_4_1, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, a, part, spart, au, ap);
-      hipLaunchKernelGGL(k_svm_colsum, dim3((d + 1 + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)spart);
-      PMH_HIP(hipGetLastError());
-      if (aux) PMH_CHK(aux_finish(nblocks));
-      PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d + 1));
-      SVM_PASS(kp_k_svm_x64_4_1, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, Ha, a, sg, shift);
-    } else {
-      SVM_PASS(kp_k_svm_xt64_4_0, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, a, part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
-      hipLaunchKernelGGL(k_svm_colsum, dim3((d + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)nullptr);
-      PMH_HIP(hipGetLastError());
-      PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d));
-      SVM_PASS(kp_k_svm_x64_4_0, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, Ha, (const double *)nullptr, 0.0, 0.0);
-    }
-    PMH_HIP(hipGetLastError());
-    return PMH_SUCCESS;
-  }
-  if (AG) {
-    SVM_PASS(k_svm_xt<1>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, a, part, spart, au, ap);
-    hipLaunchKernelGGL(k_svm_colsum, dim3((d + 1 + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)spart);
-    PMH_HIP(hipGetLastError());
-    if (aux) PMH_CHK(aux_finish(nblocks));
-    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d + 1));
-    SVM_PASS(k_svm_x<1>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, Ha, a, sg, shift);
-  } else {
-    SVM_PASS(k_svm_xt<0>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, a, part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
-    hipLaunchKernelGGL(k_svm_colsum, dim3((d + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)nullptr);
-    PMH_HIP(hipGetLastError());
-    PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d)); // samples sharded over GPUs: the one exchange step
-    SVM_PASS(k_svm_x<0>, dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, Ha, (const double *)nullptr, 0.0, 0.0);
-  }
-  PMH_HIP(hipGetLastError());
-  return PMH_SUCCESS;
+  PMH_CHK(pass1(a, AG, aux ? aux_u : nullptr, aux ? aux_part : nullptr));
+  if (aux) PMH_CHK(aux_finish(nblocks));
+  PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d + (AG ? 1 : 0))); // samples sharded over GPUs: the one exchange step
+  return pass2(a, Ha, AG);
 }
 
-// w = X'(y o a) by pass 1 alone (the model of a trained SVM)
+// w = X'(y o a) by pass 1 alone, always the plain form (the model of a trained SVM)
 int SvmDualOp::form_w(const double *a, const double **w_dev)
 {
-  SvmDualOp *o = this;
-  o->next_is = SvmDualOp::NEXT_NONE;
-  if (o->n > 0) {
-    o->npass++;
-    if (o->d == 64) hipLaunchKernelGGL(kp_k_svm_xt64_4_0, dim3(o->nblocks), dim3(PMH_BLOCK), 0, o->ctx->stream, o->n, o->X, o->y, a, o->part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
-    else hipLaunchKernelGGL(k_svm_xt<0>, dim3(o->nblocks), dim3(PMH_BLOCK), 0, o->ctx->stream, o->n, o->d, o->X, o->y, a, o->part, (double *)nullptr, (const double *)nullptr, (double *)nullptr);
-    hipLaunchKernelGGL(k_svm_colsum, dim3((o->d + 3) / 4), dim3(PMH_BLOCK), 0, o->ctx->stream, o->nblocks, o->d, (const double *)o->part, o->w, (const double *)nullptr);
-    PMH_HIP(hipGetLastError());
-  } else PMH_CHK(pmh_memset(o->ctx, o->w, 0, sizeof(double) * (size_t)o->d));
-  PMH_CHK(pmh_comm_allreduce_sum(o->ctx, o->w, (size_t)o->d));
-  *w_dev = o->w;
+  next_is = NEXT_NONE;
+  if (n > 0) PMH_CHK(pass1(a, false, nullptr, nullptr));
+  else PMH_CHK(pmh_memset(ctx, w, 0, sizeof(double) * (size_t)d));
+  PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d));
+  *w_dev = w;
   return PMH_SUCCESS;
 }
 

@@ -3,7 +3,7 @@
 #include "pmh_internal.h"
 
 #define SVM_KMAX 4 // d <= 64 * SVM_KMAX
-// a launch that streams X once (counted: pmh_op_svm_dual_passes)
+// a launch that streams X once (counted: pmh_op_svm_dual_passes); a kernel given as a template-id with a comma, or chosen by ?:, goes in parentheses
 #define SVM_PASS(...)                 \
   do {                                \
     npass++;                          \
@@ -53,6 +53,10 @@ struct SvmDualOp : SvmDualBase {
   // One GPU only (the caller falls back to the projector's own dot otherwise)
   double       *aux_part = nullptr;
   int           aux_finish(int nb);
+  // the two passes over X of one product, each with its launch counted and checked; aug: the AUG = 1 kernels (pass 1: + the 65th column sum and, where u is
+  // given, sum_i y_i u_i -> upart)
+  int           pass1(const double *v, bool aug, const double *u, double *upart);
+  int           pass2(const double *a, double *out, bool aug);
   int           form_w(const double *a, const double **w_dev) override;
   void          terms_changed() override { next_is = NEXT_NONE; }
   ~SvmDualOp() override

@@ -3,13 +3,14 @@
 //   L2: min 1/2 a'(H + I/C)a - 1'a,  0 <= a        (primal 1/2 |w|^2 + C/2 sum xi^2)
 //   bias: additionally y'a = 0, posed as (y / sqrt(n))'a = 0 -- a one-row projector (onerow.hip) under SMALXE, whose penalty term the operator absorbs (qppf.hip)
 // H = diag(y) X X' diag(y).  No bias: MPGP on the box alone.  Model: w = X'(y o a) by the operator's pass-1 kernels; b by one pass over X (k_svm_bias);
-// prediction by one pass over the test samples (k_svm_predict: one wavefront per row, lane j owns columns j, j + 64, ...: any d the operator accepts;
-// k_svm_predict64 for d = 64: the two-rows-per-wave layout of the operator's own pass 2).  Samples in CSR: x_i . w by the entry-balanced sweep of svm_csr.hip
-// (one pass over the stored entries), then one kernel over the n dot products (k_svm_bias_dots, k_svm_predict_dots).
+// prediction by one pass over the test samples (k_svm_predict: svm_sweep_rows, any d the operator accepts; k_svm_predict64 for d = 64: svm_sweep_rows64, the
+// sweeps of the operator's own pass 2, svm_rows.h).  Samples in CSR: x_i . w by the entry-balanced sweep of svm_csr.hip (one pass over the stored entries), then
+// one kernel over the n dot products (k_svm_bias_dots, k_svm_predict_dots).  What a row's dot product is used for is written once whichever kernel found it:
+// svm_bias_row, svm_classify_row; their four sums per thread leave every kernel through svm_store4.
 #include <cmath>
 
 #include "svm_internal.h"
-#include "reduce.h"
+#include "svm_rows.h"
 
 struct pmh_svm_s {
   pmh_ctx       ctx;
@@ -37,47 +38,36 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_fill_row(int n, const double 
   for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) row[i] = c * y[i];
 }
 
-// the row's dot product x_i . w in every lane of the wave
-static __device__ __forceinline__ double svm_row_dot_any(const double *__restrict__ xr, int d, const double *wr, int lane)
+// the four sums a thread holds, reduced over the workgroup one after the other -> part[4][gridDim.x]
+static __device__ __forceinline__ void svm_store4(double s0, double s1, double s2, double s3, double *red, double *__restrict__ part)
 {
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < SVM_KMAX; k++) {
-    const int c = lane + 64 * k;
-    if (c < d) s += __builtin_nontemporal_load(&xr[c]) * wr[k];
-  }
-  s = pmh_wave_sum(s);
-  return __shfl(s, 0, 64);
-}
-
-// One pass over X for the bias: per workgroup the partial sums of (sum over free support vectors of y_i - x_i . w, y'a, number of free support vectors, number of
-// support vectors) -> part[4][gridDim.x]; free: astol < a_i and (ubound > 0: a_i < ubound - astol)
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, const double *__restrict__ alpha, double astol,
-                                                        double ubound, double *__restrict__ part)
-{
-  __shared__ double red[PMH_BLOCK / 64];
-  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  double            wr[SVM_KMAX];
-#pragma unroll
-  for (int k = 0; k < SVM_KMAX; k++) wr[k] = (lane + 64 * k < d) ? w[lane + 64 * k] : 0.0;
-  double sb = 0.0, sya = 0.0, nf = 0.0, ns = 0.0;
-  for (long long i = gw; i < n; i += nw) {
-    const double s = svm_row_dot_any(X + (size_t)i * d, d, wr, lane);
-    if (lane == 0) {
-      const double ai = alpha[i], yi = y[i];
-      sya += yi * ai;
-      if (ai > astol) {
-        ns += 1.0;
-        if (!(ubound > 0.0) || ai < ubound - astol) nf += 1.0, sb += yi - s;
-      }
-    }
-  }
-  const double r0 = pmh_block_reduce<PMH_RED_SUM>(sb, red), r1 = pmh_block_reduce<PMH_RED_SUM>(sya, red), r2 = pmh_block_reduce<PMH_RED_SUM>(nf, red), r3 = pmh_block_reduce<PMH_RED_SUM>(ns, red);
+  const double r0 = pmh_block_reduce<PMH_RED_SUM>(s0, red), r1 = pmh_block_reduce<PMH_RED_SUM>(s1, red), r2 = pmh_block_reduce<PMH_RED_SUM>(s2, red), r3 = pmh_block_reduce<PMH_RED_SUM>(s3, red);
   if (threadIdx.x == 0) {
     const size_t g = gridDim.x;
     part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
   }
+}
+
+// sample i with dot = x_i . w in the sums of the bias: sb over the free support vectors of y_i - x_i . w, sya = y'a, nf the number of free support vectors, ns of
+// support vectors; free: astol < a_i and (ubound > 0: a_i < ubound - astol)
+static __device__ __forceinline__ void svm_bias_row(long long i, double dot, const double *__restrict__ y, const double *__restrict__ alpha, double astol, double ubound, double &sb, double &sya,
+                                                    double &nf, double &ns)
+{
+  const double ai = alpha[i], yi = y[i];
+  sya += yi * ai;
+  if (ai > astol) {
+    ns += 1.0;
+    if (!(ubound > 0.0) || ai < ubound - astol) nf += 1.0, sb += yi - dot;
+  }
+}
+// One pass over X for the bias: per workgroup the partial sums of svm_bias_row -> part[4][gridDim.x]
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, const double *__restrict__ alpha, double astol,
+                                                        double ubound, double *__restrict__ part)
+{
+  __shared__ double red[PMH_BLOCK / 64];
+  double            sb = 0.0, sya = 0.0, nf = 0.0, ns = 0.0;
+  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { svm_bias_row(i, dot, y, alpha, astol, ubound, sb, sya, nf, ns); });
+  svm_store4(sb, sya, nf, ns, red, part);
 }
 // out[k] = sum_b part[k][b], k < K: one workgroup, fixed order (the counts are sums of ones: exact below 2^53)
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_sum_rows(int nb, int K, const double *__restrict__ part, double *__restrict__ out)
@@ -91,82 +81,41 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_sum_rows(int nb, int K, const
   }
 }
 
-// One pass over the test samples: score_i = x_i . w + b, label_i = +-1 (score >= 0: +1), and with the true labels the confusion counts (TP, FP, TN, FN) per
-// workgroup -> part[4][gridDim.x].  scores / labels / ytrue may each be nullptr
+struct svm_counts {
+  double tp = 0.0, fp = 0.0, tn = 0.0, fn = 0.0;
+};
+// sample i with the score s = x_i . w + b: label_i = +-1 (s >= 0: +1) and, with the true labels, the confusion counts.  scores / labels / ytrue may each be
+// nullptr; no __restrict__ on scores: the CSR form reads the dot products from the array the scores go to.  The counts go in and out by value: through
+// references the choice (pos ? tp : fp) is one between addresses, and the compiler then keeps the counts in memory (40 bytes of scratch per lane, or 8 KiB of LDS)
+static __device__ __forceinline__ svm_counts svm_classify_row(long long i, double s, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, svm_counts c)
+{
+  const double l = s >= 0.0 ? 1.0 : -1.0;
+  if (scores) scores[i] = s;
+  if (labels) labels[i] = l;
+  if (ytrue) {
+    const bool pos = ytrue[i] > 0.0;
+    if (l > 0.0) (pos ? c.tp : c.fp) += 1.0;
+    else (pos ? c.fn : c.tn) += 1.0;
+  }
+  return c;
+}
+// One pass over the test samples: scores, labels and per workgroup the confusion counts -> part[4][gridDim.x] (svm_classify_row)
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict(int n, int d, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
                                                            const double *__restrict__ ytrue, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
-  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  double            wr[SVM_KMAX];
-#pragma unroll
-  for (int k = 0; k < SVM_KMAX; k++) wr[k] = (lane + 64 * k < d) ? w[lane + 64 * k] : 0.0;
-  double tp = 0.0, fp = 0.0, tn = 0.0, fn = 0.0;
-  for (long long i = gw; i < n; i += nw) {
-    const double s = svm_row_dot_any(X + (size_t)i * d, d, wr, lane) + b;
-    if (lane == 0) {
-      const double l = s >= 0.0 ? 1.0 : -1.0;
-      if (scores) scores[i] = s;
-      if (labels) labels[i] = l;
-      if (ytrue) {
-        const bool pos = ytrue[i] > 0.0;
-        if (l > 0.0) (pos ? tp : fp) += 1.0;
-        else (pos ? fn : tn) += 1.0;
-      }
-    }
-  }
-  if (!ytrue) return; // (uniform: a kernel argument)
-  const double r0 = pmh_block_reduce<PMH_RED_SUM>(tp, red), r1 = pmh_block_reduce<PMH_RED_SUM>(fp, red), r2 = pmh_block_reduce<PMH_RED_SUM>(tn, red), r3 = pmh_block_reduce<PMH_RED_SUM>(fn, red);
-  if (threadIdx.x == 0) {
-    const size_t g = gridDim.x;
-    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
-  }
+  svm_counts        c;
+  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { c = svm_classify_row(i, dot + b, scores, labels, ytrue, c); });
+  if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
-
-// d == 64: the row layout of k_svm_x64 (svm.hip) -- 16-byte loads, two rows per wave-instruction (lanes 0-31 row r, lanes 32-63 row r + 1), four in flight
-typedef double svm_dbl2 __attribute__((ext_vector_type(2)));
-#define SVM_PU 4
+// d == 64: the row layout of k_svm_x64 (svm.hip), four row pairs in flight
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
                                                              const double *__restrict__ ytrue, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
-  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
-  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  const svm_dbl2    wr = ((const svm_dbl2 *)w)[l2];
-  double            tp = 0.0, fp = 0.0, tn = 0.0, fn = 0.0;
-  for (long long r0 = gw * 2 * SVM_PU; r0 < n; r0 += nw * 2 * SVM_PU) {
-    svm_dbl2 v[SVM_PU];
-#pragma unroll
-    for (int u = 0; u < SVM_PU; u++) {
-      const long long i = r0 + 2 * u + half;
-      v[u] = (i < n) ? __builtin_nontemporal_load((const svm_dbl2 *)(X + (size_t)i * 64) + l2) : svm_dbl2{0.0, 0.0};
-    }
-#pragma unroll
-    for (int u = 0; u < SVM_PU; u++) {
-      const long long i = r0 + 2 * u + half;
-      double          s = v[u].x * wr.x + v[u].y * wr.y;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) s += __shfl_down(s, o, 32);
-      if (l2 == 0 && i < n) {
-        s += b;
-        const double l = s >= 0.0 ? 1.0 : -1.0;
-        if (scores) scores[i] = s;
-        if (labels) labels[i] = l;
-        if (ytrue) {
-          const bool pos = ytrue[i] > 0.0;
-          if (l > 0.0) (pos ? tp : fp) += 1.0;
-          else (pos ? fn : tn) += 1.0;
-        }
-      }
-    }
-  }
-  if (!ytrue) return; // (uniform: a kernel argument)
-  const double q0 = pmh_block_reduce<PMH_RED_SUM>(tp, red), q1 = pmh_block_reduce<PMH_RED_SUM>(fp, red), q2 = pmh_block_reduce<PMH_RED_SUM>(tn, red), q3 = pmh_block_reduce<PMH_RED_SUM>(fn, red);
-  if (threadIdx.x == 0) {
-    const size_t g = gridDim.x;
-    part[blockIdx.x] = q0, part[g + blockIdx.x] = q1, part[2 * g + blockIdx.x] = q2, part[3 * g + blockIdx.x] = q3;
-  }
+  svm_counts        c;
+  svm_sweep_rows64<4>(n, X, w, [&](long long i, double dot) { c = svm_classify_row(i, dot + b, scores, labels, ytrue, c); });
+  if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
 
 // ---- samples in CSR: the same sums as k_svm_bias / k_svm_predict from the rows' dot products x_i . w (svm_csr.hip), one entry per thread ----
@@ -175,41 +124,16 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias_dots(int n, const double
 {
   __shared__ double red[PMH_BLOCK / 64];
   double            sb = 0.0, sya = 0.0, nf = 0.0, ns = 0.0;
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
-    const double ai = alpha[i], yi = y[i];
-    sya += yi * ai;
-    if (ai > astol) {
-      ns += 1.0;
-      if (!(ubound > 0.0) || ai < ubound - astol) nf += 1.0, sb += yi - dots[i];
-    }
-  }
-  const double r0 = pmh_block_reduce<PMH_RED_SUM>(sb, red), r1 = pmh_block_reduce<PMH_RED_SUM>(sya, red), r2 = pmh_block_reduce<PMH_RED_SUM>(nf, red), r3 = pmh_block_reduce<PMH_RED_SUM>(ns, red);
-  if (threadIdx.x == 0) {
-    const size_t g = gridDim.x;
-    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
-  }
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) svm_bias_row(i, dots[i], y, alpha, astol, ubound, sb, sya, nf, ns);
+  svm_store4(sb, sya, nf, ns, red, part);
 }
 // (dots and scores may be the same array)
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict_dots(int n, const double *dots, double b, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
-  double            tp = 0.0, fp = 0.0, tn = 0.0, fn = 0.0;
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
-    const double s = dots[i] + b, l = s >= 0.0 ? 1.0 : -1.0;
-    if (scores) scores[i] = s;
-    if (labels) labels[i] = l;
-    if (ytrue) {
-      const bool pos = ytrue[i] > 0.0;
-      if (l > 0.0) (pos ? tp : fp) += 1.0;
-      else (pos ? fn : tn) += 1.0;
-    }
-  }
-  if (!ytrue) return; // (uniform: a kernel argument)
-  const double r0 = pmh_block_reduce<PMH_RED_SUM>(tp, red), r1 = pmh_block_reduce<PMH_RED_SUM>(fp, red), r2 = pmh_block_reduce<PMH_RED_SUM>(tn, red), r3 = pmh_block_reduce<PMH_RED_SUM>(fn, red);
-  if (threadIdx.x == 0) {
-    const size_t g = gridDim.x;
-    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2, part[3 * g + blockIdx.x] = r3;
-  }
+  svm_counts        c;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) c = svm_classify_row(i, dots[i] + b, scores, labels, ytrue, c);
+  if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
 
 extern "C" int pmh_svm_default_opts(pmh_svm_opts *o)
@@ -307,6 +231,16 @@ extern "C" int pmh_svm_create_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, c
   return svm_create(ctx, X->nrows, X->ncols, nullptr, X, y_dev, opts, out);
 }
 
+// scal[0..3] = the sums over all workgroups and ranks of the four rows a bias / predict kernel left in part[4][nb] (n == 0: no kernel ran, zeros)
+static int svm_sum_part(pmh_svm s, int n, int nb)
+{
+  if (n > 0) {
+    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, s->ctx->stream, nb, 4, (const double *)s->part, s->scal);
+    PMH_HIP(hipGetLastError()); // (also the launch of the kernel that filled part)
+  } else PMH_CHK(pmh_memset(s->ctx, s->scal, 0, sizeof(double) * 4));
+  return pmh_comm_allreduce_sum(s->ctx, s->scal, 4);
+}
+
 // w, b and the counts from the current alpha
 static int svm_model(pmh_svm s)
 {
@@ -317,20 +251,16 @@ static int svm_model(pmh_svm s)
   PMH_CHK(pmh_vec_copy(ctx, s->d, w, s->w));
   s->h_w.resize((size_t)s->d);
   const int    nb    = SVM_NB(s->n);
-  const double astol = s->sx ? s->o.smalxe.inner.astol : s->o.mpgp.astol;
+  const double astol = s->sx ? s->o.smalxe.inner.astol : s->o.mpgp.astol, ubound = s->o.loss_type == PMH_SVM_LOSS_L1 ? s->o.C : 0.0;
   if (s->n > 0 && s->Xcsr) {
     if (!s->dots) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)s->n, (void **)&s->dots));
     PMH_CHK(pmh_svm_csr_op_row_dots(H, s->w, s->dots));
-    hipLaunchKernelGGL(k_svm_bias_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, (const double *)s->dots, s->y, (const double *)s->alpha, astol, s->o.loss_type == PMH_SVM_LOSS_L1 ? s->o.C : 0.0, s->part);
-    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, ctx->stream, nb, 4, (const double *)s->part, s->scal);
-    PMH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_svm_bias_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, (const double *)s->dots, s->y, (const double *)s->alpha, astol, ubound, s->part);
   } else if (s->n > 0) {
     H->npass++;
-    hipLaunchKernelGGL(k_svm_bias, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, s->o.loss_type == PMH_SVM_LOSS_L1 ? s->o.C : 0.0, s->part);
-    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, ctx->stream, nb, 4, (const double *)s->part, s->scal);
-    PMH_HIP(hipGetLastError());
-  } else PMH_CHK(pmh_memset(ctx, s->scal, 0, sizeof(double) * 4));
-  PMH_CHK(pmh_comm_allreduce_sum(ctx, s->scal, 4));
+    hipLaunchKernelGGL(k_svm_bias, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, ubound, s->part);
+  }
+  PMH_CHK(svm_sum_part(s, s->n, nb));
   // the equality's multiplier: SMALXE keeps B'mu = mu row (the Lagrangian is 1/2 a'Ha - 1'a + mu (row'a)), so mu = row'(B'mu) / (row'row) and, with
   // row = y / sqrt(n), stationarity in a free sample reads y_i - x_i . w = mu / sqrt(n): b = mu / sqrt(n)
   if (s->sx) {
@@ -436,11 +366,7 @@ static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *sc
     PMH_HIP(hipGetLastError());
   }
   if (!counts) return PMH_SUCCESS;
-  if (n > 0) {
-    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, s->ctx->stream, nb, 4, (const double *)s->part, s->scal);
-    PMH_HIP(hipGetLastError());
-  } else PMH_CHK(pmh_memset(s->ctx, s->scal, 0, sizeof(double) * 4));
-  PMH_CHK(pmh_comm_allreduce_sum(s->ctx, s->scal, 4));
+  PMH_CHK(svm_sum_part(s, n, nb));
   double h[4];
   PMH_CHK(pmh_memcpy_d2h(s->ctx, h, s->scal, sizeof(h)));
   for (int k = 0; k < 4; k++) counts[k] = (long long)h[k];
