@@ -468,6 +468,12 @@ int pmh_op_svm_dual_passes(pmh_op op, long long *passes);
    Hessian; sigma y y' is what penalising the bias equality y'a = 0 adds.  One more column sum, s = sum_i y_i a_i, travels with the d of w: no extra pass over X,
    and every fused epilogue of the plain operator carries both terms */
 int pmh_op_svm_dual_set_terms(pmh_op op, double shift, double sigma);
+/* H + diag(diag) + sigma y y': a diagonal in place of the scalar shift (the L2-loss dual with a penalty per sample: diag_i = 1 / C_i).  diag_dev: n_local doubles
+   on the device, borrowed until it is replaced or the operator destroyed; NULL: off.  Dense rows of any admitted d and CSR.  Pass 2 reads diag_i where it
+   reads a_i and y_i: 8 more bytes per sample, no extra launch, and the paired passes, the folded one-row equality and the ||B u|| rider stay as with a shift.
+   A diagonal and a non-zero shift exclude each other: whichever call arrives second while the other term is on is PMH_ERR_ARG.  Prepared sums of the paired
+   passes are dropped, as by pmh_op_svm_dual_set_terms */
+int pmh_op_svm_dual_set_diag(pmh_op op, const double *diag_dev /* n_local doubles, borrowed; NULL: off */);
 /* The same operator for samples in CSR (X: n_local x d, any d >= 1, column indices ascending inside a row; y in {-1, +1}); X and y_dev are borrowed and must
    stay unchanged.  Two sweeps over the stored entries per application, the work divided by entries, no float atomics: the same input gives the same bits
    (svm_csr.hip).  Creation builds a column-ordered device copy of X: 12 (nnz + n_local) bytes beside X.  Unsorted column indices and nnz + n_local >= 2^31 are
@@ -577,6 +583,16 @@ int pmh_svm_get_model(pmh_svm svm, double *w_host /* d doubles, or NULL */, doub
 int pmh_svm_get_dual(pmh_svm svm, double *alpha_dev);               /* n_local doubles */
 int pmh_svm_get_stats(pmh_svm svm, pmh_svm_stats *st);
 int pmh_svm_get_solver(pmh_svm svm, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh_smalxe *smalxe); /* borrowed; any pointer may be NULL, a solver not in use comes back NULL */
+/* A penalty per sample, C_i = (y_i > 0 ? C_pos : C_neg) weight_i, in place of the one C of the options (unbalanced classes; weighted samples):
+ *   L1: 0 <= a_i <= C_i;   L2: 0 <= a_i, Hessian H + diag(1 / C_i) (pmh_op_svm_dual_set_diag on the handle's operator, in place of the scalar 1/C).
+ * Free support vectors (the bias) are counted against C_i.  Call it after create, and again between trainings at will (pmh_svm_train starts from a = 0); the
+ * handle is untrained afterwards and its solver is built anew, so handles from pmh_svm_get_solver must be fetched again.  weight_dev: n_local doubles on the
+ * device, copied, or NULL = all 1.  C_pos / C_neg not positive and finite: PMH_ERR_ARG naming the value.  Weights that are not positive and finite (zero
+ * included: masking samples out is not supported): PMH_ERR_ARG saying how many, counted on the device, over all ranks.  Nothing is exchanged in training
+ * that was not before: the bounds and the diagonal are local vectors */
+int pmh_svm_set_penalties(pmh_svm svm, double C_pos, double C_neg, const double *weight_dev /* n_local doubles or NULL = all 1; copied */);
+/* the effective C_i (n_local doubles, device); opts.C everywhere if pmh_svm_set_penalties was never called */
+int pmh_svm_get_penalties(pmh_svm svm, double *c_dev /* n_local */);
 /* one pass over the n samples of X_dev: scores_dev[i] = x_i . w + b, labels_dev[i] = +-1 (either may be NULL) */
 int pmh_svm_predict(pmh_svm svm, int n, const double *X_dev, double *scores_dev, double *labels_dev);
 /* one pass: counts = (TP, FP, TN, FN) of the predicted labels against y_dev (summed over the ranks under a communicator) */

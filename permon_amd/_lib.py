@@ -251,6 +251,7 @@ _PROTOS = {
     "pmh_op_create_svm_dual_csr": [vp, vp, vp, C.POINTER(vp)],
     "pmh_op_svm_dual_passes": [vp, C.POINTER(C.c_longlong)],
     "pmh_op_svm_dual_set_terms": [vp, C.c_double, C.c_double],
+    "pmh_op_svm_dual_set_diag": [vp, vp],
     "pmh_qppf_create_onerow": [vp, vp, C.c_int, C.POINTER(vp)],
     "pmh_svm_default_opts": [C.POINTER(SvmOpts)],
     "pmh_svm_set_from_options": [C.c_char_p, C.POINTER(SvmOpts), C.c_char_p, C.c_int],
@@ -260,6 +261,8 @@ _PROTOS = {
     "pmh_svm_get_dual": [vp, vp],
     "pmh_svm_get_stats": [vp, C.POINTER(SvmStats)],
     "pmh_svm_get_solver": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+    "pmh_svm_set_penalties": [vp, C.c_double, C.c_double, vp],
+    "pmh_svm_get_penalties": [vp, vp],
     "pmh_svm_predict": [vp, C.c_int, vp, vp, vp],
     "pmh_svm_test": [vp, C.c_int, vp, vp, C.POINTER(C.c_longlong)],
     "pmh_svm_create_csr": [vp, vp, vp, C.POINTER(SvmOpts), C.POINTER(vp)],

@@ -73,13 +73,13 @@ static __device__ __forceinline__ void svm_colsum(int nblocks, int d, const doub
 }
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart) { svm_colsum(nblocks, d, part, w, spart); }
 
-// pass 2: (H a)_i = y_i (x_i . w); AUG: + sigma s y_i + shift a_i
+// pass 2: (H a)_i = y_i (x_i . w); AUG 1: + sigma s y_i + shift a_i; AUG 2: + sigma s y_i + diag_i a_i
 template <int AUG>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
-                                                     const double *__restrict__ a, double sigma, double shift)
+                                                     const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[d] : 0.0;
-  svm_sweep_rows(n, d, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s; });
+  svm_sweep_rows(n, d, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
 }
 
 // ---- d == 64 fast path: the two-rows-per-wave-instruction layout of svm_rows.h, 4-fold unroll ----
@@ -144,10 +144,10 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__r
 
 template <int SVM_UNR, int AUG>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
-                                                       const double *__restrict__ a, double sigma, double shift)
+                                                       const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[64] : 0.0;
-  svm_sweep_rows64<SVM_UNR>(n, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, shift, a[i]) : y[i] * s; });
+  svm_sweep_rows64<SVM_UNR>(n, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
 }
 
 // ---- paired passes -------------------------------------------------------------------------------------------------------------------------
@@ -172,6 +172,7 @@ struct svm_grad_args {
   // AUG
   double       *spart_next;
   double        sigma, shift;
+  const double *diag; // AUG 2: the diagonal, in place of shift
 };
 // pass 2 of g = H x - b with the gradient split, p = gf, the partial sums of (0, |gP|^2, |gc|^2, |gf|^2), QPCFeas(x, p) and X'(y o p)
 #define SVM_EU 4
@@ -193,16 +194,17 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
     // the dot products so that they travel with the rows of X, the elementwise work once
     const long long i   = r0 + lane;
     const bool      act = lane < 2 * SVM_EU && i < n;
-    double          yi = 0.0, xi = 0.0, bi = 0.0, li = -INFINITY, ui = INFINITY;
+    double          yi = 0.0, xi = 0.0, bi = 0.0, li = -INFINITY, ui = INFINITY, sh = AUG == 1 ? a.shift : 0.0;
     if (act) {
       yi = y[i], xi = a.x_in[i], bi = a.b[i];
+      if (AUG == 2) sh = a.diag[i];
       if (a.lb) li = a.lb[i];
       if (a.ub) ui = a.ub[i];
     }
     const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
     double t = 0.0; // y_i p_i: the row's weight in X'(y o p)
     if (act) {
-      const double gi = (AUG ? svm_aug_row(yi, sm, sS, a.shift, xi) : yi * sm) - bi;
+      const double gi = (AUG ? svm_aug_row(yi, sm, sS, sh, xi) : yi * sm) - bi;
       double       f, c;
       pmh_box_split_v(xi, gi, li, ui, a.astol, f, c);
       a.g[i] = gi, a.gf[i] = f, a.p[i] = f;
@@ -242,6 +244,7 @@ struct svm_p1_args {
   // AUG
   double       *spart_next, *aux_part; // aux_part != nullptr: sum_i y_i x_i of the iterate (the one-row equality's B u up to the row's scale)
   double        sigma, shift;
+  const double *diag; // AUG 2: the diagonal, in place of shift
 };
 // pass 2 of Ap = H p with the partial sums of p'Ap, g'p, QPCFeas(x, p); SPEC: + the iterate of the expansion step and X'(y o x+)
 template <int SPEC, int AUG>
@@ -261,16 +264,17 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
     // (as in k_svm_x64_grad: lane j < 2 SVM_EU takes row r0 + j, its scalars asked for up front)
     const long long i   = r0 + lane;
     const bool      act = lane < 2 * SVM_EU && i < n;
-    double          yi = 0.0, pi = 0.0, gi = 0.0, xi = 0.0, li = -INFINITY, ui = INFINITY;
+    double          yi = 0.0, pi = 0.0, gi = 0.0, xi = 0.0, li = -INFINITY, ui = INFINITY, sh = AUG == 1 ? a.shift : 0.0;
     if (act) {
       yi = y[i], pi = a.p[i], gi = a.g[i], xi = a.x[i];
+      if (AUG == 2) sh = a.diag[i];
       if (a.lb) li = a.lb[i];
       if (a.ub) ui = a.ub[i];
     }
     const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
     double t = 0.0; // y_i x+_i: the row's weight in X'(y o x+)
     if (act) {
-      const double api = AUG ? svm_aug_row(yi, sm, sS, a.shift, pi) : yi * sm;
+      const double api = AUG ? svm_aug_row(yi, sm, sS, sh, pi) : yi * sm;
       a.Ap[i] = api;
       if (AUG) sux += yi * xi;
       s0 += pi * api, s1 += gi * pi;
@@ -366,13 +370,19 @@ int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
-// pass 2: out_i = y_i (x_i . w), augmented + (sigma + sigma_fold) w[d] y_i + shift a_i
+// pass 2: out_i = y_i (x_i . w), augmented + (sigma + sigma_fold) w[d] y_i + shift a_i (or + diag_i a_i)
+#define SVM_K_X64(A) k_svm_x64<4, A>
+#define SVM_K_X(A) k_svm_x<A>
+#define SVM_K_GRAD(A) k_svm_x64_grad<A>
+#define SVM_K_P1(A) k_svm_x64_p1<0, A>
+#define SVM_K_P1_SPEC(A) k_svm_x64_p1<1, A>
 int SvmDualOp::pass2(const double *a, double *out, bool aug)
 {
   const double *ap = aug ? a : nullptr;
   const double  sg = aug ? sigma + sigma_fold : 0.0, sh = aug ? shift : 0.0;
-  if (d == 64) SVM_PASS((aug ? k_svm_x64<4, 1> : k_svm_x64<4, 0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, out, ap, sg, sh);
-  else SVM_PASS((aug ? k_svm_x<1> : k_svm_x<0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, out, ap, sg, sh);
+  const int     form = aug ? aug_form() : 0;
+  if (d == 64) SVM_PASS(SVM_AUG_PICK(form, SVM_K_X64), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, out, ap, sg, sh, diag);
+  else SVM_PASS(SVM_AUG_PICK(form, SVM_K_X), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, out, ap, sg, sh, diag);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
@@ -393,8 +403,9 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&x_spec));
     PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)grid_epi, (void **)&spart_next));
   }
-  // the augmented forms (shift / rank-one term): the same launches with the 65th column sum s = sum_i y_i v_i beside the 64 of w
+  // the augmented forms (shift or diagonal / rank-one term): the same launches with the 65th column sum s = sum_i y_i v_i beside the 64 of w
   const bool    AG  = aug();
+  const int     form = aug_form();
   const double  sg  = sigma + sigma_fold;
   const double *spn = AG ? spart_next : nullptr;
   const size_t  nw  = AG ? 65 : 64;
@@ -418,9 +429,9 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     svm_grad_args a;
     a.b = e.b, a.x_in = spec ? (const double *)x_spec : in, a.lb = e.lb, a.ub = e.ub, a.x_out = spec ? e.x_out : nullptr, a.g = out, a.gf = e.gf, a.p = e.p;
     a.partials = e.partials, a.feas_part = feas_part, a.part_next = part_next, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
-    a.spart_next = spart_next, a.sigma = sg, a.shift = shift;
+    a.spart_next = spart_next, a.sigma = sg, a.shift = shift, a.diag = diag;
     if (spec && !e.x_out) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: x_from_spec needs x_out");
-    SVM_PASS((AG ? k_svm_x64_grad<1> : k_svm_x64_grad<0>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    SVM_PASS(SVM_AUG_PICK(form, SVM_K_GRAD), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
     PMH_HIP(hipGetLastError());
     next_is = NEXT_P, next_p = e.p;
     return PMH_SUCCESS;
@@ -436,9 +447,9 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     svm_p1_args a;
     a.p = in, a.g = e.g, a.x = e.xx, a.lb = e.lb, a.ub = e.ub, a.afeas = d_afeas, a.Ap = out, a.partials = e.partials, a.x_spec = x_spec, a.part_next = part_next;
     a.alpha = e.spec_alpha, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
-    a.spart_next = spart_next, a.aux_part = aux ? aux_part : nullptr, a.sigma = sg, a.shift = shift;
+    a.spart_next = spart_next, a.aux_part = aux ? aux_part : nullptr, a.sigma = sg, a.shift = shift, a.diag = diag;
     const bool spec = paired && e.spec_alpha > 0.0; // afeas is known before this pass only when the gradient pass computed it
-    SVM_PASS((spec ? (AG ? k_svm_x64_p1<1, 1> : k_svm_x64_p1<1, 0>) : (AG ? k_svm_x64_p1<0, 1> : k_svm_x64_p1<0, 0>)), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    SVM_PASS((spec ? SVM_AUG_PICK(form, SVM_K_P1_SPEC) : SVM_AUG_PICK(form, SVM_K_P1)), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
     PMH_HIP(hipGetLastError());
     if (aux) PMH_CHK(aux_finish(grid_epi));
     if (spec) next_is = NEXT_XSPEC;
@@ -522,7 +533,18 @@ extern "C" int pmh_op_svm_dual_set_terms(pmh_op op, double shift, double sigma)
 {
   SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
   PMH_ARG(o && shift >= 0.0 && sigma >= 0.0);
+  if (shift != 0.0 && o->diag) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_terms: shift = %g while a diagonal is set (pmh_op_svm_dual_set_diag): the operator carries a scalar shift or a diagonal, not both", shift);
   o->shift = shift, o->sigma = sigma;
+  o->terms_changed();
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_op_svm_dual_set_diag(pmh_op op, const double *diag_dev)
+{
+  SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
+  PMH_ARG(o);
+  if (diag_dev && o->shift != 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_diag: a diagonal while shift = %g is set (pmh_op_svm_dual_set_terms): the operator carries a scalar shift or a diagonal, not both", o->shift);
+  o->diag = diag_dev;
   o->terms_changed();
   return PMH_SUCCESS;
 }

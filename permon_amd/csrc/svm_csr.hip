@@ -3,7 +3,7 @@
 // applied matrix-free in two sweeps over the stored entries, as the dense operator of svm.hip:
 //   pass 1  w = X'(y o a)  (d doubles) and, in the augmented form, s = sum_i y_i a_i in the same sweep;
 //   all-reduce of w (d or d + 1 doubles) under a communicator;
-//   pass 2  (H a)_i = y_i (x_i . w) + sigma s y_i + shift a_i  (svm_aug_row).
+//   pass 2  (H a)_i = y_i (x_i . w) + sigma s y_i + shift a_i  (svm_aug_row; with a diagonal set, diag_i a_i: MODE 3 of the finishing step).
 // Both passes, the bias pass of the model and prediction are ONE kernel pair, a segmented sum over a compressed array (ptr / idx / val): segments are the
 // samples (the caller's CSR) in pass 2 and in prediction, and the features in pass 1, which runs over a column-ordered device copy built once at creation.
 //
@@ -51,17 +51,19 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svc_first(int nb, int nseg, const
   first[b] = b > 0 ? lo : 0;
 }
 
-// what a finished segment sum becomes.  MODE 0: out[c] = sum; 1: out[c] = y_c sum; 2: out[c] = svm_aug_row(y_c, sum, sigma s, shift, a_c)
+// what a finished segment sum becomes.  MODE 0: out[c] = sum; 1: out[c] = y_c sum; 2: out[c] = svm_aug_row(y_c, sum, sigma s, shift, a_c); 3: the same with diag_c
+// where shift was (pmh_op_svm_dual_set_diag)
 struct svc_out {
   double       *out;
   const double *y, *a, *s; // s: device scalar (w[d])
   double        sigma, shift;
+  const double *diag = nullptr; // MODE 3
 };
 template <int MODE> static __device__ __forceinline__ void svc_store(const svc_out &o, int c, double v, double sS)
 {
   if (MODE == 0) o.out[c] = v;
   else if (MODE == 1) o.out[c] = o.y[c] * v;
-  else o.out[c] = svm_aug_row(o.y[c], v, sS, o.shift, o.a[c]);
+  else o.out[c] = svm_aug_row(o.y[c], v, sS, MODE == 3 ? o.diag[c] : o.shift, o.a[c]);
 }
 
 // the segments of span b: c0 .. c1.  A segment that ends exactly at the span's end is the span's; empty segments at that boundary too
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svc_seg(int nent, int nseg, int n
   int       G   = 1;
   while (G < 64 && G * 8 <= avg) G <<= 1;
   const int    g = threadIdx.x / G, l = threadIdx.x % G;
-  const double sS = MODE == 2 ? o.sigma * *o.s : 0.0;
+  const double sS = MODE >= 2 ? o.sigma * *o.s : 0.0;
   for (int c = c0 + g; c <= c1; c += PMH_BLOCK / G) { // (the trip count is uniform over a segment's G lanes)
     const int p0 = ptr[c], p1 = ptr[c + 1], lo = max(p0, start) - start, hi = min(p1, end) - start;
     double    s = 0.0;
@@ -135,7 +137,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svc_fin(int nent, int nseg, int n
   double     s     = 0.0;
   for (int bb = b0 + lane; bb <= b; bb += 64) s += (bb == b0 && tail0) ? tail[b0] : head[bb];
   s = pmh_wave_sum(s);
-  if (lane == 0) svc_store<MODE>(o, c, s, MODE == 2 ? o.sigma * *o.s : 0.0);
+  if (lane == 0) svc_store<MODE>(o, c, s, MODE >= 2 ? o.sigma * *o.s : 0.0);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------------------
@@ -199,7 +201,8 @@ struct SvmCsrOp : SvmDualBase {
     PMH_CHK(pass1(a, AG));
     PMH_CHK(pmh_comm_allreduce_sum(ctx, w, (size_t)d + (AG ? 1 : 0))); // samples sharded over GPUs: the one exchange step, as in the dense operator
     npass++;
-    svc_out o{Ha, y, a, w + d, sigma + sigma_fold, shift};
+    svc_out o{Ha, y, a, w + d, sigma + sigma_fold, shift, diag};
+    if (diag) return svc_sweep<3>(ctx, rows, n, nnz, X->d_rowptr, X->d_col, X->d_val, w, o);
     if (AG) return svc_sweep<2>(ctx, rows, n, nnz, X->d_rowptr, X->d_col, X->d_val, w, o);
     return svc_sweep<1>(ctx, rows, n, nnz, X->d_rowptr, X->d_col, X->d_val, w, o);
   }

@@ -9,6 +9,8 @@
     npass++;                          \
     hipLaunchKernelGGL(__VA_ARGS__);  \
   } while (0)
+// the instance of a pass-2 kernel for SvmDualBase::aug_form(): K(0) plain, K(1) scalar shift, K(2) diagonal
+#define SVM_AUG_PICK(form, K) ((form) == 2 ? K(2) : ((form) == 1 ? K(1) : K(0)))
 
 // What the penalised operator (qppf.hip) and the front end (svm_train.hip) need of an SVM dual operator, whichever way it holds the samples: dense rows
 // (SvmDualOp, svm.hip) or CSR (SvmCsrOp, svm_csr.hip)
@@ -20,7 +22,11 @@ struct SvmDualBase : pmh_op_s {
   // row c y, set by the penalised operator around each of its products, see qppf.hip).  s = sum_i y_i v_i travels with the column sums: w[d].  All three zero:
   // the kernels of the plain operator, the bits of the plain operator.
   double        shift = 0.0, sigma = 0.0, sigma_fold = 0.0;
-  bool          aug() const { return shift != 0.0 || sigma != 0.0 || sigma_fold != 0.0; }
+  // H + diag(diag) + (sigma + sigma_fold) y y' (pmh_op_svm_dual_set_diag: per-sample penalties of the L2 loss, diag_i = 1 / C_i): n doubles, borrowed, read by
+  // pass 2 where it reads a_i and y_i; excludes a non-zero shift.  The kernels' AUG template argument is aug_form(): 0 plain, 1 shift, 2 diag
+  const double *diag = nullptr;
+  bool          aug() const { return shift != 0.0 || sigma != 0.0 || sigma_fold != 0.0 || diag != nullptr; }
+  int           aug_form() const { return !aug() ? 0 : (diag ? 2 : 1); }
   // ||B u|| of the one-row equality riding on the next product (the penalised operator arms it); an operator that does not serve it leaves aux_done 0 and the
   // caller's own dot product runs
   const double *aux_u = nullptr;
@@ -29,7 +35,7 @@ struct SvmDualBase : pmh_op_s {
   int           aux_slot = -1, aux_done = 0;
   // w = X'(y o a) into the operator's own w (d doubles, device; all-reduced under a communicator) by the pass-1 kernels (the model of a trained SVM)
   virtual int   form_w(const double *a, const double **w_dev) = 0;
-  virtual void  terms_changed() {} // pmh_op_svm_dual_set_terms was called
+  virtual void  terms_changed() {} // pmh_op_svm_dual_set_terms / pmh_op_svm_dual_set_diag was called
 };
 
 struct SvmDualOp : SvmDualBase {
@@ -70,7 +76,7 @@ struct SvmDualOp : SvmDualBase {
 };
 
 
-// the augmented row result: (y_i (x_i . w) + (sigma s) y_i) + shift a_i, in this order (s = w[d])
+// the augmented row result: (y_i (x_i . w) + (sigma s) y_i) + shift a_i, in this order (s = w[d]); the diagonal form hands diag_i over as shift
 static __device__ __forceinline__ double svm_aug_row(double yi, double dot, double sS, double shift, double ai) { return (yi * dot + sS * yi) + shift * ai; }
 
 // 1 (and c, with row = c y) if pf is a one-row projector whose row is a multiple of this operator's labels, entry by entry

@@ -1,6 +1,7 @@
 // SVM front end (PermonSVM's role: train, model, predict) over the dual operators of svm.hip (dense rows) and svm_csr.hip (samples in CSR):
 //   L1: min 1/2 a'Ha - 1'a,          0 <= a <= C   (primal 1/2 |w|^2 + C sum xi)
 //   L2: min 1/2 a'(H + I/C)a - 1'a,  0 <= a        (primal 1/2 |w|^2 + C/2 sum xi^2)
+//   penalties (pmh_svm_set_penalties): C_i = (y_i > 0 ? C_pos : C_neg) weight_i per sample: L1 the upper bounds, L2 the diagonal 1 / C_i of the operator
 //   bias: additionally y'a = 0, posed as (y / sqrt(n))'a = 0 -- a one-row projector (onerow.hip) under SMALXE, whose penalty term the operator absorbs (qppf.hip)
 // H = diag(y) X X' diag(y).  No bias: MPGP on the box alone.  Model: w = X'(y o a) by the operator's pass-1 kernels; b by one pass over X (k_svm_bias);
 // prediction by one pass over the test samples (k_svm_predict: svm_sweep_rows, any d the operator accepts; k_svm_predict64 for d = 64: svm_sweep_rows64, the
@@ -25,6 +26,7 @@ struct pmh_svm_s {
   pmh_mpgp      mpgp  = nullptr;
   pmh_smalxe    sx    = nullptr;
   double       *alpha = nullptr, *rhs = nullptr, *lb = nullptr, *ub = nullptr, *row = nullptr, *w = nullptr, *part = nullptr, *scal = nullptr;
+  double       *Cv = nullptr, *Cinv = nullptr; // pmh_svm_set_penalties: C_i (n doubles) and, L2, 1 / C_i (the operator's diagonal); nullptr: opts.C everywhere
   std::vector<double> h_w;
   double        b = 0.0;
   int           trained = 0;
@@ -60,13 +62,15 @@ static __device__ __forceinline__ void svm_bias_row(long long i, double dot, con
     if (!(ubound > 0.0) || ai < ubound - astol) nf += 1.0, sb += yi - dot;
   }
 }
-// One pass over X for the bias: per workgroup the partial sums of svm_bias_row -> part[4][gridDim.x]
+// One pass over X for the bias: per workgroup the partial sums of svm_bias_row -> part[4][gridDim.x].  UBV: the upper bound of sample i is ubv[i] (per-sample
+// penalties, L1), not the scalar
+template <int UBV>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, const double *__restrict__ alpha, double astol,
-                                                        double ubound, double *__restrict__ part)
+                                                        double ubound, const double *__restrict__ ubv, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
   double            sb = 0.0, sya = 0.0, nf = 0.0, ns = 0.0;
-  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { svm_bias_row(i, dot, y, alpha, astol, ubound, sb, sya, nf, ns); });
+  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { svm_bias_row(i, dot, y, alpha, astol, UBV ? ubv[i] : ubound, sb, sya, nf, ns); });
   svm_store4(sb, sya, nf, ns, red, part);
 }
 // out[k] = sum_b part[k][b], k < K: one workgroup, fixed order (the counts are sums of ones: exact below 2^53)
@@ -119,12 +123,13 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double
 }
 
 // ---- samples in CSR: the same sums as k_svm_bias / k_svm_predict from the rows' dot products x_i . w (svm_csr.hip), one entry per thread ----
+template <int UBV>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias_dots(int n, const double *__restrict__ dots, const double *__restrict__ y, const double *__restrict__ alpha, double astol, double ubound,
-                                                             double *__restrict__ part)
+                                                             const double *__restrict__ ubv, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
   double            sb = 0.0, sya = 0.0, nf = 0.0, ns = 0.0;
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) svm_bias_row(i, dots[i], y, alpha, astol, ubound, sb, sya, nf, ns);
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) svm_bias_row(i, dots[i], y, alpha, astol, UBV ? ubv[i] : ubound, sb, sya, nf, ns);
   svm_store4(sb, sya, nf, ns, red, part);
 }
 // (dots and scores may be the same array)
@@ -155,11 +160,28 @@ extern "C" int pmh_svm_destroy(pmh_svm s)
   if (s->sx) pmh_smalxe_destroy(s->sx);
   if (s->pf) pmh_qppf_destroy(s->pf);
   if (s->H) pmh_op_destroy(s->H);
-  double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal, s->dots};
+  double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal, s->dots, s->Cv, s->Cinv};
   for (double *p : v)
     if (p) pmh_free(s->ctx, p);
   delete s;
   return PMH_SUCCESS;
+}
+
+// The solver over the handle's operator, vectors and projector: SMALXE (bias) or MPGP.  Both size their steps and penalties by the operator's largest
+// eigenvalue, estimated at creation: whoever changes the operator's terms (pmh_svm_set_penalties, L2) builds the solver anew
+static int svm_build_solver(pmh_svm s)
+{
+  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
+  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
+  if (s->o.bias) {
+    pmh_smalxe_opts so = s->o.smalxe;
+    so.rtol = s->o.qps.rtol, so.atol = s->o.qps.atol, so.divtol = s->o.qps.divtol;
+    if (s->o.qps.max_it_set) so.max_it = s->o.qps.max_it;
+    return pmh_smalxe_create(s->ctx, s->H, s->rhs, s->alpha, s->lb, s->ub, s->pf, &so, &s->sx);
+  }
+  pmh_mpgp_opts mo = s->o.mpgp;
+  mo.rtol = s->o.qps.rtol, mo.atol = s->o.qps.atol, mo.divtol = s->o.qps.divtol, mo.max_it = s->o.qps.max_it;
+  return pmh_mpgp_create(s->ctx, s->H, s->rhs, s->alpha, s->lb, s->ub, &mo, &s->mpgp);
 }
 
 // X_dev (dense rows) or Xcsr
@@ -200,15 +222,8 @@ static int svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_
         break;
       }
       if ((rc = pmh_qppf_create_onerow(ctx, s->row, n, &s->pf))) break;
-      pmh_smalxe_opts so = s->o.smalxe;
-      so.rtol = s->o.qps.rtol, so.atol = s->o.qps.atol, so.divtol = s->o.qps.divtol;
-      if (s->o.qps.max_it_set) so.max_it = s->o.qps.max_it;
-      if ((rc = pmh_smalxe_create(ctx, s->H, s->rhs, s->alpha, s->lb, s->ub, s->pf, &so, &s->sx))) break;
-    } else {
-      pmh_mpgp_opts mo = s->o.mpgp;
-      mo.rtol = s->o.qps.rtol, mo.atol = s->o.qps.atol, mo.divtol = s->o.qps.divtol, mo.max_it = s->o.qps.max_it;
-      if ((rc = pmh_mpgp_create(ctx, s->H, s->rhs, s->alpha, s->lb, s->ub, &mo, &s->mpgp))) break;
     }
+    if ((rc = svm_build_solver(s))) break;
   } while (0);
   if (rc) {
     pmh_svm_destroy(s);
@@ -252,13 +267,14 @@ static int svm_model(pmh_svm s)
   s->h_w.resize((size_t)s->d);
   const int    nb    = SVM_NB(s->n);
   const double astol = s->sx ? s->o.smalxe.inner.astol : s->o.mpgp.astol, ubound = s->o.loss_type == PMH_SVM_LOSS_L1 ? s->o.C : 0.0;
+  const double *ubv  = s->o.loss_type == PMH_SVM_LOSS_L1 ? s->Cv : nullptr; // per-sample penalties: free means a_i < C_i - astol
   if (s->n > 0 && s->Xcsr) {
     if (!s->dots) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)s->n, (void **)&s->dots));
     PMH_CHK(pmh_svm_csr_op_row_dots(H, s->w, s->dots));
-    hipLaunchKernelGGL(k_svm_bias_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, (const double *)s->dots, s->y, (const double *)s->alpha, astol, ubound, s->part);
+    hipLaunchKernelGGL((ubv ? k_svm_bias_dots<1> : k_svm_bias_dots<0>), dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, (const double *)s->dots, s->y, (const double *)s->alpha, astol, ubound, ubv, s->part);
   } else if (s->n > 0) {
     H->npass++;
-    hipLaunchKernelGGL(k_svm_bias, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, ubound, s->part);
+    hipLaunchKernelGGL((ubv ? k_svm_bias<1> : k_svm_bias<0>), dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, ubound, ubv, s->part);
   }
   PMH_CHK(svm_sum_part(s, s->n, nb));
   // the equality's multiplier: SMALXE keeps B'mu = mu row (the Lagrangian is 1/2 a'Ha - 1'a + mu (row'a)), so mu = row'(B'mu) / (row'row) and, with
@@ -340,6 +356,82 @@ extern "C" int pmh_svm_get_solver(pmh_svm s, pmh_op *H, pmh_qppf *pf, pmh_mpgp *
   if (mpgp) *mpgp = s->mpgp;
   if (smalxe) *smalxe = s->sx;
   return PMH_SUCCESS;
+}
+
+// ---- per-class and per-sample penalties ---------------------------------------------------------------------------------------------------------------------
+// how many weights are not positive and finite, or give a C_i = c_{y_i} weight_i that is not (a count: any order gives the same integer)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_weights_bad(int n, const double *__restrict__ y, const double *__restrict__ weight, double cpos, double cneg, int *__restrict__ bad)
+{
+  int b = 0;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const double wi = weight[i], ci = (y[i] > 0.0 ? cpos : cneg) * wi;
+    b += (wi > 0.0 && isfinite(wi) && ci > 0.0 && isfinite(ci)) ? 0 : 1;
+  }
+  if (b) atomicAdd(bad, b);
+}
+// Cv_i = (y_i > 0 ? cpos : cneg) weight_i (weight == nullptr: 1); ub / Cinv where given: ub_i = Cv_i, Cinv_i = 1 / Cv_i
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_fill_penalties(int n, const double *__restrict__ y, const double *__restrict__ weight, double cpos, double cneg, double *__restrict__ Cv,
+                                                                  double *__restrict__ ub, double *__restrict__ Cinv)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const double ci = (y[i] > 0.0 ? cpos : cneg) * (weight ? weight[i] : 1.0);
+    Cv[i] = ci;
+    if (ub) ub[i] = ci;
+    if (Cinv) Cinv[i] = 1.0 / ci;
+  }
+}
+
+extern "C" int pmh_svm_set_penalties(pmh_svm s, double C_pos, double C_neg, const double *weight_dev)
+{
+  PMH_ARG(s);
+  if (!(C_pos > 0.0) || !std::isfinite(C_pos)) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_set_penalties: C_pos = %g, must be positive and finite", C_pos);
+  if (!(C_neg > 0.0) || !std::isfinite(C_neg)) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_set_penalties: C_neg = %g, must be positive and finite", C_neg);
+  pmh_ctx      ctx = s->ctx;
+  const int    n   = s->n;
+  const size_t nb  = sizeof(double) * (size_t)(n ? n : 1);
+  const bool   L2  = s->o.loss_type == PMH_SVM_LOSS_L2;
+  if (weight_dev) {
+    // every rank decides alike: the counts are summed over the communicator before anything is changed
+    int  bad   = 0;
+    int *d_bad = nullptr;
+    PMH_CHK(pmh_malloc(ctx, sizeof(int), (void **)&d_bad));
+    int rc = pmh_memset(ctx, d_bad, 0, sizeof(int));
+    if (!rc && n > 0) {
+      hipLaunchKernelGGL(k_svm_weights_bad, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, s->y, weight_dev, C_pos, C_neg, d_bad);
+      if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_set_penalties: the launch that checks the weights failed");
+    }
+    if (!rc) rc = pmh_memcpy_d2h(ctx, &bad, d_bad, sizeof(int));
+    pmh_free(ctx, d_bad);
+    PMH_CHK(rc);
+    double nbad = (double)bad;
+    if (pmh_comm_on(ctx)) {
+      PMH_CHK(pmh_vec_set(ctx, 1, s->scal, nbad));
+      PMH_CHK(pmh_comm_allreduce_sum(ctx, s->scal, 1));
+      PMH_CHK(pmh_memcpy_d2h(ctx, &nbad, s->scal, sizeof(double)));
+    }
+    if (nbad != 0.0)
+      return pmh_set_error(PMH_ERR_ARG, "pmh_svm_set_penalties: %lld of the sample weights are not positive and finite (or give a penalty C_i that is not); masking samples out by a zero weight is not supported",
+                           (long long)nbad);
+  }
+  if (!s->Cv) PMH_CHK(pmh_malloc(ctx, nb, (void **)&s->Cv));
+  if (L2 && !s->Cinv) PMH_CHK(pmh_malloc(ctx, nb, (void **)&s->Cinv));
+  s->trained = 0;
+  if (n > 0) {
+    hipLaunchKernelGGL(k_svm_fill_penalties, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, s->y, weight_dev, C_pos, C_neg, s->Cv, L2 ? nullptr : s->ub, L2 ? s->Cinv : nullptr);
+    PMH_HIP(hipGetLastError());
+  }
+  if (L2) { // the diagonal 1 / C_i in place of the scalar 1 / C
+    PMH_CHK(pmh_op_svm_dual_set_terms(s->H, 0.0, 0.0));
+    PMH_CHK(pmh_op_svm_dual_set_diag(s->H, s->Cinv));
+  }
+  return svm_build_solver(s);
+}
+
+extern "C" int pmh_svm_get_penalties(pmh_svm s, double *c_dev)
+{
+  PMH_ARG(s && c_dev);
+  if (s->Cv) return pmh_vec_copy(s->ctx, s->n, s->Cv, c_dev);
+  return pmh_vec_set(s->ctx, s->n, c_dev, s->o.C);
 }
 
 // X (dense rows, n x d) or Xt (CSR)

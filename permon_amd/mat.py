@@ -698,6 +698,16 @@ def MatCreateSVMDual(ctx, X, y):
         """H + shift I + sigma y y' (pmh_op_svm_dual_set_terms); both 0: the plain operator."""
         check(ctx.L.pmh_op_svm_dual_set_terms(op.h, float(shift), float(sigma)))
 
+    def set_diag(diag=None):
+        """H + diag(diag) + sigma y y' (pmh_op_svm_dual_set_diag): a Vec or an array of n_local doubles, kept alive by the operator; None: off.  Excludes a
+        non-zero shift of set_terms."""
+        v = diag if diag is None or isinstance(diag, Vec) else Vec.from_numpy(ctx, np.ascontiguousarray(diag, dtype=np.float64).ravel())
+        if v is not None and v.n != n:
+            raise ValueError("set_diag: %d entries, the operator has %d rows" % (v.n, n))
+        check(ctx.L.pmh_op_svm_dual_set_diag(op.h, v.p if v is not None else None))
+        op._diag = v
+
     op.passes = passes
     op.set_terms = set_terms
+    op.set_diag = set_diag
     return op

@@ -2,6 +2,7 @@
 
     L1: min 1/2 a'Ha - 1'a,          0 <= a <= C
     L2: min 1/2 a'(H + I/C)a - 1'a,  0 <= a
+    penalties: C_i = (y_i > 0 ? C_pos : C_neg) sample_weight_i in place of C (L1: the bound of a_i; L2: the diagonal entry 1 / C_i)
     bias: additionally y'a = 0 (SMALXE over a one-row projector; without bias MPGP alone)
 
 H = diag(y) X X' diag(y).  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width (kept in CSR on the device: 24 bytes per stored entry for
@@ -17,9 +18,10 @@ from .mat import csr_from_scipy, is_sparse
 
 
 class SVM:
-    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options=""):
+    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", C_pos=None, C_neg=None):
         """options: a PETSc-style option string for the solver (-qps_rtol 1e-6, -qps_mpgp_*, -qps_smalxe_*, -smalxe_qps_* ...) and -svm_loss_type / -svm_C /
-        -svm_bias, which override the keyword arguments."""
+        -svm_bias, which override the keyword arguments.  C_pos / C_neg: the penalty of the samples with y = +1 / y = -1 (None: C)."""
+        self.C_pos, self.C_neg = C_pos, C_neg
         self.ctx, self.L = ctx, ctx.L
         o = _lib.SvmOpts()
         check(self.L.pmh_svm_default_opts(o))
@@ -37,8 +39,45 @@ class SVM:
     def _dev(self, a):
         return a if isinstance(a, Vec) else Vec.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.float64).ravel())
 
-    def create(self, X, y):
-        """Set the training samples (X: (n, d) row-major ndarray or scipy.sparse matrix, y: +-1) and build the solver without training."""
+    def create(self, X, y, sample_weight=None):
+        """Set the training samples (X: (n, d) row-major ndarray or scipy.sparse matrix, y: +-1) and build the solver without training.  sample_weight: n
+        positive numbers that scale the samples' penalties (None: all 1)."""
+        self._create(X, y)
+        if self.C_pos is not None or self.C_neg is not None or sample_weight is not None:
+            self.set_penalties(self.C_pos, self.C_neg, sample_weight)
+        return self
+
+    def set_penalties(self, C_pos=None, C_neg=None, sample_weight=None):
+        """C_i = (y_i > 0 ? C_pos : C_neg) sample_weight_i on the created handle (pmh_svm_set_penalties; None: C, C, all 1); the handle is untrained afterwards."""
+        self._need()
+        wd = None
+        if sample_weight is not None:
+            wd = self._dev(sample_weight)
+            if wd.n != self.n:
+                raise ValueError("SVM: sample_weight must have %d entries" % self.n)
+        try:
+            check(self.L.pmh_svm_set_penalties(self.h, float(self.C if C_pos is None else C_pos), float(self.C if C_neg is None else C_neg), wd.p if wd is not None else None))
+        finally:
+            if wd is not None and wd is not sample_weight:
+                wd.free()
+        return self
+
+    def train(self):
+        self._need()
+        check(self.L.pmh_svm_train(self.h))
+        return self
+
+    @property
+    def penalties(self):
+        """The effective penalty C_i of every training sample (pmh_svm_get_penalties)."""
+        self._need()
+        v = Vec(self.ctx, self.n, zero=False)
+        check(self.L.pmh_svm_get_penalties(self.h, v.p))
+        c = v.to_numpy()
+        v.free()
+        return c
+
+    def _create(self, X, y):
         self.destroy()
         if is_sparse(X):
             self.n, self.d = X.shape
@@ -63,8 +102,8 @@ class SVM:
         self.h, self._keep = h, (Xd, yd)
         return self
 
-    def fit(self, X, y):
-        self.create(X, y)
+    def fit(self, X, y, sample_weight=None):
+        self.create(X, y, sample_weight)
         check(self.L.pmh_svm_train(self.h))
         return self
 
