@@ -479,6 +479,12 @@ int pmh_op_svm_dual_set_diag(pmh_op op, const double *diag_dev /* n_local double
    (svm_csr.hip).  Creation builds a column-ordered device copy of X: 12 (nnz + n_local) bytes beside X.  Unsorted column indices and nnz + n_local >= 2^31 are
    PMH_ERR_ARG.  pmh_op_svm_dual_set_terms and pmh_op_svm_dual_passes apply (a pass = one sweep over all stored entries); no fused MPGP epilogues */
 int pmh_op_create_svm_dual_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, pmh_op *op);
+/* New labels on a created operator (dense rows or CSR): y_dev, n_local doubles of +-1, borrowed from now on in place of the old ones.  y_dev MAY be the buffer
+   the operator borrows already, with new contents: the operator reads nothing of the old labels from the caller's memory.  Dense rows: the pointer is swapped
+   and prepared sums of the paired passes are dropped, as by pmh_op_svm_dual_set_terms.  CSR: the column-ordered copy (12 (nnz + n_local) bytes) is re-signed in
+   place, every stored value times y_i(old) y_i(new) = +-1 from the signs the operator keeps itself -- 8 n_local bytes more beside the copy -- so the copy
+   equals, bit for bit, the one a fresh operator builds.  Terms and diagonal stay as set */
+int pmh_op_svm_dual_set_labels(pmh_op op, const double *y_dev /* n_local doubles, borrowed */);
 
 /* ---- QPS SMALXE (src/qps/impls/smalxe/smalxe.c) -------------------------------------------------------- */
 typedef struct {
@@ -593,6 +599,13 @@ int pmh_svm_get_solver(pmh_svm svm, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh
 int pmh_svm_set_penalties(pmh_svm svm, double C_pos, double C_neg, const double *weight_dev /* n_local doubles or NULL = all 1; copied */);
 /* the effective C_i (n_local doubles, device); opts.C everywhere if pmh_svm_set_penalties was never called */
 int pmh_svm_get_penalties(pmh_svm svm, double *c_dev /* n_local */);
+/* New labels on the created handle, X staying where it is (no upload, no new column-ordered copy; pmh_op_svm_dual_set_labels).  y_dev: n_local doubles of +-1,
+ * borrowed in place of the old ones; it may be the buffer lent at creation with new contents.  The equality's row y / sqrt(n) is refilled and its one-row
+ * projector rebuilt (bias); the penalties go back to the scalar opts.C (L1: ub = C; L2: the diagonal comes off, the shift is 1 / C; pmh_svm_get_penalties
+ * answers C everywhere) -- set them again afterwards: labels, then penalties; the handle is untrained and its solver built anew (handles from
+ * pmh_svm_get_solver must be fetched again).  A training afterwards gives alpha, w, b and every counter of the statistics identical to those of a fresh handle
+ * created on (X, y_dev) with the same options.  Allowed under a communicator: nothing is collective beyond what create does */
+int pmh_svm_set_labels(pmh_svm svm, const double *y_dev /* n_local doubles, borrowed */);
 /* one pass over the n samples of X_dev: scores_dev[i] = x_i . w + b, labels_dev[i] = +-1 (either may be NULL) */
 int pmh_svm_predict(pmh_svm svm, int n, const double *X_dev, double *scores_dev, double *labels_dev);
 /* one pass: counts = (TP, FP, TN, FN) of the predicted labels against y_dev (summed over the ranks under a communicator) */
@@ -604,6 +617,37 @@ int pmh_svm_create_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, const pmh_sv
 int pmh_svm_predict_csr(pmh_svm svm, pmh_csr Xt, double *scores_dev, double *labels_dev);
 int pmh_svm_test_csr(pmh_svm svm, pmh_csr Xt, const double *y_dev, long long counts[4]);
 int pmh_svm_destroy(pmh_svm svm);
+
+/* ---- SVM with more than two classes: one-vs-rest (svm_multi.hip) --------------------------------------------------------------------------------------------
+ * The classes are the distinct values of the n labels, ascending: c_0 < .. < c_{K-1}, K >= 2.  Training solves the K binary problems "class k (+1) against the
+ * rest (-1)" one after the other on ONE binary handle over X (pmh_svm_set_labels between them: X is uploaded once, the CSR operator's column-ordered copy is
+ * built once) and keeps W (K x d, row k = the w of class k) and b (K).  K = 2 trains two classifiers; pmh_svm is there for that case.  balanced: class k is
+ * trained with C_pos = C n / (2 n_k), C_neg = C n / (2 (n - n_k)) (pmh_svm_set_penalties, no sample weights), n_k the samples of class k; else C for both.
+ * Prediction is ONE pass over the test samples for up to pmh_svm_multi_chunk classes (per kernel path), ceil(K / chunk) passes in all: scores S[i,k] = x_i . W_k + b_k (n x K,
+ * row-major) and labels[i] = c_k of the greatest score of row i; ties go to the lowest class index; NaN scores are not a case.  No float atomics and a fixed
+ * summation order: two calls give the same bits, and scores-only, labels-only and both give the same arrays.  One GPU: a context with a communicator on is
+ * PMH_ERR_ARG, as are a label that is not finite and fewer than two classes.  X and labels_dev are borrowed. */
+typedef struct pmh_svm_multi_s *pmh_svm_multi;
+int pmh_svm_multi_chunk(int path, int *KC); /* classes per pass over the test samples, a compile-time constant per kernel path: 0 dense d = 64, 1 dense any d, 2 CSR */
+int pmh_svm_multi_create(pmh_ctx ctx, int n, int d, const double *X_dev, const double *labels_dev, const pmh_svm_opts *opts, int balanced, pmh_svm_multi *svm);
+int pmh_svm_multi_create_csr(pmh_ctx ctx, pmh_csr X, const double *labels_dev, const pmh_svm_opts *opts, int balanced, pmh_svm_multi *svm);
+int pmh_svm_multi_train(pmh_svm_multi svm);
+int pmh_svm_multi_get_classes(pmh_svm_multi svm, int *K, double *classes_host /* K, ascending; NULL to ask K */);
+/* the model; before pmh_svm_multi_train / pmh_svm_multi_set_model: PMH_ERR_STATE */
+int pmh_svm_multi_get_model(pmh_svm_multi svm, double *W_host /* K x d row-major, or NULL */, double *b_host /* K, or NULL */);
+/* a saved model: the handle counts as trained afterwards (it has no statistics) */
+int pmh_svm_multi_set_model(pmh_svm_multi svm, const double *W_host, const double *b_host);
+/* the statistics of class k's training (st may be NULL; PMH_ERR_STATE before pmh_svm_multi_train) and the penalties it is trained with (either may be NULL) */
+int pmh_svm_multi_get_stats(pmh_svm_multi svm, int k, pmh_svm_stats *st, double *C_pos, double *C_neg);
+/* scores_dev: n x K, labels_dev: n, either may be NULL.  Dense test samples need d <= 256, CSR test samples the model's d columns, whichever form the training
+   samples had; a mismatch is PMH_ERR_ARG.  Before a model exists: PMH_ERR_STATE */
+int pmh_svm_multi_predict(pmh_svm_multi svm, int n, const double *X_dev, double *scores_dev, double *labels_dev);
+int pmh_svm_multi_predict_csr(pmh_svm_multi svm, pmh_csr Xt, double *scores_dev, double *labels_dev);
+/* confusion[t K + p] = the samples of true class c_t predicted as c_p (K x K, host; integer atomics: counts have no order); a true label that is no class
+   is counted in *n_unknown (may be NULL) and in no cell */
+int pmh_svm_multi_test(pmh_svm_multi svm, int n, const double *X_dev, const double *labels_true_dev, long long *confusion, long long *n_unknown);
+int pmh_svm_multi_test_csr(pmh_svm_multi svm, pmh_csr Xt, const double *labels_true_dev, long long *confusion, long long *n_unknown);
+int pmh_svm_multi_destroy(pmh_svm_multi svm);
 
 
 /* ---- PC for the inner KSP of MATINV: multigrid V-cycle (PCMG semantics) ----------------------------------------

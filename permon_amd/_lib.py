@@ -269,6 +269,21 @@ _PROTOS = {
     "pmh_svm_predict_csr": [vp, vp, vp, vp],
     "pmh_svm_test_csr": [vp, vp, vp, C.POINTER(C.c_longlong)],
     "pmh_svm_destroy": [vp],
+    "pmh_op_svm_dual_set_labels": [vp, vp],
+    "pmh_svm_set_labels": [vp, vp],
+    "pmh_svm_multi_chunk": [C.c_int, c_int_p],
+    "pmh_svm_multi_create": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvmOpts), C.c_int, C.POINTER(vp)],
+    "pmh_svm_multi_create_csr": [vp, vp, vp, C.POINTER(SvmOpts), C.c_int, C.POINTER(vp)],
+    "pmh_svm_multi_train": [vp],
+    "pmh_svm_multi_get_classes": [vp, c_int_p, vp],
+    "pmh_svm_multi_get_model": [vp, vp, vp],
+    "pmh_svm_multi_set_model": [vp, vp, vp],
+    "pmh_svm_multi_get_stats": [vp, C.c_int, C.POINTER(SvmStats), c_double_p, c_double_p],
+    "pmh_svm_multi_predict": [vp, C.c_int, vp, vp, vp],
+    "pmh_svm_multi_predict_csr": [vp, vp, vp, vp],
+    "pmh_svm_multi_test": [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_multi_test_csr": [vp, vp, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_multi_destroy": [vp],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],
     "pmh_smalxe_destroy": [vp],

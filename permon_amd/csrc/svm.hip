@@ -549,6 +549,13 @@ extern "C" int pmh_op_svm_dual_set_diag(pmh_op op, const double *diag_dev)
   return PMH_SUCCESS;
 }
 
+extern "C" int pmh_op_svm_dual_set_labels(pmh_op op, const double *y_dev)
+{
+  SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
+  PMH_ARG(o && y_dev);
+  return o->set_labels(y_dev);
+}
+
 extern "C" int pmh_op_svm_dual_passes(pmh_op op, long long *passes)
 {
   SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);

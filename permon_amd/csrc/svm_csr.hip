@@ -20,6 +20,9 @@
 // column, d, holds y_i for every sample, so s = sum_i y_i a_i = w[d] is a segment like the others and a long one like the others.  The plain operator
 // (shift = sigma = sigma_fold = 0) stops the sweep before that column and runs the pass-2 kernel without the extra terms (MODE 1 instead of 2).  The copy
 // costs 12 (nnz + n) bytes of device memory beside the caller's matrix (8 value + 4 row index per entry); the labels are read at creation, not later.
+// New labels (pmh_op_svm_dual_set_labels) re-sign the copy in place: the operator keeps the signs it built the copy with (ysign, 8 n bytes more, its own
+// memory: the caller may hand over the very buffer it lent before, overwritten), and every stored value is multiplied by ysign_i y_i(new) = +-1, an exact
+// sign flip, so the copy equals the one a fresh operator builds from the new labels bit for bit (k_svc_resign).
 // The first segment of every span is found once, at creation, by binary search (k_svc_first): 4 bytes per span.
 //
 // Algorithmic bytes of one application: 24 nnz + 4 (n + d) + 8 (3 n + 2 d) (both copies' values and indices, the two pointer arrays, a, y, H a, w written
@@ -30,9 +33,9 @@
 #include <algorithm>
 
 #include "svm_internal.h"
+#include "svm_csr_seg.h"
 #include "reduce.h"
 
-#define SVC_SPAN 2048 // stored entries per workgroup: 8 per thread, 16 KiB of products in LDS (up to 8 workgroups per CU)
 typedef double svc_dbl2 __attribute__((ext_vector_type(2)));
 typedef int    svc_int2 __attribute__((ext_vector_type(2)));
 
@@ -64,17 +67,6 @@ template <int MODE> static __device__ __forceinline__ void svc_store(const svc_o
   if (MODE == 0) o.out[c] = v;
   else if (MODE == 1) o.out[c] = o.y[c] * v;
   else o.out[c] = svm_aug_row(o.y[c], v, sS, MODE == 3 ? o.diag[c] : o.shift, o.a[c]);
-}
-
-// the segments of span b: c0 .. c1.  A segment that ends exactly at the span's end is the span's; empty segments at that boundary too
-static __device__ __forceinline__ void svc_range(int b, int nb, int nseg, int end, const int *__restrict__ ptr, const int *__restrict__ first, int &c0, int &c1)
-{
-  c0 = first[b];
-  c1 = nseg - 1;
-  if (b + 1 < nb) {
-    const int cf = first[b + 1];
-    c1           = ptr[cf] == end ? cf - 1 : cf;
-  }
 }
 
 template <int MODE>
@@ -140,26 +132,33 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svc_fin(int nent, int nseg, int n
   if (lane == 0) svc_store<MODE>(o, c, s, MODE >= 2 ? o.sigma * *o.s : 0.0);
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------------------------------------
-struct svc_tab { // per compressed array: the spans' first segments and their shared pieces
-  int    *first = nullptr;
-  double *head = nullptr, *tail = nullptr;
-  int     nb = 0;
-};
-static inline int svc_nb(long long nent) { return (int)std::max<long long>(1, (nent + SVC_SPAN - 1) / SVC_SPAN); } // (no entries: one span, every segment sums to 0)
+// new labels: cval[q] = y_i(old) y_i(new) cval[q] for the entry q of sample i = crow[q] (column d included: y_i(old)^2 y_i(new) = y_i(new)); the products
+// with +-1 are exact.  ysign is brought up to date by k_svc_copy afterwards (every entry of a sample needs the old sign)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svc_resign(long long nent, const int *__restrict__ crow, const double *__restrict__ ysign, const double *__restrict__ ynew, double *__restrict__ cval)
+{
+  for (long long q = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; q < nent; q += (long long)gridDim.x * PMH_BLOCK) {
+    const int i = crow[q];
+    cval[q]     = (ysign[i] * ynew[i]) * cval[q];
+  }
+}
+__global__ __launch_bounds__(PMH_BLOCK) void k_svc_copy(int n, const double *__restrict__ src, double *__restrict__ dst)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) dst[i] = src[i];
+}
 
-static int svc_tab_free(pmh_ctx ctx, svc_tab *t)
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------------------
+int svc_tab_free(pmh_ctx ctx, svc_tab *t)
 {
   if (t->first) pmh_free(ctx, t->first), pmh_free(ctx, t->head), pmh_free(ctx, t->tail);
   t->first = nullptr, t->head = t->tail = nullptr;
   return PMH_SUCCESS;
 }
-static int svc_tab_build(pmh_ctx ctx, int nseg, const int *ptr, long long nent, svc_tab *t)
+int svc_tab_build(pmh_ctx ctx, int nseg, const int *ptr, long long nent, svc_tab *t, int ncol)
 {
   t->nb = svc_nb(nent);
   PMH_CHK(pmh_malloc(ctx, sizeof(int) * (size_t)t->nb, (void **)&t->first));
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)t->nb, (void **)&t->head));
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)t->nb, (void **)&t->tail));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)t->nb * ncol, (void **)&t->head));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)t->nb * ncol, (void **)&t->tail));
   hipLaunchKernelGGL(k_svc_first, dim3((t->nb + PMH_BLOCK - 1) / PMH_BLOCK), dim3(PMH_BLOCK), 0, ctx->stream, t->nb, nseg, ptr, t->first);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
@@ -180,10 +179,12 @@ struct SvmCsrOp : SvmDualBase {
   long long nnz = 0;
   int      *cptr = nullptr, *crow = nullptr; // the column-ordered copy: [d + 2], [nnz + n]
   double   *cval = nullptr, *w = nullptr;    // [nnz + n] (y_i x_ic; column d: y_i), [d + 1]
+  double   *ysign = nullptr;                 // [n] the labels cval was signed with (the operator's own copy)
   svc_tab   rows, cols;
   ~SvmCsrOp() override
   {
     pmh_free(ctx, cptr), pmh_free(ctx, crow), pmh_free(ctx, cval), pmh_free(ctx, w);
+    if (ysign) pmh_free(ctx, ysign);
     svc_tab_free(ctx, &rows), svc_tab_free(ctx, &cols);
   }
   // w[0 .. d) = X'(y o a); with_s: also w[d] = sum_i y_i a_i (the sweep goes on through column d)
@@ -192,6 +193,17 @@ struct SvmCsrOp : SvmDualBase {
     npass++;
     svc_out o{w, nullptr, nullptr, nullptr, 0.0, 0.0};
     return svc_sweep<0>(ctx, cols, with_s ? d + 1 : d, with_s ? nnz + n : nnz, cptr, crow, cval, a, o);
+  }
+  int set_labels(const double *y_dev) override
+  {
+    if (n > 0) {
+      const long long nent = nnz + n, nbl = (nent + PMH_BLOCK - 1) / PMH_BLOCK;
+      hipLaunchKernelGGL(k_svc_resign, dim3((unsigned)std::min<long long>(nbl, 8 * PMH_MAX_VEC_BLOCKS)), dim3(PMH_BLOCK), 0, ctx->stream, nent, (const int *)crow, (const double *)ysign, y_dev, cval);
+      hipLaunchKernelGGL(k_svc_copy, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, y_dev, ysign);
+      PMH_HIP(hipGetLastError());
+    }
+    y = y_dev;
+    return PMH_SUCCESS;
   }
   int mult(const double *a, double *Ha) override
   {
@@ -281,8 +293,10 @@ extern "C" int pmh_op_create_svm_dual_csr(pmh_ctx ctx, pmh_csr X, const double *
   int rc = PMH_SUCCESS;
   do {
     if ((rc = pmh_malloc(ctx, sizeof(int) * cp.size(), (void **)&o->cptr)) || (rc = pmh_malloc(ctx, sizeof(int) * (cr.size() + 2), (void **)&o->crow)) ||
-        (rc = pmh_malloc(ctx, sizeof(double) * (cv.size() + 2), (void **)&o->cval)) || (rc = pmh_malloc(ctx, sizeof(double) * ((size_t)d + 1), (void **)&o->w)))
+        (rc = pmh_malloc(ctx, sizeof(double) * (cv.size() + 2), (void **)&o->cval)) || (rc = pmh_malloc(ctx, sizeof(double) * ((size_t)d + 1), (void **)&o->w)) ||
+        (rc = pmh_malloc(ctx, sizeof(double) * (size_t)(n ? n : 1), (void **)&o->ysign)))
       break;
+    if (n > 0 && (rc = pmh_memcpy_h2d(ctx, o->ysign, yh.data(), sizeof(double) * yh.size()))) break;
     if ((rc = pmh_memcpy_h2d(ctx, o->cptr, cp.data(), sizeof(int) * cp.size()))) break;
     if (!cr.empty() && ((rc = pmh_memcpy_h2d(ctx, o->crow, cr.data(), sizeof(int) * cr.size())) || (rc = pmh_memcpy_h2d(ctx, o->cval, cv.data(), sizeof(double) * cv.size())))) break;
     if ((rc = pmh_memset(ctx, o->w, 0, sizeof(double) * ((size_t)d + 1)))) break;

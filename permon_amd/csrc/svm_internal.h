@@ -3,6 +3,8 @@
 #include "pmh_internal.h"
 
 #define SVM_KMAX 4 // d <= 64 * SVM_KMAX
+// grid of the row sweeps over n samples (svm_rows.h): 64 rows per workgroup, capped
+#define SVM_NB(n) ((int)((((long long)(n) + 63) / 64) < 1 ? 1 : ((((long long)(n) + 63) / 64) > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : (((long long)(n) + 63) / 64))))
 // a launch that streams X once (counted: pmh_op_svm_dual_passes); a kernel given as a template-id with a comma, or chosen by ?:, goes in parentheses
 #define SVM_PASS(...)                 \
   do {                                \
@@ -36,6 +38,14 @@ struct SvmDualBase : pmh_op_s {
   // w = X'(y o a) into the operator's own w (d doubles, device; all-reduced under a communicator) by the pass-1 kernels (the model of a trained SVM)
   virtual int   form_w(const double *a, const double **w_dev) = 0;
   virtual void  terms_changed() {} // pmh_op_svm_dual_set_terms / pmh_op_svm_dual_set_diag was called
+  // pmh_op_svm_dual_set_labels: new labels (n doubles of +-1, borrowed; may be the buffer borrowed so far with new contents).  Whatever the operator derived
+  // from the old labels it redoes from state of its own, never from the caller's memory
+  virtual int   set_labels(const double *y_dev)
+  {
+    y = y_dev;
+    terms_changed();
+    return PMH_SUCCESS;
+  }
 };
 
 struct SvmDualOp : SvmDualBase {

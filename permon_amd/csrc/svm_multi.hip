@@ -1,0 +1,548 @@
+// SVM with more than two classes: K-column scoring in one pass over the test samples, and the one-vs-rest front end (pmh_svm_multi_*) over ONE binary handle.
+//
+// Scoring: S[i,k] = x_i . W_k + b_k (n x K, row-major) and label[i] = the class value of the greatest score of row i (ties: the lowest class index; NaN scores
+// are not a case).  Either output may be NULL.  The classes go through a sweep in chunks of SVMM_KC: the chunk's weights sit in registers (dense) or are
+// gathered as SVMM_KC contiguous doubles per stored entry (CSR), so one read of a sample serves SVMM_KC dot products.  K > SVMM_KC: one sweep per chunk, chunks
+// ascending; the running greatest score of a row travels in a workspace of n doubles (best), and a later chunk takes the label only with a strictly greater
+// score, so the lowest class index wins a tie across chunks as inside one.  No float atomics; the order of every sum is fixed (below), so two calls give the
+// same bits, and a class's score does not depend on where in its chunk it sits, nor on which outputs were asked for.
+//
+//   dense, d = 64 (k_svmm_rows64): the row-pair layout and 16-byte non-temporal loads of svm_rows.h (lanes 0-31 row r, lanes 32-63 row r + 1, lane l2 holds
+//     columns 2 l2, 2 l2 + 1).  Per class the lane's partial sum is x_0 w_0 + x_1 w_1 (two products, one addition), then the halving butterfly over the 32
+//     lanes of the row (svmm_halve): at offset 16 a lane keeps the sums of one half of the chunk's classes and gives the other half to its partner, at 8 and 4
+//     again (4 + 2 + 1 shuffles for a chunk of 8; for the chunk of 4 in use: offsets 16 and 8, 2 + 1 shuffles), every step kept + received; then the sum of the
+//     one class left is completed over the remaining offsets (.., 2, 1: t + partner's t).  The class c of the chunk ends in lanes c (32 / KC) .. of the row.  Last: + b_k.
+//   dense, any d <= 256 (k_svmm_rows): one wavefront per row as svm_sweep_rows, lane j holds columns j, j + 64, ..; per class 0 + x_j w_j + x_{j+64} w_{j+64} + ..
+//     (columns past d count as 0 * 0), then the same butterfly over 64 lanes (a chunk of 4: offsets 32, 16 halving; 8, 4, 2, 1 completing), + b_k.
+//   CSR (k_svmm_seg / k_svmm_fin): the entry-partitioned segmented sum of svm_csr.hip with SVMM_KC sums per segment.  A workgroup stages its span's values and
+//     column indices in LDS (24 KiB); the G lanes of a sample add, per class, val * Wt[col][class] over the sample's entries lo + l, lo + l + G, .. ascending,
+//     then the shfl_down tree G/2 .. 1; samples shared between spans are finished in the span where they end: the pieces in span order over the lanes of one
+//     wavefront, then pmh_wave_sum, per class.  Last: + b_k.  Wt is the chunk's weights as d x SVMM_KC, class index fastest: 8 SVMM_KC contiguous bytes per stored entry.
+//     Work is divided by entries, a sample without entries scores b_k, one long sample is summed by whole wavefronts in many spans.
+//
+// Algorithmic bytes of one call: dense 8 n d ceil(K / KC) + 8 n K (scores) + 8 n (labels), against K (8 n d + 8 n) for K binary calls; CSR 12 nnz ceil(K / KC)
+// + 4 n + 8 n K + 8 n, the gathers of Wt (8 KC bytes per entry) served by the caches where 8 KC d bytes fit.
+//
+// One-vs-rest training: the K binary problems "class k against the rest" are trained one after the other on ONE pmh_svm handle over X -- X is uploaded once and
+// the CSR operator's column-ordered copy is built once; pmh_svm_set_labels re-labels the handle between the classes -- and give W (K x d) and b (K).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "svm_csr_seg.h"
+#include "svm_internal.h"
+#include "svm_rows.h"
+
+// classes per sweep (SVMM_KC in the text above), a power of two >= 2, per path: dense d = 64 (<= 32), dense any d (<= 64), CSR.  Measured with 4, 8 and 16
+// on every path (docs/LAB_NOTEBOOK.md, "SVM multiclass"): the sweeps are bound by their instructions, not by HBM, a sweep's time grows about in proportion
+// to its chunk, and 4 is the one value with which one call beats K binary calls at K = 4 and K = 10 on all three paths (8 is ahead only at K = 32, by <= 20 %)
+#ifndef SVMM_KC64
+#define SVMM_KC64 4
+#endif
+#ifndef SVMM_KCD
+#define SVMM_KCD 4
+#endif
+#ifndef SVMM_KCC
+#define SVMM_KCC 4
+#endif
+
+// where a chunk's results go
+struct svmm_out {
+  int           K, k0, kc; // classes in all; the chunk's first class and its number of classes (<= SVMM_KC)
+  const double *b, *classes; // K each
+  double       *scores, *labels; // n x K / n, either may be nullptr
+  double       *best;            // n: the greatest score of the chunks so far (K > SVMM_KC and labels asked for), else nullptr
+};
+
+// row i's greatest score of this chunk, bv of class index bk: the label, unless an earlier chunk holds a score at least as great
+static __device__ __forceinline__ void svmm_label(const svmm_out &o, long long i, double bv, int bk)
+{
+  if (o.k0 > 0 && !(bv > o.best[i])) return;
+  if (o.best) o.best[i] = bv;
+  o.labels[i] = o.classes[bk];
+}
+
+// all KC sums of row i in one lane (the CSR kernels): + b_k, scores, the chunk's first maximum
+template <int KC> static __device__ __forceinline__ void svmm_row_done(const svmm_out &o, long long i, const double (&s)[KC])
+{
+  double bv = -INFINITY;
+  int    bk = o.k0;
+#pragma unroll
+  for (int j = 0; j < KC; j++)
+    if (j < o.kc) {
+      const double t = s[j] + o.b[o.k0 + j];
+      if (o.scores) o.scores[(size_t)i * o.K + o.k0 + j] = t;
+      if (t > bv) bv = t, bk = o.k0 + j;
+    }
+  if (o.labels) svmm_label(o, i, bv, bk);
+}
+
+// The halving butterfly: each of LW lanes (l = the lane's index among them) holds KC partial sums; returns the full sum of class l / (LW / KC) in every
+// lane.  KC / 2 + KC / 4 + .. + 1 shuffles to one class per lane, then log2(LW / KC) to complete it
+template <int KC, int LW> static __device__ __forceinline__ double svmm_halve(double (&s)[KC], int l)
+{
+  static_assert((KC & (KC - 1)) == 0 && KC <= LW, "SVMM_KC: a power of two, at most the lanes of a row");
+#pragma unroll
+  for (int m = KC / 2, off = LW / 2; m >= 1; m >>= 1, off >>= 1) {
+    const bool up = (l & off) != 0;
+#pragma unroll
+    for (int j = 0; j < m; j++) {
+      const double give = up ? s[j] : s[j + m], keep = up ? s[j + m] : s[j];
+      s[j] = keep + __shfl_xor(give, off, 64);
+    }
+  }
+  double t = s[0];
+#pragma unroll
+  for (int off = LW / KC / 2; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
+  return t;
+}
+
+// the LW lanes of row i after svmm_halve: lane l holds t = the sum of the chunk's class l / (LW / KC).  Every lane of the wavefront calls this (shuffles);
+// live: the row exists
+template <int KC, int LW> static __device__ __forceinline__ void svmm_lanes_done(const svmm_out &o, long long i, bool live, int l, double t, double bc)
+{
+  constexpr int LPC = LW / KC; // lanes per class
+  const int     c   = l / LPC;
+  t += bc;
+  if (o.labels) { // (uniform: a kernel argument)
+    double bv = c < o.kc ? t : -INFINITY;
+    int    bk = o.k0 + c;
+#pragma unroll
+    for (int off = LPC; off < LW; off <<= 1) {
+      const double v2 = __shfl_xor(bv, off, 64);
+      const int    k2 = __shfl_xor(bk, off, 64);
+      if (v2 > bv || (v2 == bv && k2 < bk)) bv = v2, bk = k2;
+    }
+    if (live && l == 0) svmm_label(o, i, bv, bk);
+  }
+  if (o.scores && live && (l % LPC) == 0 && c < o.kc) o.scores[(size_t)i * o.K + o.k0 + c] = t;
+}
+
+// d == 64: W is the model (K x 64, row-major)
+template <int KC, int UNR> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows64(int n, const double *__restrict__ X, const double *__restrict__ W, svmm_out o)
+{
+  const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
+  const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
+  dbl2            wr[KC];
+#pragma unroll
+  for (int c = 0; c < KC; c++) wr[c] = c < o.kc ? ((const dbl2 *)(W + (size_t)(o.k0 + c) * 64))[l2] : dbl2{0.0, 0.0};
+  const int    myc = l2 / (32 / KC);
+  const double bc  = myc < o.kc ? o.b[o.k0 + myc] : 0.0;
+  for (long long r0 = gw * 2 * UNR; r0 < n; r0 += nw * 2 * UNR) {
+    dbl2 v[UNR];
+    svm_load_rows64<UNR>(n, X, r0, v);
+#pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      const long long i = r0 + 2 * u + half;
+      double          s[KC];
+#pragma unroll
+      for (int c = 0; c < KC; c++) s[c] = v[u].x * wr[c].x + v[u].y * wr[c].y;
+      const double t = svmm_halve<KC, 32>(s, l2);
+      svmm_lanes_done<KC, 32>(o, i, i < n, l2, t, bc);
+    }
+  }
+}
+
+// any d <= 64 SVM_KMAX: W is the model (K x d, row-major)
+template <int KC> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ W, svmm_out o)
+{
+  const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
+  double          wr[KC][SVM_KMAX];
+#pragma unroll
+  for (int c = 0; c < KC; c++)
+#pragma unroll
+    for (int k = 0; k < SVM_KMAX; k++) wr[c][k] = (c < o.kc && lane + 64 * k < d) ? W[(size_t)(o.k0 + c) * d + lane + 64 * k] : 0.0;
+  const int    myc = lane / (64 / KC);
+  const double bc  = myc < o.kc ? o.b[o.k0 + myc] : 0.0;
+  for (long long i = gw; i < n; i += nw) {
+    const double *xr = X + (size_t)i * d;
+    double        x[SVM_KMAX], s[KC];
+#pragma unroll
+    for (int k = 0; k < SVM_KMAX; k++) x[k] = (lane + 64 * k < d) ? __builtin_nontemporal_load(&xr[lane + 64 * k]) : 0.0;
+#pragma unroll
+    for (int c = 0; c < KC; c++) {
+      double a = 0.0;
+#pragma unroll
+      for (int k = 0; k < SVM_KMAX; k++) a += x[k] * wr[c][k];
+      s[c] = a;
+    }
+    const double t = svmm_halve<KC, 64>(s, lane);
+    svmm_lanes_done<KC, 64>(o, i, true, lane, t, bc);
+  }
+}
+
+// CSR: span b's pieces of the samples' KC sums (k_svc_seg with KC columns; Wt: d x KC, class index fastest; head / tail: KC doubles per span)
+template <int KC>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_seg(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ Wt,
+                                                        const int *__restrict__ first, double *__restrict__ head, double *__restrict__ tail, svmm_out o)
+{
+  __shared__ dbl2 sval2[SVC_SPAN / 2];
+  typedef int     int2v __attribute__((ext_vector_type(2)));
+  __shared__ int2v sidx2[SVC_SPAN / 2];
+  const int        b = blockIdx.x, start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent);
+  // the span's values and indices: 16-byte and 8-byte loads (start is even and the arrays are 16-byte aligned); entries past the end: 0, column 0, never read
+#pragma unroll
+  for (int j = 0; j < SVC_SPAN / PMH_BLOCK / 2; j++) {
+    const int q = j * PMH_BLOCK + (int)threadIdx.x, k = start + 2 * q;
+    dbl2      v = dbl2{0.0, 0.0};
+    int2v     ix = int2v{0, 0};
+    if (k + 1 < end) {
+      v  = __builtin_nontemporal_load((const dbl2 *)(val + k));
+      ix = __builtin_nontemporal_load((const int2v *)(idx + k));
+    } else if (k < end) v.x = val[k], ix.x = idx[k];
+    sval2[q] = v, sidx2[q] = ix;
+  }
+  __syncthreads();
+  const double *sval = (const double *)sval2;
+  const int    *sidx = (const int *)sidx2;
+  int           c0, c1;
+  svc_range(b, nb, nseg, end, ptr, first, c0, c1);
+  // lanes per sample: as k_svc_seg
+  const int avg = (end - start) / (c1 - c0 + 1);
+  int       G   = 1;
+  while (G < 64 && G * 8 <= avg) G <<= 1;
+  const int g = threadIdx.x / G, l = threadIdx.x % G;
+  for (int c = c0 + g; c <= c1; c += PMH_BLOCK / G) { // (the trip count is uniform over a sample's G lanes)
+    const int p0 = ptr[c], p1 = ptr[c + 1], lo = max(p0, start) - start, hi = min(p1, end) - start;
+    double    s[KC];
+#pragma unroll
+    for (int j = 0; j < KC; j++) s[j] = 0.0;
+    for (int k = lo + l; k < hi; k += G) {
+      const double  xv = sval[k];
+      const dbl2   *wr = (const dbl2 *)(Wt + (size_t)sidx[k] * KC);
+#pragma unroll
+      for (int j = 0; j < KC / 2; j++) {
+        const dbl2 w2 = wr[j];
+        s[2 * j] += xv * w2.x, s[2 * j + 1] += xv * w2.y;
+      }
+    }
+    for (int w = G >> 1; w > 0; w >>= 1)
+#pragma unroll
+      for (int j = 0; j < KC; j++) s[j] += __shfl_down(s[j], w, G);
+    if (l == 0) {
+      if (p0 >= start && p1 <= end) svmm_row_done<KC>(o, c, s); // the whole sample lies in this span
+      else {
+        double *dst = (c == c0 ? head : tail) + (size_t)b * KC;
+#pragma unroll
+        for (int j = 0; j < KC; j++) dst[j] = s[j];
+      }
+    }
+  }
+}
+
+// one wavefront per span (k_svc_fin with KC columns): the sample that began in an earlier span and ends in this one
+template <int KC>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_fin(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ first, const double *__restrict__ head,
+                                                        const double *__restrict__ tail, svmm_out o)
+{
+  const int lane = threadIdx.x & 63, b = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
+  if (b >= nb) return;
+  const int start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent), c = first[b], p0 = ptr[c], p1 = ptr[c + 1];
+  if (!(p0 < start && p1 <= end)) return; // (wave-uniform)
+  const int  b0    = p0 / SVC_SPAN;
+  const bool tail0 = first[b0] != c; // in the span where it begins the sample is the last of several: its piece is that span's tail
+  double     s[KC];
+#pragma unroll
+  for (int j = 0; j < KC; j++) s[j] = 0.0;
+  for (int bb = b0 + lane; bb <= b; bb += 64) {
+    const double *p = ((bb == b0 && tail0) ? tail : head) + (size_t)bb * KC;
+#pragma unroll
+    for (int j = 0; j < KC; j++) s[j] += p[j];
+  }
+#pragma unroll
+  for (int j = 0; j < KC; j++) s[j] = pmh_wave_sum(s[j]);
+  if (lane == 0) svmm_row_done<KC>(o, c, s);
+}
+
+// Wt[ch][col][j] = W[ch KC + j][col] (0 past the last class): the model as the CSR sweep gathers it
+template <int KC> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_pack(int K, int d, long long total, const double *__restrict__ W, double *__restrict__ Wt)
+{
+  for (long long t = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; t < total; t += (long long)gridDim.x * PMH_BLOCK) {
+    const int       j = (int)(t % KC);
+    const long long r = t / KC;
+    const int       col = (int)(r % d), k = (int)(r / d) * KC + j;
+    Wt[t] = k < K ? W[(size_t)k * d + col] : 0.0;
+  }
+}
+
+// y_i = +1 where label_i == c, else -1: the binary problem "class c against the rest"
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_relabel(int n, const double *__restrict__ labels, double c, double *__restrict__ y)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) y[i] = labels[i] == c ? 1.0 : -1.0;
+}
+
+// the index of v in the ascending classes, or K
+static __device__ __forceinline__ int svmm_class_index(int K, const double *__restrict__ classes, double v)
+{
+  int lo = 0, hi = K;
+  while (lo < hi) {
+    const int mid = (lo + hi) / 2;
+    if (classes[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < K && classes[lo] == v) ? lo : K;
+}
+// conf[t K + p]++ for the true class t and the predicted class p of every sample; conf[K K]++ where the true label is no class (counts: integer atomics, any
+// order gives the same integers)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_confusion(int n, int K, const double *__restrict__ classes, const double *__restrict__ pred, const double *__restrict__ ytrue,
+                                                              unsigned long long *__restrict__ conf)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const int t = svmm_class_index(K, classes, ytrue[i]), p = svmm_class_index(K, classes, pred[i]);
+    atomicAdd(&conf[(t < K && p < K) ? (size_t)t * K + p : (size_t)K * K], 1ull);
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------------------
+struct pmh_svm_multi_s {
+  pmh_ctx       ctx;
+  int           n = 0, d = 0, K = 0, nchc = 0, balanced = 0; // nchc: chunks of the CSR sweep
+  int           cur = 0; // the class the binary handle is labelled for
+  pmh_svm_opts  o;
+  const double *labels = nullptr; // the training labels, borrowed
+  pmh_svm       bin    = nullptr; // the one binary handle over X
+  double       *y = nullptr, *W = nullptr, *Wt = nullptr, *b = nullptr, *classes = nullptr; // device: n (the binary handle borrows it), K d, nch d KC, K, K
+  std::vector<double>        h_classes, h_W, h_b;
+  std::vector<long long>     count; // samples per class
+  std::vector<pmh_svm_stats> st;    // per class, of the last pmh_svm_multi_train
+  int           trained = 0, have_stats = 0;
+};
+
+extern "C" int pmh_svm_multi_chunk(int path, int *KC)
+{
+  PMH_ARG(KC && path >= 0 && path <= 2);
+  *KC = path == 0 ? SVMM_KC64 : (path == 1 ? SVMM_KCD : SVMM_KCC);
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_destroy(pmh_svm_multi m)
+{
+  if (!m) return PMH_SUCCESS;
+  if (m->bin) pmh_svm_destroy(m->bin);
+  double *v[] = {m->y, m->W, m->Wt, m->b, m->classes};
+  for (double *p : v)
+    if (p) pmh_free(m->ctx, p);
+  delete m;
+  return PMH_SUCCESS;
+}
+
+static int svmm_relabel(pmh_svm_multi m, int k)
+{
+  if (m->n > 0) hipLaunchKernelGGL(k_svmm_relabel, dim3(pmh_vec_grid(m->n)), dim3(PMH_BLOCK), 0, m->ctx->stream, m->n, m->labels, m->h_classes[(size_t)k], m->y);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+static int svmm_create(pmh_ctx ctx, int n, int d, const double *X_dev, pmh_csr Xcsr, const double *labels_dev, const pmh_svm_opts *opts, int balanced, pmh_svm_multi *out)
+{
+  const char *who = Xcsr ? "pmh_svm_multi_create_csr" : "pmh_svm_multi_create";
+  if (pmh_comm_on(ctx)) return pmh_set_error(PMH_ERR_ARG, "%s: a communicator is on; the one-vs-rest front end runs on one GPU", who);
+  std::vector<double> lab((size_t)n);
+  if (n > 0) PMH_CHK(pmh_memcpy_d2h(ctx, lab.data(), labels_dev, sizeof(double) * lab.size()));
+  for (int i = 0; i < n; i++)
+    if (!std::isfinite(lab[(size_t)i])) return pmh_set_error(PMH_ERR_ARG, "%s: the label of sample %d is not finite", who, i);
+  std::vector<double> cls(lab);
+  std::sort(cls.begin(), cls.end());
+  cls.erase(std::unique(cls.begin(), cls.end()), cls.end());
+  if (cls.size() < 2) return pmh_set_error(PMH_ERR_ARG, "%s: %d distinct labels, a classifier needs at least two", who, (int)cls.size());
+  pmh_svm_multi m = new pmh_svm_multi_s();
+  m->ctx = ctx, m->n = n, m->d = d, m->K = (int)cls.size(), m->nchc = (m->K + SVMM_KCC - 1) / SVMM_KCC, m->balanced = balanced ? 1 : 0, m->o = *opts, m->labels = labels_dev;
+  m->h_classes = cls;
+  m->count.assign((size_t)m->K, 0);
+  for (int i = 0; i < n; i++) m->count[(size_t)(std::lower_bound(cls.begin(), cls.end(), lab[(size_t)i]) - cls.begin())]++;
+  m->h_W.assign((size_t)m->K * d, 0.0), m->h_b.assign((size_t)m->K, 0.0);
+  m->st.resize((size_t)m->K);
+  int rc = PMH_SUCCESS;
+  do {
+    if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&m->y)) || (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->K * d, (void **)&m->W)) ||
+        (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->nchc * d * SVMM_KCC, (void **)&m->Wt)) || (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->K, (void **)&m->b)) ||
+        (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->K, (void **)&m->classes)))
+      break;
+    if ((rc = pmh_memcpy_h2d(ctx, m->classes, cls.data(), sizeof(double) * cls.size()))) break;
+    if ((rc = svmm_relabel(m, 0))) break; // the binary handle is created on the labels of class 0
+    rc = Xcsr ? pmh_svm_create_csr(ctx, Xcsr, m->y, opts, &m->bin) : pmh_svm_create(ctx, n, d, X_dev, m->y, opts, &m->bin);
+  } while (0);
+  if (rc) {
+    pmh_svm_multi_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_create(pmh_ctx ctx, int n, int d, const double *X_dev, const double *labels_dev, const pmh_svm_opts *opts, int balanced, pmh_svm_multi *out)
+{
+  PMH_ARG(ctx && out && opts && n >= 1 && d >= 1 && d <= 64 * SVM_KMAX && X_dev && labels_dev);
+  return svmm_create(ctx, n, d, X_dev, nullptr, labels_dev, opts, balanced, out);
+}
+
+extern "C" int pmh_svm_multi_create_csr(pmh_ctx ctx, pmh_csr X, const double *labels_dev, const pmh_svm_opts *opts, int balanced, pmh_svm_multi *out)
+{
+  PMH_ARG(ctx && out && opts && X && labels_dev && X->ctx == ctx && X->nrows >= 1);
+  if (X->ncols < 1) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_create_csr: the sample matrix has no columns");
+  return svmm_create(ctx, X->nrows, X->ncols, nullptr, X, labels_dev, opts, balanced, out);
+}
+
+// the penalties of the binary problem of class k
+static void svmm_penalties(pmh_svm_multi m, int k, double *C_pos, double *C_neg)
+{
+  const double C = m->o.C, n = (double)m->n, nk = (double)m->count[(size_t)k];
+  *C_pos = m->balanced ? C * n / (2.0 * nk) : C;
+  *C_neg = m->balanced ? C * n / (2.0 * (n - nk)) : C;
+}
+
+// the host model -> W, b and the CSR sweep's Wt on the device
+static int svmm_upload_model(pmh_svm_multi m)
+{
+  PMH_CHK(pmh_memcpy_h2d(m->ctx, m->W, m->h_W.data(), sizeof(double) * m->h_W.size()));
+  PMH_CHK(pmh_memcpy_h2d(m->ctx, m->b, m->h_b.data(), sizeof(double) * m->h_b.size()));
+  const long long total = (long long)m->nchc * m->d * SVMM_KCC, nbl = (total + PMH_BLOCK - 1) / PMH_BLOCK;
+  hipLaunchKernelGGL(k_svmm_pack<SVMM_KCC>, dim3((unsigned)std::min<long long>(nbl, PMH_MAX_VEC_BLOCKS)), dim3(PMH_BLOCK), 0, m->ctx->stream, m->K, m->d, total, (const double *)m->W, m->Wt);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_train(pmh_svm_multi m)
+{
+  PMH_ARG(m);
+  m->trained = m->have_stats = 0;
+  for (int k = 0; k < m->K; k++) {
+    if (k != m->cur) { // (a fresh handle is labelled for class 0 already)
+      m->cur = -1;
+      PMH_CHK(svmm_relabel(m, k)); // into the buffer the handle borrows already
+      PMH_CHK(pmh_svm_set_labels(m->bin, m->y));
+      m->cur = k;
+    }
+    if (m->balanced) {
+      double cp, cn;
+      svmm_penalties(m, k, &cp, &cn);
+      PMH_CHK(pmh_svm_set_penalties(m->bin, cp, cn, nullptr));
+    }
+    PMH_CHK(pmh_svm_train(m->bin));
+    PMH_CHK(pmh_svm_get_model(m->bin, m->h_W.data() + (size_t)k * m->d, &m->h_b[(size_t)k]));
+    PMH_CHK(pmh_svm_get_stats(m->bin, &m->st[(size_t)k]));
+  }
+  PMH_CHK(svmm_upload_model(m));
+  m->trained = m->have_stats = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_get_classes(pmh_svm_multi m, int *K, double *classes_host)
+{
+  PMH_ARG(m);
+  if (K) *K = m->K;
+  if (classes_host) memcpy(classes_host, m->h_classes.data(), sizeof(double) * (size_t)m->K);
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_get_model(pmh_svm_multi m, double *W_host, double *b_host)
+{
+  PMH_ARG(m);
+  if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_get_model: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
+  if (W_host) memcpy(W_host, m->h_W.data(), sizeof(double) * m->h_W.size());
+  if (b_host) memcpy(b_host, m->h_b.data(), sizeof(double) * m->h_b.size());
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_set_model(pmh_svm_multi m, const double *W_host, const double *b_host)
+{
+  PMH_ARG(m && W_host && b_host);
+  m->trained = m->have_stats = 0;
+  memcpy(m->h_W.data(), W_host, sizeof(double) * m->h_W.size());
+  memcpy(m->h_b.data(), b_host, sizeof(double) * m->h_b.size());
+  PMH_CHK(svmm_upload_model(m));
+  m->trained = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_get_stats(pmh_svm_multi m, int k, pmh_svm_stats *st, double *C_pos, double *C_neg)
+{
+  PMH_ARG(m && k >= 0 && k < m->K);
+  if (st) {
+    if (!m->have_stats) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_get_stats: call pmh_svm_multi_train first (a model that was set has no statistics)");
+    *st = m->st[(size_t)k];
+  }
+  double cp, cn;
+  svmm_penalties(m, k, &cp, &cn);
+  if (C_pos) *C_pos = cp;
+  if (C_neg) *C_neg = cn;
+  return PMH_SUCCESS;
+}
+
+// X (dense rows, n x d) or Xt (CSR): one sweep per chunk of classes, chunks ascending
+static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *scores, double *labels)
+{
+  PMH_ARG(m && n >= 0 && (X || Xt || n == 0));
+  if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_predict: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
+  if (Xt && Xt->ncols != m->d) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_predict_csr: the test samples have %d features, the model has %d", Xt->ncols, m->d);
+  if (!Xt && m->d > 64 * SVM_KMAX)
+    return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_predict: dense test samples need d <= %d, the model has d = %d: hand them over in CSR (pmh_svm_multi_predict_csr)", 64 * SVM_KMAX, m->d);
+  if (Xt && Xt->nnz >= (1LL << 31) - SVC_SPAN) return pmh_set_error(PMH_ERR_ARG, "SVM on CSR samples: %lld stored entries, the count must stay below 2^31 (32-bit offsets)", Xt->nnz);
+  if (n == 0 || (!scores && !labels)) return PMH_SUCCESS;
+  pmh_ctx ctx  = m->ctx;
+  double *best = nullptr;
+  const int kcp = Xt ? SVMM_KCC : (m->d == 64 ? SVMM_KC64 : SVMM_KCD), nch = (m->K + kcp - 1) / kcp; // the path's chunk
+  if (labels && nch > 1) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&best));
+  svc_tab t;
+  int     rc = Xt ? svc_tab_build(ctx, n, Xt->d_rowptr, Xt->nnz, &t, SVMM_KCC) : PMH_SUCCESS;
+  for (int ch = 0; ch < nch && !rc; ch++) {
+    svmm_out o{m->K, ch * kcp, std::min(kcp, m->K - ch * kcp), m->b, m->classes, scores, labels, best};
+    if (Xt) {
+      const int nb = t.nb;
+      hipLaunchKernelGGL(k_svmm_seg<SVMM_KCC>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, (int)Xt->nnz, n, nb, (const int *)Xt->d_rowptr, (const int *)Xt->d_col, (const double *)Xt->d_val,
+                         (const double *)(m->Wt + (size_t)ch * m->d * SVMM_KCC), (const int *)t.first, t.head, t.tail, o);
+      hipLaunchKernelGGL(k_svmm_fin<SVMM_KCC>, dim3((nb + PMH_BLOCK / 64 - 1) / (PMH_BLOCK / 64)), dim3(PMH_BLOCK), 0, ctx->stream, (int)Xt->nnz, n, nb, (const int *)Xt->d_rowptr, (const int *)t.first,
+                         (const double *)t.head, (const double *)t.tail, o);
+    } else if (m->d == 64) hipLaunchKernelGGL((k_svmm_rows64<SVMM_KC64, 4>), dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, X, (const double *)m->W, o);
+    else hipLaunchKernelGGL(k_svmm_rows<SVMM_KCD>, dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->d, X, (const double *)m->W, o);
+    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_multi_predict: the launch failed");
+  }
+  if (Xt) svc_tab_free(ctx, &t); // (waits for the stream)
+  if (best) pmh_free(ctx, best);
+  return rc;
+}
+
+extern "C" int pmh_svm_multi_predict(pmh_svm_multi m, int n, const double *X_dev, double *scores_dev, double *labels_dev) { return svmm_predict(m, n, X_dev, nullptr, scores_dev, labels_dev); }
+
+extern "C" int pmh_svm_multi_predict_csr(pmh_svm_multi m, pmh_csr Xt, double *scores_dev, double *labels_dev)
+{
+  PMH_ARG(m && Xt);
+  return svmm_predict(m, Xt->nrows, nullptr, Xt, scores_dev, labels_dev);
+}
+
+static int svmm_test(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *ytrue, long long *confusion, long long *n_unknown)
+{
+  PMH_ARG(m && ytrue && confusion && n >= 0);
+  pmh_ctx             ctx = m->ctx;
+  const size_t        nc  = (size_t)m->K * m->K + 1;
+  double             *pred = nullptr;
+  unsigned long long *conf = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)(n ? n : 1), (void **)&pred));
+  int rc = pmh_malloc(ctx, sizeof(unsigned long long) * nc, (void **)&conf);
+  if (!rc) rc = pmh_memset(ctx, conf, 0, sizeof(unsigned long long) * nc);
+  if (!rc) rc = svmm_predict(m, n, X, Xt, nullptr, pred);
+  if (!rc && n > 0) {
+    hipLaunchKernelGGL(k_svmm_confusion, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->K, (const double *)m->classes, (const double *)pred, ytrue, conf);
+    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_multi_test: the launch failed");
+  }
+  std::vector<long long> h(nc, 0);
+  if (!rc) rc = pmh_memcpy_d2h(ctx, h.data(), conf, sizeof(long long) * nc);
+  pmh_free(ctx, pred);
+  if (conf) pmh_free(ctx, conf);
+  PMH_CHK(rc);
+  memcpy(confusion, h.data(), sizeof(long long) * (nc - 1));
+  if (n_unknown) *n_unknown = h[nc - 1];
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_test(pmh_svm_multi m, int n, const double *X_dev, const double *labels_true_dev, long long *confusion, long long *n_unknown)
+{
+  return svmm_test(m, n, X_dev, nullptr, labels_true_dev, confusion, n_unknown);
+}
+
+extern "C" int pmh_svm_multi_test_csr(pmh_svm_multi m, pmh_csr Xt, const double *labels_true_dev, long long *confusion, long long *n_unknown)
+{
+  PMH_ARG(m && Xt);
+  return svmm_test(m, Xt->nrows, nullptr, Xt, labels_true_dev, confusion, n_unknown);
+}

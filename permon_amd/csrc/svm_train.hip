@@ -33,8 +33,6 @@ struct pmh_svm_s {
   pmh_svm_stats st;
 };
 
-#define SVM_NB(n) ((int)((((long long)(n) + 63) / 64) < 1 ? 1 : ((((long long)(n) + 63) / 64) > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : (((long long)(n) + 63) / 64))))
-
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_fill_row(int n, const double *__restrict__ y, double c, double *__restrict__ row)
 {
   for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) row[i] = c * y[i];
@@ -299,6 +297,7 @@ static int svm_model(pmh_svm s)
 extern "C" int pmh_svm_train(pmh_svm s)
 {
   PMH_ARG(s);
+  if (!s->sx && !s->mpgp) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_train: the handle has no solver (an earlier pmh_svm_set_labels / pmh_svm_set_penalties failed)");
   const size_t nb = sizeof(double) * (size_t)(s->n ? s->n : 1);
   PMH_CHK(pmh_memset(s->ctx, s->alpha, 0, nb));
   long long p0 = 0, p1 = 0;
@@ -432,6 +431,34 @@ extern "C" int pmh_svm_get_penalties(pmh_svm s, double *c_dev)
   PMH_ARG(s && c_dev);
   if (s->Cv) return pmh_vec_copy(s->ctx, s->n, s->Cv, c_dev);
   return pmh_vec_set(s->ctx, s->n, c_dev, s->o.C);
+}
+
+// New labels on the created handle: everything svm_create derived from y is redone in svm_create's order (the operator's labels, the penalties back to the
+// scalar C, the equality's row and its projector, the solver), so a training afterwards gives what a fresh handle on (X, y_dev) gives, bit for bit
+extern "C" int pmh_svm_set_labels(pmh_svm s, const double *y_dev)
+{
+  PMH_ARG(s && y_dev);
+  pmh_ctx   ctx = s->ctx;
+  const int n   = s->n;
+  s->trained    = 0;
+  // the solvers hold the operator and the projector: they go first
+  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
+  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
+  PMH_CHK(pmh_op_svm_dual_set_labels(s->H, y_dev));
+  s->y = y_dev;
+  if (s->o.loss_type == PMH_SVM_LOSS_L2) {
+    PMH_CHK(pmh_op_svm_dual_set_diag(s->H, nullptr));
+    PMH_CHK(pmh_op_svm_dual_set_terms(s->H, 1.0 / s->o.C, 0.0));
+  } else PMH_CHK(pmh_vec_set(ctx, n, s->ub, s->o.C));
+  if (s->Cv) pmh_free(ctx, s->Cv), s->Cv = nullptr;
+  if (s->Cinv) pmh_free(ctx, s->Cinv), s->Cinv = nullptr;
+  if (s->o.bias) {
+    if (s->pf) pmh_qppf_destroy(s->pf), s->pf = nullptr;
+    if (n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, y_dev, 1.0 / sqrt((double)s->n_global), s->row);
+    PMH_HIP(hipGetLastError());
+    PMH_CHK(pmh_qppf_create_onerow(ctx, s->row, n, &s->pf));
+  }
+  return svm_build_solver(s);
 }
 
 // X (dense rows, n x d) or Xt (CSR)

@@ -267,6 +267,37 @@ def svm_sparse(N, d, nnz_row, skew, offset, C=1.0, seed=7, N_test=0):
     return out
 
 
+def svm_blobs(N, d, K, sep, seed, N_test=0, sparse=None):
+    """K classes for SVMMulticlass, K <= d.  Sample i has the label i mod K (as a float) and x_i = sep e_label + noise, all draws from default_rng(seed).
+    sparse=None: N(0,1) noise in every entry.  sparse=m: N(0,1) noise in m distinct columns per sample, chosen uniformly; sep is then added in the column of the
+    label, which may or may not be one of the m, so a sample stores m or m + 1 entries.  Returns dict(n, d, K, X (ndarray), X_csr (scipy CSR of the same
+    values), labels); N_test > 0: a held-out draw (X_test, X_test_csr, labels_test) from default_rng(seed + 1000)."""
+    import scipy.sparse as sp
+
+    if K > d:
+        raise ValueError("svm_blobs: K = %d classes need d >= K" % K)
+
+    def draw(r, n):
+        lab = (np.arange(n) % K).astype(np.float64)
+        if sparse is None:
+            X = r.standard_normal((n, d))
+        else:
+            X = np.zeros((n, d))
+            cols = np.argsort(r.random((n, d)), axis=1)[:, :sparse]
+            X[np.repeat(np.arange(n), sparse), cols.ravel()] = r.standard_normal(n * sparse)
+        X[np.arange(n), lab.astype(int)] += sep
+        Xs = sp.csr_matrix(X)
+        Xs.sort_indices()
+        return X, Xs, lab
+
+    X, Xs, lab = draw(np.random.default_rng(seed), N)
+    out = dict(n=N, d=d, K=K, X=X, X_csr=Xs, labels=lab)
+    if N_test > 0:
+        Xt, Xts, lt = draw(np.random.default_rng(seed + 1000), N_test)
+        out.update(X_test=Xt, X_test_csr=Xts, labels_test=lt)
+    return out
+
+
 def write_contact_problem(path, f):
     """A CubeFeti contact problem (permon_amd.feti.CubeFeti) in the binary layout examples/contact_tfeti.c reads:
     everything pmh_feti_contact_solve takes -- block-diagonal K, f, B as leaves (equality rows first), c, R, the node boxes."""

@@ -62,6 +62,29 @@ class SVM:
                 wd.free()
         return self
 
+    def set_labels(self, y):
+        """New labels (+-1) on the created handle, X staying on the device (pmh_svm_set_labels): no upload of X, no new column-ordered copy.  y: an array, or a
+        Vec -- also the very Vec handed over before, overwritten in place.  The penalties go back to C (set them again afterwards: labels, then penalties) and
+        the handle is untrained; train() then gives what a fresh fit on (X, y) gives, bit for bit."""
+        self._need()
+        yd = self._dev(y)
+        if yd.n != self.n:
+            if yd is not y:
+                yd.free()
+            raise ValueError("SVM: y must have %d entries" % self.n)
+        try:
+            check(self.L.pmh_svm_set_labels(self.h, yd.p))
+        except Exception:
+            # the handle may borrow either buffer now and has no solver (train raises): it is of no further use, so both buffers go with it
+            self._keep = (self._keep[0], self._keep[1]) + ((yd,) if yd is not y and yd is not self._keep[1] else ())
+            self.destroy()
+            raise
+        Xd, old = self._keep
+        self._keep = (Xd, yd)
+        if old is not yd and old is not y:
+            old.free()
+        return self
+
     def train(self):
         self._need()
         check(self.L.pmh_svm_train(self.h))
@@ -215,10 +238,195 @@ class SVM:
             self._keep = None
 
 
-def load_svmlight(path, n_features=None, zero_based="auto"):
+class SVMMulticlass:
+    """One-vs-rest linear SVM for two or more classes (pmh_svm_multi_*, csrc/svm_multi.hip).  The classes are the distinct labels, ascending; class k is trained
+    against the rest on ONE binary handle over X (uploaded once; in CSR the operator's column-ordered copy is built once), which gives W (K, d) and b (K).
+    Two classes train two classifiers: SVM is there for that case.  balanced: class k is trained with C_pos = C n / (2 n_k), C_neg = C n / (2 (n - n_k)).
+    decision_function / predict score all K classes in one pass over X per chunk of classes (SVMMulticlass.chunk); the label is the class of the greatest score,
+    ties to the lowest class.  X: (n, d) ndarray (d <= 256) or scipy.sparse, as in SVM.  One GPU."""
+
+    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", balanced=False):
+        self.ctx, self.L = ctx, ctx.L
+        o = _lib.SvmOpts()
+        check(self.L.pmh_svm_default_opts(o))
+        left = ct.create_string_buffer(4096)
+        check(self.L.pmh_svm_set_from_options(("-svm_loss_type %s -svm_C %r -svm_bias %d %s" % (loss, float(C), int(bool(bias)), options)).encode(), o, left, len(left)))
+        self.opts = o
+        self.options_left = [k for k in left.value.decode().split() if k]
+        self.balanced = bool(balanced)
+        self.h = None
+        self._keep = None
+
+    loss = property(lambda self: "L2" if self.opts.loss_type == 1 else "L1")
+    C = property(lambda self: self.opts.C)
+    bias = property(lambda self: bool(self.opts.bias))
+
+    @staticmethod
+    def chunk(path):
+        """Classes scored per pass over the test samples (pmh_svm_multi_chunk) on the kernel path "dense64" (d = 64), "dense" (any other d) or "csr"."""
+        kc = ct.c_int()
+        check(_lib.load().pmh_svm_multi_chunk(("dense64", "dense", "csr").index(path), ct.byref(kc)))
+        return kc.value
+
+    def _dev(self, a):
+        return a if isinstance(a, Vec) else Vec.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.float64).ravel())
+
+    def create(self, X, labels):
+        """Set the training samples and find the classes, without training (then fit's train, or set_model)."""
+        self.destroy()
+        h = ct.c_void_p()
+        if is_sparse(X):
+            self.n, self.d = X.shape
+            Xd, ld = csr_from_scipy(self.ctx, X), self._dev(labels)
+            try:
+                check(self.L.pmh_svm_multi_create_csr(self.ctx.h, Xd.h, ld.p, self.opts, int(self.balanced), ct.byref(h)))
+            except Exception:
+                Xd.destroy(), ld.free()
+                raise
+        else:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+            self.n, self.d = X.shape
+            Xd, ld = self._dev(X), self._dev(labels)
+            try:
+                check(self.L.pmh_svm_multi_create(self.ctx.h, self.n, self.d, Xd.p, ld.p, self.opts, int(self.balanced), ct.byref(h)))
+            except Exception:
+                Xd.free(), ld.free()
+                raise
+        self.h, self._keep = h, (Xd, ld)
+        k = ct.c_int()
+        check(self.L.pmh_svm_multi_get_classes(self.h, ct.byref(k), None))
+        self.K = k.value
+        return self
+
+    def train(self):
+        self._need()
+        check(self.L.pmh_svm_multi_train(self.h))
+        return self
+
+    def fit(self, X, labels):
+        return self.create(X, labels).train()
+
+    def _need(self):
+        if self.h is None:
+            raise RuntimeError("SVMMulticlass: call fit first")
+
+    @property
+    def classes_(self):
+        self._need()
+        c = np.empty(self.K)
+        check(self.L.pmh_svm_multi_get_classes(self.h, None, c.ctypes.data_as(ct.c_void_p)))
+        return c
+
+    @property
+    def W(self):
+        self._need()
+        W = np.empty((self.K, self.d))
+        check(self.L.pmh_svm_multi_get_model(self.h, W.ctypes.data_as(ct.c_void_p), None))
+        return W
+
+    @property
+    def b(self):
+        self._need()
+        b = np.empty(self.K)
+        check(self.L.pmh_svm_multi_get_model(self.h, None, b.ctypes.data_as(ct.c_void_p)))
+        return b
+
+    @property
+    def stats(self):
+        """The statistics of the K trainings, class by class (a list of pmh_svm_stats)."""
+        self._need()
+        out = []
+        for k in range(self.K):
+            st = _lib.SvmStats()
+            check(self.L.pmh_svm_multi_get_stats(self.h, k, ct.byref(st), None, None))
+            out.append(st)
+        return out
+
+    def class_penalties(self, k):
+        """(C_pos, C_neg) class k is trained with."""
+        self._need()
+        cp, cn = ct.c_double(), ct.c_double()
+        check(self.L.pmh_svm_multi_get_stats(self.h, int(k), None, ct.byref(cp), ct.byref(cn)))
+        return cp.value, cn.value
+
+    def set_model(self, W, b):
+        """A saved model in place of training: W (K, d), b (K)."""
+        self._need()
+        W, b = np.ascontiguousarray(W, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64).ravel()
+        if W.shape != (self.K, self.d) or b.shape != (self.K,):
+            raise ValueError("SVMMulticlass: W must be (%d, %d) and b (%d,)" % (self.K, self.d, self.K))
+        check(self.L.pmh_svm_multi_set_model(self.h, W.ctypes.data_as(ct.c_void_p), b.ctypes.data_as(ct.c_void_p)))
+        return self
+
+    def _run(self, X, want_scores, want_labels, labels_true=None):
+        """predict (scores and / or labels) or, with labels_true, test: (scores, labels) or (confusion, n_unknown)."""
+        self._need()
+        sparse = is_sparse(X)
+        if not sparse:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+            if X.ndim != 2:
+                raise ValueError("SVMMulticlass: X must be (n, d)")
+        n = X.shape[0]
+        Xd = csr_from_scipy(self.ctx, X) if sparse else self._dev(X)
+        s = Vec(self.ctx, n * self.K, zero=False) if want_scores else None
+        l = Vec(self.ctx, n, zero=False) if want_labels else None
+        t = self._dev(labels_true) if labels_true is not None else None
+        try:
+            if t is not None:
+                if t.n != n:
+                    raise ValueError("SVMMulticlass: labels must have %d entries" % n)
+                conf, unk = np.zeros((self.K, self.K), dtype=np.int64), ct.c_longlong()
+                if sparse:
+                    check(self.L.pmh_svm_multi_test_csr(self.h, Xd.h, t.p, conf.ctypes.data_as(ct.c_void_p), ct.byref(unk)))
+                else:
+                    if X.shape[1] != self.d:
+                        raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
+                    check(self.L.pmh_svm_multi_test(self.h, n, Xd.p, t.p, conf.ctypes.data_as(ct.c_void_p), ct.byref(unk)))
+                return conf, int(unk.value)
+            if sparse:
+                check(self.L.pmh_svm_multi_predict_csr(self.h, Xd.h, s.p if s else None, l.p if l else None))
+            else:
+                if X.shape[1] != self.d:
+                    raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
+                check(self.L.pmh_svm_multi_predict(self.h, n, Xd.p, s.p if s else None, l.p if l else None))
+            return (s.to_numpy().reshape(n, self.K) if s else None, l.to_numpy() if l else None)
+        finally:
+            Xd.destroy() if sparse else Xd.free()
+            for v in (s, l, t):
+                if v is not None and v is not labels_true:
+                    v.free()
+
+    def decision_function(self, X):
+        """(n, K): x_i . W_k + b_k."""
+        return self._run(X, True, False)[0]
+
+    def predict(self, X):
+        return self._run(X, False, True)[1]
+
+    def predict_both(self, X):
+        """(scores (n, K), labels (n,)) from one call."""
+        return self._run(X, True, True)
+
+    def test(self, X, labels):
+        """dict(accuracy, confusion, n_unknown): confusion[t, p] counts the samples of true class t predicted as class p; a true label that is no class is
+        counted in n_unknown; accuracy = trace / n."""
+        conf, unk = self._run(X, False, False, labels_true=labels)
+        n = X.shape[0]
+        return dict(accuracy=float(np.trace(conf)) / n if n else float("nan"), confusion=conf, n_unknown=unk)
+
+    def destroy(self):
+        if self.h is not None:
+            self.L.pmh_svm_multi_destroy(self.h)
+            self.h = None
+            for v in self._keep or ():
+                v.destroy() if hasattr(v, "destroy") else v.free()
+            self._keep = None
+
+
+def load_svmlight(path, n_features=None, zero_based="auto", multiclass=False):
     """Read a file in the svmlight / libsvm text format, `label idx:val idx:val ...` per sample, into (X, y): X a scipy.sparse CSR matrix (fp64, int32, sorted
     indices, duplicates summed), y in {-1, +1}.  Text after `#` is a comment; `qid:` tokens are ignored; a sample may have no feature.  The labels must take
-    exactly two distinct values: the smaller becomes -1, the larger +1.  zero_based: True / False, or "auto" (one-based unless an index 0 occurs).
+    exactly two distinct values: the smaller becomes -1, the larger +1; multiclass=True: y is the labels as read, two or more distinct values (SVMMulticlass).  zero_based: True / False, or "auto" (one-based unless an index 0 occurs).
     n_features: the width of X (default: the largest index + 1 after the shift); an index beyond it is an error."""
     import scipy.sparse as sp
 
@@ -255,9 +463,14 @@ def load_svmlight(path, n_features=None, zero_based="auto"):
         d = int(n_features)
     lab = np.asarray(labels, dtype=np.float64)
     u = np.unique(lab)
-    if u.size != 2:
-        raise ValueError("%s: %d distinct labels, a binary classifier needs exactly two" % (path, u.size))
-    y = np.where(lab == u[1], 1.0, -1.0)
+    if multiclass:
+        if u.size < 2:
+            raise ValueError("%s: %d distinct labels, a classifier needs at least two" % (path, u.size))
+        y = lab
+    else:
+        if u.size != 2:
+            raise ValueError("%s: %d distinct labels, a binary classifier needs exactly two" % (path, u.size))
+        y = np.where(lab == u[1], 1.0, -1.0)
     X = sp.csr_matrix((np.asarray(val, dtype=np.float64), idx.astype(np.int32), np.asarray(indptr, dtype=np.int32)), shape=(lab.size, d))
     X.sum_duplicates()
     X.sort_indices()
