@@ -649,6 +649,45 @@ int pmh_svm_multi_test(pmh_svm_multi svm, int n, const double *X_dev, const doub
 int pmh_svm_multi_test_csr(pmh_svm_multi svm, pmh_csr Xt, const double *labels_true_dev, long long *confusion, long long *n_unknown);
 int pmh_svm_multi_destroy(pmh_svm_multi svm);
 
+/* ---- SVM probabilities: Platt scaling (svm_proba.hip) --------------------------------------------------------------------------------------------------------
+ * P(y = +1 | x) = 1 / (1 + exp(A s(x) + B)), s the score x . w + b.  A, B minimise the regularised negative log-likelihood
+ *   F(A, B) = - sum_i (t_i log p_i + (1 - t_i) log(1 - p_i)),  t_i = (n_pos + 1) / (n_pos + 2) for y_i = +1, 1 / (n_neg + 2) for y_i = -1,
+ * by Newton's method with backtracking: the algorithm of H.-T. Lin, C.-J. Lin, R. C. Weng, "A note on Platt's probabilistic outputs for support vector
+ * machines", Machine Learning 68 (2007), with its constants (LIBSVM's sigmoid_train).  Every evaluated point (A, B) is ONE launch over the n scores that
+ * gives F, the gradient and the Hessian (six sums, fixed order, no float atomics: two fits give the same bits); six doubles cross to the host per point.
+ * Under a communicator the scores are sharded as the samples are and the sums and class counts are all-reduced.
+ * pmh_svm_platt_fit: n < 1 (over all ranks) or a label that is not +-1: PMH_ERR_ARG (the message says how many).  One class only: the start point A = 0,
+ * B = log((n_neg + 1) / (n_pos + 1)) is stationary and is returned.  Separable scores: A runs off until the iteration limit or the line search ends the fit;
+ * the last accepted (finite) point is returned, reason says which.  The caller supplies the calibration samples (held-out ones, or the training set). */
+enum { PMH_PLATT_CONVERGED = 1, PMH_PLATT_MAX_IT = 2, PMH_PLATT_LINE_SEARCH = 3 };
+typedef struct {
+  int       reason;                  /* PMH_PLATT_CONVERGED | _MAX_IT | _LINE_SEARCH (0: the calibration was set, not fitted) */
+  int       iterations, evaluations; /* Newton steps taken; launches of the sums kernel */
+  long long n_pos, n_neg;
+  double    fval, g1, g2;            /* F and its gradient at the returned point */
+} pmh_svm_platt_stats;
+int pmh_svm_platt_fit(pmh_ctx ctx, int n, const double *scores_dev, const double *y_dev, double *A, double *B, pmh_svm_platt_stats *st /* or NULL */);
+/* The binary handle: calibrate scores the samples as pmh_svm_predict(_csr) does and fits A, B on those scores (the result is pmh_svm_platt_fit of
+ * pmh_svm_predict's scores, bit for bit); set_calibration takes a saved pair.  A calibration belongs to a model: pmh_svm_train, pmh_svm_set_labels and
+ * pmh_svm_set_penalties clear it.  predict_proba: proba_dev[i] = 1 / (1 + exp(A (x_i . w + b) + B)) in ONE pass over the samples, the dot product summed as
+ * pmh_svm_predict sums it.  Untrained handle (calibrate), no calibration (predict_proba, get_calibration): PMH_ERR_STATE */
+int pmh_svm_calibrate(pmh_svm svm, int n, const double *X_dev, const double *y_dev);
+int pmh_svm_calibrate_csr(pmh_svm svm, pmh_csr Xt, const double *y_dev);
+int pmh_svm_set_calibration(pmh_svm svm, double A, double B);
+int pmh_svm_get_calibration(pmh_svm svm, double *A, double *B, pmh_svm_platt_stats *st /* or NULL */);
+int pmh_svm_predict_proba(pmh_svm svm, int n, const double *X_dev, double *proba_dev);
+int pmh_svm_predict_proba_csr(pmh_svm svm, pmh_csr Xt, double *proba_dev);
+/* One-vs-rest: one scoring call (pmh_svm_multi_predict's), then K fits, fit k on column k of the scores with "label == c_k" as +1 and every other label (a
+ * value that is no class included) as -1.  predict_proba (n x K): sigma_ik = 1 / (1 + exp(A_k S[i,k] + B_k)) written by the scoring sweeps, then every row
+ * divided by its sum (k ascending); a row sum of 0 gives 1 / K everywhere.  pmh_svm_multi_train and pmh_svm_multi_set_model clear the calibration;
+ * pmh_svm_multi_predict stays the arg-max of the raw scores */
+int pmh_svm_multi_calibrate(pmh_svm_multi svm, int n, const double *X_dev, const double *labels_dev);
+int pmh_svm_multi_calibrate_csr(pmh_svm_multi svm, pmh_csr Xt, const double *labels_dev);
+int pmh_svm_multi_set_calibration(pmh_svm_multi svm, const double *A_host /* K */, const double *B_host /* K */);
+int pmh_svm_multi_get_calibration(pmh_svm_multi svm, double *A_host /* K, or NULL */, double *B_host /* K, or NULL */, pmh_svm_platt_stats *st_host /* K, or NULL */);
+int pmh_svm_multi_predict_proba(pmh_svm_multi svm, int n, const double *X_dev, double *proba_dev);
+int pmh_svm_multi_predict_proba_csr(pmh_svm_multi svm, pmh_csr Xt, double *proba_dev);
+
 
 /* ---- PC for the inner KSP of MATINV: multigrid V-cycle (PCMG semantics) ----------------------------------------
  * The reference's iterative MATINV applies K^+ with a PETSc KSP whose PC is chosen by -mat_inv_pc_type

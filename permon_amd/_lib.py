@@ -83,6 +83,11 @@ class SvmStats(C.Structure):  # pmh_svm_stats
                 ("rho", C.c_double), ("normBu", C.c_double), ("rnorm", C.c_double)]
 
 
+class SvmPlattStats(C.Structure):  # pmh_svm_platt_stats
+    _fields_ = [("reason", C.c_int), ("iterations", C.c_int), ("evaluations", C.c_int), ("n_pos", C.c_longlong), ("n_neg", C.c_longlong),
+                ("fval", C.c_double), ("g1", C.c_double), ("g2", C.c_double)]
+
+
 class KspFetiOpts(C.Structure):
     _fields_ = [("gluing_type", C.c_int), ("scale", C.c_int), ("exclude_dirichlet", C.c_int), ("regularize", C.c_int), ("kplus_left", C.c_int), ("project", C.c_int),
                 ("E_orth_type", C.c_int), ("lumped_pc", C.c_int), ("regularize_rho", C.c_double),
@@ -284,6 +289,19 @@ _PROTOS = {
     "pmh_svm_multi_test": [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_longlong)],
     "pmh_svm_multi_test_csr": [vp, vp, vp, vp, C.POINTER(C.c_longlong)],
     "pmh_svm_multi_destroy": [vp],
+    "pmh_svm_platt_fit": [vp, C.c_int, vp, vp, c_double_p, c_double_p, C.POINTER(SvmPlattStats)],
+    "pmh_svm_calibrate": [vp, C.c_int, vp, vp],
+    "pmh_svm_calibrate_csr": [vp, vp, vp],
+    "pmh_svm_set_calibration": [vp, C.c_double, C.c_double],
+    "pmh_svm_get_calibration": [vp, c_double_p, c_double_p, C.POINTER(SvmPlattStats)],
+    "pmh_svm_predict_proba": [vp, C.c_int, vp, vp],
+    "pmh_svm_predict_proba_csr": [vp, vp, vp],
+    "pmh_svm_multi_calibrate": [vp, C.c_int, vp, vp],
+    "pmh_svm_multi_calibrate_csr": [vp, vp, vp],
+    "pmh_svm_multi_set_calibration": [vp, vp, vp],
+    "pmh_svm_multi_get_calibration": [vp, vp, vp, vp],
+    "pmh_svm_multi_predict_proba": [vp, C.c_int, vp, vp],
+    "pmh_svm_multi_predict_proba_csr": [vp, vp, vp],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],
     "pmh_smalxe_destroy": [vp],

@@ -23,6 +23,10 @@
 // Algorithmic bytes of one call: dense 8 n d ceil(K / KC) + 8 n K (scores) + 8 n (labels), against K (8 n d + 8 n) for K binary calls; CSR 12 nnz ceil(K / KC)
 // + 4 n + 8 n K + 8 n, the gathers of Wt (8 KC bytes per entry) served by the caches where 8 KC d bytes fit.
 //
+// Probabilities (pmh_svm_multi_predict_proba): the same sweeps instantiated on svmm_out_proba write sigma_ik = 1 / (1 + exp(A_k S[i,k] + B_k)) where they write
+// S[i,k] -- S[i,k] the very sum the scoring instance forms -- and k_svmm_normalise divides every row by its sum, k ascending: 16 n K bytes more.  The scoring
+// instances (svmm_out) are what they were: the probability is a separate instance, not a branch.
+//
 // One-vs-rest training: the K binary problems "class k against the rest" are trained one after the other on ONE pmh_svm handle over X -- X is uploaded once and
 // the CSR operator's column-ordered copy is built once; pmh_svm_set_labels re-labels the handle between the classes -- and give W (K x d) and b (K).
 #include <algorithm>
@@ -52,7 +56,20 @@ struct svmm_out {
   const double *b, *classes; // K each
   double       *scores, *labels; // n x K / n, either may be nullptr
   double       *best;            // n: the greatest score of the chunks so far (K > SVMM_KC and labels asked for), else nullptr
+  static constexpr bool PROBA = false;
 };
+// probabilities in place of the scores: scores[i K + k] = svm_sigmoid(A[k] S[i,k] + B[k]); no labels
+struct svmm_out_proba : svmm_out {
+  const double *A, *B; // K each: the classes' Platt pairs
+  static constexpr bool PROBA = true;
+};
+// what a lane that ends with the sum of class c needs beside b_c
+template <class OUT> static __device__ __forceinline__ void svmm_lane_cal(const OUT &o, int c, double &ca, double &cb)
+{
+  ca = cb = 0.0;
+  if constexpr (OUT::PROBA)
+    if (c < o.kc) ca = o.A[o.k0 + c], cb = o.B[o.k0 + c];
+}
 
 // row i's greatest score of this chunk, bv of class index bk: the label, unless an earlier chunk holds a score at least as great
 static __device__ __forceinline__ void svmm_label(const svmm_out &o, long long i, double bv, int bk)
@@ -63,8 +80,14 @@ static __device__ __forceinline__ void svmm_label(const svmm_out &o, long long i
 }
 
 // all KC sums of row i in one lane (the CSR kernels): + b_k, scores, the chunk's first maximum
-template <int KC> static __device__ __forceinline__ void svmm_row_done(const svmm_out &o, long long i, const double (&s)[KC])
+template <int KC, class OUT> static __device__ __forceinline__ void svmm_row_done(const OUT &o, long long i, const double (&s)[KC])
 {
+  if constexpr (OUT::PROBA) {
+#pragma unroll
+    for (int j = 0; j < KC; j++)
+      if (j < o.kc) o.scores[(size_t)i * o.K + o.k0 + j] = svm_sigmoid(o.A[o.k0 + j] * (s[j] + o.b[o.k0 + j]) + o.B[o.k0 + j]);
+    return;
+  }
   double bv = -INFINITY;
   int    bk = o.k0;
 #pragma unroll
@@ -98,12 +121,16 @@ template <int KC, int LW> static __device__ __forceinline__ double svmm_halve(do
 }
 
 // the LW lanes of row i after svmm_halve: lane l holds t = the sum of the chunk's class l / (LW / KC).  Every lane of the wavefront calls this (shuffles);
-// live: the row exists
-template <int KC, int LW> static __device__ __forceinline__ void svmm_lanes_done(const svmm_out &o, long long i, bool live, int l, double t, double bc)
+// live: the row exists.  ca, cb: the Platt pair of the lane's class (svmm_lane_cal; the probability instances)
+template <int KC, int LW, class OUT> static __device__ __forceinline__ void svmm_lanes_done(const OUT &o, long long i, bool live, int l, double t, double bc, double ca, double cb)
 {
   constexpr int LPC = LW / KC; // lanes per class
   const int     c   = l / LPC;
   t += bc;
+  if constexpr (OUT::PROBA) {
+    if (live && (l % LPC) == 0 && c < o.kc) o.scores[(size_t)i * o.K + o.k0 + c] = svm_sigmoid(ca * t + cb);
+    return;
+  }
   if (o.labels) { // (uniform: a kernel argument)
     double bv = c < o.kc ? t : -INFINITY;
     int    bk = o.k0 + c;
@@ -119,7 +146,7 @@ template <int KC, int LW> static __device__ __forceinline__ void svmm_lanes_done
 }
 
 // d == 64: W is the model (K x 64, row-major)
-template <int KC, int UNR> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows64(int n, const double *__restrict__ X, const double *__restrict__ W, svmm_out o)
+template <int KC, int UNR, class OUT> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows64(int n, const double *__restrict__ X, const double *__restrict__ W, OUT o)
 {
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
@@ -128,6 +155,8 @@ template <int KC, int UNR> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_r
   for (int c = 0; c < KC; c++) wr[c] = c < o.kc ? ((const dbl2 *)(W + (size_t)(o.k0 + c) * 64))[l2] : dbl2{0.0, 0.0};
   const int    myc = l2 / (32 / KC);
   const double bc  = myc < o.kc ? o.b[o.k0 + myc] : 0.0;
+  double       ca, cb;
+  svmm_lane_cal(o, myc, ca, cb);
   for (long long r0 = gw * 2 * UNR; r0 < n; r0 += nw * 2 * UNR) {
     dbl2 v[UNR];
     svm_load_rows64<UNR>(n, X, r0, v);
@@ -138,13 +167,13 @@ template <int KC, int UNR> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_r
 #pragma unroll
       for (int c = 0; c < KC; c++) s[c] = v[u].x * wr[c].x + v[u].y * wr[c].y;
       const double t = svmm_halve<KC, 32>(s, l2);
-      svmm_lanes_done<KC, 32>(o, i, i < n, l2, t, bc);
+      svmm_lanes_done<KC, 32>(o, i, i < n, l2, t, bc, ca, cb);
     }
   }
 }
 
 // any d <= 64 SVM_KMAX: W is the model (K x d, row-major)
-template <int KC> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ W, svmm_out o)
+template <int KC, class OUT> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ W, OUT o)
 {
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
@@ -155,6 +184,8 @@ template <int KC> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows(int n
     for (int k = 0; k < SVM_KMAX; k++) wr[c][k] = (c < o.kc && lane + 64 * k < d) ? W[(size_t)(o.k0 + c) * d + lane + 64 * k] : 0.0;
   const int    myc = lane / (64 / KC);
   const double bc  = myc < o.kc ? o.b[o.k0 + myc] : 0.0;
+  double       ca, cb;
+  svmm_lane_cal(o, myc, ca, cb);
   for (long long i = gw; i < n; i += nw) {
     const double *xr = X + (size_t)i * d;
     double        x[SVM_KMAX], s[KC];
@@ -168,14 +199,14 @@ template <int KC> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows(int n
       s[c] = a;
     }
     const double t = svmm_halve<KC, 64>(s, lane);
-    svmm_lanes_done<KC, 64>(o, i, true, lane, t, bc);
+    svmm_lanes_done<KC, 64>(o, i, true, lane, t, bc, ca, cb);
   }
 }
 
 // CSR: span b's pieces of the samples' KC sums (k_svc_seg with KC columns; Wt: d x KC, class index fastest; head / tail: KC doubles per span)
-template <int KC>
+template <int KC, class OUT>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_seg(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ Wt,
-                                                        const int *__restrict__ first, double *__restrict__ head, double *__restrict__ tail, svmm_out o)
+                                                        const int *__restrict__ first, double *__restrict__ head, double *__restrict__ tail, OUT o)
 {
   __shared__ dbl2 sval2[SVC_SPAN / 2];
   typedef int     int2v __attribute__((ext_vector_type(2)));
@@ -232,9 +263,9 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_seg(int nent, int nseg, int 
 }
 
 // one wavefront per span (k_svc_fin with KC columns): the sample that began in an earlier span and ends in this one
-template <int KC>
+template <int KC, class OUT>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_fin(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ first, const double *__restrict__ head,
-                                                        const double *__restrict__ tail, svmm_out o)
+                                                        const double *__restrict__ tail, OUT o)
 {
   const int lane = threadIdx.x & 63, b = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
   if (b >= nb) return;
@@ -253,6 +284,17 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_fin(int nent, int nseg, int 
 #pragma unroll
   for (int j = 0; j < KC; j++) s[j] = pmh_wave_sum(s[j]);
   if (lane == 0) svmm_row_done<KC>(o, c, s);
+}
+
+// proba[i][k] /= sum_k proba[i][k], the sum taken k ascending; a row whose sum is 0 (every sigma underflowed) becomes 1 / K everywhere.  One row per thread
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_normalise(int n, int K, double *__restrict__ proba)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    double *p = proba + (size_t)i * K;
+    double  s = 0.0;
+    for (int k = 0; k < K; k++) s += p[k];
+    for (int k = 0; k < K; k++) p[k] = s == 0.0 ? 1.0 / K : p[k] / s;
+  }
 }
 
 // Wt[ch][col][j] = W[ch KC + j][col] (0 past the last class): the model as the CSR sweep gathers it
@@ -307,6 +349,11 @@ struct pmh_svm_multi_s {
   std::vector<long long>     count; // samples per class
   std::vector<pmh_svm_stats> st;    // per class, of the last pmh_svm_multi_train
   int           trained = 0, have_stats = 0;
+  // the probability model of the current (W, b): the classes' Platt pairs (svm_proba.hip); a new model clears it
+  int                              calibrated = 0;
+  double                          *cal = nullptr; // device: A (K) then B (K)
+  std::vector<double>              h_A, h_B;
+  std::vector<pmh_svm_platt_stats> cal_st;
 };
 
 extern "C" int pmh_svm_multi_chunk(int path, int *KC)
@@ -320,7 +367,7 @@ extern "C" int pmh_svm_multi_destroy(pmh_svm_multi m)
 {
   if (!m) return PMH_SUCCESS;
   if (m->bin) pmh_svm_destroy(m->bin);
-  double *v[] = {m->y, m->W, m->Wt, m->b, m->classes};
+  double *v[] = {m->y, m->W, m->Wt, m->b, m->classes, m->cal};
   for (double *p : v)
     if (p) pmh_free(m->ctx, p);
   delete m;
@@ -353,11 +400,12 @@ static int svmm_create(pmh_ctx ctx, int n, int d, const double *X_dev, pmh_csr X
   for (int i = 0; i < n; i++) m->count[(size_t)(std::lower_bound(cls.begin(), cls.end(), lab[(size_t)i]) - cls.begin())]++;
   m->h_W.assign((size_t)m->K * d, 0.0), m->h_b.assign((size_t)m->K, 0.0);
   m->st.resize((size_t)m->K);
+  m->h_A.assign((size_t)m->K, 0.0), m->h_B.assign((size_t)m->K, 0.0), m->cal_st.resize((size_t)m->K);
   int rc = PMH_SUCCESS;
   do {
     if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&m->y)) || (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->K * d, (void **)&m->W)) ||
         (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->nchc * d * SVMM_KCC, (void **)&m->Wt)) || (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->K, (void **)&m->b)) ||
-        (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->K, (void **)&m->classes)))
+        (rc = pmh_malloc(ctx, sizeof(double) * (size_t)m->K, (void **)&m->classes)) || (rc = pmh_malloc(ctx, sizeof(double) * 2 * (size_t)m->K, (void **)&m->cal)))
       break;
     if ((rc = pmh_memcpy_h2d(ctx, m->classes, cls.data(), sizeof(double) * cls.size()))) break;
     if ((rc = svmm_relabel(m, 0))) break; // the binary handle is created on the labels of class 0
@@ -406,7 +454,7 @@ static int svmm_upload_model(pmh_svm_multi m)
 extern "C" int pmh_svm_multi_train(pmh_svm_multi m)
 {
   PMH_ARG(m);
-  m->trained = m->have_stats = 0;
+  m->trained = m->have_stats = m->calibrated = 0;
   for (int k = 0; k < m->K; k++) {
     if (k != m->cur) { // (a fresh handle is labelled for class 0 already)
       m->cur = -1;
@@ -448,7 +496,7 @@ extern "C" int pmh_svm_multi_get_model(pmh_svm_multi m, double *W_host, double *
 extern "C" int pmh_svm_multi_set_model(pmh_svm_multi m, const double *W_host, const double *b_host)
 {
   PMH_ARG(m && W_host && b_host);
-  m->trained = m->have_stats = 0;
+  m->trained = m->have_stats = m->calibrated = 0;
   memcpy(m->h_W.data(), W_host, sizeof(double) * m->h_W.size());
   memcpy(m->h_b.data(), b_host, sizeof(double) * m->h_b.size());
   PMH_CHK(svmm_upload_model(m));
@@ -470,8 +518,22 @@ extern "C" int pmh_svm_multi_get_stats(pmh_svm_multi m, int k, pmh_svm_stats *st
   return PMH_SUCCESS;
 }
 
-// X (dense rows, n x d) or Xt (CSR): one sweep per chunk of classes, chunks ascending
-static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *scores, double *labels)
+// the launches of one chunk of classes on the instances of OUT
+template <class OUT> static void svmm_launch_chunk(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const svc_tab &t, int ch, const OUT &o)
+{
+  pmh_ctx ctx = m->ctx;
+  if (Xt) {
+    const int nb = t.nb;
+    hipLaunchKernelGGL((k_svmm_seg<SVMM_KCC, OUT>), dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, (int)Xt->nnz, n, nb, (const int *)Xt->d_rowptr, (const int *)Xt->d_col, (const double *)Xt->d_val,
+                       (const double *)(m->Wt + (size_t)ch * m->d * SVMM_KCC), (const int *)t.first, t.head, t.tail, o);
+    hipLaunchKernelGGL((k_svmm_fin<SVMM_KCC, OUT>), dim3((nb + PMH_BLOCK / 64 - 1) / (PMH_BLOCK / 64)), dim3(PMH_BLOCK), 0, ctx->stream, (int)Xt->nnz, n, nb, (const int *)Xt->d_rowptr, (const int *)t.first,
+                       (const double *)t.head, (const double *)t.tail, o);
+  } else if (m->d == 64) hipLaunchKernelGGL((k_svmm_rows64<SVMM_KC64, 4, OUT>), dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, X, (const double *)m->W, o);
+  else hipLaunchKernelGGL((k_svmm_rows<SVMM_KCD, OUT>), dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->d, X, (const double *)m->W, o);
+}
+
+// X (dense rows, n x d) or Xt (CSR): one sweep per chunk of classes, chunks ascending.  proba: scores receives the classes' sigmoids (m->cal), labels is nullptr
+static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *scores, double *labels, bool proba = false)
 {
   PMH_ARG(m && n >= 0 && (X || Xt || n == 0));
   if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_predict: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
@@ -488,14 +550,12 @@ static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, dou
   int     rc = Xt ? svc_tab_build(ctx, n, Xt->d_rowptr, Xt->nnz, &t, SVMM_KCC) : PMH_SUCCESS;
   for (int ch = 0; ch < nch && !rc; ch++) {
     svmm_out o{m->K, ch * kcp, std::min(kcp, m->K - ch * kcp), m->b, m->classes, scores, labels, best};
-    if (Xt) {
-      const int nb = t.nb;
-      hipLaunchKernelGGL(k_svmm_seg<SVMM_KCC>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, (int)Xt->nnz, n, nb, (const int *)Xt->d_rowptr, (const int *)Xt->d_col, (const double *)Xt->d_val,
-                         (const double *)(m->Wt + (size_t)ch * m->d * SVMM_KCC), (const int *)t.first, t.head, t.tail, o);
-      hipLaunchKernelGGL(k_svmm_fin<SVMM_KCC>, dim3((nb + PMH_BLOCK / 64 - 1) / (PMH_BLOCK / 64)), dim3(PMH_BLOCK), 0, ctx->stream, (int)Xt->nnz, n, nb, (const int *)Xt->d_rowptr, (const int *)t.first,
-                         (const double *)t.head, (const double *)t.tail, o);
-    } else if (m->d == 64) hipLaunchKernelGGL((k_svmm_rows64<SVMM_KC64, 4>), dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, X, (const double *)m->W, o);
-    else hipLaunchKernelGGL(k_svmm_rows<SVMM_KCD>, dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->d, X, (const double *)m->W, o);
+    if (proba) {
+      svmm_out_proba op;
+      static_cast<svmm_out &>(op) = o;
+      op.A = m->cal, op.B = m->cal + m->K;
+      svmm_launch_chunk(m, n, X, Xt, t, ch, op);
+    } else svmm_launch_chunk(m, n, X, Xt, t, ch, o);
     if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_multi_predict: the launch failed");
   }
   if (Xt) svc_tab_free(ctx, &t); // (waits for the stream)
@@ -545,4 +605,82 @@ extern "C" int pmh_svm_multi_test_csr(pmh_svm_multi m, pmh_csr Xt, const double 
 {
   PMH_ARG(m && Xt);
   return svmm_test(m, Xt->nrows, nullptr, Xt, labels_true_dev, confusion, n_unknown);
+}
+
+// ---- probabilities (Platt scaling, svm_proba.hip) ---------------------------------------------------------------------------------------------------------------
+static int svmm_upload_cal(pmh_svm_multi m)
+{
+  PMH_CHK(pmh_memcpy_h2d(m->ctx, m->cal, m->h_A.data(), sizeof(double) * (size_t)m->K));
+  return pmh_memcpy_h2d(m->ctx, m->cal + m->K, m->h_B.data(), sizeof(double) * (size_t)m->K);
+}
+
+// one scoring call for all K classes, then fit k on column k of the scores in place, "label == class k" against the rest
+static int svmm_calibrate(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *labels)
+{
+  PMH_ARG(m && n >= 0 && (labels || n == 0));
+  if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_calibrate: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
+  m->calibrated  = 0;
+  double *scores = nullptr;
+  PMH_CHK(pmh_malloc(m->ctx, sizeof(double) * (size_t)(n ? n : 1) * m->K, (void **)&scores));
+  int rc = svmm_predict(m, n, X, Xt, scores, nullptr);
+  for (int k = 0; k < m->K && !rc; k++)
+    rc = pmh_svm_platt_fit_strided(m->ctx, n, scores + k, m->K, labels, m->h_classes[(size_t)k], 0, &m->h_A[(size_t)k], &m->h_B[(size_t)k], &m->cal_st[(size_t)k]);
+  pmh_free(m->ctx, scores);
+  PMH_CHK(rc);
+  PMH_CHK(svmm_upload_cal(m));
+  m->calibrated = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_calibrate(pmh_svm_multi m, int n, const double *X_dev, const double *labels_dev) { return svmm_calibrate(m, n, X_dev, nullptr, labels_dev); }
+
+extern "C" int pmh_svm_multi_calibrate_csr(pmh_svm_multi m, pmh_csr Xt, const double *labels_dev)
+{
+  PMH_ARG(m && Xt);
+  return svmm_calibrate(m, Xt->nrows, nullptr, Xt, labels_dev);
+}
+
+extern "C" int pmh_svm_multi_set_calibration(pmh_svm_multi m, const double *A_host, const double *B_host)
+{
+  PMH_ARG(m && A_host && B_host);
+  if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_set_calibration: call pmh_svm_multi_train or pmh_svm_multi_set_model first (a calibration belongs to a model)");
+  for (int k = 0; k < m->K; k++)
+    if (!std::isfinite(A_host[k]) || !std::isfinite(B_host[k])) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_set_calibration: class %d: A = %g, B = %g, both must be finite", k, A_host[k], B_host[k]);
+  m->calibrated = 0;
+  memcpy(m->h_A.data(), A_host, sizeof(double) * (size_t)m->K);
+  memcpy(m->h_B.data(), B_host, sizeof(double) * (size_t)m->K);
+  memset(m->cal_st.data(), 0, sizeof(pmh_svm_platt_stats) * (size_t)m->K);
+  PMH_CHK(svmm_upload_cal(m));
+  m->calibrated = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_get_calibration(pmh_svm_multi m, double *A_host, double *B_host, pmh_svm_platt_stats *st_host)
+{
+  PMH_ARG(m);
+  if (!m->calibrated) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_get_calibration: call pmh_svm_multi_calibrate or pmh_svm_multi_set_calibration first");
+  if (A_host) memcpy(A_host, m->h_A.data(), sizeof(double) * (size_t)m->K);
+  if (B_host) memcpy(B_host, m->h_B.data(), sizeof(double) * (size_t)m->K);
+  if (st_host) memcpy(st_host, m->cal_st.data(), sizeof(pmh_svm_platt_stats) * (size_t)m->K);
+  return PMH_SUCCESS;
+}
+
+static int svmm_predict_proba(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *proba)
+{
+  PMH_ARG(m && (proba || n == 0));
+  if (m->trained && !m->calibrated) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_predict_proba: call pmh_svm_multi_calibrate or pmh_svm_multi_set_calibration first");
+  PMH_CHK(svmm_predict(m, n, X, Xt, proba, nullptr, true));
+  if (n > 0) {
+    hipLaunchKernelGGL(k_svmm_normalise, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, m->ctx->stream, n, m->K, proba);
+    PMH_HIP(hipGetLastError());
+  }
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_multi_predict_proba(pmh_svm_multi m, int n, const double *X_dev, double *proba_dev) { return svmm_predict_proba(m, n, X_dev, nullptr, proba_dev); }
+
+extern "C" int pmh_svm_multi_predict_proba_csr(pmh_svm_multi m, pmh_csr Xt, double *proba_dev)
+{
+  PMH_ARG(m && Xt);
+  return svmm_predict_proba(m, Xt->nrows, nullptr, Xt, proba_dev);
 }

@@ -5,6 +5,16 @@
 #include "reduce.h"
 #include "svm_internal.h"
 
+// 1 / (1 + e^z) without overflow: the two-branch form of Lin, Lin and Weng (svm_proba.hip), which the Platt fit and every probability kernel share
+static __device__ __forceinline__ double svm_sigmoid(double z)
+{
+  if (z >= 0.0) {
+    const double e = exp(-z);
+    return e / (1.0 + e);
+  }
+  return 1.0 / (1.0 + exp(z));
+}
+
 // any d <= 64 * SVM_KMAX: one wavefront per row, lane j owns columns j, j + 64, ...; f(i, x_i . w) in lane 0 of the wave that owns row i
 template <class F>
 static __device__ __forceinline__ void svm_sweep_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ w, F f)

@@ -8,6 +8,8 @@
 // sweeps of the operator's own pass 2, svm_rows.h).  Samples in CSR: x_i . w by the entry-balanced sweep of svm_csr.hip (one pass over the stored entries), then
 // one kernel over the n dot products (k_svm_bias_dots, k_svm_predict_dots).  What a row's dot product is used for is written once whichever kernel found it:
 // svm_bias_row, svm_classify_row; their four sums per thread leave every kernel through svm_store4.
+// Probabilities (pmh_svm_calibrate, pmh_svm_predict_proba): A, B of the Platt fit (svm_proba.hip) on the handle; 1 / (1 + exp(A (x_i . w + b) + B)) is one more
+// functor on the same sweeps (k_svm_proba, k_svm_proba64, k_svm_proba_dots), so a probability costs the one pass over X that a score costs.
 #include <cmath>
 
 #include "svm_internal.h"
@@ -31,6 +33,10 @@ struct pmh_svm_s {
   double        b = 0.0;
   int           trained = 0;
   pmh_svm_stats st;
+  // the probability model of the current (w, b): whatever gives the handle another model clears it
+  int                 calibrated = 0;
+  double              cal_A = 0.0, cal_B = 0.0;
+  pmh_svm_platt_stats cal_st;
 };
 
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_fill_row(int n, const double *__restrict__ y, double c, double *__restrict__ row)
@@ -120,6 +126,16 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double
   if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
 
+// One pass over the test samples: proba[i] = 1 / (1 + exp(A (x_i . w + b) + B)), the dot product summed as k_svm_predict / k_svm_predict64 sum it
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_proba(int n, int d, const double *__restrict__ X, const double *__restrict__ w, double b, double A, double B, double *__restrict__ proba)
+{
+  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { proba[i] = svm_sigmoid(A * (dot + b) + B); });
+}
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_proba64(int n, const double *__restrict__ X, const double *__restrict__ w, double b, double A, double B, double *__restrict__ proba)
+{
+  svm_sweep_rows64<4>(n, X, w, [&](long long i, double dot) { proba[i] = svm_sigmoid(A * (dot + b) + B); });
+}
+
 // ---- samples in CSR: the same sums as k_svm_bias / k_svm_predict from the rows' dot products x_i . w (svm_csr.hip), one entry per thread ----
 template <int UBV>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias_dots(int n, const double *__restrict__ dots, const double *__restrict__ y, const double *__restrict__ alpha, double astol, double ubound,
@@ -137,6 +153,19 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict_dots(int n, const dou
   svm_counts        c;
   for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) c = svm_classify_row(i, dots[i] + b, scores, labels, ytrue, c);
   if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
+}
+
+// (in place: the dot products lie where the probabilities go)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_proba_dots(int n, double b, double A, double B, double *proba)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) proba[i] = svm_sigmoid(A * (proba[i] + b) + B);
+}
+
+int pmh_svm_sum_rows(pmh_ctx ctx, int nb, int K, const double *part, double *out)
+{
+  hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, ctx->stream, nb, K, part, out);
+  PMH_HIP(hipGetLastError()); // (also the launch of the kernel that filled part)
+  return PMH_SUCCESS;
 }
 
 extern "C" int pmh_svm_default_opts(pmh_svm_opts *o)
@@ -299,6 +328,7 @@ extern "C" int pmh_svm_train(pmh_svm s)
   PMH_ARG(s);
   if (!s->sx && !s->mpgp) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_train: the handle has no solver (an earlier pmh_svm_set_labels / pmh_svm_set_penalties failed)");
   const size_t nb = sizeof(double) * (size_t)(s->n ? s->n : 1);
+  s->calibrated   = 0;
   PMH_CHK(pmh_memset(s->ctx, s->alpha, 0, nb));
   long long p0 = 0, p1 = 0;
   PMH_CHK(pmh_op_svm_dual_passes(s->H, &p0));
@@ -414,7 +444,7 @@ extern "C" int pmh_svm_set_penalties(pmh_svm s, double C_pos, double C_neg, cons
   }
   if (!s->Cv) PMH_CHK(pmh_malloc(ctx, nb, (void **)&s->Cv));
   if (L2 && !s->Cinv) PMH_CHK(pmh_malloc(ctx, nb, (void **)&s->Cinv));
-  s->trained = 0;
+  s->trained = s->calibrated = 0;
   if (n > 0) {
     hipLaunchKernelGGL(k_svm_fill_penalties, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, s->y, weight_dev, C_pos, C_neg, s->Cv, L2 ? nullptr : s->ub, L2 ? s->Cinv : nullptr);
     PMH_HIP(hipGetLastError());
@@ -440,7 +470,7 @@ extern "C" int pmh_svm_set_labels(pmh_svm s, const double *y_dev)
   PMH_ARG(s && y_dev);
   pmh_ctx   ctx = s->ctx;
   const int n   = s->n;
-  s->trained    = 0;
+  s->trained = s->calibrated = 0;
   // the solvers hold the operator and the projector: they go first
   if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
   if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
@@ -461,13 +491,20 @@ extern "C" int pmh_svm_set_labels(pmh_svm s, const double *y_dev)
   return svm_build_solver(s);
 }
 
+// the test samples against the model's width: CSR of the model's d columns, dense only up to the sweeps' limit
+static int svm_check_test_samples(pmh_svm s, pmh_csr Xt)
+{
+  if (Xt && Xt->ncols != s->d) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict_csr: the test samples have %d features, the model has %d", Xt->ncols, s->d);
+  if (!Xt && s->d > 64 * SVM_KMAX) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict: dense test samples need d <= %d, the model has d = %d: hand them over in CSR (pmh_svm_predict_csr)", 64 * SVM_KMAX, s->d);
+  return PMH_SUCCESS;
+}
+
 // X (dense rows, n x d) or Xt (CSR)
 static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts)
 {
   PMH_ARG(s && n >= 0 && (X || Xt || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict: call pmh_svm_train first");
-  if (Xt && Xt->ncols != s->d) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict_csr: the test samples have %d features, the model has %d", Xt->ncols, s->d);
-  if (!Xt && s->d > 64 * SVM_KMAX) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict: dense test samples need d <= %d, the model has d = %d: hand them over in CSR (pmh_svm_predict_csr)", 64 * SVM_KMAX, s->d);
+  PMH_CHK(svm_check_test_samples(s, Xt));
   const int nb = SVM_NB(n);
   if (n > 0 && Xt) {
     double *dots = scores; // the dot products land where the scores go; without scores in a buffer of this call
@@ -510,4 +547,77 @@ extern "C" int pmh_svm_test(pmh_svm s, int n, const double *X_dev, const double 
 {
   PMH_ARG(y_dev && counts);
   return svm_predict(s, n, X_dev, nullptr, nullptr, nullptr, y_dev, counts);
+}
+
+// ---- probabilities (Platt scaling, svm_proba.hip) ---------------------------------------------------------------------------------------------------------------
+// the scores of the calibration samples by the predict path, then the fit on them
+static int svm_calibrate(pmh_svm s, int n, const double *X, pmh_csr Xt, const double *y)
+{
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0) && (y || n == 0));
+  if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_calibrate: call pmh_svm_train first");
+  double *scores = nullptr;
+  PMH_CHK(pmh_malloc(s->ctx, sizeof(double) * (size_t)(n ? n : 1), (void **)&scores));
+  double              A = 0.0, B = 0.0;
+  pmh_svm_platt_stats st;
+  int                 rc = svm_predict(s, n, X, Xt, scores, nullptr, nullptr, nullptr);
+  if (!rc) rc = pmh_svm_platt_fit(s->ctx, n, scores, y, &A, &B, &st);
+  pmh_free(s->ctx, scores);
+  PMH_CHK(rc);
+  s->cal_A = A, s->cal_B = B, s->cal_st = st, s->calibrated = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_calibrate(pmh_svm s, int n, const double *X_dev, const double *y_dev) { return svm_calibrate(s, n, X_dev, nullptr, y_dev); }
+
+extern "C" int pmh_svm_calibrate_csr(pmh_svm s, pmh_csr Xt, const double *y_dev)
+{
+  PMH_ARG(s && Xt);
+  return svm_calibrate(s, Xt->nrows, nullptr, Xt, y_dev);
+}
+
+extern "C" int pmh_svm_set_calibration(pmh_svm s, double A, double B)
+{
+  PMH_ARG(s);
+  if (!std::isfinite(A) || !std::isfinite(B)) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_set_calibration: A = %g, B = %g, both must be finite", A, B);
+  if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_set_calibration: call pmh_svm_train first (a calibration belongs to a model)");
+  memset(&s->cal_st, 0, sizeof(s->cal_st));
+  s->cal_A = A, s->cal_B = B, s->calibrated = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_get_calibration(pmh_svm s, double *A, double *B, pmh_svm_platt_stats *st)
+{
+  PMH_ARG(s);
+  if (!s->calibrated) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_get_calibration: call pmh_svm_calibrate or pmh_svm_set_calibration first");
+  if (A) *A = s->cal_A;
+  if (B) *B = s->cal_B;
+  if (st) *st = s->cal_st;
+  return PMH_SUCCESS;
+}
+
+// X (dense rows, n x d) or Xt (CSR): one pass over the samples
+static int svm_predict_proba(pmh_svm s, int n, const double *X, pmh_csr Xt, double *proba)
+{
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0) && (proba || n == 0));
+  if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict_proba: call pmh_svm_train first");
+  if (!s->calibrated) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict_proba: call pmh_svm_calibrate or pmh_svm_set_calibration first");
+  PMH_CHK(svm_check_test_samples(s, Xt));
+  if (n == 0) return PMH_SUCCESS;
+  pmh_ctx   ctx = s->ctx;
+  const int nb  = SVM_NB(n);
+  if (Xt) {
+    PMH_CHK(pmh_svm_csr_row_dots(Xt, s->w, proba));
+    hipLaunchKernelGGL(k_svm_proba_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, s->b, s->cal_A, s->cal_B, proba);
+  } else if (s->d == 64) hipLaunchKernelGGL(k_svm_proba64, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, X, (const double *)s->w, s->b, s->cal_A, s->cal_B, proba);
+  else hipLaunchKernelGGL(k_svm_proba, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, s->d, X, (const double *)s->w, s->b, s->cal_A, s->cal_B, proba);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_predict_proba(pmh_svm s, int n, const double *X_dev, double *proba_dev) { return svm_predict_proba(s, n, X_dev, nullptr, proba_dev); }
+
+extern "C" int pmh_svm_predict_proba_csr(pmh_svm s, pmh_csr Xt, double *proba_dev)
+{
+  PMH_ARG(s && Xt);
+  return svm_predict_proba(s, Xt->nrows, nullptr, Xt, proba_dev);
 }

@@ -6,7 +6,11 @@
     bias: additionally y'a = 0 (SMALXE over a one-row projector; without bias MPGP alone)
 
 H = diag(y) X X' diag(y).  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width (kept in CSR on the device: 24 bytes per stored entry for
-the two orderings the operator sweeps).  Everything is computed by libpermonhip.so; there is no CPU fallback."""
+the two orderings the operator sweeps).  Everything is computed by libpermonhip.so; there is no CPU fallback.
+
+Probabilities: P(y = +1 | x) = 1 / (1 + exp(A s(x) + B)) by Platt scaling (csrc/svm_proba.hip: the Newton iteration of Lin, Lin and Weng, 2007).  calibrate(X, y)
+fits A, B on the scores of samples the caller supplies -- held-out ones, or the training set with the bias that brings -- and predict_proba applies them in
+the one pass over X that scoring takes."""
 import ctypes as ct
 
 import numpy as np
@@ -15,6 +19,27 @@ from . import _lib
 from ._lib import check
 from .core import Vec
 from .mat import csr_from_scipy, is_sparse
+
+
+PLATT_REASONS = {0: "set", 1: "converged", 2: "max_it", 3: "line_search"}  # pmh_svm_platt_stats.reason (PMH_PLATT_*); 0: the pair was set, not fitted
+
+
+def platt_fit(ctx, scores, y):
+    """Fit P(y = +1 | s) = 1 / (1 + exp(A s + B)) to scores and labels +-1 on the device (pmh_svm_platt_fit) -> (A, B, stats); stats.reason indexes
+    PLATT_REASONS.  scores, y: arrays or Vecs of one length."""
+    sd = scores if isinstance(scores, Vec) else Vec.from_numpy(ctx, np.ascontiguousarray(scores, dtype=np.float64).ravel())
+    yd = y if isinstance(y, Vec) else Vec.from_numpy(ctx, np.ascontiguousarray(y, dtype=np.float64).ravel())
+    try:
+        if sd.n != yd.n:
+            raise ValueError("platt_fit: %d scores and %d labels" % (sd.n, yd.n))
+        A, B, st = ct.c_double(), ct.c_double(), _lib.SvmPlattStats()
+        check(ctx.L.pmh_svm_platt_fit(ctx.h, sd.n, sd.p, yd.p, ct.byref(A), ct.byref(B), ct.byref(st)))
+        return A.value, B.value, st
+    finally:
+        if sd is not scores:
+            sd.free()
+        if yd is not y:
+            yd.free()
 
 
 class SVM:
@@ -209,6 +234,78 @@ class SVM:
     def predict(self, X):
         return self._predict(X, False, True)[1]
 
+    def calibrate(self, X, y):
+        """Fit the probability model of the trained handle on the samples X with labels y = +-1 (pmh_svm_calibrate): exactly platt_fit of
+        decision_function(X).  train, set_labels and set_penalties clear it."""
+        self._need()
+        yd = self._dev(y)
+        try:
+            if is_sparse(X):
+                if X.shape[1] != self.d or X.shape[0] != yd.n:
+                    raise ValueError("SVM: X must be (%d, %d)" % (yd.n, self.d))
+                Xd = csr_from_scipy(self.ctx, X)
+                try:
+                    check(self.L.pmh_svm_calibrate_csr(self.h, Xd.h, yd.p))
+                finally:
+                    Xd.destroy()
+            else:
+                X = np.ascontiguousarray(X, dtype=np.float64)
+                if X.ndim != 2 or X.shape[1] != self.d or X.shape[0] != yd.n:
+                    raise ValueError("SVM: X must be (%d, %d)" % (yd.n, self.d))
+                Xd = self._dev(X)
+                try:
+                    check(self.L.pmh_svm_calibrate(self.h, X.shape[0], Xd.p, yd.p))
+                finally:
+                    Xd.free()
+        finally:
+            if yd is not y:
+                yd.free()
+        return self
+
+    def set_calibration(self, A, B):
+        """A saved pair (A, B) in place of calibrate."""
+        self._need()
+        check(self.L.pmh_svm_set_calibration(self.h, float(A), float(B)))
+        return self
+
+    @property
+    def calibration(self):
+        """(A, B) of the probability model."""
+        self._need()
+        A, B = ct.c_double(), ct.c_double()
+        check(self.L.pmh_svm_get_calibration(self.h, ct.byref(A), ct.byref(B), None))
+        return A.value, B.value
+
+    @property
+    def calibration_stats(self):
+        """pmh_svm_platt_stats of the fit behind calibration (reason 0: the pair was set)."""
+        self._need()
+        st = _lib.SvmPlattStats()
+        check(self.L.pmh_svm_get_calibration(self.h, None, None, ct.byref(st)))
+        return st
+
+    def predict_proba(self, X):
+        """(n,): P(y = +1 | x_i) = 1 / (1 + exp(A decision_function(x_i) + B)), in one pass over X (pmh_svm_predict_proba)."""
+        self._need()
+        if is_sparse(X):
+            if X.shape[1] != self.d:
+                raise ValueError("SVM: X must be (n, %d)" % self.d)
+            Xd, p = csr_from_scipy(self.ctx, X), Vec(self.ctx, X.shape[0], zero=False)
+            try:
+                check(self.L.pmh_svm_predict_proba_csr(self.h, Xd.h, p.p))
+                return p.to_numpy()
+            finally:
+                Xd.destroy(), p.free()
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError("SVM: X must be (n, %d)" % self.d)
+        Xd, p = self._dev(X), Vec(self.ctx, X.shape[0], zero=False)
+        try:
+            check(self.L.pmh_svm_predict_proba(self.h, X.shape[0], Xd.p, p.p))
+            return p.to_numpy()
+        finally:
+            Xd.free(), p.free()
+
     def test(self, X, y):
         """Confusion counts of the predicted labels against y: dict(TP, FP, TN, FN, accuracy)."""
         self._need()
@@ -395,6 +492,75 @@ class SVMMulticlass:
             for v in (s, l, t):
                 if v is not None and v is not labels_true:
                     v.free()
+
+    def calibrate(self, X, labels):
+        """Fit the K probability models on the samples X with true labels (pmh_svm_multi_calibrate): model k is platt_fit of column k of decision_function(X)
+        with "label == class k" as +1; a label that is no class counts among the rest.  train and set_model clear them."""
+        self._need()
+        sparse = is_sparse(X)
+        if not sparse:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+        ld = self._dev(labels)
+        try:
+            if X.ndim != 2 or X.shape[1] != self.d or X.shape[0] != ld.n:
+                raise ValueError("SVMMulticlass: X must be (%d, %d)" % (ld.n, self.d))
+            Xd = csr_from_scipy(self.ctx, X) if sparse else self._dev(X)
+            try:
+                if sparse:
+                    check(self.L.pmh_svm_multi_calibrate_csr(self.h, Xd.h, ld.p))
+                else:
+                    check(self.L.pmh_svm_multi_calibrate(self.h, X.shape[0], Xd.p, ld.p))
+            finally:
+                Xd.destroy() if sparse else Xd.free()
+        finally:
+            if ld is not labels:
+                ld.free()
+        return self
+
+    def set_calibration(self, A, B):
+        """Saved pairs in place of calibrate: A (K), B (K)."""
+        self._need()
+        A, B = np.ascontiguousarray(A, dtype=np.float64).ravel(), np.ascontiguousarray(B, dtype=np.float64).ravel()
+        if A.shape != (self.K,) or B.shape != (self.K,):
+            raise ValueError("SVMMulticlass: A and B must have %d entries each" % self.K)
+        check(self.L.pmh_svm_multi_set_calibration(self.h, A.ctypes.data_as(ct.c_void_p), B.ctypes.data_as(ct.c_void_p)))
+        return self
+
+    @property
+    def calibration(self):
+        """(A, B), two K-vectors: the classes' probability models."""
+        self._need()
+        A, B = np.empty(self.K), np.empty(self.K)
+        check(self.L.pmh_svm_multi_get_calibration(self.h, A.ctypes.data_as(ct.c_void_p), B.ctypes.data_as(ct.c_void_p), None))
+        return A, B
+
+    @property
+    def calibration_stats(self):
+        """The K fits' pmh_svm_platt_stats, class by class."""
+        self._need()
+        st = (_lib.SvmPlattStats * self.K)()
+        check(self.L.pmh_svm_multi_get_calibration(self.h, None, None, ct.cast(st, ct.c_void_p)))
+        return list(st)
+
+    def predict_proba(self, X):
+        """(n, K): sigma_ik = 1 / (1 + exp(A_k score_ik + B_k)), every row divided by its sum (a row of zeros: 1 / K); one pass over X per chunk of classes."""
+        self._need()
+        sparse = is_sparse(X)
+        if not sparse:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
+        n = X.shape[0]
+        Xd, p = csr_from_scipy(self.ctx, X) if sparse else self._dev(X), Vec(self.ctx, n * self.K, zero=False)
+        try:
+            if sparse:
+                check(self.L.pmh_svm_multi_predict_proba_csr(self.h, Xd.h, p.p))
+            else:
+                check(self.L.pmh_svm_multi_predict_proba(self.h, n, Xd.p, p.p))
+            return p.to_numpy().reshape(n, self.K)
+        finally:
+            Xd.destroy() if sparse else Xd.free()
+            p.free()
 
     def decision_function(self, X):
         """(n, K): x_i . W_k + b_k."""
