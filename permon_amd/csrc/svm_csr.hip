@@ -6,6 +6,7 @@
 //   pass 2  (H a)_i = y_i (x_i . w) + sigma s y_i + shift a_i  (svm_aug_row; with a diagonal set, diag_i a_i: MODE 3 of the finishing step).
 // Both passes, the bias pass of the model and prediction are ONE kernel pair, a segmented sum over a compressed array (ptr / idx / val): segments are the
 // samples (the caller's CSR) in pass 2 and in prediction, and the features in pass 1, which runs over a column-ordered device copy built once at creation.
+// The sum's code is in svm_csr_seg.h (svc_segments, svc_finish), where the K-column scoring of svm_multi.hip shares it; its description is here.
 //
 // Work is divided by stored entries, not by segments: workgroup b owns the SVC_SPAN entries [b SVC_SPAN, (b + 1) SVC_SPAN) (k_svc_seg).  It forms their
 // products with the gathered vector in LDS, sums every segment's piece inside the span with G lanes per segment (G = 1 .. 64, from the span's mean piece
@@ -32,12 +33,7 @@
 // runs its separate vector kernels; the ||B u|| rider of the penalised operator is declined too (the one-row projector's own dot runs).
 #include <algorithm>
 
-#include "svm_internal.h"
 #include "svm_csr_seg.h"
-#include "reduce.h"
-
-typedef double svc_dbl2 __attribute__((ext_vector_type(2)));
-typedef int    svc_int2 __attribute__((ext_vector_type(2)));
 
 // first[b] = the segment that holds entry b SVC_SPAN (the smallest c with ptr[c + 1] > b SVC_SPAN); first[0] = 0, so that leading empty segments belong to span 0
 __global__ __launch_bounds__(PMH_BLOCK) void k_svc_first(int nb, int nseg, const int *__restrict__ ptr, int *__restrict__ first)
@@ -75,18 +71,11 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svc_seg(int nent, int nseg, int n
 {
   __shared__ double prod[SVC_SPAN];
   const int         b = blockIdx.x, start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent);
-  // the span's products: 16-byte value and 8-byte index loads (start is even and the arrays are 16-byte aligned), all asked for before the gathers
-  svc_dbl2 v[SVC_SPAN / PMH_BLOCK / 2];
-  svc_int2 ix[SVC_SPAN / PMH_BLOCK / 2];
+  // the span's products: every load of values and indices asked for before the gathers
+  dbl2  v[SVC_SPAN / PMH_BLOCK / 2];
+  int2v ix[SVC_SPAN / PMH_BLOCK / 2];
 #pragma unroll
-  for (int j = 0; j < SVC_SPAN / PMH_BLOCK / 2; j++) {
-    const int k = start + 2 * (j * PMH_BLOCK + (int)threadIdx.x);
-    v[j] = svc_dbl2{0.0, 0.0}, ix[j] = svc_int2{0, 0};
-    if (k + 1 < end) {
-      v[j]  = __builtin_nontemporal_load((const svc_dbl2 *)(val + k));
-      ix[j] = __builtin_nontemporal_load((const svc_int2 *)(idx + k));
-    } else if (k < end) v[j].x = val[k], ix[j].x = idx[k];
-  }
+  for (int j = 0; j < SVC_SPAN / PMH_BLOCK / 2; j++) svc_load_pair(j, start, end, val, idx, v[j], ix[j]);
 #pragma unroll
   for (int j = 0; j < SVC_SPAN / PMH_BLOCK / 2; j++) {
     const int k = 2 * (j * PMH_BLOCK + (int)threadIdx.x);
@@ -94,42 +83,17 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svc_seg(int nent, int nseg, int n
     prod[k + 1] = v[j].y * x[ix[j].y];
   }
   __syncthreads();
-  int c0, c1;
-  svc_range(b, nb, nseg, end, ptr, first, c0, c1);
-  // lanes per segment: the largest power of two <= mean piece length / 4, at most a wavefront
-  const int avg = (end - start) / (c1 - c0 + 1);
-  int       G   = 1;
-  while (G < 64 && G * 8 <= avg) G <<= 1;
-  const int    g = threadIdx.x / G, l = threadIdx.x % G;
   const double sS = MODE >= 2 ? o.sigma * *o.s : 0.0;
-  for (int c = c0 + g; c <= c1; c += PMH_BLOCK / G) { // (the trip count is uniform over a segment's G lanes)
-    const int p0 = ptr[c], p1 = ptr[c + 1], lo = max(p0, start) - start, hi = min(p1, end) - start;
-    double    s = 0.0;
-    for (int k = lo + l; k < hi; k += G) s += prod[k];
-    for (int w = G >> 1; w > 0; w >>= 1) s += __shfl_down(s, w, G);
-    if (l == 0) {
-      if (p0 >= start && p1 <= end) svc_store<MODE>(o, c, s, sS); // the whole segment lies in this span
-      else if (c == c0) head[b] = s;
-      else tail[b] = s;
-    }
-  }
+  svc_segments<1>(
+    b, nb, nseg, start, end, ptr, first, head, tail, [&](int k, double(&s)[1]) { s[0] += prod[k]; }, [&](int c, const double(&s)[1]) { svc_store<MODE>(o, c, s[0], sS); });
 }
 
-// one wavefront per span: where the span's first segment began in an earlier span and ends in this one, add its pieces in span order and store the segment
+// the shared segments, each completed in the span where it ends
 template <int MODE>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svc_fin(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ first, const double *__restrict__ head,
                                                        const double *__restrict__ tail, svc_out o)
 {
-  const int lane = threadIdx.x & 63, b = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
-  if (b >= nb) return;
-  const int start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent), c = first[b], p0 = ptr[c], p1 = ptr[c + 1];
-  if (!(p0 < start && p1 <= end)) return; // (wave-uniform)
-  const int  b0    = p0 / SVC_SPAN;
-  const bool tail0 = first[b0] != c; // in the span where it begins the segment is the last of several: its piece is that span's tail
-  double     s     = 0.0;
-  for (int bb = b0 + lane; bb <= b; bb += 64) s += (bb == b0 && tail0) ? tail[b0] : head[bb];
-  s = pmh_wave_sum(s);
-  if (lane == 0) svc_store<MODE>(o, c, s, MODE >= 2 ? o.sigma * *o.s : 0.0);
+  svc_finish<1>(nent, nseg, nb, ptr, first, head, tail, [&](int c, const double(&s)[1]) { svc_store<MODE>(o, c, s[0], MODE >= 2 ? o.sigma * *o.s : 0.0); });
 }
 
 // new labels: cval[q] = y_i(old) y_i(new) cval[q] for the entry q of sample i = crow[q] (column d included: y_i(old)^2 y_i(new) = y_i(new)); the products
@@ -243,11 +207,22 @@ int pmh_svm_csr_op_row_dots(SvmDualBase *op, const double *wv, double *dots)
   return svc_sweep<0>(o->ctx, o->rows, o->n, o->nnz, o->X->d_rowptr, o->X->d_col, o->X->d_val, wv, so);
 }
 
+// the kernels' 32-bit offsets: an array of nent entries, and the span past its end, must stay below 2^31
+static bool svc_too_many(long long nent) { return nent >= (1LL << 31) - SVC_SPAN; }
+static int  svc_check_entries(long long nnz) { return svc_too_many(nnz) ? pmh_set_error(PMH_ERR_ARG, "SVM on CSR samples: %lld stored entries, the count must stay below 2^31 (32-bit offsets)", nnz) : PMH_SUCCESS; }
+
+int pmh_svm_check_test_samples(const char *who, int d, pmh_csr Xt)
+{
+  if (Xt && Xt->ncols != d) return pmh_set_error(PMH_ERR_ARG, "%s_csr: the test samples have %d features, the model has %d", who, Xt->ncols, d);
+  if (!Xt && d > 64 * SVM_KMAX) return pmh_set_error(PMH_ERR_ARG, "%s: dense test samples need d <= %d, the model has d = %d: hand them over in CSR (%s_csr)", who, 64 * SVM_KMAX, d, who);
+  return Xt ? svc_check_entries(Xt->nnz) : PMH_SUCCESS;
+}
+
 int pmh_svm_csr_row_dots(pmh_csr X, const double *wv, double *dots)
 {
   PMH_ARG(X && wv && dots);
   if (X->nrows == 0) return PMH_SUCCESS;
-  if (X->nnz >= (1LL << 31) - SVC_SPAN) return pmh_set_error(PMH_ERR_ARG, "SVM on CSR samples: %lld stored entries, the count must stay below 2^31 (32-bit offsets)", X->nnz);
+  PMH_CHK(svc_check_entries(X->nnz));
   svc_tab t;
   int     rc = svc_tab_build(X->ctx, X->nrows, X->d_rowptr, X->nnz, &t);
   svc_out so{dots, nullptr, nullptr, nullptr, 0.0, 0.0};
@@ -262,7 +237,7 @@ extern "C" int pmh_op_create_svm_dual_csr(pmh_ctx ctx, pmh_csr X, const double *
   const int       n = X->nrows, d = X->ncols;
   const long long nnz = X->nnz;
   if (d < 1) return pmh_set_error(PMH_ERR_ARG, "pmh_op_create_svm_dual_csr: the sample matrix has no columns");
-  if (nnz + n >= (1LL << 31) - SVC_SPAN) return pmh_set_error(PMH_ERR_ARG, "pmh_op_create_svm_dual_csr: %lld stored entries and %d samples: the entry count must stay below 2^31 (32-bit offsets)", nnz, n);
+  if (svc_too_many(nnz + n)) return pmh_set_error(PMH_ERR_ARG, "pmh_op_create_svm_dual_csr: %lld stored entries and %d samples: the entry count must stay below 2^31 (32-bit offsets)", nnz, n);
   // the caller's matrix on the host: checked (columns ascending inside a row; their range was checked by pmh_csr_create) and turned by columns
   std::vector<int>    rp((size_t)n + 1, 0), col((size_t)nnz);
   std::vector<double> val((size_t)nnz), yh((size_t)n);

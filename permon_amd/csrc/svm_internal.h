@@ -104,3 +104,6 @@ int pmh_svm_platt_fit_strided(pmh_ctx ctx, int n, const double *scores, int stri
 int pmh_svm_csr_row_dots(pmh_csr X, const double *w, double *dots);
 // the same for the operator's own samples, with the tables it already holds; counted as a pass
 int pmh_svm_csr_op_row_dots(SvmDualBase *op, const double *w, double *dots);
+// the test samples of the entry `who` (Xt, or dense rows: Xt == nullptr) against a model of d features: CSR of exactly d columns and fewer than 2^31 stored
+// entries, dense only up to the sweeps' limit; else PMH_ERR_ARG in the name of who / who_csr
+int pmh_svm_check_test_samples(const char *who, int d, pmh_csr Xt);

@@ -14,11 +14,9 @@
 //     one class left is completed over the remaining offsets (.., 2, 1: t + partner's t).  The class c of the chunk ends in lanes c (32 / KC) .. of the row.  Last: + b_k.
 //   dense, any d <= 256 (k_svmm_rows): one wavefront per row as svm_sweep_rows, lane j holds columns j, j + 64, ..; per class 0 + x_j w_j + x_{j+64} w_{j+64} + ..
 //     (columns past d count as 0 * 0), then the same butterfly over 64 lanes (a chunk of 4: offsets 32, 16 halving; 8, 4, 2, 1 completing), + b_k.
-//   CSR (k_svmm_seg / k_svmm_fin): the entry-partitioned segmented sum of svm_csr.hip with SVMM_KC sums per segment.  A workgroup stages its span's values and
-//     column indices in LDS (24 KiB); the G lanes of a sample add, per class, val * Wt[col][class] over the sample's entries lo + l, lo + l + G, .. ascending,
-//     then the shfl_down tree G/2 .. 1; samples shared between spans are finished in the span where they end: the pieces in span order over the lanes of one
-//     wavefront, then pmh_wave_sum, per class.  Last: + b_k.  Wt is the chunk's weights as d x SVMM_KC, class index fastest: 8 SVMM_KC contiguous bytes per stored entry.
-//     Work is divided by entries, a sample without entries scores b_k, one long sample is summed by whole wavefronts in many spans.
+//   CSR (k_svmm_seg / k_svmm_fin): the entry-partitioned segmented sum of svm_csr.hip (svc_segments / svc_finish of svm_csr_seg.h) with SVMM_KC sums per sample.
+//     A workgroup stages its span's values and column indices in LDS (24 KiB); a stored entry adds val * Wt[col][class] to each class's sum.  Last: + b_k.  Wt is
+//     the chunk's weights as d x SVMM_KC, class index fastest: 8 SVMM_KC contiguous bytes per stored entry.  A sample without entries scores b_k.
 //
 // Algorithmic bytes of one call: dense 8 n d ceil(K / KC) + 8 n K (scores) + 8 n (labels), against K (8 n d + 8 n) for K binary calls; CSR 12 nnz ceil(K / KC)
 // + 4 n + 8 n K + 8 n, the gathers of Wt (8 KC bytes per entry) served by the caches where 8 KC d bytes fit.
@@ -203,87 +201,46 @@ template <int KC, class OUT> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm
   }
 }
 
-// CSR: span b's pieces of the samples' KC sums (k_svc_seg with KC columns; Wt: d x KC, class index fastest; head / tail: KC doubles per span)
+// CSR: span b's pieces of the samples' KC sums (svc_segments; Wt: d x KC, class index fastest; head / tail: KC doubles per span)
 template <int KC, class OUT>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_seg(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ Wt,
                                                         const int *__restrict__ first, double *__restrict__ head, double *__restrict__ tail, OUT o)
 {
-  __shared__ dbl2 sval2[SVC_SPAN / 2];
-  typedef int     int2v __attribute__((ext_vector_type(2)));
+  __shared__ dbl2  sval2[SVC_SPAN / 2];
   __shared__ int2v sidx2[SVC_SPAN / 2];
   const int        b = blockIdx.x, start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent);
-  // the span's values and indices: 16-byte and 8-byte loads (start is even and the arrays are 16-byte aligned); entries past the end: 0, column 0, never read
+  // the span's values and indices (entries past the end: 0, column 0, never read)
 #pragma unroll
   for (int j = 0; j < SVC_SPAN / PMH_BLOCK / 2; j++) {
-    const int q = j * PMH_BLOCK + (int)threadIdx.x, k = start + 2 * q;
-    dbl2      v = dbl2{0.0, 0.0};
-    int2v     ix = int2v{0, 0};
-    if (k + 1 < end) {
-      v  = __builtin_nontemporal_load((const dbl2 *)(val + k));
-      ix = __builtin_nontemporal_load((const int2v *)(idx + k));
-    } else if (k < end) v.x = val[k], ix.x = idx[k];
+    const int q = j * PMH_BLOCK + (int)threadIdx.x;
+    dbl2      v;
+    int2v     ix;
+    svc_load_pair(j, start, end, val, idx, v, ix);
     sval2[q] = v, sidx2[q] = ix;
   }
   __syncthreads();
   const double *sval = (const double *)sval2;
   const int    *sidx = (const int *)sidx2;
-  int           c0, c1;
-  svc_range(b, nb, nseg, end, ptr, first, c0, c1);
-  // lanes per sample: as k_svc_seg
-  const int avg = (end - start) / (c1 - c0 + 1);
-  int       G   = 1;
-  while (G < 64 && G * 8 <= avg) G <<= 1;
-  const int g = threadIdx.x / G, l = threadIdx.x % G;
-  for (int c = c0 + g; c <= c1; c += PMH_BLOCK / G) { // (the trip count is uniform over a sample's G lanes)
-    const int p0 = ptr[c], p1 = ptr[c + 1], lo = max(p0, start) - start, hi = min(p1, end) - start;
-    double    s[KC];
-#pragma unroll
-    for (int j = 0; j < KC; j++) s[j] = 0.0;
-    for (int k = lo + l; k < hi; k += G) {
-      const double  xv = sval[k];
-      const dbl2   *wr = (const dbl2 *)(Wt + (size_t)sidx[k] * KC);
+  svc_segments<KC>(
+    b, nb, nseg, start, end, ptr, first, head, tail,
+    [&](int k, double(&s)[KC]) { // two classes per load of the entry's row of Wt
+      const double xv = sval[k];
+      const dbl2  *wr = (const dbl2 *)(Wt + (size_t)sidx[k] * KC);
 #pragma unroll
       for (int j = 0; j < KC / 2; j++) {
         const dbl2 w2 = wr[j];
         s[2 * j] += xv * w2.x, s[2 * j + 1] += xv * w2.y;
       }
-    }
-    for (int w = G >> 1; w > 0; w >>= 1)
-#pragma unroll
-      for (int j = 0; j < KC; j++) s[j] += __shfl_down(s[j], w, G);
-    if (l == 0) {
-      if (p0 >= start && p1 <= end) svmm_row_done<KC>(o, c, s); // the whole sample lies in this span
-      else {
-        double *dst = (c == c0 ? head : tail) + (size_t)b * KC;
-#pragma unroll
-        for (int j = 0; j < KC; j++) dst[j] = s[j];
-      }
-    }
-  }
+    },
+    [&](int c, const double(&s)[KC]) { svmm_row_done<KC>(o, c, s); });
 }
 
-// one wavefront per span (k_svc_fin with KC columns): the sample that began in an earlier span and ends in this one
+// the samples shared between spans, each completed in the span where it ends (svc_finish)
 template <int KC, class OUT>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_fin(int nent, int nseg, int nb, const int *__restrict__ ptr, const int *__restrict__ first, const double *__restrict__ head,
                                                         const double *__restrict__ tail, OUT o)
 {
-  const int lane = threadIdx.x & 63, b = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
-  if (b >= nb) return;
-  const int start = b * SVC_SPAN, end = min(start + SVC_SPAN, nent), c = first[b], p0 = ptr[c], p1 = ptr[c + 1];
-  if (!(p0 < start && p1 <= end)) return; // (wave-uniform)
-  const int  b0    = p0 / SVC_SPAN;
-  const bool tail0 = first[b0] != c; // in the span where it begins the sample is the last of several: its piece is that span's tail
-  double     s[KC];
-#pragma unroll
-  for (int j = 0; j < KC; j++) s[j] = 0.0;
-  for (int bb = b0 + lane; bb <= b; bb += 64) {
-    const double *p = ((bb == b0 && tail0) ? tail : head) + (size_t)bb * KC;
-#pragma unroll
-    for (int j = 0; j < KC; j++) s[j] += p[j];
-  }
-#pragma unroll
-  for (int j = 0; j < KC; j++) s[j] = pmh_wave_sum(s[j]);
-  if (lane == 0) svmm_row_done<KC>(o, c, s);
+  svc_finish<KC>(nent, nseg, nb, ptr, first, head, tail, [&](int c, const double(&s)[KC]) { svmm_row_done<KC>(o, c, s); });
 }
 
 // proba[i][k] /= sum_k proba[i][k], the sum taken k ascending; a row whose sum is 0 (every sigma underflowed) becomes 1 / K everywhere.  One row per thread
@@ -537,10 +494,7 @@ static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, dou
 {
   PMH_ARG(m && n >= 0 && (X || Xt || n == 0));
   if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_predict: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
-  if (Xt && Xt->ncols != m->d) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_predict_csr: the test samples have %d features, the model has %d", Xt->ncols, m->d);
-  if (!Xt && m->d > 64 * SVM_KMAX)
-    return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_predict: dense test samples need d <= %d, the model has d = %d: hand them over in CSR (pmh_svm_multi_predict_csr)", 64 * SVM_KMAX, m->d);
-  if (Xt && Xt->nnz >= (1LL << 31) - SVC_SPAN) return pmh_set_error(PMH_ERR_ARG, "SVM on CSR samples: %lld stored entries, the count must stay below 2^31 (32-bit offsets)", Xt->nnz);
+  PMH_CHK(pmh_svm_check_test_samples("pmh_svm_multi_predict", m->d, Xt));
   if (n == 0 || (!scores && !labels)) return PMH_SUCCESS;
   pmh_ctx ctx  = m->ctx;
   double *best = nullptr;

@@ -276,10 +276,8 @@ extern "C" int pmh_svm_create_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, c
 // scal[0..3] = the sums over all workgroups and ranks of the four rows a bias / predict kernel left in part[4][nb] (n == 0: no kernel ran, zeros)
 static int svm_sum_part(pmh_svm s, int n, int nb)
 {
-  if (n > 0) {
-    hipLaunchKernelGGL(k_svm_sum_rows, dim3(1), dim3(PMH_BLOCK), 0, s->ctx->stream, nb, 4, (const double *)s->part, s->scal);
-    PMH_HIP(hipGetLastError()); // (also the launch of the kernel that filled part)
-  } else PMH_CHK(pmh_memset(s->ctx, s->scal, 0, sizeof(double) * 4));
+  if (n > 0) PMH_CHK(pmh_svm_sum_rows(s->ctx, nb, 4, s->part, s->scal));
+  else PMH_CHK(pmh_memset(s->ctx, s->scal, 0, sizeof(double) * 4));
   return pmh_comm_allreduce_sum(s->ctx, s->scal, 4);
 }
 
@@ -491,20 +489,12 @@ extern "C" int pmh_svm_set_labels(pmh_svm s, const double *y_dev)
   return svm_build_solver(s);
 }
 
-// the test samples against the model's width: CSR of the model's d columns, dense only up to the sweeps' limit
-static int svm_check_test_samples(pmh_svm s, pmh_csr Xt)
-{
-  if (Xt && Xt->ncols != s->d) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict_csr: the test samples have %d features, the model has %d", Xt->ncols, s->d);
-  if (!Xt && s->d > 64 * SVM_KMAX) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_predict: dense test samples need d <= %d, the model has d = %d: hand them over in CSR (pmh_svm_predict_csr)", 64 * SVM_KMAX, s->d);
-  return PMH_SUCCESS;
-}
-
 // X (dense rows, n x d) or Xt (CSR)
 static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts)
 {
   PMH_ARG(s && n >= 0 && (X || Xt || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict: call pmh_svm_train first");
-  PMH_CHK(svm_check_test_samples(s, Xt));
+  PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
   const int nb = SVM_NB(n);
   if (n > 0 && Xt) {
     double *dots = scores; // the dot products land where the scores go; without scores in a buffer of this call
@@ -601,7 +591,7 @@ static int svm_predict_proba(pmh_svm s, int n, const double *X, pmh_csr Xt, doub
   PMH_ARG(s && n >= 0 && (X || Xt || n == 0) && (proba || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict_proba: call pmh_svm_train first");
   if (!s->calibrated) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict_proba: call pmh_svm_calibrate or pmh_svm_set_calibration first");
-  PMH_CHK(svm_check_test_samples(s, Xt));
+  PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
   if (n == 0) return PMH_SUCCESS;
   pmh_ctx   ctx = s->ctx;
   const int nb  = SVM_NB(n);

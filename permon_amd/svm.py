@@ -11,6 +11,7 @@ the two orderings the operator sweeps).  Everything is computed by libpermonhip.
 Probabilities: P(y = +1 | x) = 1 / (1 + exp(A s(x) + B)) by Platt scaling (csrc/svm_proba.hip: the Newton iteration of Lin, Lin and Weng, 2007).  calibrate(X, y)
 fits A, B on the scores of samples the caller supplies -- held-out ones, or the training set with the bias that brings -- and predict_proba applies them in
 the one pass over X that scoring takes."""
+import contextlib
 import ctypes as ct
 
 import numpy as np
@@ -42,11 +43,53 @@ def platt_fit(ctx, scores, y):
             yd.free()
 
 
-class SVM:
-    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", C_pos=None, C_neg=None):
-        """options: a PETSc-style option string for the solver (-qps_rtol 1e-6, -qps_mpgp_*, -qps_smalxe_*, -smalxe_qps_* ...) and -svm_loss_type / -svm_C /
-        -svm_bias, which override the keyword arguments.  C_pos / C_neg: the penalty of the samples with y = +1 / y = -1 (None: C)."""
-        self.C_pos, self.C_neg = C_pos, C_neg
+class _Samples:
+    """Samples for one library call: X, a scipy.sparse matrix (csr_from_scipy) or anything else (a contiguous float64 array), is put on the device on entry
+    and taken off again on exit, whatever happened in between.  Entering gives n and the samples' arguments of the entry: (handle,) for CSR, (n, pointer)
+    for dense rows -- with_d: (n, d, pointer), as the create entries take them.  X is the converted array: the shape checks are the caller's."""
+
+    def __init__(self, ctx, X, with_d=False):
+        self.ctx, self.sparse, self.with_d, self.dev = ctx, is_sparse(X), with_d, None
+        self.X = X if self.sparse else np.ascontiguousarray(X, dtype=np.float64)
+
+    def __enter__(self):
+        n = self.X.shape[0]
+        if self.sparse:
+            self.dev = csr_from_scipy(self.ctx, self.X)
+            return n, (self.dev.h,)
+        self.dev = Vec.from_numpy(self.ctx, self.X.ravel())
+        return n, ((n, self.X.shape[1], self.dev.p) if self.with_d else (n, self.dev.p))
+
+    def keep(self):
+        """The device copy, the caller's from now on."""
+        d, self.dev = self.dev, None
+        return d
+
+    def __exit__(self, *exc):
+        if self.dev is not None:
+            self.dev.destroy() if self.sparse else self.dev.free()
+
+
+@contextlib.contextmanager
+def _vecs(ctx, *sizes):
+    """Uninitialised device vectors of the given lengths for the length of a call (None: no vector, None in its place)."""
+    vs = []
+    try:
+        for m in sizes:
+            vs.append(None if m is None else Vec(ctx, m, zero=False))
+        yield vs
+    finally:
+        for v in vs:
+            if v is not None:
+                v.free()
+
+
+class _SVMHandle:
+    """What SVM and SVMMulticlass share: the options, the handle with the buffers it borrows, and how a call is made on samples of either kind."""
+
+    _who, _pre = "SVM", "pmh_svm_"  # the class in messages, the prefix of its entries
+
+    def __init__(self, ctx, loss, C, bias, options):
         self.ctx, self.L = ctx, ctx.L
         o = _lib.SvmOpts()
         check(self.L.pmh_svm_default_opts(o))
@@ -64,10 +107,59 @@ class SVM:
     def _dev(self, a):
         return a if isinstance(a, Vec) else Vec.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.float64).ravel())
 
+    @contextlib.contextmanager
+    def _lent(self, a):
+        """a (an array, a Vec or None) as a Vec for the length of a call; a Vec made here is freed afterwards, the caller's is not."""
+        v = None if a is None else self._dev(a)
+        try:
+            yield v
+        finally:
+            if v is not None and v is not a:
+                v.free()
+
+    def _need(self):
+        if self.h is None:
+            raise RuntimeError("%s: call fit first" % self._who)
+
+    def _entry(self, name, sparse):
+        return getattr(self.L, self._pre + name + ("_csr" if sparse else ""))
+
+    def _create_handle(self, X, y, *more):
+        """The handle on (X, y), which it borrows for its lifetime: both stay on the device in _keep."""
+        self.destroy()
+        S = _Samples(self.ctx, X, with_d=True)
+        self.n, self.d = S.X.shape
+        h = ct.c_void_p()
+        with S as (n, xa):
+            yd = self._dev(y)
+            try:
+                check(self._entry("create", S.sparse)(self.ctx.h, *xa, yd.p, self.opts, *more, ct.byref(h)))
+            except Exception:
+                yd.free()
+                raise
+            self.h, self._keep = h, (S.keep(), yd)
+        return self
+
+    def destroy(self):
+        if self.h is not None:
+            self._entry("destroy", False)(self.h)
+            self.h = None
+            for v in self._keep or ():
+                v.destroy() if hasattr(v, "destroy") else v.free()
+            self._keep = None
+
+
+class SVM(_SVMHandle):
+    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", C_pos=None, C_neg=None):
+        """options: a PETSc-style option string for the solver (-qps_rtol 1e-6, -qps_mpgp_*, -qps_smalxe_*, -smalxe_qps_* ...) and -svm_loss_type / -svm_C /
+        -svm_bias, which override the keyword arguments.  C_pos / C_neg: the penalty of the samples with y = +1 / y = -1 (None: C)."""
+        self.C_pos, self.C_neg = C_pos, C_neg
+        super().__init__(ctx, loss, C, bias, options)
+
     def create(self, X, y, sample_weight=None):
         """Set the training samples (X: (n, d) row-major ndarray or scipy.sparse matrix, y: +-1) and build the solver without training.  sample_weight: n
         positive numbers that scale the samples' penalties (None: all 1)."""
-        self._create(X, y)
+        self._create_handle(X, y)
         if self.C_pos is not None or self.C_neg is not None or sample_weight is not None:
             self.set_penalties(self.C_pos, self.C_neg, sample_weight)
         return self
@@ -75,16 +167,10 @@ class SVM:
     def set_penalties(self, C_pos=None, C_neg=None, sample_weight=None):
         """C_i = (y_i > 0 ? C_pos : C_neg) sample_weight_i on the created handle (pmh_svm_set_penalties; None: C, C, all 1); the handle is untrained afterwards."""
         self._need()
-        wd = None
-        if sample_weight is not None:
-            wd = self._dev(sample_weight)
-            if wd.n != self.n:
+        with self._lent(sample_weight) as wd:
+            if wd is not None and wd.n != self.n:
                 raise ValueError("SVM: sample_weight must have %d entries" % self.n)
-        try:
             check(self.L.pmh_svm_set_penalties(self.h, float(self.C if C_pos is None else C_pos), float(self.C if C_neg is None else C_neg), wd.p if wd is not None else None))
-        finally:
-            if wd is not None and wd is not sample_weight:
-                wd.free()
         return self
 
     def set_labels(self, y):
@@ -115,49 +201,21 @@ class SVM:
         check(self.L.pmh_svm_train(self.h))
         return self
 
+    def _get_vec(self, entry):
+        self._need()
+        with _vecs(self.ctx, self.n) as (v,):
+            check(entry(self.h, v.p))
+            return v.to_numpy()
+
     @property
     def penalties(self):
         """The effective penalty C_i of every training sample (pmh_svm_get_penalties)."""
-        self._need()
-        v = Vec(self.ctx, self.n, zero=False)
-        check(self.L.pmh_svm_get_penalties(self.h, v.p))
-        c = v.to_numpy()
-        v.free()
-        return c
-
-    def _create(self, X, y):
-        self.destroy()
-        if is_sparse(X):
-            self.n, self.d = X.shape
-            Xd, yd = csr_from_scipy(self.ctx, X), self._dev(y)
-            h = ct.c_void_p()
-            try:
-                check(self.L.pmh_svm_create_csr(self.ctx.h, Xd.h, yd.p, self.opts, ct.byref(h)))
-            except Exception:
-                Xd.destroy(), yd.free()
-                raise
-            self.h, self._keep = h, (Xd, yd)
-            return self
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        self.n, self.d = X.shape
-        Xd, yd = self._dev(X), self._dev(y)
-        h = ct.c_void_p()
-        try:
-            check(self.L.pmh_svm_create(self.ctx.h, self.n, self.d, Xd.p, yd.p, self.opts, ct.byref(h)))
-        except Exception:
-            Xd.free(), yd.free()
-            raise
-        self.h, self._keep = h, (Xd, yd)
-        return self
+        return self._get_vec(self.L.pmh_svm_get_penalties)
 
     def fit(self, X, y, sample_weight=None):
         self.create(X, y, sample_weight)
         check(self.L.pmh_svm_train(self.h))
         return self
-
-    def _need(self):
-        if self.h is None:
-            raise RuntimeError("SVM: call fit first")
 
     @property
     def w(self):
@@ -175,12 +233,7 @@ class SVM:
 
     @property
     def alpha(self):
-        self._need()
-        v = Vec(self.ctx, self.n, zero=False)
-        check(self.L.pmh_svm_get_dual(self.h, v.p))
-        a = v.to_numpy()
-        v.free()
-        return a
+        return self._get_vec(self.L.pmh_svm_get_dual)
 
     @property
     def stats(self):
@@ -196,37 +249,19 @@ class SVM:
         check(self.L.pmh_svm_get_solver(self.h, *[ct.byref(x) for x in v]))
         return tuple(x if x.value else None for x in v)
 
-    def _predict(self, X, want_scores, want_labels):
+    def _test_samples(self, X):
+        """X for a scoring call: refused before any upload unless it is (n, d)."""
         self._need()
-        if is_sparse(X):
-            if X.shape[1] != self.d:
-                raise ValueError("SVM: X must be (n, %d)" % self.d)
-            n = X.shape[0]
-            Xd = csr_from_scipy(self.ctx, X)
-            s = Vec(self.ctx, n, zero=False) if want_scores else None
-            l = Vec(self.ctx, n, zero=False) if want_labels else None
-            try:
-                check(self.L.pmh_svm_predict_csr(self.h, Xd.h, s.p if s else None, l.p if l else None))
-                out = (s.to_numpy() if s else None, l.to_numpy() if l else None)
-            finally:
-                Xd.destroy()
-                for v in (s, l):
-                    if v is not None:
-                        v.free()
-            return out
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[1] != self.d:
+        S = _Samples(self.ctx, X)
+        if S.X.ndim != 2 or S.X.shape[1] != self.d:
             raise ValueError("SVM: X must be (n, %d)" % self.d)
-        n = X.shape[0]
-        Xd = self._dev(X)
-        s = Vec(self.ctx, n, zero=False) if want_scores else None
-        l = Vec(self.ctx, n, zero=False) if want_labels else None
-        check(self.L.pmh_svm_predict(self.h, n, Xd.p, s.p if s else None, l.p if l else None))
-        out = (s.to_numpy() if s else None, l.to_numpy() if l else None)
-        for v in (Xd, s, l):
-            if v is not None:
-                v.free()
-        return out
+        return S
+
+    def _predict(self, X, want_scores, want_labels):
+        S = self._test_samples(X)
+        with S as (n, xa), _vecs(self.ctx, n if want_scores else None, n if want_labels else None) as (s, l):
+            check(self._entry("predict", S.sparse)(self.h, *xa, s.p if s else None, l.p if l else None))
+            return (s.to_numpy() if s else None, l.to_numpy() if l else None)
 
     def decision_function(self, X):
         return self._predict(X, True, False)[0]
@@ -238,28 +273,12 @@ class SVM:
         """Fit the probability model of the trained handle on the samples X with labels y = +-1 (pmh_svm_calibrate): exactly platt_fit of
         decision_function(X).  train, set_labels and set_penalties clear it."""
         self._need()
-        yd = self._dev(y)
-        try:
-            if is_sparse(X):
-                if X.shape[1] != self.d or X.shape[0] != yd.n:
-                    raise ValueError("SVM: X must be (%d, %d)" % (yd.n, self.d))
-                Xd = csr_from_scipy(self.ctx, X)
-                try:
-                    check(self.L.pmh_svm_calibrate_csr(self.h, Xd.h, yd.p))
-                finally:
-                    Xd.destroy()
-            else:
-                X = np.ascontiguousarray(X, dtype=np.float64)
-                if X.ndim != 2 or X.shape[1] != self.d or X.shape[0] != yd.n:
-                    raise ValueError("SVM: X must be (%d, %d)" % (yd.n, self.d))
-                Xd = self._dev(X)
-                try:
-                    check(self.L.pmh_svm_calibrate(self.h, X.shape[0], Xd.p, yd.p))
-                finally:
-                    Xd.free()
-        finally:
-            if yd is not y:
-                yd.free()
+        with self._lent(y) as yd:
+            S = _Samples(self.ctx, X)
+            if S.X.ndim != 2 or S.X.shape[1] != self.d or S.X.shape[0] != yd.n:
+                raise ValueError("SVM: X must be (%d, %d)" % (yd.n, self.d))
+            with S as (n, xa):
+                check(self._entry("calibrate", S.sparse)(self.h, *xa, yd.p))
         return self
 
     def set_calibration(self, A, B):
@@ -286,77 +305,38 @@ class SVM:
 
     def predict_proba(self, X):
         """(n,): P(y = +1 | x_i) = 1 / (1 + exp(A decision_function(x_i) + B)), in one pass over X (pmh_svm_predict_proba)."""
-        self._need()
-        if is_sparse(X):
-            if X.shape[1] != self.d:
-                raise ValueError("SVM: X must be (n, %d)" % self.d)
-            Xd, p = csr_from_scipy(self.ctx, X), Vec(self.ctx, X.shape[0], zero=False)
-            try:
-                check(self.L.pmh_svm_predict_proba_csr(self.h, Xd.h, p.p))
-                return p.to_numpy()
-            finally:
-                Xd.destroy(), p.free()
-        X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise ValueError("SVM: X must be (n, %d)" % self.d)
-        Xd, p = self._dev(X), Vec(self.ctx, X.shape[0], zero=False)
-        try:
-            check(self.L.pmh_svm_predict_proba(self.h, X.shape[0], Xd.p, p.p))
+        S = self._test_samples(X)
+        with S as (n, xa), _vecs(self.ctx, n) as (p,):
+            check(self._entry("predict_proba", S.sparse)(self.h, *xa, p.p))
             return p.to_numpy()
-        finally:
-            Xd.free(), p.free()
 
     def test(self, X, y):
         """Confusion counts of the predicted labels against y: dict(TP, FP, TN, FN, accuracy)."""
         self._need()
         cnt = (ct.c_longlong * 4)()
-        if is_sparse(X):
-            n = X.shape[0]
-            Xd, yd = csr_from_scipy(self.ctx, X), self._dev(y)
+        S = _Samples(self.ctx, X)
+        with S as (n, xa):
+            yd = self._dev(y)
             try:
-                check(self.L.pmh_svm_test_csr(self.h, Xd.h, yd.p, cnt))
+                check(self._entry("test", S.sparse)(self.h, *xa, yd.p, cnt))
             finally:
-                Xd.destroy(), yd.free()
-        else:
-            X = np.ascontiguousarray(X, dtype=np.float64)
-            n = X.shape[0]
-            Xd, yd = self._dev(X), self._dev(y)
-            check(self.L.pmh_svm_test(self.h, n, Xd.p, yd.p, cnt))
-            Xd.free(), yd.free()
+                yd.free()  # (also the caller's own Vec)
         tp, fp, tn, fn = (int(c) for c in cnt)
         return dict(TP=tp, FP=fp, TN=tn, FN=fn, accuracy=(tp + tn) / n if n else float("nan"))
 
-    def destroy(self):
-        if self.h is not None:
-            self.L.pmh_svm_destroy(self.h)
-            self.h = None
-            for v in self._keep or ():
-                v.destroy() if hasattr(v, "destroy") else v.free()
-            self._keep = None
 
-
-class SVMMulticlass:
+class SVMMulticlass(_SVMHandle):
     """One-vs-rest linear SVM for two or more classes (pmh_svm_multi_*, csrc/svm_multi.hip).  The classes are the distinct labels, ascending; class k is trained
     against the rest on ONE binary handle over X (uploaded once; in CSR the operator's column-ordered copy is built once), which gives W (K, d) and b (K).
     Two classes train two classifiers: SVM is there for that case.  balanced: class k is trained with C_pos = C n / (2 n_k), C_neg = C n / (2 (n - n_k)).
     decision_function / predict score all K classes in one pass over X per chunk of classes (SVMMulticlass.chunk); the label is the class of the greatest score,
     ties to the lowest class.  X: (n, d) ndarray (d <= 256) or scipy.sparse, as in SVM.  One GPU."""
 
-    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", balanced=False):
-        self.ctx, self.L = ctx, ctx.L
-        o = _lib.SvmOpts()
-        check(self.L.pmh_svm_default_opts(o))
-        left = ct.create_string_buffer(4096)
-        check(self.L.pmh_svm_set_from_options(("-svm_loss_type %s -svm_C %r -svm_bias %d %s" % (loss, float(C), int(bool(bias)), options)).encode(), o, left, len(left)))
-        self.opts = o
-        self.options_left = [k for k in left.value.decode().split() if k]
-        self.balanced = bool(balanced)
-        self.h = None
-        self._keep = None
+    _who, _pre = "SVMMulticlass", "pmh_svm_multi_"
 
-    loss = property(lambda self: "L2" if self.opts.loss_type == 1 else "L1")
-    C = property(lambda self: self.opts.C)
-    bias = property(lambda self: bool(self.opts.bias))
+    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", balanced=False):
+        super().__init__(ctx, loss, C, bias, options)
+        self.balanced = bool(balanced)
 
     @staticmethod
     def chunk(path):
@@ -365,31 +345,9 @@ class SVMMulticlass:
         check(_lib.load().pmh_svm_multi_chunk(("dense64", "dense", "csr").index(path), ct.byref(kc)))
         return kc.value
 
-    def _dev(self, a):
-        return a if isinstance(a, Vec) else Vec.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.float64).ravel())
-
     def create(self, X, labels):
         """Set the training samples and find the classes, without training (then fit's train, or set_model)."""
-        self.destroy()
-        h = ct.c_void_p()
-        if is_sparse(X):
-            self.n, self.d = X.shape
-            Xd, ld = csr_from_scipy(self.ctx, X), self._dev(labels)
-            try:
-                check(self.L.pmh_svm_multi_create_csr(self.ctx.h, Xd.h, ld.p, self.opts, int(self.balanced), ct.byref(h)))
-            except Exception:
-                Xd.destroy(), ld.free()
-                raise
-        else:
-            X = np.ascontiguousarray(X, dtype=np.float64)
-            self.n, self.d = X.shape
-            Xd, ld = self._dev(X), self._dev(labels)
-            try:
-                check(self.L.pmh_svm_multi_create(self.ctx.h, self.n, self.d, Xd.p, ld.p, self.opts, int(self.balanced), ct.byref(h)))
-            except Exception:
-                Xd.free(), ld.free()
-                raise
-        self.h, self._keep = h, (Xd, ld)
+        self._create_handle(X, labels, int(self.balanced))
         k = ct.c_int()
         check(self.L.pmh_svm_multi_get_classes(self.h, ct.byref(k), None))
         self.K = k.value
@@ -402,10 +360,6 @@ class SVMMulticlass:
 
     def fit(self, X, labels):
         return self.create(X, labels).train()
-
-    def _need(self):
-        if self.h is None:
-            raise RuntimeError("SVMMulticlass: call fit first")
 
     @property
     def classes_(self):
@@ -458,63 +412,31 @@ class SVMMulticlass:
     def _run(self, X, want_scores, want_labels, labels_true=None):
         """predict (scores and / or labels) or, with labels_true, test: (scores, labels) or (confusion, n_unknown)."""
         self._need()
-        sparse = is_sparse(X)
-        if not sparse:
-            X = np.ascontiguousarray(X, dtype=np.float64)
-            if X.ndim != 2:
-                raise ValueError("SVMMulticlass: X must be (n, d)")
-        n = X.shape[0]
-        Xd = csr_from_scipy(self.ctx, X) if sparse else self._dev(X)
-        s = Vec(self.ctx, n * self.K, zero=False) if want_scores else None
-        l = Vec(self.ctx, n, zero=False) if want_labels else None
-        t = self._dev(labels_true) if labels_true is not None else None
-        try:
+        S = _Samples(self.ctx, X)
+        if S.X.ndim != 2:
+            raise ValueError("SVMMulticlass: X must be (n, d)")
+        with S as (n, xa), _vecs(self.ctx, n * self.K if want_scores else None, n if want_labels else None) as (s, l), self._lent(labels_true) as t:
+            if t is not None and t.n != n:
+                raise ValueError("SVMMulticlass: labels must have %d entries" % n)
+            if not S.sparse and S.X.shape[1] != self.d:  # (a sparse X of another width is the library's to refuse)
+                raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
             if t is not None:
-                if t.n != n:
-                    raise ValueError("SVMMulticlass: labels must have %d entries" % n)
                 conf, unk = np.zeros((self.K, self.K), dtype=np.int64), ct.c_longlong()
-                if sparse:
-                    check(self.L.pmh_svm_multi_test_csr(self.h, Xd.h, t.p, conf.ctypes.data_as(ct.c_void_p), ct.byref(unk)))
-                else:
-                    if X.shape[1] != self.d:
-                        raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
-                    check(self.L.pmh_svm_multi_test(self.h, n, Xd.p, t.p, conf.ctypes.data_as(ct.c_void_p), ct.byref(unk)))
+                check(self._entry("test", S.sparse)(self.h, *xa, t.p, conf.ctypes.data_as(ct.c_void_p), ct.byref(unk)))
                 return conf, int(unk.value)
-            if sparse:
-                check(self.L.pmh_svm_multi_predict_csr(self.h, Xd.h, s.p if s else None, l.p if l else None))
-            else:
-                if X.shape[1] != self.d:
-                    raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
-                check(self.L.pmh_svm_multi_predict(self.h, n, Xd.p, s.p if s else None, l.p if l else None))
+            check(self._entry("predict", S.sparse)(self.h, *xa, s.p if s else None, l.p if l else None))
             return (s.to_numpy().reshape(n, self.K) if s else None, l.to_numpy() if l else None)
-        finally:
-            Xd.destroy() if sparse else Xd.free()
-            for v in (s, l, t):
-                if v is not None and v is not labels_true:
-                    v.free()
 
     def calibrate(self, X, labels):
         """Fit the K probability models on the samples X with true labels (pmh_svm_multi_calibrate): model k is platt_fit of column k of decision_function(X)
         with "label == class k" as +1; a label that is no class counts among the rest.  train and set_model clear them."""
         self._need()
-        sparse = is_sparse(X)
-        if not sparse:
-            X = np.ascontiguousarray(X, dtype=np.float64)
-        ld = self._dev(labels)
-        try:
-            if X.ndim != 2 or X.shape[1] != self.d or X.shape[0] != ld.n:
+        S = _Samples(self.ctx, X)
+        with self._lent(labels) as ld:
+            if S.X.ndim != 2 or S.X.shape[1] != self.d or S.X.shape[0] != ld.n:
                 raise ValueError("SVMMulticlass: X must be (%d, %d)" % (ld.n, self.d))
-            Xd = csr_from_scipy(self.ctx, X) if sparse else self._dev(X)
-            try:
-                if sparse:
-                    check(self.L.pmh_svm_multi_calibrate_csr(self.h, Xd.h, ld.p))
-                else:
-                    check(self.L.pmh_svm_multi_calibrate(self.h, X.shape[0], Xd.p, ld.p))
-            finally:
-                Xd.destroy() if sparse else Xd.free()
-        finally:
-            if ld is not labels:
-                ld.free()
+            with S as (n, xa):
+                check(self._entry("calibrate", S.sparse)(self.h, *xa, ld.p))
         return self
 
     def set_calibration(self, A, B):
@@ -545,22 +467,12 @@ class SVMMulticlass:
     def predict_proba(self, X):
         """(n, K): sigma_ik = 1 / (1 + exp(A_k score_ik + B_k)), every row divided by its sum (a row of zeros: 1 / K); one pass over X per chunk of classes."""
         self._need()
-        sparse = is_sparse(X)
-        if not sparse:
-            X = np.ascontiguousarray(X, dtype=np.float64)
-        if X.ndim != 2 or X.shape[1] != self.d:
+        S = _Samples(self.ctx, X)
+        if S.X.ndim != 2 or S.X.shape[1] != self.d:
             raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
-        n = X.shape[0]
-        Xd, p = csr_from_scipy(self.ctx, X) if sparse else self._dev(X), Vec(self.ctx, n * self.K, zero=False)
-        try:
-            if sparse:
-                check(self.L.pmh_svm_multi_predict_proba_csr(self.h, Xd.h, p.p))
-            else:
-                check(self.L.pmh_svm_multi_predict_proba(self.h, n, Xd.p, p.p))
+        with S as (n, xa), _vecs(self.ctx, n * self.K) as (p,):
+            check(self._entry("predict_proba", S.sparse)(self.h, *xa, p.p))
             return p.to_numpy().reshape(n, self.K)
-        finally:
-            Xd.destroy() if sparse else Xd.free()
-            p.free()
 
     def decision_function(self, X):
         """(n, K): x_i . W_k + b_k."""
@@ -579,14 +491,6 @@ class SVMMulticlass:
         conf, unk = self._run(X, False, False, labels_true=labels)
         n = X.shape[0]
         return dict(accuracy=float(np.trace(conf)) / n if n else float("nan"), confusion=conf, n_unknown=unk)
-
-    def destroy(self):
-        if self.h is not None:
-            self.L.pmh_svm_multi_destroy(self.h)
-            self.h = None
-            for v in self._keep or ():
-                v.destroy() if hasattr(v, "destroy") else v.free()
-            self._keep = None
 
 
 def load_svmlight(path, n_features=None, zero_based="auto", multiclass=False):

@@ -7,25 +7,9 @@ import pytest
 import permon_amd as pa
 from permon_amd import problems as P
 from permon_amd._lib import check
+from svm_train_cases import solve as _solve
 
 pytestmark = pytest.mark.gpu
-
-
-def _solve(ctx, p, distributed=False, rtol=1e-6):
-    H = pa.MatCreateSVMDual(ctx, p["X"], p["y"])
-    qp = pa.QP(ctx)
-    qp.SetOperator(H)
-    qp.SetRhs(ctx.vec_from(p["b"]))
-    x = ctx.vec_from(p["x0"])
-    qp.SetInitialVector(x)
-    qp.SetBox(None, ctx.vec_from(p["lb"]), ctx.vec_from(p["ub"]))
-    qps = pa.QPS(ctx)
-    qps.SetQP(qp)
-    qps.SetType("mpgp")
-    qps.SetTolerances(rtol=rtol)
-    qps.MPGPSetDistributed(distributed)
-    st = qps.Solve()
-    return H, st, x.to_numpy()
 
 
 @pytest.mark.parametrize("N,d", [(3000, 64), (1111, 37), (500, 130)])

@@ -100,6 +100,8 @@ def test_one_vs_rest_equals_binary_fits(case, balanced):
         s = pa.SVM(ctx, loss, 1.0, True, OPT, C_pos=cp if balanced else None, C_neg=cn if balanced else None).fit(X, y)
         assert np.array_equal(W[k], s.w) and b[k] == s.b, (case, k)
         assert _counters(st[k]) == _counters(s.stats)
+        if sparse:  # both CSR scoring paths are one segmented sum (svm_csr_seg.h): equal models, equal products, one order of addition, b last -> equal bits
+            assert np.array_equal(m.decision_function(X)[:, k], s.decision_function(X)), (case, k)
         s.destroy()
     m.destroy()
     ctx.close()

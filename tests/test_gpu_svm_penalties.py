@@ -9,36 +9,10 @@ import pytest
 import permon_amd as pa
 from permon_amd import problems as P
 from permon_amd._lib import check
+from svm_train_cases import ASTOL, EPS, gamma, check_counts as _check_counts, np_model as _np_model
 
 pytestmark = pytest.mark.gpu
-EPS = np.finfo(float).eps
-ASTOL = 10 * EPS  # qpc.c:28
 PMH_ERR_ARG, PMH_ERR_STATE = 2, 3
-
-
-def gamma(k):  # tests/test_gpu_svm_train.py::gamma, restated (a test module is not imported from another)
-    """Higham's gamma_k = k eps / (1 - k eps): |fl(sum of k products) - exact| <= gamma_k sum |a_i v_i| for ANY order of summation of a k-term fp64 dot product."""
-    return k * EPS / (1.0 - k * EPS)
-
-
-def _np_model(p, a, loss, Ci):
-    """tests/test_gpu_svm_train.py::_np_model with the bound of every sample: free means astol < a_i and, for L1, a_i < C_i - astol."""
-    X, y = p["X"], p["y"]
-    w = X.T @ (y * a)
-    free = (a > ASTOL) & ((a < Ci - ASTOL) if loss == "L1" else True)
-    return w, float(np.mean(y[free] - X[free] @ w)), free
-
-
-def _check_counts(t, sc_np, yt, sure):
-    """The four counts against numpy's on the samples whose label the score decides beyond rounding: each library count lies between numpy's count on those samples
-    and that plus the number left out (equality where none is left out)."""
-    l_np = np.where(sc_np >= 0, 1.0, -1.0)
-    out = int((~sure).sum())
-    ref = dict(TP=(l_np > 0) & (yt > 0), FP=(l_np > 0) & (yt < 0), TN=(l_np < 0) & (yt < 0), FN=(l_np < 0) & (yt > 0))
-    assert t["TP"] + t["FP"] + t["TN"] + t["FN"] == yt.size
-    for k, m in ref.items():
-        c = int((m & sure).sum())
-        assert c <= t[k] <= c + out, (k, t[k], c, out)
 
 
 def _sparse_instance():

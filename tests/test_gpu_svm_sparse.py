@@ -15,17 +15,12 @@ import permon_amd as pa
 from permon_amd import _lib
 from permon_amd import problems as P
 from permon_amd._lib import check
+from svm_train_cases import ASTOL, EPS, gamma, check_counts as _check_counts, np_model as _np_model, oracle_train as _oracle_train, solve as _solve
 
 pytestmark = pytest.mark.gpu
-EPS = np.finfo(float).eps
-ASTOL = 10 * EPS  # qpc.c:28
 PMH_ERR_ARG = 2
 
 INST = dict(A=(4000, 5000, 30, 1.0, 0.5, 1.0), B=(4000, 300, 12, 1.2, 0.5, 1.0), C=(3000, 20000, 40, 0.8, 0.5, 10.0))
-
-
-def gamma(k):
-    return k * EPS / (1.0 - k * EPS)
 
 
 def _cmax_kmax(X):
@@ -157,33 +152,6 @@ def test_penalized_operator_folds_the_one_row_equality_sparse():
 
 
 # ---- 4. / 5. training against the oracle, the model, prediction ------------------------------------------------------------------------------------------------
-def _oracle_train(oracle, p, loss):
-    X, y, n = p["X"], p["y"], p["n"]
-    Xt = X.T.tocsr()
-    sh = 0.0 if loss == "L1" else 1.0 / p["C"]
-    op = oracle.Op(n, fn=lambda a: y * (X @ (Xt @ (y * a))) + sh * a)
-    pf = oracle.Qppf(oracle.Csr(1, n, [0, n], np.arange(n), y / np.sqrt(n)), orthonormal=True)
-    box = oracle.Box(n, lb=p["lb"], ub=p["ub"] if loss == "L1" else None)
-    return oracle.smalxe(op, p["b"], p["x0"], box, pf, rtol=1e-6, max_it=100)
-
-
-def _np_model(p, a, loss):
-    X, y = p["X"], p["y"]
-    w = X.T @ (y * a)
-    free = (a > ASTOL) & ((a < p["C"] - ASTOL) if loss == "L1" else True)
-    return w, float(np.mean(y[free] - X[free] @ w)), free
-
-
-def _check_counts(t, sc_np, yt, sure):
-    l_np = np.where(sc_np >= 0, 1.0, -1.0)
-    out = int((~sure).sum())
-    ref = dict(TP=(l_np > 0) & (yt > 0), FP=(l_np > 0) & (yt < 0), TN=(l_np < 0) & (yt < 0), FN=(l_np < 0) & (yt > 0))
-    assert t["TP"] + t["FP"] + t["TN"] + t["FN"] == yt.size
-    for k, m in ref.items():
-        c = int((m & sure).sum())
-        assert c <= t[k] <= c + out, (k, t[k], c, out)
-
-
 @pytest.mark.parametrize("loss", ["L1", "L2"])
 @pytest.mark.parametrize("name", ["A", "B", "C"])
 def test_biased_training_against_the_oracle_sparse(oracle, name, loss):
@@ -282,23 +250,6 @@ def test_sparse_model_predicts_dense_samples_and_back():
 
 
 # ---- 6. - 8. no bias: the plain MPGP solve; reproducibility; the one-rank communicator ---------------------------------------------------------------------
-def _solve(ctx, p, rtol=1e-6, distributed=False):
-    H = pa.MatCreateSVMDual(ctx, p["X"], p["y"])
-    qp = pa.QP(ctx)
-    qp.SetOperator(H)
-    qp.SetRhs(ctx.vec_from(p["b"]))
-    x = ctx.vec_from(p["x0"])
-    qp.SetInitialVector(x)
-    qp.SetBox(None, ctx.vec_from(p["lb"]), ctx.vec_from(p["ub"]))
-    qps = pa.QPS(ctx)
-    qps.SetQP(qp)
-    qps.SetType("mpgp")
-    qps.SetTolerances(rtol=rtol)
-    qps.MPGPSetDistributed(distributed)
-    st = qps.Solve()
-    return H, st, x.to_numpy()
-
-
 def test_unbiased_l1_fit_is_the_plain_mpgp_solve_sparse():
     ctx = pa.Context(0)
     p = P.svm_sparse(*INST["A"])

@@ -13,33 +13,10 @@ import permon_amd as pa
 from permon_amd import _lib
 from permon_amd import problems as P
 from permon_amd._lib import check
+from svm_train_cases import ASTOL, EPS, gamma, check_counts as _check_counts, np_model as _np_model, oracle_train as _oracle_train, solve as _solve
 
 pytestmark = pytest.mark.gpu
-EPS = np.finfo(float).eps
-ASTOL = 10 * EPS  # qpc.c:28
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def gamma(k):
-    """Higham's gamma_k = k eps / (1 - k eps): |fl(sum of k products) - exact| <= gamma_k sum |a_i v_i| for ANY order of summation of a k-term fp64 dot product."""
-    return k * EPS / (1.0 - k * EPS)
-
-
-def _solve(ctx, p, rtol=1e-6):  # tests/test_gpu_svm.py::_solve, restated (a test module is not imported from another)
-    H = pa.MatCreateSVMDual(ctx, p["X"], p["y"])
-    qp = pa.QP(ctx)
-    qp.SetOperator(H)
-    qp.SetRhs(ctx.vec_from(p["b"]))
-    x = ctx.vec_from(p["x0"])
-    qp.SetInitialVector(x)
-    qp.SetBox(None, ctx.vec_from(p["lb"]), ctx.vec_from(p["ub"]))
-    qps = pa.QPS(ctx)
-    qps.SetQP(qp)
-    qps.SetType("mpgp")
-    qps.SetTolerances(rtol=rtol)
-    qps.MPGPSetDistributed(False)
-    st = qps.Solve()
-    return H, st, x.to_numpy()
 
 
 # ---- 1. the one-row projector against the same row as a 1 x n CSR ------------------------------------------------------------------------------------------
@@ -236,34 +213,6 @@ def test_unbiased_l1_fit_is_the_existing_solve():
 
 
 # ---- 4. - 6. biased training ------------------------------------------------------------------------------------------------------------------------------------
-def _oracle_train(oracle, p, loss):
-    X, y, n = p["X"], p["y"], p["n"]
-    sh = 0.0 if loss == "L1" else 1.0 / p["C"]
-    op = oracle.Op(n, fn=lambda a: y * (X @ (X.T @ (y * a))) + sh * a)
-    pf = oracle.Qppf(oracle.Csr(1, n, [0, n], np.arange(n), y / np.sqrt(n)), orthonormal=True)
-    box = oracle.Box(n, lb=p["lb"], ub=p["ub"] if loss == "L1" else None)
-    return oracle.smalxe(op, p["b"], p["x0"], box, pf, rtol=1e-6, max_it=100)
-
-
-def _np_model(p, a, loss):
-    X, y = p["X"], p["y"]
-    w = X.T @ (y * a)
-    free = (a > ASTOL) & ((a < p["C"] - ASTOL) if loss == "L1" else True)
-    return w, float(np.mean(y[free] - X[free] @ w)), free
-
-
-def _check_counts(t, sc_np, yt, sure):
-    """The four counts against numpy's on the samples whose label the score decides beyond rounding: each library count lies between numpy's count on those samples
-    and that plus the number left out (equality where none is left out)."""
-    l_np = np.where(sc_np >= 0, 1.0, -1.0)
-    out = int((~sure).sum())
-    ref = dict(TP=(l_np > 0) & (yt > 0), FP=(l_np > 0) & (yt < 0), TN=(l_np < 0) & (yt < 0), FN=(l_np < 0) & (yt > 0))
-    assert t["TP"] + t["FP"] + t["TN"] + t["FN"] == yt.size
-    for k, m in ref.items():
-        c = int((m & sure).sum())
-        assert c <= t[k] <= c + out, (k, t[k], c, out)
-
-
 @pytest.mark.parametrize("loss", ["L1", "L2"])
 def test_biased_training_against_the_oracle(oracle, loss):
     """svm_offset(4000, 64, 3.0), rtol 1e-6, at most 100 outer iterations (the CPU oracle needs 27 for L1 and 19 for L2).  Then, from the returned dual solution
