@@ -889,6 +889,22 @@ int pmh_mv_test_spmv(pmh_csr A, int storage, const double *x, double *y, int rep
 int pmh_csr_kernel_info(pmh_csr A, int info[6], unsigned long long *uid);
 int pmh_csr_test_mult_epi(pmh_csr A, int kind, const double *x, const double *y1, const double *g, const double *xx, const double *lb, const double *ub, int halt, double *y,
                           double scal_host[3]);
+/* ---- 3x3-block product test entries (csrc/bsr.hip: the conversion as the V-cycle and K^+ call it, and one launch of k_bsr3; nothing inside the solvers changes) ----
+ * pmh_bsr3_test_create: the 3x3-block device copy of the square CSR A with entries kept in `storage` (0 fp64, 1 fp32, 2 fp16 scaled by a power of two, fp32
+ * arithmetic), tiles of `tile` blocks (512; any other value: 1024) and nrep_hint congruent diagonal blocks (believed only after an entry-by-entry comparison).
+ * *B = NULL with PMH_SUCCESS where the conversion declines: n == 0 or n % 3 != 0, a block row with more blocks than a tile, blocks mostly empty
+ * (9 nblocks > 2 nnz + 64).
+ * pmh_bsr3_test_info: info = {n, block rows, tiles, blocks per tile (512 / 1024), replicas, blocks, padded blocks, W = blocks per vector load (2 fp64, 4 fp32 / fp16)};
+ * block rows, tiles, blocks and padded blocks describe ONE replica.  *scale (or NULL): the fp16 scale (1 otherwise; 1 for a matrix without entries).
+ * pmh_bsr3_test_mult_epi: one launch with the epilogue `epi` on device vectors of n entries -- double for fp64 storage, float otherwise (z64: always double):
+ *   0 NONE y = A x;  1 ADD y = y1 + A x;  2 SUB y = A x - y1;  10 PRE y = c0 x + c2 dinv (y1 - A x);  11 POST1 r = dinv (y1 - A x), d = c0 r, y = x + d;
+ *   12 POST2 y += c1 x + c2 (r - dinv A x), z64 (or NULL) = (double)y.
+ * halt != 0: the launch sees a device flag set to 1 and changes nothing.  Synchronises.  PMH_ERR_ARG for an operand the epilogue needs and does not get, and for
+ * y (POST1: also r, d; POST2: also z64) == x: no variant may write the vector it gathers from. */
+int pmh_bsr3_test_create(pmh_csr A, int storage, int tile, int nrep_hint, void **B);
+int pmh_bsr3_test_info(void *B, long long info[8], double *scale);
+int pmh_bsr3_test_mult_epi(void *B, int epi, const void *x, void *y, const void *y1, const void *dinv, void *r, void *d, double *z64, double c0, double c1, double c2, int halt);
+int pmh_bsr3_test_destroy(void *B);
 /* U = K^+ F for 8 columns per block at once: F, U device arrays of 8 n doubles, entry (dof i, column r) at i * 8 + r; K, the V-cycle (pmh_matinv_set_pc_mg), the kernel
  * basis (pmh_matinv_set_nullspace: K^+ = P_R K^- P_R) and the tolerances are the solver's own; every (block, column) pair converges by its own test.  PMH_ERR_SUP where
  * the multi-right-hand-side kernels do not apply (K without regular 3 x 3 blocks, a V-cycle other than the fused fp32 one, the left generalised inverse). */

@@ -328,6 +328,10 @@ _PROTOS = {
     "pmh_mv_test_spmv": [vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_float)],
     "pmh_csr_kernel_info": [vp, c_int_p, C.POINTER(C.c_ulonglong)],
     "pmh_csr_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, c_double_p],
+    "pmh_bsr3_test_create": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
+    "pmh_bsr3_test_info": [vp, C.POINTER(C.c_longlong), c_double_p],
+    "pmh_bsr3_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int],
+    "pmh_bsr3_test_destroy": [vp],
     "pmh_matinv_mult_multi": [vp, vp, vp, c_int_p],
     "pmh_matinv_multi_rhs_active": [vp, c_int_p],
     "pmh_fexplicit_assemble_auto": [vp, vp, vp, vp, C.c_double, C.c_int, c_int_p],

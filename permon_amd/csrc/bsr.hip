@@ -320,7 +320,7 @@ int pmh_bsr3_from_csr(pmh_csr A, int storage, pmh_bsr3 *out, int tile, int nrep_
     // power-of-two scale that brings the largest entry to [1, 2): entries below 2^-24 of it flush to zero
     int ex = 0;
     if (amax > 0.0) frexp(amax, &ex);
-    B->scale = ldexp(1.0, ex - 1);
+    B->scale = amax > 0.0 ? ldexp(1.0, ex - 1) : 1.0; // (no entry at all: 1, not the 2^-1 of ex = 0)
     const double               sc = B->scale;
     std::unique_ptr<_Float16[]> bh(new _Float16[nbv + 1]);
     threaded([&](size_t i0, size_t i1) {
@@ -447,6 +447,63 @@ int pmh_bsr3_spmv_f32(pmh_bsr3 B, const float *x, float *y, int epi, const float
   e.y1 = y1;
   return pmh_bsr3_spmv_epi_f32(B, x, y, epi, e, halt);
 }
+
+// ---- test entries (tests/test_gpu_bsr3_paths.py): the conversion as mg.hip and feti.hip call it, what it laid out, and one launch with a given epilogue; nothing
+// inside the solvers calls them ----
+extern "C" int pmh_bsr3_test_create(pmh_csr A, int storage, int tile, int nrep_hint, void **B)
+{
+  PMH_ARG(A && B);
+  pmh_bsr3 b = nullptr;
+  *B         = nullptr;
+  PMH_CHK(pmh_bsr3_from_csr(A, storage, &b, tile, nrep_hint));
+  *B = b;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_bsr3_test_info(void *B_, long long info[8], double *scale)
+{
+  pmh_bsr3 B = (pmh_bsr3)B_;
+  PMH_ARG(B && info);
+  info[0] = B->n, info[1] = B->nbr, info[2] = B->ntiles, info[3] = B->tb, info[4] = B->nrep, info[5] = B->nblocks, info[6] = B->npad;
+  info[7] = B->storage == PMH_BSR_F64 ? bsr_w<double> : B->storage == PMH_BSR_F32 ? bsr_w<float> : bsr_w<_Float16>;
+  if (scale) *scale = B->scale;
+  return PMH_SUCCESS;
+}
+
+template <typename T>
+static int bsr3_test_launch(pmh_bsr3 B, int epi, const void *x, void *y, const void *y1, const void *dinv, void *r, void *d, double *z64, double c0, double c1, double c2, const int *halt)
+{
+  pmh_bsr3_epi<T> e;
+  memset(&e, 0, sizeof(e));
+  e.y1 = (const T *)y1, e.dinv = (const T *)dinv, e.r = (T *)r, e.d = (T *)d, e.z64 = z64, e.c0 = (T)c0, e.c1 = (T)c1, e.c2 = (T)c2;
+  if constexpr (sizeof(T) == 8) return pmh_bsr3_spmv_epi_f64(B, (const T *)x, (T *)y, epi, e, halt);
+  else return pmh_bsr3_spmv_epi_f32(B, (const T *)x, (T *)y, epi, e, halt);
+}
+
+extern "C" int pmh_bsr3_test_mult_epi(void *B_, int epi, const void *x, void *y, const void *y1, const void *dinv, void *r, void *d, double *z64, double c0, double c1, double c2, int halt)
+{
+  pmh_bsr3 B = (pmh_bsr3)B_;
+  PMH_ARG(B && x && y);
+  PMH_ARG(epi == PMH_EPI_NONE || epi == PMH_EPI_ADD || epi == PMH_EPI_SUB || epi == PMH_BSR_EPI_PRE || epi == PMH_BSR_EPI_POST1 || epi == PMH_BSR_EPI_POST2);
+  PMH_ARG(x != (const void *)y); // no variant may write the vector it gathers from
+  PMH_ARG((epi != PMH_EPI_ADD && epi != PMH_EPI_SUB) || y1);
+  PMH_ARG(epi != PMH_BSR_EPI_PRE || (y1 && dinv));
+  PMH_ARG(epi != PMH_BSR_EPI_POST1 || (y1 && dinv && r && d && x != (const void *)r && x != (const void *)d));
+  PMH_ARG(epi != PMH_BSR_EPI_POST2 || (dinv && r && x != (const void *)z64));
+  pmh_ctx ctx    = B->ctx;
+  int    *d_halt = nullptr;
+  if (halt) {
+    const int one = 1;
+    PMH_CHK(pmh_malloc(ctx, sizeof(int), (void **)&d_halt));
+    PMH_CHK(pmh_memcpy_h2d(ctx, d_halt, &one, sizeof(int)));
+  }
+  int rc = B->storage == PMH_BSR_F64 ? bsr3_test_launch<double>(B, epi, x, y, y1, dinv, r, d, z64, c0, c1, c2, d_halt) : bsr3_test_launch<float>(B, epi, x, y, y1, dinv, r, d, z64, c0, c1, c2, d_halt);
+  if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_bsr3_test_mult_epi: stream synchronisation failed");
+  if (d_halt) pmh_free(ctx, d_halt);
+  return rc;
+}
+
+extern "C" int pmh_bsr3_test_destroy(void *B) { return pmh_bsr3_destroy((pmh_bsr3)B); }
 
 int pmh_bsr3_timing_enable(pmh_bsr3 B, int max_launches)
 {
