@@ -485,6 +485,15 @@ int pmh_op_create_svm_dual_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, pmh_
    place, every stored value times y_i(old) y_i(new) = +-1 from the signs the operator keeps itself -- 8 n_local bytes more beside the copy -- so the copy
    equals, bit for bit, the one a fresh operator builds.  Terms and diagonal stay as set */
 int pmh_op_svm_dual_set_labels(pmh_op op, const double *y_dev /* n_local doubles, borrowed */);
+/* A sample subset S on a created operator (dense rows or CSR): H_S = M (H + D) M with M = diag(m), D the scalar shift or the diagonal, i.e.
+     out_i = m_i [ y_i (x_i . w) + sigma s y_i + D_i v_i ],  w = sum_{j in S} y_j v_j x_j,  s = sum_{j in S} y_j v_j.
+   m_dev: n_local doubles on the device, each exactly 0 or 1, read during the call only (the operator keeps a copy and the masked labels m o y: 16 n_local bytes);
+   NULL: all samples, the plain operator again.  Any other entry (a NaN is one) is PMH_ERR_ARG with the count, an all-zero mask (over all ranks) too; a refused
+   mask changes nothing.  Held-out rows of the result are exactly 0, shift or diagonal included; held-out entries of v have no effect whatever they hold.  The
+   subset survives pmh_op_svm_dual_set_labels, _set_terms and _set_diag; prepared sums of the paired passes are dropped.  Dense rows: a held-out row of X is not
+   read at all (the kernels' SUB instances read the masked label first), in both passes, the paired passes and the ||B u|| rider, which all stay in use; CSR:
+   every stored entry is still swept (no row skipping), one n-vector kernel masks the operand before pass 1 */
+int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev /* n_local doubles of 0 / 1, or NULL = all */);
 
 /* ---- QPS SMALXE (src/qps/impls/smalxe/smalxe.c) -------------------------------------------------------- */
 typedef struct {
@@ -594,7 +603,7 @@ int pmh_svm_get_solver(pmh_svm svm, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh
  * Free support vectors (the bias) are counted against C_i.  Call it after create, and again between trainings at will (pmh_svm_train starts from a = 0); the
  * handle is untrained afterwards and its solver is built anew, so handles from pmh_svm_get_solver must be fetched again.  weight_dev: n_local doubles on the
  * device, copied, or NULL = all 1.  C_pos / C_neg not positive and finite: PMH_ERR_ARG naming the value.  Weights that are not positive and finite (zero
- * included: masking samples out is not supported): PMH_ERR_ARG saying how many, counted on the device, over all ranks.  Nothing is exchanged in training
+ * included: a weight does not leave a sample out, pmh_svm_set_subset does): PMH_ERR_ARG saying how many, counted on the device, over all ranks.  Nothing is exchanged in training
  * that was not before: the bounds and the diagonal are local vectors */
 int pmh_svm_set_penalties(pmh_svm svm, double C_pos, double C_neg, const double *weight_dev /* n_local doubles or NULL = all 1; copied */);
 /* the effective C_i (n_local doubles, device); opts.C everywhere if pmh_svm_set_penalties was never called */
@@ -606,6 +615,23 @@ int pmh_svm_get_penalties(pmh_svm svm, double *c_dev /* n_local */);
  * pmh_svm_get_solver must be fetched again).  A training afterwards gives alpha, w, b and every counter of the statistics identical to those of a fresh handle
  * created on (X, y_dev) with the same options.  Allowed under a communicator: nothing is collective beyond what create does */
 int pmh_svm_set_labels(pmh_svm svm, const double *y_dev /* n_local doubles, borrowed */);
+/* Train on a subset S of the handle's samples and score the held-out rows, X staying where it is (no upload, no new column-ordered copy).  m_dev as in
+ * pmh_op_svm_dual_set_subset (copied; NULL: all samples again).  Over S only: the operator's subset, rhs = m, the equality's row m o y / sqrt(n_S) (n_S summed
+ * over the ranks as n is), L2 the diagonal m_i / C_i in place of the shift; L1 keeps its bounds C_i.  The solver is built anew (as by pmh_svm_set_penalties),
+ * the handle is untrained and uncalibrated afterwards; a refused mask (PMH_ERR_ARG) leaves the handle as it was.  pmh_svm_set_labels and pmh_svm_set_penalties
+ * keep the subset.  After pmh_svm_train alpha is exactly 0 on the held-out rows and w, b, n_sv, n_free_sv are those of training on (X[S], y[S]) alone */
+int pmh_svm_set_subset(pmh_svm svm, const double *m_dev /* n_local doubles of 0 / 1, or NULL = all */);
+/* the mask (n_local doubles, device; all 1 without a subset; may be NULL) and n_S over all ranks (n without a subset; may be NULL) */
+int pmh_svm_get_subset(pmh_svm svm, double *m_dev, long long *n_in);
+/* Scores and labels of ALL n_local samples the handle was created on, held-out ones included, by the sweep of pmh_svm_predict(_csr) over the handle's own X
+   (CSR: with the tables the operator holds): the same bits as pmh_svm_predict on an uploaded copy.  Either pointer may be NULL */
+int pmh_svm_predict_own(pmh_svm svm, double *scores_dev, double *labels_dev);
+/* (TP, FP, TN, FN) of the handle's own samples against its labels, over the rows `which` selects, in one sweep (fixed order, no float atomics).
+   PMH_SVM_OWN_HELD_OUT without a subset: PMH_ERR_STATE; PMH_SVM_OWN_SUBSET without a subset: all rows */
+#define PMH_SVM_OWN_HELD_OUT 0
+#define PMH_SVM_OWN_SUBSET 1
+#define PMH_SVM_OWN_ALL 2
+int pmh_svm_test_own(pmh_svm svm, int which, long long counts[4]);
 /* one pass over the n samples of X_dev: scores_dev[i] = x_i . w + b, labels_dev[i] = +-1 (either may be NULL) */
 int pmh_svm_predict(pmh_svm svm, int n, const double *X_dev, double *scores_dev, double *labels_dev);
 /* one pass: counts = (TP, FP, TN, FN) of the predicted labels against y_dev (summed over the ranks under a communicator) */

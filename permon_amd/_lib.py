@@ -276,6 +276,11 @@ _PROTOS = {
     "pmh_svm_destroy": [vp],
     "pmh_op_svm_dual_set_labels": [vp, vp],
     "pmh_svm_set_labels": [vp, vp],
+    "pmh_op_svm_dual_set_subset": [vp, vp],
+    "pmh_svm_set_subset": [vp, vp],
+    "pmh_svm_get_subset": [vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_predict_own": [vp, vp, vp],
+    "pmh_svm_test_own": [vp, C.c_int, C.POINTER(C.c_longlong)],
     "pmh_svm_multi_chunk": [C.c_int, c_int_p],
     "pmh_svm_multi_create": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvmOpts), C.c_int, C.POINTER(vp)],
     "pmh_svm_multi_create_csr": [vp, vp, vp, C.POINTER(SvmOpts), C.c_int, C.POINTER(vp)],

@@ -14,7 +14,9 @@
 
 // pass 1: per-workgroup partial of w = sum_i (y_i a_i) x_i ; one wavefront per row, lane j owns columns j, j+64, ...
 // AUG: also s = sum_i y_i a_i (-> spart[workgroup]) and, where u is given, sum_i y_i u_i (-> upart[workgroup]); every lane of a wave holds the same two sums
-template <int AUG>
+// SUB (every kernel below that has it): y holds the masked labels m_i y_i of a sample subset (pmh_op_svm_dual_set_subset); it is read first, and a held-out row
+// (y_i == 0) is not loaded and adds to no sum, whatever a_i holds.  SUB = 0: the kernels without subsets
+template <int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
                                                       double *__restrict__ spart, const double *__restrict__ u, double *__restrict__ upart)
 {
@@ -27,6 +29,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double
 #pragma unroll
   for (int k = 0; k < SVM_KMAX; k++) acc[k] = 0.0;
   for (long long i = gw; i < n; i += nw) {
+    if (SUB && y[i] == 0.0) continue; // (uniform over the wave)
     const double  s  = y[i] * a[i];
     const double *xr = X + (size_t)i * d;
     if (AUG) {
@@ -74,12 +77,13 @@ static __device__ __forceinline__ void svm_colsum(int nblocks, int d, const doub
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart) { svm_colsum(nblocks, d, part, w, spart); }
 
 // pass 2: (H a)_i = y_i (x_i . w); AUG 1: + sigma s y_i + shift a_i; AUG 2: + sigma s y_i + diag_i a_i
-template <int AUG>
+template <int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
                                                      const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[d] : 0.0;
-  svm_sweep_rows(n, d, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
+  if (SUB) svm_sweep_rows<1>(n, d, X, w, [&](long long i, double s) { Ha[i] = y[i] == 0.0 ? 0.0 : (AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s); }, y);
+  else svm_sweep_rows(n, d, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
 }
 
 // ---- d == 64 fast path: the two-rows-per-wave-instruction layout of svm_rows.h, 4-fold unroll ----
@@ -102,7 +106,7 @@ static __device__ __forceinline__ void svm_fold_cols(double a0, double a1, doubl
     part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
   }
 }
-template <int SVM_UNR, int AUG>
+template <int SVM_UNR, int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
                                                         double *__restrict__ spart, const double *__restrict__ uu, double *__restrict__ upart)
 {
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__r
 #pragma unroll
     for (int u = 0; u < SVM_UNR; u++) {
       const long long i = r0 + 2 * u + half;
-      const bool      ok = i < n;
+      const bool      ok = i < n && (!SUB || y[i] != 0.0);
       v[u] = ok ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
       s[u] = ok ? y[i] * a[i] : 0.0;
       if (AUG && l2 == 0) {
@@ -142,12 +146,13 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__r
   }
 }
 
-template <int SVM_UNR, int AUG>
+template <int SVM_UNR, int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
                                                        const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[64] : 0.0;
-  svm_sweep_rows64<SVM_UNR>(n, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
+  if (SUB) svm_sweep_rows64<SVM_UNR, 1>(n, X, w, [&](long long i, double s) { Ha[i] = y[i] == 0.0 ? 0.0 : (AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s); }, y);
+  else svm_sweep_rows64<SVM_UNR>(n, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
 }
 
 // ---- paired passes -------------------------------------------------------------------------------------------------------------------------
@@ -176,7 +181,7 @@ struct svm_grad_args {
 };
 // pass 2 of g = H x - b with the gradient split, p = gf, the partial sums of (0, |gP|^2, |gc|^2, |gf|^2), QPCFeas(x, p) and X'(y o p)
 #define SVM_EU 4
-template <int AUG>
+template <int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_grad_args a)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
@@ -187,8 +192,10 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
   const double      sS = AUG ? a.sigma * w[64] : 0.0;
   double            a0 = 0.0, a1 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, m = INFINITY, ts = 0.0;
   for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
-    dbl2 v[SVM_EU];
-    svm_load_rows64<SVM_EU>(n, X, r0, v);
+    dbl2   v[SVM_EU];
+    double ym = 0.0; // SUB: the row's masked label, read before the rows: a held-out row is not loaded
+    if (SUB) svm_load_rows64<SVM_EU, SUB>(n, X, r0, v, svm_live_rows64<SVM_EU>(n, y, r0, ym));
+    else svm_load_rows64<SVM_EU>(n, X, r0, v);
     // the rows' dot products land in the first lane of each half-wave; lane j < 2 SVM_EU takes row r0 + j (u = j >> 1, half = j & 1): ONE coalesced load per
     // vector for the 2 SVM_EU rows (a load per row costs the address unit a whole instruction each: measured 2 x the time of the plain pass), asked for before
     // the dot products so that they travel with the rows of X, the elementwise work once
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
     const bool      act = lane < 2 * SVM_EU && i < n;
     double          yi = 0.0, xi = 0.0, bi = 0.0, li = -INFINITY, ui = INFINITY, sh = AUG == 1 ? a.shift : 0.0;
     if (act) {
-      yi = y[i], xi = a.x_in[i], bi = a.b[i];
+      yi = SUB ? ym : y[i], xi = a.x_in[i], bi = a.b[i];
       if (AUG == 2) sh = a.diag[i];
       if (a.lb) li = a.lb[i];
       if (a.ub) ui = a.ub[i];
@@ -204,7 +211,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
     const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
     double t = 0.0; // y_i p_i: the row's weight in X'(y o p)
     if (act) {
-      const double gi = (AUG ? svm_aug_row(yi, sm, sS, sh, xi) : yi * sm) - bi;
+      const double gi = ((SUB && yi == 0.0) ? 0.0 : (AUG ? svm_aug_row(yi, sm, sS, sh, xi) : yi * sm)) - bi;
       double       f, c;
       pmh_box_split_v(xi, gi, li, ui, a.astol, f, c);
       a.g[i] = gi, a.gf[i] = f, a.p[i] = f;
@@ -247,7 +254,7 @@ struct svm_p1_args {
   const double *diag; // AUG 2: the diagonal, in place of shift
 };
 // pass 2 of Ap = H p with the partial sums of p'Ap, g'p, QPCFeas(x, p); SPEC: + the iterate of the expansion step and X'(y o x+)
-template <int SPEC, int AUG>
+template <int SPEC, int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_p1_args a)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
@@ -259,14 +266,16 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
   const double      sS = AUG ? a.sigma * w[64] : 0.0;
   double            a0 = 0.0, a1 = 0.0, s0 = 0.0, s1 = 0.0, m = INFINITY, ts = 0.0, sux = 0.0;
   for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
-    dbl2 v[SVM_EU];
-    svm_load_rows64<SVM_EU>(n, X, r0, v);
+    dbl2   v[SVM_EU];
+    double ym = 0.0;
+    if (SUB) svm_load_rows64<SVM_EU, SUB>(n, X, r0, v, svm_live_rows64<SVM_EU>(n, y, r0, ym));
+    else svm_load_rows64<SVM_EU>(n, X, r0, v);
     // (as in k_svm_x64_grad: lane j < 2 SVM_EU takes row r0 + j, its scalars asked for up front)
     const long long i   = r0 + lane;
     const bool      act = lane < 2 * SVM_EU && i < n;
     double          yi = 0.0, pi = 0.0, gi = 0.0, xi = 0.0, li = -INFINITY, ui = INFINITY, sh = AUG == 1 ? a.shift : 0.0;
     if (act) {
-      yi = y[i], pi = a.p[i], gi = a.g[i], xi = a.x[i];
+      yi = SUB ? ym : y[i], pi = a.p[i], gi = a.g[i], xi = a.x[i];
       if (AUG == 2) sh = a.diag[i];
       if (a.lb) li = a.lb[i];
       if (a.ub) ui = a.ub[i];
@@ -274,9 +283,9 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
     const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
     double t = 0.0; // y_i x+_i: the row's weight in X'(y o x+)
     if (act) {
-      const double api = AUG ? svm_aug_row(yi, sm, sS, sh, pi) : yi * sm;
+      const double api = (SUB && yi == 0.0) ? 0.0 : (AUG ? svm_aug_row(yi, sm, sS, sh, pi) : yi * sm);
       a.Ap[i] = api;
-      if (AUG) sux += yi * xi;
+      if (AUG && (!SUB || yi != 0.0)) sux += yi * xi;
       s0 += pi * api, s1 += gi * pi;
       m = pmh_box_feas_v(m, xi, pi, li, ui);
       if (SPEC) { // k_expansion_std (mpgp.hip) on this entry
@@ -359,28 +368,31 @@ static int svm_aux_ready(SvmDualOp *o, bool aug, bool *ok)
 // hands the AUG = 0 kernels null pointers: the kernels of the plain operator, the bits of the plain operator
 int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
 {
-  double *sp = aug ? spart : nullptr;
+  double       *sp = aug ? spart : nullptr;
+  const double *y  = yk(); // (the masked labels under a subset, with the SUB kernels)
   // d == 64: rows in flight per wave-instruction group: 2 x UNR rows of 512 B (16-byte loads, UNR of them outstanding per lane).  UNR decides which wave visits
   // which rows, i.e. the summation order of pass 1 (last-digit differences between UNR values; fixed for a given UNR).  Measured 4 / 8 / 12 / 16 on configs[4]:
   // 464 / 452-488 / 433 / 487 iterations per second -- inside the run-to-run spread of the box (the two passes already stream X at the box's copy rate): 4 stays,
   // and only that instance is compiled
-  if (d == 64) SVM_PASS((aug ? k_svm_xt64<4, 1> : k_svm_xt64<4, 0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, sp, u, upart);
-  else SVM_PASS((aug ? k_svm_xt<1> : k_svm_xt<0>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, v, part, sp, u, upart);
+  if (d == 64) SVM_PASS((ym ? (aug ? k_svm_xt64<4, 1, 1> : k_svm_xt64<4, 0, 1>) : (aug ? k_svm_xt64<4, 1, 0> : k_svm_xt64<4, 0, 0>)), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, sp, u, upart);
+  else SVM_PASS((ym ? (aug ? k_svm_xt<1, 1> : k_svm_xt<0, 1>) : (aug ? k_svm_xt<1, 0> : k_svm_xt<0, 0>)), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, v, part, sp, u, upart);
   hipLaunchKernelGGL(k_svm_colsum, dim3((d + (aug ? 1 : 0) + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)sp);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
 // pass 2: out_i = y_i (x_i . w), augmented + (sigma + sigma_fold) w[d] y_i + shift a_i (or + diag_i a_i)
-#define SVM_K_X64(A) k_svm_x64<4, A>
-#define SVM_K_X(A) k_svm_x<A>
-#define SVM_K_GRAD(A) k_svm_x64_grad<A>
-#define SVM_K_P1(A) k_svm_x64_p1<0, A>
-#define SVM_K_P1_SPEC(A) k_svm_x64_p1<1, A>
+// (ym: the operator's masked labels, set under a subset: the SUB = 1 instances)
+#define SVM_K_X64(A) (ym ? k_svm_x64<4, A, 1> : k_svm_x64<4, A, 0>)
+#define SVM_K_X(A) (ym ? k_svm_x<A, 1> : k_svm_x<A, 0>)
+#define SVM_K_GRAD(A) (ym ? k_svm_x64_grad<A, 1> : k_svm_x64_grad<A, 0>)
+#define SVM_K_P1(A) (ym ? k_svm_x64_p1<0, A, 1> : k_svm_x64_p1<0, A, 0>)
+#define SVM_K_P1_SPEC(A) (ym ? k_svm_x64_p1<1, A, 1> : k_svm_x64_p1<1, A, 0>)
 int SvmDualOp::pass2(const double *a, double *out, bool aug)
 {
   const double *ap = aug ? a : nullptr;
   const double  sg = aug ? sigma + sigma_fold : 0.0, sh = aug ? shift : 0.0;
   const int     form = aug ? aug_form() : 0;
+  const double *y    = yk();
   if (d == 64) SVM_PASS(SVM_AUG_PICK(form, SVM_K_X64), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, out, ap, sg, sh, diag);
   else SVM_PASS(SVM_AUG_PICK(form, SVM_K_X), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, out, ap, sg, sh, diag);
   PMH_HIP(hipGetLastError());
@@ -409,6 +421,7 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
   const double  sg  = sigma + sigma_fold;
   const double *spn = AG ? spart_next : nullptr;
   const size_t  nw  = AG ? 65 : 64;
+  const double *y   = yk();
   int           have = next_is;
   if (next_aug != AG) have = NEXT_NONE; // (sums prepared by the other form lack / carry the 65th column)
   next_is  = NEXT_NONE;
@@ -483,10 +496,11 @@ int SvmDualOp::form_w(const double *a, const double **w_dev)
   return PMH_SUCCESS;
 }
 
-// how many entries of row differ from c y (c = row_0 / y_0): 0 <=> the row is c y, entry by entry, to the rounding of one multiplication
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_row_vs_labels(int n, const double *__restrict__ row, const double *__restrict__ y, int *__restrict__ bad)
+// how many entries of row differ from c y (c = row_i0 / y_i0): 0 <=> the row is c y, entry by entry, to the rounding of one multiplication.  Under a subset y
+// holds the masked labels and i0 is a sample of the subset; a zero entry of the row against a zero label is a match
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_row_vs_labels(int n, const double *__restrict__ row, const double *__restrict__ y, int *__restrict__ bad, int i0)
 {
-  const double c = row[0] / y[0];
+  const double c = row[i0] / y[i0];
   int          b = 0;
   for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) b += fabs(row[i] - c * y[i]) > 4.0 * 2.220446049250313e-16 * fabs(row[i]) ? 1 : 0;
   if (b) atomicAdd(bad, b); // (a count of mismatches: any order gives the same integer)
@@ -499,14 +513,16 @@ int pmh_svm_op_row_is_labels(SvmDualBase *o, pmh_qppf pf, double *c)
   pmh_ctx ctx = o->ctx;
   double  h[4] = {0.0, 0.0, 0.0, 0.0}; // mismatches (or: this rank cannot tell), holds rows, c, c^2
   if (pf->n != o->n) h[0] = 1.0;
-  else if (o->n > 0) {
+  else if (o->n > 0 && !(o->ym && o->n_sub == 0)) { // (a rank whose samples are all held out has no say, as one without rows)
+    const double *yk = o->yk();
+    const int     i0 = o->ym ? o->sub_first : 0;
     int *d_bad = nullptr, bad = 1;
     double r0 = 0.0, y0 = 0.0;
     int rc = pmh_malloc(ctx, sizeof(int), (void **)&d_bad);
     if (!rc) rc = pmh_memset(ctx, d_bad, 0, sizeof(int));
     if (!rc) {
-      hipLaunchKernelGGL(k_svm_row_vs_labels, dim3(pmh_vec_grid(o->n)), dim3(PMH_BLOCK), 0, ctx->stream, o->n, pf->row, o->y, d_bad);
-      rc = (hipGetLastError() != hipSuccess) || pmh_memcpy_d2h(ctx, &bad, d_bad, sizeof(int)) || pmh_memcpy_d2h(ctx, &r0, pf->row, sizeof(double)) || pmh_memcpy_d2h(ctx, &y0, o->y, sizeof(double));
+      hipLaunchKernelGGL(k_svm_row_vs_labels, dim3(pmh_vec_grid(o->n)), dim3(PMH_BLOCK), 0, ctx->stream, o->n, pf->row, yk, d_bad, i0);
+      rc = (hipGetLastError() != hipSuccess) || pmh_memcpy_d2h(ctx, &bad, d_bad, sizeof(int)) || pmh_memcpy_d2h(ctx, &r0, pf->row + i0, sizeof(double)) || pmh_memcpy_d2h(ctx, &y0, yk + i0, sizeof(double));
     }
     if (d_bad) pmh_free(ctx, d_bad);
     if (rc || bad || y0 == 0.0 || r0 == 0.0) h[0] = 1.0;
@@ -545,6 +561,83 @@ extern "C" int pmh_op_svm_dual_set_diag(pmh_op op, const double *diag_dev)
   PMH_ARG(o);
   if (diag_dev && o->shift != 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_diag: a diagonal while shift = %g is set (pmh_op_svm_dual_set_terms): the operator carries a scalar shift or a diagonal, not both", o->shift);
   o->diag = diag_dev;
+  o->terms_changed();
+  return PMH_SUCCESS;
+}
+
+// ---- sample subsets ----------------------------------------------------------------------------------------------------------------------------------------
+// st[0]: entries of m that are neither 0 nor 1 (a NaN is one), st[1]: ones, st[2]: the index of the first one (n: none).  Integer counts and a minimum: any
+// order gives the same integers
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_mask_stats(int n, const double *__restrict__ m, int *__restrict__ st)
+{
+  int bad = 0, ones = 0, first = n;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const double mi = m[i];
+    if (mi == 1.0) ones++, first = min(first, (int)i);
+    else if (!(mi == 0.0)) bad++;
+  }
+  if (bad) atomicAdd(st, bad);
+  if (ones) atomicAdd(st + 1, ones), atomicMin(st + 2, first);
+}
+// msk = m (m != nullptr: the new mask; nullptr: msk stays) and ym_i = msk_i != 0 ? y_i : +0
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_mask_labels(int n, const double *__restrict__ m, const double *__restrict__ y, double *__restrict__ msk, double *__restrict__ ym)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const double mi = m ? m[i] : msk[i];
+    if (m) msk[i] = mi != 0.0 ? 1.0 : 0.0;
+    ym[i] = mi != 0.0 ? y[i] : 0.0;
+  }
+}
+int SvmDualBase::refresh_ym()
+{
+  if (!msk || n <= 0) return PMH_SUCCESS;
+  hipLaunchKernelGGL(k_svm_mask_labels, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, (const double *)nullptr, y, msk, ym);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev)
+{
+  SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
+  PMH_ARG(o);
+  pmh_ctx   ctx = o->ctx;
+  const int n   = o->n;
+  if (!m_dev) {
+    if (o->msk) pmh_free(ctx, o->msk), pmh_free(ctx, o->ym);
+    o->msk = o->ym = nullptr, o->n_sub = 0, o->sub_first = 0;
+    o->terms_changed();
+    return PMH_SUCCESS;
+  }
+  // every rank decides alike: the counts are summed over the communicator before anything is changed
+  int     h[3] = {0, 0, n};
+  double  tot[2];
+  double *d_st = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * 2, (void **)&d_st)); // (the three ints first, then the two sums of the all-reduce)
+  int rc = pmh_memcpy_h2d(ctx, d_st, h, sizeof(h));
+  if (!rc && n > 0) {
+    hipLaunchKernelGGL(k_svm_mask_stats, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m_dev, (int *)d_st);
+    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_op_svm_dual_set_subset: the launch that checks the mask failed");
+  }
+  if (!rc) rc = pmh_memcpy_d2h(ctx, h, d_st, sizeof(h));
+  tot[0] = (double)h[0], tot[1] = (double)h[1];
+  if (!rc && pmh_comm_on(ctx)) rc = pmh_memcpy_h2d(ctx, d_st, tot, sizeof(tot)) || pmh_comm_allreduce_sum(ctx, d_st, 2) || pmh_memcpy_d2h(ctx, tot, d_st, sizeof(tot));
+  pmh_free(ctx, d_st);
+  PMH_CHK(rc);
+  if (tot[0] != 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_subset: %lld entries of the mask are neither 0 nor 1", (long long)tot[0]);
+  if (tot[1] == 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_subset: the mask holds no sample (all zero)");
+  if (!o->msk) {
+    const size_t nb = sizeof(double) * (size_t)(n ? n : 1);
+    PMH_CHK(pmh_malloc(ctx, nb, (void **)&o->msk));
+    if ((rc = pmh_malloc(ctx, nb, (void **)&o->ym))) {
+      pmh_free(ctx, o->msk), o->msk = nullptr;
+      return rc;
+    }
+  }
+  if (n > 0) {
+    hipLaunchKernelGGL(k_svm_mask_labels, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m_dev, o->y, o->msk, o->ym);
+    PMH_HIP(hipGetLastError());
+  }
+  o->n_sub = h[1], o->sub_first = h[1] ? h[2] : 0;
   o->terms_changed();
   return PMH_SUCCESS;
 }

@@ -27,6 +27,18 @@ struct SvmDualBase : pmh_op_s {
   // H + diag(diag) + (sigma + sigma_fold) y y' (pmh_op_svm_dual_set_diag: per-sample penalties of the L2 loss, diag_i = 1 / C_i): n doubles, borrowed, read by
   // pass 2 where it reads a_i and y_i; excludes a non-zero shift.  The kernels' AUG template argument is aug_form(): 0 plain, 1 shift, 2 diag
   const double *diag = nullptr;
+  // A sample subset S (pmh_op_svm_dual_set_subset): H_S = M (H + D) M, M = diag(m), m_i in {0, 1}.  The operator keeps the mask (msk) and the masked labels
+  // ym = m o y (n doubles each, its own memory; both nullptr: all samples) and hands ym to its kernels where they read y: a held-out row is ym_i == 0 at no
+  // extra traffic.  y stays the caller's labels; set_labels rebuilds ym from msk
+  double       *msk = nullptr, *ym = nullptr;
+  long long     n_sub = 0;    // samples of this rank in S
+  int           sub_first = 0; // the first of them (the entry pmh_svm_op_row_is_labels takes the row's scale from)
+  const double *yk() const { return ym ? ym : y; }
+  int           refresh_ym(); // ym = m o y (after new labels)
+  ~SvmDualBase() override
+  {
+    if (msk) pmh_free(ctx, msk), pmh_free(ctx, ym);
+  }
   bool          aug() const { return shift != 0.0 || sigma != 0.0 || sigma_fold != 0.0 || diag != nullptr; }
   int           aug_form() const { return !aug() ? 0 : (diag ? 2 : 1); }
   // ||B u|| of the one-row equality riding on the next product (the penalised operator arms it); an operator that does not serve it leaves aux_done 0 and the
@@ -44,7 +56,7 @@ struct SvmDualBase : pmh_op_s {
   {
     y = y_dev;
     terms_changed();
-    return PMH_SUCCESS;
+    return refresh_ym();
   }
 };
 

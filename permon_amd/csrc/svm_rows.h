@@ -15,9 +15,12 @@ static __device__ __forceinline__ double svm_sigmoid(double z)
   return 1.0 / (1.0 + exp(z));
 }
 
+// A sample subset (pmh_op_svm_dual_set_subset) reaches the sweeps as the template argument SUB and the operator's masked labels ym (m_i y_i: 0 on a held-out
+// row).  SUB = 0: ym is not read and the code is the sweep without subsets.  SUB = 1: ym_i is read first and the loads of a held-out row are not issued (its
+// dot product is 0, f is still called: it writes the row's 0)
 // any d <= 64 * SVM_KMAX: one wavefront per row, lane j owns columns j, j + 64, ...; f(i, x_i . w) in lane 0 of the wave that owns row i
-template <class F>
-static __device__ __forceinline__ void svm_sweep_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ w, F f)
+template <int SUB = 0, class F>
+static __device__ __forceinline__ void svm_sweep_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ w, F f, const double *__restrict__ ym = nullptr)
 {
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
@@ -27,6 +30,10 @@ static __device__ __forceinline__ void svm_sweep_rows(int n, int d, const double
   for (long long i = gw; i < n; i += nw) {
     const double *xr = X + (size_t)i * d;
     double        s  = 0.0;
+    if (SUB && ym[i] == 0.0) { // (uniform over the wave)
+      if (lane == 0) f(i, 0.0);
+      continue;
+    }
 #pragma unroll
     for (int k = 0; k < SVM_KMAX; k++) {
       const int c = lane + 64 * k;
@@ -41,15 +48,26 @@ static __device__ __forceinline__ void svm_sweep_rows(int n, int d, const double
 typedef double dbl2 __attribute__((ext_vector_type(2))); // native 16-byte vector: accepted by the non-temporal builtins
 
 // the UNR row pairs from row r0 on: v[u] = columns 2 l2, 2 l2 + 1 of row r0 + 2 u + half (zero past the last row)
-template <int UNR>
-static __device__ __forceinline__ void svm_load_rows64(int n, const double *__restrict__ X, long long r0, dbl2 (&v)[UNR])
+// SUB: bit j of live says that row r0 + j is in the subset (svm_live_rows64); a row that is not is not loaded (zero)
+template <int UNR, int SUB = 0>
+static __device__ __forceinline__ void svm_load_rows64(int n, const double *__restrict__ X, long long r0, dbl2 (&v)[UNR], unsigned long long live = ~0ull)
 {
-  const int lane = threadIdx.x & 63, half = lane >> 5, l2 = lane & 31;
+  const int      lane = threadIdx.x & 63, half = lane >> 5, l2 = lane & 31;
+  const unsigned lh = SUB ? (unsigned)(live >> half) : ~0u; // bit 2 u: this half-wave's row of pair u is in the subset
 #pragma unroll
   for (int u = 0; u < UNR; u++) {
     const long long i = r0 + 2 * u + half;
-    v[u] = (i < n) ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
+    v[u] = (i < n && (!SUB || ((lh >> (2 * u)) & 1))) ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
   }
+}
+// lane j < 2 UNR reads the masked label of row r0 + j (ONE coalesced load for the 2 UNR rows; 0 past the last row) -> yi; bit j of the result: row r0 + j is in the subset
+template <int UNR>
+static __device__ __forceinline__ unsigned long long svm_live_rows64(int n, const double *__restrict__ ym, long long r0, double &yi)
+{
+  const int       lane = threadIdx.x & 63;
+  const long long i = r0 + lane;
+  yi = (lane < 2 * UNR && i < n) ? ym[i] : 0.0;
+  return __ballot(yi != 0.0);
 }
 // the row's dot product in the first lane of its half-wave
 static __device__ __forceinline__ double svm_row_dot(dbl2 v, dbl2 wr)
@@ -75,15 +93,18 @@ static __device__ __forceinline__ double svm_row_dots_to_lanes(const dbl2 (&v)[U
   return sm;
 }
 // f(i, x_i . w) in the first lane of the half-wave that owns row i
-template <int UNR, class F>
-static __device__ __forceinline__ void svm_sweep_rows64(int n, const double *__restrict__ X, const double *__restrict__ w, F f)
+template <int UNR, int SUB = 0, class F>
+static __device__ __forceinline__ void svm_sweep_rows64(int n, const double *__restrict__ X, const double *__restrict__ w, F f, const double *__restrict__ ym = nullptr)
 {
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   const dbl2      wr = ((const dbl2 *)w)[l2];
   for (long long r0 = gw * 2 * UNR; r0 < n; r0 += nw * 2 * UNR) {
     dbl2 v[UNR];
-    svm_load_rows64<UNR>(n, X, r0, v);
+    if (SUB) {
+      double yi;
+      svm_load_rows64<UNR, SUB>(n, X, r0, v, svm_live_rows64<UNR>(n, ym, r0, yi));
+    } else svm_load_rows64<UNR>(n, X, r0, v);
 #pragma unroll
     for (int u = 0; u < UNR; u++) {
       const long long i = r0 + 2 * u + half;

@@ -29,6 +29,10 @@ struct pmh_svm_s {
   pmh_smalxe    sx    = nullptr;
   double       *alpha = nullptr, *rhs = nullptr, *lb = nullptr, *ub = nullptr, *row = nullptr, *w = nullptr, *part = nullptr, *scal = nullptr;
   double       *Cv = nullptr, *Cinv = nullptr; // pmh_svm_set_penalties: C_i (n doubles) and, L2, 1 / C_i (the operator's diagonal); nullptr: opts.C everywhere
+  // pmh_svm_set_subset: the mask and the masked labels are the operator's (SvmDualBase::msk, ym); n_sub: the subset's samples over all ranks (0: no subset);
+  // Dm: L2, the operator's diagonal m_i / C_i under a subset (n doubles)
+  long long     n_sub = 0;
+  double       *Dm = nullptr;
   std::vector<double> h_w;
   double        b = 0.0;
   int           trained = 0;
@@ -95,12 +99,17 @@ struct svm_counts {
 // sample i with the score s = x_i . w + b: label_i = +-1 (s >= 0: +1) and, with the true labels, the confusion counts.  scores / labels / ytrue may each be
 // nullptr; no __restrict__ on scores: the CSR form reads the dot products from the array the scores go to.  The counts go in and out by value: through
 // references the choice (pos ? tp : fp) is one between addresses, and the compiler then keeps the counts in memory (40 bytes of scratch per lane, or 8 KiB of LDS)
-static __device__ __forceinline__ svm_counts svm_classify_row(long long i, double s, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, svm_counts c)
+// The selector of pmh_svm_test_own: with sel.m given, a sample is counted only where m_i == sel.want (the handle's subset mask: 1 the subset, 0 the held-out rows)
+struct svm_sel {
+  const double *m = nullptr;
+  double        want = 0.0;
+};
+static __device__ __forceinline__ svm_counts svm_classify_row(long long i, double s, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, svm_counts c, svm_sel sel)
 {
   const double l = s >= 0.0 ? 1.0 : -1.0;
   if (scores) scores[i] = s;
   if (labels) labels[i] = l;
-  if (ytrue) {
+  if (ytrue && (!sel.m || sel.m[i] == sel.want)) {
     const bool pos = ytrue[i] > 0.0;
     if (l > 0.0) (pos ? c.tp : c.fp) += 1.0;
     else (pos ? c.fn : c.tn) += 1.0;
@@ -109,20 +118,20 @@ static __device__ __forceinline__ svm_counts svm_classify_row(long long i, doubl
 }
 // One pass over the test samples: scores, labels and per workgroup the confusion counts -> part[4][gridDim.x] (svm_classify_row)
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict(int n, int d, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
-                                                           const double *__restrict__ ytrue, double *__restrict__ part)
+                                                           const double *__restrict__ ytrue, double *__restrict__ part, svm_sel sel)
 {
   __shared__ double red[PMH_BLOCK / 64];
   svm_counts        c;
-  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { c = svm_classify_row(i, dot + b, scores, labels, ytrue, c); });
+  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { c = svm_classify_row(i, dot + b, scores, labels, ytrue, c, sel); });
   if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
 // d == 64: the row layout of k_svm_x64 (svm.hip), four row pairs in flight
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
-                                                             const double *__restrict__ ytrue, double *__restrict__ part)
+                                                             const double *__restrict__ ytrue, double *__restrict__ part, svm_sel sel)
 {
   __shared__ double red[PMH_BLOCK / 64];
   svm_counts        c;
-  svm_sweep_rows64<4>(n, X, w, [&](long long i, double dot) { c = svm_classify_row(i, dot + b, scores, labels, ytrue, c); });
+  svm_sweep_rows64<4>(n, X, w, [&](long long i, double dot) { c = svm_classify_row(i, dot + b, scores, labels, ytrue, c, sel); });
   if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
 
@@ -147,11 +156,11 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias_dots(int n, const double
   svm_store4(sb, sya, nf, ns, red, part);
 }
 // (dots and scores may be the same array)
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict_dots(int n, const double *dots, double b, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, double *__restrict__ part)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict_dots(int n, const double *dots, double b, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, double *__restrict__ part, svm_sel sel)
 {
   __shared__ double red[PMH_BLOCK / 64];
   svm_counts        c;
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) c = svm_classify_row(i, dots[i] + b, scores, labels, ytrue, c);
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) c = svm_classify_row(i, dots[i] + b, scores, labels, ytrue, c, sel);
   if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
 
@@ -187,7 +196,7 @@ extern "C" int pmh_svm_destroy(pmh_svm s)
   if (s->sx) pmh_smalxe_destroy(s->sx);
   if (s->pf) pmh_qppf_destroy(s->pf);
   if (s->H) pmh_op_destroy(s->H);
-  double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal, s->dots, s->Cv, s->Cinv};
+  double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal, s->dots, s->Cv, s->Cinv, s->Dm};
   for (double *p : v)
     if (p) pmh_free(s->ctx, p);
   delete s;
@@ -209,6 +218,41 @@ static int svm_build_solver(pmh_svm s)
   pmh_mpgp_opts mo = s->o.mpgp;
   mo.rtol = s->o.qps.rtol, mo.atol = s->o.qps.atol, mo.divtol = s->o.qps.divtol, mo.max_it = s->o.qps.max_it;
   return pmh_mpgp_create(s->ctx, s->H, s->rhs, s->alpha, s->lb, s->ub, &mo, &s->mpgp);
+}
+
+// the samples the problem is posed over, all ranks: the subset's, or all
+static long long svm_n_posed(pmh_svm s) { return s->n_sub > 0 ? s->n_sub : s->n_global; }
+// the equality's row y / sqrt(n) and its projector; under a subset the masked labels over sqrt(n_S): zero on the held-out rows
+static int svm_refresh_row(pmh_svm s)
+{
+  if (!s->o.bias) return PMH_SUCCESS;
+  if (s->pf) pmh_qppf_destroy(s->pf), s->pf = nullptr;
+  if (s->n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, static_cast<SvmDualBase *>(s->H)->yk(), 1.0 / sqrt((double)svm_n_posed(s)), s->row);
+  PMH_HIP(hipGetLastError());
+  return pmh_qppf_create_onerow(s->ctx, s->row, s->n, &s->pf);
+}
+// Dm_i = m_i cinv_i (cinv == nullptr: m_i c)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_mask_diag(int n, const double *__restrict__ m, const double *__restrict__ cinv, double c, double *__restrict__ Dm)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) Dm[i] = m[i] != 0.0 ? (cinv ? cinv[i] : c) : 0.0;
+}
+// L2: the operator's term beside H from the handle's state: the shift 1 / C, the diagonal 1 / C_i (penalties) or, under a subset, the diagonal m_i / C_i
+static int svm_refresh_l2(pmh_svm s)
+{
+  if (s->o.loss_type != PMH_SVM_LOSS_L2) return PMH_SUCCESS;
+  if (s->n_sub > 0) {
+    if (!s->Dm) PMH_CHK(pmh_malloc(s->ctx, sizeof(double) * (size_t)(s->n ? s->n : 1), (void **)&s->Dm));
+    if (s->n > 0) hipLaunchKernelGGL(k_svm_mask_diag, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, (const double *)static_cast<SvmDualBase *>(s->H)->msk, (const double *)s->Cinv, 1.0 / s->o.C, s->Dm);
+    PMH_HIP(hipGetLastError());
+    PMH_CHK(pmh_op_svm_dual_set_terms(s->H, 0.0, 0.0));
+    return pmh_op_svm_dual_set_diag(s->H, s->Dm);
+  }
+  if (s->Cinv) {
+    PMH_CHK(pmh_op_svm_dual_set_terms(s->H, 0.0, 0.0));
+    return pmh_op_svm_dual_set_diag(s->H, s->Cinv);
+  }
+  PMH_CHK(pmh_op_svm_dual_set_diag(s->H, nullptr));
+  return pmh_op_svm_dual_set_terms(s->H, 1.0 / s->o.C, 0.0);
 }
 
 // X_dev (dense rows) or Xcsr
@@ -313,7 +357,7 @@ static int svm_model(pmh_svm s)
   PMH_CHK(pmh_memcpy_d2h(ctx, h, s->scal, sizeof(h)));
   PMH_CHK(pmh_memcpy_d2h(ctx, s->h_w.data(), s->w, sizeof(double) * (size_t)s->d));
   s->st.yTalpha = h[1], s->st.n_free_sv = (long long)h[2], s->st.n_sv = (long long)h[3];
-  s->st.b_multiplier = h[4] / sqrt((double)(s->n_global > 0 ? s->n_global : 1));
+  s->st.b_multiplier = h[4] / sqrt((double)(svm_n_posed(s) > 0 ? svm_n_posed(s) : 1)); // (the row is y / sqrt(n), over the subset: n_S)
   s->st.b_free       = h[2] > 0.0 ? h[0] / h[2] : NAN;
   if (!s->o.bias) s->b = 0.0;
   else s->b = h[2] > 0.0 ? s->st.b_free : s->st.b_multiplier;
@@ -437,7 +481,7 @@ extern "C" int pmh_svm_set_penalties(pmh_svm s, double C_pos, double C_neg, cons
       PMH_CHK(pmh_memcpy_d2h(ctx, &nbad, s->scal, sizeof(double)));
     }
     if (nbad != 0.0)
-      return pmh_set_error(PMH_ERR_ARG, "pmh_svm_set_penalties: %lld of the sample weights are not positive and finite (or give a penalty C_i that is not); masking samples out by a zero weight is not supported",
+      return pmh_set_error(PMH_ERR_ARG, "pmh_svm_set_penalties: %lld of the sample weights are not positive and finite (or give a penalty C_i that is not); a zero weight does not leave a sample out: pmh_svm_set_subset does",
                            (long long)nbad);
   }
   if (!s->Cv) PMH_CHK(pmh_malloc(ctx, nb, (void **)&s->Cv));
@@ -447,10 +491,7 @@ extern "C" int pmh_svm_set_penalties(pmh_svm s, double C_pos, double C_neg, cons
     hipLaunchKernelGGL(k_svm_fill_penalties, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, s->y, weight_dev, C_pos, C_neg, s->Cv, L2 ? nullptr : s->ub, L2 ? s->Cinv : nullptr);
     PMH_HIP(hipGetLastError());
   }
-  if (L2) { // the diagonal 1 / C_i in place of the scalar 1 / C
-    PMH_CHK(pmh_op_svm_dual_set_terms(s->H, 0.0, 0.0));
-    PMH_CHK(pmh_op_svm_dual_set_diag(s->H, s->Cinv));
-  }
+  PMH_CHK(svm_refresh_l2(s)); // the diagonal 1 / C_i in place of the scalar 1 / C (under a subset m_i / C_i)
   return svm_build_solver(s);
 }
 
@@ -474,41 +515,74 @@ extern "C" int pmh_svm_set_labels(pmh_svm s, const double *y_dev)
   if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
   PMH_CHK(pmh_op_svm_dual_set_labels(s->H, y_dev));
   s->y = y_dev;
-  if (s->o.loss_type == PMH_SVM_LOSS_L2) {
-    PMH_CHK(pmh_op_svm_dual_set_diag(s->H, nullptr));
-    PMH_CHK(pmh_op_svm_dual_set_terms(s->H, 1.0 / s->o.C, 0.0));
-  } else PMH_CHK(pmh_vec_set(ctx, n, s->ub, s->o.C));
+  if (s->o.loss_type != PMH_SVM_LOSS_L2) PMH_CHK(pmh_vec_set(ctx, n, s->ub, s->o.C));
   if (s->Cv) pmh_free(ctx, s->Cv), s->Cv = nullptr;
   if (s->Cinv) pmh_free(ctx, s->Cinv), s->Cinv = nullptr;
-  if (s->o.bias) {
-    if (s->pf) pmh_qppf_destroy(s->pf), s->pf = nullptr;
-    if (n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, y_dev, 1.0 / sqrt((double)s->n_global), s->row);
-    PMH_HIP(hipGetLastError());
-    PMH_CHK(pmh_qppf_create_onerow(ctx, s->row, n, &s->pf));
-  }
+  PMH_CHK(svm_refresh_l2(s)); // (a subset stays: the operator rebuilt its masked labels, the diagonal is m_i / C again)
+  PMH_CHK(svm_refresh_row(s));
   return svm_build_solver(s);
 }
 
-// X (dense rows, n x d) or Xt (CSR)
-static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts)
+// ---- sample subsets ----------------------------------------------------------------------------------------------------------------------------------------
+// Train on the subset S of the handle's samples, X staying where it is: the operator becomes H_S = M (H + D) M (pmh_op_svm_dual_set_subset), rhs = m, the
+// equality's row the masked labels over sqrt(n_S), L2 the diagonal m_i / C_i; L1 keeps its bounds.  From alpha = 0 every iterate, gradient and direction of
+// the solvers is then zero on the held-out rows, so the multiplier, the free support vectors and n_sv are those of S.  The solver is built anew as by
+// pmh_svm_set_penalties: the eigenvalue estimate must be H_S's.  A refused mask leaves the handle as it was
+extern "C" int pmh_svm_set_subset(pmh_svm s, const double *m_dev)
 {
-  PMH_ARG(s && n >= 0 && (X || Xt || n == 0));
+  PMH_ARG(s);
+  pmh_ctx      ctx = s->ctx;
+  SvmDualBase *H   = static_cast<SvmDualBase *>(s->H);
+  PMH_CHK(pmh_op_svm_dual_set_subset(s->H, m_dev)); // (checks the mask before anything changes; the solvers only hold the operator)
+  s->trained = s->calibrated = 0;
+  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
+  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
+  s->n_sub = 0;
+  if (m_dev) {
+    double ns = (double)H->n_sub; // all-reduced as n_global is
+    if (pmh_comm_on(ctx)) {
+      PMH_CHK(pmh_vec_set(ctx, 1, s->scal, ns));
+      PMH_CHK(pmh_comm_allreduce_sum(ctx, s->scal, 1));
+      PMH_CHK(pmh_memcpy_d2h(ctx, &ns, s->scal, sizeof(double)));
+    }
+    s->n_sub = (long long)ns;
+    PMH_CHK(pmh_vec_copy(ctx, s->n, H->msk, s->rhs));
+  } else PMH_CHK(pmh_vec_set(ctx, s->n, s->rhs, 1.0));
+  PMH_CHK(svm_refresh_l2(s));
+  PMH_CHK(svm_refresh_row(s));
+  return svm_build_solver(s);
+}
+
+extern "C" int pmh_svm_get_subset(pmh_svm s, double *m_dev, long long *n_in)
+{
+  PMH_ARG(s);
+  SvmDualBase *H = static_cast<SvmDualBase *>(s->H);
+  if (n_in) *n_in = svm_n_posed(s);
+  if (!m_dev) return PMH_SUCCESS;
+  return H->msk ? pmh_vec_copy(s->ctx, s->n, H->msk, m_dev) : pmh_vec_set(s->ctx, s->n, m_dev, 1.0);
+}
+
+// X (dense rows, n x d) or Xt (CSR)
+// own: the handle's own samples (X or, CSR, the operator's tables: Xt == nullptr); sel: which of them the counts are taken over
+static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts, bool own = false, svm_sel sel = svm_sel())
+{
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || own));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict: call pmh_svm_train first");
-  PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
+  if (!own) PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
   const int nb = SVM_NB(n);
-  if (n > 0 && Xt) {
+  if (n > 0 && (Xt || (own && s->Xcsr))) {
     double *dots = scores; // the dot products land where the scores go; without scores in a buffer of this call
     if (!dots) PMH_CHK(pmh_malloc(s->ctx, sizeof(double) * (size_t)n, (void **)&dots));
-    int rc = pmh_svm_csr_row_dots(Xt, s->w, dots);
+    int rc = Xt ? pmh_svm_csr_row_dots(Xt, s->w, dots) : pmh_svm_csr_op_row_dots(static_cast<SvmDualBase *>(s->H), s->w, dots);
     if (!rc) {
-      hipLaunchKernelGGL(k_svm_predict_dots, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, (const double *)dots, s->b, scores, labels, ytrue, s->part);
+      hipLaunchKernelGGL(k_svm_predict_dots, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, (const double *)dots, s->b, scores, labels, ytrue, s->part, sel);
       if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_predict_csr: the launch failed");
     }
     if (!scores) pmh_free(s->ctx, dots);
     PMH_CHK(rc);
   } else if (n > 0) {
-    if (s->d == 64) hipLaunchKernelGGL(k_svm_predict64, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part);
-    else hipLaunchKernelGGL(k_svm_predict, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, s->d, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part);
+    if (s->d == 64) hipLaunchKernelGGL(k_svm_predict64, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part, sel);
+    else hipLaunchKernelGGL(k_svm_predict, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, s->d, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part, sel);
     PMH_HIP(hipGetLastError());
   }
   if (!counts) return PMH_SUCCESS;
@@ -537,6 +611,24 @@ extern "C" int pmh_svm_test(pmh_svm s, int n, const double *X_dev, const double 
 {
   PMH_ARG(y_dev && counts);
   return svm_predict(s, n, X_dev, nullptr, nullptr, nullptr, y_dev, counts);
+}
+
+// the handle's own samples, nothing uploaded: the predict sweep over the X the handle was created on (CSR: the row sweep with the operator's tables)
+extern "C" int pmh_svm_predict_own(pmh_svm s, double *scores_dev, double *labels_dev)
+{
+  PMH_ARG(s);
+  return svm_predict(s, s->n, s->X, nullptr, scores_dev, labels_dev, nullptr, nullptr, true);
+}
+
+extern "C" int pmh_svm_test_own(pmh_svm s, int which, long long counts[4])
+{
+  PMH_ARG(s && counts);
+  if (which != PMH_SVM_OWN_HELD_OUT && which != PMH_SVM_OWN_SUBSET && which != PMH_SVM_OWN_ALL) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_test_own: which = %d (PMH_SVM_OWN_HELD_OUT | PMH_SVM_OWN_SUBSET | PMH_SVM_OWN_ALL)", which);
+  SvmDualBase *H = static_cast<SvmDualBase *>(s->H);
+  if (which == PMH_SVM_OWN_HELD_OUT && !H->msk) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_test_own: no subset is set (pmh_svm_set_subset), so no sample is held out");
+  svm_sel sel;
+  if (which != PMH_SVM_OWN_ALL && H->msk) sel.m = H->msk, sel.want = which == PMH_SVM_OWN_SUBSET ? 1.0 : 0.0;
+  return svm_predict(s, s->n, s->X, nullptr, nullptr, nullptr, s->y, counts, true, sel);
 }
 
 // ---- probabilities (Platt scaling, svm_proba.hip) ---------------------------------------------------------------------------------------------------------------

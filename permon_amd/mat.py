@@ -707,7 +707,23 @@ def MatCreateSVMDual(ctx, X, y):
         check(ctx.L.pmh_op_svm_dual_set_diag(op.h, v.p if v is not None else None))
         op._diag = v
 
+    def set_subset(mask=None):
+        """H_S = M (H + D) M over the samples where mask is true (pmh_op_svm_dual_set_subset): n_local booleans or 0 / 1 numbers, copied by the operator; None:
+        all samples.  Held-out rows of a product are exactly 0 and, in the dense kernels, not read."""
+        if mask is None:
+            check(ctx.L.pmh_op_svm_dual_set_subset(op.h, None))
+            return
+        m = np.ascontiguousarray(mask, dtype=np.float64).ravel()
+        if m.size != n:
+            raise ValueError("set_subset: %d entries, the operator has %d rows" % (m.size, n))
+        v = Vec.from_numpy(ctx, m)
+        try:
+            check(ctx.L.pmh_op_svm_dual_set_subset(op.h, v.p))
+        finally:
+            v.free()
+
     op.passes = passes
     op.set_terms = set_terms
     op.set_diag = set_diag
+    op.set_subset = set_subset
     return op

@@ -196,6 +196,30 @@ class SVM(_SVMHandle):
             old.free()
         return self
 
+    def set_subset(self, mask):
+        """Train on the samples where mask is true, X staying on the device (pmh_svm_set_subset): n booleans or 0 / 1 numbers; None: all samples again.  The
+        handle is untrained and uncalibrated afterwards; set_labels and set_penalties keep the subset.  After train() alpha is 0 on the held-out samples and
+        the model is that of a fit on (X[mask], y[mask]); decision_function_own / test_own score the held-out samples without an upload."""
+        self._need()
+        if mask is None:
+            check(self.L.pmh_svm_set_subset(self.h, None))
+            return self
+        m = np.ascontiguousarray(mask, dtype=np.float64).ravel()
+        if m.size != self.n:
+            raise ValueError("SVM: the mask must have %d entries" % self.n)
+        with self._lent(m) as md:
+            check(self.L.pmh_svm_set_subset(self.h, md.p))
+        return self
+
+    @property
+    def subset(self):
+        """The training mask as n booleans (pmh_svm_get_subset), or None where all samples train."""
+        self._need()
+        k = ct.c_longlong()
+        check(self.L.pmh_svm_get_subset(self.h, None, ct.byref(k)))
+        m = self._get_vec(lambda h, p: self.L.pmh_svm_get_subset(h, p, None)) != 0.0
+        return None if m.all() else m
+
     def train(self):
         self._need()
         check(self.L.pmh_svm_train(self.h))
@@ -309,6 +333,25 @@ class SVM(_SVMHandle):
         with S as (n, xa), _vecs(self.ctx, n) as (p,):
             check(self._entry("predict_proba", S.sparse)(self.h, *xa, p.p))
             return p.to_numpy()
+
+    def decision_function_own(self):
+        """(n,): the scores of the samples the handle was created on, held-out ones included, without an upload (pmh_svm_predict_own): bit for bit
+        decision_function(X)."""
+        return self._get_vec(lambda h, p: self.L.pmh_svm_predict_own(h, p, None))
+
+    OWN = {"held_out": 0, "subset": 1, "all": 2}  # PMH_SVM_OWN_*
+
+    def test_own(self, which="held_out"):
+        """Confusion counts of the handle's own samples against its labels over the held-out samples, the subset or all of them (pmh_svm_test_own), as test
+        returns them: dict(TP, FP, TN, FN, accuracy)."""
+        self._need()
+        if which not in self.OWN:
+            raise ValueError("SVM: which must be one of %s" % ", ".join(sorted(self.OWN)))
+        cnt = (ct.c_longlong * 4)()
+        check(self.L.pmh_svm_test_own(self.h, self.OWN[which], cnt))
+        tp, fp, tn, fn = (int(c) for c in cnt)
+        n = tp + fp + tn + fn
+        return dict(TP=tp, FP=fp, TN=tn, FN=fn, accuracy=(tp + tn) / n if n else float("nan"))
 
     def test(self, X, y):
         """Confusion counts of the predicted labels against y: dict(TP, FP, TN, FN, accuracy)."""
@@ -491,6 +534,41 @@ class SVMMulticlass(_SVMHandle):
         conf, unk = self._run(X, False, False, labels_true=labels)
         n = X.shape[0]
         return dict(accuracy=float(np.trace(conf)) / n if n else float("nan"), confusion=conf, n_unknown=unk)
+
+
+def kfold(y, k, seed=0, stratified=True):
+    """k boolean training masks over the samples of y whose complements (the folds) partition them.  One seeded shuffle, then the samples are dealt to the
+    folds round-robin -- stratified: class by class (classes ascending), the deal going on where the previous class stopped, so every fold's share of a class
+    and of the whole differs from another fold's by at most one sample.  A class of fewer than k samples leaves some folds without it.  Host only."""
+    y = np.asarray(y).ravel()
+    n, k = y.size, int(k)
+    if k < 2 or k > n:
+        raise ValueError("kfold: k = %d, need 2 <= k <= n = %d" % (k, n))
+    perm = np.random.default_rng(seed).permutation(n)
+    if stratified:
+        order = np.concatenate([perm[y[perm] == c] for c in np.unique(y)])
+    else:
+        order = perm
+    fold = np.empty(n, dtype=np.int64)
+    fold[order] = np.arange(n) % k
+    return [fold != f for f in range(k)]
+
+
+def cross_validate(svm, k=5, seed=0, stratified=True):
+    """k-fold cross-validation on a created SVM handle, X uploaded once (CSR: one column-ordered copy): for every mask of kfold(y, k, seed, stratified)
+    set_subset, train, test_own("held_out").  -> dict(folds: the k dicts of test_own, accuracy: their mean accuracy, masks).  The handle gets back the subset
+    it had and is left untrained."""
+    svm._need()
+    before = svm.subset
+    y = svm._keep[1].to_numpy()
+    masks = kfold(y, k, seed, stratified)
+    folds = []
+    try:
+        for m in masks:
+            folds.append(svm.set_subset(m).train().test_own("held_out"))
+    finally:
+        svm.set_subset(before)
+    return dict(folds=folds, accuracy=float(np.mean([f["accuracy"] for f in folds])), masks=masks)
 
 
 def load_svmlight(path, n_features=None, zero_based="auto", multiclass=False):
