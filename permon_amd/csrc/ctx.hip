@@ -358,6 +358,18 @@ extern "C" int pmh_comm_allreduce_min(pmh_ctx c, double *dbuf, size_t count)
   return PMH_SUCCESS;
 }
 
+int pmh_comm_sum_host(pmh_ctx c, double *h, int k)
+{
+  if (!pmh_comm_on(c) || k <= 0) return PMH_SUCCESS;
+  double *d = nullptr;
+  PMH_CHK(pmh_malloc(c, sizeof(double) * (size_t)k, (void **)&d));
+  int rc = pmh_memcpy_h2d(c, d, h, sizeof(double) * (size_t)k);
+  if (!rc) rc = pmh_comm_allreduce_sum(c, d, (size_t)k);
+  if (!rc) rc = pmh_memcpy_d2h(c, h, d, sizeof(double) * (size_t)k);
+  pmh_free(c, d);
+  return rc;
+}
+
 // K device scalars with their own operations (the MPGP reductions of a phase: sums and QPCFeas's MIN) in one grouped exchange
 int pmh_comm_allreduce_scalars(pmh_ctx c, double *dscal, int K, const int *ops)
 {

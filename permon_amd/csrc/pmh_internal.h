@@ -87,6 +87,10 @@ struct pmh_ctx_s {
 // the data-path collectives are live: a transport exists (RCCL communicator or host transport) and there is more than one rank (or PMH_COMM_FORCE=1)
 static inline bool pmh_comm_on(pmh_ctx c) { return (c->comm || c->hook) && (c->size > 1 || c->force_comm); }
 int pmh_comm_allreduce_scalars(pmh_ctx c, double *dscal, int K, const int *ops /* PMH_RED_SUM / PMH_RED_MIN per scalar */); // K device scalars, one grouped exchange
+// h[0..k) summed over the ranks, so that every rank decides alike on what it then holds: host -> a device buffer of the call's own -> ONE pmh_comm_allreduce_sum
+// -> host.  Without a communicator nothing happens and no device memory is touched.  With one, every call allocates and frees its buffer (the free synchronises
+// the device): meant for set-up decisions, a handful per handle; a caller that would make one per step or per fold of a long loop should keep a buffer instead
+int pmh_comm_sum_host(pmh_ctx c, double *h, int k);
 
 // ---- CSR -----------------------------------------------------------------------------------------------
 // the product plan pmh_csr_create picks per matrix, numbered as pmh_csr_kernel_info reports it (spmv.hip)

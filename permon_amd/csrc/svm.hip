@@ -5,6 +5,8 @@
 // is "parity unpinned" beyond the MPGP solver that calls it; the oracle side of its test is a numpy restatement.
 // HBM-bound: algorithmic bytes per apply 2*8*N*d + 40*N (X read twice; a, y read, Ha written, y read again).
 // Samples shard over GPUs by rows; the only exchange is the all-reduce of w (d doubles) between the passes.
+#include <type_traits>
+
 #include "pmh_internal.h"
 #include "reduce.h"
 #include "box_inline.h"
@@ -82,8 +84,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double 
                                                      const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[d] : 0.0;
-  if (SUB) svm_sweep_rows<1>(n, d, X, w, [&](long long i, double s) { Ha[i] = y[i] == 0.0 ? 0.0 : (AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s); }, y);
-  else svm_sweep_rows(n, d, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
+  svm_sweep_rows<SUB>(n, d, X, w, [&](long long i, double s) { Ha[i] = (SUB && y[i] == 0.0) ? 0.0 : (AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s); }, y);
 }
 
 // ---- d == 64 fast path: the two-rows-per-wave-instruction layout of svm_rows.h, 4-fold unroll ----
@@ -151,8 +152,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__re
                                                        const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[64] : 0.0;
-  if (SUB) svm_sweep_rows64<SVM_UNR, 1>(n, X, w, [&](long long i, double s) { Ha[i] = y[i] == 0.0 ? 0.0 : (AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s); }, y);
-  else svm_sweep_rows64<SVM_UNR>(n, X, w, [&](long long i, double s) { Ha[i] = AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s; });
+  svm_sweep_rows64<SVM_UNR, SUB>(n, X, w, [&](long long i, double s) { Ha[i] = (SUB && y[i] == 0.0) ? 0.0 : (AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s); }, y);
 }
 
 // ---- paired passes -------------------------------------------------------------------------------------------------------------------------
@@ -179,6 +179,10 @@ struct svm_grad_args {
   double        sigma, shift;
   const double *diag; // AUG 2: the diagonal, in place of shift
 };
+// what a lane asks for of its row before the dot products arrive (svm_sweep_rows64_lanes' pre); sh: the shift or diag_i
+struct svm_grad_row {
+  double yi, xi, bi, li, ui, sh;
+};
 // pass 2 of g = H x - b with the gradient split, p = gf, the partial sums of (0, |gP|^2, |gc|^2, |gf|^2), QPCFeas(x, p) and X'(y o p)
 #define SVM_EU 4
 template <int AUG, int SUB>
@@ -186,48 +190,37 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
   __shared__ double red[PMH_BLOCK / 64];
-  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
-  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  const dbl2        wr = ((const dbl2 *)w)[l2];
   const double      sS = AUG ? a.sigma * w[64] : 0.0;
   double            a0 = 0.0, a1 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, m = INFINITY, ts = 0.0;
-  for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
-    dbl2   v[SVM_EU];
-    double ym = 0.0; // SUB: the row's masked label, read before the rows: a held-out row is not loaded
-    if (SUB) svm_load_rows64<SVM_EU, SUB>(n, X, r0, v, svm_live_rows64<SVM_EU>(n, y, r0, ym));
-    else svm_load_rows64<SVM_EU>(n, X, r0, v);
-    // the rows' dot products land in the first lane of each half-wave; lane j < 2 SVM_EU takes row r0 + j (u = j >> 1, half = j & 1): ONE coalesced load per
-    // vector for the 2 SVM_EU rows (a load per row costs the address unit a whole instruction each: measured 2 x the time of the plain pass), asked for before
-    // the dot products so that they travel with the rows of X, the elementwise work once
-    const long long i   = r0 + lane;
-    const bool      act = lane < 2 * SVM_EU && i < n;
-    double          yi = 0.0, xi = 0.0, bi = 0.0, li = -INFINITY, ui = INFINITY, sh = AUG == 1 ? a.shift : 0.0;
-    if (act) {
-      yi = SUB ? ym : y[i], xi = a.x_in[i], bi = a.b[i];
-      if (AUG == 2) sh = a.diag[i];
-      if (a.lb) li = a.lb[i];
-      if (a.ub) ui = a.ub[i];
-    }
-    const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
-    double t = 0.0; // y_i p_i: the row's weight in X'(y o p)
-    if (act) {
-      const double gi = ((SUB && yi == 0.0) ? 0.0 : (AUG ? svm_aug_row(yi, sm, sS, sh, xi) : yi * sm)) - bi;
-      double       f, c;
-      pmh_box_split_v(xi, gi, li, ui, a.astol, f, c);
-      a.g[i] = gi, a.gf[i] = f, a.p[i] = f;
-      if (a.x_out) a.x_out[i] = xi;
-      const double gPi = f + c;
-      acc1 += gPi * gPi, acc2 += c * c, acc3 += f * f;
-      m = pmh_box_feas_v(m, xi, f, li, ui);
-      t = yi * f;
-      if (AUG) ts += t;
-    }
-#pragma unroll
-    for (int u = 0; u < SVM_EU; u++) {
-      const double tu = __shfl(t, 2 * u + half, 64);
-      a0 += tu * v[u].x, a1 += tu * v[u].y;
-    }
-  }
+  svm_sweep_rows64_lanes<SVM_EU, SUB, 1>(
+    n, X, y, w, a0, a1,
+    [&](long long i, bool act, double ym) {
+      svm_grad_row r = {0.0, 0.0, 0.0, -INFINITY, INFINITY, AUG == 1 ? a.shift : 0.0};
+      if (act) {
+        r.yi = SUB ? ym : y[i], r.xi = a.x_in[i], r.bi = a.b[i];
+        if (AUG == 2) r.sh = a.diag[i];
+        if (a.lb) r.li = a.lb[i];
+        if (a.ub) r.ui = a.ub[i];
+      }
+      return r;
+    },
+    [&](long long i, bool act, double sm, svm_grad_row r) {
+      const double yi = r.yi, xi = r.xi, bi = r.bi, li = r.li, ui = r.ui, sh = r.sh;
+      double       t = 0.0; // y_i p_i: the row's weight in X'(y o p)
+      if (act) {
+        const double gi = ((SUB && yi == 0.0) ? 0.0 : (AUG ? svm_aug_row(yi, sm, sS, sh, xi) : yi * sm)) - bi;
+        double       f, c;
+        pmh_box_split_v(xi, gi, li, ui, a.astol, f, c);
+        a.g[i] = gi, a.gf[i] = f, a.p[i] = f;
+        if (a.x_out) a.x_out[i] = xi;
+        const double gPi = f + c;
+        acc1 += gPi * gPi, acc2 += c * c, acc3 += f * f;
+        m = pmh_box_feas_v(m, xi, f, li, ui);
+        t = yi * f;
+        if (AUG) ts += t;
+      }
+      return t;
+    });
   svm_fold_cols(a0, a1, lds, a.part_next);
   if (AUG) {
     const double rs = pmh_block_reduce<PMH_RED_SUM>(ts, red);
@@ -253,59 +246,51 @@ struct svm_p1_args {
   double        sigma, shift;
   const double *diag; // AUG 2: the diagonal, in place of shift
 };
+struct svm_p1_row {
+  double yi, pi, gi, xi, li, ui, sh;
+};
 // pass 2 of Ap = H p with the partial sums of p'Ap, g'p, QPCFeas(x, p); SPEC: + the iterate of the expansion step and X'(y o x+)
 template <int SPEC, int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_p1_args a)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
   __shared__ double red[PMH_BLOCK / 64];
-  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
-  const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  const dbl2        wr = ((const dbl2 *)w)[l2];
   const double      maf = SPEC ? -(*a.afeas) : 0.0, mal = -a.alpha;
   const double      sS = AUG ? a.sigma * w[64] : 0.0;
   double            a0 = 0.0, a1 = 0.0, s0 = 0.0, s1 = 0.0, m = INFINITY, ts = 0.0, sux = 0.0;
-  for (long long r0 = gw * 2 * SVM_EU; r0 < n; r0 += nw * 2 * SVM_EU) {
-    dbl2   v[SVM_EU];
-    double ym = 0.0;
-    if (SUB) svm_load_rows64<SVM_EU, SUB>(n, X, r0, v, svm_live_rows64<SVM_EU>(n, y, r0, ym));
-    else svm_load_rows64<SVM_EU>(n, X, r0, v);
-    // (as in k_svm_x64_grad: lane j < 2 SVM_EU takes row r0 + j, its scalars asked for up front)
-    const long long i   = r0 + lane;
-    const bool      act = lane < 2 * SVM_EU && i < n;
-    double          yi = 0.0, pi = 0.0, gi = 0.0, xi = 0.0, li = -INFINITY, ui = INFINITY, sh = AUG == 1 ? a.shift : 0.0;
-    if (act) {
-      yi = SUB ? ym : y[i], pi = a.p[i], gi = a.g[i], xi = a.x[i];
-      if (AUG == 2) sh = a.diag[i];
-      if (a.lb) li = a.lb[i];
-      if (a.ub) ui = a.ub[i];
-    }
-    const double sm = svm_row_dots_to_lanes<SVM_EU>(v, wr);
-    double t = 0.0; // y_i x+_i: the row's weight in X'(y o x+)
-    if (act) {
-      const double api = (SUB && yi == 0.0) ? 0.0 : (AUG ? svm_aug_row(yi, sm, sS, sh, pi) : yi * sm);
-      a.Ap[i] = api;
-      if (AUG && (!SUB || yi != 0.0)) sux += yi * xi;
-      s0 += pi * api, s1 += gi * pi;
-      m = pmh_box_feas_v(m, xi, pi, li, ui);
-      if (SPEC) { // k_expansion_std (mpgp.hip) on this entry
-        const double xs = xi + maf * pi, gs = gi + maf * api;
-        double       f, c;
-        pmh_box_split_v(xs, gs, li, ui, a.astol, f, c);
-        const double r = pmh_box_reduced_v(xs, f, li, ui, a.lb != nullptr, a.ub != nullptr, a.alpha), xn = xs + mal * r;
-        a.x_spec[i] = xn;
-        t = yi * xn;
-        if (AUG) ts += t;
+  svm_sweep_rows64_lanes<SVM_EU, SUB, SPEC>(
+    n, X, y, w, a0, a1,
+    [&](long long i, bool act, double ym) {
+      svm_p1_row r = {0.0, 0.0, 0.0, 0.0, -INFINITY, INFINITY, AUG == 1 ? a.shift : 0.0};
+      if (act) {
+        r.yi = SUB ? ym : y[i], r.pi = a.p[i], r.gi = a.g[i], r.xi = a.x[i];
+        if (AUG == 2) r.sh = a.diag[i];
+        if (a.lb) r.li = a.lb[i];
+        if (a.ub) r.ui = a.ub[i];
       }
-    }
-    if (SPEC) {
-#pragma unroll
-      for (int u = 0; u < SVM_EU; u++) {
-        const double tu = __shfl(t, 2 * u + half, 64);
-        a0 += tu * v[u].x, a1 += tu * v[u].y;
+      return r;
+    },
+    [&](long long i, bool act, double sm, svm_p1_row r) {
+      const double yi = r.yi, pi = r.pi, gi = r.gi, xi = r.xi, li = r.li, ui = r.ui, sh = r.sh;
+      double       t = 0.0; // y_i x+_i: the row's weight in X'(y o x+)
+      if (act) {
+        const double api = (SUB && yi == 0.0) ? 0.0 : (AUG ? svm_aug_row(yi, sm, sS, sh, pi) : yi * sm);
+        a.Ap[i] = api;
+        if (AUG && (!SUB || yi != 0.0)) sux += yi * xi;
+        s0 += pi * api, s1 += gi * pi;
+        m = pmh_box_feas_v(m, xi, pi, li, ui);
+        if (SPEC) { // k_expansion_std (mpgp.hip) on this entry
+          const double xs = xi + maf * pi, gs = gi + maf * api;
+          double       f, c;
+          pmh_box_split_v(xs, gs, li, ui, a.astol, f, c);
+          const double rr = pmh_box_reduced_v(xs, f, li, ui, a.lb != nullptr, a.ub != nullptr, a.alpha), xn = xs + mal * rr;
+          a.x_spec[i] = xn;
+          t = yi * xn;
+          if (AUG) ts += t;
+        }
       }
-    }
-  }
+      return t;
+    });
   if (SPEC) svm_fold_cols(a0, a1, lds, a.part_next);
   if (AUG) {
     const double rs = pmh_block_reduce<PMH_RED_SUM>(ts, red), ru = pmh_block_reduce<PMH_RED_SUM>(sux, red);
@@ -364,6 +349,24 @@ static int svm_aux_ready(SvmDualOp *o, bool aug, bool *ok)
   return PMH_SUCCESS;
 }
 
+// Picking a kernel instance: f(std::integral_constant<int, v>()) for the run-time v in [0, N), so that the launch site names its kernel once, with
+// decltype(V)::value as template arguments, and exactly the instances that can be picked are compiled
+template <int N, class F>
+static void svm_const(int v, F f)
+{
+  if constexpr (N > 1) {
+    if (v == N - 1) return f(std::integral_constant<int, N - 1>());
+    return svm_const<N - 1>(v, f);
+  } else f(std::integral_constant<int, 0>());
+}
+// f(A, S): A::value the operator's form out of NAUG (SvmDualBase::aug_form(): 0 plain, 1 scalar shift, 2 diagonal; pass 1 knows 0 and 1 only), S::value 1 under
+// a subset (the SUB = 1 instances, which read the masked labels)
+template <int NAUG, class F>
+static void svm_pick(int form, bool sub, F f)
+{
+  svm_const<NAUG>(form, [&](auto A) { svm_const<2>(sub, [&](auto S) { f(A, S); }); });
+}
+
 // pass 1 and the column sums: w = X'(y o v) and, augmented, w[d] = s = sum_i y_i v_i (+ sum_i y_i u_i -> upart[workgroup] where u is given).  The plain form
 // hands the AUG = 0 kernels null pointers: the kernels of the plain operator, the bits of the plain operator
 int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
@@ -374,27 +377,27 @@ int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
   // which rows, i.e. the summation order of pass 1 (last-digit differences between UNR values; fixed for a given UNR).  Measured 4 / 8 / 12 / 16 on configs[4]:
   // 464 / 452-488 / 433 / 487 iterations per second -- inside the run-to-run spread of the box (the two passes already stream X at the box's copy rate): 4 stays,
   // and only that instance is compiled
-  if (d == 64) SVM_PASS((ym ? (aug ? k_svm_xt64<4, 1, 1> : k_svm_xt64<4, 0, 1>) : (aug ? k_svm_xt64<4, 1, 0> : k_svm_xt64<4, 0, 0>)), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, sp, u, upart);
-  else SVM_PASS((ym ? (aug ? k_svm_xt<1, 1> : k_svm_xt<0, 1>) : (aug ? k_svm_xt<1, 0> : k_svm_xt<0, 0>)), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, v, part, sp, u, upart);
+  svm_pick<2>(aug, ym != nullptr, [&](auto A, auto S) {
+    constexpr int AUG = decltype(A)::value, SUB = decltype(S)::value;
+    if (d == 64) SVM_PASS((k_svm_xt64<4, AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, sp, u, upart);
+    else SVM_PASS((k_svm_xt<AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, v, part, sp, u, upart);
+  });
   hipLaunchKernelGGL(k_svm_colsum, dim3((d + (aug ? 1 : 0) + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)sp);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
 // pass 2: out_i = y_i (x_i . w), augmented + (sigma + sigma_fold) w[d] y_i + shift a_i (or + diag_i a_i)
-// (ym: the operator's masked labels, set under a subset: the SUB = 1 instances)
-#define SVM_K_X64(A) (ym ? k_svm_x64<4, A, 1> : k_svm_x64<4, A, 0>)
-#define SVM_K_X(A) (ym ? k_svm_x<A, 1> : k_svm_x<A, 0>)
-#define SVM_K_GRAD(A) (ym ? k_svm_x64_grad<A, 1> : k_svm_x64_grad<A, 0>)
-#define SVM_K_P1(A) (ym ? k_svm_x64_p1<0, A, 1> : k_svm_x64_p1<0, A, 0>)
-#define SVM_K_P1_SPEC(A) (ym ? k_svm_x64_p1<1, A, 1> : k_svm_x64_p1<1, A, 0>)
 int SvmDualOp::pass2(const double *a, double *out, bool aug)
 {
   const double *ap = aug ? a : nullptr;
   const double  sg = aug ? sigma + sigma_fold : 0.0, sh = aug ? shift : 0.0;
   const int     form = aug ? aug_form() : 0;
   const double *y    = yk();
-  if (d == 64) SVM_PASS(SVM_AUG_PICK(form, SVM_K_X64), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, out, ap, sg, sh, diag);
-  else SVM_PASS(SVM_AUG_PICK(form, SVM_K_X), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, out, ap, sg, sh, diag);
+  svm_pick<3>(form, ym != nullptr, [&](auto A, auto S) {
+    constexpr int AUG = decltype(A)::value, SUB = decltype(S)::value;
+    if (d == 64) SVM_PASS((k_svm_x64<4, AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, out, ap, sg, sh, diag);
+    else SVM_PASS((k_svm_x<AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, out, ap, sg, sh, diag);
+  });
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
@@ -444,7 +447,7 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     a.partials = e.partials, a.feas_part = feas_part, a.part_next = part_next, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
     a.spart_next = spart_next, a.sigma = sg, a.shift = shift, a.diag = diag;
     if (spec && !e.x_out) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: x_from_spec needs x_out");
-    SVM_PASS(SVM_AUG_PICK(form, SVM_K_GRAD), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    svm_pick<3>(form, ym != nullptr, [&](auto A, auto S) { SVM_PASS((k_svm_x64_grad<decltype(A)::value, decltype(S)::value>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a); });
     PMH_HIP(hipGetLastError());
     next_is = NEXT_P, next_p = e.p;
     return PMH_SUCCESS;
@@ -462,7 +465,9 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     a.alpha = e.spec_alpha, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
     a.spart_next = spart_next, a.aux_part = aux ? aux_part : nullptr, a.sigma = sg, a.shift = shift, a.diag = diag;
     const bool spec = paired && e.spec_alpha > 0.0; // afeas is known before this pass only when the gradient pass computed it
-    SVM_PASS((spec ? SVM_AUG_PICK(form, SVM_K_P1_SPEC) : SVM_AUG_PICK(form, SVM_K_P1)), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a);
+    svm_pick<3>(form, ym != nullptr, [&](auto A, auto S) {
+      svm_const<2>(spec, [&](auto P) { SVM_PASS((k_svm_x64_p1<decltype(P)::value, decltype(A)::value, decltype(S)::value>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a); });
+    });
     PMH_HIP(hipGetLastError());
     if (aux) PMH_CHK(aux_finish(grid_epi));
     if (spec) next_is = NEXT_XSPEC;
@@ -528,17 +533,11 @@ int pmh_svm_op_row_is_labels(SvmDualBase *o, pmh_qppf pf, double *c)
     if (rc || bad || y0 == 0.0 || r0 == 0.0) h[0] = 1.0;
     else h[1] = 1.0, h[2] = r0 / y0, h[3] = h[2] * h[2];
   }
-  if (pmh_comm_on(ctx)) {
-    double *d = nullptr;
-    if (pmh_malloc(ctx, sizeof(h), (void **)&d)) return 0;
-    const int rc = pmh_memcpy_h2d(ctx, d, h, sizeof(h)) || pmh_comm_allreduce_sum(ctx, d, 4) || pmh_memcpy_d2h(ctx, h, d, sizeof(h));
-    pmh_free(ctx, d);
-    if (rc) return 0;
-    if (h[0] == 0.0 && h[1] > 0.0) {
-      const double mean = h[2] / h[1];
-      if (fabs(h[3] - h[1] * mean * mean) > 8.0 * 2.220446049250313e-16 * h[3]) return 0; // the ranks' c differ
-      h[2] = mean;
-    }
+  if (pmh_comm_sum_host(ctx, h, 4)) return 0;
+  if (pmh_comm_on(ctx) && h[0] == 0.0 && h[1] > 0.0) {
+    const double mean = h[2] / h[1];
+    if (fabs(h[3] - h[1] * mean * mean) > 8.0 * 2.220446049250313e-16 * h[3]) return 0; // the ranks' c differ
+    h[2] = mean;
   }
   if (h[0] != 0.0 || h[1] == 0.0) return 0;
   *c = h[2];
@@ -609,20 +608,19 @@ extern "C" int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev)
     return PMH_SUCCESS;
   }
   // every rank decides alike: the counts are summed over the communicator before anything is changed
-  int     h[3] = {0, 0, n};
-  double  tot[2];
-  double *d_st = nullptr;
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * 2, (void **)&d_st)); // (the three ints first, then the two sums of the all-reduce)
+  int  h[3] = {0, 0, n};
+  int *d_st = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(h), (void **)&d_st));
   int rc = pmh_memcpy_h2d(ctx, d_st, h, sizeof(h));
   if (!rc && n > 0) {
-    hipLaunchKernelGGL(k_svm_mask_stats, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m_dev, (int *)d_st);
+    hipLaunchKernelGGL(k_svm_mask_stats, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m_dev, d_st);
     if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_op_svm_dual_set_subset: the launch that checks the mask failed");
   }
   if (!rc) rc = pmh_memcpy_d2h(ctx, h, d_st, sizeof(h));
-  tot[0] = (double)h[0], tot[1] = (double)h[1];
-  if (!rc && pmh_comm_on(ctx)) rc = pmh_memcpy_h2d(ctx, d_st, tot, sizeof(tot)) || pmh_comm_allreduce_sum(ctx, d_st, 2) || pmh_memcpy_d2h(ctx, tot, d_st, sizeof(tot));
   pmh_free(ctx, d_st);
   PMH_CHK(rc);
+  double tot[2] = {(double)h[0], (double)h[1]};
+  PMH_CHK(pmh_comm_sum_host(ctx, tot, 2));
   if (tot[0] != 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_subset: %lld entries of the mask are neither 0 nor 1", (long long)tot[0]);
   if (tot[1] == 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_subset: the mask holds no sample (all zero)");
   if (!o->msk) {

@@ -5,14 +5,12 @@
 #define SVM_KMAX 4 // d <= 64 * SVM_KMAX
 // grid of the row sweeps over n samples (svm_rows.h): 64 rows per workgroup, capped
 #define SVM_NB(n) ((int)((((long long)(n) + 63) / 64) < 1 ? 1 : ((((long long)(n) + 63) / 64) > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : (((long long)(n) + 63) / 64))))
-// a launch that streams X once (counted: pmh_op_svm_dual_passes); a kernel given as a template-id with a comma, or chosen by ?:, goes in parentheses
+// a launch that streams X once (counted: pmh_op_svm_dual_passes); a kernel given as a template-id with a comma goes in parentheses
 #define SVM_PASS(...)                 \
   do {                                \
     npass++;                          \
     hipLaunchKernelGGL(__VA_ARGS__);  \
   } while (0)
-// the instance of a pass-2 kernel for SvmDualBase::aug_form(): K(0) plain, K(1) scalar shift, K(2) diagonal
-#define SVM_AUG_PICK(form, K) ((form) == 2 ? K(2) : ((form) == 1 ? K(1) : K(0)))
 
 // What the penalised operator (qppf.hip) and the front end (svm_train.hip) need of an SVM dual operator, whichever way it holds the samples: dense rows
 // (SvmDualOp, svm.hip) or CSR (SvmCsrOp, svm_csr.hip)

@@ -1,6 +1,11 @@
-// The two row sweeps of the dense SVM kernels (svm.hip, svm_train.hip), each written once: what a kernel does with row i's dot product x_i . w is a functor
-// f(i, dot).  Device code only (svm_internal.h is what qppf.hip sees).  The loads, their order and the summation order are the kernels' bits: k ascending
-// then pmh_wave_sum for any d, the two products then the 16-8-4-2-1 tree of the half-wave for d = 64.
+// The row sweeps of the dense SVM kernels (svm.hip, svm_train.hip), each written once:
+//   svm_sweep_rows<SUB>            any d: one wavefront per row; what a kernel does with row i's dot product x_i . w is a functor f(i, dot)
+//   svm_sweep_rows64<UNR, SUB>     d = 64: two rows per wave-instruction, UNR row pairs in flight; f(i, dot) as above
+//   svm_sweep_rows64_lanes<UNR, SUB, NEXT>  d = 64, the paired passes: the rows' dot products handed out one per lane, the row's scalars asked for up front by a
+//                                  functor pre, the elementwise work a functor row; NEXT: the rows' weights t_i accumulated into the column sums X't on the way
+// (k_svm_xt64, pass 1 for d = 64, keeps a row loop of its own in svm.hip: it needs y_i a_i in every lane of the half-wave.)
+// Device code only (svm_internal.h is what qppf.hip sees).  The loads, their order and the summation order are the kernels' bits: k ascending then pmh_wave_sum
+// for any d, the two products then the 16-8-4-2-1 tree of the half-wave for d = 64.
 #pragma once
 #include "reduce.h"
 #include "svm_internal.h"
@@ -92,6 +97,14 @@ static __device__ __forceinline__ double svm_row_dots_to_lanes(const dbl2 (&v)[U
   }
   return sm;
 }
+// the rows from r0 on with or without a subset, the one place that chooses: SUB = 0 loads them all and leaves yi alone; SUB = 1 takes the masked labels first
+// (svm_live_rows64: lane j < 2 UNR gets that of row r0 + j in yi) and loads the rows of the subset only
+template <int UNR, int SUB>
+static __device__ __forceinline__ void svm_load_rows64_sub(int n, const double *__restrict__ X, const double *__restrict__ ym, long long r0, dbl2 (&v)[UNR], double &yi)
+{
+  if (SUB) svm_load_rows64<UNR, SUB>(n, X, r0, v, svm_live_rows64<UNR>(n, ym, r0, yi));
+  else svm_load_rows64<UNR>(n, X, r0, v);
+}
 // f(i, x_i . w) in the first lane of the half-wave that owns row i
 template <int UNR, int SUB = 0, class F>
 static __device__ __forceinline__ void svm_sweep_rows64(int n, const double *__restrict__ X, const double *__restrict__ w, F f, const double *__restrict__ ym = nullptr)
@@ -100,16 +113,46 @@ static __device__ __forceinline__ void svm_sweep_rows64(int n, const double *__r
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   const dbl2      wr = ((const dbl2 *)w)[l2];
   for (long long r0 = gw * 2 * UNR; r0 < n; r0 += nw * 2 * UNR) {
-    dbl2 v[UNR];
-    if (SUB) {
-      double yi;
-      svm_load_rows64<UNR, SUB>(n, X, r0, v, svm_live_rows64<UNR>(n, ym, r0, yi));
-    } else svm_load_rows64<UNR>(n, X, r0, v);
+    dbl2   v[UNR];
+    double yi;
+    svm_load_rows64_sub<UNR, SUB>(n, X, ym, r0, v, yi);
 #pragma unroll
     for (int u = 0; u < UNR; u++) {
       const long long i = r0 + 2 * u + half;
       const double    s = svm_row_dot(v[u], wr);
       if (l2 == 0 && i < n) f(i, s);
+    }
+  }
+}
+
+// The row loop of the paired passes (k_svm_x64_grad, k_svm_x64_p1 in svm.hip).  The rows' dot products land in the first lane of each half-wave; lane
+// j < 2 UNR then takes row i = r0 + j (u = j >> 1, half = j & 1; act: it has one) and does the row's elementwise work once: ONE coalesced load per vector
+// for the 2 UNR rows (a load per row costs the address unit a whole instruction each: measured 2 x the time of the plain pass).
+//   sc = pre(i, act, ym)   asks for the row's scalars, the label among them, BEFORE the dot products, so that they travel with the rows of X.  SUB: ym is the
+//                          row's masked label, which the loads have read already (a held-out row is not loaded); SUB = 0: ym is 0 and pre reads the label
+//   t = row(i, act, dot, sc)  the elementwise work; t is the row's weight in the column sums that the NEXT pass 1 would form (0 where !act)
+// NEXT: a0, a1 += t_i x_i for the two columns this lane holds of its half-wave's rows (svm_fold_cols finishes them)
+template <int UNR, int SUB, int NEXT, class PRE, class ROW>
+static __device__ __forceinline__ void svm_sweep_rows64_lanes(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double &a0, double &a1, PRE pre, ROW row)
+{
+  const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
+  const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
+  const dbl2      wr = ((const dbl2 *)w)[l2];
+  for (long long r0 = gw * 2 * UNR; r0 < n; r0 += nw * 2 * UNR) {
+    dbl2   v[UNR];
+    double ym = 0.0;
+    svm_load_rows64_sub<UNR, SUB>(n, X, y, r0, v, ym);
+    const long long i   = r0 + lane;
+    const bool      act = lane < 2 * UNR && i < n;
+    const auto      sc  = pre(i, act, ym);
+    const double    sm  = svm_row_dots_to_lanes<UNR>(v, wr);
+    const double    t   = row(i, act, sm, sc);
+    if (NEXT) {
+#pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        const double tu = __shfl(t, 2 * u + half, 64);
+        a0 += tu * v[u].x, a1 += tu * v[u].y;
+      }
     }
   }
 }

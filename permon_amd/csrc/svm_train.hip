@@ -203,12 +203,17 @@ extern "C" int pmh_svm_destroy(pmh_svm s)
   return PMH_SUCCESS;
 }
 
+// the solvers hold the operator and the projector: whoever changes or replaces either drops them first
+static void svm_drop_solver(pmh_svm s)
+{
+  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
+  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
+}
 // The solver over the handle's operator, vectors and projector: SMALXE (bias) or MPGP.  Both size their steps and penalties by the operator's largest
 // eigenvalue, estimated at creation: whoever changes the operator's terms (pmh_svm_set_penalties, L2) builds the solver anew
 static int svm_build_solver(pmh_svm s)
 {
-  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
-  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
+  svm_drop_solver(s);
   if (s->o.bias) {
     pmh_smalxe_opts so = s->o.smalxe;
     so.rtol = s->o.qps.rtol, so.atol = s->o.qps.atol, so.divtol = s->o.qps.divtol;
@@ -268,7 +273,7 @@ static int svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_
   int          rc = PMH_SUCCESS;
   do {
     if ((rc = Xcsr ? pmh_op_create_svm_dual_csr(ctx, Xcsr, y_dev, &s->H) : pmh_op_create_svm_dual(ctx, n, d, X_dev, y_dev, &s->H))) break;
-    if (opts->loss_type == PMH_SVM_LOSS_L2 && (rc = pmh_op_svm_dual_set_terms(s->H, 1.0 / opts->C, 0.0))) break;
+    if ((rc = svm_refresh_l2(s))) break;
     if ((rc = pmh_malloc(ctx, nb, (void **)&s->alpha)) || (rc = pmh_malloc(ctx, nb, (void **)&s->rhs)) || (rc = pmh_malloc(ctx, nb, (void **)&s->lb))) break;
     if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)d, (void **)&s->w)) || (rc = pmh_malloc(ctx, sizeof(double) * 4 * PMH_MAX_VEC_BLOCKS, (void **)&s->part)) || (rc = pmh_malloc(ctx, sizeof(double) * 8, (void **)&s->scal))) break;
     if ((rc = pmh_memset(ctx, s->alpha, 0, nb)) || (rc = pmh_memset(ctx, s->lb, 0, nb)) || (rc = pmh_vec_set(ctx, n, s->rhs, 1.0))) break;
@@ -277,22 +282,14 @@ static int svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_
     }
     // the number of samples over all ranks (the row of the equality is y / sqrt(n))
     double ng = (double)n;
-    if (pmh_comm_on(ctx)) {
-      if ((rc = pmh_vec_set(ctx, 1, s->scal, ng)) || (rc = pmh_comm_allreduce_sum(ctx, s->scal, 1)) || (rc = pmh_memcpy_d2h(ctx, &ng, s->scal, sizeof(double)))) break;
-    }
+    if ((rc = pmh_comm_sum_host(ctx, &ng, 1))) break;
     s->n_global = (long long)ng;
     if (opts->bias) {
       if (s->n_global < 1) {
         rc = pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: no samples");
         break;
       }
-      if ((rc = pmh_malloc(ctx, nb, (void **)&s->row))) break;
-      if (n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, y_dev, 1.0 / sqrt(ng), s->row);
-      if (hipGetLastError() != hipSuccess) {
-        rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_create: the launch that fills the equality's row failed");
-        break;
-      }
-      if ((rc = pmh_qppf_create_onerow(ctx, s->row, n, &s->pf))) break;
+      if ((rc = pmh_malloc(ctx, nb, (void **)&s->row)) || (rc = svm_refresh_row(s))) break;
     }
     if ((rc = svm_build_solver(s))) break;
   } while (0);
@@ -475,11 +472,7 @@ extern "C" int pmh_svm_set_penalties(pmh_svm s, double C_pos, double C_neg, cons
     pmh_free(ctx, d_bad);
     PMH_CHK(rc);
     double nbad = (double)bad;
-    if (pmh_comm_on(ctx)) {
-      PMH_CHK(pmh_vec_set(ctx, 1, s->scal, nbad));
-      PMH_CHK(pmh_comm_allreduce_sum(ctx, s->scal, 1));
-      PMH_CHK(pmh_memcpy_d2h(ctx, &nbad, s->scal, sizeof(double)));
-    }
+    PMH_CHK(pmh_comm_sum_host(ctx, &nbad, 1));
     if (nbad != 0.0)
       return pmh_set_error(PMH_ERR_ARG, "pmh_svm_set_penalties: %lld of the sample weights are not positive and finite (or give a penalty C_i that is not); a zero weight does not leave a sample out: pmh_svm_set_subset does",
                            (long long)nbad);
@@ -502,17 +495,16 @@ extern "C" int pmh_svm_get_penalties(pmh_svm s, double *c_dev)
   return pmh_vec_set(s->ctx, s->n, c_dev, s->o.C);
 }
 
-// New labels on the created handle: everything svm_create derived from y is redone in svm_create's order (the operator's labels, the penalties back to the
-// scalar C, the equality's row and its projector, the solver), so a training afterwards gives what a fresh handle on (X, y_dev) gives, bit for bit
+// New labels on the created handle: everything svm_create derived from y is redone by the calls svm_create makes (svm_refresh_l2, svm_refresh_row,
+// svm_build_solver) after the operator's labels and the penalties, which go back to the scalar C: a training afterwards gives what a fresh handle on (X, y_dev)
+// gives, bit for bit
 extern "C" int pmh_svm_set_labels(pmh_svm s, const double *y_dev)
 {
   PMH_ARG(s && y_dev);
   pmh_ctx   ctx = s->ctx;
   const int n   = s->n;
   s->trained = s->calibrated = 0;
-  // the solvers hold the operator and the projector: they go first
-  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
-  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
+  svm_drop_solver(s);
   PMH_CHK(pmh_op_svm_dual_set_labels(s->H, y_dev));
   s->y = y_dev;
   if (s->o.loss_type != PMH_SVM_LOSS_L2) PMH_CHK(pmh_vec_set(ctx, n, s->ub, s->o.C));
@@ -535,16 +527,11 @@ extern "C" int pmh_svm_set_subset(pmh_svm s, const double *m_dev)
   SvmDualBase *H   = static_cast<SvmDualBase *>(s->H);
   PMH_CHK(pmh_op_svm_dual_set_subset(s->H, m_dev)); // (checks the mask before anything changes; the solvers only hold the operator)
   s->trained = s->calibrated = 0;
-  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
-  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
+  svm_drop_solver(s);
   s->n_sub = 0;
   if (m_dev) {
     double ns = (double)H->n_sub; // all-reduced as n_global is
-    if (pmh_comm_on(ctx)) {
-      PMH_CHK(pmh_vec_set(ctx, 1, s->scal, ns));
-      PMH_CHK(pmh_comm_allreduce_sum(ctx, s->scal, 1));
-      PMH_CHK(pmh_memcpy_d2h(ctx, &ns, s->scal, sizeof(double)));
-    }
+    PMH_CHK(pmh_comm_sum_host(ctx, &ns, 1));
     s->n_sub = (long long)ns;
     PMH_CHK(pmh_vec_copy(ctx, s->n, H->msk, s->rhs));
   } else PMH_CHK(pmh_vec_set(ctx, s->n, s->rhs, 1.0));

@@ -1,7 +1,8 @@
 """What a sample subset on the SVM dual operator costs or saves in time (docs/LAB_NOTEBOOK.md, "SVM subsets"): one process, one GPU.
 
 --what product: L1-loss dual without bias, MPGP on H_S for a fixed number of iterations with no subset, a random subset and a contiguous subset of the share
-`--share` of the samples (dense rows: --d; CSR: --csr N_FEATURES NNZ_ROW).  A subset changes the problem, hence the steps; the figure that compares is the time
+`--share` of the samples (dense rows: --d; CSR: --csr N_FEATURES NNZ_ROW).  `--shift S` / `--diag` put the scalar shift / a diagonal on the operator, so that
+the AUG = 1 / AUG = 2 instances of the dense kernels run in place of the plain ones; `--unbounded` makes every step a CG step (k_svm_x64_p1<0, ...>).  A subset changes the problem, hence the steps; the figure that compares is the time
 per pass over X (every variant's windows count their own passes).  Windows of `--steps` iterations from the zero iterate after `--warmup` iterations, the
 variants alternated `--rounds` times, timed by a host clock around work that ends in a device synchronise.  `--variants none` runs on a library without the
 subset entries too (the parent commit's, for the A/B of the unchanged instances).
@@ -30,17 +31,22 @@ from permon_amd._lib import check  # noqa: E402
 class Fixed:
     """MPGP on H_S (rhs = m, 0 <= a <= C) that runs exactly k iterations from the zero iterate."""
 
-    def __init__(self, ctx, p, mask):
+    def __init__(self, ctx, p, mask, shift=0.0, diag=None, unbounded=False):
         n = p["n"]
         self.ctx, self.H = ctx, pa.MatCreateSVMDual(ctx, p["X"], p["y"])
         if mask is not None:
             self.H.set_subset(mask)
+        if shift:
+            self.H.set_terms(shift, 0.0)  # (the AUG = 1 kernel instances)
+        if diag is not None:
+            self.H.set_diag(diag)  # (AUG = 2)
         qp = pa.QP(ctx)
         qp.SetOperator(self.H)
         qp.SetRhs(ctx.vec_from(np.ones(n) if mask is None else mask.astype(float)))
         self.x = ctx.vec_from(np.zeros(n))
         qp.SetInitialVector(self.x)
-        qp.SetBox(None, ctx.vec_from(np.zeros(n)), ctx.vec_from(np.full(n, float(p["C"]))))
+        # (unbounded: bounds nothing reaches, so MPGP takes CG steps alone: pass 1 and k_svm_x64_p1<0, ...>, which the expansion steps of the box hardly run)
+        qp.SetBox(None, ctx.vec_from(np.full(n, -1e300 if unbounded else 0.0)), ctx.vec_from(np.full(n, 1e300 if unbounded else float(p["C"]))))
         self.qps = pa.QPS(ctx)
         self.qps.SetQP(qp)
         self.qps.SetType("mpgp")
@@ -68,7 +74,8 @@ def product(a, ctx, p, res):
     n = p["n"]
     rng = np.random.default_rng(5)
     masks = dict(none=None, random=rng.random(n) < a.share, contiguous=np.arange(n) < int(a.share * n))
-    solvers = {k: Fixed(ctx, p, masks[k]) for k in a.variants.split(",")}
+    diag = ctx.vec_from(rng.uniform(0.5, 2.0, n)) if a.diag else None  # (one device vector, shared by the variants)
+    solvers = {k: Fixed(ctx, p, masks[k], a.shift, diag, a.unbounded) for k in a.variants.split(",")}
     for s in solvers.values():
         s.run(a.warmup)
     runs = {k: [] for k in solvers}
@@ -129,6 +136,9 @@ def main():
     ap.add_argument("--csr", type=int, nargs=2, default=None, metavar=("N_FEATURES", "NNZ_ROW"))
     ap.add_argument("--share", type=float, default=0.8)
     ap.add_argument("--variants", default="none,random,contiguous")
+    ap.add_argument("--shift", type=float, default=0.0, help="product: H + shift I (the operator's scalar-shift kernels); excludes --diag")
+    ap.add_argument("--unbounded", action="store_true", help="product: bounds of +-1e300 in place of 0 <= a <= C: CG steps only (use with --shift or --diag: H alone is singular)")
+    ap.add_argument("--diag", action="store_true", help="product: H + diag(D), D uniform in [0.5, 2) (the operator's diagonal kernels)")
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--rtol", type=float, default=1e-3)
     ap.add_argument("--steps", type=int, default=100)
@@ -138,7 +148,7 @@ def main():
     a = ap.parse_args()
     ctx = pa.Context(0)
     p = P.svm_sparse(a.n, a.csr[0], a.csr[1], 1.0, 0.5, 1.0) if a.csr else P.svm_offset(a.n, a.d, 3.0)
-    res = dict(device=ctx.name(), what=a.what, n=p["n"], d=a.csr[0] if a.csr else a.d, csr=bool(a.csr), nnz=int(p["X"].nnz) if a.csr else None, steps=a.steps, warmup=a.warmup, rounds=a.rounds)
+    res = dict(device=ctx.name(), what=a.what, shift=a.shift, diag=bool(a.diag), unbounded=bool(a.unbounded), n=p["n"], d=a.csr[0] if a.csr else a.d, csr=bool(a.csr), nnz=int(p["X"].nnz) if a.csr else None, steps=a.steps, warmup=a.warmup, rounds=a.rounds)
     (product if a.what == "product" else cv)(a, ctx, p, res)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
