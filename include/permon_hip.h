@@ -460,6 +460,13 @@ int pmh_qpt_feti_chain_kkt(pmh_feti_chain chain, pmh_blockdiag K, const double *
 /* H = diag(y) X X' diag(y), X: n_local x d row-major in HBM (d <= 256), applied as two GEMV passes; with a
    communicator the samples are sharded by rows and w = X'(y o a) is all-reduced (d doubles) between the passes */
 int pmh_op_create_svm_dual(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, pmh_op *op);
+/* The same operator over samples stored in float32 (X_dev: n_local x d floats, row-major, borrowed): half the device memory and half the traffic of X per pass.
+   Only the storage of X changes: a float enters the arithmetic as (double)x, which is exact; w, every n-vector, every partial sum and the all-reduce stay fp64.
+   Any d but 64: the kernels of the fp64 operator with another load, bit for bit what pmh_op_create_svm_dual gives on the widened samples.  d = 64: a layout
+   of its own on 16-byte loads (four rows per wave-instruction), whose summation order is fixed (no float atomics; two runs give the same bits) but is not the fp64
+   layout's: results agree with the fp64 operator's to rounding.  Terms, diagonal, subsets, labels, the paired passes and a communicator work as on the fp64
+   operator; same limits (d <= 256) */
+int pmh_op_create_svm_dual_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, const double *y_dev, pmh_op *op);
 /* how many times the operator has streamed X since it was created (2 per plain application; inside pmh_mpgp_solve on one GPU with d = 64 the second pass of an
    application also does the first pass of the next one wherever the MPGP step allows it -- svm.hip, "paired passes" -- so a run of expansion steps costs 2 passes
    per step instead of 4): what a bandwidth figure for this operator has to be computed from */
@@ -593,6 +600,10 @@ int pmh_svm_default_opts(pmh_svm_opts *o);
 int pmh_svm_set_from_options(const char *options, pmh_svm_opts *o, char *unknown, int unknown_cap);
 /* X_dev (n_local x d, d <= 256) and y_dev are borrowed: the caller keeps them alive and unchanged.  Under a communicator the samples are sharded by rows */
 int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *svm);
+/* The training samples stored in float32 (pmh_op_create_svm_dual_f32): X_dev is n_local x d floats.  alpha, w, b, the solvers and the model stay fp64 and every
+   other entry (set_labels, set_penalties, set_subset, train, predict_own, test_own, ...) works unchanged on the handle.  d != 64: a training gives bit for bit
+   what pmh_svm_create gives on the widened samples */
+int pmh_svm_create_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *svm);
 int pmh_svm_train(pmh_svm svm);                                     /* from a = 0: MPGP (no bias) or SMALXE + MPGP (bias), then the model */
 int pmh_svm_get_model(pmh_svm svm, double *w_host /* d doubles, or NULL */, double *b /* or NULL */);
 int pmh_svm_get_dual(pmh_svm svm, double *alpha_dev);               /* n_local doubles */
@@ -636,6 +647,10 @@ int pmh_svm_test_own(pmh_svm svm, int which, long long counts[4]);
 int pmh_svm_predict(pmh_svm svm, int n, const double *X_dev, double *scores_dev, double *labels_dev);
 /* one pass: counts = (TP, FP, TN, FN) of the predicted labels against y_dev (summed over the ranks under a communicator) */
 int pmh_svm_test(pmh_svm svm, int n, const double *X_dev, const double *y_dev, long long counts[4]);
+/* Test samples in float32 (n x d floats), for any handle with d <= 256 whatever it was trained on -- fp64, float32 or CSR samples; a handle created on float32
+   samples likewise scores fp64 and CSR test samples through the entries above and below.  Same limits and messages as the fp64 entries */
+int pmh_svm_predict_f32(pmh_svm svm, int n, const float *X_dev, double *scores_dev, double *labels_dev);
+int pmh_svm_test_f32(pmh_svm svm, int n, const float *X_dev, const double *y_dev, long long counts[4]);
 /* Samples in CSR (any d; see pmh_op_create_svm_dual_csr): X and y_dev borrowed.  Every other entry works unchanged on the handle.  Test samples may come in
    either form whatever the training samples were: pmh_svm_predict / pmh_svm_test need d <= 256, the _csr entries a matrix of the model's d columns; a
    mismatch is PMH_ERR_ARG */
@@ -698,10 +713,12 @@ int pmh_svm_platt_fit(pmh_ctx ctx, int n, const double *scores_dev, const double
  * pmh_svm_set_penalties clear it.  predict_proba: proba_dev[i] = 1 / (1 + exp(A (x_i . w + b) + B)) in ONE pass over the samples, the dot product summed as
  * pmh_svm_predict sums it.  Untrained handle (calibrate), no calibration (predict_proba, get_calibration): PMH_ERR_STATE */
 int pmh_svm_calibrate(pmh_svm svm, int n, const double *X_dev, const double *y_dev);
+int pmh_svm_calibrate_f32(pmh_svm svm, int n, const float *X_dev, const double *y_dev); /* the calibration samples in float32 (pmh_svm_predict_f32's scores) */
 int pmh_svm_calibrate_csr(pmh_svm svm, pmh_csr Xt, const double *y_dev);
 int pmh_svm_set_calibration(pmh_svm svm, double A, double B);
 int pmh_svm_get_calibration(pmh_svm svm, double *A, double *B, pmh_svm_platt_stats *st /* or NULL */);
 int pmh_svm_predict_proba(pmh_svm svm, int n, const double *X_dev, double *proba_dev);
+int pmh_svm_predict_proba_f32(pmh_svm svm, int n, const float *X_dev, double *proba_dev); /* the samples in float32 */
 int pmh_svm_predict_proba_csr(pmh_svm svm, pmh_csr Xt, double *proba_dev);
 /* One-vs-rest: one scoring call (pmh_svm_multi_predict's), then K fits, fit k on column k of the scores with "label == c_k" as +1 and every other label (a
  * value that is no class included) as -1.  predict_proba (n x K): sigma_ik = 1 / (1 + exp(A_k S[i,k] + B_k)) written by the scoring sweeps, then every row

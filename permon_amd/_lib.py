@@ -253,6 +253,7 @@ _PROTOS = {
     "pmh_qpt_feti_chain_destroy": [vp],
     "pmh_qpt_feti_chain_kkt": [vp, vp, vp, vp, vp, vp],
     "pmh_op_create_svm_dual": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)],
+    "pmh_op_create_svm_dual_f32": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)],
     "pmh_op_create_svm_dual_csr": [vp, vp, vp, C.POINTER(vp)],
     "pmh_op_svm_dual_passes": [vp, C.POINTER(C.c_longlong)],
     "pmh_op_svm_dual_set_terms": [vp, C.c_double, C.c_double],
@@ -270,6 +271,11 @@ _PROTOS = {
     "pmh_svm_get_penalties": [vp, vp],
     "pmh_svm_predict": [vp, C.c_int, vp, vp, vp],
     "pmh_svm_test": [vp, C.c_int, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_create_f32": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvmOpts), C.POINTER(vp)],
+    "pmh_svm_predict_f32": [vp, C.c_int, vp, vp, vp],
+    "pmh_svm_test_f32": [vp, C.c_int, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_calibrate_f32": [vp, C.c_int, vp, vp],
+    "pmh_svm_predict_proba_f32": [vp, C.c_int, vp, vp],
     "pmh_svm_create_csr": [vp, vp, vp, C.POINTER(SvmOpts), C.POINTER(vp)],
     "pmh_svm_predict_csr": [vp, vp, vp, vp],
     "pmh_svm_test_csr": [vp, vp, vp, C.POINTER(C.c_longlong)],

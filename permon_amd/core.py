@@ -179,6 +179,69 @@ class Vec:
         return r.value
 
 
+class VecF32:
+    """float32 device array: storage only (the samples of an SVM kept in float32), no arithmetic.  `.p` is the raw device pointer, `.n` the number of floats."""
+
+    def __init__(self, ctx, n):
+        self.ctx, self.n = ctx, int(n)
+        p = C.c_void_p()
+        check(ctx.L.pmh_malloc(ctx.h, 4 * max(self.n, 1), C.byref(p)))
+        self.p = p
+
+    @classmethod
+    def from_numpy(cls, ctx, a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        v = cls(ctx, a.size)
+        v.set_numpy(a)
+        return v
+
+    def set_numpy(self, a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        assert a.size == self.n
+        check(self.ctx.L.pmh_memcpy_h2d(self.ctx.h, self.p, a.ctypes.data_as(C.c_void_p), 4 * a.size))
+
+    def to_numpy(self):
+        a = np.empty(self.n, dtype=np.float32)
+        check(self.ctx.L.pmh_memcpy_d2h(self.ctx.h, a.ctypes.data_as(C.c_void_p), self.p, 4 * self.n))
+        return a
+
+    def free(self):
+        if self.p:
+            self.ctx.L.pmh_free(self.ctx.h, self.p)
+        self.p = None
+
+
+def sample_array(X, dt, who):
+    """The dense samples X as the contiguous host array that goes to the device in the type dt (sample_dtype_of's answer): float64 widens whatever X holds, as
+    ever; float32 keeps float32 and rounds anything else -- a finite value that rounding makes non-finite is refused."""
+    if dt is not np.float32:
+        return np.ascontiguousarray(X, dtype=np.float64)
+    X = np.asarray(X)
+    if X.dtype == np.float32:
+        return np.ascontiguousarray(X)
+    with np.errstate(over="ignore"):
+        X32 = np.ascontiguousarray(X, dtype=np.float32)
+    lost = np.isfinite(X) & ~np.isfinite(X32)
+    if lost.any():
+        raise ValueError("%s: %d finite values of the samples are not finite in float32 (beyond %.3g in magnitude)" % (who, int(lost.sum()), np.finfo(np.float32).max))
+    return X32
+
+
+def sample_dtype_of(sample_dtype, sparse, who):
+    """numpy.float64 or numpy.float32 for the sample_dtype argument; float32 with sparse samples is refused: CSR values stay fp64."""
+    if sample_dtype is None:
+        return np.float64
+    try:
+        dt = np.dtype(sample_dtype)
+    except TypeError:
+        dt = None
+    if dt is None or dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("%s: sample_dtype must be numpy.float32, numpy.float64 or None, not %r" % (who, sample_dtype))
+    if sparse and dt == np.float32:
+        raise ValueError("%s: sample_dtype = float32 with sparse samples: the values of a CSR matrix stay fp64" % who)
+    return dt.type
+
+
 def _ptr(v):
     return v.p if v is not None else None
 

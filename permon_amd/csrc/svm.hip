@@ -5,8 +5,8 @@
 // is "parity unpinned" beyond the MPGP solver that calls it; the oracle side of its test is a numpy restatement.
 // HBM-bound: algorithmic bytes per apply 2*8*N*d + 40*N (X read twice; a, y read, Ha written, y read again).
 // Samples shard over GPUs by rows; the only exchange is the all-reduce of w (d doubles) between the passes.
-#include <type_traits>
-
+// The samples are stored in fp64 or in float32 (pmh_op_create_svm_dual_f32: 4 bytes per feature in memory and in every pass, 2*4*N*d + 40*N per apply); a float
+// is widened where it is loaded and everything else -- w, the n-vectors, every sum, the all-reduce -- is fp64 either way (svm_rows.h).
 #include "pmh_internal.h"
 #include "reduce.h"
 #include "box_inline.h"
@@ -18,8 +18,9 @@
 // AUG: also s = sum_i y_i a_i (-> spart[workgroup]) and, where u is given, sum_i y_i u_i (-> upart[workgroup]); every lane of a wave holds the same two sums
 // SUB (every kernel below that has it): y holds the masked labels m_i y_i of a sample subset (pmh_op_svm_dual_set_subset); it is read first, and a held-out row
 // (y_i == 0) is not loaded and adds to no sum, whatever a_i holds.  SUB = 0: the kernels without subsets
-template <int AUG, int SUB>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
+// T (every kernel below that has it): the type the samples are stored in, double or float; a float is widened where it is loaded and the arithmetic is the same
+template <int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const T *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
                                                       double *__restrict__ spart, const double *__restrict__ u, double *__restrict__ upart)
 {
   __shared__ double lds[PMH_BLOCK / 64][64 * SVM_KMAX];
@@ -32,8 +33,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double
   for (int k = 0; k < SVM_KMAX; k++) acc[k] = 0.0;
   for (long long i = gw; i < n; i += nw) {
     if (SUB && y[i] == 0.0) continue; // (uniform over the wave)
-    const double  s  = y[i] * a[i];
-    const double *xr = X + (size_t)i * d;
+    const double s  = y[i] * a[i];
+    const T     *xr = X + (size_t)i * d;
     if (AUG) {
       as += s;
       if (u) au += y[i] * u[i];
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt(int n, int d, const double
 #pragma unroll
     for (int k = 0; k < SVM_KMAX; k++) {
       const int c = lane + 64 * k;
-      if (c < d) acc[k] += s * __builtin_nontemporal_load(&xr[c]);
+      if (c < d) acc[k] += s * (double)__builtin_nontemporal_load(&xr[c]);
     }
   }
   if (AUG && lane == 0) sred[0][wave] = as, sred[AUG][wave] = au;
@@ -79,25 +80,31 @@ static __device__ __forceinline__ void svm_colsum(int nblocks, int d, const doub
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart) { svm_colsum(nblocks, d, part, w, spart); }
 
 // pass 2: (H a)_i = y_i (x_i . w); AUG 1: + sigma s y_i + shift a_i; AUG 2: + sigma s y_i + diag_i a_i
-template <int AUG, int SUB>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
+template <int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const T *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
                                                      const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[d] : 0.0;
   svm_sweep_rows<SUB>(n, d, X, w, [&](long long i, double s) { Ha[i] = (SUB && y[i] == 0.0) ? 0.0 : (AUG ? svm_aug_row(y[i], s, sS, AUG == 2 ? diag[i] : shift, a[i]) : y[i] * s); }, y);
 }
 
-// ---- d == 64 fast path: the two-rows-per-wave-instruction layout of svm_rows.h, 4-fold unroll ----
-// the two column sums a lane holds (columns 2 l2, 2 l2 + 1 of the rows its half of the wave visited) -> part[workgroup][64]: lanes l and l + 32 hold the same
-// two columns of different rows: fold, then across the 4 waves in order
-static __device__ __forceinline__ void svm_fold_cols(double a0, double a1, double (*lds)[64], double *__restrict__ part)
+// ---- d == 64 fast path: the RPI-rows-per-wave-instruction layout of svm_rows.h (double: 2 rows, float: 4), 4-fold unroll ----
+// the CPL column sums a lane holds (double: columns 2 l2, 2 l2 + 1; float: columns 4 q .. 4 q + 3, of the rows its LPR lanes visited) -> part[workgroup][64]:
+// lanes l, l + LPR, ... hold the same columns of different rows: fold by halving, double: l + (l + 32); float: (q + (q + 32)) + ((q + 16) + (q + 48)); then
+// across the 4 waves in order
+template <class T>
+static __device__ __forceinline__ void svm_fold_cols(double (&acc)[svm_row64<T>::CPL], double (*lds)[64], double *__restrict__ part)
 {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
-  a0 += __shfl_down(a0, 32, 64);
-  a1 += __shfl_down(a1, 32, 64);
-  if (half == 0) {
-    lds[wave][2 * l2]     = a0;
-    lds[wave][2 * l2 + 1] = a1;
+  typedef svm_row64<T> R;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane / R::LPR, lq = lane & (R::LPR - 1);
+#pragma unroll
+  for (int o = 32; o >= R::LPR; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < R::CPL; c++) acc[c] += __shfl_down(acc[c], o, 64);
+  }
+  if (sub == 0) {
+#pragma unroll
+    for (int c = 0; c < R::CPL; c++) lds[wave][R::CPL * lq + c] = acc[c];
   }
   __syncthreads();
   if (threadIdx.x < 64) {
@@ -107,37 +114,42 @@ static __device__ __forceinline__ void svm_fold_cols(double a0, double a1, doubl
     part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
   }
 }
-template <int SVM_UNR, int AUG, int SUB>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
+// pass 1 for d = 64.  A wave takes RPI SVM_UNR rows at a time, rows r0 + RPI u + sub to the LPR lanes sub; a lane's column sums take its rows in the order
+// it visits them (u ascending within a group, groups ascending), then svm_fold_cols
+template <int SVM_UNR, int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const T *__restrict__ X, const double *__restrict__ y, const double *__restrict__ a, double *__restrict__ part,
                                                         double *__restrict__ spart, const double *__restrict__ uu, double *__restrict__ upart)
 {
+  typedef svm_row64<T> R;
   __shared__ double lds[PMH_BLOCK / 64][64];
   __shared__ double red[PMH_BLOCK / 64];
-  double            as = 0.0, au = 0.0; // AUG: sum_i y_i a_i, sum_i y_i u_i, taken by the first lane of each half-wave for its rows
-  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
+  double            as = 0.0, au = 0.0; // AUG: sum_i y_i a_i, sum_i y_i u_i, taken by the first of the LPR lanes of a row for its rows
+  const int         lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane / R::LPR, lq = lane & (R::LPR - 1);
   const long long   gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
-  double            a0 = 0.0, a1 = 0.0;
-  for (long long r0 = gw * 2 * SVM_UNR; r0 < n; r0 += nw * 2 * SVM_UNR) {
-    dbl2   v[SVM_UNR];
-    double s[SVM_UNR];
+  double            acc[R::CPL];
+#pragma unroll
+  for (int c = 0; c < R::CPL; c++) acc[c] = 0.0;
+  for (long long r0 = gw * R::RPI * SVM_UNR; r0 < n; r0 += nw * R::RPI * SVM_UNR) {
+    typename R::vec v[SVM_UNR];
+    double          s[SVM_UNR];
 #pragma unroll
     for (int u = 0; u < SVM_UNR; u++) {
-      const long long i = r0 + 2 * u + half;
+      const long long i = r0 + R::RPI * u + sub;
       const bool      ok = i < n && (!SUB || y[i] != 0.0);
-      v[u] = ok ? __builtin_nontemporal_load((const dbl2 *)(X + (size_t)i * 64) + l2) : dbl2{0.0, 0.0};
+      v[u] = ok ? __builtin_nontemporal_load((const typename R::vec *)(X + (size_t)i * 64) + lq) : R::zero();
       s[u] = ok ? y[i] * a[i] : 0.0;
-      if (AUG && l2 == 0) {
+      if (AUG && lq == 0) {
         as += s[u];
         if (uu && ok) au += y[i] * uu[i];
       }
     }
 #pragma unroll
     for (int u = 0; u < SVM_UNR; u++) {
-      a0 += s[u] * v[u].x;
-      a1 += s[u] * v[u].y;
+#pragma unroll
+      for (int c = 0; c < R::CPL; c++) acc[c] += s[u] * R::col(v[u], c);
     }
   }
-  svm_fold_cols(a0, a1, lds, part);
+  svm_fold_cols<T>(acc, lds, part);
   if (AUG) {
     const double r0 = pmh_block_reduce<PMH_RED_SUM>(as, red), r1 = pmh_block_reduce<PMH_RED_SUM>(au, red);
     if (threadIdx.x == 0) {
@@ -147,8 +159,8 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_xt64(int n, const double *__r
   }
 }
 
-template <int SVM_UNR, int AUG, int SUB>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
+template <int SVM_UNR, int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64(int n, const T *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, double *__restrict__ Ha,
                                                        const double *__restrict__ a, double sigma, double shift, const double *__restrict__ diag)
 {
   const double sS = AUG ? sigma * w[64] : 0.0;
@@ -185,15 +197,15 @@ struct svm_grad_row {
 };
 // pass 2 of g = H x - b with the gradient split, p = gf, the partial sums of (0, |gP|^2, |gc|^2, |gf|^2), QPCFeas(x, p) and X'(y o p)
 #define SVM_EU 4
-template <int AUG, int SUB>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_grad_args a)
+template <int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const T *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_grad_args a)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
   __shared__ double red[PMH_BLOCK / 64];
   const double      sS = AUG ? a.sigma * w[64] : 0.0;
-  double            a0 = 0.0, a1 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, m = INFINITY, ts = 0.0;
+  double            cs[svm_row64<T>::CPL] = {}, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, m = INFINITY, ts = 0.0;
   svm_sweep_rows64_lanes<SVM_EU, SUB, 1>(
-    n, X, y, w, a0, a1,
+    n, X, y, w, cs,
     [&](long long i, bool act, double ym) {
       svm_grad_row r = {0.0, 0.0, 0.0, -INFINITY, INFINITY, AUG == 1 ? a.shift : 0.0};
       if (act) {
@@ -221,7 +233,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_grad(int n, const double 
       }
       return t;
     });
-  svm_fold_cols(a0, a1, lds, a.part_next);
+  svm_fold_cols<T>(cs, lds, a.part_next);
   if (AUG) {
     const double rs = pmh_block_reduce<PMH_RED_SUM>(ts, red);
     if (threadIdx.x == 0) a.spart_next[blockIdx.x] = rs;
@@ -250,16 +262,16 @@ struct svm_p1_row {
   double yi, pi, gi, xi, li, ui, sh;
 };
 // pass 2 of Ap = H p with the partial sums of p'Ap, g'p, QPCFeas(x, p); SPEC: + the iterate of the expansion step and X'(y o x+)
-template <int SPEC, int AUG, int SUB>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_p1_args a)
+template <int SPEC, int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const T *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, svm_p1_args a)
 {
   __shared__ double lds[PMH_BLOCK / 64][64];
   __shared__ double red[PMH_BLOCK / 64];
   const double      maf = SPEC ? -(*a.afeas) : 0.0, mal = -a.alpha;
   const double      sS = AUG ? a.sigma * w[64] : 0.0;
-  double            a0 = 0.0, a1 = 0.0, s0 = 0.0, s1 = 0.0, m = INFINITY, ts = 0.0, sux = 0.0;
+  double            cs[svm_row64<T>::CPL] = {}, s0 = 0.0, s1 = 0.0, m = INFINITY, ts = 0.0, sux = 0.0;
   svm_sweep_rows64_lanes<SVM_EU, SUB, SPEC>(
-    n, X, y, w, a0, a1,
+    n, X, y, w, cs,
     [&](long long i, bool act, double ym) {
       svm_p1_row r = {0.0, 0.0, 0.0, 0.0, -INFINITY, INFINITY, AUG == 1 ? a.shift : 0.0};
       if (act) {
@@ -291,7 +303,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x64_p1(int n, const double *_
       }
       return t;
     });
-  if (SPEC) svm_fold_cols(a0, a1, lds, a.part_next);
+  if (SPEC) svm_fold_cols<T>(cs, lds, a.part_next);
   if (AUG) {
     const double rs = pmh_block_reduce<PMH_RED_SUM>(ts, red), ru = pmh_block_reduce<PMH_RED_SUM>(sux, red);
     if (threadIdx.x == 0) {
@@ -349,24 +361,6 @@ static int svm_aux_ready(SvmDualOp *o, bool aug, bool *ok)
   return PMH_SUCCESS;
 }
 
-// Picking a kernel instance: f(std::integral_constant<int, v>()) for the run-time v in [0, N), so that the launch site names its kernel once, with
-// decltype(V)::value as template arguments, and exactly the instances that can be picked are compiled
-template <int N, class F>
-static void svm_const(int v, F f)
-{
-  if constexpr (N > 1) {
-    if (v == N - 1) return f(std::integral_constant<int, N - 1>());
-    return svm_const<N - 1>(v, f);
-  } else f(std::integral_constant<int, 0>());
-}
-// f(A, S): A::value the operator's form out of NAUG (SvmDualBase::aug_form(): 0 plain, 1 scalar shift, 2 diagonal; pass 1 knows 0 and 1 only), S::value 1 under
-// a subset (the SUB = 1 instances, which read the masked labels)
-template <int NAUG, class F>
-static void svm_pick(int form, bool sub, F f)
-{
-  svm_const<NAUG>(form, [&](auto A) { svm_const<2>(sub, [&](auto S) { f(A, S); }); });
-}
-
 // pass 1 and the column sums: w = X'(y o v) and, augmented, w[d] = s = sum_i y_i v_i (+ sum_i y_i u_i -> upart[workgroup] where u is given).  The plain form
 // hands the AUG = 0 kernels null pointers: the kernels of the plain operator, the bits of the plain operator
 int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
@@ -377,10 +371,13 @@ int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
   // which rows, i.e. the summation order of pass 1 (last-digit differences between UNR values; fixed for a given UNR).  Measured 4 / 8 / 12 / 16 on configs[4]:
   // 464 / 452-488 / 433 / 487 iterations per second -- inside the run-to-run spread of the box (the two passes already stream X at the box's copy rate): 4 stays,
   // and only that instance is compiled
-  svm_pick<2>(aug, ym != nullptr, [&](auto A, auto S) {
+  // float samples: 4 x UNR rows of 256 B, the same 16-byte loads and the same bytes in flight per lane.  UNR = 4 there too, the one instance compiled: a
+  // wave's group is 16 rows, which is what a wave gets of the grid below the cap (64 rows per workgroup)
+  svm_pick<2>(aug, ym != nullptr, f32, [&](auto A, auto S, auto F) {
     constexpr int AUG = decltype(A)::value, SUB = decltype(S)::value;
-    if (d == 64) SVM_PASS((k_svm_xt64<4, AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, v, part, sp, u, upart);
-    else SVM_PASS((k_svm_xt<AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, v, part, sp, u, upart);
+    using T           = svm_sample_t<decltype(F)>;
+    if (d == 64) SVM_PASS((k_svm_xt64<4, AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, (const T *)X, y, v, part, sp, u, upart);
+    else SVM_PASS((k_svm_xt<AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, (const T *)X, y, v, part, sp, u, upart);
   });
   hipLaunchKernelGGL(k_svm_colsum, dim3((d + (aug ? 1 : 0) + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)sp);
   PMH_HIP(hipGetLastError());
@@ -393,10 +390,11 @@ int SvmDualOp::pass2(const double *a, double *out, bool aug)
   const double  sg = aug ? sigma + sigma_fold : 0.0, sh = aug ? shift : 0.0;
   const int     form = aug ? aug_form() : 0;
   const double *y    = yk();
-  svm_pick<3>(form, ym != nullptr, [&](auto A, auto S) {
+  svm_pick<3>(form, ym != nullptr, f32, [&](auto A, auto S, auto F) {
     constexpr int AUG = decltype(A)::value, SUB = decltype(S)::value;
-    if (d == 64) SVM_PASS((k_svm_x64<4, AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, out, ap, sg, sh, diag);
-    else SVM_PASS((k_svm_x<AUG, SUB>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, X, y, (const double *)w, out, ap, sg, sh, diag);
+    using T           = svm_sample_t<decltype(F)>;
+    if (d == 64) SVM_PASS((k_svm_x64<4, AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, (const T *)X, y, (const double *)w, out, ap, sg, sh, diag);
+    else SVM_PASS((k_svm_x<AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, (const T *)X, y, (const double *)w, out, ap, sg, sh, diag);
   });
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
@@ -447,7 +445,10 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     a.partials = e.partials, a.feas_part = feas_part, a.part_next = part_next, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
     a.spart_next = spart_next, a.sigma = sg, a.shift = shift, a.diag = diag;
     if (spec && !e.x_out) return pmh_set_error(PMH_ERR_ARG, "SVM dual operator: x_from_spec needs x_out");
-    svm_pick<3>(form, ym != nullptr, [&](auto A, auto S) { SVM_PASS((k_svm_x64_grad<decltype(A)::value, decltype(S)::value>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a); });
+    svm_pick<3>(form, ym != nullptr, f32, [&](auto A, auto S, auto F) {
+      using T = svm_sample_t<decltype(F)>;
+      SVM_PASS((k_svm_x64_grad<decltype(A)::value, decltype(S)::value, T>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, (const T *)X, y, (const double *)w, a);
+    });
     PMH_HIP(hipGetLastError());
     next_is = NEXT_P, next_p = e.p;
     return PMH_SUCCESS;
@@ -465,8 +466,9 @@ int SvmDualOp::mult_epi(const double *in, double *out, const pmh_vec_epi &e)
     a.alpha = e.spec_alpha, a.astol = e.astol, a.ld = e.ld, a.prow = e.prow;
     a.spart_next = spart_next, a.aux_part = aux ? aux_part : nullptr, a.sigma = sg, a.shift = shift, a.diag = diag;
     const bool spec = paired && e.spec_alpha > 0.0; // afeas is known before this pass only when the gradient pass computed it
-    svm_pick<3>(form, ym != nullptr, [&](auto A, auto S) {
-      svm_const<2>(spec, [&](auto P) { SVM_PASS((k_svm_x64_p1<decltype(P)::value, decltype(A)::value, decltype(S)::value>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, X, y, (const double *)w, a); });
+    svm_pick<3>(form, ym != nullptr, f32, [&](auto A, auto S, auto F) {
+      using T = svm_sample_t<decltype(F)>;
+      svm_const<2>(spec, [&](auto P) { SVM_PASS((k_svm_x64_p1<decltype(P)::value, decltype(A)::value, decltype(S)::value, T>), dim3(grid_epi), dim3(PMH_BLOCK), 0, ctx->stream, n, (const T *)X, y, (const double *)w, a); });
     });
     PMH_HIP(hipGetLastError());
     if (aux) PMH_CHK(aux_finish(grid_epi));
@@ -655,7 +657,8 @@ extern "C" int pmh_op_svm_dual_passes(pmh_op op, long long *passes)
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_op_create_svm_dual(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, pmh_op *op)
+// X_dev: n_local x d doubles, or floats where f32
+static int svm_dual_create(pmh_ctx ctx, int n_local, int d, const void *X_dev, int f32, const double *y_dev, pmh_op *op)
 {
   PMH_ARG(ctx && op && n_local >= 0 && d >= 1 && d <= 64 * SVM_KMAX && X_dev && y_dev);
   SvmDualOp *o = new SvmDualOp();
@@ -663,6 +666,7 @@ extern "C" int pmh_op_create_svm_dual(pmh_ctx ctx, int n_local, int d, const dou
   o->n         = n_local;
   o->d         = d;
   o->X         = X_dev;
+  o->f32       = f32;
   o->y         = y_dev;
   long long nb = ((long long)n_local + 4 * 16 - 1) / (4 * 16); // >= 16 rows per wavefront
   o->nblocks   = (int)(nb < 1 ? 1 : (nb > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : nb));
@@ -672,3 +676,5 @@ extern "C" int pmh_op_create_svm_dual(pmh_ctx ctx, int n_local, int d, const dou
   *op = o;
   return PMH_SUCCESS;
 }
+extern "C" int pmh_op_create_svm_dual(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, pmh_op *op) { return svm_dual_create(ctx, n_local, d, X_dev, 0, y_dev, op); }
+extern "C" int pmh_op_create_svm_dual_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, const double *y_dev, pmh_op *op) { return svm_dual_create(ctx, n_local, d, X_dev, 1, y_dev, op); }

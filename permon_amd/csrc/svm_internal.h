@@ -1,5 +1,7 @@
 // The SVM dual operators (svm.hip: dense rows; svm_csr.hip: CSR) as the penalised operator (qppf.hip) and the SVM front end (svm_train.hip) see them.
 #pragma once
+#include <type_traits>
+
 #include "pmh_internal.h"
 
 #define SVM_KMAX 4 // d <= 64 * SVM_KMAX
@@ -58,8 +60,29 @@ struct SvmDualBase : pmh_op_s {
   }
 };
 
+// Picking a kernel instance: f(std::integral_constant<int, v>()) for the run-time v in [0, N), so that the launch site names its kernel once, with
+// decltype(V)::value as template arguments, and exactly the instances that can be picked are compiled
+template <int N, class F>
+static void svm_const(int v, F f)
+{
+  if constexpr (N > 1) {
+    if (v == N - 1) return f(std::integral_constant<int, N - 1>());
+    return svm_const<N - 1>(v, f);
+  } else f(std::integral_constant<int, 0>());
+}
+// the type dense samples are stored in, as a picked constant: 0 double, 1 float (pmh_op_create_svm_dual_f32, pmh_svm_*_f32)
+template <class V> using svm_sample_t = std::conditional_t<V::value != 0, float, double>;
+// f(A, S, T): A::value the operator's form out of NAUG (SvmDualBase::aug_form(): 0 plain, 1 scalar shift, 2 diagonal; pass 1 knows 0 and 1 only), S::value 1 under
+// a subset (the SUB = 1 instances, which read the masked labels), svm_sample_t<T> the samples' type
+template <int NAUG, class F>
+static void svm_pick(int form, bool sub, bool f32, F f)
+{
+  svm_const<NAUG>(form, [&](auto A) { svm_const<2>(sub, [&](auto S) { svm_const<2>(f32, [&](auto T) { f(A, S, T); }); }); });
+}
+
 struct SvmDualOp : SvmDualBase {
-  const double *X;
+  const void   *X;       // n x d row-major, borrowed: doubles, or floats where f32
+  int           f32 = 0; // the samples are stored in float32 (widened on arrival in the kernels; everything else stays fp64)
   double       *w, *part; // w: d; part: [nblocks][d]
   int           nblocks;
   int           mult(const double *a, double *Ha) override;

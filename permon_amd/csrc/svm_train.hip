@@ -10,6 +10,8 @@
 // svm_bias_row, svm_classify_row; their four sums per thread leave every kernel through svm_store4.
 // Probabilities (pmh_svm_calibrate, pmh_svm_predict_proba): A, B of the Platt fit (svm_proba.hip) on the handle; 1 / (1 + exp(A (x_i . w + b) + B)) is one more
 // functor on the same sweeps (k_svm_proba, k_svm_proba64, k_svm_proba_dots), so a probability costs the one pass over X that a score costs.
+// Dense samples in float32 (pmh_svm_create_f32; test samples: pmh_svm_predict_f32, _test_f32, _predict_proba_f32, _calibrate_f32): the same kernels with the
+// sample type as template argument, picked where they are launched; alpha, w, b, the solvers and the model are fp64 either way.
 #include <cmath>
 
 #include "svm_internal.h"
@@ -19,7 +21,9 @@ struct pmh_svm_s {
   pmh_ctx       ctx;
   int           n, d;
   long long     n_global;
-  const double *X, *y;
+  const void   *X; // dense rows: doubles, or floats where f32 (pmh_svm_create_f32)
+  int           f32 = 0;
+  const double *y;
   pmh_csr       Xcsr = nullptr; // the samples in CSR (then X == nullptr), borrowed
   double       *dots = nullptr; // CSR: x_i . w of the training samples (n doubles, allocated by the first model)
   pmh_svm_opts  o;
@@ -72,8 +76,9 @@ static __device__ __forceinline__ void svm_bias_row(long long i, double dot, con
 }
 // One pass over X for the bias: per workgroup the partial sums of svm_bias_row -> part[4][gridDim.x].  UBV: the upper bound of sample i is ubv[i] (per-sample
 // penalties, L1), not the scalar
-template <int UBV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias(int n, int d, const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, const double *__restrict__ alpha, double astol,
+// T (this kernel and the predict / proba kernels below): the type the samples are stored in, double or float (widened in the sweep, svm_rows.h)
+template <int UBV, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_bias(int n, int d, const T *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w, const double *__restrict__ alpha, double astol,
                                                         double ubound, const double *__restrict__ ubv, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
@@ -117,7 +122,8 @@ static __device__ __forceinline__ svm_counts svm_classify_row(long long i, doubl
   return c;
 }
 // One pass over the test samples: scores, labels and per workgroup the confusion counts -> part[4][gridDim.x] (svm_classify_row)
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict(int n, int d, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
+template <class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict(int n, int d, const T *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
                                                            const double *__restrict__ ytrue, double *__restrict__ part, svm_sel sel)
 {
   __shared__ double red[PMH_BLOCK / 64];
@@ -125,8 +131,9 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict(int n, int d, const d
   svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { c = svm_classify_row(i, dot + b, scores, labels, ytrue, c, sel); });
   if (ytrue) svm_store4(c.tp, c.fp, c.tn, c.fn, red, part); // (uniform: a kernel argument)
 }
-// d == 64: the row layout of k_svm_x64 (svm.hip), four row pairs in flight
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
+// d == 64: the row layout of k_svm_x64 (svm.hip), four row groups in flight
+template <class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const T *__restrict__ X, const double *__restrict__ w, double b, double *__restrict__ scores, double *__restrict__ labels,
                                                              const double *__restrict__ ytrue, double *__restrict__ part, svm_sel sel)
 {
   __shared__ double red[PMH_BLOCK / 64];
@@ -136,11 +143,13 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_predict64(int n, const double
 }
 
 // One pass over the test samples: proba[i] = 1 / (1 + exp(A (x_i . w + b) + B)), the dot product summed as k_svm_predict / k_svm_predict64 sum it
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_proba(int n, int d, const double *__restrict__ X, const double *__restrict__ w, double b, double A, double B, double *__restrict__ proba)
+template <class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_proba(int n, int d, const T *__restrict__ X, const double *__restrict__ w, double b, double A, double B, double *__restrict__ proba)
 {
   svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { proba[i] = svm_sigmoid(A * (dot + b) + B); });
 }
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_proba64(int n, const double *__restrict__ X, const double *__restrict__ w, double b, double A, double B, double *__restrict__ proba)
+template <class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_proba64(int n, const T *__restrict__ X, const double *__restrict__ w, double b, double A, double B, double *__restrict__ proba)
 {
   svm_sweep_rows64<4>(n, X, w, [&](long long i, double dot) { proba[i] = svm_sigmoid(A * (dot + b) + B); });
 }
@@ -260,19 +269,19 @@ static int svm_refresh_l2(pmh_svm s)
   return pmh_op_svm_dual_set_terms(s->H, 1.0 / s->o.C, 0.0);
 }
 
-// X_dev (dense rows) or Xcsr
-static int svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_csr Xcsr, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
+// X_dev (dense rows: doubles, or floats where f32) or Xcsr
+static int svm_create(pmh_ctx ctx, int n_local, int d, const void *X_dev, int f32, pmh_csr Xcsr, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
 {
   if (opts->loss_type != PMH_SVM_LOSS_L1 && opts->loss_type != PMH_SVM_LOSS_L2) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: unknown loss type %d (PMH_SVM_LOSS_L1 | PMH_SVM_LOSS_L2)", opts->loss_type);
   if (!(opts->C > 0.0)) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create: C = %g, must be positive", opts->C);
   pmh_svm s = new pmh_svm_s();
-  s->ctx = ctx, s->n = n_local, s->d = d, s->X = X_dev, s->Xcsr = Xcsr, s->y = y_dev, s->o = *opts;
+  s->ctx = ctx, s->n = n_local, s->d = d, s->X = X_dev, s->f32 = f32, s->Xcsr = Xcsr, s->y = y_dev, s->o = *opts;
   memset(&s->st, 0, sizeof(s->st));
   const int    n  = n_local;
   const size_t nb = sizeof(double) * (size_t)(n ? n : 1);
   int          rc = PMH_SUCCESS;
   do {
-    if ((rc = Xcsr ? pmh_op_create_svm_dual_csr(ctx, Xcsr, y_dev, &s->H) : pmh_op_create_svm_dual(ctx, n, d, X_dev, y_dev, &s->H))) break;
+    if ((rc = Xcsr ? pmh_op_create_svm_dual_csr(ctx, Xcsr, y_dev, &s->H) : (f32 ? pmh_op_create_svm_dual_f32(ctx, n, d, (const float *)X_dev, y_dev, &s->H) : pmh_op_create_svm_dual(ctx, n, d, (const double *)X_dev, y_dev, &s->H)))) break;
     if ((rc = svm_refresh_l2(s))) break;
     if ((rc = pmh_malloc(ctx, nb, (void **)&s->alpha)) || (rc = pmh_malloc(ctx, nb, (void **)&s->rhs)) || (rc = pmh_malloc(ctx, nb, (void **)&s->lb))) break;
     if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)d, (void **)&s->w)) || (rc = pmh_malloc(ctx, sizeof(double) * 4 * PMH_MAX_VEC_BLOCKS, (void **)&s->part)) || (rc = pmh_malloc(ctx, sizeof(double) * 8, (void **)&s->scal))) break;
@@ -301,17 +310,19 @@ static int svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
+static int svm_create_dense(pmh_ctx ctx, int n_local, int d, const void *X_dev, int f32, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
 {
   PMH_ARG(ctx && out && opts && n_local >= 0 && d >= 1 && d <= 64 * SVM_KMAX && X_dev && y_dev);
-  return svm_create(ctx, n_local, d, X_dev, nullptr, y_dev, opts, out);
+  return svm_create(ctx, n_local, d, X_dev, f32, nullptr, y_dev, opts, out);
 }
+extern "C" int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out) { return svm_create_dense(ctx, n_local, d, X_dev, 0, y_dev, opts, out); }
+extern "C" int pmh_svm_create_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out) { return svm_create_dense(ctx, n_local, d, X_dev, 1, y_dev, opts, out); }
 
 extern "C" int pmh_svm_create_csr(pmh_ctx ctx, pmh_csr X, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *out)
 {
   PMH_ARG(ctx && out && opts && X && y_dev && X->ctx == ctx);
   if (X->ncols < 1) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_create_csr: the sample matrix has no columns");
-  return svm_create(ctx, X->nrows, X->ncols, nullptr, X, y_dev, opts, out);
+  return svm_create(ctx, X->nrows, X->ncols, nullptr, 0, X, y_dev, opts, out);
 }
 
 // scal[0..3] = the sums over all workgroups and ranks of the four rows a bias / predict kernel left in part[4][nb] (n == 0: no kernel ran, zeros)
@@ -340,7 +351,12 @@ static int svm_model(pmh_svm s)
     hipLaunchKernelGGL((ubv ? k_svm_bias_dots<1> : k_svm_bias_dots<0>), dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, (const double *)s->dots, s->y, (const double *)s->alpha, astol, ubound, ubv, s->part);
   } else if (s->n > 0) {
     H->npass++;
-    hipLaunchKernelGGL((ubv ? k_svm_bias<1> : k_svm_bias<0>), dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, ubound, ubv, s->part);
+    svm_const<2>(ubv != nullptr, [&](auto U) {
+      svm_const<2>(s->f32, [&](auto F) {
+        using T = svm_sample_t<decltype(F)>;
+        hipLaunchKernelGGL((k_svm_bias<decltype(U)::value, T>), dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, s->n, s->d, (const T *)s->X, s->y, (const double *)s->w, (const double *)s->alpha, astol, ubound, ubv, s->part);
+      });
+    });
   }
   PMH_CHK(svm_sum_part(s, s->n, nb));
   // the equality's multiplier: SMALXE keeps B'mu = mu row (the Lagrangian is 1/2 a'Ha - 1'a + mu (row'a)), so mu = row'(B'mu) / (row'row) and, with
@@ -549,9 +565,9 @@ extern "C" int pmh_svm_get_subset(pmh_svm s, double *m_dev, long long *n_in)
   return H->msk ? pmh_vec_copy(s->ctx, s->n, H->msk, m_dev) : pmh_vec_set(s->ctx, s->n, m_dev, 1.0);
 }
 
-// X (dense rows, n x d) or Xt (CSR)
+// X (dense rows, n x d: doubles, or floats where f32 -- the test samples' type, whatever the handle was trained on) or Xt (CSR)
 // own: the handle's own samples (X or, CSR, the operator's tables: Xt == nullptr); sel: which of them the counts are taken over
-static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts, bool own = false, svm_sel sel = svm_sel())
+static int svm_predict(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts, bool own = false, svm_sel sel = svm_sel())
 {
   PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || own));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict: call pmh_svm_train first");
@@ -568,8 +584,11 @@ static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *sc
     if (!scores) pmh_free(s->ctx, dots);
     PMH_CHK(rc);
   } else if (n > 0) {
-    if (s->d == 64) hipLaunchKernelGGL(k_svm_predict64, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part, sel);
-    else hipLaunchKernelGGL(k_svm_predict, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, s->d, X, (const double *)s->w, s->b, scores, labels, ytrue, s->part, sel);
+    svm_const<2>(f32, [&](auto F) {
+      using T = svm_sample_t<decltype(F)>;
+      if (s->d == 64) hipLaunchKernelGGL(k_svm_predict64<T>, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, (const T *)X, (const double *)s->w, s->b, scores, labels, ytrue, s->part, sel);
+      else hipLaunchKernelGGL(k_svm_predict<T>, dim3(nb), dim3(PMH_BLOCK), 0, s->ctx->stream, n, s->d, (const T *)X, (const double *)s->w, s->b, scores, labels, ytrue, s->part, sel);
+    });
     PMH_HIP(hipGetLastError());
   }
   if (!counts) return PMH_SUCCESS;
@@ -580,31 +599,37 @@ static int svm_predict(pmh_svm s, int n, const double *X, pmh_csr Xt, double *sc
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_svm_predict(pmh_svm s, int n, const double *X_dev, double *scores_dev, double *labels_dev) { return svm_predict(s, n, X_dev, nullptr, scores_dev, labels_dev, nullptr, nullptr); }
+extern "C" int pmh_svm_predict(pmh_svm s, int n, const double *X_dev, double *scores_dev, double *labels_dev) { return svm_predict(s, n, X_dev, 0, nullptr, scores_dev, labels_dev, nullptr, nullptr); }
+extern "C" int pmh_svm_predict_f32(pmh_svm s, int n, const float *X_dev, double *scores_dev, double *labels_dev) { return svm_predict(s, n, X_dev, 1, nullptr, scores_dev, labels_dev, nullptr, nullptr); }
 
 extern "C" int pmh_svm_predict_csr(pmh_svm s, pmh_csr Xt, double *scores_dev, double *labels_dev)
 {
   PMH_ARG(s && Xt);
-  return svm_predict(s, Xt->nrows, nullptr, Xt, scores_dev, labels_dev, nullptr, nullptr);
+  return svm_predict(s, Xt->nrows, nullptr, 0, Xt, scores_dev, labels_dev, nullptr, nullptr);
 }
 
 extern "C" int pmh_svm_test_csr(pmh_svm s, pmh_csr Xt, const double *y_dev, long long counts[4])
 {
   PMH_ARG(s && Xt && y_dev && counts);
-  return svm_predict(s, Xt->nrows, nullptr, Xt, nullptr, nullptr, y_dev, counts);
+  return svm_predict(s, Xt->nrows, nullptr, 0, Xt, nullptr, nullptr, y_dev, counts);
 }
 
 extern "C" int pmh_svm_test(pmh_svm s, int n, const double *X_dev, const double *y_dev, long long counts[4])
 {
   PMH_ARG(y_dev && counts);
-  return svm_predict(s, n, X_dev, nullptr, nullptr, nullptr, y_dev, counts);
+  return svm_predict(s, n, X_dev, 0, nullptr, nullptr, nullptr, y_dev, counts);
+}
+extern "C" int pmh_svm_test_f32(pmh_svm s, int n, const float *X_dev, const double *y_dev, long long counts[4])
+{
+  PMH_ARG(y_dev && counts);
+  return svm_predict(s, n, X_dev, 1, nullptr, nullptr, nullptr, y_dev, counts);
 }
 
 // the handle's own samples, nothing uploaded: the predict sweep over the X the handle was created on (CSR: the row sweep with the operator's tables)
 extern "C" int pmh_svm_predict_own(pmh_svm s, double *scores_dev, double *labels_dev)
 {
   PMH_ARG(s);
-  return svm_predict(s, s->n, s->X, nullptr, scores_dev, labels_dev, nullptr, nullptr, true);
+  return svm_predict(s, s->n, s->X, s->f32, nullptr, scores_dev, labels_dev, nullptr, nullptr, true);
 }
 
 extern "C" int pmh_svm_test_own(pmh_svm s, int which, long long counts[4])
@@ -615,12 +640,12 @@ extern "C" int pmh_svm_test_own(pmh_svm s, int which, long long counts[4])
   if (which == PMH_SVM_OWN_HELD_OUT && !H->msk) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_test_own: no subset is set (pmh_svm_set_subset), so no sample is held out");
   svm_sel sel;
   if (which != PMH_SVM_OWN_ALL && H->msk) sel.m = H->msk, sel.want = which == PMH_SVM_OWN_SUBSET ? 1.0 : 0.0;
-  return svm_predict(s, s->n, s->X, nullptr, nullptr, nullptr, s->y, counts, true, sel);
+  return svm_predict(s, s->n, s->X, s->f32, nullptr, nullptr, nullptr, s->y, counts, true, sel);
 }
 
 // ---- probabilities (Platt scaling, svm_proba.hip) ---------------------------------------------------------------------------------------------------------------
 // the scores of the calibration samples by the predict path, then the fit on them
-static int svm_calibrate(pmh_svm s, int n, const double *X, pmh_csr Xt, const double *y)
+static int svm_calibrate(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, const double *y)
 {
   PMH_ARG(s && n >= 0 && (X || Xt || n == 0) && (y || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_calibrate: call pmh_svm_train first");
@@ -628,7 +653,7 @@ static int svm_calibrate(pmh_svm s, int n, const double *X, pmh_csr Xt, const do
   PMH_CHK(pmh_malloc(s->ctx, sizeof(double) * (size_t)(n ? n : 1), (void **)&scores));
   double              A = 0.0, B = 0.0;
   pmh_svm_platt_stats st;
-  int                 rc = svm_predict(s, n, X, Xt, scores, nullptr, nullptr, nullptr);
+  int                 rc = svm_predict(s, n, X, f32, Xt, scores, nullptr, nullptr, nullptr);
   if (!rc) rc = pmh_svm_platt_fit(s->ctx, n, scores, y, &A, &B, &st);
   pmh_free(s->ctx, scores);
   PMH_CHK(rc);
@@ -636,12 +661,13 @@ static int svm_calibrate(pmh_svm s, int n, const double *X, pmh_csr Xt, const do
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_svm_calibrate(pmh_svm s, int n, const double *X_dev, const double *y_dev) { return svm_calibrate(s, n, X_dev, nullptr, y_dev); }
+extern "C" int pmh_svm_calibrate(pmh_svm s, int n, const double *X_dev, const double *y_dev) { return svm_calibrate(s, n, X_dev, 0, nullptr, y_dev); }
+extern "C" int pmh_svm_calibrate_f32(pmh_svm s, int n, const float *X_dev, const double *y_dev) { return svm_calibrate(s, n, X_dev, 1, nullptr, y_dev); }
 
 extern "C" int pmh_svm_calibrate_csr(pmh_svm s, pmh_csr Xt, const double *y_dev)
 {
   PMH_ARG(s && Xt);
-  return svm_calibrate(s, Xt->nrows, nullptr, Xt, y_dev);
+  return svm_calibrate(s, Xt->nrows, nullptr, 0, Xt, y_dev);
 }
 
 extern "C" int pmh_svm_set_calibration(pmh_svm s, double A, double B)
@@ -664,8 +690,8 @@ extern "C" int pmh_svm_get_calibration(pmh_svm s, double *A, double *B, pmh_svm_
   return PMH_SUCCESS;
 }
 
-// X (dense rows, n x d) or Xt (CSR): one pass over the samples
-static int svm_predict_proba(pmh_svm s, int n, const double *X, pmh_csr Xt, double *proba)
+// X (dense rows, n x d: doubles, or floats where f32) or Xt (CSR): one pass over the samples
+static int svm_predict_proba(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, double *proba)
 {
   PMH_ARG(s && n >= 0 && (X || Xt || n == 0) && (proba || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict_proba: call pmh_svm_train first");
@@ -677,16 +703,21 @@ static int svm_predict_proba(pmh_svm s, int n, const double *X, pmh_csr Xt, doub
   if (Xt) {
     PMH_CHK(pmh_svm_csr_row_dots(Xt, s->w, proba));
     hipLaunchKernelGGL(k_svm_proba_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, s->b, s->cal_A, s->cal_B, proba);
-  } else if (s->d == 64) hipLaunchKernelGGL(k_svm_proba64, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, X, (const double *)s->w, s->b, s->cal_A, s->cal_B, proba);
-  else hipLaunchKernelGGL(k_svm_proba, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, s->d, X, (const double *)s->w, s->b, s->cal_A, s->cal_B, proba);
+  } else
+    svm_const<2>(f32, [&](auto F) {
+      using T = svm_sample_t<decltype(F)>;
+      if (s->d == 64) hipLaunchKernelGGL(k_svm_proba64<T>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, (const T *)X, (const double *)s->w, s->b, s->cal_A, s->cal_B, proba);
+      else hipLaunchKernelGGL(k_svm_proba<T>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, s->d, (const T *)X, (const double *)s->w, s->b, s->cal_A, s->cal_B, proba);
+    });
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_svm_predict_proba(pmh_svm s, int n, const double *X_dev, double *proba_dev) { return svm_predict_proba(s, n, X_dev, nullptr, proba_dev); }
+extern "C" int pmh_svm_predict_proba(pmh_svm s, int n, const double *X_dev, double *proba_dev) { return svm_predict_proba(s, n, X_dev, 0, nullptr, proba_dev); }
+extern "C" int pmh_svm_predict_proba_f32(pmh_svm s, int n, const float *X_dev, double *proba_dev) { return svm_predict_proba(s, n, X_dev, 1, nullptr, proba_dev); }
 
 extern "C" int pmh_svm_predict_proba_csr(pmh_svm s, pmh_csr Xt, double *proba_dev)
 {
   PMH_ARG(s && Xt);
-  return svm_predict_proba(s, Xt->nrows, nullptr, Xt, proba_dev);
+  return svm_predict_proba(s, Xt->nrows, nullptr, 0, Xt, proba_dev);
 }

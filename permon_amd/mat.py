@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import check
-from .core import CsrMat, Op, Vec
+from .core import CsrMat, Op, Vec, VecF32, sample_array, sample_dtype_of
 
 
 class MatGluing:
@@ -669,9 +669,12 @@ def is_sparse(X):
     return hasattr(X, "tocsr")
 
 
-def MatCreateSVMDual(ctx, X, y):
+def MatCreateSVMDual(ctx, X, y, sample_dtype=None):
     """Matrix-free H = diag(y) X X' diag(y) of the hinge-loss SVM dual (BASELINE configs[4]); X: (n_local, d) row-major ndarray (d <= 256), or a scipy.sparse
-    matrix of any width (pmh_op_create_svm_dual_csr: two sweeps over the stored entries per product)."""
+    matrix of any width (pmh_op_create_svm_dual_csr: two sweeps over the stored entries per product).  sample_dtype: the type a dense X is stored in on the
+    device -- None or numpy.float64: fp64, whatever X holds; numpy.float32: float32 (pmh_op_create_svm_dual_f32: half the memory and traffic of X, all
+    arithmetic still fp64; a float64 X is rounded).  op.sample_dtype reports it."""
+    dt = sample_dtype_of(sample_dtype, is_sparse(X), "MatCreateSVMDual")
     if is_sparse(X):
         Xc = csr_from_scipy(ctx, X)
         n = Xc.nrows
@@ -680,13 +683,15 @@ def MatCreateSVMDual(ctx, X, y):
         check(ctx.L.pmh_op_create_svm_dual_csr(ctx.h, Xc.h, yd.p, C.byref(h)))
         op = Op(ctx, h, n, keep=[Xc, yd])
     else:
-        X = np.ascontiguousarray(X, dtype=np.float64)
+        X = sample_array(X, dt, "MatCreateSVMDual")
         n, d = X.shape
-        Xd = Vec.from_numpy(ctx, X.ravel())
+        f32 = dt is np.float32
+        Xd = (VecF32 if f32 else Vec).from_numpy(ctx, X.ravel())
         yd = Vec.from_numpy(ctx, y)
         h = C.c_void_p()
-        check(ctx.L.pmh_op_create_svm_dual(ctx.h, n, d, Xd.p, yd.p, C.byref(h)))
+        check((ctx.L.pmh_op_create_svm_dual_f32 if f32 else ctx.L.pmh_op_create_svm_dual)(ctx.h, n, d, Xd.p, yd.p, C.byref(h)))
         op = Op(ctx, h, n, keep=[Xd, yd])
+    op.sample_dtype = dt
 
     def passes():
         """How many times the operator has streamed X so far (pmh_op_svm_dual_passes)."""

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .core import Vec
+from .core import Vec, VecF32, sample_array, sample_dtype_of
 from .mat import csr_from_scipy, is_sparse
 
 
@@ -44,20 +44,22 @@ def platt_fit(ctx, scores, y):
 
 
 class _Samples:
-    """Samples for one library call: X, a scipy.sparse matrix (csr_from_scipy) or anything else (a contiguous float64 array), is put on the device on entry
-    and taken off again on exit, whatever happened in between.  Entering gives n and the samples' arguments of the entry: (handle,) for CSR, (n, pointer)
-    for dense rows -- with_d: (n, d, pointer), as the create entries take them.  X is the converted array: the shape checks are the caller's."""
+    """Samples for one library call: X, a scipy.sparse matrix (csr_from_scipy) or anything else (a contiguous array of dtype: float64, or float32 for the
+    _f32 entries), is put on the device on entry and taken off again on exit, whatever happened in between.  Entering gives n and the samples' arguments of
+    the entry: (handle,) for CSR, (n, pointer) for dense rows -- with_d: (n, d, pointer), as the create entries take them.  X is the converted array: the shape
+    checks are the caller's."""
 
-    def __init__(self, ctx, X, with_d=False):
+    def __init__(self, ctx, X, with_d=False, dtype=np.float64):
         self.ctx, self.sparse, self.with_d, self.dev = ctx, is_sparse(X), with_d, None
-        self.X = X if self.sparse else np.ascontiguousarray(X, dtype=np.float64)
+        self.f32 = not self.sparse and dtype is np.float32
+        self.X = X if self.sparse else sample_array(X, dtype, "SVM")
 
     def __enter__(self):
         n = self.X.shape[0]
         if self.sparse:
             self.dev = csr_from_scipy(self.ctx, self.X)
             return n, (self.dev.h,)
-        self.dev = Vec.from_numpy(self.ctx, self.X.ravel())
+        self.dev = (VecF32 if self.f32 else Vec).from_numpy(self.ctx, self.X.ravel())
         return n, ((n, self.X.shape[1], self.dev.p) if self.with_d else (n, self.dev.p))
 
     def keep(self):
@@ -121,19 +123,21 @@ class _SVMHandle:
         if self.h is None:
             raise RuntimeError("%s: call fit first" % self._who)
 
-    def _entry(self, name, sparse):
-        return getattr(self.L, self._pre + name + ("_csr" if sparse else ""))
+    sample_dtype = np.float64  # the type dense samples are stored in on the device (SVM: the sample_dtype argument)
+
+    def _entry(self, name, sparse, f32=False):
+        return getattr(self.L, self._pre + name + ("_csr" if sparse else "_f32" if f32 else ""))
 
     def _create_handle(self, X, y, *more):
         """The handle on (X, y), which it borrows for its lifetime: both stay on the device in _keep."""
         self.destroy()
-        S = _Samples(self.ctx, X, with_d=True)
+        S = _Samples(self.ctx, X, with_d=True, dtype=self.sample_dtype)
         self.n, self.d = S.X.shape
         h = ct.c_void_p()
         with S as (n, xa):
             yd = self._dev(y)
             try:
-                check(self._entry("create", S.sparse)(self.ctx.h, *xa, yd.p, self.opts, *more, ct.byref(h)))
+                check(self._entry("create", S.sparse, S.f32)(self.ctx.h, *xa, yd.p, self.opts, *more, ct.byref(h)))
             except Exception:
                 yd.free()
                 raise
@@ -150,15 +154,20 @@ class _SVMHandle:
 
 
 class SVM(_SVMHandle):
-    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", C_pos=None, C_neg=None):
+    def __init__(self, ctx, loss="L1", C=1.0, bias=True, options="", C_pos=None, C_neg=None, sample_dtype=None):
         """options: a PETSc-style option string for the solver (-qps_rtol 1e-6, -qps_mpgp_*, -qps_smalxe_*, -smalxe_qps_* ...) and -svm_loss_type / -svm_C /
-        -svm_bias, which override the keyword arguments.  C_pos / C_neg: the penalty of the samples with y = +1 / y = -1 (None: C)."""
+        -svm_bias, which override the keyword arguments.  C_pos / C_neg: the penalty of the samples with y = +1 / y = -1 (None: C).  sample_dtype: the type
+        dense samples are stored in on the device, training and test samples alike -- None or numpy.float64: fp64, whatever X holds; numpy.float32: float32
+        (pmh_svm_create_f32: half the memory and traffic of X; alpha, w, b and all arithmetic stay fp64; a float64 X is rounded, sparse samples are
+        refused).  svm.sample_dtype reports it."""
         self.C_pos, self.C_neg = C_pos, C_neg
+        self.sample_dtype = sample_dtype_of(sample_dtype, False, "SVM")
         super().__init__(ctx, loss, C, bias, options)
 
     def create(self, X, y, sample_weight=None):
         """Set the training samples (X: (n, d) row-major ndarray or scipy.sparse matrix, y: +-1) and build the solver without training.  sample_weight: n
         positive numbers that scale the samples' penalties (None: all 1)."""
+        sample_dtype_of(self.sample_dtype, is_sparse(X), "SVM")  # (float32 with sparse samples is refused)
         self._create_handle(X, y)
         if self.C_pos is not None or self.C_neg is not None or sample_weight is not None:
             self.set_penalties(self.C_pos, self.C_neg, sample_weight)
@@ -276,7 +285,7 @@ class SVM(_SVMHandle):
     def _test_samples(self, X):
         """X for a scoring call: refused before any upload unless it is (n, d)."""
         self._need()
-        S = _Samples(self.ctx, X)
+        S = _Samples(self.ctx, X, dtype=self.sample_dtype)
         if S.X.ndim != 2 or S.X.shape[1] != self.d:
             raise ValueError("SVM: X must be (n, %d)" % self.d)
         return S
@@ -284,7 +293,7 @@ class SVM(_SVMHandle):
     def _predict(self, X, want_scores, want_labels):
         S = self._test_samples(X)
         with S as (n, xa), _vecs(self.ctx, n if want_scores else None, n if want_labels else None) as (s, l):
-            check(self._entry("predict", S.sparse)(self.h, *xa, s.p if s else None, l.p if l else None))
+            check(self._entry("predict", S.sparse, S.f32)(self.h, *xa, s.p if s else None, l.p if l else None))
             return (s.to_numpy() if s else None, l.to_numpy() if l else None)
 
     def decision_function(self, X):
@@ -298,11 +307,11 @@ class SVM(_SVMHandle):
         decision_function(X).  train, set_labels and set_penalties clear it."""
         self._need()
         with self._lent(y) as yd:
-            S = _Samples(self.ctx, X)
+            S = _Samples(self.ctx, X, dtype=self.sample_dtype)
             if S.X.ndim != 2 or S.X.shape[1] != self.d or S.X.shape[0] != yd.n:
                 raise ValueError("SVM: X must be (%d, %d)" % (yd.n, self.d))
             with S as (n, xa):
-                check(self._entry("calibrate", S.sparse)(self.h, *xa, yd.p))
+                check(self._entry("calibrate", S.sparse, S.f32)(self.h, *xa, yd.p))
         return self
 
     def set_calibration(self, A, B):
@@ -331,7 +340,7 @@ class SVM(_SVMHandle):
         """(n,): P(y = +1 | x_i) = 1 / (1 + exp(A decision_function(x_i) + B)), in one pass over X (pmh_svm_predict_proba)."""
         S = self._test_samples(X)
         with S as (n, xa), _vecs(self.ctx, n) as (p,):
-            check(self._entry("predict_proba", S.sparse)(self.h, *xa, p.p))
+            check(self._entry("predict_proba", S.sparse, S.f32)(self.h, *xa, p.p))
             return p.to_numpy()
 
     def decision_function_own(self):
@@ -357,11 +366,11 @@ class SVM(_SVMHandle):
         """Confusion counts of the predicted labels against y: dict(TP, FP, TN, FN, accuracy)."""
         self._need()
         cnt = (ct.c_longlong * 4)()
-        S = _Samples(self.ctx, X)
+        S = _Samples(self.ctx, X, dtype=self.sample_dtype)
         with S as (n, xa):
             yd = self._dev(y)
             try:
-                check(self._entry("test", S.sparse)(self.h, *xa, yd.p, cnt))
+                check(self._entry("test", S.sparse, S.f32)(self.h, *xa, yd.p, cnt))
             finally:
                 yd.free()  # (also the caller's own Vec)
         tp, fp, tn, fn = (int(c) for c in cnt)

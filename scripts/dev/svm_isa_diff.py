@@ -49,10 +49,28 @@ def demangle(names):
         return {n: n for n in names}
 
 
+KERNEL = re.compile(r"^(?:void )?(\w+)(?:<([^()]*)>)?(?=\()")
+
+
+def drop_sample_type(name):
+    """The kernel's name without a trailing template argument `double` (the sample type the dense SVM kernels gained) and without the return type a
+    template's demangled name carries: k_svm_xt<0, 0, double>(...) and k_svm_predict<double>(...) pair up with k_svm_xt<0, 0>(...) and k_svm_predict(...)."""
+    m = KERNEL.match(name)
+    if not m:
+        return name
+    args = [t for t in (m.group(2) or "").split(", ") if t]
+    if args and args[-1] == "double":
+        args.pop()
+    return m.group(1) + ("<%s>" % ", ".join(args) if args else "") + name[m.end():]
+
+
 def main():
     verbose = "-v" in sys.argv
     a, b = [kernels(p) for p in sys.argv[1:] if p != "-v"]
     dm = demangle(sorted(set(a) | set(b)))
+    # pair the kernels up by their demangled names less the sample type
+    a, b = [{drop_sample_type(dm[k]): v for k, v in side.items()} for side in (a, b)]
+    dm = {k: k for k in set(a) | set(b)}
     same = 0
     for k in sorted(set(a) | set(b), key=lambda k: dm[k]):
         if k not in a or k not in b:
