@@ -920,6 +920,24 @@ int pmh_smalxe_run_fixed(pmh_smalxe s, int inner_iters, int *solves, int *outer_
  * pmh_mv_test_spmv: the operator product alone (measurement / test entry): Y = A X for a resident CSR of 3 x 3 blocks and 8 columns, entries kept in `storage`
  * (0 fp64, 1 fp32, 2 fp16 with fp32 vectors); x, y: device, 8 n doubles; the average launch time of `repeats` products through HIP events. */
 int pmh_mv_test_spmv(pmh_csr A, int storage, const double *x, double *y, int repeats, float *ms_per_launch);
+/* ---- multi-right-hand-side product test entries (csrc/mv.hip: the ELL builders as the V-cycle and the block CG call them, and one launch of k_mv_spmv; nothing inside the
+ * solvers changes) ----
+ * pmh_mv_test_create: the ELL copy of the CSR A with entries kept in `storage` (0 fp64, 1 fp32, 2 fp16 scaled by a power of two, fp32 arithmetic).  kind 0: square, the
+ * FIRST of nrep congruent diagonal blocks (PMH_ERR_ARG where that block's rows do not end at nnz / nrep or reach beyond its own columns); 1: rectangular; 2: rectangular,
+ * the copy holds -A (nrep = 1 for both).  *E = NULL with PMH_SUCCESS where the builder declines: no rows, 3 not dividing rows or columns, kind 0 and not square, 3 nrep
+ * not dividing the rows or nrep the entries, a row with unsorted or repeated columns, no block at all or a block row of more than 2048, a padded copy beyond 2 GB.
+ * pmh_mv_test_info: info = {block rows, block columns, W = slots per block row, lanes per block row (4 / 16), storage, workgroups per launch, XCD order of the workgroups
+ * (0 / 1), kind}; *scale (or NULL): the fp16 scale (1 otherwise), negative for a negated fp16 copy (whose stored entries are those of A).
+ * pmh_mv_test_mult_epi: one launch with the epilogue `epi` on device multivectors of 8 columns -- double for fp64 storage, float otherwise (z64: always double); x:
+ * 3 (block columns) 8 entries, y, y1, r, d, z64: 3 (block rows) 8, dinv: 3 (block rows), one per ROW:
+ *   0 NONE y = A x;  1 ADD y = y1 + A x (y1 may be y);  2 SUB y = A x - y1;  10 PRE y = c0 x + c2 dinv (y1 - A x);  11 POST1 r = dinv (y1 - A x), d = c0 r, y = x + d;
+ *   12 POST2 y += c1 x + c2 (r - dinv A x), z64 (or NULL) = (double)y;  20 RESTRICT y = A x and, d != NULL, d = (dinv c0) y.
+ * halt != 0: the launch sees a device flag set to 1 and changes nothing.  Synchronises.  PMH_ERR_ARG, and no launch, for an unknown epilogue, an operand the epilogue
+ * needs and does not get, an output that is x, and 10 / 11 / 12 on a rectangular copy (they read x at the row's own offset). */
+int pmh_mv_test_create(pmh_csr A, int storage, int kind, int nrep, void **E);
+int pmh_mv_test_info(void *E, long long info[8], double *scale);
+int pmh_mv_test_mult_epi(void *E, int epi, const void *x, void *y, const void *y1, const void *dinv, void *r, void *d, double *z64, double c0, double c1, double c2, int halt);
+int pmh_mv_test_destroy(void *E);
 /* ---- CSR product test entries (csrc/spmv.hip: read the plan, or wrap one launch; nothing inside the solvers changes) ----------------------------------------
  * pmh_csr_kernel_info: the kernel plan pmh_csr_create chose for A.  info[0]: path of a plain product -- 0 ELL (slot-major copy), 1 stream with one lane per row,
  * 2 medium stream with 8 lanes per row, 3 vector, 4 long-row chunks; info[1]: ELL width or lanes per row (1, 8, 32, 64), 0 for long-row chunks; info[2]: 1 when the

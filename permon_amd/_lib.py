@@ -337,6 +337,10 @@ _PROTOS = {
     "pmh_matinv_enable_bsr3": [vp],
     "pmh_matinv_bsr3_replicas": [vp, c_int_p],
     "pmh_mv_test_spmv": [vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_float)],
+    "pmh_mv_test_create": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
+    "pmh_mv_test_info": [vp, C.POINTER(C.c_longlong), c_double_p],
+    "pmh_mv_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int],
+    "pmh_mv_test_destroy": [vp],
     "pmh_csr_kernel_info": [vp, c_int_p, C.POINTER(C.c_ulonglong)],
     "pmh_csr_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, c_double_p],
     "pmh_bsr3_test_create": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],

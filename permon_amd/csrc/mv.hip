@@ -136,7 +136,7 @@ static int mv_ell_build(pmh_csr A, int nrep, int storage, int rect, int negate, 
     return PMH_SUCCESS;
   }
   pmh_mv_ell E = new pmh_mv_ell_s();
-  E->ctx = ctx, E->nbr = nbr, E->storage = storage, E->scale = 1.0, E->col = nullptr, E->val = nullptr;
+  E->ctx = ctx, E->nbr = nbr, E->nbc = rect ? A->ncols / 3 : nbr, E->kind = rect ? (negate ? 2 : 1) : 0, E->storage = storage, E->scale = 1.0, E->col = nullptr, E->val = nullptr;
   // long rows (W > 48: the coarse operators of an aggregation hierarchy) and small levels (fewer block rows than fill the chip with 4 lanes each: the trips of a row are a
   // serial chain -- 7 of them for a 27-point operator) take 16 lanes per block row
   E->lpr = (info[0] > 48 || nbr < 16384) ? 16 : 4;
@@ -450,16 +450,25 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_mv_spmv(int nbr, int W4, const in
   mv_vec<T, R>::store(y + o, out);
 }
 
+// the launch figures of a product: workgroups of PMH_BLOCK lanes, lpr lanes per block row; the XCD order of the workgroups from 64 of them on (8 per XCD)
+static void mv_grid(const pmh_mv_ell_s *E, unsigned *nwg, int *xmap)
+{
+  *nwg  = (unsigned)(((long long)E->nbr * E->lpr + PMH_BLOCK - 1) / PMH_BLOCK);
+  *xmap = *nwg >= 64 ? 1 : 0;
+}
+
 template <typename TM, typename T>
 static int mv_launch(pmh_mv_ell E, const T *x, T *y, int epi, const pmh_mv_epi<T> *ep, const int *halt)
 {
-  const dim3    g((unsigned)(((long long)E->nbr * E->lpr + PMH_BLOCK - 1) / PMH_BLOCK)), blk(PMH_BLOCK);
+  unsigned nwg;
+  int      xmap;
+  mv_grid(E, &nwg, &xmap);
+  const dim3    g(nwg), blk(PMH_BLOCK);
   hipStream_t   st = E->ctx->stream;
   pmh_mv_epi<T> e;
   if (ep) e = *ep;
   else memset(&e, 0, sizeof(e));
   const T sc = (T)E->scale;
-  const int xmap = g.x >= 64 ? 1 : 0;
 #define MV_LAUNCH(EPI) \
   do { \
     if (E->lpr == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_spmv<TM, T, PMH_MV_R, EPI, 16>), g, blk, 0, st, E->nbr, E->W / 4, (const int *)E->col, (const void *)E->val, sc, x, y, e, halt, xmap); \
@@ -539,3 +548,79 @@ extern "C" int pmh_mv_test_spmv(pmh_csr A, int storage, const double *x /* 3 nbr
   pmh_mv_ell_destroy(E);
   return rc;
 }
+
+// ---- test entries (tests/test_gpu_mv_paths.py): the three builders as mg_mv.hip and matinv_mv.hip call them, what they laid out, and ONE launch of k_mv_spmv with
+// a given epilogue; nothing inside the solvers calls them ----
+extern "C" int pmh_mv_test_create(pmh_csr A, int storage, int kind, int nrep, void **E_)
+{
+  PMH_ARG(A && E_ && kind >= 0 && kind <= 2 && nrep >= 1 && (kind == 0 || nrep == 1));
+  *E_ = nullptr;
+  if (nrep > 1 && A->nrows > 0 && A->nrows == A->ncols && A->nrows % (3 * nrep) == 0 && A->nnz % nrep == 0) {
+    // the builder takes the caller's word that the diagonal blocks are congruent; a first block whose rows end elsewhere than nnz / nrep or reach beyond its own columns
+    // would send the product outside a one-block operand: refused here
+    const int           nr = A->nrows / nrep;
+    const long long     nz = A->nnz / nrep;
+    std::vector<int>    rp((size_t)nr + 1), cj((size_t)nz);
+    PMH_CHK(pmh_memcpy_d2h(A->ctx, rp.data(), A->d_rowptr, sizeof(int) * ((size_t)nr + 1)));
+    if (nz) PMH_CHK(pmh_memcpy_d2h(A->ctx, cj.data(), A->d_col, sizeof(int) * (size_t)nz));
+    bool ok = rp[nr] == nz;
+    for (long long k = 0; k < nz && ok; k++) ok = cj[k] < nr;
+    if (!ok) return pmh_set_error(PMH_ERR_ARG, "pmh_mv_test_create: the first of %d diagonal blocks is not closed", nrep);
+  }
+  pmh_mv_ell E = nullptr;
+  if (kind == 0) PMH_CHK(pmh_mv_ell_create_prefix(A, nrep, storage, &E));
+  else PMH_CHK(pmh_mv_ell_create_rect(A, storage, kind == 2, &E));
+  *E_ = E;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_mv_test_info(void *E_, long long info[8], double *scale)
+{
+  pmh_mv_ell E = (pmh_mv_ell)E_;
+  PMH_ARG(E && info);
+  unsigned nwg;
+  int      xmap;
+  mv_grid(E, &nwg, &xmap);
+  info[0] = E->nbr, info[1] = E->nbc, info[2] = E->W, info[3] = E->lpr, info[4] = E->storage, info[5] = nwg, info[6] = xmap, info[7] = E->kind;
+  if (scale) *scale = E->scale;
+  return PMH_SUCCESS;
+}
+
+template <typename T>
+static int mv_test_launch(pmh_mv_ell E, int epi, const void *x, void *y, const void *y1, const void *dinv, void *r, void *d, double *z64, double c0, double c1, double c2, const int *halt)
+{
+  pmh_mv_epi<T> e;
+  memset(&e, 0, sizeof(e));
+  e.y1 = (const T *)y1, e.dinv = (const T *)dinv, e.r = (T *)r, e.d = (T *)d, e.z64 = z64, e.c0 = (T)c0, e.c1 = (T)c1, e.c2 = (T)c2;
+  if constexpr (sizeof(T) == 8) return pmh_mv_spmv_f64(E, (const T *)x, (T *)y, epi, &e, halt);
+  else return pmh_mv_spmv_f32(E, (const T *)x, (T *)y, epi, &e, halt);
+}
+
+extern "C" int pmh_mv_test_mult_epi(void *E_, int epi, const void *x, void *y, const void *y1, const void *dinv, void *r, void *d, double *z64, double c0, double c1, double c2, int halt)
+{
+  pmh_mv_ell E = (pmh_mv_ell)E_;
+  PMH_ARG(E && x && y);
+  PMH_ARG(epi == PMH_EPI_NONE || epi == PMH_EPI_ADD || epi == PMH_EPI_SUB || epi == PMH_BSR_EPI_PRE || epi == PMH_BSR_EPI_POST1 || epi == PMH_BSR_EPI_POST2 ||
+          epi == PMH_MV_EPI_RESTRICT);
+  PMH_ARG(x != (const void *)y); // no variant may write the vector it gathers from
+  PMH_ARG((epi != PMH_EPI_ADD && epi != PMH_EPI_SUB) || y1); // y1 == y: in place, as the prolongation adds (a lane reads and writes its own row only)
+  // PRE / POST1 / POST2 read x at the ROW's own offset: a square operator only (rows may outnumber the columns of a rectangular one)
+  PMH_ARG((epi != PMH_BSR_EPI_PRE && epi != PMH_BSR_EPI_POST1 && epi != PMH_BSR_EPI_POST2) || E->kind == 0);
+  PMH_ARG(epi != PMH_BSR_EPI_PRE || (y1 && dinv));
+  PMH_ARG(epi != PMH_BSR_EPI_POST1 || (y1 && dinv && r && d && x != (const void *)r && x != (const void *)d && r != d && r != y && d != y));
+  PMH_ARG(epi != PMH_BSR_EPI_POST2 || (dinv && r && x != (const void *)z64 && (const void *)z64 != (const void *)y));
+  PMH_ARG(epi != PMH_MV_EPI_RESTRICT || !d || (dinv && x != (const void *)d && d != y)); // d == NULL: y alone
+  pmh_ctx ctx    = E->ctx;
+  int    *d_halt = nullptr;
+  if (halt) {
+    const int one = 1;
+    PMH_CHK(pmh_malloc(ctx, sizeof(int), (void **)&d_halt));
+    PMH_CHK(pmh_memcpy_h2d(ctx, d_halt, &one, sizeof(int)));
+  }
+  int rc = E->storage == PMH_BSR_F64 ? mv_test_launch<double>(E, epi, x, y, y1, dinv, r, d, z64, c0, c1, c2, d_halt) : mv_test_launch<float>(E, epi, x, y, y1, dinv, r, d, z64, c0, c1, c2, d_halt);
+  if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_mv_test_mult_epi: stream synchronisation failed");
+  if (d_halt) pmh_free(ctx, d_halt);
+  return rc;
+}
+
+extern "C" int pmh_mv_test_destroy(void *E) { return pmh_mv_ell_destroy((pmh_mv_ell)E); }

@@ -19,7 +19,9 @@
 struct pmh_mv_ell_s {
   pmh_ctx ctx;
   int     nbr, W, storage; // PMH_BSR_F64 / F32 / F16
-  int     lpr = 4;         // lanes per block row of the product: 4, or 16 where the rows are long (W > 48: the coarse operators of an aggregation hierarchy); W is a multiple of it
+  int     nbc = 0;         // block columns: nbr, or those of a rectangular copy (the operand multivector has 3 nbc R entries)
+  int     lpr = 4;         // lanes per block row of the product: 16 where the rows are long (more than 48 blocks: the coarse operators of an aggregation hierarchy) or few (nbr < 16384), else 4; W is a multiple of it
+  int     kind = 0;        // how it was built: 0 square (or the prefix of congruent blocks), 1 rectangular, 2 rectangular and negated; the product does not read it
   int    *col;
   void   *val;
   double  scale;
