@@ -543,6 +543,14 @@ int pmh_smalxe_solve(pmh_smalxe s);                                  /* QPSSolve
 int pmh_smalxe_set_reuse_products(pmh_smalxe s, int on);
 int pmh_smalxe_get_stats(pmh_smalxe s, pmh_smalxe_stats *st);
 int pmh_smalxe_reset(pmh_smalxe s);                                  /* QPSReset: the state machine of the inner convergence test back to 1 (a solve from a fresh initial guess) */
+/* One-shot: the next pmh_smalxe_solve starts from the caller's pair (u, B'mu = Btmu0) where it otherwise zeroes B'mu; the solve after that one starts from
+   zero again.  On such a solve: the Knoll start (-qps_smalxe_knoll) is not applied, the caller's u being the start; u is projected onto the box and the pair is
+   put to the outer criterion before anything moves -- rnorm = max(|B u| / rtol_E, |gP|), gP the projected gradient of A u - b + B'mu, one product with A -- and
+   where it holds the solve returns with 0 outer and 0 inner iterations, u and B'mu the caller's; otherwise the first inner problem is posed with B'mu as given
+   (the update B'mu += rho B'B u every later outer iteration begins with is not made from the caller's u, which no inner solve has produced).  M1, rho and the
+   state machine are reset exactly as in any solve.  Btmu0_dev: n doubles on the device, copied (it may be the solver's own B'mu of pmh_smalxe_get_penalized,
+   filled in place); NULL: zero, as without the call */
+int pmh_smalxe_set_initial_multiplier(pmh_smalxe s, const double *Btmu0_dev /* n, copied; NULL: zero */);
 int pmh_smalxe_set_inner_max_it(pmh_smalxe s, int max_it);           /* the inner QPS's iteration limit, summed over the outer iterations (smalxe.c:626-631: DIVERGED_ITS / outer BREAKDOWN beyond it) */
 int pmh_smalxe_get_inner_max_it(pmh_smalxe s, int *max_it);
 int pmh_smalxe_get_solution(pmh_smalxe s, pmh_ctx *ctx, double **u, int *n); /* QPGetSolutionVector: the caller's device vector (+ context, length); any pointer may be NULL */
@@ -605,13 +613,28 @@ int pmh_svm_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const d
    what pmh_svm_create gives on the widened samples */
 int pmh_svm_create_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, const double *y_dev, const pmh_svm_opts *opts, pmh_svm *svm);
 int pmh_svm_train(pmh_svm svm);                                     /* from a = 0: MPGP (no bias) or SMALXE + MPGP (bias), then the model */
+/* Warm starts: a training from the handle's last dual instead of zero -- along a path of penalties C_1 < C_2 < ..., or from one subset (fold) to the next.
+ * The handle keeps alpha and a flag "alpha is the dual of a training with the current labels": pmh_svm_train and pmh_svm_train_warm set it,
+ * pmh_svm_set_labels clears it, pmh_svm_set_penalties and pmh_svm_set_subset leave alpha and the flag as they are (a promise).  Only one GPU is tested; under a
+ * communicator the start vector is elementwise and local and the multiplier's scalar is the same on every rank.
+ * pmh_svm_warm_start_vector: a0_i = m_i ? min(max(alpha_scale alpha_i, 0), ub_i) : 0 in exactly this order of operations, one kernel launch; m the current
+ * subset mask (all ones without one), ub_i the current upper bound (L1: C_i; L2: none).  It leaves two counts on the handle (pmh_svm_get_warm_start_counts,
+ * summed over the ranks): entries the mask zeroed that were not zero, and entries clipped at ub.  alpha_scale not positive and finite: PMH_ERR_ARG; no dual of
+ * the current labels (never trained, or pmh_svm_set_labels since): PMH_ERR_STATE.
+ * pmh_svm_train_warm: pmh_svm_train, except that alpha starts as that vector (formed by the same function, in place) and, with a bias, SMALXE starts from the
+ * last training's multiplier (pmh_smalxe_set_initial_multiplier): B'mu_0 = (b_prev sqrt(n_S)) row, b_prev the last pmh_svm_stats::b_multiplier, row and n_S the
+ * current ones -- so it survives a new subset.  Statistics, passes_X, the model and the clearing of the calibration as in pmh_svm_train; a refusal changes
+ * nothing.  pmh_svm_train itself is untouched by any of this: after a warm training it gives what a fresh handle gives, bit for bit */
+int pmh_svm_warm_start_vector(pmh_svm svm, double alpha_scale, double *a0_dev /* n_local doubles */);
+int pmh_svm_get_warm_start_counts(pmh_svm svm, long long *masked /* or NULL */, long long *clipped /* or NULL */); /* of the last start vector formed (0, 0 before any) */
+int pmh_svm_train_warm(pmh_svm svm, double alpha_scale);
 int pmh_svm_get_model(pmh_svm svm, double *w_host /* d doubles, or NULL */, double *b /* or NULL */);
 int pmh_svm_get_dual(pmh_svm svm, double *alpha_dev);               /* n_local doubles */
 int pmh_svm_get_stats(pmh_svm svm, pmh_svm_stats *st);
 int pmh_svm_get_solver(pmh_svm svm, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh_smalxe *smalxe); /* borrowed; any pointer may be NULL, a solver not in use comes back NULL */
 /* A penalty per sample, C_i = (y_i > 0 ? C_pos : C_neg) weight_i, in place of the one C of the options (unbalanced classes; weighted samples):
  *   L1: 0 <= a_i <= C_i;   L2: 0 <= a_i, Hessian H + diag(1 / C_i) (pmh_op_svm_dual_set_diag on the handle's operator, in place of the scalar 1/C).
- * Free support vectors (the bias) are counted against C_i.  Call it after create, and again between trainings at will (pmh_svm_train starts from a = 0); the
+ * Free support vectors (the bias) are counted against C_i.  Call it after create, and again between trainings at will (pmh_svm_train starts from a = 0; the last dual stays on the handle for pmh_svm_train_warm); the
  * handle is untrained afterwards and its solver is built anew, so handles from pmh_svm_get_solver must be fetched again.  weight_dev: n_local doubles on the
  * device, copied, or NULL = all 1.  C_pos / C_neg not positive and finite: PMH_ERR_ARG naming the value.  Weights that are not positive and finite (zero
  * included: a weight does not leave a sample out, pmh_svm_set_subset does): PMH_ERR_ARG saying how many, counted on the device, over all ranks.  Nothing is exchanged in training

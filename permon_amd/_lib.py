@@ -263,6 +263,9 @@ _PROTOS = {
     "pmh_svm_set_from_options": [C.c_char_p, C.POINTER(SvmOpts), C.c_char_p, C.c_int],
     "pmh_svm_create": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvmOpts), C.POINTER(vp)],
     "pmh_svm_train": [vp],
+    "pmh_svm_train_warm": [vp, C.c_double],
+    "pmh_svm_warm_start_vector": [vp, C.c_double, vp],
+    "pmh_svm_get_warm_start_counts": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     "pmh_svm_get_model": [vp, vp, c_double_p],
     "pmh_svm_get_dual": [vp, vp],
     "pmh_svm_get_stats": [vp, C.POINTER(SvmStats)],
@@ -322,6 +325,7 @@ _PROTOS = {
     "pmh_smalxe_get_inner": [vp, C.POINTER(vp)],
     "pmh_smalxe_run_fixed": [vp, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p],
     "pmh_smalxe_reset": [vp],
+    "pmh_smalxe_set_initial_multiplier": [vp, vp],
     "pmh_smalxe_set_inner_max_it": [vp, C.c_int],
     "pmh_smalxe_get_inner_max_it": [vp, c_int_p],
     "pmh_smalxe_get_solution": [vp, C.POINTER(vp), C.POINTER(vp), c_int_p],

@@ -41,6 +41,7 @@ struct pmh_smalxe_s {
   // pmh_smalxe_set_reuse_products: A_rho u is carried from the inner solve's last gradient into the Lagrangian and into the next inner solve's first gradient
   int reuse;
   int normBu_final_valid; // normBu / enorm are those of the current u (set by the inner convergence test)
+  int Btmu_given; // pmh_smalxe_set_initial_multiplier: Btmu holds the caller's B'mu, the next solve starts from it (one-shot)
 };
 
 // QPSCreate_SMALXE defaults smalxe.c:1159-1207
@@ -383,6 +384,26 @@ static int smalxe_update(pmh_smalxe s, double Lag_old, double Lag, double rho)
   return PMH_SUCCESS;
 }
 
+// pmh_smalxe_set_initial_multiplier: the caller's (u, B'mu) as a primal-dual pair, under the outer criterion before anything moves -- rnorm = max(|B u| / rtol_E,
+// |gP|), gP the projected gradient (MPGP's split of the box) of the Lagrangian's gradient A u - b + B'mu, with the plain A: one product.  The inner test cannot
+// say this: it sees the penalised gradient, rho B'B u more, which at a converged pair is rho |B u| and not small beside the tolerance
+static int given_pair_converged(pmh_smalxe s)
+{
+  pmh_ctx   ctx = s->ctx;
+  const int n   = s->n;
+  double    gnorm;
+  PMH_CHK(s->A->mult(s->u, s->xwork));
+  PMH_CHK(pmh_vec_axpy(ctx, n, s->xwork, -1.0, s->b));
+  PMH_CHK(pmh_vec_axpy(ctx, n, s->xwork, 1.0, s->Btmu));
+  PMH_CHK(pmh_qpc_box_grads(ctx, n, s->u, s->xwork, s->lb, s->ub, s->o.inner.astol, s->BtBu, s->b_inner)); // (two work vectors the loop fills before it reads them)
+  PMH_CHK(pmh_vec_axpy(ctx, n, s->BtBu, 1.0, s->b_inner));
+  PMH_CHK(pmh_vec_norm2(ctx, n, s->BtBu, &gnorm));
+  s->BtBu_valid = 0;
+  PMH_CHK(update_normBu(s, s->u, &s->normBu, &s->enorm));
+  s->rnorm = fmax(s->enorm, gnorm);
+  return outer_converged(s, &s->reason);
+}
+
 // QPSSolve_SMALXE smalxe.c:893-997
 extern "C" int pmh_smalxe_solve(pmh_smalxe s)
 {
@@ -394,21 +415,31 @@ extern "C" int pmh_smalxe_solve(pmh_smalxe s)
 
   s->M1 = s->M1_initial;
   PMH_CHK(pmh_op_penalized_get_penalty(s->A_inner, &rho));
-  PMH_CHK(pmh_memset(ctx, s->Btmu, 0, sizeof(double) * (size_t)n));
+  const int given = s->Btmu_given; // the caller's B'mu and u are the start: no zeroing, no Knoll start
+  s->Btmu_given   = 0;
+  if (!given) PMH_CHK(pmh_memset(ctx, s->Btmu, 0, sizeof(double) * (size_t)n));
   s->BtBu_valid = 0;
-  if (s->o.knoll) PMH_CHK(pmh_qppf_apply_P(s->pf, s->b, s->u)); // the Knoll trick smalxe.c:938-943: projected rhs as initial guess
+  if (given) PMH_CHK(pmh_qpc_box_project(ctx, n, s->u, s->lb, s->ub, s->u)); // (what the inner MPGP does to its start, before the pair is looked at)
+  if (s->o.knoll && !given) PMH_CHK(pmh_qppf_apply_P(s->pf, s->b, s->u)); // the Knoll trick smalxe.c:938-943: projected rhs as initial guess
   PMH_CHK(objective(s, &Lag_old));
   PMH_CHK(update_normBu(s, s->u, &s->normBu_old, &s->enorm));
   s->iteration       = 0;
   s->inner_iter_accu = 0;
   s->reason          = PMH_CONVERGED_ITERATING;
   PMH_CHK(pmh_mpgp_reset_statistics(s->inner));
+  if (given) {
+    PMH_CHK(given_pair_converged(s));
+    if (s->reason) return PMH_SUCCESS; // no outer iteration, no inner iteration: u and B'mu are the caller's
+  }
 
   for (i = 0; i < maxits; i++) {
     // QPSSMALXEUpdateLambda_SMALXE smalxe.c:402-435: Btmu += rho * BtB u
-    if (!s->BtBu_valid) PMH_CHK(pmh_qppf_apply_GtG(s->pf, s->u, s->BtBu)); // "BtBu reused" otherwise (smalxe.c:421-430)
-    s->BtBu_valid = 1;
-    PMH_CHK(pmh_vec_axpy(ctx, n, s->Btmu, rho, s->BtBu));
+    // (not from the caller's u under a given multiplier: that one is the multiplier of the first inner problem, which no solve has yet answered)
+    if (!(given && i == 0)) {
+      if (!s->BtBu_valid) PMH_CHK(pmh_qppf_apply_GtG(s->pf, s->u, s->BtBu)); // "BtBu reused" otherwise (smalxe.c:421-430)
+      s->BtBu_valid = 1;
+      PMH_CHK(pmh_vec_axpy(ctx, n, s->Btmu, rho, s->BtBu));
+    }
     if (s->reason) break;
     PMH_CHK(pmh_vec_waxpy(ctx, n, s->b_inner, -1.0, s->Btmu, s->b)); // b_inner = b - Btmu
     // QPSConvergedSetUp_Inner_SMALXE smalxe.c:537-557
@@ -457,6 +488,18 @@ extern "C" int pmh_smalxe_solve(pmh_smalxe s)
     s->normBu_old = s->normBu;
   }
   if (i == maxits && !s->reason) s->reason = PMH_DIVERGED_ITS;
+  return PMH_SUCCESS;
+}
+
+// The next pmh_smalxe_solve starts from B'mu = Btmu0 (copied; the solver's own B'mu of pmh_smalxe_get_penalized, filled in place, is taken as it lies) in place
+// of zero, once; NULL: from zero, as without the call.  M1, rho and the state machine are the solve's and the caller's (pmh_smalxe_reset) as ever
+extern "C" int pmh_smalxe_set_initial_multiplier(pmh_smalxe s, const double *Btmu0_dev)
+{
+  PMH_ARG(s);
+  s->Btmu_given = 0;
+  if (!Btmu0_dev) return PMH_SUCCESS;
+  if (Btmu0_dev != s->Btmu) PMH_CHK(pmh_vec_copy(s->ctx, s->n, Btmu0_dev, s->Btmu));
+  s->Btmu_given = 1;
   return PMH_SUCCESS;
 }
 

@@ -41,6 +41,13 @@ struct pmh_svm_s {
   double        b = 0.0;
   int           trained = 0;
   pmh_svm_stats st;
+  // warm starts (pmh_svm_train_warm): has_dual: alpha is the dual of a training with the current labels (pmh_svm_set_labels clears it; set_penalties and
+  // set_subset keep alpha and the flag); b_mult: that training's bias from the equality's multiplier; ws_cnt / ws_masked, ws_clipped: the two counts of the
+  // last start vector, on the device and (over all ranks) on the host
+  int           has_dual = 0;
+  double        b_mult   = 0.0;
+  int          *ws_cnt   = nullptr;
+  long long     ws_masked = 0, ws_clipped = 0;
   // the probability model of the current (w, b): whatever gives the handle another model clears it
   int                 calibrated = 0;
   double              cal_A = 0.0, cal_B = 0.0;
@@ -208,6 +215,7 @@ extern "C" int pmh_svm_destroy(pmh_svm s)
   double *v[] = {s->alpha, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal, s->dots, s->Cv, s->Cinv, s->Dm};
   for (double *p : v)
     if (p) pmh_free(s->ctx, p);
+  if (s->ws_cnt) pmh_free(s->ctx, s->ws_cnt);
   delete s;
   return PMH_SUCCESS;
 }
@@ -378,17 +386,81 @@ static int svm_model(pmh_svm s)
   return PMH_SUCCESS;
 }
 
-extern "C" int pmh_svm_train(pmh_svm s)
+// The start vector of a warm training from the handle's last dual: a0_i = m_i ? min(max(scale alpha_i, 0), ub_i) : 0, in this order of operations (m: the subset
+// mask, nullptr: all ones; ub: the upper bounds, nullptr: none), and how many entries the mask zeroed that were not zero (cnt[0]) and how many were clipped at
+// ub (cnt[1]).  alpha and a0 may be the same array
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_warm_start(int n, const double *alpha, const double *__restrict__ m, const double *__restrict__ ub, double scale, double *a0, int *__restrict__ cnt)
+{
+  int nm = 0, nc = 0;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const double ai = alpha[i];
+    double       v  = 0.0;
+    if (!m || m[i] != 0.0) {
+      v = fmax(scale * ai, 0.0);
+      if (ub && v > ub[i]) v = ub[i], nc++;
+    } else if (ai != 0.0) nm++;
+    a0[i] = v;
+  }
+  if (nm) atomicAdd(cnt, nm);
+  if (nc) atomicAdd(cnt + 1, nc);
+}
+
+// the one place the start vector is formed: pmh_svm_warm_start_vector (a0: the caller's) and pmh_svm_train_warm (a0 = alpha, in place)
+static int svm_warm_start(pmh_svm s, const char *who, double scale, double *a0)
+{
+  if (!(scale > 0.0) || !std::isfinite(scale)) return pmh_set_error(PMH_ERR_ARG, "%s: alpha_scale = %g, must be positive and finite", who, scale);
+  if (!s->has_dual) return pmh_set_error(PMH_ERR_STATE, "%s: the handle holds no dual of its current labels (call pmh_svm_train first; pmh_svm_set_labels drops the dual)", who);
+  pmh_ctx ctx = s->ctx;
+  if (!s->ws_cnt) PMH_CHK(pmh_malloc(ctx, sizeof(int) * 2, (void **)&s->ws_cnt));
+  PMH_CHK(pmh_memset(ctx, s->ws_cnt, 0, sizeof(int) * 2));
+  if (s->n > 0) {
+    hipLaunchKernelGGL(k_svm_warm_start, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, ctx->stream, s->n, (const double *)s->alpha, (const double *)static_cast<SvmDualBase *>(s->H)->msk, (const double *)s->ub, scale, a0, s->ws_cnt);
+    PMH_HIP(hipGetLastError());
+  }
+  int h[2];
+  PMH_CHK(pmh_memcpy_d2h(ctx, h, s->ws_cnt, sizeof(h)));
+  double c[2] = {(double)h[0], (double)h[1]};
+  PMH_CHK(pmh_comm_sum_host(ctx, c, 2));
+  s->ws_masked = (long long)c[0], s->ws_clipped = (long long)c[1];
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_warm_start_vector(pmh_svm s, double alpha_scale, double *a0_dev)
+{
+  PMH_ARG(s && a0_dev);
+  return svm_warm_start(s, "pmh_svm_warm_start_vector", alpha_scale, a0_dev);
+}
+
+extern "C" int pmh_svm_get_warm_start_counts(pmh_svm s, long long *masked, long long *clipped)
 {
   PMH_ARG(s);
-  if (!s->sx && !s->mpgp) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_train: the handle has no solver (an earlier pmh_svm_set_labels / pmh_svm_set_penalties failed)");
+  if (masked) *masked = s->ws_masked;
+  if (clipped) *clipped = s->ws_clipped;
+  return PMH_SUCCESS;
+}
+
+// warm: alpha starts as the start vector of its own last value, SMALXE from the last training's multiplier; else both from zero
+static int svm_train(pmh_svm s, const char *who, int warm, double alpha_scale)
+{
+  if (!s->sx && !s->mpgp) return pmh_set_error(PMH_ERR_STATE, "%s: the handle has no solver (an earlier pmh_svm_set_labels / pmh_svm_set_penalties failed)", who);
   const size_t nb = sizeof(double) * (size_t)(s->n ? s->n : 1);
-  s->calibrated   = 0;
-  PMH_CHK(pmh_memset(s->ctx, s->alpha, 0, nb));
+  if (warm) PMH_CHK(svm_warm_start(s, who, alpha_scale, s->alpha)); // (a refusal changes nothing)
+  s->calibrated = 0;
+  if (!warm) PMH_CHK(pmh_memset(s->ctx, s->alpha, 0, nb));
+  s->has_dual = 0; // (until the solve has returned: alpha is an iterate meanwhile)
   long long p0 = 0, p1 = 0;
   PMH_CHK(pmh_op_svm_dual_passes(s->H, &p0));
   if (s->sx) {
     PMH_CHK(pmh_smalxe_reset(s->sx));
+    if (warm) {
+      // B'mu = mu row with b = mu / sqrt(n_S) (svm_model): the last bias over the CURRENT row m o y / sqrt(n_S), which a new subset has rebuilt -- written into
+      // the solver's own B'mu
+      double *Btmu = nullptr;
+      PMH_CHK(pmh_smalxe_get_penalized(s->sx, nullptr, nullptr, &Btmu));
+      if (s->n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, (const double *)s->row, s->b_mult * sqrt((double)svm_n_posed(s)), Btmu);
+      PMH_HIP(hipGetLastError());
+      PMH_CHK(pmh_smalxe_set_initial_multiplier(s->sx, Btmu));
+    }
     PMH_CHK(pmh_smalxe_solve(s->sx));
     pmh_smalxe_stats st;
     PMH_CHK(pmh_smalxe_get_stats(s->sx, &st));
@@ -405,9 +477,23 @@ extern "C" int pmh_svm_train(pmh_svm s)
   }
   PMH_CHK(pmh_op_svm_dual_passes(s->H, &p1));
   s->st.passes_X = p1 - p0; // the solve's passes over X (the model's two are not counted)
+  s->has_dual    = 1;
   PMH_CHK(svm_model(s));
+  s->b_mult  = s->st.b_multiplier;
   s->trained = 1;
   return PMH_SUCCESS;
+}
+
+extern "C" int pmh_svm_train(pmh_svm s)
+{
+  PMH_ARG(s);
+  return svm_train(s, "pmh_svm_train", 0, 1.0);
+}
+
+extern "C" int pmh_svm_train_warm(pmh_svm s, double alpha_scale)
+{
+  PMH_ARG(s);
+  return svm_train(s, "pmh_svm_train_warm", 1, alpha_scale);
 }
 
 extern "C" int pmh_svm_get_model(pmh_svm s, double *w_host, double *b)
@@ -520,6 +606,7 @@ extern "C" int pmh_svm_set_labels(pmh_svm s, const double *y_dev)
   pmh_ctx   ctx = s->ctx;
   const int n   = s->n;
   s->trained = s->calibrated = 0;
+  s->has_dual = 0; // alpha belongs to the old labels: no warm start from it
   svm_drop_solver(s);
   PMH_CHK(pmh_op_svm_dual_set_labels(s->H, y_dev));
   s->y = y_dev;

@@ -13,6 +13,7 @@ fits A, B on the scores of samples the caller supplies -- held-out ones, or the 
 the one pass over X that scoring takes."""
 import contextlib
 import ctypes as ct
+import math
 
 import numpy as np
 
@@ -229,10 +230,25 @@ class SVM(_SVMHandle):
         m = self._get_vec(lambda h, p: self.L.pmh_svm_get_subset(h, p, None)) != 0.0
         return None if m.all() else m
 
-    def train(self):
+    def train(self, warm_start=False, alpha_scale=1.0):
+        """Train from alpha = 0 (pmh_svm_train).  warm_start: from warm_start_vector(alpha_scale) of the handle's last dual and, with a bias, from its last
+        multiplier (pmh_svm_train_warm) -- after set_penalties (alpha_scale = C_new / C_old scales the dual with its bounds) or set_subset; not after set_labels."""
         self._need()
-        check(self.L.pmh_svm_train(self.h))
+        check(self.L.pmh_svm_train_warm(self.h, float(alpha_scale)) if warm_start else self.L.pmh_svm_train(self.h))
         return self
+
+    def warm_start_vector(self, alpha_scale=1.0):
+        """(n,): the vector train(warm_start=True, alpha_scale) starts from (pmh_svm_warm_start_vector): min(max(alpha_scale alpha, 0), C_i) on the subset
+        (L2: no upper bound), 0 on the held-out samples.  warm_start_counts then says how many entries the mask zeroed and how many the bound clipped."""
+        return self._get_vec(lambda h, p: self.L.pmh_svm_warm_start_vector(h, float(alpha_scale), p))
+
+    @property
+    def warm_start_counts(self):
+        """dict(masked, clipped) of the last start vector formed (pmh_svm_get_warm_start_counts)."""
+        self._need()
+        m, c = ct.c_longlong(), ct.c_longlong()
+        check(self.L.pmh_svm_get_warm_start_counts(self.h, ct.byref(m), ct.byref(c)))
+        return dict(masked=m.value, clipped=c.value)
 
     def _get_vec(self, entry):
         self._need()
@@ -578,6 +594,92 @@ def cross_validate(svm, k=5, seed=0, stratified=True):
     finally:
         svm.set_subset(before)
     return dict(folds=folds, accuracy=float(np.mean([f["accuracy"] for f in folds])), masks=masks)
+
+
+SCORES = ("accuracy", "precision", "recall", "specificity", "f1", "balanced_accuracy", "mcc")
+
+
+def scores(counts):
+    """The scores of confusion counts: dict(TP, FP, TN, FN) as test / test_own return it, or a list of such dicts (summed) -> dict of SCORES.  A score whose
+    denominator is 0 is nan, except mcc, which is 0 there.  Host arithmetic."""
+    if isinstance(counts, dict):
+        counts = [counts]
+    tp, fp, tn, fn = (sum(int(c[k]) for c in counts) for k in ("TP", "FP", "TN", "FN"))
+    div = lambda a, b: a / b if b else float("nan")
+    prec, rec, spec = div(tp, tp + fp), div(tp, tp + fn), div(tn, tn + fp)
+    den = (tp + fp) * (tp + fn) * (tn + fp) * (tn + fn)  # (Python integers: exact)
+    return dict(accuracy=div(tp + tn, tp + fp + tn + fn), precision=prec, recall=rec, specificity=spec, f1=div(2 * tp, 2 * tp + fp + fn),
+                balanced_accuracy=(rec + spec) / 2, mcc=(tp * tn - fp * fn) / math.sqrt(den) if den else 0.0)
+
+
+def select_C(Cs, score):
+    """(C, its index in Cs) of the highest score; among equal scores the smallest C; a nan never wins; all nan: ValueError.  Cs in any order.  Host only."""
+    best = None
+    for g in np.argsort(np.asarray(Cs, dtype=np.float64), kind="stable"):
+        if not np.isnan(score[g]) and (best is None or score[g] > score[best]):
+            best = int(g)
+    if best is None:
+        raise ValueError("grid_search: every score is nan")
+    return float(Cs[best]), best
+
+
+def _grid(Cs, score):
+    """Cs as an ascending list of floats; ValueError for an empty list, a value that is not positive and finite, or an unknown score."""
+    if score not in SCORES:
+        raise ValueError("grid_search: score must be one of %s" % ", ".join(SCORES))
+    Cs = sorted(float(c) for c in np.asarray(Cs, dtype=np.float64).ravel())
+    if not Cs:
+        raise ValueError("grid_search: Cs is empty")
+    if not all(c > 0.0 and np.isfinite(c) for c in Cs):
+        raise ValueError("grid_search: every C must be positive and finite")
+    return Cs
+
+
+def grid_search(svm, Cs, k=5, seed=0, stratified=True, score="accuracy", warm_start=True, sample_weight=None, refit=True, return_models=False):
+    """Choose C by k-fold cross-validation on a created SVM handle, X uploaded once.  Cs: absolute values of C, sorted ascending here; C_pos and C_neg keep the
+    ratio to C they were constructed with (C_pos_g = C_g C_pos / C) and sample_weight goes to set_penalties at every grid point.  For every mask of
+    kfold(y, k, seed, stratified) set_subset once, then C ascending: set_penalties, train, test_own("held_out") -- the first C of a fold from zero, every later
+    one with warm_start from the previous C's solution (alpha_scale = C_g / C_{g-1}); warm_start=False: all from zero, which gives exactly what the same loop
+    written by hand gives.
+    -> dict(Cs, counts[g][f] (test_own's dicts), score[g] (`score` of the counts summed over the folds; any of SCORES), nmv[g][f], passes_X[g][f], best_index,
+    best_C (the highest score, the smallest C among equals, a nan never), masks; return_models: W[g][f], b[g][f]).
+    The handle gets back the subset it had.  refit: it is left with best_C's penalties and trained on that subset; else with the penalties it was constructed
+    with (and sample_weight), untrained.  SVM only: SVMMulticlass is not covered."""
+    svm._need()
+    Cs = _grid(Cs, score)
+    ratio = lambda c: 1.0 if c is None else float(c) / svm.C
+    pen = lambda C: svm.set_penalties(C * ratio(svm.C_pos), C * ratio(svm.C_neg), sample_weight)
+    before = svm.subset
+    masks = kfold(svm._keep[1].to_numpy(), k, seed, stratified)
+    cell = lambda: [[None] * len(masks) for _ in Cs]
+    counts, nmv, passes, W, b = cell(), cell(), cell(), cell(), cell()
+    try:
+        for f, m in enumerate(masks):
+            svm.set_subset(m)
+            for g, C in enumerate(Cs):
+                pen(C)
+                if warm_start and g > 0:
+                    svm.train(warm_start=True, alpha_scale=C / Cs[g - 1])
+                else:
+                    svm.train()
+                t = svm.test_own("held_out")
+                st = svm.stats
+                counts[g][f], nmv[g][f], passes[g][f] = t, st.nmv, st.passes_X
+                if return_models:
+                    W[g][f], b[g][f] = svm.w, svm.b
+    finally:
+        svm.set_subset(before)
+    sc = [scores(row)[score] for row in counts]
+    best_C, best = select_C(Cs, sc)
+    out = dict(Cs=Cs, counts=counts, score=sc, nmv=nmv, passes_X=passes, best_index=best, best_C=best_C, masks=masks)
+    if return_models:
+        out.update(W=W, b=b)
+    if refit:
+        pen(best_C)
+        svm.train()
+    else:
+        svm.set_penalties(svm.C_pos, svm.C_neg, sample_weight)
+    return out
 
 
 def load_svmlight(path, n_features=None, zero_based="auto", multiclass=False):
