@@ -51,7 +51,10 @@ int pmh_init(int device, pmh_ctx *ctx);     /* PermonInitialize's device part; f
 /* Process-wide run-time switches (the role of PETSc's options database for the library's own A/B switches; the environment variable PMH_<NAME> gives the initial value).
  * "chain" (PMH_NO_CHAIN unset = 1): the penalised, projected FETI operator as the five-launch dual-space chain (dualchain.hip); 0 = the round-4 launch sequence.
  * Takes effect for operators created afterwards.  "chain_applies" / "chain_launches": counters of the chain's applications and of its own kernel launches (the middle
- * stage's -- GEMM + finishing launch, or the inner Krylov solve -- not included); set to reset.  "host_threads": threads of the host-side set-up builders (3x3-block
+ * stage's -- GEMM + finishing launch, or the inner Krylov solve -- not included); set to reset.  "chain_replay" (PMH_NO_CHAIN_REPLAY unset = 1): where SMALXE and its
+ * inner MPGP multiply the same iterate twice in a row (objective, first gradient of the next inner solve) the chain runs only its last kernel on the intermediates it
+ * kept -- the same bits, no product with F; 0 = every application is the full chain.  "chain_replays": counter of such applications (each also counts in "chain_applies");
+ * "chain_replays_redone": how many of them were taken again in full because the inner solve's projection onto the box had changed the iterate; set to reset.  "host_threads": threads of the host-side set-up builders (3x3-block
  * copies, multigrid hierarchy, class detection); initial value PMH_HOST_THREADS, else OMP_NUM_THREADS, else min(16, the CPUs the process may run on) -- with several ranks
  * per node every rank must get its share.  "svm_pairing" (PMH_SVM_NO_PAIRING unset = 1): the SVM dual's paired passes over X inside MPGP; 0 = every Hessian application as its
  * own two passes (may change between two solves; every rank of a job must set it alike).  "gt_fusion" (PMH_NO_GT_FUSION), "smalxe_prefetch" (PMH_SMALXE_NO_PREFETCH),
@@ -335,6 +338,8 @@ int pmh_feti_gluing_from_l2g(int nsub, const int *l2g_start, const int *l2g, int
 
 /* F = B K^+ B' (QPTDualize qptransform.c:1103-1128; MatCreateProd matprod.c:42-48) */
 int pmh_op_create_feti_dual(pmh_gluing B, pmh_matinv Kplus, pmh_op *F);
+/* the applications of F since its creation, through either K^+ (what the dual-space chain serves from its kept intermediates is not one); PMH_ERR_ARG for another operator */
+int pmh_feti_dual_applies(pmh_op F, long long *n);
 /* PCApply_Dual lumped: y = B K B' x (src/pc/impls/dual/pcdual.c:63-78) */
 int pmh_pc_dual_lumped_apply(pmh_gluing B, pmh_blockdiag K, const double *x, double *y);
 
@@ -973,6 +978,16 @@ int pmh_mv_test_destroy(void *E);
 int pmh_csr_kernel_info(pmh_csr A, int info[6], unsigned long long *uid);
 int pmh_csr_test_mult_epi(pmh_csr A, int kind, const double *x, const double *y1, const double *g, const double *xx, const double *lb, const double *ub, int halt, double *y,
                           double scal_host[3]);
+/* ---- test entries of the dual-space chain behind a penalised operator (csrc/qppf.hip, csrc/dualchain.hip; nothing inside the solvers changes) -----------------------
+ * pmh_op_penalized_test_mult_epi: one application to the device vector x.  kind 0: y = A_rho x.  kind 2: the gradient split of MPGP -- y = g = A_rho x - b, gf, p = gf
+ * (device vectors; lb may be NULL), the block partials of (0, |gP|^2, |gc|^2, |gf|^2) -> partials_host[4][*nblocks] and the segment sums of G0 p the last kernel emitted
+ * -> psums_host[*nseg] (both at most cap doubles per row).  same_input != 0: the caller asserts that x still holds what the operator was last applied to.  Synchronises.
+ * PMH_ERR_SUP where the operator does not run on the chain.
+ * pmh_op_penalized_test_emit: what 0: the caller is about to change x or p without emission (pmh_op_s::emit_invalidate); what 1: a kernel that writes the iterate x and
+ * leaves the segment sums of G0 x behind (here: x as it is). */
+int pmh_op_penalized_test_mult_epi(pmh_op op, int kind, int same_input, const double *x, const double *b, const double *lb, double astol, double *y, double *gf, double *p, int cap,
+                                   double *partials_host, double *psums_host, int *nblocks, int *nseg);
+int pmh_op_penalized_test_emit(pmh_op op, int what, const double *x);
 /* ---- 3x3-block product test entries (csrc/bsr.hip: the conversion as the V-cycle and K^+ call it, and one launch of k_bsr3; nothing inside the solvers changes) ----
  * pmh_bsr3_test_create: the 3x3-block device copy of the square CSR A with entries kept in `storage` (0 fp64, 1 fp32, 2 fp16 scaled by a power of two, fp32
  * arithmetic), tiles of `tile` blocks (512; any other value: 1024) and nrep_hint congruent diagonal blocks (believed only after an entry-by-entry comparison).

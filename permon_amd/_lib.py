@@ -242,6 +242,7 @@ _PROTOS = {
     "pmh_mat_regularize_csr": [C.c_int, vp, vp, vp, C.c_int, vp, C.c_double, vp, vp, vp, vp, C.POINTER(C.c_longlong)],
     "pmh_feti_gluing_from_l2g": [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, c_int_p, c_int_p, vp, vp, vp],
     "pmh_op_create_feti_dual": [vp, vp, C.POINTER(vp)],
+    "pmh_feti_dual_applies": [vp, C.POINTER(C.c_longlong)],
     "pmh_pc_dual_lumped_apply": [vp, vp, vp, vp],
     "pmh_op_create_pc_dual_dirichlet": [vp, vp, C.c_int, C.c_double, C.c_int, C.POINTER(vp)],
     "pmh_pc_dual_dirichlet_stats": [vp, C.POINTER(C.c_longlong), c_double_p, c_double_p],
@@ -347,6 +348,8 @@ _PROTOS = {
     "pmh_mv_test_destroy": [vp],
     "pmh_csr_kernel_info": [vp, c_int_p, C.POINTER(C.c_ulonglong)],
     "pmh_csr_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, c_double_p],
+    "pmh_op_penalized_test_mult_epi": [vp, C.c_int, C.c_int, vp, vp, vp, C.c_double, vp, vp, vp, C.c_int, vp, vp, c_int_p, c_int_p],
+    "pmh_op_penalized_test_emit": [vp, C.c_int, vp],
     "pmh_bsr3_test_create": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
     "pmh_bsr3_test_info": [vp, C.POINTER(C.c_longlong), c_double_p],
     "pmh_bsr3_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int],

@@ -25,6 +25,7 @@ pmh_knobs_s &pmh_knobs()
   static pmh_knobs_s k = [] {
     pmh_knobs_s v;
     v.chain = getenv("PMH_NO_CHAIN") ? 0 : 1;
+    v.chain_replay = getenv("PMH_NO_CHAIN_REPLAY") ? 0 : 1;
     v.svm_pairing = getenv("PMH_SVM_NO_PAIRING") ? 0 : 1;
     v.gt_fusion = getenv("PMH_NO_GT_FUSION") ? 0 : 1;
     v.multi_rhs = getenv("PMH_NO_MULTI_RHS") ? 0 : 1;
@@ -54,6 +55,9 @@ static int *knob_by_name(const char *name)
   if (!strcmp(name, "chain")) return &pmh_knobs().chain;
   if (!strcmp(name, "chain_applies")) return &pmh_knobs().chain_applies;
   if (!strcmp(name, "chain_launches")) return &pmh_knobs().chain_launches;
+  if (!strcmp(name, "chain_replay")) return &pmh_knobs().chain_replay;
+  if (!strcmp(name, "chain_replays")) return &pmh_knobs().chain_replays;
+  if (!strcmp(name, "chain_replays_redone")) return &pmh_knobs().chain_replays_redone;
   if (!strcmp(name, "host_threads")) return &pmh_knobs().host_threads;
   if (!strcmp(name, "svm_pairing")) return &pmh_knobs().svm_pairing;
   if (!strcmp(name, "gt_fusion")) return &pmh_knobs().gt_fusion;
@@ -181,6 +185,7 @@ extern "C" int pmh_free(pmh_ctx c, void *dptr)
   if (dptr) {
     PMH_HIP(hipStreamSynchronize(c->stream));
     PMH_HIP(hipFree(dptr));
+    c->free_epoch++; // (the next allocation may return this address for another vector)
   }
   return PMH_SUCCESS;
 }

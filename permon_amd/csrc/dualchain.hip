@@ -56,6 +56,11 @@ struct pmh_dualchain_s {
   bool     norm_done = false;        // ... and whether its norm has been formed (enqueued)
   const double *norm_ptr = nullptr;  // the vector whose T G0 u / squared norm are in normGu / the slot (as far as the stream has got)
   int      launches = 0;
+  // Whose intermediates c_cur and [w; sums of G0 w] are: the input vector of the last full application, as long as no device vector has been freed since (the
+  // context's free_epoch -- an address alone does not name a vector: a freed one's may be handed to the next allocation).  nullptr: nobody's.  rho and the
+  // epilogue's operands enter the last kernel only, so they are not part of the record (pmh_dc_replay)
+  const double      *kept_x     = nullptr;
+  unsigned long long kept_epoch = 0;
 };
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
@@ -541,6 +546,7 @@ int pmh_dc_emit_begin(pmh_dualchain dc, const double *x, const double *p, pmh_em
 {
   memset(ea, 0, sizeof(*ea));
   ea->tab = dc_tab(dc);
+  if ((x && x == dc->kept_x) || (p && p == dc->kept_x)) dc->kept_x = nullptr; // a kernel is about to write that vector
   if (x) {
     ea->o[0].part = dc->part[0];
     dc->x_emitted = x, dc->norm_done = false, dc->norm_ptr = nullptr;
@@ -549,7 +555,11 @@ int pmh_dc_emit_begin(pmh_dualchain dc, const double *x, const double *p, pmh_em
   return PMH_SUCCESS;
 }
 
-void pmh_dc_invalidate(pmh_dualchain dc) { dc->x_emitted = nullptr, dc->norm_ptr = nullptr, dc->norm_done = false; }
+void pmh_dc_invalidate(pmh_dualchain dc, bool keep_applied)
+{
+  dc->x_emitted = nullptr, dc->norm_ptr = nullptr, dc->norm_done = false;
+  if (!keep_applied) dc->kept_x = nullptr;
+}
 
 int pmh_dc_set_norm_target(pmh_dualchain dc, double *Gu, int slot)
 {
@@ -581,6 +591,47 @@ bool pmh_dc_norm_ready(pmh_dualchain dc, const double *u)
 }
 int pmh_dc_last_launches(pmh_dualchain dc) { return dc ? dc->launches : 0; }
 
+// ---- the last stage: everything before it is a function of x alone, everything that depends on rho and on the epilogue's operands is here ----------
+static int dc_last_stage(pmh_dualchain dc, const double *x, double *y, double rho, const pmh_vec_epi *epi)
+{
+  pmh_ctx     ctx = dc->ctx;
+  hipStream_t st  = ctx->stream;
+  const int   n = dc->n;
+  const dim3  vgrid((unsigned)dc->nwg), eblk(PMH_EMIT_TILE);
+  const int   kind = epi ? epi->kind : 0;
+  const pmh_emit_tab tab = dc_tab(dc);
+  pmh_emit_args      ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.tab = tab;
+  pmh_vec_epi e;
+  memset(&e, 0, sizeof(e));
+  if (epi) e = *epi;
+  e.h_partials = nullptr;
+  if (epi && epi->hosted) e.h_partials = ctx->h_partials, *epi->hosted = dc->nwg;
+  if (kind == PMH_VEPI_GRAD_SPLIT && epi->emitted_p) {
+    ea.o[1].part    = dc->part[1];
+    *epi->emitted_p = 1;
+  }
+#define DC_FINAL(EPI, WW, NU)                                                                                                                                                        \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dc_final<EPI, WW, NU>), vgrid, eblk, 0, st, n, (const double *)dc->d_ev, (const unsigned char *)dc->d_ec, tab, (const double *)dc->pf->d_S, \
+                     (const double *)dc->c_cur, (const double *)dc->w, rho, y, e, x, ea)
+#define DC_FINAL_W(EPI)                                                                                                                                                              \
+  do {                                                                                                                                                                               \
+    if (dc->W == 8 && dc->nwg <= 128) DC_FINAL(EPI, 8, 2);                                                                                                                           \
+    else if (dc->W == 8) DC_FINAL(EPI, 8, 8);                                                                                                                                        \
+    else if (dc->nwg <= 128) DC_FINAL(EPI, 16, 2);                                                                                                                                   \
+    else DC_FINAL(EPI, 16, 8);                                                                                                                                                       \
+  } while (0)
+  if (kind == PMH_VEPI_P1) DC_FINAL_W(PMH_VEPI_P1);
+  else if (kind == PMH_VEPI_GRAD_SPLIT) DC_FINAL_W(PMH_VEPI_GRAD_SPLIT);
+  else DC_FINAL_W(0);
+#undef DC_FINAL_W
+#undef DC_FINAL
+  dc->launches++;
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
 // ---- one application ---------------------------------------------------------------------------------------------------------------
 int pmh_dc_apply(pmh_dualchain dc, const double *x, double *y, double rho, const pmh_vec_epi *epi)
 {
@@ -590,6 +641,7 @@ int pmh_dc_apply(pmh_dualchain dc, const double *x, double *y, double rho, const
   const dim3  vgrid((unsigned)dc->nwg), eblk(PMH_EMIT_TILE);
   const int   kind = epi ? epi->kind : 0;
   dc->launches     = 0;
+  dc->kept_x       = nullptr; // (set again where this application gets to its end)
   const pmh_emit_tab tab = dc_tab(dc);
   // 1. the segment sums of G0 x: left behind by the kernel that wrote x, or formed here
   int slot = (epi && epi->in_slot > 0) ? epi->in_slot - 1 : -1;
@@ -643,37 +695,67 @@ int pmh_dc_apply(pmh_dualchain dc, const double *x, double *y, double rho, const
   // the ranks' shares of B u and of the sums of G0 (B u) in one exchange (PetscSFReduce, gluing.c:144-147)
   PMH_CHK(pmh_comm_allreduce_sum(ctx, dc->w, (size_t)n + (size_t)dc->nseg));
   // 5. the second projection, the penalty term and the vector phase
-  {
-    pmh_emit_args ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.tab = tab;
-    pmh_vec_epi e;
-    memset(&e, 0, sizeof(e));
-    if (epi) e = *epi;
-    e.h_partials = nullptr;
-    if (epi && epi->hosted) e.h_partials = ctx->h_partials, *epi->hosted = dc->nwg;
-    if (kind == PMH_VEPI_GRAD_SPLIT && epi->emitted_p) {
-      ea.o[1].part    = dc->part[1];
-      *epi->emitted_p = 1;
-    }
-#define DC_FINAL(EPI, WW, NU)                                                                                                                                                        \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dc_final<EPI, WW, NU>), vgrid, eblk, 0, st, n, (const double *)dc->d_ev, (const unsigned char *)dc->d_ec, tab, (const double *)dc->pf->d_S, \
-                     (const double *)dc->c_cur, (const double *)dc->w, rho, y, e, x, ea)
-#define DC_FINAL_W(EPI)                                                                                                                                                              \
-  do {                                                                                                                                                                               \
-    if (dc->W == 8 && dc->nwg <= 128) DC_FINAL(EPI, 8, 2);                                                                                                                           \
-    else if (dc->W == 8) DC_FINAL(EPI, 8, 8);                                                                                                                                        \
-    else if (dc->nwg <= 128) DC_FINAL(EPI, 16, 2);                                                                                                                                   \
-    else DC_FINAL(EPI, 16, 8);                                                                                                                                                       \
-  } while (0)
-    if (kind == PMH_VEPI_P1) DC_FINAL_W(PMH_VEPI_P1);
-    else if (kind == PMH_VEPI_GRAD_SPLIT) DC_FINAL_W(PMH_VEPI_GRAD_SPLIT);
-    else DC_FINAL_W(0);
-#undef DC_FINAL_W
-#undef DC_FINAL
-    dc->launches++;
-  }
-  PMH_HIP(hipGetLastError());
+  PMH_CHK(dc_last_stage(dc, x, y, rho, epi));
+  dc->kept_x = x, dc->kept_epoch = ctx->free_epoch;
   pmh_knobs().chain_applies++, pmh_knobs().chain_launches += dc->launches;
   return PMH_SUCCESS;
+}
+
+// ---- the same vector again: the last stage alone ---------------------------------------------------------------------------------------
+// The caller asserts that x still holds what the chain was last applied to (it wrote nothing there, nobody else did); the chain takes that only together with
+// its own record -- the address AND no pmh_free since (tests/test_gpu_chain.py frees a vector and gets the next one at its address) AND unchanged stages of F.
+// Then c_cur and [w; sums of G0 w] are what the first four stages would write again, bit for bit (fixed summation orders, no atomics), and the last kernel
+// alone gives y / g, gf, p, the block partials and the sums of G0 p of the full chain with this rho and this epilogue.  Anything else: the full application.
+//
+// Several ranks: the full application has a collective (the all-reduce of [w; sums]), this path has none.  Which of the two runs is therefore decided from host
+// state that every rank holds alike -- the knob (set alike on every rank, like every A/B switch), addresses compared for equality on the rank's own device,
+// the count of pmh_free calls, the identities of F's stage matrices, the step types behind the caller's assertion -- and never from a device value, a
+// rank-local quantity or the clock: a rank must not enter the all-reduce alone.
+// (One decision further up does read a device-written word: solve_fused, mpgp.hip, takes a replayed first gradient again in full where its projection onto the
+// box changed an entry of x.  That word is a function of x, lb and ub alone, which the ranks of a replicated dual space hold bit for bit -- every rank reads the
+// same word -- and the solve does not ask for a replay at all where its vectors are row-distributed.  Nothing in THIS function depends on it.)
+int pmh_dc_replay(pmh_dualchain dc, const double *x, double *y, double rho, const pmh_vec_epi *epi, int *replayed)
+{
+  const int kind = epi ? epi->kind : 0;
+  if (replayed) *replayed = 0;
+  bool      ok   = pmh_knobs().chain_replay && x && dc->kept_x == x && dc->kept_epoch == dc->ctx->free_epoch && (kind == 0 || kind == PMH_VEPI_GRAD_SPLIT);
+  if (ok) { // explicit local dual operators may have been attached to K^+ (or taken away) since
+    pmh_csr       g = nullptr, sc = nullptr;
+    double       *mi = nullptr;
+    const double *mo = nullptr;
+    PMH_CHK(dc->F->stages(&g, &mi, &sc, &mo));
+    ok = g && sc && g == dc->list_for && g->uid == dc->list_uid && mi == dc->zeroed && sc == dc->sc_for && sc->uid == dc->sc_uid && mo == dc->mid_out;
+  }
+  if (!ok) return pmh_dc_apply(dc, x, y, rho, epi);
+  dc->launches = 0;
+  // what the skipped launches would have left for others.  The gradient split of an iterate nobody emitted: the segment sums of G0 x in target 0 (SMALXE's
+  // ||B u|| forms from them: k_dc_norm, or the next gather).  A plain product: nothing but y
+  if (kind == PMH_VEPI_GRAD_SPLIT && !(epi->in_slot > 0)) {
+    pmh_emit_args ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.tab = dc_tab(dc), ea.o[0].part = dc->part[0];
+    dc->x_emitted = x, dc->norm_done = false, dc->norm_ptr = nullptr;
+    hipLaunchKernelGGL(k_dc_emit, dim3((unsigned)dc->nwg), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc->n, x, ea);
+    dc->launches++;
+  }
+  PMH_CHK(dc_last_stage(dc, x, y, rho, epi));
+  if (replayed) *replayed = 1;
+  pmh_knobs().chain_applies++, pmh_knobs().chain_replays++, pmh_knobs().chain_launches += dc->launches;
+  return PMH_SUCCESS;
+}
+
+// ---- test entries (pmh_op_penalized_test_emit / _test_mult_epi, qppf.hip) ------------------------------------------------------------------
+int pmh_dc_test_emit(pmh_dualchain dc, const double *x)
+{
+  pmh_emit_args ea;
+  PMH_CHK(pmh_dc_emit_begin(dc, x, nullptr, &ea));
+  hipLaunchKernelGGL(k_dc_emit, dim3((unsigned)dc->nwg), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc->n, x, ea);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+int pmh_dc_test_direction_sums(pmh_dualchain dc, int cap, double *host, int *nseg)
+{
+  PMH_ARG(host && nseg && cap >= dc->nseg);
+  *nseg = dc->nseg;
+  return pmh_memcpy_d2h(dc->ctx, host, dc->part[1], sizeof(double) * (size_t)dc->nseg);
 }

@@ -925,7 +925,7 @@ struct FetiDualOp : pmh_op_s {
   }
 };
 
-int pmh_feti_dual_applies(pmh_op F, long long *n)
+extern "C" int pmh_feti_dual_applies(pmh_op F, long long *n)
 {
   const FetiDualOp *o = dynamic_cast<const FetiDualOp *>(F);
   PMH_ARG(o && n);

@@ -80,8 +80,7 @@ struct fx_batch_window {
   bool      complete = false;
 };
 int  pmh_fexplicit_set_window(pmh_fexplicit_s *E, fx_batch_window *w); // NULL: the whole set-up (w is borrowed until then)
-// F = B K^+ B' (pmh_op_create_feti_dual): the applications since its creation, either K^+; PMH_ERR_ARG for another operator
-int  pmh_feti_dual_applies(pmh_op F, long long *n);
+// (pmh_feti_dual_applies: include/permon_hip.h)
 
 // ---- what the set-up loops of the explicit operators (fexplicit.hip, fshared.hip) need from a K^+ solver: one COLUMN per slot ----------------------------------
 // nslots == solver->nblocks: slot s = block s of the one-column solver (pmh_matinv_mult).  nslots == PMH_MV_R * solver->nblocks: the multi-right-hand-side solver

@@ -71,6 +71,10 @@ struct pmh_mpgp_s {
   int   hsum4 = 0, hsum3 = 0;
   // fused dual-space chain (pmh_op_s::emit_begin): the operator holds G0 x (0) / G0 p (1) of the CURRENT x / p, emitted by the kernel that wrote them
   bool  cx[2] = {false, false};
+  // the operator's last application was the gradient at x and nothing has written x since (every write of x and every other application clears it): a caller
+  // that multiplies x again may say so (pmh_op_s::mult_same_input).  first_applied: the caller's word that the NEXT solve's first gradient is such a repeat
+  bool  x_applied = false;
+  int   first_applied = 0;
   int   fin4_pending;      // the partials of the gradient split (rows 0..3) wait for the finalising launch of the next P1 (rows 4..6): one launch for both
   void            *cvg_user;
   double           norm_rhs, ttol, norm_rhs_div;
@@ -562,7 +566,7 @@ static pmh_emit_args g_noea;
 // the kernel about to be launched writes x (wx) and / or p (wp), one entry per thread: true = *ea is filled and the EMIT variant must be launched
 static bool emit_try(pmh_mpgp s, bool wx, bool wp, pmh_emit_args *ea)
 {
-  if (wx) s->cx[0] = false;
+  if (wx) s->cx[0] = false, s->x_applied = false;
   if (wp) s->cx[1] = false;
   if (s->csr || s->epi_ok != 1 || s->o.distributed) {
     if (wx) s->A->emit_invalidate();
@@ -727,6 +731,7 @@ static int u_objective_from_gradient(pmh_mpgp s, const double *x, const double *
 static int solve_unfused(pmh_mpgp s)
 {
   s->g_valid  = 0; // (this driver always forms its own gradient)
+  s->x_applied = false, s->first_applied = 0;
   s->cx[0] = s->cx[1] = false;
   s->A->emit_invalidate();
   pmh_ctx ctx = s->ctx;
@@ -857,6 +862,7 @@ static int solve_unfused(pmh_mpgp s)
 static int f_apply_p1(pmh_mpgp s, const int *halt = nullptr, bool p_fresh = false)
 {
   double *g = s->work[3], *p = s->work[4], *Ap = s->work[5];
+  s->x_applied = false; // the operator's last application is to p from here on
   if (s->csr) {
     pmh_spmv_epi e;
     memset(&e, 0, sizeof(e));
@@ -914,7 +920,7 @@ static int f_apply_p1(pmh_mpgp s, const int *halt = nullptr, bool p_fresh = fals
 }
 
 // g = A x - b (mpgp.c:500-502, :578-580)
-static int f_gradient(pmh_mpgp s)
+static int f_gradient(pmh_mpgp s, bool same_input = false, int *replayed = nullptr)
 {
   double *g = s->work[3];
   if (s->csr) {
@@ -924,23 +930,25 @@ static int f_gradient(pmh_mpgp s)
     e.y1   = s->b;
     return pmh_csr_spmv_launch(s->csr, s->x, g, e);
   }
-  PMH_CHK(s->A->mult(s->x, g));
+  PMH_CHK(same_input ? s->A->mult_same_input(s->x, g, replayed) : s->A->mult(s->x, g));
   return pmh_vec_axpy(s->ctx, s->n, g, -1.0, s->b);
 }
 
 // g = A x - b, the gradient split with p = gf and the partials of its norms (mpgp.c:500-507, :578-580 + :612-615): inside the operator's last kernel where it
 // offers that (the finalising launch then waits for the next P1: fin4_pending), else as three launches + the finalising one
-static int f_gradient_split(pmh_mpgp s, bool defer_finalize, bool x_from_spec = false)
+// same_input: x still holds what the operator was last applied to (pmh_vec_epi::same_input); *replayed = 1 where the operator took that word
+static int f_gradient_split(pmh_mpgp s, bool defer_finalize, bool x_from_spec = false, bool same_input = false, int *replayed = nullptr)
 {
   pmh_ctx ctx = s->ctx;
   double *gf = s->work[1], *g = s->work[3], *p = s->work[4];
+  s->x_applied = true; // whichever form follows applies the operator to x, last of all
   if (s->epi_ok && !s->csr) {
     pmh_vec_epi e;
     memset(&e, 0, sizeof(e));
     e.kind = PMH_VEPI_GRAD_SPLIT, e.b = s->b, e.lb = s->lb, e.ub = s->ub, e.astol = s->o.astol, e.gf = gf, e.p = p, e.partials = ctx->d_partials, e.ld = ctx->partials_cap, e.prow = 0;
-    e.x_from_spec = x_from_spec, e.x_out = s->x;
+    e.x_from_spec = x_from_spec, e.x_out = s->x, e.same_input = same_input;
     int hosted = 0, p_emitted = 0;
-    e.in_slot = s->cx[0] ? 1 : 0, e.hosted = ctx->dist_scalars ? nullptr : &hosted, e.emitted_p = &p_emitted;
+    e.in_slot = s->cx[0] ? 1 : 0, e.hosted = ctx->dist_scalars ? nullptr : &hosted, e.emitted_p = &p_emitted, e.replayed = replayed;
     const int rc = s->A->mult_epi(s->x, g, e);
     if (rc != PMH_EPI_UNSUPPORTED) {
       PMH_CHK(rc);
@@ -959,7 +967,7 @@ static int f_gradient_split(pmh_mpgp s, bool defer_finalize, bool x_from_spec = 
     s->epi_ok = 0;
   }
   if (x_from_spec) return pmh_set_error(PMH_ERR_STATE, "pmh_mpgp: the operator prepared an expansion step and then refused the gradient");
-  PMH_CHK(f_gradient(s));
+  PMH_CHK(f_gradient(s, same_input, replayed));
   s->cx[1] = false;
   LAUNCH(k_split_setp<false>, (const double *)s->x, (const double *)g, s->lb, s->ub, s->o.astol, gf, p, ctx->d_partials, ctx->partials_cap, g_noea, (double *)nullptr);
   return finalize_vec4(s);
@@ -982,8 +990,17 @@ static int solve_fused(pmh_mpgp s)
 
   s->cx[0] = s->cx[1] = false; // x and p come from outside
   s->hsum4 = s->hsum3 = 0;
-  s->A->emit_invalidate();
-  PMH_CHK(pmh_qpc_box_project(ctx, n, x, s->lb, s->ub, x)); // mpgp.c:497
+  // The caller's word (pmh_mpgp_set_first_operand_applied) that x is the vector the operator was last applied to: the operator keeps what it remembers of that
+  // application, and the first gradient below passes the word on.  The projection rewrites a feasible x with the bits it had -- but the x an expansion step
+  // leaves (x - afeas p - alpha gr, no re-projection) may lie below a bound by a rounding error, and then the projection does change it.  So the projection
+  // leaves a word for the host where it changed an entry, read after the first wait below (no wait of its own): the gradient is then taken again, in full.
+  // (Not with row-distributed vectors: that word would be each rank's own.)
+  const bool first_same = s->first_applied != 0 && !s->g_valid && !s->o.distributed;
+  bool       check_projection = false;
+  s->first_applied = 0, s->x_applied = false;
+  s->A->emit_invalidate(first_same);
+  if (first_same) PMH_CHK(pmh_qpc_box_project_flag(ctx, n, x, s->lb, s->ub, x, PMH_SLOT_PROJ_CHANGED));
+  else PMH_CHK(pmh_qpc_box_project(ctx, n, x, s->lb, s->ub, x)); // mpgp.c:497
   s->fin4_pending = 0;
   // asked once: a refusal (PMH_EPI_UNSUPPORTED) clears it.  (Row-distributed vectors: the operator's
   if (s->epi_ok < 0) s->epi_ok = (s->csr || !pmh_knobs().vec_epi) ? 0 : 1;
@@ -1000,7 +1017,9 @@ static int solve_fused(pmh_mpgp s)
       PMH_CHK(finalize_vec4(s));
     }
   } else {
-    PMH_CHK(f_gradient_split(s, false)); // :500-507 (the host reads the norms before any P1: finalised at once)
+    int replayed = 0;
+    PMH_CHK(f_gradient_split(s, false, false, first_same, &replayed)); // :500-507 (the host reads the norms before any P1: finalised at once)
+    check_projection = first_same && replayed != 0; // the operator did take the caller's word
     nmv++;
     p_fresh = true;
   }
@@ -1044,6 +1063,7 @@ static int solve_fused(pmh_mpgp s)
     if (can_spec && spec && spec_len > 0) {
       // a batch of CG steps decided on the device: no host round trip between them
       const int nbatch = spec_len;
+      s->x_applied     = false;
       s->h_ctl[CTL_HALT] = 0, s->h_ctl[CTL_ITER] = s->iteration, s->h_ctl[CTL_NCG] = 0, s->h_ctl[CTL_BASE] = s->iteration;
       PMH_HIP(hipMemcpyAsync(s->d_ctl, s->h_ctl, sizeof(int) * CTL_NWORDS, hipMemcpyHostToDevice, ctx->stream));
       for (int j = 0; j < nbatch; j++) {
@@ -1075,6 +1095,20 @@ static int solve_fused(pmh_mpgp s)
     }
     if (s->pre_test) PMH_CHK(s->pre_test(s->pre_test_user));
     PMH_CHK(pmh_sync(ctx));
+    if (check_projection) {
+      check_projection = false;
+      // The projection did change an entry: what the operator kept belongs to the vector as it was before.  Everything the first gradient wrote (g, gf, p, the
+      // partial sums, the emitted sums) is written again by the full application to the projected x -- the launches a solve without the caller's word makes.
+      // Several ranks: x is replicated bit for bit and every rank ran the same projection on it, so every rank reads the same word here and all of them enter
+      // the full application's all-reduce, or none does
+      if (ctx->h_scal[PMH_SLOT_PROJ_CHANGED] != 0.0) {
+        pmh_knobs().chain_replays_redone++;
+        s->hsum4 = 0;
+        s->A->emit_invalidate();
+        PMH_CHK(f_gradient_split(s, false));
+        PMH_CHK(pmh_sync(ctx));
+      }
+    }
     host_sums(s);
     s->rnorm           = sqrt(ctx->h_scal[S_GP2]);
     const double gcTgc = ctx->h_scal[S_GC2], gfTgf = ctx->h_scal[S_GF2];
@@ -1243,6 +1277,15 @@ int pmh_mpgp_set_convergence_margin(pmh_mpgp s, double margin)
 {
   PMH_ARG(s);
   s->cvg_margin = margin;
+  return PMH_SUCCESS;
+}
+
+// internal (smalxe.hip): see pmh_internal.h
+int pmh_mpgp_x_applied(pmh_mpgp s) { return (s && s->x_applied) ? 1 : 0; }
+int pmh_mpgp_set_first_operand_applied(pmh_mpgp s, int on)
+{
+  PMH_ARG(s);
+  s->first_applied = (on && use_fused(s)) ? 1 : 0;
   return PMH_SUCCESS;
 }
 

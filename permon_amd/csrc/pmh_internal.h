@@ -23,6 +23,10 @@ struct pmh_knobs_s {
   int chain; // the five-launch dual-space chain (dualchain.hip)
   // counters (pmh_get_knob; pmh_set_knob resets them): applications of the chain and its OWN launches (the middle stage's are not counted)
   int chain_applies = 0, chain_launches = 0;
+  // the chain's last stage alone on the intermediates it kept, where the same vector is multiplied again (dualchain.hip pmh_dc_replay): PMH_NO_CHAIN_REPLAY = 0;
+  // chain_replays counts them (a replay also counts in chain_applies, and adds only its own launches to chain_launches)
+  // chain_replays_redone: first gradients of an inner solve taken again in full because the solve's projection onto the box had changed the iterate (mpgp.hip)
+  int chain_replay = 1, chain_replays = 0, chain_replays_redone = 0;
   // A/B switches that sit on per-product / per-iteration paths: the environment is read ONCE (ctx.hip pmh_knobs), never inside a solver loop
   int gt_fusion = 1;       // PMH_NO_GT_FUSION: the projector's v - G'(...) epilogue folded into the G' kernel (qppf.hip)
   int smalxe_prefetch = 1; // PMH_SMALXE_NO_PREFETCH: ||B u|| enqueued before the inner solver's host wait (smalxe.hip)
@@ -74,6 +78,7 @@ struct pmh_ctx_s {
   int        rank, size, force_comm;
   double    *d_commbuf; // small staging buffer for scalar allreduces
   int        dist_scalars; // set while a solver with row-distributed vectors runs: finalised scalars are all-reduced
+  unsigned long long free_epoch = 0; // counts pmh_free: what is remembered about a device vector by its address holds only while no vector has been freed
   // host-staged transport of the collectives (pmh_comm_set_host_transport: e.g. MPI_Allreduce on the glue's communicator) instead of RCCL
   pmh_comm_host_fn hook      = nullptr;
   void            *hook_user = nullptr;
@@ -179,9 +184,12 @@ struct pmh_vec_epi {
   // 0 = none: the operator forms it itself).  hosted != nullptr: the operator may ALSO store its block partials in the pinned host copy h_partials (same rows /
   // ld) and then sets *hosted = the number of blocks it wrote: the caller adds them up on the host after its next wait, no finalising launch.  emitted_p
   // (GRAD_SPLIT): the last kernel also emits G0 p for the p = gf it writes and sets *emitted_p = 1
-  int           in_slot;
+  // same_input: the caller asserts that x still holds, entry by entry, what this operator was last applied to (whatever rho and the epilogue were then).  The
+  // chain then runs its last kernel alone on the intermediates it kept -- the same bits -- where its own record agrees; every other operator ignores it.
+  // replayed != nullptr: set to 1 where the operator did take the caller's word; the caller clears it first (an operator that ignores same_input never writes it)
+  int           in_slot, same_input;
   double       *h_partials;
-  int          *hosted, *emitted_p;
+  int          *hosted, *emitted_p, *replayed;
 };
 // ---- coarse-space emission of the fused dual-space chain (dualchain.hip, emit_inline.h) ----------------------------------
 // G0 of the projector cut into (row, block of 256 columns) segments; the kernel that writes a dual vector sums its own segments (see emit_inline.h)
@@ -207,12 +215,15 @@ struct pmh_op_s {
   virtual ~pmh_op_s() {}
   virtual int     mult(const double *x, double *y) = 0;
   virtual int     mult_epi(const double *, double *, const pmh_vec_epi &) { return PMH_EPI_UNSUPPORTED; }
+  // mult for a caller who asserts that x still holds what this operator was last applied to (pmh_vec_epi::same_input); *replayed as pmh_vec_epi::replayed
+  virtual int     mult_same_input(const double *x, double *y, int * /*replayed*/ = nullptr) { return mult(x, y); }
   // Coarse emission (fused dual-space chain): the caller is about to launch a kernel that writes the iterate x (x != nullptr) and / or the direction p (p !=
   // nullptr), one entry per thread on the grid of the streaming Vec kernels; on PMH_SUCCESS *ea is filled and the kernel MUST end with pmh_emit_tail(*ea, ...)
   // -- the operator then takes G0 x / G0 p as given when it is applied with pmh_vec_epi::in_slot 0 / 1.  PMH_EPI_UNSUPPORTED: no such chain, launch the plain
   // kernel.
   virtual int     emit_begin(const double * /*x*/, const double * /*p*/, pmh_emit_args *) { return PMH_EPI_UNSUPPORTED; }
-  virtual void    emit_invalidate() {} // x or p are about to change without emission
+  // x or p are about to change without emission; keep_applied: the vector this operator was last applied to is not among them (pmh_vec_epi::same_input may follow)
+  virtual void    emit_invalidate(bool /*keep_applied*/ = false) {}
   virtual int     spec_expansion_ready() { return 0; } // the last PMH_VEPI_P1 prepared the expansion step (pmh_vec_epi::spec_alpha)
   // MatMultTranspose slot; operators that are symmetric by construction forward to mult
   virtual int     mult_transpose(const double *, double *) { return pmh_set_error(PMH_ERR_SUP, "this operator has no MatMultTranspose slot"); }
@@ -261,6 +272,8 @@ int pmh_finalize_partials_slots(pmh_ctx ctx, const double *partials, int ld, int
 int pmh_vec_grid(int n); // deterministic grid size of the streaming kernels (function of n only)
 
 // vec kernels needed across translation units (device pointers, enqueue only)
+// pmh_qpc_box_project that also says whether it changed an entry: the host zeroes h_scal[slot] here, a thread that changes an entry writes 1 there
+int pmh_qpc_box_project_flag(pmh_ctx ctx, int n, const double *x, const double *lb, const double *ub, double *Px, int slot);
 int pmh_k_dot_partials(pmh_ctx ctx, int n, const double *x, const double *y, int slot); // -> d_scal/h_scal[slot]
 int pmh_qppf_apply_G_norm2(pmh_qppf pf, const double *v, double *Gv, int slot);          // qppf.hip: G v and ||G v||^2 -> scalar slot, enqueue only
 int pmh_mpgp_set_pre_test_hook(pmh_mpgp s, int (*f)(void *), void *user);             // mpgp.hip: see there
@@ -268,6 +281,12 @@ int pmh_mpgp_set_pre_test_hook(pmh_mpgp s, int (*f)(void *), void *user);       
 int pmh_mpgp_set_convergence_margin(pmh_mpgp s, double margin);
 // the next solve starts from a gradient the caller has put into the solver's g (returned): smalxe.hip
 int pmh_mpgp_set_gradient_valid(pmh_mpgp s, int valid, double **g);
+// mpgp.hip: 1 = the operator's last application was the gradient at the solver's current x and nothing has written x since
+int pmh_mpgp_x_applied(pmh_mpgp s);
+// the next solve's first gradient is taken at the very vector the operator was last applied to (one-shot, like the gradient above): passed on as
+// pmh_vec_epi::same_input.  Should the solve's projection onto the box change an entry of that vector after all (an iterate a rounding error below a bound), the
+// solve notices at its first wait and takes the gradient again in full: never another result
+int pmh_mpgp_set_first_operand_applied(pmh_mpgp s, int on);
 // mpgp.hip: called right before the speculative Ap = A p of the next iteration is enqueued
 int pmh_mpgp_set_pre_p1_hook(pmh_mpgp s, int (*f)(void *), void *user);
 // SMALXE's ||B u|| riding on the next product of the penalised operator (qppf.hip): G0 u shares the pass over G0 with G0 x, T (G0 u) and its squared norm are
@@ -280,6 +299,7 @@ int pmh_op_penalized_normG_ready(pmh_op op, const double *u);           // 1: sl
 // launches of the chain's last application (-1: no chain) // 1 if the armed request was served by the last product (and clears it), 0 otherwise (and disarms)
 int pmh_op_penalized_chain_launches(pmh_op op);
 #define PMH_SLOT_NORMBU2 48 // ||B u||^2 prefetched for SMALXE's inner convergence test
+#define PMH_SLOT_PROJ_CHANGED 52 // pmh_qpc_box_project_flag: non-zero = the projection changed an entry
 #define PMH_SLOT_TEST_SPMV 56 // [56, 59): p'Ap, g'p, feasible step of pmh_csr_test_mult_epi (spmv.hip; a test entry, no solver writes them)
 int pmh_host_scalar(pmh_ctx ctx, int slot, double *v);                                  // sync + read h_scal[slot]
 

@@ -811,9 +811,9 @@ struct PenalizedOp : pmh_op_s {
     return rc;
   }
   int  emit_begin(const double *x, const double *p, pmh_emit_args *ea) override { return chain() ? pmh_dc_emit_begin(dc, x, p, ea) : PMH_EPI_UNSUPPORTED; }
-  void emit_invalidate() override
+  void emit_invalidate(bool keep_applied = false) override
   {
-    if (dc) pmh_dc_invalidate(dc);
+    if (dc) pmh_dc_invalidate(dc, keep_applied);
   }
   // the fully fused product y = rho Q x + P F (P x) [+ vector epilogue] of the one-launch projector form
   bool fused_dense()
@@ -836,7 +836,7 @@ struct PenalizedOp : pmh_op_s {
     // (the chain leaves its block partials per 1024-entry tile for the HOST to sum: a caller that finalises on the device -- row-distributed scalars, e.hosted == NULL --
     // counts on one partial per workgroup of the streaming Vec kernels' grid, so it gets the separate vector kernels behind the chain's plain product instead)
     if (fold()) return pmh_knobs().vec_epi ? fold_apply(x, y, &e) : PMH_EPI_UNSUPPORTED;
-    if (chain()) return e.hosted ? pmh_dc_apply(dc, x, y, rho, &e) : PMH_EPI_UNSUPPORTED;
+    if (chain()) return !e.hosted ? PMH_EPI_UNSUPPORTED : (e.same_input ? pmh_dc_replay(dc, x, y, rho, &e, e.replayed) : pmh_dc_apply(dc, x, y, rho, &e));
     if (!pmh_knobs().vec_epi) return PMH_EPI_UNSUPPORTED; // A/B: the separate vector kernels
     if (!fused_dense() || n > PMH_MAX_VEC_BLOCKS * PMH_BLOCK || pmh_vec_grid(n) != (n + PMH_BLOCK - 1) / PMH_BLOCK) return PMH_EPI_UNSUPPORTED;
     return mult_fused_dense(x, y, &e);
@@ -846,6 +846,13 @@ struct PenalizedOp : pmh_op_s {
     pmh_dc_destroy(dc);
     pmh_free(ctx, t);
     if (xwork) pmh_free(ctx, xwork);
+  }
+  // only the chain has anything to gain from the caller's assertion (it keeps the intermediates that do not depend on rho); the folded SVM form, the fused-dense
+  // form, the 10- and 12-launch forms and CSR operators multiply as ever
+  int mult_same_input(const double *x, double *y, int *replayed = nullptr) override
+  {
+    if (!fold() && chain()) return pmh_dc_replay(dc, x, y, rho, nullptr, replayed);
+    return mult(x, y);
   }
   // MatMult_Penalized matpenalized.c:12-22: y = BtB x; y *= rho; y = y + A x
   int mult(const double *x, double *y) override
@@ -977,6 +984,43 @@ int pmh_op_penalized_chain_launches(pmh_op op)
 {
   PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
   return (o && o->dc) ? pmh_dc_last_launches(o->dc) : -1;
+}
+
+extern "C" int pmh_op_penalized_test_emit(pmh_op op, int what, const double *x)
+{
+  PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
+  PMH_ARG(o && (what == 0 || (what == 1 && x)));
+  if (!o->chain()) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_emit: the operator does not run on the dual-space chain");
+  if (what == 0) {
+    o->emit_invalidate();
+    return PMH_SUCCESS;
+  }
+  return pmh_dc_test_emit(o->dc, x);
+}
+
+extern "C" int pmh_op_penalized_test_mult_epi(pmh_op op, int kind, int same_input, const double *x, const double *b, const double *lb, double astol, double *y, double *gf, double *p, int cap,
+                                              double *partials_host, double *psums_host, int *nblocks, int *nseg)
+{
+  PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
+  PMH_ARG(o && x && y && (kind == 0 || kind == PMH_VEPI_GRAD_SPLIT));
+  if (!o->chain()) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_mult_epi: the operator does not run on the dual-space chain");
+  pmh_ctx ctx = o->ctx;
+  if (kind == 0) {
+    PMH_CHK(same_input ? o->mult_same_input(x, y) : o->mult(x, y));
+    return pmh_sync(ctx);
+  }
+  PMH_ARG(b && gf && p && partials_host && psums_host && nblocks && nseg);
+  pmh_vec_epi e;
+  memset(&e, 0, sizeof(e));
+  int hosted = 0, p_emitted = 0;
+  e.kind = PMH_VEPI_GRAD_SPLIT, e.b = b, e.lb = lb, e.astol = astol, e.gf = gf, e.p = p, e.partials = ctx->d_partials, e.ld = ctx->partials_cap, e.prow = 0;
+  e.hosted = &hosted, e.emitted_p = &p_emitted, e.same_input = same_input;
+  PMH_CHK(o->mult_epi(x, y, e));
+  PMH_CHK(pmh_sync(ctx));
+  if (!hosted || !p_emitted || hosted > cap) return pmh_set_error(PMH_ERR_STATE, "pmh_op_penalized_test_mult_epi: %d blocks of partials (room for %d), direction emitted: %d", hosted, cap, p_emitted);
+  for (int k = 0; k < 4; k++) memcpy(partials_host + (size_t)k * hosted, ctx->h_partials + (size_t)k * ctx->partials_cap, sizeof(double) * (size_t)hosted);
+  *nblocks = hosted;
+  return pmh_dc_test_direction_sums(o->dc, cap, psums_host, nseg);
 }
 
 int pmh_op_penalized_take_aux_done(pmh_op op)

@@ -347,9 +347,13 @@ extern "C" int pmh_smalxe_destroy(pmh_smalxe s)
 }
 
 // QPComputeObjective qp.c:913-927 on the penalised QP: f = -u'(b_inner - 1/2 A_rho u)
-static int objective(pmh_smalxe s, double *f)
+// after_inner: the inner solve has just ended and nothing has touched u since.  Where its last application of A_rho was the gradient at this very u (an
+// expansion step followed by the test that ended the solve, no product enqueued ahead), the operator is told so: the chain then runs its last kernel alone
+// (dualchain.hip pmh_dc_replay) -- the same bits.  What is asked depends on the inner solver's step types alone, which every rank takes alike
+static int objective(pmh_smalxe s, double *f, bool after_inner)
 {
-  PMH_CHK(s->A_inner->mult(s->u, s->xwork));
+  if (after_inner && pmh_mpgp_x_applied(s->inner)) PMH_CHK(s->A_inner->mult_same_input(s->u, s->xwork));
+  else PMH_CHK(s->A_inner->mult(s->u, s->xwork));
   PMH_CHK(pmh_vec_aypx(s->ctx, s->n, s->xwork, -0.5, s->b_inner));
   double dot;
   PMH_CHK(pmh_vec_dot(s->ctx, s->n, s->u, s->xwork, &dot));
@@ -421,7 +425,10 @@ extern "C" int pmh_smalxe_solve(pmh_smalxe s)
   s->BtBu_valid = 0;
   if (given) PMH_CHK(pmh_qpc_box_project(ctx, n, s->u, s->lb, s->ub, s->u)); // (what the inner MPGP does to its start, before the pair is looked at)
   if (s->o.knoll && !given) PMH_CHK(pmh_qppf_apply_P(s->pf, s->b, s->u)); // the Knoll trick smalxe.c:938-943: projected rhs as initial guess
-  PMH_CHK(objective(s, &Lag_old));
+  PMH_CHK(objective(s, &Lag_old, false)); // (u comes from outside: a full application)
+  // A_rho was last applied to u, and u is known to be feasible: true of a given pair (projected above) and after every objective() in the loop -- not of the
+  // Knoll start or of whatever else the caller left in u, which the inner solver's projection may change
+  bool u_applied = given != 0;
   PMH_CHK(update_normBu(s, s->u, &s->normBu_old, &s->enorm));
   s->iteration       = 0;
   s->inner_iter_accu = 0;
@@ -460,6 +467,9 @@ extern "C" int pmh_smalxe_solve(pmh_smalxe s)
       PMH_CHK(pmh_mpgp_set_gradient_valid(s->inner, 1, &g));
       if (g) PMH_CHK(pmh_vec_axpy(ctx, n, g, rho_now, s->BtBu));
     }
+    // the inner solve's first gradient is A_rho u - b_inner at the u of the objective just evaluated: only rho and b_inner have changed since
+    PMH_CHK(pmh_mpgp_set_first_operand_applied(s->inner, u_applied && !s->reuse));
+    u_applied = false;
     PMH_CHK(pmh_mpgp_solve(s->inner));
     pmh_mpgp_stats st;
     PMH_CHK(pmh_mpgp_get_stats(s->inner, &st));
@@ -481,8 +491,10 @@ extern "C" int pmh_smalxe_solve(pmh_smalxe s)
       PMH_CHK(pmh_vec_waxpy(ctx, n, s->xwork, -1.0, g, s->b_inner));
       PMH_CHK(pmh_vec_dot(ctx, n, s->u, s->xwork, &dot));
       Lag = -0.5 * dot;
-    } else
-    PMH_CHK(objective(s, &Lag));
+    } else {
+      PMH_CHK(objective(s, &Lag, true));
+      u_applied = true;
+    }
     PMH_CHK(smalxe_update(s, Lag_old, Lag, rho));
     Lag_old       = Lag;
     s->normBu_old = s->normBu;

@@ -271,6 +271,34 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_box_gradreduced(long long n, cons
   }
 }
 
+// the same projection, and a word for the host: 1 -> *changed where an entry of Px differs from x's in its bits (every such thread stores the same value; nobody stores 0)
+__global__ __launch_bounds__(PMH_BLOCK) void k_box_project_flag(long long n, const double *x, const double *lb, const double *ub, double *Px, double *changed)
+{
+  GRID_STRIDE(i, n)
+  {
+    const double xi = x[i];
+    double       v  = xi;
+    if (lb) {
+      double l = lb[i];
+      v        = (v > l) ? v : l;
+    }
+    if (ub) {
+      double u = ub[i];
+      v        = (v < u) ? v : u;
+    }
+    Px[i] = v;
+    if (__double_as_longlong(v) != __double_as_longlong(xi)) *changed = 1.0; // bit patterns: -0.0 moved onto a bound +0.0 is a change too
+  }
+}
+
+int pmh_qpc_box_project_flag(pmh_ctx ctx, int n, const double *x, const double *lb, const double *ub, double *Px, int slot)
+{
+  PMH_ARG(ctx && n >= 0 && slot >= 0 && slot < PMH_NSCAL);
+  ctx->h_scal[slot] = 0.0;
+  LAUNCH_VEC(k_box_project_flag, n, x, lb, ub, Px, ctx->h_scal + slot);
+  return PMH_SUCCESS;
+}
+
 extern "C" int pmh_qpc_box_project(pmh_ctx ctx, int n, const double *x, const double *lb, const double *ub, double *Px)
 {
   PMH_ARG(ctx && n >= 0);
