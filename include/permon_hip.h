@@ -58,7 +58,11 @@ int pmh_init(int device, pmh_ctx *ctx);     /* PermonInitialize's device part; f
  * copies, multigrid hierarchy, class detection); initial value PMH_HOST_THREADS, else OMP_NUM_THREADS, else min(16, the CPUs the process may run on) -- with several ranks
  * per node every rank must get its share.  "svm_pairing" (PMH_SVM_NO_PAIRING unset = 1): the SVM dual's paired passes over X inside MPGP; 0 = every Hessian application as its
  * own two passes (may change between two solves; every rank of a job must set it alike).  "gt_fusion" (PMH_NO_GT_FUSION), "smalxe_prefetch" (PMH_SMALXE_NO_PREFETCH),
- * "mg_d0_fusion" (PMH_MG_NO_D0_FUSION): A/B switches of fusions on per-product paths, 1 = fused (the default).  Unknown name: PMH_ERR_ARG. */
+ * "mg_d0_fusion" (PMH_MG_NO_D0_FUSION): A/B switches of fusions on per-product paths, 1 = fused (the default).  "orbit_adapted" (PMH_NO_ORBIT_ADAPTED unset = 1): a class of
+ * PMH_FX_CLASS_ORBIT with all 48 operations of the cube (pmh_fexplicit_set_box_symmetry) on one rank applies W_c in the group's symmetry-adapted basis (fshared_adapted.h)
+ * instead of the orbit GEMM; read at the assembly and at every application, 0 = the GEMM.  "orbit_adapted_classes": counter of classes that took that form at their assembly,
+ * "orbit_adapted_fallbacks": of classes that were eligible but failed the set-up's self-check against the GEMM and stayed on it; set to reset.  "orbit_adapted_spoil" (tests):
+ * 1 = the next assembly builds its basis with one table row negated, which the self-check must catch.  Unknown name: PMH_ERR_ARG. */
 int pmh_set_knob(const char *name, int value);
 int pmh_get_knob(const char *name, int *value);
 int pmh_finalize(pmh_ctx ctx);
@@ -393,6 +397,16 @@ int pmh_fexplicit_stripe_bytes(int nblocks, const int *n_gamma, int size, double
    induced by the signed coordinate permutations that map the box onto itself and leave the block's matrix (CSR rowptr / col / val, n rows; NULL: not
    checked) invariant -- generators checked on nsample rows, the group is their closure (<= 48 operations, 0 = identity).  perm, sign: [48 * n]. */
 int pmh_box_symmetries(const int *dims, int ndof, const int *rowptr, const int *col, const double *val, int nsample, int *nsym, int *perm, signed char *sign);
+/* the same, and the operations themselves: ops[6 g ...] = (ax[3], fl[3]), new coordinate a = fl[a] * old coordinate ax[a] (NULL: not wanted) */
+int pmh_box_symmetries_ops(const int *dims, int ndof, const int *rowptr, const int *col, const double *val, int nsample, int *nsym, int *perm, signed char *sign, int *ops);
+/* Host routine (no device): the symmetry-adapted basis of the dofs rel[0 .. n_c) (block-relative, ascending, closed under the box's 48 operations) of a cube.  mult / dim: [10]
+   multiplicity and dimension of the irreps A1g A2g Eg T1g T2g A1u A2u Eu T1u T2u; the basis functions are numbered orbit after orbit, irrep after irrep, copy after copy, partner
+   after partner; orbit o (of orb_size[o] positions, orb_pos in the same running order) owns as many functions as positions.  Per function: its irrep, the row of its copy in the
+   irrep's block W^_i, its partner, the copy's vector v_k (3 doubles) and its values on the orbit's positions (tables[48 row ...]).  PMH_ERR_SUP: no such basis (not all 48). */
+int pmh_orbit_basis(const int *dims, int ndof, int n_c, const int *rel, int *norb, int *mult, int *dim, int *orb_size, int *orb_pos, int *row_irrep, int *row_index, int *row_partner,
+                    double *row_v, double *tables);
+/* whether class cls of a PMH_FX_CLASS_ORBIT operator applies W_c in the symmetry-adapted basis (after the assembly) */
+int pmh_fexplicit_orbit_adapted(pmh_fexplicit E, int cls, int *adapted);
 /* sorted union of the images of the dofs in_rel under those operations (out_rel: capacity nx ny nz ndof, may be NULL to get the count); host */
 int pmh_box_symmetry_closure(const int *dims, int ndof, const int *rowptr, const int *col, const double *val, int n_in, const int *in_rel, int *n_out, int *out_rel, int *nsym);
 /* the two together for box-shaped blocks: symmetries of the box checked against the CSR of one block of the class (column indices relative to the block),

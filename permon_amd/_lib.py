@@ -381,6 +381,9 @@ _PROTOS = {
     "pmh_fexplicit_class_sym_plan": [C.c_int, C.c_int, vp, vp],
     "pmh_fexplicit_orbit_row_tile": [C.c_int, vp, vp],
     "pmh_box_symmetries": [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp],
+    "pmh_box_symmetries_ops": [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp],
+    "pmh_orbit_basis": [vp, C.c_int, C.c_int, vp, c_int_p, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "pmh_fexplicit_orbit_adapted": [vp, C.c_int, c_int_p],
     "pmh_box_symmetry_closure": [vp, C.c_int, vp, vp, vp, C.c_int, vp, c_int_p, vp, c_int_p],
     "pmh_fexplicit_set_box_symmetry": [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp],
     "pmh_fexplicit_class_union": [vp, C.c_int, vp, vp],

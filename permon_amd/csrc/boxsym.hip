@@ -55,7 +55,8 @@ double csr_entry(const int *rowptr, const int *col, const double *val, int i, in
 // dims: nodes per direction; rowptr / col / val: the block's matrix (n = nx ny nz ndof rows) or NULL: every GENERATOR (3 reflections, the swaps of
 // equal axes) is checked on `nsample` rows spread over the block (K[g i][g j] s_i s_j = K[i][j] to 1e-11 of the largest sampled entry) and dropped if
 // it fails; the operations returned are the closure of the surviving generators (<= 48), operation 0 the identity.  perm / sign: [48 * n] each.
-extern "C" int pmh_box_symmetries(const int *dims, int ndof, const int *rowptr, const int *col, const double *val, int nsample, int *nsym, int *perm, signed char *sign)
+// ops (optional): [48 * 6] the operations themselves, (ax[3], fl[3]) each, for the symmetry-adapted basis (orbitbasis.hip)
+extern "C" int pmh_box_symmetries_ops(const int *dims, int ndof, const int *rowptr, const int *col, const double *val, int nsample, int *nsym, int *perm, signed char *sign, int *ops)
 {
   PMH_ARG(dims && dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1 && ndof >= 1 && nsym && perm && sign);
   const long long nn = (long long)dims[0] * dims[1] * dims[2] * ndof;
@@ -110,7 +111,15 @@ extern "C" int pmh_box_symmetries(const int *dims, int ndof, const int *rowptr, 
   }
   *nsym = (int)group.size();
   for (size_t g = 0; g < group.size(); g++) materialise(group[g], dims, ndof, perm + g * (size_t)n, sign + g * (size_t)n);
+  if (ops)
+    for (size_t g = 0; g < group.size(); g++)
+      for (int a = 0; a < 3; a++) ops[6 * g + a] = group[g].ax[a], ops[6 * g + 3 + a] = group[g].fl[a];
   return PMH_SUCCESS;
+}
+
+extern "C" int pmh_box_symmetries(const int *dims, int ndof, const int *rowptr, const int *col, const double *val, int nsample, int *nsym, int *perm, signed char *sign)
+{
+  return pmh_box_symmetries_ops(dims, ndof, rowptr, col, val, nsample, nsym, perm, sign, nullptr);
 }
 
 // The closure of a set of a block's dofs (in_rel: n_in block-relative indices) under the box's symmetries that leave the block's matrix invariant (pmh_box_symmetries):

@@ -34,6 +34,7 @@ pmh_knobs_s &pmh_knobs()
     v.mg_d0_fusion = getenv("PMH_MG_NO_D0_FUSION") ? 0 : 1;
     v.vec_epi = getenv("PMH_NO_VEC_EPI") ? 0 : 1;
     v.mpgp_spec = getenv("PMH_MPGP_NO_SPEC") ? 0 : 1;
+    v.orbit_adapted = getenv("PMH_NO_ORBIT_ADAPTED") ? 0 : 1;
     int         nt = 0;
     const char *e  = getenv("PMH_HOST_THREADS");
     if (!e) e = getenv("OMP_NUM_THREADS");
@@ -67,6 +68,10 @@ static int *knob_by_name(const char *name)
   if (!strcmp(name, "mg_d0_fusion")) return &pmh_knobs().mg_d0_fusion;
   if (!strcmp(name, "mpgp_spec")) return &pmh_knobs().mpgp_spec;
   if (!strcmp(name, "vec_epi")) return &pmh_knobs().vec_epi;
+  if (!strcmp(name, "orbit_adapted")) return &pmh_knobs().orbit_adapted;
+  if (!strcmp(name, "orbit_adapted_classes")) return &pmh_knobs().orbit_adapted_classes;
+  if (!strcmp(name, "orbit_adapted_fallbacks")) return &pmh_knobs().orbit_adapted_fallbacks;
+  if (!strcmp(name, "orbit_adapted_spoil")) return &pmh_knobs().orbit_adapted_spoil;
   return nullptr;
 }
 extern "C" int pmh_set_knob(const char *name, int value)

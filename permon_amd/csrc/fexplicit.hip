@@ -643,10 +643,10 @@ extern "C" int pmh_fexplicit_set_box_symmetry(pmh_fexplicit E, int cls, const in
   PMH_CHK(fxs_class_union(E->sh, cls, &nc, urel.data()));
   const long long n = (long long)dims[0] * dims[1] * dims[2] * ndof;
   if (urel.back() >= n) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_set_box_symmetry: the blocks of class %d have more than %d x %d x %d x %d dofs", cls, dims[0], dims[1], dims[2], ndof);
-  std::vector<int>         perm((size_t)48 * n), pos((size_t)n, -1), pm;
+  std::vector<int>         perm((size_t)48 * n), pos((size_t)n, -1), pm, ops(6 * 48), ops_used;
   std::vector<signed char> sign((size_t)48 * n), sg;
   int                      nsym = 0;
-  PMH_CHK(pmh_box_symmetries(dims, ndof, rowptr, col, val, 4000, &nsym, perm.data(), sign.data()));
+  PMH_CHK(pmh_box_symmetries_ops(dims, ndof, rowptr, col, val, 4000, &nsym, perm.data(), sign.data(), ops.data()));
   for (int i = 0; i < nc; i++) pos[urel[i]] = i;
   int used = 0;
   for (int g = 0; g < nsym; g++) { // keep the operations under which the touched set is closed
@@ -654,12 +654,21 @@ extern "C" int pmh_fexplicit_set_box_symmetry(pmh_fexplicit E, int cls, const in
     for (int i = 0; i < nc && closed; i++) closed = pos[perm[(size_t)g * n + urel[i]]] >= 0;
     if (!closed) continue;
     for (int i = 0; i < nc; i++) pm.push_back(pos[perm[(size_t)g * n + urel[i]]]), sg.push_back(sign[(size_t)g * n + urel[i]]);
+    ops_used.insert(ops_used.end(), ops.begin() + 6 * g, ops.begin() + 6 * (g + 1));
     used++;
   }
   if (nsym_used) *nsym_used = used;
   if (used <= 1) return PMH_SUCCESS;
   if (E->assembled) return pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_set_box_symmetry: call before the assembly");
-  return fxs_set_symmetry(E->sh, cls, used, pm.data(), sg.data());
+  PMH_CHK(fxs_set_symmetry(E->sh, cls, used, pm.data(), sg.data()));
+  return fxs_set_symmetry_ops(E->sh, cls, used, ops_used.data()); // (the symmetry-adapted apply of the orbit storage needs the operations themselves)
+}
+
+extern "C" int pmh_fexplicit_orbit_adapted(pmh_fexplicit E, int cls, int *adapted)
+{
+  PMH_ARG(E && adapted);
+  *adapted = E->sh ? fxs_orbit_adapted(E->sh, cls) : 0;
+  return PMH_SUCCESS;
 }
 
 extern "C" int pmh_fexplicit_apply_flops(pmh_fexplicit E, double *flops)

@@ -8,6 +8,8 @@ void      fxs_destroy(fx_shared *S);
 int       fxs_set_stripe(fx_shared *S, int rank, int size);
 int       fxs_class_union(fx_shared *S, int c, int *n_c, int *urel_out);
 int       fxs_set_symmetry(fx_shared *S, int c, int nsym, const int *posmap, const signed char *sign);
+int       fxs_set_symmetry_ops(fx_shared *S, int c, int nsym, const int *ops); // after fxs_set_symmetry: the box operations (ax[3], fl[3]) behind the class's symmetries
+int       fxs_orbit_adapted(fx_shared *S, int c);                              // the class applies W_c in the symmetry-adapted basis
 long long fxs_dense_bytes(fx_shared *S);
 double    fxs_apply_bytes(fx_shared *S);
 double    fxs_apply_flops(fx_shared *S);

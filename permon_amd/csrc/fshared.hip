@@ -19,11 +19,15 @@
 //   2 PMH_FX_CLASS_ORBIT only the rows of the orbit representatives under the class's symmetries, k_fxo_gemm16: a GEMM on the fp64 matrix
 //     instruction,
 //                          4 n_c^2 / 24 bytes for the cube's 48 operations, compute-bound (the default for congruent cubes)
+//     -- and, where all 48 operations of the cube act on one rank, W_c applied in the group's symmetry-adapted basis instead (fshared_adapted.h, orbitbasis.hip):
+//     ten small dense blocks, as many bytes read once, memory-bound; knob orbit_adapted
 // and the set-up by symmetry (fxs_set_symmetry: one K^+ solve per orbit of rows, self-checked against direct solves) serves 1 and 2.
 // The file is split four ways (round 5): fshared_types.h (the storage structures), fshared_kernels.h (the device kernels), fshared_plan.hip (the orbit GEMM's plan, host only)
 // and this file: creation, stripes, symmetries, the launches of the products, the assembly by K^+ solves.
-#include "fshared_kernels.h"
+#include "fshared_adapted.h"
+#include "orbitbasis.h"
 
+extern char **environ;
 
 static int fxs_build_launch(fx_shared *S)
 {
@@ -289,6 +293,18 @@ int fxs_create(pmh_gluing B, pmh_blockdiag K, const int *block_class, int sym, f
   return PMH_SUCCESS;
 }
 
+static void fxa_free(pmh_ctx ctx, fxs_class &C)
+{
+  fxa_class *a = C.oa;
+  if (!a) return;
+  if (a->Wh) (void)hipFree(a->Wh);
+  for (void *q : {(void *)a->d_ir, (void *)a->d_tab, (void *)a->Xh, (void *)a->Yh, (void *)a->d_toff, (void *)a->d_osize, (void *)a->d_tbase, (void *)a->d_opos, (void *)a->d_rowinfo, (void *)a->d_items,
+                  (void *)a->d_tmask})
+    if (q) pmh_free(ctx, q);
+  delete a;
+  C.oa = nullptr;
+}
+
 void fxs_destroy(fx_shared *S)
 {
   if (!S) return;
@@ -302,6 +318,7 @@ void fxs_destroy(fx_shared *S)
     if (C.d_gidx) pmh_free(ctx, C.d_gidx), pmh_free(ctx, C.d_reppos), pmh_free(ctx, C.d_use);
     if (C.d_coltab) pmh_free(ctx, C.d_coltab), pmh_free(ctx, C.d_fintab), pmh_free(ctx, C.d_finbase);
     if (C.d_kinv) pmh_free(ctx, C.d_kinv), pmh_free(ctx, C.d_unittab), pmh_free(ctx, C.d_lut);
+    fxa_free(ctx, C);
   }
   if (S->pt) pmh_free(ctx, S->pt);
   if (S->d_wgl) pmh_free(ctx, S->d_wgl);
@@ -372,9 +389,44 @@ int fxs_set_stripe(fx_shared *S, int rank, int size)
 }
 
 long long fxs_dense_bytes(fx_shared *S) { return S->sym ? (long long)S->owned_bytes : (long long)sizeof(double) * S->wtot; }
-double    fxs_apply_flops(fx_shared *S) { return S->sym == 2 ? S->flops : 0.0; } // orbit storage: the GEMM's useful flops per apply
-void      fxs_apply_flops_detail(fx_shared *S, double *issued, double *dense) { *issued = S->sym == 2 ? S->flops_issued : 0.0, *dense = S->sym == 2 ? S->flops_dense : 0.0; }
-double    fxs_apply_bytes(fx_shared *S) { return S->bytes; }
+// orbit storage: every class with touched dofs applies W_c in the symmetry-adapted basis (set at the assembly) and the switch is on
+static bool fxa_active(fx_shared *S)
+{
+  if (S->sym != 2 || !pmh_knobs().orbit_adapted) return false;
+  bool any = false;
+  for (const fxs_class &C : S->C) {
+    if (!C.nc) continue;
+    if (!C.oa) return false;
+    any = true;
+  }
+  return any;
+}
+int fxs_orbit_adapted(fx_shared *S, int c) { return c >= 0 && c < S->ncls && S->C[c].oa && fxa_active(S); }
+// orbit storage: the GEMM's useful flops per apply; in the symmetry-adapted basis what the blocks' products and the two transforms need / execute
+double fxs_apply_flops(fx_shared *S)
+{
+  if (!fxa_active(S)) return S->sym == 2 ? S->flops : 0.0;
+  double f = 0.0;
+  for (const fxs_class &C : S->C)
+    if (C.oa) f += C.oa->flops;
+  return f;
+}
+void fxs_apply_flops_detail(fx_shared *S, double *issued, double *dense)
+{
+  *issued = S->sym == 2 ? S->flops_issued : 0.0, *dense = S->sym == 2 ? S->flops_dense : 0.0;
+  if (!fxa_active(S)) return;
+  *issued = 0.0;
+  for (const fxs_class &C : S->C)
+    if (C.oa) *issued += C.oa->flops_issued;
+}
+double fxs_apply_bytes(fx_shared *S)
+{
+  if (!fxa_active(S)) return S->bytes;
+  double b = 0.0;
+  for (const fxs_class &C : S->C)
+    if (C.oa) b += C.oa->bytes;
+  return b;
+}
 
 // the touched dofs of class c, ascending, relative to the block start (the numbering of W_c's rows)
 int fxs_class_union(fx_shared *S, int c, int *n_c, int *urel_out)
@@ -408,6 +460,8 @@ int fxs_set_symmetry(fx_shared *S, int c, int nsym, const int *posmap, const sig
     }
   }
   C.nsym = nsym;
+  C.h_ops.clear(); // (set-up by box symmetries hands them on afterwards: fxs_set_symmetry_ops)
+  fxa_free(S->ctx, C);
   C.h_posmap.assign(posmap, posmap + (size_t)nsym * nc);
   C.h_sign.assign(sign, sign + (size_t)nsym * nc);
   if (C.d_posmap) pmh_free(S->ctx, C.d_posmap), pmh_free(S->ctx, C.d_sign);
@@ -420,6 +474,13 @@ int fxs_set_symmetry(fx_shared *S, int c, int nsym, const int *posmap, const sig
   return PMH_SUCCESS;
 }
 
+
+int fxs_set_symmetry_ops(fx_shared *S, int c, int nsym, const int *ops)
+{
+  PMH_ARG(S && c >= 0 && c < S->ncls && ops && nsym == S->C[c].nsym);
+  S->C[c].h_ops.assign(ops, ops + 6 * (size_t)nsym);
+  return PMH_SUCCESS;
+}
 
 static int fxo_gemm(fx_shared *S)
 {
@@ -533,6 +594,254 @@ static int fxo_gemm(fx_shared *S)
     hipLaunchKernelGGL(k_fxo_fin_all, dim3((unsigned)S->fin_nbx, (unsigned)S->fin_ngroups, (unsigned)S->ncls), dim3(PMH_BLOCK), 0, st, (const fxo_fin_args *)S->d_fin_args, (const double *)S->cpart, S->Y);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
+}
+
+// X (position, slot) -> X2 (position, +-, slot): only for the dense kernel alone on a multivector handed in (pmh_fexplicit_dense_mult); the operator fills X2
+// by its own gluing
+__global__ __launch_bounds__(PMH_BLOCK) void k_fxo_signed_copy(long long n, int nslot, const double *__restrict__ X, double *__restrict__ X2)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const long long p = i / nslot, sl = i % nslot;
+    const double    v = X[i];
+    X2[2 * p * nslot + sl] = v, X2[(2 * p + 1) * nslot + sl] = -v;
+  }
+}
+
+// ---- orbit storage applied in the symmetry-adapted basis (kernels: fshared_adapted.h, basis: orbitbasis.hip) ---------------------------------------------------
+// forward transform, the ten blocks' products, inverse transform; the mid event (fxs_timing_get: first_kernel_ms) is recorded before the last launch
+static int fxa_launch(fx_shared *S)
+{
+  hipStream_t st = S->ctx->stream;
+  for (fxs_class &C : S->C)
+    if (fxa_class *a = C.oa)
+      hipLaunchKernelGGL(k_fxa_transform<false>, dim3(a->norb, (a->NC + FXA_CB - 1) / FXA_CB), dim3(PMH_BLOCK), 0, st, (const fxa_irrep *)a->d_ir, (const double *)a->d_tab, (const long long *)a->d_toff,
+                         (const int *)a->d_osize, (const int *)a->d_tbase, (const int *)a->d_opos, (const int *)a->d_rowinfo, a->NC, C.nc, C.ld, C.xoff, (const double *)S->X2, a->Xh, (const double *)a->Yh, S->Y,
+                         (const char *)a->d_tmask);
+  for (fxs_class &C : S->C)
+    if (fxa_class *a = C.oa)
+      if (a->nitems) hipLaunchKernelGGL(k_fxa_prod, dim3(a->nitems), dim3(64 * FXA_WAVES), 0, st, (const int *)a->d_items, (const fxa_irrep *)a->d_ir, (const double *)a->Wh, (const double *)a->Xh, a->Yh);
+  if (S->ev_mid_pending >= 0) PMH_HIP(hipEventRecord(S->ev_mid[S->ev_mid_pending], st));
+  for (fxs_class &C : S->C)
+    if (fxa_class *a = C.oa)
+      hipLaunchKernelGGL(k_fxa_transform<true>, dim3(a->norb, (a->NC + FXA_CB - 1) / FXA_CB), dim3(PMH_BLOCK), 0, st, (const fxa_irrep *)a->d_ir, (const double *)a->d_tab, (const long long *)a->d_toff,
+                         (const int *)a->d_osize, (const int *)a->d_tbase, (const int *)a->d_opos, (const int *)a->d_rowinfo, a->NC, C.nc, C.ld, C.xoff, (const double *)S->X2, a->Xh, (const double *)a->Yh, S->Y,
+                         (const char *)a->d_tmask);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+template <class T> static int fxa_upload(pmh_ctx ctx, const std::vector<T> &h, T **d)
+{
+  PMH_CHK(pmh_malloc(ctx, sizeof(T) * std::max<size_t>(1, h.size()), (void **)d));
+  if (!h.empty()) PMH_CHK(pmh_memcpy_h2d(ctx, *d, h.data(), sizeof(T) * h.size()));
+  return PMH_SUCCESS;
+}
+
+// the class's basis, its device tables and the blocks W^_i from the representatives' rows of A (after fxs_assemble has filled them); a class whose operations
+// give no such basis keeps the GEMM (C.oa stays null)
+static int fxa_build_class(fx_shared *S, fxs_class &C, bool spoil)
+{
+  pmh_ctx     ctx = S->ctx;
+  oab_basis   B;
+  std::string why;
+  if (!oab_build(C.nsym, C.nc, C.h_posmap.data(), C.h_sign.data(), C.h_ops.data(), B, why)) {
+    if (getenv("PMH_ORBIT_ADAPTED_VERBOSE")) fprintf(stderr, "orbit_adapted: no basis (%s): the class keeps the GEMM\n", why.c_str());
+    return PMH_SUCCESS;
+  }
+  if (B.norb != C.M_all) return PMH_SUCCESS;
+  for (int o = 0; o < B.norb; o++) // orbit o's representative is row reprow[o] of A (fxo_prepare numbers the orbits the same way)
+    if (B.opos[B.tbase[o]] != C.reps[o]) return PMH_SUCCESS;
+  fxa_class *a = new fxa_class();
+  C.oa = a;
+  a->norb = B.norb, a->NC = C.ngroups * FXS_S, a->nc = C.nc;
+  const int M = C.M_all;
+  long long wtot = 0, htot = 0, ytot = 0;
+  double    tfl = 0.0;
+  for (int o = 0; o < B.norb; o++) tfl += 2.0 * 2.0 * (double)B.osize[o] * B.osize[o] * a->NC;
+  a->flops = a->flops_issued = tfl;
+  for (int i = 0; i < OAB_NIRREP; i++) {
+    fxa_irrep &I = a->ir[i];
+    I.d = B.d[i], I.m = B.m[i];
+    I.nks = ((I.m + 7) / 8 + FXA_KU - 1) / FXA_KU * FXA_KU, I.nob = (I.m + 15) / 16, I.nbt = (I.d * a->NC + 15) / 16, I.ldy = 16 * I.nbt;
+    I.woff = wtot, I.hoff = htot, I.yoff = ytot;
+    wtot += (long long)I.nob * I.nks * 128, htot += (long long)I.nbt * I.nks * 128, ytot += (long long)I.nob * 16 * I.ldy;
+    a->flops += 2.0 * (double)I.m * I.m * I.d * a->NC;
+    a->flops_issued += 2.0 * (16.0 * I.nob) * (8.0 * I.nks) * (16.0 * I.nbt);
+  }
+  // the blocks once, X^ written and read, Y^ written and read, the tables twice, X read and Y written
+  a->bytes = 8.0 * ((double)wtot + 2.0 * htot + 2.0 * ytot + 2.0 * 48.0 * 48.0 * B.norb + 2.0 * (double)C.nc * a->NC);
+  {
+    const size_t bytes = sizeof(double) * (size_t)std::max(128LL, wtot);
+    hipError_t   e     = hipMalloc((void **)&a->Wh, bytes);
+    if (e != hipSuccess) return pmh_set_error(PMH_ERR_HIP, "PMH_FX_CLASS_ORBIT: %.2f GB for the blocks of the symmetry-adapted form: %s", bytes / 1e9, hipGetErrorString(e));
+    PMH_HIP(hipMemsetAsync(a->Wh, 0, bytes, ctx->stream));
+  }
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)std::max(128LL, htot), (void **)&a->Xh));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)std::max(128LL, ytot), (void **)&a->Yh));
+  PMH_CHK(pmh_memset(ctx, a->Xh, 0, sizeof(double) * (size_t)std::max(128LL, htot))); // rows past m and columns past D stay zero
+  PMH_CHK(pmh_memset(ctx, a->Yh, 0, sizeof(double) * (size_t)std::max(128LL, ytot)));
+  std::vector<int> rowinfo((size_t)C.nc), orb_of((size_t)C.nc), items;
+  for (int o = 0; o < B.norb; o++)
+    for (int t = 0; t < B.osize[o]; t++) orb_of[B.tbase[o] + t] = o;
+  for (int r = 0; r < C.nc; r++) rowinfo[r] = B.row_irrep[r] | (B.row_partner[r] << 4) | (B.row_index[r] << 8);
+  { // the longest irreps first
+    int order[OAB_NIRREP];
+    for (int i = 0; i < OAB_NIRREP; i++) order[i] = i;
+    std::stable_sort(order, order + OAB_NIRREP, [&](int x, int y) { return a->ir[x].m > a->ir[y].m; });
+    for (int i : order) {
+      const fxa_irrep &I = a->ir[i];
+      for (int nb0 = 0; nb0 < I.nbt; nb0 += 4)
+        for (int ob = 0; ob < I.nob; ob++) items.insert(items.end(), {i, ob, nb0, std::min(4, I.nbt - nb0)});
+    }
+    a->nitems = (int)(items.size() / 4);
+  }
+  std::vector<fxa_irrep> irv(a->ir, a->ir + OAB_NIRREP);
+  std::vector<char>      tmask(C.tmask.begin(), C.tmask.end());
+  PMH_CHK(fxa_upload(ctx, irv, &a->d_ir));
+  std::vector<double>    tabp((size_t)B.norb * 48 * 48, 0.0); // every table as 48 x 48
+  std::vector<long long> toffp((size_t)B.norb);
+  for (int o = 0; o < B.norb; o++) {
+    toffp[o] = (long long)o * 48 * 48;
+    for (int t = 0; t < B.osize[o]; t++)
+      for (int j = 0; j < B.osize[o]; j++) tabp[(size_t)toffp[o] + t * 48 + j] = B.tab[(size_t)B.toff[o] + (size_t)t * B.osize[o] + j];
+  }
+  PMH_CHK(fxa_upload(ctx, tabp, &a->d_tab));
+  PMH_CHK(fxa_upload(ctx, toffp, &a->d_toff));
+  PMH_CHK(fxa_upload(ctx, B.osize, &a->d_osize));
+  PMH_CHK(fxa_upload(ctx, B.tbase, &a->d_tbase));
+  PMH_CHK(fxa_upload(ctx, B.opos, &a->d_opos));
+  PMH_CHK(fxa_upload(ctx, rowinfo, &a->d_rowinfo));
+  PMH_CHK(fxa_upload(ctx, items, &a->d_items));
+  PMH_CHK(fxa_upload(ctx, tmask, &a->d_tmask));
+  // the blocks: the forward transform of the representatives' rows, then the d-term combination per entry
+  double *Abuf = nullptr;
+  int    *d_reprow = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)C.nc * M, (void **)&Abuf));
+  PMH_CHK(fxa_upload(ctx, C.reprow, &d_reprow));
+  { // step 0: the rows of representatives with a stabiliser, averaged over it
+    std::vector<int> hops;
+    int             *d_hops = nullptr;
+    double          *tmp = nullptr;
+    PMH_CHK(pmh_malloc(ctx, sizeof(int) * OAB_NOP, (void **)&d_hops));
+    PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)C.nc, (void **)&tmp));
+    const int nbx = std::max(1, std::min(64, (C.nc + PMH_BLOCK - 1) / PMH_BLOCK));
+    for (int o = 0; o < B.norb; o++) {
+      if (B.osize[o] == OAB_NOP) continue;
+      const int p = C.reps[o];
+      hops.clear();
+      for (int g = 0; g < OAB_NOP; g++)
+        if (C.h_posmap[(size_t)g * C.nc + p] == p) hops.push_back(g);
+      PMH_CHK(pmh_memcpy_h2d(ctx, d_hops, hops.data(), sizeof(int) * hops.size())); // (synchronous: the buffer is free again)
+      hipLaunchKernelGGL(k_fxa_stab_avg, dim3(nbx), dim3(PMH_BLOCK), 0, ctx->stream, (int)hops.size(), (const int *)d_hops, p, C.reprow[o], C.tm, C.nc, C.nkc, (const int *)C.d_posmap, (const signed char *)C.d_sign,
+                         (const int *)C.d_kinv, (const double *)(S->Afund + C.aoff), tmp);
+      hipLaunchKernelGGL(k_fxa_stab_store, dim3(nbx), dim3(PMH_BLOCK), 0, ctx->stream, C.reprow[o], C.tm, C.nc, C.nkc, (const int *)C.d_kinv, (const double *)tmp, S->Afund + C.aoff);
+      PMH_CHK(pmh_sync(ctx));
+    }
+    pmh_free(ctx, d_hops), pmh_free(ctx, tmp);
+  }
+  hipLaunchKernelGGL(k_fxa_rows, dim3(B.norb, (M + 63) / 64), dim3(64), 0, ctx->stream, M, C.tm, C.nkc, (const double *)a->d_tab, (const long long *)a->d_toff, (const int *)a->d_osize, (const int *)a->d_tbase,
+                     (const int *)a->d_opos, (const int *)C.d_kinv, (const int *)d_reprow, (const double *)(S->Afund + C.aoff), Abuf);
+  int rc = PMH_SUCCESS;
+  for (int i = 0; i < OAB_NIRREP && !rc; i++) {
+    const fxa_irrep &I = a->ir[i];
+    if (!I.m) continue;
+    std::vector<int>    fn0((size_t)I.m), orb((size_t)I.m);
+    std::vector<double> vs(3 * (size_t)I.m);
+    for (int r = 0; r < C.nc; r++)
+      if (B.row_irrep[r] == i && B.row_partner[r] == 0) {
+        const int k = B.row_index[r], o = orb_of[r];
+        fn0[k] = r, orb[k] = o;
+        for (int b = 0; b < 3; b++) vs[3 * (size_t)k + b] = B.row_vs[3 * (size_t)r + b];
+      }
+    int    *d_fn0 = nullptr, *d_orb = nullptr;
+    double *d_vs = nullptr;
+    if ((rc = fxa_upload(ctx, fn0, &d_fn0)) || (rc = fxa_upload(ctx, orb, &d_orb)) || (rc = fxa_upload(ctx, vs, &d_vs))) break;
+    hipLaunchKernelGGL(k_fxa_combine, dim3((unsigned)(((long long)I.m * I.m + PMH_BLOCK - 1) / PMH_BLOCK)), dim3(PMH_BLOCK), 0, ctx->stream, I, M, (const int *)d_fn0, (const int *)d_orb, (const double *)d_vs,
+                       (const double *)Abuf, a->Wh);
+    rc = pmh_sync(ctx);
+    pmh_free(ctx, d_fn0), pmh_free(ctx, d_orb), pmh_free(ctx, d_vs);
+  }
+  if (!rc) rc = pmh_sync(ctx);
+  pmh_free(ctx, Abuf), pmh_free(ctx, d_reprow);
+  if (!rc && hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "PMH_FX_CLASS_ORBIT: a set-up launch of the symmetry-adapted form failed");
+  if (!rc && spoil) { // tests: the transforms get a table whose first row is negated in every orbit -- no longer the basis the blocks were built in
+    std::vector<double> bad = tabp;
+    for (int o = 0; o < B.norb; o++)
+      for (int j = 0; j < B.osize[o]; j++) bad[(size_t)toffp[o] + j] = -bad[(size_t)toffp[o] + j];
+    rc = pmh_memcpy_h2d(ctx, a->d_tab, bad.data(), sizeof(double) * bad.size());
+  }
+  return rc;
+}
+
+// After the assembly: every eligible class gets its symmetry-adapted form, then ONE random multivector goes through both that form and the GEMM -- a blunder detector:
+// a wrong basis is wrong by O(1), rounding is 1e-15, the bound of 1e-10 sits five orders from either.  A class that misses it stays on the GEMM (counter
+// orbit_adapted_fallbacks).  One rank only (the several-rank k-range split keeps the GEMM); any PMH_FXO_* switch steers the GEMM, so it selects the GEMM.
+static int fxa_setup(fx_shared *S)
+{
+  pmh_ctx ctx = S->ctx;
+  for (fxs_class &C : S->C) fxa_free(ctx, C);
+  if (!pmh_knobs().orbit_adapted || S->stripe_size > 1 || ctx->size > 1) return PMH_SUCCESS;
+  for (char **e = environ; e && *e; e++)
+    if (!strncmp(*e, "PMH_FXO_", 8)) return PMH_SUCCESS;
+  const bool spoil = pmh_knobs().orbit_adapted_spoil != 0;
+  pmh_knobs().orbit_adapted_spoil = 0;
+  bool any = false;
+  for (fxs_class &C : S->C) {
+    if (!C.nc) continue;
+    // (records of fewer than 8 slots -- classes of fewer than 8 blocks -- keep the GEMM)
+    if (C.S != FXS_S || C.nsym != OAB_NOP || C.h_ops.size() != 6 * (size_t)OAB_NOP || C.m0 != 0 || C.m1 != C.M_all || C.tmask.empty()) {
+      if (getenv("PMH_ORBIT_ADAPTED_VERBOSE")) fprintf(stderr, "orbit_adapted: not eligible (slots %d, operations %d, box operations known %d): the class keeps the GEMM\n", C.S, C.nsym, (int)(C.h_ops.size() / 6));
+      continue;
+    }
+    const int rc = fxa_build_class(S, C, spoil);
+    if (rc) {
+      fxa_free(ctx, C);
+      return rc;
+    }
+    any = any || C.oa;
+  }
+  if (!any) return PMH_SUCCESS;
+  std::vector<double> x((size_t)S->nX, 0.0), y0((size_t)S->nX), y1((size_t)S->nX);
+  unsigned long long  seed = 0x9E3779B97F4A7C15ULL;
+  for (fxs_class &C : S->C) {
+    if (!C.oa) continue;
+    for (int g = 0; g < C.ngroups; g++)
+      for (int p = 0; p < C.nc; p++)
+        for (int sl = 0; sl < FXS_S; sl++)
+          if (C.tmask[((size_t)g * C.nc + p) * FXS_S + sl]) {
+            seed = seed * 6364136223846793005ULL + 1442695040888963407ULL;
+            x[(size_t)(C.xoff + (long long)g * C.ld * FXS_S + (long long)p * FXS_S + sl)] = (double)(seed >> 11) / 4503599627370496.0 - 1.0;
+          }
+  }
+  PMH_CHK(pmh_memcpy_h2d(ctx, S->X, x.data(), sizeof(double) * x.size()));
+  for (const fxs_class &C : S->C) {
+    const long long n = (long long)C.ngroups * C.ld * C.S;
+    if (!n) continue;
+    hipLaunchKernelGGL(k_fxo_signed_copy, dim3((unsigned)std::min<long long>(4096, (n + PMH_BLOCK - 1) / PMH_BLOCK)), dim3(PMH_BLOCK), 0, ctx->stream, n, C.S, (const double *)(S->X + C.xoff), S->X2 + 2 * C.xoff);
+  }
+  PMH_CHK(fxo_gemm(S));
+  PMH_CHK(pmh_memcpy_d2h(ctx, y0.data(), S->Y, sizeof(double) * y0.size()));
+  PMH_CHK(pmh_memset(ctx, S->Y, 0, sizeof(double) * (size_t)S->nX));
+  PMH_CHK(fxa_launch(S));
+  PMH_CHK(pmh_memcpy_d2h(ctx, y1.data(), S->Y, sizeof(double) * y1.size()));
+  for (fxs_class &C : S->C) {
+    if (!C.oa) continue;
+    double dd = 0.0, nn = 0.0;
+    for (int g = 0; g < C.ngroups; g++) // where some block reads Y (the GEMM's finishing kernel also writes entries of its column lists that nobody reads)
+      for (long long k = 0; k < (long long)C.nc * FXS_S; k++)
+        if (C.tmask[(size_t)g * C.nc * FXS_S + (size_t)k]) {
+          const size_t i = (size_t)(C.xoff + (long long)g * C.ld * FXS_S + k);
+          dd += (y1[i] - y0[i]) * (y1[i] - y0[i]), nn += y0[i] * y0[i];
+        }
+    if (getenv("PMH_ORBIT_ADAPTED_VERBOSE")) fprintf(stderr, "orbit_adapted: self-check against the GEMM: normwise relative difference %.3e (n_c = %d, %d groups)\n", std::sqrt(dd / nn), C.nc, C.ngroups);
+    if (!(dd <= 1e-20 * nn)) fxa_free(ctx, C), pmh_knobs().orbit_adapted_fallbacks++;
+    else pmh_knobs().orbit_adapted_classes++;
+  }
+  // the multivectors as the operator expects them: zero wherever its own gluing does not write
+  PMH_CHK(pmh_memset(ctx, S->X, 0, sizeof(double) * (size_t)S->nX));
+  PMH_CHK(pmh_memset(ctx, S->X2, 0, sizeof(double) * 2 * (size_t)S->nX));
+  PMH_CHK(pmh_memset(ctx, S->Y, 0, sizeof(double) * (size_t)S->nX));
+  return pmh_sync(ctx);
 }
 
 int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_class, double rtol, int max_it, long long *n_solves, fx_batch_window *w)
@@ -716,6 +1025,7 @@ int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_cl
   pmh_matinv_set_tolerances(solver, old_rtol, old_atol, old_maxit);
   pmh_free(ctx, rhs), pmh_free(ctx, sol), pmh_free(ctx, d_idx);
   (void)hipHostFree(h_idx);
+  if (!rc && last && S->sym == 2) rc = fxa_setup(S);
   return rc;
 }
 
@@ -729,7 +1039,8 @@ static int fxs_gemm(fx_shared *S)
   const long long stride = std::max(16LL, S->nX);
   if (S->sym == 2) {
     S->ev_mid_pending = timed ? S->ev_used : -1;
-    PMH_CHK(fxo_gemm(S));
+    if (fxa_active(S)) PMH_CHK(fxa_launch(S));
+    else PMH_CHK(fxo_gemm(S));
     S->ev_mid_pending = -1;
   } else if (S->sym) {
     hipLaunchKernelGGL(k_fxs_symm8, dim3(S->nwg), dim3(FXM_THREADS), 0, st, (const int *)S->d_wg, (const int *)S->d_items, (const long long *)S->d_wgl, (const int *)S->d_ld, (const long long *)S->d_xoff,
@@ -748,17 +1059,6 @@ static int fxs_gemm(fx_shared *S)
   }
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
-}
-
-// X (position, slot) -> X2 (position, +-, slot): only for the dense kernel alone on a multivector handed in (pmh_fexplicit_dense_mult); the operator fills X2
-// by its own gluing
-__global__ __launch_bounds__(PMH_BLOCK) void k_fxo_signed_copy(long long n, int nslot, const double *__restrict__ X, double *__restrict__ X2)
-{
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
-    const long long p = i / nslot, sl = i % nslot;
-    const double    v = X[i];
-    X2[2 * p * nslot + sl] = v, X2[(2 * p + 1) * nslot + sl] = -v;
-  }
 }
 
 int fxs_apply(fx_shared *S, const double *lambda, double *y)

@@ -15,7 +15,27 @@ typedef double dbl2 __attribute__((ext_vector_type(2)));
 #define FXS_S 8    // right-hand sides per pass (blocks per group)
 #define FXS_PAD 128
 
+// Orbit storage applied in the symmetry-adapted basis (fshared_adapted.h): per irrep i the block W^_i (m x m), the transformed multivector X^_i and the
+// product Y^_i = W^_i X^_i (m x D, D = d * 8 * groups columns: partner, group, slot), in the operand layouts of v_mfma_f64_16x16x4_f64
+struct fxa_irrep {
+  int       d, m, nks, nob, nbt, ldy; // k steps of 8 (whole unrolls), blocks of 16 output rows, blocks of 16 columns, row length of Y^_i
+  long long woff, hoff, yoff;         // offsets in Wh / Xh / Yh
+};
+struct fxa_class {
+  int        norb = 0, NC = 0, nitems = 0, nc = 0;
+  fxa_irrep  ir[10];
+  fxa_irrep *d_ir = nullptr;
+  double    *d_tab = nullptr, *Wh = nullptr, *Xh = nullptr, *Yh = nullptr;
+  long long *d_toff = nullptr;
+  int       *d_osize = nullptr, *d_tbase = nullptr, *d_opos = nullptr, *d_rowinfo = nullptr, *d_items = nullptr;
+  char      *d_tmask = nullptr;
+  double     flops = 0.0, flops_issued = 0.0, bytes = 0.0;
+};
+
 struct fxs_class {
+  // orbit storage in the symmetry-adapted basis: the box operations behind the symmetries (fxs_set_symmetry_ops), the device data once the class took that form
+  std::vector<int> h_ops;
+  fxa_class       *oa = nullptr;
   std::vector<int> blocks; // blocks of the class, ascending: slot = index % 8, group = index / 8
   std::vector<int> urel;   // sorted union of the touched dofs, relative to the block start
   std::vector<int> pos;    // relative dof -> position in urel (-1)

@@ -31,6 +31,9 @@ struct pmh_knobs_s {
   int gt_fusion = 1;       // PMH_NO_GT_FUSION: the projector's v - G'(...) epilogue folded into the G' kernel (qppf.hip)
   int smalxe_prefetch = 1; // PMH_SMALXE_NO_PREFETCH: ||B u|| enqueued before the inner solver's host wait (smalxe.hip)
   int vec_epi = 1;         // PMH_NO_VEC_EPI: MPGP's vector phase in the operator's last kernel (mpgp.hip, qppf.hip)
+  // PMH_NO_ORBIT_ADAPTED: orbit storage applied in the cube group's symmetry-adapted basis (fshared_adapted.h) instead of by the orbit GEMM; the counters of classes
+  // that took it / that failed the set-up's self-check and stayed on the GEMM; spoil (tests): the next assembly negates one table row
+  int orbit_adapted = 1, orbit_adapted_classes = 0, orbit_adapted_fallbacks = 0, orbit_adapted_spoil = 0;
   int mpgp_spec = 1;       // PMH_MPGP_NO_SPEC: batches of device-side CG steps for CSR operators (mpgp.hip)
   int mg_d0_fusion = 1;    // PMH_MG_NO_D0_FUSION: the first smoothing step written by the producer of the right-hand side (feti.hip)
   int kplus_mv = 1;        // PMH_NO_KPLUS_MV: pmh_matinv_mult on 8 congruent blocks runs them as the 8 columns of one block on the multi-right-hand-side kernels (feti.hip)

@@ -308,6 +308,25 @@ def box_symmetry_closure(dims, ndof, K, rel):
     return out[:n_out.value].copy(), nsym.value
 
 
+def orbit_basis(dims, ndof, rel):
+    """pmh_orbit_basis (host only): the symmetry-adapted basis of the block-relative dofs `rel` (ascending, closed under the cube's 48 operations) of a box of dims nodes x ndof.
+    Returns a dict: mult, dim [10] (irreps A1g A2g Eg T1g T2g A1u A2u Eu T1u T2u), orb_size [orbits], and per basis function (numbered orbit after orbit; an orbit owns as
+    many functions as positions, in the same running order) orb_pos, irrep, index (row of the function's copy in the irrep's block), partner, v [n, 3], table [n, 48]
+    (the function's values on its orbit's positions)."""
+    from . import _lib
+
+    dm = np.ascontiguousarray(dims, dtype=np.int32)
+    rel = np.ascontiguousarray(rel, dtype=np.int32)
+    n = int(rel.size)
+    norb = C.c_int()
+    mult, dim = np.zeros(10, dtype=np.int32), np.zeros(10, dtype=np.int32)
+    ints = [np.zeros(n, dtype=np.int32) for _ in range(5)]
+    v, tab = np.zeros((n, 3)), np.zeros((n, 48))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check(_lib.load().pmh_orbit_basis(p(dm), int(ndof), n, p(rel), C.byref(norb), p(mult), p(dim), *[p(a) for a in ints], p(v), p(tab)))
+    return dict(mult=mult, dim=dim, orb_size=ints[0][:norb.value].copy(), orb_pos=ints[1], irrep=ints[2], index=ints[3], partner=ints[4], v=v, table=tab)
+
+
 class MatExplicitDual:
     """Explicit local dual operators (pmh_fexplicit): W_b = (K_b^+)[Gamma_b, Gamma_b] dense per block, F = Bhat W Bhat'.
     The exact-K^+ path (MatInvExplicitly_Inv, src/mat/impls/inv/matinv.c:670-730, restricted to the dofs B touches)."""
@@ -386,6 +405,13 @@ class MatExplicitDual:
         check(self.ctx.L.pmh_fexplicit_set_box_symmetry(self.h, int(cls), d.ctypes.data_as(C.c_void_p), int(ndof), ip.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
                                                          va.ctypes.data_as(C.c_void_p), C.byref(n)))
         return n.value
+
+    def orbit_adapted(self, cls=0):
+        """"class_orbit", after the assembly: whether class `cls` applies W_c in the cube group's symmetry-adapted basis (48 operations, one rank, knob "orbit_adapted")
+        rather than by the orbit GEMM."""
+        a = C.c_int()
+        check(self.ctx.L.pmh_fexplicit_orbit_adapted(self.h, int(cls), C.byref(a)))
+        return bool(a.value)
 
     def refresh_sizes(self):
         """dense_bytes / gemv_bytes after the plan changed (stripe, symmetries, assembly)."""
