@@ -1018,6 +1018,21 @@ int pmh_bsr3_test_create(pmh_csr A, int storage, int tile, int nrep_hint, void *
 int pmh_bsr3_test_info(void *B, long long info[8], double *scale);
 int pmh_bsr3_test_mult_epi(void *B, int epi, const void *x, void *y, const void *y1, const void *dinv, void *r, void *d, double *z64, double c0, double c1, double c2, int halt);
 int pmh_bsr3_test_destroy(void *B);
+/* ---- orbit GEMM test entries (csrc/fshared.hip: the plan as the assembly makes it and the launches of the apply; nothing inside the kernels, the plan or the solvers
+ * changes) ----
+ * pmh_fexplicit_test_load_class: PMH_FX_CLASS_ORBIT, after the symmetries of every class with touched dofs are set: plans the GEMM (as the assembly does) and stores
+ * the rows of class cls's orbit representatives from the HOST matrix W_host (n_c x n_c, row-major, in the numbering of pmh_fexplicit_class_union) -- any matrix that
+ * is invariant under the class's signed permutations; no K^+ solve, no symmetry-adapted form (callers keep the knob orbit_adapted at 0).  Once every class with touched
+ * dofs is loaded the operator counts as assembled: pmh_fexplicit_dense_mult, _mult and _get_block work as after pmh_fexplicit_assemble.  PMH_ERR_ARG for another
+ * storage or a class out of range, PMH_ERR_STATE where a class with touched dofs has no symmetries.
+ * pmh_fexplicit_orbit_plan_info: what the plan decided for class cls and what the apply launches, info = {0 n_c, 1 ld, 2 slots per multivector record, 3 groups,
+ * 4 offset of the class in the multivector numbering (entry: offset + group ld slots + position slots + slot), 5 operations, 6 padded operations, 7 representatives M,
+ * 8 row tile, 9 padded rows, 10 row tiles, 11 column tile TN (128 / 64), 12 TNW (48: the 48-column kernel of one-block classes, else 0), 13 k segments, 14 chunks of
+ * 16 k positions, 15 units (group, row tile, segment), 16 units with chunks on this rank, 17 largest split count of a unit, 18 workgroups, 19 workgroups with two or
+ * more items, 20 launch: 0 the single-class kernel, 1 a table-driven launch per class, 2 one merged table-driven launch over all classes, 21 finishing: 0 k_fxo_fin per
+ * class, 1 k_fxo_fin_all, 22 / 23 this rank's range of the representatives}.  PMH_ERR_STATE before there is a plan. */
+int pmh_fexplicit_test_load_class(pmh_fexplicit E, int cls, const double *W_host);
+int pmh_fexplicit_orbit_plan_info(pmh_fexplicit E, int cls, long long info[24]);
 /* U = K^+ F for 8 columns per block at once: F, U device arrays of 8 n doubles, entry (dof i, column r) at i * 8 + r; K, the V-cycle (pmh_matinv_set_pc_mg), the kernel
  * basis (pmh_matinv_set_nullspace: K^+ = P_R K^- P_R) and the tolerances are the solver's own; every (block, column) pair converges by its own test.  PMH_ERR_SUP where
  * the multi-right-hand-side kernels do not apply (K without regular 3 x 3 blocks, a V-cycle other than the fused fp32 one, the left generalised inverse). */

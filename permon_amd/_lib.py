@@ -400,6 +400,8 @@ _PROTOS = {
     "pmh_fexplicit_mult": [vp, vp, vp],
     "pmh_fexplicit_compressed_size": [vp, c_int_p, vp],
     "pmh_fexplicit_dense_mult": [vp, vp, vp],
+    "pmh_fexplicit_test_load_class": [vp, C.c_int, vp],
+    "pmh_fexplicit_orbit_plan_info": [vp, C.c_int, vp],
     "pmh_fexplicit_timing_enable": [vp, C.c_int, C.c_int],
     "pmh_fexplicit_timing_get": [vp, c_int_p, c_double_p, c_double_p],
     "pmh_matinv_attach_explicit": [vp, vp],

@@ -937,6 +937,24 @@ extern "C" int pmh_fexplicit_fill_pattern(pmh_fexplicit E, int byte)
   return pmh_sync(E->ctx);
 }
 
+// ---- orbit storage: test entries (fshared.hip; nothing inside the kernels, the plan or the solvers changes) -----------------------------------------------------
+extern "C" int pmh_fexplicit_test_load_class(pmh_fexplicit E, int cls, const double *W_host)
+{
+  PMH_ARG(E && W_host);
+  if (!E->sh || E->storage != PMH_FX_CLASS_ORBIT) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_load_class: needs the PMH_FX_CLASS_ORBIT storage");
+  int all = 0;
+  PMH_CHK(fxs_test_load_class(E->sh, cls, W_host, &all));
+  if (all) E->assembled = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_fexplicit_orbit_plan_info(pmh_fexplicit E, int cls, long long info[24])
+{
+  PMH_ARG(E && info);
+  if (!E->sh || E->storage != PMH_FX_CLASS_ORBIT) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_orbit_plan_info: needs the PMH_FX_CLASS_ORBIT storage");
+  return fxs_orbit_plan_info(E->sh, cls, info);
+}
+
 int pmh_fexplicit_set_window(pmh_fexplicit_s *E, fx_batch_window *w)
 {
   PMH_ARG(E);

@@ -248,6 +248,10 @@ int fxs_create(pmh_gluing B, pmh_blockdiag K, const int *block_class, int sym, f
       fxs_class &C = S->C[S->cls[b]];
       C.tmask[((size_t)group[b] * C.nc + C.pos[B->h_row[i] - K->rowstart[b]]) * FXS_S + slot[b]] = 1;
     }
+    for (auto &C : S->C) {
+      PMH_CHK(pmh_malloc(ctx, C.tmask.size(), (void **)&C.d_tmask));
+      PMH_CHK(pmh_memcpy_h2d(ctx, C.d_tmask, C.tmask.data(), C.tmask.size()));
+    }
   }
   PMH_CHK(pmh_gluing_create(ctx, (int)std::max(1LL, xtot), B->n_lambda, B->n_leaves, rows.data(), B->h_root.data(), B->h_sign.data(), &S->Bc));
   if (sym == 2) {
@@ -311,6 +315,7 @@ void fxs_destroy(fx_shared *S)
   pmh_ctx ctx = S->ctx;
   for (auto &C : S->C) {
     if (C.d_urel) pmh_free(ctx, C.d_urel);
+    if (C.d_tmask) pmh_free(ctx, C.d_tmask);
     if (C.d_nseg) pmh_free(ctx, C.d_nseg);
     if (C.d_ptoff) pmh_free(ctx, C.d_ptoff);
     if (C.d_ownfirst) pmh_free(ctx, C.d_ownfirst);
@@ -482,6 +487,18 @@ int fxs_set_symmetry_ops(fx_shared *S, int c, int nsym, const int *ops)
   return PMH_SUCCESS;
 }
 
+// The k_fxo_gemm16 instantiation of a row tile tm, a column tile tn (128 / 64) and tnw (48: one-block classes): 1000 + tm for the single-class kernel (tn = 128), tm + 1 for
+// tn = 64 and one more for tnw = 48 on the table-driven (MULTI) kernels; 0: no such kernel.  The launches below and pmh_fexplicit_orbit_plan_info go by it.
+static int fxo_instance(int tm, int tn, int tnw, bool tables)
+{
+  if (tnw == 48) return tables && tn == 64 && (tm == 192 || tm == 128 || tm == 64) ? tm + 2 : 0;
+  if (tm != 144 && tm != 128 && tm != 112 && tm != 96 && tm != 80) return 0;
+  if (!tables) return tn == 128 ? 1000 + tm : 0;
+  return tn == 64 ? tm + 1 : (tn == 128 ? tm : 0);
+}
+// how class c is launched: 2 in the ONE launch over all classes' items (merged), 1 by a table-driven launch of its own (records of fewer than 8 slots), 0 by the single-class kernel
+static int fxo_launch_kind(const fx_shared *S, const fxs_class &C) { return S->merged_tm > 0 && S->nwg_all > 0 ? 2 : (C.S != FXS_S ? 1 : 0); }
+
 static int fxo_gemm(fx_shared *S)
 {
   hipStream_t st = S->ctx->stream;
@@ -492,7 +509,7 @@ static int fxo_gemm(fx_shared *S)
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fxo_gemm16<NI, NWM, true, TNW>), dim3(S->nwg_all), dim3(256), 0, st, (const int *)S->d_items, (const long long *)S->d_wgl, (const int *)S->d_wg,                 \
                      (const int *)(S->d_wg + S->ncls), (const int *)nullptr, 0, (const double *)S->Afund, (const int *)nullptr, (const double *)S->X2, S->cpart, (const int *)S->d_wgfirst_all, \
                      (const int *const *)S->d_coltab_of, (const int *)S->d_zrow_of, (const int *const *)S->d_gidx_of, (const int *)(S->d_zrow_of + S->ncls))
-    switch (S->merged_tm + (S->merged_tn == 64 ? 1 : 0) + (S->merged_tnw == 48 ? 1 : 0)) {
+    switch (fxo_instance(S->merged_tm, S->merged_tn, S->merged_tnw, true)) {
     case 194: FXO_LAUNCH_ALL(3, 4, 48); break;
     case 130: FXO_LAUNCH_ALL(2, 4, 48); break;
     case 66: FXO_LAUNCH_ALL(1, 4, 48); break;
@@ -530,12 +547,12 @@ static int fxo_gemm(fx_shared *S)
 #endif
     if (merged) {
       // (the class's products were part of the launch above)
-    } else if (C.S != FXS_S) { // records of fewer than 8 slots: the table-driven kernel on this class's slice of the items
+    } else if (fxo_launch_kind(S, C) == 1) { // records of fewer than 8 slots: the table-driven kernel on this class's slice of the items
 #define FXO_LAUNCH_T(NI, NWM, TNW)                                                                                                                                                                             \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fxo_gemm16<NI, NWM, true, TNW>), dim3(count), dim3(256), 0, st, (const int *)(S->d_items + 8 * first), (const long long *)(S->d_wgl + 4 * first), (const int *)S->d_wg, \
                      (const int *)(S->d_wg + S->ncls), (const int *)nullptr, 0, (const double *)S->Afund, (const int *)nullptr, (const double *)S->X2, S->cpart, (const int *)(S->d_wgfirst + C.wgf_first),     \
                      (const int *const *)S->d_coltab_of, (const int *)S->d_zrow_of, (const int *const *)S->d_gidx_of, (const int *)(S->d_zrow_of + S->ncls))
-      switch (C.tm + (C.tn == 64 ? 1 : 0) + (C.tnw == 48 ? 1 : 0)) {
+      switch (fxo_instance(C.tm, C.tn, C.tnw, true)) {
       case 194: FXO_LAUNCH_T(3, 4, 48); break;
       case 130: FXO_LAUNCH_T(2, 4, 48); break;
       case 66: FXO_LAUNCH_T(1, 4, 48); break;
@@ -553,12 +570,12 @@ static int fxo_gemm(fx_shared *S)
       }
 #undef FXO_LAUNCH_T
     } else {
-      switch (C.tm) {
-      case 144: FXO_LAUNCH((k_fxo_gemm16<9, 1>)); break;
-      case 128: FXO_LAUNCH((k_fxo_gemm16<4, 2>)); break;
-      case 112: FXO_LAUNCH((k_fxo_gemm16<7, 1>)); break;
-      case 96: FXO_LAUNCH((k_fxo_gemm16<3, 2>)); break;
-      case 80: FXO_LAUNCH((k_fxo_gemm16<5, 1>)); break;
+      switch (fxo_instance(C.tm, C.tn, C.tnw, false)) {
+      case 1144: FXO_LAUNCH((k_fxo_gemm16<9, 1>)); break;
+      case 1128: FXO_LAUNCH((k_fxo_gemm16<4, 2>)); break;
+      case 1112: FXO_LAUNCH((k_fxo_gemm16<7, 1>)); break;
+      case 1096: FXO_LAUNCH((k_fxo_gemm16<3, 2>)); break;
+      case 1080: FXO_LAUNCH((k_fxo_gemm16<5, 1>)); break;
       default: return pmh_set_error(PMH_ERR_STATE, "PMH_FX_CLASS_ORBIT: row tile %d has no 16x16x4 kernel", C.tm);
       }
     }
@@ -588,7 +605,7 @@ static int fxo_gemm(fx_shared *S)
     if (C.fin_elems > 0 && !S->d_fin_args)
       hipLaunchKernelGGL(k_fxo_fin, dim3((unsigned)((C.fin_elems + PMH_BLOCK - 1) / PMH_BLOCK), C.ngroups), dim3(PMH_BLOCK), 0, st, C.Mp / C.tm, C.tm, C.nsymp, C.nc, (const int *)C.d_fintab,
                          (const int *)C.d_unittab, (const long long *)C.d_finbase, (const int *)C.d_lut, (const int *)C.d_coltab, (const double *)S->cpart, (const signed char *)C.d_use, (const int *)C.d_reppos, (const int *)C.d_posmap, C.xoff, C.ld,
-                         S->Y, C.S);
+                         S->Y, C.S, (const char *)C.d_tmask);
   }
   if (S->d_fin_args && S->fin_nbx > 0) // after ALL classes' products
     hipLaunchKernelGGL(k_fxo_fin_all, dim3((unsigned)S->fin_nbx, (unsigned)S->fin_ngroups, (unsigned)S->ncls), dim3(PMH_BLOCK), 0, st, (const fxo_fin_args *)S->d_fin_args, (const double *)S->cpart, S->Y);
@@ -827,7 +844,7 @@ static int fxa_setup(fx_shared *S)
   for (fxs_class &C : S->C) {
     if (!C.oa) continue;
     double dd = 0.0, nn = 0.0;
-    for (int g = 0; g < C.ngroups; g++) // where some block reads Y (the GEMM's finishing kernel also writes entries of its column lists that nobody reads)
+    for (int g = 0; g < C.ngroups; g++) // where some block reads Y (both forms leave every other entry zero)
       for (long long k = 0; k < (long long)C.nc * FXS_S; k++)
         if (C.tmask[(size_t)g * C.nc * FXS_S + (size_t)k]) {
           const size_t i = (size_t)(C.xoff + (long long)g * C.ld * FXS_S + k);
@@ -1148,6 +1165,63 @@ int fxs_get_block(fx_shared *S, int b, int n, const int *gamma, double *out_host
     PMH_HIP(hipMemcpy(row.data(), S->Wbase + C.woff + (long long)p * C.ld, sizeof(double) * (size_t)C.ld, hipMemcpyDeviceToHost));
     for (int k = 0; k < n; k++) out_host[(size_t)i * n + k] = row[C.pos[gamma[k] - S->K->rowstart[b]]];
   }
+  return PMH_SUCCESS;
+}
+
+// ---- orbit storage: test entries (pmh_fexplicit_test_load_class / pmh_fexplicit_orbit_plan_info) ---------------------------------------------------------------
+// The representatives' rows of class c from a HOST matrix W (n_c x n_c, row-major, in the numbering of fxs_class_union) instead of K^+ solves: the plan as the
+// assembly makes it (fxo_prepare), row reps[pl] stored through k_fxo_store_row into row reprow[pl] of the pre-tiled A.  No solver, no symmetry-adapted form.
+// *all_loaded: every class with touched dofs has its rows.
+int fxs_test_load_class(fx_shared *S, int c, const double *W, int *all_loaded)
+{
+  PMH_ARG(S && W && all_loaded && c >= 0 && c < S->ncls);
+  if (S->sym != 2) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_load_class: needs the PMH_FX_CLASS_ORBIT storage");
+  pmh_ctx    ctx = S->ctx;
+  if (!S->fxo_ready) // a new plan: its A starts from zero
+    for (fxs_class &D : S->C) D.test_loaded = 0;
+  PMH_CHK(fxo_prepare(S)); // PMH_ERR_STATE: a class with touched dofs has no symmetries yet
+  fxs_class &C = S->C[c];
+  const int  M = C.m1 - C.m0;
+  if (C.nc) {
+    std::vector<double> rows((size_t)M * C.nc);
+    std::vector<int>    ident((size_t)C.nc);
+    for (int pl = 0; pl < M; pl++) memcpy(&rows[(size_t)pl * C.nc], W + (size_t)C.reps[C.m0 + pl] * C.nc, sizeof(double) * (size_t)C.nc);
+    for (int i = 0; i < C.nc; i++) ident[i] = i;
+    double *d_rows = nullptr;
+    int    *d_ident = nullptr;
+    PMH_CHK(pmh_malloc(ctx, sizeof(double) * rows.size(), (void **)&d_rows));
+    int rc = pmh_malloc(ctx, sizeof(int) * ident.size(), (void **)&d_ident);
+    if (!rc) rc = pmh_memcpy_h2d(ctx, d_rows, rows.data(), sizeof(double) * rows.size());
+    if (!rc) rc = pmh_memcpy_h2d(ctx, d_ident, ident.data(), sizeof(int) * ident.size());
+    for (int pl = 0; pl < M && !rc; pl++)
+      hipLaunchKernelGGL(k_fxo_store_row, dim3(std::max(1, std::min(64, (C.nc + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, C.reprow[pl], C.tm, C.nc, C.nkc, (const int *)d_ident,
+                         (const int *)C.d_kinv, (const double *)(d_rows + (size_t)pl * C.nc), S->Afund + C.aoff);
+    if (!rc && hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_test_load_class: launch failed");
+    if (!rc) rc = pmh_sync(ctx);
+    if (d_rows) pmh_free(ctx, d_rows);
+    if (d_ident) pmh_free(ctx, d_ident);
+    if (rc) return rc;
+  }
+  C.test_loaded = 1;
+  *all_loaded = 1;
+  for (const fxs_class &D : S->C)
+    if (D.nc && !D.test_loaded) *all_loaded = 0;
+  return PMH_SUCCESS;
+}
+
+// what fxo_prepare decided for class c and what fxo_gemm launches for it (the layout of info: include/permon_hip.h)
+int fxs_orbit_plan_info(fx_shared *S, int c, long long info[24])
+{
+  PMH_ARG(S && info && c >= 0 && c < S->ncls);
+  if (S->sym != 2) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_orbit_plan_info: needs the PMH_FX_CLASS_ORBIT storage");
+  if (!S->fxo_ready) return pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_orbit_plan_info: no plan yet (after the assembly or pmh_fexplicit_test_load_class)");
+  const fxs_class &C    = S->C[c];
+  const int        kind = fxo_launch_kind(S, C);
+  if (C.nc && !(kind == 2 ? fxo_instance(S->merged_tm, S->merged_tn, S->merged_tnw, true) : fxo_instance(C.tm, C.tn, C.tnw, kind == 1)))
+    return pmh_set_error(PMH_ERR_STATE, "PMH_FX_CLASS_ORBIT: row tile %d has no 16x16x4 kernel", C.tm);
+  const long long v[24] = {C.nc, C.ld, C.S, C.ngroups, C.xoff, C.nsym, C.nsymp, C.M_all, C.tm, C.Mp, C.nc ? C.Mp / C.tm : 0, C.tn, C.tnw, C.nseg, C.nkc, C.plan_units, C.plan_units_work, C.plan_smax,
+                           C.wg_count, C.plan_wg2, kind, S->d_fin_args ? 1 : 0, C.m0, C.m1};
+  memcpy(info, v, sizeof(v));
   return PMH_SUCCESS;
 }
 

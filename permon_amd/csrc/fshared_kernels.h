@@ -534,13 +534,14 @@ __global__ __launch_bounds__(256, 2) void k_fxo_gemm16(const int *__restrict__ i
 
 // Y[g p][slot] = s_g(p) * (sum over the row tile's units (k segments) in unit order, over a unit's splits in split order) for the (row, operation) pairs that
 // own their row (use = +-1: the operation the row was assigned to; rows fixed by several operations are written once), over the columns the (group, row tile)
-// pairs list. One thread per (row, listed column); grid.y = group.  fintab per (group, row tile): offset of its column list, its padded column count, its first
+// pairs list -- and of those only where block (group, slot) touches row g p (tmask: a column is listed for the whole tile; Y stays zero on the other rows).
+// One thread per (row, listed column); grid.y = group.  fintab per (group, row tile): offset of its column list, its padded column count, its first
 // element in the group's numbering, its first unit; unittab per unit: offset of its look-up table (column of the tile's list -> column of the unit's list, -1:
 // B is zero there on the whole segment, nothing was multiplied), its padded column count, its splits; unitbase: split 0 of the unit in cpart
 #define FXO_FU 4
 __device__ __forceinline__ void fxo_fin_body(int bx, int by, int ntile, int tm, int nsymp, int nc, const int *__restrict__ fintab, const int *__restrict__ unittab, const long long *__restrict__ unitbase,
                                                        const int *__restrict__ lut, const int *__restrict__ coltab, const double *__restrict__ cp, const signed char *__restrict__ use,
-                                                       const int *__restrict__ reppos, const int *__restrict__ posmap, long long xbase0, int ld, double *__restrict__ Y, int nslot)
+                                                       const int *__restrict__ reppos, const int *__restrict__ posmap, long long xbase0, int ld, double *__restrict__ Y, int nslot, const char *__restrict__ tmask)
 {
   const int  i  = bx * PMH_BLOCK + (int)threadIdx.x;
   const int *ft = fintab + 4 * (ntile + 1) * by;
@@ -553,7 +554,10 @@ __device__ __forceinline__ void fxo_fin_body(int bx, int by, int ntile, int tm, 
   const int g = ct >> 3, sl = ct & 7, row = mt * tm + r;
   const int u = use[(long long)row * nsymp + g];
   if (u == 0) return;
-  const long long dst = xbase0 + (long long)by * ld * nslot + (long long)posmap[(long long)g * nc + reppos[row]] * nslot + sl;
+  const int gp = posmap[(long long)g * nc + reppos[row]];
+  // the column is listed for the whole row tile; this row has it only where block (group, slot) touches row g p -- nothing is summed or written elsewhere (Y stays 0 there)
+  if (!tmask[((long long)by * nc + gp) * FXS_S + sl]) return;
+  const long long dst = xbase0 + (long long)by * ld * nslot + (long long)gp * nslot + sl;
   double          s   = 0.0;
   // FXO_FU units at a time: their look-ups, then the first 8 splits of each travel together (a plain loop compiles to load - wait - add per unit and split);
   // the sums are still taken unit after unit, split after split (+ 0.0 for a split that does not exist changes nothing)
@@ -588,9 +592,9 @@ __device__ __forceinline__ void fxo_fin_body(int bx, int by, int ntile, int tm, 
 
 __global__ __launch_bounds__(PMH_BLOCK) void k_fxo_fin(int ntile, int tm, int nsymp, int nc, const int *__restrict__ fintab, const int *__restrict__ unittab, const long long *__restrict__ unitbase,
                                                        const int *__restrict__ lut, const int *__restrict__ coltab, const double *__restrict__ cp, const signed char *__restrict__ use,
-                                                       const int *__restrict__ reppos, const int *__restrict__ posmap, long long xbase0, int ld, double *__restrict__ Y, int nslot)
+                                                       const int *__restrict__ reppos, const int *__restrict__ posmap, long long xbase0, int ld, double *__restrict__ Y, int nslot, const char *__restrict__ tmask)
 {
-  fxo_fin_body(blockIdx.x, blockIdx.y, ntile, tm, nsymp, nc, fintab, unittab, unitbase, lut, coltab, cp, use, reppos, posmap, xbase0, ld, Y, nslot);
+  fxo_fin_body(blockIdx.x, blockIdx.y, ntile, tm, nsymp, nc, fintab, unittab, unitbase, lut, coltab, cp, use, reppos, posmap, xbase0, ld, Y, nslot, tmask);
 }
 
 // (struct fxo_fin_args: fshared_types.h)
@@ -598,7 +602,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_fxo_fin_all(const fxo_fin_args *_
 {
   const fxo_fin_args a = args[blockIdx.z];
   if ((int)blockIdx.x >= a.nbx || (int)blockIdx.y >= a.ngroups) return;
-  fxo_fin_body(blockIdx.x, blockIdx.y, a.ntile, a.tm, a.nsymp, a.nc, a.fintab, a.unittab, a.unitbase, a.lut, a.coltab, cp, a.use, a.reppos, a.posmap, a.xbase0, a.ld, Y, a.nslot);
+  fxo_fin_body(blockIdx.x, blockIdx.y, a.ntile, a.tm, a.nsymp, a.nc, a.fintab, a.unittab, a.unitbase, a.lut, a.coltab, cp, a.use, a.reppos, a.posmap, a.xbase0, a.ld, Y, a.nslot, a.tmask);
 }
 
 // row of representative pl (local index) from its K^+ solve -> the pre-tiled A (column kinv[c] for position c)

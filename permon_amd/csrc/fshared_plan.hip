@@ -101,8 +101,10 @@ int fxo_prepare(fx_shared *S)
         for (int g = 0; g < C.nsym; g++) {
           if (!use_h[(size_t)pl * C.nsym + g]) continue;
           const int r = C.h_posmap[(size_t)g * C.nc + p];
+          // (unpruned: the slots of the class's multivector records only -- a record of C.S < 8 slots has no entry for the others, and a column for one would gather
+          // from, and be written into, the neighbouring positions' records)
           for (int sl = 0; sl < FXS_S; sl++)
-            if (!prune || C.tmask[((size_t)gr * C.nc + r) * FXS_S + sl]) {
+            if (prune ? C.tmask[((size_t)gr * C.nc + r) * FXS_S + sl] != 0 : sl < C.S) {
               const size_t b = ((size_t)gr * C.nsym + g) * FXS_S + sl;
               pat[(size_t)pl * nw + b / 64] |= 1ULL << (b % 64), cnt[pl]++;
             }
@@ -529,6 +531,8 @@ int fxo_prepare(fx_shared *S)
       wgfirst.push_back((int)(items.size() / 8) - C.item_first);
     }
     C.item_count = (int)(items.size() / 8) - C.item_first;
+    C.plan_units = (int)P.units.size(), C.plan_units_work = (int)unitbase.size(), C.plan_wg2 = nitem2, C.plan_smax = 0;
+    for (const fxo_unit &U : P.units) C.plan_smax = std::max(C.plan_smax, U.S);
     if (getenv("PMH_FXO_VERBOSE")) {
       fprintf(stderr, "PMH_FX_CLASS_ORBIT class %d: %d representatives in %d row tiles of %d, %d k segments (chunks:", c, Mrows, ntile, C.tm, C.nseg);
       for (int sg = 0; sg < C.nseg; sg++) fprintf(stderr, " %d", P.segc0[sg + 1] - P.segc0[sg]);
@@ -624,7 +628,7 @@ int fxo_prepare(fx_shared *S)
       memset(&a, 0, sizeof(a));
       if (!C.nc || C.fin_elems <= 0) continue; // nbx = 0: the class's workgroups return at once
       a.ntile = C.Mp / C.tm, a.tm = C.tm, a.nsymp = C.nsymp, a.nc = C.nc, a.ld = C.ld, a.nslot = C.S, a.nbx = (C.fin_elems + PMH_BLOCK - 1) / PMH_BLOCK, a.ngroups = C.ngroups;
-      a.fintab = C.d_fintab, a.unittab = C.d_unittab, a.lut = C.d_lut, a.coltab = C.d_coltab, a.reppos = C.d_reppos, a.posmap = C.d_posmap, a.unitbase = C.d_finbase, a.use = C.d_use, a.xbase0 = C.xoff;
+      a.fintab = C.d_fintab, a.unittab = C.d_unittab, a.lut = C.d_lut, a.coltab = C.d_coltab, a.reppos = C.d_reppos, a.posmap = C.d_posmap, a.unitbase = C.d_finbase, a.use = C.d_use, a.tmask = C.d_tmask, a.xbase0 = C.xoff;
       S->fin_nbx = std::max(S->fin_nbx, a.nbx), S->fin_ngroups = std::max(S->fin_ngroups, a.ngroups);
     }
     PMH_CHK(pmh_malloc(ctx, sizeof(fxo_fin_args) * fa.size(), &S->d_fin_args));

@@ -66,6 +66,9 @@ struct fxs_class {
   // row tile) the columns (operation << 3 | slot) some row of the tile needs, padded to 128 with -1; the representatives are ordered by their need pattern
   // (rows of A)
   std::vector<char> tmask;              // [ngroups][nc][8]
+  // its device copy: a column is listed for a whole row tile, the finishing kernel sums and writes a (row, column) pair only where the block touches the row, so Y
+  // stays zero everywhere else
+  char             *d_tmask = nullptr;
   std::vector<int>  reprow;             // representative index (in reps) -> row of A / cpart
   // fintab per (group, row tile): coltab offset, padded columns, first element of the tile in the group's numbering
   int              *d_coltab = nullptr, *d_fintab = nullptr;
@@ -85,6 +88,9 @@ struct fxs_class {
   // unittab per (group, row tile, segment) unit: offset of its look-up table, padded columns, splits, 0
   int             *d_kinv = nullptr, *d_unittab = nullptr, *d_lut = nullptr;
   int              nseg = 1;
+  // what fxo_prepare decided, for pmh_fexplicit_orbit_plan_info (tests): units, units with chunks on this rank, the largest split count of a unit, workgroups with
+  // two or more items; test_loaded: the representatives' rows came from pmh_fexplicit_test_load_class
+  int              plan_units = 0, plan_units_work = 0, plan_smax = 0, plan_wg2 = 0, test_loaded = 0;
 };
 
 struct fx_shared {
@@ -146,6 +152,7 @@ struct fxo_fin_args {
   const int       *fintab, *unittab, *lut, *coltab, *reppos, *posmap;
   const long long *unitbase;
   const signed char *use;
+  const char      *tmask;
   long long        xbase0;
 };
 

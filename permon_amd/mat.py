@@ -443,6 +443,25 @@ class MatExplicitDual:
                                                 bc.ctypes.data_as(C.c_void_p) if bc is not None else None, float(rtol), int(max_it)))
         self.refresh_sizes()
 
+    ORBIT_PLAN_FIELDS = ("n_c", "ld", "slots", "groups", "xoff", "nsym", "nsymp", "M", "tm", "Mp", "row_tiles", "tn", "tnw", "segments", "chunks", "units", "units_work",
+                         "max_split", "workgroups", "workgroups_multi", "launch", "finish", "rep0", "rep1")
+
+    def test_load_class(self, cls, W):
+        """"class_orbit" test entry (pmh_fexplicit_test_load_class): the representatives' rows of class `cls` from the host matrix W (n_c x n_c in the numbering of
+        class_union, invariant under the class's symmetries) instead of K^+ solves; after the symmetries of every class are set."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        n = self.class_union(cls).size
+        if W.shape != (n, n):
+            raise ValueError("W must be %d x %d" % (n, n))
+        check(self.ctx.L.pmh_fexplicit_test_load_class(self.h, int(cls), W.ctypes.data_as(C.c_void_p)))
+
+    def orbit_plan_info(self, cls):
+        """"class_orbit": what the plan of the orbit GEMM decided for class `cls` and what the apply launches (pmh_fexplicit_orbit_plan_info), as a dict over
+        ORBIT_PLAN_FIELDS."""
+        info = np.zeros(24, dtype=np.int64)
+        check(self.ctx.L.pmh_fexplicit_orbit_plan_info(self.h, int(cls), info.ctypes.data_as(C.c_void_p)))
+        return dict(zip(self.ORBIT_PLAN_FIELDS, (int(v) for v in info)))
+
     def assemble_stats(self):
         n, t = C.c_longlong(), C.c_double()
         check(self.ctx.L.pmh_fexplicit_assemble_stats(self.h, C.byref(n), C.byref(t)))

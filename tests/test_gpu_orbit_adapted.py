@@ -65,7 +65,8 @@ SHAPES = [((2, 2, 2), 4), ((2, 2, 2), 5), ((4, 4, 4), 4)]
 def test_adapted_dense_apply_against_longdouble(ctx, sub, nel):
     """(a), (d): Y = blockdiag(W_b) X on a random multivector (zero off every block's touched set) through the adapted form and through the GEMM (knob off), both judged
     against a numpy.longdouble product with the dense blocks of get_block.  Three sums in sequence instead of one, each no longer than the GEMM's, plus one spare factor:
-    the adapted form's normwise error may be at most 4 x the GEMM's in the same test.  Two applications give the same bits.
+    the adapted form's normwise error may be at most 4 x the GEMM's in the same test, and the GEMM's own error meets the bound derived for a sum of n_c terms
+    ((n_c + 8) 2^-53 || |W| |x| || / || ref ||), so that the yardstick has a checked base.  Two applications give the same bits.
     Measured (adapted / GEMM): see docs/LAB_NOTEBOOK.md, entry "Orbit operator in the symmetry-adapted basis"."""
     f, q = _problem(ctx, sub, nel)
     E = q.E
@@ -75,13 +76,14 @@ def test_adapted_dense_apply_against_longdouble(ctx, sub, nel):
     ld = ntot // (8 * ngroups)
     urel = E.class_union(0)
     rng = np.random.default_rng(100 + nel)
-    x, ref = np.zeros(ntot), np.zeros(ntot, dtype=np.longdouble)
+    x, ref, mag = np.zeros(ntot), np.zeros(ntot, dtype=np.longdouble), np.zeros(ntot, dtype=np.longdouble)
     touched = np.zeros(ntot, dtype=bool)
     for b in range(f.nsub):
         W, g = E.block(b)
         idx = (b // 8) * ld * 8 + np.searchsorted(urel, g - b * f.n_i) * 8 + b % 8
         x[idx] = rng.standard_normal(idx.size)
         ref[idx] = W.astype(np.longdouble) @ x[idx].astype(np.longdouble)
+        mag[idx] = np.abs(W).astype(np.longdouble) @ np.abs(x[idx]).astype(np.longdouble)
         touched[idx] = True
     xv = ctx.vec_from(x)
     ya, ya2, yg = ctx.vec(ntot), ctx.vec(ntot), ctx.vec(ntot)
@@ -100,6 +102,10 @@ def test_adapted_dense_apply_against_longdouble(ctx, sub, nel):
     err_g = float(np.linalg.norm((yg[touched] - ref[touched]).astype(np.float64))) / nrm
     print("orbit_adapted dense apply %s nel %d: adapted %.3e, GEMM %.3e (normwise, against longdouble)" % (sub, nel, err_a, err_g))
     assert not np.any(ya[~touched])  # nothing written off the touched set
+    # the yardstick itself: a sum of n_c fused terms in any order is within (n_c + 8) 2^-53 (|W| |x|)_i of the exact one, hence normwise (tests/orbit_cases.py)
+    bound_g = (urel.size + 8) * 2.0 ** -53 * float(np.linalg.norm(mag[touched])) / nrm
+    print("orbit GEMM dense apply %s nel %d: %.3e against the derived bound %.3e" % (sub, nel, err_g, bound_g))
+    assert err_g <= bound_g
     assert err_a <= 4.0 * err_g
 
 
