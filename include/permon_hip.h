@@ -819,6 +819,27 @@ int pmh_mg_stats(pmh_mg mg, long long *fine_spmv);
 int pmh_mg_timing_enable(pmh_mg mg, int max_launches); /* HIP-event pairs around the fine-level operator launches */
 int pmh_mg_timing_get(pmh_mg mg, int *launches, double *total_ms, double *bytes_per_launch);
 int pmh_mg_destroy(pmh_mg mg);
+/* Test entries (tests/test_gpu_mg_paths.py): the V-cycle as an operator, one column (pmh_mg) and 8 interleaved columns (the multi-right-hand-side form inside K^+).
+ * pmh_mg_test_info: info = {rows of the level, level operator (0 CSR / none on the coarsest level, 1 blocks of 3 x 3), its storage (PMH_BSR_*, -1 without a block copy),
+ *   transfer kernels to the next level (0 none, 1 node-wise, 2 scalar short rows, 3 scalar long rows), the level runs fused, cycle precision (0 fp64, 1 fp32), coarse
+ *   pseudo-inverse in fp16, every coarse block a multiple of 16 rows and >= 512, coarse blocks, congruent replicas of the block copy}; cp_scale: the fp16 pseudo-inverse's
+ *   power of two.
+ * pmh_mg_test_apply: pmh_mg_apply under a device halt word of the entry's own holding `halt` (non-zero: every launch must be a no-op); synchronises.
+ * pmh_mg_test_vector: one work vector of a level to the host in the cycle's precision -- which = 0 x, 1 b, 2 r, 3 d, 4 t, 5 xa, 6 dinv; PMH_ERR_ARG for a vector the
+ *   level does not own (x, b of level 0 in fp64; all but x, b on the coarsest level).
+ * pmh_mg_mv_test_create: the 8-column cycle on the hierarchy of mg (of the first of nrep congruent blocks); PMH_ERR_SUP with the reason where it declines.
+ * pmh_mg_mv_test_info: info = {rows per replica, nrep, transfer kernels (0 none, 1 node-wise, 2 rectangular ELL pair, 3 scalar), coarse solve on the last level (0 fp32
+ *   entries, 1 fp16 entries, 2 fp16 on the matrix cores; -1 on a smoothed level), storage of the level operator's copy (-1 on the last level), the next level's first
+ *   direction rides on the restriction, coarse blocks per replica, 0}.
+ * pmh_mg_mv_test_apply: b (and z64, or NULL as the solver calls it) fp64 device multivectors of rows x 8; pmh_mg_mv_test_vector: as above in float, rows x 8 (dinv: rows). */
+int pmh_mg_test_info(pmh_mg mg, int level, long long info[10], double *cp_scale);
+int pmh_mg_test_apply(pmh_mg mg, const double *b_dev, double *x_dev, int halt);
+int pmh_mg_test_vector(pmh_mg mg, int level, int which, void *host_out);
+int pmh_mg_mv_test_create(pmh_mg mg, int nrep, void **M);
+int pmh_mg_mv_test_info(void *M, int level, long long info[8]);
+int pmh_mg_mv_test_apply(void *M, const double *b_dev, double *z64_dev, int halt);
+int pmh_mg_mv_test_vector(void *M, int level, int which, float *host_out);
+int pmh_mg_mv_test_destroy(void *M);
 int pmh_matinv_set_pc_mg(pmh_matinv Kplus, pmh_mg mg); /* NULL: back to Jacobi / none */
 /* MATINV's own K x product on the 3x3-block kernel (PETSc MATSEQBAIJ role: 8.44 instead of 12 bytes per non-zero);
  * returns PMH_ERR_SUP if K has no 3x3 block structure.  Timing as pmh_csr_timing_*. */

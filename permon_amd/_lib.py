@@ -362,6 +362,14 @@ _PROTOS = {
     "pmh_mg_apply": [vp, vp, vp],
     "pmh_mg_stats": [vp, C.POINTER(C.c_longlong)],
     "pmh_mg_destroy": [vp],
+    "pmh_mg_test_info": [vp, C.c_int, C.POINTER(C.c_longlong), c_double_p],
+    "pmh_mg_test_apply": [vp, vp, vp, C.c_int],
+    "pmh_mg_test_vector": [vp, C.c_int, C.c_int, vp],
+    "pmh_mg_mv_test_create": [vp, C.c_int, C.POINTER(vp)],
+    "pmh_mg_mv_test_info": [vp, C.c_int, C.POINTER(C.c_longlong)],
+    "pmh_mg_mv_test_apply": [vp, vp, vp, C.c_int],
+    "pmh_mg_mv_test_vector": [vp, C.c_int, C.c_int, vp],
+    "pmh_mg_mv_test_destroy": [vp],
     "pmh_matinv_set_pc_mg": [vp, vp],
     "pmh_qps_default_opts": [C.POINTER(QpsOpts)],
     "pmh_qps_set_from_options": [C.c_char_p, C.c_char_p, C.POINTER(QpsOpts), C.POINTER(MpgpOpts), C.POINTER(SmalxeOpts), C.c_char_p, C.c_int],

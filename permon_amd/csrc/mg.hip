@@ -336,6 +336,16 @@ template <typename TV> static int mg_cycle(pmh_mg mg, int l, const TV *b, TV *x,
 // does level l run mg_level_fused (its first smoothing direction can then be produced by the kernel that makes its b)?
 static inline bool mg_fused_level(pmh_mg mg, int l) { return l < mg->nlevels - 1 && mg->fused && mg->L[l].Ab; }
 
+// which pair of transfer kernels level l launches (pmh_mg_test_info reports the same number): the node-level copies exist (both or none) where P = P_node (x) I_3
+enum { MG_TRANSFER_NONE = 0, MG_TRANSFER_NODAL = 1, MG_TRANSFER_SHORT = 2, MG_TRANSFER_LONG = 3 };
+static inline int mg_transfer_kind(pmh_mg mg, int l)
+{
+  const mg_level &Lv = mg->L[l];
+  if (l >= mg->nlevels - 1) return MG_TRANSFER_NONE;
+  if (Lv.rn_rowptr && Lv.pn_rowptr) return MG_TRANSFER_NODAL;
+  return Lv.long_rows ? MG_TRANSFER_LONG : MG_TRANSFER_SHORT;
+}
+
 // b_c = P' t (+ the coarse level's d0) and x -= P x_c: node-level kernels when P = P_node (x) I_3, scalar CSR kernels otherwise
 template <typename TV>
 static void mg_restrict(pmh_mg mg, int l, const TV *t, bool with_d0)
@@ -345,10 +355,11 @@ static void mg_restrict(pmh_mg mg, int l, const TV *t, bool with_d0)
   const TV   *dv = with_d0 ? (const TV *)Lc.dinv : (const TV *)nullptr;
   const TV    it = with_d0 ? (TV)(1.0 / Lc.theta) : (TV)0;
   TV         *dc = with_d0 ? (TV *)Lc.d : (TV *)nullptr;
-  if (Lv.rn_rowptr) {
+  const int   kind = mg_transfer_kind(mg, l);
+  if (kind == MG_TRANSFER_NODAL) {
     const int ncn = Lc.n / 3;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_restrict3<TV>), mg_grid(8 * ncn), dim3(PMH_BLOCK), 0, st, ncn, mg->halt, (const int *)Lv.rn_rowptr, (const int *)Lv.rn_col, (const TV *)Lv.rn_val, t, (TV *)Lc.b, dv, it, dc);
-  } else if (Lv.long_rows) {
+  } else if (kind == MG_TRANSFER_LONG) {
     pmh_csr R = Lv.P->transpose;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_restrict_w<TV>), mg_grid(64LL * Lc.n > 0x7fffffff ? 0x7fffffff : 64 * Lc.n), dim3(PMH_BLOCK), 0, st, Lc.n, mg->halt, (const int *)R->d_rowptr, (const int *)R->d_col, (const TV *)Lv.rv, t,
                        (TV *)Lc.b, dv, it, dc);
@@ -364,9 +375,10 @@ static void mg_prolong_sub(pmh_mg mg, int l, TV *x)
 {
   mg_level   &Lv = mg->L[l], &Lc = mg->L[l + 1];
   hipStream_t st = mg->ctx->stream;
-  if (Lv.pn_rowptr)
+  const int   kind = mg_transfer_kind(mg, l);
+  if (kind == MG_TRANSFER_NODAL)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_prolong_sub3<TV>), mg_grid(Lv.n / 3), dim3(PMH_BLOCK), 0, st, Lv.n / 3, mg->halt, (const int *)Lv.pn_rowptr, (const int *)Lv.pn_col, (const TV *)Lv.pn_val, (const TV *)Lc.x, x);
-  else if (Lv.long_rows)
+  else if (kind == MG_TRANSFER_LONG)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_prolong_sub8<TV>), mg_grid(8LL * Lv.n > 0x7fffffff ? 0x7fffffff : 8 * Lv.n), dim3(PMH_BLOCK), 0, st, Lv.n, mg->halt, (const int *)Lv.P->d_rowptr, (const int *)Lv.P->d_col, (const TV *)Lv.pv, (const TV *)Lc.x, x);
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_prolong_sub<TV>), mg_grid(Lv.n), dim3(PMH_BLOCK), 0, st, Lv.n, mg->halt, (const int *)Lv.P->d_rowptr, (const int *)Lv.P->d_col, (const TV *)Lv.pv, (const TV *)Lc.x, x);
@@ -748,4 +760,47 @@ extern "C" int pmh_mg_timing_get(pmh_mg mg, int *launches, double *total_ms, dou
   PMH_CHK(pmh_bsr3_timing_get(mg->L[0].Ab, launches, total_ms, &ex));
   if (bytes_per_launch) *bytes_per_launch = pmh_bsr3_bytes(mg->L[0].Ab) + (*launches ? ex / *launches : 0.0);
   return PMH_SUCCESS;
+}
+
+// ---- test entries (tests/test_gpu_mg_paths.py): what pmh_mg_create decided for a level, ONE cycle under a halt word of the entry's own, and the work vectors a cycle leaves
+// behind; nothing inside the solvers calls them ----
+// info = {rows, level operator (0: CSR, or none on the coarsest level; 1: 3 x 3 blocks), its storage (PMH_BSR_*, -1 without a block copy), transfer kernels to the next level
+// (0 none, 1 node-wise, 2 scalar short rows, 3 scalar long rows), the level runs fused, cycle precision (0 fp64, 1 fp32), cp_half, coarse_m16, nb_coarse, congruent replicas
+// of the block copy (1 without one)}; cp_scale: the power of two of the fp16 pseudo-inverse (1 otherwise)
+extern "C" int pmh_mg_test_info(pmh_mg mg, int level, long long info[10], double *cp_scale)
+{
+  PMH_ARG(mg && info && level >= 0 && level < mg->nlevels);
+  const mg_level &Lv = mg->L[level];
+  const bool      smoothed = level < mg->nlevels - 1;
+  info[0] = Lv.n, info[1] = (smoothed && Lv.Ab) ? 1 : 0, info[2] = (smoothed && Lv.Ab) ? Lv.Ab->storage : -1, info[3] = mg_transfer_kind(mg, level);
+  info[4] = mg_fused_level(mg, level) ? 1 : 0, info[5] = mg->is_float ? 1 : 0, info[6] = mg->cp_half, info[7] = mg->coarse_m16, info[8] = mg->nb_coarse;
+  info[9] = (smoothed && Lv.Ab) ? Lv.Ab->nrep : 1;
+  if (cp_scale) *cp_scale = mg->cp_scale;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_mg_test_apply(pmh_mg mg, const double *b, double *x, int halt)
+{
+  PMH_ARG(mg && b && x && b != x);
+  pmh_ctx ctx    = mg->ctx;
+  int    *d_halt = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(int), (void **)&d_halt));
+  int rc = pmh_memcpy_h2d(ctx, d_halt, &halt, sizeof(int));
+  if (!rc) rc = pmh_mg_apply_halt(mg, b, x, d_halt);
+  if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_mg_test_apply: stream synchronisation failed");
+  pmh_free(ctx, d_halt);
+  return rc;
+}
+
+// which: 0 x, 1 b, 2 r, 3 d, 4 t, 5 xa, 6 dinv -- the level's rows in the cycle's precision (double / float); PMH_ERR_ARG for a vector the level does not own (x and b of
+// level 0 in fp64 are the caller's; the coarsest level has x and b only)
+extern "C" int pmh_mg_test_vector(pmh_mg mg, int level, int which, void *host_out)
+{
+  PMH_ARG(mg && host_out && level >= 0 && level < mg->nlevels && which >= 0 && which <= 6);
+  const mg_level &Lv   = mg->L[level];
+  const void     *v[7] = {Lv.x, Lv.b, Lv.r, Lv.d, Lv.t, Lv.xa, Lv.dinv};
+  PMH_ARG(v[which]);
+  if (hipStreamSynchronize(mg->ctx->stream) != hipSuccess) return pmh_set_error(PMH_ERR_HIP, "pmh_mg_test_vector: stream synchronisation failed");
+  if (Lv.n == 0) return PMH_SUCCESS;
+  return pmh_memcpy_d2h(mg->ctx, host_out, v[which], (mg->is_float ? sizeof(float) : sizeof(double)) * (size_t)Lv.n);
 }

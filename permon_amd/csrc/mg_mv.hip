@@ -365,6 +365,19 @@ int pmh_mg_mv_create(pmh_mg mg, pmh_mg_mv *out, int nrep)
   return PMH_SUCCESS;
 }
 
+// which transfer kernels level l launches and which coarse solve the last level (pmh_mg_mv_test_info reports the same numbers): the rectangular ELL pair exists both or none
+enum { MVG_TRANSFER_NONE = 0, MVG_TRANSFER_NODAL = 1, MVG_TRANSFER_ELL = 2, MVG_TRANSFER_SCALAR = 3 };
+enum { MVG_COARSE_F32 = 0, MVG_COARSE_F16 = 1, MVG_COARSE_MFMA = 2 };
+static inline int mvg_transfer_kind(pmh_mg_mv M, int l)
+{
+  if (l >= M->mg->nlevels - 1) return MVG_TRANSFER_NONE;
+  if (M->L[l].ER && M->L[l].EP) return MVG_TRANSFER_ELL;
+  return M->mg->L[l].rn_rowptr != nullptr ? MVG_TRANSFER_NODAL : MVG_TRANSFER_SCALAR;
+}
+static inline int mvg_coarse_kind(pmh_mg mg) { return (mg->cp_half && mg->coarse_m16) ? MVG_COARSE_MFMA : (mg->cp_half ? MVG_COARSE_F16 : MVG_COARSE_F32); }
+// the coarse level is a smoothed one: its d0 rides on the restriction
+static inline bool mvg_coarse_d0(pmh_mg mg, int l) { return l + 2 < mg->nlevels; }
+
 static int mvg_cycle(pmh_mg_mv M, int l, const double *b64, double *z64, bool d0_ready, const int *halt)
 {
   pmh_mg       mg = M->mg;
@@ -374,12 +387,12 @@ static int mvg_cycle(pmh_mg_mv M, int l, const double *b64, double *z64, bool d0
   const dim3   blk(PMH_BLOCK);
   const int    nrep = M->nrep, n_l = Lv.n / nrep; // (congruent blocks: the first block's share of every level)
   if (l == mg->nlevels - 1) {
-    const int nbc = mg->nb_coarse / nrep;
-    if (mg->cp_half && mg->coarse_m16)
+    const int nbc = mg->nb_coarse / nrep, ck = mvg_coarse_kind(mg);
+    if (ck == MVG_COARSE_MFMA)
       // (16 wavefronts x 2 steps per stage: 21.4 us on the 5 184-row block; 8 x 3: 23.2, 8 x 6: 26.9, 16 x 3: 25.3, 4 x 6: 26.6)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse_mfma<16, 2>), dim3(n_l / 16), dim3(64 * 16), 0, st, nbc, halt, (const int *)mg->d_crs, (const long long *)mg->d_cofs,
                          (const _Float16 *)mg->d_cpinv, (float)mg->cp_scale, (const float *)Ml.b, Ml.x);
-    else if (mg->cp_half)
+    else if (ck == MVG_COARSE_F16)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse<_Float16>), dim3((n_l + 3) / 4), blk, 0, st, nbc, n_l, halt, (const int *)mg->d_crs,
                          (const long long *)mg->d_cofs, (const _Float16 *)mg->d_cpinv, (float)mg->cp_scale,
                          (const float *)Ml.b, Ml.x);
@@ -405,15 +418,15 @@ static int mvg_cycle(pmh_mg_mv M, int l, const double *b64, double *z64, bool d0
   e.c0 = 1.f + c1, e.c1 = c1, e.c2 = c2;
   PMH_CHK(pmh_mv_spmv_f32(Ml.E, Ml.d, Ml.xa, PMH_BSR_EPI_PRE, &e, halt));
   PMH_CHK(pmh_mv_spmv_f32(Ml.E, Ml.xa, Ml.t, PMH_EPI_SUB, &e, halt));
-  const bool cf  = l + 2 < mg->nlevels; // the coarse level is a smoothed one: its d0 rides on the restriction
+  const bool cf  = mvg_coarse_d0(mg, l);
   const int  ncn = Lc.n / 3 / nrep;
-  const bool nodal = Lv.rn_rowptr != nullptr;
-  if (Ml.ER) {
+  const int  tk  = mvg_transfer_kind(M, l);
+  if (tk == MVG_TRANSFER_ELL) {
     pmh_mv_epi<float> er;
     memset(&er, 0, sizeof(er));
     if (cf) er.dinv = (const float *)Lc.dinv, er.d = Mc.d, er.c0 = (float)(1.0 / Lc.theta);
     PMH_CHK(pmh_mv_spmv_f32(Ml.ER, Ml.t, Mc.b, PMH_MV_EPI_RESTRICT, &er, halt));
-  } else if (nodal)
+  } else if (tk == MVG_TRANSFER_NODAL)
     hipLaunchKernelGGL(k_mvg_restrict, mvg_grid((long long)ncn * 32), blk, 0, st, ncn, halt, (const int *)Lv.rn_rowptr, (const int *)Lv.rn_col,
                        (const float *)Lv.rn_val, (const float *)Ml.t, Mc.b,
                        cf ? (const float *)Lc.dinv : (const float *)nullptr, cf ? (float)(1.0 / Lc.theta) : 0.f, cf ? Mc.d : (float *)nullptr);
@@ -422,12 +435,12 @@ static int mvg_cycle(pmh_mg_mv M, int l, const double *b64, double *z64, bool d0
                        (const float *)Lv.rv, (const float *)Ml.t, Mc.b,
                        cf ? (const float *)Lc.dinv : (const float *)nullptr, cf ? (float)(1.0 / Lc.theta) : 0.f, cf ? Mc.d : (float *)nullptr);
   PMH_CHK(mvg_cycle(M, l + 1, nullptr, nullptr, cf, halt));
-  if (Ml.EP) {
+  if (tk == MVG_TRANSFER_ELL) {
     pmh_mv_epi<float> ep;
     memset(&ep, 0, sizeof(ep));
     ep.y1 = Ml.xa;
     PMH_CHK(pmh_mv_spmv_f32(Ml.EP, Mc.x, Ml.xa, PMH_EPI_ADD, &ep, halt)); // xa += (-P) x_c
-  } else if (nodal)
+  } else if (tk == MVG_TRANSFER_NODAL)
     hipLaunchKernelGGL(k_mvg_prolong_sub, mvg_grid((long long)(n_l / 3) * MV_R), blk, 0, st, n_l / 3, halt, (const int *)Lv.pn_rowptr, (const int *)Lv.pn_col,
                        (const float *)Lv.pn_val, (const float *)Mc.x, Ml.xa);
   else
@@ -447,3 +460,62 @@ int pmh_mg_mv_apply(pmh_mg_mv M, const double *b, double *z, const int *halt)
   return mvg_cycle(M, 0, b, z, false, halt);
 }
 const float *pmh_mg_mv_result(pmh_mg_mv M) { return M->L[0].x; }
+
+// ---- test entries (tests/test_gpu_mg_paths.py): the 8-column cycle as an operator -- which kernels it chose, ONE cycle under a halt word of the entry's own, and the work
+// multivectors it leaves behind; nothing inside the solvers calls them ----
+extern "C" int pmh_mg_mv_test_create(pmh_mg mg, int nrep, void **M_)
+{
+  PMH_ARG(mg && M_ && nrep >= 1);
+  *M_ = nullptr;
+  pmh_mg_mv M  = nullptr;
+  const int rc = pmh_mg_mv_create(mg, &M, nrep);
+  if (rc == PMH_EPI_UNSUPPORTED) return pmh_set_error(PMH_ERR_SUP, "pmh_mg_mv_test_create: %s", pmh_mv_why());
+  if (rc) return rc;
+  *M_ = M;
+  return PMH_SUCCESS;
+}
+
+// info = {rows of the level per replica, nrep, transfer kernels to the next level (0 none, 1 node-wise, 2 the rectangular ELL pair, 3 scalar), coarse solve on the last level
+// (0 k_mvg_coarse<float>, 1 k_mvg_coarse<_Float16>, 2 matrix cores; -1 on a smoothed level), storage of the level operator's ELL copy (-1 on the last level), the next
+// level's d0 rides on the restriction, coarse blocks of one replica, 0}
+extern "C" int pmh_mg_mv_test_info(void *M_, int level, long long info[8])
+{
+  pmh_mg_mv M = (pmh_mg_mv)M_;
+  PMH_ARG(M && info && level >= 0 && level < M->mg->nlevels);
+  pmh_mg     mg   = M->mg;
+  const bool last = level == mg->nlevels - 1;
+  info[0] = mg->L[level].n / M->nrep, info[1] = M->nrep, info[2] = mvg_transfer_kind(M, level), info[3] = last ? mvg_coarse_kind(mg) : -1;
+  info[4] = last ? -1 : M->L[level].E->storage, info[5] = (!last && mvg_coarse_d0(mg, level)) ? 1 : 0, info[6] = mg->nb_coarse / M->nrep, info[7] = 0;
+  return PMH_SUCCESS;
+}
+
+// b: fp64 multivector of the fine level (rows of one replica x 8, device); z64: the same for the result, or NULL (the production call: the fp32 result is level 0's x)
+extern "C" int pmh_mg_mv_test_apply(void *M_, const double *b, double *z64, int halt)
+{
+  pmh_mg_mv M = (pmh_mg_mv)M_;
+  PMH_ARG(M && b && b != z64);
+  pmh_ctx ctx    = M->ctx;
+  int    *d_halt = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(int), (void **)&d_halt));
+  int rc = pmh_memcpy_h2d(ctx, d_halt, &halt, sizeof(int));
+  if (!rc) rc = pmh_mg_mv_apply(M, b, z64, d_halt);
+  if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_mg_mv_test_apply: stream synchronisation failed");
+  pmh_free(ctx, d_halt);
+  return rc;
+}
+
+// which: 0 x, 1 b, 2 r, 3 d, 4 t, 5 xa (rows per replica x 8 floats), 6 dinv (rows per replica floats, the hierarchy's own); PMH_ERR_ARG on the last level for 2 .. 6
+extern "C" int pmh_mg_mv_test_vector(void *M_, int level, int which, float *host_out)
+{
+  pmh_mg_mv M = (pmh_mg_mv)M_;
+  PMH_ARG(M && host_out && level >= 0 && level < M->mg->nlevels && which >= 0 && which <= 6);
+  const mg_mv_level &Ml   = M->L[level];
+  const void        *v[7] = {Ml.x, Ml.b, Ml.r, Ml.d, Ml.t, Ml.xa, M->mg->L[level].dinv};
+  PMH_ARG(v[which]);
+  if (hipStreamSynchronize(M->ctx->stream) != hipSuccess) return pmh_set_error(PMH_ERR_HIP, "pmh_mg_mv_test_vector: stream synchronisation failed");
+  const size_t n = (size_t)(M->mg->L[level].n / M->nrep) * (which == 6 ? 1 : MV_R);
+  if (n == 0) return PMH_SUCCESS;
+  return pmh_memcpy_d2h(M->ctx, host_out, v[which], sizeof(float) * n);
+}
+
+extern "C" int pmh_mg_mv_test_destroy(void *M_) { return pmh_mg_mv_destroy((pmh_mg_mv)M_); }

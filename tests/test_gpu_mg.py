@@ -46,6 +46,8 @@ def test_vcycle_matches_numpy_restatement(ctx, physics, degree, csr_only, monkey
     b = np.random.default_rng(5).standard_normal(f.N)
     x = ctx.vec(f.N)
     mg.apply(ctx.vec_from(b), x)
+    # (tests/test_gpu_mg_paths.py now compares the block-operator cycles -- fused, unfused, degree 1 and 3 -- with == against the kernel-order restatement and the CSR-operator
+    # cycle with == on dyadic data; this norm check stays as the check on a Galerkin hierarchy of a real problem)
     ref = _vcycle_numpy(H, degree, 0.1, 1.1)(b)
     assert np.linalg.norm(x.to_numpy() - ref) <= 1e-11 * np.linalg.norm(ref)
     # symmetric: <V a, b> == <a, V b>
@@ -65,6 +67,7 @@ def test_fp32_cycle_is_a_close_copy_of_the_fp64_cycle(ctx):
         x = ctx.vec(f.N)
         mg.apply(ctx.vec_from(b), x)
         out.append(x.to_numpy())
+    # (a norm forgives a wrong lane or row of a small block: the fp32 / fp16 cycles are pinned entry by entry in tests/test_gpu_mg_paths.py; kept for the real hierarchy)
     assert np.linalg.norm(out[1] - out[0]) <= 2e-5 * np.linalg.norm(out[0])
     assert np.linalg.norm(out[2] - out[0]) <= 5e-3 * np.linalg.norm(out[0])  # fp16 entries: 2^-11 relative perturbation of K
     with pytest.raises(pa.PermonHipError):  # Poisson blocks have no 3x3 structure

@@ -176,7 +176,8 @@ def test_large_dense_coarse_block_is_solved_on_the_matrix_cores(ctx, nel):
     """The one-block regime of bench.py's inner-Krylov pass in small: 15^3- (23^3-) node cubes coarsened ONCE, dense coarse blocks of 8^3 (12^3) nodes = 1 536 (5 184, bench.py's)
     rows in fp16 -- multiples of 16 and >= 512, so the 8-column cycle takes k_mvg_coarse_mfma (v_mfma_f32_16x16x4_f32, 16 rows per workgroup, the k range split over its 8
     wavefronts: 48 steps of 32 k's = 6 per wavefront, whole pipeline stages; 162 steps = 21 per wavefront, 15 for the last one: the guarded tails) -- against the one-column
-    cycle's k_mg_coarse on 8 replicas: the same K^+ to 1e-8, iteration counts within 2."""
+    cycle's k_mg_coarse on 8 replicas: the same K^+ to 1e-8, iteration counts within 2.  (A converging CG forgives a slightly wrong preconditioner: the kernel itself is
+    compared on dyadic data and against its a-priori bound in tests/test_gpu_mg_paths.py, blocks of 528, 1008 + 528 and 1584 rows; this test stays for the solver around it.)"""
     from permon_amd.feti import CubeFeti
 
     f = CubeFeti((2, 2, 2), nel, "elasticity", contact=False)

@@ -31,7 +31,8 @@ def _local(f):
 
 def test_sa_cycle_matches_scipy_restatement(ctx):
     """One V-cycle of the C++-built hierarchy (fp64) on three staircase blocks against oracle.mg_host.vcycle on feti.sa_mg_hierarchy: same aggregates, same
-    Gram-Schmidt, same smoothing => the same linear operator to rounding."""
+    Gram-Schmidt, same smoothing => the same linear operator to rounding.  (The long-row transfer kernels this hierarchy takes are compared with == in
+    tests/test_gpu_mg_paths.py, case long_rows; this test stays for the hierarchy BUILDER.)"""
     from oracle import mg_host
 
     f = feti.MeshFeti(feti.irregular_partition(6, "staircase"), contact=False)
