@@ -730,6 +730,24 @@ int pmh_svm_multi_predict_csr(pmh_svm_multi svm, pmh_csr Xt, double *scores_dev,
    is counted in *n_unknown (may be NULL) and in no cell */
 int pmh_svm_multi_test(pmh_svm_multi svm, int n, const double *X_dev, const double *labels_true_dev, long long *confusion, long long *n_unknown);
 int pmh_svm_multi_test_csr(pmh_svm_multi svm, pmh_csr Xt, const double *labels_true_dev, long long *confusion, long long *n_unknown);
+/* Train the K problems on a subset S of the handle's samples, X staying where it is (pmh_svm_set_subset of the one binary handle, which pmh_svm_set_labels and
+ * pmh_svm_set_penalties between the classes keep).  m_dev as in pmh_svm_set_subset (copied; NULL: all samples again).  The classes stay those of ALL training
+ * labels: K, the classes, the shape of W and the chunks do not change.  A class without a sample in S is PMH_ERR_ARG, the message giving the class value (its
+ * problem against the rest would have no positive sample); what pmh_svm_set_subset refuses (an entry that is neither 0 nor 1, an empty S) is passed on.  A
+ * refusal leaves the handle as it was: subset, model, statistics, calibration.  On success the handle is untrained (pmh_svm_multi_get_model: PMH_ERR_STATE),
+ * without statistics and uncalibrated; pmh_svm_multi_set_model keeps the subset.  balanced under a subset: C_pos = C n_S / (2 n_{k,S}), C_neg = C n_S /
+ * (2 (n_S - n_{k,S})), the counts over S (pmh_svm_multi_get_stats reports them) */
+int pmh_svm_multi_set_subset(pmh_svm_multi svm, const double *m_dev /* n doubles of 0 / 1, or NULL = all samples; copied */);
+/* the mask (n doubles, device; all 1 without a subset), n_S (n without a subset) and the samples of each class inside S (K, host); each may be NULL */
+int pmh_svm_multi_get_subset(pmh_svm_multi svm, double *m_dev /* n, or NULL */, long long *n_in /* or NULL */, long long *class_counts_host /* K, or NULL */);
+/* Scores (n x K) and labels (n) of ALL n samples the handle was created on, held-out ones included, nothing uploaded: the sweeps of pmh_svm_multi_predict(_csr)
+   over the handle's own X (CSR: its own pmh_csr), the same bits as on an uploaded copy.  Either pointer may be NULL.  Before a model exists: PMH_ERR_STATE */
+int pmh_svm_multi_predict_own(pmh_svm_multi svm, double *scores_dev /* n x K, or NULL */, double *labels_dev /* n, or NULL */);
+/* confusion (K x K, host, as pmh_svm_multi_test's) of the handle's own samples against its training labels over the rows `which` selects; *n_counted (may be
+   NULL): how many rows that is.  Dense samples: a row that is not selected is not loaded from X; CSR: every stored entry is swept (no row skipping, as on the
+   binary handle) and only the count selects.  PMH_SVM_OWN_HELD_OUT without a subset: PMH_ERR_STATE; PMH_SVM_OWN_SUBSET without a subset: all rows; any other
+   `which`: PMH_ERR_ARG */
+int pmh_svm_multi_test_own(pmh_svm_multi svm, int which /* PMH_SVM_OWN_HELD_OUT | _SUBSET | _ALL */, long long *confusion /* K x K */, long long *n_counted /* or NULL */);
 int pmh_svm_multi_destroy(pmh_svm_multi svm);
 
 /* ---- SVM probabilities: Platt scaling (svm_proba.hip) --------------------------------------------------------------------------------------------------------

@@ -303,6 +303,10 @@ _PROTOS = {
     "pmh_svm_multi_predict_csr": [vp, vp, vp, vp],
     "pmh_svm_multi_test": [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_longlong)],
     "pmh_svm_multi_test_csr": [vp, vp, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_multi_set_subset": [vp, vp],
+    "pmh_svm_multi_get_subset": [vp, vp, C.POINTER(C.c_longlong), vp],
+    "pmh_svm_multi_predict_own": [vp, vp, vp],
+    "pmh_svm_multi_test_own": [vp, C.c_int, vp, C.POINTER(C.c_longlong)],
     "pmh_svm_multi_destroy": [vp],
     "pmh_svm_platt_fit": [vp, C.c_int, vp, vp, c_double_p, c_double_p, C.POINTER(SvmPlattStats)],
     "pmh_svm_calibrate": [vp, C.c_int, vp, vp],

@@ -132,6 +132,11 @@ int pmh_svm_sum_rows(pmh_ctx ctx, int nb, int K, const double *part, double *out
 // where y[i] == pos.  binary: every label must be +-1 (else PMH_ERR_ARG with the count); otherwise every label that is not pos is "the rest"
 int pmh_svm_platt_fit_strided(pmh_ctx ctx, int n, const double *scores, int stride, const double *y, double pos, int binary, double *A, double *B, pmh_svm_platt_stats *st);
 
+// the samples a binary handle was created on, as it borrows them, and its subset mask (svm_multi.hip scores its own rows over them): dense rows (*X, doubles
+// unless *f32) or CSR (*Xcsr, then *X == nullptr); *msk: n doubles of 0 / 1 on the device, the operator's, valid until the next pmh_svm_set_subset; nullptr
+// without a subset.  Any pointer may be NULL
+void pmh_svm_own_samples(pmh_svm s, const void **X, int *f32, pmh_csr *Xcsr, const double **msk);
+
 // ---- svm_csr.hip: samples in CSR --------------------------------------------------------------------------------------------------------------------
 // dots[i] = x_i . w for the rows of X (one sweep over its stored entries, work divided by entries; w: X->ncols doubles, dots: X->nrows doubles, device)
 int pmh_svm_csr_row_dots(pmh_csr X, const double *w, double *dots);

@@ -27,6 +27,14 @@
 //
 // One-vs-rest training: the K binary problems "class k against the rest" are trained one after the other on ONE pmh_svm handle over X -- X is uploaded once and
 // the CSR operator's column-ordered copy is built once; pmh_svm_set_labels re-labels the handle between the classes -- and give W (K x d) and b (K).
+//
+// Subsets and the handle's own rows (pmh_svm_multi_set_subset, _predict_own, _test_own): the subset is the binary handle's, which keeps it across the re-labelling,
+// so training over S is the binary handle's SUB = 1 kernels and nothing new here but k_svmm_class_count.  pmh_svm_multi_predict_own runs the sweeps above over the
+// X the binary handle borrows (CSR: the handle's own pmh_csr).  pmh_svm_multi_test_own over the held-out rows or the subset runs the dense sweeps' SEL = 1 instances:
+// the row's selector (n doubles, non-zero = selected: the binary handle's mask, or its complement 1 - m kept here) is read before anything of the row, an
+// unselected row of X is never loaded and nothing is stored for it, and k_svmm_confusion<1> counts the selected rows alone.  Bytes: dense share (8 n d + 8 n)
+// ceil(K / KC) + 8 n ceil(K / KC) (the selector) + 8 n + 16 share n (confusion), share the selected rows' part of n.  CSR: no row skipping, as on the binary
+// handle -- every stored entry is swept and every row written, 12 nnz ceil(K / KC) + 4 n as above, and the selection happens in the confusion kernel alone.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -143,9 +151,16 @@ template <int KC, int LW, class OUT> static __device__ __forceinline__ void svmm
   if (o.scores && live && (l % LPC) == 0 && c < o.kc) o.scores[(size_t)i * o.K + o.k0 + c] = t;
 }
 
-// d == 64: W is the model (K x 64, row-major)
-template <int KC, int UNR, class OUT> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows64(int n, const double *__restrict__ X, const double *__restrict__ W, OUT o)
+// A row selector on the two dense sweeps (pmh_svm_multi_test_own: the held-out rows or the subset of the handle's own samples): the template argument SEL and
+// sel, n doubles, non-zero = the row is selected.  SEL = 0: sel is not read and the code is the sweep without a selector.  SEL = 1: the selector is read before
+// anything of the row; a row that is not selected is not loaded and nothing is stored for it, neither score nor label nor best.  A selected row gets the bits
+// of the SEL = 0 instance: the same loads, products and butterflies, in which every lane takes part whatever its row is.  Instantiated for svmm_out only.
+// d == 64: W is the model (K x 64, row-major).  SEL: the selectors of the 2 UNR rows in flight come in ONE coalesced load and a ballot (svm_live_rows64); a
+// row group without a selected row is passed over (uniform over the wave: the ballot)
+template <int KC, int UNR, class OUT, int SEL = 0>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows64(int n, const double *__restrict__ X, const double *__restrict__ W, OUT o, const double *__restrict__ sel = nullptr)
 {
+  static_assert(!SEL || !OUT::PROBA, "the row selector is for the scoring instances");
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l2 = lane & 31;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   dbl2            wr[KC];
@@ -156,23 +171,33 @@ template <int KC, int UNR, class OUT> __global__ __launch_bounds__(PMH_BLOCK) vo
   double       ca, cb;
   svmm_lane_cal(o, myc, ca, cb);
   for (long long r0 = gw * 2 * UNR; r0 < n; r0 += nw * 2 * UNR) {
-    dbl2 v[UNR];
-    svm_load_rows64<UNR>(n, X, r0, v);
+    dbl2               v[UNR];
+    unsigned long long live = ~0ull; // SEL: bit j says that row r0 + j is selected (0 past the last row)
+    if constexpr (SEL) {
+      double si;
+      live = svm_live_rows64<2 * UNR>(n, sel, r0, si);
+      svm_load_rows64<UNR, 1>(n, X, r0, v, live);
+    } else svm_load_rows64<UNR>(n, X, r0, v);
+    const unsigned lh = SEL ? (unsigned)(live >> half) : ~0u; // bit 2 u: this lane's row of group u is selected (shifted once: a constant bit per u)
 #pragma unroll
     for (int u = 0; u < UNR; u++) {
+      if (SEL && !((live >> (2 * u)) & 3)) continue; // (uniform over the wave)
       const long long i = r0 + 2 * u + half;
       double          s[KC];
 #pragma unroll
       for (int c = 0; c < KC; c++) s[c] = v[u].x * wr[c].x + v[u].y * wr[c].y;
       const double t = svmm_halve<KC, 32>(s, l2);
-      svmm_lanes_done<KC, 32>(o, i, i < n, l2, t, bc, ca, cb);
+      svmm_lanes_done<KC, 32>(o, i, i < n && ((lh >> (2 * u)) & 1), l2, t, bc, ca, cb);
     }
   }
 }
 
-// any d <= 64 SVM_KMAX: W is the model (K x d, row-major)
-template <int KC, class OUT> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ W, OUT o)
+// any d <= 64 SVM_KMAX: W is the model (K x d, row-major).  SEL: the row's selector is uniform over the wave that owns the row, as the masked label is in
+// svm_sweep_rows
+template <int KC, class OUT, int SEL = 0>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_rows(int n, int d, const double *__restrict__ X, const double *__restrict__ W, OUT o, const double *__restrict__ sel = nullptr)
 {
+  static_assert(!SEL || !OUT::PROBA, "the row selector is for the scoring instances");
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long gw = (long long)blockIdx.x * (PMH_BLOCK / 64) + wave, nw = (long long)gridDim.x * (PMH_BLOCK / 64);
   double          wr[KC][SVM_KMAX];
@@ -185,6 +210,7 @@ template <int KC, class OUT> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm
   double       ca, cb;
   svmm_lane_cal(o, myc, ca, cb);
   for (long long i = gw; i < n; i += nw) {
+    if (SEL && sel[i] == 0.0) continue; // (uniform over the wave)
     const double *xr = X + (size_t)i * d;
     double        x[SVM_KMAX], s[KC];
 #pragma unroll
@@ -283,14 +309,24 @@ static __device__ __forceinline__ int svmm_class_index(int K, const double *__re
   return (lo < K && classes[lo] == v) ? lo : K;
 }
 // conf[t K + p]++ for the true class t and the predicted class p of every sample; conf[K K]++ where the true label is no class (counts: integer atomics, any
-// order gives the same integers)
+// order gives the same integers).  SEL: only the samples with sel[i] != 0 (the selector of the dense sweeps); pred of any other sample is not read -- the
+// dense sweeps have stored nothing there
+template <int SEL = 0>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_confusion(int n, int K, const double *__restrict__ classes, const double *__restrict__ pred, const double *__restrict__ ytrue,
-                                                              unsigned long long *__restrict__ conf)
+                                                              unsigned long long *__restrict__ conf, const double *__restrict__ sel = nullptr)
 {
   for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    if (SEL && sel[i] == 0.0) continue;
     const int t = svmm_class_index(K, classes, ytrue[i]), p = svmm_class_index(K, classes, pred[i]);
     atomicAdd(&conf[(t < K && p < K) ? (size_t)t * K + p : (size_t)K * K], 1ull);
   }
+}
+// cnt[k]++ for the class k of every sample inside the subset (msk[i] != 0); cnt[K] stays 0: every training label is a class (integer atomics)
+__global__ __launch_bounds__(PMH_BLOCK) void k_svmm_class_count(int n, int K, const double *__restrict__ classes, const double *__restrict__ labels, const double *__restrict__ msk,
+                                                                unsigned long long *__restrict__ cnt)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK)
+    if (msk[i] != 0.0) atomicAdd(&cnt[svmm_class_index(K, classes, labels[i])], 1ull);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------------------
@@ -306,6 +342,11 @@ struct pmh_svm_multi_s {
   std::vector<long long>     count; // samples per class
   std::vector<pmh_svm_stats> st;    // per class, of the last pmh_svm_multi_train
   int           trained = 0, have_stats = 0;
+  // pmh_svm_multi_set_subset: the mask itself is the binary handle's (pmh_svm_own_samples); here the subset's size (0: no subset), its samples per class and
+  // the complement 1 - m (n doubles, device: the selector of the held-out rows; allocated by the first subset)
+  long long              n_sub = 0;
+  std::vector<long long> count_sub;
+  double                *cmsk = nullptr;
   // the probability model of the current (W, b): the classes' Platt pairs (svm_proba.hip); a new model clears it
   int                              calibrated = 0;
   double                          *cal = nullptr; // device: A (K) then B (K)
@@ -324,7 +365,7 @@ extern "C" int pmh_svm_multi_destroy(pmh_svm_multi m)
 {
   if (!m) return PMH_SUCCESS;
   if (m->bin) pmh_svm_destroy(m->bin);
-  double *v[] = {m->y, m->W, m->Wt, m->b, m->classes, m->cal};
+  double *v[] = {m->y, m->W, m->Wt, m->b, m->classes, m->cal, m->cmsk};
   for (double *p : v)
     if (p) pmh_free(m->ctx, p);
   delete m;
@@ -389,10 +430,10 @@ extern "C" int pmh_svm_multi_create_csr(pmh_ctx ctx, pmh_csr X, const double *la
   return svmm_create(ctx, X->nrows, X->ncols, nullptr, X, labels_dev, opts, balanced, out);
 }
 
-// the penalties of the binary problem of class k
+// the penalties of the binary problem of class k: the counts over the samples that train, n_S and n_{k,S} under a subset
 static void svmm_penalties(pmh_svm_multi m, int k, double *C_pos, double *C_neg)
 {
-  const double C = m->o.C, n = (double)m->n, nk = (double)m->count[(size_t)k];
+  const double C = m->o.C, n = (double)(m->n_sub ? m->n_sub : m->n), nk = (double)(m->n_sub ? m->count_sub[(size_t)k] : m->count[(size_t)k]);
   *C_pos = m->balanced ? C * n / (2.0 * nk) : C;
   *C_neg = m->balanced ? C * n / (2.0 * (n - nk)) : C;
 }
@@ -461,6 +502,59 @@ extern "C" int pmh_svm_multi_set_model(pmh_svm_multi m, const double *W_host, co
   return PMH_SUCCESS;
 }
 
+// ---- sample subsets ----------------------------------------------------------------------------------------------------------------------------------------
+// Train the K problems on the subset S of the handle's samples (the binary handle's pmh_svm_set_subset, which pmh_svm_set_labels and pmh_svm_set_penalties
+// keep).  The classes stay those of all training labels; a class without a sample in S is refused before anything changes, as is whatever the binary handle
+// refuses, which changes nothing either
+extern "C" int pmh_svm_multi_set_subset(pmh_svm_multi m, const double *m_dev)
+{
+  PMH_ARG(m);
+  pmh_ctx ctx = m->ctx;
+  const int n = m->n, K = m->K;
+  if (!m_dev) {
+    PMH_CHK(pmh_svm_set_subset(m->bin, nullptr));
+    m->n_sub = 0, m->count_sub.clear();
+    m->trained = m->have_stats = m->calibrated = 0;
+    return PMH_SUCCESS;
+  }
+  std::vector<long long> cnt((size_t)K + 1, 0);
+  unsigned long long    *d_cnt = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(unsigned long long) * cnt.size(), (void **)&d_cnt));
+  int rc = pmh_memset(ctx, d_cnt, 0, sizeof(unsigned long long) * cnt.size());
+  if (!rc) {
+    hipLaunchKernelGGL(k_svmm_class_count, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, K, (const double *)m->classes, m->labels, m_dev, d_cnt);
+    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_multi_set_subset: the launch that counts the classes failed");
+  }
+  if (!rc) rc = pmh_memcpy_d2h(ctx, cnt.data(), d_cnt, sizeof(long long) * cnt.size());
+  pmh_free(ctx, d_cnt);
+  PMH_CHK(rc);
+  for (int k = 0; k < K; k++)
+    if (cnt[(size_t)k] == 0)
+      return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_set_subset: the subset holds no sample of class %g (class %d of %d): its problem against the rest has no positive sample", m->h_classes[(size_t)k],
+                           k, K);
+  if (!m->cmsk) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&m->cmsk));
+  PMH_CHK(pmh_svm_set_subset(m->bin, m_dev)); // (checks the mask before anything changes)
+  m->trained = m->have_stats = m->calibrated = 0;
+  cnt.resize((size_t)K);
+  m->count_sub = cnt;
+  m->n_sub     = 0;
+  for (long long c : cnt) m->n_sub += c;
+  // the selector of the held-out rows: 1 - m from the mask the binary handle holds now
+  const double *msk = nullptr;
+  pmh_svm_own_samples(m->bin, nullptr, nullptr, nullptr, &msk);
+  PMH_CHK(pmh_vec_set(ctx, n, m->cmsk, 1.0));
+  return pmh_vec_axpy(ctx, n, m->cmsk, -1.0, msk);
+}
+
+extern "C" int pmh_svm_multi_get_subset(pmh_svm_multi m, double *m_dev, long long *n_in, long long *class_counts_host)
+{
+  PMH_ARG(m);
+  if (m_dev) PMH_CHK(pmh_svm_get_subset(m->bin, m_dev, nullptr));
+  if (n_in) *n_in = m->n_sub ? m->n_sub : m->n;
+  if (class_counts_host) memcpy(class_counts_host, (m->n_sub ? m->count_sub : m->count).data(), sizeof(long long) * (size_t)m->K);
+  return PMH_SUCCESS;
+}
+
 extern "C" int pmh_svm_multi_get_stats(pmh_svm_multi m, int k, pmh_svm_stats *st, double *C_pos, double *C_neg)
 {
   PMH_ARG(m && k >= 0 && k < m->K);
@@ -475,10 +569,17 @@ extern "C" int pmh_svm_multi_get_stats(pmh_svm_multi m, int k, pmh_svm_stats *st
   return PMH_SUCCESS;
 }
 
-// the launches of one chunk of classes on the instances of OUT
-template <class OUT> static void svmm_launch_chunk(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const svc_tab &t, int ch, const OUT &o)
+// the launches of one chunk of classes on the instances of OUT.  sel (dense rows, scoring only): the SEL = 1 instances, which sweep the selected rows alone
+template <class OUT> static void svmm_launch_chunk(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const svc_tab &t, int ch, const OUT &o, const double *sel = nullptr)
 {
   pmh_ctx ctx = m->ctx;
+  if constexpr (!OUT::PROBA) {
+    if (!Xt && sel) {
+      if (m->d == 64) hipLaunchKernelGGL((k_svmm_rows64<SVMM_KC64, 4, OUT, 1>), dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, X, (const double *)m->W, o, sel);
+      else hipLaunchKernelGGL((k_svmm_rows<SVMM_KCD, OUT, 1>), dim3(SVM_NB(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->d, X, (const double *)m->W, o, sel);
+      return;
+    }
+  }
   if (Xt) {
     const int nb = t.nb;
     hipLaunchKernelGGL((k_svmm_seg<SVMM_KCC, OUT>), dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, (int)Xt->nnz, n, nb, (const int *)Xt->d_rowptr, (const int *)Xt->d_col, (const double *)Xt->d_val,
@@ -490,7 +591,9 @@ template <class OUT> static void svmm_launch_chunk(pmh_svm_multi m, int n, const
 }
 
 // X (dense rows, n x d) or Xt (CSR): one sweep per chunk of classes, chunks ascending.  proba: scores receives the classes' sigmoids (m->cal), labels is nullptr
-static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *scores, double *labels, bool proba = false)
+// sel (n doubles, or nullptr: every row): dense rows are swept, and scores, labels and best written, only where sel[i] != 0; CSR has no row skipping, as on
+// the binary handle: every stored entry is swept and every row written, and the selection is k_svmm_confusion's alone
+static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *scores, double *labels, bool proba = false, const double *sel = nullptr)
 {
   PMH_ARG(m && n >= 0 && (X || Xt || n == 0));
   if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_predict: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
@@ -509,7 +612,7 @@ static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, dou
       static_cast<svmm_out &>(op) = o;
       op.A = m->cal, op.B = m->cal + m->K;
       svmm_launch_chunk(m, n, X, Xt, t, ch, op);
-    } else svmm_launch_chunk(m, n, X, Xt, t, ch, o);
+    } else svmm_launch_chunk(m, n, X, Xt, t, ch, o, sel);
     if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_multi_predict: the launch failed");
   }
   if (Xt) svc_tab_free(ctx, &t); // (waits for the stream)
@@ -525,7 +628,8 @@ extern "C" int pmh_svm_multi_predict_csr(pmh_svm_multi m, pmh_csr Xt, double *sc
   return svmm_predict(m, Xt->nrows, nullptr, Xt, scores_dev, labels_dev);
 }
 
-static int svmm_test(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *ytrue, long long *confusion, long long *n_unknown)
+// sel: the rows that are scored (dense) and counted, or nullptr: every row
+static int svmm_test(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *ytrue, long long *confusion, long long *n_unknown, const double *sel = nullptr)
 {
   PMH_ARG(m && ytrue && confusion && n >= 0);
   pmh_ctx             ctx = m->ctx;
@@ -535,9 +639,10 @@ static int svmm_test(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const 
   PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)(n ? n : 1), (void **)&pred));
   int rc = pmh_malloc(ctx, sizeof(unsigned long long) * nc, (void **)&conf);
   if (!rc) rc = pmh_memset(ctx, conf, 0, sizeof(unsigned long long) * nc);
-  if (!rc) rc = svmm_predict(m, n, X, Xt, nullptr, pred);
+  if (!rc) rc = svmm_predict(m, n, X, Xt, nullptr, pred, false, sel);
   if (!rc && n > 0) {
-    hipLaunchKernelGGL(k_svmm_confusion, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->K, (const double *)m->classes, (const double *)pred, ytrue, conf);
+    if (sel) hipLaunchKernelGGL(k_svmm_confusion<1>, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->K, (const double *)m->classes, (const double *)pred, ytrue, conf, sel);
+    else hipLaunchKernelGGL(k_svmm_confusion<0>, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->K, (const double *)m->classes, (const double *)pred, ytrue, conf);
     if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_multi_test: the launch failed");
   }
   std::vector<long long> h(nc, 0);
@@ -559,6 +664,39 @@ extern "C" int pmh_svm_multi_test_csr(pmh_svm_multi m, pmh_csr Xt, const double 
 {
   PMH_ARG(m && Xt);
   return svmm_test(m, Xt->nrows, nullptr, Xt, labels_true_dev, confusion, n_unknown);
+}
+
+// ---- the handle's own samples ------------------------------------------------------------------------------------------------------------------------------
+// nothing uploaded: the scoring sweeps over the X the binary handle borrows, or over the handle's own pmh_csr
+extern "C" int pmh_svm_multi_predict_own(pmh_svm_multi m, double *scores_dev, double *labels_dev)
+{
+  PMH_ARG(m);
+  const void *X    = nullptr;
+  pmh_csr     Xcsr = nullptr;
+  pmh_svm_own_samples(m->bin, &X, nullptr, &Xcsr, nullptr);
+  return svmm_predict(m, m->n, (const double *)X, Xcsr, scores_dev, labels_dev);
+}
+
+// the confusion matrix of the own samples against the training labels over the held-out rows, the subset or all rows.  Dense: the unselected rows of X are
+// not loaded (the SEL = 1 sweeps); CSR: all rows are scored and the confusion kernel selects
+extern "C" int pmh_svm_multi_test_own(pmh_svm_multi m, int which, long long *confusion, long long *n_counted)
+{
+  PMH_ARG(m && confusion);
+  if (which != PMH_SVM_OWN_HELD_OUT && which != PMH_SVM_OWN_SUBSET && which != PMH_SVM_OWN_ALL)
+    return pmh_set_error(PMH_ERR_ARG, "pmh_svm_multi_test_own: which = %d (PMH_SVM_OWN_HELD_OUT | PMH_SVM_OWN_SUBSET | PMH_SVM_OWN_ALL)", which);
+  const void   *X    = nullptr;
+  pmh_csr       Xcsr = nullptr;
+  const double *msk  = nullptr;
+  pmh_svm_own_samples(m->bin, &X, nullptr, &Xcsr, &msk);
+  if (which == PMH_SVM_OWN_HELD_OUT && !msk) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_test_own: no subset is set (pmh_svm_multi_set_subset), so no sample is held out");
+  const double *sel = (which == PMH_SVM_OWN_ALL || !msk) ? nullptr : (which == PMH_SVM_OWN_SUBSET ? msk : (const double *)m->cmsk);
+  long long     unk = 0;
+  PMH_CHK(svmm_test(m, m->n, (const double *)X, Xcsr, m->labels, confusion, &unk, sel));
+  if (n_counted) {
+    *n_counted = unk; // (0: every training label is a class)
+    for (size_t j = 0; j < (size_t)m->K * m->K; j++) *n_counted += confusion[j];
+  }
+  return PMH_SUCCESS;
 }
 
 // ---- probabilities (Platt scaling, svm_proba.hip) ---------------------------------------------------------------------------------------------------------------

@@ -652,6 +652,14 @@ extern "C" int pmh_svm_get_subset(pmh_svm s, double *m_dev, long long *n_in)
   return H->msk ? pmh_vec_copy(s->ctx, s->n, H->msk, m_dev) : pmh_vec_set(s->ctx, s->n, m_dev, 1.0);
 }
 
+void pmh_svm_own_samples(pmh_svm s, const void **X, int *f32, pmh_csr *Xcsr, const double **msk)
+{
+  if (X) *X = s->X;
+  if (f32) *f32 = s->f32;
+  if (Xcsr) *Xcsr = s->Xcsr;
+  if (msk) *msk = static_cast<SvmDualBase *>(s->H)->msk;
+}
+
 // X (dense rows, n x d: doubles, or floats where f32 -- the test samples' type, whatever the handle was trained on) or Xt (CSR)
 // own: the handle's own samples (X or, CSR, the operator's tables: Xt == nullptr); sel: which of them the counts are taken over
 static int svm_predict(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts, bool own = false, svm_sel sel = svm_sel())

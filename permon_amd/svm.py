@@ -429,6 +429,39 @@ class SVMMulticlass(_SVMHandle):
     def fit(self, X, labels):
         return self.create(X, labels).train()
 
+    def set_subset(self, mask):
+        """Train the K problems on the samples where mask is true, X staying on the device (pmh_svm_multi_set_subset): n booleans or 0 / 1 numbers; None: all
+        samples again.  The classes stay those of all labels; a mask that leaves a class without a sample is refused (PMH_ERR_ARG) and the handle stays as it
+        was.  The handle is untrained and uncalibrated afterwards; set_model keeps the subset.  balanced: the penalties follow the counts over the subset.
+        decision_function_own / predict_own / test_own score the handle's own samples without an upload."""
+        self._need()
+        if mask is None:
+            check(self.L.pmh_svm_multi_set_subset(self.h, None))
+            return self
+        m = np.ascontiguousarray(mask, dtype=np.float64).ravel()
+        if m.size != self.n:
+            raise ValueError("SVMMulticlass: the mask must have %d entries" % self.n)
+        with self._lent(m) as md:
+            check(self.L.pmh_svm_multi_set_subset(self.h, md.p))
+        return self
+
+    @property
+    def subset(self):
+        """The training mask as n booleans (pmh_svm_multi_get_subset), or None where all samples train."""
+        self._need()
+        with _vecs(self.ctx, self.n) as (v,):
+            check(self.L.pmh_svm_multi_get_subset(self.h, v.p, None, None))
+            m = v.to_numpy() != 0.0
+        return None if m.all() else m
+
+    @property
+    def subset_class_counts(self):
+        """(K,) int64: the samples of each class inside the subset; over all samples where no subset is set."""
+        self._need()
+        c = np.zeros(self.K, dtype=np.int64)
+        check(self.L.pmh_svm_multi_get_subset(self.h, None, None, c.ctypes.data_as(ct.c_void_p)))
+        return c
+
     @property
     def classes_(self):
         self._need()
@@ -560,6 +593,36 @@ class SVMMulticlass(_SVMHandle):
         n = X.shape[0]
         return dict(accuracy=float(np.trace(conf)) / n if n else float("nan"), confusion=conf, n_unknown=unk)
 
+    def _run_own(self, want_scores, want_labels):
+        self._need()
+        n = self.n
+        with _vecs(self.ctx, n * self.K if want_scores else None, n if want_labels else None) as (s, l):
+            check(self.L.pmh_svm_multi_predict_own(self.h, s.p if s else None, l.p if l else None))
+            return (s.to_numpy().reshape(n, self.K) if s else None, l.to_numpy() if l else None)
+
+    def decision_function_own(self):
+        """(n, K): the scores of the samples the handle was created on, held-out ones included, without an upload (pmh_svm_multi_predict_own): bit for bit
+        decision_function(X)."""
+        return self._run_own(True, False)[0]
+
+    def predict_own(self):
+        """(n,): the labels of the handle's own samples, bit for bit predict(X)."""
+        return self._run_own(False, True)[1]
+
+    OWN = SVM.OWN  # PMH_SVM_OWN_*
+
+    def test_own(self, which="held_out"):
+        """The handle's own samples against its training labels over the held-out samples, the subset or all of them (pmh_svm_multi_test_own), nothing
+        uploaded; dense samples that are not selected are not read.  -> dict(accuracy, confusion, n): confusion as test returns it, n the samples counted,
+        accuracy = trace / n."""
+        self._need()
+        if which not in self.OWN:
+            raise ValueError("SVMMulticlass: which must be one of %s" % ", ".join(sorted(self.OWN)))
+        conf, n = np.zeros((self.K, self.K), dtype=np.int64), ct.c_longlong()
+        check(self.L.pmh_svm_multi_test_own(self.h, self.OWN[which], conf.ctypes.data_as(ct.c_void_p), ct.byref(n)))
+        n = int(n.value)
+        return dict(accuracy=float(np.trace(conf)) / n if n else float("nan"), confusion=conf, n=n)
+
 
 def kfold(y, k, seed=0, stratified=True):
     """k boolean training masks over the samples of y whose complements (the folds) partition them.  One seeded shuffle, then the samples are dealt to the
@@ -582,7 +645,9 @@ def kfold(y, k, seed=0, stratified=True):
 def cross_validate(svm, k=5, seed=0, stratified=True):
     """k-fold cross-validation on a created SVM handle, X uploaded once (CSR: one column-ordered copy): for every mask of kfold(y, k, seed, stratified)
     set_subset, train, test_own("held_out").  -> dict(folds: the k dicts of test_own, accuracy: their mean accuracy, masks).  The handle gets back the subset
-    it had and is left untrained."""
+    it had and is left untrained.  An SVMMulticlass handle is cross-validated the same way, the masks stratified over its K classes, and the result has
+    confusion, the sum of the folds' K x K matrices, as well; a class of one sample leaves one fold's training set without it, and set_subset's PMH_ERR_ARG
+    comes through (the subset is still restored)."""
     svm._need()
     before = svm.subset
     y = svm._keep[1].to_numpy()
@@ -593,7 +658,10 @@ def cross_validate(svm, k=5, seed=0, stratified=True):
             folds.append(svm.set_subset(m).train().test_own("held_out"))
     finally:
         svm.set_subset(before)
-    return dict(folds=folds, accuracy=float(np.mean([f["accuracy"] for f in folds])), masks=masks)
+    out = dict(folds=folds, accuracy=float(np.mean([f["accuracy"] for f in folds])), masks=masks)
+    if isinstance(svm, SVMMulticlass):
+        out["confusion"] = sum(f["confusion"] for f in folds)
+    return out
 
 
 SCORES = ("accuracy", "precision", "recall", "specificity", "f1", "balanced_accuracy", "mcc")
