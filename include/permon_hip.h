@@ -1041,6 +1041,68 @@ int pmh_csr_test_mult_epi(pmh_csr A, int kind, const double *x, const double *y1
 int pmh_op_penalized_test_mult_epi(pmh_op op, int kind, int same_input, const double *x, const double *b, const double *lb, double astol, double *y, double *gf, double *p, int cap,
                                    double *partials_host, double *psums_host, int *nblocks, int *nseg);
 int pmh_op_penalized_test_emit(pmh_op op, int what, const double *x);
+/* ---- test entries of the MPGP phase kernels and the reduction finishers (csrc/mpgp.hip, csrc/vec.hip, csrc/emit_inline.h; nothing inside the solvers changes) ------
+ * They overwrite the context's block partials and scalar slots, which every solve writes before it reads them.  All of them synchronise.
+ * pmh_vec_test_finalize: ONE launch of k_finalize on K <= 8 caller-chosen rows (rows_host[K][nblocks], nblocks <= 2048), quantity k reduced with ops[k] (0 SUM, 1 MIN)
+ * into scalar slot slots[k] (0..63).  scal_dev / scal_pinned [K]: in, what the device slot / its pinned mirror hold before the launch; out, what they hold afterwards.
+ * halt < 0: no halt word, else a device word of that value.  post_inc (or NULL): the two device counters the launch bumps, in / out.
+ * pmh_mpgp_test_host_sum_row: the host's own last step of a reduction (host_sum_row of mpgp.hip) on row[nb], nb <= 512, op 0 SUM / 1 MIN.
+ * pmh_mpgp_test_block_sum: pmh_sum_block_partials of row_host[nb] (nb <= 512) in one wave; out_host[64] = what every lane returns.
+ * pmh_mpgp_test_block_partials: pmh_block_partials<3> with (SUM, SUM, MIN) in workgroups of 1024 threads, thread t of workgroup b holding entry 1024 b + t of the
+ * device vectors a, b, c (past the end: 0, 0, +inf); dev_host / pinned_host [3][nblocks]: in, what the device rows / the pinned rows hold before; out, afterwards.
+ * pmh_mpgp_test_phase: ONE launch of the phase kernel `phase` on the caller's device vectors (see the struct), as solve_fused / solve_unfused launch it.
+ * pmh_mpgp_test_set_gradient_valid: the carried gradient as SMALXE hands it over (fused driver only): g (device, n doubles) is copied into the solver's gradient vector
+ * and the NEXT pmh_mpgp_solve takes it as A x - b at its starting point instead of forming it.
+ * pmh_mpgp_test_spec_words: after a solve, words[0] = 1 where the solver set up the speculative device-side CG chain (only where it may use it), words[1..4] = halt,
+ * iteration, ncg, base as the last batch left them. */
+typedef struct {
+  double       *x, *g, *p, *Ap, *gf;  /* device vectors of n entries; a phase touches those its kernel takes (phase 6: gP = x, gc = g) */
+  const double *lb, *ub, *b;          /* device; lb / ub may be NULL; b: phase 7 */
+  pmh_op        op;                   /* emit: NULL, the emission targets are off; else a penalised operator on the dual-space chain, asked for them through emit_begin as the driver asks */
+  double       *partials_dev, *partials_pinned; /* HOST [8][2048]: in, the block partials on the device / in the pinned copy before the launch; out, afterwards */
+  double        astol, afeas, alpha, acg_host, pAp_host;
+  double        ttol, divtol_rhs, gamma2;       /* SPEC: the constants of pmh_spec_args */
+  double        ring[48];                       /* SPEC: the monitor ring, in / out */
+  double        scal_dev[64], scal_pinned[64];  /* in, every scalar slot on the device / in the pinned mirror before the launch; out, afterwards */
+  int           emit;     /* 1: the 1024-thread variant */
+  int           spec;     /* phase 1: the device-side verdict (needs use_ctl, setp = 0, emit = 0) */
+  int           setp;     /* phase 1: the proportioning form (p = gf) */
+  int           finalize; /* 1: followed by the driver's finalising launch of that phase (phases 0, 1, 5, 6, 7) */
+  int           use_ctl;  /* 1: the control words go to the device; phases 1 (SPEC), 2 and the finalising launch run under ctl[0] and bump ctl[1], ctl[2] */
+  int           nb;       /* emit: block partials to add -- phase 1 (rows 4, 5: acg; 0: acg_host), phase 2 (row 0) */
+  int           ring_cap, max_it;
+  int           ctl[4];   /* halt, iteration, ncg, base: in / out */
+} pmh_mpgp_phase_test;
+enum { PMH_PHASE_SPLIT = 0, PMH_PHASE_STEP, PMH_PHASE_DIR, PMH_PHASE_PROP_DIR, PMH_PHASE_EXPANSION, PMH_PHASE_P1_DOTS, PMH_PHASE_THREE_NORMS, PMH_PHASE_OBJ };
+int pmh_vec_test_finalize(pmh_ctx ctx, int K, int nblocks, const double *rows_host, const int *ops, const int *slots, int halt, int *post_inc, double *scal_dev, double *scal_pinned);
+int pmh_mpgp_test_host_sum_row(const double *row, int nb, int op, double *out);
+int pmh_mpgp_test_block_sum(pmh_ctx ctx, int nb, const double *row_host, double *out_host);
+int pmh_mpgp_test_block_partials(pmh_ctx ctx, int n, const double *a, const double *b, const double *c, double *dev_host, double *pinned_host);
+int pmh_mpgp_test_phase(pmh_ctx ctx, int phase, int n, pmh_mpgp_phase_test *t);
+int pmh_mpgp_test_set_gradient_valid(pmh_mpgp s, const double *g);
+int pmh_mpgp_test_spec_words(pmh_mpgp s, int words[5]);
+/* ---- further test entries of the dual-space chain (csrc/dualchain.hip, csrc/qppf.hip) -----------------------------------------------------------------------------
+ * pmh_op_test_create_staged: F = scatter middle gather from three device CSR matrices (gather nmid x n, middle nmid x nmid, scatter n x nmid) as an operator that
+ * answers pmh_op_s::stages, its middle stage pmh_csr_mult; its plain product is the three products.  Under pmh_op_create_penalized(pmh_op_create_projected(F, pf, 1),
+ * pf, rho) with an implicitly orthonormalised pf it runs on the chain.  Destroyed by pmh_op_destroy; the matrices stay the caller's.
+ * pmh_op_penalized_test_chain_info: info = {n, m, tiles, segments, W (8 / 16), NU (2 / 8), listed gather rows, records with a partner row, gather rows with more than
+ * 3 entries, scatter rows with more than 2 entries}.  PMH_ERR_SUP where the operator does not run on the chain.
+ * pmh_op_penalized_test_chain_read: what 0..2 the segment sums of the iterate's, the direction's and the scratch target; 3 c = S G0 x [m]; 4 mid_in; 5 mid_out;
+ * 6 [w; the segment sums of G0 w]; 7 the norm target's T G0 u [m]; 8 its scalar slot on the device and in the pinned mirror [2]; 9 S [m m]; 10 T' [m m] -> host[*len],
+ * *len <= cap.
+ * pmh_op_penalized_test_norm_target: Gu != NULL: T G0 u of every emitted iterate -> Gu (device, m doubles), its squared norm -> scalar slot `slot`; Gu == NULL:
+ * *ready = whether both hold the values of the device vector u (one small launch forms them where the sums wait and no application followed); synchronises.
+ * pmh_op_penalized_test_mult_epi2: pmh_op_penalized_test_mult_epi with every operand: kind 0, 1 (P1: x = p, y = Ap, operands g, xx, lb, ub; block partials in rows
+ * 4..6) or 2 (gradient split: operands b, lb, ub, astol; rows 0..3), in_slot 0 (the chain forms G0 x itself), 1 / 2 (the iterate's / the direction's target holds
+ * it).  partials_*_host [8][2048]: in, the block partials on the device / in the pinned copy before; out, afterwards.  *nblocks: blocks the last kernel wrote;
+ * *replayed: 1 where the last kernel ran alone. */
+int pmh_op_test_create_staged(pmh_csr gather, pmh_csr middle, pmh_csr scatter, pmh_op *op);
+int pmh_op_penalized_test_chain_info(pmh_op op, long long info[10]);
+int pmh_op_penalized_test_chain_read(pmh_op op, int what, int cap, double *host, int *len);
+int pmh_op_penalized_test_norm_target(pmh_op op, double *Gu, int slot, const double *u, int *ready);
+int pmh_op_penalized_test_mult_epi2(pmh_op op, int kind, int same_input, int in_slot, const double *x, const double *b, const double *g, const double *xx, const double *lb,
+                                    const double *ub, double astol, double *y, double *gf, double *p, double *partials_dev_host, double *partials_pinned_host, int *nblocks,
+                                    int *replayed);
 /* ---- 3x3-block product test entries (csrc/bsr.hip: the conversion as the V-cycle and K^+ call it, and one launch of k_bsr3; nothing inside the solvers changes) ----
  * pmh_bsr3_test_create: the 3x3-block device copy of the square CSR A with entries kept in `storage` (0 fp64, 1 fp32, 2 fp16 scaled by a power of two, fp32
  * arithmetic), tiles of `tile` blocks (512; any other value: 1024) and nrep_hint congruent diagonal blocks (believed only after an entry-by-entry comparison).

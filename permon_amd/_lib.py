@@ -118,6 +118,13 @@ class PcpgStats(C.Structure):
     _fields_ = [("iteration", C.c_int), ("reason", C.c_int), ("rnorm", C.c_double)]
 
 
+class MpgpPhaseTest(C.Structure):  # pmh_mpgp_phase_test
+    _fields_ = [(k, vp) for k in ("x", "g", "p", "Ap", "gf", "lb", "ub", "b", "op", "partials_dev", "partials_pinned")] + \
+               [(k, C.c_double) for k in ("astol", "afeas", "alpha", "acg_host", "pAp_host", "ttol", "divtol_rhs", "gamma2")] + \
+               [("ring", C.c_double * 48), ("scal_dev", C.c_double * 64), ("scal_pinned", C.c_double * 64)] + \
+               [(k, C.c_int) for k in ("emit", "spec", "setp", "finalize", "use_ctl", "nb", "ring_cap", "max_it")] + [("ctl", C.c_int * 4)]
+
+
 SHELL_MULT_FN = C.CFUNCTYPE(C.c_int, vp, vp, vp)
 CONVERGED_FN = C.CFUNCTYPE(C.c_int, vp, C.c_int, C.c_double, c_int_p)
 
@@ -354,6 +361,18 @@ _PROTOS = {
     "pmh_csr_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, c_double_p],
     "pmh_op_penalized_test_mult_epi": [vp, C.c_int, C.c_int, vp, vp, vp, C.c_double, vp, vp, vp, C.c_int, vp, vp, c_int_p, c_int_p],
     "pmh_op_penalized_test_emit": [vp, C.c_int, vp],
+    "pmh_vec_test_finalize": [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp],
+    "pmh_mpgp_test_host_sum_row": [vp, C.c_int, C.c_int, c_double_p],
+    "pmh_mpgp_test_block_sum": [vp, C.c_int, vp, vp],
+    "pmh_mpgp_test_block_partials": [vp, C.c_int, vp, vp, vp, vp, vp],
+    "pmh_mpgp_test_phase": [vp, C.c_int, C.c_int, C.POINTER(MpgpPhaseTest)],
+    "pmh_mpgp_test_set_gradient_valid": [vp, vp],
+    "pmh_mpgp_test_spec_words": [vp, c_int_p],
+    "pmh_op_test_create_staged": [vp, vp, vp, C.POINTER(vp)],
+    "pmh_op_penalized_test_chain_info": [vp, C.POINTER(C.c_longlong)],
+    "pmh_op_penalized_test_chain_read": [vp, C.c_int, C.c_int, vp, c_int_p],
+    "pmh_op_penalized_test_norm_target": [vp, vp, C.c_int, vp, c_int_p],
+    "pmh_op_penalized_test_mult_epi2": [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, c_int_p, c_int_p],
     "pmh_bsr3_test_create": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
     "pmh_bsr3_test_info": [vp, C.POINTER(C.c_longlong), c_double_p],
     "pmh_bsr3_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int],

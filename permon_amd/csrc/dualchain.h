@@ -25,3 +25,6 @@ int  pmh_dc_set_norm_target(pmh_dualchain dc, double *Gu, int slot);
 bool pmh_dc_norm_ready(pmh_dualchain dc, const double *u);
 // launches of the last application (tests, bench)
 int  pmh_dc_last_launches(pmh_dualchain dc);
+// test entries: what the chain planned; what one application left behind (see dualchain.hip)
+int  pmh_dc_test_info(pmh_dualchain dc, long long info[10]);
+int  pmh_dc_test_read(pmh_dualchain dc, int what, int cap, double *host, int *len);

@@ -535,6 +535,9 @@ void pmh_dc_destroy(pmh_dualchain dc)
   delete dc;
 }
 
+// loads per lane of pmh_coarse_share: 64 NU >= the number of tiles.  The three dispatches below and the info entry share it
+static int dc_nu(pmh_dualchain dc) { return dc->nwg <= 128 ? 2 : 8; }
+
 static pmh_emit_tab dc_tab(pmh_dualchain dc)
 {
   pmh_emit_tab t;
@@ -575,7 +578,7 @@ bool pmh_dc_norm_ready(pmh_dualchain dc, const double *u)
   if (!dc || !dc->normGu) return false;
   if (dc->norm_ptr == u) return true;
   if (dc->x_emitted == u && !dc->norm_done) {
-    if (dc->nwg <= 128)
+    if (dc_nu(dc) == 2)
       hipLaunchKernelGGL(k_dc_norm<2>, dim3(1), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc_tab(dc), (const double *)dc->part[0], (const double *)dc->pf->d_Tt,
                          dc->normGu, dc->ctx->d_scal + dc->norm_slot,
                          dc->ctx->h_scal + dc->norm_slot);
@@ -617,9 +620,9 @@ static int dc_last_stage(pmh_dualchain dc, const double *x, double *y, double rh
                      (const double *)dc->c_cur, (const double *)dc->w, rho, y, e, x, ea)
 #define DC_FINAL_W(EPI)                                                                                                                                                              \
   do {                                                                                                                                                                               \
-    if (dc->W == 8 && dc->nwg <= 128) DC_FINAL(EPI, 8, 2);                                                                                                                           \
+    if (dc->W == 8 && dc_nu(dc) == 2) DC_FINAL(EPI, 8, 2);                                                                                                                              \
     else if (dc->W == 8) DC_FINAL(EPI, 8, 8);                                                                                                                                        \
-    else if (dc->nwg <= 128) DC_FINAL(EPI, 16, 2);                                                                                                                                   \
+    else if (dc_nu(dc) == 2) DC_FINAL(EPI, 16, 2);                                                                                                                                      \
     else DC_FINAL(EPI, 16, 8);                                                                                                                                                       \
   } while (0)
   if (kind == PMH_VEPI_P1) DC_FINAL_W(PMH_VEPI_P1);
@@ -671,9 +674,9 @@ int pmh_dc_apply(pmh_dualchain dc, const double *x, double *y, double rho, const
 #define DC_GATHER(WW, NU)                                                                                                                                                                       \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dc_gather<WW, NU>), ggrid, eblk, 0, st, dc->nlist, (const int *)dc->d_reci, (const double *)dc->d_recd, (const int *)Bg->d_col, (const double *)Bg->d_val, \
                      (const double *)dc->d_ev, (const unsigned char *)dc->d_ec, tab, (const double *)dc->part[slot], (const double *)dc->pf->d_S, dc->c_cur, na, x, dc->mid_in)
-    if (dc->W == 8 && dc->nwg <= 128) DC_GATHER(8, 2);
+    if (dc->W == 8 && dc_nu(dc) == 2) DC_GATHER(8, 2);
     else if (dc->W == 8) DC_GATHER(8, 8);
-    else if (dc->nwg <= 128) DC_GATHER(16, 2);
+    else if (dc_nu(dc) == 2) DC_GATHER(16, 2);
     else DC_GATHER(16, 8);
 #undef DC_GATHER
     dc->launches++;
@@ -758,4 +761,83 @@ int pmh_dc_test_direction_sums(pmh_dualchain dc, int cap, double *host, int *nse
   PMH_ARG(host && nseg && cap >= dc->nseg);
   *nseg = dc->nseg;
   return pmh_memcpy_d2h(dc->ctx, host, dc->part[1], sizeof(double) * (size_t)dc->nseg);
+}
+// what the chain planned: {n, m, nwg, nseg, W, NU, nlist, records with a partner row, gather rows with more than 3 entries, scatter rows with more than 2 entries}
+int pmh_dc_test_info(pmh_dualchain dc, long long info[10])
+{
+  pmh_ctx ctx = dc->ctx;
+  PMH_CHK(dc->F->stages(&dc->gather, &dc->mid_in, &dc->scatter, &dc->mid_out));
+  PMH_CHK(dc_prepare_stages(dc));
+  std::vector<int>           reci((size_t)8 * dc->nlist);
+  std::vector<unsigned char> cnt((size_t)dc->n);
+  PMH_CHK(pmh_memcpy_d2h(ctx, reci.data(), dc->d_reci, sizeof(int) * reci.size()));
+  PMH_CHK(pmh_memcpy_d2h(ctx, cnt.data(), dc->d_scnt, cnt.size()));
+  long long np = 0, n3 = 0, n2 = 0;
+  for (int i = 0; i < dc->nlist; i++) np += reci[(size_t)8 * i + 1] >= 0, n3 += reci[(size_t)8 * i + 3] - reci[(size_t)8 * i + 2] > 3;
+  for (int r = 0; r < dc->n; r++) n2 += cnt[r] > 2;
+  const long long v[10] = {dc->n, dc->m, dc->nwg, dc->nseg, dc->W, dc_nu(dc), dc->nlist, np, n3, n2};
+  for (int k = 0; k < 10; k++) info[k] = v[k];
+  return PMH_SUCCESS;
+}
+// what one application leaves behind -- what 0..2: the segment sums of the three targets; 3: c_cur [m]; 4: mid_in; 5: mid_out; 6: [w; the sums of G0 w]; 7: the norm
+// target's T G0 u [m]; 8: its scalar slot on the device and in the pinned mirror [2]; 9: S [m m]; 10: T' [m m]
+int pmh_dc_test_read(pmh_dualchain dc, int what, int cap, double *host, int *len)
+{
+  PMH_ARG(host && len && what >= 0 && what <= 10);
+  PMH_ARG(what < 4 || what > 6 || what == 6 || (dc->gather && dc->scatter));
+  PMH_ARG((what != 7 && what != 8) || dc->normGu);
+  pmh_ctx       ctx = dc->ctx;
+  const int     m = dc->m;
+  const double *src[11] = {dc->part[0], dc->part[1], dc->part[2], dc->c_cur, dc->mid_in, dc->mid_out, dc->w, dc->normGu, nullptr, dc->pf->d_S, dc->pf->d_Tt};
+  const int     cnt[11] = {dc->nseg, dc->nseg, dc->nseg, m, dc->gather ? dc->gather->nrows : 0, dc->scatter ? dc->scatter->ncols : 0, dc->n + dc->nseg, m, 2, m * m, m * m};
+  PMH_ARG(cap >= cnt[what]);
+  *len = cnt[what];
+  PMH_CHK(pmh_sync(ctx));
+  if (what == 8) {
+    host[1] = ctx->h_scal[dc->norm_slot];
+    return pmh_memcpy_d2h(ctx, host, ctx->d_scal + dc->norm_slot, sizeof(double));
+  }
+  return pmh_memcpy_d2h(ctx, host, src[what], sizeof(double) * (size_t)cnt[what]);
+}
+
+// a staged operator from three CSR matrices: F = scatter * middle * gather (nothing but the test entries creates one)
+struct StagedOp : pmh_op_s {
+  pmh_csr g, mdl, sc;
+  double *mi = nullptr, *mo = nullptr;
+  ~StagedOp() override
+  {
+    pmh_free(ctx, mi);
+    pmh_free(ctx, mo);
+  }
+  int mult(const double *x, double *y) override
+  {
+    PMH_CHK(pmh_csr_mult(g, x, mi));
+    PMH_CHK(pmh_csr_mult(mdl, mi, mo));
+    return pmh_csr_mult(sc, mo, y);
+  }
+  int stages(pmh_csr *gather, double **mid_in, pmh_csr *scatter, const double **mid_out) override
+  {
+    *gather = g, *mid_in = mi, *scatter = sc, *mid_out = mo;
+    return PMH_SUCCESS;
+  }
+  int mid_apply() override { return pmh_csr_mult(mdl, mi, mo); }
+};
+
+extern "C" int pmh_op_test_create_staged(pmh_csr gather, pmh_csr middle, pmh_csr scatter, pmh_op *op)
+{
+  PMH_ARG(gather && middle && scatter && op && gather->nrows >= 1 && gather->ncols >= 1);
+  PMH_ARG(middle->nrows == gather->nrows && middle->ncols == gather->nrows && scatter->nrows == gather->ncols && scatter->ncols == gather->nrows);
+  StagedOp *o = new StagedOp();
+  o->ctx = gather->ctx, o->n = gather->ncols, o->g = gather, o->mdl = middle, o->sc = scatter;
+  const size_t bytes = sizeof(double) * (size_t)gather->nrows;
+  int          rc    = pmh_malloc(o->ctx, bytes, (void **)&o->mi);
+  if (!rc) rc = pmh_malloc(o->ctx, bytes, (void **)&o->mo);
+  if (!rc) rc = pmh_memset(o->ctx, o->mi, 0, bytes);
+  if (!rc) rc = pmh_memset(o->ctx, o->mo, 0, bytes);
+  if (rc) {
+    delete o;
+    return rc;
+  }
+  *op = o;
+  return PMH_SUCCESS;
 }

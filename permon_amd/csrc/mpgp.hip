@@ -1313,3 +1313,202 @@ extern "C" int pmh_mpgp_get_work(pmh_mpgp s, int idx, const double **dptr)
   *dptr = s->work[idx];
   return PMH_SUCCESS;
 }
+
+// --------------------------------------------------------------------------------------------------------------------
+// test entries (include/permon_hip.h): one phase kernel, or one reduction finisher, on the caller's data.  No solver calls them.
+// --------------------------------------------------------------------------------------------------------------------
+extern "C" int pmh_mpgp_test_host_sum_row(const double *row, int nb, int op, double *out)
+{
+  PMH_ARG(out && nb >= 0 && nb <= 512 && (row || !nb) && (op == PMH_RED_SUM || op == PMH_RED_MIN));
+  *out = host_sum_row(row, nb, op);
+  return PMH_SUCCESS;
+}
+
+__global__ __launch_bounds__(64) void k_test_block_sum(const double *__restrict__ row, int nb, double *__restrict__ out)
+{
+  out[threadIdx.x] = pmh_sum_block_partials(row, nb);
+}
+
+extern "C" int pmh_mpgp_test_block_sum(pmh_ctx ctx, int nb, const double *row_host, double *out_host)
+{
+  PMH_ARG(ctx && out_host && nb >= 0 && nb <= 512 && (row_host || !nb));
+  double *d = nullptr; // the row, then the 64 lanes' answers
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * (512 + 64), (void **)&d));
+  int rc = pmh_memcpy_h2d(ctx, d, row_host, sizeof(double) * (size_t)nb);
+  if (!rc) {
+    hipLaunchKernelGGL(k_test_block_sum, dim3(1), dim3(64), 0, ctx->stream, (const double *)d, nb, d + 512);
+    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_mpgp_test_block_sum: the launch failed");
+  }
+  if (!rc) rc = pmh_memcpy_d2h(ctx, out_host, d + 512, sizeof(double) * 64);
+  pmh_free(ctx, d);
+  return rc;
+}
+
+__global__ __launch_bounds__(PMH_EMIT_TILE) void k_test_block_partials(long long n, const double *__restrict__ a, const double *__restrict__ b, const double *__restrict__ c, double *__restrict__ partials, double *__restrict__ h_partials, int ld)
+{
+  const long long i    = (long long)blockIdx.x * PMH_EMIT_TILE + threadIdx.x;
+  const double    v[3] = {i < n ? a[i] : 0.0, i < n ? b[i] : 0.0, i < n ? c[i] : INFINITY};
+  const int       op[3] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
+  pmh_block_partials<3>(v, op, partials, h_partials, ld);
+}
+
+extern "C" int pmh_mpgp_test_block_partials(pmh_ctx ctx, int n, const double *a, const double *b, const double *c, double *dev_host, double *pinned_host)
+{
+  PMH_ARG(ctx && n >= 1 && n <= 512 * PMH_EMIT_TILE && a && b && c && dev_host && pinned_host);
+  const int nb = (n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE, ld = ctx->partials_cap;
+  PMH_CHK(pmh_sync(ctx));
+  for (int k = 0; k < 3; k++) {
+    PMH_CHK(pmh_memcpy_h2d(ctx, ctx->d_partials + (size_t)k * ld, dev_host + (size_t)k * nb, sizeof(double) * (size_t)nb));
+    memcpy(ctx->h_partials + (size_t)k * ld, pinned_host + (size_t)k * nb, sizeof(double) * (size_t)nb);
+  }
+  hipLaunchKernelGGL(k_test_block_partials, dim3(nb), dim3(PMH_EMIT_TILE), 0, ctx->stream, (long long)n, a, b, c, ctx->d_partials, ctx->h_partials, ld);
+  PMH_HIP(hipGetLastError());
+  PMH_CHK(pmh_sync(ctx));
+  for (int k = 0; k < 3; k++) {
+    PMH_CHK(pmh_memcpy_d2h(ctx, dev_host + (size_t)k * nb, ctx->d_partials + (size_t)k * ld, sizeof(double) * (size_t)nb));
+    memcpy(pinned_host + (size_t)k * nb, ctx->h_partials + (size_t)k * ld, sizeof(double) * (size_t)nb);
+  }
+  return PMH_SUCCESS;
+}
+
+#define TLAUNCH(kern, ...) \
+  do { \
+    if (n > 0) hipLaunchKernelGGL(kern, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, (long long)n, __VA_ARGS__); \
+  } while (0)
+#define TLAUNCH_EMIT(kern, ...) \
+  do { \
+    if (n > 0) hipLaunchKernelGGL(kern, dim3((n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE), dim3(PMH_EMIT_TILE), 0, ctx->stream, (long long)n, __VA_ARGS__); \
+  } while (0)
+
+static int test_phase_launch(pmh_ctx ctx, int phase, int n, pmh_mpgp_phase_test *t, int *d_ctl, double *d_ring)
+{
+  const int     ld = ctx->partials_cap, nblocks = n > 0 ? (t->emit ? (n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE : pmh_vec_grid(n)) : 0;
+  const int    *halt = t->use_ctl ? d_ctl + CTL_HALT : nullptr;
+  int          *post = t->use_ctl ? d_ctl + CTL_ITER : nullptr;
+  const double *scal = ctx->d_scal;
+  const int     ops4[4] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM}, ops3[3] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
+  pmh_spec_args sa;
+  memset(&sa, 0, sizeof(sa));
+  if (t->spec) {
+    sa.ctl = d_ctl, sa.ring = d_ring, sa.ring_cap = t->ring_cap, sa.max_it = t->max_it;
+    sa.ttol = t->ttol, sa.divtol_rhs = t->divtol_rhs, sa.gamma2 = t->gamma2;
+  }
+  // the emission arguments from a chained operator, as emit_try asks for them: the kernel of this phase writes x (wx) and / or p (wp)
+  pmh_emit_args ea = g_noea;
+  if (t->emit && t->op) {
+    const bool wx = phase == PMH_PHASE_EXPANSION || phase == PMH_PHASE_STEP, wp = phase == PMH_PHASE_SPLIT || phase == PMH_PHASE_DIR || phase == PMH_PHASE_PROP_DIR || (phase == PMH_PHASE_STEP && t->setp);
+    if (t->op->emit_begin(wx ? t->x : nullptr, wp ? t->p : nullptr, &ea) != PMH_SUCCESS) return pmh_set_error(PMH_ERR_SUP, "pmh_mpgp_test_phase: the operator does not run on the dual-space chain");
+  }
+  int fin = 0; // quantities the driver's finalising launch of this phase reduces
+  switch (phase) {
+  case PMH_PHASE_SPLIT:
+    if (t->emit) TLAUNCH_EMIT(k_split_setp<true>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->gf, t->p, ctx->d_partials, ld, ea, ctx->h_partials);
+    else TLAUNCH(k_split_setp<false>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->gf, t->p, ctx->d_partials, ld, g_noea, (double *)nullptr);
+    fin = 4;
+    break;
+  case PMH_PHASE_STEP: {
+#define STEP_ARGS scal, sa, t->x, t->g, t->p, (const double *)t->Ap, t->lb, t->ub, t->astol, t->gf, ctx->d_partials, ld, ea
+    if (t->emit && t->setp) TLAUNCH_EMIT((k_step_update<true, false, true>), STEP_ARGS, ctx->h_partials, t->acg_host, t->nb);
+    else if (t->emit) TLAUNCH_EMIT((k_step_update<false, false, true>), STEP_ARGS, ctx->h_partials, t->acg_host, t->nb);
+    else if (t->spec) TLAUNCH((k_step_update<false, true>), STEP_ARGS, (double *)nullptr, 0.0, 0);
+    else if (t->setp) TLAUNCH((k_step_update<true, false>), STEP_ARGS, (double *)nullptr, 0.0, 0);
+    else TLAUNCH((k_step_update<false, false>), STEP_ARGS, (double *)nullptr, 0.0, 0);
+#undef STEP_ARGS
+    fin = 4;
+    break;
+  }
+  case PMH_PHASE_DIR:
+    if (t->emit) TLAUNCH_EMIT(k_dir_update<true>, scal, halt, (const double *)t->gf, t->p, ea, (const double *)ctx->d_partials, t->nb, t->pAp_host);
+    else TLAUNCH(k_dir_update<false>, scal, halt, (const double *)t->gf, t->p, g_noea, (const double *)nullptr, 0, 0.0);
+    break;
+  case PMH_PHASE_PROP_DIR:
+    if (t->emit) TLAUNCH_EMIT(k_prop_dir<true>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->p, ea);
+    else TLAUNCH(k_prop_dir<false>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->p, g_noea);
+    break;
+  case PMH_PHASE_EXPANSION:
+    if (t->emit) TLAUNCH_EMIT(k_expansion_std<true>, t->afeas, t->alpha, t->x, (const double *)t->g, (const double *)t->p, (const double *)t->Ap, t->lb, t->ub, t->astol, ea);
+    else TLAUNCH(k_expansion_std<false>, t->afeas, t->alpha, t->x, (const double *)t->g, (const double *)t->p, (const double *)t->Ap, t->lb, t->ub, t->astol, g_noea);
+    break;
+  case PMH_PHASE_P1_DOTS:
+    TLAUNCH(k_p1_dots, (const double *)t->p, (const double *)t->Ap, (const double *)t->g, (const double *)t->x, t->lb, t->ub, ctx->d_partials, ld);
+    fin = 3;
+    break;
+  case PMH_PHASE_THREE_NORMS:
+    TLAUNCH(k_three_norms, (const double *)t->x, (const double *)t->g, (const double *)t->gf, ctx->d_partials, ld);
+    fin = 4;
+    break;
+  case PMH_PHASE_OBJ:
+    TLAUNCH(k_obj_from_grad, (const double *)t->x, (const double *)t->g, t->b, ctx->d_partials);
+    fin = 1;
+    break;
+  }
+  PMH_HIP(hipGetLastError());
+  if (!t->finalize) return PMH_SUCCESS;
+  if (fin == 4) return pmh_finalize_partials(ctx, ctx->d_partials, ld, nblocks, 4, ops4, S_APGF, halt, post);
+  if (fin == 3) return pmh_finalize_partials(ctx, ctx->d_partials, ld, nblocks, 3, ops3, S_PAP);
+  return pmh_finalize_partials(ctx, ctx->d_partials, ld, nblocks, 1, ops4, S_TMP);
+}
+
+#undef TLAUNCH
+#undef TLAUNCH_EMIT
+
+extern "C" int pmh_mpgp_test_phase(pmh_ctx ctx, int phase, int n, pmh_mpgp_phase_test *t)
+{
+  PMH_ARG(ctx && t && n >= 0 && phase >= PMH_PHASE_SPLIT && phase <= PMH_PHASE_OBJ && t->partials_dev && t->partials_pinned);
+  PMH_ARG(!t->emit || (phase <= PMH_PHASE_EXPANSION && n <= 512 * PMH_EMIT_TILE && t->nb >= 0 && t->nb <= 512));
+  PMH_ARG(!t->spec || (phase == PMH_PHASE_STEP && t->use_ctl && !t->setp && !t->emit && t->ring_cap >= 0 && t->ring_cap <= 16 && t->ctl[CTL_ITER] >= t->ctl[CTL_BASE]));
+  PMH_ARG(!t->op || (t->emit && t->op->n == n));
+  PMH_ARG(!t->finalize || phase == PMH_PHASE_SPLIT || phase == PMH_PHASE_STEP || phase >= PMH_PHASE_P1_DOTS);
+  // the operands the kernel of this phase dereferences
+  const bool nx = phase != PMH_PHASE_DIR, ng = phase != PMH_PHASE_DIR, np = phase <= PMH_PHASE_P1_DOTS, nap = phase == PMH_PHASE_STEP || phase == PMH_PHASE_EXPANSION || phase == PMH_PHASE_P1_DOTS;
+  const bool ngf = phase <= PMH_PHASE_DIR || phase == PMH_PHASE_THREE_NORMS;
+  PMH_ARG(n == 0 || ((!nx || t->x) && (!ng || t->g) && (!np || t->p) && (!nap || t->Ap) && (!ngf || t->gf) && (phase != PMH_PHASE_OBJ || t->b)));
+  const size_t pbytes = sizeof(double) * PMH_MAX_RED * (size_t)ctx->partials_cap;
+  PMH_CHK(pmh_sync(ctx));
+  int    *d_ctl  = nullptr;
+  double *d_ring = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(int) * CTL_NWORDS, (void **)&d_ctl));
+  int rc = pmh_malloc(ctx, sizeof(double) * 48, (void **)&d_ring);
+  if (!rc) rc = pmh_memcpy_h2d(ctx, d_ctl, t->ctl, sizeof(int) * CTL_NWORDS);
+  if (!rc) rc = pmh_memcpy_h2d(ctx, d_ring, t->ring, sizeof(double) * 48);
+  if (!rc) rc = pmh_memcpy_h2d(ctx, ctx->d_partials, t->partials_dev, pbytes);
+  if (!rc) rc = pmh_memcpy_h2d(ctx, ctx->d_scal, t->scal_dev, sizeof(double) * PMH_NSCAL);
+  if (!rc) {
+    memcpy(ctx->h_partials, t->partials_pinned, pbytes);
+    memcpy(ctx->h_scal, t->scal_pinned, sizeof(double) * PMH_NSCAL);
+    rc = test_phase_launch(ctx, phase, n, t, d_ctl, d_ring);
+  }
+  if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_mpgp_test_phase: stream synchronisation failed");
+  if (!rc) rc = pmh_memcpy_d2h(ctx, t->ctl, d_ctl, sizeof(int) * CTL_NWORDS);
+  if (!rc) rc = pmh_memcpy_d2h(ctx, t->ring, d_ring, sizeof(double) * 48);
+  if (!rc) rc = pmh_memcpy_d2h(ctx, t->partials_dev, ctx->d_partials, pbytes);
+  if (!rc) rc = pmh_memcpy_d2h(ctx, t->scal_dev, ctx->d_scal, sizeof(double) * PMH_NSCAL);
+  if (!rc) {
+    memcpy(t->partials_pinned, ctx->h_partials, pbytes);
+    memcpy(t->scal_pinned, ctx->h_scal, sizeof(double) * PMH_NSCAL);
+  }
+  if (d_ring) pmh_free(ctx, d_ring);
+  pmh_free(ctx, d_ctl);
+  return rc;
+}
+
+// the carried gradient as smalxe.hip hands it over: g (device, n doubles) goes into the solver's work[3] and the next fused solve takes it as A x - b at its starting point
+extern "C" int pmh_mpgp_test_set_gradient_valid(pmh_mpgp s, const double *g)
+{
+  PMH_ARG(s && g && use_fused(s));
+  PMH_CHK(ensure_work(s, 3));
+  PMH_CHK(pmh_memcpy_d2d(s->ctx, s->work[3], g, sizeof(double) * (size_t)s->n));
+  PMH_CHK(pmh_mpgp_set_gradient_valid(s, 1, nullptr));
+  return s->g_valid ? PMH_SUCCESS : pmh_set_error(PMH_ERR_STATE, "pmh_mpgp_test_set_gradient_valid: the solver did not take the gradient");
+}
+
+// the speculative chain's host-side words after a solve: words[0] = 1 where the solver set the chain up (it does so only where it may use it), words[1..4] = halt,
+// iteration, ncg, base as the last batch left them
+extern "C" int pmh_mpgp_test_spec_words(pmh_mpgp s, int words[5])
+{
+  PMH_ARG(s && words);
+  PMH_CHK(pmh_sync(s->ctx));
+  words[0] = s->d_ctl != nullptr;
+  for (int k = 0; k < CTL_NWORDS; k++) words[1 + k] = s->h_ctl ? s->h_ctl[k] : 0;
+  return PMH_SUCCESS;
+}

@@ -1023,6 +1023,66 @@ extern "C" int pmh_op_penalized_test_mult_epi(pmh_op op, int kind, int same_inpu
   return pmh_dc_test_direction_sums(o->dc, cap, psums_host, nseg);
 }
 
+// the sibling with every operand of the two epilogues, the caller's in_slot and the block partials of both copies (include/permon_hip.h)
+extern "C" int pmh_op_penalized_test_mult_epi2(pmh_op op, int kind, int same_input, int in_slot, const double *x, const double *b, const double *g, const double *xx, const double *lb,
+                                               const double *ub, double astol, double *y, double *gf, double *p, double *partials_dev_host, double *partials_pinned_host, int *nblocks,
+                                               int *replayed)
+{
+  PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
+  PMH_ARG(o && x && y && (kind == 0 || kind == PMH_VEPI_P1 || kind == PMH_VEPI_GRAD_SPLIT) && in_slot >= 0 && in_slot <= 2 && partials_dev_host && partials_pinned_host && nblocks && replayed);
+  PMH_ARG(kind != PMH_VEPI_P1 || (g && xx));
+  PMH_ARG(kind != PMH_VEPI_GRAD_SPLIT || (b && gf && p));
+  PMH_ARG(kind != 0 || in_slot == 0); // (a plain product always forms its own sums)
+  if (!o->chain()) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_mult_epi2: the operator does not run on the dual-space chain");
+  pmh_ctx      ctx    = o->ctx;
+  const size_t pbytes = sizeof(double) * PMH_MAX_RED * (size_t)ctx->partials_cap;
+  PMH_CHK(pmh_sync(ctx));
+  PMH_CHK(pmh_memcpy_h2d(ctx, ctx->d_partials, partials_dev_host, pbytes));
+  memcpy(ctx->h_partials, partials_pinned_host, pbytes);
+  *nblocks = 0, *replayed = 0;
+  if (kind == 0) {
+    PMH_CHK(same_input ? o->mult_same_input(x, y, replayed) : o->mult(x, y));
+  } else {
+    pmh_vec_epi e;
+    memset(&e, 0, sizeof(e));
+    int hosted = 0, p_emitted = 0;
+    e.kind = kind, e.b = b, e.g = g, e.xx = xx, e.lb = lb, e.ub = ub, e.astol = astol, e.gf = gf, e.p = p, e.partials = ctx->d_partials, e.ld = ctx->partials_cap;
+    e.prow = kind == PMH_VEPI_P1 ? 4 : 0; // as f_apply_p1 / f_gradient_split (mpgp.hip) place them
+    e.hosted = &hosted, e.emitted_p = &p_emitted, e.same_input = same_input, e.in_slot = in_slot, e.replayed = replayed;
+    PMH_CHK(o->mult_epi(x, y, e));
+    *nblocks = hosted;
+  }
+  PMH_CHK(pmh_sync(ctx));
+  PMH_CHK(pmh_memcpy_d2h(ctx, partials_dev_host, ctx->d_partials, pbytes));
+  memcpy(partials_pinned_host, ctx->h_partials, pbytes);
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_op_penalized_test_chain_info(pmh_op op, long long info[10])
+{
+  PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
+  PMH_ARG(o && info);
+  if (!o->chain()) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_chain_info: the operator does not run on the dual-space chain");
+  return pmh_dc_test_info(o->dc, info);
+}
+
+extern "C" int pmh_op_penalized_test_chain_read(pmh_op op, int what, int cap, double *host, int *len)
+{
+  PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
+  PMH_ARG(o);
+  if (!o->chain()) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_chain_read: the operator does not run on the dual-space chain");
+  return pmh_dc_test_read(o->dc, what, cap, host, len);
+}
+
+// SMALXE's norm target as smalxe.hip sets it; ready: pmh_op_penalized_normG_ready (which launches k_dc_norm where the sums wait and no application followed)
+extern "C" int pmh_op_penalized_test_norm_target(pmh_op op, double *Gu, int slot, const double *u, int *ready)
+{
+  PMH_ARG(op && ((Gu && !u) || (u && ready)));
+  if (Gu) return pmh_op_penalized_set_normG_target(op, Gu, slot);
+  *ready = pmh_op_penalized_normG_ready(op, u);
+  return pmh_sync(op->ctx);
+}
+
 int pmh_op_penalized_take_aux_done(pmh_op op)
 {
   PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);

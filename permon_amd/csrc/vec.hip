@@ -90,6 +90,37 @@ int pmh_finalize_partials_slots(pmh_ctx ctx, const double *partials, int ld, int
   return PMH_SUCCESS;
 }
 
+// test entry (include/permon_hip.h): one launch of k_finalize on the caller's rows, slots, halt word and counters
+extern "C" int pmh_vec_test_finalize(pmh_ctx ctx, int K, int nblocks, const double *rows_host, const int *ops, const int *slots, int halt, int *post_inc, double *scal_dev, double *scal_pinned)
+{
+  PMH_ARG(ctx && K >= 1 && K <= PMH_MAX_RED && nblocks >= 0 && nblocks <= ctx->partials_cap && ops && slots && scal_dev && scal_pinned && (rows_host || !nblocks));
+  for (int k = 0; k < K; k++) PMH_ARG(slots[k] >= 0 && slots[k] < PMH_NSCAL && (ops[k] == PMH_RED_SUM || ops[k] == PMH_RED_MIN));
+  const int ld = ctx->partials_cap;
+  PMH_CHK(pmh_sync(ctx));
+  pmh_ops8 o;
+  for (int k = 0; k < PMH_MAX_RED; k++) o.op[k] = (k < K) ? ops[k] : 0, o.slot[k] = (k < K) ? slots[k] : 0;
+  for (int k = 0; k < K; k++) {
+    PMH_CHK(pmh_memcpy_h2d(ctx, ctx->d_partials + (size_t)k * ld, rows_host + (size_t)k * nblocks, sizeof(double) * (size_t)nblocks));
+    PMH_CHK(pmh_memcpy_h2d(ctx, ctx->d_scal + slots[k], scal_dev + k, sizeof(double)));
+    ctx->h_scal[slots[k]] = scal_pinned[k];
+  }
+  int *d_words = nullptr; // halt, then the two counters
+  PMH_CHK(pmh_malloc(ctx, sizeof(int) * 3, (void **)&d_words));
+  const int words[3] = {halt > 0 ? halt : 0, post_inc ? post_inc[0] : 0, post_inc ? post_inc[1] : 0};
+  int       rc       = pmh_memcpy_h2d(ctx, d_words, words, sizeof(words));
+  if (!rc) {
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(PMH_FIN_THREADS), 0, ctx->stream, (const double *)ctx->d_partials, ld, nblocks, K, o, ctx->d_scal, ctx->h_scal, halt < 0 ? (const int *)nullptr : (const int *)d_words, post_inc ? d_words + 1 : (int *)nullptr);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_vec_test_finalize: the launch failed");
+  }
+  for (int k = 0; k < K && !rc; k++) {
+    rc             = pmh_memcpy_d2h(ctx, scal_dev + k, ctx->d_scal + slots[k], sizeof(double));
+    scal_pinned[k] = ctx->h_scal[slots[k]];
+  }
+  if (!rc && post_inc) rc = pmh_memcpy_d2h(ctx, post_inc, d_words + 1, sizeof(int) * 2);
+  pmh_free(ctx, d_words);
+  return rc;
+}
+
 // ---- BLAS-1 ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PMH_BLOCK) void k_axpy(long long n, double *__restrict__ y, double a, const double *__restrict__ x)
 {
