@@ -521,6 +521,28 @@ int pmh_op_svm_dual_set_labels(pmh_op op, const double *y_dev /* n_local doubles
    every stored entry is still swept (no row skipping), one n-vector kernel masks the operand before pass 1 */
 int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev /* n_local doubles of 0 / 1, or NULL = all */);
 
+/* ---- the dual Hessian of epsilon-insensitive regression (svr.hip) ---------------------------------------------------------------------------------------------
+ * The classification dual on the doubled samples [X; X] with labels [+1; -1], X kept ONCE.  The operator acts on 2 n_local doubles u = [p; q]:
+ *   s_i = p_i - q_i,  w = X's,  S = sum_i s_i,
+ *   out_p[i] =   x_i . w  + sigma S + D_i p_i
+ *   out_q[i] = -(x_i . w) - sigma S + D_i q_i,      D the scalar shift or the diagonal (n_local doubles, used for both halves).
+ * Dense rows (fp64 or float32, d <= 256, X borrowed and never copied): a product streams X twice in three launches -- pass 1 reads p_i and q_i where the
+ * classification kernel reads y_i a_i, the column sums, pass 2 writes both halves of row i from the one dot product; no n-vector s or X w goes through memory.
+ * Fixed summation orders, no float atomics: two products give the same bits.  float32 with d != 64: bit for bit the fp64 operator on the widened samples.
+ * CSR (any d): the entry-balanced sweeps of the classification operator over X with all labels +1 (one column-ordered copy, 12 (nnz + n_local) bytes), one
+ * n-vector kernel before pass 1 (p - q) and one after pass 2 (the two halves).  Device memory beside X, CSR: that copy, the sweeps' tables and 6 n-vectors of
+ * doubles (the labels of both orderings 2, p - q 1, X w 1, the labels [+1; -1] of the doubled problem 2); dense: the last 2 only.
+ * With a communicator the samples are sharded by rows and w (d doubles, d + 1 with sigma) is all-reduced between the passes (kept, not tested on more than one
+ * GPU).  Under pmh_op_create_penalized with a one-row projector whose row is a multiple of [1; -1] the penalty is absorbed as the rank-one term (as the
+ * classification operator does).  No fused MPGP epilogues (MPGP takes its unfused path), no sample subsets, no new labels.
+ * set_terms / set_diag: the rules of pmh_op_svm_dual_set_terms / _set_diag (shift, sigma >= 0; a diagonal and a non-zero shift exclude each other). */
+int pmh_op_create_svr_dual(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_op *op);
+int pmh_op_create_svr_dual_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, pmh_op *op);
+int pmh_op_create_svr_dual_csr(pmh_ctx ctx, pmh_csr X, pmh_op *op);
+int pmh_op_svr_dual_set_terms(pmh_op op, double shift, double sigma);
+int pmh_op_svr_dual_set_diag(pmh_op op, const double *diag_dev /* n_local doubles, borrowed, used for both halves; NULL: off */);
+int pmh_op_svr_dual_passes(pmh_op op, long long *passes); /* passes over X so far: 2 per product */
+
 /* ---- QPS SMALXE (src/qps/impls/smalxe/smalxe.c) -------------------------------------------------------- */
 typedef struct {
   double rtol, atol, divtol;
@@ -790,6 +812,70 @@ int pmh_svm_multi_set_calibration(pmh_svm_multi svm, const double *A_host /* K *
 int pmh_svm_multi_get_calibration(pmh_svm_multi svm, double *A_host /* K, or NULL */, double *B_host /* K, or NULL */, pmh_svm_platt_stats *st_host /* K, or NULL */);
 int pmh_svm_multi_predict_proba(pmh_svm_multi svm, int n, const double *X_dev, double *proba_dev);
 int pmh_svm_multi_predict_proba_csr(pmh_svm_multi svm, pmh_csr Xt, double *proba_dev);
+
+/* ---- SVR: linear epsilon-insensitive support vector regression (svr_train.hip) --------------------------------------------------------------------------------
+ * Samples X (n x d), targets t (all finite), epsilon >= 0, C > 0, optional sample weights: C_i = C weight_i.
+ *   L1: primal 1/2 |w|^2 + sum C_i max(0, |x_i . w + b - t_i| - eps);    L2: primal 1/2 |w|^2 + 1/2 sum C_i max(0, |x_i . w + b - t_i| - eps)^2
+ *   dual in u = [p; q] (2 n doubles):  min 1/2 u'H^u - c^'u,  H^ the operator of pmh_op_create_svr_dual with D = 0 (L1) or diag(1 / C_i) (L2),
+ *   c^ = [t - eps; -t - eps];  L1: 0 <= u <= [C_i; C_i];  L2: 0 <= u;  bias: additionally sum (p_i - q_i) = 0, posed as the unit row [1; -1] / sqrt(2 n).
+ * Without bias the QP goes to MPGP, with bias to SMALXE over pmh_qppf_create_onerow, the penalty absorbed by the operator as its rank-one term -- the route of
+ * pmh_svm_train.  Model: w = X'(p - q), f(x) = x . w + b.  b_free is the mean over the free entries of the box (astol < u_k and, L1, u_k < C_i - astol; astol
+ * the inner MPGP's) of  t_i - eps - D_i p_i - x_i . w  (a free p_i)  and  t_i + eps + D_i q_i - x_i . w  (a free q_i): stationarity in a free entry.
+ * b_multiplier = mu / sqrt(2 n), mu the multiplier of the row in the Lagrangian 1/2 u'H^u - c^'u + mu (row'u).  The bias returned is b_free, or b_multiplier
+ * where no entry is free; without bias it is 0.  The bias and the counts take one pass over X, in a fixed summation order.
+ * Not here: sample subsets, cross-validation, warm starts, a grid search.  Sharding by rows under a communicator is kept in the code, one GPU is tested. */
+typedef struct {
+  int             loss_type;  /* -svr_loss_type L1 | L2 (PMH_SVM_LOSS_L1 | PMH_SVM_LOSS_L2) */
+  double          C;          /* -svr_C, > 0 */
+  double          epsilon;    /* -svr_epsilon, >= 0 */
+  int             bias;       /* -svr_bias 0 | 1 */
+  pmh_qps_opts    qps;        /* as in pmh_svm_opts */
+  pmh_mpgp_opts   mpgp;
+  pmh_smalxe_opts smalxe;
+} pmh_svr_opts;
+typedef struct {
+  int       reason;                             /* converged reason of the training solve */
+  int       outer_iterations, inner_iterations; /* as in pmh_svm_stats */
+  int       nmv, ncg, nexp, nprop;
+  long long passes_X;                           /* passes over X of the solve */
+  long long n_sv, n_free_sv;                    /* entries of [p; q] above astol, free ones */
+  double    sum_beta;                           /* sum (p_i - q_i) of the returned dual */
+  double    b, b_free, b_multiplier;            /* the bias returned, the mean over the free entries (NaN: none), the multiplier's value */
+  double    rho, normBu, rnorm;                 /* as in pmh_svm_stats */
+} pmh_svr_stats;
+typedef struct {
+  long long n, n_in_tube;                       /* samples; those with |r_i| <= eps, r_i = f(x_i) - t_i */
+  double    sum_r, sum_r2, sum_abs_r, max_abs, sum_t, sum_t2; /* the sums of the one pass, each in a fixed order */
+  double    mse, mae, r2;                       /* sum_r2 / n, sum_abs_r / n, 1 - sum_r2 / (sum_t2 - sum_t^2 / n) (NaN for n == 0; r2 NaN for constant targets) */
+} pmh_svr_metrics;
+typedef struct pmh_svr_s *pmh_svr;
+int pmh_svr_default_opts(pmh_svr_opts *o); /* L1, C = 1, epsilon = 0.1, bias */
+/* -svr_loss_type, -svr_C, -svr_epsilon, -svr_bias here; everything else through pmh_qps_set_from_options with the empty prefix */
+int pmh_svr_set_from_options(const char *options, pmh_svr_opts *o, char *unknown, int unknown_cap);
+/* X_dev, t_dev (n_local doubles) borrowed.  epsilon < 0 or not finite, C <= 0, a target that is not finite (counted on the device): PMH_ERR_ARG with the value */
+int pmh_svr_create(pmh_ctx ctx, int n_local, int d, const double *X_dev, const double *t_dev, const pmh_svr_opts *opts, pmh_svr *svr);
+int pmh_svr_create_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, const double *t_dev, const pmh_svr_opts *opts, pmh_svr *svr);
+int pmh_svr_create_csr(pmh_ctx ctx, pmh_csr X, const double *t_dev, const pmh_svr_opts *opts, pmh_svr *svr);
+/* C_i = C weight_i (weight_dev: n_local doubles, copied; NULL: all 1) with the checks and messages of pmh_svm_set_penalties; the solver is built anew and the
+   handle is untrained afterwards */
+int pmh_svr_set_penalties(pmh_svr svr, double C, const double *weight_dev);
+/* A new epsilon: the right-hand side alone changes, the handle is untrained afterwards.  MPGP (no bias) is kept; SMALXE sizes eta by |c^| when it is created,
+   so with a bias the solver is built anew (the operator, its CSR copy and the projector stay).  Either way a training afterwards gives a fresh handle's bits */
+int pmh_svr_set_epsilon(pmh_svr svr, double epsilon);
+int pmh_svr_train(pmh_svr svr); /* from u = 0 */
+int pmh_svr_get_model(pmh_svr svr, double *w_host /* d doubles, or NULL */, double *b /* or NULL */); /* before training: PMH_ERR_STATE */
+int pmh_svr_get_dual(pmh_svr svr, double *u_dev /* 2 n_local doubles: p, then q */);
+int pmh_svr_get_stats(pmh_svr svr, pmh_svr_stats *st);
+int pmh_svr_get_solver(pmh_svr svr, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh_smalxe *smalxe); /* borrowed, as pmh_svm_get_solver */
+/* f(x_i) = x_i . w + b in one pass over the test samples.  Dense test samples need d <= 256, CSR ones the model's d columns, whatever the handle was trained on */
+int pmh_svr_predict(pmh_svr svr, int n, const double *X_dev, double *f_dev);
+int pmh_svr_predict_f32(pmh_svr svr, int n, const float *X_dev, double *f_dev);
+int pmh_svr_predict_csr(pmh_svr svr, pmh_csr Xt, double *f_dev);
+/* scores and reduces in the same pass: the sums of pmh_svr_metrics (the tube is the handle's epsilon), turned into mse, mae, r2 on the host */
+int pmh_svr_test(pmh_svr svr, int n, const double *X_dev, const double *t_dev, pmh_svr_metrics *m);
+int pmh_svr_test_f32(pmh_svr svr, int n, const float *X_dev, const double *t_dev, pmh_svr_metrics *m);
+int pmh_svr_test_csr(pmh_svr svr, pmh_csr Xt, const double *t_dev, pmh_svr_metrics *m);
+int pmh_svr_destroy(pmh_svr svr);
 
 
 /* ---- PC for the inner KSP of MATINV: multigrid V-cycle (PCMG semantics) ----------------------------------------

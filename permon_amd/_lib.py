@@ -88,6 +88,24 @@ class SvmPlattStats(C.Structure):  # pmh_svm_platt_stats
                 ("fval", C.c_double), ("g1", C.c_double), ("g2", C.c_double)]
 
 
+class SvrOpts(C.Structure):  # pmh_svr_opts
+    _fields_ = [("loss_type", C.c_int), ("C", C.c_double), ("epsilon", C.c_double), ("bias", C.c_int), ("qps", QpsOpts), ("mpgp", MpgpOpts), ("smalxe", SmalxeOpts)]
+
+
+class SvrStats(C.Structure):  # pmh_svr_stats
+    _fields_ = [("reason", C.c_int), ("outer_iterations", C.c_int), ("inner_iterations", C.c_int),
+                ("nmv", C.c_int), ("ncg", C.c_int), ("nexp", C.c_int), ("nprop", C.c_int),
+                ("passes_X", C.c_longlong), ("n_sv", C.c_longlong), ("n_free_sv", C.c_longlong),
+                ("sum_beta", C.c_double), ("b", C.c_double), ("b_free", C.c_double), ("b_multiplier", C.c_double),
+                ("rho", C.c_double), ("normBu", C.c_double), ("rnorm", C.c_double)]
+
+
+class SvrMetrics(C.Structure):  # pmh_svr_metrics
+    _fields_ = [("n", C.c_longlong), ("n_in_tube", C.c_longlong),
+                ("sum_r", C.c_double), ("sum_r2", C.c_double), ("sum_abs_r", C.c_double), ("max_abs", C.c_double), ("sum_t", C.c_double), ("sum_t2", C.c_double),
+                ("mse", C.c_double), ("mae", C.c_double), ("r2", C.c_double)]
+
+
 class KspFetiOpts(C.Structure):
     _fields_ = [("gluing_type", C.c_int), ("scale", C.c_int), ("exclude_dirichlet", C.c_int), ("regularize", C.c_int), ("kplus_left", C.c_int), ("project", C.c_int),
                 ("E_orth_type", C.c_int), ("lumped_pc", C.c_int), ("regularize_rho", C.c_double),
@@ -328,6 +346,31 @@ _PROTOS = {
     "pmh_svm_multi_get_calibration": [vp, vp, vp, vp],
     "pmh_svm_multi_predict_proba": [vp, C.c_int, vp, vp],
     "pmh_svm_multi_predict_proba_csr": [vp, vp, vp],
+    "pmh_op_create_svr_dual": [vp, C.c_int, C.c_int, vp, C.POINTER(vp)],
+    "pmh_op_create_svr_dual_f32": [vp, C.c_int, C.c_int, vp, C.POINTER(vp)],
+    "pmh_op_create_svr_dual_csr": [vp, vp, C.POINTER(vp)],
+    "pmh_op_svr_dual_passes": [vp, C.POINTER(C.c_longlong)],
+    "pmh_op_svr_dual_set_terms": [vp, C.c_double, C.c_double],
+    "pmh_op_svr_dual_set_diag": [vp, vp],
+    "pmh_svr_default_opts": [C.POINTER(SvrOpts)],
+    "pmh_svr_set_from_options": [C.c_char_p, C.POINTER(SvrOpts), C.c_char_p, C.c_int],
+    "pmh_svr_create": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvrOpts), C.POINTER(vp)],
+    "pmh_svr_create_f32": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvrOpts), C.POINTER(vp)],
+    "pmh_svr_create_csr": [vp, vp, vp, C.POINTER(SvrOpts), C.POINTER(vp)],
+    "pmh_svr_set_penalties": [vp, C.c_double, vp],
+    "pmh_svr_set_epsilon": [vp, C.c_double],
+    "pmh_svr_train": [vp],
+    "pmh_svr_get_model": [vp, vp, c_double_p],
+    "pmh_svr_get_dual": [vp, vp],
+    "pmh_svr_get_stats": [vp, C.POINTER(SvrStats)],
+    "pmh_svr_get_solver": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+    "pmh_svr_predict": [vp, C.c_int, vp, vp],
+    "pmh_svr_predict_f32": [vp, C.c_int, vp, vp],
+    "pmh_svr_predict_csr": [vp, vp, vp],
+    "pmh_svr_test": [vp, C.c_int, vp, vp, C.POINTER(SvrMetrics)],
+    "pmh_svr_test_f32": [vp, C.c_int, vp, vp, C.POINTER(SvrMetrics)],
+    "pmh_svr_test_csr": [vp, vp, vp, C.POINTER(SvrMetrics)],
+    "pmh_svr_destroy": [vp],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],
     "pmh_smalxe_destroy": [vp],

@@ -82,7 +82,14 @@ extern "C" int pmh_op_max_eigenvalue(pmh_op op, double tol, int maxits, double *
   double *v = nullptr, *Av = nullptr;
   PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&v));
   PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&Av));
-  PMH_CHK(pmh_vec_set(ctx, n, v, 1.0));
+  {
+    int rc0 = op->maxeig_start(v); // (an operator may know that all ones will not do)
+    if (rc0 == PMH_EPI_UNSUPPORTED) rc0 = pmh_vec_set(ctx, n, v, 1.0);
+    if (rc0) {
+      pmh_free(ctx, v), pmh_free(ctx, Av);
+      return rc0;
+    }
+  }
   double lambda = 0.0, lambda0, vAv, vv;
   int    i, rc = PMH_SUCCESS;
   bool   seeded = false;

@@ -358,6 +358,40 @@ extern "C" int pmh_svm_set_from_options(const char *options, pmh_svm_opts *o, ch
   return pmh_qps_set_from_options(rest.c_str(), "", &o->qps, &o->mpgp, &o->smalxe, unknown, unknown_cap);
 }
 
+// Options of the SVR front end (svr_train.hip): -svr_loss_type L1|L2, -svr_C, -svr_epsilon, -svr_bias here; every other key as in pmh_svm_set_from_options
+extern "C" int pmh_svr_set_from_options(const char *options, pmh_svr_opts *o, char *unknown, int unknown_cap)
+{
+  PMH_ARG(options && o);
+  std::vector<Token> toks;
+  PMH_CHK(tokenize(options, toks));
+  std::string rest;
+  for (const Token &t : toks) {
+    if (t.key == "svr_loss_type") {
+      if (!t.has_val) return pmh_set_error(PMH_ERR_ARG, "options: -%s needs a value", t.key.c_str());
+      const std::string v = lower(t.val);
+      if (v == "l1") o->loss_type = PMH_SVM_LOSS_L1;
+      else if (v == "l2") o->loss_type = PMH_SVM_LOSS_L2;
+      else return pmh_set_error(PMH_ERR_ARG, "options: unknown SVR loss type \"%s\" for -svr_loss_type (L1 | L2)", t.val.c_str());
+    } else if (t.key == "svr_C") {
+      double c;
+      if (get_real(t, &c)) return PMH_ERR_ARG;
+      if (!(c > 0.0)) return pmh_set_error(PMH_ERR_ARG, "options: -svr_C %s, must be positive", t.val.c_str());
+      o->C = c;
+    } else if (t.key == "svr_epsilon") {
+      double e;
+      if (get_real(t, &e)) return PMH_ERR_ARG;
+      if (!(e >= 0.0) || e > 1.7976931348623157e308) return pmh_set_error(PMH_ERR_ARG, "options: -svr_epsilon %s, must be non-negative and finite", t.val.c_str());
+      o->epsilon = e;
+    } else if (t.key == "svr_bias") {
+      if (get_bool(t, &o->bias)) return PMH_ERR_ARG;
+    } else {
+      rest += (rest.empty() ? "-" : " -") + t.key;
+      if (t.has_val) rest += " " + t.val;
+    }
+  }
+  return pmh_qps_set_from_options(rest.c_str(), "", &o->qps, &o->mpgp, &o->smalxe, unknown, unknown_cap);
+}
+
 // QPSCreate defaults (qps.c:73-76); type "" = QPSSetDefaultType decides at set-up (qps.c:422-455)
 extern "C" int pmh_qps_default_opts(pmh_qps_opts *q)
 {

@@ -231,6 +231,9 @@ struct pmh_op_s {
   // MatMultTranspose slot; operators that are symmetric by construction forward to mult
   virtual int     mult_transpose(const double *, double *) { return pmh_set_error(PMH_ERR_SUP, "this operator has no MatMultTranspose slot"); }
   virtual pmh_csr as_csr() { return nullptr; }
+  // The vector pmh_op_max_eigenvalue's power method starts from, where all ones will not do: an operator of which 1 is an eigenvector of a small eigenvalue
+  // (the regression dual, svr.hip: H^ 1 = D 1) fills v (n doubles, device) with a start of its own.  PMH_EPI_UNSUPPORTED: all ones, as the reference starts
+  virtual int     maxeig_start(double * /*v*/) { return PMH_EPI_UNSUPPORTED; }
   // Operators of the form (scatter) o (middle) o (gather) -- F = B K^+ B' with either K^+ (feti.hip): gather = B' as CSR (rows = entries of mid_in), scatter =
   // B as CSR (rows = dual entries, columns = entries of mid_out); mid_apply runs the middle stage mid_in -> mid_out.  The fused dual-space chain folds the
   // projector into the two sparse stages.

@@ -78,6 +78,12 @@ static __device__ __forceinline__ void svm_colsum(int nblocks, int d, const doub
   if (lane == 0) w[c] = v;
 }
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_colsum(int nblocks, int d, const double *__restrict__ part, double *__restrict__ w, const double *__restrict__ spart) { svm_colsum(nblocks, d, part, w, spart); }
+int pmh_svm_colsum(pmh_ctx ctx, int nblocks, int d, const double *part, double *w, const double *spart)
+{
+  hipLaunchKernelGGL(k_svm_colsum, dim3((d + (spart ? 1 : 0) + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, part, w, spart);
+  PMH_HIP(hipGetLastError()); // (also the launch of the pass that filled part)
+  return PMH_SUCCESS;
+}
 
 // pass 2: (H a)_i = y_i (x_i . w); AUG 1: + sigma s y_i + shift a_i; AUG 2: + sigma s y_i + diag_i a_i
 template <int AUG, int SUB, class T>
@@ -89,31 +95,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_x(int n, int d, const T *__re
 }
 
 // ---- d == 64 fast path: the RPI-rows-per-wave-instruction layout of svm_rows.h (double: 2 rows, float: 4), 4-fold unroll ----
-// the CPL column sums a lane holds (double: columns 2 l2, 2 l2 + 1; float: columns 4 q .. 4 q + 3, of the rows its LPR lanes visited) -> part[workgroup][64]:
-// lanes l, l + LPR, ... hold the same columns of different rows: fold by halving, double: l + (l + 32); float: (q + (q + 32)) + ((q + 16) + (q + 48)); then
-// across the 4 waves in order
-template <class T>
-static __device__ __forceinline__ void svm_fold_cols(double (&acc)[svm_row64<T>::CPL], double (*lds)[64], double *__restrict__ part)
-{
-  typedef svm_row64<T> R;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane / R::LPR, lq = lane & (R::LPR - 1);
-#pragma unroll
-  for (int o = 32; o >= R::LPR; o >>= 1) {
-#pragma unroll
-    for (int c = 0; c < R::CPL; c++) acc[c] += __shfl_down(acc[c], o, 64);
-  }
-  if (sub == 0) {
-#pragma unroll
-    for (int c = 0; c < R::CPL; c++) lds[wave][R::CPL * lq + c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    double v = lds[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v += lds[wv][threadIdx.x];
-    part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
-  }
-}
+// (svm_fold_cols, which finishes a lane's column sums, is in svm_rows.h: svr.hip folds the same way)
 // pass 1 for d = 64.  A wave takes RPI SVM_UNR rows at a time, rows r0 + RPI u + sub to the LPR lanes sub; a lane's column sums take its rows in the order
 // it visits them (u ascending within a group, groups ascending), then svm_fold_cols
 template <int SVM_UNR, int AUG, int SUB, class T>
@@ -379,9 +361,7 @@ int SvmDualOp::pass1(const double *v, bool aug, const double *u, double *upart)
     if (d == 64) SVM_PASS((k_svm_xt64<4, AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, (const T *)X, y, v, part, sp, u, upart);
     else SVM_PASS((k_svm_xt<AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, n, d, (const T *)X, y, v, part, sp, u, upart);
   });
-  hipLaunchKernelGGL(k_svm_colsum, dim3((d + (aug ? 1 : 0) + 3) / 4), dim3(PMH_BLOCK), 0, ctx->stream, nblocks, d, (const double *)part, w, (const double *)sp);
-  PMH_HIP(hipGetLastError());
-  return PMH_SUCCESS;
+  return pmh_svm_colsum(ctx, nblocks, d, part, w, sp);
 }
 // pass 2: out_i = y_i (x_i . w), augmented + (sigma + sigma_fold) w[d] y_i + shift a_i (or + diag_i a_i)
 int SvmDualOp::pass2(const double *a, double *out, bool aug)
@@ -601,6 +581,7 @@ extern "C" int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev)
 {
   SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
   PMH_ARG(o);
+  if (o->doubled()) return pmh_set_error(PMH_ERR_SUP, "pmh_op_svm_dual_set_subset: the regression operator (pmh_op_create_svr_dual) takes no sample subset");
   pmh_ctx   ctx = o->ctx;
   const int n   = o->n;
   if (!m_dev) {

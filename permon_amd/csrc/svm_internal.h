@@ -50,6 +50,10 @@ struct SvmDualBase : pmh_op_s {
   // w = X'(y o a) into the operator's own w (d doubles, device; all-reduced under a communicator) by the pass-1 kernels (the model of a trained SVM)
   virtual int   form_w(const double *a, const double **w_dev) = 0;
   virtual void  terms_changed() {} // pmh_op_svm_dual_set_terms / pmh_op_svm_dual_set_diag was called
+  // The regression operator (svr.hip) is this dual on the doubled samples [X; X] with labels [+1; -1], X held once: n = 2 n_local, y its own 2 n_local labels
+  // (what pmh_svm_op_row_is_labels compares the equality's row with, so that the penalised operator folds rho G'G into sigma_fold as it does here), diag
+  // n_local doubles used for both halves.  It takes no subset and no new labels
+  virtual bool  doubled() const { return false; }
   // pmh_op_svm_dual_set_labels: new labels (n doubles of +-1, borrowed; may be the buffer borrowed so far with new contents).  Whatever the operator derived
   // from the old labels it redoes from state of its own, never from the caller's memory
   virtual int   set_labels(const double *y_dev)
@@ -121,6 +125,9 @@ struct SvmDualOp : SvmDualBase {
 
 // the augmented row result: (y_i (x_i . w) + (sigma s) y_i) + shift a_i, in this order (s = w[d]); the diagonal form hands diag_i over as shift
 static __device__ __forceinline__ double svm_aug_row(double yi, double dot, double sS, double shift, double ai) { return (yi * dot + sS * yi) + shift * ai; }
+
+// w[c] = sum over the nblocks workgroups of part[b][c], c < d; spart != nullptr: w[d] = sum_b spart[b] too (k_svm_colsum: one wavefront per column, fixed order)
+int pmh_svm_colsum(pmh_ctx ctx, int nblocks, int d, const double *part, double *w, const double *spart);
 
 // 1 (and c, with row = c y) if pf is a one-row projector whose row is a multiple of this operator's labels, entry by entry
 int pmh_svm_op_row_is_labels(SvmDualBase *o, pmh_qppf pf, double *c);

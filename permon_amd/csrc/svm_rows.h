@@ -165,6 +165,33 @@ static __device__ __forceinline__ void svm_sweep_rows64(int n, const T *__restri
   }
 }
 
+// ---- the column sums of a pass 1 for d = 64 (k_svm_xt64 and the paired passes in svm.hip, k_svr_xt64 in svr.hip) ----
+// the CPL column sums a lane holds (double: columns 2 l2, 2 l2 + 1; float: columns 4 q .. 4 q + 3, of the rows its LPR lanes visited) -> part[workgroup][64]:
+// lanes l, l + LPR, ... hold the same columns of different rows: fold by halving, double: l + (l + 32); float: (q + (q + 32)) + ((q + 16) + (q + 48)); then
+// across the 4 waves in order
+template <class T>
+static __device__ __forceinline__ void svm_fold_cols(double (&acc)[svm_row64<T>::CPL], double (*lds)[64], double *__restrict__ part)
+{
+  typedef svm_row64<T> R;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane / R::LPR, lq = lane & (R::LPR - 1);
+#pragma unroll
+  for (int o = 32; o >= R::LPR; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < R::CPL; c++) acc[c] += __shfl_down(acc[c], o, 64);
+  }
+  if (sub == 0) {
+#pragma unroll
+    for (int c = 0; c < R::CPL; c++) lds[wave][R::CPL * lq + c] = acc[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    double v = lds[0][threadIdx.x];
+#pragma unroll
+    for (int wv = 1; wv < PMH_BLOCK / 64; wv++) v += lds[wv][threadIdx.x];
+    part[(size_t)blockIdx.x * 64 + threadIdx.x] = v;
+  }
+}
+
 // The row loop of the paired passes (k_svm_x64_grad, k_svm_x64_p1 in svm.hip).  The rows' dot products land in the first lane of the LPR lanes of each row; lane
 // j < RPI UNR then takes row i = r0 + j (u = j / RPI, sub = j % RPI; act: it has one) and does the row's elementwise work once: ONE coalesced load per vector
 // for the RPI UNR rows (a load per row costs the address unit a whole instruction each: measured 2 x the time of the plain pass).

@@ -777,3 +777,48 @@ def MatCreateSVMDual(ctx, X, y, sample_dtype=None):
     op.set_diag = set_diag
     op.set_subset = set_subset
     return op
+
+
+def MatCreateSVRDual(ctx, X, sample_dtype=None):
+    """Matrix-free dual Hessian of epsilon-insensitive regression on u = [p; q] (2 n_local entries): with s = p - q, w = X's, S = sum s,
+    out_p = X w + sigma S + D p, out_q = -X w - sigma S + D q -- the classification dual of MatCreateSVMDual on vstack(X, X) with labels [+1; -1], X kept once
+    and streamed twice per product (csrc/svr.hip).  X and sample_dtype as in MatCreateSVMDual."""
+    dt = sample_dtype_of(sample_dtype, is_sparse(X), "MatCreateSVRDual")
+    h = C.c_void_p()
+    if is_sparse(X):
+        Xc = csr_from_scipy(ctx, X)
+        n = Xc.nrows
+        check(ctx.L.pmh_op_create_svr_dual_csr(ctx.h, Xc.h, C.byref(h)))
+        op = Op(ctx, h, 2 * n, keep=[Xc])
+    else:
+        X = sample_array(X, dt, "MatCreateSVRDual")
+        n, d = X.shape
+        f32 = dt is np.float32
+        Xd = (VecF32 if f32 else Vec).from_numpy(ctx, X.ravel())
+        check((ctx.L.pmh_op_create_svr_dual_f32 if f32 else ctx.L.pmh_op_create_svr_dual)(ctx.h, n, d, Xd.p, C.byref(h)))
+        op = Op(ctx, h, 2 * n, keep=[Xd])
+    op.sample_dtype = dt
+
+    def passes():
+        """How many times the operator has streamed X so far (pmh_op_svr_dual_passes): 2 per product."""
+        k = C.c_longlong(0)
+        check(ctx.L.pmh_op_svr_dual_passes(op.h, C.byref(k)))
+        return int(k.value)
+
+    def set_terms(shift=0.0, sigma=0.0):
+        """D = shift I and the rank-one term sigma [1; -1][1; -1]' (pmh_op_svr_dual_set_terms); both 0: the plain operator."""
+        check(ctx.L.pmh_op_svr_dual_set_terms(op.h, float(shift), float(sigma)))
+
+    def set_diag(diag=None):
+        """D = diag(diag) (pmh_op_svr_dual_set_diag): a Vec or an array of n_local doubles, used for both halves and kept alive by the operator; None: off.
+        Excludes a non-zero shift of set_terms."""
+        v = diag if diag is None or isinstance(diag, Vec) else Vec.from_numpy(ctx, np.ascontiguousarray(diag, dtype=np.float64).ravel())
+        if v is not None and v.n != n:
+            raise ValueError("set_diag: %d entries, the operator has %d samples" % (v.n, n))
+        check(ctx.L.pmh_op_svr_dual_set_diag(op.h, v.p if v is not None else None))
+        op._diag = v
+
+    op.passes = passes
+    op.set_terms = set_terms
+    op.set_diag = set_diag
+    return op

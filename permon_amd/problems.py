@@ -267,6 +267,43 @@ def svm_sparse(N, d, nnz_row, skew, offset, C=1.0, seed=7, N_test=0):
     return out
 
 
+def svr_linear(n, d, noise, seed, sparse=None, b_true=3.0, eps=0.1, C=1.0, n_test=0):
+    """Linear regression data for SVR: t = X w* + b* + noise N(0,1), w* ~ N(0,1) / sqrt(d) so that the targets' spread does not grow with d.
+    sparse=None: X i.i.d. N(0,1), dense.  sparse=(nnz_row, skew): X scipy CSR drawn in the style of svm_sparse -- nnz_row feature draws per sample with
+    probability proportional to 1 / rank^skew, values N(0,1), duplicates summed, rows scaled to unit length.  X, then the noise, from default_rng(seed); w* from
+    default_rng(seed + 1).  Returns dict(n, d, X, t, w_true, b_true, eps, C) and, for the QP-level tests on MatCreateSVRDual, the vectors of the dual in
+    u = [p; q]: c = [t - eps; -t - eps], lb = 0, ub = C (the L1 box), x0 = 0.  n_test > 0: a held-out draw (X_test, t_test) from default_rng(seed + 1000)."""
+    import scipy.sparse as sp
+
+    def draw(r, m):
+        if sparse is None:
+            return r.standard_normal((m, d))
+        nnz_row, skew = sparse
+        p = 1.0 / np.arange(1, d + 1) ** skew
+        p /= p.sum()
+        cols = r.choice(d, size=(m, nnz_row), p=p)
+        vals = r.standard_normal((m, nnz_row))
+        X = sp.csr_matrix((vals.ravel(), (np.repeat(np.arange(m), nnz_row), cols.ravel())), shape=(m, d))
+        X.sum_duplicates()
+        nr = np.sqrt(np.asarray(X.multiply(X).sum(axis=1)).ravel())
+        nr[nr == 0] = 1.0
+        X = (sp.diags(1.0 / nr) @ X).tocsr()
+        X.sort_indices()
+        return X
+
+    rng = np.random.default_rng(seed)
+    X = draw(rng, n)
+    w = np.random.default_rng(seed + 1).standard_normal(d) / np.sqrt(d)
+    t = X @ w + b_true + noise * rng.standard_normal(n)
+    out = dict(n=n, d=d, X=X, t=t, w_true=w, b_true=float(b_true), eps=float(eps), C=float(C),
+               c=np.concatenate([t - eps, -t - eps]), lb=np.zeros(2 * n), ub=np.full(2 * n, float(C)), x0=np.zeros(2 * n))
+    if n_test > 0:
+        rt = np.random.default_rng(seed + 1000)
+        Xt = draw(rt, n_test)
+        out.update(X_test=Xt, t_test=Xt @ w + b_true + noise * rt.standard_normal(n_test))
+    return out
+
+
 def svm_blobs(N, d, K, sep, seed, N_test=0, sparse=None):
     """K classes for SVMMulticlass, K <= d.  Sample i has the label i mod K (as a float) and x_i = sep e_label + noise, all draws from default_rng(seed).
     sparse=None: N(0,1) noise in every entry.  sparse=m: N(0,1) noise in m distinct columns per sample, chosen uniformly; sep is then added in the column of the

@@ -1,0 +1,187 @@
+"""SVR front end (pmh_svr_*, csrc/svr_train.hip): linear epsilon-insensitive support vector regression, trained and scored on the device.
+
+    L1: primal 1/2 |w|^2 + sum C_i max(0, |x_i . w + b - t_i| - eps)
+    L2: primal 1/2 |w|^2 + 1/2 sum C_i max(0, |x_i . w + b - t_i| - eps)^2,      C_i = C sample_weight_i
+    dual in u = [p; q]: min 1/2 u'H^u - c^'u, H^ = [Q + D, -Q; -Q, Q + D] (MatCreateSVRDual), c^ = [t - eps; -t - eps], 0 <= u (L1: <= C_i)
+    bias: additionally sum (p_i - q_i) = 0 (SMALXE over a one-row projector; without bias MPGP alone)
+
+Model: w = X'(p - q), f(x) = x . w + b.  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width, kept ONCE on the device.  Everything is
+computed by libpermonhip.so; there is no CPU fallback.  Not here: subsets, cross-validation, warm starts, a grid search (SVM has them)."""
+import ctypes as ct
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .core import Vec, sample_dtype_of
+from .mat import is_sparse
+from .svm import _Samples, _vecs
+
+
+class SVR:
+    def __init__(self, ctx, loss="L1", C=1.0, epsilon=0.1, bias=True, options="", sample_dtype=None):
+        """options: a PETSc-style option string for the solver (-qps_rtol 1e-6, -qps_mpgp_*, -qps_smalxe_*, -smalxe_qps_* ...) and -svr_loss_type / -svr_C /
+        -svr_epsilon / -svr_bias, which override the keyword arguments.  sample_dtype: as in SVM (numpy.float32 keeps dense samples in float32 on the device)."""
+        self.ctx, self.L = ctx, ctx.L
+        self.sample_dtype = sample_dtype_of(sample_dtype, False, "SVR")
+        o = _lib.SvrOpts()
+        check(self.L.pmh_svr_default_opts(o))
+        if loss not in ("L1", "L2"):
+            raise ValueError("SVR: loss must be \"L1\" or \"L2\"")
+        o.loss_type, o.C, o.epsilon, o.bias = int(loss == "L2"), float(C), float(epsilon), int(bool(bias))  # (checked by pmh_svr_create)
+        left = ct.create_string_buffer(4096)
+        check(self.L.pmh_svr_set_from_options(options.encode(), o, left, len(left)))
+        self.opts = o
+        self.options_left = [k for k in left.value.decode().split() if k]
+        self.h = None
+        self._keep = None
+
+    loss = property(lambda self: "L2" if self.opts.loss_type == 1 else "L1")
+    C = property(lambda self: self.opts.C)
+    epsilon = property(lambda self: self.opts.epsilon)
+    bias = property(lambda self: bool(self.opts.bias))
+
+    def _dev(self, a):
+        return a if isinstance(a, Vec) else Vec.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.float64).ravel())
+
+    def _need(self):
+        if self.h is None:
+            raise RuntimeError("SVR: call fit first")
+
+    def _entry(self, name, sparse, f32=False):
+        return getattr(self.L, "pmh_svr_" + name + ("_csr" if sparse else "_f32" if f32 else ""))
+
+    def create(self, X, t, sample_weight=None):
+        """Set the training samples (X: (n, d) row-major ndarray or scipy.sparse matrix; t: n finite targets) and build the solver without training.  The handle
+        borrows both for its lifetime.  sample_weight: n positive numbers that scale the samples' penalties (None: all 1)."""
+        sample_dtype_of(self.sample_dtype, is_sparse(X), "SVR")  # (float32 with sparse samples is refused)
+        self.destroy()
+        S = _Samples(self.ctx, X, with_d=True, dtype=self.sample_dtype)
+        if S.X.ndim != 2:
+            raise ValueError("SVR: X must be (n, d)")
+        self.n, self.d = S.X.shape
+        tn = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        if tn.size != self.n:
+            raise ValueError("SVR: t must have %d entries" % self.n)
+        h = ct.c_void_p()
+        with S as (n, xa):
+            td = Vec.from_numpy(self.ctx, tn)
+            try:
+                check(self._entry("create", S.sparse, S.f32)(self.ctx.h, *xa, td.p, self.opts, ct.byref(h)))
+            except Exception:
+                td.free()
+                raise
+            self.h, self._keep = h, (S.keep(), td)
+        if sample_weight is not None:
+            self.set_penalties(sample_weight=sample_weight)
+        return self
+
+    def destroy(self):
+        if self.h is not None:
+            self.L.pmh_svr_destroy(self.h)
+            self.h = None
+            for v in self._keep or ():
+                v.destroy() if hasattr(v, "destroy") else v.free()
+            self._keep = None
+
+    def set_penalties(self, C=None, sample_weight=None):
+        """C_i = C sample_weight_i on the created handle (pmh_svr_set_penalties; None: the handle's C, all 1); the handle is untrained afterwards."""
+        self._need()
+        wd = None if sample_weight is None else self._dev(sample_weight)
+        try:
+            if wd is not None and wd.n != self.n:
+                raise ValueError("SVR: sample_weight must have %d entries" % self.n)
+            check(self.L.pmh_svr_set_penalties(self.h, float(self.C if C is None else C), wd.p if wd is not None else None))
+        finally:
+            if wd is not None and wd is not sample_weight:
+                wd.free()
+        return self
+
+    def set_epsilon(self, epsilon):
+        """A new epsilon on the created handle (pmh_svr_set_epsilon): the right-hand side alone changes; the handle is untrained afterwards."""
+        self._need()
+        check(self.L.pmh_svr_set_epsilon(self.h, float(epsilon)))
+        self.opts.epsilon = float(epsilon)
+        return self
+
+    def train(self):
+        """Train from u = 0 (pmh_svr_train)."""
+        self._need()
+        check(self.L.pmh_svr_train(self.h))
+        return self
+
+    def fit(self, X, t, sample_weight=None):
+        return self.create(X, t, sample_weight).train()
+
+    @property
+    def w(self):
+        self._need()
+        w = np.empty(self.d)
+        check(self.L.pmh_svr_get_model(self.h, w.ctypes.data_as(ct.c_void_p), None))
+        return w
+
+    @property
+    def b(self):
+        self._need()
+        b = ct.c_double()
+        check(self.L.pmh_svr_get_model(self.h, None, ct.byref(b)))
+        return b.value
+
+    @property
+    def alpha(self):
+        """(2 n,): the dual [p; q] (pmh_svr_get_dual)."""
+        self._need()
+        with _vecs(self.ctx, 2 * self.n) as (v,):
+            check(self.L.pmh_svr_get_dual(self.h, v.p))
+            return v.to_numpy()
+
+    @property
+    def beta(self):
+        """(n,): p - q, the coefficients of w = X'beta."""
+        u = self.alpha
+        return u[:self.n] - u[self.n:]
+
+    @property
+    def stats(self):
+        self._need()
+        st = _lib.SvrStats()
+        check(self.L.pmh_svr_get_stats(self.h, ct.byref(st)))
+        return st
+
+    def solver_handles(self):
+        """(H, pf, mpgp, smalxe) as ctypes handles, borrowed (pmh_svr_get_solver); a solver not in use is None."""
+        self._need()
+        v = [ct.c_void_p() for _ in range(4)]
+        check(self.L.pmh_svr_get_solver(self.h, *[ct.byref(x) for x in v]))
+        return tuple(x if x.value else None for x in v)
+
+    def _test_samples(self, X):
+        """X for a scoring call: refused before any upload unless it is (n, d)."""
+        self._need()
+        S = _Samples(self.ctx, X, dtype=self.sample_dtype)
+        if S.X.ndim != 2 or S.X.shape[1] != self.d:
+            raise ValueError("SVR: X must be (n, %d)" % self.d)
+        return S
+
+    def predict(self, X):
+        """(n,): f(x_i) = x_i . w + b in one pass over X (pmh_svr_predict)."""
+        S = self._test_samples(X)
+        with S as (n, xa), _vecs(self.ctx, n) as (f,):
+            check(self._entry("predict", S.sparse, S.f32)(self.h, *xa, f.p))
+            return f.to_numpy()
+
+    def test(self, X, t):
+        """Scores X and reduces the residuals r = f(x) - t in the same pass (pmh_svr_test): dict(mse, mae, r2, max_abs, n_in_tube, n) and the sums they come
+        from (sum_r, sum_r2, sum_abs_r, sum_t, sum_t2)."""
+        S = self._test_samples(X)
+        tn = np.ascontiguousarray(t, dtype=np.float64).ravel()
+        if tn.size != S.X.shape[0]:
+            raise ValueError("SVR: t must have %d entries" % S.X.shape[0])
+        m = _lib.SvrMetrics()
+        with S as (n, xa):
+            td = Vec.from_numpy(self.ctx, tn)
+            try:
+                check(self._entry("test", S.sparse, S.f32)(self.h, *xa, td.p, ct.byref(m)))
+            finally:
+                td.free()
+        return {k: getattr(m, k) for k, _ in _lib.SvrMetrics._fields_}
