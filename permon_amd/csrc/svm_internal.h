@@ -132,9 +132,7 @@ int pmh_svm_colsum(pmh_ctx ctx, int nblocks, int d, const double *part, double *
 // 1 (and c, with row = c y) if pf is a one-row projector whose row is a multiple of this operator's labels, entry by entry
 int pmh_svm_op_row_is_labels(SvmDualBase *o, pmh_qppf pf, double *c);
 
-// ---- svm_train.hip / svm_proba.hip: what the probability model shares across translation units ---------------------------------------------------------
-// out[k] = sum_b part[k][b], k < K (k_svm_sum_rows: one workgroup, fixed order), enqueue only
-int pmh_svm_sum_rows(pmh_ctx ctx, int nb, int K, const double *part, double *out);
+// ---- svm_train.hip / svm_proba.hip: what the probability model shares across translation units (the sums and their finishing kernel: svm_front.h) ---------------------------------------------------------
 // The Platt fit on scores[i * stride], i < n (column k of an n x K score matrix in place: scores + k, stride K).  The target of sample i is the positive one
 // where y[i] == pos.  binary: every label must be +-1 (else PMH_ERR_ARG with the count); otherwise every label that is not pos is "the rest"
 int pmh_svm_platt_fit_strided(pmh_ctx ctx, int n, const double *scores, int stride, const double *y, double pos, int binary, double *A, double *B, pmh_svm_platt_stats *st);

@@ -5,14 +5,13 @@
 //   F = sum_i F_i,  F_i = t_i z_i + log(1 + e^{-z_i}),   dF/dA = g1 = sum f_i (t_i - p_i),   dF/dB = g2 = sum (t_i - p_i),
 //   h11 = sum f_i^2 p_i (1 - p_i),  h22 = sum p_i (1 - p_i),  h21 = sum f_i p_i (1 - p_i).
 // k_svm_platt_sums forms all six in one pass over the scores for one point (A, B): the point a line search accepts then has its gradient and Hessian already.
-// The order of every sum is fixed: per-thread sums over i = tid, tid + grid, .., pmh_block_reduce one sum after the other -> part[6][grid], then
-// k_svm_sum_rows (svm_train.hip) over the workgroups; the grid is a function of n alone.  No float atomics: two fits give the same bits.  Six doubles cross to
+// The order of every sum is fixed: per-thread sums over i = tid, tid + grid, .., pmh_block_reduce one sum after the other -> part[6][grid] (svm_store), then
+// k_svm_finish (svm_front.hip) over the workgroups; the grid is a function of n alone.  No float atomics: two fits give the same bits.  Six doubles cross to
 // the host per evaluated point, where the Newton step and the backtracking run.  The kernels that apply the model (svm_train.hip, svm_multi.hip) take the
 // sigmoid in the same two branches (svm_sigmoid, svm_rows.h).
 #include <cmath>
 
-#include "reduce.h"
-#include "svm_internal.h"
+#include "svm_front.h"
 
 // The constants of Lin, Lin and Weng's algorithm (their Appendix 3 / sigmoid_train): not tunables
 static const int    PLATT_MAX_IT   = 100;   // Newton iterations at most
@@ -20,17 +19,6 @@ static const double PLATT_MIN_STEP = 1e-10; // the line search gives up below th
 static const double PLATT_SIGMA    = 1e-12; // added to h11 and h22: the Hessian stays positive definite
 static const double PLATT_EPS      = 1e-5;  // stop when |g1| and |g2| are below
 static const double PLATT_ARMIJO   = 1e-4;  // sufficient decrease: F_new < F + PLATT_ARMIJO step (g . d)
-
-// the six sums a thread holds -> part[6][gridDim.x] (svm_store4's order, for six)
-static __device__ __forceinline__ void svm_store6(const double (&s)[6], double *red, double *__restrict__ part)
-{
-  const size_t g = gridDim.x;
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const double r = pmh_block_reduce<PMH_RED_SUM>(s[k], red);
-    if (threadIdx.x == 0) part[k * g + blockIdx.x] = r;
-  }
-}
 
 // One pass over the scores f_i = scores[i stride] for the point (A, B): F, g1, g2, h11, h22, h21 -> part[6][gridDim.x].  The target of sample i is tpos where
 // y[i] == pos, else tneg.  The objective and the sigmoid in the two-branch form that cannot overflow
@@ -52,25 +40,21 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svm_platt_sums(int n, const doubl
     const double q = p * (1.0 - p), r = t - p;
     s[0] += Fi, s[1] += f * r, s[2] += r, s[3] += f * f * q, s[4] += q, s[5] += f * q;
   }
-  svm_store6(s, red, part);
+  svm_store<6>(s, red, part);
 }
 
 // the class counts: y[i] == pos, the rest, and (binary) the labels that are neither pos nor -pos, which count in neither class -> part[3][gridDim.x]
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_platt_count(int n, const double *__restrict__ y, double pos, int binary, double *__restrict__ part)
 {
   __shared__ double red[PMH_BLOCK / 64];
-  double            np = 0.0, nn = 0.0, no = 0.0;
+  double            c[3] = {0.0, 0.0, 0.0}; // y[i] == pos, the rest, neither
   for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
     const double yi = y[i];
-    if (yi == pos) np += 1.0;
-    else if (!binary || yi == -pos) nn += 1.0;
-    else no += 1.0;
+    if (yi == pos) c[0] += 1.0;
+    else if (!binary || yi == -pos) c[1] += 1.0;
+    else c[2] += 1.0;
   }
-  const double r0 = pmh_block_reduce<PMH_RED_SUM>(np, red), r1 = pmh_block_reduce<PMH_RED_SUM>(nn, red), r2 = pmh_block_reduce<PMH_RED_SUM>(no, red);
-  if (threadIdx.x == 0) {
-    const size_t g = gridDim.x;
-    part[blockIdx.x] = r0, part[g + blockIdx.x] = r1, part[2 * g + blockIdx.x] = r2;
-  }
+  svm_store<3>(c, red, part);
 }
 
 namespace {
@@ -84,9 +68,7 @@ struct platt_fit {
   // h[0..5] = the sums over all workgroups and ranks
   int           finish(int K, double *h)
   {
-    if (n > 0) PMH_CHK(pmh_svm_sum_rows(ctx, nb, K, part, scal));
-    else PMH_CHK(pmh_memset(ctx, scal, 0, sizeof(double) * (size_t)K));
-    if (pmh_comm_on(ctx)) PMH_CHK(pmh_comm_allreduce_sum(ctx, scal, (size_t)K));
+    PMH_CHK(pmh_svm_finish_part(ctx, n, nb, K, -1, part, scal));
     return pmh_memcpy_d2h(ctx, h, scal, sizeof(double) * (size_t)K);
   }
   int count(int binary, double *h)

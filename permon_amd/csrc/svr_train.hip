@@ -1,97 +1,44 @@
-// SVR front end: linear epsilon-insensitive support vector regression over the dual operators of svr.hip, the route of svm_train.hip:
+// SVR front end: linear epsilon-insensitive support vector regression over the dual operators of svr.hip, on the training core of svm_front.h (sv_front: the
+// solver, the statistics, the model's tail and the buffers are those of svm_train.hip):
 //   dual in u = [p; q]:  min 1/2 u'H^u - c^'u,  c^ = [t - eps; -t - eps],  L1: 0 <= u <= [C_i; C_i] (D = 0),  L2: 0 <= u (D = diag(1 / C_i))
 //   bias: additionally sum (p_i - q_i) = 0, posed as ([1; -1] / sqrt(2 n))'u = 0 -- a one-row projector under SMALXE whose penalty term the operator absorbs
-// No bias: MPGP on the box alone.  Model: w = X'(p - q) by the operator's pass 1; b by one pass over X (k_svr_bias: the sums of svr_bias_row); prediction and
-// the regression metrics by one pass over the test samples (k_svr_score / k_svr_score64 on the sweeps of svm_rows.h).  Samples in CSR: x_i . w by the
-// entry-balanced row sweep of svm_csr.hip, then one kernel over the n dot products (k_svr_bias_dots, k_svr_score_dots).  Dense samples in float32: the same
-// kernels with the sample type as template argument.  Every sum leaves a workgroup through svr_store and is finished by one workgroup in a fixed order.
-#include <cmath>
+// No bias: MPGP on the box alone.  Model: w = X'(p - q) by the operator's pass 1; b by one pass over X (svr_bias_f); prediction and the regression metrics by
+// one pass over the test samples (svr_score_f), both on the kernel shells of svm_front.h, picked by sv_sweep: dense rows in fp64 or float32, d == 64, or CSR
+// (x_i . w by the entry-balanced row sweep of svm_csr.hip, then one thread per dot product).  Every sum leaves a workgroup through svm_store and is finished by
+// one workgroup in a fixed order.  Here: epsilon, the doubled right-hand side, the [1; -1] row, the metrics.
+#include "svm_front.h"
 
-#include "svr_internal.h"
-#include "svm_rows.h"
-
-struct pmh_svr_s {
-  pmh_ctx       ctx;
-  int           n, d; // samples of this rank, features
-  long long     n_global;
-  const void   *X; // dense rows: doubles, or floats where f32
-  int           f32 = 0;
-  pmh_csr       Xcsr = nullptr; // the samples in CSR (then X == nullptr), borrowed
-  const double *t;
-  pmh_svr_opts  o;
-  pmh_op        H    = nullptr;
-  pmh_qppf      pf   = nullptr;
-  pmh_mpgp      mpgp = nullptr;
-  pmh_smalxe    sx   = nullptr;
-  double       *u = nullptr, *rhs = nullptr, *lb = nullptr, *ub = nullptr, *row = nullptr; // 2 n each (ub: L1 only; row: bias only)
-  double       *w = nullptr, *part = nullptr, *scal = nullptr, *dots = nullptr;
-  double       *Cv = nullptr, *Cinv = nullptr; // pmh_svr_set_penalties: C_i and, L2, 1 / C_i (n doubles); nullptr: opts.C everywhere
-  std::vector<double> h_w;
-  double        b = 0.0;
-  int           trained = 0;
+struct pmh_svr_s : sv_front { // (nu = 2 n: u = [p; q])
+  const double *t = nullptr;
+  double        C = 0.0, epsilon = 0.0;
   pmh_svr_stats st;
 };
 
-#define SVR_NSUM 7 // the most sums a kernel here leaves per workgroup (k_svr_score); the bias kernels leave 4
-
-// K sums of a thread reduced over the workgroup one after the other -> part[K][gridDim.x]; MINROW: that row is a minimum (max |r| travels as -|r|)
-template <int K, int MINROW = -1> static __device__ __forceinline__ void svr_store(const double (&s)[K], double *red, double *__restrict__ part)
-{
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    const double r = k == MINROW ? pmh_block_reduce<PMH_RED_MIN>(s[k], red) : pmh_block_reduce<PMH_RED_SUM>(s[k], red);
-    if (threadIdx.x == 0) part[(size_t)k * gridDim.x + blockIdx.x] = r;
-  }
-}
-// out[k] = sum (k == minrow: min) over b of part[k][b]: one workgroup, fixed order
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_finish(int nb, int K, int minrow, const double *__restrict__ part, double *__restrict__ out)
-{
-  __shared__ double red[PMH_BLOCK / 64];
-  for (int k = 0; k < K; k++) {
-    const bool mn = k == minrow;
-    double     v  = mn ? INFINITY : 0.0;
-    for (int b = threadIdx.x; b < nb; b += PMH_BLOCK) v = mn ? fmin(v, part[(size_t)k * nb + b]) : v + part[(size_t)k * nb + b];
-    v = mn ? pmh_block_reduce<PMH_RED_MIN>(v, red) : pmh_block_reduce<PMH_RED_SUM>(v, red);
-    if (threadIdx.x == 0) out[k] = v;
-  }
-}
+#define SVR_NSUM 7 // the most sums a kernel here leaves per workgroup (svr_score_f); the bias leaves 4
 
 // ---- the bias -------------------------------------------------------------------------------------------------------------------------------------------------
-struct svr_bias_args {
-  const double *t, *p, *q, *ubv, *dv; // ubv: the upper bound of sample i (per-sample penalties, L1) or nullptr: ub; dv: D_i (L2) or nullptr: dsc
-  double        eps, astol, ub, dsc;  // ub <= 0: no upper bound (L2); dsc: the scalar D (L1: 0)
-};
 // sample i with dot = x_i . w in s[0]: the sum over the free entries of t_i - eps - D_i p_i - dot (a free p_i) and t_i + eps + D_i q_i - dot (a free q_i), each
 // evaluated left to right; s[1]: sum (p_i - q_i); s[2]: free entries; s[3]: entries above astol.  free: astol < u_k and (ub > 0: u_k < ub - astol)
-static __device__ __forceinline__ void svr_bias_row(const svr_bias_args &a, long long i, double dot, double (&s)[4])
-{
-  const double pi = a.p[i], qi = a.q[i], ti = a.t[i], ub = a.ubv ? a.ubv[i] : a.ub, D = a.dv ? a.dv[i] : a.dsc;
-  s[1] += pi - qi;
-  if (pi > a.astol) {
-    s[3] += 1.0;
-    if (!(ub > 0.0) || pi < ub - a.astol) s[2] += 1.0, s[0] += ((ti - a.eps) - D * pi) - dot;
+struct svr_bias_f {
+  const double *t, *p, *q, *ubv, *dv; // ubv: the upper bound of sample i (per-sample penalties, L1) or nullptr: ub; dv: D_i (L2) or nullptr: dsc
+  double        eps, astol, ub, dsc;  // ub <= 0: no upper bound (L2); dsc: the scalar D (L1: 0)
+  double       *part;                 // -> part[4][gridDim.x]
+  double        s[4] = {0.0, 0.0, 0.0, 0.0};
+  __device__ __forceinline__ void row(long long i, double dot)
+  {
+    const double pi = p[i], qi = q[i], ti = t[i], ubi = ubv ? ubv[i] : ub, D = dv ? dv[i] : dsc;
+    s[1] += pi - qi;
+    if (pi > astol) {
+      s[3] += 1.0;
+      if (!(ubi > 0.0) || pi < ubi - astol) s[2] += 1.0, s[0] += ((ti - eps) - D * pi) - dot;
+    }
+    if (qi > astol) {
+      s[3] += 1.0;
+      if (!(ubi > 0.0) || qi < ubi - astol) s[2] += 1.0, s[0] += ((ti + eps) + D * qi) - dot;
+    }
   }
-  if (qi > a.astol) {
-    s[3] += 1.0;
-    if (!(ub > 0.0) || qi < ub - a.astol) s[2] += 1.0, s[0] += ((ti + a.eps) + D * qi) - dot;
-  }
-}
-// One pass over X for the bias -> part[4][gridDim.x]
-template <class T>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_bias(int n, int d, const T *__restrict__ X, const double *__restrict__ w, svr_bias_args a, double *__restrict__ part)
-{
-  __shared__ double red[PMH_BLOCK / 64];
-  double            s[4] = {0.0, 0.0, 0.0, 0.0};
-  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { svr_bias_row(a, i, dot, s); });
-  svr_store<4>(s, red, part);
-}
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_bias_dots(int n, const double *__restrict__ dots, svr_bias_args a, double *__restrict__ part)
-{
-  __shared__ double red[PMH_BLOCK / 64];
-  double            s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) svr_bias_row(a, i, dots[i], s);
-  svr_store<4>(s, red, part);
-}
+  __device__ __forceinline__ void done(double *red) { svm_store<4>(s, red, part); }
+};
 
 // ---- prediction and the metrics ---------------------------------------------------------------------------------------------------------------------------------
 // sample i with the score f = x_i . w + b: f -> scores (where given) and, with targets, r = f - t_i in the seven sums: sum r, sum r^2, sum |r|, -max |r|, sum t,
@@ -104,34 +51,19 @@ static __device__ __forceinline__ void svr_score_row(long long i, double f, doub
     s[0] += r, s[1] += r * r, s[2] += ar, s[3] = fmin(s[3], -ar), s[4] += ti, s[5] += ti * ti, s[6] += ar <= eps ? 1.0 : 0.0;
   }
 }
-#define SVR_SUMS_INIT {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0} // (-max |r| starts at -0: no sample, max 0)
-template <class T>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_score(int n, int d, const T *__restrict__ X, const double *__restrict__ w, double b, double *scores, const double *__restrict__ t, double eps,
-                                                         double *__restrict__ part)
-{
-  __shared__ double red[PMH_BLOCK / 64];
-  double            s[SVR_NSUM] = SVR_SUMS_INIT;
-  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { svr_score_row(i, dot + b, scores, t, eps, s); });
-  if (t) svr_store<SVR_NSUM, 3>(s, red, part); // (uniform: a kernel argument)
-}
-// d == 64: the row layout of k_svr_x64, four row groups in flight
-template <class T>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_score64(int n, const T *__restrict__ X, const double *__restrict__ w, double b, double *scores, const double *__restrict__ t, double eps,
-                                                           double *__restrict__ part)
-{
-  __shared__ double red[PMH_BLOCK / 64];
-  double            s[SVR_NSUM] = SVR_SUMS_INIT;
-  svm_sweep_rows64<4>(n, X, w, [&](long long i, double dot) { svr_score_row(i, dot + b, scores, t, eps, s); });
-  if (t) svr_store<SVR_NSUM, 3>(s, red, part);
-}
-// (dots and scores may be the same array)
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_score_dots(int n, const double *dots, double b, double *scores, const double *__restrict__ t, double eps, double *__restrict__ part)
-{
-  __shared__ double red[PMH_BLOCK / 64];
-  double            s[SVR_NSUM] = SVR_SUMS_INIT;
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) svr_score_row(i, dots[i] + b, scores, t, eps, s);
-  if (t) svr_store<SVR_NSUM, 3>(s, red, part);
-}
+struct svr_score_f {
+  double        b;
+  double       *scores;
+  const double *t;
+  double        eps;
+  double       *part;                                              // -> part[SVR_NSUM][gridDim.x]
+  double        s[SVR_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // (-max |r| starts at -0: no sample, max 0)
+  __device__ __forceinline__ void row(long long i, double dot) { svr_score_row(i, dot + b, scores, t, eps, s); }
+  __device__ __forceinline__ void done(double *red)
+  {
+    if (t) svm_store<SVR_NSUM, 3>(s, red, part); // (uniform: a kernel argument)
+  }
+};
 
 // ---- the vectors of the QP ------------------------------------------------------------------------------------------------------------------------------------
 // rhs = [t - eps; -t - eps]
@@ -171,25 +103,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svr_fill_penalties(int n, const d
     if (Cinv) Cinv[i] = 1.0 / ci;
   }
 }
-// the count an int-counting kernel leaves (launch: what runs it on d_bad), summed over the ranks so that every rank decides alike
-template <class L> static int svr_count_bad(pmh_ctx ctx, const char *who, L launch, long long *nbad)
-{
-  int  bad   = 0;
-  int *d_bad = nullptr;
-  PMH_CHK(pmh_malloc(ctx, sizeof(int), (void **)&d_bad));
-  int rc = pmh_memset(ctx, d_bad, 0, sizeof(int));
-  if (!rc) {
-    launch(d_bad);
-    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "%s: the launch that checks the values failed", who);
-  }
-  if (!rc) rc = pmh_memcpy_d2h(ctx, &bad, d_bad, sizeof(int));
-  pmh_free(ctx, d_bad);
-  PMH_CHK(rc);
-  double c = (double)bad;
-  PMH_CHK(pmh_comm_sum_host(ctx, &c, 1));
-  *nbad = (long long)c;
-  return PMH_SUCCESS;
-}
 
 extern "C" int pmh_svr_default_opts(pmh_svr_opts *o)
 {
@@ -207,47 +120,25 @@ extern "C" int pmh_svr_default_opts(pmh_svr_opts *o)
 extern "C" int pmh_svr_destroy(pmh_svr s)
 {
   if (!s) return PMH_SUCCESS;
-  if (s->mpgp) pmh_mpgp_destroy(s->mpgp);
-  if (s->sx) pmh_smalxe_destroy(s->sx);
-  if (s->pf) pmh_qppf_destroy(s->pf);
-  if (s->H) pmh_op_destroy(s->H);
-  double *v[] = {s->u, s->rhs, s->lb, s->ub, s->row, s->w, s->part, s->scal, s->dots, s->Cv, s->Cinv};
-  for (double *p : v)
-    if (p) pmh_free(s->ctx, p);
+  sv_free(s);
   delete s;
   return PMH_SUCCESS;
 }
 
-// The solver over the handle's operator, vectors and projector: SMALXE (bias) or MPGP, built as svm_train.hip builds them.  Both size their steps by the
-// operator's largest eigenvalue, estimated at creation: whoever changes the operator's terms builds the solver anew
-static int svr_build_solver(pmh_svr s)
-{
-  if (s->mpgp) pmh_mpgp_destroy(s->mpgp), s->mpgp = nullptr;
-  if (s->sx) pmh_smalxe_destroy(s->sx), s->sx = nullptr;
-  if (s->o.bias) {
-    pmh_smalxe_opts so = s->o.smalxe;
-    so.rtol = s->o.qps.rtol, so.atol = s->o.qps.atol, so.divtol = s->o.qps.divtol;
-    if (s->o.qps.max_it_set) so.max_it = s->o.qps.max_it;
-    return pmh_smalxe_create(s->ctx, s->H, s->rhs, s->u, s->lb, s->ub, s->pf, &so, &s->sx);
-  }
-  pmh_mpgp_opts mo = s->o.mpgp;
-  mo.rtol = s->o.qps.rtol, mo.atol = s->o.qps.atol, mo.divtol = s->o.qps.divtol, mo.max_it = s->o.qps.max_it;
-  return pmh_mpgp_create(s->ctx, s->H, s->rhs, s->u, s->lb, s->ub, &mo, &s->mpgp);
-}
 // L2: the operator's D: the shift 1 / C or the diagonal 1 / C_i
 static int svr_refresh_l2(pmh_svr s)
 {
-  if (s->o.loss_type != PMH_SVM_LOSS_L2) return PMH_SUCCESS;
+  if (s->loss_type != PMH_SVM_LOSS_L2) return PMH_SUCCESS;
   if (s->Cinv) {
     PMH_CHK(pmh_op_svr_dual_set_terms(s->H, 0.0, 0.0));
     return pmh_op_svr_dual_set_diag(s->H, s->Cinv);
   }
   PMH_CHK(pmh_op_svr_dual_set_diag(s->H, nullptr));
-  return pmh_op_svr_dual_set_terms(s->H, 1.0 / s->o.C, 0.0);
+  return pmh_op_svr_dual_set_terms(s->H, 1.0 / s->C, 0.0);
 }
 static int svr_fill_rhs(pmh_svr s)
 {
-  if (s->n > 0) hipLaunchKernelGGL(k_svr_fill_rhs, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, s->t, s->o.epsilon, s->rhs);
+  if (s->n > 0) hipLaunchKernelGGL(k_svr_fill_rhs, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, s->t, s->epsilon, s->rhs);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
@@ -264,32 +155,22 @@ static int svr_create(pmh_ctx ctx, int n, int d, const void *X_dev, int f32, pmh
   if (!(opts->C > 0.0) || !std::isfinite(opts->C)) return pmh_set_error(PMH_ERR_ARG, "pmh_svr_create: C = %g, must be positive and finite", opts->C);
   PMH_CHK(svr_check_epsilon("pmh_svr_create", opts->epsilon));
   long long nbad = 0;
-  PMH_CHK(svr_count_bad(ctx, "pmh_svr_create", [&](int *d_bad) {
-    if (n > 0) hipLaunchKernelGGL(k_svr_targets_bad, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, t_dev, d_bad);
+  PMH_CHK(sv_count_bad(ctx, "pmh_svr_create", "values", [&](int *cnt) {
+    if (n > 0) hipLaunchKernelGGL(k_svr_targets_bad, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, t_dev, cnt);
   }, &nbad));
   if (nbad) return pmh_set_error(PMH_ERR_ARG, "pmh_svr_create: %lld of the targets are not finite", nbad);
   pmh_svr s = new pmh_svr_s();
-  s->ctx = ctx, s->n = n, s->d = d, s->X = X_dev, s->f32 = f32, s->Xcsr = Xcsr, s->t = t_dev, s->o = *opts;
+  s->ctx = ctx, s->n = n, s->nu = 2 * n, s->d = d, s->X = X_dev, s->f32 = f32, s->Xcsr = Xcsr, s->t = t_dev, s->C = opts->C, s->epsilon = opts->epsilon;
+  sv_take_opts(s, *opts);
   memset(&s->st, 0, sizeof(s->st));
   const size_t nb2 = sizeof(double) * 2 * (size_t)(n ? n : 1);
   int          rc  = PMH_SUCCESS;
   do {
     if ((rc = Xcsr ? pmh_op_create_svr_dual_csr(ctx, Xcsr, &s->H) : (f32 ? pmh_op_create_svr_dual_f32(ctx, n, d, (const float *)X_dev, &s->H) : pmh_op_create_svr_dual(ctx, n, d, (const double *)X_dev, &s->H)))) break;
     if ((rc = svr_refresh_l2(s))) break;
-    if ((rc = pmh_malloc(ctx, nb2, (void **)&s->u)) || (rc = pmh_malloc(ctx, nb2, (void **)&s->rhs)) || (rc = pmh_malloc(ctx, nb2, (void **)&s->lb))) break;
-    if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)d, (void **)&s->w)) || (rc = pmh_malloc(ctx, sizeof(double) * SVR_NSUM * PMH_MAX_VEC_BLOCKS, (void **)&s->part)) || (rc = pmh_malloc(ctx, sizeof(double) * 8, (void **)&s->scal))) break;
-    if ((rc = pmh_memset(ctx, s->u, 0, nb2)) || (rc = pmh_memset(ctx, s->lb, 0, nb2)) || (rc = svr_fill_rhs(s))) break;
-    if (opts->loss_type == PMH_SVM_LOSS_L1) {
-      if ((rc = pmh_malloc(ctx, nb2, (void **)&s->ub)) || (rc = pmh_vec_set(ctx, 2 * n, s->ub, opts->C))) break;
-    }
-    double ng = (double)n; // the number of samples over all ranks (the row of the equality is [1; -1] / sqrt(2 n))
-    if ((rc = pmh_comm_sum_host(ctx, &ng, 1))) break;
-    s->n_global = (long long)ng;
+    if ((rc = sv_alloc_common(s, SVR_NSUM, opts->C)) || (rc = svr_fill_rhs(s))) break;
+    if ((rc = sv_count_samples(s, "pmh_svr_create"))) break; // (the row of the equality is [1; -1] / sqrt(2 n))
     if (opts->bias) {
-      if (s->n_global < 1) {
-        rc = pmh_set_error(PMH_ERR_ARG, "pmh_svr_create: no samples");
-        break;
-      }
       if ((rc = pmh_malloc(ctx, nb2, (void **)&s->row))) break;
       if (n > 0) hipLaunchKernelGGL(k_svr_fill_row, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, 1.0 / sqrt(2.0 * (double)s->n_global), s->row);
       if (hipGetLastError() != hipSuccess) {
@@ -298,7 +179,7 @@ static int svr_create(pmh_ctx ctx, int n, int d, const void *X_dev, int f32, pmh
       }
       if ((rc = pmh_qppf_create_onerow(ctx, s->row, 2 * n, &s->pf))) break;
     }
-    if ((rc = svr_build_solver(s))) break;
+    if ((rc = sv_build_solver(s))) break;
   } while (0);
   if (rc) {
     pmh_svr_destroy(s);
@@ -328,93 +209,45 @@ extern "C" int pmh_svr_set_penalties(pmh_svr s, double C, const double *weight_d
   if (!(C > 0.0) || !std::isfinite(C)) return pmh_set_error(PMH_ERR_ARG, "pmh_svr_set_penalties: C = %g, must be positive and finite", C);
   pmh_ctx      ctx = s->ctx;
   const int    n   = s->n;
-  const size_t nb  = sizeof(double) * (size_t)(n ? n : 1);
-  const bool   L2  = s->o.loss_type == PMH_SVM_LOSS_L2;
+  const bool   L2  = s->loss_type == PMH_SVM_LOSS_L2;
   if (weight_dev) {
     long long nbad = 0;
-    PMH_CHK(svr_count_bad(ctx, "pmh_svr_set_penalties", [&](int *d_bad) {
-      if (n > 0) hipLaunchKernelGGL(k_svr_weights_bad, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, weight_dev, C, d_bad);
+    PMH_CHK(sv_count_bad(ctx, "pmh_svr_set_penalties", "values", [&](int *cnt) {
+      if (n > 0) hipLaunchKernelGGL(k_svr_weights_bad, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, weight_dev, C, cnt);
     }, &nbad));
     if (nbad) return pmh_set_error(PMH_ERR_ARG, "pmh_svr_set_penalties: %lld of the sample weights are not positive and finite (or give a penalty C_i that is not); a zero weight does not leave a sample out", nbad);
   }
-  if (!s->Cv) PMH_CHK(pmh_malloc(ctx, nb, (void **)&s->Cv));
-  if (L2 && !s->Cinv) PMH_CHK(pmh_malloc(ctx, nb, (void **)&s->Cinv));
+  PMH_CHK(sv_alloc_penalties(s));
   s->trained = 0;
   if (n > 0) {
     hipLaunchKernelGGL(k_svr_fill_penalties, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, weight_dev, C, s->Cv, L2 ? nullptr : s->ub, L2 ? s->Cinv : nullptr);
     PMH_HIP(hipGetLastError());
   }
   PMH_CHK(svr_refresh_l2(s));
-  return svr_build_solver(s);
+  return sv_build_solver(s);
 }
 
 extern "C" int pmh_svr_set_epsilon(pmh_svr s, double epsilon)
 {
   PMH_ARG(s);
   PMH_CHK(svr_check_epsilon("pmh_svr_set_epsilon", epsilon));
-  s->o.epsilon = epsilon;
-  s->trained   = 0;
+  s->epsilon = epsilon;
+  s->trained = 0;
   PMH_CHK(svr_fill_rhs(s));
   // MPGP takes |c^| for its stopping test at its first solve: asked to take it again.  SMALXE sizes eta by |c^| when it is created: built anew
-  if (s->mpgp) return pmh_mpgp_set_tolerances(s->mpgp, s->o.qps.rtol, s->o.qps.atol, s->o.qps.divtol, s->o.qps.max_it);
-  return svr_build_solver(s);
+  if (s->mpgp) return pmh_mpgp_set_tolerances(s->mpgp, s->o_qps.rtol, s->o_qps.atol, s->o_qps.divtol, s->o_qps.max_it);
+  return sv_build_solver(s);
 }
 
-// scal[0 .. K) = the K rows a kernel left in part[K][nb], finished and joined over the ranks (n == 0: no kernel ran: zeros); minrow as in k_svr_finish
-static int svr_sum_part(pmh_svr s, int n, int nb, int K, int minrow)
-{
-  if (n > 0) {
-    hipLaunchKernelGGL(k_svr_finish, dim3(1), dim3(PMH_BLOCK), 0, s->ctx->stream, nb, K, minrow, (const double *)s->part, s->scal);
-    PMH_HIP(hipGetLastError()); // (also the launch of the kernel that filled part)
-  } else PMH_CHK(pmh_memset(s->ctx, s->scal, 0, sizeof(double) * K));
-  if (!pmh_comm_on(s->ctx)) return PMH_SUCCESS;
-  int ops[SVR_NSUM];
-  for (int k = 0; k < K; k++) ops[k] = k == minrow ? PMH_RED_MIN : PMH_RED_SUM;
-  return pmh_comm_allreduce_scalars(s->ctx, s->scal, K, ops);
-}
-
-// w, b and the counts from the current u
+// w, b and the counts from the current u.  Stationarity in a free p_i reads x_i . w + D_i p_i - (t_i - eps) + mu / sqrt(2 n) = 0: b = mu / sqrt(2 n)
 static int svr_model(pmh_svr s)
 {
-  pmh_ctx       ctx = s->ctx;
-  SvrDualBase  *H   = static_cast<SvrDualBase *>(s->H);
-  const double *w   = nullptr;
-  const int     n   = s->n;
-  PMH_CHK(H->form_w(s->u, &w));
-  PMH_CHK(pmh_vec_copy(ctx, s->d, w, s->w));
-  s->h_w.resize((size_t)s->d);
-  const int     nb = SVM_NB(n);
-  const bool    L1 = s->o.loss_type == PMH_SVM_LOSS_L1;
-  svr_bias_args a{s->t, s->u, s->u + n, L1 ? s->Cv : nullptr, L1 ? nullptr : s->Cinv, s->o.epsilon, s->sx ? s->o.smalxe.inner.astol : s->o.mpgp.astol, L1 ? s->o.C : 0.0, L1 ? 0.0 : 1.0 / s->o.C};
-  if (n > 0 && s->Xcsr) {
-    if (!s->dots) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&s->dots));
-    PMH_CHK(H->row_dots(s->w, s->dots));
-    hipLaunchKernelGGL(k_svr_bias_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, (const double *)s->dots, a, s->part);
-  } else if (n > 0) {
-    H->npass++;
-    svm_const<2>(s->f32, [&](auto F) {
-      using T = svm_sample_t<decltype(F)>;
-      hipLaunchKernelGGL(k_svr_bias<T>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, s->d, (const T *)s->X, (const double *)s->w, a, s->part);
-    });
-  }
-  PMH_CHK(svr_sum_part(s, n, nb, 4, -1));
-  // the equality's multiplier: SMALXE keeps B'mu = mu row, so mu = row'(B'mu) / (row'row); with row = [1; -1] / sqrt(2 n) stationarity in a free p_i reads
-  // x_i . w + D_i p_i - (t_i - eps) + mu / sqrt(2 n) = 0: b = mu / sqrt(2 n)
-  if (s->sx) {
-    double *Btmu = nullptr;
-    PMH_CHK(pmh_smalxe_get_penalized(s->sx, nullptr, nullptr, &Btmu));
-    PMH_CHK(pmh_onerow_dot(s->pf, Btmu, 1.0 / s->pf->row_aat, s->scal + 4));
-  } else PMH_CHK(pmh_memset(ctx, s->scal + 4, 0, sizeof(double)));
-  double h[5];
-  PMH_CHK(pmh_memcpy_d2h(ctx, h, s->scal, sizeof(h)));
-  PMH_CHK(pmh_memcpy_d2h(ctx, s->h_w.data(), s->w, sizeof(double) * (size_t)s->d));
-  s->st.sum_beta = h[1], s->st.n_free_sv = (long long)h[2], s->st.n_sv = (long long)h[3];
-  s->st.b_multiplier = h[4] / sqrt(2.0 * (double)(s->n_global > 0 ? s->n_global : 1));
-  s->st.b_free       = h[2] > 0.0 ? h[0] / h[2] : NAN;
-  if (!s->o.bias) s->b = 0.0;
-  else s->b = h[2] > 0.0 ? s->st.b_free : s->st.b_multiplier;
-  s->st.b = s->b;
-  return PMH_SUCCESS;
+  const bool L1 = s->loss_type == PMH_SVM_LOSS_L1;
+  double     h[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  svr_bias_f a{s->t, s->u, s->u + s->n, L1 ? s->Cv : nullptr, L1 ? nullptr : s->Cinv, s->epsilon, s->astol(), L1 ? s->C : 0.0, L1 ? 0.0 : 1.0 / s->C, s->part};
+  const int  rc = sv_model(s, "pmh_svr_train", a, sqrt(2.0 * (double)(s->n_global > 0 ? s->n_global : 1)), &s->st, h);
+  s->st.sum_beta = h[1];
+  return rc;
 }
 
 extern "C" int pmh_svr_train(pmh_svr s)
@@ -422,28 +255,9 @@ extern "C" int pmh_svr_train(pmh_svr s)
   PMH_ARG(s);
   if (!s->sx && !s->mpgp) return pmh_set_error(PMH_ERR_STATE, "pmh_svr_train: the handle has no solver (an earlier pmh_svr_set_penalties / pmh_svr_set_epsilon failed)");
   s->trained = 0;
-  PMH_CHK(pmh_memset(s->ctx, s->u, 0, sizeof(double) * 2 * (size_t)(s->n ? s->n : 1)));
-  long long p0 = 0, p1 = 0;
-  PMH_CHK(pmh_op_svr_dual_passes(s->H, &p0));
-  if (s->sx) {
-    PMH_CHK(pmh_smalxe_reset(s->sx));
-    PMH_CHK(pmh_smalxe_solve(s->sx));
-    pmh_smalxe_stats st;
-    PMH_CHK(pmh_smalxe_get_stats(s->sx, &st));
-    s->st.reason = st.reason, s->st.outer_iterations = st.iteration, s->st.inner_iterations = st.inner_iter_accu;
-    s->st.nmv = st.inner.nmv, s->st.ncg = st.inner.ncg, s->st.nexp = st.inner.nexp, s->st.nprop = st.inner.nprop;
-    s->st.rho = st.rho, s->st.normBu = st.normBu, s->st.rnorm = st.rnorm;
-  } else {
-    PMH_CHK(pmh_mpgp_reset_statistics(s->mpgp)); // (the solver may be kept over trainings: the counters are this solve's)
-    PMH_CHK(pmh_mpgp_solve(s->mpgp));
-    pmh_mpgp_stats st;
-    PMH_CHK(pmh_mpgp_get_stats(s->mpgp, &st));
-    s->st.reason = st.reason, s->st.outer_iterations = 0, s->st.inner_iterations = st.iteration;
-    s->st.nmv = st.nmv, s->st.ncg = st.ncg, s->st.nexp = st.nexp, s->st.nprop = st.nprop;
-    s->st.rho = 0.0, s->st.normBu = 0.0, s->st.rnorm = st.rnorm;
-  }
-  PMH_CHK(pmh_op_svr_dual_passes(s->H, &p1));
-  s->st.passes_X = p1 - p0; // the solve's passes over X (the model's two are not counted)
+  PMH_CHK(pmh_memset(s->ctx, s->u, 0, sizeof(double) * (size_t)(s->nu ? s->nu : 1)));
+  if (s->mpgp) PMH_CHK(pmh_mpgp_reset_statistics(s->mpgp)); // (the solver may be kept over trainings: the counters are this solve's)
+  PMH_CHK(sv_solve(s, &s->st));
   PMH_CHK(svr_model(s));
   s->trained = 1;
   return PMH_SUCCESS;
@@ -452,16 +266,13 @@ extern "C" int pmh_svr_train(pmh_svr s)
 extern "C" int pmh_svr_get_model(pmh_svr s, double *w_host, double *b)
 {
   PMH_ARG(s);
-  if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svr_get_model: call pmh_svr_train first");
-  if (w_host) memcpy(w_host, s->h_w.data(), sizeof(double) * (size_t)s->d);
-  if (b) *b = s->b;
-  return PMH_SUCCESS;
+  return sv_get_model(s, "pmh_svr", w_host, b);
 }
 
 extern "C" int pmh_svr_get_dual(pmh_svr s, double *u_dev)
 {
   PMH_ARG(s && u_dev);
-  return pmh_vec_copy(s->ctx, 2 * s->n, s->u, u_dev);
+  return pmh_vec_copy(s->ctx, s->nu, s->u, u_dev);
 }
 
 extern "C" int pmh_svr_get_stats(pmh_svr s, pmh_svr_stats *st)
@@ -474,11 +285,7 @@ extern "C" int pmh_svr_get_stats(pmh_svr s, pmh_svr_stats *st)
 extern "C" int pmh_svr_get_solver(pmh_svr s, pmh_op *H, pmh_qppf *pf, pmh_mpgp *mpgp, pmh_smalxe *smalxe)
 {
   PMH_ARG(s);
-  if (H) *H = s->H;
-  if (pf) *pf = s->pf;
-  if (mpgp) *mpgp = s->mpgp;
-  if (smalxe) *smalxe = s->sx;
-  return PMH_SUCCESS;
+  return sv_get_solver(s, H, pf, mpgp, smalxe);
 }
 
 // X (dense rows, n x d: doubles, or floats where f32 -- the test samples' type, whatever the handle was trained on) or Xt (CSR); t != nullptr: the metrics
@@ -487,29 +294,11 @@ static int svr_score(pmh_svr s, const char *who, int n, const void *X, int f32, 
   PMH_ARG(s && n >= 0 && (X || Xt || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "%s: call pmh_svr_train first", who);
   PMH_CHK(pmh_svm_check_test_samples(who, s->d, Xt));
-  pmh_ctx      ctx = s->ctx;
-  const int    nb  = SVM_NB(n);
-  const double eps = s->o.epsilon;
-  if (n > 0 && Xt) {
-    double *dots = scores; // the dot products land where the scores go; without scores in a buffer of this call
-    if (!dots) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&dots));
-    int rc = pmh_svm_csr_row_dots(Xt, s->w, dots);
-    if (!rc) {
-      hipLaunchKernelGGL(k_svr_score_dots, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, (const double *)dots, s->b, scores, t, eps, s->part);
-      if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "%s_csr: the launch failed", who);
-    }
-    if (!scores) pmh_free(ctx, dots); // (waits for the stream)
-    PMH_CHK(rc);
-  } else if (n > 0) {
-    svm_const<2>(f32, [&](auto F) {
-      using T = svm_sample_t<decltype(F)>;
-      if (s->d == 64) hipLaunchKernelGGL(k_svr_score64<T>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, (const T *)X, (const double *)s->w, s->b, scores, t, eps, s->part);
-      else hipLaunchKernelGGL(k_svr_score<T>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, s->d, (const T *)X, (const double *)s->w, s->b, scores, t, eps, s->part);
-    });
-    PMH_HIP(hipGetLastError());
-  }
+  pmh_ctx ctx = s->ctx;
+  // (CSR: the dot products land where the scores go; without scores in a buffer of the call)
+  PMH_CHK(sv_sweep<true>(ctx, who, n, s->d, X, f32, Xt, nullptr, s->w, scores, svr_score_f{s->b, scores, t, s->epsilon, s->part}));
   if (!m) return PMH_SUCCESS;
-  PMH_CHK(svr_sum_part(s, n, nb, SVR_NSUM, 3));
+  PMH_CHK(pmh_svm_finish_part(ctx, n, SVM_NB(n), SVR_NSUM, 3, s->part, s->scal));
   double h[SVR_NSUM], ng = (double)n;
   PMH_CHK(pmh_memcpy_d2h(ctx, h, s->scal, sizeof(h)));
   PMH_CHK(pmh_comm_sum_host(ctx, &ng, 1));

@@ -15,10 +15,14 @@ from . import _lib
 from ._lib import check
 from .core import Vec, sample_dtype_of
 from .mat import is_sparse
-from .svm import _Samples, _vecs
+from .svm import _Samples, _SVMHandle, _vecs
 
 
-class SVR:
+class SVR(_SVMHandle):
+    """The handle, its keep-alive buffers and how a call is made on samples of either kind are _SVMHandle's; the options are pmh_svr_opts."""
+
+    _who, _pre = "SVR", "pmh_svr_"
+
     def __init__(self, ctx, loss="L1", C=1.0, epsilon=0.1, bias=True, options="", sample_dtype=None):
         """options: a PETSc-style option string for the solver (-qps_rtol 1e-6, -qps_mpgp_*, -qps_smalxe_*, -smalxe_qps_* ...) and -svr_loss_type / -svr_C /
         -svr_epsilon / -svr_bias, which override the keyword arguments.  sample_dtype: as in SVM (numpy.float32 keeps dense samples in float32 on the device)."""
@@ -36,65 +40,30 @@ class SVR:
         self.h = None
         self._keep = None
 
-    loss = property(lambda self: "L2" if self.opts.loss_type == 1 else "L1")
-    C = property(lambda self: self.opts.C)
     epsilon = property(lambda self: self.opts.epsilon)
-    bias = property(lambda self: bool(self.opts.bias))
-
-    def _dev(self, a):
-        return a if isinstance(a, Vec) else Vec.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.float64).ravel())
-
-    def _need(self):
-        if self.h is None:
-            raise RuntimeError("SVR: call fit first")
-
-    def _entry(self, name, sparse, f32=False):
-        return getattr(self.L, "pmh_svr_" + name + ("_csr" if sparse else "_f32" if f32 else ""))
 
     def create(self, X, t, sample_weight=None):
         """Set the training samples (X: (n, d) row-major ndarray or scipy.sparse matrix; t: n finite targets) and build the solver without training.  The handle
         borrows both for its lifetime.  sample_weight: n positive numbers that scale the samples' penalties (None: all 1)."""
         sample_dtype_of(self.sample_dtype, is_sparse(X), "SVR")  # (float32 with sparse samples is refused)
         self.destroy()
-        S = _Samples(self.ctx, X, with_d=True, dtype=self.sample_dtype)
-        if S.X.ndim != 2:
+        if np.ndim(X) != 2:
             raise ValueError("SVR: X must be (n, d)")
-        self.n, self.d = S.X.shape
         tn = np.ascontiguousarray(t, dtype=np.float64).ravel()
-        if tn.size != self.n:
-            raise ValueError("SVR: t must have %d entries" % self.n)
-        h = ct.c_void_p()
-        with S as (n, xa):
-            td = Vec.from_numpy(self.ctx, tn)
-            try:
-                check(self._entry("create", S.sparse, S.f32)(self.ctx.h, *xa, td.p, self.opts, ct.byref(h)))
-            except Exception:
-                td.free()
-                raise
-            self.h, self._keep = h, (S.keep(), td)
+        if tn.size != np.shape(X)[0]:
+            raise ValueError("SVR: t must have %d entries" % np.shape(X)[0])
+        self._create_handle(X, tn)
         if sample_weight is not None:
             self.set_penalties(sample_weight=sample_weight)
         return self
 
-    def destroy(self):
-        if self.h is not None:
-            self.L.pmh_svr_destroy(self.h)
-            self.h = None
-            for v in self._keep or ():
-                v.destroy() if hasattr(v, "destroy") else v.free()
-            self._keep = None
-
     def set_penalties(self, C=None, sample_weight=None):
         """C_i = C sample_weight_i on the created handle (pmh_svr_set_penalties; None: the handle's C, all 1); the handle is untrained afterwards."""
         self._need()
-        wd = None if sample_weight is None else self._dev(sample_weight)
-        try:
+        with self._lent(sample_weight) as wd:
             if wd is not None and wd.n != self.n:
                 raise ValueError("SVR: sample_weight must have %d entries" % self.n)
             check(self.L.pmh_svr_set_penalties(self.h, float(self.C if C is None else C), wd.p if wd is not None else None))
-        finally:
-            if wd is not None and wd is not sample_weight:
-                wd.free()
         return self
 
     def set_epsilon(self, epsilon):

@@ -2,7 +2,10 @@
 """Compare two gfx950 assembly listings kernel by kernel (a one-off check of a refactor that must leave the generated code alone):
 
     hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S svm.hip -o before/svm.s     (at the parent, then at the head -> after/svm.s)
-    python scripts/dev/svm_isa_diff.py before/svm.s after/svm.s
+    python scripts/dev/svm_isa_diff.py before/svm.s after/svm.s [--pair OLD=NEW ...] [-v]
+
+--pair OLD=NEW compares the kernel that was OLD before with the kernel that is NEW after, both given as the demangled name up to its argument list and
+without the return type: --pair 'k_svm_predict64<float>=k_svm_rows64<float, svm_classify_f>'.  Both listings may be concatenations of several files' output.
 
 Per kernel: the instructions only, comments stripped, assembler directives dropped, local labels renamed in order of appearance.  Prints one line per kernel:
 "identical", or the register counts, scratch size, floating-point instruction count and instruction count of both sides and a unified diff with -v."""
@@ -21,7 +24,7 @@ def kernels(path):
     out, name, body, meta, seen = {}, None, None, None, None
     for raw in open(path):
         m = LABEL.match(raw)
-        if m and not m.group(1).startswith(".L") and name is None and raw.split(";")[0].strip().endswith(":"):
+        if m and not m.group(1).startswith(".L") and raw.split(";")[0].strip().endswith(":"):  # (also after a symbol that is no kernel, as between concatenated listings)
             name, body, meta, seen = m.group(1), [], {}, {}
             continue
         if name is None:
@@ -64,11 +67,27 @@ def drop_sample_type(name):
     return m.group(1) + ("<%s>" % ", ".join(args) if args else "") + name[m.end():]
 
 
+def kernel_id(name):
+    """The demangled name up to its argument list, without the return type: what --pair names a kernel by."""
+    return re.sub(r"^void ", "", name).split("(")[0]
+
+
 def main():
-    verbose = "-v" in sys.argv
-    a, b = [kernels(p) for p in sys.argv[1:] if p != "-v"]
+    args = sys.argv[1:]
+    verbose = "-v" in args
+    pairs = dict(args[i + 1].split("=", 1) for i, x in enumerate(args) if x == "--pair")
+    files = [x for i, x in enumerate(args) if x not in ("-v", "--pair") and (i == 0 or args[i - 1] != "--pair")]
+    a, b = [kernels(p) for p in files]
     dm = demangle(sorted(set(a) | set(b)))
-    # pair the kernels up by their demangled names less the sample type
+    # a renamed kernel takes its new name on the before side (--pair)
+    new = {kernel_id(dm[k]): dm[k] for k in b}
+    for old, to in pairs.items():
+        hit = [k for k in a if kernel_id(dm[k]) == old]
+        if len(hit) != 1 or to not in new:
+            sys.exit("--pair %s=%s: %s" % (old, to, "no such kernel after" if len(hit) == 1 else "%d kernels of that name before" % len(hit)))
+        key = new[to] + " [was %s]" % old
+        a[key], b[key], dm[key] = a.pop(hit[0]), b.pop([k for k in b if dm[k] == new[to]][0]), key
+    # pair the other kernels up by their demangled names less the sample type
     a, b = [{drop_sample_type(dm[k]): v for k, v in side.items()} for side in (a, b)]
     dm = {k: k for k in set(a) | set(b)}
     same = 0
