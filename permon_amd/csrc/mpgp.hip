@@ -39,59 +39,82 @@
 #define S_GF2 19
 #define S_TMP 24
 
+// Which partial sums of the context's block partials (ctx->d_partials, pinned copy ctx->h_partials) are still owed, and by whom.  A phase or an operator says
+// what it left (note); whoever reads the scalars next on the device has them finalised there (settle); the host adds the pinned rows itself after its next wait
+// (host_sums).  The op and slot tables of both groups are OWED_OPS / OWED_SLOTS and nowhere else.
+namespace { // (this file's own: the library exports no symbol of it)
+struct owed_sums {
+  enum { NONE = 0, DEVICE, HOST }; // nothing owed / a finalising launch / the host's sum of the pinned rows
+  // SPLIT: rows 0..3 (Ap'gf, |gP|^2, |gc|^2, |gf|^2) -> S_APGF..S_GF2, left by a split or step kernel; P1: rows 4..6 (p'Ap, g'p, QPCFeas) -> S_PAP..S_FEAS
+  enum { SPLIT = 1, P1 = 2 };
+  struct rows {
+    int owed = NONE, nb = 0; // nb: the block partials per row
+  } split, p1;
+
+  void clear() { split = rows(), p1 = rows(); }
+  void note(int group, int owed, int nb) { (group == SPLIT ? split : p1) = (owed == HOST && nb <= 0) ? rows() : rows{owed, nb}; } // (no block, no sum for the host)
+  // the group's finalising launch, at once, of the rows that start at `row` (halt / post: the speculative chain's words, pmh_finalize_partials)
+  static int finalize(pmh_ctx ctx, int group, int row, int nb, const int *halt = nullptr, int *post = nullptr);
+  // Finalising launches for what is owed of `groups` (SPLIT | P1) on the device -- host_too: and for what was left to the host, where the next reader is a kernel
+  // that takes the scalars from d_scal.  Both groups owed device-side over the same blocks, scalars not row-distributed: ONE launch of seven rows, every quantity
+  // reduced as on its own.  (Row-distributed scalars are never deferred: their finalising launch is completed across the ranks, in the order the phases ran.)
+  int settle(pmh_ctx ctx, int groups, bool host_too = false, const int *halt = nullptr, int *post = nullptr);
+  // after a wait on the stream: the sums the EMIT kernels / the operator's last kernel left to the host (the role of k_finalize) -> h_scal
+  void host_sums(pmh_ctx ctx);
+};
+} // namespace
+
 struct pmh_mpgp_s {
-  pmh_ctx       ctx;
-  pmh_op        A;
-  pmh_csr       csr;
-  int           n;
-  const double *b;
-  double       *x;
-  const double *lb, *ub;
+  pmh_ctx       ctx = nullptr;
+  pmh_op        A   = nullptr;
+  pmh_csr       csr = nullptr;
+  int           n   = 0;
+  const double *b   = nullptr;
+  double       *x   = nullptr;
+  const double *lb = nullptr, *ub = nullptr;
   pmh_mpgp_opts o;
   // QPS_MPGP state
-  double alpha, alpha_user, maxeig;
-  int    expproject;
-  double *work[10];
-  int     nwork;
+  double  alpha = 0.0, alpha_user = 0.0, maxeig = 0.0;
+  int     expproject = 1; // mpgp.c:839
+  double *work[10]   = {};
+  int     nwork      = 0;
   // convergence
-  pmh_converged_fn cvg;
+  pmh_converged_fn cvg      = nullptr;
+  void            *cvg_user = nullptr;
+  double           norm_rhs = 0.0, ttol = 0.0, norm_rhs_div = 0.0;
+  int              cvg_setup = 0;
   // optional: enqueues what the injected convergence test will read, BEFORE the host waits for the step's scalars (one round trip instead of two)
-  int (*pre_test)(void *);
-  void *pre_test_user;
+  int (*pre_test)(void *) = nullptr;
+  void *pre_test_user     = nullptr;
   // optional: called right before the speculative Ap = A p of the NEXT iteration is enqueued (the iterate is final then): SMALXE lets its ||B u|| ride on that
   // product
-  int (*pre_p1)(void *);
-  void *pre_p1_user;
+  int (*pre_p1)(void *) = nullptr;
+  void *pre_p1_user     = nullptr;
   // set by the convergence test: rnorm / (the threshold it has to fall below), 0 = unknown -- how close the NEXT test is to ending the solve
-  double cvg_margin;
+  double cvg_margin = 0.0;
   // work[3] already holds A x - b for the x and b the next solve starts from (pmh_mpgp_set_gradient_valid): the fused driver skips its first product
-  int   g_valid;
-  int   epi_ok;            // 1: the operator folds the vector phases into its last kernel (pmh_op_s::mult_epi), 0: it does not, -1: not asked yet
-  // > 0: rows 0..3 (gradient split) / 4..6 (P1) of the pinned block partials wait for the host's sum over that many blocks (host_sums)
-  int   hsum4 = 0, hsum3 = 0;
+  int g_valid = 0;
+  int epi_ok  = -1; // 1: the operator folds the vector phases into its last kernel (pmh_op_s::mult_epi), 0: it does not, -1: not asked yet
+  // the partial sums the phases and the operator have left behind and nobody has summed yet
+  owed_sums owed;
   // fused dual-space chain (pmh_op_s::emit_begin): the operator holds G0 x (0) / G0 p (1) of the CURRENT x / p, emitted by the kernel that wrote them
-  bool  cx[2] = {false, false};
+  bool cx[2] = {false, false};
   // the operator's last application was the gradient at x and nothing has written x since (every write of x and every other application clears it): a caller
   // that multiplies x again may say so (pmh_op_s::mult_same_input).  first_applied: the caller's word that the NEXT solve's first gradient is such a repeat
-  bool  x_applied = false;
-  int   first_applied = 0;
-  int   fin4_pending;      // the partials of the gradient split (rows 0..3) wait for the finalising launch of the next P1 (rows 4..6): one launch for both
-  void            *cvg_user;
-  double           norm_rhs, ttol, norm_rhs_div;
-  int              cvg_setup;
+  bool x_applied     = false;
+  int  first_applied = 0;
   // results
-  double rnorm, gfnorm, gcnorm;
-  int    iteration, reason;
-  int    nmv, ncg, nexp, nprop, nfinc, nfall;
-  char   step;
-  int    fallback_state;
+  double rnorm = 0.0, gfnorm = 0.0, gcnorm = 0.0;
+  int    iteration = 0, reason = 0;
+  int    nmv = 0, ncg = 0, nexp = 0, nprop = 0, nfinc = 0, nfall = 0;
+  char   step           = ' ';
+  int    fallback_state = 0;
   // monitor
   std::vector<char>   t_step;
   std::vector<double> t_gp, t_gf, t_gc, t_alpha;
-  // throughput mode
   // speculative device-side CG chain
-  int    *d_ctl, *h_ctl;
-  double *d_ring, *h_ring;
+  int    *d_ctl = nullptr, *h_ctl = nullptr;
+  double *d_ring = nullptr, *h_ring = nullptr;
 };
 
 // --------------------------------------------------------------------------------------------------------------------
@@ -326,18 +349,54 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_obj_from_grad(long long n, const 
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-#define LAUNCH(kern, ...) \
-  do { \
-    if (s->n > 0) hipLaunchKernelGGL(kern, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, (long long)s->n, __VA_ARGS__); \
-    PMH_HIP(hipGetLastError()); \
-  } while (0)
+// --------------------------------------------------------------------------------------------------------------------
+// the phases: one launcher each, called by both drivers and by the test entry (pmh_mpgp_test_phase)
+// --------------------------------------------------------------------------------------------------------------------
+static int vec_blocks(int n) { return n > 0 ? pmh_vec_grid(n) : 0; }               // grid of the plain kernels
+static int emit_blocks(int n) { return (n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE; } // grid of the EMIT variants
 
-// the EMIT variants: workgroups of PMH_EMIT_TILE threads, one entry each
-#define LAUNCH_EMIT(kern, ...) \
-  do { \
-    if (s->n > 0) hipLaunchKernelGGL(kern, dim3((s->n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE), dim3(PMH_EMIT_TILE), 0, s->ctx->stream, (long long)s->n, __VA_ARGS__); \
-    PMH_HIP(hipGetLastError()); \
-  } while (0)
+// The one launch of a vector kernel over n entries: the 256-thread grid of pmh_vec_grid, or -- tile: the EMIT variants -- workgroups of PMH_EMIT_TILE threads,
+// one entry each.  The arguments are converted to the kernel's own parameter types.
+template <typename... P, typename... T>
+static int launch(pmh_ctx ctx, int n, bool tile, void (*kern)(long long, P...), T... args)
+{
+  if (n > 0) hipLaunchKernelGGL(kern, dim3(tile ? emit_blocks(n) : pmh_vec_grid(n)), dim3(tile ? PMH_EMIT_TILE : PMH_BLOCK), 0, ctx->stream, (long long)n, (P)args...);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+
+// what the phase kernels work on: the reference's work vectors (mpgp.c:6-17) and the box
+struct phase_vecs {
+  double       *x, *g, *p, *Ap, *gf;
+  const double *lb, *ub;
+  double        astol;
+};
+
+// Each launcher: ea == nullptr is the plain kernel (no emission: g_noea, no pinned copy of the partials, no host scalars), otherwise the tile variant that
+// leaves the segment sums *ea asks for (pmh_op_s::emit_begin) and its block partials in the pinned copy as well.  The sums go to rows 0.. of ctx->d_partials.
+static pmh_emit_args g_noea;
+
+static int phase_split(pmh_ctx ctx, int n, const phase_vecs &v, const pmh_emit_args *ea) { return launch(ctx, n, ea, ea ? k_split_setp<true> : k_split_setp<false>, v.x, v.g, v.lb, v.ub, v.astol, v.gf, v.p, ctx->d_partials, ctx->partials_cap, ea ? *ea : g_noea, ea ? ctx->h_partials : nullptr); }
+
+// setp: p = gf as well (proportioning); spec: the device-side test of the speculative chain (plain kernel, CG step only).  Tile variant: acg from the host, or
+// -- nb_p1 > 0 -- from the P1 block partials.  The one place that chooses among the instantiations of k_step_update
+static int phase_step(pmh_ctx ctx, int n, const phase_vecs &v, bool setp, const pmh_spec_args *spec, const pmh_emit_args *ea, double acg_host, int nb_p1)
+{
+  auto kern = ea ? (setp ? k_step_update<true, false, true> : k_step_update<false, false, true>) : spec ? k_step_update<false, true> : setp ? k_step_update<true, false> : k_step_update<false, false>;
+  return launch(ctx, n, ea, kern, ctx->d_scal, spec ? *spec : pmh_spec_args{}, v.x, v.g, v.p, v.Ap, v.lb, v.ub, v.astol, v.gf, ctx->d_partials, ctx->partials_cap, ea ? *ea : g_noea,
+                ea ? ctx->h_partials : nullptr, ea ? acg_host : 0.0, ea ? nb_p1 : 0);
+}
+
+// tile variant: Ap'gf from the nb block partials of row 0, p'Ap from the host
+static int phase_dir(pmh_ctx ctx, int n, const phase_vecs &v, const int *halt, const pmh_emit_args *ea, int nb, double pAp_host) { return launch(ctx, n, ea, ea ? k_dir_update<true> : k_dir_update<false>, ctx->d_scal, halt, v.gf, v.p, ea ? *ea : g_noea, ea ? ctx->d_partials : nullptr, ea ? nb : 0, ea ? pAp_host : 0.0); }
+
+static int phase_prop_dir(pmh_ctx ctx, int n, const phase_vecs &v, const pmh_emit_args *ea) { return launch(ctx, n, ea, ea ? k_prop_dir<true> : k_prop_dir<false>, v.x, v.g, v.lb, v.ub, v.astol, v.p, ea ? *ea : g_noea); }
+
+static int phase_expansion(pmh_ctx ctx, int n, const phase_vecs &v, double afeas, double alpha, const pmh_emit_args *ea) { return launch(ctx, n, ea, ea ? k_expansion_std<true> : k_expansion_std<false>, afeas, alpha, v.x, v.g, v.p, v.Ap, v.lb, v.ub, v.astol, ea ? *ea : g_noea); }
+
+static int phase_p1_dots(pmh_ctx ctx, int n, const phase_vecs &v) { return launch(ctx, n, false, k_p1_dots, v.p, v.Ap, v.g, v.x, v.lb, v.ub, ctx->d_partials, ctx->partials_cap); }
+static int phase_three_norms(pmh_ctx ctx, int n, const double *gP, const double *gc, const double *gf) { return launch(ctx, n, false, k_three_norms, gP, gc, gf, ctx->d_partials, ctx->partials_cap); }
+static int phase_obj(pmh_ctx ctx, int n, const double *x, const double *g, const double *b) { return launch(ctx, n, false, k_obj_from_grad, x, g, b, ctx->d_partials); }
 
 // --------------------------------------------------------------------------------------------------------------------
 // set-up
@@ -394,25 +453,11 @@ extern "C" int pmh_mpgp_create(pmh_ctx ctx, pmh_op A, const double *b, double *x
   s->ub      = ub;
   s->o       = *o;
   if (s->o.fallback2) s->o.fallback = 0; // mpgp.c:744
-  for (int i = 0; i < 10; i++) s->work[i] = nullptr;
-  s->nwork = 0;
-  s->cvg = nullptr, s->cvg_user = nullptr, s->cvg_setup = 0;
-  s->pre_test = nullptr, s->pre_test_user = nullptr;
-  s->pre_p1 = nullptr, s->pre_p1_user = nullptr;
-  s->epi_ok = -1, s->fin4_pending = 0, s->g_valid = 0, s->cvg_margin = 0.0;
-  s->norm_rhs = s->ttol = s->norm_rhs_div = 0.0;
-  s->rnorm = s->gfnorm = s->gcnorm = 0.0;
-  s->iteration = 0, s->reason = 0;
-  s->nmv = s->ncg = s->nexp = s->nprop = s->nfinc = s->nfall = 0;
-  s->step           = ' ';
   s->fallback_state = s->o.fallback;
-  s->d_ctl = s->h_ctl = nullptr;
-  s->d_ring = s->h_ring = nullptr;
   if (s->o.bchop_tol) { // mpgp.c:379-382: VecFilter on the user's bound vectors, in place as in the reference
-    if (lb) LAUNCH(k_filter, (double *)lb, s->o.bchop_tol);
-    if (ub) LAUNCH(k_filter, (double *)ub, s->o.bchop_tol);
+    if (lb) PMH_CHK(launch(ctx, s->n, false, k_filter, lb, s->o.bchop_tol));
+    if (ub) PMH_CHK(launch(ctx, s->n, false, k_filter, ub, s->o.bchop_tol));
   }
-  s->expproject = 1; // mpgp.c:839
   if (s->o.exptype == PMH_EXP_STD && s->o.explengthtype == PMH_EXPLEN_FIXED) s->expproject = 0; // mpgp.c:388
   s->maxeig     = s->o.maxeig;
   s->alpha_user = s->o.alpha_user;
@@ -519,15 +564,21 @@ extern "C" int pmh_mpgp_reset_statistics(pmh_mpgp s)
   return PMH_SUCCESS;
 }
 
-// QPSConvergedDefault qps.c:675-714 + QPSConvergedDefaultSetUp :718-731
+// QPSConvergedDefaultSetUp qps.c:718-731
+static int converged_default_setup(pmh_mpgp s)
+{
+  if (s->cvg_setup) return PMH_SUCCESS;
+  PMH_CHK(pmh_vec_norm2(s->ctx, s->n, s->b, &s->norm_rhs));
+  s->ttol         = fmax(s->o.rtol * s->norm_rhs, s->o.atol);
+  s->norm_rhs_div = s->norm_rhs;
+  s->cvg_setup    = 1;
+  return PMH_SUCCESS;
+}
+
+// QPSConvergedDefault qps.c:675-714
 static int converged_default(pmh_mpgp s)
 {
-  if (!s->cvg_setup) {
-    PMH_CHK(pmh_vec_norm2(s->ctx, s->n, s->b, &s->norm_rhs));
-    s->ttol         = fmax(s->o.rtol * s->norm_rhs, s->o.atol);
-    s->norm_rhs_div = s->norm_rhs;
-    s->cvg_setup    = 1;
-  }
+  PMH_CHK(converged_default_setup(s));
   s->reason = PMH_CONVERGED_ITERATING;
   if (s->iteration > s->o.max_it) { // strict, qps.c:688
     s->reason = PMH_DIVERGED_ITS;
@@ -540,16 +591,21 @@ static int converged_default(pmh_mpgp s)
   return PMH_SUCCESS;
 }
 
+// one line of QPSMonitorDefault_MPGP (mpgp.c:21-34)
+static void monitor_push(pmh_mpgp s, double gp, double gf, double gc)
+{
+  if (!s->o.monitor) return;
+  s->t_step.push_back(s->step);
+  s->t_gp.push_back(gp);
+  s->t_gf.push_back(gf);
+  s->t_gc.push_back(gc);
+  s->t_alpha.push_back(s->alpha);
+}
+
 // monitor (mpgp.c:524-528) + convergence test (mpgp.c:531)
 static int test_convergence(pmh_mpgp s)
 {
-  if (s->o.monitor) {
-    s->t_step.push_back(s->step);
-    s->t_gp.push_back(s->rnorm);
-    s->t_gf.push_back(s->gfnorm);
-    s->t_gc.push_back(s->gcnorm);
-    s->t_alpha.push_back(s->alpha);
-  }
+  monitor_push(s, s->rnorm, s->gfnorm, s->gcnorm);
   if (s->cvg) {
     int reason = 0;
     int rc     = s->cvg(s->cvg_user, s->iteration, s->rnorm, &reason);
@@ -562,25 +618,19 @@ static int test_convergence(pmh_mpgp s)
 }
 
 // ---- fused dual-space chain: emission by the vector kernels (pmh_op_s::emit_begin, emit_inline.h) ----------------------------
-static pmh_emit_args g_noea;
-// the kernel about to be launched writes x (wx) and / or p (wp), one entry per thread: true = *ea is filled and the EMIT variant must be launched
-static bool emit_try(pmh_mpgp s, bool wx, bool wp, pmh_emit_args *ea)
+// the kernel about to be launched writes x (wx) and / or p (wp), one entry per thread: ea = it is filled and the EMIT variant must be launched, else nullptr
+static const pmh_emit_args *emit_try(pmh_mpgp s, bool wx, bool wp, pmh_emit_args *ea)
 {
   if (wx) s->cx[0] = false, s->x_applied = false;
   if (wp) s->cx[1] = false;
-  if (s->csr || s->epi_ok != 1 || s->o.distributed) {
+  if (s->csr || s->epi_ok != 1 || s->o.distributed || s->A->emit_begin(wx ? s->x : nullptr, wp ? s->work[4] : nullptr, ea) != PMH_SUCCESS) {
     if (wx) s->A->emit_invalidate();
-    return false;
-  }
-  if (s->A->emit_begin(wx ? s->x : nullptr, wp ? s->work[4] : nullptr, ea) != PMH_SUCCESS) {
-    if (wx) s->A->emit_invalidate();
-    return false;
+    return nullptr;
   }
   if (wx) s->cx[0] = true;
   if (wp) s->cx[1] = true;
-  return true;
+  return ea;
 }
-static int emit_blocks(pmh_mpgp s) { return (s->n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE; } // grid of the EMIT variants
 
 // The last step of a reduction whose block partials a kernel left in the pinned host copy, taken by the host after its wait: lane l of a wave of 64 adds its
 // entries l, l + 64, ... in that order, then the butterflies of pmh_wave_all (emit_inline.h) -- the order in which a device consumer adds the same row
@@ -604,33 +654,51 @@ static double host_sum_row(const double *row, int nb, int op)
   for (int l = 0; l < 64; l++) v[l] = comb(t[l], t[(l & ~15) | (15 - (l & 15))]);
   return comb(comb(v[0], v[16]), comb(v[32], v[48]));
 }
-// after a wait on the stream: the sums the EMIT kernels / the operator's last kernel left to the host (the role of k_finalize) -> h_scal
-static void host_sums(pmh_mpgp s)
+// ---- owed_sums: the rows, ops and slots of the two groups, SPLIT first --------------------------------------------------------------------------------------
+static const int OWED_OPS[7]   = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
+static const int OWED_SLOTS[7] = {S_APGF, S_GP2, S_GC2, S_GF2, S_PAP, S_GP, S_FEAS};
+static const int OWED_P1_ROW   = 4; // the P1 rows as the operator's last kernel leaves them, behind a gradient split that may still wait
+
+int owed_sums::finalize(pmh_ctx ctx, int group, int row, int nb, const int *halt, int *post)
 {
-  pmh_ctx   ctx = s->ctx;
-  const int ld  = ctx->partials_cap;
-  if (s->hsum4) {
-    for (int k = 0; k < 4; k++) ctx->h_scal[S_APGF + k] = host_sum_row(ctx->h_partials + (size_t)k * ld, s->hsum4, PMH_RED_SUM);
-    s->hsum4 = 0;
-  }
-  if (s->hsum3) {
-    ctx->h_scal[S_PAP]  = host_sum_row(ctx->h_partials + (size_t)4 * ld, s->hsum3, PMH_RED_SUM);
-    ctx->h_scal[S_GP]   = host_sum_row(ctx->h_partials + (size_t)5 * ld, s->hsum3, PMH_RED_SUM);
-    ctx->h_scal[S_FEAS] = host_sum_row(ctx->h_partials + (size_t)6 * ld, s->hsum3, PMH_RED_MIN);
-    s->hsum3            = 0;
-  }
+  const int first = group == SPLIT ? 0 : OWED_P1_ROW, K = group == SPLIT ? 4 : 3;
+  return pmh_finalize_partials(ctx, ctx->d_partials + (size_t)row * ctx->partials_cap, ctx->partials_cap, nb, K, OWED_OPS + first, OWED_SLOTS[first], halt, post);
 }
 
-static int finalize_vec4_from(pmh_mpgp s, int nblocks) // rows 0..3 written by an EMIT variant (its own grid) after all: finalise on the device
+int owed_sums::settle(pmh_ctx ctx, int groups, bool host_too, const int *halt, int *post)
 {
-  const int ops[4] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM};
-  s->hsum4         = 0;
-  return pmh_finalize_partials(s->ctx, s->ctx->d_partials, s->ctx->partials_cap, nblocks, 4, ops, S_APGF);
+  auto due = [&](int group, const rows &r) { return (groups & group) && (r.owed == DEVICE || (host_too && r.owed == HOST)); };
+  const bool ds = due(SPLIT, split), dp = due(P1, p1);
+  const int  nbs = split.nb, nbp = p1.nb;
+  if (ds) split = rows();
+  if (dp) p1 = rows();
+  if (ds && dp && nbs == nbp && !ctx->dist_scalars && !halt && !post) return pmh_finalize_partials_slots(ctx, ctx->d_partials, ctx->partials_cap, nbs, 7, OWED_OPS, OWED_SLOTS);
+  if (ds) PMH_CHK(finalize(ctx, SPLIT, 0, nbs, halt, post));
+  if (dp) PMH_CHK(finalize(ctx, P1, OWED_P1_ROW, nbp));
+  return PMH_SUCCESS;
 }
-static int finalize_vec4(pmh_mpgp s, const int *halt = nullptr, int *post = nullptr)
+
+void owed_sums::host_sums(pmh_ctx ctx)
 {
-  const int ops[4] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM};
-  return pmh_finalize_partials(s->ctx, s->ctx->d_partials, s->ctx->partials_cap, s->n > 0 ? pmh_vec_grid(s->n) : 0, 4, ops, S_APGF, halt, post);
+  for (int k = 0; k < 7; k++) {
+    const rows &r = k < OWED_P1_ROW ? split : p1;
+    if (r.owed == HOST) ctx->h_scal[OWED_SLOTS[k]] = host_sum_row(ctx->h_partials + (size_t)k * ctx->partials_cap, r.nb, OWED_OPS[k]);
+  }
+  if (split.owed == HOST) split = rows();
+  if (p1.owed == HOST) p1 = rows();
+}
+
+// the objective's one sum (k_obj_from_grad) -> S_TMP
+static int finalize_obj(pmh_ctx ctx, int nb) { return pmh_finalize_partials(ctx, ctx->d_partials, ctx->partials_cap, nb, 1, OWED_OPS, S_TMP); }
+
+// the solver's vectors as the phase launchers take them: work[1, 3, 4, 5] = gf, g, p, Ap (mpgp.c:6-17)
+static phase_vecs vecs_of(pmh_mpgp s) { return phase_vecs{s->x, s->work[3], s->work[4], s->work[5], s->work[1], s->lb, s->ub, s->o.astol}; }
+
+// a split, step or norms kernel has just left rows 0..3: the tile variant to the host, the plain one to its finalising launch, enqueued here
+static int note_split(pmh_mpgp s, bool tile, const int *halt = nullptr, int *post = nullptr)
+{
+  s->owed.note(owed_sums::SPLIT, tile ? owed_sums::HOST : owed_sums::DEVICE, tile ? emit_blocks(s->n) : vec_blocks(s->n));
+  return s->owed.settle(s->ctx, owed_sums::SPLIT, false, halt, post);
 }
 
 // --------------------------------------------------------------------------------------------------------------------
@@ -647,17 +715,8 @@ static double *exp_direction(pmh_mpgp s)
   default: return s->work[1]; // projcg fallback vectors
   }
 }
-static double *exp_lengthvec(pmh_mpgp s)
-{
-  switch (s->o.exptype) {
-  case PMH_EXP_STD: return s->work[6];
-  case PMH_EXP_GF: return s->work[1];
-  case PMH_EXP_G: return s->work[3];
-  case PMH_EXP_GFGR: return s->work[6];
-  case PMH_EXP_GGR: return s->work[6];
-  default: return s->work[1];
-  }
-}
+// the vector its length is measured by: the direction, but gr where the direction is gf or g with gr in its name
+static double *exp_lengthvec(pmh_mpgp s) { return (s->o.exptype == PMH_EXP_GFGR || s->o.exptype == PMH_EXP_GGR) ? s->work[6] : exp_direction(s); }
 
 // MPGPGrads mpgp.c:198-223
 static int u_grads(pmh_mpgp s, const double *x, const double *g)
@@ -719,9 +778,8 @@ static int u_expansion_std(pmh_mpgp s, double afeas, double *xold, double *exple
 
 static int u_objective_from_gradient(pmh_mpgp s, const double *x, const double *g, double *f)
 {
-  const int ops[1] = {PMH_RED_SUM};
-  LAUNCH(k_obj_from_grad, x, g, s->b, s->ctx->d_partials);
-  PMH_CHK(pmh_finalize_partials(s->ctx, s->ctx->d_partials, s->ctx->partials_cap, s->n > 0 ? pmh_vec_grid(s->n) : 0, 1, ops, S_TMP));
+  PMH_CHK(phase_obj(s->ctx, s->n, x, g, s->b));
+  PMH_CHK(finalize_obj(s->ctx, vec_blocks(s->n)));
   double v;
   PMH_CHK(pmh_host_scalar(s->ctx, S_TMP, &v));
   *f = .5 * v;
@@ -765,8 +823,8 @@ static int solve_unfused(pmh_mpgp s)
   s->step      = ' ';
   s->iteration = 0;
   while (1) {
-    LAUNCH(k_three_norms, (const double *)gP, (const double *)gc, (const double *)gf, ctx->d_partials, ctx->partials_cap);
-    PMH_CHK(finalize_vec4(s));
+    PMH_CHK(phase_three_norms(ctx, n, gP, gc, gf));
+    PMH_CHK(note_split(s, false));
     PMH_CHK(pmh_sync(ctx));
     s->rnorm  = sqrt(ctx->h_scal[S_GP2]);
     gcTgc     = ctx->h_scal[S_GC2];
@@ -866,18 +924,12 @@ static int f_apply_p1(pmh_mpgp s, const int *halt = nullptr, bool p_fresh = fals
   if (s->csr) {
     pmh_spmv_epi e;
     memset(&e, 0, sizeof(e));
-    e.kind      = PMH_EPI_MPGP;
-    e.g         = g;
-    e.xx        = s->x;
-    e.lb        = s->lb;
-    e.ub        = s->ub;
-    e.scal_base = S_PAP;
-    e.halt      = halt;
+    e.kind = PMH_EPI_MPGP, e.g = g, e.xx = s->x, e.lb = s->lb, e.ub = s->ub, e.scal_base = S_PAP, e.halt = halt;
     return pmh_csr_spmv_launch(s->csr, p, Ap, e);
   }
   if (halt) return pmh_set_error(PMH_ERR_STATE, "speculative chain needs a CSR operator");
-  const int ops[3] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
-  const int nb     = s->n > 0 ? pmh_vec_grid(s->n) : 0;
+  pmh_ctx   ctx = s->ctx;
+  const int nb  = vec_blocks(s->n);
   // the three reductions inside the operator's last kernel (rows 4..6 of the partials: rows 0..3 may still hold a gradient split that waits for its finalising
   // launch)
   if (s->epi_ok) {
@@ -892,31 +944,18 @@ static int f_apply_p1(pmh_mpgp s, const int *halt = nullptr, bool p_fresh = fals
     if (rc != PMH_EPI_UNSUPPORTED) {
       PMH_CHK(rc);
       s->epi_ok = 1;
-      if (hosted) {
-        if (s->fin4_pending) PMH_CHK(finalize_vec4(s)); // (an operator that leaves its sums to the host does so for the gradient split too: not reached)
-        s->fin4_pending = 0;
-        s->hsum3        = hosted;
-        return PMH_SUCCESS;
-      }
-      // (Ap'gf, |gP|^2, |gc|^2, |gf|^2) of the gradient split and (p'Ap, g'p, afeas) in ONE finalising launch: every quantity reduced as on its own
-      if (s->fin4_pending) {
-        const int ops7[7] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
-        const int slots7[7] = {S_APGF, S_GP2, S_GC2, S_GF2, S_PAP, S_GP, S_FEAS};
-        s->fin4_pending = 0;
-        return pmh_finalize_partials_slots(s->ctx, s->ctx->d_partials, s->ctx->partials_cap, nb, 7, ops7, slots7);
-      }
-      return pmh_finalize_partials(s->ctx, s->ctx->d_partials + (size_t)4 * s->ctx->partials_cap, s->ctx->partials_cap, nb, 3, ops, S_PAP);
+      // hosted: the host adds these three, and a gradient split that waits for a launch gets its own (one that waits for the host goes on waiting); else with
+      // such a split (Ap'gf, |gP|^2, |gc|^2, |gf|^2) and (p'Ap, g'p, afeas) in ONE finalising launch
+      s->owed.note(owed_sums::P1, hosted ? owed_sums::HOST : owed_sums::DEVICE, hosted ? hosted : nb);
+      return s->owed.settle(ctx, owed_sums::SPLIT | owed_sums::P1);
     }
     s->epi_ok = 0;
   }
-  // (cannot happen with one operator: it answers mult_epi the same way every time) the split's partials sit in the rows k_p1_dots is about to overwrite
-  if (s->fin4_pending) {
-    PMH_CHK(finalize_vec4(s));
-    s->fin4_pending = 0;
-  }
+  // a split that still waits for its launch sits in the rows k_p1_dots is about to overwrite
+  PMH_CHK(s->owed.settle(ctx, owed_sums::SPLIT));
   PMH_CHK(s->A->mult(p, Ap));
-  LAUNCH(k_p1_dots, (const double *)p, (const double *)Ap, (const double *)g, (const double *)s->x, s->lb, s->ub, s->ctx->d_partials, s->ctx->partials_cap);
-  return pmh_finalize_partials(s->ctx, s->ctx->d_partials, s->ctx->partials_cap, nb, 3, ops, S_PAP);
+  PMH_CHK(phase_p1_dots(ctx, s->n, vecs_of(s)));
+  return owed_sums::finalize(ctx, owed_sums::P1, 0, nb);
 }
 
 // g = A x - b (mpgp.c:500-502, :578-580)
@@ -926,8 +965,7 @@ static int f_gradient(pmh_mpgp s, bool same_input = false, int *replayed = nullp
   if (s->csr) {
     pmh_spmv_epi e;
     memset(&e, 0, sizeof(e));
-    e.kind = PMH_EPI_SUB;
-    e.y1   = s->b;
+    e.kind = PMH_EPI_SUB, e.y1 = s->b;
     return pmh_csr_spmv_launch(s->csr, s->x, g, e);
   }
   PMH_CHK(same_input ? s->A->mult_same_input(s->x, g, replayed) : s->A->mult(s->x, g));
@@ -935,7 +973,7 @@ static int f_gradient(pmh_mpgp s, bool same_input = false, int *replayed = nullp
 }
 
 // g = A x - b, the gradient split with p = gf and the partials of its norms (mpgp.c:500-507, :578-580 + :612-615): inside the operator's last kernel where it
-// offers that (the finalising launch then waits for the next P1: fin4_pending), else as three launches + the finalising one
+// offers that (defer_finalize: the finalising launch then waits for the next P1, owed_sums), else as three launches + the finalising one
 // same_input: x still holds what the operator was last applied to (pmh_vec_epi::same_input); *replayed = 1 where the operator took that word
 static int f_gradient_split(pmh_mpgp s, bool defer_finalize, bool x_from_spec = false, bool same_input = false, int *replayed = nullptr)
 {
@@ -954,271 +992,273 @@ static int f_gradient_split(pmh_mpgp s, bool defer_finalize, bool x_from_spec = 
       PMH_CHK(rc);
       s->epi_ok = 1;
       s->cx[1]  = p_emitted != 0; // p = gf was written by the operator's last kernel
-      if (hosted) {
-        s->hsum4 = hosted;
-        return PMH_SUCCESS;
-      }
-      if (defer_finalize && !ctx->dist_scalars) {
-        s->fin4_pending = 1;
-        return PMH_SUCCESS;
-      }
-      return finalize_vec4(s);
+      s->owed.note(owed_sums::SPLIT, hosted ? owed_sums::HOST : owed_sums::DEVICE, hosted ? hosted : vec_blocks(s->n));
+      if (hosted || (defer_finalize && !ctx->dist_scalars)) return PMH_SUCCESS;
+      return s->owed.settle(ctx, owed_sums::SPLIT);
     }
     s->epi_ok = 0;
   }
   if (x_from_spec) return pmh_set_error(PMH_ERR_STATE, "pmh_mpgp: the operator prepared an expansion step and then refused the gradient");
   PMH_CHK(f_gradient(s, same_input, replayed));
   s->cx[1] = false;
-  LAUNCH(k_split_setp<false>, (const double *)s->x, (const double *)g, s->lb, s->ub, s->o.astol, gf, p, ctx->d_partials, ctx->partials_cap, g_noea, (double *)nullptr);
-  return finalize_vec4(s);
+  PMH_CHK(phase_split(ctx, s->n, vecs_of(s), nullptr));
+  return note_split(s, false);
+}
+
+// ---- the steps of the fused driver: QPSSolve_MPGP (mpgp.c:438-650) cut where the reference's loop branches ------------------------------------------------
+static const int SPEC_BATCH = 16; // the longest batch of the device-side CG chain, and the room of its ring
+
+struct fused_state {
+  bool spec = false; // P1 for the current p already enqueued
+  // length of the next speculative batch: a batch that ran to its end doubles it, one that halted early cuts it to what it ran (an expansion-heavy stretch
+  // would otherwise enqueue 16 x 4 no-op launches behind every expansion step: ~0.1 ms each time); 0 = the host takes the next step.  The iterates do not
+  // depend on it: the device chain takes exactly the steps the host would.
+  int    spec_len         = SPEC_BATCH;
+  bool   p_fresh          = false; // p is the gf of the last gradient split, untouched (told to operators that pair their passes)
+  double prev_margin      = 0.0;   // cvg_margin of the previous test (f_speculate_next)
+  bool   check_projection = false; // the first gradient took the caller's word: the projection's word is read after the first wait (f_host_test)
+  int    nmv = 0, ncg = 0, nexp = 0, nprop = 0;
+};
+
+// the projection of the start (mpgp.c:497) and the first gradient with its split and p = gf (:500-507), carried or formed
+static int f_first_gradient(pmh_mpgp s, fused_state &st)
+{
+  pmh_ctx   ctx = s->ctx;
+  const int n   = s->n;
+  s->cx[0] = s->cx[1] = false; // x and p come from outside
+  s->owed.clear();
+  // The caller's word (pmh_mpgp_set_first_operand_applied) that x is the vector the operator was last applied to: the operator keeps what it remembers of that
+  // application, and the first gradient below passes the word on.  The projection rewrites a feasible x with the bits it had -- but the x an expansion step
+  // leaves (x - afeas p - alpha gr, no re-projection) may lie below a bound by a rounding error, and then the projection does change it.  So the projection
+  // leaves a word for the host where it changed an entry, read after the first wait (f_host_test, no wait of its own): the gradient is then taken again, in
+  // full.  (Not with row-distributed vectors: that word would be each rank's own.)
+  const bool first_same = s->first_applied != 0 && !s->g_valid && !s->o.distributed;
+  s->first_applied = 0, s->x_applied = false;
+  s->A->emit_invalidate(first_same);
+  if (first_same) PMH_CHK(pmh_qpc_box_project_flag(ctx, n, s->x, s->lb, s->ub, s->x, PMH_SLOT_PROJ_CHANGED));
+  else PMH_CHK(pmh_qpc_box_project(ctx, n, s->x, s->lb, s->ub, s->x)); // mpgp.c:497
+  // asked once: a refusal (PMH_EPI_UNSUPPORTED) clears it.  (Row-distributed vectors: the operator's partials are finalised at once and completed across the
+  // ranks, pmh_finalize_partials)
+  if (s->epi_ok < 0) s->epi_ok = (s->csr || !pmh_knobs().vec_epi) ? 0 : 1;
+  if (s->g_valid) { // the caller carried g = A x - b over from the previous solve (pmh_smalxe_set_reuse_products): the split, p = gf and the norms only
+    // (the operator's own gradient split does not run: whatever pairing state an operator keeps from the previous solve must not be matched with this p --
+    // p_fresh stays false, the first product of the solve is then a lone application)
+    s->g_valid = 0;
+    pmh_emit_args        ea;
+    const pmh_emit_args *e = emit_try(s, false, true, &ea);
+    PMH_CHK(phase_split(ctx, n, vecs_of(s), e));
+    return note_split(s, e);
+  }
+  int replayed = 0;
+  PMH_CHK(f_gradient_split(s, false, false, first_same, &replayed)); // :500-507 (the host reads the norms before any P1: finalised at once)
+  st.check_projection = first_same && replayed != 0;                  // the operator did take the caller's word
+  st.nmv++, st.p_fresh = true;
+  return PMH_SUCCESS;
+}
+
+// the device-side CG chain needs the default convergence test (its constants go to the kernels) and a CSR operator: sa->ctl stays null where this solve has none
+static int f_spec_setup(pmh_mpgp s, double gamma2, pmh_spec_args *sa)
+{
+  pmh_ctx ctx = s->ctx;
+  if (!(s->csr && !s->cvg && !s->o.distributed && pmh_knobs().mpgp_spec)) return PMH_SUCCESS;
+  if (!s->d_ctl) {
+    PMH_CHK(pmh_malloc(ctx, sizeof(int) * CTL_NWORDS, (void **)&s->d_ctl));
+    PMH_CHK(pmh_malloc(ctx, sizeof(double) * 3 * SPEC_BATCH, (void **)&s->d_ring));
+    PMH_HIP(hipHostMalloc((void **)&s->h_ctl, sizeof(int) * CTL_NWORDS, hipHostMallocMapped));
+    PMH_HIP(hipHostMalloc((void **)&s->h_ring, sizeof(double) * 3 * SPEC_BATCH, hipHostMallocMapped));
+  }
+  PMH_CHK(converged_default_setup(s));
+  sa->ctl = s->d_ctl, sa->ring = s->d_ring, sa->ring_cap = SPEC_BATCH, sa->max_it = s->o.max_it;
+  sa->ttol = s->ttol, sa->divtol_rhs = s->o.divtol * s->norm_rhs_div, sa->gamma2 = gamma2;
+  return PMH_SUCCESS;
+}
+
+// a batch of CG steps decided on the device (the SPEC variant of k_step_update: the test of mpgp.c:531, :535 and :547 from the device scalars): no host round trip between
+// them.  *halted = false: the whole batch were CG steps
+static int f_spec_batch(pmh_mpgp s, fused_state &st, const pmh_spec_args &sa, bool *halted)
+{
+  pmh_ctx          ctx = s->ctx;
+  const int        n = s->n, nbatch = st.spec_len;
+  const phase_vecs v    = vecs_of(s);
+  int             *halt = s->d_ctl + CTL_HALT;
+  s->x_applied          = false;
+  s->h_ctl[CTL_HALT] = 0, s->h_ctl[CTL_ITER] = s->iteration, s->h_ctl[CTL_NCG] = 0, s->h_ctl[CTL_BASE] = s->iteration;
+  PMH_HIP(hipMemcpyAsync(s->d_ctl, s->h_ctl, sizeof(int) * CTL_NWORDS, hipMemcpyHostToDevice, ctx->stream));
+  for (int j = 0; j < nbatch; j++) {
+    PMH_CHK(phase_step(ctx, n, v, false, &sa, nullptr, 0.0, 0));
+    PMH_CHK(note_split(s, false, halt, s->d_ctl + CTL_ITER));
+    PMH_CHK(phase_dir(ctx, n, v, halt, nullptr, 0, 0.0));
+    PMH_CHK(f_apply_p1(s, halt));
+  }
+  PMH_HIP(hipMemcpyAsync(s->h_ctl, s->d_ctl, sizeof(int) * CTL_NWORDS, hipMemcpyDeviceToHost, ctx->stream));
+  PMH_HIP(hipMemcpyAsync(s->h_ring, s->d_ring, sizeof(double) * 3 * SPEC_BATCH, hipMemcpyDeviceToHost, ctx->stream));
+  PMH_CHK(pmh_sync(ctx));
+  const int ndev = s->h_ctl[CTL_ITER] - s->iteration;
+  for (int j = 0; j < ndev; j++) {
+    monitor_push(s, sqrt(s->h_ring[3 * j]), sqrt(s->h_ring[3 * j + 1]), sqrt(s->h_ring[3 * j + 2])); // QPSMonitorDefault_MPGP line of iteration s->iteration + j
+    s->step = 'c';
+  }
+  s->iteration += ndev, st.ncg += ndev, st.nmv += ndev;
+  // 0 after a batch that took no step: the host path decides when speculation resumes
+  st.spec_len = (ndev >= nbatch) ? std::min(SPEC_BATCH, 2 * nbatch) : ndev;
+  *halted     = s->h_ctl[CTL_HALT] != 0;
+  return PMH_SUCCESS;
+}
+
+// the host's test: the norms of the split (mpgp.c:514-521), the monitor (:524-528) and the convergence test (:531) -> s->reason
+static int f_host_test(pmh_mpgp s, fused_state &st, double *gcTgc, double *gfTgf)
+{
+  pmh_ctx ctx = s->ctx;
+  if (s->pre_test) PMH_CHK(s->pre_test(s->pre_test_user));
+  PMH_CHK(pmh_sync(ctx));
+  if (st.check_projection) {
+    st.check_projection = false;
+    // The projection did change an entry: what the operator kept belongs to the vector as it was before.  Everything the first gradient wrote (g, gf, p, the
+    // partial sums, the emitted sums) is written again by the full application to the projected x -- the launches a solve without the caller's word makes
+    // (and its note replaces what the first gradient left to the host).  Several ranks: x is replicated bit for bit and every rank ran the same projection on
+    // it, so every rank reads the same word here and all of them enter the full application's all-reduce, or none does
+    if (ctx->h_scal[PMH_SLOT_PROJ_CHANGED] != 0.0) {
+      pmh_knobs().chain_replays_redone++;
+      s->A->emit_invalidate();
+      PMH_CHK(f_gradient_split(s, false));
+      PMH_CHK(pmh_sync(ctx));
+    }
+  }
+  s->owed.host_sums(ctx);
+  s->rnorm  = sqrt(ctx->h_scal[S_GP2]);
+  *gcTgc    = ctx->h_scal[S_GC2];
+  *gfTgf    = ctx->h_scal[S_GF2];
+  s->gfnorm = sqrt(*gfTgf);
+  s->gcnorm = sqrt(*gcTgc);
+  return test_convergence(s);
+}
+
+// CG step (mpgp.c:547-560)
+static int f_cg_step(pmh_mpgp s, fused_state &st, double acg, double pAp)
+{
+  pmh_ctx          ctx = s->ctx;
+  const int        n   = s->n;
+  const phase_vecs v   = vecs_of(s);
+  st.ncg++, s->step = 'c';
+  st.spec_len = std::max(st.spec_len, 1); // a CG step taken by the host: the next ones may well be CG steps too
+  pmh_emit_args ea;
+  // x -= acg p with the segment sums of G0 x left behind; acg as the host has it; the four sums' block partials go to the pinned host copy
+  const pmh_emit_args *e = emit_try(s, true, false, &ea);
+  PMH_CHK(phase_step(ctx, n, v, false, nullptr, e, acg, 0));
+  PMH_CHK(note_split(s, e));
+  const pmh_emit_args *ep = e ? emit_try(s, false, true, &ea) : nullptr;
+  if (!ep) { // the plain direction kernel takes Ap'gf from d_scal: a step that left its sums to the host has them finalised on the device after all
+    PMH_CHK(s->owed.settle(ctx, owed_sums::SPLIT, true));
+    s->cx[1] = false;
+  }
+  PMH_CHK(phase_dir(ctx, n, v, nullptr, ep, emit_blocks(n), pAp));
+  st.p_fresh = false;
+  return PMH_SUCCESS;
+}
+
+// expansion step (mpgp.c:561-616), std direction + fixed length => no re-projection (:388), with the gradient at the new x (:578-580) and its split (:612-615)
+static int f_expansion_step(pmh_mpgp s, fused_state &st, double afeas)
+{
+  st.nexp++, s->step = 'e';
+  // the operator's P1 pass already formed k_expansion_std's iterate (svm.hip): it hands it over with the gradient
+  const bool prepared = s->epi_ok == 1 && s->A->spec_expansion_ready();
+  if (!prepared) {
+    pmh_emit_args ea;
+    PMH_CHK(phase_expansion(s->ctx, s->n, vecs_of(s), afeas, s->alpha, emit_try(s, true, false, &ea)));
+  } else {
+    s->cx[0] = false;
+    s->A->emit_invalidate();
+  }
+  PMH_CHK(f_gradient_split(s, true, prepared)); // the speculative P1 (f_speculate_next) finalises both groups of partial sums
+  st.nmv++, st.p_fresh = true;
+  return PMH_SUCCESS;
+}
+
+// proportioning step (mpgp.c:617-639)
+static int f_proportioning_step(pmh_mpgp s, fused_state &st)
+{
+  pmh_ctx          ctx = s->ctx;
+  const int        n   = s->n;
+  const phase_vecs v   = vecs_of(s);
+  st.nprop++, s->step = 'p';
+  st.spec = st.p_fresh = false; // a speculative P1 (if any) used the wrong direction; it is simply not counted
+  pmh_emit_args ea;
+  PMH_CHK(phase_prop_dir(ctx, n, v, emit_try(s, false, true, &ea)));
+  PMH_CHK(f_apply_p1(s));
+  st.nmv++;
+  // the product left its sums to the host: the step forms acg from the P1 block partials itself (no host wait in between).  Otherwise the step reads acg from
+  // d_scal: P1 rows that were left to the host are finalised on the device after all
+  const pmh_emit_args *e = s->owed.p1.owed == owed_sums::HOST ? emit_try(s, true, true, &ea) : nullptr;
+  if (!e) {
+    PMH_CHK(s->owed.settle(ctx, owed_sums::P1, true));
+    s->cx[0] = s->cx[1] = false;
+  }
+  PMH_CHK(phase_step(ctx, n, v, true, nullptr, e, 0.0, s->owed.p1.nb));
+  return note_split(s, e);
+}
+
+// Speculation: whatever the next step type, unless it is a proportioning step it starts with Ap = A p -- enqueued before the host has seen this step's norms,
+// so that the round trip costs nothing.  If the NEXT test ends the solve that product is wasted (0.35 ms for configs[2] against the ~30 us of an exposed round
+// trip): the test reports how far the norm is above its threshold (cvg_margin), and with the last step's reduction the driver skips the speculation when the
+// next norm is likely to pass (SMALXE's early outer iterations end their inner solves after 2-3 steps: 8 of 63 products in the driver's 20-step window were
+// such orphans).  Nothing numerical depends on it: the product is then enqueued after the test, by the `!st.spec` branch of the loop.
+static int f_speculate_next(pmh_mpgp s, fused_state &st)
+{
+  bool         orphan_risk = false;
+  const double m           = s->cvg_margin;
+  if (m > 0.0) {
+    const double red = (st.prev_margin > 0.0 && m < st.prev_margin) ? m / st.prev_margin : 1.0;
+    orphan_risk      = (m < 3.0) || (m * red < 2.0);
+  }
+  st.prev_margin = m;
+  if (orphan_risk) {
+    st.spec = false;
+    return s->owed.settle(s->ctx, owed_sums::SPLIT); // a gradient split that left its sums for the product's finalising launch: the host reads the norms next
+  }
+  if (s->pre_p1) PMH_CHK(s->pre_p1(s->pre_p1_user));
+  PMH_CHK(f_apply_p1(s, nullptr, st.p_fresh));
+  st.spec = true;
+  return PMH_SUCCESS;
 }
 
 static int solve_fused(pmh_mpgp s)
 {
   pmh_ctx ctx = s->ctx;
-  int     n   = s->n;
-  PMH_CHK(ensure_work(s, 1));
-  PMH_CHK(ensure_work(s, 3));
-  PMH_CHK(ensure_work(s, 4));
-  PMH_CHK(ensure_work(s, 5));
-  double      *gf = s->work[1], *g = s->work[3], *p = s->work[4], *Ap = s->work[5], *x = s->x;
-  const double gamma2 = s->o.gamma * s->o.gamma, astol = s->o.astol;
-  int          nmv = 0, ncg = 0, nprop = 0, nexp = 0;
-  bool         spec = false; // P1 for the current p already enqueued
-  double       prev_margin = 0.0; // cvg_margin of the previous test (see the speculation at the end of the loop)
-  bool         p_fresh = false; // p is the gf of the last gradient split, untouched (told to operators that pair their passes)
-
-  s->cx[0] = s->cx[1] = false; // x and p come from outside
-  s->hsum4 = s->hsum3 = 0;
-  // The caller's word (pmh_mpgp_set_first_operand_applied) that x is the vector the operator was last applied to: the operator keeps what it remembers of that
-  // application, and the first gradient below passes the word on.  The projection rewrites a feasible x with the bits it had -- but the x an expansion step
-  // leaves (x - afeas p - alpha gr, no re-projection) may lie below a bound by a rounding error, and then the projection does change it.  So the projection
-  // leaves a word for the host where it changed an entry, read after the first wait below (no wait of its own): the gradient is then taken again, in full.
-  // (Not with row-distributed vectors: that word would be each rank's own.)
-  const bool first_same = s->first_applied != 0 && !s->g_valid && !s->o.distributed;
-  bool       check_projection = false;
-  s->first_applied = 0, s->x_applied = false;
-  s->A->emit_invalidate(first_same);
-  if (first_same) PMH_CHK(pmh_qpc_box_project_flag(ctx, n, x, s->lb, s->ub, x, PMH_SLOT_PROJ_CHANGED));
-  else PMH_CHK(pmh_qpc_box_project(ctx, n, x, s->lb, s->ub, x)); // mpgp.c:497
-  s->fin4_pending = 0;
-  // asked once: a refusal (PMH_EPI_UNSUPPORTED) clears it.  (Row-distributed vectors: the operator's
-  if (s->epi_ok < 0) s->epi_ok = (s->csr || !pmh_knobs().vec_epi) ? 0 : 1;
-                                                                                  // partials are finalised at once and completed across the ranks,
-                                                                                  // pmh_finalize_partials)
-  if (s->g_valid) { // the caller carried g = A x - b over from the previous solve (pmh_smalxe_set_reuse_products): the split, p = gf and the norms only
-    s->g_valid = 0;
-    pmh_emit_args ea;
-    if (emit_try(s, false, true, &ea)) {
-      LAUNCH_EMIT(k_split_setp<true>, (const double *)x, (const double *)g, s->lb, s->ub, astol, gf, p, ctx->d_partials, ctx->partials_cap, ea, ctx->h_partials);
-      s->hsum4 = emit_blocks(s);
-    } else {
-      LAUNCH(k_split_setp<false>, (const double *)x, (const double *)g, s->lb, s->ub, astol, gf, p, ctx->d_partials, ctx->partials_cap, g_noea, (double *)nullptr);
-      PMH_CHK(finalize_vec4(s));
-    }
-  } else {
-    int replayed = 0;
-    PMH_CHK(f_gradient_split(s, false, false, first_same, &replayed)); // :500-507 (the host reads the norms before any P1: finalised at once)
-    check_projection = first_same && replayed != 0; // the operator did take the caller's word
-    nmv++;
-    p_fresh = true;
-  }
-  // (the carried-gradient branch did not run the operator's own gradient split: whatever pairing state an operator keeps from the previous solve must not be
-  // matched with this p -- p_fresh stays false there, the first product of the solve is then a lone application)
-  s->step      = ' ';
-  s->iteration = 0;
-  pmh_spec_args nosa;
-  memset(&nosa, 0, sizeof(nosa));
-  auto k_cg_spec = k_step_update<false, true>;
-  auto k_cg_host = k_step_update<false, false>;
-  auto k_prop_host = k_step_update<true, false>;
-  auto k_cg_emit = k_step_update<false, false, true>;
-  auto k_prop_emit = k_step_update<true, false, true>;
-  // the device-side CG chain needs the default convergence test (its constants go to the kernels) and a CSR operator
-  const int SPEC_BATCH = 16;
-  bool      can_spec   = s->csr && !s->cvg && !s->o.distributed && pmh_knobs().mpgp_spec;
-  pmh_spec_args sa     = nosa;
-  if (can_spec) {
-    if (!s->d_ctl) {
-      PMH_CHK(pmh_malloc(ctx, sizeof(int) * CTL_NWORDS, (void **)&s->d_ctl));
-      PMH_CHK(pmh_malloc(ctx, sizeof(double) * 3 * SPEC_BATCH, (void **)&s->d_ring));
-      PMH_HIP(hipHostMalloc((void **)&s->h_ctl, sizeof(int) * CTL_NWORDS, hipHostMallocMapped));
-      PMH_HIP(hipHostMalloc((void **)&s->h_ring, sizeof(double) * 3 * SPEC_BATCH, hipHostMallocMapped));
-    }
-    if (!s->cvg_setup) { // QPSConvergedDefaultSetUp qps.c:718-731
-      PMH_CHK(pmh_vec_norm2(ctx, n, s->b, &s->norm_rhs));
-      s->ttol         = fmax(s->o.rtol * s->norm_rhs, s->o.atol);
-      s->norm_rhs_div = s->norm_rhs;
-      s->cvg_setup    = 1;
-    }
-    sa.ctl = s->d_ctl, sa.ring = s->d_ring, sa.ring_cap = SPEC_BATCH;
-    sa.max_it = s->o.max_it;
-    sa.ttol = s->ttol, sa.divtol_rhs = s->o.divtol * s->norm_rhs_div, sa.gamma2 = gamma2;
-  }
-  // length of the next speculative batch: a batch that ran to its end doubles it, one that halted early cuts it to what it ran (an expansion-heavy stretch
-  // would otherwise enqueue 16 x 4 no-op launches behind every expansion step: ~0.1 ms each time); 0 = the host takes the next step.  The iterates do not
-  // depend on it: the device chain takes exactly the steps the host would.
-  int spec_len = SPEC_BATCH;
+  for (int i : {1, 3, 4, 5}) PMH_CHK(ensure_work(s, i));
+  const double gamma2 = s->o.gamma * s->o.gamma;
+  fused_state  st;
+  PMH_CHK(f_first_gradient(s, st)); // mpgp.c:497-507
+  s->step = ' ', s->iteration = 0;
+  pmh_spec_args sa = {};
+  PMH_CHK(f_spec_setup(s, gamma2, &sa));
   while (1) {
-    if (can_spec && spec && spec_len > 0) {
-      // a batch of CG steps decided on the device: no host round trip between them
-      const int nbatch = spec_len;
-      s->x_applied     = false;
-      s->h_ctl[CTL_HALT] = 0, s->h_ctl[CTL_ITER] = s->iteration, s->h_ctl[CTL_NCG] = 0, s->h_ctl[CTL_BASE] = s->iteration;
-      PMH_HIP(hipMemcpyAsync(s->d_ctl, s->h_ctl, sizeof(int) * CTL_NWORDS, hipMemcpyHostToDevice, ctx->stream));
-      for (int j = 0; j < nbatch; j++) {
-        LAUNCH(k_cg_spec, (const double *)ctx->d_scal, sa, x, g, p, (const double *)Ap, s->lb, s->ub, astol, gf, ctx->d_partials, ctx->partials_cap, g_noea, (double *)nullptr, 0.0, 0);
-        PMH_CHK(finalize_vec4(s, s->d_ctl + CTL_HALT, s->d_ctl + CTL_ITER));
-        LAUNCH(k_dir_update<false>, (const double *)ctx->d_scal, (const int *)(s->d_ctl + CTL_HALT), (const double *)gf, p, g_noea, (const double *)nullptr, 0, 0.0);
-        PMH_CHK(f_apply_p1(s, s->d_ctl + CTL_HALT));
-      }
-      PMH_HIP(hipMemcpyAsync(s->h_ctl, s->d_ctl, sizeof(int) * CTL_NWORDS, hipMemcpyDeviceToHost, ctx->stream));
-      PMH_HIP(hipMemcpyAsync(s->h_ring, s->d_ring, sizeof(double) * 3 * SPEC_BATCH, hipMemcpyDeviceToHost, ctx->stream));
-      PMH_CHK(pmh_sync(ctx));
-      const int ndev = s->h_ctl[CTL_ITER] - s->iteration;
-      for (int j = 0; j < ndev; j++) {
-        if (s->o.monitor) { // QPSMonitorDefault_MPGP line of iteration s->iteration + j
-          s->t_step.push_back(s->step);
-          s->t_gp.push_back(sqrt(s->h_ring[3 * j]));
-          s->t_gf.push_back(sqrt(s->h_ring[3 * j + 1]));
-          s->t_gc.push_back(sqrt(s->h_ring[3 * j + 2]));
-          s->t_alpha.push_back(s->alpha);
-        }
-        s->step = 'c';
-      }
-      s->iteration += ndev;
-      ncg += ndev;
-      nmv += ndev;
-      // 0 after a batch that took no step: the host path decides when speculation resumes
-      spec_len = (ndev >= nbatch) ? std::min(SPEC_BATCH, 2 * nbatch) : ndev;
-      if (!s->h_ctl[CTL_HALT]) continue; // whole batch were CG steps
+    if (sa.ctl && st.spec && st.spec_len > 0) {
+      bool halted;
+      PMH_CHK(f_spec_batch(s, st, sa, &halted));
+      if (!halted) continue; // whole batch were CG steps
     }
-    if (s->pre_test) PMH_CHK(s->pre_test(s->pre_test_user));
-    PMH_CHK(pmh_sync(ctx));
-    if (check_projection) {
-      check_projection = false;
-      // The projection did change an entry: what the operator kept belongs to the vector as it was before.  Everything the first gradient wrote (g, gf, p, the
-      // partial sums, the emitted sums) is written again by the full application to the projected x -- the launches a solve without the caller's word makes.
-      // Several ranks: x is replicated bit for bit and every rank ran the same projection on it, so every rank reads the same word here and all of them enter
-      // the full application's all-reduce, or none does
-      if (ctx->h_scal[PMH_SLOT_PROJ_CHANGED] != 0.0) {
-        pmh_knobs().chain_replays_redone++;
-        s->hsum4 = 0;
-        s->A->emit_invalidate();
-        PMH_CHK(f_gradient_split(s, false));
-        PMH_CHK(pmh_sync(ctx));
-      }
-    }
-    host_sums(s);
-    s->rnorm           = sqrt(ctx->h_scal[S_GP2]);
-    const double gcTgc = ctx->h_scal[S_GC2], gfTgf = ctx->h_scal[S_GF2];
-    s->gfnorm = sqrt(gfTgf);
-    s->gcnorm = sqrt(gcTgc);
-    PMH_CHK(test_convergence(s));
+    double gcTgc, gfTgf;
+    PMH_CHK(f_host_test(s, st, &gcTgc, &gfTgf)); // mpgp.c:514-531
     if (s->reason != PMH_CONVERGED_ITERATING) break;
 
     if (gcTgc <= gamma2 * gfTgf) { // proportional (mpgp.c:535)
-      if (!spec) {
-        PMH_CHK(f_apply_p1(s, nullptr, p_fresh));
+      if (!st.spec) {
+        PMH_CHK(f_apply_p1(s, nullptr, st.p_fresh));
         PMH_CHK(pmh_sync(ctx));
-        host_sums(s);
+        s->owed.host_sums(ctx);
       }
-      spec = false;
-      nmv++;
-      const double pAp = ctx->h_scal[S_PAP], acg = ctx->h_scal[S_GP] / pAp, afeas = ctx->h_scal[S_FEAS];
-      if (acg <= afeas) { // CG step (mpgp.c:547-560)
-        ncg++;
-        s->step = 'c';
-        spec_len = std::max(spec_len, 1); // a CG step taken by the host: the next ones may well be CG steps too
-        pmh_emit_args ea;
-        bool emitted_step = false;
-        // x -= acg p with the segment sums of G0 x left behind; acg as the host has it; the four sums' block partials go to the pinned host copy
-        if (emit_try(s, true, false, &ea)) {
-          LAUNCH_EMIT(k_cg_emit, (const double *)ctx->d_scal, nosa, x, g, p, (const double *)Ap, s->lb, s->ub, astol, gf, ctx->d_partials, ctx->partials_cap, ea, ctx->h_partials, acg, 0);
-          s->hsum4 = emit_blocks(s), emitted_step = true;
-        } else {
-          LAUNCH(k_cg_host, (const double *)ctx->d_scal, nosa, x, g, p, (const double *)Ap, s->lb, s->ub, astol, gf, ctx->d_partials, ctx->partials_cap, g_noea, (double *)nullptr, 0.0, 0);
-          PMH_CHK(finalize_vec4(s));
-        }
-        if (emitted_step && emit_try(s, false, true, &ea)) {
-          LAUNCH_EMIT(k_dir_update<true>, (const double *)ctx->d_scal, (const int *)nullptr, (const double *)gf, p, ea, (const double *)ctx->d_partials, emit_blocks(s), pAp);
-        } else {
-          if (emitted_step) PMH_CHK(finalize_vec4_from(s, emit_blocks(s))); // (not reached: an operator that took the step's emission takes the direction's)
-          s->cx[1] = false;
-          LAUNCH(k_dir_update<false>, (const double *)ctx->d_scal, (const int *)nullptr, (const double *)gf, p, g_noea, (const double *)nullptr, 0, 0.0);
-        }
-        p_fresh = false;
-      } else { // expansion (mpgp.c:561-616), std direction + fixed length => no re-projection (:388)
-        nexp++;
-        s->step = 'e';
-        // the operator's P1 pass already formed k_expansion_std's iterate (svm.hip): it hands it over with the gradient
-        const bool prepared = s->epi_ok == 1 && s->A->spec_expansion_ready();
-        if (!prepared) {
-          pmh_emit_args ea;
-          if (emit_try(s, true, false, &ea)) LAUNCH_EMIT(k_expansion_std<true>, afeas, s->alpha, x, (const double *)g, (const double *)p, (const double *)Ap, s->lb, s->ub, astol, ea);
-          else LAUNCH(k_expansion_std<false>, afeas, s->alpha, x, (const double *)g, (const double *)p, (const double *)Ap, s->lb, s->ub, astol, g_noea);
-        } else {
-          s->cx[0] = false;
-          s->A->emit_invalidate();
-        }
-        PMH_CHK(f_gradient_split(s, true, prepared)); // the speculative P1 below finalises both groups of partial sums
-        p_fresh = true;
-        nmv++;
-      }
-    } else { // proportioning (mpgp.c:617-639)
-      nprop++;
-      s->step = 'p';
-      spec    = false; // a speculative P1 (if any) used the wrong direction; it is simply not counted
-      p_fresh = false;
-      pmh_emit_args ea;
-      if (emit_try(s, false, true, &ea)) LAUNCH_EMIT(k_prop_dir<true>, (const double *)x, (const double *)g, s->lb, s->ub, astol, p, ea);
-      else LAUNCH(k_prop_dir<false>, (const double *)x, (const double *)g, s->lb, s->ub, astol, p, g_noea);
-      PMH_CHK(f_apply_p1(s));
-      nmv++;
-      // the product left its sums to the host: the step forms acg from the P1 block partials itself (no host wait in between)
-      if (s->hsum3 && emit_try(s, true, true, &ea)) {
-        LAUNCH_EMIT(k_prop_emit, (const double *)ctx->d_scal, nosa, x, g, p, (const double *)Ap, s->lb, s->ub, astol, gf, ctx->d_partials, ctx->partials_cap, ea, ctx->h_partials, 0.0, s->hsum3);
-        s->hsum4 = emit_blocks(s);
-      } else {
-        // (not reached: the operator that left the sums to the host takes the emission) the step reads acg from d_scal: finalise the P1 rows on the device
-        if (s->hsum3) {
-          const int ops[3] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
-          PMH_CHK(pmh_finalize_partials(ctx, ctx->d_partials + (size_t)4 * ctx->partials_cap, ctx->partials_cap, s->hsum3, 3, ops, S_PAP));
-          s->hsum3 = 0;
-        }
-        s->cx[0] = s->cx[1] = false;
-        LAUNCH(k_prop_host, (const double *)ctx->d_scal, nosa, x, g, p, (const double *)Ap, s->lb, s->ub, astol, gf, ctx->d_partials, ctx->partials_cap, g_noea, (double *)nullptr, 0.0, 0);
-        PMH_CHK(finalize_vec4(s));
-      }
-    }
-    // speculation: whatever the next step type, unless it is a proportioning step it starts with Ap = A p -- enqueued before the host has seen this step's
-    // norms, so that the round trip costs nothing.  If the NEXT test ends the solve that product is wasted (0.35 ms for configs[2] against the ~30 us of an
-    // exposed round trip): the test reports how far the norm is above its threshold (cvg_margin), and with the last step's reduction the driver skips the
-    // speculation when the next norm is likely to pass (SMALXE's early outer iterations end their inner solves after 2-3 steps: 8 of 63 products in the
-    // driver's 20-step window were such orphans). Nothing numerical depends on it: the product is then enqueued after the test, by the `!spec` branch above.
-    bool orphan_risk = false;
-    {
-      const double m = s->cvg_margin;
-      if (m > 0.0) {
-        const double red = (prev_margin > 0.0 && m < prev_margin) ? m / prev_margin : 1.0;
-        orphan_risk      = (m < 3.0) || (m * red < 2.0);
-      }
-      prev_margin = m;
-    }
-    if (orphan_risk) {
-      spec = false;
-      if (s->fin4_pending) { // the gradient split left its partial sums for the product's finalising launch: the host reads the norms next
-        PMH_CHK(finalize_vec4(s));
-        s->fin4_pending = 0;
-      }
+      st.spec = false;
+      st.nmv++;
+      const double pAp = ctx->h_scal[S_PAP], acg = ctx->h_scal[S_GP] / pAp, afeas = ctx->h_scal[S_FEAS]; // mpgp.c:541-546
+      if (acg <= afeas) PMH_CHK(f_cg_step(s, st, acg, pAp)); // mpgp.c:547-560
+      else PMH_CHK(f_expansion_step(s, st, afeas));          // mpgp.c:561-616
     } else {
-      if (s->pre_p1) PMH_CHK(s->pre_p1(s->pre_p1_user));
-      PMH_CHK(f_apply_p1(s, nullptr, p_fresh));
-      spec = true;
+      PMH_CHK(f_proportioning_step(s, st)); // mpgp.c:617-639
     }
+    PMH_CHK(f_speculate_next(s, st));
     s->iteration++;
   }
-  s->ncg += ncg, s->nexp += nexp, s->nmv += nmv, s->nprop += nprop;
+  s->ncg += st.ncg, s->nexp += st.nexp, s->nmv += st.nmv, s->nprop += st.nprop;
   return PMH_SUCCESS;
 }
 
@@ -1371,86 +1411,41 @@ extern "C" int pmh_mpgp_test_block_partials(pmh_ctx ctx, int n, const double *a,
   return PMH_SUCCESS;
 }
 
-#define TLAUNCH(kern, ...) \
-  do { \
-    if (n > 0) hipLaunchKernelGGL(kern, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, (long long)n, __VA_ARGS__); \
-  } while (0)
-#define TLAUNCH_EMIT(kern, ...) \
-  do { \
-    if (n > 0) hipLaunchKernelGGL(kern, dim3((n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE), dim3(PMH_EMIT_TILE), 0, ctx->stream, (long long)n, __VA_ARGS__); \
-  } while (0)
-
+// through the launchers the drivers use: the argument struct, the emission arguments as emit_try asks for them, the phase, the driver's finalising launch
 static int test_phase_launch(pmh_ctx ctx, int phase, int n, pmh_mpgp_phase_test *t, int *d_ctl, double *d_ring)
 {
-  const int     ld = ctx->partials_cap, nblocks = n > 0 ? (t->emit ? (n + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE : pmh_vec_grid(n)) : 0;
-  const int    *halt = t->use_ctl ? d_ctl + CTL_HALT : nullptr;
-  int          *post = t->use_ctl ? d_ctl + CTL_ITER : nullptr;
-  const double *scal = ctx->d_scal;
-  const int     ops4[4] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM}, ops3[3] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
-  pmh_spec_args sa;
-  memset(&sa, 0, sizeof(sa));
+  const phase_vecs v = {t->x, t->g, t->p, t->Ap, t->gf, t->lb, t->ub, t->astol};
+  const int        nblocks = t->emit ? (n > 0 ? emit_blocks(n) : 0) : vec_blocks(n);
+  const int       *halt    = t->use_ctl ? d_ctl + CTL_HALT : nullptr;
+  int             *post    = t->use_ctl ? d_ctl + CTL_ITER : nullptr;
+  pmh_spec_args    sa      = {};
   if (t->spec) {
     sa.ctl = d_ctl, sa.ring = d_ring, sa.ring_cap = t->ring_cap, sa.max_it = t->max_it;
     sa.ttol = t->ttol, sa.divtol_rhs = t->divtol_rhs, sa.gamma2 = t->gamma2;
   }
-  // the emission arguments from a chained operator, as emit_try asks for them: the kernel of this phase writes x (wx) and / or p (wp)
-  pmh_emit_args ea = g_noea;
+  // a chained operator's emission: the kernel of this phase writes x (wx) and / or p (wp); without an operator the tile variant runs with nothing to emit
+  pmh_emit_args        eargs = g_noea;
+  const pmh_emit_args *ea    = t->emit ? &eargs : nullptr;
   if (t->emit && t->op) {
     const bool wx = phase == PMH_PHASE_EXPANSION || phase == PMH_PHASE_STEP, wp = phase == PMH_PHASE_SPLIT || phase == PMH_PHASE_DIR || phase == PMH_PHASE_PROP_DIR || (phase == PMH_PHASE_STEP && t->setp);
-    if (t->op->emit_begin(wx ? t->x : nullptr, wp ? t->p : nullptr, &ea) != PMH_SUCCESS) return pmh_set_error(PMH_ERR_SUP, "pmh_mpgp_test_phase: the operator does not run on the dual-space chain");
+    if (t->op->emit_begin(wx ? t->x : nullptr, wp ? t->p : nullptr, &eargs) != PMH_SUCCESS) return pmh_set_error(PMH_ERR_SUP, "pmh_mpgp_test_phase: the operator does not run on the dual-space chain");
   }
-  int fin = 0; // quantities the driver's finalising launch of this phase reduces
+  int group = 0; // the rows the driver's finalising launch of this phase reduces (owed_sums), -1: the objective's one sum
   switch (phase) {
-  case PMH_PHASE_SPLIT:
-    if (t->emit) TLAUNCH_EMIT(k_split_setp<true>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->gf, t->p, ctx->d_partials, ld, ea, ctx->h_partials);
-    else TLAUNCH(k_split_setp<false>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->gf, t->p, ctx->d_partials, ld, g_noea, (double *)nullptr);
-    fin = 4;
-    break;
-  case PMH_PHASE_STEP: {
-#define STEP_ARGS scal, sa, t->x, t->g, t->p, (const double *)t->Ap, t->lb, t->ub, t->astol, t->gf, ctx->d_partials, ld, ea
-    if (t->emit && t->setp) TLAUNCH_EMIT((k_step_update<true, false, true>), STEP_ARGS, ctx->h_partials, t->acg_host, t->nb);
-    else if (t->emit) TLAUNCH_EMIT((k_step_update<false, false, true>), STEP_ARGS, ctx->h_partials, t->acg_host, t->nb);
-    else if (t->spec) TLAUNCH((k_step_update<false, true>), STEP_ARGS, (double *)nullptr, 0.0, 0);
-    else if (t->setp) TLAUNCH((k_step_update<true, false>), STEP_ARGS, (double *)nullptr, 0.0, 0);
-    else TLAUNCH((k_step_update<false, false>), STEP_ARGS, (double *)nullptr, 0.0, 0);
-#undef STEP_ARGS
-    fin = 4;
-    break;
+  case PMH_PHASE_SPLIT: PMH_CHK(phase_split(ctx, n, v, ea)); group = owed_sums::SPLIT; break;
+  case PMH_PHASE_STEP: PMH_CHK(phase_step(ctx, n, v, t->setp != 0, t->spec ? &sa : nullptr, ea, t->acg_host, t->nb)); group = owed_sums::SPLIT; break;
+  case PMH_PHASE_DIR: PMH_CHK(phase_dir(ctx, n, v, halt, ea, t->nb, t->pAp_host)); break;
+  case PMH_PHASE_PROP_DIR: PMH_CHK(phase_prop_dir(ctx, n, v, ea)); break;
+  case PMH_PHASE_EXPANSION: PMH_CHK(phase_expansion(ctx, n, v, t->afeas, t->alpha, ea)); break;
+  case PMH_PHASE_P1_DOTS: PMH_CHK(phase_p1_dots(ctx, n, v)); group = owed_sums::P1; break;
+  case PMH_PHASE_THREE_NORMS: PMH_CHK(phase_three_norms(ctx, n, t->x, t->g, t->gf)); group = owed_sums::SPLIT; break;
+  case PMH_PHASE_OBJ: PMH_CHK(phase_obj(ctx, n, t->x, t->g, t->b)); group = -1; break;
   }
-  case PMH_PHASE_DIR:
-    if (t->emit) TLAUNCH_EMIT(k_dir_update<true>, scal, halt, (const double *)t->gf, t->p, ea, (const double *)ctx->d_partials, t->nb, t->pAp_host);
-    else TLAUNCH(k_dir_update<false>, scal, halt, (const double *)t->gf, t->p, g_noea, (const double *)nullptr, 0, 0.0);
-    break;
-  case PMH_PHASE_PROP_DIR:
-    if (t->emit) TLAUNCH_EMIT(k_prop_dir<true>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->p, ea);
-    else TLAUNCH(k_prop_dir<false>, (const double *)t->x, (const double *)t->g, t->lb, t->ub, t->astol, t->p, g_noea);
-    break;
-  case PMH_PHASE_EXPANSION:
-    if (t->emit) TLAUNCH_EMIT(k_expansion_std<true>, t->afeas, t->alpha, t->x, (const double *)t->g, (const double *)t->p, (const double *)t->Ap, t->lb, t->ub, t->astol, ea);
-    else TLAUNCH(k_expansion_std<false>, t->afeas, t->alpha, t->x, (const double *)t->g, (const double *)t->p, (const double *)t->Ap, t->lb, t->ub, t->astol, g_noea);
-    break;
-  case PMH_PHASE_P1_DOTS:
-    TLAUNCH(k_p1_dots, (const double *)t->p, (const double *)t->Ap, (const double *)t->g, (const double *)t->x, t->lb, t->ub, ctx->d_partials, ld);
-    fin = 3;
-    break;
-  case PMH_PHASE_THREE_NORMS:
-    TLAUNCH(k_three_norms, (const double *)t->x, (const double *)t->g, (const double *)t->gf, ctx->d_partials, ld);
-    fin = 4;
-    break;
-  case PMH_PHASE_OBJ:
-    TLAUNCH(k_obj_from_grad, (const double *)t->x, (const double *)t->g, t->b, ctx->d_partials);
-    fin = 1;
-    break;
-  }
-  PMH_HIP(hipGetLastError());
   if (!t->finalize) return PMH_SUCCESS;
-  if (fin == 4) return pmh_finalize_partials(ctx, ctx->d_partials, ld, nblocks, 4, ops4, S_APGF, halt, post);
-  if (fin == 3) return pmh_finalize_partials(ctx, ctx->d_partials, ld, nblocks, 3, ops3, S_PAP);
-  return pmh_finalize_partials(ctx, ctx->d_partials, ld, nblocks, 1, ops4, S_TMP);
+  if (group == owed_sums::SPLIT) return owed_sums::finalize(ctx, owed_sums::SPLIT, 0, nblocks, halt, post);
+  if (group == owed_sums::P1) return owed_sums::finalize(ctx, owed_sums::P1, 0, nblocks);
+  return finalize_obj(ctx, nblocks);
 }
-
-#undef TLAUNCH
-#undef TLAUNCH_EMIT
 
 extern "C" int pmh_mpgp_test_phase(pmh_ctx ctx, int phase, int n, pmh_mpgp_phase_test *t)
 {
