@@ -1220,6 +1220,12 @@ int pmh_bsr3_test_destroy(void *B);
  * class, 1 k_fxo_fin_all, 22 / 23 this rank's range of the representatives}.  PMH_ERR_STATE before there is a plan. */
 int pmh_fexplicit_test_load_class(pmh_fexplicit E, int cls, const double *W_host);
 int pmh_fexplicit_orbit_plan_info(pmh_fexplicit E, int cls, long long info[24]);
+/* pmh_fexplicit_orbit_adapted_info: what the block products (k_fxa_prod) run for class cls while it applies W_c in the symmetry-adapted basis (pmh_fexplicit_orbit_adapted);
+ * called by nothing inside the solvers.  20 entries per irrep i = 0 .. 9 at info + 20 i: {0 d, 1 m, 2 k steps of 8 columns nks, 3 blocks of 16 output rows, 4 blocks of 16
+ * columns, 5 .. 8 work items of 1 / 2 / 3 / 4 blocks of columns, 9 .. 12 trips of waves 0 .. 3 on an item of 1 or 2 blocks, 13 .. 16 on an item of 3 or 4, 17 / 18 k steps
+ * per trip of the two kinds (a wave's k range is its trips in increasing order), 19 zero}.  PMH_ERR_ARG for a storage other than PMH_FX_CLASS_ORBIT or a class out of
+ * range, PMH_ERR_STATE where the class is on the GEMM. */
+int pmh_fexplicit_orbit_adapted_info(pmh_fexplicit E, int cls, long long info[200]);
 /* U = K^+ F for 8 columns per block at once: F, U device arrays of 8 n doubles, entry (dof i, column r) at i * 8 + r; K, the V-cycle (pmh_matinv_set_pc_mg), the kernel
  * basis (pmh_matinv_set_nullspace: K^+ = P_R K^- P_R) and the tolerances are the solver's own; every (block, column) pair converges by its own test.  PMH_ERR_SUP where
  * the multi-right-hand-side kernels do not apply (K without regular 3 x 3 blocks, a V-cycle other than the fused fp32 one, the left generalised inverse). */

@@ -476,6 +476,7 @@ _PROTOS = {
     "pmh_fexplicit_dense_mult": [vp, vp, vp],
     "pmh_fexplicit_test_load_class": [vp, C.c_int, vp],
     "pmh_fexplicit_orbit_plan_info": [vp, C.c_int, vp],
+    "pmh_fexplicit_orbit_adapted_info": [vp, C.c_int, vp],
     "pmh_fexplicit_timing_enable": [vp, C.c_int, C.c_int],
     "pmh_fexplicit_timing_get": [vp, c_int_p, c_double_p, c_double_p],
     "pmh_matinv_attach_explicit": [vp, vp],

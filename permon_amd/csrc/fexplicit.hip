@@ -955,6 +955,13 @@ extern "C" int pmh_fexplicit_orbit_plan_info(pmh_fexplicit E, int cls, long long
   return fxs_orbit_plan_info(E->sh, cls, info);
 }
 
+extern "C" int pmh_fexplicit_orbit_adapted_info(pmh_fexplicit E, int cls, long long info[200])
+{
+  PMH_ARG(E && info);
+  if (!E->sh || E->storage != PMH_FX_CLASS_ORBIT) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_orbit_adapted_info: needs the PMH_FX_CLASS_ORBIT storage");
+  return fxs_orbit_adapted_info(E->sh, cls, info);
+}
+
 int pmh_fexplicit_set_window(pmh_fexplicit_s *E, fx_batch_window *w)
 {
   PMH_ARG(E);

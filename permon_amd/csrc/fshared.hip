@@ -708,7 +708,11 @@ static int fxa_build_class(fx_shared *S, fxs_class &C, bool spoil)
     for (int i : order) {
       const fxa_irrep &I = a->ir[i];
       for (int nb0 = 0; nb0 < I.nbt; nb0 += 4)
-        for (int ob = 0; ob < I.nob; ob++) items.insert(items.end(), {i, ob, nb0, std::min(4, I.nbt - nb0)});
+        for (int ob = 0; ob < I.nob; ob++) {
+          const int nbw = std::min(4, I.nbt - nb0);
+          items.insert(items.end(), {i, ob, nb0, nbw});
+          a->items_of_width[i][nbw - 1]++;
+        }
     }
     a->nitems = (int)(items.size() / 4);
   }
@@ -1222,6 +1226,27 @@ int fxs_orbit_plan_info(fx_shared *S, int c, long long info[24])
   const long long v[24] = {C.nc, C.ld, C.S, C.ngroups, C.xoff, C.nsym, C.nsymp, C.M_all, C.tm, C.Mp, C.nc ? C.Mp / C.tm : 0, C.tn, C.tnw, C.nseg, C.nkc, C.plan_units, C.plan_units_work, C.plan_smax,
                            C.wg_count, C.plan_wg2, kind, S->d_fin_args ? 1 : 0, C.m0, C.m1};
   memcpy(info, v, sizeof(v));
+  return PMH_SUCCESS;
+}
+
+// what k_fxa_prod runs for class c in the symmetry-adapted form (the layout of info: include/permon_hip.h); called by nothing inside the solvers
+int fxs_orbit_adapted_info(fx_shared *S, int c, long long info[200])
+{
+  PMH_ARG(S && info && c >= 0 && c < S->ncls);
+  if (!fxs_orbit_adapted(S, c)) return pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_orbit_adapted_info: class %d does not apply W_c in the symmetry-adapted basis", c);
+  const fxa_class *a = S->C[c].oa;
+  memset(info, 0, sizeof(long long) * 200);
+  for (int i = 0; i < OAB_NIRREP; i++) {
+    const fxa_irrep &I = a->ir[i];
+    long long       *v = info + 20 * i;
+    v[0] = I.d, v[1] = I.m, v[2] = I.nks, v[3] = I.nob, v[4] = I.nbt;
+    for (int nbw = 1; nbw <= 4; nbw++) v[4 + nbw] = a->items_of_width[i][nbw - 1];
+    for (int wide = 0; wide < 2; wide++) {
+      const int U = fxa_trip_steps(wide ? 4 : 1);
+      v[17 + wide] = U;
+      for (int w = 0; w < FXA_WAVES; w++) v[9 + 4 * wide + w] = (fxa_wave_k0(I.nks, U, w + 1) - fxa_wave_k0(I.nks, U, w)) / U;
+    }
+  }
   return PMH_SUCCESS;
 }
 

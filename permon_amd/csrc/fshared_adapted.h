@@ -15,8 +15,6 @@
 #pragma once
 #include "fshared_kernels.h"
 
-#define FXA_WAVES 4  // waves per workgroup of k_fxa_prod: they share the k range of ONE block of 16 output rows
-#define FXA_KU 8     // k steps per unrolled trip: nks is a multiple of it
 #define FXA_CB 64    // columns of the multivector per workgroup of the transforms
 #define FXA_LDT 49   // row length of an orbit's table in LDS
 
@@ -70,9 +68,13 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_fxa_transform(const fxa_irrep *__
   }
 }
 
-// 16 rows of Y^_i = W^_i X^_i on NBW blocks of 16 columns.  The four waves of the workgroup share the k range (whole trips of U k steps: U KB of W^ and U NBW KB of X^,
-// which stays in the caches, in flight per wave), so that a row block's sum is a chain of a quarter of the products and the chip holds several waves per SIMD to
-// cover the loads' latency; wave 0 adds the other waves' sums in wave order and stores: still ONE fixed order per output entry.
+// 16 rows of Y^_i = W^_i X^_i on NBW blocks of 16 columns.  The four waves of the workgroup share the k range (whole trips of U k steps, fxa_wave_k0: U KB of W^ and
+// U NBW KB of X^, which stays in the caches, in flight per wave), so that a row block's sum is a chain of a quarter of the products and the chip holds several waves
+// per SIMD to cover the loads' latency; wave 0 adds the other waves' sums in wave order and stores: still ONE fixed order per output entry.
+// W^ is read with plain loads, not with the non-temporal hint: the blocks are the same bytes at every application and little else is read between two of them, so
+// part of them is still in the last-level cache when the next application comes (the hint kept them out of it).  This rests on ONE class whose blocks (190 MB on the
+// headline) are smaller than that cache (256 MB): blocks larger than it, or several classes applied in turn, would sweep it for nothing and push the chain's vectors
+// out (its small kernels already take 1 .. 4 us longer beside the 190 MB).  Neither was measured; the hint would then have to be chosen by the blocks' size at set-up.
 template <int NBW, int U>
 __device__ __forceinline__ void fxa_prod_rows(const fxa_irrep &I, int ob, int nb0, const double *__restrict__ Wh, const double *__restrict__ Xh, double *__restrict__ Yh, int lane, int wave,
                                               double (*red)[16 * 64])
@@ -82,11 +84,11 @@ __device__ __forceinline__ void fxa_prod_rows(const fxa_irrep &I, int ob, int nb
   dbl4 acc[NBW];
 #pragma unroll
   for (int j = 0; j < NBW; j++) acc[j] = dbl4{0.0, 0.0, 0.0, 0.0};
-  const int ntrip = I.nks / U, ks1 = U * (ntrip * (wave + 1) / FXA_WAVES);
-  for (int ks = U * (ntrip * wave / FXA_WAVES); ks < ks1; ks += U) {
+  const int ks1 = fxa_wave_k0(I.nks, U, wave + 1);
+  for (int ks = fxa_wave_k0(I.nks, U, wave); ks < ks1; ks += U) {
     dbl2 a[U], b[U][NBW];
 #pragma unroll
-    for (int u = 0; u < U; u++) a[u] = __builtin_nontemporal_load(w + (long long)(ks + u) * 64);
+    for (int u = 0; u < U; u++) a[u] = w[(long long)(ks + u) * 64];
 #pragma unroll
     for (int u = 0; u < U; u++)
 #pragma unroll
@@ -130,10 +132,10 @@ __global__ __launch_bounds__(64 * FXA_WAVES) void k_fxa_prod(const int *__restri
   const fxa_irrep I = ir[__builtin_amdgcn_readfirstlane(it[0])];
   const int  ob = __builtin_amdgcn_readfirstlane(it[1]), nb0 = __builtin_amdgcn_readfirstlane(it[2]), nbw = __builtin_amdgcn_readfirstlane(it[3]);
   switch (nbw) {
-  case 1: fxa_prod_rows<1, FXA_KU>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
-  case 2: fxa_prod_rows<2, FXA_KU>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
-  case 3: fxa_prod_rows<3, FXA_KU / 2>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
-  default: fxa_prod_rows<4, FXA_KU / 2>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
+  case 1: fxa_prod_rows<1, fxa_trip_steps(1)>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
+  case 2: fxa_prod_rows<2, fxa_trip_steps(2)>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
+  case 3: fxa_prod_rows<3, fxa_trip_steps(3)>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
+  default: fxa_prod_rows<4, fxa_trip_steps(4)>(I, ob, nb0, Wh, Xh, Yh, lane, wave, red); break;
   }
 }
 

@@ -21,6 +21,13 @@ struct fxa_irrep {
   int       d, m, nks, nob, nbt, ldy; // k steps of 8 (whole unrolls), blocks of 16 output rows, blocks of 16 columns, row length of Y^_i
   long long woff, hoff, yoff;         // offsets in Wh / Xh / Yh
 };
+// k_fxa_prod: the four waves of a workgroup share an item's nks k steps in whole trips of U steps (FXA_KU for items of 1 or 2 blocks of columns, half of it for 3 or 4);
+// wave w takes the steps [fxa_wave_k0(nks, U, w), fxa_wave_k0(nks, U, w + 1)).  The kernel and pmh_fexplicit_orbit_adapted_info both go by these two.
+#define FXA_WAVES 4 // waves per workgroup of k_fxa_prod: they share the k range of ONE block of 16 output rows
+#define FXA_KU 8    // k steps per trip of the narrow items: nks is a multiple of it
+__host__ __device__ constexpr int fxa_trip_steps(int nbw) { return nbw <= 2 ? FXA_KU : FXA_KU / 2; }
+__host__ __device__ inline int fxa_wave_k0(int nks, int U, int wave) { return U * ((nks / U) * wave / FXA_WAVES); }
+
 struct fxa_class {
   int        norb = 0, NC = 0, nitems = 0, nc = 0;
   fxa_irrep  ir[10];
@@ -30,6 +37,7 @@ struct fxa_class {
   int       *d_osize = nullptr, *d_tbase = nullptr, *d_opos = nullptr, *d_rowinfo = nullptr, *d_items = nullptr;
   char      *d_tmask = nullptr;
   double     flops = 0.0, flops_issued = 0.0, bytes = 0.0;
+  int        items_of_width[10][4] = {}; // per irrep the work items of 1 .. 4 blocks of columns (pmh_fexplicit_orbit_adapted_info)
 };
 
 struct fxs_class {

@@ -462,6 +462,17 @@ class MatExplicitDual:
         check(self.ctx.L.pmh_fexplicit_orbit_plan_info(self.h, int(cls), info.ctypes.data_as(C.c_void_p)))
         return dict(zip(self.ORBIT_PLAN_FIELDS, (int(v) for v in info)))
 
+    def orbit_adapted_info(self, cls=0):
+        """"class_orbit", a class on the symmetry-adapted form: what the block products (k_fxa_prod) run (pmh_fexplicit_orbit_adapted_info), one dict per irrep: d, m,
+        nks (k steps of 8 columns), nob / nbt (blocks of 16 output rows / of 16 columns), items (work items of 1, 2, 3, 4 blocks of columns), trips (of waves 0 .. 3
+        on an item of 1 or 2 blocks, steps_per_trip k steps each) and trips_wide / steps_per_trip_wide (on an item of 3 or 4)."""
+        info = np.zeros(200, dtype=np.int64)
+        check(self.ctx.L.pmh_fexplicit_orbit_adapted_info(self.h, int(cls), info.ctypes.data_as(C.c_void_p)))
+        out = []
+        for v in info.reshape(10, 20).tolist():
+            out.append(dict(d=v[0], m=v[1], nks=v[2], nob=v[3], nbt=v[4], items=v[5:9], trips=v[9:13], trips_wide=v[13:17], steps_per_trip=v[17], steps_per_trip_wide=v[18]))
+        return out
+
     def assemble_stats(self):
         n, t = C.c_longlong(), C.c_double()
         check(self.ctx.L.pmh_fexplicit_assemble_stats(self.h, C.byref(n), C.byref(t)))
