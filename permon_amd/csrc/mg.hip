@@ -16,31 +16,8 @@
 #include <cstdio>
 
 #include "pmh_internal.h"
-#include "mg_internal.h"
-
-// position of the LAST entry (row i, column i) of a CSR row, -1 if there is none: 8 lanes walk the row together (one thread per row read 81 entries one after the
-// other: 2 ms for the 2 M rows of configs[2])
-static __device__ __forceinline__ int mg_diag_pos8(const int *__restrict__ rowptr, const int *__restrict__ col, int i, int lane8)
-{
-  int best = -1;
-  for (int k = rowptr[i] + lane8; k < rowptr[i + 1]; k += 8)
-    if (col[k] == i) best = k;
-  best = max(best, __shfl_xor(best, 4, 8));
-  best = max(best, __shfl_xor(best, 2, 8));
-  best = max(best, __shfl_xor(best, 1, 8));
-  return best;
-}
-template <typename TV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_mg_dinv(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val, TV *__restrict__ dinv)
-{
-  const int lane8 = threadIdx.x & 7;
-  for (int i0 = (blockIdx.x * PMH_BLOCK + threadIdx.x) >> 3; i0 < ((n + 7) & ~7); i0 += (gridDim.x * PMH_BLOCK) >> 3) { // uniform trip count within every group of 8 lanes
-    const int    i = min(i0, n - 1);
-    const int    k = mg_diag_pos8(rowptr, col, i, lane8);
-    const double d = (k >= 0) ? val[k] : 0.0;
-    if (lane8 == 0 && i0 < n) dinv[i] = (TV)((d != 0.0) ? 1.0 / d : 1.0);
-  }
-}
+#include "diag_inv.h"
+#include "mg_transfer.h"
 
 // first Chebyshev step from a zero guess: r = D^-1 b, d = r/theta, x = d
 template <typename TV>
@@ -94,152 +71,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_cheb_step(int n, const int *__res
   }
 }
 
-// restriction b_c = R t with R = P' as CSR (<= 27 entries per row): 8 lanes per coarse row, shuffle-tree sum (fixed order).
-// dinv_c != NULL: the first smoothing direction of the coarse level, d_c = D_c^-1 b_c / theta_c, is written on the way
-// (saves the k_cheb_d0 launch of every smoothed coarse level: these levels are launch-latency bound).
-template <typename TV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_mg_restrict(int nc, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col, const TV *__restrict__ val, const TV *__restrict__ t, TV *__restrict__ bc,
-                                                         const TV *__restrict__ dinv_c, TV itheta_c, TV *__restrict__ d_c)
-{
-  const int hlt  = halt ? *halt : 0; // fetched together with the first row pointers: one round trip less on a latency-bound launch
-  const int lane = threadIdx.x & 7;
-  bool      first = true;
-  for (int i0 = blockIdx.x * (PMH_BLOCK / 8); i0 < nc; i0 += gridDim.x * (PMH_BLOCK / 8)) { // uniform trip count per workgroup
-    const int i = i0 + (threadIdx.x >> 3);
-    TV        s = (TV)0;
-    const int k0 = (i < nc) ? rowptr[i] : 0, k1 = (i < nc) ? rowptr[i + 1] : 0;
-    if (first) {
-      if (hlt) return;
-      first = false;
-    }
-    for (int k = k0 + lane; k < k1; k += 8) s += (TV)val[k] * t[col[k]];
-    s += __shfl_down(s, 4, 8);
-    s += __shfl_down(s, 2, 8);
-    s += __shfl_down(s, 1, 8);
-    if (i < nc && lane == 0) {
-      bc[i] = s;
-      if (dinv_c) d_c[i] = dinv_c[i] * s * itheta_c;
-    }
-  }
-}
-
-// coarse-grid correction x -= P x_c (<= 8 entries per row of P), one thread per fine row
-template <typename TV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_mg_prolong_sub(int n, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col, const TV *__restrict__ val, const TV *__restrict__ xc, TV *__restrict__ x)
-{
-  const int hlt   = halt ? *halt : 0; // as in k_mg_restrict
-  bool      first = true;
-  for (int i = blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += gridDim.x * PMH_BLOCK) {
-    TV        s  = (TV)0;
-    const int k0 = rowptr[i], k1 = rowptr[i + 1];
-    const TV  xi = x[i];
-    if (first) {
-      if (hlt) return;
-      first = false;
-    }
-    for (int k = k0; k < k1; k++) s += (TV)val[k] * xc[col[k]];
-    x[i] = xi - s;
-  }
-  if (first && hlt) return;
-}
-
-// The same two transfers for prolongations with LONG rows (smoothed aggregation, mgsa.hip: ~ 30 entries per row of P, hundreds per row of P'): a wavefront per coarse
-// row / 8 lanes per fine row, sums by butterfly steps in a fixed order.  Chosen at pmh_mg_create by the average row length of P.
-template <typename TV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_mg_restrict_w(int nc, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col, const TV *__restrict__ val, const TV *__restrict__ t, TV *__restrict__ bc,
-                                                           const TV *__restrict__ dinv_c, TV itheta_c, TV *__restrict__ d_c)
-{
-  if (halt && *halt) return;
-  const int lane = threadIdx.x & 63;
-  for (int i = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6); i < nc; i += gridDim.x * (PMH_BLOCK / 64)) {
-    TV s = (TV)0;
-    for (int k = rowptr[i] + lane; k < rowptr[i + 1]; k += 64) s += (TV)val[k] * t[col[k]];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) {
-      bc[i] = s;
-      if (dinv_c) d_c[i] = dinv_c[i] * s * itheta_c;
-    }
-  }
-}
-template <typename TV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_mg_prolong_sub8(int n, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col, const TV *__restrict__ val, const TV *__restrict__ xc, TV *__restrict__ x)
-{
-  if (halt && *halt) return;
-  const int lane = threadIdx.x & 7;
-  for (int i0 = blockIdx.x * (PMH_BLOCK / 8); i0 < n; i0 += gridDim.x * (PMH_BLOCK / 8)) { // uniform trip count per workgroup
-    const int i = i0 + (threadIdx.x >> 3);
-    TV        s = (TV)0;
-    if (i < n)
-      for (int k = rowptr[i] + lane; k < rowptr[i + 1]; k += 8) s += (TV)val[k] * xc[col[k]];
-    s += __shfl_xor(s, 4, 8);
-    s += __shfl_xor(s, 2, 8);
-    s += __shfl_xor(s, 1, 8);
-    if (i < n && lane == 0) x[i] -= s;
-  }
-}
-
-// P = P_node (x) I_3 (nodal prolongation of a 3-dof-per-node problem, e.g. trilinear interpolation of elasticity blocks): one
-// node-level CSR entry serves the three components, so the transfer operators move a third of the index / value bytes.
-// Detected at pmh_mg_create from the entries of P; any other P runs on the scalar kernels above.
-template <typename TV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_mg_restrict3(int ncn, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col, const TV *__restrict__ val, const TV *__restrict__ t, TV *__restrict__ bc,
-                                                          const TV *__restrict__ dinv_c, TV itheta_c, TV *__restrict__ d_c)
-{
-  const int hlt  = halt ? *halt : 0;
-  const int lane = threadIdx.x & 7;
-  bool      first = true;
-  for (int i0 = blockIdx.x * (PMH_BLOCK / 8); i0 < ncn; i0 += gridDim.x * (PMH_BLOCK / 8)) { // uniform trip count per workgroup
-    const int i  = i0 + (threadIdx.x >> 3);
-    TV        s0 = (TV)0, s1 = (TV)0, s2 = (TV)0;
-    const int k0 = (i < ncn) ? rowptr[i] : 0, k1 = (i < ncn) ? rowptr[i + 1] : 0;
-    if (first) {
-      if (hlt) return;
-      first = false;
-    }
-    for (int k = k0 + lane; k < k1; k += 8) {
-      const TV  w = val[k];
-      const TV *p = t + 3 * (size_t)col[k];
-      s0 += w * p[0], s1 += w * p[1], s2 += w * p[2];
-    }
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) s0 += __shfl_down(s0, o, 8), s1 += __shfl_down(s1, o, 8), s2 += __shfl_down(s2, o, 8);
-    if (i < ncn && lane == 0) {
-      TV *o = bc + 3 * (size_t)i;
-      o[0] = s0, o[1] = s1, o[2] = s2;
-      if (dinv_c) {
-        const TV *di = dinv_c + 3 * (size_t)i;
-        TV       *dd = d_c + 3 * (size_t)i;
-        dd[0] = di[0] * s0 * itheta_c, dd[1] = di[1] * s1 * itheta_c, dd[2] = di[2] * s2 * itheta_c;
-      }
-    }
-  }
-}
-
-template <typename TV>
-__global__ __launch_bounds__(PMH_BLOCK) void k_mg_prolong_sub3(int nn, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col, const TV *__restrict__ val, const TV *__restrict__ xc, TV *__restrict__ x)
-{
-  const int hlt   = halt ? *halt : 0;
-  bool      first = true;
-  for (int i = blockIdx.x * PMH_BLOCK + threadIdx.x; i < nn; i += gridDim.x * PMH_BLOCK) {
-    const int k0 = rowptr[i], k1 = rowptr[i + 1];
-    TV       *xi = x + 3 * (size_t)i;
-    const TV  a0 = xi[0], a1 = xi[1], a2 = xi[2];
-    if (first) {
-      if (hlt) return;
-      first = false;
-    }
-    TV s0 = (TV)0, s1 = (TV)0, s2 = (TV)0;
-    for (int k = k0; k < k1; k++) {
-      const TV  w = val[k];
-      const TV *p = xc + 3 * (size_t)col[k];
-      s0 += w * p[0], s1 += w * p[1], s2 += w * p[2];
-    }
-    xi[0] = a0 - s0, xi[1] = a1 - s1, xi[2] = a2 - s2;
-  }
-  if (first && hlt) return;
-}
-
 // coarsest level: x_b = pinv_b b_b, one wavefront per row, lanes stride the row of the dense block (fixed order).
 // TP = storage type of the pseudo-inverse: TV, or _Float16 (PMH_MG_FP16: entries / scale, fp32 arithmetic) -- with one or two
 // blocks per GPU the hierarchy stops at a ~5000-dof level whose dense solve is a pure HBM stream (2 B per entry).
@@ -250,12 +81,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_mg_coarse(int nb, int n, const in
   const int lane = threadIdx.x & 63;
   const int row  = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
   if (row >= n) return;
-  int lo = 0, hi = nb; // block of this row: rs[lo] <= row < rs[lo+1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (rs[mid] <= row) lo = mid;
-    else hi = mid;
-  }
+  const int lo = mg_coarse_block(rs, nb, row);
   const int r0 = rs[lo], m = rs[lo + 1] - r0;
   const TP *a  = pinv + ofs[lo] + (size_t)(row - r0) * m;
   const TV *bb = b + r0;
@@ -279,12 +105,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_mg_convert(int n, const int *__re
 {
   if (halt && *halt) return;
   for (int i = blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += gridDim.x * PMH_BLOCK) b[i] = (TB)a[i];
-}
-
-static inline dim3 mg_grid(int n)
-{
-  long long g = ((long long)n + PMH_BLOCK - 1) / PMH_BLOCK;
-  return dim3((unsigned)(g < 1 ? 1 : (g > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : g)));
 }
 
 // y = A_l x (NONE) or A_l x - y1 (SUB)
@@ -327,17 +147,9 @@ static int mg_smooth(pmh_mg mg, int l, const TV *b, TV *x, bool zero)
   return PMH_SUCCESS;
 }
 
-template <typename TV> static int bsr_epi_launch(pmh_bsr3 B, const TV *x, TV *y, int epi, const pmh_bsr3_epi<TV> &e, const int *halt);
-template <> int bsr_epi_launch<double>(pmh_bsr3 B, const double *x, double *y, int epi, const pmh_bsr3_epi<double> &e, const int *halt) { return pmh_bsr3_spmv_epi_f64(B, x, y, epi, e, halt); }
-template <> int bsr_epi_launch<float>(pmh_bsr3 B, const float *x, float *y, int epi, const pmh_bsr3_epi<float> &e, const int *halt) { return pmh_bsr3_spmv_epi_f32(B, x, y, epi, e, halt); }
-
 template <typename TV> static int mg_cycle(pmh_mg mg, int l, const TV *b, TV *x, const double *b64 = nullptr, double *z64 = nullptr, bool d0_ready = false);
 
-// does level l run mg_level_fused (its first smoothing direction can then be produced by the kernel that makes its b)?
-static inline bool mg_fused_level(pmh_mg mg, int l) { return l < mg->nlevels - 1 && mg->fused && mg->L[l].Ab; }
-
-// which pair of transfer kernels level l launches (pmh_mg_test_info reports the same number): the node-level copies exist (both or none) where P = P_node (x) I_3
-enum { MG_TRANSFER_NONE = 0, MG_TRANSFER_NODAL = 1, MG_TRANSFER_SHORT = 2, MG_TRANSFER_LONG = 3 };
+// which pair of transfer kernels level l launches (pmh_mg_test_info reports the same number)
 static inline int mg_transfer_kind(pmh_mg mg, int l)
 {
   const mg_level &Lv = mg->L[l];
@@ -346,77 +158,31 @@ static inline int mg_transfer_kind(pmh_mg mg, int l)
   return Lv.long_rows ? MG_TRANSFER_LONG : MG_TRANSFER_SHORT;
 }
 
-// b_c = P' t (+ the coarse level's d0) and x -= P x_c: node-level kernels when P = P_node (x) I_3, scalar CSR kernels otherwise
-template <typename TV>
-static void mg_restrict(pmh_mg mg, int l, const TV *t, bool with_d0)
-{
-  mg_level   &Lv = mg->L[l], &Lc = mg->L[l + 1];
-  hipStream_t st = mg->ctx->stream;
-  const TV   *dv = with_d0 ? (const TV *)Lc.dinv : (const TV *)nullptr;
-  const TV    it = with_d0 ? (TV)(1.0 / Lc.theta) : (TV)0;
-  TV         *dc = with_d0 ? (TV *)Lc.d : (TV *)nullptr;
-  const int   kind = mg_transfer_kind(mg, l);
-  if (kind == MG_TRANSFER_NODAL) {
-    const int ncn = Lc.n / 3;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_restrict3<TV>), mg_grid(8 * ncn), dim3(PMH_BLOCK), 0, st, ncn, mg->halt, (const int *)Lv.rn_rowptr, (const int *)Lv.rn_col, (const TV *)Lv.rn_val, t, (TV *)Lc.b, dv, it, dc);
-  } else if (kind == MG_TRANSFER_LONG) {
-    pmh_csr R = Lv.P->transpose;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_restrict_w<TV>), mg_grid(64LL * Lc.n > 0x7fffffff ? 0x7fffffff : 64 * Lc.n), dim3(PMH_BLOCK), 0, st, Lc.n, mg->halt, (const int *)R->d_rowptr, (const int *)R->d_col, (const TV *)Lv.rv, t,
-                       (TV *)Lc.b, dv, it, dc);
-  } else {
-    pmh_csr R = Lv.P->transpose;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_restrict<TV>), mg_grid(8 * (long long)Lc.n > 0x7fffffff ? 0x7fffffff : 8 * Lc.n), dim3(PMH_BLOCK), 0, st, Lc.n, mg->halt, (const int *)R->d_rowptr, (const int *)R->d_col, (const TV *)Lv.rv, t,
-                       (TV *)Lc.b, dv, it, dc);
+// the one-column form of mg_fused_level (mg_internal.h): level operators as 3 x 3 blocks (bsr.hip), the level's vectors in the cycle's precision
+template <typename TV> struct mg_form1 {
+  typedef TV T;
+  pmh_mg     mg;
+  mg_vecs<TV> vecs(int l) const
+  {
+    const mg_level &Lv = mg->L[l];
+    return {(TV *)Lv.x, (TV *)Lv.b, (TV *)Lv.r, (TV *)Lv.d, (TV *)Lv.t, (TV *)Lv.xa};
   }
-}
-
-template <typename TV>
-static void mg_prolong_sub(pmh_mg mg, int l, TV *x)
-{
-  mg_level   &Lv = mg->L[l], &Lc = mg->L[l + 1];
-  hipStream_t st = mg->ctx->stream;
-  const int   kind = mg_transfer_kind(mg, l);
-  if (kind == MG_TRANSFER_NODAL)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_prolong_sub3<TV>), mg_grid(Lv.n / 3), dim3(PMH_BLOCK), 0, st, Lv.n / 3, mg->halt, (const int *)Lv.pn_rowptr, (const int *)Lv.pn_col, (const TV *)Lv.pn_val, (const TV *)Lc.x, x);
-  else if (kind == MG_TRANSFER_LONG)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_prolong_sub8<TV>), mg_grid(8LL * Lv.n > 0x7fffffff ? 0x7fffffff : 8 * Lv.n), dim3(PMH_BLOCK), 0, st, Lv.n, mg->halt, (const int *)Lv.P->d_rowptr, (const int *)Lv.P->d_col, (const TV *)Lv.pv, (const TV *)Lc.x, x);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_prolong_sub<TV>), mg_grid(Lv.n), dim3(PMH_BLOCK), 0, st, Lv.n, mg->halt, (const int *)Lv.P->d_rowptr, (const int *)Lv.P->d_col, (const TV *)Lv.pv, (const TV *)Lc.x, x);
-}
-
-// One smoothed level with the degree-2 Chebyshev steps finished inside the operator kernel (7 launches instead of 10):
-//   d0 = D^-1 b/theta | xa = (1+c1) d0 + c2 D^-1 (b - A d0) | t = A xa - b | b_c = P't | ... | xa -= P x_c |
-//   r, d, x = xa + d from A xa | x += c1 d + c2 (r - D^-1 A d)
-// b64 / z64: fp64 input / output of the fp32 cycle's fine level (the conversions ride on the first and last kernel).
-template <typename TV>
-static int mg_level_fused(pmh_mg mg, int l, const TV *b, TV *x, const double *b64, double *z64, bool d0_ready)
-{
-  mg_level   &Lv = mg->L[l], &Lc = mg->L[l + 1];
-  hipStream_t st = mg->ctx->stream;
-  const dim3  g = mg_grid(Lv.n), blk(PMH_BLOCK);
-  TV         *r = (TV *)Lv.r, *d = (TV *)Lv.d, *t = (TV *)Lv.t, *xa = (TV *)Lv.xa;
-  const TV   *dinv = (const TV *)Lv.dinv;
-  const TV    itheta = (TV)(1.0 / Lv.theta), c1 = (TV)Lv.c1[1], c2 = (TV)Lv.c2[1];
-  if (d0_ready) { // d (and the cycle-precision copy of b) were written by the producer of b
-  } else if (b64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cheb_d0<TV, double>), g, blk, 0, st, Lv.n, mg->halt, dinv, b64, itheta, d, (TV *)b);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cheb_d0<TV, TV>), g, blk, 0, st, Lv.n, mg->halt, dinv, b, itheta, d, (TV *)nullptr);
-  pmh_bsr3_epi<TV> e;
-  memset(&e, 0, sizeof(e));
-  e.y1 = b, e.dinv = dinv, e.r = r, e.d = d;
-  e.c0 = (TV)1 + c1, e.c1 = c1, e.c2 = c2;
-  if (l == 0) mg->fine_spmv += 4;
-  PMH_CHK(bsr_epi_launch<TV>(Lv.Ab, d, xa, PMH_BSR_EPI_PRE, e, mg->halt));
-  PMH_CHK(bsr_epi_launch<TV>(Lv.Ab, xa, t, PMH_EPI_SUB, e, mg->halt));
-  const bool cf = mg_fused_level(mg, l + 1); // the coarse level's d0 rides on the restriction
-  mg_restrict<TV>(mg, l, (const TV *)t, cf);
-  PMH_CHK(mg_cycle<TV>(mg, l + 1, (const TV *)Lc.b, (TV *)Lc.x, nullptr, nullptr, cf));
-  mg_prolong_sub<TV>(mg, l, xa);
-  PMH_HIP(hipGetLastError());
-  e.c0 = itheta;
-  PMH_CHK(bsr_epi_launch<TV>(Lv.Ab, xa, x, PMH_BSR_EPI_POST1, e, mg->halt));
-  e.z64 = z64;
-  return bsr_epi_launch<TV>(Lv.Ab, d, x, PMH_BSR_EPI_POST2, e, mg->halt);
-}
+  void d0(int l, const TV *b, const double *b64, const TV *dinv, TV itheta, TV *d) const
+  {
+    const int n = mg->L[l].n;
+    if (b64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cheb_d0<TV, double>), mg_grid(n), dim3(PMH_BLOCK), 0, mg->ctx->stream, n, mg->halt, dinv, b64, itheta, d, (TV *)b);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cheb_d0<TV, TV>), mg_grid(n), dim3(PMH_BLOCK), 0, mg->ctx->stream, n, mg->halt, dinv, b, itheta, d, (TV *)nullptr);
+  }
+  int op(int l, const TV *x, TV *y, int epi, const pmh_bsr3_epi<TV> &e) const
+  {
+    if (l == 0) mg->fine_spmv++;
+    if constexpr (sizeof(TV) == 8) return pmh_bsr3_spmv_epi_f64(mg->L[l].Ab, x, y, epi, e, mg->halt);
+    else return pmh_bsr3_spmv_epi_f32(mg->L[l].Ab, x, y, epi, e, mg->halt);
+  }
+  int restrict_to(int l, const TV *t, TV *bc, TV *dc) const { return mg_restrict<TV, 1>(mg, l, mg_transfer_kind(mg, l), 1, mg->halt, t, bc, dc); }
+  int prolong_sub(int l, const TV *xc, TV *x) const { return mg_prolong_sub<TV, 1>(mg, l, mg_transfer_kind(mg, l), 1, mg->halt, xc, x); }
+  int descend(int l, const TV *b, TV *x, bool d0_ready) const { return mg_cycle<TV>(mg, l, b, x, nullptr, nullptr, d0_ready); }
+};
 
 template <typename TV>
 static int mg_cycle(pmh_mg mg, int l, const TV *b, TV *x, const double *b64, double *z64, bool d0_ready)
@@ -424,7 +190,10 @@ static int mg_cycle(pmh_mg mg, int l, const TV *b, TV *x, const double *b64, dou
   mg_level   &Lv = mg->L[l];
   hipStream_t st = mg->ctx->stream;
   const dim3  blk(PMH_BLOCK);
-  if (mg_fused_level(mg, l)) return mg_level_fused<TV>(mg, l, b, x, b64, z64, d0_ready);
+  if (mg_is_fused_level(mg, l)) {
+    mg_form1<TV> f{mg};
+    return mg_fused_level(f, l, b, x, b64, z64, d0_ready);
+  }
   if (l == mg->nlevels - 1) {
     if (mg->cp_half) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_coarse<TV, _Float16>), dim3((Lv.n + 3) / 4), blk, 0, st, mg->nb_coarse, Lv.n, mg->halt, (const int *)mg->d_crs, (const long long *)mg->d_cofs, (const _Float16 *)mg->d_cpinv, (TV)mg->cp_scale, b, x);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_coarse<TV, TV>), dim3((Lv.n + 3) / 4), blk, 0, st, mg->nb_coarse, Lv.n, mg->halt, (const int *)mg->d_crs, (const long long *)mg->d_cofs, (const TV *)mg->d_cpinv, (TV)1, b, x);
@@ -435,9 +204,9 @@ static int mg_cycle(pmh_mg mg, int l, const TV *b, TV *x, const double *b64, dou
   PMH_CHK(mg_smooth<TV>(mg, l, b, x, true));
   // t = A x - b; b_{l+1} = P' t = -P'(b - A x); the coarse solve is linear, so the sign is undone by subtracting P x_{l+1}
   PMH_CHK(mg_spmv(mg, l, x, Lv.t, PMH_EPI_SUB, b));
-  mg_restrict<TV>(mg, l, (const TV *)Lv.t, false);
+  PMH_CHK((mg_restrict<TV, 1>(mg, l, mg_transfer_kind(mg, l), 1, mg->halt, (const TV *)Lv.t, (TV *)Lc.b, (TV *)nullptr)));
   PMH_CHK(mg_cycle<TV>(mg, l + 1, (const TV *)Lc.b, (TV *)Lc.x));
-  mg_prolong_sub<TV>(mg, l, x);
+  PMH_CHK((mg_prolong_sub<TV, 1>(mg, l, mg_transfer_kind(mg, l), 1, mg->halt, (const TV *)Lc.x, x)));
   PMH_HIP(hipGetLastError());
   return mg_smooth<TV>(mg, l, b, x, false);
 }
@@ -448,7 +217,7 @@ static int mg_apply_body(pmh_mg mg, const double *b, double *x, const int *halt,
 // (d0 = D^-1 b / theta in fp32, plus the fp32 copy of b): slots and constants for it; returns 0 if the cycle has no such slot.
 int pmh_mg_fine_d0_slots(pmh_mg mg, const float **dinv, float *itheta, float **d0, float **b32)
 {
-  if (!(mg->is_float && mg->fused && mg->nlevels > 1 && mg_fused_level(mg, 0))) return 0;
+  if (!(mg->is_float && mg->fused && mg->nlevels > 1 && mg_is_fused_level(mg, 0))) return 0;
   mg_level &L0 = mg->L[0];
   *dinv = (const float *)L0.dinv, *itheta = (float)(1.0 / L0.theta), *d0 = (float *)L0.d, *b32 = (float *)L0.b;
   return 1;
@@ -646,8 +415,8 @@ extern "C" int pmh_mg_create(pmh_ctx ctx, int nlevels, const pmh_csr *A, const p
       PMH_CHK(pmh_malloc(ctx, nbytes, &Lv.t));
       PMH_CHK(pmh_malloc(ctx, nbytes, &Lv.xa));
       if (Lv.n > 0) {
-        if (fl) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_dinv<float>), mg_grid((int)std::min<long long>(8LL * Lv.n, 0x7fffff00LL)), dim3(PMH_BLOCK), 0, ctx->stream, Lv.n, (const int *)A[l]->d_rowptr, (const int *)A[l]->d_col, (const double *)A[l]->d_val, (float *)Lv.dinv);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_dinv<double>), mg_grid((int)std::min<long long>(8LL * Lv.n, 0x7fffff00LL)), dim3(PMH_BLOCK), 0, ctx->stream, Lv.n, (const int *)A[l]->d_rowptr, (const int *)A[l]->d_col, (const double *)A[l]->d_val, (double *)Lv.dinv);
+        if (fl) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extract_dinv<float>), pmh_diag_inv_grid(Lv.n), dim3(PMH_BLOCK), 0, ctx->stream, Lv.n, (const int *)A[l]->d_rowptr, (const int *)A[l]->d_col, (const double *)A[l]->d_val, 1, (float *)Lv.dinv);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extract_dinv<double>), pmh_diag_inv_grid(Lv.n), dim3(PMH_BLOCK), 0, ctx->stream, Lv.n, (const int *)A[l]->d_rowptr, (const int *)A[l]->d_col, (const double *)A[l]->d_val, 1, (double *)Lv.dinv);
         PMH_HIP(hipGetLastError());
       }
       stage("value conversion, diagonal, work vectors", l);
@@ -773,7 +542,7 @@ extern "C" int pmh_mg_test_info(pmh_mg mg, int level, long long info[10], double
   const mg_level &Lv = mg->L[level];
   const bool      smoothed = level < mg->nlevels - 1;
   info[0] = Lv.n, info[1] = (smoothed && Lv.Ab) ? 1 : 0, info[2] = (smoothed && Lv.Ab) ? Lv.Ab->storage : -1, info[3] = mg_transfer_kind(mg, level);
-  info[4] = mg_fused_level(mg, level) ? 1 : 0, info[5] = mg->is_float ? 1 : 0, info[6] = mg->cp_half, info[7] = mg->coarse_m16, info[8] = mg->nb_coarse;
+  info[4] = mg_is_fused_level(mg, level) ? 1 : 0, info[5] = mg->is_float ? 1 : 0, info[6] = mg->cp_half, info[7] = mg->coarse_m16, info[8] = mg->nb_coarse;
   info[9] = (smoothed && Lv.Ab) ? Lv.Ab->nrep : 1;
   if (cp_scale) *cp_scale = mg->cp_scale;
   return PMH_SUCCESS;

@@ -2,17 +2,17 @@
 //
 // The hierarchy is the one pmh_mg holds (level operators as CSR, node-wise transfer operators, Jacobi scaling, Chebyshev constants, dense coarse
 // pseudo-inverses): nothing is set up twice but the ELL copies of the level operators (built on the device, mv.hip) and the work multivectors.  The cycle is
-// the fused form of mg.hip (mg_level_fused): degree-2 Chebyshev/Jacobi smoothing finished inside the operator kernel, fp32 vectors, level operators in the
+// the fused form of mg.hip (mg_fused_level, mg_internal.h: one driver for both): degree-2 Chebyshev/Jacobi smoothing finished inside the operator kernel, fp32 vectors, level operators in the
 // precision pmh_mg keeps them in (fp16 on the finest levels by default).  Per smoothed level: d0 | PRE | SUB | restrict (+ the coarse d0) | ... |
 // prolong-subtract | POST1 | POST2.  The transfers are node-wise where P = P_node (x) I_3 (the box hierarchies) and scalar CSR otherwise (smoothed aggregation).  A
 // hierarchy of another shape (fp64 cycle, other degree, a level without 3 x 3 blocks) is refused (PMH_EPI_UNSUPPORTED, no error recorded): the caller keeps the
 // one-column solver.
-#include "mg_internal.h"
+#include "mg_transfer.h"
 #include "mv_internal.h"
 
 #define MV_R PMH_MV_R
 typedef float mvg_flt4 __attribute__((ext_vector_type(4)));
-static_assert(MV_R == 8, "k_mvg_restrict_s: 8 entry groups x 8 columns per wavefront");
+static_assert(MV_R == 8, "k_mg_restrict<float, 8, 1, 8, 1>: 8 entry groups x 8 columns per wavefront");
 
 struct mg_mv_level {
   pmh_mv_ell E = nullptr;
@@ -52,88 +52,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_mvg_d0(long long nR, const int *_
   }
 }
 
-// b_c = P' t, node-wise P' (<= 27 entries per coarse node), every entry serving the 3 R values of its fine node: lane (coarse node, column r); optionally the
-// coarse level's first smoothing direction d_c = D_c^-1 b_c / theta_c
-__global__ __launch_bounds__(PMH_BLOCK) void k_mvg_restrict(int ncn, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col,
-                        const float *__restrict__ val, const float *__restrict__ t,
-                                                           float *__restrict__ bc, const float *__restrict__ dinv_c, float itheta_c, float *__restrict__ d_c)
-{
-  // 32 lanes per coarse node: 4 entry groups x 8 columns, the groups summed by two butterfly steps (a fixed order).  (Until round 6 one lane per (node, column) walked the up
-  // to 27 entries alone: 14 us per launch on every level of the 43^3 hierarchy -- three of them per cycle, 10 % of an inner-Krylov step.)
-  if (halt && *halt) return;
-  const int lane = threadIdx.x & 31, r = lane % MV_R, g = lane / MV_R;
-  for (int i = blockIdx.x * (PMH_BLOCK / 32) + (threadIdx.x >> 5); i < ncn; i += gridDim.x * (PMH_BLOCK / 32)) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int k = rowptr[i] + g; k < rowptr[i + 1]; k += 4) {
-      const float  w = val[k];
-      const float *p = t + (size_t)3 * col[k] * MV_R + r;
-      s0 += w * p[0], s1 += w * p[MV_R], s2 += w * p[2 * MV_R];
-    }
-#pragma unroll
-    for (int o = 8; o < 32; o <<= 1) s0 += __shfl_xor(s0, o, 32), s1 += __shfl_xor(s1, o, 32), s2 += __shfl_xor(s2, o, 32);
-    if (g == 0) {
-      float *o = bc + (size_t)3 * i * MV_R + r;
-      o[0] = s0, o[MV_R] = s1, o[2 * MV_R] = s2;
-      if (dinv_c) {
-        float *dd = d_c + (size_t)3 * i * MV_R + r;
-        dd[0] = dinv_c[3 * i] * s0 * itheta_c, dd[MV_R] = dinv_c[3 * i + 1] * s1 * itheta_c, dd[2 * MV_R] = dinv_c[3 * i + 2] * s2 * itheta_c;
-      }
-    }
-  }
-}
-
-// x -= P x_c, node-wise P (<= 8 entries per fine node): lane (fine node, column r)
-__global__ __launch_bounds__(PMH_BLOCK) void k_mvg_prolong_sub(int nn, const int *__restrict__ halt, const int *__restrict__ rowptr,
-                        const int *__restrict__ col, const float *__restrict__ val, const float *__restrict__ xc, float *__restrict__ x)
-{
-  if (halt && *halt) return;
-  const int r = threadIdx.x % MV_R;
-  for (int i = blockIdx.x * (PMH_BLOCK / MV_R) + threadIdx.x / MV_R; i < nn; i += gridDim.x * (PMH_BLOCK / MV_R)) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int k = rowptr[i]; k < rowptr[i + 1]; k++) {
-      const float  w = val[k];
-      const float *p = xc + (size_t)3 * col[k] * MV_R + r;
-      s0 += w * p[0], s1 += w * p[MV_R], s2 += w * p[2 * MV_R];
-    }
-    float *xi = x + (size_t)3 * i * MV_R + r;
-    xi[0] -= s0, xi[MV_R] -= s1, xi[2 * MV_R] -= s2;
-  }
-}
-
-// The same two transfers for a prolongation that is NOT node-wise (smoothed aggregation, mgsa.hip: a fine dof interpolates from the m dofs of several aggregates): the scalar
-// CSR of P' / P (values in the cycle's precision), lane (row, column r); the operand of an entry is the R-vector of ONE dof (32 contiguous bytes per 8 lanes).
-__global__ __launch_bounds__(PMH_BLOCK) void k_mvg_restrict_s(int nc, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col,
-                        const float *__restrict__ val, const float *__restrict__ t, float *__restrict__ bc, const float *__restrict__ dinv_c, float itheta_c,
-                        float *__restrict__ d_c)
-{
-  // a row of P' has hundreds of entries (the dofs of an aggregate and of its neighbours' rims): ONE wavefront per coarse row, lane (entry group g, column r), the 8 groups
-  // summed by three butterfly steps (a fixed order) -- one lane per (row, column) walked the row alone: 330 us per launch where the operator products take 55
-  if (halt && *halt) return;
-  const int lane = threadIdx.x & 63, r = lane % MV_R, g = lane / MV_R;
-  for (int i = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6); i < nc; i += gridDim.x * (PMH_BLOCK / 64)) {
-    float s = 0.f;
-    for (int k = rowptr[i] + g; k < rowptr[i + 1]; k += 64 / MV_R) s += val[k] * t[(size_t)col[k] * MV_R + r];
-    s += __shfl_xor(s, 8, 64);
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    if (g == 0) {
-      bc[(size_t)i * MV_R + r] = s;
-      if (dinv_c) d_c[(size_t)i * MV_R + r] = dinv_c[i] * s * itheta_c;
-    }
-  }
-}
-__global__ __launch_bounds__(PMH_BLOCK) void k_mvg_prolong_sub_s(int n, const int *__restrict__ halt, const int *__restrict__ rowptr, const int *__restrict__ col,
-                        const float *__restrict__ val, const float *__restrict__ xc, float *__restrict__ x)
-{
-  if (halt && *halt) return;
-  const int r = threadIdx.x % MV_R;
-  for (int i = blockIdx.x * (PMH_BLOCK / MV_R) + threadIdx.x / MV_R; i < n; i += gridDim.x * (PMH_BLOCK / MV_R)) {
-    float s = 0.f;
-    for (int k = rowptr[i]; k < rowptr[i + 1]; k++) s += val[k] * xc[(size_t)col[k] * MV_R + r];
-    x[(size_t)i * MV_R + r] -= s;
-  }
-}
-
 // coarsest level: X_b = pinv_b B_b for the R columns: one wavefront per row of the dense block, lanes stride the row, R sums per lane
 template <typename TP>
 __global__ __launch_bounds__(PMH_BLOCK) void k_mvg_coarse(int nb, int n, const int *__restrict__ halt, const int *__restrict__ rs,
@@ -144,12 +62,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_mvg_coarse(int nb, int n, const i
   const int lane = threadIdx.x & 63;
   const int row  = blockIdx.x * (PMH_BLOCK / 64) + (threadIdx.x >> 6);
   if (row >= n) return;
-  int lo = 0, hi = nb;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (rs[mid] <= row) lo = mid;
-    else hi = mid;
-  }
+  const int    lo = mg_coarse_block(rs, nb, row);
   const int    r0 = rs[lo], m = rs[lo + 1] - r0;
   const TP    *a  = pinv + ofs[lo] + (size_t)(row - r0) * m;
   const float *bb = b + (size_t)r0 * MV_R;
@@ -195,12 +108,7 @@ template <int MVG_CW, int MVG_CU> __global__ __launch_bounds__(64 * MVG_CW) void
   __shared__ float part[MVG_CW][16][MV_R];
   __shared__ float tr[MVG_CW][MVG_CU][4 * 8 * 8]; // per wavefront and step: the 32 x 8 entries of B, [q][column][k & 7]
   const int        row0 = blockIdx.x * 16;
-  int              lo = 0, hi = nb;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (rs[mid] <= row0) lo = mid;
-    else hi = mid;
-  }
+  const int        lo = mg_coarse_block(rs, nb, row0);
   const int       r0 = rs[lo], m = rs[lo + 1] - r0;
   const int       lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4, jr = i & 7, h = i >> 3;
   const _Float16 *a  = pinv + ofs[lo] + (size_t)(row0 - r0 + i) * m + 8 * q;
@@ -269,12 +177,6 @@ template <int MVG_CW, int MVG_CU> __global__ __launch_bounds__(64 * MVG_CW) void
     for (int w = 1; w < MVG_CW; w++) sum += part[w][rr][cc];
     x[(size_t)(row0 + rr) * MV_R + cc] = sum * scale;
   }
-}
-
-static inline dim3 mvg_grid(long long work_items)
-{
-  long long g = (work_items + PMH_BLOCK - 1) / PMH_BLOCK;
-  return dim3((unsigned)(g < 1 ? 1 : (g > PMH_MAX_VEC_BLOCKS ? PMH_MAX_VEC_BLOCKS : g)));
 }
 
 int pmh_mg_mv_destroy(pmh_mg_mv M)
@@ -366,91 +268,81 @@ int pmh_mg_mv_create(pmh_mg mg, pmh_mg_mv *out, int nrep)
 }
 
 // which transfer kernels level l launches and which coarse solve the last level (pmh_mg_mv_test_info reports the same numbers): the rectangular ELL pair exists both or none
-enum { MVG_TRANSFER_NONE = 0, MVG_TRANSFER_NODAL = 1, MVG_TRANSFER_ELL = 2, MVG_TRANSFER_SCALAR = 3 };
 enum { MVG_COARSE_F32 = 0, MVG_COARSE_F16 = 1, MVG_COARSE_MFMA = 2 };
 static inline int mvg_transfer_kind(pmh_mg_mv M, int l)
 {
-  if (l >= M->mg->nlevels - 1) return MVG_TRANSFER_NONE;
-  if (M->L[l].ER && M->L[l].EP) return MVG_TRANSFER_ELL;
-  return M->mg->L[l].rn_rowptr != nullptr ? MVG_TRANSFER_NODAL : MVG_TRANSFER_SCALAR;
+  if (l >= M->mg->nlevels - 1) return MG_TRANSFER_NONE;
+  if (M->L[l].ER && M->L[l].EP) return MG_TRANSFER_ELL;
+  return M->mg->L[l].rn_rowptr != nullptr ? MG_TRANSFER_NODAL : MG_TRANSFER_SCALAR;
 }
 static inline int mvg_coarse_kind(pmh_mg mg) { return (mg->cp_half && mg->coarse_m16) ? MVG_COARSE_MFMA : (mg->cp_half ? MVG_COARSE_F16 : MVG_COARSE_F32); }
-// the coarse level is a smoothed one: its d0 rides on the restriction
-static inline bool mvg_coarse_d0(pmh_mg mg, int l) { return l + 2 < mg->nlevels; }
+
+static int mvg_cycle(pmh_mg_mv M, int l, const double *b64, double *z64, bool d0_ready, const int *halt);
+
+// the 8-column form of mg_fused_level (mg_internal.h): level operators as ELL copies (mv.hip), fp32 multivectors of the first of nrep congruent blocks
+struct mg_form8 {
+  typedef float T;
+  pmh_mg        mg;
+  pmh_mg_mv     M;
+  const int    *halt;
+  mg_vecs<float> vecs(int l) const
+  {
+    const mg_mv_level &Ml = M->L[l];
+    return {Ml.x, Ml.b, Ml.r, Ml.d, Ml.t, Ml.xa};
+  }
+  void d0(int l, const float *b, const double *b64, const float *dinv, float itheta, float *d) const
+  {
+    const long long nR = (long long)(mg->L[l].n / M->nrep) * MV_R;
+    if (b64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_d0<double>), mg_grid(nR / 4), dim3(PMH_BLOCK), 0, mg->ctx->stream, nR, halt, dinv, b64, itheta, d, (float *)b);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_d0<float>), mg_grid(nR / 4), dim3(PMH_BLOCK), 0, mg->ctx->stream, nR, halt, dinv, b, itheta, d, (float *)nullptr);
+  }
+  int op(int l, const float *x, float *y, int epi, const pmh_mv_epi<float> &e) const { return pmh_mv_spmv_f32(M->L[l].E, x, y, epi, &e, halt); }
+  int restrict_to(int l, const float *t, float *bc, float *dc) const
+  {
+    const int tk = mvg_transfer_kind(M, l);
+    if (tk != MG_TRANSFER_ELL) return mg_restrict<float, MV_R>(mg, l, tk, M->nrep, halt, t, bc, dc);
+    pmh_mv_epi<float> er;
+    memset(&er, 0, sizeof(er));
+    if (dc) er.dinv = (const float *)mg->L[l + 1].dinv, er.d = dc, er.c0 = (float)(1.0 / mg->L[l + 1].theta);
+    return pmh_mv_spmv_f32(M->L[l].ER, t, bc, PMH_MV_EPI_RESTRICT, &er, halt);
+  }
+  int prolong_sub(int l, const float *xc, float *x) const
+  {
+    const int tk = mvg_transfer_kind(M, l);
+    if (tk != MG_TRANSFER_ELL) return mg_prolong_sub<float, MV_R>(mg, l, tk, M->nrep, halt, xc, x);
+    pmh_mv_epi<float> ep;
+    memset(&ep, 0, sizeof(ep));
+    ep.y1 = x;
+    return pmh_mv_spmv_f32(M->L[l].EP, xc, x, PMH_EPI_ADD, &ep, halt); // x += (-P) x_c
+  }
+  int descend(int l, const float *, float *, bool d0_ready) const { return mvg_cycle(M, l, nullptr, nullptr, d0_ready, halt); } // (b and x are the level's own)
+};
 
 static int mvg_cycle(pmh_mg_mv M, int l, const double *b64, double *z64, bool d0_ready, const int *halt)
 {
   pmh_mg       mg = M->mg;
-  mg_level    &Lv = mg->L[l];
   mg_mv_level &Ml = M->L[l];
-  hipStream_t  st = mg->ctx->stream;
-  const dim3   blk(PMH_BLOCK);
-  const int    nrep = M->nrep, n_l = Lv.n / nrep; // (congruent blocks: the first block's share of every level)
-  if (l == mg->nlevels - 1) {
-    const int nbc = mg->nb_coarse / nrep, ck = mvg_coarse_kind(mg);
-    if (ck == MVG_COARSE_MFMA)
-      // (16 wavefronts x 2 steps per stage: 21.4 us on the 5 184-row block; 8 x 3: 23.2, 8 x 6: 26.9, 16 x 3: 25.3, 4 x 6: 26.6)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse_mfma<16, 2>), dim3(n_l / 16), dim3(64 * 16), 0, st, nbc, halt, (const int *)mg->d_crs, (const long long *)mg->d_cofs,
-                         (const _Float16 *)mg->d_cpinv, (float)mg->cp_scale, (const float *)Ml.b, Ml.x);
-    else if (ck == MVG_COARSE_F16)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse<_Float16>), dim3((n_l + 3) / 4), blk, 0, st, nbc, n_l, halt, (const int *)mg->d_crs,
-                         (const long long *)mg->d_cofs, (const _Float16 *)mg->d_cpinv, (float)mg->cp_scale,
-                         (const float *)Ml.b, Ml.x);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse<float>), dim3((n_l + 3) / 4), blk, 0, st, nbc, n_l, halt, (const int *)mg->d_crs,
-                         (const long long *)mg->d_cofs, (const float *)mg->d_cpinv, 1.f, (const float *)Ml.b, Ml.x);
-    PMH_HIP(hipGetLastError());
-    return PMH_SUCCESS;
+  if (l < mg->nlevels - 1) {
+    mg_form8 f{mg, M, halt};
+    return mg_fused_level(f, l, (const float *)Ml.b, Ml.x, b64, z64, d0_ready);
   }
-  mg_level    &Lc = mg->L[l + 1];
-  mg_mv_level &Mc = M->L[l + 1];
-  const long long nR     = (long long)n_l * MV_R;
-  const float    *dinv   = (const float *)Lv.dinv;
-  const float     itheta = (float)(1.0 / Lv.theta), c1 = (float)Lv.c1[1], c2 = (float)Lv.c2[1];
-  if (!d0_ready) {
-    if (b64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_d0<double>), mvg_grid(nR / 4), blk, 0, st, nR, halt, dinv, b64, itheta, Ml.d, Ml.b);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_d0<float>), mvg_grid(nR / 4), blk, 0, st, nR, halt, dinv, (const float *)Ml.b, itheta, Ml.d,
-                            (float *)nullptr);
-  }
-  pmh_mv_epi<float> e;
-  memset(&e, 0, sizeof(e));
-  e.y1 = Ml.b, e.dinv = dinv, e.r = Ml.r, e.d = Ml.d;
-  e.c0 = 1.f + c1, e.c1 = c1, e.c2 = c2;
-  PMH_CHK(pmh_mv_spmv_f32(Ml.E, Ml.d, Ml.xa, PMH_BSR_EPI_PRE, &e, halt));
-  PMH_CHK(pmh_mv_spmv_f32(Ml.E, Ml.xa, Ml.t, PMH_EPI_SUB, &e, halt));
-  const bool cf  = mvg_coarse_d0(mg, l);
-  const int  ncn = Lc.n / 3 / nrep;
-  const int  tk  = mvg_transfer_kind(M, l);
-  if (tk == MVG_TRANSFER_ELL) {
-    pmh_mv_epi<float> er;
-    memset(&er, 0, sizeof(er));
-    if (cf) er.dinv = (const float *)Lc.dinv, er.d = Mc.d, er.c0 = (float)(1.0 / Lc.theta);
-    PMH_CHK(pmh_mv_spmv_f32(Ml.ER, Ml.t, Mc.b, PMH_MV_EPI_RESTRICT, &er, halt));
-  } else if (tk == MVG_TRANSFER_NODAL)
-    hipLaunchKernelGGL(k_mvg_restrict, mvg_grid((long long)ncn * 32), blk, 0, st, ncn, halt, (const int *)Lv.rn_rowptr, (const int *)Lv.rn_col,
-                       (const float *)Lv.rn_val, (const float *)Ml.t, Mc.b,
-                       cf ? (const float *)Lc.dinv : (const float *)nullptr, cf ? (float)(1.0 / Lc.theta) : 0.f, cf ? Mc.d : (float *)nullptr);
+  hipStream_t st = mg->ctx->stream;
+  const dim3  blk(PMH_BLOCK);
+  const int   nrep = M->nrep, n_l = mg->L[l].n / nrep; // (congruent blocks: the first block's share of every level)
+  const int   nbc = mg->nb_coarse / nrep, ck = mvg_coarse_kind(mg);
+  if (ck == MVG_COARSE_MFMA)
+    // (16 wavefronts x 2 steps per stage: 21.4 us on the 5 184-row block; 8 x 3: 23.2, 8 x 6: 26.9, 16 x 3: 25.3, 4 x 6: 26.6)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse_mfma<16, 2>), dim3(n_l / 16), dim3(64 * 16), 0, st, nbc, halt, (const int *)mg->d_crs, (const long long *)mg->d_cofs,
+                       (const _Float16 *)mg->d_cpinv, (float)mg->cp_scale, (const float *)Ml.b, Ml.x);
+  else if (ck == MVG_COARSE_F16)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse<_Float16>), dim3((n_l + 3) / 4), blk, 0, st, nbc, n_l, halt, (const int *)mg->d_crs,
+                       (const long long *)mg->d_cofs, (const _Float16 *)mg->d_cpinv, (float)mg->cp_scale,
+                       (const float *)Ml.b, Ml.x);
   else
-    hipLaunchKernelGGL(k_mvg_restrict_s, mvg_grid((long long)Lc.n * 64), blk, 0, st, Lc.n, halt, (const int *)Lv.P->transpose->d_rowptr, (const int *)Lv.P->transpose->d_col,
-                       (const float *)Lv.rv, (const float *)Ml.t, Mc.b,
-                       cf ? (const float *)Lc.dinv : (const float *)nullptr, cf ? (float)(1.0 / Lc.theta) : 0.f, cf ? Mc.d : (float *)nullptr);
-  PMH_CHK(mvg_cycle(M, l + 1, nullptr, nullptr, cf, halt));
-  if (tk == MVG_TRANSFER_ELL) {
-    pmh_mv_epi<float> ep;
-    memset(&ep, 0, sizeof(ep));
-    ep.y1 = Ml.xa;
-    PMH_CHK(pmh_mv_spmv_f32(Ml.EP, Mc.x, Ml.xa, PMH_EPI_ADD, &ep, halt)); // xa += (-P) x_c
-  } else if (tk == MVG_TRANSFER_NODAL)
-    hipLaunchKernelGGL(k_mvg_prolong_sub, mvg_grid((long long)(n_l / 3) * MV_R), blk, 0, st, n_l / 3, halt, (const int *)Lv.pn_rowptr, (const int *)Lv.pn_col,
-                       (const float *)Lv.pn_val, (const float *)Mc.x, Ml.xa);
-  else
-    hipLaunchKernelGGL(k_mvg_prolong_sub_s, mvg_grid((long long)n_l * MV_R), blk, 0, st, n_l, halt, (const int *)Lv.P->d_rowptr, (const int *)Lv.P->d_col,
-                       (const float *)Lv.pv, (const float *)Mc.x, Ml.xa);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mvg_coarse<float>), dim3((n_l + 3) / 4), blk, 0, st, nbc, n_l, halt, (const int *)mg->d_crs,
+                       (const long long *)mg->d_cofs, (const float *)mg->d_cpinv, 1.f, (const float *)Ml.b, Ml.x);
   PMH_HIP(hipGetLastError());
-  e.c0 = itheta;
-  PMH_CHK(pmh_mv_spmv_f32(Ml.E, Ml.xa, Ml.x, PMH_BSR_EPI_POST1, &e, halt));
-  e.z64 = z64;
-  return pmh_mv_spmv_f32(Ml.E, Ml.d, Ml.x, PMH_BSR_EPI_POST2, &e, halt);
+  return PMH_SUCCESS;
 }
 
 // Z = V(B) for R columns: b, z are fp64 multivectors of n_0 R entries
@@ -485,7 +377,7 @@ extern "C" int pmh_mg_mv_test_info(void *M_, int level, long long info[8])
   pmh_mg     mg   = M->mg;
   const bool last = level == mg->nlevels - 1;
   info[0] = mg->L[level].n / M->nrep, info[1] = M->nrep, info[2] = mvg_transfer_kind(M, level), info[3] = last ? mvg_coarse_kind(mg) : -1;
-  info[4] = last ? -1 : M->L[level].E->storage, info[5] = (!last && mvg_coarse_d0(mg, level)) ? 1 : 0, info[6] = mg->nb_coarse / M->nrep, info[7] = 0;
+  info[4] = last ? -1 : M->L[level].E->storage, info[5] = mg_is_fused_level(mg, level + 1) ? 1 : 0, info[6] = mg->nb_coarse / M->nrep, info[7] = 0;
   return PMH_SUCCESS;
 }
 

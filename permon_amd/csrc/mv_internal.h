@@ -28,12 +28,7 @@ struct pmh_mv_ell_s {
 };
 typedef pmh_mv_ell_s *pmh_mv_ell;
 
-template <typename T> struct pmh_mv_epi {
-  const T *y1, *dinv; // dinv: per ROW (not per column)
-  T       *r, *d;
-  double  *z64;
-  T        c0, c1, c2;
-};
+template <typename T> using pmh_mv_epi = pmh_bsr3_epi<T>; // the epilogue operands of the block kernel (bsr.hip), field for field; dinv is per ROW (not per column)
 
 // *out = NULL without error when A has no regular 3 x 3 block structure (unsorted rows, or more than 2048 blocks in a block row)
 int pmh_mv_ell_create(pmh_csr A, int storage, pmh_mv_ell *out);

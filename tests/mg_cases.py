@@ -605,6 +605,17 @@ def long_rows(seed=14):
     return _hier(A, P, [8] * (nc // 8), _pinv(rng, [8] * (nc // 8)))
 
 
+def long_rows_d0(seed=22):
+    """Three levels, 1500 > 360 > 45 rows, one coarse block: the first P has 13 entries per row on average (> 12: the wavefront-per-row restriction, 8 lanes per row in
+    the prolongation) and level 1 is a smoothed one, so its d0 rides on THAT restriction; rows of the first P' with 0, 1, 63, 64, 65, 200 entries.  The second P is short."""
+    rng = np.random.default_rng(seed)
+    n = [1500, 360, 45]
+    A = [block_operator(rng, n[0] // 3), block_operator(rng, n[1] // 3), eye(n[2])]
+    P = [from_columns(rng, n[0], _lens(rng, n[1], [0, 1, 63, 64, 65, 200], 40, 70)), from_columns(rng, n[1], _lens(rng, n[2], [0, 1, 7, 8, 9], 1, 12))]
+    assert int(P[0]["rowptr"][-1]) > 12 * n[0] and int(P[1]["rowptr"][-1]) <= 12 * n[1]
+    return _hier(A, P, [45], _pinv(rng, [45]))
+
+
 COARSE_STREAM_BLOCKS = [193, 256, 257, 449, 520, 2]  # around the four-stream threshold j + 192 < m and its tail; 1677 rows = 3 x 559
 
 
@@ -759,7 +770,7 @@ def congruent_base(seed=19):
     return _hier(A, P, [18], _pinv(rng, [18]))
 
 
-BUILDERS = dict(nodal3=nodal3, scalar_short=scalar_short, scalar_s=scalar_s, scalar_s_d0=scalar_s_d0, csr_dyadic=csr_dyadic, long_rows=long_rows, coarse_streams=coarse_streams, one_level=one_level,
+BUILDERS = dict(nodal3=nodal3, scalar_short=scalar_short, scalar_s=scalar_s, scalar_s_d0=scalar_s_d0, csr_dyadic=csr_dyadic, long_rows=long_rows, long_rows_d0=long_rows_d0, coarse_streams=coarse_streams, one_level=one_level,
                 diag_rules=diag_rules, congruent1=congruent_base, congruent2=lambda: replicate(congruent_base(), 2), congruent8=lambda: replicate(congruent_base(), 8))
 for _k, _b in MFMA_BLOCKS.items():
     BUILDERS[_k] = functools.partial(mfma, _b, False)
@@ -775,6 +786,7 @@ def hierarchy(name):
 
 # (case, precision, degree, PMH_MG_FUSED or None, PMH_MG_NO_BSR): what the exact tests run; the 8-column form joins wherever Hierarchy8 accepts the hierarchy
 RUNS = [(c, p, 2, None, False) for c in ("nodal3", "scalar_short", "scalar_s", "long_rows", "coarse_streams") for p in ("fp64", "fp32", "fp16")]
+RUNS += [("long_rows_d0", p, 2, None, False) for p in ("fp64", "fp32", "fp16")]  # the long-row restriction with the coarse level's d0 riding on it
 RUNS += [("one_level", p, 2, None, False) for p in ("fp64", "fp32", "fp16")]
 RUNS += [("nodal3", p, 2, 0, False) for p in ("fp64", "fp32")]  # unfused
 RUNS += [("nodal3", p, d, None, False) for d in (1, 3) for p in ("fp64", "fp32")]

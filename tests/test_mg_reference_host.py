@@ -154,7 +154,7 @@ def test_trees_are_the_shuffle_sequences():
 # case -> (transfer kernels per level of the one-column cycle, of the 8-column cycle where it accepts the hierarchy)
 TRANSFERS = {
     "nodal3": ([G.NODAL] * 3, [G.MV_NODAL] * 3), "scalar_short": ([G.SHORT] * 2, [G.MV_ELL] * 2), "scalar_s": ([G.SHORT] * 2, [G.MV_ELL, G.MV_SCALAR]),
-    "scalar_s_d0": ([G.SHORT] * 2, [G.MV_SCALAR, G.MV_ELL]), "long_rows": ([G.LONG], [G.MV_ELL]), "coarse_streams": ([G.SHORT], [G.MV_ELL]), "one_level": ([], []),
+    "scalar_s_d0": ([G.SHORT] * 2, [G.MV_SCALAR, G.MV_ELL]), "long_rows": ([G.LONG], [G.MV_ELL]), "long_rows_d0": ([G.LONG, G.SHORT], [G.MV_ELL] * 2), "coarse_streams": ([G.SHORT], [G.MV_ELL]), "one_level": ([], []),
     "m520": ([G.NODAL], [G.MV_NODAL]), "congruent1": ([G.NODAL] * 2, [G.MV_NODAL] * 2), "congruent2": ([G.NODAL] * 2, [G.MV_NODAL] * 2), "congruent8": ([G.NODAL] * 2, [G.MV_NODAL] * 2),
 }
 REFUSAL = {"fp64": "runs in fp64", 1: "not of degree 2", 3: "not of degree 2", 0: "not the fused form", "one_level": "has one level"}
@@ -208,6 +208,9 @@ def test_cases_hold_the_shapes_they_are_named_after():
     lens = np.diff(hy.L[0]["Pt"]["rowptr"])
     assert {0, 1, 63, 64, 65, 200} <= set(lens.tolist()) and hy.L[1]["n"] > 8192 and {0, 64, 65} <= set(lens[8192:].tolist())
     assert hy.L[0]["P"]["rowptr"][-1] > 12 * hy.L[0]["n"] and max(_row_lengths(hy.L[0]["P"])) > 8  # the 8-lane prolongation takes a second step over a row
+    hy = G.restated(("long_rows_d0", "fp32", 2, None, False))
+    assert {0, 1, 63, 64, 65, 200} <= _row_lengths(hy.L[0]["Pt"]) and hy.L[0]["P"]["rowptr"][-1] > 12 * hy.L[0]["n"] and hy.L[1]["P"]["rowptr"][-1] <= 12 * hy.L[1]["n"]
+    assert [hy.L[l]["n"] for l in range(3)] == [1500, 360, 45] and np.diff(hy.crs).tolist() == [45] and hy.fused_level(1)  # d_c rides on the long-row restriction
     hy = G.restated(("coarse_streams", "fp16", 2, None, False))
     m = np.diff(hy.crs)
     assert m.tolist() == [193, 256, 257, 449, 520, 2]
