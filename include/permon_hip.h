@@ -534,7 +534,7 @@ int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev /* n_local doubles
  * doubles (the labels of both orderings 2, p - q 1, X w 1, the labels [+1; -1] of the doubled problem 2); dense: the last 2 only.
  * With a communicator the samples are sharded by rows and w (d doubles, d + 1 with sigma) is all-reduced between the passes (kept, not tested on more than one
  * GPU).  Under pmh_op_create_penalized with a one-row projector whose row is a multiple of [1; -1] the penalty is absorbed as the rank-one term (as the
- * classification operator does).  No fused MPGP epilogues (MPGP takes its unfused path), no sample subsets, no new labels.
+ * classification operator does).  No fused MPGP epilogues (MPGP takes its unfused path), no new labels.
  * set_terms / set_diag: the rules of pmh_op_svm_dual_set_terms / _set_diag (shift, sigma >= 0; a diagonal and a non-zero shift exclude each other). */
 int pmh_op_create_svr_dual(pmh_ctx ctx, int n_local, int d, const double *X_dev, pmh_op *op);
 int pmh_op_create_svr_dual_f32(pmh_ctx ctx, int n_local, int d, const float *X_dev, pmh_op *op);
@@ -542,6 +542,18 @@ int pmh_op_create_svr_dual_csr(pmh_ctx ctx, pmh_csr X, pmh_op *op);
 int pmh_op_svr_dual_set_terms(pmh_op op, double shift, double sigma);
 int pmh_op_svr_dual_set_diag(pmh_op op, const double *diag_dev /* n_local doubles, borrowed, used for both halves; NULL: off */);
 int pmh_op_svr_dual_passes(pmh_op op, long long *passes); /* passes over X so far: 2 per product */
+/* A sample subset S on a created regression operator (dense rows or CSR).  m_dev: n_local doubles on the device, each exactly 0 or 1, read during the call only
+   (the operator keeps [m; -m], the masked labels of the doubled problem: 16 n_local bytes); NULL: all samples, the plain operator again.  With M^ = diag([m; m])
+   and e^ = [m; -m]:
+     out = M^ [Q + D, -Q; -Q, Q + D] M^ u + sigma (e^'u) e^.
+   The mask's rules are pmh_op_svm_dual_set_subset's, checked by the same function: any other entry (a NaN is one) is PMH_ERR_ARG with the count, an all-zero
+   mask (over all ranks) too; a refused mask changes nothing.  Rows outside S are exactly +0 in both halves; entries of u outside S are selected away, not
+   multiplied by 0: whatever they hold (a NaN, 1e300) changes no bit of the result.  The subset survives _set_terms and _set_diag.  Dense rows: the SUB = 1
+   instances of the four kernels read the mask first -- d = 64: of the 8 (float32: 16) rows a wave has in flight in one coalesced load and a ballot -- and issue
+   no load of a held-out row of X in either pass; a product is still three launches and two counted passes.  CSR: every stored entry is still swept (no row
+   skipping) and there is no second column-ordered copy: the inner classification operator takes the mask, n-vector kernels do the rest.
+   pmh_op_svm_dual_set_subset goes on refusing a regression operator */
+int pmh_op_svr_dual_set_subset(pmh_op op, const double *m_dev /* n_local doubles of 0 / 1, or NULL = all */);
 
 /* ---- QPS SMALXE (src/qps/impls/smalxe/smalxe.c) -------------------------------------------------------- */
 typedef struct {
@@ -823,7 +835,7 @@ int pmh_svm_multi_predict_proba_csr(pmh_svm_multi svm, pmh_csr Xt, double *proba
  * the inner MPGP's) of  t_i - eps - D_i p_i - x_i . w  (a free p_i)  and  t_i + eps + D_i q_i - x_i . w  (a free q_i): stationarity in a free entry.
  * b_multiplier = mu / sqrt(2 n), mu the multiplier of the row in the Lagrangian 1/2 u'H^u - c^'u + mu (row'u).  The bias returned is b_free, or b_multiplier
  * where no entry is free; without bias it is 0.  The bias and the counts take one pass over X, in a fixed summation order.
- * Not here: sample subsets, cross-validation, warm starts, a grid search.  Sharding by rows under a communicator is kept in the code, one GPU is tested. */
+ * Not here: warm starts, a grid search.  Sharding by rows under a communicator is kept in the code, one GPU is tested. */
 typedef struct {
   int             loss_type;  /* -svr_loss_type L1 | L2 (PMH_SVM_LOSS_L1 | PMH_SVM_LOSS_L2) */
   double          C;          /* -svr_C, > 0 */
@@ -875,6 +887,22 @@ int pmh_svr_predict_csr(pmh_svr svr, pmh_csr Xt, double *f_dev);
 int pmh_svr_test(pmh_svr svr, int n, const double *X_dev, const double *t_dev, pmh_svr_metrics *m);
 int pmh_svr_test_f32(pmh_svr svr, int n, const float *X_dev, const double *t_dev, pmh_svr_metrics *m);
 int pmh_svr_test_csr(pmh_svr svr, pmh_csr Xt, const double *t_dev, pmh_svr_metrics *m);
+/* Train on a subset S of the handle's samples and score the held-out rows, X staying where it is (no upload, no new column-ordered copy).  m_dev as in
+ * pmh_op_svr_dual_set_subset (copied; NULL: all samples again, and a training then has the bits of a handle that never had a subset).  Over S only: the
+ * operator's subset, c^_S = [m o (t - eps); m o (-t - eps)], the equality's row [m; -m] / sqrt(2 n_S) (n_S summed over the ranks), L2 the D term; L1 keeps its
+ * bounds.  The solver is built anew and the handle is untrained afterwards; a refused mask leaves the handle exactly as it was.  pmh_svr_set_epsilon and
+ * pmh_svr_set_penalties keep the subset.  After pmh_svr_train u is exactly 0 on the held-out rows in both halves and w, b, n_sv, n_free_sv, sum_beta are those
+ * of training on (X[S], t[S]) alone */
+int pmh_svr_set_subset(pmh_svr svr, const double *m_dev /* n_local doubles of 0 / 1, or NULL = all */);
+/* the mask (n_local doubles, device; all 1 without a subset; may be NULL) and n_S over all ranks (n without a subset; may be NULL) */
+int pmh_svr_get_subset(pmh_svr svr, double *m_dev, long long *n_in);
+/* f(x_i) for all samples the handle was created on, held-out ones included, nothing uploaded: bit for bit pmh_svr_predict on the same X (CSR: the row sweep with
+   the operator's own tables) */
+int pmh_svr_predict_own(pmh_svr svr, double *f_dev /* n_local doubles */);
+/* pmh_svr_test over the handle's own samples and targets: which = PMH_SVM_OWN_HELD_OUT | PMH_SVM_OWN_SUBSET | PMH_SVM_OWN_ALL selects the rows the seven sums
+   and the metrics are taken over (m->n: the selected rows over all ranks; every row is still swept).  PMH_SVM_OWN_HELD_OUT without a subset: PMH_ERR_STATE;
+   PMH_SVM_OWN_SUBSET without a subset: all rows */
+int pmh_svr_test_own(pmh_svr svr, int which, pmh_svr_metrics *m);
 int pmh_svr_destroy(pmh_svr svr);
 
 

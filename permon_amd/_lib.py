@@ -352,6 +352,7 @@ _PROTOS = {
     "pmh_op_svr_dual_passes": [vp, C.POINTER(C.c_longlong)],
     "pmh_op_svr_dual_set_terms": [vp, C.c_double, C.c_double],
     "pmh_op_svr_dual_set_diag": [vp, vp],
+    "pmh_op_svr_dual_set_subset": [vp, vp],
     "pmh_svr_default_opts": [C.POINTER(SvrOpts)],
     "pmh_svr_set_from_options": [C.c_char_p, C.POINTER(SvrOpts), C.c_char_p, C.c_int],
     "pmh_svr_create": [vp, C.c_int, C.c_int, vp, vp, C.POINTER(SvrOpts), C.POINTER(vp)],
@@ -370,6 +371,10 @@ _PROTOS = {
     "pmh_svr_test": [vp, C.c_int, vp, vp, C.POINTER(SvrMetrics)],
     "pmh_svr_test_f32": [vp, C.c_int, vp, vp, C.POINTER(SvrMetrics)],
     "pmh_svr_test_csr": [vp, vp, vp, C.POINTER(SvrMetrics)],
+    "pmh_svr_set_subset": [vp, vp],
+    "pmh_svr_get_subset": [vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svr_predict_own": [vp, vp],
+    "pmh_svr_test_own": [vp, C.c_int, C.POINTER(SvrMetrics)],
     "pmh_svr_destroy": [vp],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],

@@ -577,6 +577,28 @@ int SvmDualBase::refresh_ym()
   return PMH_SUCCESS;
 }
 
+int pmh_svm_check_mask(pmh_ctx ctx, const char *who, int n, const double *m_dev, long long *ones, int *first)
+{
+  // every rank decides alike: the counts are summed over the communicator before anything is changed
+  int  h[3] = {0, 0, n};
+  int *d_st = nullptr;
+  PMH_CHK(pmh_malloc(ctx, sizeof(h), (void **)&d_st));
+  int rc = pmh_memcpy_h2d(ctx, d_st, h, sizeof(h));
+  if (!rc && n > 0) {
+    hipLaunchKernelGGL(k_svm_mask_stats, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m_dev, d_st);
+    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "%s: the launch that checks the mask failed", who);
+  }
+  if (!rc) rc = pmh_memcpy_d2h(ctx, h, d_st, sizeof(h));
+  pmh_free(ctx, d_st);
+  PMH_CHK(rc);
+  double tot[2] = {(double)h[0], (double)h[1]};
+  PMH_CHK(pmh_comm_sum_host(ctx, tot, 2));
+  if (tot[0] != 0.0) return pmh_set_error(PMH_ERR_ARG, "%s: %lld entries of the mask are neither 0 nor 1", who, (long long)tot[0]);
+  if (tot[1] == 0.0) return pmh_set_error(PMH_ERR_ARG, "%s: the mask holds no sample (all zero)", who);
+  *ones = h[1], *first = h[1] ? h[2] : 0;
+  return PMH_SUCCESS;
+}
+
 extern "C" int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev)
 {
   SvmDualBase *o = dynamic_cast<SvmDualBase *>(op);
@@ -590,22 +612,9 @@ extern "C" int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev)
     o->terms_changed();
     return PMH_SUCCESS;
   }
-  // every rank decides alike: the counts are summed over the communicator before anything is changed
-  int  h[3] = {0, 0, n};
-  int *d_st = nullptr;
-  PMH_CHK(pmh_malloc(ctx, sizeof(h), (void **)&d_st));
-  int rc = pmh_memcpy_h2d(ctx, d_st, h, sizeof(h));
-  if (!rc && n > 0) {
-    hipLaunchKernelGGL(k_svm_mask_stats, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m_dev, d_st);
-    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_op_svm_dual_set_subset: the launch that checks the mask failed");
-  }
-  if (!rc) rc = pmh_memcpy_d2h(ctx, h, d_st, sizeof(h));
-  pmh_free(ctx, d_st);
-  PMH_CHK(rc);
-  double tot[2] = {(double)h[0], (double)h[1]};
-  PMH_CHK(pmh_comm_sum_host(ctx, tot, 2));
-  if (tot[0] != 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_subset: %lld entries of the mask are neither 0 nor 1", (long long)tot[0]);
-  if (tot[1] == 0.0) return pmh_set_error(PMH_ERR_ARG, "pmh_op_svm_dual_set_subset: the mask holds no sample (all zero)");
+  long long ones  = 0;
+  int       first = 0, rc;
+  PMH_CHK(pmh_svm_check_mask(ctx, "pmh_op_svm_dual_set_subset", n, m_dev, &ones, &first));
   if (!o->msk) {
     const size_t nb = sizeof(double) * (size_t)(n ? n : 1);
     PMH_CHK(pmh_malloc(ctx, nb, (void **)&o->msk));
@@ -618,7 +627,7 @@ extern "C" int pmh_op_svm_dual_set_subset(pmh_op op, const double *m_dev)
     hipLaunchKernelGGL(k_svm_mask_labels, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m_dev, o->y, o->msk, o->ym);
     PMH_HIP(hipGetLastError());
   }
-  o->n_sub = h[1], o->sub_first = h[1] ? h[2] : 0;
+  o->n_sub = ones, o->sub_first = first;
   o->terms_changed();
   return PMH_SUCCESS;
 }

@@ -2,8 +2,10 @@
 //   svm_store<K, MINROW>    K sums of a thread -> part[K][grid]; pmh_svm_sum_rows / pmh_svm_finish_part: one workgroup finishes them in a fixed order
 //   sv_front                the training core both handles derive from: samples, operator, projector, solver, the vectors of the QP, the model
 //   sv_build_solver, sv_solve, sv_model_tail, sv_count_bad, sv_alloc_common, sv_free   the steps of create / train / model that do not depend on what is trained
-// What is particular to a side stays in its file: labels, subsets, warm starts and calibration (svm_train.hip); epsilon, the doubled right-hand side, the
-// [1; -1] row and the metrics (svr_train.hip).  Definitions: svm_front.hip.
+//   sv_count_subset, sv_refresh_row, sv_get_subset, svm_sel, sv_own_selector   what a sample subset needs on either side: n_S, the equality's row over the
+//                           operator's masked labels, the mask handed back, the selector of test_own
+// What is particular to a side stays in its file: labels, the subset's right-hand side and diagonal, warm starts and calibration (svm_train.hip); epsilon, the
+// doubled right-hand side and the metrics (svr_train.hip).  Definitions: svm_front.hip.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -53,7 +55,31 @@ struct sv_front {
   pmh_smalxe_opts o_smalxe;
   int             bias = 0, loss_type = 0;
   double          astol() const { return sx ? o_smalxe.inner.astol : o_mpgp.astol; } // of the solver that trains
+  // a sample subset (pmh_svm_set_subset, pmh_svr_set_subset): the mask and the masked labels are the operator's (SvmDualBase::msk, ym); n_sub: the subset's
+  // samples over all ranks (0: no subset)
+  long long       n_sub = 0;
 };
+
+// ---- sample subsets ---------------------------------------------------------------------------------------------------------------------------------------------
+// the samples the problem is posed over, all ranks: the subset's, or all
+static inline long long sv_n_posed(const sv_front *f) { return f->n_sub > 0 ? f->n_sub : f->n_global; }
+// n_sub from the operator's mask, all-reduced as n_global is (0 where the operator holds none)
+int sv_count_subset(sv_front *f);
+// the equality's row c (labels) over the nu entries of the dual and its one-row projector, built anew: the operator's labels as its kernels read them (yk():
+// the masked ones under a subset, zero on the held-out entries).  Classification: c = 1 / sqrt(n_S); regression: the labels are [m; -m], c = 1 / sqrt(2 n_S)
+int sv_refresh_row(sv_front *f, double c);
+// row = c y (n doubles each, device)
+int sv_fill_row(pmh_ctx ctx, int n, const double *y, double c, double *row);
+// the mask (n doubles, device; all 1 without a subset; may be NULL) and n_S over all ranks (n without a subset; may be NULL)
+int sv_get_subset(sv_front *f, double *m_dev, long long *n_in);
+// The selector of pmh_svm_test_own / pmh_svr_test_own: with m given, a sample is counted only where m_i == want (the handle's subset mask: 1 the subset, 0 the
+// held-out rows)
+struct svm_sel {
+  const double *m = nullptr;
+  double        want = 0.0;
+};
+// the selector of `which` (PMH_SVM_OWN_*, checked here in the name of who: PMH_ERR_ARG; HELD_OUT without a subset: PMH_ERR_STATE) over the handle's own samples
+int sv_own_selector(sv_front *f, const char *who, const char *set_subset, int which, svm_sel *sel);
 
 // the solvers hold the operator and the projector: whoever changes or replaces either drops them first
 void sv_drop_solver(sv_front *f);

@@ -136,6 +136,51 @@ int sv_count_samples(sv_front *f, const char *who)
   return PMH_SUCCESS;
 }
 
+int sv_count_subset(sv_front *f)
+{
+  SvmDualBase *H = static_cast<SvmDualBase *>(f->H);
+  double       ns = H->msk ? (double)H->n_sub : 0.0;
+  PMH_CHK(pmh_comm_sum_host(f->ctx, &ns, 1));
+  f->n_sub = (long long)ns;
+  return PMH_SUCCESS;
+}
+
+__global__ __launch_bounds__(PMH_BLOCK) void k_svm_fill_row(int n, const double *__restrict__ y, double c, double *__restrict__ row)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) row[i] = c * y[i];
+}
+int sv_fill_row(pmh_ctx ctx, int n, const double *y, double c, double *row)
+{
+  if (n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, y, c, row);
+  PMH_HIP(hipGetLastError());
+  return PMH_SUCCESS;
+}
+int sv_refresh_row(sv_front *f, double c)
+{
+  if (!f->bias) return PMH_SUCCESS;
+  if (f->pf) pmh_qppf_destroy(f->pf), f->pf = nullptr;
+  PMH_CHK(sv_fill_row(f->ctx, f->nu, static_cast<SvmDualBase *>(f->H)->yk(), c, f->row));
+  return pmh_qppf_create_onerow(f->ctx, f->row, f->nu, &f->pf);
+}
+
+int sv_get_subset(sv_front *f, double *m_dev, long long *n_in)
+{
+  SvmDualBase *H = static_cast<SvmDualBase *>(f->H);
+  if (n_in) *n_in = sv_n_posed(f);
+  if (!m_dev) return PMH_SUCCESS;
+  return H->msk ? pmh_vec_copy(f->ctx, f->n, H->msk, m_dev) : pmh_vec_set(f->ctx, f->n, m_dev, 1.0);
+}
+
+int sv_own_selector(sv_front *f, const char *who, const char *set_subset, int which, svm_sel *sel)
+{
+  if (which != PMH_SVM_OWN_HELD_OUT && which != PMH_SVM_OWN_SUBSET && which != PMH_SVM_OWN_ALL) return pmh_set_error(PMH_ERR_ARG, "%s: which = %d (PMH_SVM_OWN_HELD_OUT | PMH_SVM_OWN_SUBSET | PMH_SVM_OWN_ALL)", who, which);
+  SvmDualBase *H = static_cast<SvmDualBase *>(f->H);
+  if (which == PMH_SVM_OWN_HELD_OUT && !H->msk) return pmh_set_error(PMH_ERR_STATE, "%s: no subset is set (%s), so no sample is held out", who, set_subset);
+  *sel = svm_sel();
+  if (which != PMH_SVM_OWN_ALL && H->msk) sel->m = H->msk, sel->want = which == PMH_SVM_OWN_SUBSET ? 1.0 : 0.0;
+  return PMH_SUCCESS;
+}
+
 int sv_alloc_penalties(sv_front *f)
 {
   const size_t nb = sizeof(double) * (size_t)(f->n ? f->n : 1);

@@ -52,7 +52,7 @@ struct SvmDualBase : pmh_op_s {
   virtual void  terms_changed() {} // pmh_op_svm_dual_set_terms / pmh_op_svm_dual_set_diag was called
   // The regression operator (svr.hip) is this dual on the doubled samples [X; X] with labels [+1; -1], X held once: n = 2 n_local, y its own 2 n_local labels
   // (what pmh_svm_op_row_is_labels compares the equality's row with, so that the penalised operator folds rho G'G into sigma_fold as it does here), diag
-  // n_local doubles used for both halves.  It takes no subset and no new labels
+  // n_local doubles used for both halves.  It takes no new labels, and a subset through its own entry (pmh_op_svr_dual_set_subset: a mask of n_local entries)
   virtual bool  doubled() const { return false; }
   // pmh_op_svm_dual_set_labels: new labels (n doubles of +-1, borrowed; may be the buffer borrowed so far with new contents).  Whatever the operator derived
   // from the old labels it redoes from state of its own, never from the caller's memory
@@ -128,6 +128,11 @@ static __device__ __forceinline__ double svm_aug_row(double yi, double dot, doub
 
 // w[c] = sum over the nblocks workgroups of part[b][c], c < d; spart != nullptr: w[d] = sum_b spart[b] too (k_svm_colsum: one wavefront per column, fixed order)
 int pmh_svm_colsum(pmh_ctx ctx, int nblocks, int d, const double *part, double *w, const double *spart);
+
+// The rules of a subset mask, checked in one place for pmh_op_svm_dual_set_subset and pmh_op_svr_dual_set_subset (who: the entry, for the messages): m_dev, n
+// doubles on the device, must hold 0 / 1 only (else PMH_ERR_ARG with the count; a NaN is one) and at least one 1; both counts are summed over the communicator
+// first, so every rank decides alike.  Nothing of the caller's is changed.  *ones: the ones of this rank, *first: the index of the first of them (0: none)
+int pmh_svm_check_mask(pmh_ctx ctx, const char *who, int n, const double *m_dev, long long *ones, int *first);
 
 // 1 (and c, with row = c y) if pf is a one-row projector whose row is a multiple of this operator's labels, entry by entry
 int pmh_svm_op_row_is_labels(SvmDualBase *o, pmh_qppf pf, double *c);

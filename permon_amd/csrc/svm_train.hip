@@ -19,9 +19,7 @@
 struct pmh_svm_s : sv_front { // (u is alpha)
   const double *y = nullptr;
   double        C = 0.0;
-  // pmh_svm_set_subset: the mask and the masked labels are the operator's (SvmDualBase::msk, ym); n_sub: the subset's samples over all ranks (0: no subset);
-  // Dm: L2, the operator's diagonal m_i / C_i under a subset (n doubles)
-  long long     n_sub = 0;
+  // pmh_svm_set_subset (the mask and n_sub: sv_front): Dm: L2, the operator's diagonal m_i / C_i under a subset (n doubles)
   double       *Dm = nullptr;
   pmh_svm_stats st;
   // warm starts (pmh_svm_train_warm): has_dual: alpha is the dual of a training with the current labels (pmh_svm_set_labels clears it; set_penalties and
@@ -37,10 +35,6 @@ struct pmh_svm_s : sv_front { // (u is alpha)
   pmh_svm_platt_stats cal_st;
 };
 
-__global__ __launch_bounds__(PMH_BLOCK) void k_svm_fill_row(int n, const double *__restrict__ y, double c, double *__restrict__ row)
-{
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) row[i] = c * y[i];
-}
 
 // sample i with dot = x_i . w in the sums of the bias: s[0] over the free support vectors of y_i - x_i . w, s[1] = y'a, s[2] the number of free support vectors,
 // s[3] of support vectors; free: astol < a_i and (ubound > 0: a_i < ubound - astol).  UBV: the upper bound of sample i is ubv[i] (per-sample penalties, L1),
@@ -68,11 +62,7 @@ struct svm_counts {
 // sample i with the score s = x_i . w + b: label_i = +-1 (s >= 0: +1) and, with the true labels, the confusion counts.  scores / labels / ytrue may each be
 // nullptr; no __restrict__ on scores: the CSR form reads the dot products from the array the scores go to.  The counts go in and out by value: through
 // references the choice (pos ? tp : fp) is one between addresses, and the compiler then keeps the counts in memory (40 bytes of scratch per lane, or 8 KiB of LDS)
-// The selector of pmh_svm_test_own: with sel.m given, a sample is counted only where m_i == sel.want (the handle's subset mask: 1 the subset, 0 the held-out rows)
-struct svm_sel {
-  const double *m = nullptr;
-  double        want = 0.0;
-};
+// The selector of pmh_svm_test_own (svm_sel, svm_front.h): with sel.m given, a sample is counted only where m_i == sel.want
 static __device__ __forceinline__ svm_counts svm_classify_row(long long i, double s, double *scores, double *__restrict__ labels, const double *__restrict__ ytrue, svm_counts c, svm_sel sel)
 {
   const double l = s >= 0.0 ? 1.0 : -1.0;
@@ -130,17 +120,9 @@ extern "C" int pmh_svm_destroy(pmh_svm s)
   return PMH_SUCCESS;
 }
 
-// the samples the problem is posed over, all ranks: the subset's, or all
-static long long svm_n_posed(pmh_svm s) { return s->n_sub > 0 ? s->n_sub : s->n_global; }
+static long long svm_n_posed(pmh_svm s) { return sv_n_posed(s); }
 // the equality's row y / sqrt(n) and its projector; under a subset the masked labels over sqrt(n_S): zero on the held-out rows
-static int svm_refresh_row(pmh_svm s)
-{
-  if (!s->bias) return PMH_SUCCESS;
-  if (s->pf) pmh_qppf_destroy(s->pf), s->pf = nullptr;
-  if (s->n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, static_cast<SvmDualBase *>(s->H)->yk(), 1.0 / sqrt((double)svm_n_posed(s)), s->row);
-  PMH_HIP(hipGetLastError());
-  return pmh_qppf_create_onerow(s->ctx, s->row, s->n, &s->pf);
-}
+static int svm_refresh_row(pmh_svm s) { return sv_refresh_row(s, 1.0 / sqrt((double)svm_n_posed(s))); }
 // Dm_i = m_i cinv_i (cinv == nullptr: m_i c)
 __global__ __launch_bounds__(PMH_BLOCK) void k_svm_mask_diag(int n, const double *__restrict__ m, const double *__restrict__ cinv, double c, double *__restrict__ Dm)
 {
@@ -288,7 +270,7 @@ static int svm_train(pmh_svm s, const char *who, int warm, double alpha_scale)
     // the solver's own B'mu
     double *Btmu = nullptr;
     PMH_CHK(pmh_smalxe_get_penalized(s->sx, nullptr, nullptr, &Btmu));
-    if (s->n > 0) hipLaunchKernelGGL(k_svm_fill_row, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, (const double *)s->row, s->b_mult * sqrt((double)svm_n_posed(s)), Btmu);
+    PMH_CHK(sv_fill_row(s->ctx, s->n, s->row, s->b_mult * sqrt((double)svm_n_posed(s)), Btmu));
     PMH_HIP(hipGetLastError());
     PMH_CHK(pmh_smalxe_set_initial_multiplier(s->sx, Btmu));
   }
@@ -427,13 +409,9 @@ extern "C" int pmh_svm_set_subset(pmh_svm s, const double *m_dev)
   PMH_CHK(pmh_op_svm_dual_set_subset(s->H, m_dev)); // (checks the mask before anything changes; the solvers only hold the operator)
   s->trained = s->calibrated = 0;
   sv_drop_solver(s);
-  s->n_sub = 0;
-  if (m_dev) {
-    double ns = (double)H->n_sub; // all-reduced as n_global is
-    PMH_CHK(pmh_comm_sum_host(ctx, &ns, 1));
-    s->n_sub = (long long)ns;
-    PMH_CHK(pmh_vec_copy(ctx, s->n, H->msk, s->rhs));
-  } else PMH_CHK(pmh_vec_set(ctx, s->n, s->rhs, 1.0));
+  PMH_CHK(sv_count_subset(s));
+  if (m_dev) PMH_CHK(pmh_vec_copy(ctx, s->n, H->msk, s->rhs));
+  else PMH_CHK(pmh_vec_set(ctx, s->n, s->rhs, 1.0));
   PMH_CHK(svm_refresh_l2(s));
   PMH_CHK(svm_refresh_row(s));
   return sv_build_solver(s);
@@ -442,10 +420,7 @@ extern "C" int pmh_svm_set_subset(pmh_svm s, const double *m_dev)
 extern "C" int pmh_svm_get_subset(pmh_svm s, double *m_dev, long long *n_in)
 {
   PMH_ARG(s);
-  SvmDualBase *H = static_cast<SvmDualBase *>(s->H);
-  if (n_in) *n_in = svm_n_posed(s);
-  if (!m_dev) return PMH_SUCCESS;
-  return H->msk ? pmh_vec_copy(s->ctx, s->n, H->msk, m_dev) : pmh_vec_set(s->ctx, s->n, m_dev, 1.0);
+  return sv_get_subset(s, m_dev, n_in);
 }
 
 void pmh_svm_own_samples(pmh_svm s, const void **X, int *f32, pmh_csr *Xcsr, const double **msk)
@@ -509,11 +484,8 @@ extern "C" int pmh_svm_predict_own(pmh_svm s, double *scores_dev, double *labels
 extern "C" int pmh_svm_test_own(pmh_svm s, int which, long long counts[4])
 {
   PMH_ARG(s && counts);
-  if (which != PMH_SVM_OWN_HELD_OUT && which != PMH_SVM_OWN_SUBSET && which != PMH_SVM_OWN_ALL) return pmh_set_error(PMH_ERR_ARG, "pmh_svm_test_own: which = %d (PMH_SVM_OWN_HELD_OUT | PMH_SVM_OWN_SUBSET | PMH_SVM_OWN_ALL)", which);
-  SvmDualBase *H = static_cast<SvmDualBase *>(s->H);
-  if (which == PMH_SVM_OWN_HELD_OUT && !H->msk) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_test_own: no subset is set (pmh_svm_set_subset), so no sample is held out");
   svm_sel sel;
-  if (which != PMH_SVM_OWN_ALL && H->msk) sel.m = H->msk, sel.want = which == PMH_SVM_OWN_SUBSET ? 1.0 : 0.0;
+  PMH_CHK(sv_own_selector(s, "pmh_svm_test_own", "pmh_svm_set_subset", which, &sel));
   return svm_predict(s, s->n, s->X, s->f32, nullptr, nullptr, nullptr, s->y, counts, true, sel);
 }
 

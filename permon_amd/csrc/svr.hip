@@ -10,7 +10,9 @@
 // halves written; + 8 n with a diagonal) against 4 * 8 n d + 80 n of the doubled classification operator.  The row loops are those of svm_rows.h; the summation
 // orders are fixed (no float atomics): two products give the same bits, and the float instances for d != 64 give the bits of the double ones on the widened
 // samples.  Samples in CSR: the entry-balanced sweeps of svm_csr.hip over X with all labels +1 (SvrCsrOp below).
-// No fused MPGP epilogues (mult_epi declines, MPGP takes its unfused path), no subsets.
+// A sample subset S (pmh_op_svr_dual_set_subset, mask m): out = M^ H^ M^ u + sigma (e^'u) e^, M^ = diag([m; m]), e^ = [m; -m].  The SUB = 1 instances of the four
+// dense kernels read m_i first and issue no load of a held-out row of X, nor of its p_i, q_i, diag_i; its two results are +0.  SUB = 0: the kernels as they were.
+// No fused MPGP epilogues (mult_epi declines, MPGP takes its unfused path).
 #include "pmh_internal.h"
 #include "reduce.h"
 
@@ -18,8 +20,10 @@
 #include "svm_rows.h"
 
 // pass 1, any d: k_svm_xt's row loop with the row's weight s_i = p_i - q_i; AUG: also S = sum_i s_i -> spart[workgroup]
-template <int AUG, class T>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt(int n, int d, const T *__restrict__ X, const double *__restrict__ p, const double *__restrict__ q, double *__restrict__ part, double *__restrict__ spart)
+// SUB: m_i is read first (uniform over the wave) and a held-out row is skipped: it adds to no sum, whatever p_i and q_i hold
+template <int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt(int n, int d, const T *__restrict__ X, const double *__restrict__ p, const double *__restrict__ q, double *__restrict__ part, double *__restrict__ spart,
+                                                      const double *__restrict__ m)
 {
   __shared__ double lds[PMH_BLOCK / 64][64 * SVM_KMAX];
   __shared__ double sred[AUG ? PMH_BLOCK / 64 : 1];
@@ -30,6 +34,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt(int n, int d, const T *__r
 #pragma unroll
   for (int k = 0; k < SVM_KMAX; k++) acc[k] = 0.0;
   for (long long i = gw; i < n; i += nw) {
+    if (SUB && m[i] == 0.0) continue;
     const double s  = p[i] - q[i];
     const T     *xr = X + (size_t)i * d;
     if (AUG) as += s;
@@ -58,8 +63,11 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt(int n, int d, const T *__r
 }
 
 // pass 1 for d = 64: k_svm_xt64's row loop (every lane that holds a part of row i needs s_i), the layouts of svm_row64<T>, then svm_fold_cols
-template <int UNR, int AUG, class T>
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt64(int n, const T *__restrict__ X, const double *__restrict__ p, const double *__restrict__ q, double *__restrict__ part, double *__restrict__ spart)
+// SUB: the mask of the RPI UNR rows in flight comes in ONE coalesced load and a ballot (svm_live_rows64); a held-out row is not loaded (svm_load_rows64<UNR, 1>)
+// and s_i = m_i ? p_i - q_i : 0, a selection: p_i and q_i of a held-out row are not read
+template <int UNR, int AUG, int SUB, class T>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt64(int n, const T *__restrict__ X, const double *__restrict__ p, const double *__restrict__ q, double *__restrict__ part, double *__restrict__ spart,
+                                                        const double *__restrict__ m)
 {
   typedef svm_row64<T> R;
   __shared__ double lds[PMH_BLOCK / 64][64];
@@ -73,13 +81,26 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt64(int n, const T *__restri
   for (long long r0 = gw * R::RPI * UNR; r0 < n; r0 += nw * R::RPI * UNR) {
     typename R::vec v[UNR];
     double          s[UNR];
+    if constexpr (SUB) {
+      double                   mi;
+      const unsigned long long live = svm_live_rows64<R::RPI * UNR>(n, m, r0, mi);
+      svm_load_rows64<UNR, 1>(n, X, r0, v, live);
+      const unsigned lh = (unsigned)(live >> sub); // bit RPI u: this lane's row of group u (shifted once: a shift per u costs registers, as in svm_load_rows64)
 #pragma unroll
-    for (int u = 0; u < UNR; u++) {
-      const long long i  = r0 + R::RPI * u + sub;
-      const bool      ok = i < n;
-      v[u] = ok ? __builtin_nontemporal_load((const typename R::vec *)(X + (size_t)i * 64) + lq) : R::zero();
-      s[u] = ok ? p[i] - q[i] : 0.0;
-      if (AUG && lq == 0) as += s[u];
+      for (int u = 0; u < UNR; u++) {
+        const long long i = r0 + R::RPI * u + sub;
+        s[u] = ((lh >> (R::RPI * u)) & 1) ? p[i] - q[i] : 0.0; // (a live row is a row below n)
+        if (AUG && lq == 0) as += s[u];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        const long long i  = r0 + R::RPI * u + sub;
+        const bool      ok = i < n;
+        v[u] = ok ? __builtin_nontemporal_load((const typename R::vec *)(X + (size_t)i * 64) + lq) : R::zero();
+        s[u] = ok ? p[i] - q[i] : 0.0;
+        if (AUG && lq == 0) as += s[u];
+      }
     }
 #pragma unroll
     for (int u = 0; u < UNR; u++) {
@@ -95,13 +116,19 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svr_xt64(int n, const T *__restri
 }
 
 // what pass 2 does with row i's dot product: both halves.  AUG 0: +-dot; 1: the scalar shift; 2: diag_i
+// SUB: the sweeps hand a held-out row over with dot = 0; the row is recognised here by m_i == 0 and both halves are +0, p_i, q_i and diag_i unread
 struct svr_row_out {
   const double *p, *q, *diag;
   double       *op, *oq;
   double        sS, shift;
+  const double *m; // SUB: the mask
 };
-template <int AUG> static __device__ __forceinline__ void svr_store_row(const svr_row_out &o, long long i, double dot)
+template <int AUG, int SUB> static __device__ __forceinline__ void svr_store_row(const svr_row_out &o, long long i, double dot)
 {
+  if (SUB && o.m[i] == 0.0) {
+    o.op[i] = 0.0, o.oq[i] = 0.0;
+    return;
+  }
   if (AUG == 0) {
     o.op[i] = dot, o.oq[i] = -dot;
     return;
@@ -110,17 +137,17 @@ template <int AUG> static __device__ __forceinline__ void svr_store_row(const sv
   o.op[i] = svm_aug_row(1.0, dot, o.sS, D, o.p[i]);
   o.oq[i] = svm_aug_row(-1.0, dot, o.sS, D, o.q[i]);
 }
-template <int AUG, class T>
+template <int AUG, int SUB, class T>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svr_x(int n, int d, const T *__restrict__ X, const double *__restrict__ w, svr_row_out o, double sigma)
 {
   o.sS = AUG ? sigma * w[d] : 0.0;
-  svm_sweep_rows(n, d, X, w, [&](long long i, double dot) { svr_store_row<AUG>(o, i, dot); });
+  svm_sweep_rows<SUB>(n, d, X, w, [&](long long i, double dot) { svr_store_row<AUG, SUB>(o, i, dot); }, o.m);
 }
-template <int UNR, int AUG, class T>
+template <int UNR, int AUG, int SUB, class T>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svr_x64(int n, const T *__restrict__ X, const double *__restrict__ w, svr_row_out o, double sigma)
 {
   o.sS = AUG ? sigma * w[64] : 0.0;
-  svm_sweep_rows64<UNR>(n, X, w, [&](long long i, double dot) { svr_store_row<AUG>(o, i, dot); });
+  svm_sweep_rows64<UNR, SUB>(n, X, w, [&](long long i, double dot) { svr_store_row<AUG, SUB>(o, i, dot); }, o.m);
 }
 
 __global__ __launch_bounds__(PMH_BLOCK) void k_svr_labels(int nl, double *__restrict__ yy)
@@ -133,6 +160,29 @@ int SvrDualBase::init_labels()
   if (nl > 0) hipLaunchKernelGGL(k_svr_labels, dim3(pmh_vec_grid(nl)), dim3(PMH_BLOCK), 0, ctx->stream, nl, yy);
   PMH_HIP(hipGetLastError());
   y = yy;
+  return PMH_SUCCESS;
+}
+
+// ym = [m; -m] with m_i -> 1 or +0: +0 in both halves of a held-out sample
+__global__ __launch_bounds__(PMH_BLOCK) void k_svr_mask_labels(int nl, const double *__restrict__ m, double *__restrict__ ym)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < nl; i += (long long)gridDim.x * PMH_BLOCK) {
+    const bool in = m[i] != 0.0;
+    ym[i] = in ? 1.0 : 0.0, ym[nl + i] = in ? -1.0 : 0.0;
+  }
+}
+int SvrDualBase::take_mask(const double *m_dev, long long ones, int first)
+{
+  if (!m_dev) {
+    if (ym) pmh_free(ctx, ym);
+    msk = ym = nullptr, n_sub = 0, sub_first = 0;
+    return PMH_SUCCESS;
+  }
+  if (!ym) PMH_CHK(pmh_malloc(ctx, sizeof(double) * 2 * (size_t)(nl ? nl : 1), (void **)&ym));
+  msk = ym;
+  if (nl > 0) hipLaunchKernelGGL(k_svr_mask_labels, dim3(pmh_vec_grid(nl)), dim3(PMH_BLOCK), 0, ctx->stream, nl, m_dev, ym);
+  PMH_HIP(hipGetLastError());
+  n_sub = ones, sub_first = first;
   return PMH_SUCCESS;
 }
 
@@ -152,14 +202,12 @@ struct SvrDualOp : SvrDualBase {
   // w = X'(p - q) (+ w[d] = sum (p_i - q_i)) of u = [p; q]: pass 1, the column sums, the all-reduce
   int pass1(const double *u, bool aug)
   {
-    svm_const<2>(aug, [&](auto A) {
-      svm_const<2>(f32, [&](auto F) {
-        constexpr int AUG = decltype(A)::value;
-        using T           = svm_sample_t<decltype(F)>;
-        // (d == 64: UNR = 4, the one instance compiled, as in SvmDualOp::pass1)
-        if (d == 64) SVM_PASS((k_svr_xt64<4, AUG, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, (const T *)X, u, u + nl, part, spart);
-        else SVM_PASS((k_svr_xt<AUG, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, d, (const T *)X, u, u + nl, part, spart);
-      });
+    svm_pick<2>(aug, ym != nullptr, f32, [&](auto A, auto S, auto F) {
+      constexpr int AUG = decltype(A)::value, SUB = decltype(S)::value;
+      using T           = svm_sample_t<decltype(F)>;
+      // (d == 64: UNR = 4, the one instance compiled, as in SvmDualOp::pass1)
+      if (d == 64) SVM_PASS((k_svr_xt64<4, AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, (const T *)X, u, u + nl, part, spart, (const double *)msk);
+      else SVM_PASS((k_svr_xt<AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, d, (const T *)X, u, u + nl, part, spart, (const double *)msk);
     });
     PMH_CHK(pmh_svm_colsum(ctx, nblocks, d, part, w, aug ? spart : nullptr));
     return pmh_comm_allreduce_sum(ctx, w, (size_t)d + (aug ? 1 : 0)); // samples sharded over GPUs: the one exchange step
@@ -170,15 +218,13 @@ struct SvrDualOp : SvrDualBase {
     if (nl == 0) return PMH_SUCCESS;
     const bool AG = aug();
     PMH_CHK(pass1(u, AG));
-    svr_row_out o{u, u + nl, diag, out, out + nl, 0.0, shift};
+    svr_row_out o{u, u + nl, diag, out, out + nl, 0.0, shift, msk};
     const double sg = sigma + sigma_fold;
-    svm_const<3>(aug_form(), [&](auto A) {
-      svm_const<2>(f32, [&](auto F) {
-        constexpr int AUG = decltype(A)::value;
-        using T           = svm_sample_t<decltype(F)>;
-        if (d == 64) SVM_PASS((k_svr_x64<4, AUG, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, (const T *)X, (const double *)w, o, sg);
-        else SVM_PASS((k_svr_x<AUG, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, d, (const T *)X, (const double *)w, o, sg);
-      });
+    svm_pick<3>(aug_form(), ym != nullptr, f32, [&](auto A, auto S, auto F) {
+      constexpr int AUG = decltype(A)::value, SUB = decltype(S)::value;
+      using T           = svm_sample_t<decltype(F)>;
+      if (d == 64) SVM_PASS((k_svr_x64<4, AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, (const T *)X, (const double *)w, o, sg);
+      else SVM_PASS((k_svr_x<AUG, SUB, T>), dim3(nblocks), dim3(PMH_BLOCK), 0, ctx->stream, nl, d, (const T *)X, (const double *)w, o, sg);
     });
     PMH_HIP(hipGetLastError());
     return PMH_SUCCESS;
@@ -208,16 +254,22 @@ struct SvrDualOp : SvrDualBase {
 };
 
 // ---- samples in CSR --------------------------------------------------------------------------------------------------------------------------------------------
-// s = p - q before pass 1
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_diff(int nl, const double *__restrict__ p, const double *__restrict__ q, double *__restrict__ s)
+// s = p - q before pass 1; SUB: s_i = m_i ? p_i - q_i : 0, a selection
+template <int SUB>
+__global__ __launch_bounds__(PMH_BLOCK) void k_svr_diff(int nl, const double *__restrict__ p, const double *__restrict__ q, double *__restrict__ s, const double *__restrict__ m)
 {
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < nl; i += (long long)gridDim.x * PMH_BLOCK) s[i] = p[i] - q[i];
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < nl; i += (long long)gridDim.x * PMH_BLOCK) s[i] = (SUB && m[i] == 0.0) ? 0.0 : p[i] - q[i];
 }
 // the two halves after pass 2 from v_i = x_i . w + sigma S: out_p[i] = v_i + D_i p_i, out_q[i] = -v_i + D_i q_i (AUG as in svr_store_row)
-template <int AUG>
+// SUB: +0 in both halves of a held-out row, nothing of it read but m_i
+template <int AUG, int SUB>
 __global__ __launch_bounds__(PMH_BLOCK) void k_svr_halves(int nl, const double *__restrict__ v, svr_row_out o)
 {
   for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < nl; i += (long long)gridDim.x * PMH_BLOCK) {
+    if (SUB && o.m[i] == 0.0) {
+      o.op[i] = 0.0, o.oq[i] = 0.0;
+      continue;
+    }
     const double vi = v[i];
     if (AUG == 0) o.op[i] = vi, o.oq[i] = -vi;
     else {
@@ -234,9 +286,16 @@ struct SvrCsrOp : SvrDualBase {
   double      *ones = nullptr, *s = nullptr, *v = nullptr; // [nl] each
   int diff(const double *u)
   {
-    hipLaunchKernelGGL(k_svr_diff, dim3(pmh_vec_grid(nl)), dim3(PMH_BLOCK), 0, ctx->stream, nl, u, u + nl, s);
+    svm_const<2>(ym != nullptr, [&](auto S) { hipLaunchKernelGGL(k_svr_diff<decltype(S)::value>, dim3(pmh_vec_grid(nl)), dim3(PMH_BLOCK), 0, ctx->stream, nl, u, u + nl, s, (const double *)msk); });
     PMH_HIP(hipGetLastError());
     return PMH_SUCCESS;
+  }
+  // A subset: the inner operator takes the mask (its labels are all +1, so its masked labels are m: its pass 1 and its sigma term run over S; every stored
+  // entry is still swept, and the one column-ordered copy stays), k_svr_halves writes the zeros of the held-out rows: n-vector work only
+  int take_mask(const double *m_dev, long long ones, int first) override
+  {
+    PMH_CHK(pmh_op_svm_dual_set_subset(inner, m_dev));
+    return SvrDualBase::take_mask(m_dev, ones, first);
   }
   int mult(const double *u, double *out) override
   {
@@ -247,8 +306,10 @@ struct SvrCsrOp : SvrDualBase {
     const int rc = in->mult(s, v);
     npass        = in->npass;
     PMH_CHK(rc);
-    svr_row_out o{u, u + nl, diag, out, out + nl, 0.0, shift};
-    svm_const<3>(diag ? 2 : (shift != 0.0 ? 1 : 0), [&](auto A) { hipLaunchKernelGGL(k_svr_halves<decltype(A)::value>, dim3(pmh_vec_grid(nl)), dim3(PMH_BLOCK), 0, ctx->stream, nl, (const double *)v, o); });
+    svr_row_out o{u, u + nl, diag, out, out + nl, 0.0, shift, msk};
+    svm_const<3>(diag ? 2 : (shift != 0.0 ? 1 : 0), [&](auto A) {
+      svm_const<2>(ym != nullptr, [&](auto S) { hipLaunchKernelGGL((k_svr_halves<decltype(A)::value, decltype(S)::value>), dim3(pmh_vec_grid(nl)), dim3(PMH_BLOCK), 0, ctx->stream, nl, (const double *)v, o); });
+    });
     PMH_HIP(hipGetLastError());
     return PMH_SUCCESS;
   }
@@ -296,6 +357,16 @@ extern "C" int pmh_op_svr_dual_set_diag(pmh_op op, const double *diag_dev)
   SvrDualBase *o;
   PMH_CHK(svr_base(op, "pmh_op_svr_dual_set_diag", &o));
   return pmh_op_svm_dual_set_diag(op, diag_dev);
+}
+// (the mask's rules and messages are pmh_svm_check_mask's, shared with pmh_op_svm_dual_set_subset; a refused mask changes nothing)
+extern "C" int pmh_op_svr_dual_set_subset(pmh_op op, const double *m_dev)
+{
+  SvrDualBase *o;
+  PMH_CHK(svr_base(op, "pmh_op_svr_dual_set_subset", &o));
+  long long ones  = 0;
+  int       first = 0;
+  if (m_dev) PMH_CHK(pmh_svm_check_mask(o->ctx, "pmh_op_svr_dual_set_subset", o->nl, m_dev, &ones, &first));
+  return o->take_mask(m_dev, ones, first);
 }
 extern "C" int pmh_op_svr_dual_passes(pmh_op op, long long *passes)
 {

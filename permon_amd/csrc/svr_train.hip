@@ -6,6 +6,9 @@
 // one pass over the test samples (svr_score_f), both on the kernel shells of svm_front.h, picked by sv_sweep: dense rows in fp64 or float32, d == 64, or CSR
 // (x_i . w by the entry-balanced row sweep of svm_csr.hip, then one thread per dot product).  Every sum leaves a workgroup through svm_store and is finished by
 // one workgroup in a fixed order.  Here: epsilon, the doubled right-hand side, the [1; -1] row, the metrics.
+// A sample subset S (pmh_svr_set_subset): the operator's H^_S (svr.hip), c^_S = [m o (t - eps); m o (-t - eps)], the row [m; -m] / sqrt(2 n_S); L2: the operator
+// restricts D to S itself (it masks its operand and writes +0 on the held-out rows), L1 keeps its bounds.  From u = 0 every iterate, gradient and direction of the
+// solvers is then exactly zero on the held-out rows in both halves, so the trained u, the multiplier, w, b and the counts are those of S alone.
 #include "svm_front.h"
 
 struct pmh_svr_s : sv_front { // (nu = 2 n: u = [p; q])
@@ -19,6 +22,8 @@ struct pmh_svr_s : sv_front { // (nu = 2 n: u = [p; q])
 // ---- the bias -------------------------------------------------------------------------------------------------------------------------------------------------
 // sample i with dot = x_i . w in s[0]: the sum over the free entries of t_i - eps - D_i p_i - dot (a free p_i) and t_i + eps + D_i q_i - dot (a free q_i), each
 // evaluated left to right; s[1]: sum (p_i - q_i); s[2]: free entries; s[3]: entries above astol.  free: astol < u_k and (ub > 0: u_k < ub - astol)
+// Under a subset the pass still visits every row, and relies on this: a held-out row has p_i = q_i = 0 after a training (above), so it adds +0 to s[1], is
+// counted in neither s[2] nor s[3], and its dot product -- whatever the row of X holds -- reaches no sum
 struct svr_bias_f {
   const double *t, *p, *q, *ubv, *dv; // ubv: the upper bound of sample i (per-sample penalties, L1) or nullptr: ub; dv: D_i (L2) or nullptr: dsc
   double        eps, astol, ub, dsc;  // ub <= 0: no upper bound (L2); dsc: the scalar D (L1: 0)
@@ -43,10 +48,11 @@ struct svr_bias_f {
 // ---- prediction and the metrics ---------------------------------------------------------------------------------------------------------------------------------
 // sample i with the score f = x_i . w + b: f -> scores (where given) and, with targets, r = f - t_i in the seven sums: sum r, sum r^2, sum |r|, -max |r|, sum t,
 // sum t^2, the count of |r| <= eps.  No __restrict__ on scores: the CSR form reads the dot products from the array the scores go to
-static __device__ __forceinline__ void svr_score_row(long long i, double f, double *scores, const double *__restrict__ t, double eps, double (&s)[SVR_NSUM])
+// sel (pmh_svr_test_own): the sums are taken over the selected samples only; every sample is still scored
+static __device__ __forceinline__ void svr_score_row(long long i, double f, double *scores, const double *__restrict__ t, double eps, svm_sel sel, double (&s)[SVR_NSUM])
 {
   if (scores) scores[i] = f;
-  if (t) {
+  if (t && (!sel.m || sel.m[i] == sel.want)) {
     const double ti = t[i], r = f - ti, ar = fabs(r);
     s[0] += r, s[1] += r * r, s[2] += ar, s[3] = fmin(s[3], -ar), s[4] += ti, s[5] += ti * ti, s[6] += ar <= eps ? 1.0 : 0.0;
   }
@@ -56,9 +62,10 @@ struct svr_score_f {
   double       *scores;
   const double *t;
   double        eps;
+  svm_sel       sel;
   double       *part;                                              // -> part[SVR_NSUM][gridDim.x]
   double        s[SVR_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // (-max |r| starts at -0: no sample, max 0)
-  __device__ __forceinline__ void row(long long i, double dot) { svr_score_row(i, dot + b, scores, t, eps, s); }
+  __device__ __forceinline__ void row(long long i, double dot) { svr_score_row(i, dot + b, scores, t, eps, sel, s); }
   __device__ __forceinline__ void done(double *red)
   {
     if (t) svm_store<SVR_NSUM, 3>(s, red, part); // (uniform: a kernel argument)
@@ -66,15 +73,13 @@ struct svr_score_f {
 };
 
 // ---- the vectors of the QP ------------------------------------------------------------------------------------------------------------------------------------
-// rhs = [t - eps; -t - eps]
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_fill_rhs(int n, const double *__restrict__ t, double eps, double *__restrict__ rhs)
+// rhs = [t - eps; -t - eps]; m given (a subset): +0 in both halves of a held-out sample
+__global__ __launch_bounds__(PMH_BLOCK) void k_svr_fill_rhs(int n, const double *__restrict__ t, double eps, const double *__restrict__ m, double *__restrict__ rhs)
 {
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) rhs[i] = t[i] - eps, rhs[n + i] = -t[i] - eps;
-}
-// row = c [1; -1]
-__global__ __launch_bounds__(PMH_BLOCK) void k_svr_fill_row(int n, double c, double *__restrict__ row)
-{
-  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) row[i] = c, row[n + i] = -c;
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    const bool in = !m || m[i] != 0.0;
+    rhs[i] = in ? t[i] - eps : 0.0, rhs[n + i] = in ? -t[i] - eps : 0.0;
+  }
 }
 // how many targets are not finite (a count: any order gives the same integer)
 __global__ __launch_bounds__(PMH_BLOCK) void k_svr_targets_bad(int n, const double *__restrict__ t, int *__restrict__ bad)
@@ -138,10 +143,12 @@ static int svr_refresh_l2(pmh_svr s)
 }
 static int svr_fill_rhs(pmh_svr s)
 {
-  if (s->n > 0) hipLaunchKernelGGL(k_svr_fill_rhs, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, s->t, s->epsilon, s->rhs);
+  if (s->n > 0) hipLaunchKernelGGL(k_svr_fill_rhs, dim3(pmh_vec_grid(s->n)), dim3(PMH_BLOCK), 0, s->ctx->stream, s->n, s->t, s->epsilon, (const double *)static_cast<SvmDualBase *>(s->H)->msk, s->rhs);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
+// the equality's row [1; -1] / sqrt(2 n) and its projector; under a subset [m; -m] / sqrt(2 n_S) (the operator's masked labels: sv_refresh_row)
+static int svr_refresh_row(pmh_svr s) { return sv_refresh_row(s, 1.0 / sqrt(2.0 * (double)sv_n_posed(s))); }
 static int svr_check_epsilon(const char *who, double eps)
 {
   if (!(eps >= 0.0) || !std::isfinite(eps)) return pmh_set_error(PMH_ERR_ARG, "%s: epsilon = %g, must be non-negative and finite", who, eps);
@@ -170,15 +177,7 @@ static int svr_create(pmh_ctx ctx, int n, int d, const void *X_dev, int f32, pmh
     if ((rc = svr_refresh_l2(s))) break;
     if ((rc = sv_alloc_common(s, SVR_NSUM, opts->C)) || (rc = svr_fill_rhs(s))) break;
     if ((rc = sv_count_samples(s, "pmh_svr_create"))) break; // (the row of the equality is [1; -1] / sqrt(2 n))
-    if (opts->bias) {
-      if ((rc = pmh_malloc(ctx, nb2, (void **)&s->row))) break;
-      if (n > 0) hipLaunchKernelGGL(k_svr_fill_row, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, 1.0 / sqrt(2.0 * (double)s->n_global), s->row);
-      if (hipGetLastError() != hipSuccess) {
-        rc = pmh_set_error(PMH_ERR_HIP, "pmh_svr_create: the launch that fills the equality's row failed");
-        break;
-      }
-      if ((rc = pmh_qppf_create_onerow(ctx, s->row, 2 * n, &s->pf))) break;
-    }
+    if (opts->bias && ((rc = pmh_malloc(ctx, nb2, (void **)&s->row)) || (rc = svr_refresh_row(s)))) break;
     if ((rc = sv_build_solver(s))) break;
   } while (0);
   if (rc) {
@@ -245,7 +244,7 @@ static int svr_model(pmh_svr s)
   const bool L1 = s->loss_type == PMH_SVM_LOSS_L1;
   double     h[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   svr_bias_f a{s->t, s->u, s->u + s->n, L1 ? s->Cv : nullptr, L1 ? nullptr : s->Cinv, s->epsilon, s->astol(), L1 ? s->C : 0.0, L1 ? 0.0 : 1.0 / s->C, s->part};
-  const int  rc = sv_model(s, "pmh_svr_train", a, sqrt(2.0 * (double)(s->n_global > 0 ? s->n_global : 1)), &s->st, h);
+  const int  rc = sv_model(s, "pmh_svr_train", a, sqrt(2.0 * (double)(sv_n_posed(s) > 0 ? sv_n_posed(s) : 1)), &s->st, h);
   s->st.sum_beta = h[1];
   return rc;
 }
@@ -288,18 +287,18 @@ extern "C" int pmh_svr_get_solver(pmh_svr s, pmh_op *H, pmh_qppf *pf, pmh_mpgp *
   return sv_get_solver(s, H, pf, mpgp, smalxe);
 }
 
-// X (dense rows, n x d: doubles, or floats where f32 -- the test samples' type, whatever the handle was trained on) or Xt (CSR); t != nullptr: the metrics
-static int svr_score(pmh_svr s, const char *who, int n, const void *X, int f32, pmh_csr Xt, double *scores, const double *t, pmh_svr_metrics *m)
+// own: the handle's own samples (X or, CSR, the operator's tables: Xt == nullptr); sel: which of them the sums are taken over, n_sel of this rank
+static int svr_score(pmh_svr s, const char *who, int n, const void *X, int f32, pmh_csr Xt, double *scores, const double *t, pmh_svr_metrics *m, bool own = false, svm_sel sel = svm_sel(), long long n_sel = -1)
 {
-  PMH_ARG(s && n >= 0 && (X || Xt || n == 0));
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || own));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "%s: call pmh_svr_train first", who);
-  PMH_CHK(pmh_svm_check_test_samples(who, s->d, Xt));
+  if (!own) PMH_CHK(pmh_svm_check_test_samples(who, s->d, Xt));
   pmh_ctx ctx = s->ctx;
   // (CSR: the dot products land where the scores go; without scores in a buffer of the call)
-  PMH_CHK(sv_sweep<true>(ctx, who, n, s->d, X, f32, Xt, nullptr, s->w, scores, svr_score_f{s->b, scores, t, s->epsilon, s->part}));
+  PMH_CHK(sv_sweep<true>(ctx, who, n, s->d, X, f32, Xt, own && s->Xcsr ? static_cast<SvmDualBase *>(s->H) : nullptr, s->w, scores, svr_score_f{s->b, scores, t, s->epsilon, sel, s->part}));
   if (!m) return PMH_SUCCESS;
   PMH_CHK(pmh_svm_finish_part(ctx, n, SVM_NB(n), SVR_NSUM, 3, s->part, s->scal));
-  double h[SVR_NSUM], ng = (double)n;
+  double h[SVR_NSUM], ng = (double)(n_sel >= 0 ? n_sel : n);
   PMH_CHK(pmh_memcpy_d2h(ctx, h, s->scal, sizeof(h)));
   PMH_CHK(pmh_comm_sum_host(ctx, &ng, 1));
   m->n = (long long)ng, m->sum_r = h[0], m->sum_r2 = h[1], m->sum_abs_r = h[2], m->max_abs = -h[3] + 0.0, m->sum_t = h[4], m->sum_t2 = h[5], m->n_in_tube = (long long)h[6];
@@ -329,4 +328,41 @@ extern "C" int pmh_svr_test_csr(pmh_svr s, pmh_csr Xt, const double *t_dev, pmh_
 {
   PMH_ARG(s && Xt && t_dev && m);
   return svr_score(s, "pmh_svr_test", Xt->nrows, nullptr, 0, Xt, nullptr, t_dev, m);
+}
+
+// ---- sample subsets, the handle's own rows ------------------------------------------------------------------------------------------------------------------------
+// Train on the subset S of the handle's samples, X staying where it is (the header of this file).  The solver is built anew as by pmh_svr_set_penalties: the
+// eigenvalue estimate must be H^_S's.  A refused mask leaves the handle exactly as it was: the operator checks it before anything changes
+extern "C" int pmh_svr_set_subset(pmh_svr s, const double *m_dev)
+{
+  PMH_ARG(s);
+  PMH_CHK(pmh_op_svr_dual_set_subset(s->H, m_dev));
+  s->trained = 0;
+  sv_drop_solver(s);
+  PMH_CHK(sv_count_subset(s));
+  PMH_CHK(svr_fill_rhs(s));
+  PMH_CHK(svr_refresh_row(s));
+  return sv_build_solver(s);
+}
+
+extern "C" int pmh_svr_get_subset(pmh_svr s, double *m_dev, long long *n_in)
+{
+  PMH_ARG(s);
+  return sv_get_subset(s, m_dev, n_in);
+}
+
+// the handle's own samples, nothing uploaded: the predict sweep over the X the handle was created on (CSR: the row sweep with the operator's tables)
+extern "C" int pmh_svr_predict_own(pmh_svr s, double *f_dev)
+{
+  PMH_ARG(s && f_dev);
+  return svr_score(s, "pmh_svr_predict_own", s->n, s->X, s->f32, nullptr, f_dev, nullptr, nullptr, true);
+}
+
+extern "C" int pmh_svr_test_own(pmh_svr s, int which, pmh_svr_metrics *m)
+{
+  PMH_ARG(s && m);
+  svm_sel sel;
+  PMH_CHK(sv_own_selector(s, "pmh_svr_test_own", "pmh_svr_set_subset", which, &sel));
+  const long long in = static_cast<SvmDualBase *>(s->H)->n_sub; // (of this rank; read only where a mask is set)
+  return svr_score(s, "pmh_svr_test_own", s->n, s->X, s->f32, nullptr, nullptr, s->t, m, true, sel, !sel.m ? s->n : (sel.want != 0.0 ? in : s->n - in));
 }

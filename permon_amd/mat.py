@@ -829,7 +829,24 @@ def MatCreateSVRDual(ctx, X, sample_dtype=None):
         check(ctx.L.pmh_op_svr_dual_set_diag(op.h, v.p if v is not None else None))
         op._diag = v
 
+    def set_subset(mask=None):
+        """H^_S = M^ H^ M^ + sigma e^ e^' with M^ = diag([m; m]), e^ = [m; -m] over the samples where mask is true (pmh_op_svr_dual_set_subset): n_local booleans or
+        0 / 1 numbers, copied by the operator; None: all samples.  Held-out rows of a product are exactly 0 in both halves and, in the dense kernels, not read;
+        held-out entries of the operand have no effect whatever they hold."""
+        if mask is None:
+            check(ctx.L.pmh_op_svr_dual_set_subset(op.h, None))
+            return
+        m = np.ascontiguousarray(mask, dtype=np.float64).ravel()
+        if m.size != n:
+            raise ValueError("set_subset: %d entries, the operator has %d samples" % (m.size, n))
+        v = Vec.from_numpy(ctx, m)
+        try:
+            check(ctx.L.pmh_op_svr_dual_set_subset(op.h, v.p))
+        finally:
+            v.free()
+
     op.passes = passes
     op.set_terms = set_terms
     op.set_diag = set_diag
+    op.set_subset = set_subset
     return op

@@ -647,21 +647,39 @@ def cross_validate(svm, k=5, seed=0, stratified=True):
     set_subset, train, test_own("held_out").  -> dict(folds: the k dicts of test_own, accuracy: their mean accuracy, masks).  The handle gets back the subset
     it had and is left untrained.  An SVMMulticlass handle is cross-validated the same way, the masks stratified over its K classes, and the result has
     confusion, the sum of the folds' K x K matrices, as well; a class of one sample leaves one fold's training set without it, and set_subset's PMH_ERR_ARG
-    comes through (the subset is still restored)."""
+    comes through (the subset is still restored).
+    An SVR handle is cross-validated the same way.  Its targets are continuous, so `stratified` does not apply to it: the masks are kfold(t, k, seed,
+    stratified=False) whatever is passed.  -> dict(folds: the k dicts of test_own, masks, and the metrics pooled over the k held-out sets by pooled_metrics: mse,
+    mae, r2, n from the folds' summed sum_r2, sum_abs_r, sum_t, sum_t2, n; max_abs: the maximum over the folds)."""
     svm._need()
     before = svm.subset
     y = svm._keep[1].to_numpy()
-    masks = kfold(y, k, seed, stratified)
+    regression = svm._who == "SVR"
+    masks = kfold(y, k, seed, stratified and not regression)
     folds = []
     try:
         for m in masks:
             folds.append(svm.set_subset(m).train().test_own("held_out"))
     finally:
         svm.set_subset(before)
+    if regression:
+        return dict(folds=folds, masks=masks, **pooled_metrics(folds))
     out = dict(folds=folds, accuracy=float(np.mean([f["accuracy"] for f in folds])), masks=masks)
     if isinstance(svm, SVMMulticlass):
         out["confusion"] = sum(f["confusion"] for f in folds)
     return out
+
+
+def pooled_metrics(folds):
+    """The regression metrics over the union of the folds' samples from the sums SVR.test / test_own return: dict(n, mse = sum_r2 / n, mae = sum_abs_r / n,
+    r2 = 1 - sum_r2 / (sum_t2 - sum_t^2 / n), max_abs = the largest of the folds'), each sum added over the folds in their order.  nan where n is 0, r2 also
+    where the pooled targets are constant.  Host arithmetic."""
+    tot = {key: sum(f[key] for f in folds) for key in ("sum_r2", "sum_abs_r", "sum_t", "sum_t2", "n")}
+    n = int(tot["n"])
+    nan = float("nan")
+    sst = tot["sum_t2"] - tot["sum_t"] ** 2 / n if n else 0.0
+    return dict(n=n, mse=tot["sum_r2"] / n if n else nan, mae=tot["sum_abs_r"] / n if n else nan, r2=1.0 - tot["sum_r2"] / sst if n and sst > 0.0 else nan,
+                max_abs=max((f["max_abs"] for f in folds), default=0.0))
 
 
 SCORES = ("accuracy", "precision", "recall", "specificity", "f1", "balanced_accuracy", "mcc")

@@ -6,7 +6,9 @@
     bias: additionally sum (p_i - q_i) = 0 (SMALXE over a one-row projector; without bias MPGP alone)
 
 Model: w = X'(p - q), f(x) = x . w + b.  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width, kept ONCE on the device.  Everything is
-computed by libpermonhip.so; there is no CPU fallback.  Not here: subsets, cross-validation, warm starts, a grid search (SVM has them)."""
+computed by libpermonhip.so; there is no CPU fallback.  set_subset trains on a part of the handle's samples with X staying where it is, predict_own / test_own
+score the handle's own rows without an upload, and permon_amd.svm.cross_validate loops the three over k folds.  Not here: warm starts, a grid search (SVM has
+them)."""
 import ctypes as ct
 
 import numpy as np
@@ -72,6 +74,41 @@ class SVR(_SVMHandle):
         check(self.L.pmh_svr_set_epsilon(self.h, float(epsilon)))
         self.opts.epsilon = float(epsilon)
         return self
+
+    def set_subset(self, mask):
+        """Train on the samples where mask is true, X staying on the device (pmh_svr_set_subset): n booleans or 0 / 1 numbers; None: all samples again.  The
+        handle is untrained afterwards; set_epsilon and set_penalties keep the subset.  After train() alpha is 0 on the held-out samples in both halves and the
+        model is that of a fit on (X[mask], t[mask]); predict_own / test_own score the held-out samples without an upload."""
+        self._need()
+        if mask is None:
+            check(self.L.pmh_svr_set_subset(self.h, None))
+            return self
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ and not (np.issubdtype(m.dtype, np.integer) or np.issubdtype(m.dtype, np.floating)):
+            raise ValueError("SVR: the mask must hold booleans or 0 / 1 numbers, not %s" % m.dtype)
+        m = np.ascontiguousarray(m, dtype=np.float64).ravel()
+        if m.size != self.n:
+            raise ValueError("SVR: the mask must have %d entries" % self.n)
+        with self._lent(m) as md:
+            check(self.L.pmh_svr_set_subset(self.h, md.p))
+        return self
+
+    @property
+    def subset(self):
+        """The training mask as n booleans (pmh_svr_get_subset), or None where all samples train."""
+        self._need()
+        with _vecs(self.ctx, self.n) as (v,):
+            check(self.L.pmh_svr_get_subset(self.h, v.p, None))
+            m = v.to_numpy() != 0.0
+        return None if m.all() else m
+
+    @property
+    def n_subset(self):
+        """The samples the problem is posed over (pmh_svr_get_subset): the subset's, or all."""
+        self._need()
+        k = ct.c_longlong()
+        check(self.L.pmh_svr_get_subset(self.h, None, ct.byref(k)))
+        return int(k.value)
 
     def train(self):
         """Train from u = 0 (pmh_svr_train)."""
@@ -153,4 +190,23 @@ class SVR(_SVMHandle):
                 check(self._entry("test", S.sparse, S.f32)(self.h, *xa, td.p, ct.byref(m)))
             finally:
                 td.free()
+        return {k: getattr(m, k) for k, _ in _lib.SvrMetrics._fields_}
+
+    def predict_own(self):
+        """(n,): f(x_i) of the samples the handle was created on, held-out ones included, without an upload (pmh_svr_predict_own): bit for bit predict(X)."""
+        self._need()
+        with _vecs(self.ctx, self.n) as (f,):
+            check(self.L.pmh_svr_predict_own(self.h, f.p))
+            return f.to_numpy()
+
+    OWN = {"held_out": 0, "subset": 1, "all": 2}  # PMH_SVM_OWN_*
+
+    def test_own(self, which="held_out"):
+        """The metrics of the handle's own samples against its targets over the held-out samples, the subset or all of them (pmh_svr_test_own), nothing
+        uploaded: the dict test returns; n is the number of selected samples."""
+        self._need()
+        if which not in self.OWN:
+            raise ValueError("SVR: which must be one of %s" % ", ".join(sorted(self.OWN)))
+        m = _lib.SvrMetrics()
+        check(self.L.pmh_svr_test_own(self.h, self.OWN[which], ct.byref(m)))
         return {k: getattr(m, k) for k, _ in _lib.SvrMetrics._fields_}
