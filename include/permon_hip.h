@@ -1209,7 +1209,15 @@ int pmh_mpgp_test_spec_words(pmh_mpgp s, int words[5]);
  * pmh_op_penalized_test_mult_epi2: pmh_op_penalized_test_mult_epi with every operand: kind 0, 1 (P1: x = p, y = Ap, operands g, xx, lb, ub; block partials in rows
  * 4..6) or 2 (gradient split: operands b, lb, ub, astol; rows 0..3), in_slot 0 (the chain forms G0 x itself), 1 / 2 (the iterate's / the direction's target holds
  * it).  partials_*_host [8][2048]: in, the block partials on the device / in the pinned copy before; out, afterwards.  *nblocks: blocks the last kernel wrote;
- * *replayed: 1 where the last kernel ran alone. */
+ * *replayed: 1 where the last kernel ran alone.  An operator that is not on the chain is taken with in_slot = 0 and same_input = 0 (else PMH_ERR_SUP): its product
+ * with the vector phase in its last kernel as a caller without a pinned copy gets it (device rows only, *nblocks = the workgroups of the streaming grid);
+ * PMH_ERR_SUP where the product has no such kernel as it is configured.
+ * pmh_op_penalized_test_form: *form = the product the next application takes under the current knobs: 0 the one-row equality folded into the SVM operator, 1 the
+ * dual-space chain, 2 the one-launch projector (k_gt_fused1d), 3 the 10-launch form (k_gt_fused / k_gt_fused1), 4 the 12-launch form with the dense (G G')^-1
+ * (k_gt_dual1), 5 the plain sequence.
+ * pmh_op_penalized_test_aux_normG: T G0 u -> Gu (device, m doubles) and its squared norm -> scalar slot `slot`, armed = 0 by the projector's own two launches, armed = 1
+ * as a request riding on the product y = A x (*served = 1 where the product took it; x, y device vectors).  scal[2]: in, what the device slot and its pinned mirror
+ * hold before; out, afterwards.  Synchronises. */
 int pmh_op_test_create_staged(pmh_csr gather, pmh_csr middle, pmh_csr scatter, pmh_op *op);
 int pmh_op_penalized_test_chain_info(pmh_op op, long long info[10]);
 int pmh_op_penalized_test_chain_read(pmh_op op, int what, int cap, double *host, int *len);
@@ -1217,6 +1225,8 @@ int pmh_op_penalized_test_norm_target(pmh_op op, double *Gu, int slot, const dou
 int pmh_op_penalized_test_mult_epi2(pmh_op op, int kind, int same_input, int in_slot, const double *x, const double *b, const double *g, const double *xx, const double *lb,
                                     const double *ub, double astol, double *y, double *gf, double *p, double *partials_dev_host, double *partials_pinned_host, int *nblocks,
                                     int *replayed);
+int pmh_op_penalized_test_form(pmh_op op, int *form);
+int pmh_op_penalized_test_aux_normG(pmh_op op, int armed, const double *u, double *Gu, int slot, const double *x, double *y, double scal[2], int *served);
 /* ---- 3x3-block product test entries (csrc/bsr.hip: the conversion as the V-cycle and K^+ call it, and one launch of k_bsr3; nothing inside the solvers changes) ----
  * pmh_bsr3_test_create: the 3x3-block device copy of the square CSR A with entries kept in `storage` (0 fp64, 1 fp32, 2 fp16 scaled by a power of two, fp32
  * arithmetic), tiles of `tile` blocks (512; any other value: 1024) and nrep_hint congruent diagonal blocks (believed only after an entry-by-entry comparison).

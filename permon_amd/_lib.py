@@ -421,6 +421,8 @@ _PROTOS = {
     "pmh_op_penalized_test_chain_read": [vp, C.c_int, C.c_int, vp, c_int_p],
     "pmh_op_penalized_test_norm_target": [vp, vp, C.c_int, vp, c_int_p],
     "pmh_op_penalized_test_mult_epi2": [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, c_int_p, c_int_p],
+    "pmh_op_penalized_test_form": [vp, c_int_p],
+    "pmh_op_penalized_test_aux_normG": [vp, C.c_int, vp, vp, C.c_int, vp, vp, c_double_p, c_int_p],
     "pmh_bsr3_test_create": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
     "pmh_bsr3_test_info": [vp, C.POINTER(C.c_longlong), c_double_p],
     "pmh_bsr3_test_mult_epi": [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int],

@@ -16,8 +16,16 @@
 // Round 4 took 9 launches + a finalising one for the same product (k_spmv_long_part, k_gt_fused1d<0>, k_spmv_ell, GEMM, fin, k_spmv_stream, k_spmv_long_part,
 // k_gt_fused1d<EPI>, k_finalize): at 5-9 us each they were a quarter of the one-GPU step and what bounded the share of one of eight GPUs.
 // Determinism: every sum has a fixed order (lane-strided in segment order -> wave tree -> waves in order); no atomics anywhere.
+//
+// Shared pieces.  Device: the vector phase of k_dc_final is pmh_p1_terms_v / pmh_split_terms (box_inline.h) and write_partials<K, true> (reduce.h), as in
+// mpgp.hip and qppf.hip; "coarse share -> LDS -> wave 0 adds the waves' shares" (k_dc_norm, twice in k_dc_gather, k_dc_final) and the slot-row products stay
+// written out in each kernel: behind device functions the compiler gave k_dc_final, k_dc_gather and k_dc_norm other register counts and, in one instantiation,
+// scratch where there was none (docs/LAB_NOTEBOOK.md).  Host: dc_dispatch is the one choice of (W, NU) for k_dc_norm, k_dc_gather and k_dc_final, dc_emit_args
+// the one fill of pmh_emit_args, dc_launch_emit the one launch of k_dc_emit; what a launch means for the record (x_emitted, norm_done, norm_ptr, kept_x,
+// launches) is written where each caller decides it.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "dualchain.h"
 #include "emit_inline.h"
@@ -288,7 +296,7 @@ __global__ __launch_bounds__(PMH_EMIT_TILE) void k_dc_final(int n, const double 
     }
     __syncthreads();
   }
-  double pv = 0.0, s0 = 0.0, s1 = 0.0, mn = INFINITY, acc[4] = {0.0, 0.0, 0.0, 0.0};
+  double pv = 0.0, s[3] = {0.0, 0.0, INFINITY}, acc[4] = {0.0, 0.0, 0.0, 0.0};
   if (r < n) {
     double sumc = 0.0, sume = 0.0;
 #pragma unroll
@@ -296,34 +304,21 @@ __global__ __launch_bounds__(PMH_EMIT_TILE) void k_dc_final(int n, const double 
     const double tt  = wr + -1.0 * sume;
     const double out = sumc * rho + tt;
     if (EPI != PMH_VEPI_GRAD_SPLIT) y[r] = out;
-    if (EPI == PMH_VEPI_P1) { // k_p1_dots (mpgp.hip): p'Ap, g'p, QPCFeas -- out is Ap[r], pin the operator's input p
-      s0 += pi * out;
-      s1 += gq * pi;
-      mn = pmh_box_feas_v(mn, xq, pi, lq, uq);
-    }
+    if (EPI == PMH_VEPI_P1) pmh_p1_terms_v(s, pi, out, gq, xq, lq, uq); // k_p1_dots (mpgp.hip): p'Ap, g'p, QPCFeas -- out is Ap[r], pin the operator's input p
     if (EPI == PMH_VEPI_GRAD_SPLIT) { // g = A x - b, the gradient split, p = gf, the partials of (0, |gP|^2, |gc|^2, |gf|^2) -- pin is the iterate
       double gi = out;
       gi += -1.0 * bq;
-      y[r] = gi;
-      double f, cc;
-      pmh_box_split(pi, gi, epi.lb, epi.ub, r, epi.astol, f, cc);
-      epi.gf[r]        = f;
-      epi.p[r]         = f;
-      pv               = f;
-      const double gPi = f + cc;
-      acc[1] += gPi * gPi;
-      acc[2] += cc * cc;
-      acc[3] += f * f;
+      y[r]      = gi;
+      pv        = pmh_split_terms(acc, pi, gi, epi.lb, epi.ub, r, epi.astol);
+      epi.gf[r] = pv;
+      epi.p[r]  = pv;
     }
   }
-  if (EPI == PMH_VEPI_P1) {
-    const double q[3]  = {s0, s1, mn};
-    const int    op[3] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN};
-    pmh_block_partials<3>(q, op, epi.partials + (size_t)epi.prow * epi.ld, epi.h_partials ? epi.h_partials + (size_t)epi.prow * epi.ld : nullptr, epi.ld);
-  }
+  // the block partials go to the epilogue's rows on the device and, where the caller hosts them, in the pinned copy
+  double *const rows = epi.partials + (size_t)epi.prow * epi.ld, *const hrows = epi.h_partials ? epi.h_partials + (size_t)epi.prow * epi.ld : nullptr;
+  if (EPI == PMH_VEPI_P1) write_partials<3, true>(s, {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN}, nullptr, rows, epi.ld, hrows);
   if (EPI == PMH_VEPI_GRAD_SPLIT) {
-    const int op[4] = {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM, PMH_RED_SUM};
-    pmh_block_partials<4>(acc, op, epi.partials + (size_t)epi.prow * epi.ld, epi.h_partials ? epi.h_partials + (size_t)epi.prow * epi.ld : nullptr, epi.ld);
+    write_partials<4, true>(acc, nullptr, rows, epi.ld, hrows);
     pmh_emit_tail(ea, R, 0.0, pv);
   }
 }
@@ -535,8 +530,20 @@ void pmh_dc_destroy(pmh_dualchain dc)
   delete dc;
 }
 
-// loads per lane of pmh_coarse_share: 64 NU >= the number of tiles.  The three dispatches below and the info entry share it
+// loads per lane of pmh_coarse_share: 64 NU >= the number of tiles.  dc_dispatch and the info entry share it
 static int dc_nu(pmh_dualchain dc) { return dc->nwg <= 128 ? 2 : 8; }
+
+// The one choice among the kernels' instantiations: f(W, NU) with the slots per row of the G0' copy (8 / 16) and the loads per lane (2 / 8) as integral constants
+template <int V> using dc_int = std::integral_constant<int, V>;
+template <typename F>
+static void dc_dispatch(pmh_dualchain dc, F f)
+{
+  const bool w8 = dc->W == 8, nu2 = dc_nu(dc) == 2;
+  if (w8 && nu2) f(dc_int<8>(), dc_int<2>());
+  else if (w8) f(dc_int<8>(), dc_int<8>());
+  else if (nu2) f(dc_int<16>(), dc_int<2>());
+  else f(dc_int<16>(), dc_int<8>());
+}
 
 static pmh_emit_tab dc_tab(pmh_dualchain dc)
 {
@@ -545,16 +552,26 @@ static pmh_emit_tab dc_tab(pmh_dualchain dc)
   return t;
 }
 
+// the emission arguments of a kernel whose segment sums go to part0 (target 0) and part1 (target 1); nullptr: that target is off
+static pmh_emit_args dc_emit_args(pmh_dualchain dc, double *part0, double *part1)
+{
+  pmh_emit_args ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.tab = dc_tab(dc), ea.o[0].part = part0, ea.o[1].part = part1;
+  return ea;
+}
+
+// k_dc_emit: the segment sums of G0 x -> part (what the caller's record says about x and part is the caller's to update)
+static void dc_launch_emit(pmh_dualchain dc, const double *x, double *part)
+{
+  hipLaunchKernelGGL(k_dc_emit, dim3((unsigned)dc->nwg), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc->n, x, dc_emit_args(dc, part, nullptr));
+}
+
 int pmh_dc_emit_begin(pmh_dualchain dc, const double *x, const double *p, pmh_emit_args *ea)
 {
-  memset(ea, 0, sizeof(*ea));
-  ea->tab = dc_tab(dc);
+  *ea = dc_emit_args(dc, x ? dc->part[0] : nullptr, p ? dc->part[1] : nullptr);
   if ((x && x == dc->kept_x) || (p && p == dc->kept_x)) dc->kept_x = nullptr; // a kernel is about to write that vector
-  if (x) {
-    ea->o[0].part = dc->part[0];
-    dc->x_emitted = x, dc->norm_done = false, dc->norm_ptr = nullptr;
-  }
-  if (p) ea->o[1].part = dc->part[1];
+  if (x) dc->x_emitted = x, dc->norm_done = false, dc->norm_ptr = nullptr;
   return PMH_SUCCESS;
 }
 
@@ -578,14 +595,10 @@ bool pmh_dc_norm_ready(pmh_dualchain dc, const double *u)
   if (!dc || !dc->normGu) return false;
   if (dc->norm_ptr == u) return true;
   if (dc->x_emitted == u && !dc->norm_done) {
-    if (dc_nu(dc) == 2)
-      hipLaunchKernelGGL(k_dc_norm<2>, dim3(1), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc_tab(dc), (const double *)dc->part[0], (const double *)dc->pf->d_Tt,
-                         dc->normGu, dc->ctx->d_scal + dc->norm_slot,
-                         dc->ctx->h_scal + dc->norm_slot);
-    else
-      hipLaunchKernelGGL(k_dc_norm<8>, dim3(1), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc_tab(dc), (const double *)dc->part[0], (const double *)dc->pf->d_Tt,
-                         dc->normGu, dc->ctx->d_scal + dc->norm_slot,
-                         dc->ctx->h_scal + dc->norm_slot);
+    dc_dispatch(dc, [&](auto, auto NU) {
+      hipLaunchKernelGGL(k_dc_norm<decltype(NU)::value>, dim3(1), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc_tab(dc), (const double *)dc->part[0], (const double *)dc->pf->d_Tt, dc->normGu,
+                         dc->ctx->d_scal + dc->norm_slot, dc->ctx->h_scal + dc->norm_slot);
+    });
     if (hipGetLastError() != hipSuccess) return false;
     dc->norm_done = true, dc->norm_ptr = u;
     return true;
@@ -602,11 +615,8 @@ static int dc_last_stage(pmh_dualchain dc, const double *x, double *y, double rh
   const int   n = dc->n;
   const dim3  vgrid((unsigned)dc->nwg), eblk(PMH_EMIT_TILE);
   const int   kind = epi ? epi->kind : 0;
-  const pmh_emit_tab tab = dc_tab(dc);
-  pmh_emit_args      ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.tab = tab;
-  pmh_vec_epi e;
+  pmh_emit_args ea = dc_emit_args(dc, nullptr, nullptr);
+  pmh_vec_epi   e;
   memset(&e, 0, sizeof(e));
   if (epi) e = *epi;
   e.h_partials = nullptr;
@@ -615,21 +625,12 @@ static int dc_last_stage(pmh_dualchain dc, const double *x, double *y, double rh
     ea.o[1].part    = dc->part[1];
     *epi->emitted_p = 1;
   }
-#define DC_FINAL(EPI, WW, NU)                                                                                                                                                        \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dc_final<EPI, WW, NU>), vgrid, eblk, 0, st, n, (const double *)dc->d_ev, (const unsigned char *)dc->d_ec, tab, (const double *)dc->pf->d_S, \
-                     (const double *)dc->c_cur, (const double *)dc->w, rho, y, e, x, ea)
-#define DC_FINAL_W(EPI)                                                                                                                                                              \
-  do {                                                                                                                                                                               \
-    if (dc->W == 8 && dc_nu(dc) == 2) DC_FINAL(EPI, 8, 2);                                                                                                                              \
-    else if (dc->W == 8) DC_FINAL(EPI, 8, 8);                                                                                                                                        \
-    else if (dc_nu(dc) == 2) DC_FINAL(EPI, 16, 2);                                                                                                                                      \
-    else DC_FINAL(EPI, 16, 8);                                                                                                                                                       \
-  } while (0)
-  if (kind == PMH_VEPI_P1) DC_FINAL_W(PMH_VEPI_P1);
-  else if (kind == PMH_VEPI_GRAD_SPLIT) DC_FINAL_W(PMH_VEPI_GRAD_SPLIT);
-  else DC_FINAL_W(0);
-#undef DC_FINAL_W
-#undef DC_FINAL
+  dc_dispatch(dc, [&](auto W, auto NU) {
+    constexpr int w = decltype(W)::value, nu = decltype(NU)::value;
+    auto kern = kind == PMH_VEPI_P1 ? k_dc_final<PMH_VEPI_P1, w, nu> : kind == PMH_VEPI_GRAD_SPLIT ? k_dc_final<PMH_VEPI_GRAD_SPLIT, w, nu> : k_dc_final<0, w, nu>;
+    hipLaunchKernelGGL(kern, vgrid, eblk, 0, st, n, (const double *)dc->d_ev, (const unsigned char *)dc->d_ec, ea.tab, (const double *)dc->pf->d_S, (const double *)dc->c_cur, (const double *)dc->w, rho, y,
+                       e, x, ea);
+  });
   dc->launches++;
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
@@ -650,11 +651,8 @@ int pmh_dc_apply(pmh_dualchain dc, const double *x, double *y, double rho, const
   int slot = (epi && epi->in_slot > 0) ? epi->in_slot - 1 : -1;
   if (slot < 0) {
     slot = (kind == PMH_VEPI_GRAD_SPLIT) ? 0 : (kind == PMH_VEPI_P1 ? 1 : 2);
-    pmh_emit_args ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.tab = tab, ea.o[0].part = dc->part[slot];
     if (slot == 0) dc->x_emitted = x, dc->norm_done = false, dc->norm_ptr = nullptr;
-    hipLaunchKernelGGL(k_dc_emit, vgrid, eblk, 0, st, n, x, ea);
+    dc_launch_emit(dc, x, dc->part[slot]);
     dc->launches++;
   }
   // 2. gather with the projection folded in
@@ -671,29 +669,20 @@ int pmh_dc_apply(pmh_dualchain dc, const double *x, double *y, double rho, const
       dc->norm_done = true, dc->norm_ptr = dc->x_emitted;
     }
     const dim3 ggrid((unsigned)(std::max(1, (dc->nlist + PMH_EMIT_TILE - 1) / PMH_EMIT_TILE) + (na.part ? 1 : 0))); // + the workgroup that forms ||B u||
-#define DC_GATHER(WW, NU)                                                                                                                                                                       \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dc_gather<WW, NU>), ggrid, eblk, 0, st, dc->nlist, (const int *)dc->d_reci, (const double *)dc->d_recd, (const int *)Bg->d_col, (const double *)Bg->d_val, \
-                     (const double *)dc->d_ev, (const unsigned char *)dc->d_ec, tab, (const double *)dc->part[slot], (const double *)dc->pf->d_S, dc->c_cur, na, x, dc->mid_in)
-    if (dc->W == 8 && dc_nu(dc) == 2) DC_GATHER(8, 2);
-    else if (dc->W == 8) DC_GATHER(8, 8);
-    else if (dc_nu(dc) == 2) DC_GATHER(16, 2);
-    else DC_GATHER(16, 8);
-#undef DC_GATHER
+    dc_dispatch(dc, [&](auto W, auto NU) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dc_gather<decltype(W)::value, decltype(NU)::value>), ggrid, eblk, 0, st, dc->nlist, (const int *)dc->d_reci, (const double *)dc->d_recd,
+                         (const int *)Bg->d_col, (const double *)Bg->d_val, (const double *)dc->d_ev, (const unsigned char *)dc->d_ec, tab, (const double *)dc->part[slot],
+                         (const double *)dc->pf->d_S, dc->c_cur, na, x, dc->mid_in);
+    });
     dc->launches++;
   }
   PMH_HIP(hipGetLastError());
   // 3. the middle stage
   PMH_CHK(dc->F->mid_apply());
   // 4. scatter + the segment sums of G0 w
-  {
-    pmh_emit_args ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.tab = tab, ea.o[0].part = dc->w + n;
-    hipLaunchKernelGGL(k_dc_scatter, vgrid, eblk, 0, st, n, (const unsigned char *)dc->d_scnt, (const int *)dc->d_sc2, (const double *)dc->d_sv2,
-                       (const int *)Bs->d_rowptr, (const int *)Bs->d_col,
-                       (const double *)Bs->d_val, dc->mid_out, dc->w, ea);
-    dc->launches++;
-  }
+  hipLaunchKernelGGL(k_dc_scatter, vgrid, eblk, 0, st, n, (const unsigned char *)dc->d_scnt, (const int *)dc->d_sc2, (const double *)dc->d_sv2, (const int *)Bs->d_rowptr, (const int *)Bs->d_col,
+                     (const double *)Bs->d_val, dc->mid_out, dc->w, dc_emit_args(dc, dc->w + n, nullptr));
+  dc->launches++;
   PMH_HIP(hipGetLastError());
   // the ranks' shares of B u and of the sums of G0 (B u) in one exchange (PetscSFReduce, gluing.c:144-147)
   PMH_CHK(pmh_comm_allreduce_sum(ctx, dc->w, (size_t)n + (size_t)dc->nseg));
@@ -734,11 +723,8 @@ int pmh_dc_replay(pmh_dualchain dc, const double *x, double *y, double rho, cons
   // what the skipped launches would have left for others.  The gradient split of an iterate nobody emitted: the segment sums of G0 x in target 0 (SMALXE's
   // ||B u|| forms from them: k_dc_norm, or the next gather).  A plain product: nothing but y
   if (kind == PMH_VEPI_GRAD_SPLIT && !(epi->in_slot > 0)) {
-    pmh_emit_args ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.tab = dc_tab(dc), ea.o[0].part = dc->part[0];
     dc->x_emitted = x, dc->norm_done = false, dc->norm_ptr = nullptr;
-    hipLaunchKernelGGL(k_dc_emit, dim3((unsigned)dc->nwg), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc->n, x, ea);
+    dc_launch_emit(dc, x, dc->part[0]);
     dc->launches++;
   }
   PMH_CHK(dc_last_stage(dc, x, y, rho, epi));
@@ -751,8 +737,8 @@ int pmh_dc_replay(pmh_dualchain dc, const double *x, double *y, double rho, cons
 int pmh_dc_test_emit(pmh_dualchain dc, const double *x)
 {
   pmh_emit_args ea;
-  PMH_CHK(pmh_dc_emit_begin(dc, x, nullptr, &ea));
-  hipLaunchKernelGGL(k_dc_emit, dim3((unsigned)dc->nwg), dim3(PMH_EMIT_TILE), 0, dc->ctx->stream, dc->n, x, ea);
+  PMH_CHK(pmh_dc_emit_begin(dc, x, nullptr, &ea)); // (the record updates of an emitting kernel)
+  dc_launch_emit(dc, x, ea.o[0].part);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }

@@ -120,24 +120,8 @@ struct pmh_mpgp_s {
 // --------------------------------------------------------------------------------------------------------------------
 // device helpers: the box predicates of qpcbox.c restated per element
 // --------------------------------------------------------------------------------------------------------------------
-// (the box predicates pmh_box_split / pmh_box_reduced: box_inline.h)
-template <int K, bool EMIT = false>
-__device__ __forceinline__ void write_partials(double (&v)[K], double *lds, double *__restrict__ partials, int ld, double *__restrict__ h_partials = nullptr)
-{
-  // 1024-thread workgroups; the rows also go to the pinned host copy: the host adds the block sums after its next wait (host_sums), no finalising launch
-  if (EMIT) {
-    int op[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) op[k] = PMH_RED_SUM;
-    pmh_block_partials<K>(v, op, partials, h_partials, ld);
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    double r = pmh_block_reduce<PMH_RED_SUM>(v[k], lds);
-    if (threadIdx.x == 0) partials[(size_t)k * ld + blockIdx.x] = r;
-  }
-}
+// (the box predicates pmh_box_split / pmh_box_reduced / pmh_box_feas and the per-entry terms of the two vector phases, pmh_p1_terms / pmh_split_terms:
+// box_inline.h; a workgroup's accumulators to its row of block partials, write_partials: reduce.h)
 
 // gradient split + norms (+ p = gf): after the initial gradient and after an expansion step
 // (MPGPGrads mpgp.c:198-223 + VecCopy(gf,p) :507/:615 + the three reductions of :514-521)
@@ -150,15 +134,10 @@ __global__ VEC_BOUNDS void k_split_setp(long long n, const double *__restrict__ 
   if (EMIT) pmh_emit_prefetch(ea, R);
   VEC_ENTRIES(i, n)
   {
-    double f, c;
-    pmh_box_split(x[i], g[i], lb, ub, i, astol, f, c);
-    gf[i]      = f;
-    p[i]       = f;
-    pv     = f;
-    double gPi = f + c; // VecWAXPY(gP,1,gf,gc)
-    acc[1] += gPi * gPi;
-    acc[2] += c * c;
-    acc[3] += f * f;
+    const double f = pmh_split_terms(acc, x[i], g[i], lb, ub, i, astol);
+    gf[i]          = f;
+    p[i]           = f;
+    pv             = f;
   }
   write_partials<4, EMIT>(acc, lds, partials, ld, h_partials);
   if (EMIT) pmh_emit_tail(ea, R, zv, pv); // the segment sums of G0 p for the p = gf just written
@@ -228,7 +207,7 @@ __global__ VEC_BOUNDS void k_step_update(long long n, const double *__restrict__
     gf[i] = f;
     if (SETP) p[i] = f;
     xv = xi, pv = f;
-    double gPi = f + c;
+    double gPi = f + c; // (pmh_split_terms written out: through the helper three instantiations take two more registers)
     acc[0] += api * f;
     acc[1] += gPi * gPi;
     acc[2] += c * c;
@@ -294,29 +273,9 @@ __global__ VEC_BOUNDS void k_expansion_std(long long n, double afeas, double alp
 __global__ __launch_bounds__(PMH_BLOCK) void k_p1_dots(long long n, const double *__restrict__ p, const double *__restrict__ Ap, const double *__restrict__ g, const double *__restrict__ x, const double *__restrict__ lb, const double *__restrict__ ub, double *__restrict__ partials, int ld)
 {
   __shared__ double lds[PMH_BLOCK / 64];
-  double            s0 = 0.0, s1 = 0.0, m = INFINITY;
-  GRID_STRIDE(i, n)
-  {
-    double pi = p[i];
-    s0 += pi * Ap[i];
-    s1 += g[i] * pi;
-    if (pi > 0. && lb) {
-      double l = lb[i];
-      if (l > -INFINITY) m = fmin(m, (x[i] - l) / pi);
-    }
-    if (pi < 0. && ub) {
-      double u = ub[i];
-      if (u < INFINITY) m = fmin(m, (x[i] - u) / pi);
-    }
-  }
-  s0 = pmh_block_reduce<PMH_RED_SUM>(s0, lds);
-  s1 = pmh_block_reduce<PMH_RED_SUM>(s1, lds);
-  m  = pmh_block_reduce<PMH_RED_MIN>(m, lds);
-  if (threadIdx.x == 0) {
-    partials[blockIdx.x]          = s0;
-    partials[ld + blockIdx.x]     = s1;
-    partials[2 * ld + blockIdx.x] = m;
-  }
+  double            s[3] = {0.0, 0.0, INFINITY};
+  GRID_STRIDE(i, n) pmh_p1_terms(s, p[i], Ap[i], g[i], x, lb, ub, i);
+  write_partials<3>(s, {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN}, lds, partials, ld);
 }
 
 // three squared norms in one pass (unfused driver: VecNorm(gP), VecDot(gc,gc), VecDot(gf,gf) mpgp.c:514-521)

@@ -298,6 +298,10 @@ int pmh_mpgp_set_pre_p1_hook(pmh_mpgp s, int (*f)(void *), void *user);
 // SMALXE's ||B u|| riding on the next product of the penalised operator (qppf.hip): G0 u shares the pass over G0 with G0 x, T (G0 u) and its squared norm are
 // finished by workgroup 0 of the projector's kernel -- two launches less per inner iteration, the same bits as pmh_qppf_apply_G_norm2
 int pmh_op_penalized_arm_aux_normG(pmh_op op, const double *u, double *Gu, int slot);
+// the form a product of the penalised operator takes (qppf.hip PenalizedOp::form; pmh_op_penalized_test_form reports it): the one-row equality folded into the SVM
+// operator, the five-launch chain, the one-launch projector (k_gt_fused1d), the 10-launch form (k_gt_fused / k_gt_fused1), the 12-launch form with the dense
+// (G G')^{-1} (k_gt_dual1), the plain sequence of matpenalized.c
+enum { PMH_PEN_FOLD = 0, PMH_PEN_CHAIN = 1, PMH_PEN_ONE_LAUNCH = 2, PMH_PEN_TEN_LAUNCH = 3, PMH_PEN_DENSE_INVERSE = 4, PMH_PEN_PLAIN = 5 };
 int pmh_op_penalized_take_aux_done(pmh_op op);
 // the five-launch chain (dualchain.hip): ||T G0 u||^2 of every emitted iterate -> Gu, scalar slot
 int pmh_op_penalized_set_normG_target(pmh_op op, double *Gu, int slot);

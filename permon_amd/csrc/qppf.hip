@@ -7,6 +7,12 @@
 // path on the transposed CSR.  The coarse problem (GG')^{-1} is small and dense: GG' is assembled and
 // inverted on the host once (the reference's QPPFSetUpGGt_Private / -qppf_explicit_inv path, qppf.c:213-333)
 // and applied as a dense GEMV, redundantly on every GPU (mirrors -qppf_redundancy, qppf.c:182,305).
+//
+// Shared pieces.  The projector kernels k_gt_fused / k_gt_fused1 / k_gt_dual1 / k_gt_fused1d are built from gt_row_sum (a row of G' left to right, 16 loads in
+// flight, one or two coarse vectors), gt_chunk_sum (a long row's chunk sums in order) and gt_epilogue (mode 0 / mode 1), all in this file.  The MPGP vector phase
+// folded into k_gt_fused1d is pmh_p1_terms / pmh_split_terms (box_inline.h) and write_partials (reduce.h), the same functions k_p1_dots and k_split_setp
+// (mpgp.hip) are made of: that is why its block partials are theirs (tests/test_gpu_projector_paths.py).  Which product of the penalised operator applies is
+// PenalizedOp::form() (PMH_PEN_* of pmh_internal.h); mult, mult_epi and mult_same_input switch on it.
 #include <chrono>
 
 #include "pmh_internal.h"
@@ -399,6 +405,57 @@ extern "C" int pmh_qppf_apply_halfQ_transpose(pmh_qppf pf, const double *x, doub
 // and the epilogue arithmetic is the unfused sequence term by term, so the result is bit-identical to the separate calls:
 //   mode 0:  s = (G'w)_r;  y_r = s;  z_r = (-1) s + x_r                      (Q x, and P x = x - Q x: VecWAXPY)
 //   mode 1:  s = (G'w)_r;  t = x_r + (-1) s;  y_r = y_r rho + t              (VecAYPX, VecScale, VecAXPY of matpenalized.c:12-22)
+// The pieces the kernels below share.  gt_epilogue: the two epilogues above for row r with sum s = (G'w)_r; mode 1 returns the new y_r and stores it where STORE.
+template <bool STORE = true>
+static __device__ __forceinline__ double gt_epilogue(int mode, int r, double sum, const double *__restrict__ x, double *__restrict__ y, double *__restrict__ z, double rho)
+{
+  if (mode == 0) {
+    y[r] = sum;
+    z[r] = -1.0 * sum + x[r];
+    return 0.0;
+  }
+  const double t   = x[r] + -1.0 * sum;
+  const double out = y[r] * rho + t;
+  if (STORE) y[r] = out;
+  return out;
+}
+// gt_row_sum: entries [k0, k1) of a CSR row against NV coarse vectors that share the loads of the row, each sum left to right as the plain loop, the loads of 16
+// entries in flight together (G0' has 6 or 12 entries per row: one trip)
+template <int NV>
+static __device__ __forceinline__ void gt_row_sum(int k0, int k1, const int *__restrict__ col, const double *__restrict__ val, const double *w0, const double *w1, double (&s)[NV])
+{
+  for (int k = k0; k < k1; k += 16) {
+    double v[16];
+    int    c[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const bool in = k + j < k1;
+      v[j] = in ? val[k + j] : 0.0, c[j] = in ? col[k + j] : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < 16; j++)
+      if (k + j < k1) {
+        s[0] += v[j] * w0[c[j]];
+        if (NV == 2) s[NV - 1] += v[j] * w1[c[j]];
+      }
+  }
+}
+// gt_chunk_sum: the chunk sums of long row t (k_spmv_long_part) added in chunk order, 8 loads in flight
+static __device__ __forceinline__ double gt_chunk_sum(const int *__restrict__ lrow, const double *__restrict__ part, int t)
+{
+  const int c0 = lrow[t], c1 = lrow[t + 1];
+  double    sum = 0.0;
+  for (int c = c0; c < c1; c += 8) {
+    double v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = (c + j < c1) ? part[c + j] : 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      if (c + j < c1) sum += v[j];
+  }
+  return sum;
+}
+
 __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ w, int mode,
                                                        const double *__restrict__ x, double *__restrict__ y, double *__restrict__ z, double rho)
 {
@@ -411,15 +468,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused(int n, const int *__rest
   }
 #pragma unroll
   for (int o = 4; o > 0; o >>= 1) sum += __shfl_down(sum, o, 8);
-  if (r < n && lane == 0) {
-    if (mode == 0) {
-      y[r] = sum;
-      z[r] = -1.0 * sum + x[r];
-    } else {
-      const double t = x[r] + -1.0 * sum;
-      y[r]           = y[r] * rho + t;
-    }
-  }
+  if (r < n && lane == 0) gt_epilogue(mode, r, sum, x, y, z, rho);
 }
 
 // the same for short rows (the one-lane-per-row case of the stream kernel: a row is summed left to right by one thread), e.g. the <= 12
@@ -429,27 +478,9 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused1(int n, const int *__res
 {
   const int r = blockIdx.x * PMH_BLOCK + threadIdx.x;
   if (r >= n) return;
-  const int k0 = rowptr[r], k1 = rowptr[r + 1];
-  double    sum = 0.0;
-  for (int k = k0; k < k1; k += 16) { // left to right as the plain loop, the loads of 16 entries in flight together
-    double v[16];
-    int    c[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      const bool in = k + j < k1;
-      v[j] = in ? val[k + j] : 0.0, c[j] = in ? col[k + j] : 0;
-    }
-#pragma unroll
-    for (int j = 0; j < 16; j++)
-      if (k + j < k1) sum += v[j] * w[c[j]];
-  }
-  if (mode == 0) {
-    y[r] = sum;
-    z[r] = -1.0 * sum + x[r];
-  } else {
-    const double t = x[r] + -1.0 * sum;
-    y[r]           = y[r] * rho + t;
-  }
+  double s[1] = {0.0};
+  gt_row_sum<1>(rowptr[r], rowptr[r + 1], col, val, w, nullptr, s);
+  gt_epilogue(mode, r, s[0], x, y, z, rho);
 }
 
 // G not orthonormalised (the dense (G G')^{-1} of QPPFSetUp, qppf.c:213-278): the penalty term rho G'G x and the projector's G'(GG')^{-1}G x are two
@@ -459,22 +490,10 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_dual1(int n, const int *__rest
 {
   const int r = blockIdx.x * PMH_BLOCK + threadIdx.x;
   if (r >= n) return;
-  const int k0 = rowptr[r], k1 = rowptr[r + 1];
-  double    s0 = 0.0, s1 = 0.0;
-  for (int k = k0; k < k1; k += 16) {
-    double v[16];
-    int    c[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      const bool in = k + j < k1;
-      v[j] = in ? val[k + j] : 0.0, c[j] = in ? col[k + j] : 0;
-    }
-#pragma unroll
-    for (int j = 0; j < 16; j++)
-      if (k + j < k1) s0 += v[j] * t0[c[j]], s1 += v[j] * w[c[j]];
-  }
-  y[r] = s0;
-  z[r] = -1.0 * s1 + x[r];
+  double s[2] = {0.0, 0.0};
+  gt_row_sum<2>(rowptr[r], rowptr[r + 1], col, val, t0, w, s);
+  y[r] = s[0];
+  z[r] = -1.0 * s[1] + x[r];
 }
 
 // ... and with the finishing step of G0 v and the dense T'T product folded in (implicit orthonormalisation, m <= 64): every workgroup adds the chunk sums of
@@ -504,19 +523,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused1d(int n, const int *__re
   const int r  = blockIdx.x * PMH_BLOCK + t;
   int       k0 = 0, k1 = 0;
   if (r < n) k0 = rowptr[r], k1 = rowptr[r + 1];
-  if (t < m) {
-    const int c0 = lrow[t], c1 = lrow[t + 1];
-    double    sum = 0.0;
-    for (int c = c0; c < c1; c += 8) {
-      double v[8];
-#pragma unroll
-      for (int j = 0; j < 8; j++) v[j] = (c + j < c1) ? part[c + j] : 0.0;
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        if (c + j < c1) sum += v[j];
-    }
-    t0[t] = sum;
-  }
+  if (t < m) t0[t] = gt_chunk_sum(lrow, part, t);
 #pragma unroll
   for (int e = 0; e < 16; e++)
     if (t + PMH_BLOCK * e < mm) Ms[t + PMH_BLOCK * e] = mreg[e];
@@ -529,19 +536,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused1d(int n, const int *__re
   __syncthreads();
   if (aux.part2 && blockIdx.x == 0) { // uniform per workgroup.  k_rows_then_dense(m, lrow, part2, Mt2, y2, norm): same sums, same order
     __shared__ double t2[64], red2[PMH_BLOCK / 64];
-    if (t < m) {
-      const int c0 = lrow[t], c1 = lrow[t + 1];
-      double    sum = 0.0;
-      for (int c = c0; c < c1; c += 8) {
-        double v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = (c + j < c1) ? aux.part2[c + j] : 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-          if (c + j < c1) sum += v[j];
-      }
-      t2[t] = sum;
-    }
+    if (t < m) t2[t] = gt_chunk_sum(lrow, aux.part2, t);
     __syncthreads();
     double sq = 0.0;
     if (t < m) {
@@ -560,56 +555,17 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused1d(int n, const int *__re
     sq = pmh_block_reduce<PMH_RED_SUM>(sq, red2);
     if (t == 0) *aux.norm_d = sq, *aux.norm_h = sq;
   }
-  double sum = 0.0;
+  double sum[1] = {0.0}, out = 0.0;
   if (r < n) {
-    for (int k = k0; k < k1; k += 16) { // G0' has 6 or 12 entries per row: one trip
-      double v[16];
-      int    c[16];
-#pragma unroll
-      for (int j = 0; j < 16; j++) {
-        const bool in = k + j < k1;
-        v[j] = in ? val[k + j] : 0.0, c[j] = in ? col[k + j] : 0;
-      }
-#pragma unroll
-      for (int j = 0; j < 16; j++)
-        if (k + j < k1) sum += v[j] * w[c[j]];
-    }
+    gt_row_sum<1>(k0, k1, col, val, w, nullptr, sum);
+    out = gt_epilogue<EPI != PMH_VEPI_GRAD_SPLIT>(mode, r, sum[0], x, y, z, rho);
   }
-  double out = 0.0;
-  if (r < n) {
-    if (mode == 0) {
-      y[r] = sum;
-      z[r] = -1.0 * sum + x[r];
-    } else {
-      const double tt = x[r] + -1.0 * sum;
-      out             = y[r] * rho + tt;
-      if (EPI != PMH_VEPI_GRAD_SPLIT) y[r] = out;
-    }
-  }
+  double *const rows = epi.partials + (size_t)epi.prow * epi.ld; // this epilogue's rows of the block partials
   if (EPI == PMH_VEPI_P1) { // k_p1_dots (mpgp.hip) on this workgroup's rows: p'Ap, g'p, QPCFeas -- `out` is Ap[r], pin the operator's input p
     __shared__ double redp[PMH_BLOCK / 64];
-    double            s0 = 0.0, s1 = 0.0, mn = INFINITY;
-    if (r < n) {
-      const double pi = pin[r];
-      s0 += pi * out;
-      s1 += epi.g[r] * pi;
-      if (pi > 0. && epi.lb) {
-        const double l = epi.lb[r];
-        if (l > -INFINITY) mn = fmin(mn, (epi.xx[r] - l) / pi);
-      }
-      if (pi < 0. && epi.ub) {
-        const double u = epi.ub[r];
-        if (u < INFINITY) mn = fmin(mn, (epi.xx[r] - u) / pi);
-      }
-    }
-    s0 = pmh_block_reduce<PMH_RED_SUM>(s0, redp);
-    s1 = pmh_block_reduce<PMH_RED_SUM>(s1, redp);
-    mn = pmh_block_reduce<PMH_RED_MIN>(mn, redp);
-    if (t == 0) {
-      epi.partials[(size_t)epi.prow * epi.ld + blockIdx.x]       = s0;
-      epi.partials[(size_t)(epi.prow + 1) * epi.ld + blockIdx.x] = s1;
-      epi.partials[(size_t)(epi.prow + 2) * epi.ld + blockIdx.x] = mn;
-    }
+    double            s[3] = {0.0, 0.0, INFINITY};
+    if (r < n) pmh_p1_terms(s, pin[r], out, epi.g[r], epi.xx, epi.lb, epi.ub, r);
+    write_partials<3>(s, {PMH_RED_SUM, PMH_RED_SUM, PMH_RED_MIN}, redp, rows, epi.ld);
   }
   // k_axpy(g, -1, b) + k_split_setp (mpgp.hip): g = A x - b, gf, p = gf, the partials of (0, |gP|^2, |gc|^2, |gf|^2) -- pin is the iterate
   if (EPI == PMH_VEPI_GRAD_SPLIT) {
@@ -618,21 +574,12 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_gt_fused1d(int n, const int *__re
     if (r < n) {
       double gi = out;
       gi += -1.0 * epi.b[r];
-      y[r] = gi;
-      double f, c;
-      pmh_box_split(pin[r], gi, epi.lb, epi.ub, r, epi.astol, f, c);
-      epi.gf[r]        = f;
-      epi.p[r]         = f;
-      const double gPi = f + c;
-      acc[1] += gPi * gPi;
-      acc[2] += c * c;
-      acc[3] += f * f;
+      y[r]           = gi;
+      const double f = pmh_split_terms(acc, pin[r], gi, epi.lb, epi.ub, r, epi.astol);
+      epi.gf[r]      = f;
+      epi.p[r]       = f;
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const double rr = pmh_block_reduce<PMH_RED_SUM>(acc[k], redg);
-      if (t == 0) epi.partials[(size_t)(epi.prow + k) * epi.ld + blockIdx.x] = rr;
-    }
+    write_partials<4>(acc, redg, rows, epi.ld);
   }
 }
 
@@ -766,12 +713,18 @@ struct PenalizedOp : pmh_op_s {
   pmh_dualchain dc = nullptr;
   int           dc_state = -1; // -1 not asked yet, 0 does not apply, 1 live
   int           chain_allowed = 1; // pmh_set_knob("chain") as it stood when the operator was created
+  // the inner operator where it is P . P with this very projector (the forms below fold the two projections into the penalty term's pass), else null
+  ProjectedOp *projected()
+  {
+    ProjectedOp *pa = dynamic_cast<ProjectedOp *>(A);
+    return pa && pa->pf == pf && pa->symmetric ? pa : nullptr;
+  }
   pmh_dualchain chain()
   {
     if (dc_state < 0) {
       dc_state        = 0;
-      ProjectedOp *pa = dynamic_cast<ProjectedOp *>(A);
-      if (chain_allowed && !pf->onerow && pa && pa->pf == pf && pa->symmetric && pmh_dc_create(pf, pa->A, &dc) == PMH_SUCCESS && dc) {
+      ProjectedOp *pa = projected();
+      if (chain_allowed && !pf->onerow && pa && pmh_dc_create(pf, pa->A, &dc) == PMH_SUCCESS && dc) {
         dc_state = 1;
         if (norm_Gu) (void)pmh_dc_set_norm_target(dc, norm_Gu, norm_slot);
       }
@@ -815,12 +768,21 @@ struct PenalizedOp : pmh_op_s {
   {
     if (dc) pmh_dc_invalidate(dc, keep_applied);
   }
-  // the fully fused product y = rho Q x + P F (P x) [+ vector epilogue] of the one-launch projector form
-  bool fused_dense()
+  // the one-launch projector form applies (asked on its own by pmh_op_penalized_arm_aux_normG, which must not set the chain up)
+  bool one_launch() { return projected() && gt_fusable(pf) && q_fused_dense(pf); }
+  // Which product the knobs and the operands allow (PMH_PEN_*): asked at every product, because gt_fusion, vec_epi and svm_pairing may change between two products
+  // of one operator; only the fold's and the chain's own probes are kept
+  int form()
   {
-    ProjectedOp *pa = dynamic_cast<ProjectedOp *>(A);
-    return pa && pa->pf == pf && pa->symmetric && gt_fusable(pf) && q_fused_dense(pf);
+    if (fold()) return PMH_PEN_FOLD;
+    if (chain()) return PMH_PEN_CHAIN;
+    if (projected()) {
+      if (gt_fusable(pf)) return q_fused_dense(pf) ? PMH_PEN_ONE_LAUNCH : PMH_PEN_TEN_LAUNCH;
+      if (gt_fusable_dense_inverse(pf)) return PMH_PEN_DENSE_INVERSE;
+    }
+    return PMH_PEN_PLAIN;
   }
+  // y = rho Q x + P F (P x) [+ vector epilogue]: 10 launches (see k_gt_fused), one launch per projector where q_fused folds it (PMH_PEN_ONE_LAUNCH)
   int mult_fused_dense(const double *x, double *y, const pmh_vec_epi *epi)
   {
     ProjectedOp *pa = static_cast<ProjectedOp *>(A);
@@ -831,15 +793,65 @@ struct PenalizedOp : pmh_op_s {
     PMH_CHK(pa->A->mult(pa->w1, pa->w2));
     return q_fused(pf, pa->w2, 1, pa->w2, y, nullptr, rho, nullptr, nullptr, -1, epi, x); // y = rho y + (w2 - Q w2) (+ the vector phase)
   }
+  // y = rho G'G x + P F P x, P = I - G'(GG')^{-1}G: G x once for both terms, one pass over G' for G'(G x) and x - G'(GG')^{-1}(G x), the second
+  // projector with the penalty update in its epilogue -- 12 launches instead of 19, the same bits as the plain sequence
+  int mult_dense_inverse(const double *x, double *y)
+  {
+    ProjectedOp  *pa = static_cast<ProjectedOp *>(A);
+    const pmh_csr Gt = pf->G->transpose;
+    const dim3    grid((Gt->nrows + PMH_BLOCK - 1) / PMH_BLOCK);
+    PMH_CHK(pmh_csr_mult(pf->G, x, pf->G_left));
+    PMH_CHK(pmh_qppf_apply_CP(pf, pf->G_left, pf->Gt_right));
+    hipLaunchKernelGGL(k_gt_dual1, grid, dim3(PMH_BLOCK), 0, ctx->stream, Gt->nrows, (const int *)Gt->d_rowptr, (const int *)Gt->d_col, (const double *)Gt->d_val, (const double *)pf->G_left,
+                       (const double *)pf->Gt_right, x, y, pa->w1);
+    PMH_HIP(hipGetLastError());
+    PMH_CHK(pa->A->mult(pa->w1, pa->w2));
+    PMH_CHK(pmh_csr_mult(pf->G, pa->w2, pf->G_left));
+    PMH_CHK(pmh_qppf_apply_CP(pf, pf->G_left, pf->Gt_right));
+    hipLaunchKernelGGL(k_gt_fused1, grid, dim3(PMH_BLOCK), 0, ctx->stream, Gt->nrows, (const int *)Gt->d_rowptr, (const int *)Gt->d_col, (const double *)Gt->d_val, (const double *)pf->Gt_right, 1,
+                       (const double *)pa->w2, y, (double *)nullptr, rho);
+    PMH_HIP(hipGetLastError());
+    return PMH_SUCCESS;
+  }
+  // MatMult_Penalized matpenalized.c:12-22: y = BtB x; y *= rho; y = y + A x
+  int mult_plain(const double *x, double *y)
+  {
+    ProjectedOp *pa = projected();
+    PMH_CHK(pmh_qppf_apply_GtG(pf, x, y));
+    if (pa && pf->orthonormal) {
+      PMH_CHK(pa->mult_with_Qx(x, y, t)); // y currently holds Q x: reuse it before scaling
+    } else {
+      PMH_CHK(A->mult(x, t));
+    }
+    PMH_CHK(pmh_vec_scale(ctx, n, y, rho));
+    return pmh_vec_axpy(ctx, n, y, 1.0, t);
+  }
+  int mult(const double *x, double *y) override
+  {
+    const int f = form();
+    if (f != PMH_PEN_FOLD && f != PMH_PEN_CHAIN && f != PMH_PEN_ONE_LAUNCH) aux_u = nullptr; // a ||G u|| request rides on the fold's pass or the one-launch form only
+    switch (f) {
+    case PMH_PEN_FOLD: return fold_apply(x, y, nullptr);
+    case PMH_PEN_CHAIN: return pmh_dc_apply(dc, x, y, rho, nullptr);
+    case PMH_PEN_ONE_LAUNCH:
+    case PMH_PEN_TEN_LAUNCH: return mult_fused_dense(x, y, nullptr);
+    case PMH_PEN_DENSE_INVERSE: return mult_dense_inverse(x, y);
+    default: return mult_plain(x, y);
+    }
+  }
+  // The vector phase in the product's last kernel, or PMH_EPI_UNSUPPORTED: the caller then runs the separate vector kernels behind the plain product.
+  // (The chain leaves its block partials per 1024-entry tile for the HOST to sum: a caller that finalises on the device -- row-distributed scalars, e.hosted == NULL --
+  // counts on one partial per workgroup of the streaming Vec kernels' grid.  The one-launch form gives exactly that where the grid is one row per thread.)
   int mult_epi(const double *x, double *y, const pmh_vec_epi &e) override
   {
-    // (the chain leaves its block partials per 1024-entry tile for the HOST to sum: a caller that finalises on the device -- row-distributed scalars, e.hosted == NULL --
-    // counts on one partial per workgroup of the streaming Vec kernels' grid, so it gets the separate vector kernels behind the chain's plain product instead)
-    if (fold()) return pmh_knobs().vec_epi ? fold_apply(x, y, &e) : PMH_EPI_UNSUPPORTED;
-    if (chain()) return !e.hosted ? PMH_EPI_UNSUPPORTED : (e.same_input ? pmh_dc_replay(dc, x, y, rho, &e, e.replayed) : pmh_dc_apply(dc, x, y, rho, &e));
-    if (!pmh_knobs().vec_epi) return PMH_EPI_UNSUPPORTED; // A/B: the separate vector kernels
-    if (!fused_dense() || n > PMH_MAX_VEC_BLOCKS * PMH_BLOCK || pmh_vec_grid(n) != (n + PMH_BLOCK - 1) / PMH_BLOCK) return PMH_EPI_UNSUPPORTED;
-    return mult_fused_dense(x, y, &e);
+    switch (form()) {
+    case PMH_PEN_FOLD: return pmh_knobs().vec_epi ? fold_apply(x, y, &e) : PMH_EPI_UNSUPPORTED;
+    case PMH_PEN_CHAIN: return !e.hosted ? PMH_EPI_UNSUPPORTED : (e.same_input ? pmh_dc_replay(dc, x, y, rho, &e, e.replayed) : pmh_dc_apply(dc, x, y, rho, &e));
+    case PMH_PEN_ONE_LAUNCH:
+      if (!pmh_knobs().vec_epi || n > PMH_MAX_VEC_BLOCKS * PMH_BLOCK || pmh_vec_grid(n) != (n + PMH_BLOCK - 1) / PMH_BLOCK) return PMH_EPI_UNSUPPORTED;
+      return mult_fused_dense(x, y, &e);
+    default: return PMH_EPI_UNSUPPORTED;
+    }
   }
   ~PenalizedOp() override
   {
@@ -847,53 +859,10 @@ struct PenalizedOp : pmh_op_s {
     pmh_free(ctx, t);
     if (xwork) pmh_free(ctx, xwork);
   }
-  // only the chain has anything to gain from the caller's assertion (it keeps the intermediates that do not depend on rho); the folded SVM form, the fused-dense
-  // form, the 10- and 12-launch forms and CSR operators multiply as ever
+  // only the chain has anything to gain from the caller's assertion (it keeps the intermediates that do not depend on rho)
   int mult_same_input(const double *x, double *y, int *replayed = nullptr) override
   {
-    if (!fold() && chain()) return pmh_dc_replay(dc, x, y, rho, nullptr, replayed);
-    return mult(x, y);
-  }
-  // MatMult_Penalized matpenalized.c:12-22: y = BtB x; y *= rho; y = y + A x
-  int mult(const double *x, double *y) override
-  {
-    if (fold()) return fold_apply(x, y, nullptr);
-    ProjectedOp *pa = dynamic_cast<ProjectedOp *>(A);
-    if (chain()) return pmh_dc_apply(dc, x, y, rho, nullptr);
-    if (fused_dense()) return mult_fused_dense(x, y, nullptr);
-    aux_u = nullptr; // a ||G u|| request can only ride on the one-launch form
-    if (pa && pa->pf == pf && pa->symmetric && gt_fusable(pf)) {
-      // A = P F P with the same orthonormal projector: y = rho Q x + P F (P x) in 10 launches (see k_gt_fused)
-      PMH_CHK(q_fused(pf, x, 0, x, y, pa->w1, 0.0)); // y = Q x, w1 = P x
-      PMH_CHK(pa->A->mult(pa->w1, pa->w2));
-      return q_fused(pf, pa->w2, 1, pa->w2, y, nullptr, rho); // y = rho y + (w2 - Q w2)
-    }
-    if (pa && pa->pf == pf && pa->symmetric && gt_fusable_dense_inverse(pf)) {
-      // y = rho G'G x + P F P x, P = I - G'(GG')^{-1}G: G x once for both terms, one pass over G' for G'(G x) and x - G'(GG')^{-1}(G x), the second
-      // projector with the penalty update in its epilogue -- 12 launches instead of 19, the same bits as the sequence below
-      const pmh_csr Gt = pf->G->transpose;
-      const dim3    grid((Gt->nrows + PMH_BLOCK - 1) / PMH_BLOCK);
-      PMH_CHK(pmh_csr_mult(pf->G, x, pf->G_left));
-      PMH_CHK(pmh_qppf_apply_CP(pf, pf->G_left, pf->Gt_right));
-      hipLaunchKernelGGL(k_gt_dual1, grid, dim3(PMH_BLOCK), 0, ctx->stream, Gt->nrows, (const int *)Gt->d_rowptr, (const int *)Gt->d_col, (const double *)Gt->d_val, (const double *)pf->G_left,
-                         (const double *)pf->Gt_right, x, y, pa->w1);
-      PMH_HIP(hipGetLastError());
-      PMH_CHK(pa->A->mult(pa->w1, pa->w2));
-      PMH_CHK(pmh_csr_mult(pf->G, pa->w2, pf->G_left));
-      PMH_CHK(pmh_qppf_apply_CP(pf, pf->G_left, pf->Gt_right));
-      hipLaunchKernelGGL(k_gt_fused1, grid, dim3(PMH_BLOCK), 0, ctx->stream, Gt->nrows, (const int *)Gt->d_rowptr, (const int *)Gt->d_col, (const double *)Gt->d_val, (const double *)pf->Gt_right, 1,
-                         (const double *)pa->w2, y, (double *)nullptr, rho);
-      PMH_HIP(hipGetLastError());
-      return PMH_SUCCESS;
-    }
-    PMH_CHK(pmh_qppf_apply_GtG(pf, x, y));
-    if (pa && pa->pf == pf && pa->symmetric && pf->orthonormal) {
-      PMH_CHK(pa->mult_with_Qx(x, y, t)); // y currently holds Q x: reuse it before scaling
-    } else {
-      PMH_CHK(A->mult(x, t));
-    }
-    PMH_CHK(pmh_vec_scale(ctx, n, y, rho));
-    return pmh_vec_axpy(ctx, n, y, 1.0, t);
+    return form() == PMH_PEN_CHAIN ? pmh_dc_replay(dc, x, y, rho, nullptr, replayed) : mult(x, y);
   }
   // MatMultTranspose_Penalized matpenalized.c:26-36: y = BtB x; y *= rho; y = y + A' x
   int mult_transpose(const double *x, double *y) override
@@ -960,7 +929,7 @@ int pmh_op_penalized_arm_aux_normG(pmh_op op, const double *u, double *Gu, int s
     o->aux_u = u, o->aux_Gu = Gu, o->aux_slot = slot;
     return PMH_SUCCESS;
   }
-  if (o->dc || !o->fused_dense()) return PMH_SUCCESS; // not armed: the caller's own launches follow
+  if (o->dc || !o->one_launch()) return PMH_SUCCESS; // not armed: the caller's own launches follow
   o->aux_u = u, o->aux_Gu = Gu, o->aux_slot = slot;
   return PMH_SUCCESS;
 }
@@ -1033,7 +1002,8 @@ extern "C" int pmh_op_penalized_test_mult_epi2(pmh_op op, int kind, int same_inp
   PMH_ARG(kind != PMH_VEPI_P1 || (g && xx));
   PMH_ARG(kind != PMH_VEPI_GRAD_SPLIT || (b && gf && p));
   PMH_ARG(kind != 0 || in_slot == 0); // (a plain product always forms its own sums)
-  if (!o->chain()) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_mult_epi2: the operator does not run on the dual-space chain");
+  const bool chained = o->chain() != nullptr;
+  if (!chained && (in_slot || same_input)) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_mult_epi2: the operator does not run on the dual-space chain");
   pmh_ctx      ctx    = o->ctx;
   const size_t pbytes = sizeof(double) * PMH_MAX_RED * (size_t)ctx->partials_cap;
   PMH_CHK(pmh_sync(ctx));
@@ -1048,13 +1018,51 @@ extern "C" int pmh_op_penalized_test_mult_epi2(pmh_op op, int kind, int same_inp
     int hosted = 0, p_emitted = 0;
     e.kind = kind, e.b = b, e.g = g, e.xx = xx, e.lb = lb, e.ub = ub, e.astol = astol, e.gf = gf, e.p = p, e.partials = ctx->d_partials, e.ld = ctx->partials_cap;
     e.prow = kind == PMH_VEPI_P1 ? 4 : 0; // as f_apply_p1 / f_gradient_split (mpgp.hip) place them
-    e.hosted = &hosted, e.emitted_p = &p_emitted, e.same_input = same_input, e.in_slot = in_slot, e.replayed = replayed;
-    PMH_CHK(o->mult_epi(x, y, e));
-    *nblocks = hosted;
+    if (chained) {
+      e.hosted = &hosted, e.emitted_p = &p_emitted, e.same_input = same_input, e.in_slot = in_slot, e.replayed = replayed;
+      PMH_CHK(o->mult_epi(x, y, e));
+      *nblocks = hosted;
+    } else { // device rows only, one partial per workgroup of the streaming grid
+      const int rc = o->mult_epi(x, y, e);
+      if (rc == PMH_EPI_UNSUPPORTED) return pmh_set_error(PMH_ERR_SUP, "pmh_op_penalized_test_mult_epi2: the operator's product has no vector epilogue as it is configured");
+      PMH_CHK(rc);
+      *nblocks = pmh_vec_grid(o->n);
+    }
   }
   PMH_CHK(pmh_sync(ctx));
   PMH_CHK(pmh_memcpy_d2h(ctx, partials_dev_host, ctx->d_partials, pbytes));
   memcpy(partials_pinned_host, ctx->h_partials, pbytes);
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_op_penalized_test_form(pmh_op op, int *form)
+{
+  PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
+  PMH_ARG(o && form);
+  *form = o->form();
+  return PMH_SUCCESS;
+}
+
+// ||G u||^2 as SMALXE asks for it: armed = 0, the two launches of pmh_qppf_apply_G_norm2; armed = 1, the request riding on the product y = A x (include/permon_hip.h)
+extern "C" int pmh_op_penalized_test_aux_normG(pmh_op op, int armed, const double *u, double *Gu, int slot, const double *x, double *y, double scal[2], int *served)
+{
+  PenalizedOp *o = dynamic_cast<PenalizedOp *>(op);
+  PMH_ARG(o && u && Gu && slot >= 0 && slot < PMH_NSCAL && scal && served && (!armed || (x && y)));
+  pmh_ctx ctx = o->ctx;
+  PMH_CHK(pmh_sync(ctx));
+  PMH_CHK(pmh_memcpy_h2d(ctx, ctx->d_scal + slot, &scal[0], sizeof(double)));
+  ctx->h_scal[slot] = scal[1];
+  *served           = 0;
+  if (armed) {
+    PMH_CHK(pmh_op_penalized_arm_aux_normG(op, u, Gu, slot));
+    PMH_CHK(o->mult(x, y));
+    *served = pmh_op_penalized_take_aux_done(op);
+  } else {
+    PMH_CHK(pmh_qppf_apply_G_norm2(o->pf, u, Gu, slot));
+  }
+  PMH_CHK(pmh_sync(ctx));
+  PMH_CHK(pmh_memcpy_d2h(ctx, &scal[0], ctx->d_scal + slot, sizeof(double)));
+  scal[1] = ctx->h_scal[slot];
   return PMH_SUCCESS;
 }
 

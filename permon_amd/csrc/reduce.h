@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pmh_internal.h"
+#include "emit_inline.h" // pmh_block_partials: the 1024-thread form of write_partials
 
 __device__ __forceinline__ double pmh_wave_sum(double v)
 {
@@ -37,4 +38,30 @@ __device__ __forceinline__ double pmh_block_reduce(double v, double *lds)
     v = r;
   }
   return v;
+}
+
+// A workgroup's K accumulators -> row k of the block partials, partials[k ld + blockIdx.x], row k reduced with op[k] (pmh_finalize_partials or the host adds the
+// blocks).  256-thread workgroups: pmh_block_reduce per row, thread 0 stores.  EMIT: the 1024-thread workgroups of emit_inline.h, the rows also to the pinned
+// host copy where there is one (the host adds the block sums after its next wait, no finalising launch).
+template <int K, bool EMIT = false>
+__device__ __forceinline__ void write_partials(const double (&v)[K], const int (&op)[K], double *lds, double *__restrict__ partials, int ld, double *__restrict__ h_partials = nullptr)
+{
+  if (EMIT) {
+    pmh_block_partials<K>(v, op, partials, h_partials, ld);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    const double r = (op[k] == PMH_RED_SUM) ? pmh_block_reduce<PMH_RED_SUM>(v[k], lds) : pmh_block_reduce<PMH_RED_MIN>(v[k], lds);
+    if (threadIdx.x == 0) partials[(size_t)k * ld + blockIdx.x] = r;
+  }
+}
+// ... K sums
+template <int K, bool EMIT = false>
+__device__ __forceinline__ void write_partials(const double (&v)[K], double *lds, double *__restrict__ partials, int ld, double *__restrict__ h_partials = nullptr)
+{
+  int op[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) op[k] = PMH_RED_SUM;
+  write_partials<K, EMIT>(v, op, lds, partials, ld, h_partials);
 }

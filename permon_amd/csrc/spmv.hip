@@ -23,6 +23,7 @@
 
 #include "pmh_internal.h"
 #include "reduce.h"
+#include "box_inline.h"
 
 #define PMH_MAX_ROWS_PER_BLOCK 1024 // bounds the per-row phase when rows are (nearly) empty, e.g. B' of MATGLUING
 #define PMH_STREAM_NNZB 1024        // entries per row block (LDS tile) of the STREAM plan ...
@@ -61,14 +62,7 @@ __device__ __forceinline__ void epi_row(int r, double sum, const double *__restr
     double p = xin[r];
     s0 += p * sum;
     s1 += ldg<NT>(&a.g[r]) * p;
-    if (p > 0. && a.lb) {
-      double l = ldg<NT>(&a.lb[r]);
-      if (l > -INFINITY) m = fmin(m, (ldg<NT>(&a.xx[r]) - l) / p);
-    }
-    if (p < 0. && a.ub) {
-      double u = ldg<NT>(&a.ub[r]);
-      if (u < INFINITY) m = fmin(m, (ldg<NT>(&a.xx[r]) - u) / p);
-    }
+    m = pmh_box_feas(m, a.xx, p, a.lb, a.ub, r); // (plain loads: no caller asks for NT with this epilogue)
   }
 }
 
@@ -219,8 +213,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_spmv_stream(const int *__restrict
             y[fr] = sum;
             acc0 += fp * sum;
             acc1 += fg * fp;
-            if (fp > 0. && fl > -INFINITY) amin = fmin(amin, (fx - fl) / fp);
-            if (fp < 0. && fu < INFINITY) amin = fmin(amin, (fx - fu) / fp);
+            amin = pmh_box_feas_v(amin, fx, fp, fl, fu);
           }
         }
         for (int r = fr + PMH_BLOCK; r < cr1; r += PMH_BLOCK) { // (nearly) empty rows: more rows than lanes in a block

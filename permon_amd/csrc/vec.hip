@@ -5,6 +5,7 @@
 
 #include "pmh_internal.h"
 #include "reduce.h"
+#include "box_inline.h"
 
 int pmh_vec_grid(int n)
 {
@@ -251,18 +252,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_box_feas(long long n, const doubl
 {
   __shared__ double lds[PMH_BLOCK / 64];
   double            a = INFINITY;
-  GRID_STRIDE(i, n)
-  {
-    double di = d[i], xi = x[i];
-    if (di > 0. && lb) {
-      double l = lb[i];
-      if (l > -INFINITY) a = fmin(a, (xi - l) / di);
-    }
-    if (di < 0. && ub) {
-      double u = ub[i];
-      if (u < INFINITY) a = fmin(a, (xi - u) / di);
-    }
-  }
+  GRID_STRIDE(i, n) a = pmh_box_feas(a, x, d[i], lb, ub, i);
   a = pmh_block_reduce<PMH_RED_MIN>(a, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = a;
 }

@@ -508,13 +508,29 @@ CHAIN_CASES = {  # name -> (n, m, columns every row of G0 shares (pushes W to 16
 }
 
 
+# The same generator at the sizes where pmh_csr_create gives G0 the long-row plan (more than LONG_AVG entries per row on average, chunks of LONG_CHUNK) and the
+# penalised operator created with chain = 0 takes the one-launch projector (k_gt_fused1d, csrc/qppf.hip): name -> (n, m, 0, chunks of row 0, 256-row workgroups)
+LONG_AVG, LONG_CHUNK = 1024, 4096
+PROJECTOR_CASES = {
+    "n4300_m6": (4300, 6, 0, 2, 17),  # just above the threshold: two chunks, a ragged last workgroup
+    "n36900_m6": (36900, 6, 0, 10, 145),  # a second trip of the 8-in-flight chunk loop with a ragged tail
+    "n33793_m64": (33793, 64, 0, 9, 133),  # the full 64 x 64 matrix in LDS, t < m on every lane of wave 0; one row in the last workgroup
+}
+
+
+def long_rows(G0):
+    """pmh_csr_create's long-row plan: whether it applies, and the chunks per row."""
+    length = np.diff(G0["rowptr"])
+    return bool(length.sum() / G0["nrows"] > LONG_AVG), -(-length // LONG_CHUNK)
+
+
 @functools.lru_cache(maxsize=None)
 def chain_case(name, dyadic=False):
     """G0 (m x n): row r holds the columns r, r + m, ... below `span` (1024 for the two-tile case of 1500: its second tile has no segment), but row 0 every column of
     that span (a segment of 1024 entries in each full tile), row 1 the first 256, row 2 the first 257, row 3 column 3 alone; `wide` > 0: rows 4..12 also the first `wide`
     columns (columns with up to 14 entries).  gather (nmid x n): rows of 1, 0, 2, 3, 1, 5 entries in turn, every 7th row followed by its negative (a partner) and
     every 11th by a copy of itself (the same key, no partner).  middle: two entries per row, not symmetric.  scatter (n x nmid): rows of 1, 2, 0, 4 entries."""
-    n, m, wide, _, _ = CHAIN_CASES[name]
+    n, m, wide, _, _ = CHAIN_CASES[name] if name in CHAIN_CASES else PROJECTOR_CASES[name]
     rng = np.random.default_rng([n, m, wide])
     val = (lambda k: rng.choice([-2.0, -1.0, 1.0, 2.0], k)) if dyadic else (lambda k: rng.uniform(0.5, 1.5, k) * rng.choice([-1.0, 1.0], k))
     span = 1024 if n == 1500 else n

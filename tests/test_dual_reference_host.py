@@ -333,6 +333,22 @@ def test_chain_cases_reach_the_plans_they_are_named_after():
     assert 9 <= cnt.max() <= 16 and np.bincount(D.chain_case("n1025_m64")["G0"]["col"]).max() <= 8
 
 
+def test_projector_cases_reach_the_long_row_plan_and_every_loop():
+    """The cases of tests/test_gpu_projector_paths.py: G0 on the long-row plan, the chunk counts and workgroups each is named for, a one-lane-per-row G0' (at most 16
+    entries per column: one trip of the row loop), m at both ends -- and n4300 close enough to the threshold that a tenth fewer columns would leave the plan."""
+    for name, (n, m, _, chunks0, nwg) in D.PROJECTOR_CASES.items():
+        c = D.chain_case(name)
+        G0 = c["G0"]
+        is_long, chunks = D.long_rows(G0)
+        assert is_long and (c["n"], c["m"]) == (n, m) and chunks[0] == chunks0 and D.vec_grid(n) == nwg == -(-n // D.BLOCK), (name, chunks)
+        assert chunks[1:].min() == 1 and chunks[1:].max() <= 2 and n % D.LONG_CHUNK and n % D.BLOCK  # ragged last chunk, ragged last workgroup
+        assert 1 <= np.bincount(G0["col"], minlength=n).min() and np.bincount(G0["col"], minlength=n).max() <= 4
+    assert D.PROJECTOR_CASES["n36900_m6"][3] > 8 and D.PROJECTOR_CASES["n36900_m6"][3] % 8  # a second, ragged trip of the 8-in-flight loop
+    assert max(v[1] for v in D.PROJECTOR_CASES.values()) == 64
+    rp = D.chain_case("n4300_m6")["G0"]["rowptr"]
+    assert (rp[-1] - 0.1 * 4300 * 4 / 3) / 6 <= D.LONG_AVG
+
+
 @pytest.mark.parametrize("name", SMALL_CHAINS)
 def test_chain_restatement_counts_every_entry_once(name):
     """Small integers everywhere (G0, S, the three stages, x, rho = 2): every sum is exact in any order, and the restated chain must equal the dense float64 product bit
