@@ -1257,6 +1257,11 @@ int pmh_bsr3_test_destroy(void *B);
  * more items, 20 launch: 0 the single-class kernel, 1 a table-driven launch per class, 2 one merged table-driven launch over all classes, 21 finishing: 0 k_fxo_fin per
  * class, 1 k_fxo_fin_all, 22 / 23 this rank's range of the representatives}.  PMH_ERR_STATE before there is a plan. */
 int pmh_fexplicit_test_load_class(pmh_fexplicit E, int cls, const double *W_host);
+/* pmh_fexplicit_assemble_window (tests of the set-up's batch windows, which the library itself reaches only through the probe of pmh_feti_contact_solve): pmh_fexplicit_assemble
+ * restricted to the batches [begin, end) of its plan, in the order and with the columns the whole set-up gives them; call it window after window.  Out: the plan's batches (the
+ * self-check of a set-up by symmetry is the last one) and K^+ solves, and whether this window reached the last batch -- only then the operator counts as assembled. */
+int pmh_fexplicit_assemble_window(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it, int begin, int end, int *nbatch,
+                                  long long *nsolves, int *complete);
 int pmh_fexplicit_orbit_plan_info(pmh_fexplicit E, int cls, long long info[24]);
 /* pmh_fexplicit_orbit_adapted_info: what the block products (k_fxa_prod) run for class cls while it applies W_c in the symmetry-adapted basis (pmh_fexplicit_orbit_adapted);
  * called by nothing inside the solvers.  20 entries per irrep i = 0 .. 9 at info + 20 i: {0 d, 1 m, 2 k steps of 8 columns nks, 3 blocks of 16 output rows, 4 blocks of 16

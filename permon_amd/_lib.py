@@ -482,6 +482,7 @@ _PROTOS = {
     "pmh_fexplicit_compressed_size": [vp, c_int_p, vp],
     "pmh_fexplicit_dense_mult": [vp, vp, vp],
     "pmh_fexplicit_test_load_class": [vp, C.c_int, vp],
+    "pmh_fexplicit_assemble_window": [vp, vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, c_int_p, C.POINTER(C.c_longlong), c_int_p],
     "pmh_fexplicit_orbit_plan_info": [vp, C.c_int, vp],
     "pmh_fexplicit_orbit_adapted_info": [vp, C.c_int, vp],
     "pmh_fexplicit_timing_enable": [vp, C.c_int, C.c_int],

@@ -28,6 +28,7 @@
 
 #include "feti_internal.h"
 #include "fshared.h"
+#include "fx_assemble.h"
 #include "pmh_internal.h"
 #include "reduce.h"
 
@@ -755,148 +756,211 @@ static inline bool fx_owns_row(pmh_fexplicit E, int b, int p) { return E->stripe
 
 // ---- assembly -------------------------------------------------------------------------------------------------------------
 // MatInvExplicitly_Private (matinv.c:640-665: KSPSolve on the columns of the identity, one row of the explicit matrix per solve),
-// restricted to the columns / rows in Gamma and batched over the slots of `solver`.
-// slot_class[s]: class of the matrix in slot s of the solver; block_class[b]: class of block b of this operator (blocks of one
-// class have identical K_b, so K_b^+ e_j serves all of them).  NULL, NULL: slot s <-> block s (the solver is the operator's own K^+).
-extern "C" int pmh_fexplicit_assemble(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it)
+// restricted to the columns / rows in Gamma and batched over the slots of `solver`: the loop of every storage form (fx_assemble.h).
+void fx_extract_row(pmh_ctx ctx, int n, const int *rel, const double *u, double *wrow)
 {
-  PMH_ARG(E && solver && nslots >= 1 && (solver->nblocks == nslots || solver->nblocks * PMH_MV_R == nslots));
-  PMH_ARG((slot_class && block_class) || (!slot_class && !block_class && (nslots == E->nb || nslots == E->nb * PMH_MV_R)));
-  if (E->sh) { // class-shared storage: one full row of W_c per solve (the classes are those given at creation)
-    PMH_ARG(slot_class);
-    auto t0s = std::chrono::steady_clock::now();
-    PMH_CHK(fxs_assemble(E->sh, solver, nslots, slot_class, rtol, max_it, &E->n_solves, E->win));
-    if (!E->win || E->win->complete) E->assembled = 1;
-    E->assemble_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0s).count();
-    return PMH_SUCCESS;
+  hipLaunchKernelGGL(k_fx_extract, dim3(std::max(1, std::min(64, (n + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, n, rel, u, wrow);
+}
+
+namespace {
+// what a run of the loop holds: freed, closed and (the solver's tolerances) put back on every way out
+struct fx_asm_scope {
+  pmh_ctx        ctx;
+  pmh_asm_solver A;
+  pmh_matinv     solver = nullptr; // set once its tolerances are saved
+  double        *rhs = nullptr, *sol = nullptr, *d_out = nullptr;
+  int           *d_idx = nullptr, *h_idx = nullptr; // h_idx: pinned staging of the batches' indices, two halves
+  double         old_rtol = 0.0, old_atol = 0.0;
+  int            old_maxit = 0;
+  ~fx_asm_scope()
+  {
+    if (solver) pmh_matinv_set_tolerances(solver, old_rtol, old_atol, old_maxit);
+    pmh_free(ctx, d_out), pmh_free(ctx, rhs), pmh_free(ctx, sol), pmh_free(ctx, d_idx);
+    if (h_idx) (void)hipHostFree(h_idx);
+    A.close();
   }
+};
+} // namespace
+
+int fx_assemble_run(pmh_ctx ctx, const fx_asm_plan &P, pmh_matinv solver, int nslots, const int *slot_class, double rtol, int max_it, long long *n_solves, fx_batch_window *w)
+{
+  const int    ncls = (int)P.nloc.size();
+  fx_asm_scope G{ctx};
+  pmh_asm_solver &A = G.A;
+  PMH_CHK(A.open(solver, nslots));
+  std::vector<std::vector<int>> cslots(ncls);
+  for (int s = 0; s < nslots; s++)
+    if (slot_class[s] >= 0 && slot_class[s] < ncls) cslots[slot_class[s]].push_back(s);
+  // the batches: column j of a class in batch j / (its slots); then ONE batch of self-check rows, spread over every class's candidates
+  std::vector<std::vector<fx_asm_row>> chk(ncls);
+  int                                  nbatch = 0;
+  long long                            ncol = 0;
+  bool                                 any_check = false;
+  for (int c = 0; c < ncls; c++) {
+    if (P.nloc[c] < 0) continue;
+    if (cslots[c].empty()) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_assemble: no solver slot for block class %d", c);
+    for (int s : cslots[c])
+      if (A.rows(s) != P.nloc[c]) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_assemble: slot %d has %d rows, class %d blocks have %d", s, A.rows(s), c, P.nloc[c]);
+    const size_t ns = cslots[c].size(), nchk = std::min(P.check[c].size(), ns);
+    for (size_t i = 0; i < nchk; i++) chk[c].push_back(P.check[c][(size_t)((long long)P.check[c].size() * (2 * i + 1) / (2 * nchk))]);
+    nbatch = std::max(nbatch, (int)((P.todo[c].size() + ns - 1) / ns));
+    ncol += (long long)(P.todo[c].size() + nchk);
+    any_check = any_check || nchk > 0;
+  }
+  // the batches of this call: all of them, or the caller's window (the self-check is batch nbatch)
+  const int total = nbatch + (any_check ? 1 : 0);
+  const int kbeg = w ? std::max(0, w->begin) : 0, kend = w ? std::min(total, w->end) : total;
+  if (w) w->nbatch = total, w->nsolves = ncol, w->complete = w->end >= total;
+  const size_t nsol = A.len();
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * nsol, (void **)&G.rhs));
+  PMH_CHK(pmh_malloc(ctx, sizeof(double) * nsol, (void **)&G.sol));
+  PMH_CHK(pmh_malloc(ctx, sizeof(int) * nslots, (void **)&G.d_idx));
+  PMH_HIP(hipHostMalloc((void **)&G.h_idx, sizeof(int) * nslots * 2, hipHostMallocDefault));
+  PMH_CHK(pmh_memset(ctx, G.rhs, 0, sizeof(double) * nsol));
+  PMH_CHK(pmh_matinv_get_tolerances(solver, &G.old_rtol, &G.old_atol, &G.old_maxit));
+  G.solver = solver;
+  PMH_CHK(pmh_matinv_set_tolerances(solver, rtol, 1e-300, max_it > 0 ? max_it : G.old_maxit));
+  std::vector<int> id(nslots);
+  const dim3       sgrid((nslots + 63) / 64);
+  // batch k: the unit entries of its columns, one K^+ application, the rows stored (or, in the self-check batch, compared)
+  auto batch = [&](int k) -> int {
+    const bool  checking = k == nbatch;
+    const auto &rows     = checking ? chk : P.todo;
+    const int   kk       = checking ? 0 : k;
+    int        *hh       = G.h_idx + (k & 1) * nslots; // pinned staging, alternating halves (every K^+ application synchronises the stream at least once)
+    for (int s = 0; s < nslots; s++) hh[s] = -1, id[s] = -1;
+    for (int c = 0; c < ncls; c++)
+      for (size_t t = 0; t < cslots[c].size(); t++) {
+        const size_t j = (size_t)kk * cslots[c].size() + t;
+        if (j < rows[c].size()) {
+          const int s = cslots[c][t];
+          id[s]       = rows[c][j].id;
+          hh[s]       = A.rhs_index(s, rows[c][j].rel);
+        }
+      }
+    if (hipMemcpyAsync(G.d_idx, hh, sizeof(int) * nslots, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: index upload failed");
+    hipLaunchKernelGGL(k_fx_set_entries, sgrid, dim3(64), 0, ctx->stream, nslots, (const int *)G.d_idx, 1.0, G.rhs);
+    PMH_CHK(A.solve(G.rhs, G.sol));
+    if (A.hit_the_limit()) // a column that is not converged would silently make F inexact (or fail the self-check for the wrong reason)
+      return pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_assemble: a set-up solve of batch %d did not reach rtol %.1e within %d iterations of the inner KSP", k, rtol, solver->max_it);
+    if (!checking) hipLaunchKernelGGL(k_fx_set_entries, sgrid, dim3(64), 0, ctx->stream, nslots, (const int *)G.d_idx, 0.0, G.rhs); // (nothing follows the self-check)
+    else if (!G.d_out) PMH_CHK(pmh_malloc(ctx, sizeof(double) * 2 * 64, (void **)&G.d_out));
+    for (int s = 0; s < nslots; s++) {
+      if (id[s] < 0) continue;
+      (*n_solves)++;
+      if (!checking) {
+        P.write(slot_class[s], id[s], A.sol_of(G.sol, s));
+        continue;
+      }
+      // the set-up by symmetry checks itself: a symmetry-filled row against its direct solve
+      double    h_out[2 * 64], d = 0.0, m = 0.0;
+      const int np = P.check_row(slot_class[s], id[s], A.sol_of(G.sol, s), G.d_out);
+      PMH_CHK(pmh_memcpy_d2h(ctx, h_out, G.d_out, sizeof(double) * 2 * np));
+      for (int i = 0; i < np; i++) d = std::max(d, h_out[2 * i]), m = std::max(m, h_out[2 * i + 1]);
+      if (!(d <= 1e-8 * m))
+        return pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_assemble: row %d of class %d filled by symmetry differs from its direct solve by %.2e (relative to the row's largest entry): the operations handed to pmh_fexplicit_set_class_symmetry are not symmetries of K^+", id[s], slot_class[s], d / m);
+    }
+    if (hipGetLastError() != hipSuccess) return pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: launch failed in batch %d", k);
+    return PMH_SUCCESS;
+  };
+  const bool progress = getenv("PMH_PROGRESS") != nullptr || getenv("PMH_CONTACT_TIMING") != nullptr; // (set-up only: a long assembly says where it is every ~ 20 s)
+  if (w) PMH_CHK(pmh_sync(ctx)); // (the window's seconds are the batches' alone)
+  auto       t_prog = std::chrono::steady_clock::now();
+  const auto t_loop = t_prog;
+  int        rc     = PMH_SUCCESS;
+  for (int k = kbeg; k < kend && !rc; k++) {
+    if (progress && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_prog).count() > 20.0) {
+      t_prog = std::chrono::steady_clock::now();
+      fprintf(stderr, "  pmh_fexplicit_assemble: batch %d of %d (%d columns per batch), %.0f s\n", k, total, nslots, std::chrono::duration<double>(t_prog - t_loop).count());
+      fflush(stderr);
+    }
+    rc = batch(k);
+  }
+  if (!rc) rc = pmh_sync(ctx);
+  if (w) w->loop_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
+  return rc;
+}
+
+// FULL / SYM, one matrix per block: the columns of a class are the union of its blocks' owned Gamma rows; column j is row pos_b(j) of every block of the class
+// that has it.  block_class[b]: class of block b (blocks of one class have identical K_b, so K_b^+ e_j serves all of them).
+static int fx_assemble_blocks(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it)
+{
   pmh_ctx   ctx = E->ctx;
   const int nb  = E->nb;
-  auto      t0  = std::chrono::steady_clock::now();
   std::vector<int> sc(nslots), bc(nb);
   for (int s = 0; s < nslots; s++) sc[s] = slot_class ? slot_class[s] : s / (nslots / nb); // (no classes given: slot s is block s, or column s % R of block s / R)
   for (int b = 0; b < nb; b++) bc[b] = block_class ? block_class[b] : b;
   int ncls = 0;
   for (int b = 0; b < nb; b++) ncls = std::max(ncls, bc[b] + 1);
-  pmh_asm_solver A;
-  struct closer {
-    pmh_asm_solver &a;
-    ~closer() { a.close(); }
-  } closer_{A};
-  PMH_CHK(A.open(solver, nslots));
-  // per class: its slots, its blocks, the union of the blocks' relative Gamma indices
-  std::vector<std::vector<int>> cslots(ncls), cblocks(ncls), cunion(ncls);
-  for (int s = 0; s < nslots; s++)
-    if (sc[s] >= 0 && sc[s] < ncls) cslots[sc[s]].push_back(s);
+  fx_asm_plan                   P(ncls);
+  std::vector<std::vector<int>> cblocks(ncls), pos(nb); // pos: position of a relative dof inside Gamma_b (-1: not in it)
   for (int b = 0; b < nb; b++) {
     PMH_ARG(bc[b] >= 0);
     cblocks[bc[b]].push_back(b);
+    pos[b].assign((size_t)std::max(1, E->K->rowstart[b + 1] - E->K->rowstart[b]), -1);
+    for (size_t k = E->goff[b]; k < E->goff[b + 1]; k++) pos[b][E->gamma[k] - E->K->rowstart[b]] = (int)(k - E->goff[b]);
   }
   for (int c = 0; c < ncls; c++) {
     if (cblocks[c].empty()) continue;
-    if (cslots[c].empty()) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_assemble: no solver slot for block class %d", c);
-    const int nloc = E->K->rowstart[cblocks[c][0] + 1] - E->K->rowstart[cblocks[c][0]];
+    const int nloc = P.nloc[c] = E->K->rowstart[cblocks[c][0] + 1] - E->K->rowstart[cblocks[c][0]];
     for (int b : cblocks[c])
       if (E->K->rowstart[b + 1] - E->K->rowstart[b] != nloc) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_assemble: blocks of class %d differ in size", c);
-    for (int s : cslots[c])
-      if (A.rows(s) != nloc) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_assemble: slot %d has %d rows, class %d blocks have %d", s, A.rows(s), c, nloc);
     std::vector<char> in((size_t)std::max(1, nloc), 0);
     for (int b : cblocks[c])
       for (size_t k = E->goff[b]; k < E->goff[b + 1]; k++)
         if (fx_owns_row(E, b, (int)(k - E->goff[b]))) in[E->gamma[k] - E->K->rowstart[b]] = 1;
     for (int i = 0; i < nloc; i++)
-      if (in[i]) cunion[c].push_back(i);
+      if (in[i]) P.todo[c].push_back({i, i});
   }
-  // position of a relative dof inside Gamma_b (-1: not in it)
-  std::vector<std::vector<int>> pos(nb);
-  for (int b = 0; b < nb; b++) {
-    pos[b].assign((size_t)std::max(1, E->K->rowstart[b + 1] - E->K->rowstart[b]), -1);
-    for (size_t k = E->goff[b]; k < E->goff[b + 1]; k++) pos[b][E->gamma[k] - E->K->rowstart[b]] = (int)(k - E->goff[b]);
-  }
-  int nbatch = 0;
-  for (int c = 0; c < ncls; c++)
-    if (!cblocks[c].empty()) nbatch = std::max(nbatch, (int)((cunion[c].size() + cslots[c].size() - 1) / cslots[c].size()));
-  fx_batch_window *w    = E->win; // the batches of this call: all of them, or the caller's window
-  const int        kbeg = w ? std::max(0, w->begin) : 0, kend = w ? std::min(nbatch, w->end) : nbatch;
-  if (w) {
-    w->nbatch = nbatch, w->nsolves = 0, w->complete = w->end >= nbatch;
-    for (int c = 0; c < ncls; c++) w->nsolves += (long long)cunion[c].size();
-  }
-  double *rhs, *sol;
-  int    *d_idx, *h_idx;
-  const size_t nsol = A.len();
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * nsol, (void **)&rhs));
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * nsol, (void **)&sol));
-  PMH_CHK(pmh_malloc(ctx, sizeof(int) * nslots, (void **)&d_idx));
-  PMH_HIP(hipHostMalloc((void **)&h_idx, sizeof(int) * nslots * 2, hipHostMallocDefault));
-  PMH_CHK(pmh_memset(ctx, rhs, 0, sizeof(double) * nsol));
-  double old_rtol, old_atol;
-  int    old_maxit;
-  PMH_CHK(pmh_matinv_get_tolerances(solver, &old_rtol, &old_atol, &old_maxit));
-  PMH_CHK(pmh_matinv_set_tolerances(solver, rtol, 1e-300, max_it > 0 ? max_it : old_maxit));
-  int        rc = PMH_SUCCESS;
-  std::vector<int> col(nslots);
-  const bool progress = getenv("PMH_PROGRESS") != nullptr || getenv("PMH_CONTACT_TIMING") != nullptr; // (set-up only: a long assembly says where it is every ~ 20 s)
-  if (w) rc = pmh_sync(ctx); // (the window's seconds are the batches' alone)
-  auto       t_prog   = std::chrono::steady_clock::now();
-  const auto t_loop   = t_prog;
-  for (int k = kbeg; k < kend && !rc; k++) {
-    if (progress && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_prog).count() > 20.0) {
-      t_prog = std::chrono::steady_clock::now();
-      fprintf(stderr, "  pmh_fexplicit_assemble: batch %d of %d (%d columns per batch), %.0f s\n", k, nbatch, nslots, std::chrono::duration<double>(t_prog - t0).count());
-      fflush(stderr);
+  auto rows_of = [&](int c, int col, auto store) {
+    for (int b : cblocks[c]) {
+      const int p = pos[b][col];
+      if (p >= 0 && fx_owns_row(E, b, p)) store(b, p);
     }
-    int *hh = h_idx + (k & 1) * nslots; // pinned staging, alternating halves (every K^+ application synchronises the stream at least once)
-    for (int s = 0; s < nslots; s++) hh[s] = -1, col[s] = -1;
-    for (int c = 0; c < ncls; c++) {
-      if (cblocks[c].empty()) continue;
-      for (size_t t = 0; t < cslots[c].size(); t++) {
-        const size_t j = (size_t)k * cslots[c].size() + t;
-        if (j < cunion[c].size()) {
-          const int s = cslots[c][t];
-          col[s]      = cunion[c][j];
-          hh[s]       = A.rhs_index(s, col[s]);
-        }
-      }
-    }
-    if (hipMemcpyAsync(d_idx, hh, sizeof(int) * nslots, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: index upload failed");
-      break;
-    }
-    hipLaunchKernelGGL(k_fx_set_entries, dim3((nslots + 63) / 64), dim3(64), 0, ctx->stream, nslots, (const int *)d_idx, 1.0, rhs);
-    if ((rc = A.solve(rhs, sol))) break;
-    if (A.hit_the_limit()) { // a column that is not converged would silently make F inexact
-      rc = pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_assemble: a set-up solve of batch %d did not reach rtol %.1e within %d iterations of the inner KSP", k, rtol, solver->max_it);
-      break;
-    }
-    hipLaunchKernelGGL(k_fx_set_entries, dim3((nslots + 63) / 64), dim3(64), 0, ctx->stream, nslots, (const int *)d_idx, 0.0, rhs);
-    for (int s = 0; s < nslots; s++) {
-      if (col[s] < 0) continue;
-      E->n_solves++;
-      for (int b : cblocks[sc[s]]) {
-        const int p = pos[b][col[s]];
-        if (p < 0 || !fx_owns_row(E, b, p)) continue;
-        // row p of W_b: FULL all n_Gamma columns; SYM the columns of its band (0 .. 32(k+1)-1, capped at n_Gamma: the rest is padding)
-        const int       kb   = p / FX_RB;
-        const int       n    = (E->storage == PMH_FX_SYM) ? std::min(E->ngam[b], FX_RB * (kb + 1)) : E->ngam[b];
-        const dim3      grid(std::max(1, std::min(64, (n + PMH_BLOCK - 1) / PMH_BLOCK)));
-        if (E->storage == PMH_FX_SYM)
-          hipLaunchKernelGGL(k_fx_extract_tiled, grid, dim3(PMH_BLOCK), 0, ctx->stream, n, (const int *)(E->d_gamma_rel + E->goff[b]), A.sol_of(sol, s), E->W[b] + fx_band_off(kb), p - FX_RB * kb);
-        else
-          hipLaunchKernelGGL(k_fx_extract, grid, dim3(PMH_BLOCK), 0, ctx->stream, n, (const int *)(E->d_gamma_rel + E->goff[b]), A.sol_of(sol, s), E->W[b] + (long long)p * E->ld[b]);
-      }
-    }
-    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: launch failed in batch %d", k);
-  }
-  if (!rc) rc = pmh_sync(ctx);
-  if (w) w->loop_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
-  pmh_matinv_set_tolerances(solver, old_rtol, old_atol, old_maxit);
-  pmh_free(ctx, rhs), pmh_free(ctx, sol), pmh_free(ctx, d_idx);
-  (void)hipHostFree(h_idx);
-  if (rc) return rc;
-  if (!w || w->complete) E->assembled = 1;
+  };
+  if (E->storage == PMH_FX_SYM) // row p: the columns of its band (0 .. 32(k+1)-1, capped at n_Gamma: the rest is padding)
+    P.write = [&](int c, int col, const double *u) {
+      rows_of(c, col, [&](int b, int p) {
+        const int kb = p / FX_RB, n = std::min(E->ngam[b], FX_RB * (kb + 1));
+        hipLaunchKernelGGL(k_fx_extract_tiled, dim3(std::max(1, std::min(64, (n + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, n, (const int *)(E->d_gamma_rel + E->goff[b]), u,
+                           E->W[b] + fx_band_off(kb), p - FX_RB * kb);
+      });
+    };
+  else // row p: all n_Gamma columns
+    P.write = [&](int c, int col, const double *u) { rows_of(c, col, [&](int b, int p) { fx_extract_row(ctx, E->ngam[b], E->d_gamma_rel + E->goff[b], u, E->W[b] + (long long)p * E->ld[b]); }); };
+  return fx_assemble_run(ctx, P, solver, nslots, sc.data(), rtol, max_it, &E->n_solves, E->win);
+}
+
+// slot_class[s]: class of the matrix in slot s of the solver; block_class[b]: class of block b of this operator (the class-shared storages: the classes given at
+// creation).  NULL, NULL: slot s <-> block s (the solver is the operator's own K^+).
+extern "C" int pmh_fexplicit_assemble(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it)
+{
+  PMH_ARG(E && solver && nslots >= 1 && (solver->nblocks == nslots || solver->nblocks * PMH_MV_R == nslots));
+  PMH_ARG((slot_class && block_class) || (!slot_class && !block_class && (nslots == E->nb || nslots == E->nb * PMH_MV_R)));
+  PMH_ARG(!E->sh || slot_class);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (E->sh) PMH_CHK(fxs_assemble(E->sh, solver, nslots, slot_class, rtol, max_it, &E->n_solves, E->win));
+  else PMH_CHK(fx_assemble_blocks(E, solver, nslots, slot_class, block_class, rtol, max_it));
+  if (!E->win || E->win->complete) E->assembled = 1;
   E->assemble_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return PMH_SUCCESS;
+}
+
+// tests: batches [begin, end) of the set-up alone (pmh_fexplicit_set_window around one pmh_fexplicit_assemble); out: the plan's batches and K^+ solves, and whether
+// this window reached the last batch
+extern "C" int pmh_fexplicit_assemble_window(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it, int begin, int end, int *nbatch,
+                                             long long *nsolves, int *complete)
+{
+  PMH_ARG(E && begin >= 0 && end >= begin);
+  fx_batch_window w;
+  w.begin = begin, w.end = end;
+  PMH_CHK(pmh_fexplicit_set_window(E, &w));
+  const int rc = pmh_fexplicit_assemble(E, solver, nslots, slot_class, block_class, rtol, max_it);
+  E->win = nullptr;
+  if (nbatch) *nbatch = w.nbatch;
+  if (nsolves) *nsolves = w.nsolves;
+  if (complete) *complete = w.complete ? 1 : 0;
+  return rc;
 }
 
 // The set-up with 8 columns per block and application where the multi-right-hand-side K^+ applies to `solver` (matinv_mv.hip), one column per block otherwise

@@ -25,6 +25,7 @@
 // The file is split four ways (round 5): fshared_types.h (the storage structures), fshared_kernels.h (the device kernels), fshared_plan.hip (the orbit GEMM's plan, host only)
 // and this file: creation, stripes, symmetries, the launches of the products, the assembly by K^+ solves.
 #include "fshared_adapted.h"
+#include "fx_assemble.h"
 #include "orbitbasis.h"
 
 extern char **environ;
@@ -865,189 +866,114 @@ static int fxa_setup(fx_shared *S)
   return pmh_sync(ctx);
 }
 
+// ---- the set-up: what each storage form hands the loop of fx_assemble.h (its columns, its row writer, its self-check), chosen once per call -------------------------
+static inline int     fxs_row_grid(int n) { return std::max(1, std::min(64, (n + PMH_BLOCK - 1) / PMH_BLOCK)); }
+static inline double *fxs_super_band(fx_shared *S, const fxs_class &C, int row) // the first tile of the row's super band (symmetric tiles)
+{
+  const long long sb = row / FXM_RS;
+  return S->Wbase + C.woff + (long long)FXM_RS * FXM_RS * (sb * (sb + 1) / 2);
+}
+// orbit storage: a row of W_c (u[rel[i]], i < n_c) into row `row` of the pre-tiled A
+static void fxo_store_row(fx_shared *S, const fxs_class &C, int row, const int *d_rel, const double *u)
+{
+  hipLaunchKernelGGL(k_fxo_store_row, dim3(fxs_row_grid(C.nc)), dim3(PMH_BLOCK), 0, S->ctx->stream, row, C.tm, C.nc, C.nkc, d_rel, (const int *)C.d_kinv, u, S->Afund + C.aoff);
+}
+
+// PMH_FX_CLASS: the rows of this rank's stripe, each stored in full
+static void fxs_plan_full(fx_shared *S, fx_asm_plan &P)
+{
+  for (int c = 0; c < S->ncls; c++) {
+    const fxs_class &C = S->C[c];
+    for (int p = C.r0; p < std::min(C.r1, C.nc); p++) P.todo[c].push_back({C.urel[p], p});
+  }
+  P.write = [S](int c, int p, const double *u) { // row p of W_c = column p (K^+ symmetric)
+    const fxs_class &C = S->C[c];
+    fx_extract_row(S->ctx, C.nc, C.d_urel, u, S->Wbase + C.woff + (long long)p * C.ld);
+  };
+}
+
+// PMH_FX_CLASS_SYM: the rows of this rank's super bands.  A class with symmetries solves one row per orbit that has a row there and fills the orbit's owned rows from it;
+// symmetry-filled rows are the self-check's candidates.
+static void fxs_plan_tiles(fx_shared *S, fx_asm_plan &P)
+{
+  std::vector<std::map<int, std::vector<std::pair<int, int>>>> members(S->ncls); // per class with symmetries: representative row -> (owned row of its orbit, the operation that reaches it)
+  for (int c = 0; c < S->ncls; c++) {
+    const fxs_class &C = S->C[c];
+    if (C.nsym <= 1) {
+      for (int p = 0; p < C.nc; p++)
+        if (C.own[p / FXM_RS]) P.todo[c].push_back({C.urel[p], p});
+      continue;
+    }
+    std::vector<int> rep_of((size_t)C.nc, -1), op_of((size_t)C.nc, 0);
+    for (int p = 0; p < C.nc; p++) {
+      if (rep_of[p] >= 0) continue;
+      for (int g = 0; g < C.nsym; g++) {
+        const int r = C.h_posmap[(size_t)g * C.nc + p];
+        if (rep_of[r] < 0) rep_of[r] = p, op_of[r] = g;
+      }
+    }
+    for (int r = 0; r < C.nc; r++)
+      if (C.own[r / FXM_RS]) {
+        members[c][rep_of[r]].push_back({r, op_of[r]});
+        if (op_of[r] != 0) P.check[c].push_back({C.urel[r], r});
+      }
+    for (const auto &m : members[c]) P.todo[c].push_back({C.urel[m.first], m.first}); // (ascending)
+  }
+  P.write = [S, members = std::move(members)](int c, int p, const double *u) {
+    const fxs_class &C = S->C[c];
+    if (members[c].empty()) {
+      hipLaunchKernelGGL(k_fxs_extract_sym, dim3(fxs_row_grid(p + 1)), dim3(PMH_BLOCK), 0, S->ctx->stream, p, (const int *)C.d_urel, u, fxs_super_band(S, C, p));
+      return;
+    }
+    for (const auto &rg : members[c].at(p)) {
+      const int r = rg.first, g = rg.second;
+      hipLaunchKernelGGL(k_fxs_extract_symg, dim3(fxs_row_grid(C.nc)), dim3(PMH_BLOCK), 0, S->ctx->stream, r, C.nc, (double)C.h_sign[(size_t)g * C.nc + p], (const int *)C.d_urel, u,
+                         (const int *)(C.d_posmap + (size_t)g * C.nc), (const signed char *)(C.d_sign + (size_t)g * C.nc), fxs_super_band(S, C, r));
+    }
+  };
+  P.check_row = [S](int c, int r, const double *u, double *d_out) {
+    const fxs_class &C = S->C[c];
+    hipLaunchKernelGGL(k_fxs_check_row, dim3(fxs_row_grid(r + 1)), dim3(PMH_BLOCK), 0, S->ctx->stream, r, (const int *)C.d_urel, u, (const double *)fxs_super_band(S, C, r), d_out);
+    return fxs_row_grid(r + 1);
+  };
+}
+
+// PMH_FX_CLASS_ORBIT (after fxo_prepare): the owned representatives' rows; self-check candidates: rows of their orbits reached by a non-trivial operation
+static void fxs_plan_orbit(fx_shared *S, fx_asm_plan &P)
+{
+  for (int c = 0; c < S->ncls; c++) {
+    const fxs_class &C = S->C[c];
+    if (!C.nc) continue;
+    for (int pl = 0; pl < C.m1 - C.m0; pl++) P.todo[c].push_back({C.urel[C.reps[C.m0 + pl]], pl});
+    for (int r = 0; r < C.nc; r++)
+      if (C.op_of[r] != 0) {
+        const int k = (int)(std::lower_bound(C.reps.begin(), C.reps.end(), C.rep_of[r]) - C.reps.begin());
+        if (k >= C.m0 && k < C.m1) P.check[c].push_back({C.urel[r], r});
+      }
+  }
+  P.write     = [S](int c, int pl, const double *u) { fxo_store_row(S, S->C[c], S->C[c].reprow[pl], S->C[c].d_urel, u); };
+  P.check_row = [S](int c, int r, const double *u, double *d_out) {
+    const fxs_class &C = S->C[c];
+    const int        g = C.op_of[r], p = C.rep_of[r], pl = (int)(std::lower_bound(C.reps.begin(), C.reps.end(), p) - C.reps.begin()) - C.m0;
+    hipLaunchKernelGGL(k_fxo_check_row, dim3(fxs_row_grid(C.nc)), dim3(PMH_BLOCK), 0, S->ctx->stream, C.reprow[pl], C.tm, C.nc, C.nkc, (double)C.h_sign[(size_t)g * C.nc + p], (const int *)C.d_urel,
+                       (const int *)C.d_kinv, u, (const int *)(C.d_posmap + (size_t)g * C.nc), (const signed char *)(C.d_sign + (size_t)g * C.nc), (const double *)(S->Afund + C.aoff), d_out);
+    return fxs_row_grid(C.nc);
+  };
+}
+
 int fxs_assemble(fx_shared *S, pmh_matinv solver, int nslots, const int *slot_class, double rtol, int max_it, long long *n_solves, fx_batch_window *w)
 {
   PMH_ARG(S && solver && nslots >= 1 && (solver->nblocks == nslots || solver->nblocks * PMH_MV_R == nslots) && slot_class);
-  pmh_ctx                       ctx = S->ctx;
   if (S->sym == 2) PMH_CHK(fxo_prepare(S));
-  pmh_asm_solver                A;
-  struct closer {
-    pmh_asm_solver &a;
-    ~closer() { a.close(); }
-  } closer_{A};
-  PMH_CHK(A.open(solver, nslots));
-  std::vector<std::vector<int>> cslots(S->ncls), todo(S->ncls);
-  std::vector<std::vector<int>> rep_of(S->ncls), op_of(S->ncls), check(S->ncls);
-  std::vector<std::map<int, std::vector<int>>> members(S->ncls); // representative row -> the owned rows of its orbit
-  for (int s = 0; s < nslots; s++)
-    if (slot_class[s] >= 0 && slot_class[s] < S->ncls) cslots[slot_class[s]].push_back(s);
-  int nbatch = 0;
-  for (int c = 0; c < S->ncls; c++) {
-    fxs_class &C = S->C[c];
-    if (C.nc == 0) continue;
-    if (cslots[c].empty()) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_assemble: no solver slot for block class %d", c);
-    for (int s : cslots[c])
-      if (A.rows(s) != C.nloc) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_assemble: slot %d has %d rows, class %d blocks have %d", s, A.rows(s), c, C.nloc);
-    if (S->sym == 2) {
-      // orbit storage: the owned representatives; self-check: rows of their orbits reached by a non-trivial operation
-      for (int pl = 0; pl < C.m1 - C.m0; pl++) todo[c].push_back(C.reps[C.m0 + pl]);
-      std::vector<int> filled;
-      for (int r = 0; r < C.nc; r++)
-        if (C.op_of[r] != 0) {
-          const int k = (int)(std::lower_bound(C.reps.begin(), C.reps.end(), C.rep_of[r]) - C.reps.begin());
-          if (k >= C.m0 && k < C.m1) filled.push_back(r);
-        }
-      const int nchk = (int)std::min(filled.size(), cslots[c].size());
-      for (int i = 0; i < nchk; i++) check[c].push_back(filled[(size_t)((long long)filled.size() * (2 * i + 1) / (2 * nchk))]);
-    } else if (S->sym && C.nsym > 1) {
-      // orbits of the rows under the class's symmetries: rep_of / op_of, one solve per orbit that has a row in this rank's super bands
-      rep_of[c].assign((size_t)C.nc, -1), op_of[c].assign((size_t)C.nc, 0);
-      for (int p = 0; p < C.nc; p++) {
-        if (rep_of[c][p] >= 0) continue;
-        for (int g = 0; g < C.nsym; g++) {
-          const int r = C.h_posmap[(size_t)g * C.nc + p];
-          if (rep_of[c][r] < 0) rep_of[c][r] = p, op_of[c][r] = g;
-        }
-      }
-      std::vector<char> need((size_t)C.nc, 0);
-      for (int r = 0; r < C.nc; r++)
-        if (C.own[r / FXM_RS]) need[rep_of[c][r]] = 1, members[c][rep_of[c][r]].push_back(r);
-      for (int p = 0; p < C.nc; p++)
-        if (need[p]) todo[c].push_back(p);
-      // self-check: up to one batch of symmetry-filled owned rows, spread over the range, solved directly at the end
-      std::vector<int> filled;
-      for (int r = 0; r < C.nc; r++)
-        if (C.own[r / FXM_RS] && op_of[c][r] != 0) filled.push_back(r);
-      const int nchk = (int)std::min(filled.size(), cslots[c].size());
-      for (int i = 0; i < nchk; i++) check[c].push_back(filled[(size_t)((long long)filled.size() * (2 * i + 1) / (2 * nchk))]);
-    } else if (S->sym) {
-      for (int p = 0; p < C.nc; p++)
-        if (C.own[p / FXM_RS]) todo[c].push_back(p); // the rows of this rank's super bands
-    } else
-      for (int p = C.r0; p < std::min(C.r1, C.nc); p++) todo[c].push_back(p); // the rows of this rank's stripe
-    nbatch = std::max(nbatch, (int)((todo[c].size() + cslots[c].size() - 1) / cslots[c].size()));
-  }
-  bool any_check = false;
-  for (int c = 0; c < S->ncls; c++) any_check = any_check || !check[c].empty();
-  // the batches of this call: all of them, or the caller's window (the self-check is batch nbatch)
-  const int  kbeg = w ? std::max(0, w->begin) : 0, kend = w ? std::min(nbatch, w->end) : nbatch;
-  const bool last = !w || w->end >= nbatch + (any_check ? 1 : 0);
-  if (w) {
-    w->nbatch = nbatch + (any_check ? 1 : 0), w->nsolves = 0, w->complete = last;
-    for (int c = 0; c < S->ncls; c++) w->nsolves += (long long)todo[c].size() + (long long)check[c].size();
-  }
-  double      *rhs, *sol;
-  int         *d_idx, *h_idx;
-  const size_t nsol = A.len();
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * nsol, (void **)&rhs));
-  PMH_CHK(pmh_malloc(ctx, sizeof(double) * nsol, (void **)&sol));
-  PMH_CHK(pmh_malloc(ctx, sizeof(int) * nslots, (void **)&d_idx));
-  PMH_HIP(hipHostMalloc((void **)&h_idx, sizeof(int) * nslots * 2, hipHostMallocDefault));
-  PMH_CHK(pmh_memset(ctx, rhs, 0, sizeof(double) * nsol));
-  double old_rtol, old_atol;
-  int    old_maxit;
-  PMH_CHK(pmh_matinv_get_tolerances(solver, &old_rtol, &old_atol, &old_maxit));
-  PMH_CHK(pmh_matinv_set_tolerances(solver, rtol, 1e-300, max_it > 0 ? max_it : old_maxit));
-  int              rc = PMH_SUCCESS;
-  std::vector<int> prow(nslots);
-  if (w) rc = pmh_sync(ctx); // (the window's seconds are the batches' alone)
-  const auto t_loop = std::chrono::steady_clock::now();
-  for (int k = kbeg; k < kend && !rc; k++) {
-    int *hh = h_idx + (k & 1) * nslots;
-    for (int s = 0; s < nslots; s++) hh[s] = -1, prow[s] = -1;
-    for (int c = 0; c < S->ncls; c++)
-      for (size_t t = 0; t < cslots[c].size(); t++) {
-        const size_t j = (size_t)k * cslots[c].size() + t;
-        if (j < todo[c].size()) {
-          const int s = cslots[c][t];
-          prow[s]     = todo[c][j];
-          hh[s]       = A.rhs_index(s, S->C[c].urel[prow[s]]);
-        }
-      }
-    if (hipMemcpyAsync(d_idx, hh, sizeof(int) * nslots, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: index upload failed");
-      break;
-    }
-    hipLaunchKernelGGL(k_fxs_set_entries, dim3((nslots + 63) / 64), dim3(64), 0, ctx->stream, nslots, (const int *)d_idx, 1.0, rhs);
-    if ((rc = A.solve(rhs, sol))) break;
-    if (A.hit_the_limit()) {
-      rc = pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_assemble: a set-up solve of batch %d did not reach rtol %.1e within %d iterations of the inner KSP", k, rtol, solver->max_it);
-      break;
-    }
-    hipLaunchKernelGGL(k_fxs_set_entries, dim3((nslots + 63) / 64), dim3(64), 0, ctx->stream, nslots, (const int *)d_idx, 0.0, rhs);
-    for (int s = 0; s < nslots; s++) {
-      if (prow[s] < 0) continue;
-      (*n_solves)++;
-      const fxs_class &C = S->C[slot_class[s]];
-      if (S->sym == 2) {
-        const int pl = (int)(std::lower_bound(C.reps.begin(), C.reps.end(), prow[s]) - C.reps.begin()) - C.m0;
-        hipLaunchKernelGGL(k_fxo_store_row, dim3(std::max(1, std::min(64, (C.nc + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, C.reprow[pl], C.tm, C.nc, C.nkc, (const int *)C.d_urel,
-                           (const int *)C.d_kinv, A.sol_of(sol, s), S->Afund + C.aoff);
-      } else if (S->sym && C.nsym > 1) {
-        const int p = prow[s];
-        for (int r : members[slot_class[s]][p]) {
-          const int g = op_of[slot_class[s]][r], sb = r / FXM_RS;
-          hipLaunchKernelGGL(k_fxs_extract_symg, dim3(std::max(1, std::min(64, (C.nc + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, r, C.nc, (double)C.h_sign[(size_t)g * C.nc + p],
-                             (const int *)C.d_urel, A.sol_of(sol, s), (const int *)(C.d_posmap + (size_t)g * C.nc), (const signed char *)(C.d_sign + (size_t)g * C.nc),
-                             S->Wbase + C.woff + (long long)FXM_RS * FXM_RS * ((long long)sb * (sb + 1) / 2));
-        }
-      } else if (S->sym) {
-        const int sb = prow[s] / FXM_RS;
-        hipLaunchKernelGGL(k_fxs_extract_sym, dim3(std::max(1, std::min(64, (prow[s] + PMH_BLOCK) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, prow[s], (const int *)C.d_urel, A.sol_of(sol, s),
-                           S->Wbase + C.woff + (long long)FXM_RS * FXM_RS * ((long long)sb * (sb + 1) / 2));
-      } else
-      hipLaunchKernelGGL(k_fxs_extract, dim3(std::max(1, std::min(64, (C.nc + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, C.nc, (const int *)C.d_urel, A.sol_of(sol, s),
-                         S->Wbase + C.woff + (long long)prow[s] * C.ld); // row p of W_c = column p (K^+ symmetric)
-    }
-    if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: launch failed in batch %d", k);
-  }
-  // self-check of the set-up by symmetry: a few symmetry-filled rows against their direct solves
-  if (!last) any_check = false;
-  if (!rc && any_check) rc = pmh_sync(ctx); // the pinned index buffer is reused below
-  if (!rc && any_check) {
-    int *hh = h_idx;
-    for (int s = 0; s < nslots; s++) hh[s] = -1, prow[s] = -1;
-    for (int c = 0; c < S->ncls; c++)
-      for (size_t t = 0; t < check[c].size(); t++) {
-        const int s = cslots[c][t];
-        prow[s] = check[c][t], hh[s] = A.rhs_index(s, S->C[c].urel[prow[s]]);
-      }
-    double *d_out = nullptr, h_out[2 * 64];
-    rc = pmh_malloc(ctx, sizeof(double) * 2 * 64, (void **)&d_out);
-    if (!rc && hipMemcpyAsync(d_idx, hh, sizeof(int) * nslots, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_assemble: index upload failed");
-    if (!rc) {
-      hipLaunchKernelGGL(k_fxs_set_entries, dim3((nslots + 63) / 64), dim3(64), 0, ctx->stream, nslots, (const int *)d_idx, 1.0, rhs);
-      rc = A.solve(rhs, sol);
-    }
-    for (int s = 0; s < nslots && !rc; s++) {
-      if (prow[s] < 0) continue;
-      (*n_solves)++;
-      const fxs_class &C  = S->C[slot_class[s]];
-      const int        r = prow[s], sb = r / FXM_RS;
-      int              nb = std::max(1, std::min(64, (r + PMH_BLOCK) / PMH_BLOCK));
-      if (S->sym == 2) {
-        const int g = C.op_of[r], p = C.rep_of[r], pl = (int)(std::lower_bound(C.reps.begin(), C.reps.end(), p) - C.reps.begin()) - C.m0;
-        nb          = std::max(1, std::min(64, (C.nc + PMH_BLOCK - 1) / PMH_BLOCK));
-        hipLaunchKernelGGL(k_fxo_check_row, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, C.reprow[pl], C.tm, C.nc, C.nkc, (double)C.h_sign[(size_t)g * C.nc + p], (const int *)C.d_urel, (const int *)C.d_kinv, A.sol_of(sol, s),
-                           (const int *)(C.d_posmap + (size_t)g * C.nc), (const signed char *)(C.d_sign + (size_t)g * C.nc), (const double *)(S->Afund + C.aoff), d_out);
-      } else
-      hipLaunchKernelGGL(k_fxs_check_row, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, r, (const int *)C.d_urel, A.sol_of(sol, s),
-                         (const double *)(S->Wbase + C.woff + (long long)FXM_RS * FXM_RS * ((long long)sb * (sb + 1) / 2)), d_out);
-      if ((rc = pmh_memcpy_d2h(ctx, h_out, d_out, sizeof(double) * 2 * nb))) break;
-      double d = 0.0, m = 0.0;
-      for (int i = 0; i < nb; i++) d = std::max(d, h_out[2 * i]), m = std::max(m, h_out[2 * i + 1]);
-      if (!(d <= 1e-8 * m))
-        rc = pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_assemble: row %d of class %d filled by symmetry differs from its direct solve by %.2e (relative to the row's largest entry): the operations handed to pmh_fexplicit_set_class_symmetry are not symmetries of K^+", r, slot_class[s], d / m);
-    }
-    if (d_out) pmh_free(ctx, d_out);
-  }
-  if (!rc) rc = pmh_sync(ctx);
-  if (w) w->loop_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
-  pmh_matinv_set_tolerances(solver, old_rtol, old_atol, old_maxit);
-  pmh_free(ctx, rhs), pmh_free(ctx, sol), pmh_free(ctx, d_idx);
-  (void)hipHostFree(h_idx);
-  if (!rc && last && S->sym == 2) rc = fxa_setup(S);
-  return rc;
+  fx_asm_plan P(S->ncls);
+  for (int c = 0; c < S->ncls; c++)
+    if (S->C[c].nc) P.nloc[c] = S->C[c].nloc;
+  if (S->sym == 2) fxs_plan_orbit(S, P);
+  else if (S->sym) fxs_plan_tiles(S, P);
+  else fxs_plan_full(S, P);
+  PMH_CHK(fx_assemble_run(S->ctx, P, solver, nslots, slot_class, rtol, max_it, n_solves, w));
+  if (S->sym == 2 && (!w || w->complete)) return fxa_setup(S); // every representative's row is there: the symmetry-adapted form
+  return PMH_SUCCESS;
 }
 
 static int fxs_gemm(fx_shared *S)
@@ -1198,8 +1124,7 @@ int fxs_test_load_class(fx_shared *S, int c, const double *W, int *all_loaded)
     if (!rc) rc = pmh_memcpy_h2d(ctx, d_rows, rows.data(), sizeof(double) * rows.size());
     if (!rc) rc = pmh_memcpy_h2d(ctx, d_ident, ident.data(), sizeof(int) * ident.size());
     for (int pl = 0; pl < M && !rc; pl++)
-      hipLaunchKernelGGL(k_fxo_store_row, dim3(std::max(1, std::min(64, (C.nc + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, C.reprow[pl], C.tm, C.nc, C.nkc, (const int *)d_ident,
-                         (const int *)C.d_kinv, (const double *)(d_rows + (size_t)pl * C.nc), S->Afund + C.aoff);
+      fxo_store_row(S, C, C.reprow[pl], d_ident, d_rows + (size_t)pl * C.nc);
     if (!rc && hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_test_load_class: launch failed");
     if (!rc) rc = pmh_sync(ctx);
     if (d_rows) pmh_free(ctx, d_rows);

@@ -95,17 +95,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_fxs_fin(long long n, int nseg, lo
   *(dbl2 *)(Y + i) = s;
 }
 
-__global__ __launch_bounds__(PMH_BLOCK) void k_fxs_extract(int n, const int *__restrict__ urel, const double *__restrict__ u, double *__restrict__ wrow)
-{
-  for (int i = blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += gridDim.x * PMH_BLOCK) wrow[i] = u[urel[i]];
-}
-
-__global__ void k_fxs_set_entries(int m, const int *__restrict__ idx, double val, double *__restrict__ rhs)
-{
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < m && idx[s] >= 0) rhs[idx[s]] = val;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Symmetric tile storage (PMH_FX_CLASS_SYM): W_c = W_c' kept as its lower block-triangle, HALF the bytes of the full storage above.

@@ -142,7 +142,7 @@ int fxo_prepare(fx_shared *S)
     std::vector<int> coltab, fintab((size_t)C.ngroups * (ntile + 1) * 4, 0);
     std::vector<unsigned long long> need((size_t)C.ngroups * ntile * cw, 0ULL); // the same lists as bit sets over the codes
     { // the class's column tile: 64 when no (group, row tile) lists more than 64 columns -- a class of ONE block lists at most its 48 operations, and a 128-wide tile would
-      // multiply 80 columns of zeros (PMH_FXO_TN=128 keeps the wide tile for the A/B)
+      // multiply 80 columns of zeros
       int most = 0;
       for (int gr = 0; gr < C.ngroups; gr++)
         for (int mt = 0; mt < ntile; mt++) {

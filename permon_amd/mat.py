@@ -431,17 +431,25 @@ class MatExplicitDual:
         check(self.ctx.L.pmh_fexplicit_apply_flops_detail(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def assemble(self, solver, slot_class=None, block_class=None, rtol=1e-12, max_it=0, multi_rhs=False):
+    def assemble(self, solver, slot_class=None, block_class=None, rtol=1e-12, max_it=0, multi_rhs=False, window=None):
         """One K^+ application of `solver` (a MatInv with solver.K.nblocks slots) per batch of unit right-hand sides.  multi_rhs: 8 columns per block and application on the
-        multi-right-hand-side solver (matinv_mv.hip: slot s = column s % 8 of block s // 8; slot_class still names the class of every BLOCK of the solver)."""
+        multi-right-hand-side solver (matinv_mv.hip: slot s = column s % 8 of block s // 8; slot_class still names the class of every BLOCK of the solver).
+        window = (begin, end), tests: the batches [begin, end) of the set-up alone (pmh_fexplicit_assemble_window; end None: to the last); returns (batches, K^+ solves of
+        the whole plan, whether this window reached the last batch -- the operator applies only then)."""
         nslots = solver.K.nblocks * (8 if multi_rhs else 1)
         if multi_rhs and slot_class is not None:
             slot_class = np.repeat(np.asarray(slot_class, dtype=np.int32), 8)
         sc = np.ascontiguousarray(slot_class, dtype=np.int32) if slot_class is not None else None
         bc = np.ascontiguousarray(block_class, dtype=np.int32) if block_class is not None else None
-        check(self.ctx.L.pmh_fexplicit_assemble(self.h, solver.h, nslots, sc.ctypes.data_as(C.c_void_p) if sc is not None else None,
-                                                bc.ctypes.data_as(C.c_void_p) if bc is not None else None, float(rtol), int(max_it)))
+        args = (self.h, solver.h, nslots, sc.ctypes.data_as(C.c_void_p) if sc is not None else None, bc.ctypes.data_as(C.c_void_p) if bc is not None else None, float(rtol), int(max_it))
+        if window is None:
+            check(self.ctx.L.pmh_fexplicit_assemble(*args))
+            self.refresh_sizes()
+            return None
+        nbatch, nsolves, complete = C.c_int(), C.c_longlong(), C.c_int()
+        check(self.ctx.L.pmh_fexplicit_assemble_window(*args, int(window[0]), int(window[1]) if window[1] is not None else 1 << 30, C.byref(nbatch), C.byref(nsolves), C.byref(complete)))
         self.refresh_sizes()
+        return nbatch.value, nsolves.value, bool(complete.value)
 
     ORBIT_PLAN_FIELDS = ("n_c", "ld", "slots", "groups", "xoff", "nsym", "nsymp", "M", "tm", "Mp", "row_tiles", "tn", "tnw", "segments", "chunks", "units", "units_work",
                          "max_split", "workgroups", "workgroups_multi", "launch", "finish", "rep0", "rep1")
