@@ -62,7 +62,9 @@ int pmh_init(int device, pmh_ctx *ctx);     /* PermonInitialize's device part; f
  * PMH_FX_CLASS_ORBIT with all 48 operations of the cube (pmh_fexplicit_set_box_symmetry) on one rank applies W_c in the group's symmetry-adapted basis (fshared_adapted.h)
  * instead of the orbit GEMM; read at the assembly and at every application, 0 = the GEMM.  "orbit_adapted_classes": counter of classes that took that form at their assembly,
  * "orbit_adapted_fallbacks": of classes that were eligible but failed the set-up's self-check against the GEMM and stayed on it; set to reset.  "orbit_adapted_spoil" (tests):
- * 1 = the next assembly builds its basis with one table row negated, which the self-check must catch.  Unknown name: PMH_ERR_ARG. */
+ * 1 = the next assembly builds its basis with one table row negated, which the self-check must catch.  "orbit_narrow" (tests' A/B, default 1): read at the assembly; a class on
+ * that form whose multivector has at most 16 columns (two groups of 8 blocks) runs the transforms sized for it (k_fxa_narrow), 0 = the wide transforms for every width; the
+ * results are the same bits either way.  Unknown name: PMH_ERR_ARG. */
 int pmh_set_knob(const char *name, int value);
 int pmh_get_knob(const char *name, int *value);
 int pmh_finalize(pmh_ctx ctx);
@@ -1266,9 +1268,14 @@ int pmh_fexplicit_orbit_plan_info(pmh_fexplicit E, int cls, long long info[24]);
 /* pmh_fexplicit_orbit_adapted_info: what the block products (k_fxa_prod) run for class cls while it applies W_c in the symmetry-adapted basis (pmh_fexplicit_orbit_adapted);
  * called by nothing inside the solvers.  20 entries per irrep i = 0 .. 9 at info + 20 i: {0 d, 1 m, 2 k steps of 8 columns nks, 3 blocks of 16 output rows, 4 blocks of 16
  * columns, 5 .. 8 work items of 1 / 2 / 3 / 4 blocks of columns, 9 .. 12 trips of waves 0 .. 3 on an item of 1 or 2 blocks, 13 .. 16 on an item of 3 or 4, 17 / 18 k steps
- * per trip of the two kinds (a wave's k range is its trips in increasing order), 19 zero}.  PMH_ERR_ARG for a storage other than PMH_FX_CLASS_ORBIT or a class out of
- * range, PMH_ERR_STATE where the class is on the GEMM. */
+ * per trip of the two kinds (a wave's k range is its trips in increasing order), 19 whether the class's transforms are the narrow kernels (k_fxa_narrow; the same in
+ * every irrep's entry)}.  PMH_ERR_ARG for a storage other than PMH_FX_CLASS_ORBIT or a class out of range, PMH_ERR_STATE where the class is on the GEMM. */
 int pmh_fexplicit_orbit_adapted_info(pmh_fexplicit E, int cls, long long info[200]);
+/* pmh_fexplicit_orbit_adapted_transform (tests; called by nothing inside the solvers): ONE transform of class cls as the application launches it.  inverse = 0: in is a
+ * multivector in the numbering of pmh_fexplicit_dense_mult (zero off the touched sets), out receives X^ = U' X as n_c x NC doubles, entry (basis function r in the numbering
+ * of pmh_orbit_basis, column = group * 8 + slot) at r * NC + column, NC = 8 * groups.  inverse = 1: in is Y^ in that order, out receives the multivector Y = U Y^ (zero where
+ * no block touches).  Device arrays.  PMH_ERR_STATE where the class is on the GEMM. */
+int pmh_fexplicit_orbit_adapted_transform(pmh_fexplicit E, int cls, int inverse, const double *in, double *out);
 /* U = K^+ F for 8 columns per block at once: F, U device arrays of 8 n doubles, entry (dof i, column r) at i * 8 + r; K, the V-cycle (pmh_matinv_set_pc_mg), the kernel
  * basis (pmh_matinv_set_nullspace: K^+ = P_R K^- P_R) and the tolerances are the solver's own; every (block, column) pair converges by its own test.  PMH_ERR_SUP where
  * the multi-right-hand-side kernels do not apply (K without regular 3 x 3 blocks, a V-cycle other than the fused fp32 one, the left generalised inverse). */

@@ -485,6 +485,7 @@ _PROTOS = {
     "pmh_fexplicit_assemble_window": [vp, vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, c_int_p, C.POINTER(C.c_longlong), c_int_p],
     "pmh_fexplicit_orbit_plan_info": [vp, C.c_int, vp],
     "pmh_fexplicit_orbit_adapted_info": [vp, C.c_int, vp],
+    "pmh_fexplicit_orbit_adapted_transform": [vp, C.c_int, C.c_int, vp, vp],
     "pmh_fexplicit_timing_enable": [vp, C.c_int, C.c_int],
     "pmh_fexplicit_timing_get": [vp, c_int_p, c_double_p, c_double_p],
     "pmh_matinv_attach_explicit": [vp, vp],

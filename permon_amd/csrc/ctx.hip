@@ -72,6 +72,7 @@ static int *knob_by_name(const char *name)
   if (!strcmp(name, "orbit_adapted_classes")) return &pmh_knobs().orbit_adapted_classes;
   if (!strcmp(name, "orbit_adapted_fallbacks")) return &pmh_knobs().orbit_adapted_fallbacks;
   if (!strcmp(name, "orbit_adapted_spoil")) return &pmh_knobs().orbit_adapted_spoil;
+  if (!strcmp(name, "orbit_narrow")) return &pmh_knobs().orbit_narrow;
   return nullptr;
 }
 extern "C" int pmh_set_knob(const char *name, int value)

@@ -1026,6 +1026,13 @@ extern "C" int pmh_fexplicit_orbit_adapted_info(pmh_fexplicit E, int cls, long l
   return fxs_orbit_adapted_info(E->sh, cls, info);
 }
 
+extern "C" int pmh_fexplicit_orbit_adapted_transform(pmh_fexplicit E, int cls, int inverse, const double *in, double *out)
+{
+  PMH_ARG(E && in && out);
+  if (!E->sh || E->storage != PMH_FX_CLASS_ORBIT) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_orbit_adapted_transform: needs the PMH_FX_CLASS_ORBIT storage");
+  return fxs_orbit_adapted_transform(E->sh, cls, inverse, in, out);
+}
+
 int pmh_fexplicit_set_window(pmh_fexplicit_s *E, fx_batch_window *w)
 {
   PMH_ARG(E);

@@ -27,5 +27,6 @@ int       fxs_get_block(fx_shared *S, int b, int n, const int *gamma, double *ou
 int       fxs_test_load_class(fx_shared *S, int c, const double *W_host, int *all_loaded); // orbit storage, tests: the representatives' rows of class c from a host matrix
 int       fxs_orbit_plan_info(fx_shared *S, int c, long long info[24]);
 int       fxs_orbit_adapted_info(fx_shared *S, int c, long long info[200]);
+int       fxs_orbit_adapted_transform(fx_shared *S, int c, int inverse, const double *in, double *out); // tests: one transform of the symmetry-adapted form alone
 int       fxs_timing_enable(fx_shared *S, int max_launches);
 int       fxs_timing_get(fx_shared *S, int *launches, double *total_ms, double *first_kernel_ms);

@@ -304,7 +304,7 @@ static void fxa_free(pmh_ctx ctx, fxs_class &C)
   if (!a) return;
   if (a->Wh) (void)hipFree(a->Wh);
   for (void *q : {(void *)a->d_ir, (void *)a->d_tab, (void *)a->Xh, (void *)a->Yh, (void *)a->d_toff, (void *)a->d_osize, (void *)a->d_tbase, (void *)a->d_opos, (void *)a->d_rowinfo, (void *)a->d_items,
-                  (void *)a->d_tmask})
+                  (void *)a->d_tmask, (void *)a->d_tabN, (void *)a->d_tabNT, (void *)a->d_nfx, (void *)a->d_nyd, (void *)a->d_nxh, (void *)a->d_nyh})
     if (q) pmh_free(ctx, q);
   delete a;
   C.oa = nullptr;
@@ -627,23 +627,41 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_fxo_signed_copy(long long n, int 
 
 // ---- orbit storage applied in the symmetry-adapted basis (kernels: fshared_adapted.h, basis: orbitbasis.hip) ---------------------------------------------------
 // forward transform, the ten blocks' products, inverse transform; the mid event (fxs_timing_get: first_kernel_ms) is recorded before the last launch
+// one class's transform, X^ = U' X (inv = false) or Y = U Y^: k_fxa_narrow where the set-up chose it (fxa_class::narrow), k_fxa_transform otherwise
+static void fxa_launch_transform(fx_shared *S, const fxs_class &C, bool inv)
+{
+  const fxa_class *a  = C.oa;
+  hipStream_t      st = S->ctx->stream;
+  if (a->narrow) {
+    const dim3 grid(a->norb, C.ngroups), block(FXN_T);
+    if (inv)
+      hipLaunchKernelGGL(k_fxa_narrow<true>, grid, block, 0, st, (const double *)a->d_tabNT, (const int *)a->d_osize, (const int *)a->d_nyd, (const long long *)a->d_nyh, a->norb, (long long)C.ld * FXS_S,
+                         (const double *)a->Yh, S->Y + C.xoff);
+    else
+      hipLaunchKernelGGL(k_fxa_narrow<false>, grid, block, 0, st, (const double *)a->d_tabN, (const int *)a->d_osize, (const int *)a->d_nfx, (const long long *)a->d_nxh, a->norb, 2LL * C.ld * FXS_S,
+                         (const double *)(S->X2 + 2 * C.xoff), a->Xh);
+    return;
+  }
+  const dim3 grid(a->norb, (a->NC + FXA_CB - 1) / FXA_CB);
+  if (inv)
+    hipLaunchKernelGGL(k_fxa_transform<true>, grid, dim3(PMH_BLOCK), 0, st, (const fxa_irrep *)a->d_ir, (const double *)a->d_tab, (const long long *)a->d_toff, (const int *)a->d_osize, (const int *)a->d_tbase,
+                       (const int *)a->d_opos, (const int *)a->d_rowinfo, a->NC, C.nc, C.ld, C.xoff, (const double *)S->X2, a->Xh, (const double *)a->Yh, S->Y, (const char *)a->d_tmask);
+  else
+    hipLaunchKernelGGL(k_fxa_transform<false>, grid, dim3(PMH_BLOCK), 0, st, (const fxa_irrep *)a->d_ir, (const double *)a->d_tab, (const long long *)a->d_toff, (const int *)a->d_osize, (const int *)a->d_tbase,
+                       (const int *)a->d_opos, (const int *)a->d_rowinfo, a->NC, C.nc, C.ld, C.xoff, (const double *)S->X2, a->Xh, (const double *)a->Yh, S->Y, (const char *)a->d_tmask);
+}
+
 static int fxa_launch(fx_shared *S)
 {
   hipStream_t st = S->ctx->stream;
   for (fxs_class &C : S->C)
-    if (fxa_class *a = C.oa)
-      hipLaunchKernelGGL(k_fxa_transform<false>, dim3(a->norb, (a->NC + FXA_CB - 1) / FXA_CB), dim3(PMH_BLOCK), 0, st, (const fxa_irrep *)a->d_ir, (const double *)a->d_tab, (const long long *)a->d_toff,
-                         (const int *)a->d_osize, (const int *)a->d_tbase, (const int *)a->d_opos, (const int *)a->d_rowinfo, a->NC, C.nc, C.ld, C.xoff, (const double *)S->X2, a->Xh, (const double *)a->Yh, S->Y,
-                         (const char *)a->d_tmask);
+    if (C.oa) fxa_launch_transform(S, C, false);
   for (fxs_class &C : S->C)
     if (fxa_class *a = C.oa)
       if (a->nitems) hipLaunchKernelGGL(k_fxa_prod, dim3(a->nitems), dim3(64 * FXA_WAVES), 0, st, (const int *)a->d_items, (const fxa_irrep *)a->d_ir, (const double *)a->Wh, (const double *)a->Xh, a->Yh);
   if (S->ev_mid_pending >= 0) PMH_HIP(hipEventRecord(S->ev_mid[S->ev_mid_pending], st));
   for (fxs_class &C : S->C)
-    if (fxa_class *a = C.oa)
-      hipLaunchKernelGGL(k_fxa_transform<true>, dim3(a->norb, (a->NC + FXA_CB - 1) / FXA_CB), dim3(PMH_BLOCK), 0, st, (const fxa_irrep *)a->d_ir, (const double *)a->d_tab, (const long long *)a->d_toff,
-                         (const int *)a->d_osize, (const int *)a->d_tbase, (const int *)a->d_opos, (const int *)a->d_rowinfo, a->NC, C.nc, C.ld, C.xoff, (const double *)S->X2, a->Xh, (const double *)a->Yh, S->Y,
-                         (const char *)a->d_tmask);
+    if (C.oa) fxa_launch_transform(S, C, true);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
@@ -674,9 +692,16 @@ static int fxa_build_class(fx_shared *S, fxs_class &C, bool spoil)
   a->norb = B.norb, a->NC = C.ngroups * FXS_S, a->nc = C.nc;
   const int M = C.M_all;
   long long wtot = 0, htot = 0, ytot = 0;
-  double    tfl = 0.0;
-  for (int o = 0; o < B.norb; o++) tfl += 2.0 * 2.0 * (double)B.osize[o] * B.osize[o] * a->NC;
-  a->flops = a->flops_issued = tfl;
+  // the one place that chooses the transforms' kernels: k_fxa_narrow for one or two groups of columns (the record of the inverse direction packs the position into 24 bits)
+  a->narrow = pmh_knobs().orbit_narrow && a->NC <= FXN_NC && C.nc < (1 << 23);
+  double    tfl = 0.0, tfl_issued = 0.0, tab_read = 0.0;
+  for (int o = 0; o < B.norb; o++) {
+    const double no = B.osize[o], no4 = (B.osize[o] + 3) & ~3;
+    tfl += 2.0 * 2.0 * no * no * a->NC;
+    tfl_issued += 2.0 * 2.0 * no * (a->narrow ? no4 : no) * a->NC;
+    tab_read += a->narrow ? no * no4 * C.ngroups : 48.0 * 48.0; // the rows its threads read per (orbit, group) / the whole table
+  }
+  a->flops = tfl, a->flops_issued = tfl_issued;
   for (int i = 0; i < OAB_NIRREP; i++) {
     fxa_irrep &I = a->ir[i];
     I.d = B.d[i], I.m = B.m[i];
@@ -686,8 +711,8 @@ static int fxa_build_class(fx_shared *S, fxs_class &C, bool spoil)
     a->flops += 2.0 * (double)I.m * I.m * I.d * a->NC;
     a->flops_issued += 2.0 * (16.0 * I.nob) * (8.0 * I.nks) * (16.0 * I.nbt);
   }
-  // the blocks once, X^ written and read, Y^ written and read, the tables twice, X read and Y written
-  a->bytes = 8.0 * ((double)wtot + 2.0 * htot + 2.0 * ytot + 2.0 * 48.0 * 48.0 * B.norb + 2.0 * (double)C.nc * a->NC);
+  // the blocks once, X^ written and read, Y^ written and read, a table copy per transform, X read and Y written; the narrow transforms' records (12 bytes per function and group, twice)
+  a->bytes = 8.0 * ((double)wtot + 2.0 * htot + 2.0 * ytot + 2.0 * tab_read + 2.0 * (double)C.nc * a->NC) + (a->narrow ? 2.0 * 12.0 * C.nc * C.ngroups : 0.0);
   {
     const size_t bytes = sizeof(double) * (size_t)std::max(128LL, wtot);
     hipError_t   e     = hipMalloc((void **)&a->Wh, bytes);
@@ -735,6 +760,28 @@ static int fxa_build_class(fx_shared *S, fxs_class &C, bool spoil)
   PMH_CHK(fxa_upload(ctx, rowinfo, &a->d_rowinfo));
   PMH_CHK(fxa_upload(ctx, items, &a->d_items));
   PMH_CHK(fxa_upload(ctx, tmask, &a->d_tmask));
+  if (a->narrow) { // k_fxa_narrow's records (their layout: fshared_adapted.h); an orbit's functions past its size are never read
+    const size_t     nf = (size_t)C.ngroups * B.norb * 48;
+    std::vector<int> nfx((size_t)B.norb * 48, 0), nyd(nf, 0);
+    std::vector<long long> nxh(nf, 0), nyh(nf, 0);
+    for (int o = 0; o < B.norb; o++)
+      for (int t = 0; t < B.osize[o]; t++) {
+        const int        r = B.tbase[o] + t, pos = B.opos[r];
+        const fxa_irrep &I = a->ir[B.row_irrep[r]];
+        nfx[(size_t)o * 48 + t] = 2 * FXS_S * pos;
+        for (int g = 0; g < C.ngroups; g++) {
+          const size_t f = ((size_t)g * B.norb + o) * 48 + t;
+          const int    n = B.row_partner[r] * a->NC + FXS_S * g; // the group's slot 0
+          int          bits = 0;
+          for (int sl = 0; sl < FXS_S; sl++) bits |= (C.tmask[((size_t)g * C.nc + pos) * FXS_S + sl] ? 1 : 0) << sl;
+          nxh[f] = fxa_xh_off(I, B.row_index[r], n), nyh[f] = I.yoff + (long long)B.row_index[r] * I.ldy + n, nyd[f] = pos << 8 | bits;
+        }
+      }
+    PMH_CHK(fxa_upload(ctx, nfx, &a->d_nfx));
+    PMH_CHK(fxa_upload(ctx, nyd, &a->d_nyd));
+    PMH_CHK(fxa_upload(ctx, nxh, &a->d_nxh));
+    PMH_CHK(fxa_upload(ctx, nyh, &a->d_nyh));
+  }
   // the blocks: the forward transform of the representatives' rows, then the d-term combination per entry
   double *Abuf = nullptr;
   int    *d_reprow = nullptr;
@@ -791,6 +838,18 @@ static int fxa_build_class(fx_shared *S, fxs_class &C, bool spoil)
     for (int o = 0; o < B.norb; o++)
       for (int j = 0; j < B.osize[o]; j++) bad[(size_t)toffp[o] + j] = -bad[(size_t)toffp[o] + j];
     rc = pmh_memcpy_h2d(ctx, a->d_tab, bad.data(), sizeof(double) * bad.size());
+    tabp.swap(bad);
+  }
+  if (!rc && a->narrow) { // k_fxa_narrow's two copies (fxn_tab_off: the order its waves load in), of whichever table the wide kernels would read
+    std::vector<double> tabN(tabp.size()), tabNT(tabp.size());
+    for (int o = 0; o < B.norb; o++)
+      for (int t = 0; t < 48; t++)
+        for (int j = 0; j < 48; j++) {
+          const double v = tabp[(size_t)toffp[o] + t * 48 + j];
+          tabN[(size_t)toffp[o] + fxn_tab_off(t, j)] = v, tabNT[(size_t)toffp[o] + fxn_tab_off(j, t)] = v;
+        }
+    rc = fxa_upload(ctx, tabN, &a->d_tabN);
+    if (!rc) rc = fxa_upload(ctx, tabNT, &a->d_tabNT);
   }
   return rc;
 }
@@ -1164,7 +1223,7 @@ int fxs_orbit_adapted_info(fx_shared *S, int c, long long info[200])
   for (int i = 0; i < OAB_NIRREP; i++) {
     const fxa_irrep &I = a->ir[i];
     long long       *v = info + 20 * i;
-    v[0] = I.d, v[1] = I.m, v[2] = I.nks, v[3] = I.nob, v[4] = I.nbt;
+    v[0] = I.d, v[1] = I.m, v[2] = I.nks, v[3] = I.nob, v[4] = I.nbt, v[19] = a->narrow;
     for (int nbw = 1; nbw <= 4; nbw++) v[4 + nbw] = a->items_of_width[i][nbw - 1];
     for (int wide = 0; wide < 2; wide++) {
       const int U = fxa_trip_steps(wide ? 4 : 1);
@@ -1173,6 +1232,31 @@ int fxs_orbit_adapted_info(fx_shared *S, int c, long long info[200])
     }
   }
   return PMH_SUCCESS;
+}
+
+// tests: ONE transform of class c, launched as fxa_launch launches it; X^ / Y^ cross the interface as (basis function, column).  Called by nothing inside the solvers
+int fxs_orbit_adapted_transform(fx_shared *S, int c, int inverse, const double *in, double *out)
+{
+  PMH_ARG(S && in && out && c >= 0 && c < S->ncls);
+  if (!fxs_orbit_adapted(S, c)) return pmh_set_error(PMH_ERR_STATE, "pmh_fexplicit_orbit_adapted_transform: class %d does not apply W_c in the symmetry-adapted basis", c);
+  pmh_ctx          ctx = S->ctx;
+  const fxs_class &C   = S->C[c];
+  const fxa_class *a   = C.oa;
+  const long long  n   = (long long)C.nc * a->NC, ncopy = (long long)C.ngroups * C.ld * C.S;
+  const unsigned   nbx = (unsigned)((n + PMH_BLOCK - 1) / PMH_BLOCK);
+  if (inverse) {
+    PMH_CHK(pmh_memset(ctx, S->Y, 0, sizeof(double) * (size_t)S->nX));
+    hipLaunchKernelGGL(k_fxa_logical<true>, dim3(nbx), dim3(PMH_BLOCK), 0, ctx->stream, (const fxa_irrep *)a->d_ir, (const int *)a->d_rowinfo, C.nc, a->NC, in, a->Yh);
+    fxa_launch_transform(S, C, true);
+    PMH_HIP(hipGetLastError());
+    return pmh_memcpy_d2d(ctx, out, S->Y, sizeof(double) * (size_t)S->nX);
+  }
+  PMH_CHK(pmh_memcpy_d2d(ctx, S->X, in, sizeof(double) * (size_t)S->nX));
+  hipLaunchKernelGGL(k_fxo_signed_copy, dim3((unsigned)std::min<long long>(4096, (ncopy + PMH_BLOCK - 1) / PMH_BLOCK)), dim3(PMH_BLOCK), 0, ctx->stream, ncopy, C.S, (const double *)(S->X + C.xoff), S->X2 + 2 * C.xoff);
+  fxa_launch_transform(S, C, false);
+  hipLaunchKernelGGL(k_fxa_logical<false>, dim3(nbx), dim3(PMH_BLOCK), 0, ctx->stream, (const fxa_irrep *)a->d_ir, (const int *)a->d_rowinfo, C.nc, a->NC, (const double *)a->Xh, out);
+  PMH_HIP(hipGetLastError());
+  return pmh_sync(ctx);
 }
 
 int fxs_timing_enable(fx_shared *S, int max_launches)

@@ -2,8 +2,11 @@
 //
 // W_c commutes with the 48 signed coordinate permutations, so in the basis U of orbitbasis.hip  U' W_c U = (+)_i (W^_i (x) I_{d_i})  over the ten irreps:
 //     Y = U (+)_i (W^_i X^_i),  X^ = U' X,
-// three launches: k_fxa_transform<false> (per orbit a 48 x 48 table times the orbit's rows of the multivector), k_fxa_prod (all ten blocks, one work table) and
-// k_fxa_transform<true>, which writes Y where k_fxo_fin writes it.  The blocks hold sum m_i^2 entries -- as many bytes as the orbit GEMM's A -- and are read ONCE
+// three launches: the forward transform (per orbit a 48 x 48 table times the orbit's rows of the multivector), k_fxa_prod (all ten blocks, one work table) and
+// the inverse transform, which writes Y where k_fxo_fin writes it.  The transforms are k_fxa_narrow<false / true> for a multivector of at most 16 columns (the
+// headline's 8; chosen once per class by fxa_build_class, launched by fxa_launch_transform) and k_fxa_transform<false / true>, shaped for 64 columns per workgroup,
+// for wider ones (configs[3]); both sum every output in the same order, so the choice changes no bit.  X^ is written by the forward transform from the +x copies of
+// X2, which the chain's gather (k_dc_gather) fills one launch earlier.  The blocks hold sum m_i^2 entries -- as many bytes as the orbit GEMM's A -- and are read ONCE
 // per application for 8 d_i right-hand sides per group: about 5 flop per byte, a memory stream where the GEMM was compute-bound.
 //
 // Operand layouts (v_mfma_f64_16x16x4_f64: A[m = l & 15][k = l >> 4], B[k = l >> 4][n = l & 15], D column l & 15, rows (l >> 4) + 4 r):
@@ -18,7 +21,7 @@
 #define FXA_CB 64    // columns of the multivector per workgroup of the transforms
 #define FXA_LDT 49   // row length of an orbit's table in LDS
 
-__device__ __forceinline__ long long fxa_xh_off(const fxa_irrep &I, int r, int n) { return I.hoff + ((((long long)(n >> 4) * I.nks + (r >> 3)) * 64 + (r & 3) * 16 + (n & 15)) << 1) + ((r >> 2) & 1); }
+__host__ __device__ __forceinline__ long long fxa_xh_off(const fxa_irrep &I, int r, int n) { return I.hoff + ((((long long)(n >> 4) * I.nks + (r >> 3)) * 64 + (r & 3) * 16 + (n & 15)) << 1) + ((r >> 2) & 1); }
 __device__ __forceinline__ long long fxa_wh_off(const fxa_irrep &I, int r, int c) { return I.woff + ((((long long)(r >> 4) * I.nks + (c >> 3)) * 64 + (c & 3) * 16 + (r & 15)) << 1) + ((c >> 2) & 1); }
 
 // One workgroup per (orbit, block of 64 columns); every orbit's table is stored as 48 x 48 (zero past the orbit's size).  rowinfo per basis function: irrep | partner << 4 | row of W^_irrep << 8.
@@ -66,6 +69,80 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_fxa_transform(const fxa_irrep *__
       Xh[fxa_xh_off(I, ri >> 8, ((ri >> 4) & 3) * NC + col)] = s;
     }
   }
+}
+
+// The transforms of a narrow multivector (NC <= FXN_NC: one or two groups of 8 slots; the headline has one).  One workgroup of 192 threads per (orbit, group of 8
+// columns), one thread per (output row a, pair of slots): all 48 x 8 outputs in ONE round, nothing divided by a run-time number.  The thread reads ITS row of the table
+// straight from memory with 16-byte loads -- the 4 lanes of a row share every load -- so no table is staged, transposed or indexed in LDS.  The set-up stores the
+// tables for this kernel in the order its waves load them (fxn_tab_off: the k-th 16 bytes of a wave's 16 rows side by side, so one load instruction reads 256
+// contiguous bytes, not 16 bytes out of each of 16 rows 384 bytes apart) and a second time transposed for the inverse direction; a launch reads one of the two
+// copies.  LDS holds the orbit's operand block alone (3 KB), read 16 bytes at a time.
+// A thread per (row, slot) was built first: its 48 table entries are 96 VGPRs whichever way the loads are placed (108 .. 114 in all, scratch under a tighter bound), 4
+// waves per SIMD, and the headline's 715 orbits x 6 waves then do not fit the chip at once; with two slots per thread the same registers feed two outputs and 715 x 3
+// waves do.  Every look-up chain of k_fxa_transform is a record per basis function, built by fxa_build_class (orbits padded to 48 functions,
+// f = (group * orbits + orbit) * 48 + a):
+//   forward  rec[orbit * 48 + a] = 16 * position: the +x copy in the group's part of X2;  recl[f] = fxa_xh_off of the function's row for slot 0 of the group (+ 2 per slot)
+//   inverse  recl[f] = the function's entry of Y^ for slot 0 of the group (+ 1 per slot);  rec[f] = position << 8 | the 8 slots' tmask bits
+// so both kernels have two dependent global loads in front of their sums (record -> operand; the table's row comes beside them) and none behind.
+// The sums are k_fxa_transform's: per output four interleaved partial sums over b = 0, 4, 8, ..., each term by FXS_MAD, (s0 + s1) + (s2 + s3); the table's entries and
+// the operands past the orbit's size are zero -- every output keeps its bits.
+#define FXN_NC 16
+#define FXN_T (48 * FXS_S / 2)
+// entry (row a, column j) of an orbit's 48 x 48 table in k_fxa_narrow's copies: wave a >> 4, its 16-byte piece j >> 1, row a & 15 of the wave
+__host__ __device__ __forceinline__ int fxn_tab_off(int a, int j) { return ((((a >> 4) * 24 + (j >> 1)) * 16 + (a & 15)) << 1) + (j & 1); }
+
+template <bool INV>
+__global__ __launch_bounds__(FXN_T) void k_fxa_narrow(const double *__restrict__ tab, const int *__restrict__ osize, const int *__restrict__ rec, const long long *__restrict__ recl, int norb,
+                                                      long long gstride, const double *__restrict__ src, double *__restrict__ dst)
+{
+  __shared__ dbl2 vs[FXN_T];
+  const int  o = blockIdx.x, g = blockIdx.y, a = threadIdx.x >> 2, sl = 2 * (threadIdx.x & 3), no = osize[o];
+  const bool live = a < no;
+  int        r  = 0;
+  long long  rl = 0;
+  dbl2       v  = dbl2{0.0, 0.0}, t[24];
+#pragma unroll
+  for (int k = 0; k < 24; k++) t[k] = dbl2{0.0, 0.0};
+  if (live) {
+    const long long f = ((long long)g * norb + o) * 48 + a;
+    r = rec[INV ? f : o * 48 + a], rl = recl[f];
+    const dbl2 *__restrict__ row = (const dbl2 *)(tab + (long long)o * 48 * 48 + fxn_tab_off(a, 0));
+#pragma unroll
+    for (int k = 0; k < 24; k++)
+      if (2 * k < no) t[k] = row[16 * k];
+    v = *(const dbl2 *)(INV ? src + rl + sl : src + (long long)g * gstride + r + sl);
+  }
+  vs[threadIdx.x] = v; // (rows past the orbit's size: zero, the sums below run in fours)
+  __syncthreads();
+  if (!live) return;
+  dbl2 s0 = dbl2{0.0, 0.0}, s1 = s0, s2 = s0, s3 = s0; // .x: slot sl, .y: slot sl + 1
+#pragma unroll
+  for (int k = 0; k < 12; k++)
+    if (4 * k < no) {
+      const dbl2 *x = vs + 4 * k * (FXS_S / 2) + (threadIdx.x & 3);
+      const dbl2  x0 = x[0], x1 = x[FXS_S / 2], x2 = x[2 * (FXS_S / 2)], x3 = x[3 * (FXS_S / 2)];
+      s0.x = FXS_MAD(t[2 * k].x, x0.x, s0.x), s1.x = FXS_MAD(t[2 * k].y, x1.x, s1.x), s2.x = FXS_MAD(t[2 * k + 1].x, x2.x, s2.x), s3.x = FXS_MAD(t[2 * k + 1].y, x3.x, s3.x);
+      s0.y = FXS_MAD(t[2 * k].x, x0.y, s0.y), s1.y = FXS_MAD(t[2 * k].y, x1.y, s1.y), s2.y = FXS_MAD(t[2 * k + 1].x, x2.y, s2.y), s3.y = FXS_MAD(t[2 * k + 1].y, x3.y, s3.y);
+    }
+  const double sx = (s0.x + s1.x) + (s2.x + s3.x), sy = (s0.y + s1.y) + (s2.y + s3.y);
+  if (INV) {
+    double *__restrict__ y = dst + (long long)g * gstride + (long long)(r >> 8) * FXS_S + sl;
+    if ((r >> sl) & 1) y[0] = sx;
+    if ((r >> sl) & 2) y[1] = sy;
+  } else
+    dst[rl + 2 * sl] = sx, dst[rl + 2 * sl + 2] = sy;
+}
+
+// tests (pmh_fexplicit_orbit_adapted_transform): X^ / Y^ in the order (basis function, column) <-> the operand layouts
+template <bool TOYH>
+__global__ __launch_bounds__(PMH_BLOCK) void k_fxa_logical(const fxa_irrep *__restrict__ ir, const int *__restrict__ rowinfo, int nc, int NC, const double *__restrict__ in, double *__restrict__ out)
+{
+  const long long e = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x;
+  if (e >= (long long)nc * NC) return;
+  const int       ri = rowinfo[e / NC], col = (int)(e % NC), n = ((ri >> 4) & 3) * NC + col;
+  const fxa_irrep I  = ir[ri & 15];
+  if (TOYH) out[I.yoff + (long long)(ri >> 8) * I.ldy + n] = in[e];
+  else out[e] = in[fxa_xh_off(I, ri >> 8, n)];
 }
 
 // 16 rows of Y^_i = W^_i X^_i on NBW blocks of 16 columns.  The four waves of the workgroup share the k range (whole trips of U k steps, fxa_wave_k0: U KB of W^ and

@@ -36,6 +36,11 @@ struct fxa_class {
   long long *d_toff = nullptr;
   int       *d_osize = nullptr, *d_tbase = nullptr, *d_opos = nullptr, *d_rowinfo = nullptr, *d_items = nullptr;
   char      *d_tmask = nullptr;
+  // a multivector of at most 16 columns (knob orbit_narrow, decided by fxa_build_class): k_fxa_narrow with the transposed tables and its records per basis function
+  int        narrow = 0;
+  double    *d_tabN = nullptr, *d_tabNT = nullptr; // the tables and their transposes in the order of fxn_tab_off
+  int       *d_nfx = nullptr, *d_nyd = nullptr;
+  long long *d_nxh = nullptr, *d_nyh = nullptr;
   double     flops = 0.0, flops_issued = 0.0, bytes = 0.0;
   int        items_of_width[10][4] = {}; // per irrep the work items of 1 .. 4 blocks of columns (pmh_fexplicit_orbit_adapted_info)
 };

@@ -34,6 +34,7 @@ struct pmh_knobs_s {
   // PMH_NO_ORBIT_ADAPTED: orbit storage applied in the cube group's symmetry-adapted basis (fshared_adapted.h) instead of by the orbit GEMM; the counters of classes
   // that took it / that failed the set-up's self-check and stayed on the GEMM; spoil (tests): the next assembly negates one table row
   int orbit_adapted = 1, orbit_adapted_classes = 0, orbit_adapted_fallbacks = 0, orbit_adapted_spoil = 0;
+  int orbit_narrow = 1;    // tests' A/B: multivectors of at most 16 columns take the transforms sized for them (k_fxa_narrow); 0 = k_fxa_transform for every width.  Read at the assembly
   int mpgp_spec = 1;       // PMH_MPGP_NO_SPEC: batches of device-side CG steps for CSR operators (mpgp.hip)
   int mg_d0_fusion = 1;    // PMH_MG_NO_D0_FUSION: the first smoothing step written by the producer of the right-hand side (feti.hip)
   int kplus_mv = 1;        // PMH_NO_KPLUS_MV: pmh_matinv_mult on 8 congruent blocks runs them as the 8 columns of one block on the multi-right-hand-side kernels (feti.hip)

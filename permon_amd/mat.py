@@ -473,13 +473,20 @@ class MatExplicitDual:
     def orbit_adapted_info(self, cls=0):
         """"class_orbit", a class on the symmetry-adapted form: what the block products (k_fxa_prod) run (pmh_fexplicit_orbit_adapted_info), one dict per irrep: d, m,
         nks (k steps of 8 columns), nob / nbt (blocks of 16 output rows / of 16 columns), items (work items of 1, 2, 3, 4 blocks of columns), trips (of waves 0 .. 3
-        on an item of 1 or 2 blocks, steps_per_trip k steps each) and trips_wide / steps_per_trip_wide (on an item of 3 or 4)."""
+        on an item of 1 or 2 blocks, steps_per_trip k steps each) and trips_wide / steps_per_trip_wide (on an item of 3 or 4); narrow: whether the class's two
+        transforms are the kernels for at most 16 columns (k_fxa_narrow; knob "orbit_narrow" at the assembly)."""
         info = np.zeros(200, dtype=np.int64)
         check(self.ctx.L.pmh_fexplicit_orbit_adapted_info(self.h, int(cls), info.ctypes.data_as(C.c_void_p)))
         out = []
         for v in info.reshape(10, 20).tolist():
-            out.append(dict(d=v[0], m=v[1], nks=v[2], nob=v[3], nbt=v[4], items=v[5:9], trips=v[9:13], trips_wide=v[13:17], steps_per_trip=v[17], steps_per_trip_wide=v[18]))
+            out.append(dict(d=v[0], m=v[1], nks=v[2], nob=v[3], nbt=v[4], items=v[5:9], trips=v[9:13], trips_wide=v[13:17], steps_per_trip=v[17], steps_per_trip_wide=v[18],
+                            narrow=bool(v[19])))
         return out
+
+    def orbit_adapted_transform(self, cls, inverse, vin, vout):
+        """"class_orbit", tests (pmh_fexplicit_orbit_adapted_transform): one transform of class `cls` alone.  Forward: vin a multivector as dense_mult takes it, vout
+        X^ = U' X of n_c x NC doubles (basis function in orbit_basis's numbering, column = group * 8 + slot); inverse: the other way round."""
+        check(self.ctx.L.pmh_fexplicit_orbit_adapted_transform(self.h, int(cls), int(bool(inverse)), vin.p, vout.p))
 
     def assemble_stats(self):
         n, t = C.c_longlong(), C.c_double()
