@@ -907,6 +907,27 @@ int pmh_svr_predict_own(pmh_svr svr, double *f_dev /* n_local doubles */);
 int pmh_svr_test_own(pmh_svr svr, int which, pmh_svr_metrics *m);
 int pmh_svr_destroy(pmh_svr svr);
 
+/* ---- random Fourier features: Z[i, k] = scale cos(sum_j X[i, j] omega[j, k] + beta[k]) (rff.hip) ------------------------------------------------
+ * With the columns of omega drawn from a shift-invariant kernel's spectral density, beta uniform on [0, 2 pi) and scale = sqrt(2 / D), z(x) . z(x') ~ k(x, x'):
+ * pmh_svm_create / pmh_svm_multi_create / pmh_svr_create on Z (n x D row-major, D <= 256) train an approximate kernel machine, and the scoring entries take the
+ * map of the test samples.  The caller draws omega and beta: the library holds no random generator.  One kernel on the fp64 matrix cores; all arithmetic fp64
+ * whatever the storage types; every row is summed in an order fixed by d alone, without atomics: a sample has the same features alone and in any batch. */
+typedef struct pmh_rff_s *pmh_rff;
+enum { PMH_F64 = 0, PMH_F32 = 1 }; /* the type an array is stored in */
+/* omega_dev: d x D row-major, copied; beta_dev: D doubles, copied (NULL: all 0).  d < 1, D < 1, a scale that is not finite, an entry of omega or beta that is not
+ * finite (counted on the device): PMH_ERR_ARG with a message */
+int pmh_rff_create(pmh_ctx ctx, int d, int D, const double *omega_dev, const double *beta_dev, double scale, pmh_rff *f);
+/* X_dev: n x d row-major doubles (PMH_F64) or floats (PMH_F32: a value enters as (double)x); Z_dev: n x D row-major doubles or floats (rounded once, at the store).
+ * n = 0 launches nothing.  Another type code, n < 0: PMH_ERR_ARG.  Enqueues on the context's stream */
+int pmh_rff_apply(pmh_rff f, long long n, const void *X_dev, int x_type, void *Z_dev, int z_type);
+/* any pointer may be NULL; omega_host: d D doubles, beta_host: D doubles */
+int pmh_rff_get(pmh_rff f, int *d, int *D, double *omega_host, double *beta_host, double *scale);
+/* info = {rows per workgroup, rows per wave, column tile, k-block, LDS bytes, waves per workgroup, 0, 0} */
+int pmh_rff_info(pmh_rff f, int info[8]);
+/* tests: the same kernel with the identity in place of scale cos(.): T_dev (n x D doubles) = X omega + beta */
+int pmh_rff_test_args(pmh_rff f, long long n, const void *X_dev, int x_type, double *T_dev);
+int pmh_rff_destroy(pmh_rff f);
+
 
 /* ---- PC for the inner KSP of MATINV: multigrid V-cycle (PCMG semantics) ----------------------------------------
  * The reference's iterative MATINV applies K^+ with a PETSc KSP whose PC is chosen by -mat_inv_pc_type

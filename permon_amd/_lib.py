@@ -376,6 +376,12 @@ _PROTOS = {
     "pmh_svr_predict_own": [vp, vp],
     "pmh_svr_test_own": [vp, C.c_int, C.POINTER(SvrMetrics)],
     "pmh_svr_destroy": [vp],
+    "pmh_rff_create": [vp, C.c_int, C.c_int, vp, vp, C.c_double, C.POINTER(vp)],
+    "pmh_rff_apply": [vp, C.c_longlong, vp, C.c_int, vp, C.c_int],
+    "pmh_rff_get": [vp, c_int_p, c_int_p, vp, vp, c_double_p],
+    "pmh_rff_info": [vp, c_int_p],
+    "pmh_rff_test_args": [vp, C.c_longlong, vp, C.c_int, vp],
+    "pmh_rff_destroy": [vp],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],
     "pmh_smalxe_destroy": [vp],

@@ -211,6 +211,53 @@ class VecF32:
         self.p = None
 
 
+class DeviceSamples:
+    """Dense samples that already are on the device: n rows of d entries, row-major, float64 or float32 (RFFMap.transform returns one).  SVM, SVMMulticlass and
+    SVR take it wherever they take a dense X and read it where it is: nothing is uploaded, nothing converted -- its dtype must be the handle's sample_dtype.  A
+    handle created on it borrows it (and keeps a reference); the buffer stays the caller's: free() it once no handle uses it any more."""
+
+    ndim = 2
+
+    def __init__(self, ctx, n, d, dtype, buf):
+        """buf: the Vec (float64) or VecF32 (float32) of n d entries, owned from now on."""
+        self.ctx, self.n, self.d, self.dtype, self.buf = ctx, int(n), int(d), np.dtype(dtype), buf
+        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError("DeviceSamples: dtype must be float64 or float32, not %s" % self.dtype)
+
+    @classmethod
+    def empty(cls, ctx, n, d, dtype=np.float64):
+        f32 = np.dtype(dtype) == np.dtype(np.float32)
+        return cls(ctx, n, d, dtype, VecF32(ctx, int(n) * int(d)) if f32 else Vec(ctx, int(n) * int(d), zero=False))
+
+    @classmethod
+    def from_numpy(cls, ctx, X, dtype=None):
+        """Upload an (n, d) array as it is typed (float32 stays float32, anything else becomes float64), or as dtype."""
+        X = np.asarray(X)
+        if X.ndim != 2:
+            raise ValueError("DeviceSamples: X must be (n, d)")
+        dt = np.dtype(dtype) if dtype is not None else (X.dtype if X.dtype == np.float32 else np.dtype(np.float64))
+        return cls(ctx, X.shape[0], X.shape[1], dt, (VecF32 if dt == np.dtype(np.float32) else Vec).from_numpy(ctx, X.ravel()))
+
+    shape = property(lambda self: (self.n, self.d))
+
+    @property
+    def p(self):
+        """The raw device pointer; RuntimeError after free()."""
+        if self.buf is None:
+            raise RuntimeError("DeviceSamples: the samples have been freed")
+        return self.buf.p
+
+    def numpy(self):
+        """The samples as an (n, d) host array of their dtype."""
+        self.p
+        return self.buf.to_numpy().reshape(self.n, self.d)
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+            self.buf = None
+
+
 def sample_array(X, dt, who):
     """The dense samples X as the contiguous host array that goes to the device in the type dt (sample_dtype_of's answer): float64 widens whatever X holds, as
     ever; float32 keeps float32 and rounds anything else -- a finite value that rounding makes non-finite is refused."""

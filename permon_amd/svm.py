@@ -6,7 +6,8 @@
     bias: additionally y'a = 0 (SMALXE over a one-row projector; without bias MPGP alone)
 
 H = diag(y) X X' diag(y).  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width (kept in CSR on the device: 24 bytes per stored entry for
-the two orderings the operator sweeps).  Everything is computed by libpermonhip.so; there is no CPU fallback.
+the two orderings the operator sweeps), or a DeviceSamples (core.py: dense rows already on the device, such as RFFMap.transform returns -- read where they are, in
+the handle's sample_dtype).  Everything is computed by libpermonhip.so; there is no CPU fallback.
 
 Probabilities: P(y = +1 | x) = 1 / (1 + exp(A s(x) + B)) by Platt scaling (csrc/svm_proba.hip: the Newton iteration of Lin, Lin and Weng, 2007).  calibrate(X, y)
 fits A, B on the scores of samples the caller supplies -- held-out ones, or the training set with the bias that brings -- and predict_proba applies them in
@@ -19,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .core import Vec, VecF32, sample_array, sample_dtype_of
+from .core import DeviceSamples, Vec, VecF32, sample_array, sample_dtype_of
 from .mat import csr_from_scipy, is_sparse
 
 
@@ -44,19 +45,36 @@ def platt_fit(ctx, scores, y):
             yd.free()
 
 
+class _Borrowed:
+    """What a handle keeps of a DeviceSamples it was created on: a reference, so that the buffer outlives the handle's use of it; freeing it is the caller's."""
+
+    def __init__(self, samples):
+        self.samples = samples
+
+    def free(self):
+        self.samples = None
+
+
 class _Samples:
     """Samples for one library call: X, a scipy.sparse matrix (csr_from_scipy) or anything else (a contiguous array of dtype: float64, or float32 for the
-    _f32 entries), is put on the device on entry and taken off again on exit, whatever happened in between.  Entering gives n and the samples' arguments of
-    the entry: (handle,) for CSR, (n, pointer) for dense rows -- with_d: (n, d, pointer), as the create entries take them.  X is the converted array: the shape
-    checks are the caller's."""
+    _f32 entries), is put on the device on entry and taken off again on exit, whatever happened in between.  A DeviceSamples is on the device already:
+    entering uploads nothing, leaving frees nothing, and its dtype must be `dtype` -- nothing is converted.  Entering gives n and the samples' arguments of
+    the entry: (handle,) for CSR, (n, pointer) for dense rows -- with_d: (n, d, pointer), as the create entries take them.  X is the converted array (the
+    DeviceSamples itself, which has shape and ndim): the shape checks are the caller's."""
 
     def __init__(self, ctx, X, with_d=False, dtype=np.float64):
         self.ctx, self.sparse, self.with_d, self.dev = ctx, is_sparse(X), with_d, None
+        self.device = isinstance(X, DeviceSamples)
         self.f32 = not self.sparse and dtype is np.float32
-        self.X = X if self.sparse else sample_array(X, dtype, "SVM")
+        if self.device and X.dtype != np.dtype(dtype):
+            raise ValueError("SVM: the DeviceSamples hold %s and the handle's sample_dtype is %s: nothing is converted on the device (transform with out_dtype = "
+                             "the handle's sample_dtype)" % (X.dtype, np.dtype(dtype)))
+        self.X = X if self.sparse or self.device else sample_array(X, dtype, "SVM")
 
     def __enter__(self):
         n = self.X.shape[0]
+        if self.device:
+            return n, ((n, self.X.shape[1], self.X.p) if self.with_d else (n, self.X.p))
         if self.sparse:
             self.dev = csr_from_scipy(self.ctx, self.X)
             return n, (self.dev.h,)
@@ -64,7 +82,9 @@ class _Samples:
         return n, ((n, self.X.shape[1], self.dev.p) if self.with_d else (n, self.dev.p))
 
     def keep(self):
-        """The device copy, the caller's from now on."""
+        """The device copy, the caller's from now on (a DeviceSamples: a reference to it that frees nothing)."""
+        if self.device:
+            return _Borrowed(self.X)
         d, self.dev = self.dev, None
         return d
 

@@ -5,7 +5,8 @@
     dual in u = [p; q]: min 1/2 u'H^u - c^'u, H^ = [Q + D, -Q; -Q, Q + D] (MatCreateSVRDual), c^ = [t - eps; -t - eps], 0 <= u (L1: <= C_i)
     bias: additionally sum (p_i - q_i) = 0 (SMALXE over a one-row projector; without bias MPGP alone)
 
-Model: w = X'(p - q), f(x) = x . w + b.  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width, kept ONCE on the device.  Everything is
+Model: w = X'(p - q), f(x) = x . w + b.  X is an (n, d) ndarray (d <= 256), a DeviceSamples (dense rows already on the device: RFFMap.transform) or a
+scipy.sparse matrix of any width, kept ONCE on the device.  Everything is
 computed by libpermonhip.so; there is no CPU fallback.  set_subset trains on a part of the handle's samples with X staying where it is, predict_own / test_own
 score the handle's own rows without an upload, and permon_amd.svm.cross_validate loops the three over k folds.  Not here: warm starts, a grid search (SVM has
 them)."""
