@@ -922,11 +922,37 @@ int pmh_rff_create(pmh_ctx ctx, int d, int D, const double *omega_dev, const dou
 int pmh_rff_apply(pmh_rff f, long long n, const void *X_dev, int x_type, void *Z_dev, int z_type);
 /* any pointer may be NULL; omega_host: d D doubles, beta_host: D doubles */
 int pmh_rff_get(pmh_rff f, int *d, int *D, double *omega_host, double *beta_host, double *scale);
-/* info = {rows per workgroup, rows per wave, column tile, k-block, LDS bytes, waves per workgroup, 0, 0} */
+/* info = {rows per workgroup, rows per wave, column tile, k-block, LDS bytes, waves per workgroup, classes per chunk of pmh_rffdots, LDS bytes of its kernel} */
 int pmh_rff_info(pmh_rff f, int info[8]);
 /* tests: the same kernel with the identity in place of scale cos(.): T_dev (n x D doubles) = X omega + beta */
 int pmh_rff_test_args(pmh_rff f, long long n, const void *X_dev, int x_type, double *T_dev);
 int pmh_rff_destroy(pmh_rff f);
+
+/* ---- scoring on the features without storing them (rff_score.hip) ---------------------------------------------------------------------------------------
+ * dots_dev[i K + k] = sum_c scale cos(x_i . omega_c + beta_c) W_dev[k ldw + c], c < D: the dot products of the features of X (as pmh_rff_apply reads it) with the K
+ * rows of a model W (K x D row-major doubles, row stride ldw >= D); no bias is added and no n x D array exists.  The classes go through the map's kernel in
+ * chunks of info[6]; a chunk's features are computed anew (K = 10: three times).  Each product enters its sum by a fused multiply-add; a sum's order is fixed
+ * by d and D alone, without atomics: a sample's dots have the same bits alone and in any batch, and a class's dots whatever K is and wherever the class sits.
+ * n = 0 launches nothing.  n < 0, K < 1, ldw < D, another type code, a NULL pointer with n > 0: PMH_ERR_ARG.  D > 256: n ceil(D / 256) info[6] doubles of
+ * workspace for the length of the call */
+int pmh_rffdots(pmh_rff f, long long n, const void *X_dev, int x_type, int K, const double *W_dev, int ldw, double *dots_dev);
+/* tests: the same kernel with the identity in place of scale cos(.): dots_dev = (X omega + beta) W' */
+int pmh_rffdots_test_args(pmh_rff f, long long n, const void *X_dev, int x_type, int K, const double *W_dev, int ldw, double *dots_dev);
+/* The scoring entries of the three front ends on MAPPED samples: (map, n, X_dev, x_type) stands where the dense entries take (n, X_dev) -- X_dev: n x map.d
+ * row-major of x_type -- and the handle scores the features map(X) it would be given by pmh_rff_apply, through pmh_rffdots against its model and then through
+ * the kernels that finish its CSR paths (n K doubles of workspace for the call); everything after the samples is the dense entry's.  map.D must be the handle's
+ * d: PMH_ERR_ARG naming both.  The state checks (trained, calibrated) are the dense entries'.  The handle's sample type does not matter: the features are fp64
+ * and never rounded, so a handle trained on float32 features scores features here that were not rounded to float32 */
+int pmh_svm_predict_rff(pmh_svm svm, pmh_rff map, int n, const void *X_dev, int x_type, double *scores_dev, double *labels_dev);
+int pmh_svm_test_rff(pmh_svm svm, pmh_rff map, int n, const void *X_dev, int x_type, const double *y_dev, long long counts[4]);
+int pmh_svm_calibrate_rff(pmh_svm svm, pmh_rff map, int n, const void *X_dev, int x_type, const double *y_dev);
+int pmh_svm_predict_proba_rff(pmh_svm svm, pmh_rff map, int n, const void *X_dev, int x_type, double *proba_dev);
+int pmh_svm_multi_predict_rff(pmh_svm_multi svm, pmh_rff map, int n, const void *X_dev, int x_type, double *scores_dev, double *labels_dev);
+int pmh_svm_multi_test_rff(pmh_svm_multi svm, pmh_rff map, int n, const void *X_dev, int x_type, const double *labels_true_dev, long long *confusion, long long *n_unknown);
+int pmh_svm_multi_calibrate_rff(pmh_svm_multi svm, pmh_rff map, int n, const void *X_dev, int x_type, const double *labels_dev);
+int pmh_svm_multi_predict_proba_rff(pmh_svm_multi svm, pmh_rff map, int n, const void *X_dev, int x_type, double *proba_dev);
+int pmh_svr_predict_rff(pmh_svr svr, pmh_rff map, int n, const void *X_dev, int x_type, double *f_dev);
+int pmh_svr_test_rff(pmh_svr svr, pmh_rff map, int n, const void *X_dev, int x_type, const double *t_dev, pmh_svr_metrics *m);
 
 
 /* ---- PC for the inner KSP of MATINV: multigrid V-cycle (PCMG semantics) ----------------------------------------

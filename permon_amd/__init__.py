@@ -4,7 +4,7 @@ box-constraint kernels and the FETI dual operator).  All computation happens in 
 reference's QP / QPS / Mat interface for that path.  There is no CPU fallback."""
 from . import problems  # noqa: F401
 from ._lib import PermonHipError, load  # noqa: F401
-from .core import Context, CsrMat, DeviceSamples, Op, Vec  # noqa: F401
+from .core import Context, CsrMat, DeviceSamples, MappedSamples, Op, Vec  # noqa: F401
 from .qps import QP, QPS  # noqa: F401
 from .mat import MG, MatBlockDiag, MatExplicitDual, csr_block_classes, MatCreateFetiDual, MatCreatePenalized, MatCreateProjected, MatCreateSVMDual, MatCreateSVRDual, MatExtension, MatGluing, MatInv, MatRegularize, PCDualDirichletOp, PCDualLumpedOp, QPPF  # noqa: F401,E402
 from .feti import CubeFeti, DmdaFeti, box_mg_hierarchy, gluing_from_l2g, gluing_links  # noqa: F401,E402

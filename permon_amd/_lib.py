@@ -382,6 +382,18 @@ _PROTOS = {
     "pmh_rff_info": [vp, c_int_p],
     "pmh_rff_test_args": [vp, C.c_longlong, vp, C.c_int, vp],
     "pmh_rff_destroy": [vp],
+    "pmh_rffdots": [vp, C.c_longlong, vp, C.c_int, C.c_int, vp, C.c_int, vp],
+    "pmh_rffdots_test_args": [vp, C.c_longlong, vp, C.c_int, C.c_int, vp, C.c_int, vp],
+    "pmh_svm_predict_rff": [vp, vp, C.c_int, vp, C.c_int, vp, vp],
+    "pmh_svm_test_rff": [vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_calibrate_rff": [vp, vp, C.c_int, vp, C.c_int, vp],
+    "pmh_svm_predict_proba_rff": [vp, vp, C.c_int, vp, C.c_int, vp],
+    "pmh_svm_multi_predict_rff": [vp, vp, C.c_int, vp, C.c_int, vp, vp],
+    "pmh_svm_multi_test_rff": [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_longlong)],
+    "pmh_svm_multi_calibrate_rff": [vp, vp, C.c_int, vp, C.c_int, vp],
+    "pmh_svm_multi_predict_proba_rff": [vp, vp, C.c_int, vp, C.c_int, vp],
+    "pmh_svr_predict_rff": [vp, vp, C.c_int, vp, C.c_int, vp],
+    "pmh_svr_test_rff": [vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(SvrMetrics)],
     "pmh_smalxe_default_opts": [C.POINTER(SmalxeOpts)],
     "pmh_smalxe_create": [vp, vp, vp, vp, vp, vp, vp, C.POINTER(SmalxeOpts), C.POINTER(vp)],
     "pmh_smalxe_destroy": [vp],

@@ -258,9 +258,45 @@ class DeviceSamples:
             self.buf = None
 
 
+class MappedSamples:
+    """Samples seen through a feature map without their features being stored (RFFMap.lazy returns one): n rows whose D features exist only inside the kernel
+    that scores them (pmh_rffdots).  SVM, SVMMulticlass and SVR take it wherever they take TEST samples -- decision_function, predict, predict_proba,
+    calibrate, test -- and nothing is computed until one does; training needs the stored features (RFFMap.transform) and refuses it with a TypeError.
+    map: the RFFMap; source: the DeviceSamples (n, map.d) behind it, freed by free() only if owned (they were uploaded for this object)."""
+
+    ndim = 2
+
+    def __init__(self, fmap, source, owned):
+        if source.d != fmap.d:
+            raise ValueError("MappedSamples: the source must be (n, %d), not (n, %d)" % (fmap.d, source.d))
+        self.map, self.source, self.owned = fmap, source, bool(owned)
+        self.n, self.d = source.n, fmap.D
+
+    shape = property(lambda self: (self.n, self.d))
+
+    def entry_args(self):
+        """(map, n, X_dev, x_type): what the *_rff entries take where the dense ones take (n, X_dev); RuntimeError after free() or the map's destroy()."""
+        if self.source is None:
+            raise RuntimeError("MappedSamples: the samples have been freed")
+        self.map._need()
+        return self.map.h, self.n, self.source.p, 1 if self.source.dtype == np.dtype(np.float32) else 0  # PMH_F32 / PMH_F64
+
+    def free(self):
+        if self.source is not None and self.owned:
+            self.source.free()
+        self.source = None
+
+
+def refuse_mapped(X, who):
+    """Training samples must be stored: a MappedSamples where they are expected is a TypeError that says how to get them."""
+    if isinstance(X, MappedSamples):
+        raise TypeError("%s: training samples must be stored, a MappedSamples (RFFMap.lazy) holds no features: train on RFFMap.transform(X), and score lazily" % who)
+
+
 def sample_array(X, dt, who):
     """The dense samples X as the contiguous host array that goes to the device in the type dt (sample_dtype_of's answer): float64 widens whatever X holds, as
     ever; float32 keeps float32 and rounds anything else -- a finite value that rounding makes non-finite is refused."""
+    refuse_mapped(X, who)
     if dt is not np.float32:
         return np.ascontiguousarray(X, dtype=np.float64)
     X = np.asarray(X)

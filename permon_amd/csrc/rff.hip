@@ -2,7 +2,7 @@
 // whose spectral density the columns of Omega were drawn from.  A linear SVM / SVR on Z (n x D row-major, the layout pmh_svm_create takes) is then an
 // approximate kernel machine; nothing in a solver, an operator or a scoring kernel knows about it.  The library draws nothing: Omega, beta and s are the caller's.
 //
-// One kernel, k_rff<TX, TZ, EPI, NG>: TX / TZ the types X is read in and Z is written in (double or float: a float enters the arithmetic as (double)x, a result is
+// One kernel here, k_rff<TX, TZ, EPI, NG> (k_rff_dots of rff_score.hip shares its product phase and scores on the features without storing them): TX / TZ the types X is read in and Z is written in (double or float: a float enters the arithmetic as (double)x, a result is
 // rounded once, at the store; all arithmetic is fp64), EPI what happens to an argument t = x . omega_k + beta_k in registers (rff_cos: s cos(t); rff_arg: t
 // itself, for pmh_rff_test_args).  There is no n x D array of arguments.
 //
@@ -29,55 +29,9 @@
 // Bytes: n d size_x read + n D size_z written (+ d D 8 of Omega per workgroup, from L2); flops 2 n d D on the matrix cores + n D cosines on the vector ALU.
 #include "pmh_internal.h"
 
+#include "rff_internal.h"
 #include "svm_front.h"
 
-#define RFF_WAVES 8
-#define RFF_NT (64 * RFF_WAVES)
-#define RFF_RW (16 * RFF_WAVES) // rows per workgroup and trip
-#define RFF_CT 256              // column tile
-#define RFF_KB 64               // k-block
-#define RFF_LDW 260             // row stride of Omega's LDS image (doubles)
-#define RFF_LDS_BYTES ((RFF_KB * RFF_LDW + RFF_CT) * (int)sizeof(double)) // the k-block of Omega and the tile's beta, permuted alike
-
-typedef double rff_d4 __attribute__((ext_vector_type(4)));
-typedef float  rff_f4 __attribute__((ext_vector_type(4)));
-
-struct rff_cos {
-  double s;
-  __device__ __forceinline__ double operator()(double t) const { return s * cos(t); }
-};
-struct rff_arg {
-  __device__ __forceinline__ double operator()(double t) const { return t; }
-};
-
-// LDS position of column cc of the column tile: tile j = 4 (cc >> 6) + (cc & 3), lane column (cc & 63) >> 2
-static __device__ __forceinline__ int rff_pos(int cc) { return (cc & ~63) + 16 * (cc & 3) + ((cc & 63) >> 2); }
-
-// X[row][k .. k + 4) as doubles, zeros past d (xr == nullptr: a row past n, all zeros); vec: d % 4 == 0 and X aligned to the vector
-static __device__ __forceinline__ rff_d4 rff_load4(const double *xr, int k, int d, int vec)
-{
-  rff_d4 v = {0.0, 0.0, 0.0, 0.0};
-  if (!xr || k >= d) return v;
-  if (vec) return __builtin_nontemporal_load((const rff_d4 *)(xr + k));
-#pragma unroll
-  for (int e = 0; e < 4; e++)
-    if (k + e < d) v[e] = xr[k + e];
-  return v;
-}
-static __device__ __forceinline__ rff_d4 rff_load4(const float *xr, int k, int d, int vec)
-{
-  rff_d4 v = {0.0, 0.0, 0.0, 0.0};
-  if (!xr || k >= d) return v;
-  if (vec) {
-    const rff_f4 f = __builtin_nontemporal_load((const rff_f4 *)(xr + k));
-    v[0] = (double)f[0], v[1] = (double)f[1], v[2] = (double)f[2], v[3] = (double)f[3];
-    return v;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; e++)
-    if (k + e < d) v[e] = (double)xr[k + e];
-  return v;
-}
 static __device__ __forceinline__ void rff_store4(double *z, const double v[4]) { *(rff_d4 *)z = rff_d4{v[0], v[1], v[2], v[3]}; }
 static __device__ __forceinline__ void rff_store4(float *z, const double v[4]) { *(rff_f4 *)z = rff_f4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
 
@@ -95,33 +49,7 @@ __global__ __launch_bounds__(RFF_NT) void k_rff(long long n, int d, int D, const
   if (threadIdx.x < 64 * NG) Bs[sp] = sc < Dt ? beta[c0 + sc] : 0.0;
   bool staged = false;
   for (long long rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
-    const long long row = rb * RFF_RW + wave * 16 + c;
-    const TX       *xr  = row < n ? X + (size_t)row * d : nullptr;
-    rff_d4          acc[4 * NG];
-#pragma unroll
-    for (int j = 0; j < 4 * NG; j++) acc[j] = rff_d4{0.0, 0.0, 0.0, 0.0};
-    for (int kb = 0; kb < nkb; kb++) {
-      const int k0 = kb * RFF_KB, nt = (min(RFF_KB, d - k0) + 15) >> 4; // nt: the k-block's steps of 16 in use
-      rff_d4    xn = rff_load4(xr, k0 + 4 * g, d, xvec); // X one step of 16 ahead of the products
-      if (nkb > 1 || !staged) {
-        if (staged) __syncthreads(); // the previous image has been read by all waves
-        if (sc < 64 * NG)
-          for (int kk = threadIdx.x / RFF_CT; kk < 16 * nt; kk += RFF_NT / RFF_CT) Ws[kk * RFF_LDW + sp] = (k0 + kk < d && sc < Dt) ? Om[(size_t)(k0 + kk) * D + c0 + sc] : 0.0;
-        __syncthreads();
-        staged = true;
-      }
-#pragma nounroll
-      for (int t = 0; t < nt; t++) {
-        const rff_d4 xa = xn;
-        if (t + 1 < nt) xn = rff_load4(xr, k0 + 16 * (t + 1) + 4 * g, d, xvec);
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const double *wr = Ws + (16 * t + 4 * g + e) * RFF_LDW + c;
-#pragma unroll
-          for (int j = 0; j < 4 * NG; j++) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[e], wr[16 * j], acc[j], 0, 0, 0);
-        }
-      }
-    }
+    RFF_PRODUCT_ROW_BLOCK(acc, rb)
     // the epilogue on the accumulators: group q of 64 columns sits in acc[0 .. 3] on trip q
     const long long r0 = rb * RFF_RW + wave * 16 + g;
 #pragma nounroll
@@ -161,13 +89,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_rff_bad(long long m, const double
   if (b) atomicAdd(bad, b);
 }
 
-struct pmh_rff_s {
-  pmh_ctx ctx;
-  int     d, D;
-  double  scale;
-  double *omega, *beta; // device copies: d x D row-major, D
-};
-
 // one launch over ntiles column tiles from column c0base on, each with at most NG groups of 64 columns in use
 template <class TX, class TZ, class EPI, int NG> static int rff_launch_ng(pmh_rff f, long long n, const void *X, void *Z, EPI epi, int c0base, int ntiles)
 {
@@ -181,25 +102,9 @@ template <class TX, class TZ, class EPI, int NG> static int rff_launch_ng(pmh_rf
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
 }
-// the whole column tiles in one launch, the last, narrower one in a launch of the instance with as many groups of 64 columns as it needs: its products of zeros
-// stay below 64 columns' worth
 template <class TX, class TZ, class EPI> static int rff_launch(pmh_rff f, long long n, const void *X, void *Z, EPI epi)
 {
-  const int nfull = f->D / RFF_CT, tail = f->D % RFF_CT;
-  if (nfull) PMH_CHK((rff_launch_ng<TX, TZ, EPI, 4>(f, n, X, Z, epi, 0, nfull)));
-  switch ((tail + 63) / 64) {
-  case 0: return PMH_SUCCESS;
-  case 1: return rff_launch_ng<TX, TZ, EPI, 1>(f, n, X, Z, epi, nfull * RFF_CT, 1);
-  case 2: return rff_launch_ng<TX, TZ, EPI, 2>(f, n, X, Z, epi, nfull * RFF_CT, 1);
-  case 3: return rff_launch_ng<TX, TZ, EPI, 3>(f, n, X, Z, epi, nfull * RFF_CT, 1);
-  default: return rff_launch_ng<TX, TZ, EPI, 4>(f, n, X, Z, epi, nfull * RFF_CT, 1);
-  }
-}
-
-static int rff_check_type(const char *who, const char *what, int t)
-{
-  if (t != PMH_F64 && t != PMH_F32) return pmh_set_error(PMH_ERR_ARG, "%s: %s = %d, must be PMH_F64 (0) or PMH_F32 (1)", who, what, t);
-  return PMH_SUCCESS;
+  return rff_tile_launches(f->D, [&](auto ng, int tile0, int ntiles) { return rff_launch_ng<TX, TZ, EPI, decltype(ng)::value>(f, n, X, Z, epi, tile0 * RFF_CT, ntiles); });
 }
 
 extern "C" int pmh_rff_create(pmh_ctx ctx, int d, int D, const double *omega_dev, const double *beta_dev, double scale, pmh_rff *out)
@@ -276,6 +181,6 @@ extern "C" int pmh_rff_get(pmh_rff f, int *d, int *D, double *omega_host, double
 extern "C" int pmh_rff_info(pmh_rff f, int info[8])
 {
   PMH_ARG(f && info);
-  info[0] = RFF_RW, info[1] = 16, info[2] = RFF_CT, info[3] = RFF_KB, info[4] = RFF_LDS_BYTES, info[5] = RFF_WAVES, info[6] = 0, info[7] = 0;
+  info[0] = RFF_RW, info[1] = 16, info[2] = RFF_CT, info[3] = RFF_KB, info[4] = RFF_LDS_BYTES, info[5] = RFF_WAVES, info[6] = RFF_KC, info[7] = RFF_DOTS_LDS_BYTES;
   return PMH_SUCCESS;
 }

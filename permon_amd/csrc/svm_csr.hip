@@ -242,6 +242,16 @@ int pmh_svm_check_test_samples(const char *who, int d, pmh_csr Xt)
   return Xt ? svc_check_entries(Xt->nnz) : PMH_SUCCESS;
 }
 
+int sv_check_mapped(const char *who, const sv_mapped &mp, int n, int d)
+{
+  if (!mp.map) return pmh_set_error(PMH_ERR_ARG, "%s_rff: the map is NULL", who);
+  if (n < 0 || (n > 0 && !mp.X)) return pmh_set_error(PMH_ERR_ARG, "%s_rff: n = %d, X_dev %s", who, n, mp.X ? "given" : "NULL");
+  int D = 0;
+  PMH_CHK(pmh_rff_get(mp.map, nullptr, &D, nullptr, nullptr, nullptr));
+  if (D != d) return pmh_set_error(PMH_ERR_ARG, "%s_rff: the map has D = %d features, the model has d = %d", who, D, d);
+  return PMH_SUCCESS;
+}
+
 int pmh_svm_csr_row_dots(pmh_csr X, const double *wv, double *dots)
 {
   PMH_ARG(X && wv && dots);

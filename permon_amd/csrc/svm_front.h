@@ -153,19 +153,22 @@ template <class F> __global__ __launch_bounds__(PMH_BLOCK) void k_svm_dots(int n
 }
 
 // One pass of f over n samples against w, SVM_NB(n) workgroups: dense rows X (doubles, or floats where f32: the generic sweep or, LAY64 and d == 64, the
-// 64-column layout, whose dot products sum in another order: the scoring passes take it, the bias pass never did) or CSR: Xt or, Xt == nullptr, the rows of the operator own, whose dot products go through dots
-// first (nullptr: a buffer of this call).  who names the entry in the messages
-template <bool LAY64, class F> static int sv_sweep(pmh_ctx ctx, const char *who, int n, int d, const void *X, int f32, pmh_csr Xt, SvmDualBase *own, const double *w, double *dots, F f)
+// 64-column layout, whose dot products sum in another order: the scoring passes take it, the bias pass never did) or ready dot products: of the CSR samples Xt,
+// of the rows of the operator own, or of the mapped samples mp, which go through dots first (nullptr: a buffer of this call).  who names the entry in the messages
+template <bool LAY64, class F>
+static int sv_sweep(pmh_ctx ctx, const char *who, int n, int d, const void *X, int f32, pmh_csr Xt, SvmDualBase *own, const double *w, double *dots, F f, const sv_mapped *mp = nullptr)
 {
   if (n <= 0) return PMH_SUCCESS;
   const int nb = SVM_NB(n);
-  if (Xt || own) {
+  if (Xt || own || mp) {
     double *buf = dots;
     if (!buf) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&buf));
-    int rc = Xt ? pmh_svm_csr_row_dots(Xt, w, buf) : own->doubled() ? static_cast<SvrDualBase *>(own)->row_dots(w, buf) : pmh_svm_csr_op_row_dots(own, w, buf);
+    int rc = mp   ? pmh_rffdots(mp->map, n, mp->X, mp->x_type, 1, w, d, buf)
+             : Xt ? pmh_svm_csr_row_dots(Xt, w, buf)
+                  : own->doubled() ? static_cast<SvrDualBase *>(own)->row_dots(w, buf) : pmh_svm_csr_op_row_dots(own, w, buf);
     if (!rc) {
       hipLaunchKernelGGL(k_svm_dots<F>, dim3(nb), dim3(PMH_BLOCK), 0, ctx->stream, n, (const double *)buf, f);
-      if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "%s_csr: the launch failed", who);
+      if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "%s%s: the launch failed", who, mp ? "_rff" : "_csr");
     }
     if (!dots) pmh_free(ctx, buf); // (waits for the stream)
     return rc;

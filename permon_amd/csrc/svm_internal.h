@@ -155,3 +155,12 @@ int pmh_svm_csr_op_row_dots(SvmDualBase *op, const double *w, double *dots);
 // the test samples of the entry `who` (Xt, or dense rows: Xt == nullptr) against a model of d features: CSR of exactly d columns and fewer than 2^31 stored
 // entries, dense only up to the sweeps' limit; else PMH_ERR_ARG in the name of who / who_csr
 int pmh_svm_check_test_samples(const char *who, int d, pmh_csr Xt);
+// Mapped samples (the *_rff entries): the features map(X) of n x map.d rows X of x_type (PMH_F64 / PMH_F32), which exist nowhere; their dot products with a
+// model come from pmh_rffdots (rff_score.hip)
+struct sv_mapped {
+  pmh_rff     map;
+  const void *X;
+  int         x_type;
+};
+// the map's D must be the model's d (PMH_ERR_ARG naming both, in the name of who); n and X as the dense entries check them
+int sv_check_mapped(const char *who, const sv_mapped &mp, int n, int d);

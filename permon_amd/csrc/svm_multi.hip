@@ -269,6 +269,18 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_fin(int nent, int nseg, int 
   svc_finish<KC>(nent, nseg, nb, ptr, first, head, tail, [&](int c, const double(&s)[KC]) { svmm_row_done<KC>(o, c, s); });
 }
 
+// mapped samples (rff_score.hip): the chunk's dot products x_i . W_k come ready in dots (n x K, row-major: the chunk's columns k0 .. k0 + kc); one thread per row
+// hands them to svmm_row_done.  (no __restrict__ on dots: the scores may be written over them)
+template <int KC, class OUT> __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_dots(int n, const double *dots, OUT o)
+{
+  for (long long i = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * PMH_BLOCK) {
+    double s[KC];
+#pragma unroll
+    for (int j = 0; j < KC; j++) s[j] = j < o.kc ? dots[(size_t)i * o.K + o.k0 + j] : 0.0;
+    svmm_row_done<KC>(o, i, s);
+  }
+}
+
 // proba[i][k] /= sum_k proba[i][k], the sum taken k ascending; a row whose sum is 0 (every sigma underflowed) becomes 1 / K everywhere.  One row per thread
 __global__ __launch_bounds__(PMH_BLOCK) void k_svmm_normalise(int n, int K, double *__restrict__ proba)
 {
@@ -593,29 +605,36 @@ template <class OUT> static void svmm_launch_chunk(pmh_svm_multi m, int n, const
 // X (dense rows, n x d) or Xt (CSR): one sweep per chunk of classes, chunks ascending.  proba: scores receives the classes' sigmoids (m->cal), labels is nullptr
 // sel (n doubles, or nullptr: every row): dense rows are swept, and scores, labels and best written, only where sel[i] != 0; CSR has no row skipping, as on
 // the binary handle: every stored entry is swept and every row written, and the selection is k_svmm_confusion's alone
-static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *scores, double *labels, bool proba = false, const double *sel = nullptr)
+// mp: mapped samples (then X and Xt are nullptr): all K dot products of a row by one pmh_rffdots into a buffer of the call, then k_svmm_dots per chunk
+static int svmm_predict(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *scores, double *labels, bool proba = false, const double *sel = nullptr, const sv_mapped *mp = nullptr)
 {
-  PMH_ARG(m && n >= 0 && (X || Xt || n == 0));
+  PMH_ARG(m && n >= 0 && (X || Xt || n == 0 || mp));
   if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_predict: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
-  PMH_CHK(pmh_svm_check_test_samples("pmh_svm_multi_predict", m->d, Xt));
+  if (mp) PMH_CHK(sv_check_mapped("pmh_svm_multi_predict", *mp, n, m->d));
+  else PMH_CHK(pmh_svm_check_test_samples("pmh_svm_multi_predict", m->d, Xt));
   if (n == 0 || (!scores && !labels)) return PMH_SUCCESS;
   pmh_ctx ctx  = m->ctx;
-  double *best = nullptr;
-  const int kcp = Xt ? SVMM_KCC : (m->d == 64 ? SVMM_KC64 : SVMM_KCD), nch = (m->K + kcp - 1) / kcp; // the path's chunk
+  double *best = nullptr, *dots = nullptr;
+  const int kcp = (mp || Xt) ? SVMM_KCC : (m->d == 64 ? SVMM_KC64 : SVMM_KCD), nch = (m->K + kcp - 1) / kcp; // the path's chunk
   if (labels && nch > 1) PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)n, (void **)&best));
   svc_tab t;
   int     rc = Xt ? svc_tab_build(ctx, n, Xt->d_rowptr, Xt->nnz, &t, SVMM_KCC) : PMH_SUCCESS;
+  if (mp && !rc) rc = pmh_malloc(ctx, sizeof(double) * (size_t)n * m->K, (void **)&dots);
+  if (mp && !rc) rc = pmh_rffdots(mp->map, n, mp->X, mp->x_type, m->K, m->W, m->d, dots);
   for (int ch = 0; ch < nch && !rc; ch++) {
     svmm_out o{m->K, ch * kcp, std::min(kcp, m->K - ch * kcp), m->b, m->classes, scores, labels, best};
     if (proba) {
       svmm_out_proba op;
       static_cast<svmm_out &>(op) = o;
       op.A = m->cal, op.B = m->cal + m->K;
-      svmm_launch_chunk(m, n, X, Xt, t, ch, op);
-    } else svmm_launch_chunk(m, n, X, Xt, t, ch, o, sel);
+      if (mp) hipLaunchKernelGGL((k_svmm_dots<SVMM_KCC, svmm_out_proba>), dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, (const double *)dots, op);
+      else svmm_launch_chunk(m, n, X, Xt, t, ch, op);
+    } else if (mp) hipLaunchKernelGGL((k_svmm_dots<SVMM_KCC, svmm_out>), dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, (const double *)dots, o);
+    else svmm_launch_chunk(m, n, X, Xt, t, ch, o, sel);
     if (hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_svm_multi_predict: the launch failed");
   }
   if (Xt) svc_tab_free(ctx, &t); // (waits for the stream)
+  if (dots) pmh_free(ctx, dots); // (waits for the stream)
   if (best) pmh_free(ctx, best);
   return rc;
 }
@@ -629,7 +648,7 @@ extern "C" int pmh_svm_multi_predict_csr(pmh_svm_multi m, pmh_csr Xt, double *sc
 }
 
 // sel: the rows that are scored (dense) and counted, or nullptr: every row
-static int svmm_test(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *ytrue, long long *confusion, long long *n_unknown, const double *sel = nullptr)
+static int svmm_test(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *ytrue, long long *confusion, long long *n_unknown, const double *sel = nullptr, const sv_mapped *mp = nullptr)
 {
   PMH_ARG(m && ytrue && confusion && n >= 0);
   pmh_ctx             ctx = m->ctx;
@@ -639,7 +658,7 @@ static int svmm_test(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const 
   PMH_CHK(pmh_malloc(ctx, sizeof(double) * (size_t)(n ? n : 1), (void **)&pred));
   int rc = pmh_malloc(ctx, sizeof(unsigned long long) * nc, (void **)&conf);
   if (!rc) rc = pmh_memset(ctx, conf, 0, sizeof(unsigned long long) * nc);
-  if (!rc) rc = svmm_predict(m, n, X, Xt, nullptr, pred, false, sel);
+  if (!rc) rc = svmm_predict(m, n, X, Xt, nullptr, pred, false, sel, mp);
   if (!rc && n > 0) {
     if (sel) hipLaunchKernelGGL(k_svmm_confusion<1>, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->K, (const double *)m->classes, (const double *)pred, ytrue, conf, sel);
     else hipLaunchKernelGGL(k_svmm_confusion<0>, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, ctx->stream, n, m->K, (const double *)m->classes, (const double *)pred, ytrue, conf);
@@ -707,14 +726,14 @@ static int svmm_upload_cal(pmh_svm_multi m)
 }
 
 // one scoring call for all K classes, then fit k on column k of the scores in place, "label == class k" against the rest
-static int svmm_calibrate(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *labels)
+static int svmm_calibrate(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, const double *labels, const sv_mapped *mp = nullptr)
 {
   PMH_ARG(m && n >= 0 && (labels || n == 0));
   if (!m->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_calibrate: call pmh_svm_multi_train or pmh_svm_multi_set_model first");
   m->calibrated  = 0;
   double *scores = nullptr;
   PMH_CHK(pmh_malloc(m->ctx, sizeof(double) * (size_t)(n ? n : 1) * m->K, (void **)&scores));
-  int rc = svmm_predict(m, n, X, Xt, scores, nullptr);
+  int rc = svmm_predict(m, n, X, Xt, scores, nullptr, false, nullptr, mp);
   for (int k = 0; k < m->K && !rc; k++)
     rc = pmh_svm_platt_fit_strided(m->ctx, n, scores + k, m->K, labels, m->h_classes[(size_t)k], 0, &m->h_A[(size_t)k], &m->h_B[(size_t)k], &m->cal_st[(size_t)k]);
   pmh_free(m->ctx, scores);
@@ -757,11 +776,11 @@ extern "C" int pmh_svm_multi_get_calibration(pmh_svm_multi m, double *A_host, do
   return PMH_SUCCESS;
 }
 
-static int svmm_predict_proba(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *proba)
+static int svmm_predict_proba(pmh_svm_multi m, int n, const double *X, pmh_csr Xt, double *proba, const sv_mapped *mp = nullptr)
 {
   PMH_ARG(m && (proba || n == 0));
   if (m->trained && !m->calibrated) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_multi_predict_proba: call pmh_svm_multi_calibrate or pmh_svm_multi_set_calibration first");
-  PMH_CHK(svmm_predict(m, n, X, Xt, proba, nullptr, true));
+  PMH_CHK(svmm_predict(m, n, X, Xt, proba, nullptr, true, nullptr, mp));
   if (n > 0) {
     hipLaunchKernelGGL(k_svmm_normalise, dim3(pmh_vec_grid(n)), dim3(PMH_BLOCK), 0, m->ctx->stream, n, m->K, proba);
     PMH_HIP(hipGetLastError());
@@ -775,4 +794,26 @@ extern "C" int pmh_svm_multi_predict_proba_csr(pmh_svm_multi m, pmh_csr Xt, doub
 {
   PMH_ARG(m && Xt);
   return svmm_predict_proba(m, Xt->nrows, nullptr, Xt, proba_dev);
+}
+
+// ---- mapped samples (rff_score.hip) -------------------------------------------------------------------------------------------------------------------------------
+extern "C" int pmh_svm_multi_predict_rff(pmh_svm_multi m, pmh_rff map, int n, const void *X_dev, int x_type, double *scores_dev, double *labels_dev)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svmm_predict(m, n, nullptr, nullptr, scores_dev, labels_dev, false, nullptr, &mp);
+}
+extern "C" int pmh_svm_multi_test_rff(pmh_svm_multi m, pmh_rff map, int n, const void *X_dev, int x_type, const double *labels_true_dev, long long *confusion, long long *n_unknown)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svmm_test(m, n, nullptr, nullptr, labels_true_dev, confusion, n_unknown, nullptr, &mp);
+}
+extern "C" int pmh_svm_multi_calibrate_rff(pmh_svm_multi m, pmh_rff map, int n, const void *X_dev, int x_type, const double *labels_dev)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svmm_calibrate(m, n, nullptr, nullptr, labels_dev, &mp);
+}
+extern "C" int pmh_svm_multi_predict_proba_rff(pmh_svm_multi m, pmh_rff map, int n, const void *X_dev, int x_type, double *proba_dev)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svmm_predict_proba(m, n, nullptr, nullptr, proba_dev, &mp);
 }

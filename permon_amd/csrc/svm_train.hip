@@ -433,13 +433,16 @@ void pmh_svm_own_samples(pmh_svm s, const void **X, int *f32, pmh_csr *Xcsr, con
 
 // X (dense rows, n x d: doubles, or floats where f32 -- the test samples' type, whatever the handle was trained on) or Xt (CSR)
 // own: the handle's own samples (X or, CSR, the operator's tables: Xt == nullptr); sel: which of them the counts are taken over
-static int svm_predict(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts, bool own = false, svm_sel sel = svm_sel())
+// mp: mapped samples (then X, f32 and Xt are not looked at)
+static int svm_predict(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, double *scores, double *labels, const double *ytrue, long long *counts, bool own = false, svm_sel sel = svm_sel(),
+                       const sv_mapped *mp = nullptr)
 {
-  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || own));
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || own || mp));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict: call pmh_svm_train first");
-  if (!own) PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
+  if (mp) PMH_CHK(sv_check_mapped("pmh_svm_predict", *mp, n, s->d));
+  else if (!own) PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
   // (CSR: the dot products land where the scores go; without scores in a buffer of the call)
-  PMH_CHK(sv_sweep<true>(s->ctx, "pmh_svm_predict", n, s->d, X, f32, Xt, own && s->Xcsr ? static_cast<SvmDualBase *>(s->H) : nullptr, s->w, scores, svm_classify_f{s->b, scores, labels, ytrue, sel, s->part}));
+  PMH_CHK(sv_sweep<true>(s->ctx, "pmh_svm_predict", n, s->d, X, f32, Xt, own && s->Xcsr ? static_cast<SvmDualBase *>(s->H) : nullptr, s->w, scores, svm_classify_f{s->b, scores, labels, ytrue, sel, s->part}, mp));
   if (!counts) return PMH_SUCCESS;
   PMH_CHK(pmh_svm_finish_part(s->ctx, n, SVM_NB(n), 4, -1, s->part, s->scal));
   double h[4];
@@ -491,15 +494,15 @@ extern "C" int pmh_svm_test_own(pmh_svm s, int which, long long counts[4])
 
 // ---- probabilities (Platt scaling, svm_proba.hip) ---------------------------------------------------------------------------------------------------------------
 // the scores of the calibration samples by the predict path, then the fit on them
-static int svm_calibrate(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, const double *y)
+static int svm_calibrate(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, const double *y, const sv_mapped *mp = nullptr)
 {
-  PMH_ARG(s && n >= 0 && (X || Xt || n == 0) && (y || n == 0));
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || mp) && (y || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_calibrate: call pmh_svm_train first");
   double *scores = nullptr;
   PMH_CHK(pmh_malloc(s->ctx, sizeof(double) * (size_t)(n ? n : 1), (void **)&scores));
   double              A = 0.0, B = 0.0;
   pmh_svm_platt_stats st;
-  int                 rc = svm_predict(s, n, X, f32, Xt, scores, nullptr, nullptr, nullptr);
+  int                 rc = svm_predict(s, n, X, f32, Xt, scores, nullptr, nullptr, nullptr, false, svm_sel(), mp);
   if (!rc) rc = pmh_svm_platt_fit(s->ctx, n, scores, y, &A, &B, &st);
   pmh_free(s->ctx, scores);
   PMH_CHK(rc);
@@ -537,13 +540,14 @@ extern "C" int pmh_svm_get_calibration(pmh_svm s, double *A, double *B, pmh_svm_
 }
 
 // X (dense rows, n x d: doubles, or floats where f32) or Xt (CSR): one pass over the samples
-static int svm_predict_proba(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, double *proba)
+static int svm_predict_proba(pmh_svm s, int n, const void *X, int f32, pmh_csr Xt, double *proba, const sv_mapped *mp = nullptr)
 {
-  PMH_ARG(s && n >= 0 && (X || Xt || n == 0) && (proba || n == 0));
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || mp) && (proba || n == 0));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict_proba: call pmh_svm_train first");
   if (!s->calibrated) return pmh_set_error(PMH_ERR_STATE, "pmh_svm_predict_proba: call pmh_svm_calibrate or pmh_svm_set_calibration first");
-  PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
-  return sv_sweep<true>(s->ctx, "pmh_svm_predict_proba", n, s->d, X, f32, Xt, nullptr, s->w, proba, svm_sigmoid_f{s->b, s->cal_A, s->cal_B, proba});
+  if (mp) PMH_CHK(sv_check_mapped("pmh_svm_predict_proba", *mp, n, s->d));
+  else PMH_CHK(pmh_svm_check_test_samples("pmh_svm_predict", s->d, Xt));
+  return sv_sweep<true>(s->ctx, "pmh_svm_predict_proba", n, s->d, X, f32, Xt, nullptr, s->w, proba, svm_sigmoid_f{s->b, s->cal_A, s->cal_B, proba}, mp);
 }
 
 extern "C" int pmh_svm_predict_proba(pmh_svm s, int n, const double *X_dev, double *proba_dev) { return svm_predict_proba(s, n, X_dev, 0, nullptr, proba_dev); }
@@ -553,4 +557,27 @@ extern "C" int pmh_svm_predict_proba_csr(pmh_svm s, pmh_csr Xt, double *proba_de
 {
   PMH_ARG(s && Xt);
   return svm_predict_proba(s, Xt->nrows, nullptr, 0, Xt, proba_dev);
+}
+
+// ---- mapped samples (rff_score.hip): the features' dot products with w come ready, as the CSR samples' do, and every functor applies through k_svm_dots ------------
+extern "C" int pmh_svm_predict_rff(pmh_svm s, pmh_rff map, int n, const void *X_dev, int x_type, double *scores_dev, double *labels_dev)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svm_predict(s, n, nullptr, 0, nullptr, scores_dev, labels_dev, nullptr, nullptr, false, svm_sel(), &mp);
+}
+extern "C" int pmh_svm_test_rff(pmh_svm s, pmh_rff map, int n, const void *X_dev, int x_type, const double *y_dev, long long counts[4])
+{
+  PMH_ARG(y_dev && counts);
+  const sv_mapped mp{map, X_dev, x_type};
+  return svm_predict(s, n, nullptr, 0, nullptr, nullptr, nullptr, y_dev, counts, false, svm_sel(), &mp);
+}
+extern "C" int pmh_svm_calibrate_rff(pmh_svm s, pmh_rff map, int n, const void *X_dev, int x_type, const double *y_dev)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svm_calibrate(s, n, nullptr, 0, nullptr, y_dev, &mp);
+}
+extern "C" int pmh_svm_predict_proba_rff(pmh_svm s, pmh_rff map, int n, const void *X_dev, int x_type, double *proba_dev)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svm_predict_proba(s, n, nullptr, 0, nullptr, proba_dev, &mp);
 }

@@ -288,14 +288,17 @@ extern "C" int pmh_svr_get_solver(pmh_svr s, pmh_op *H, pmh_qppf *pf, pmh_mpgp *
 }
 
 // own: the handle's own samples (X or, CSR, the operator's tables: Xt == nullptr); sel: which of them the sums are taken over, n_sel of this rank
-static int svr_score(pmh_svr s, const char *who, int n, const void *X, int f32, pmh_csr Xt, double *scores, const double *t, pmh_svr_metrics *m, bool own = false, svm_sel sel = svm_sel(), long long n_sel = -1)
+// mp: mapped samples (then X, f32 and Xt are not looked at)
+static int svr_score(pmh_svr s, const char *who, int n, const void *X, int f32, pmh_csr Xt, double *scores, const double *t, pmh_svr_metrics *m, bool own = false, svm_sel sel = svm_sel(), long long n_sel = -1,
+                     const sv_mapped *mp = nullptr)
 {
-  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || own));
+  PMH_ARG(s && n >= 0 && (X || Xt || n == 0 || own || mp));
   if (!s->trained) return pmh_set_error(PMH_ERR_STATE, "%s: call pmh_svr_train first", who);
-  if (!own) PMH_CHK(pmh_svm_check_test_samples(who, s->d, Xt));
+  if (mp) PMH_CHK(sv_check_mapped(who, *mp, n, s->d));
+  else if (!own) PMH_CHK(pmh_svm_check_test_samples(who, s->d, Xt));
   pmh_ctx ctx = s->ctx;
   // (CSR: the dot products land where the scores go; without scores in a buffer of the call)
-  PMH_CHK(sv_sweep<true>(ctx, who, n, s->d, X, f32, Xt, own && s->Xcsr ? static_cast<SvmDualBase *>(s->H) : nullptr, s->w, scores, svr_score_f{s->b, scores, t, s->epsilon, sel, s->part}));
+  PMH_CHK(sv_sweep<true>(ctx, who, n, s->d, X, f32, Xt, own && s->Xcsr ? static_cast<SvmDualBase *>(s->H) : nullptr, s->w, scores, svr_score_f{s->b, scores, t, s->epsilon, sel, s->part}, mp));
   if (!m) return PMH_SUCCESS;
   PMH_CHK(pmh_svm_finish_part(ctx, n, SVM_NB(n), SVR_NSUM, 3, s->part, s->scal));
   double h[SVR_NSUM], ng = (double)(n_sel >= 0 ? n_sel : n);
@@ -328,6 +331,18 @@ extern "C" int pmh_svr_test_csr(pmh_svr s, pmh_csr Xt, const double *t_dev, pmh_
 {
   PMH_ARG(s && Xt && t_dev && m);
   return svr_score(s, "pmh_svr_test", Xt->nrows, nullptr, 0, Xt, nullptr, t_dev, m);
+}
+// mapped samples (rff_score.hip): the features' dot products with w come ready, as the CSR samples' do
+extern "C" int pmh_svr_predict_rff(pmh_svr s, pmh_rff map, int n, const void *X_dev, int x_type, double *f_dev)
+{
+  const sv_mapped mp{map, X_dev, x_type};
+  return svr_score(s, "pmh_svr_predict", n, nullptr, 0, nullptr, f_dev, nullptr, nullptr, false, svm_sel(), -1, &mp);
+}
+extern "C" int pmh_svr_test_rff(pmh_svr s, pmh_rff map, int n, const void *X_dev, int x_type, const double *t_dev, pmh_svr_metrics *m)
+{
+  PMH_ARG(t_dev && m);
+  const sv_mapped mp{map, X_dev, x_type};
+  return svr_score(s, "pmh_svr_test", n, nullptr, 0, nullptr, nullptr, t_dev, m, false, svm_sel(), -1, &mp);
 }
 
 // ---- sample subsets, the handle's own rows ------------------------------------------------------------------------------------------------------------------------

@@ -5,25 +5,32 @@ machine, and every tool of the linear front ends -- subsets, cross-validation, g
     fmap = RFFMap(ctx, d=X.shape[1], D=256, gamma=0.5)
     Z = fmap.transform(X)                       # DeviceSamples: computed and kept on the device
     svm = SVM(ctx, C=10).fit(Z, y)
-    svm.predict(fmap.transform(Xt))
+    svm.predict(fmap.transform(Xt))          # stores the (n, D) features of the test samples, or
+    svm.predict(fmap.lazy(Xt))               # MappedSamples: scores them from the map's registers, no (n, D) array (pmh_rffdots, csrc/rff_score.hip)
 
     rbf:        k(x, x') = exp(-gamma |x - x'|_2^2),  Omega = sqrt(2 gamma) N(0, 1)
     laplacian:  k(x, x') = exp(-gamma |x - x'|_1),    Omega = gamma standard Cauchy
 
-The draw is the host's (numpy.random.default_rng(seed)); the map itself is one HIP kernel on the fp64 matrix cores; there is no CPU fallback.  Not here: sparse
-X, polynomial kernels, gamma = "scale", Nystroem features."""
+The draw is the host's (numpy.random.default_rng(seed)); the map itself is one HIP kernel on the fp64 matrix cores; there is no CPU fallback.
+
+lazy(X) is accepted wherever a front end takes TEST samples (decision_function, predict, predict_both, predict_proba, calibrate, test) and refused, with a
+TypeError, where it takes training samples.  The features are fp64 there and never rounded: a handle trained on float32 features (sample_dtype = float32) scores
+lazy features that were not rounded to float32.  The classes go through the kernel four at a time and the features are computed again for every four: nothing
+chooses between the lazy and the stored path for the caller.  dots(X, W) is the raw entry: the features' dot products with the rows of any W.
+
+Not here: sparse X, polynomial kernels, gamma = "scale", Nystroem features, training on lazy features."""
 import ctypes as ct
 import math
 
 import numpy as np
 
 from ._lib import check
-from .core import DeviceSamples, Vec
+from .core import DeviceSamples, MappedSamples, Vec
 from .mat import is_sparse
 
 KERNELS = ("rbf", "laplacian")
 TYPE_CODES = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}  # PMH_F64, PMH_F32
-INFO = ("rows_per_workgroup", "rows_per_wave", "column_tile", "k_block", "lds_bytes", "waves_per_workgroup")
+INFO = ("rows_per_workgroup", "rows_per_wave", "column_tile", "k_block", "lds_bytes", "waves_per_workgroup", "classes_per_chunk", "dots_lds_bytes")
 
 
 def draw(d, D=256, gamma=1.0, kernel="rbf", seed=0):
@@ -92,7 +99,8 @@ class RFFMap:
     scale = property(lambda self: self._get(2))
 
     def info(self):
-        """The kernel's tiling (pmh_rff_info): dict(rows_per_workgroup, rows_per_wave, column_tile, k_block, lds_bytes, waves_per_workgroup)."""
+        """The kernels' tiling (pmh_rff_info): dict(rows_per_workgroup, rows_per_wave, column_tile, k_block, lds_bytes, waves_per_workgroup) of the map and
+        (classes_per_chunk, dots_lds_bytes) of the scoring kernel behind lazy() and dots()."""
         self._need()
         v = (ct.c_int * 8)()
         check(self.L.pmh_rff_info(self.h, v))
@@ -146,6 +154,47 @@ class RFFMap:
                 T.free()
             if made:
                 src.free()
+
+    def lazy(self, X):
+        """X seen through the map as MappedSamples (n, D), for the scoring calls of SVM, SVMMulticlass and SVR: nothing is computed until a handle scores it, and
+        then no (n, D) array is made.  X as in transform; an ndarray is uploaded here and freed by the result's free(), a DeviceSamples stays the caller's."""
+        self._need()
+        src, made = self._source(X)
+        return MappedSamples(self, src, made)
+
+    def _dots(self, entry, X, W, ldw):
+        W = np.asarray(W, dtype=np.float64)
+        W = np.ascontiguousarray(W.reshape(1, -1) if W.ndim == 1 else W)
+        if W.ndim != 2 or W.shape[1] != self.D:
+            raise ValueError("RFFMap.dots: W must be (K, %d) or (%d,)" % (self.D, self.D))
+        K, ldw = W.shape[0], self.D if ldw is None else int(ldw)
+        Wp = W
+        if ldw > self.D:  # (rows ldw apart, the gaps NaN: nothing of them may be read)
+            Wp = np.full((K, ldw), np.nan)
+            Wp[:, :self.D] = W
+        src, made = self._source(X)
+        wd = out = None
+        try:
+            self._need()
+            wd = Vec.from_numpy(self.ctx, Wp.ravel()[:(K - 1) * ldw + self.D] if K else Wp.ravel())
+            out = Vec(self.ctx, max(src.n * K, 1), zero=False)
+            check(entry(self.h, src.n, src.p, TYPE_CODES[src.dtype], K, wd.p, ldw, out.p))
+            return out.to_numpy()[:src.n * K].reshape(src.n, K)
+        finally:
+            for v in (wd, out):
+                if v is not None:
+                    v.free()
+            if made:
+                src.free()
+
+    def dots(self, X, W, ldw=None):
+        """(n, K): transform(X) @ W.T without the features being stored (pmh_rffdots); W (K, D), or (D,) for K = 1; no bias.  ldw: the row stride W is given
+        to the device with (None: D)."""
+        return self._dots(self.L.pmh_rffdots, X, W, ldw)
+
+    def dot_arguments(self, X, W, ldw=None):
+        """tests: arguments(X) @ W.T from the SAME kernel with the identity in place of scale cos(.) (pmh_rffdots_test_args)."""
+        return self._dots(self.L.pmh_rffdots_test_args, X, W, ldw)
 
     def destroy(self):
         if self.h is not None:

@@ -7,7 +7,8 @@
 
 H = diag(y) X X' diag(y).  X is an (n, d) ndarray (d <= 256) or a scipy.sparse matrix of any width (kept in CSR on the device: 24 bytes per stored entry for
 the two orderings the operator sweeps), or a DeviceSamples (core.py: dense rows already on the device, such as RFFMap.transform returns -- read where they are, in
-the handle's sample_dtype).  Everything is computed by libpermonhip.so; there is no CPU fallback.
+the handle's sample_dtype).  Test samples may also be a MappedSamples (RFFMap.lazy: scored from the feature map's registers, the features never stored, through the
+_rff entries; training refuses it).  Everything is computed by libpermonhip.so; there is no CPU fallback.
 
 Probabilities: P(y = +1 | x) = 1 / (1 + exp(A s(x) + B)) by Platt scaling (csrc/svm_proba.hip: the Newton iteration of Lin, Lin and Weng, 2007).  calibrate(X, y)
 fits A, B on the scores of samples the caller supplies -- held-out ones, or the training set with the bias that brings -- and predict_proba applies them in
@@ -20,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .core import DeviceSamples, Vec, VecF32, sample_array, sample_dtype_of
+from .core import DeviceSamples, MappedSamples, Vec, VecF32, refuse_mapped, sample_array, sample_dtype_of
 from .mat import csr_from_scipy, is_sparse
 
 
@@ -60,19 +61,26 @@ class _Samples:
     _f32 entries), is put on the device on entry and taken off again on exit, whatever happened in between.  A DeviceSamples is on the device already:
     entering uploads nothing, leaving frees nothing, and its dtype must be `dtype` -- nothing is converted.  Entering gives n and the samples' arguments of
     the entry: (handle,) for CSR, (n, pointer) for dense rows -- with_d: (n, d, pointer), as the create entries take them.  X is the converted array (the
-    DeviceSamples itself, which has shape and ndim): the shape checks are the caller's."""
+    DeviceSamples itself, which has shape and ndim): the shape checks are the caller's.  A MappedSamples (test samples only: with_d is a TypeError) is on the
+    device as well, whatever its source's dtype: entering gives (map, n, pointer, type) for the _rff entries; its shape is (n, D).  suffix: the entries'."""
 
     def __init__(self, ctx, X, with_d=False, dtype=np.float64):
         self.ctx, self.sparse, self.with_d, self.dev = ctx, is_sparse(X), with_d, None
+        self.mapped = isinstance(X, MappedSamples)
+        if self.mapped and with_d:
+            refuse_mapped(X, "SVM")
         self.device = isinstance(X, DeviceSamples)
-        self.f32 = not self.sparse and dtype is np.float32
+        self.f32 = not self.sparse and not self.mapped and dtype is np.float32
+        self.suffix = "_rff" if self.mapped else "_csr" if self.sparse else "_f32" if self.f32 else ""
         if self.device and X.dtype != np.dtype(dtype):
             raise ValueError("SVM: the DeviceSamples hold %s and the handle's sample_dtype is %s: nothing is converted on the device (transform with out_dtype = "
                              "the handle's sample_dtype)" % (X.dtype, np.dtype(dtype)))
-        self.X = X if self.sparse or self.device else sample_array(X, dtype, "SVM")
+        self.X = X if self.sparse or self.device or self.mapped else sample_array(X, dtype, "SVM")
 
     def __enter__(self):
         n = self.X.shape[0]
+        if self.mapped:
+            return n, self.X.entry_args()
         if self.device:
             return n, ((n, self.X.shape[1], self.X.p) if self.with_d else (n, self.X.p))
         if self.sparse:
@@ -146,8 +154,9 @@ class _SVMHandle:
 
     sample_dtype = np.float64  # the type dense samples are stored in on the device (SVM: the sample_dtype argument)
 
-    def _entry(self, name, sparse, f32=False):
-        return getattr(self.L, self._pre + name + ("_csr" if sparse else "_f32" if f32 else ""))
+    def _entry(self, name, S=None):
+        """The entry `name` of the handle for the samples S (a _Samples: its suffix _csr, _f32, _rff or none)."""
+        return getattr(self.L, self._pre + name + (S.suffix if S is not None else ""))
 
     def _create_handle(self, X, y, *more):
         """The handle on (X, y), which it borrows for its lifetime: both stay on the device in _keep."""
@@ -158,7 +167,7 @@ class _SVMHandle:
         with S as (n, xa):
             yd = self._dev(y)
             try:
-                check(self._entry("create", S.sparse, S.f32)(self.ctx.h, *xa, yd.p, self.opts, *more, ct.byref(h)))
+                check(self._entry("create", S)(self.ctx.h, *xa, yd.p, self.opts, *more, ct.byref(h)))
             except Exception:
                 yd.free()
                 raise
@@ -167,7 +176,7 @@ class _SVMHandle:
 
     def destroy(self):
         if self.h is not None:
-            self._entry("destroy", False)(self.h)
+            self._entry("destroy")(self.h)
             self.h = None
             for v in self._keep or ():
                 v.destroy() if hasattr(v, "destroy") else v.free()
@@ -329,7 +338,7 @@ class SVM(_SVMHandle):
     def _predict(self, X, want_scores, want_labels):
         S = self._test_samples(X)
         with S as (n, xa), _vecs(self.ctx, n if want_scores else None, n if want_labels else None) as (s, l):
-            check(self._entry("predict", S.sparse, S.f32)(self.h, *xa, s.p if s else None, l.p if l else None))
+            check(self._entry("predict", S)(self.h, *xa, s.p if s else None, l.p if l else None))
             return (s.to_numpy() if s else None, l.to_numpy() if l else None)
 
     def decision_function(self, X):
@@ -347,7 +356,7 @@ class SVM(_SVMHandle):
             if S.X.ndim != 2 or S.X.shape[1] != self.d or S.X.shape[0] != yd.n:
                 raise ValueError("SVM: X must be (%d, %d)" % (yd.n, self.d))
             with S as (n, xa):
-                check(self._entry("calibrate", S.sparse, S.f32)(self.h, *xa, yd.p))
+                check(self._entry("calibrate", S)(self.h, *xa, yd.p))
         return self
 
     def set_calibration(self, A, B):
@@ -376,7 +385,7 @@ class SVM(_SVMHandle):
         """(n,): P(y = +1 | x_i) = 1 / (1 + exp(A decision_function(x_i) + B)), in one pass over X (pmh_svm_predict_proba)."""
         S = self._test_samples(X)
         with S as (n, xa), _vecs(self.ctx, n) as (p,):
-            check(self._entry("predict_proba", S.sparse, S.f32)(self.h, *xa, p.p))
+            check(self._entry("predict_proba", S)(self.h, *xa, p.p))
             return p.to_numpy()
 
     def decision_function_own(self):
@@ -406,7 +415,7 @@ class SVM(_SVMHandle):
         with S as (n, xa):
             yd = self._dev(y)
             try:
-                check(self._entry("test", S.sparse, S.f32)(self.h, *xa, yd.p, cnt))
+                check(self._entry("test", S)(self.h, *xa, yd.p, cnt))
             finally:
                 yd.free()  # (also the caller's own Vec)
         tp, fp, tn, fn = (int(c) for c in cnt)
@@ -543,9 +552,9 @@ class SVMMulticlass(_SVMHandle):
                 raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
             if t is not None:
                 conf, unk = np.zeros((self.K, self.K), dtype=np.int64), ct.c_longlong()
-                check(self._entry("test", S.sparse)(self.h, *xa, t.p, conf.ctypes.data_as(ct.c_void_p), ct.byref(unk)))
+                check(self._entry("test", S)(self.h, *xa, t.p, conf.ctypes.data_as(ct.c_void_p), ct.byref(unk)))
                 return conf, int(unk.value)
-            check(self._entry("predict", S.sparse)(self.h, *xa, s.p if s else None, l.p if l else None))
+            check(self._entry("predict", S)(self.h, *xa, s.p if s else None, l.p if l else None))
             return (s.to_numpy().reshape(n, self.K) if s else None, l.to_numpy() if l else None)
 
     def calibrate(self, X, labels):
@@ -557,7 +566,7 @@ class SVMMulticlass(_SVMHandle):
             if S.X.ndim != 2 or S.X.shape[1] != self.d or S.X.shape[0] != ld.n:
                 raise ValueError("SVMMulticlass: X must be (%d, %d)" % (ld.n, self.d))
             with S as (n, xa):
-                check(self._entry("calibrate", S.sparse)(self.h, *xa, ld.p))
+                check(self._entry("calibrate", S)(self.h, *xa, ld.p))
         return self
 
     def set_calibration(self, A, B):
@@ -592,7 +601,7 @@ class SVMMulticlass(_SVMHandle):
         if S.X.ndim != 2 or S.X.shape[1] != self.d:
             raise ValueError("SVMMulticlass: X must be (n, %d)" % self.d)
         with S as (n, xa), _vecs(self.ctx, n * self.K) as (p,):
-            check(self._entry("predict_proba", S.sparse)(self.h, *xa, p.p))
+            check(self._entry("predict_proba", S)(self.h, *xa, p.p))
             return p.to_numpy().reshape(n, self.K)
 
     def decision_function(self, X):

@@ -6,7 +6,7 @@
     bias: additionally sum (p_i - q_i) = 0 (SMALXE over a one-row projector; without bias MPGP alone)
 
 Model: w = X'(p - q), f(x) = x . w + b.  X is an (n, d) ndarray (d <= 256), a DeviceSamples (dense rows already on the device: RFFMap.transform) or a
-scipy.sparse matrix of any width, kept ONCE on the device.  Everything is
+scipy.sparse matrix of any width, kept ONCE on the device; predict and test also take a MappedSamples (RFFMap.lazy: the features are never stored).  Everything is
 computed by libpermonhip.so; there is no CPU fallback.  set_subset trains on a part of the handle's samples with X staying where it is, predict_own / test_own
 score the handle's own rows without an upload, and permon_amd.svm.cross_validate loops the three over k folds.  Not here: warm starts, a grid search (SVM has
 them)."""
@@ -174,7 +174,7 @@ class SVR(_SVMHandle):
         """(n,): f(x_i) = x_i . w + b in one pass over X (pmh_svr_predict)."""
         S = self._test_samples(X)
         with S as (n, xa), _vecs(self.ctx, n) as (f,):
-            check(self._entry("predict", S.sparse, S.f32)(self.h, *xa, f.p))
+            check(self._entry("predict", S)(self.h, *xa, f.p))
             return f.to_numpy()
 
     def test(self, X, t):
@@ -188,7 +188,7 @@ class SVR(_SVMHandle):
         with S as (n, xa):
             td = Vec.from_numpy(self.ctx, tn)
             try:
-                check(self._entry("test", S.sparse, S.f32)(self.h, *xa, td.p, ct.byref(m)))
+                check(self._entry("test", S)(self.h, *xa, td.p, ct.byref(m)))
             finally:
                 td.free()
         return {k: getattr(m, k) for k, _ in _lib.SvrMetrics._fields_}
