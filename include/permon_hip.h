@@ -1330,6 +1330,17 @@ int pmh_matinv_mult_multi(pmh_matinv M, const double *F, double *U, int *max_ite
 /* pmh_matinv_mult (MatMult_Inv, matinv.c:734-743) itself takes these kernels when the solver has exactly 8 congruent blocks (verified entry by entry by pmh_matinv_enable_bsr3)
    and the fused fp32 V-cycle: the 8 blocks' vectors are the 8 columns of ONE block.  *active: whether the next application will (knob "kplus_mv" / PMH_NO_KPLUS_MV for the A/B). */
 int pmh_matinv_multi_rhs_active(pmh_matinv M, int *active);
+/* Test entries of the block CG (tests/test_gpu_cg_paths.py; called by nothing inside the solvers, and they launch nothing).
+ * pmh_matinv_test_info: the state the last pmh_matinv_mult left on the device.  info = {0 workgroups per block of the vector kernels (wgs), 1 the product: 0 CSR, 1 3 x 3
+ * blocks, 2 the 8-column ELL copy, 2 the solver: 1 one column a block, 8 eight columns a block, 9 eight congruent blocks as the columns of one, 3 nactive, 4 done, 5 entries =
+ * blocks (one column) or columns, 6 the largest iteration count the host read, 7 operator products so far}.  For entry e < min(entries, cap): scal[2 e] = {rz, tol}, ints[2 e]
+ * = {active, its} of the parity written last (the one with the larger its; a carried frozen state makes the two equal).  scal / ints may be NULL.
+ * pmh_matinv_test_mv_*: the solver of pmh_matinv_mult_multi with its handle kept from one application to the next (_mult synchronises), and the same info for it. */
+int pmh_matinv_test_info(pmh_matinv M, long long info[8], int cap, double *scal, int *ints);
+int pmh_matinv_test_mv_create(pmh_matinv M, void **V);
+int pmh_matinv_test_mv_mult(void *V, const double *F, double *U);
+int pmh_matinv_test_mv_info(void *V, long long info[8], int cap, double *scal, int *ints);
+int pmh_matinv_test_mv_destroy(void *V);
 
 #ifdef __cplusplus
 }

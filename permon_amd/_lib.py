@@ -447,6 +447,11 @@ _PROTOS = {
     "pmh_bsr3_test_destroy": [vp],
     "pmh_matinv_mult_multi": [vp, vp, vp, c_int_p],
     "pmh_matinv_multi_rhs_active": [vp, c_int_p],
+    "pmh_matinv_test_info": [vp, C.POINTER(C.c_longlong), C.c_int, vp, vp],
+    "pmh_matinv_test_mv_create": [vp, C.POINTER(vp)],
+    "pmh_matinv_test_mv_mult": [vp, vp, vp],
+    "pmh_matinv_test_mv_info": [vp, C.POINTER(C.c_longlong), C.c_int, vp, vp],
+    "pmh_matinv_test_mv_destroy": [vp],
     "pmh_fexplicit_assemble_auto": [vp, vp, vp, vp, C.c_double, C.c_int, c_int_p],
     "pmh_matinv_timing_enable": [vp, C.c_int],
     "pmh_matinv_timing_get": [vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)],

@@ -854,6 +854,35 @@ extern "C" int pmh_matinv_multi_rhs_active(pmh_matinv M, int *active)
   return PMH_SUCCESS;
 }
 
+// tests: what the last application left on the device (permon_hip.h).  Per block the parity with the larger iteration count is the one written last (a carry makes them equal)
+int pmh_matinv_test_pick(int entries, const double *hs, const int *hi, int cap, double *scal, int *ints)
+{
+  for (int e = 0; e < entries && e < cap; e++) {
+    const int q = hi[(1 * entries + e) * 2 + 1] > hi[(0 * entries + e) * 2 + 1] ? 1 : 0;
+    for (int k = 0; k < 2; k++) {
+      if (scal) scal[2 * e + k] = hs[(q * entries + e) * 2 + k];
+      if (ints) ints[2 * e + k] = hi[(q * entries + e) * 2 + k];
+    }
+  }
+  return PMH_SUCCESS;
+}
+extern "C" int pmh_matinv_test_info(pmh_matinv M, long long info[8], int cap, double *scal, int *ints)
+{
+  PMH_ARG(M && info && cap >= 0);
+  if (M->mvc_state == 1) return pmh_matinv_mv_test_state(M->mvc, info, cap, scal, ints);
+  const int           nb = M->nblocks;
+  std::vector<double> hs(4 * (size_t)nb);
+  std::vector<int>    hi(4 * (size_t)nb);
+  int                 na = 0, dn = 0;
+  PMH_CHK(pmh_sync(M->ctx));
+  PMH_CHK(pmh_memcpy_d2h(M->ctx, hs.data(), M->d_bs, sizeof(double) * hs.size()));
+  PMH_CHK(pmh_memcpy_d2h(M->ctx, hi.data(), M->d_bi, sizeof(int) * hi.size()));
+  PMH_CHK(pmh_memcpy_d2h(M->ctx, &na, M->d_nactive, sizeof(int)));
+  PMH_CHK(pmh_memcpy_d2h(M->ctx, &dn, M->d_done, sizeof(int)));
+  info[0] = M->wgs, info[1] = M->Kb ? 1 : 0, info[2] = 1, info[3] = na, info[4] = dn, info[5] = nb, info[6] = M->last_max_its, info[7] = M->total_spmv;
+  return pmh_matinv_test_pick(nb, hs.data(), hi.data(), cap, scal, ints);
+}
+
 extern "C" int pmh_matinv_last_iterations(pmh_matinv M, int *max_block_its, long long *total_spmv)
 {
   PMH_ARG(M);

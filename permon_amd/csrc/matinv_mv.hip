@@ -550,3 +550,36 @@ extern "C" int pmh_matinv_mult_multi(pmh_matinv M, const double *F, double *U, i
   pmh_matinv_mv_destroy(V);
   return rc;
 }
+
+// ---- tests: the same solver with the handle kept between applications, and the state an application left (permon_hip.h) --------------------------------------
+int pmh_matinv_mv_test_state(pmh_matinv_mv V, long long info[8], int cap, double *scal, int *ints)
+{
+  PMH_ARG(V && info && cap >= 0);
+  std::vector<double> hs(4 * (size_t)V->ncol);
+  std::vector<int>    hi(4 * (size_t)V->ncol);
+  int                 na = 0, dn = 0;
+  PMH_CHK(pmh_sync(V->ctx));
+  PMH_CHK(pmh_memcpy_d2h(V->ctx, hs.data(), V->cs, sizeof(double) * hs.size()));
+  PMH_CHK(pmh_memcpy_d2h(V->ctx, hi.data(), V->ci, sizeof(int) * hi.size()));
+  PMH_CHK(pmh_memcpy_d2h(V->ctx, &na, V->d_nactive, sizeof(int)));
+  PMH_CHK(pmh_memcpy_d2h(V->ctx, &dn, V->d_done, sizeof(int)));
+  info[0] = V->wgs, info[1] = 2, info[2] = V->nrep == MV_R ? 9 : 8, info[3] = na, info[4] = dn, info[5] = V->ncol, info[6] = V->last_max_its, info[7] = V->products;
+  return pmh_matinv_test_pick(V->ncol, hs.data(), hi.data(), cap, scal, ints);
+}
+extern "C" int pmh_matinv_test_mv_create(pmh_matinv M, void **V)
+{
+  PMH_ARG(M && V);
+  pmh_matinv_mv W  = nullptr;
+  const int     rc = pmh_matinv_mv_create(M, &W);
+  if (rc == PMH_EPI_UNSUPPORTED) return pmh_set_error(PMH_ERR_SUP, "pmh_matinv_test_mv_create: the multi-right-hand-side solver does not apply to this K^+: %s", pmh_mv_why());
+  *V = W;
+  return rc;
+}
+extern "C" int pmh_matinv_test_mv_mult(void *V, const double *F, double *U)
+{
+  PMH_ARG(V);
+  PMH_CHK(pmh_matinv_mv_mult((pmh_matinv_mv)V, F, U));
+  return pmh_sync(((pmh_matinv_mv)V)->ctx);
+}
+extern "C" int pmh_matinv_test_mv_info(void *V, long long info[8], int cap, double *scal, int *ints) { return pmh_matinv_mv_test_state((pmh_matinv_mv)V, info, cap, scal, ints); }
+extern "C" int pmh_matinv_test_mv_destroy(void *V) { return pmh_matinv_mv_destroy((pmh_matinv_mv)V); }

@@ -68,6 +68,9 @@ int pmh_matinv_mv_mult(pmh_matinv_mv V, const double *f, double *u);            
 int pmh_matinv_mv_to_columns(pmh_matinv_mv V, const double *u, double *cols);       // cols[r * n + i] = u[i * R + r]
 int pmh_matinv_mv_columns(pmh_matinv_mv V);                                         // nblocks * R
 int pmh_matinv_mv_last_iterations(pmh_matinv_mv V);
+// tests (pmh_matinv_test_info of permon_hip.h): the state the last application left, per column; _pick (feti.hip): of the two parities the one written last
+int pmh_matinv_mv_test_state(pmh_matinv_mv V, long long info[8], int cap, double *scal, int *ints);
+int pmh_matinv_test_pick(int entries, const double *hs, const int *hi, int cap, double *scal, int *ints);
 
 // why the last pmh_mg_mv_create / pmh_matinv_mv_create answered PMH_EPI_UNSUPPORTED (a static string, for the caller's error message)
 const char *pmh_mv_why();
