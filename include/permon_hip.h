@@ -954,6 +954,36 @@ int pmh_svm_multi_predict_proba_rff(pmh_svm_multi svm, pmh_rff map, int n, const
 int pmh_svr_predict_rff(pmh_svr svr, pmh_rff map, int n, const void *X_dev, int x_type, double *f_dev);
 int pmh_svr_test_rff(pmh_svr svr, pmh_rff map, int n, const void *X_dev, int x_type, const double *t_dev, pmh_svr_metrics *m);
 
+/* ---- Nystroem features: Z = k(X, L) M (nys.hip) -----------------------------------------------------------------------------------------------------------
+ * L: m landmarks taken from the data; M (m x D) = U_r Lambda_r^{-1/2} from k(L, L) = U Lambda U', so that z(x) . z(x') = k(x, L) k(L, L)^+ k(L, x') ~ k(x, x').
+ *   PMH_NYS_RBF   k(x, l) = exp(-gamma |x - l|^2), |x - l|^2 = max((|x|^2 + |l|^2) - 2 x . l, 0)      PMH_NYS_POLY  k(x, l) = (gamma x . l + coef0)^degree
+ * The caller chooses the landmarks and computes M: the library holds no random generator and no eigen-solver.  Z is what pmh_svm_create / pmh_svm_multi_create /
+ * pmh_svr_create take.  Two kernels on the fp64 matrix cores per chunk of rows (C = k(X, L) into a workspace of chunk rows x m doubles, then Z = C M); all
+ * arithmetic fp64 whatever the storage types; no atomics; every sum in an order fixed by d and m alone: a sample has the same features alone and in any batch,
+ * whatever the chunk size.  |x - l|^2 comes from norms and a product: for a sample that is itself a landmark it is of the order of u d |x|^2, not exactly 0. */
+typedef struct pmh_nys_s *pmh_nys;
+enum { PMH_NYS_RBF = 0, PMH_NYS_POLY = 1 };
+/* landmarks_dev: m x d row-major, copied; M_dev: m x D row-major, copied.  d, m or D < 1, D > m, another kernel code, a gamma that is not positive and finite, a
+ * coef0 that is not finite, a degree outside 1 .. 16 (all three are checked for either kernel), an entry of the landmarks or of M that is not finite (counted on
+ * the device): PMH_ERR_ARG with a message */
+int pmh_nys_create(pmh_ctx ctx, int d, int m, int D, const double *landmarks_dev, int kernel, double gamma, double coef0, int degree, const double *M_dev, pmh_nys *f);
+/* C_dev (n x m row-major doubles) = k(X, L), with no workspace.  X_dev: n x d row-major doubles (PMH_F64) or floats (PMH_F32: a value enters as (double)x).
+ * n = 0 launches nothing.  Another type code, n < 0: PMH_ERR_ARG.  Enqueues on the context's stream */
+int pmh_nys_kernel(pmh_nys f, long long n, const void *X_dev, int x_type, double *C_dev);
+/* Z_dev (n x D row-major doubles or floats: rounded once, at the store) = k(X, L) M, chunk by chunk; otherwise as pmh_nys_kernel */
+int pmh_nys_apply(pmh_nys f, long long n, const void *X_dev, int x_type, void *Z_dev, int z_type);
+/* any pointer may be NULL; landmarks_host: m d doubles, M_host: m D doubles */
+int pmh_nys_get(pmh_nys f, int *d, int *m, int *D, int *kernel, double *gamma, double *coef0, int *degree, double *landmarks_host, double *M_host);
+/* info = {rows per workgroup, rows per wave, column tile, k-block, LDS bytes of the kernel behind pmh_nys_kernel, waves per workgroup, chunk rows, workspace bytes
+ * (INT_MAX if they are more)} */
+int pmh_nys_info(pmh_nys f, int info[8]);
+/* the rows of C that exist at a time in pmh_nys_apply: a positive multiple of info[0], else PMH_ERR_ARG; the workspace is allocated anew.  No result depends on it */
+int pmh_nys_set_chunk_rows(pmh_nys f, long long rows);
+/* tests: the kernel behind pmh_nys_kernel with an identity in place of the kernel function: T_dev (n x m doubles) = X L' (what = 0), or the |x - l|^2 the rbf map
+ * exponentiates (what = 1; on a PMH_NYS_POLY map: PMH_ERR_ARG) */
+int pmh_nys_test_args(pmh_nys f, long long n, const void *X_dev, int x_type, int what, double *T_dev);
+int pmh_nys_destroy(pmh_nys f);
+
 
 /* ---- PC for the inner KSP of MATINV: multigrid V-cycle (PCMG semantics) ----------------------------------------
  * The reference's iterative MATINV applies K^+ with a PETSc KSP whose PC is chosen by -mat_inv_pc_type

@@ -11,4 +11,5 @@ from .feti import CubeFeti, DmdaFeti, box_mg_hierarchy, gluing_from_l2g, gluing_
 from .svm import SVM, SVMMulticlass, grid_search  # noqa: F401,E402
 from .svr import SVR  # noqa: F401,E402
 from .rff import RFFMap  # noqa: F401,E402
+from .nystroem import NystroemMap  # noqa: F401,E402
 from .chain import FetiDualQP, FETIContactSolve, KSPFETISolve, regularize_blocks  # noqa: F401,E402

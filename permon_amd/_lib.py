@@ -382,6 +382,14 @@ _PROTOS = {
     "pmh_rff_info": [vp, c_int_p],
     "pmh_rff_test_args": [vp, C.c_longlong, vp, C.c_int, vp],
     "pmh_rff_destroy": [vp],
+    "pmh_nys_create": [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.POINTER(vp)],
+    "pmh_nys_kernel": [vp, C.c_longlong, vp, C.c_int, vp],
+    "pmh_nys_apply": [vp, C.c_longlong, vp, C.c_int, vp, C.c_int],
+    "pmh_nys_get": [vp, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p, vp, vp],
+    "pmh_nys_info": [vp, c_int_p],
+    "pmh_nys_set_chunk_rows": [vp, C.c_longlong],
+    "pmh_nys_test_args": [vp, C.c_longlong, vp, C.c_int, C.c_int, vp],
+    "pmh_nys_destroy": [vp],
     "pmh_rffdots": [vp, C.c_longlong, vp, C.c_int, C.c_int, vp, C.c_int, vp],
     "pmh_rffdots_test_args": [vp, C.c_longlong, vp, C.c_int, C.c_int, vp, C.c_int, vp],
     "pmh_svm_predict_rff": [vp, vp, C.c_int, vp, C.c_int, vp, vp],

@@ -107,6 +107,16 @@ template <class TX, class TZ, class EPI> static int rff_launch(pmh_rff f, long l
   return rff_tile_launches(f->D, [&](auto ng, int tile0, int ntiles) { return rff_launch_ng<TX, TZ, EPI, decltype(ng)::value>(f, n, X, Z, epi, tile0 * RFF_CT, ntiles); });
 }
 
+int rff_count_not_finite(pmh_ctx ctx, const char *who, const char *what, long long m, const double *a_dev, long long *nbad)
+{
+  return sv_count_bad(ctx, who, what, [&](int *cnt) { hipLaunchKernelGGL(k_rff_bad, dim3(pmh_vec_grid((int)(m < (1 << 30) ? m : (1 << 30)))), dim3(PMH_BLOCK), 0, ctx->stream, m, a_dev, cnt); }, nbad);
+}
+
+int rff_identity_apply(pmh_rff f, long long n, const double *X_dev, void *Z_dev, int z_type)
+{
+  return z_type == PMH_F64 ? rff_launch<double, double>(f, n, X_dev, Z_dev, rff_arg{}) : rff_launch<double, float>(f, n, X_dev, Z_dev, rff_arg{});
+}
+
 extern "C" int pmh_rff_create(pmh_ctx ctx, int d, int D, const double *omega_dev, const double *beta_dev, double scale, pmh_rff *out)
 {
   PMH_ARG(ctx && out);
@@ -123,8 +133,8 @@ extern "C" int pmh_rff_create(pmh_ctx ctx, int d, int D, const double *omega_dev
     if ((rc = pmh_malloc(ctx, sizeof(double) * (size_t)m, (void **)&f->omega)) || (rc = pmh_malloc(ctx, sizeof(double) * (size_t)D, (void **)&f->beta))) break;
     if ((rc = pmh_memcpy_d2d(ctx, f->omega, omega_dev, sizeof(double) * (size_t)m))) break;
     if ((rc = beta_dev ? pmh_memcpy_d2d(ctx, f->beta, beta_dev, sizeof(double) * (size_t)D) : pmh_memset(ctx, f->beta, 0, sizeof(double) * (size_t)D))) break;
-    if ((rc = sv_count_bad(ctx, "pmh_rff_create", "entries of omega", [&](int *cnt) { hipLaunchKernelGGL(k_rff_bad, dim3(pmh_vec_grid((int)(m < (1 << 30) ? m : (1 << 30)))), dim3(PMH_BLOCK), 0, ctx->stream, m, (const double *)f->omega, cnt); }, &bad_o))) break;
-    if ((rc = sv_count_bad(ctx, "pmh_rff_create", "entries of beta", [&](int *cnt) { hipLaunchKernelGGL(k_rff_bad, dim3(pmh_vec_grid(D)), dim3(PMH_BLOCK), 0, ctx->stream, (long long)D, (const double *)f->beta, cnt); }, &bad_b))) break;
+    if ((rc = rff_count_not_finite(ctx, "pmh_rff_create", "entries of omega", m, f->omega, &bad_o))) break;
+    if ((rc = rff_count_not_finite(ctx, "pmh_rff_create", "entries of beta", D, f->beta, &bad_b))) break;
     if (bad_o || bad_b) rc = pmh_set_error(PMH_ERR_ARG, "pmh_rff_create: %lld of the entries of omega and %lld of beta are not finite", bad_o, bad_b);
   } while (0);
   if (rc) {

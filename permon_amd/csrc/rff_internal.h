@@ -8,7 +8,8 @@
 //                         of a row's sum are described in rff.hip
 //   rff_tile_launches     which instance is launched over which column tiles
 //   pmh_rff_s             the map's handle
-// Device code and the handle: included by rff.hip and rff_score.hip only.
+// k_nys (nys.hip: the kernel block of the Nystroem map) expands the same product phase under its own epilogues and multiplies by M through rff_identity_apply.
+// Device code and the handle: included by rff.hip, rff_score.hip and (through nys_internal.h) nys.hip only.
 #pragma once
 #include <type_traits>
 
@@ -123,6 +124,12 @@ struct pmh_rff_s {
   double  scale;
   double *omega, *beta; // device copies: d x D row-major, D
 };
+
+// For nys.hip (definitions: rff.hip).  rff_identity_apply: Z (n x f->D of z_type) = X f->omega + f->beta for fp64 X on the device -- the launches of
+// pmh_rff_test_args, k_rff<double, TZ, rff_arg, NG>, with either type of Z.  rff_count_not_finite: *nbad = how many of a[0 .. m) are not finite, as
+// pmh_rff_create counts them (k_rff_bad)
+int rff_identity_apply(pmh_rff f, long long n, const double *X_dev, void *Z_dev, int z_type);
+int rff_count_not_finite(pmh_ctx ctx, const char *who, const char *what, long long m, const double *a_dev, long long *nbad);
 
 static inline int rff_check_type(const char *who, const char *what, int t)
 {

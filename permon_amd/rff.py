@@ -18,7 +18,7 @@ TypeError, where it takes training samples.  The features are fp64 there and nev
 lazy features that were not rounded to float32.  The classes go through the kernel four at a time and the features are computed again for every four: nothing
 chooses between the lazy and the stored path for the caller.  dots(X, W) is the raw entry: the features' dot products with the rows of any W.
 
-Not here: sparse X, polynomial kernels, gamma = "scale", Nystroem features, training on lazy features."""
+Not here: sparse X, gamma = "scale", training on lazy features.  Polynomial kernels and data-dependent (Nystroem) features: NystroemMap, nystroem.py."""
 import ctypes as ct
 import math
 
