@@ -5,20 +5,21 @@
 // operator or a scoring kernel knows about it.  The library computes no eigen-decomposition and draws nothing: L and M are the caller's.
 //
 // Two stages per chunk of rows:
-//   A  k_nys<TX, EPI, NG>: C = k(X, L) (rows x m, fp64).  The product phase is k_rff's, as the text RFF_PRODUCT_ROW_BLOCK with Omega := L' (d x m, transposed
-//      once at create): v_mfma_f64_16x16x4_f64, RFF_WAVES waves of 16 rows, a column tile of RFF_CT landmarks, k-blocks of RFF_KB in LDS; the layouts and the
-//      order of a row's sum are described in rff.hip.  The epilogue EPI (nys_internal.h) runs on the accumulators where k_rff applies + beta, cos: lane (c, g),
-//      register r, tile jm of group q is row g + 4 r, column 64 q + 4 c + jm.
-//        poly  b = gamma t + coef0 (two roundings), then v = b multiplied by b another degree - 1 times, left to right
-//        rbf   q = max((nx_i + nl_j) - 2 t, 0), k = exp(-(gamma q)).  nl_j = |l_j|^2 is computed once at create and sits in LDS where k_rff keeps beta, at
-//              rff_pos positions; nx_i = |x_i|^2 comes from k_nys_norms over the chunk (it reads the chunk of X a first time; k_nys then reads it from cache), one
-//              double per row, and a lane reads the 4 values of its rows g + 4 r
+//   A  k_rff<TX, double, EPI, NG> (rff_kernel.h), the kernel of the random Fourier features under this map's functors: C = k(X, L) (rows x m, fp64), with
+//      Omega := L' (d x m, transposed once at create) and |l|^2 where that map has beta: v_mfma_f64_16x16x4_f64, RFF_WAVES waves of 16 rows, a column tile of
+//      RFF_CT landmarks, k-blocks of RFF_KB in LDS; the layouts and the order of a row's sum are described in rff.hip.  The functor EPI (nys_internal.h) runs on the
+//      accumulators: lane (c, g), register r, tile jm of group q is row g + 4 r, column 64 q + 4 c + jm.
+//        poly  b = gamma t + coef0 (two roundings), then v = b multiplied by b another degree - 1 times, left to right.  It takes no value of a row or a column:
+//              nothing is staged and nothing loaded for it
+//        rbf   q = max((nx_i + nl_j) - 2 t, 0), k = exp(-(gamma q)).  nl_j = |l_j|^2, the launch's column vector, is computed once at create and sits in LDS at
+//              rff_pos positions; nx_i = |x_i|^2, the functor's row value, comes from k_nys_norms over the chunk (it reads the chunk of X a first time; k_rff then
+//              reads it from cache), one double per row, and a lane reads the 4 values of its rows g + 4 r
 //        nys_t, nys_q  the identities of pmh_nys_test_args
-//      NG as in k_rff: rff_tile_launches chooses the instances.
+//      NG as for the Fourier features: rff_tile_launches chooses the instances.
 //   B  Z = C M: k_rff<double, TZ, rff_arg, NG> of rff.hip on (m, D, M, beta = 0) through rff_identity_apply -- the kernel tests/test_gpu_rff.py pins.
-// pmh_nys_apply walks X in chunks of chunk_rows rows: norms (rbf), stage A into the handle's workspace of chunk_rows x m doubles, stage B from the workspace into
-// Z, so that C never exists as an n x m array in HBM and a chunk of it can be read back from the Infinity Cache.  pmh_nys_kernel is stage A straight into the
-// caller's array.
+// One walk, nys_walk, takes X in chunks of chunk_rows rows.  pmh_nys_apply: norms (rbf), stage A into the handle's workspace of chunk_rows x m doubles, stage B
+// from the workspace into Z, so that C never exists as an n x m array in HBM and a chunk of it can be read back from the Infinity Cache.  pmh_nys_kernel and
+// pmh_nys_test_args: stage A straight into the caller's array.
 //
 // The contract:
 //   - no atomics (the count of non-finite entries at create apart: an integer, the same in any order);
@@ -62,73 +63,6 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_nys_transpose(int m, int d, const
   for (long long p = (long long)blockIdx.x * PMH_BLOCK + threadIdx.x; p < tot; p += (long long)gridDim.x * PMH_BLOCK) Lt[p] = L[(p % m) * d + p / m];
 }
 
-// C[i][c0 + cc] = epi(x_i . l, |x_i|^2, |l|^2) over the launch's column tiles; D is m, the number of landmarks (the name the product phase reads)
-template <class TX, class EPI, int NG>
-__global__ __launch_bounds__(RFF_NT) void k_nys(long long n, int d, int D, const TX *__restrict__ X, const double *__restrict__ Om, const double *__restrict__ nl, const double *__restrict__ nx,
-                                                double *__restrict__ C, EPI epi, int xvec, int zvec, int c0base)
-{
-  extern __shared__ double rff_lds[];
-  double   *Ws = rff_lds, *Bs = rff_lds + RFF_KB * RFF_LDW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
-  const int c0 = c0base + blockIdx.y * RFF_CT, Dt = min(64 * NG, D - c0); // the launch's tiles have at most NG groups of 64 landmarks in use
-  const int nkb = (d + RFF_KB - 1) / RFF_KB;
-  const long long nrb = (n + RFF_RW - 1) / RFF_RW;
-  const int sc = threadIdx.x & (RFF_CT - 1), sp = rff_pos(sc); // staging: this thread's landmark of the tile and its LDS position
-  if (EPI::norms && threadIdx.x < 64 * NG) Bs[sp] = sc < Dt ? nl[c0 + sc] : 0.0;
-  bool staged = false;
-  for (long long rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
-    RFF_PRODUCT_ROW_BLOCK(acc, rb)
-    // the epilogue on the accumulators: group q of 64 landmarks sits in acc[0 .. 3] on trip q
-    const long long r0 = rb * RFF_RW + wave * 16 + g;
-    double          nxr[4] = {0.0, 0.0, 0.0, 0.0};
-    if (EPI::norms) {
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-        if (r0 + 4 * r < n) nxr[r] = nx[r0 + 4 * r];
-    }
-#pragma nounroll
-    for (int q = 0; q < NG; q++) {
-      const int cc = 64 * q + 4 * c; // the lane's 4 landmarks of the tile: cc .. cc + 3
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const long long i = r0 + 4 * r;
-        if (i < n && cc < Dt) {
-          double v[4];
-#pragma unroll
-          for (int jm = 0; jm < 4; jm++) {
-            v[jm] = epi(acc[jm][r], nxr[r], EPI::norms ? Bs[64 * q + 16 * jm + c] : 0.0);
-            __builtin_amdgcn_sched_barrier(0); // one exponential at a time, as k_rff takes its cosines
-          }
-          double *z = C + (size_t)i * D + c0 + cc;
-          if (zvec) {
-            *(rff_d4 *)z = rff_d4{v[0], v[1], v[2], v[3]}; // (m % 4 == 0: the 4 landmarks are inside together)
-          } else {
-#pragma unroll
-            for (int jm = 0; jm < 4; jm++)
-              if (cc + jm < Dt) z[jm] = v[jm];
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4 * NG - 4; j++) acc[j] = acc[j + 4];
-    }
-  }
-}
-
-// one launch over ntiles column tiles from landmark c0base on, each with at most NG groups of 64 landmarks in use
-template <class TX, class EPI, int NG> static int nys_launch_ng(pmh_nys f, long long n, const void *X, double *C, EPI epi, int c0base, int ntiles)
-{
-  auto *k = k_nys<TX, EPI, NG>;
-  PMH_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, RFF_LDS_BYTES));
-  const long long nrb  = (n + RFF_RW - 1) / RFF_RW;
-  const int       cus  = f->ctx->num_cus > 0 ? f->ctx->num_cus : 256;
-  const int       xvec = f->d % 4 == 0 && (uintptr_t)X % (4 * sizeof(TX)) == 0, zvec = f->m % 4 == 0 && (uintptr_t)C % (4 * sizeof(double)) == 0;
-  const dim3      grid((unsigned)(nrb < cus ? nrb : cus), (unsigned)ntiles);
-  hipLaunchKernelGGL(k, grid, dim3(RFF_NT), RFF_LDS_BYTES, f->ctx->stream, n, f->d, f->m, (const TX *)X, (const double *)f->lt, (const double *)f->nl, (const double *)f->nx, C, epi, xvec, zvec, c0base);
-  PMH_HIP(hipGetLastError());
-  return PMH_SUCCESS;
-}
-
 template <class TX> static int nys_norms(pmh_ctx ctx, long long n, int d, const void *X, double *nx)
 {
   const long long threads = 16 * n;
@@ -137,11 +71,11 @@ template <class TX> static int nys_norms(pmh_ctx ctx, long long n, int d, const 
   return PMH_SUCCESS;
 }
 
-// stage A of at most chunk_rows rows: the norms where the epilogue takes them, then the launches that cover the m landmarks
+// stage A of at most chunk_rows rows: the norms where the epilogue takes them, then k_rff<TX, double, EPI, NG> on (m, L', |l|^2) over the m landmarks
 template <class TX, class EPI> static int nys_stage_a(pmh_nys f, long long n, const void *X, double *C, EPI epi)
 {
-  if (EPI::norms) PMH_CHK(nys_norms<TX>(f->ctx, n, f->d, X, f->nx));
-  return rff_tile_launches(f->m, [&](auto ng, int tile0, int ntiles) { return nys_launch_ng<TX, EPI, decltype(ng)::value>(f, n, X, C, epi, tile0 * RFF_CT, ntiles); });
+  if (EPI::rows) PMH_CHK(nys_norms<TX>(f->ctx, n, f->d, X, f->nx));
+  return rff_launch<TX, double>(rff_operands{f->ctx, f->d, f->m, f->lt, f->nl}, n, X, C, epi);
 }
 template <class EPI> static int nys_stage_a(pmh_nys f, long long n, const void *X, int x_type, double *C, EPI epi)
 {
@@ -151,18 +85,20 @@ template <class EPI> static int nys_stage_a(pmh_nys f, long long n, const void *
 static int nys_stage_a(pmh_nys f, long long n, const void *X, int x_type, double *C, int what)
 {
   if (what == 0) return nys_stage_a(f, n, X, x_type, C, nys_t{});
-  if (what == 1) return nys_stage_a(f, n, X, x_type, C, nys_q{});
-  if (f->kernel == PMH_NYS_RBF) return nys_stage_a(f, n, X, x_type, C, nys_rbf{f->gamma});
+  if (what == 1) return nys_stage_a(f, n, X, x_type, C, nys_q{f->nx});
+  if (f->kernel == PMH_NYS_RBF) return nys_stage_a(f, n, X, x_type, C, nys_rbf{f->gamma, f->nx});
   return nys_stage_a(f, n, X, x_type, C, nys_poly{f->gamma, f->coef0, f->degree});
 }
 
-// stage A over all n rows, chunk by chunk (the norms live in the handle's chunk_rows doubles), straight into C (n x m)
-static int nys_block(pmh_nys f, long long n, const void *X, int x_type, double *C, int what)
+// The walk over all n rows, chunk by chunk (the norms live in the handle's chunk_rows doubles).  Z == nullptr: stage A straight into C (n x m).  Else stage A into
+// the handle's workspace and stage B from there into the chunk's rows of Z (n x D of z_type)
+static int nys_walk(pmh_nys f, long long n, const void *X, int x_type, int what, double *C, void *Z, int z_type)
 {
-  const size_t sx = x_type == PMH_F64 ? sizeof(double) : sizeof(float);
+  const size_t sx = x_type == PMH_F64 ? sizeof(double) : sizeof(float), sz = z_type == PMH_F64 ? sizeof(double) : sizeof(float);
   for (long long i0 = 0; i0 < n; i0 += f->chunk_rows) {
     const long long nc = n - i0 < f->chunk_rows ? n - i0 : f->chunk_rows;
-    PMH_CHK(nys_stage_a(f, nc, (const char *)X + (size_t)i0 * f->d * sx, x_type, C + (size_t)i0 * f->m, what));
+    PMH_CHK(nys_stage_a(f, nc, (const char *)X + (size_t)i0 * f->d * sx, x_type, Z ? f->work : C + (size_t)i0 * f->m, what));
+    if (Z) PMH_CHK(rff_identity_apply(f->stage_b, nc, f->work, (char *)Z + (size_t)i0 * f->D * sz, z_type));
   }
   return PMH_SUCCESS;
 }
@@ -240,40 +176,26 @@ extern "C" int pmh_nys_destroy(pmh_nys f)
 extern "C" int pmh_nys_kernel(pmh_nys f, long long n, const void *X_dev, int x_type, double *C_dev)
 {
   PMH_ARG(f);
-  if (n < 0) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_kernel: n = %lld, must not be negative", n);
-  PMH_CHK(rff_check_type("pmh_nys_kernel", "x_type", x_type));
-  if (n == 0) return PMH_SUCCESS;
-  if (!X_dev || !C_dev) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_kernel: X_dev or C_dev is NULL with n = %lld", n);
-  return nys_block(f, n, X_dev, x_type, C_dev, -1);
+  PMH_CHK(rff_check_entry("pmh_nys_kernel", n, x_type, nullptr, X_dev && C_dev, "X_dev or C_dev"));
+  return nys_walk(f, n, X_dev, x_type, -1, C_dev, nullptr, PMH_F64);
 }
 
 extern "C" int pmh_nys_apply(pmh_nys f, long long n, const void *X_dev, int x_type, void *Z_dev, int z_type)
 {
   PMH_ARG(f);
-  if (n < 0) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_apply: n = %lld, must not be negative", n);
-  PMH_CHK(rff_check_type("pmh_nys_apply", "x_type", x_type));
-  PMH_CHK(rff_check_type("pmh_nys_apply", "z_type", z_type));
-  if (n == 0) return PMH_SUCCESS;
-  if (!X_dev || !Z_dev) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_apply: X_dev or Z_dev is NULL with n = %lld", n);
-  const size_t sx = x_type == PMH_F64 ? sizeof(double) : sizeof(float), sz = z_type == PMH_F64 ? sizeof(double) : sizeof(float);
-  for (long long i0 = 0; i0 < n; i0 += f->chunk_rows) {
-    const long long nc = n - i0 < f->chunk_rows ? n - i0 : f->chunk_rows;
-    PMH_CHK(nys_stage_a(f, nc, (const char *)X_dev + (size_t)i0 * f->d * sx, x_type, f->work, -1));
-    PMH_CHK(rff_identity_apply(f->stage_b, nc, f->work, (char *)Z_dev + (size_t)i0 * f->D * sz, z_type));
-  }
-  return PMH_SUCCESS;
+  PMH_CHK(rff_check_entry("pmh_nys_apply", n, x_type, &z_type, X_dev && Z_dev, "X_dev or Z_dev"));
+  return nys_walk(f, n, X_dev, x_type, -1, nullptr, Z_dev, z_type);
 }
 
 extern "C" int pmh_nys_test_args(pmh_nys f, long long n, const void *X_dev, int x_type, int what, double *T_dev)
 {
   PMH_ARG(f);
-  if (n < 0) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_test_args: n = %lld, must not be negative", n);
-  PMH_CHK(rff_check_type("pmh_nys_test_args", "x_type", x_type));
-  if (what != 0 && what != 1) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_test_args: what = %d, must be 0 (t = x . l) or 1 (q = |x - l|^2)", what);
-  if (what == 1 && f->kernel != PMH_NYS_RBF) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_test_args: what = 1 (q = |x - l|^2) on a map whose kernel is not PMH_NYS_RBF");
-  if (n == 0) return PMH_SUCCESS;
-  if (!X_dev || !T_dev) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_test_args: X_dev or T_dev is NULL with n = %lld", n);
-  return nys_block(f, n, X_dev, x_type, T_dev, what);
+  PMH_CHK(rff_check_entry("pmh_nys_test_args", n, x_type, nullptr, X_dev && T_dev, "X_dev or T_dev", [&] {
+    if (what != 0 && what != 1) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_test_args: what = %d, must be 0 (t = x . l) or 1 (q = |x - l|^2)", what);
+    if (what == 1 && f->kernel != PMH_NYS_RBF) return pmh_set_error(PMH_ERR_ARG, "pmh_nys_test_args: what = 1 (q = |x - l|^2) on a map whose kernel is not PMH_NYS_RBF");
+    return (int)PMH_SUCCESS;
+  }));
+  return nys_walk(f, n, X_dev, x_type, what, T_dev, nullptr, PMH_F64);
 }
 
 extern "C" int pmh_nys_get(pmh_nys f, int *d, int *m, int *D, int *kernel, double *gamma, double *coef0, int *degree, double *landmarks_host, double *M_host)

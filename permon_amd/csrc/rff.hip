@@ -2,9 +2,11 @@
 // whose spectral density the columns of Omega were drawn from.  A linear SVM / SVR on Z (n x D row-major, the layout pmh_svm_create takes) is then an
 // approximate kernel machine; nothing in a solver, an operator or a scoring kernel knows about it.  The library draws nothing: Omega, beta and s are the caller's.
 //
-// One kernel here, k_rff<TX, TZ, EPI, NG> (k_rff_dots of rff_score.hip shares its product phase and scores on the features without storing them): TX / TZ the types X is read in and Z is written in (double or float: a float enters the arithmetic as (double)x, a result is
-// rounded once, at the store; all arithmetic is fp64), EPI what happens to an argument t = x . omega_k + beta_k in registers (rff_cos: s cos(t); rff_arg: t
-// itself, for pmh_rff_test_args).  There is no n x D array of arguments.
+// One kernel, k_rff<TX, TZ, EPI, NG> (rff_kernel.h: the kernel block of the Nystroem map, nys.hip, is the same kernel under other functors; k_rff_dots of
+// rff_score.hip shares its product phase and scores on the features without storing them): TX / TZ the types X is read in and Z is written in (double or float: a
+// float enters the arithmetic as (double)x, a result is rounded once, at the store; all arithmetic is fp64), EPI what happens in registers to a product
+// t = x . omega_k, a value of the row and the column's value beta_k, which sits in LDS beside Omega (rff_cos: s cos(t + beta_k); rff_arg: t + beta_k itself, for
+// pmh_rff_test_args; neither takes a value of the row).  There is no n x D array of arguments.
 //
 // The product runs on v_mfma_f64_16x16x4_f64 (A[m = l & 15][k = l >> 4], B[k = l >> 4][n = l & 15], D column l & 15, rows (l >> 4) + 4 r).  A workgroup of
 // RFF_WAVES waves takes RFF_RW = 16 RFF_WAVES rows at a time, a wave 16 of them over a column tile of RFF_CT = 256 columns (16 instruction tiles: 64 accumulator
@@ -29,57 +31,8 @@
 // Bytes: n d size_x read + n D size_z written (+ d D 8 of Omega per workgroup, from L2); flops 2 n d D on the matrix cores + n D cosines on the vector ALU.
 #include "pmh_internal.h"
 
-#include "rff_internal.h"
+#include "rff_kernel.h"
 #include "svm_front.h"
-
-static __device__ __forceinline__ void rff_store4(double *z, const double v[4]) { *(rff_d4 *)z = rff_d4{v[0], v[1], v[2], v[3]}; }
-static __device__ __forceinline__ void rff_store4(float *z, const double v[4]) { *(rff_f4 *)z = rff_f4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
-
-template <class TX, class TZ, class EPI, int NG>
-__global__ __launch_bounds__(RFF_NT) void k_rff(long long n, int d, int D, const TX *__restrict__ X, const double *__restrict__ Om, const double *__restrict__ beta, TZ *__restrict__ Z, EPI epi,
-                                                int xvec, int zvec, int c0base)
-{
-  extern __shared__ double rff_lds[];
-  double   *Ws = rff_lds, *Bs = rff_lds + RFF_KB * RFF_LDW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
-  const int c0 = c0base + blockIdx.y * RFF_CT, Dt = min(64 * NG, D - c0); // the launch's tiles have at most NG groups of 64 columns in use
-  const int nkb = (d + RFF_KB - 1) / RFF_KB;
-  const long long nrb = (n + RFF_RW - 1) / RFF_RW;
-  const int sc = threadIdx.x & (RFF_CT - 1), sp = rff_pos(sc); // staging: this thread's column of the tile and its LDS position
-  if (threadIdx.x < 64 * NG) Bs[sp] = sc < Dt ? beta[c0 + sc] : 0.0;
-  bool staged = false;
-  for (long long rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
-    RFF_PRODUCT_ROW_BLOCK(acc, rb)
-    // the epilogue on the accumulators: group q of 64 columns sits in acc[0 .. 3] on trip q
-    const long long r0 = rb * RFF_RW + wave * 16 + g;
-#pragma nounroll
-    for (int q = 0; q < NG; q++) {
-      const int cc = 64 * q + 4 * c; // the lane's 4 columns of the tile: cc .. cc + 3
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const long long i = r0 + 4 * r;
-        if (i < n && cc < Dt) {
-          double v[4];
-#pragma unroll
-          for (int jm = 0; jm < 4; jm++) {
-            v[jm] = epi(acc[jm][r] + Bs[64 * q + 16 * jm + c]);
-            __builtin_amdgcn_sched_barrier(0); // one cosine at a time: interleaved, their temporaries do not fit beside 128 accumulator registers
-          }
-          TZ *z = Z + (size_t)i * D + c0 + cc;
-          if (zvec) {
-            rff_store4(z, v); // (D % 4 == 0: the 4 columns are inside together)
-          } else {
-#pragma unroll
-            for (int jm = 0; jm < 4; jm++)
-              if (cc + jm < Dt) z[jm] = (TZ)v[jm];
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4 * NG - 4; j++) acc[j] = acc[j + 4];
-    }
-  }
-}
 
 // how many entries are not finite (a count: any order gives the same integer)
 __global__ __launch_bounds__(PMH_BLOCK) void k_rff_bad(long long m, const double *__restrict__ a, int *__restrict__ bad)
@@ -89,32 +42,17 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_rff_bad(long long m, const double
   if (b) atomicAdd(bad, b);
 }
 
-// one launch over ntiles column tiles from column c0base on, each with at most NG groups of 64 columns in use
-template <class TX, class TZ, class EPI, int NG> static int rff_launch_ng(pmh_rff f, long long n, const void *X, void *Z, EPI epi, int c0base, int ntiles)
-{
-  auto *k = k_rff<TX, TZ, EPI, NG>;
-  PMH_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, RFF_LDS_BYTES));
-  const long long nrb  = (n + RFF_RW - 1) / RFF_RW;
-  const int       cus  = f->ctx->num_cus > 0 ? f->ctx->num_cus : 256;
-  const int       xvec = f->d % 4 == 0 && (uintptr_t)X % (4 * sizeof(TX)) == 0, zvec = f->D % 4 == 0 && (uintptr_t)Z % (4 * sizeof(TZ)) == 0;
-  const dim3      grid((unsigned)(nrb < cus ? nrb : cus), (unsigned)ntiles);
-  hipLaunchKernelGGL(k, grid, dim3(RFF_NT), RFF_LDS_BYTES, f->ctx->stream, n, f->d, f->D, (const TX *)X, (const double *)f->omega, (const double *)f->beta, (TZ *)Z, epi, xvec, zvec, c0base);
-  PMH_HIP(hipGetLastError());
-  return PMH_SUCCESS;
-}
-template <class TX, class TZ, class EPI> static int rff_launch(pmh_rff f, long long n, const void *X, void *Z, EPI epi)
-{
-  return rff_tile_launches(f->D, [&](auto ng, int tile0, int ntiles) { return rff_launch_ng<TX, TZ, EPI, decltype(ng)::value>(f, n, X, Z, epi, tile0 * RFF_CT, ntiles); });
-}
-
 int rff_count_not_finite(pmh_ctx ctx, const char *who, const char *what, long long m, const double *a_dev, long long *nbad)
 {
   return sv_count_bad(ctx, who, what, [&](int *cnt) { hipLaunchKernelGGL(k_rff_bad, dim3(pmh_vec_grid((int)(m < (1 << 30) ? m : (1 << 30)))), dim3(PMH_BLOCK), 0, ctx->stream, m, a_dev, cnt); }, nbad);
 }
 
+static rff_operands rff_operands_of(pmh_rff f) { return {f->ctx, f->d, f->D, f->omega, f->beta}; }
+
 int rff_identity_apply(pmh_rff f, long long n, const double *X_dev, void *Z_dev, int z_type)
 {
-  return z_type == PMH_F64 ? rff_launch<double, double>(f, n, X_dev, Z_dev, rff_arg{}) : rff_launch<double, float>(f, n, X_dev, Z_dev, rff_arg{});
+  const rff_operands o = rff_operands_of(f);
+  return z_type == PMH_F64 ? rff_launch<double, double>(o, n, X_dev, Z_dev, rff_arg{}) : rff_launch<double, float>(o, n, X_dev, Z_dev, rff_arg{});
 }
 
 extern "C" int pmh_rff_create(pmh_ctx ctx, int d, int D, const double *omega_dev, const double *beta_dev, double scale, pmh_rff *out)
@@ -157,24 +95,21 @@ extern "C" int pmh_rff_destroy(pmh_rff f)
 extern "C" int pmh_rff_apply(pmh_rff f, long long n, const void *X_dev, int x_type, void *Z_dev, int z_type)
 {
   PMH_ARG(f);
-  if (n < 0) return pmh_set_error(PMH_ERR_ARG, "pmh_rff_apply: n = %lld, must not be negative", n);
-  PMH_CHK(rff_check_type("pmh_rff_apply", "x_type", x_type));
-  PMH_CHK(rff_check_type("pmh_rff_apply", "z_type", z_type));
+  PMH_CHK(rff_check_entry("pmh_rff_apply", n, x_type, &z_type, X_dev && Z_dev, "X_dev or Z_dev"));
   if (n == 0) return PMH_SUCCESS;
-  if (!X_dev || !Z_dev) return pmh_set_error(PMH_ERR_ARG, "pmh_rff_apply: X_dev or Z_dev is NULL with n = %lld", n);
-  const rff_cos epi{f->scale};
-  if (x_type == PMH_F64) return z_type == PMH_F64 ? rff_launch<double, double>(f, n, X_dev, Z_dev, epi) : rff_launch<double, float>(f, n, X_dev, Z_dev, epi);
-  return z_type == PMH_F64 ? rff_launch<float, double>(f, n, X_dev, Z_dev, epi) : rff_launch<float, float>(f, n, X_dev, Z_dev, epi);
+  const rff_operands o = rff_operands_of(f);
+  const rff_cos      epi{f->scale};
+  if (x_type == PMH_F64) return z_type == PMH_F64 ? rff_launch<double, double>(o, n, X_dev, Z_dev, epi) : rff_launch<double, float>(o, n, X_dev, Z_dev, epi);
+  return z_type == PMH_F64 ? rff_launch<float, double>(o, n, X_dev, Z_dev, epi) : rff_launch<float, float>(o, n, X_dev, Z_dev, epi);
 }
 
 extern "C" int pmh_rff_test_args(pmh_rff f, long long n, const void *X_dev, int x_type, double *T_dev)
 {
   PMH_ARG(f);
-  if (n < 0) return pmh_set_error(PMH_ERR_ARG, "pmh_rff_test_args: n = %lld, must not be negative", n);
-  PMH_CHK(rff_check_type("pmh_rff_test_args", "x_type", x_type));
+  PMH_CHK(rff_check_entry("pmh_rff_test_args", n, x_type, nullptr, X_dev && T_dev, "X_dev or T_dev"));
   if (n == 0) return PMH_SUCCESS;
-  if (!X_dev || !T_dev) return pmh_set_error(PMH_ERR_ARG, "pmh_rff_test_args: X_dev or T_dev is NULL with n = %lld", n);
-  return x_type == PMH_F64 ? rff_launch<double, double>(f, n, X_dev, T_dev, rff_arg{}) : rff_launch<float, double>(f, n, X_dev, T_dev, rff_arg{});
+  const rff_operands o = rff_operands_of(f);
+  return x_type == PMH_F64 ? rff_launch<double, double>(o, n, X_dev, T_dev, rff_arg{}) : rff_launch<float, double>(o, n, X_dev, T_dev, rff_arg{});
 }
 
 extern "C" int pmh_rff_get(pmh_rff f, int *d, int *D, double *omega_host, double *beta_host, double *scale)

@@ -1,15 +1,18 @@
-// What the two kernels over the random Fourier feature map share, each written once: k_rff (rff.hip: Z = s cos(X Omega + beta), stored) and k_rff_dots
-// (rff_score.hip: the same features multiplied by a model's weights and summed over the columns, never stored).
+// What the kernels over the product x . omega_k share, each written once: k_rff (rff_kernel.h: Z = epi(X Omega), stored -- the random Fourier features of rff.hip
+// and the kernel block of the Nystroem map, nys.hip) and k_rff_dots (rff_score.hip: the Fourier features multiplied by a model's weights and summed over the
+// columns, never stored).
 //   RFF_*                 the tiling: RFF_WAVES waves of 16 rows, a column tile of RFF_CT columns, k-blocks of RFF_KB rows of Omega in LDS
-//   rff_cos, rff_arg      what happens to an argument t = x . omega_k + beta_k in registers
+//   rff_cos, rff_arg      the epilogue functors of the Fourier features, in the one form every functor of k_rff has (rff_kernel.h): what happens in registers to a
+//                         product t = x . omega_k, a value of the row (none here) and the column's value beta_k
 //   rff_pos               where a column of the tile sits in LDS (Omega's image, beta and the weights of k_rff_dots are permuted alike)
 //   rff_load4             4 consecutive entries of a row of X as doubles, zeros past d
 //   RFF_PRODUCT_ROW_BLOCK the product phase of a row block: the staging of Omega, the k-block loop with X one step ahead and the MFMAs.  The layouts and the order
 //                         of a row's sum are described in rff.hip
 //   rff_tile_launches     which instance is launched over which column tiles
+//   rff_launch_shape      the grid of such a launch and whether X is read in vectors
+//   rff_check_entry       the argument checks every entry over n samples opens with
 //   pmh_rff_s             the map's handle
-// k_nys (nys.hip: the kernel block of the Nystroem map) expands the same product phase under its own epilogues and multiplies by M through rff_identity_apply.
-// Device code and the handle: included by rff.hip, rff_score.hip and (through nys_internal.h) nys.hip only.
+// Device code and the handle: included by rff.hip, rff_score.hip and nys.hip only.
 #pragma once
 #include <type_traits>
 
@@ -32,12 +35,15 @@
 typedef double rff_d4 __attribute__((ext_vector_type(4)));
 typedef float  rff_f4 __attribute__((ext_vector_type(4)));
 
+// t + beta is one rounded sum, then the cosine (the library is built with -ffp-contract=off)
 struct rff_cos {
-  double s;
-  __device__ __forceinline__ double operator()(double t) const { return s * cos(t); }
+  static constexpr bool cols = true, rows = false;
+  double                s;
+  __device__ __forceinline__ double operator()(double t, double, double beta) const { return s * cos(t + beta); }
 };
 struct rff_arg {
-  __device__ __forceinline__ double operator()(double t) const { return t; }
+  static constexpr bool cols = true, rows = false;
+  __device__ __forceinline__ double operator()(double t, double, double beta) const { return t + beta; }
 };
 
 // LDS position of column cc of the column tile: tile j = 4 (cc >> 6) + (cc & 3), lane column (cc & 63) >> 2
@@ -69,7 +75,7 @@ static __device__ __forceinline__ rff_d4 rff_load4(const float *xr, int k, int d
   return v;
 }
 
-// The product phase of one row block rb, the text both kernels expand inside their walk `for (rb = blockIdx.x; rb < nrb; rb += gridDim.x)`: it declares
+// The product phase of one row block rb, the text k_rff and k_rff_dots expand inside their walk `for (rb = blockIdx.x; rb < nrb; rb += gridDim.x)`: it declares
 // acc[4 NG] and leaves in acc[j] the instruction tile j of X[the wave's 16 rows of rb] times Omega[:, c0 .. c0 + Dt) (NG groups of 64 columns).  A macro and not
 // a function: a kernel that reaches this loop through a call, however it is inlined, is scheduled and given registers differently from the kernel that
 // contains it (docs/LAB_NOTEBOOK.md, "SVM fused feature scoring"), and k_rff's instances must stay what they were.  It reads the names of the kernel around it:
@@ -125,6 +131,18 @@ struct pmh_rff_s {
   double *omega, *beta; // device copies: d x D row-major, D
 };
 
+// The grid of a launch over ntiles column tiles -- a workgroup per row block, at most one per CU: it walks its row blocks -- and whether X is read in vectors
+struct rff_shape {
+  dim3 grid;
+  int  xvec;
+};
+template <class TX> static inline rff_shape rff_launch_shape(pmh_ctx ctx, long long n, int d, const void *X, int ntiles)
+{
+  const long long nrb = (n + RFF_RW - 1) / RFF_RW;
+  const int       cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  return {dim3((unsigned)(nrb < cus ? nrb : cus), (unsigned)ntiles), d % 4 == 0 && (uintptr_t)X % (4 * sizeof(TX)) == 0};
+}
+
 // For nys.hip (definitions: rff.hip).  rff_identity_apply: Z (n x f->D of z_type) = X f->omega + f->beta for fp64 X on the device -- the launches of
 // pmh_rff_test_args, k_rff<double, TZ, rff_arg, NG>, with either type of Z.  rff_count_not_finite: *nbad = how many of a[0 .. m) are not finite, as
 // pmh_rff_create counts them (k_rff_bad)
@@ -135,4 +153,21 @@ static inline int rff_check_type(const char *who, const char *what, int t)
 {
   if (t != PMH_F64 && t != PMH_F32) return pmh_set_error(PMH_ERR_ARG, "%s: %s = %d, must be PMH_F64 (0) or PMH_F32 (1)", who, what, t);
   return PMH_SUCCESS;
+}
+
+// What the entry `who` over n samples opens with, in the order it is reported: n < 0, the type codes (z_type: nullptr where the entry has none), what the entry
+// alone checks (more(): PMH_SUCCESS or its error) and, with n > 0, a NULL among its arrays (arrays: none is NULL; names: how the message lists them).  n == 0
+// passes whatever the pointers are: the caller then returns PMH_SUCCESS before it touches them
+template <class MORE> static int rff_check_entry(const char *who, long long n, int x_type, const int *z_type, bool arrays, const char *names, MORE more)
+{
+  if (n < 0) return pmh_set_error(PMH_ERR_ARG, "%s: n = %lld, must not be negative", who, n);
+  PMH_CHK(rff_check_type(who, "x_type", x_type));
+  if (z_type) PMH_CHK(rff_check_type(who, "z_type", *z_type));
+  PMH_CHK(more());
+  if (n > 0 && !arrays) return pmh_set_error(PMH_ERR_ARG, "%s: %s is NULL with n = %lld", who, names, n);
+  return PMH_SUCCESS;
+}
+static inline int rff_check_entry(const char *who, long long n, int x_type, const int *z_type, bool arrays, const char *names)
+{
+  return rff_check_entry(who, n, x_type, z_type, arrays, names, [] { return PMH_SUCCESS; });
 }

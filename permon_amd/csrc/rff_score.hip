@@ -81,7 +81,7 @@ __global__ __launch_bounds__(RFF_NT) void k_rff_dots(long long n, int d, int D, 
 #pragma unroll
           for (int jm = 0; jm < 4; jm++) {
             const int    pos = 64 * q + 16 * jm + c;
-            const double v   = epi(acc[jm][r] + Bs[pos]);
+            const double v   = epi(acc[jm][r], 0.0, Bs[pos]);
 #pragma unroll
             for (int k = 0; k < KC; k++) p[r * KC + k] = fma(v, Vs[k * RFF_CT + pos], p[r * KC + k]);
             __builtin_amdgcn_sched_barrier(0); // one cosine at a time, as in k_rff
@@ -119,11 +119,8 @@ static int rffd_launch_ng(pmh_rff f, long long n, const void *X, const double *W
 {
   auto *k = k_rff_dots<TX, EPI, NG, RFF_KC>;
   PMH_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, RFF_DOTS_LDS_BYTES));
-  const long long nrb  = (n + RFF_RW - 1) / RFF_RW;
-  const int       cus  = f->ctx->num_cus > 0 ? f->ctx->num_cus : 256;
-  const int       xvec = f->d % 4 == 0 && (uintptr_t)X % (4 * sizeof(TX)) == 0;
-  const dim3      grid((unsigned)(nrb < cus ? nrb : cus), (unsigned)ntiles);
-  hipLaunchKernelGGL(k, grid, dim3(RFF_NT), RFF_DOTS_LDS_BYTES, f->ctx->stream, n, f->d, f->D, (const TX *)X, (const double *)f->omega, (const double *)f->beta, W, ldw, kc, out, ldo, tstride, epi, xvec,
+  const rff_shape s = rff_launch_shape<TX>(f->ctx, n, f->d, X, ntiles);
+  hipLaunchKernelGGL(k, s.grid, dim3(RFF_NT), RFF_DOTS_LDS_BYTES, f->ctx->stream, n, f->d, f->D, (const TX *)X, (const double *)f->omega, (const double *)f->beta, W, ldw, kc, out, ldo, tstride, epi, s.xvec,
                      tile0);
   PMH_HIP(hipGetLastError());
   return PMH_SUCCESS;
@@ -156,12 +153,11 @@ template <class TX, class EPI> static int rffd_run(pmh_rff f, long long n, const
 
 static int rffd_check(const char *who, pmh_rff f, long long n, const void *X, int x_type, int K, const double *W, int ldw, const double *dots)
 {
-  if (n < 0) return pmh_set_error(PMH_ERR_ARG, "%s: n = %lld, must not be negative", who, n);
-  PMH_CHK(rff_check_type(who, "x_type", x_type));
-  if (K < 1) return pmh_set_error(PMH_ERR_ARG, "%s: K = %d, must be at least 1", who, K);
-  if (ldw < f->D) return pmh_set_error(PMH_ERR_ARG, "%s: ldw = %d, must be at least D = %d", who, ldw, f->D);
-  if (n > 0 && (!X || !W || !dots)) return pmh_set_error(PMH_ERR_ARG, "%s: X_dev, W_dev or dots_dev is NULL with n = %lld", who, n);
-  return PMH_SUCCESS;
+  return rff_check_entry(who, n, x_type, nullptr, X && W && dots, "X_dev, W_dev or dots_dev", [&] {
+    if (K < 1) return pmh_set_error(PMH_ERR_ARG, "%s: K = %d, must be at least 1", who, K);
+    if (ldw < f->D) return pmh_set_error(PMH_ERR_ARG, "%s: ldw = %d, must be at least D = %d", who, ldw, f->D);
+    return (int)PMH_SUCCESS;
+  });
 }
 
 extern "C" int pmh_rffdots(pmh_rff f, long long n, const void *X_dev, int x_type, int K, const double *W_dev, int ldw, double *dots_dev)

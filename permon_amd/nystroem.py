@@ -27,12 +27,13 @@ import math
 import numpy as np
 
 from ._lib import check
-from .core import DeviceSamples, Vec
+from .core import Vec
+from .featuremap import TYPE_CODES, FeatureMap
 from .mat import is_sparse
-from .rff import TYPE_CODES
 
 KERNELS = ("rbf", "poly")  # PMH_NYS_RBF, PMH_NYS_POLY
 MAX_DEGREE = 16
+# pmh_nys_info: the tiling of the kernel behind kernel_block, then (chunk_rows, workspace_bytes) of transform
 INFO = ("rows_per_workgroup", "rows_per_wave", "column_tile", "k_block", "lds_bytes", "waves_per_workgroup", "chunk_rows", "workspace_bytes")
 
 
@@ -89,7 +90,9 @@ def whitening(landmarks, kernel="rbf", gamma=1.0, coef0=1.0, degree=3, n_compone
     return np.ascontiguousarray(U[:, :keep] / np.sqrt(lam[:keep])), lam[:keep].copy()
 
 
-class NystroemMap:
+class NystroemMap(FeatureMap):
+    ENTRY, INFO = "pmh_nys", INFO
+
     def __init__(self, ctx, landmarks, kernel="rbf", gamma=1.0, coef0=1.0, degree=3, n_components=None, rcond=1e-12):
         M, lam = whitening(landmarks, kernel, gamma, coef0, degree, n_components, rcond)
         self._create(ctx, landmarks, M, kernel, gamma, coef0, degree)
@@ -121,10 +124,6 @@ class NystroemMap:
             ld.free()
             md.free()
 
-    def _need(self):
-        if self.h is None:
-            raise RuntimeError("NystroemMap: the map has been destroyed")
-
     def _get(self, what):
         self._need()
         a = np.empty((self.m, self.d if what == 0 else self.D))
@@ -135,56 +134,16 @@ class NystroemMap:
     landmarks = property(lambda self: self._get(0))
     M = property(lambda self: self._get(1))
 
-    def info(self):
-        """The tiling (pmh_nys_info): dict(rows_per_workgroup, rows_per_wave, column_tile, k_block, lds_bytes, waves_per_workgroup) of the kernel behind
-        kernel_block, and (chunk_rows, workspace_bytes) of transform."""
-        self._need()
-        v = (ct.c_int * 8)()
-        check(self.L.pmh_nys_info(self.h, v))
-        return dict(zip(INFO, (int(x) for x in v)))
-
     def set_chunk_rows(self, rows):
         """The rows of C = k(X, L) that exist at a time in transform: a positive multiple of rows_per_workgroup.  No result depends on it."""
         self._need()
         check(self.L.pmh_nys_set_chunk_rows(self.h, int(rows)))
         return self
 
-    def _source(self, X):
-        """X as (DeviceSamples, made here): an ndarray goes up as float32 if it is float32 and as float64 otherwise."""
-        if is_sparse(X):
-            raise TypeError("NystroemMap.transform: X is a scipy.sparse matrix; sparse samples are not supported by the map (it reads dense rows): pass X.toarray(), or dense blocks of rows")
-        if isinstance(X, DeviceSamples):
-            src, made = X, False
-        else:
-            src, made = DeviceSamples.from_numpy(self.ctx, X), True
-        if src.d != self.d:
-            if made:
-                src.free()
-            raise ValueError("NystroemMap: X must be (n, %d), not (n, %d)" % (self.d, src.d))
-        return src, made
-
-    def _run(self, X, width, dtype, call):
-        """call(src, out) on X as the device sees it and a new DeviceSamples (n, self.<width>) of dtype, which is returned."""
-        src, made = self._source(X)
-        out = None
-        try:
-            self._need()
-            out = DeviceSamples.empty(self.ctx, src.n, getattr(self, width), dtype)
-            check(call(src, out))
-            res, out = out, None
-            return res
-        finally:
-            if out is not None:
-                out.free()
-            if made:
-                src.free()
-
     def transform(self, X, out_dtype=np.float64):
         """Z = k(X, L) M as DeviceSamples (n, D) of out_dtype (float64 or float32: rounded once, at the store), computed and left on the device (pmh_nys_apply).
         X: an (n, d) ndarray -- float32 goes up and is read as float32, anything else as float64 -- or a DeviceSamples; all arithmetic is fp64."""
-        odt = np.dtype(out_dtype)
-        if odt not in TYPE_CODES:
-            raise ValueError("NystroemMap.transform: out_dtype must be numpy.float64 or numpy.float32, not %r" % (out_dtype,))
+        odt = self._out_dtype(out_dtype)
         return self._run(X, "D", odt, lambda src, Z: self.L.pmh_nys_apply(self.h, src.n, src.p, TYPE_CODES[src.dtype], Z.p, TYPE_CODES[odt]))
 
     def kernel_block(self, X):
@@ -192,11 +151,7 @@ class NystroemMap:
         return self._run(X, "m", np.float64, lambda src, Cb: self.L.pmh_nys_kernel(self.h, src.n, src.p, TYPE_CODES[src.dtype], Cb.p))
 
     def _test_args(self, X, what):
-        T = self._run(X, "m", np.float64, lambda src, T: self.L.pmh_nys_test_args(self.h, src.n, src.p, TYPE_CODES[src.dtype], what, T.p))
-        try:
-            return T.numpy()
-        finally:
-            T.free()
+        return self._run_host(X, "m", lambda src, T: self.L.pmh_nys_test_args(self.h, src.n, src.p, TYPE_CODES[src.dtype], what, T.p))
 
     def arguments(self, X):
         """tests: t = X L' as an (n, m) float64 host array, from the SAME kernel as kernel_block with the identity in place of the kernel function."""
@@ -205,8 +160,3 @@ class NystroemMap:
     def distances(self, X):
         """tests, rbf maps: q = max((|x|^2 + |l|^2) - 2 x . l, 0) as an (n, m) float64 host array, what the SAME kernel exponentiates."""
         return self._test_args(X, 1)
-
-    def destroy(self):
-        if self.h is not None:
-            self.L.pmh_nys_destroy(self.h)
-            self.h = None

@@ -25,11 +25,11 @@ import math
 import numpy as np
 
 from ._lib import check
-from .core import DeviceSamples, MappedSamples, Vec
-from .mat import is_sparse
+from .core import MappedSamples, Vec
+from .featuremap import TYPE_CODES, FeatureMap
 
 KERNELS = ("rbf", "laplacian")
-TYPE_CODES = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}  # PMH_F64, PMH_F32
+# pmh_rff_info: the tiling of the map's kernel, then (classes_per_chunk, dots_lds_bytes) of the scoring kernel behind lazy() and dots()
 INFO = ("rows_per_workgroup", "rows_per_wave", "column_tile", "k_block", "lds_bytes", "waves_per_workgroup", "classes_per_chunk", "dots_lds_bytes")
 
 
@@ -49,7 +49,9 @@ def draw(d, D=256, gamma=1.0, kernel="rbf", seed=0):
     return omega, beta, math.sqrt(2.0 / D)
 
 
-class RFFMap:
+class RFFMap(FeatureMap):
+    ENTRY, INFO = "pmh_rff", INFO
+
     def __init__(self, ctx, d, D=256, gamma=1.0, kernel="rbf", seed=0):
         self._create(ctx, *draw(d, D, gamma, kernel, seed))
         self.gamma, self.kernel, self.seed = float(gamma), kernel, seed
@@ -83,10 +85,6 @@ class RFFMap:
             if bd is not None:
                 bd.free()
 
-    def _need(self):
-        if self.h is None:
-            raise RuntimeError("RFFMap: the map has been destroyed")
-
     def _get(self, what):
         self._need()
         omega, beta, scale = np.empty((self.d, self.D)), np.empty(self.D), ct.c_double()
@@ -98,62 +96,15 @@ class RFFMap:
     beta = property(lambda self: self._get(1))
     scale = property(lambda self: self._get(2))
 
-    def info(self):
-        """The kernels' tiling (pmh_rff_info): dict(rows_per_workgroup, rows_per_wave, column_tile, k_block, lds_bytes, waves_per_workgroup) of the map and
-        (classes_per_chunk, dots_lds_bytes) of the scoring kernel behind lazy() and dots()."""
-        self._need()
-        v = (ct.c_int * 8)()
-        check(self.L.pmh_rff_info(self.h, v))
-        return dict(zip(INFO, (int(x) for x in v)))
-
-    def _source(self, X):
-        """X as (DeviceSamples, made here): an ndarray goes up as float32 if it is float32 and as float64 otherwise."""
-        if is_sparse(X):
-            raise TypeError("RFFMap.transform: X is a scipy.sparse matrix; sparse samples are not supported by the map (it reads dense rows): pass X.toarray(), or dense blocks of rows")
-        if isinstance(X, DeviceSamples):
-            src, made = X, False
-        else:
-            src, made = DeviceSamples.from_numpy(self.ctx, X), True
-        if src.d != self.d:
-            if made:
-                src.free()
-            raise ValueError("RFFMap: X must be (n, %d), not (n, %d)" % (self.d, src.d))
-        return src, made
-
     def transform(self, X, out_dtype=np.float64):
         """Z = scale cos(X Omega + beta) as DeviceSamples (n, D) of out_dtype (float64 or float32: rounded once, at the store), computed and left on the device
         (pmh_rff_apply).  X: an (n, d) ndarray -- float32 goes up and is read as float32, anything else as float64 -- or a DeviceSamples; all arithmetic is fp64."""
-        src, made = self._source(X)
-        Z = None
-        try:
-            self._need()
-            odt = np.dtype(out_dtype)
-            if odt not in TYPE_CODES:
-                raise ValueError("RFFMap.transform: out_dtype must be numpy.float64 or numpy.float32, not %r" % (out_dtype,))
-            Z = DeviceSamples.empty(self.ctx, src.n, self.D, odt)
-            check(self.L.pmh_rff_apply(self.h, src.n, src.p, TYPE_CODES[src.dtype], Z.p, TYPE_CODES[odt]))
-            out, Z = Z, None
-            return out
-        finally:
-            if Z is not None:
-                Z.free()
-            if made:
-                src.free()
+        odt = self._out_dtype(out_dtype)
+        return self._run(X, "D", odt, lambda src, Z: self.L.pmh_rff_apply(self.h, src.n, src.p, TYPE_CODES[src.dtype], Z.p, TYPE_CODES[odt]))
 
     def arguments(self, X):
         """tests: T = X Omega + beta as an (n, D) float64 host array, from the SAME kernel with the identity in place of scale cos(.) (pmh_rff_test_args)."""
-        src, made = self._source(X)
-        T = None
-        try:
-            self._need()
-            T = DeviceSamples.empty(self.ctx, src.n, self.D, np.float64)
-            check(self.L.pmh_rff_test_args(self.h, src.n, src.p, TYPE_CODES[src.dtype], T.p))
-            return T.numpy()
-        finally:
-            if T is not None:
-                T.free()
-            if made:
-                src.free()
+        return self._run_host(X, "D", lambda src, T: self.L.pmh_rff_test_args(self.h, src.n, src.p, TYPE_CODES[src.dtype], T.p))
 
     def lazy(self, X):
         """X seen through the map as MappedSamples (n, D), for the scoring calls of SVM, SVMMulticlass and SVR: nothing is computed until a handle scores it, and
@@ -195,8 +146,3 @@ class RFFMap:
     def dot_arguments(self, X, W, ldw=None):
         """tests: arguments(X) @ W.T from the SAME kernel with the identity in place of scale cos(.) (pmh_rffdots_test_args)."""
         return self._dots(self.L.pmh_rffdots_test_args, X, W, ldw)
-
-    def destroy(self):
-        if self.h is not None:
-            self.L.pmh_rff_destroy(self.h)
-            self.h = None
