@@ -1342,6 +1342,27 @@ int pmh_fexplicit_test_load_class(pmh_fexplicit E, int cls, const double *W_host
 int pmh_fexplicit_assemble_window(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it, int begin, int end, int *nbatch,
                                   long long *nsolves, int *complete);
 int pmh_fexplicit_orbit_plan_info(pmh_fexplicit E, int cls, long long info[24]);
+/* ---- test entries of the other four storages (PMH_FX_FULL, _SYM: csrc/fexplicit.hip; PMH_FX_CLASS, _CLASS_SYM: csrc/fshared.hip); no kernel, launch or table of the
+ * apply changes, called by nothing inside the solvers.  unit: the block (FULL / SYM) or the class (CLASS / CLASS_SYM); matrix numbering: Gamma_b resp.
+ * pmh_fexplicit_class_union.
+ * pmh_fexplicit_test_load_rows: the rows [row0, row0 + nrows) of the unit's matrix from HOST memory (nrows rows of n doubles), stored by the launches of the set-up's
+ * own plan -- fx_extract_row (FULL, CLASS), k_fx_extract_tiled with the band's column cap (SYM), k_fxs_extract_sym (CLASS_SYM) or, in a class with symmetries,
+ * k_fxs_extract_symg for every owned row of the orbit of a loaded representative (other rows of that class are ignored) -- from a device vector in block-relative dof
+ * numbering; no K^+ solve.  Rows outside this rank's stripe are skipped as in the assembly.  mode 1 (FULL / SYM, row0 = 0, nrows = n, not striped): the n x n matrix
+ * goes through k_fx_store_sym instead, (S + S') / 2 as the Dirichlet preconditioner stores its blocks.  Once every row of every unit with touched dofs was handed over
+ * the operator counts as assembled (pmh_fexplicit_dense_mult, _mult, _get_block); later loads overwrite.
+ * pmh_fexplicit_test_info (reads state only): info = {0 storage, 1 n, 2 ld, 3 bands (SYM: super bands of 128 rows; CLASS: row groups of 32; CLASS_SYM: mega bands of
+ * 1024 rows), 4 bands this rank owns, 5 .. 9 by storage, 10 offset of the unit in the compressed / multivector numbering, 11 its offset in the dense allocation,
+ * 12 groups of 8 blocks (class storages), 16 + k: band k < 64 is owned}.  FULL: 5 rows per wave, 6 workgroups.  SYM: 5 tile columns per workgroup of k_fx_symv (the
+ * segment length in use), 6 the length the rule fx_pick_seg gives, 7 workgroups of k_fx_symv, 8 of k_fx_symv_fin, 9 segments of the unit's last super band.  CLASS:
+ * 5 row segments of k_fxs_gemm8, 6 / 7 this rank's rows [r0, r1), 8 workgroups.  CLASS_SYM: 5 workgroups of k_fxs_symm8, 6 its work items, 7 the most items a
+ * (group, mega band) of the class is cut into, 9 super bands of 256 rows.
+ * pmh_fexplicit_test_set_seg: PMH_FX_SYM, seg in {2, 4, 8, 16}: rebuilds the launch table of k_fx_symv with that segment length (the buffers are sized for the shortest);
+ * 0 restores the rule.  pmh_fexplicit_test_read_storage: count doubles of the dense allocation from `offset` on, pads included, to HOST memory. */
+int pmh_fexplicit_test_load_rows(pmh_fexplicit E, int unit, int row0, int nrows, const double *rows_host, int mode);
+int pmh_fexplicit_test_info(pmh_fexplicit E, int unit, long long info[80]);
+int pmh_fexplicit_test_set_seg(pmh_fexplicit E, int seg);
+int pmh_fexplicit_test_read_storage(pmh_fexplicit E, long long offset, long long count, double *out_host);
 /* pmh_fexplicit_orbit_adapted_info: what the block products (k_fxa_prod) run for class cls while it applies W_c in the symmetry-adapted basis (pmh_fexplicit_orbit_adapted);
  * called by nothing inside the solvers.  20 entries per irrep i = 0 .. 9 at info + 20 i: {0 d, 1 m, 2 k steps of 8 columns nks, 3 blocks of 16 output rows, 4 blocks of 16
  * columns, 5 .. 8 work items of 1 / 2 / 3 / 4 blocks of columns, 9 .. 12 trips of waves 0 .. 3 on an item of 1 or 2 blocks, 13 .. 16 on an item of 3 or 4, 17 / 18 k steps

@@ -515,6 +515,10 @@ _PROTOS = {
     "pmh_fexplicit_test_load_class": [vp, C.c_int, vp],
     "pmh_fexplicit_assemble_window": [vp, vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, C.c_int, c_int_p, C.POINTER(C.c_longlong), c_int_p],
     "pmh_fexplicit_orbit_plan_info": [vp, C.c_int, vp],
+    "pmh_fexplicit_test_load_rows": [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int],
+    "pmh_fexplicit_test_info": [vp, C.c_int, vp],
+    "pmh_fexplicit_test_set_seg": [vp, C.c_int],
+    "pmh_fexplicit_test_read_storage": [vp, C.c_longlong, C.c_longlong, vp],
     "pmh_fexplicit_orbit_adapted_info": [vp, C.c_int, vp],
     "pmh_fexplicit_orbit_adapted_transform": [vp, C.c_int, C.c_int, vp, vp],
     "pmh_fexplicit_timing_enable": [vp, C.c_int, C.c_int],

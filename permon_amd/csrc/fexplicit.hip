@@ -25,6 +25,7 @@
 #include <chrono>
 #include <cmath>
 #include <map>
+#include <memory>
 
 #include "feti_internal.h"
 #include "fshared.h"
@@ -52,7 +53,7 @@ struct pmh_fexplicit_s {
   int     *d_gamma_rel;    // [sum ngam] gamma relative to its block's first row
   int     *d_ld, *d_gstart, *d_ngam;
   int     *d_wg_block, *d_wg_row0;
-  int      nwg, rw;        // GEMV launch table: workgroup -> (block, first row); rows per wave
+  int      nwg;            // GEMV launch table: workgroup -> (block, first row)
   fx_shared *sh;           // PMH_FX_CLASS: congruent blocks share one full matrix per class (fshared.hip); everything dense lives there
   int      storage;        // PMH_FX_FULL: n x ld row-major; PMH_FX_SYM: lower block-triangle in bands of 32 rows (see k_fx_symv)
   double  *partial, *ydir; // SYM: transposed-product partials [block][super band][npad] and the direct products [block][segment][npad]
@@ -61,11 +62,14 @@ struct pmh_fexplicit_s {
   int     *d_fw_block, *d_fw_col0; // SYM second launch: workgroup -> (block, first of its 128 columns)
   int     *d_own_ptr, *d_own_list; // SYM: per block the ascending list of the super bands this rank owns
   int      nsw, nfw, seg; // seg: tile columns per workgroup of k_fx_symv
+  int      seg_forced;    // tests (pmh_fexplicit_test_set_seg): the segment length instead of fx_pick_seg's; 0: the rule
   double   sym_bytes;      // SYM: algorithmic bytes of one apply
   double  *xh, *yh;        // compressed work vectors
   int      assembled;
   int      stripe_rank, stripe_size; // > 0: this rank applies / assembles only the super bands idx % size == rank (see pmh_fexplicit_set_stripe)
   std::vector<std::vector<char>> owned; // [block][super band]
+  std::vector<std::vector<char>> test_rows; // tests (pmh_fexplicit_test_load_rows): [block][row] the rows handed over so far
+  long long wtot;          // doubles of the dense allocation
   long long n_solves;
   double   assemble_seconds;
   fx_batch_window *win; // the next assembly runs this window of its batches only (pmh_fexplicit_set_window); NULL: all of them
@@ -79,6 +83,7 @@ struct pmh_fexplicit_s {
 // row0 + w*RW ...), every lane streams its 16-byte column pairs of the RW rows (non-temporal: each byte is used once) against the
 // matching pair of x (served by L2: x_b is 0.2 MB), per-lane partial sums in column order, one shuffle tree per row at the end.
 // Fixed summation order => bitwise reproducible; -ffp-contract=off keeps the two products of a pair separate.
+#define FX_RW 4 // rows per wave (2 / 4 / 8 measured in round 2: profiles/r02_symv_tune.txt); one instance, k_fx_gemv<FX_RW>: the benchmark attributes a profile's rows by the prefix "void k_fx_gemv<"
 template <int RW>
 __global__ __launch_bounds__(PMH_BLOCK) void k_fx_gemv(const int *__restrict__ wg_block, const int *__restrict__ wg_row0, const int *__restrict__ gstart, const int *__restrict__ ngam, const int *__restrict__ ldv,
                                                       const long long *__restrict__ woff, const double *__restrict__ Wbase, const double *__restrict__ xh, double *__restrict__ yh)
@@ -160,6 +165,8 @@ __host__ __device__ __forceinline__ long long fx_sym_size(int npad) { return fx_
 // the same 2 MB (except the last segment of a super band), so the grid balances at any block count.
 #define FX_SEG_MIN 2
 #define FX_SEG_MAX 16 // tile columns per workgroup: 16, or fewer when the rank's share is small (see fx_pick_seg)
+// (VAR: read by nothing, 0 is the only instance; the parameter is kept for the kernel's name alone -- the benchmark attributes a profile's rows to this storage by the
+// prefix "void k_fx_symv<", and the recorded profiles carry k_fx_symv<0>)
 template <int VAR>
 __global__ __launch_bounds__(PMH_BLOCK) void k_fx_symv(const int *__restrict__ sw_block, const int *__restrict__ sw_sband, const int *__restrict__ sw_seg, const int *__restrict__ gstart, const int *__restrict__ ldv,
                                                       const long long *__restrict__ woff, const long long *__restrict__ poff, const long long *__restrict__ doff, const double *__restrict__ Wbase,
@@ -188,7 +195,7 @@ __global__ __launch_bounds__(PMH_BLOCK) void k_fx_symv(const int *__restrict__ s
     for (int h = 0; h < FX_RB; h += 16) {
       dbl2 a[16];
 #pragma unroll
-      for (int r = 0; r < 16; r++) a[r] = (VAR == 1) ? *(const dbl2 *)(ap + (h + r) * FX_TC) : __builtin_nontemporal_load((const dbl2 *)(ap + (h + r) * FX_TC));
+      for (int r = 0; r < 16; r++) a[r] = __builtin_nontemporal_load((const dbl2 *)(ap + (h + r) * FX_TC));
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         acc[h + r] = __builtin_fma(a[r].x, xc.x, acc[h + r]); // fused multiply-adds: the dense product has no reference summation order to
@@ -296,23 +303,30 @@ static int fx_upload_owned(pmh_fexplicit E)
   return pmh_memcpy_h2d(E->ctx, E->d_own_list, lst.data(), sizeof(int) * std::max<size_t>(1, lst.size() - 1));
 }
 
-// launch table of k_fx_symv for the super bands this rank owns, largest first; picks the segment length (tile columns per workgroup):
-// 16 unless that leaves fewer than ~6 rounds of workgroups on the chip (256 CUs x 2 resident), then 8, 4 or 2 -- a rank's 1/8 share
-// of configs[2] would otherwise run 2.2 rounds of equal 2 MB workgroups, i.e. a third of the last round idle.  Also the algorithmic
-// bytes of one apply of this rank's share.
+// the segment length of k_fx_symv (tile columns per workgroup) for the super bands this rank owns: 16 unless that leaves fewer than ~6 rounds of
+// workgroups on the chip (256 CUs x 2 resident), then 8, 4 or 2 -- a rank's 1/8 share of configs[2] would otherwise run 2.2 rounds of equal 2 MB
+// workgroups, i.e. a third of the last round idle
+static int fx_pick_seg(pmh_fexplicit E)
+{
+  int seg = FX_SEG_MAX;
+  for (; seg > FX_SEG_MIN; seg /= 2) {
+    long long n = 0;
+    for (int b = 0; b < E->nb; b++)
+      for (int sb = 0; sb < E->ld[b] / FX_TC; sb++)
+        if (E->owned[b][sb]) n += (sb + seg) / seg;
+    if (n >= 6 * 512) break;
+  }
+  return seg;
+}
+
+// launch table of k_fx_symv for the super bands this rank owns, largest first, cut into segments of fx_pick_seg's length (tests: of the length
+// pmh_fexplicit_test_set_seg asked for).  Also the algorithmic bytes of one apply of this rank's share.
 static int fx_build_launch(pmh_fexplicit E)
 {
   const int nb = E->nb;
   int       maxsb = 0;
   for (int b = 0; b < nb; b++) maxsb = std::max(maxsb, E->ld[b] / FX_TC);
-  int seg = FX_SEG_MAX;
-  for (; seg > FX_SEG_MIN; seg /= 2) {
-      long long n = 0;
-      for (int b = 0; b < nb; b++)
-        for (int sb = 0; sb < E->ld[b] / FX_TC; sb++)
-          if (E->owned[b][sb]) n += (sb + seg) / seg;
-      if (n >= 6 * 512) break;
-    }
+  const int seg = E->seg_forced ? E->seg_forced : fx_pick_seg(E);
   E->seg = seg;
   std::vector<int> swb, swk, swj;
   for (int sb = maxsb - 1; sb >= 0; sb--)
@@ -395,7 +409,7 @@ static int fx_create(pmh_gluing B, pmh_blockdiag K, int storage, const int *bloc
   E->ctx = ctx, E->B = B, E->K = K, E->Bhat = nullptr, E->nb = K->nblocks;
   E->d_gamma_rel = nullptr, E->Wbase = nullptr, E->d_woff = nullptr, E->d_ld = E->d_gstart = E->d_ngam = E->d_wg_block = E->d_wg_row0 = nullptr;
   E->xh = E->yh = nullptr, E->assembled = 0, E->n_solves = 0, E->assemble_seconds = 0.0, E->win = nullptr;
-  E->stripe_rank = 0, E->stripe_size = 0, E->sh = nullptr;
+  E->stripe_rank = 0, E->stripe_size = 0, E->sh = nullptr, E->seg_forced = 0, E->seg = 0, E->wtot = 0;
   E->ev_used = E->ev_on = E->ev_seen = 0, E->ev_stride = 1;
   E->storage = storage, E->partial = E->ydir = nullptr, E->d_poff = E->d_doff = nullptr, E->d_sw_block = E->d_sw_band = E->d_sw_seg = E->d_fw_block = E->d_fw_col0 = E->d_own_ptr = E->d_own_list = nullptr, E->nsw = E->nfw = 0, E->sym_bytes = 0.0;
   const int nb = E->nb;
@@ -442,6 +456,7 @@ static int fx_create(pmh_gluing B, pmh_blockdiag K, int storage, const int *bloc
     hipError_t   e     = hipMalloc((void **)&E->Wbase, bytes);
     if (e != hipSuccess) return pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_create: %.2f GB for the explicit blocks: %s", bytes / 1e9, hipGetErrorString(e));
     PMH_HIP(hipMemsetAsync(E->Wbase, 0, bytes, ctx->stream));
+    E->wtot = wtot;
   }
   for (int b = 0; b < nb; b++) E->W[b] = E->Wbase + E->woff[b];
   std::vector<int> grel(E->gamma.size() + 1);
@@ -458,8 +473,7 @@ static int fx_create(pmh_gluing B, pmh_blockdiag K, int storage, const int *bloc
   PMH_CHK(pmh_malloc(ctx, sizeof(int) * nb, (void **)&E->d_ngam));
   PMH_CHK(pmh_memcpy_h2d(ctx, E->d_ngam, E->ngam.data(), sizeof(int) * nb));
   // GEMV launch table
-  E->rw = 4; // rows per wave of the full-matrix GEMV (2 / 4 / 8 measured in round 2: profiles/r02_symv_tune.txt)
-  const int        rows_per_wg = 4 * E->rw;
+  const int        rows_per_wg = 4 * FX_RW;
   std::vector<int> wb, wr;
   for (int b = 0; b < nb; b++)
     for (int r = 0; r < E->ngam[b]; r += rows_per_wg) wb.push_back(b), wr.push_back(r);
@@ -883,17 +897,18 @@ int fx_assemble_run(pmh_ctx ctx, const fx_asm_plan &P, pmh_matinv solver, int ns
 
 // FULL / SYM, one matrix per block: the columns of a class are the union of its blocks' owned Gamma rows; column j is row pos_b(j) of every block of the class
 // that has it.  block_class[b]: class of block b (blocks of one class have identical K_b, so K_b^+ e_j serves all of them).
-static int fx_assemble_blocks(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it)
+// The plan of that set-up (fx_assemble.h), P built for the classes of bc (bc[b]: class of block b): the columns to solve and the store launches of a row.  The
+// assembly and the test entry pmh_fexplicit_test_load_rows both store rows through P.write.
+static int fx_plan_blocks(pmh_fexplicit E, const std::vector<int> &bc, fx_asm_plan &P)
 {
-  pmh_ctx   ctx = E->ctx;
-  const int nb  = E->nb;
-  std::vector<int> sc(nslots), bc(nb);
-  for (int s = 0; s < nslots; s++) sc[s] = slot_class ? slot_class[s] : s / (nslots / nb); // (no classes given: slot s is block s, or column s % R of block s / R)
-  for (int b = 0; b < nb; b++) bc[b] = block_class ? block_class[b] : b;
-  int ncls = 0;
-  for (int b = 0; b < nb; b++) ncls = std::max(ncls, bc[b] + 1);
-  fx_asm_plan                   P(ncls);
-  std::vector<std::vector<int>> cblocks(ncls), pos(nb); // pos: position of a relative dof inside Gamma_b (-1: not in it)
+  pmh_ctx   ctx  = E->ctx;
+  const int nb   = E->nb, ncls = (int)P.nloc.size();
+  struct maps {
+    std::vector<std::vector<int>> cblocks, pos; // pos: position of a relative dof inside Gamma_b (-1: not in it)
+  };
+  auto  M       = std::make_shared<maps>();
+  auto &cblocks = M->cblocks, &pos = M->pos;
+  cblocks.resize(ncls), pos.resize(nb);
   for (int b = 0; b < nb; b++) {
     PMH_ARG(bc[b] >= 0);
     cblocks[bc[b]].push_back(b);
@@ -912,14 +927,14 @@ static int fx_assemble_blocks(pmh_fexplicit E, pmh_matinv solver, int nslots, co
     for (int i = 0; i < nloc; i++)
       if (in[i]) P.todo[c].push_back({i, i});
   }
-  auto rows_of = [&](int c, int col, auto store) {
-    for (int b : cblocks[c]) {
-      const int p = pos[b][col];
+  auto rows_of = [E, M](int c, int col, auto store) {
+    for (int b : M->cblocks[c]) {
+      const int p = M->pos[b][col];
       if (p >= 0 && fx_owns_row(E, b, p)) store(b, p);
     }
   };
   if (E->storage == PMH_FX_SYM) // row p: the columns of its band (0 .. 32(k+1)-1, capped at n_Gamma: the rest is padding)
-    P.write = [&](int c, int col, const double *u) {
+    P.write = [E, ctx, rows_of](int c, int col, const double *u) {
       rows_of(c, col, [&](int b, int p) {
         const int kb = p / FX_RB, n = std::min(E->ngam[b], FX_RB * (kb + 1));
         hipLaunchKernelGGL(k_fx_extract_tiled, dim3(std::max(1, std::min(64, (n + PMH_BLOCK - 1) / PMH_BLOCK))), dim3(PMH_BLOCK), 0, ctx->stream, n, (const int *)(E->d_gamma_rel + E->goff[b]), u,
@@ -927,8 +942,21 @@ static int fx_assemble_blocks(pmh_fexplicit E, pmh_matinv solver, int nslots, co
       });
     };
   else // row p: all n_Gamma columns
-    P.write = [&](int c, int col, const double *u) { rows_of(c, col, [&](int b, int p) { fx_extract_row(ctx, E->ngam[b], E->d_gamma_rel + E->goff[b], u, E->W[b] + (long long)p * E->ld[b]); }); };
-  return fx_assemble_run(ctx, P, solver, nslots, sc.data(), rtol, max_it, &E->n_solves, E->win);
+    P.write = [E, ctx, rows_of](int c, int col, const double *u) { rows_of(c, col, [&](int b, int p) { fx_extract_row(ctx, E->ngam[b], E->d_gamma_rel + E->goff[b], u, E->W[b] + (long long)p * E->ld[b]); }); };
+  return PMH_SUCCESS;
+}
+
+static int fx_assemble_blocks(pmh_fexplicit E, pmh_matinv solver, int nslots, const int *slot_class, const int *block_class, double rtol, int max_it)
+{
+  const int        nb = E->nb;
+  std::vector<int> sc(nslots), bc(nb);
+  for (int s = 0; s < nslots; s++) sc[s] = slot_class ? slot_class[s] : s / (nslots / nb); // (no classes given: slot s is block s, or column s % R of block s / R)
+  for (int b = 0; b < nb; b++) bc[b] = block_class ? block_class[b] : b;
+  int ncls = 0;
+  for (int b = 0; b < nb; b++) ncls = std::max(ncls, bc[b] + 1);
+  fx_asm_plan P(ncls);
+  PMH_CHK(fx_plan_blocks(E, bc, P));
+  return fx_assemble_run(E->ctx, P, solver, nslots, sc.data(), rtol, max_it, &E->n_solves, E->win);
 }
 
 // slot_class[s]: class of the matrix in slot s of the solver; block_class[b]: class of block b of this operator (the class-shared storages: the classes given at
@@ -1033,6 +1061,104 @@ extern "C" int pmh_fexplicit_orbit_adapted_transform(pmh_fexplicit E, int cls, i
   return fxs_orbit_adapted_transform(E->sh, cls, inverse, in, out);
 }
 
+// ---- FULL / SYM / CLASS / CLASS_SYM: test entries (the layout of info: include/permon_hip.h; no kernel, launch or table of the apply changes) -----------------------
+// Rows [row0, row0 + nrows) of unit `unit` (a block; class storages: a class) from a HOST matrix instead of K^+ solves, through the plan's own P.write: every row
+// becomes a device vector in block-relative dof numbering (u[rel[i]] = row[i]), so the store kernels gather as they do from a solution.
+extern "C" int pmh_fexplicit_test_load_rows(pmh_fexplicit E, int unit, int row0, int nrows, const double *rows_host, int mode)
+{
+  PMH_ARG(E && rows_host && unit >= 0 && row0 >= 0 && nrows >= 0 && (mode == 0 || mode == 1));
+  if (E->storage == PMH_FX_CLASS_ORBIT) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_load_rows: the orbit storage loads through pmh_fexplicit_test_load_class");
+  if (E->sh) {
+    if (mode) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_load_rows: mode 1 needs the PMH_FX_FULL or PMH_FX_SYM storage");
+    int all = 0;
+    PMH_CHK(fxs_test_load_rows(E->sh, unit, row0, nrows, rows_host, &all));
+    if (all) E->assembled = 1;
+    return PMH_SUCCESS;
+  }
+  PMH_ARG(unit < E->nb);
+  pmh_ctx   ctx = E->ctx;
+  const int b = unit, n = E->ngam[b], nloc = E->K->rowstart[b + 1] - E->K->rowstart[b];
+  PMH_ARG(row0 + nrows <= n && (!mode || (row0 == 0 && nrows == n)));
+  if (E->test_rows.empty()) E->test_rows.resize(E->nb);
+  E->test_rows[b].resize((size_t)n, 0);
+  if (nrows) {
+    const int           width = mode ? n : nloc;
+    std::vector<double> U((size_t)nrows * width, 0.0);
+    const int          *g = &E->gamma[E->goff[b]];
+    for (int k = 0; k < nrows; k++)
+      for (int i = 0; i < n; i++) U[(size_t)k * width + (mode ? i : g[i] - E->K->rowstart[b])] = rows_host[(size_t)k * n + i];
+    double *dU = nullptr;
+    PMH_CHK(pmh_malloc(ctx, sizeof(double) * U.size(), (void **)&dU));
+    int rc = pmh_memcpy_h2d(ctx, dU, U.data(), sizeof(double) * U.size());
+    if (!rc && mode) rc = pmh_fexplicit_store_symmetrized(E, b, dU, n);
+    if (!rc && !mode) {
+      std::vector<int> bc(E->nb);
+      for (int i = 0; i < E->nb; i++) bc[i] = i; // every block a class of its own: class = block, column = the row's relative dof
+      fx_asm_plan P(E->nb);
+      rc = fx_plan_blocks(E, bc, P);
+      std::vector<char> todo((size_t)std::max(1, nloc), 0);
+      if (!rc)
+        for (const fx_asm_row &t : P.todo[b]) todo[t.id] = 1;
+      for (int k = 0; k < nrows && !rc; k++) {
+        const int rel = g[row0 + k] - E->K->rowstart[b];
+        if (todo[rel]) P.write(b, rel, dU + (size_t)k * nloc); // (rows of another rank's stripe are not in the plan)
+      }
+      if (!rc && hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_test_load_rows: launch failed");
+    }
+    if (!rc) rc = pmh_sync(ctx);
+    pmh_free(ctx, dU);
+    if (rc) return rc;
+    for (int k = 0; k < nrows; k++) E->test_rows[b][row0 + k] = 1;
+  }
+  bool all = true;
+  for (int i = 0; i < E->nb && all; i++)
+    if (E->ngam[i]) all = (int)E->test_rows[i].size() == E->ngam[i] && std::find(E->test_rows[i].begin(), E->test_rows[i].end(), 0) == E->test_rows[i].end();
+  if (all) E->assembled = 1;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_fexplicit_test_info(pmh_fexplicit E, int unit, long long info[80])
+{
+  PMH_ARG(E && info && unit >= 0);
+  memset(info, 0, sizeof(long long) * 80);
+  info[0] = E->storage;
+  if (E->storage == PMH_FX_CLASS_ORBIT) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_info: the orbit storage reports through pmh_fexplicit_orbit_plan_info");
+  if (E->sh) return fxs_test_info(E->sh, unit, info);
+  PMH_ARG(unit < E->nb);
+  const int b = unit, nsb = E->ld[b] / FX_TC;
+  info[1] = E->ngam[b], info[2] = E->ld[b], info[10] = E->gstart[b], info[11] = E->woff[b];
+  if (E->storage == PMH_FX_FULL) {
+    info[5] = FX_RW, info[6] = E->nwg;
+    return PMH_SUCCESS;
+  }
+  info[3] = nsb;
+  for (int sb = 0; sb < nsb; sb++)
+    if (E->owned[b][sb]) {
+      info[4]++;
+      if (sb < 64) info[16 + sb] = 1;
+    }
+  info[5] = E->seg, info[6] = fx_pick_seg(E), info[7] = E->nsw, info[8] = E->nfw, info[9] = nsb ? (nsb - 1) / E->seg + 1 : 0;
+  return PMH_SUCCESS;
+}
+
+extern "C" int pmh_fexplicit_test_set_seg(pmh_fexplicit E, int seg)
+{
+  PMH_ARG(E && (seg == 0 || seg == 2 || seg == 4 || seg == 8 || seg == 16));
+  if (E->sh || E->storage != PMH_FX_SYM) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_set_seg: needs the PMH_FX_SYM storage");
+  PMH_CHK(pmh_sync(E->ctx)); // (no apply in flight reads the table that is rewritten)
+  E->seg_forced = seg;
+  return fx_build_launch(E); // partial / ydir and the table's arrays are sized for FX_SEG_MIN
+}
+
+extern "C" int pmh_fexplicit_test_read_storage(pmh_fexplicit E, long long offset, long long count, double *out_host)
+{
+  PMH_ARG(E && out_host && offset >= 0 && count >= 0);
+  if (E->storage == PMH_FX_CLASS_ORBIT) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_read_storage: not for the orbit storage");
+  if (E->sh) return fxs_test_read_storage(E->sh, offset, count, out_host);
+  PMH_ARG(offset + count <= E->wtot);
+  return count ? pmh_memcpy_d2h(E->ctx, out_host, E->Wbase + offset, sizeof(double) * (size_t)count) : PMH_SUCCESS;
+}
+
 int pmh_fexplicit_set_window(pmh_fexplicit_s *E, fx_batch_window *w)
 {
   PMH_ARG(E);
@@ -1131,9 +1257,10 @@ static int fx_gemv(pmh_fexplicit E)
       timed = true;
       PMH_HIP(hipEventRecord(E->ev[2 * E->ev_used], st));
     }
-#define SYMV_LAUNCH(V) hipLaunchKernelGGL(k_fx_symv<V>, dim3(E->nsw), dim3(PMH_BLOCK), 0, st, (const int *)E->d_sw_block, (const int *)E->d_sw_band, (const int *)E->d_sw_seg, (const int *)E->d_gstart, (const int *)E->d_ld, (const long long *)E->d_woff, (const long long *)E->d_poff, (const long long *)E->d_doff, (const double *)E->Wbase, (const double *)E->xh, E->ydir, E->partial, E->seg)
-    SYMV_LAUNCH(0);
-#undef SYMV_LAUNCH
+    // a stripe rank that owns no super band has nothing to stream: k_fx_symv_fin alone then sums its (zero) direct products and no partials into exact zeros
+    if (E->nsw)
+      hipLaunchKernelGGL(k_fx_symv<0>, dim3(E->nsw), dim3(PMH_BLOCK), 0, st, (const int *)E->d_sw_block, (const int *)E->d_sw_band, (const int *)E->d_sw_seg, (const int *)E->d_gstart, (const int *)E->d_ld,
+                         (const long long *)E->d_woff, (const long long *)E->d_poff, (const long long *)E->d_doff, (const double *)E->Wbase, (const double *)E->xh, E->ydir, E->partial, E->seg);
     if (timed) PMH_HIP(hipEventRecord(E->ev_mid[E->ev_used], st));
     if (E->nfw)
       hipLaunchKernelGGL(k_fx_symv_fin, dim3(E->nfw), dim3(PMH_BLOCK), 0, st, (const int *)E->d_fw_block, (const int *)E->d_fw_col0, (const int *)E->d_gstart, (const int *)E->d_ld, (const long long *)E->d_poff,
@@ -1151,11 +1278,8 @@ static int fx_gemv(pmh_fexplicit E)
     timed = true;
     PMH_HIP(hipEventRecord(E->ev[2 * E->ev_used], st));
   }
-#define FX_LAUNCH(RW) hipLaunchKernelGGL(k_fx_gemv<RW>, dim3(E->nwg), dim3(PMH_BLOCK), 0, st, (const int *)E->d_wg_block, (const int *)E->d_wg_row0, (const int *)E->d_gstart, (const int *)E->d_ngam, (const int *)E->d_ld, (const long long *)E->d_woff, (const double *)E->Wbase, (const double *)E->xh, E->yh)
-  if (E->rw == 8) FX_LAUNCH(8);
-  else if (E->rw == 2) FX_LAUNCH(2);
-  else FX_LAUNCH(4);
-#undef FX_LAUNCH
+  hipLaunchKernelGGL(k_fx_gemv<FX_RW>, dim3(E->nwg), dim3(PMH_BLOCK), 0, st, (const int *)E->d_wg_block, (const int *)E->d_wg_row0, (const int *)E->d_gstart, (const int *)E->d_ngam, (const int *)E->d_ld,
+                     (const long long *)E->d_woff, (const double *)E->Wbase, (const double *)E->xh, E->yh);
   if (timed) {
     PMH_HIP(hipEventRecord(E->ev[2 * E->ev_used + 1], st));
     E->ev_used++;

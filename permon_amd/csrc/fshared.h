@@ -25,6 +25,10 @@ double   *fxs_Y(fx_shared *S);
 int       fxs_fill_pattern(fx_shared *S, int byte);
 int       fxs_get_block(fx_shared *S, int b, int n, const int *gamma, double *out_host);
 int       fxs_test_load_class(fx_shared *S, int c, const double *W_host, int *all_loaded); // orbit storage, tests: the representatives' rows of class c from a host matrix
+// PMH_FX_CLASS / PMH_FX_CLASS_SYM, tests: rows of class c from a host matrix through the plan's store launches; what the launch tables hold; the raw dense allocation
+int       fxs_test_load_rows(fx_shared *S, int c, int row0, int nrows, const double *rows_host, int *all_loaded);
+int       fxs_test_info(fx_shared *S, int c, long long info[80]);
+int       fxs_test_read_storage(fx_shared *S, long long offset, long long count, double *out_host);
 int       fxs_orbit_plan_info(fx_shared *S, int c, long long info[24]);
 int       fxs_orbit_adapted_info(fx_shared *S, int c, long long info[200]);
 int       fxs_orbit_adapted_transform(fx_shared *S, int c, int inverse, const double *in, double *out); // tests: one transform of the symmetry-adapted form alone

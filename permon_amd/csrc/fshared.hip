@@ -81,6 +81,7 @@ static int fxs_build_launch(fx_shared *S)
       fxs_class &C     = S->C[c];
       double     tiles = 0.0, parts = 0.0;
       std::vector<int> ownm, own_first((size_t)C.nmb + 1, 0);
+      C.nseg_max = 0;
       for (int m = 0; m < C.nmb; m++) {
         own_first[m] = (int)ownm.size();
         if (C.own[FXM_MB * m]) ownm.push_back(m);
@@ -97,7 +98,7 @@ static int fxs_build_launch(fx_shared *S)
         for (int sb = FXM_MB * m; sb < sb1; sb++) tiles += (double)(sb + 1) * FXM_RT * FXM_RT * 2048.0;
         int ns = 0;
         for (int g = 0; g < C.ngroups; g++) ns = std::max(ns, nseg_of[c][(size_t)g * C.nmb + m]);
-        nsegmax = std::max(nsegmax, ns);
+        nsegmax = std::max(nsegmax, ns), C.nseg_max = std::max(C.nseg_max, ns);
         // direct sums per item + transposed sums per column
         parts += (double)ns * (sb1 - FXM_MB * m) * FXM_RS * FXS_S * 8.0 + (double)sb1 * FXM_RS * FXS_S * 8.0;
       }
@@ -110,7 +111,7 @@ static int fxs_build_launch(fx_shared *S)
       if (!C.d_ptoff) PMH_CHK(pmh_malloc(S->ctx, sizeof(long long) * ptoff_of.size(), (void **)&C.d_ptoff));
       PMH_CHK(pmh_memcpy_h2d(S->ctx, C.d_ptoff, ptoff_of.data(), sizeof(long long) * ptoff_of.size()));
     }
-    S->nwg = items.empty() ? 0 : nwg, S->nseg = nsegmax;
+    S->nwg = items.empty() ? 0 : nwg, S->nseg = nsegmax, S->nitems = (int)(items.size() / 8);
     items.insert(items.end(), {0, 0, 0, 0, 0, 0, 0, 0});
     iteml.insert(iteml.end(), {0, 0});
     if (S->d_wg) pmh_free(S->ctx, S->d_wg);
@@ -1052,7 +1053,8 @@ static int fxs_gemm(fx_shared *S)
     hipLaunchKernelGGL(k_fxs_symm8, dim3(S->nwg), dim3(FXM_THREADS), 0, st, (const int *)S->d_wg, (const int *)S->d_items, (const long long *)S->d_wgl, (const int *)S->d_ld, (const long long *)S->d_xoff,
                        (const double *)S->Wbase, (const double *)S->X, S->part, stride, S->pt);
     for (auto &C : S->C)
-      hipLaunchKernelGGL(k_fxs_symfin, dim3((unsigned)(((long long)C.ld * FXS_S / 2 * 8 + PMH_BLOCK - 1) / PMH_BLOCK), C.ngroups), dim3(PMH_BLOCK), 0, st, C.ld, C.nmb, C.nown, (const int *)C.d_nseg, (const int *)C.d_ownfirst,
+      if (C.ld) // (a class B does not touch has no entry of Y: a grid of 0 workgroups is not a launch)
+        hipLaunchKernelGGL(k_fxs_symfin, dim3((unsigned)(((long long)C.ld * FXS_S / 2 * 8 + PMH_BLOCK - 1) / PMH_BLOCK), C.ngroups), dim3(PMH_BLOCK), 0, st, C.ld, C.nmb, C.nown, (const int *)C.d_nseg, (const int *)C.d_ownfirst,
                          (const long long *)C.d_ptoff, C.xoff, stride, (const double *)S->part, (const double *)S->pt, S->Y);
   } else {
   hipLaunchKernelGGL(k_fxs_gemm8, dim3(S->nwg), dim3(PMH_BLOCK), 0, st, (const int *)S->d_wg, (const int *)S->d_ld, (const long long *)S->d_woff, (const long long *)S->d_xoff, (const double *)S->Wbase,
@@ -1195,6 +1197,75 @@ int fxs_test_load_class(fx_shared *S, int c, const double *W, int *all_loaded)
   for (const fxs_class &D : S->C)
     if (D.nc && !D.test_loaded) *all_loaded = 0;
   return PMH_SUCCESS;
+}
+
+// ---- PMH_FX_CLASS / PMH_FX_CLASS_SYM: test entries (pmh_fexplicit_test_load_rows / _test_info / _test_read_storage) -------------------------------------------
+// Rows [row0, row0 + nrows) of W_c from a HOST matrix (rows of n_c doubles in the numbering of fxs_class_union), stored by the write function of the plan the assembly
+// makes (fxs_plan_full / fxs_plan_tiles): each row goes to the device in block-relative dof numbering, so the store kernels gather through d_urel as they do from a
+// K^+ solution.  Rows outside the plan (another rank's stripe; with symmetries: rows that are no representative) are skipped, as the assembly never solves for them.
+int fxs_test_load_rows(fx_shared *S, int c, int row0, int nrows, const double *rows_host, int *all_loaded)
+{
+  PMH_ARG(S && rows_host && all_loaded && c >= 0 && c < S->ncls && row0 >= 0 && nrows >= 0);
+  if (S->sym == 2) return pmh_set_error(PMH_ERR_ARG, "pmh_fexplicit_test_load_rows: the orbit storage loads through pmh_fexplicit_test_load_class");
+  pmh_ctx    ctx = S->ctx;
+  fxs_class &C   = S->C[c];
+  PMH_ARG(row0 + nrows <= C.nc);
+  C.test_rows.resize((size_t)C.nc, 0);
+  if (nrows) {
+    fx_asm_plan P(S->ncls);
+    if (S->sym) fxs_plan_tiles(S, P);
+    else fxs_plan_full(S, P);
+    std::vector<char> todo((size_t)C.nc, 0);
+    for (const fx_asm_row &t : P.todo[c]) todo[t.id] = 1;
+    std::vector<double> U((size_t)nrows * C.nloc, 0.0);
+    for (int k = 0; k < nrows; k++)
+      for (int i = 0; i < C.nc; i++) U[(size_t)k * C.nloc + C.urel[i]] = rows_host[(size_t)k * C.nc + i];
+    double *dU = nullptr;
+    PMH_CHK(pmh_malloc(ctx, sizeof(double) * U.size(), (void **)&dU));
+    int rc = pmh_memcpy_h2d(ctx, dU, U.data(), sizeof(double) * U.size());
+    for (int k = 0; k < nrows && !rc; k++)
+      if (todo[row0 + k]) P.write(c, row0 + k, dU + (size_t)k * C.nloc);
+    if (!rc && hipGetLastError() != hipSuccess) rc = pmh_set_error(PMH_ERR_HIP, "pmh_fexplicit_test_load_rows: launch failed");
+    if (!rc) rc = pmh_sync(ctx);
+    pmh_free(ctx, dU);
+    if (rc) return rc;
+    for (int k = 0; k < nrows; k++) C.test_rows[row0 + k] = 1;
+  }
+  *all_loaded = 1;
+  for (const fxs_class &D : S->C)
+    if (D.nc && ((int)D.test_rows.size() != D.nc || std::find(D.test_rows.begin(), D.test_rows.end(), 0) != D.test_rows.end())) *all_loaded = 0;
+  return PMH_SUCCESS;
+}
+
+// what the launch tables of the two streaming class storages hold for class c (the layout of info: include/permon_hip.h); reads state only
+int fxs_test_info(fx_shared *S, int c, long long info[80])
+{
+  PMH_ARG(S && info && c >= 0 && c < S->ncls);
+  const fxs_class &C = S->C[c];
+  info[1] = C.nc, info[2] = C.ld, info[10] = C.xoff, info[11] = C.woff, info[12] = C.ngroups;
+  if (!S->sym) { // bands: the row groups of 32 the stripes are dealt in
+    info[3] = C.ld / 32;
+    for (int k = C.r0 / 32; k < C.r1 / 32; k++) {
+      info[4]++;
+      if (k < 64) info[16 + k] = 1;
+    }
+    info[5] = S->nseg, info[6] = C.r0, info[7] = C.r1, info[8] = S->nwg;
+    return PMH_SUCCESS;
+  }
+  info[3] = C.nmb, info[9] = C.nsb;
+  for (int m = 0; m < C.nmb; m++)
+    if (C.own[FXM_MB * m]) {
+      info[4]++;
+      if (m < 64) info[16 + m] = 1;
+    }
+  info[5] = S->nwg, info[6] = S->nitems, info[7] = C.nseg_max;
+  return PMH_SUCCESS;
+}
+
+int fxs_test_read_storage(fx_shared *S, long long offset, long long count, double *out_host)
+{
+  PMH_ARG(S && out_host && S->sym != 2 && offset >= 0 && count >= 0 && offset + count <= S->wtot);
+  return count ? pmh_memcpy_d2h(S->ctx, out_host, S->Wbase + offset, sizeof(double) * (size_t)count) : PMH_SUCCESS;
 }
 
 // what fxo_prepare decided for class c and what fxo_gemm launches for it (the layout of info: include/permon_hip.h)

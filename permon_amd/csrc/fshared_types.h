@@ -104,6 +104,9 @@ struct fxs_class {
   // what fxo_prepare decided, for pmh_fexplicit_orbit_plan_info (tests): units, units with chunks on this rank, the largest split count of a unit, workgroups with
   // two or more items; test_loaded: the representatives' rows came from pmh_fexplicit_test_load_class
   int              plan_units = 0, plan_units_work = 0, plan_smax = 0, plan_wg2 = 0, test_loaded = 0;
+  // PMH_FX_CLASS / PMH_FX_CLASS_SYM: the rows pmh_fexplicit_test_load_rows handed over so far; CLASS_SYM: the most items any (group, mega band) of the class was cut into
+  std::vector<char> test_rows;
+  int               nseg_max = 0;
 };
 
 struct fx_shared {
@@ -123,7 +126,7 @@ struct fx_shared {
   double                *Wbase = nullptr, *X = nullptr, *Y = nullptr;
   long long              nX = 0, wtot = 0;
   int                   *d_wg = nullptr; // launch table: (class, group, first column, segment, first row, one-past-last row) per workgroup
-  int                    nwg = 0, nseg = 0;
+  int                    nwg = 0, nseg = 0, nitems = 0; // nitems: work items of k_fxs_symm8
   double                *part = nullptr; // [nseg][nX] segment sums of k_fxs_gemm8
   long long              part_cap = 0;
   int                   *d_ld = nullptr;

@@ -470,6 +470,37 @@ class MatExplicitDual:
         check(self.ctx.L.pmh_fexplicit_orbit_plan_info(self.h, int(cls), info.ctypes.data_as(C.c_void_p)))
         return dict(zip(self.ORBIT_PLAN_FIELDS, (int(v) for v in info)))
 
+    def test_load_rows(self, unit, row0, rows, mode=0):
+        """"full" / "sym" / "class" / "class_sym" test entry (pmh_fexplicit_test_load_rows): the rows row0 .. of the matrix of block (class storages: class) `unit` from the
+        host array `rows` (k x n), stored by the set-up's own store launches instead of K^+ solves.  mode 1 ("full" / "sym"): the whole n x n matrix through
+        k_fx_store_sym, (S + S') / 2."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        check(self.ctx.L.pmh_fexplicit_test_load_rows(self.h, int(unit), int(row0), int(rows.shape[0]), rows.ctypes.data_as(C.c_void_p), int(mode)))
+
+    TEST_INFO_FIELDS = {0: ("storage", "n", "ld", "bands", "owned_bands", "rw", "workgroups"),
+                        1: ("storage", "n", "ld", "bands", "owned_bands", "seg", "seg_rule", "nsw", "nfw", "last_segments"),
+                        2: ("storage", "n", "ld", "bands", "owned_bands", "nseg", "r0", "r1", "workgroups"),
+                        3: ("storage", "n", "ld", "bands", "owned_bands", "nwg", "items", "max_items", "", "super_bands")}
+
+    def test_info(self, unit):
+        """What the launch tables hold for block (class) `unit` (pmh_fexplicit_test_info) as a dict: the fields of TEST_INFO_FIELDS for the storage, offset (of the unit in
+        the compressed / multivector numbering), woff (in the dense allocation), groups, owned (the owned bands, ascending)."""
+        info = np.zeros(80, dtype=np.int64)
+        check(self.ctx.L.pmh_fexplicit_test_info(self.h, int(unit), info.ctypes.data_as(C.c_void_p)))
+        out = {k: int(v) for k, v in zip(self.TEST_INFO_FIELDS[int(info[0])], info) if k}
+        out.update(offset=int(info[10]), woff=int(info[11]), groups=int(info[12]), owned=[k for k in range(64) if info[16 + k]])
+        return out
+
+    def test_set_seg(self, seg):
+        """"sym": the launch table of k_fx_symv rebuilt with `seg` tile columns per workgroup (2, 4, 8, 16; 0: the rule again)."""
+        check(self.ctx.L.pmh_fexplicit_test_set_seg(self.h, int(seg)))
+
+    def test_read_storage(self, offset, count):
+        """`count` raw doubles of the dense allocation from `offset` on (pads included)."""
+        out = np.zeros(max(int(count), 1))
+        check(self.ctx.L.pmh_fexplicit_test_read_storage(self.h, int(offset), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out[:int(count)]
+
     def orbit_adapted_info(self, cls=0):
         """"class_orbit", a class on the symmetry-adapted form: what the block products (k_fxa_prod) run (pmh_fexplicit_orbit_adapted_info), one dict per irrep: d, m,
         nks (k steps of 8 columns), nob / nbt (blocks of 16 output rows / of 16 columns), items (work items of 1, 2, 3, 4 blocks of columns), trips (of waves 0 .. 3
